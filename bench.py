@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: stereo frames/s of ORB extract + match + triangulate
-at 752x480, 2000 ORB/frame (configs[1]), plus local-BA LM iterations/s (configs[2]) as extra keys.
+at 752x480, 2000 ORB/frame (configs[1]); with --full, local-BA LM iterations/s (configs[2]) and the other legs as extra keys.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (orbx_process_stereo_batch_device) over one batch of B synthetic
 stereo pairs that are already resident in HBM.  For N > 1 the driver launches one rank per GPU
 (torch.distributed.run); frames shard across ranks with no data-path collective, so
 per-GPU work is fixed ("weak" scaling) and value = all ranks' frames / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the `roofline` and `cpu_baseline` objects described in DESIGN.md.
+A plain run sets up, warms up W steps, times K steps with no per-kernel events and prints ONE JSON line on rank 0: `value`
+(stereo frames/s over the K steps), `ms_per_step` (wall milliseconds of one timed step), metric, unit, higher_is_better, dtype and
+the workload's config.  --full adds what DESIGN.md §5 describes: the `roofline` and `cpu_baseline` objects, the batch sweep and the
+other legs, local BA; its `value` is timed with HIP events around the dominant kernel's launches, and `value_unprofiled` repeats the
+K steps without them.  --dump-outputs DIR writes the last timed step's results as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -173,11 +177,15 @@ def main():
     ap.add_argument("--steps", type=int, default=60)      # 60 x 2.3 ms: a timed region of ~0.14 s (20 steps = 45 ms was thin)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=512, help="stereo pairs per step per GPU (256 until round 4; round 5: 512 — same kernels, the launches' ramps and tails "
-                                                          "over twice the work: +3.7 %, profiles/r05_batch_sweep.txt; the 256-pair figure stays in batch_sweep)")
+                                                          "over twice the work: +3.7 %%, profiles/r05_batch_sweep.txt; the 256-pair figure stays in batch_sweep)")
     ap.add_argument("--n-batches", type=int, default=3)
     ap.add_argument("--features", type=int, default=2000)
     ap.add_argument("--width", type=int, default=752)
     ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline: roofline and per-kernel table, value_unprofiled, batch sweep / "
+                                                        "PCIe-inclusive / latency / config0 legs, local BA, the PNG-file leg, cpu_baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (float32 / float64 .npy, "
+                                                                         "a fixed sample of pairs, at most 48 MiB) to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ba", action="store_true")
     ap.add_argument("--no-files", action="store_true", help="skip the EuRoC-directory (PNG decode inclusive) leg")
@@ -237,50 +245,136 @@ def main():
         if world > 1:
             dist.barrier()
 
+    def timed_steps():
+        """The K timed steps, bracketed by barrier + synchronise: wall seconds on this rank."""
+        barrier(); torch.cuda.synchronize(); h.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            h.process_stereo_batch_device(batches[i % len(batches)], out)
+        h.synchronize(); torch.cuda.synchronize(); barrier()
+        return time.perf_counter() - t0
+
     for i in range(args.warmup):
         h.process_stereo_batch_device(batches[i % len(batches)], out)
     h.check_status()
-    # Which kernel dominates, and the per-kernel table: an UNTIMED pass with HIP events around every launch (on the library's stream).
-    # The timed region then brackets the dominant kernel's launches only — the roofline block needs that kernel's durations over the
-    # timed region, and two event records per launch of every kernel cost the step about 1.5 % (value_unprofiled below is the same
-    # K steps with no events at all).
-    n_pre = max(3, min(args.steps, 10))
-    h.set_profiling(True)
-    h.synchronize()
-    t_pre = time.perf_counter()
-    for i in range(n_pre):
-        h.process_stereo_batch_device(batches[i % len(batches)], out)
-    h.synchronize()
-    elapsed_pre = time.perf_counter() - t_pre            # rounds 1-3 measured `value` this way (events around every launch)
-    acc_pre = {k: [v[0], v[1]] for k, v in h.kernel_times().items()}
-    h.set_profiling(False)
-    dom_pre = max(acc_pre.items(), key=lambda kv: kv[1][0])[0]
-    h.set_profiling(True, only=dom_pre)
-    barrier(); torch.cuda.synchronize(); h.synchronize()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        h.process_stereo_batch_device(batches[i % len(batches)], out)
-    h.synchronize(); torch.cuda.synchronize(); barrier()
-    elapsed = time.perf_counter() - t0
-    acc_dom = {k: [v[0], v[1]] for k, v in h.kernel_times().items()}   # the dominant kernel's durations over the timed region
-    h.set_profiling(False)
-    h.check_status()
-    # per-kernel milliseconds scaled to the timed region's K steps: the dominant kernel from the timed region itself, the others from the untimed pass
-    acc = {k: [v[0] * args.steps / n_pre, int(round(v[1] * args.steps / n_pre))] for k, v in acc_pre.items()}
-    acc.update(acc_dom)
-    # the same K steps once more without the per-kernel HIP events: reported as value_unprofiled, never as value
-    barrier(); torch.cuda.synchronize(); h.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        h.process_stereo_batch_device(batches[i % len(batches)], out)
-    h.synchronize(); torch.cuda.synchronize(); barrier()
-    elapsed_np = time.perf_counter() - t1
+    if args.full:
+        # Which kernel dominates, and the per-kernel table: an UNTIMED pass with HIP events around every launch (on the library's stream).
+        # The timed region then brackets the dominant kernel's launches only — the roofline block needs that kernel's durations over the
+        # timed region, and two event records per launch of every kernel cost the step about 1.5 % (value_unprofiled below is the same
+        # K steps with no events at all).
+        n_pre = max(3, min(args.steps, 10))
+        h.set_profiling(True)
+        h.synchronize()
+        t_pre = time.perf_counter()
+        for i in range(n_pre):
+            h.process_stereo_batch_device(batches[i % len(batches)], out)
+        h.synchronize()
+        elapsed_pre = time.perf_counter() - t_pre            # rounds 1-3 measured `value` this way (events around every launch)
+        acc_pre = {k: [v[0], v[1]] for k, v in h.kernel_times().items()}
+        h.set_profiling(False)
+        dom_pre = max(acc_pre.items(), key=lambda kv: kv[1][0])[0]
+        h.set_profiling(True, only=dom_pre)
+        elapsed = timed_steps()
+        acc_dom = {k: [v[0], v[1]] for k, v in h.kernel_times().items()}   # the dominant kernel's durations over the timed region
+        h.set_profiling(False)
+        h.check_status()
+        # per-kernel milliseconds scaled to the timed region's K steps: the dominant kernel from the timed region itself, the others from the untimed pass
+        acc = {k: [v[0] * args.steps / n_pre, int(round(v[1] * args.steps / n_pre))] for k, v in acc_pre.items()}
+        acc.update(acc_dom)
+        # the same K steps once more without the per-kernel HIP events: reported as value_unprofiled, never as value
+        elapsed_np = timed_steps()
+    else:
+        # a plain run: the headline alone, the K steps with no per-kernel events (the figure --full reports as value_unprofiled)
+        elapsed = timed_steps()
+        h.check_status()
     if world > 1:
         elapsed = P.dist.allreduce_max_seconds(elapsed, dev)
-        elapsed_np = P.dist.allreduce_max_seconds(elapsed_np, dev)
+        if args.full:
+            elapsed_np = P.dist.allreduce_max_seconds(elapsed_np, dev)
     n_matches = float(out["nmatches"].float().mean().item())
     n_kp = float(out["nkp"].float().mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
+    frames = args.batch * args.steps * world
+    value = frames / elapsed
+    res = dict(metric="stereo frames/sec ORB extract+match @%dx%d" % (W, H), value=round(value, 2), unit="stereo frames/s",
+               n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4),
+               higher_is_better=True, scaling="weak", vs_baseline=None, dtype="u8", data="synthetic",
+               config=dict(workload="Synthetic %dx%d stereo, %d ORB/frame, extract+match+triangulate (BASELINE configs[%d])"
+                                    % (W, H, args.features, 1 if (W, H, args.features) == (752, 480, 2000) else 4),
+                           image=[W, H], n_features=args.features, batch_pairs_per_gpu=args.batch,
+                           distinct_batches=args.n_batches, unique_pairs=(min(32, args.batch * args.n_batches) if args.small_gen else args.batch * args.n_batches),
+                           parallelism="frames sharded, %d rank(s), no collective%s" % (world, " (REHEARSAL: ranks share GPUs, gloo)" if rehearse else ""),
+                           mean_keypoints_per_image=round(n_kp, 1), mean_matches_per_frame=round(n_matches, 1)))
+    if args.full:
+        res.update(roofline=roofline_block(args, acc, dom_pre, n_pre, elapsed, world, W, H),
+                   value_unprofiled=round(args.batch * args.steps * world / elapsed_np, 2),
+                   value_all_kernel_events=dict(value=round(args.batch * n_pre / elapsed_pre, 2), steps=n_pre,
+                                                note="rank 0's untimed pass with HIP events around EVERY launch: how `value` was measured until round 3 "
+                                                     "(since round 4 the timed region brackets the dominant kernel only)"))
+        if rank == 0 and world == 1 and not args.no_extras:
+            try:
+                res.update(bench_extras(P, h, torch, batches, out, args, W, H))
+            except Exception as e:
+                res["extras_error"] = repr(e)
+        if not args.no_ba:
+            try:
+                res["local_ba"] = bench_ba(P, h, cam, rank, world, dev)
+            except Exception as e:  # BA leg must not hide the headline number
+                res["local_ba"] = dict(error=repr(e))
+            if world > 1 and isinstance(res["local_ba"], dict) and res["local_ba"].get("transport"):
+                res["config"]["parallelism"] += "; local BA: map points partitioned over the ranks, normal equations all-reduced — " + res["local_ba"]["transport"]
+        if rank == 0 and world == 1 and not args.no_files and (W, H) == (752, 480):
+            try:
+                res["from_png_files"] = bench_from_files(P, h, torch, args.features)
+            except Exception as e:
+                res["from_png_files"] = dict(error=repr(e))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            big = W * H > 752 * 480
+            res["cpu_baseline"] = cpu_baseline(P, 16 if big else 48, 2 if big else 12, W, H, args.features)
+        elif rank == 0:
+            res["cpu_baseline"] = None
+    if rank == 0:
+        print(json.dumps(res))
+    h.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out, d, n_sample=32, budget=48 << 20):
+    """--dump-outputs: what the last timed step handed its caller (alloc_batch_outputs), as .npy files under `d`, so that two builds can
+    be compared output for output.  Per-pair counts of every pair; keypoints, descriptors, matches and points of a fixed, seeded sample of
+    at most `n_sample` pairs (and `budget` bytes).  Entries past a pair's counts are zeroed (they hold whatever an earlier step left there),
+    as are the points of left keypoints without one; integer and f32 fields are widened to f64, descriptor bytes to f32."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    B, cap = out["batch"], out["cap_kp"]
+    per_pair = cap * (2 * 7 * 8 + 2 * 32 * 4 + 4 * 8 + 3 * 8 + 4)
+    S = max(1, min(B, n_sample, budget // per_pair))
+    idx = np.sort(np.random.default_rng(0x5EED).choice(B, S, replace=False))
+    ti = torch.from_numpy(idx).to(out["kp"].device)
+    take = lambda k: out[k].index_select(0, ti).cpu().numpy()
+    nkp = np.minimum(out["nkp"].cpu().numpy(), cap)
+    nm = np.minimum(out["nmatches"].cpu().numpy(), cap)
+    kp, desc, m, pts, has = take("kp"), take("desc"), take("matches"), take("points"), take("has_point")
+    slot = np.arange(cap)
+    live_kp = slot[None, None, :] < nkp[idx][:, :, None]         # [S, 2, cap]
+    live_left = slot[None, :] < nkp[idx, 0][:, None]             # [S, cap]: points / has_point are per left keypoint
+    live_m = slot[None, :] < nm[idx][:, None]                    # [S, cap]
+    kp = np.concatenate([kp[..., :5].astype(np.float64), kp[..., 5:].view(np.int32).astype(np.float64)], -1)   # x y size angle response | octave class_id
+    m = np.concatenate([m[..., :3].astype(np.float64), m[..., 3:].view(np.float32).astype(np.float64)], -1)    # query train img | distance
+    has = np.where(live_left, has, 0)
+    arrays = dict(sample_pairs=idx.astype(np.float64), n_keypoints=nkp.astype(np.float64), n_matches=nm.astype(np.float64),
+                  keypoints=np.where(live_kp[..., None], kp, 0.0), descriptors=np.where(live_kp[..., None], desc, 0).astype(np.float32),
+                  matches=np.where(live_m[..., None], m, 0.0), points=np.where((has == 1)[..., None], pts, 0.0),
+                  has_point=has.astype(np.float32))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def roofline_block(args, acc, dom_pre, n_pre, elapsed, world, W, H):
+    """--full: the `roofline` object of the line, from the per-kernel HIP-event times `acc` ({kernel: [ms, launches]} over the K timed steps)."""
     # roofline of the dominant kernel (largest summed HIP-event duration over the timed region)
     total_ms = sum(a[0] for a in acc.values())
     dom = max(acc.items(), key=lambda kv: kv[1][0])
@@ -396,50 +490,7 @@ def main():
                     kernel_ms_per_step_source="%s: HIP events over the timed region; the other kernels: an untimed pass of %d steps with events around every launch" % (dom_pre, n_pre),
                     path_algorithmic_GBps=round(algo_bytes_per_frame(W, H, args.features) * args.batch * world * args.steps / elapsed / 1e9, 3),
                     path_hbm_frac=round(algo_bytes_per_frame(W, H, args.features) * args.batch * world * args.steps / elapsed / 1e9 / HBM_PEAK_GBS / world, 5))
-
-    frames = args.batch * args.steps * world
-    value = frames / elapsed
-    res = dict(metric="stereo frames/sec ORB extract+match @%dx%d" % (W, H), value=round(value, 2), unit="stereo frames/s",
-               n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4),
-               higher_is_better=True, scaling="weak", vs_baseline=None, dtype="u8", data="synthetic",
-               config=dict(workload="Synthetic %dx%d stereo, %d ORB/frame, extract+match+triangulate (BASELINE configs[%d])"
-                                    % (W, H, args.features, 1 if (W, H, args.features) == (752, 480, 2000) else 4),
-                           image=[W, H], n_features=args.features, batch_pairs_per_gpu=args.batch,
-                           distinct_batches=args.n_batches, unique_pairs=(min(32, args.batch * args.n_batches) if args.small_gen else args.batch * args.n_batches),
-                           parallelism="frames sharded, %d rank(s), no collective%s" % (world, " (REHEARSAL: ranks share GPUs, gloo)" if rehearse else ""),
-                           mean_keypoints_per_image=round(n_kp, 1), mean_matches_per_frame=round(n_matches, 1)),
-               roofline=roofline, value_unprofiled=round(args.batch * args.steps * world / elapsed_np, 2),
-               value_all_kernel_events=dict(value=round(args.batch * n_pre / elapsed_pre, 2), steps=n_pre,
-                                            note="rank 0's untimed pass with HIP events around EVERY launch: how `value` was measured until round 3 "
-                                                 "(since round 4 the timed region brackets the dominant kernel only)"))
-
-    if rank == 0 and world == 1 and not args.no_extras:
-        try:
-            res.update(bench_extras(P, h, torch, batches, out, args, W, H))
-        except Exception as e:
-            res["extras_error"] = repr(e)
-    if not args.no_ba:
-        try:
-            res["local_ba"] = bench_ba(P, h, cam, rank, world, dev)
-        except Exception as e:  # BA leg must not hide the headline number
-            res["local_ba"] = dict(error=repr(e))
-        if world > 1 and isinstance(res["local_ba"], dict) and res["local_ba"].get("transport"):
-            res["config"]["parallelism"] += "; local BA: map points partitioned over the ranks, normal equations all-reduced — " + res["local_ba"]["transport"]
-    if rank == 0 and world == 1 and not args.no_files and (W, H) == (752, 480):
-        try:
-            res["from_png_files"] = bench_from_files(P, h, torch, args.features)
-        except Exception as e:
-            res["from_png_files"] = dict(error=repr(e))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        big = W * H > 752 * 480
-        res["cpu_baseline"] = cpu_baseline(P, 16 if big else 48, 2 if big else 12, W, H, args.features)
-    elif rank == 0:
-        res["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(res))
-    h.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return roofline
 
 
 def bench_extras(P, h, torch, batches, out, args, W, H):

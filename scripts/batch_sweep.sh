@@ -5,7 +5,7 @@ TAG=$1; shift
 O=gpurun_out/$TAG
 mkdir -p $O
 for b in "$@"; do
-  python bench.py --no-cpu-baseline --no-ba --no-files --no-extras --batch $b --steps ${STEPS:-20} > $O/batch_$b.json 2> $O/batch_$b.err
+  python bench.py --full --no-cpu-baseline --no-ba --no-files --no-extras --batch $b --steps ${STEPS:-20} > $O/batch_$b.json 2> $O/batch_$b.err
   python - "$O/batch_$b.json" "$b" <<'PY' | tee -a $O/sweep.txt
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

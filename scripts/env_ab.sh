@@ -10,7 +10,7 @@ for rep in 1 2; do
   for cfg in "$@"; do
     i=$((i+1))
     if [ "$cfg" = "-" ]; then envs=""; else envs="$cfg"; fi
-    env $envs python bench.py --no-cpu-baseline --no-ba --no-files --no-extras --steps ${STEPS:-40} > $O/run_$i.json 2> $O/run_$i.err
+    env $envs python bench.py --full --no-cpu-baseline --no-ba --no-files --no-extras --steps ${STEPS:-40} > $O/run_$i.json 2> $O/run_$i.err
     python - "$O/run_$i.json" "$cfg" <<'PY' | tee -a $O/ab.txt
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

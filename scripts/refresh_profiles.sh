@@ -11,9 +11,9 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 B=/tmp/orbx_bench_batches.npy
-python bench.py --batch $BATCH --save-batches $B > $O/bench_b$BATCH.json 2> $O/bench_b$BATCH.err
+python bench.py --full --batch $BATCH --save-batches $B > $O/bench_b$BATCH.json 2> $O/bench_b$BATCH.err
 cd /tmp && export TMPDIR=/tmp
-COMMON="--batch $BATCH --no-cpu-baseline --no-files --no-extras --load-batches $B"
+COMMON="--full --batch $BATCH --no-cpu-baseline --no-files --no-extras --load-batches $B"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 10 --warmup 2 $COMMON > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "sq:SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "sq2:SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT"; do
   name=${pass%%:*}; ctrs=${pass#*:}

@@ -227,7 +227,7 @@ def test_bench_two_rank_rehearsal_line(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, ORBX_DIST_REHEARSE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
+                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full",
                         "--no-cpu-baseline", "--no-files", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -238,3 +238,33 @@ def test_bench_two_rank_rehearsal_line(tmp_path):
     assert ba["iterations"] == 10 and ba["lm_iters_per_s"] > 0 and "points partitioned over 2 ranks" in ba["workload"]
     assert "REHEARSAL" in ba["transport"] and "REHEARSAL" in d["config"]["parallelism"] and "all-reduced" in d["config"]["parallelism"]
     assert ba["independent_windows"]["windows"] == 2 and ba["independent_windows"]["lm_iters_per_s"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline line alone (no roofline, no other legs) over exactly --steps timed steps, and --dump-outputs
+    writes the last timed step's results as float32 / float64 .npy files — the same bytes from two runs with the same arguments (the inputs
+    are seeded)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = os.path.join(str(tmp_path), "out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--n-batches", "1", "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["unit"] == "stereo frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+        assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 8e3 - 1) < 1e-2
+        assert not {"roofline", "value_unprofiled", "local_ba", "cpu_baseline", "batch_sweep", "from_png_files"} & set(line)
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert {"n_keypoints", "n_matches", "keypoints", "descriptors", "matches", "points", "has_point"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["n_keypoints"].shape == (8, 2) and arrays["keypoints"].shape == (8, 2, 2304, 7)
+        assert abs(arrays["n_keypoints"].mean() - line["config"]["mean_keypoints_per_image"]) < 0.06
+        runs.append(arrays)
+    assert all(runs[0][k].tobytes() == runs[1][k].tobytes() for k in runs[0])
