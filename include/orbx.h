@@ -538,6 +538,65 @@ int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_in
                            double* poses_wc_out, double* vel_out, double* bias_out, int* iterations,
                            double* initial_error, double* final_error);
 
+/* ---- PnP-RANSAC pose estimation (src/geometry/pnp.rs) --------------------------------------------------------
+ * Replaces solve_pnp_ransac / solve_pnp_ransac_detailed (pnp.rs:29-134): cv::solvePnPRansac(100 iterations, 8 px,
+ * confidence 0.99, SOLVEPNP_ITERATIVE, useExtrinsicGuess = prior given) + Rodrigues, the result inverted back to T_wc, then the
+ * per-correspondence reprojection error sqrt(du^2 + dv^2) (+inf where the camera-frame z <= 0) and the mask err < reproj_error.
+ * OpenCV's internals are not reproduced; the library implements a specification with OpenCV's structure:
+ *   [spec] a counter-based sampler (splitmix64 of seed + 0x9E3779B97F4A7C15 * (h*64 + a + 1); index = ((z >> 32) * n) >> 32;
+ *          duplicates skipped, 64 draws at most), so that a problem's result does not depend on the batch around it;
+ *   [spec] hypotheses by Levenberg-Marquardt on each model_points sample starting from the prior (every reference call site
+ *          passes one) instead of EPnP: left perturbation, the visual BA's pose block, lambda 1e-3 and the project's damping rule;
+ *   OpenCV's inlier test (float)(du^2 + dv^2) <= (float)reproj_error^2, its sequential best-model walk with RANSACUpdateNumIters
+ *   (applied after all hypotheses were scored in parallel), and a final LM over the best model's inliers (refine_iterations);
+ *   [spec] 4 <= n <= model_points: one hypothesis from all points; n < 4: TOO_FEW; no model: NO_MODEL and the prior's bytes back.
+ * Poses are 7 doubles (qw,qx,qy,qz,tx,ty,tz), camera-to-world as the reference passes them. */
+enum {
+  ORBX_PNP_OK = 0,
+  ORBX_PNP_NO_MODEL = 1,     /* no hypothesis passed the walk: pose = prior (the reference ignores solvePnPRansac's bool) */
+  ORBX_PNP_TOO_FEW = 2,      /* n < 4: pose = prior (the callers guard n < 4 / n < 10 themselves)                         */
+  ORBX_PNP_OVER_MAX_N = 3    /* device form: n > max_n: pose = prior                                                   */
+};
+/* orbx_default_pnp_config: max_iterations 100, reproj_error 8.0, confidence 0.99 (pnp.rs:71-84), model_points 5 (OpenCV's
+ * model size for SOLVEPNP_ITERATIVE), hypothesis_iterations 10, refine_iterations 20 (OpenCV's extrinsic LM), seed 0.
+ * Accepted ranges: 1 <= max_iterations <= 1024, 4 <= model_points <= 8, reproj_error > 0, 0 <= confidence <= 1, iteration counts
+ * 0..1000; other values -> ORBX_ERR_INVALID. */
+typedef struct {
+  int max_iterations;
+  double reproj_error, confidence;
+  int model_points, hypothesis_iterations, refine_iterations;
+  uint64_t seed;
+} orbx_pnp_config;
+/* One problem's record.  n_inliers: of the final mask (err < reproj_error); ransac_inliers: the best hypothesis' count under
+ * OpenCV's test; hypotheses_evaluated: where the sequential walk ended (OpenCV's iteration count); refine_iterations: LM
+ * iterations of the final refinement; final_rms: sqrt(mean err^2) over the final inliers (0 without any). */
+typedef struct {
+  int status, n_inliers, ransac_inliers, best_hypothesis, hypotheses_evaluated, refine_iterations;
+  double final_rms;
+} orbx_pnp_result;
+void orbx_default_pnp_config(orbx_pnp_config* cfg);
+
+/* One problem in host memory, synchronous.  pts3d [n][3] f64 world points, pts2d [n][2] f32 pixels (cv::Point2f), prior_wc [7]
+ * (required: every reference call site passes Some), pose_wc_out [7], inlier_out [n] u8 (1 = inlier), err_out [n] f64,
+ * result [1].  Every buffer is the caller's; the library copies in and out. */
+int orbx_pnp_ransac(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* cfg, int n, const double* pts3d,
+                    const float* pts2d, const double* prior_wc, double* pose_wc_out, uint8_t* inlier_out, double* err_out,
+                    orbx_pnp_result* result);
+/* n_problems independent problems in host memory, one upload and one download: problem p owns correspondences
+ * [offsets[p], offsets[p+1]) of pts3d / pts2d / inlier_out / err_out (offsets [n_problems+1], ascending, offsets[0] = 0);
+ * priors_wc / poses_wc_out [n_problems][7], results [n_problems].  Each problem's result equals orbx_pnp_ransac on it, byte for
+ * byte.  Synchronous; caller-owned buffers. */
+int orbx_pnp_ransac_batch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* cfg, int n_problems, const int* offsets,
+                          const double* pts3d, const float* pts2d, const double* priors_wc, double* poses_wc_out,
+                          uint8_t* inlier_out, double* err_out, orbx_pnp_result* results);
+/* The same with every array in device memory (the caller's; the library only reads the inputs and writes the outputs),
+ * asynchronous on the handle's stream.  max_n: a host-known bound on the correspondences of one problem (it sizes the scoring
+ * launch); a problem with more gets ORBX_PNP_OVER_MAX_N and its prior, with the detailed pass still computed.  d_offsets must be
+ * ascending from 0 (they are trusted: they index the point arrays). */
+int orbx_pnp_ransac_batch_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* cfg, int n_problems, int max_n,
+                                 const int* d_offsets, const double* d_pts3d, const float* d_pts2d, const double* d_priors_wc,
+                                 double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_results);
+
 /* Per-kernel device time for bench.py's roofline block.  While profiling is on
  * (orbx_set_profiling), every launch is bracketed by HIP events on the handle's stream;
  * orbx_get_kernel_times synchronises, fills up to `cap` entries with the durations summed

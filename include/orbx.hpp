@@ -13,6 +13,7 @@
 //   orbx::LocalBAConfigLM                   src/optimizer/local_ba_lm.rs:96-119
 //   orbx::VisualObservation/ProblemData/ResultData   local_ba_lm.rs:48-93
 //   orbx::solve_visual_ba                   local_ba_lm.rs:912-1098
+//   orbx::PnPResult / solve_pnp_ransac_detailed    src/geometry/pnp.rs:12-20, :100-134
 //
 // Errors: the reference propagates `anyhow::Error` with `?` — here orbx::Error is thrown; where the
 // reference returns `None` (solve_visual_ba) std::nullopt is returned.  Everything computes on the GPU.
@@ -480,6 +481,39 @@ inline SE3 se3_inverse(const SE3& p) {   // se3.rs:56-63 with nalgebra's quatern
   SE3 r;
   r.rotation = {w, x, y, z};
   for (int i = 0; i < 3; ++i) r.translation[i] = -(t[i] * w + c[i] + v[i]);
+  return r;
+}
+
+struct PnPResult {   // pnp.rs:12-20; pose is T_wc
+  SE3 pose;
+  std::vector<bool> inlier_mask;
+  std::vector<double> reproj_errors;   // +inf where the point is behind the camera
+};
+
+// pnp.rs:100-134 (solvePnPRansac with 100 iterations, 8 px, confidence 0.99, then the per-correspondence errors), as the
+// specification of orbx_pnp_ransac (orbx.h) states it.  prior: T_wc; required — every reference call site passes Some, and the
+// prior-free path is not implemented (std::invalid_argument).  Without a model the prior comes back, as in the reference.
+inline PnPResult solve_pnp_ransac_detailed(Handle& h, const std::vector<std::array<double, 3>>& points3d,
+                                           const std::vector<std::array<float, 2>>& points2d, const CameraModel& camera,
+                                           const std::optional<SE3>& prior) {
+  if (!prior) throw std::invalid_argument("solve_pnp_ransac_detailed: a prior pose is required");
+  if (points3d.size() != points2d.size()) throw std::invalid_argument("solve_pnp_ransac_detailed: points3d / points2d differ in length");
+  const int n = (int)points3d.size();
+  const orbx_camera cam = camera.c();
+  orbx_pnp_config cfg;
+  orbx_default_pnp_config(&cfg);
+  const double p7[7] = {prior->rotation[0], prior->rotation[1], prior->rotation[2], prior->rotation[3],
+                        prior->translation[0], prior->translation[1], prior->translation[2]};
+  double o7[7];
+  std::vector<uint8_t> inl(std::max(n, 1));
+  PnPResult r;
+  r.reproj_errors.resize(n);
+  orbx_pnp_result res;
+  h.check(orbx_pnp_ransac(h.get(), &cam, &cfg, n, n ? points3d[0].data() : nullptr, n ? points2d[0].data() : nullptr, p7, o7, inl.data(),
+                          n ? r.reproj_errors.data() : nullptr, &res));
+  r.pose.rotation = {o7[0], o7[1], o7[2], o7[3]};
+  r.pose.translation = {o7[4], o7[5], o7[6]};
+  r.inlier_mask.assign(inl.begin(), inl.begin() + n);
   return r;
 }
 

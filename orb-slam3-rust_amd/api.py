@@ -13,6 +13,7 @@ written in Python with the reference's own names and argument meaning:
     LocalBAConfigLM              local_ba_lm.rs:96-119   LocalBAConfigLM
     VisualBAProblemData/Result   local_ba_lm.rs:48-93    VisualBAProblemData / VisualBAResultData
     solve_visual_ba              local_ba_lm.rs:912      solve_visual_ba
+    solve_pnp_ransac[_detailed]  pnp.rs:29-134           solve_pnp_ransac[_detailed] / Handle.solve_pnp_ransac_batch
 
 Everything computes on the GPU through liborbx_hip.so; there is no CPU fallback, and a missing
 library or device raises.
@@ -80,6 +81,7 @@ ABI_SYMBOLS = [
     "orbx_euroc_frame_timestamp", "orbx_euroc_calibration", "orbx_euroc_read_pairs",
     "orbx_set_profiling", "orbx_set_profiling_only", "orbx_get_kernel_times", "orbx_debug_read_level",
     "orbx_debug_read_candidates",
+    "orbx_default_pnp_config", "orbx_pnp_ransac", "orbx_pnp_ransac_batch", "orbx_pnp_ransac_batch_device",
 ]
 
 
@@ -131,6 +133,24 @@ class _BaWindow(C.Structure):
     _fields_ = [("K", C.c_int), ("poses_cw", C.c_void_p), ("F", C.c_int), ("fixed_poses_cw", C.c_void_p), ("M", C.c_int),
                 ("points", C.c_void_p), ("N", C.c_int), ("obs", C.c_void_p), ("poses_wc_out", C.c_void_p), ("status", C.c_int),
                 ("iterations", C.c_int), ("initial_error", C.c_double), ("final_error", C.c_double), ("obs32", C.c_void_p)]
+
+
+class _PnpConfig(C.Structure):
+    """orbx_pnp_config (include/orbx.h)"""
+    _fields_ = [("max_iterations", C.c_int), ("reproj_error", C.c_double), ("confidence", C.c_double), ("model_points", C.c_int),
+                ("hypothesis_iterations", C.c_int), ("refine_iterations", C.c_int), ("seed", C.c_uint64)]
+
+
+class _PnpResult(C.Structure):
+    """orbx_pnp_result (include/orbx.h)"""
+    _fields_ = [("status", C.c_int), ("n_inliers", C.c_int), ("ransac_inliers", C.c_int), ("best_hypothesis", C.c_int),
+                ("hypotheses_evaluated", C.c_int), ("refine_iterations", C.c_int), ("final_rms", C.c_double)]
+
+
+# orbx_pnp_result as a numpy record (the batch forms' results array)
+PNP_RESULT = np.dtype([("status", "<i4"), ("n_inliers", "<i4"), ("ransac_inliers", "<i4"), ("best_hypothesis", "<i4"),
+                       ("hypotheses_evaluated", "<i4"), ("refine_iterations", "<i4"), ("final_rms", "<f8")])
+PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N = 0, 1, 2, 3
 
 
 SHOULD_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -264,6 +284,39 @@ class LocalInertialBAConfig:
     def _c(self):
         return _InertialBaConfig(self.max_iterations, self.window_size, self.huber_threshold_mono, self.huber_threshold_stereo,
                                  self.initial_lambda, self.gyro_rw_info, self.accel_rw_info)
+
+
+@dataclass
+class PnPConfig:
+    """cv::solvePnPRansac's arguments of pnp.rs:71-84 (100 iterations, 8 px, confidence 0.99) and the [spec] choices of
+    orbx_pnp_config (include/orbx.h): OpenCV's 5-point model, 10 LM iterations per hypothesis, 20 for the final refinement,
+    the sampler's seed."""
+    max_iterations: int = 100
+    reproj_error: float = 8.0
+    confidence: float = 0.99
+    model_points: int = 5
+    hypothesis_iterations: int = 10
+    refine_iterations: int = 20
+    seed: int = 0
+
+    def _c(self):
+        return _PnpConfig(self.max_iterations, self.reproj_error, self.confidence, self.model_points, self.hypothesis_iterations,
+                          self.refine_iterations, self.seed)
+
+
+@dataclass
+class PnPResult:
+    """pnp.rs:12-20: pose (T_wc, 7 doubles qw,qx,qy,qz,tx,ty,tz), inlier_mask [n] bool, reproj_errors [n] f64 (+inf behind the
+    camera); stats = the orbx_pnp_result record as a dict (status, n_inliers, ransac_inliers, best_hypothesis,
+    hypotheses_evaluated, refine_iterations, final_rms)."""
+    pose: np.ndarray
+    inlier_mask: np.ndarray
+    reproj_errors: np.ndarray
+    stats: Dict[str, float] = field(default_factory=dict)
+
+
+def _pnp_stats(rec):
+    return {k: (float(rec[k]) if k == "final_rms" else int(rec[k])) for k in PNP_RESULT.names}
 
 
 @dataclass
@@ -415,6 +468,53 @@ class Handle:
                                               C.c_double(img_h), _vp(q_uv), _vp(q_desc), C.c_int(nq), C.c_double(radius),
                                               C.c_int(mode), _vp(idx), _vp(dist)))
         return idx[:nq].copy(), dist[:nq].copy()
+
+    def solve_pnp_ransac_detailed(self, camera, points3d, points2d, prior_wc, cfg: PnPConfig = None) -> PnPResult:
+        """pnp.rs:100-134 on one problem: points3d [n,3] f64 world points, points2d [n,2] (taken as f32, cv::Point2f), prior_wc
+        [7] T_wc.  The pose comes back as T_wc; a problem without a model returns the prior (status in .stats)."""
+        return self.solve_pnp_ransac_batch(camera, [(points3d, points2d, prior_wc)], cfg)[0]
+
+    def solve_pnp_ransac_batch(self, camera, problems, cfg: PnPConfig = None) -> List[PnPResult]:
+        """Many problems [(points3d, points2d, prior_wc), ...] in one call (one upload, one download); each result equals the
+        single-problem call's byte for byte."""
+        pts3d = [np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a, _, _ in problems]
+        pts2d = [np.ascontiguousarray(b, np.float32).reshape(-1, 2) for _, b, _ in problems]
+        if any(len(a) != len(b) for a, b in zip(pts3d, pts2d)):
+            raise ValueError("points3d and points2d differ in length")
+        P = len(problems)
+        off = np.zeros(P + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in pts3d])
+        N = int(off[-1])
+        p3 = np.concatenate(pts3d) if N else np.zeros((1, 3), np.float64)
+        p2 = np.concatenate(pts2d) if N else np.zeros((1, 2), np.float32)
+        priors = np.ascontiguousarray(np.stack([np.asarray(c, np.float64).reshape(7) for _, _, c in problems]) if P else
+                                      np.zeros((1, 7)), np.float64)
+        poses = np.zeros((max(P, 1), 7), np.float64)
+        inl = np.zeros(max(N, 1), np.uint8); err = np.zeros(max(N, 1), np.float64)
+        res = np.zeros(max(P, 1), PNP_RESULT)
+        c = (cfg or PnPConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_pnp_ransac_batch(self._h, C.byref(cam), C.byref(c), C.c_int(P), _vp(off), _vp(p3), _vp(p2), _vp(priors),
+                                                  _vp(poses), _vp(inl), _vp(err), _vp(res)))
+        return [PnPResult(poses[p].copy(), inl[off[p]:off[p + 1]].astype(bool), err[off[p]:off[p + 1]].copy(), _pnp_stats(res[p]))
+                for p in range(P)]
+
+    def solve_pnp_ransac_batch_device(self, camera, offsets, points3d, points2d, priors_wc, max_n, cfg: PnPConfig = None):
+        """Device-resident batch: torch CUDA tensors offsets [P+1] int32 (ascending from 0), points3d [N,3] f64, points2d [N,2] f32,
+        priors_wc [P,7] f64; max_n bounds a problem's n (larger ones get PNP_OVER_MAX_N and the prior).  Returns (poses_wc [P,7] f64,
+        inlier [N] u8, err [N] f64, results [P,32] u8 — view the bytes as PNP_RESULT); asynchronous on the handle's stream."""
+        import torch
+        P, N = int(offsets.shape[0]) - 1, int(points3d.shape[0])
+        dev = points3d.device
+        poses = torch.empty((max(P, 1), 7), dtype=torch.float64, device=dev)
+        inl = torch.empty(max(N, 1), dtype=torch.uint8, device=dev)
+        err = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+        res = torch.empty((max(P, 1), PNP_RESULT.itemsize), dtype=torch.uint8, device=dev)
+        c = (cfg or PnPConfig())._c(); cam = camera._c()
+        self._after_torch(offsets, points3d, points2d, priors_wc, poses, inl, err, res)
+        self._check(self._L.orbx_pnp_ransac_batch_device(self._h, C.byref(cam), C.byref(c), C.c_int(P), C.c_int(int(max_n)), _vp(offsets),
+                                                         _vp(points3d), _vp(points2d), _vp(priors_wc), _vp(poses), _vp(inl), _vp(err),
+                                                         _vp(res)))
+        return poses[:P], inl[:N], err[:N], res[:P]
 
     def search_for_triangulation(self, camera, kp1, desc1, mp1, stereo1, kp2, desc2, mp2, pose1_wc, pose2_wc, max_dist=50):
         """triangulation.rs:401-527.  Returns [(idx1, idx2)] as an int32 [n,2] array, ascending idx1."""
@@ -846,6 +946,19 @@ def descriptor_distance(desc1, desc2) -> int:
 def bf_match_crosscheck(query_descriptors, train_descriptors):
     """tracker.rs:1001-1010: BFMatcher::new(NORM_HAMMING, true).train_match(query, train)."""
     return _handle().hamming_match_crosscheck(query_descriptors, train_descriptors)
+
+
+def solve_pnp_ransac_detailed(points3d, points2d, camera: CameraModel, prior=None) -> PnPResult:
+    """pnp.rs:100-134: the reference's name and argument order (prior = T_wc, 7 doubles).  A prior is required: every reference call
+    site passes one, and the prior-free (EPnP) path is not implemented."""
+    if prior is None:
+        raise ValueError("solve_pnp_ransac_detailed needs a prior pose (the prior-free solver is not implemented)")
+    return _handle().solve_pnp_ransac_detailed(camera, points3d, points2d, prior)
+
+
+def solve_pnp_ransac(points3d, points2d, camera: CameraModel, prior=None) -> np.ndarray:
+    """pnp.rs:29-97: the pose (T_wc, 7 doubles) alone."""
+    return solve_pnp_ransac_detailed(points3d, points2d, camera, prior).pose
 
 
 @dataclass

@@ -45,6 +45,7 @@
 #include <thread>
 
 #include "orbx_internal.hpp"
+#include "pose_dev.hpp"
 
 namespace {
 
@@ -59,15 +60,6 @@ struct BaDims {
   int ntile;    // P/16
   int pps;      // map points per k-split, a multiple of 16 (= 48 rows = one LDS operand tile of the producer / consumer body, two of the general body)
   int ncb;      // 128-column blocks of the reduced system: ceil(ntile / 8)
-};
-
-struct BaCam {
-  double fx, fy, cx, cy, huber;
-  int zero_behind;   // solve_global_ba: Jacobian rows are zero where z_c <= 0.001 (global_ba.rs:561-563)
-  int inertial;      // solve_inertial_ba: T_wc pose parameters, the Jacobian forms of local_inertial_ba.rs:735-804,
-                     // no Huber on the 100-px penalty, Huber threshold per observation (o_flag bit 0 = stereo)
-  double huber_stereo;
-  const int* o_flag;
 };
 
 // Levenberg-Marquardt state kept on the device (local_ba_lm.rs:1004-1056): the host only polls should_stop and
@@ -182,39 +174,6 @@ __device__ __forceinline__ BaWin ba_win_global(const BaWin* __restrict__ wins, i
   g.obs_raw = (const orbx_ba_obs*)v.obs_raw; g.obs32 = v.obs32; g.pad_ = 0; g.pt_fill = (int*)v.pt_fill; g.obs_tmp = (int*)v.obs_tmp; g.o_flag = (int*)v.o_flag;
   g.Mz = (double*)v.Mz; g.Vraw = (double*)v.Vraw; g.rej = (double*)v.rej; g.dbl = v.dbl; g.pad2_ = 0;
   return g;
-}
-
-// ---- small device math ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void quat_to_R(const double* q, double* R) {
-  const double w = q[0], i = q[1], j = q[2], k = q[3];
-  const double ww = w * w, ii = i * i, jj = j * j, kk = k * k;
-  const double ij = i * j * 2.0, wk = w * k * 2.0, wj = w * j * 2.0;
-  const double ik = i * k * 2.0, jk = j * k * 2.0, wi = w * i * 2.0;
-  R[0] = ww + ii - jj - kk; R[1] = ij - wk;           R[2] = wj + ik;
-  R[3] = wk + ij;           R[4] = ww - ii + jj - kk; R[5] = jk - wi;
-  R[6] = ik - wj;           R[7] = wi + jk;           R[8] = ww - ii - jj + kk;
-}
-
-// local_ba_lm.rs:648-662 then R|t (12 doubles)
-// nalgebra UnitQuaternion::from_scaled_axis = exp of the pure quaternion r/2 (identity when |r/2|^2 <= eps^2)
-__device__ __forceinline__ void dev_q_from_scaled_axis(const double* r, double* q) {
-  const double v0 = r[0] / 2.0, v1 = r[1] / 2.0, v2 = r[2] / 2.0;
-  const double nn = v0 * v0 + v1 * v1 + v2 * v2;
-  const double eps = 2.220446049250313e-16;
-  if (nn <= eps * eps) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; return; }
-  const double n = sqrt(nn), s = 1.0 * sin(n) / n;
-  q[0] = 1.0 * cos(n); q[1] = v0 * s; q[2] = v1 * s; q[3] = v2 * s;
-}
-__device__ __forceinline__ void dev_q_rot(const double* q, const double* v, double* o) {   // UnitQuaternion * Vector3
-  const double t0 = 2.0 * (q[2] * v[2] - q[3] * v[1]), t1 = 2.0 * (q[3] * v[0] - q[1] * v[2]), t2 = 2.0 * (q[1] * v[1] - q[2] * v[0]);
-  const double c0 = q[2] * t2 - q[3] * t1, c1 = q[3] * t0 - q[1] * t2, c2 = q[1] * t1 - q[2] * t0;
-  o[0] = t0 * q[0] + c0 + v[0]; o[1] = t1 * q[0] + c1 + v[1]; o[2] = t2 * q[0] + c2 + v[2];
-}
-__device__ __forceinline__ void dev_q_mul(const double* a, const double* b, double* o) {
-  o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
 }
 
 // pose parameters -> R|t of T_cw (12 doubles).  Visual solvers: se3_from_params (local_ba_lm.rs:648-662) of T_cw parameters;
@@ -493,34 +452,6 @@ __global__ __launch_bounds__(BA_KFL_THREADS) void ba_kflist_kernel(const BaWin* 
 
 struct ObsOut { double r0, r1, A[12], B[6]; double px, py, piz, psw; double chi; };
 
-// The 2x6 pose block A and the 2x3 point block B of one observation (both * sqrt(w)) from its four "projective" numbers —
-// x, y of the point in the camera frame, 1/z, and the square root of the Huber weight — and the keyframe's R|t: no division, no
-// square root.  piz == 0 marks an observation whose Jacobian rows are zero (|z| < 1e-6, or behind the camera in the global /
-// inertial forms).  obs_terms itself goes through this function, so every kernel that rebuilds the blocks from the stored
-// (x, y, 1/z, sqrt w) gets the same bits the build kernel used for V and g_l.
-// J_pose (:239-254), J_point (:281-287); inertial: local_inertial_ba.rs:735-804.
-// Round 4: the entries as products of six shared factors (f_x sqrt w, f_y sqrt w, those times 1/z, x/z, y/z) instead of each entry's own
-// chain of four or five multiplications as the reference writes them — 28 double-precision operations where there were 70, in every
-// per-observation kernel (these kernels issue f64 operations and little else).  The values agree with the literal form to rounding.
-// The inertial form's point block is the same expression; its pose block is the visual one with the opposite sign (the perturbation
-// is applied on the other side), so one body serves both.  A[4] and A[9] are structurally zero: the callers skip their products.
-__device__ __forceinline__ void obs_jac_from_proj(const BaCam& cam, const double* Rt, double x, double y, double piz, double sw,
-                                                  double* __restrict__ A, double* __restrict__ B) {
-  // (piz == 0 comes with sw == 0 — obs_terms sets both or neither, an empty Schur slot is all zeros — and then every entry below is
-  // 0 * finite: no test, no branch, so that two observations' blocks can be scheduled into each other)
-  const double fs = cam.fx * sw, gs = cam.fy * sw, fz = fs * piz, gz = gs * piz, xz = x * piz, yz = y * piz;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    B[c] = fz * fma(xz, Rt[6 + c], -Rt[c]);                // -(1/z) (f_x R_0c - f_x (x/z) R_2c) sqrt w
-    B[3 + c] = gz * fma(yz, Rt[6 + c], -Rt[3 + c]);
-  }
-  const double sg = cam.inertial ? -1.0 : 1.0;
-  const double fa = sg * fs, ga = sg * gs, fza = sg * fz, gza = sg * gz;
-  A[2] = yz * fa;                    A[0] = xz * A[2];                  A[1] = -(fma(xz, xz, 1.0) * fa);
-  A[3] = -fza;                       A[4] = 0.0;                        A[5] = xz * fza;
-  A[8] = -(xz * ga);                 A[7] = yz * A[8];                  A[6] = fma(yz, yz, 1.0) * ga;
-  A[9] = 0.0;                        A[10] = -gza;                      A[11] = yz * gza;
-}
 // (the pose block's structural zeros: column 4 of the u row, column 3 of the v row)
 __device__ __forceinline__ constexpr bool ba_a0_zero(int a) { return a == 4; }
 __device__ __forceinline__ constexpr bool ba_a1_zero(int a) { return a == 3; }

@@ -201,6 +201,8 @@ struct orbx_handle {
   DevBuf ws_pyr, ws_blur, ws_cand, ws_counters, ws_sel, ws_sel2, ws_match, ws_io[12];
   DevBuf ws_dtile;                       // [image][describe tile] (begin, end) inside the level's spatially ordered keypoint list (rank_select_kernel)
   DevBuf ws_ba[28];
+  DevBuf ws_pnp[2];                      // PnP-RANSAC: [0] hypotheses + counts (pnp_kernels.hip), [1] the host forms' input / output blobs
+  void* h_pnp = nullptr; size_t h_pnp_bytes = 0;   // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};

@@ -478,3 +478,36 @@ def read_ba_batch_results(path, windows):
             pts = np.frombuffer(f.read(24 * M), np.float64).reshape(M, 3)
             out.append(dict(status=status, iterations=iters, initial_error=e0, final_error=e1, poses_wc=poses, points=pts))
     return out
+
+
+def pnp_problem(seed, n, outlier_frac, prior_rot_deg, prior_trans_m, noise_px=0.5, camera=EUROC_CAMERA, w=752, h=480):
+    """A PnP-RANSAC scene (solve_pnp_ransac_detailed, src/geometry/pnp.rs:100-134).  Ground truth T_wc: a rotation of up to 0.5 rad
+    about a random axis, position U[-2,2]^3 m.  Each point is drawn as a pixel U[4, w-4] x U[4, h-4] at depth U[1,20] m and
+    back-projected, so the points cover the image.  Inlier observations carry Gaussian noise of sigma noise_px with its length
+    clipped at 2 px; round(outlier_frac * n) outliers are displaced 30-200 px from their true projection in a random direction —
+    a wide margin on both sides of the 8-px threshold.  The prior is the truth turned by prior_rot_deg about a random axis and
+    moved by prior_trans_m in a random direction.
+    Returns points3d [n,3] f64 (world), points2d [n,2] f32, prior_wc / pose_wc [7] (qw,qx,qy,qz,tx,ty,tz), inliers [n] bool, camera."""
+    rng = np.random.default_rng(seed)
+    cam = camera
+    q_wc = _quat_from_axis_angle(rng.normal(size=3), rng.uniform(0.0, 0.5))
+    t_wc = rng.uniform(-2.0, 2.0, 3)
+    u = rng.uniform(4.0, w - 4.0, n); v = rng.uniform(4.0, h - 4.0, n); d = rng.uniform(1.0, 20.0, n)
+    Xc = np.stack([(u - cam["cx"]) / cam["fx"] * d, (v - cam["cy"]) / cam["fy"] * d, d], 1)
+    Xw = _quat_rot(q_wc, Xc) + t_wc
+    e = rng.normal(0.0, noise_px, (n, 2))
+    e *= np.minimum(1.0, 2.0 / np.maximum(np.linalg.norm(e, axis=1), 1e-300))[:, None]
+    uv = np.stack([u, v], 1) + e
+    inliers = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        idx = rng.choice(n, n_out, replace=False)
+        ang = rng.uniform(0.0, 2.0 * np.pi, n_out); mag = rng.uniform(30.0, 200.0, n_out)
+        uv[idx] = np.stack([u[idx], v[idx]], 1) + np.stack([np.cos(ang), np.sin(ang)], 1) * mag[:, None]
+        inliers[idx] = False
+    dq = _quat_from_axis_angle(rng.normal(size=3), np.deg2rad(prior_rot_deg))
+    dt = rng.normal(size=3)
+    dt *= prior_trans_m / np.linalg.norm(dt)
+    q_prior = _quat_mul(dq, q_wc)
+    return dict(points3d=Xw, points2d=uv.astype(np.float32), pose_wc=np.concatenate([q_wc, t_wc]),
+                prior_wc=np.concatenate([q_prior / np.linalg.norm(q_prior), t_wc + dt]), inliers=inliers, camera=dict(cam))
