@@ -3588,7 +3588,6 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   // Where each window's observations come from: straight out of the caller's memory when that is pinned (the copy engine reads it where
   // it lies: no host pass over the observations at all), else through the pinned blob (a plain copy, on the handle's workers when it is
   // large).  Windows whose observations follow each other in memory travel as one copy.
-  static const bool force_stage = getenv("ORBX_BA_STAGE_OBS") != nullptr;   // (A/B and tests: never read the caller's memory directly)
   struct Run { int w0, w1; size_t off, bytes; const void* src; bool direct; };
   std::vector<Run> runs;
   bool any_stage = false;
@@ -3601,7 +3600,7 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
     } else runs.push_back(Run{w, w + 1, plan[w].i_obs, bytes, src, false});
   }
   for (Run& r : runs) {
-    r.direct = !force_stage && host_is_pinned(r.src, r.bytes);
+    r.direct = host_is_pinned(r.src, r.bytes);
     if (!r.direct) any_stage = true;
   }
   enum { B_IN, B_ARENA, B_OUT, B_IMU, B_S15 };
@@ -3703,7 +3702,7 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   // the K rotations — per 32 points instead of per 8; 32-window batch: build 0.103 -> 0.096, back-substitution 0.068 -> 0.064 ms per iteration)
   const int ppg = W >= 8 ? 4 : 1;
   const int ptl = W >= 8 ? 16 : 32;   // lanes per point in those two kernels (group_sum<>: the sums do not depend on it)
-  static const int one_launch_max_n = getenv("ORBX_BA_BIG_STEPS") ? 0 : BF_MAX_N;   // (ORBX_BA_BIG_STEPS: the multi-launch factorisation for every size, for A/B runs)
+  const int one_launch_max_n = BF_MAX_N;   // reduced systems up to this size: the one-launch factorisation, larger ones one launch per panel
   int any_one = 0;
   int any_lds = 0, any_big = 0, n_big_max = 0, maxM = 0, maxK = 0, max_schur_blocks = 1, all_diag = 1, max_gather = 1, max_back = 1, max_asm = 1;
   for (int w = 0; w < W; ++w) {
@@ -3749,7 +3748,6 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   if (ptl == 16) {
     const size_t cap = 3 * (size_t)h->n_cu, wt = (size_t)(W + h->ba_peer_windows);
     while (ppg_build < 16 && wt * (size_t)((((maxM + ppg_build - 1) / ppg_build) * ptl + 255) / 256) > cap) ++ppg_build;
-    if (const char* e = getenv("ORBX_BA_PPG")) if (*e) ppg_build = std::max(1, atoi(e));
   }
   const int pt_groups = (maxM + ppg_build - 1) / ppg_build;
   // a batch large enough to fill the chip with one workgroup per (window, gather share): the Schur workgroups add their share's partials
@@ -3922,16 +3920,15 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
         ProfScope ps(h, "ba_kf_kernel");
         hipLaunchKernelGGL(ba_kf_kernel, dim3(maxK * BA_KFSPLIT, W), dim3(BA_KF_THREADS), 0, st, d_wins, bc);
       }
-      ProfScope ps(h, "ba_schur_kernel", nullptr, true);
+      ProfScope ps(h, "ba_schur_kernel", true);
       if (all_diag) hipLaunchKernelGGL(ba_schur_kernel<true>, dim3(schur_sums ? BA_GATHER_LANES : (max_schur_blocks + schur_spb - 1) / schur_spb, W), dim3(SCHW_THREADS), SCHW_LDS_BYTES, st, d_wins, bc, schur_spb);
       else hipLaunchKernelGGL(ba_schur_kernel<false>, dim3(max_schur_blocks, W), dim3(256), 0, st, d_wins, bc, 1);
     }
     {
       ProfScope ps(h, "ba_gather_kernel");
       // (with the shares already summed by the Schur launch a lane reads ONE pair per element: a block per 32 element pairs was 7 200 blocks of a
-      // few hundred cycles each for 32 windows; ORBX_BA_GATHER_DIV elements per thread: 1 / 2 / 4 / 8 / 16 measured 14.7 / 13.4 / 12.8 / 15.1 / 18.5 us)
-      static const int gather_div = [] { const char* e = getenv("ORBX_BA_GATHER_DIV"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 64 ? v : 4; }();
-      hipLaunchKernelGGL(ba_gather_kernel, dim3(schur_sums ? std::max(1, max_gather / gather_div) : max_gather, W), dim3(256), 0, st, d_wins, fused_loop && iter > 0 ? iter : -1);
+      // few hundred cycles each for 32 windows; 4 elements per thread: 1 / 2 / 4 / 8 / 16 measured 14.7 / 13.4 / 12.8 / 15.1 / 18.5 us)
+      hipLaunchKernelGGL(ba_gather_kernel, dim3(schur_sums ? std::max(1, max_gather / 4) : max_gather, W), dim3(256), 0, st, d_wins, fused_loop && iter > 0 ? iter : -1);
     }
     if (int rc = allreduce(w0.rb, plan[0].rb_len)) return rc;
     if (inertial) {

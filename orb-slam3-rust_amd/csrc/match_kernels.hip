@@ -205,7 +205,7 @@ __global__ __launch_bounds__(SM_THREADS) void stereo_match_kernel(
 // dependent round trips to L2; here the chain runs on LDS, the right descriptors leave HBM once per pair (the line-granular gathers of the first
 // form fetched 4.9 times the compulsory bytes), and the group reduction is four DPP row rotations instead of twelve LDS swizzles.  Same candidate
 // sets, same order-independent top-2: the matches are bit-identical (tests/test_matcher_gpu.py, test_extract_gpu.py).  Large batches only: a pair
-// occupies ONE CU for its ~31 rounds, so a call needs at least as many pairs as CUs to fill the chip (launch_stereo_match_range picks).
+// occupies ONE CU for its ~31 rounds, so a call needs at least as many pairs as CUs to fill the chip (launch_stereo_match picks).
 constexpr int SML_THREADS = 1024;
 #ifndef ORBX_SML_LPK
 #define ORBX_SML_LPK 4
@@ -956,28 +956,20 @@ __global__ __launch_bounds__(256) void hamming_batch_kernel(const uint8_t* __res
 
 }  // namespace
 
-// `batch_total` pairs size the workspace; this call matches the `batch` pairs that start at pair `pair0` of the caller's arrays on stream
-// `st` (nullptr = the handle's).  Pairs are independent and every array — the workspace's too — is indexed by pair, so a batch processed
-// as several ranges (orbx_process_stereo_batch_device's two-stream form) gives the bits of one call over the whole batch.
-int launch_stereo_match_range(orbx_handle* h, hipStream_t st, int batch_total, int pair0, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
-                              const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
-                              double* d_points, uint8_t* d_has_point) {
-  if (batch_total <= 0) return ORBX_OK;
-  if (!st) st = h->stream;
-  // workspace: tmp int2[batch*cap] | bstart int[batch*(SB_ROWS+1)] | sidx int[batch*cap] | sxy float2[batch*cap]
-  const size_t n_tmp = (size_t)batch_total * cap_kp;
-  const size_t bytes = sizeof(int2) * n_tmp + sizeof(int) * (size_t)batch_total * (SB_ROWS + 1) + sizeof(int) * n_tmp +
+int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
+                        const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
+                        double* d_points, uint8_t* d_has_point) {
+  if (batch <= 0) return ORBX_OK;
+  const hipStream_t st = h->stream;
+  // workspace: tmp int2[batch*cap] | sxy float2[batch*cap] | sidx int[batch*cap] | bstart int[batch*(SB_ROWS+1)]
+  const size_t n_tmp = (size_t)batch * cap_kp;
+  const size_t bytes = sizeof(int2) * n_tmp + sizeof(int) * (size_t)batch * (SB_ROWS + 1) + sizeof(int) * n_tmp +
                        sizeof(float2) * n_tmp + 64;
   if (int rc = orbx_reserve(h, h->ws_match, bytes)) return rc;
-  if (batch <= 0) return ORBX_OK;                      // (a call that only sizes the workspace)
-  const size_t o = (size_t)pair0 * cap_kp;
   int2* tmp = (int2*)h->ws_match.p;
   float2* sxy = (float2*)(tmp + n_tmp);
   int* sidx = (int*)(sxy + n_tmp);
-  int* bstart = sidx + n_tmp + (size_t)pair0 * (SB_ROWS + 1);
-  tmp += o; sxy += o; sidx += o;
-  d_kp += 2 * o; d_desc += 64 * o; d_nkp += 2 * (size_t)pair0;
-  d_matches += o; d_nmatches += pair0; d_points += 3 * o; d_has_point += o;
+  int* bstart = sidx + n_tmp;
   // stereo.rs:84-90: f64 product/quotient, then `as f32`
   const float max_disp = (float)(h->cam.fx * h->cam.baseline / 0.1);
   const float min_disp = (float)(h->cam.fx * h->cam.baseline / 40.0);
@@ -990,39 +982,33 @@ int launch_stereo_match_range(orbx_handle* h, hipStream_t st, int batch_total, i
                               hipFuncSetAttribute((const void*)stereo_match_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
   const bool use_lds = sm_attr && lds_need <= 160 * 1024 && (sm_env >= 1 || (sm_env < 0 && batch >= h->n_cu));
   if (use_lds && lds_fused <= 160 * 1024 && sm_env != 2) {
-    ProfScope ps(h, "stereo_match_kernel", st, true);
+    ProfScope ps(h, "stereo_match_kernel", true);
     hipLaunchKernelGGL(stereo_match_lds_kernel<true>, dim3(batch), dim3(SML_THREADS), lds_fused, st, d_kp, d_desc, d_nkp,
                        cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   }
   {
-    ProfScope ps(h, "stereo_bucket_kernel", st);
+    ProfScope ps(h, "stereo_bucket_kernel");
     hipLaunchKernelGGL(stereo_bucket_kernel, dim3(batch), dim3(SB_THREADS), 0, st, d_kp, d_nkp, cap_kp, bstart, sidx, sxy);
   }
   if (use_lds) {
-    ProfScope ps(h, "stereo_match_kernel", st, true);
+    ProfScope ps(h, "stereo_match_kernel", true);
     hipLaunchKernelGGL(stereo_match_lds_kernel<false>, dim3(batch), dim3(SML_THREADS), lds_need, st, d_kp, d_desc, d_nkp,
                        cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point);
   } else {
-    ProfScope ps(h, "stereo_match_kernel", st, true);
+    ProfScope ps(h, "stereo_match_kernel", true);
     dim3 grid((cap_kp + SM_LEFT_PER_BLOCK - 1) / SM_LEFT_PER_BLOCK, batch);
     hipLaunchKernelGGL(stereo_match_kernel, grid, dim3(SM_THREADS), 0, st, d_kp, d_desc, d_nkp,
                        cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp);
   }
   {
-    ProfScope ps(h, "stereo_compact_kernel", st, true);
+    ProfScope ps(h, "stereo_compact_kernel", true);
     hipLaunchKernelGGL(stereo_compact_kernel, dim3(batch), dim3(256), 0, st, d_kp, d_nkp, cap_kp,
                        (const int2*)tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point);
   }
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
-}
-
-int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
-                        const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
-                        double* d_points, uint8_t* d_has_point) {
-  return launch_stereo_match_range(h, nullptr, batch, 0, batch, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point);
 }
 
 int launch_crosscheck(orbx_handle* h, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,

@@ -7,9 +7,7 @@
 //   copy_l0_kernel        (only if the caller's rows are not 4-byte aligned)
 //   resize_kernel  x7     level l from level l-1, INTER_LINEAR_EXACT fixed point: 4 px x 6 rows per thread from an LDS-staged source tile,
 //                         8-byte source windows, v_dot4 taps                                  (A.4)
-//   blur_kernel           7x7 sigma-2 fixed-point Gaussian of every level: register window walking down
-//                         column strips (no LDS), DPP neighbours, v_dot4 / v_dot2 taps       (A.8)
-//   fast_kernel           FAST-9/16 score + 3x3 NMS + border filter on 62x62 LDS tiles, 3 tiles per block with the next
+//   fast_kernel          FAST-9/16 score + 3x3 NMS + border filter on 62x62 LDS tiles, 3 tiles per block with the next
 //                         tile's pixels prefetched: byte-parallel compass pre-test (v_bitop3_b32), compacted survivors,
 //                         arc score on f16 denormals (v_pk_minimum3/maximum3_f16), one append per chain; per-level
 //                         candidate lists + score histograms                                  (A.5)
@@ -17,9 +15,13 @@
 //                         of the survivors                                                    (A.6)
 //   rank_select_kernel    canonical order (response desc, y, x) by bitonic sort in LDS, retainBest(n_l)
 //                         incl. ties with the n-th; the kept keypoints again in spatial order  (A.6)
-//   describe_kernel       16 lanes per keypoint, 4 keypoints per wave, walking the spatial list:
-//                         intensity-centroid angle from the level, 37x37 blurred patch in LDS ->
-//                         256 steered BRIEF tests, one __ballot per 16 bits of 4 descriptors (A.7, A.8)
+//   describe_tile_kernel  one workgroup per describe tile: the tile's blurred rectangle on the matrix pipe in LDS,
+//                         intensity-centroid angle and 256 steered BRIEF tests per keypoint   (A.7, A.8)
+//   describe_fused_kernel the same per keypoint (small calls, levels too small for tiles): each keypoint's
+//                         37x37 patch blurred on the matrix pipe                               (A.7, A.8)
+//
+//   blur_kernel           7x7 sigma-2 fixed-point Gaussian of every level (not on the product path:
+//                         orbx_debug_read_level(which = 1) runs it to expose the blurred levels) (A.8)
 //
 // Everything is integer/byte work except the Harris response, the angle and the pattern rotation,
 // which are f32/f64 written one IEEE operation at a time (no contraction) so that the results are
@@ -1099,7 +1101,7 @@ __device__ __forceinline__ void rank_pass(const unsigned long long* __restrict__
 
 // Besides the canonical list (sel2, the order of the output slots) the kernel leaves the kept keypoints of the level a
 // second time in `sel` — which it has consumed by then — in SPATIAL order: by 128-pixel column band, then by row, each
-// entry x | y << 16 | slot-in-level << 32.  describe_kernel walks that list, so the 16 keypoints of a block are
+// entry x | y << 16 | slot-in-level << 32.  describe_fused_kernel walks that list, so the 16 keypoints of a block are
 // neighbours in one band and share the cache lines of their patch rows (results go to the keypoint's slot: the order
 // of processing is free).
 // exclusive prefix sum over skey[0..1024) in place (all RK_NT threads; skey[1024..1024+RK_NT/64) is scratch): 1024 / RK_NT counters per
@@ -1315,29 +1317,15 @@ __device__ __forceinline__ void sincos_deg(float angle_deg, float& c_out, float&
   s_out = (float)sn;
 }
 
-#ifndef ORBX_PB_PITCH
-#define ORBX_PB_PITCH 10
-#endif
-constexpr int PB_ROWS = 37, PB_PITCH = ORBX_PB_PITCH;   // blurred 37x37 patch: 10 dwords per row (26.7 KB per block with the tables: 6 blocks per CU)
-
 // Intensity-centroid weights (Appendix A.7): the 31x31 patch as 31 rows x 8 dwords (task t = r*8 + c,
 // pixel column 4c+b); per task one dword of 0/1 disc-membership bytes and one of (column index)*membership
 // bytes, so that v_dot4_u32_u8 yields sum(I) and sum((u+15) I) of four pixels at once.
 __constant__ unsigned c_ic_ones[256];
 __constant__ unsigned c_ic_col[256];
 
-// What binds this kernel (PMC, 128-pair batch): the texture addresser — TA busy 86 %, VALU 50 %, LDS 28 % — i.e. the
-// scattered row segments of the two patches, not arithmetic or latency.  Measured and dropped: all pixel loads hoisted
-// in front of their first use (7 -> 2 dependent round trips: +-0), 6 waves/SIMD by a VGPR cap (slower), 16-byte lane
-// loads (unaligned wide accesses split: 0.31 -> 0.36 ms), the test pattern as floats in LDS (ds_read_b128: slower),
-// 8-byte loads at aligned addresses with the misalignment undone in the arithmetic (24 loads instead of 29, bit-exact,
-// 0.31 -> 0.32 ms; per-lane task constants must then be kept from being hoisted out of the keypoint loop, ~50 VGPRs).
-// Round 2: not requesting the tenth of the patch / disc bytes that can never be read (rows |dy| >= 13 need fewer 8-byte columns)
-// — as predicated loads 0.485 -> 0.62 ms (the branches break the load schedule), as loads redirected to a needed neighbour address 0.54.
 // Four keypoints per wave, 16 lanes each: the per-keypoint work that every lane would otherwise repeat (slot and
 // key decode, the three centroid reductions, fastAtan2, the f64 sin/cos) is shared by 4 keypoints per instruction.
-// Lane li of a group owns centroid tasks t = it*16 + li and descriptor bits r*16 + li (it, r = 0..15); a ballot
-// delivers 16 bits of each of the four descriptors at once.
+// Lane li of a group owns centroid tasks t = it*16 + li (it = 0..15).
 constexpr int DG_PER_WAVE = 4, DG_PER_BLOCK = 16;   // 16 lanes per keypoint
 typedef float desc_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int row16_sum(int v) {
@@ -1348,160 +1336,8 @@ __device__ __forceinline__ int row16_sum(int v) {
   return v;
 }
 
-// (round 2 re-check of the occupancy: 4 / 5 / 6 waves per SIMD — 5 is what the 95 VGPRs give — 0.546 / 0.490 / 0.540 ms per 256 pairs)
-#ifdef ORBX_DESC_WAVES
-__attribute__((amdgpu_waves_per_eu(ORBX_DESC_WAVES, ORBX_DESC_WAVES)))
-#endif
-__global__ __launch_bounds__(256) void describe_kernel(OrbSrc s, OrbGeom g, int n_img, XcdMap xm, int blocks_per_img,
-                                                       const unsigned long long* __restrict__ sel2,
-                                                       const unsigned long long* __restrict__ spatial,
-                                                       const unsigned* __restrict__ kept,
-                                                       orbx_keypoint* __restrict__ kp_out, uint8_t* __restrict__ desc_out,
-                                                       int* __restrict__ nkp, int cap_kp, float patch_size,
-                                                       unsigned* __restrict__ status) {
-  __shared__ unsigned pb[DG_PER_BLOCK][PB_ROWS * PB_PITCH];
-  int img, bx;
-  if (!xcd_decode(xm, n_img, img, bx)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int grp = lane >> 4, li = lane & 15;
-  // block-wide tables in LDS (registers are better spent on occupancy): 256 rBRIEF test pairs, 256 centroid tasks
-  __shared__ int s_pat[256];
-  __shared__ __attribute__((aligned(8))) unsigned s_ones[256], s_col[256];
-  s_pat[tid] = reinterpret_cast<const int*>(c_pattern)[tid];
-  s_ones[tid] = c_ic_ones[tid];
-  s_col[tid] = c_ic_col[tid];
-  __syncthreads();
-  unsigned start[ORBX_MAX_LEVELS + 1];
-  start[0] = 0;
-#pragma unroll
-  for (int l = 0; l < ORBX_MAX_LEVELS; ++l)
-    start[l + 1] = start[l] + (l < g.n_levels ? kept[img * g.n_levels + l] : 0u);
-  const unsigned total = start[ORBX_MAX_LEVELS];
-  const unsigned limit = min(total, (unsigned)cap_kp);
-  if (bx == 0 && tid == 0) {
-    nkp[img] = (int)limit;
-    if (total > (unsigned)cap_kp) atomicOr(status, ORBX_ST_KP_OVERFLOW);
-  }
-  unsigned* myp = pb[wave * DG_PER_WAVE + grp];
-  const uint8_t* pbb = reinterpret_cast<const uint8_t*>(myp);
-  for (unsigned base = (bx * 4 + wave) * DG_PER_WAVE; base < total; base += blocks_per_img * DG_PER_BLOCK) {
-    // position `pos` of the image's spatially ordered walk (levels one after the other) -> level, entry of the level's
-    // spatial list -> the keypoint and its output slot
-    const unsigned pos_raw = base + grp;
-    const unsigned pos = pos_raw < total ? pos_raw : base;  // idle groups shadow the wave's first keypoint
-    int l = 0;
-    unsigned lbase = 0;
-#pragma unroll
-    for (int i = 1; i < ORBX_MAX_LEVELS; ++i) if (pos >= start[i]) { l = i; lbase = start[i]; }
-    // (levels beyond n_levels have start == total > pos, so l < n_levels)
-    const size_t lofs = (size_t)img * g.cand_total + g.lv[l].cand_off;
-    const unsigned long long ent = spatial[lofs + (pos - lbase)];
-    const int kx = (int)(ent & 0xffffu), ky = (int)((ent >> 16) & 0xffffu);
-    const unsigned j2 = (unsigned)(ent >> 32) & 0xffffu;
-    const unsigned slot = lbase + j2;
-    const bool active = pos_raw < total && slot < limit;
-    const float resp = from_orderable(~(unsigned)(sel2[lofs + j2] >> 32));   // only needed for the output record
-    int pitch;
-    const uint8_t* src = level_ptr(s, g, img, l, pitch);
-    const uint8_t* blr = s.blur + (size_t)img * g.slot_bytes + g.lv[l].off;
-    const int bpitch = g.lv[l].pitch;
-    // stage the blurred 37x37 patch (rows of 40 bytes starting at kx-18) into this group's LDS patch: 5 lanes x 8 bytes
-    // per row, 3 rows per step (no division, half the loads of a dword-per-lane loop)
-    {
-      const int sub = li / 5, c2 = li - 5 * sub;           // li = 15 idles
-      // (row pointers by 32-bit steps: a 64-bit multiply-add per load is a quarter-rate instruction)
-      const uint8_t* b0 = blr + (unsigned)(__umul24((unsigned)(ky - 18 + sub), (unsigned)bpitch) + (unsigned)(kx - 18 + 8 * c2));
-      const unsigned bstep = 3u * (unsigned)bpitch;
-#pragma unroll
-      for (int it = 0; it < 13; ++it) {
-        const int r = 3 * it + sub;
-        if (sub < 3 && r < PB_ROWS) {
-          unsigned long long v;
-          __builtin_memcpy(&v, b0 + (unsigned)it * bstep, 8);
-          myp[r * PB_PITCH + 2 * c2] = (unsigned)v;
-          myp[r * PB_PITCH + 2 * c2 + 1] = (unsigned)(v >> 32);
-        }
-      }
-    }
-    // intensity centroid over the 749-pixel disc straight from the level image (integer, order independent)
-    int sA = 0, sB = 0, sC = 0;
-    {
-      // lane li: rows 4 it + (li >> 2), dwords 2 (li & 3) and 2 (li & 3) + 1 of the row as ONE 8-byte load (row 31 does not exist:
-      // zero weights, re-reads row 30).  Builds without the centroid loads / without the patch loads run 0.38 / 0.35 ms against 0.505:
-      // the addresser's time follows the bytes, but not quite — an 8-byte instruction costs 1.5x a 4-byte one, so 8 rounds of 8-byte
-      // loads instead of 16 of dwords: 0.502 -> 0.485 ms per 256 pairs
-      const uint8_t* a0 = src + (unsigned)(__umul24((unsigned)(ky - 15 + (li >> 2)), (unsigned)pitch) + (unsigned)(kx - 15 + 8 * (li & 3)));
-      const unsigned astep = 4u * (unsigned)pitch;
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int row = 4 * it + (li >> 2);
-        const int r = min(row, 30);
-        unsigned long long px;
-        __builtin_memcpy(&px, a0 + ((unsigned)it * astep - (row > 30 ? (unsigned)pitch : 0u)), 8);
-        const int t0 = row * 8 + 2 * (li & 3);
-        const uint2 w1 = *reinterpret_cast<const uint2*>(&s_ones[t0]);
-        const uint2 wc = *reinterpret_cast<const uint2*>(&s_col[t0]);
-        const unsigned sI = __builtin_amdgcn_udot4((unsigned)(px >> 32), w1.y, __builtin_amdgcn_udot4((unsigned)px, w1.x, 0u, false), false);
-        sA += (int)__builtin_amdgcn_udot4((unsigned)(px >> 32), wc.y, __builtin_amdgcn_udot4((unsigned)px, wc.x, 0u, false), false);
-        sB += (int)sI;
-        sC += (r - 15) * (int)sI;
-      }
-    }
-    // sums over the 16 lanes of the group = one DPP row: four rotate-and-add steps, no LDS crossbar
-    sA = row16_sum(sA); sB = row16_sum(sB); sC = row16_sum(sC);
-    const int m10 = sA - 15 * sB, m01 = sC;
-    const float angle = fast_atan2_deg((float)m01, (float)m10);
-    float ca, sa;
-    sincos_deg(angle, ca, sa);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0);   // staging stores visible to the whole wave before the reads
-    // 16 test rounds, 16 lanes x 4 keypoints each: one ballot per round holds 16 descriptor bits of each of the four
-    // keypoints.  Fully unrolled so that the word / shift a round's bits go to are compile-time constants (with a
-    // partial unroll the four 64-bit words were updated through selects: ~16 extra VALU instructions per round).
-    unsigned long long word[4] = {0ull, 0ull, 0ull, 0ull};
-    const desc_f2 ca2 = {ca, ca}, sa2 = {sa, sa}, magic2 = {12582912.f, 12582912.f};
-    // byte (row + 18) * pitch + col + 18 of the patch from the raw float bits: the 24-bit multiply sees 0x400000 + row, the
-    // column term carries the whole 0x4B400000 + col
-    constexpr unsigned kBias = 0x400000u * (PB_PITCH * 4) + 0x4B400000u - (18u * (PB_PITCH * 4) + 18u);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      // rotated test points, both ends of the pair per packed-f32 instruction (each product and sum rounded on its own,
-      // as the reference's scalar code); rint by the 1.5*2^23 trick: the low 24 bits of (x + magic) are 0x400000 + rint(x)
-      const int pr = s_pat[r * 16 + li];
-      const desc_f2 X = {(float)(signed char)(pr & 0xff), (float)(signed char)((pr >> 16) & 0xff)};
-      const desc_f2 Y = {(float)(signed char)((pr >> 8) & 0xff), (float)(signed char)((pr >> 24) & 0xff)};
-      const desc_f2 fx = X * ca2 - Y * sa2 + magic2;
-      const desc_f2 fy = X * sa2 + Y * ca2 + magic2;
-      const unsigned a0 = __umul24(__float_as_uint(fy[0]), PB_PITCH * 4) + __float_as_uint(fx[0]) - kBias;
-      const unsigned a1 = __umul24(__float_as_uint(fy[1]), PB_PITCH * 4) + __float_as_uint(fx[1]) - kBias;
-      const int t0 = pbb[a0];
-      const int t1 = pbb[a1];
-      const unsigned long long bal = __ballot(t0 < t1);
-      const unsigned chunk = (unsigned)(bal >> (16 * grp)) & 0xffffu;        // this keypoint's bits 16r .. 16r+15
-      word[r >> 2] |= (unsigned long long)chunk << (16 * (r & 3));
-    }
-    if (active && li < 4) {
-      const unsigned long long wv = li == 0 ? word[0] : li == 1 ? word[1] : li == 2 ? word[2] : word[3];
-      reinterpret_cast<unsigned long long*>(desc_out + ((size_t)img * cap_kp + slot) * 32)[li] = wv;
-    }
-    if (active && li == 4) {
-      const float sc = g.lv[l].scale;
-      orbx_keypoint o;
-      o.x = __fmul_rn((float)kx, sc);
-      o.y = __fmul_rn((float)ky, sc);
-      o.size = __fmul_rn(patch_size, sc);
-      o.angle = angle;
-      o.response = resp;
-      o.octave = l;
-      o.class_id = -1;
-      kp_out[(size_t)img * cap_kp + slot] = o;
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
 // ---- A.7 + A.8 with the blur inside (round 4): no blurred pyramid ----------------------------------------------------------------
-// The blurred levels exist for ONE reader, this kernel, which takes a 37 x 37 patch per keypoint out of them — so the whole-level blur
+// The blurred levels existed for ONE reader, the descriptor kernel of rounds 1-3, which took a 37 x 37 patch per keypoint out of them — so the whole-level blur
 // (0.31 ms per 256 pairs, 1.39 GB of HBM traffic per launch) and the second image per keypoint that the texture addresser had to walk
 // (31 + 37 row segments) are replaced by ONE 43-row window of the unblurred level per keypoint, staged in LDS, from which the kernel
 // takes the intensity centroid and computes the patch's blur itself.  The blur is exact integer arithmetic whichever way it is summed —
@@ -1529,7 +1365,7 @@ __constant__ __attribute__((aligned(16))) unsigned c_blur_band[6 * 64 * 4];   //
 #define ORBX_DF_ITERS 2        // keypoint groups per wave: the block prologue (tables, level starts) is paid once per ORBX_DF_ITERS x 16 keypoints (1 / 2: 0.705 / 0.699 ms)
 #endif
 // Measured on the way (round 4, same box, per 256 pairs; every variant bit-exact on the frozen digests):
-//   whole-level blur + describe_kernel 0.299 + 0.484 = 0.783 ms;  this kernel as first written 0.785 — the compiler put the MFMA destinations in
+//   whole-level blur + the descriptor kernel of rounds 1-3 0.299 + 0.484 = 0.783 ms;  this kernel as first written 0.785 — the compiler put the MFMA destinations in
 //   AGPRs and every VALU consumer behind a v_accvgpr_read_b32 (108 of 261 vector instructions per keypoint); with -mllvm
 //   -amdgpu-mfma-vgpr-form=1 (Makefile, this file only) 0.705;  the patch bytes stored one by one straight from bits 16..23 of the sums
 //   (ds_write_b8_d16_hi by inline asm — as C++ byte stores the compiler merges them back into a dword with MORE VALU work — 27 v_perm_b32
@@ -2096,10 +1932,9 @@ int orb_prepare_geometry(orbx_handle* h, int w, int h_px) {
   if (h->geom_w == w && h->geom_h == h_px) return ORBX_OK;
   // A new image size rewrites the resize / tile tables IN PLACE (the buffer rarely grows, so orbx_reserve does not see
   // it): work of earlier asynchronous calls may still be reading them — the blocking copy below runs on the null stream,
-  // which the handle's non-blocking streams do not order against — and a captured hipGraph of orbx_process_stereo has the
-  // old OrbGeom and table offsets baked into its kernel nodes.  Drain the streams and drop the graph first.
+  // which the handle's non-blocking stream does not order against — and a captured hipGraph of orbx_process_stereo has the
+  // old OrbGeom and table offsets baked into its kernel nodes.  Drain the stream and drop the graph first.
   ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (h->s_aux) ORBX_HIP(h, hipStreamSynchronize(h->s_aux));
   if (h->pair_graph) { hipGraphExecDestroy(h->pair_graph); h->pair_graph = nullptr; }
   h->pg_calls = 0;
   h->geom_w = 0; h->geom_h = 0;     // nothing valid until the new tables are up
@@ -2276,184 +2111,128 @@ int orb_prepare_geometry(orbx_handle* h, int w, int h_px) {
   return ORBX_OK;
 }
 
-int orb_extract_prepare(orbx_handle* h, int n_images, int w, int h_px) {
-  if (n_images <= 0) return ORBX_OK;
-  if (int rc = orb_prepare_geometry(h, w, h_px)) return rc;
-  const OrbGeom& g = h->geom;
-  const size_t n_il = (size_t)n_images * g.n_levels;
-  if (int rc = orbx_reserve(h, h->ws_pyr, (size_t)g.slot_bytes * n_images)) return rc;
-  static const bool unfused_ws = getenv("ORBX_DESC_UNFUSED") != nullptr;
-  if (unfused_ws) { if (int rc = orbx_reserve(h, h->ws_blur, (size_t)g.slot_bytes * n_images)) return rc; }
-  if (int rc = orbx_reserve(h, h->ws_cand, sizeof(unsigned) * (size_t)g.cand_total * n_images)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_sel, sizeof(unsigned long long) * (size_t)g.cand_total * n_images)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_sel2, sizeof(unsigned long long) * (size_t)g.cand_total * n_images)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_dtile, sizeof(uint2) * (size_t)std::max(g.dt_total, 1) * n_images)) return rc;
-  // counters: cand_count[n_il], sel_count[n_il], kept[n_il], hist[n_il*256]
-  const size_t n_cnt = n_il * (3 + 256);
-  if (int rc = orbx_reserve(h, h->ws_counters, sizeof(unsigned) * n_cnt)) return rc;
-  ORBX_HIP(h, hipMemsetAsync(h->ws_counters.p, 0, sizeof(unsigned) * n_cnt, h->stream));
-  return ORBX_OK;
-}
-
-int orb_extract_range(orbx_handle* h, hipStream_t st, const uint8_t* d_images, int n_images, int img0, int n, int w, int h_px, size_t stride,
-                      orbx_keypoint* d_kp, uint8_t* d_desc, int* d_nkp, int cap_kp, hipEvent_t after_resize) {
-  if (n <= 0) return ORBX_OK;
-  const OrbGeom& g = h->geom;
-  const int nl = g.n_levels;
-  const size_t n_il = (size_t)n_images * nl;
-  unsigned* cand_count = (unsigned*)h->ws_counters.p;
-  unsigned* sel_count = cand_count + n_il;
-  unsigned* kept = sel_count + n_il;
-  unsigned* hist = kept + n_il;
-  const bool aligned = ((uintptr_t)d_images % 4 == 0) && (stride % 4 == 0) && (((size_t)h_px * stride) % 4 == 0);
-  const unsigned* tab = (const unsigned*)h->resize_tab.p;
-  {
-    OrbSrc s{};
-    s.pyr = (uint8_t*)h->ws_pyr.p + (size_t)img0 * g.slot_bytes;
-    s.blur = (uint8_t*)h->ws_blur.p + (size_t)img0 * g.slot_bytes;
-    const uint8_t* imgs = d_images + (size_t)img0 * h_px * stride;
-    if (aligned) {
-      s.l0 = imgs; s.l0_img_stride = (size_t)h_px * stride; s.l0_pitch = (int)stride;
-    } else {
-      ProfScope ps(h, "copy_l0_kernel", st);
-      hipLaunchKernelGGL(copy_l0_kernel, dim3(1, h_px, n), dim3(256), 0, st, imgs, (size_t)h_px * stride, stride, w, h_px, s.pyr,
-                         g.slot_bytes, g.lv[0].pitch);
-      s.l0 = s.pyr; s.l0_img_stride = g.slot_bytes; s.l0_pitch = g.lv[0].pitch;
-    }
-    if (img0 == 0) { h->last_src = s; h->last_n_images = n_images; }     // (orbx_debug_read_level addresses the whole call's images)
-    unsigned* cc = cand_count + (size_t)img0 * nl;
-    unsigned* sc = sel_count + (size_t)img0 * nl;
-    unsigned* kp = kept + (size_t)img0 * nl;
-    unsigned* hs = hist + (size_t)img0 * nl * 256;
-    unsigned* cand = (unsigned*)h->ws_cand.p + (size_t)img0 * g.cand_total;
-    unsigned long long* sel = (unsigned long long*)h->ws_sel.p + (size_t)img0 * g.cand_total;
-    unsigned long long* sel2 = (unsigned long long*)h->ws_sel2.p + (size_t)img0 * g.cand_total;
-    uint2* dtile = (uint2*)h->ws_dtile.p + (size_t)img0 * (size_t)g.dt_total;
-    {
-      ProfScope ps(h, "resize_kernel", st);
-      for (int l = 1; l < nl; ++l) {
-        const bool small = n < 64;                       // up to 32 pairs: latency counts, keep the blocks short and many (4 / 8 / 16 pairs: 1-2 % over the 6-row form)
-        // (rows chosen per level to waste least of its last tile row, among 3..6: 0.262 against 0.258 ms with 6 everywhere)
-        const int rows = small ? RESIZE_ROWS_SMALL : RESIZE_ROWS;
-        const int tx = (g.lv[l].w + 63) / 64, ty = (g.lv[l].h + 16 * rows - 1) / (16 * rows);
-        const int chains = (tx * ty + RESIZE_CHAIN - 1) / RESIZE_CHAIN;
-        if (small)
-          hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS_SMALL>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
-                             tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
-        else
-          hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
-                             tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
-      }
-    }
-    if (after_resize) ORBX_HIP(h, hipEventRecord(after_resize, st));
-    // blur (latency-bound, ~50 % VALU-busy) and the FAST -> Harris -> ordering chain (issue-bound) both depend only on the
-    // pyramid and meet again at describe: with ORBX_FORK_BLUR=1 in the environment the blur runs beside the chain on a
-    // second stream (+2-3 % frames/s).  Off by default and never while per-kernel profiling is on: two kernels sharing the
-    // chip stretch each other's duration, so per-kernel times (HIP events, rocprof) would describe the overlap instead of
-    // the kernels and no longer agree between runs.
-    // Round 4: describe_fused_kernel blurs each keypoint's patch itself (matrix pipe): no blurred pyramid, no blur launch.  ORBX_DESC_UNFUSED=1
-    // keeps the two-kernel form (whole-level blur + describe_kernel) for A/B runs; orbx_debug_read_level(which = 1) blurs on demand.
-    static const bool unfused = getenv("ORBX_DESC_UNFUSED") != nullptr;
-    const bool fork = unfused && n >= 16 && !h->profiling && getenv("ORBX_FORK_BLUR") != nullptr;
-    if (fork && !h->s_aux) {
-      ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_aux, hipStreamNonBlocking));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-    if (fork) {
-      ORBX_HIP(h, hipEventRecord(h->ev_fork, st));
-      ORBX_HIP(h, hipStreamWaitEvent(h->s_aux, h->ev_fork, 0));
-    }
-    if (unfused) {
-      ProfScope ps(h, "blur_kernel", fork ? h->s_aux : st, true);
-      hipLaunchKernelGGL(blur_kernel, xcd_grid(g.btiles_total, n), dim3(256), 0, fork ? h->s_aux : st, s, g, n, xcd_map(g.btiles_total),
-                         tab + h->btile_tab_off);
-    }
-    if (fork) ORBX_HIP(h, hipEventRecord(h->ev_join, h->s_aux));
-    if (g.ftiles_total > 0) {
-      ProfScope ps(h, "fast_kernel", st, true);
-      // chains of FAST_CHAIN tiles per block once there are blocks to spare (each CU holds 8): for a pair one tile per block
-      const int chain_len = (size_t)g.ftiles_total * n >= (size_t)4 * 8 * h->n_cu ? FAST_CHAIN : 1;
-      const int chains = (g.ftiles_total + chain_len - 1) / chain_len;
-      if (g.fast_threshold < 128)
-        hipLaunchKernelGGL(fast_kernel<true>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
-      else
-        hipLaunchKernelGGL(fast_kernel<false>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
-    }
-    {
-      ProfScope ps(h, "harris_select_kernel", st, true);
-      // (round 3: the first round's candidates requested before the histogram, which they do not depend on — one round trip less on the
-      // block's chain —: 0.152 -> 0.165 ms per 256 pairs; not kept)
-      // 8 blocks per (image, level).  1 / 2 / 4 / 8 / 16 / 32 blocks: 0.210 / 0.169 / 0.153 / 0.150 / 0.204 / 0.375 ms per 256 pairs:
-      // a level's 2 x quota survivors are a few hundred, so a block is one latency chain (histogram -> candidates -> 27 loads per
-      // response -> store) and the kernel lives on how many of them are in flight
-      // Round 5: the blocks dealt to the levels in proportion to their area (candidates follow the area: level 0 holds 12.8 x level 7's, and
-      // with 8 blocks each a level-7 block held ~10 candidates for its 256 threads), at least one each.  Same box, ms per 256 pairs: 8 per
-      // level 0.153; 64 / 40 / 24 / 16 blocks per image by area: 0.146 / 0.141 / 0.144 / 0.149 (profiles/r05_harris_blocks_by_area_ab.txt).
-      // ORBX_HARRIS_BLOCKS=<total per image> overrides, ORBX_HARRIS_BLOCKS=0 keeps 8 per level (A/B runs).
-      HarrisPlan hp{};
-      // (the 40 is per 2000 features: 4000 features on 1920x1080 with 40 blocks ran 0.148 against 0.128 ms per 64 pairs with round 4's 64)
-      static const int hb_env = [] { const char* e = getenv("ORBX_HARRIS_BLOCKS"); return e ? atoi(e) : -1; }();
-      const int hb_auto = std::min(512, std::max(16, (40 * h->orb.n_features + 1000) / 2000));
-      const int hb_total = hb_env < 0 ? hb_auto : (hb_env >= 8 && hb_env <= 512 ? hb_env : 0);
-      if (hb_total) {
-        double area = 0;
-        for (int l = 0; l < nl; ++l) area += (double)g.lv[l].w * g.lv[l].h;
-        for (int l = 0; l < nl; ++l) hp.start[l + 1] = hp.start[l] + std::max(1, (int)lrint(hb_total * ((double)g.lv[l].w * g.lv[l].h) / area));
-      } else
-        for (int l = 0; l < nl; ++l) hp.start[l + 1] = hp.start[l] + 8;
-      for (int l = nl; l < ORBX_MAX_LEVELS; ++l) hp.start[l + 1] = hp.start[nl];
-      const int hblocks = hp.start[nl];
-      hipLaunchKernelGGL(harris_select_kernel, xcd_grid(hblocks, n), dim3(256), 0, st, s, g, n, xcd_map(hblocks),
-                         (const unsigned*)cand, cc, hs, sel, sc, hp);
-    }
-    {
-      ProfScope ps(h, "rank_select_kernel", st, true);
-      hipLaunchKernelGGL(rank_select_kernel, xcd_grid(nl, n), dim3(RK_NT), 0, st, g, n, xcd_map(nl), sel, sc,
-                         sel2, kp, dtile);
-    }
-    if (fork) ORBX_HIP(h, hipStreamWaitEvent(st, h->ev_join, 0));
-    // Round 5: one workgroup per describe tile, the patch blur shared by the tile's keypoints (describe_tile_kernel); ORBX_DESC_TILE=0 (read when
-    // the geometry is prepared) or a level too small for a 64 x 64 window keeps the per-keypoint form
-    // Small calls keep the per-keypoint form: a pair is 104 tiles — 104 workgroups that each walk ~4 window rounds and ~3 keypoint rounds one after
-    // the other — against 126 workgroups of 32 keypoints; one pair per call 0.319 against 0.272 ms, 8 pairs 50.9 against 52.7 k frames/s, 64 pairs
-    // 133 against 126 k (profiles/r05_bench_b512_mid.json against round 4's line).  ORBX_DESC_TILE=1 forces the tile form (tests).
-    static const bool dt_force = [] { const char* e = getenv("ORBX_DESC_TILE"); return e && atoi(e) == 1; }();
-    if (g.dt_total > 0 && !unfused && (dt_force || (size_t)g.dt_total * (size_t)n >= (size_t)8 * (size_t)h->n_cu)) {
-      ProfScope ps(h, "describe_tile_kernel", st, true);
-      // the level's bytes of a window are read where the level lives: level 0 may be the caller's image (row pitch s.l0_pitch >= w >= 64)
-      hipLaunchKernelGGL(describe_tile_kernel, xcd_grid(g.dt_total, n), dim3(256), 0, st, s, g, n, xcd_map(g.dt_total), tab + h->dtile_tab_off,
-                         (const uint2*)dtile, (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp + (size_t)img0 * cap_kp,
-                         d_desc + (size_t)img0 * cap_kp * 32, d_nkp + img0, cap_kp, (float)h->orb.patch_size, h->d_status);
-    } else {
-      ProfScope ps(h, unfused ? "describe_kernel" : "describe_fused_kernel", st, true);
-      const int blocks_x16 = (h->orb.n_features + 64 + 15) / 16;   // 16 keypoints per block and round
-      const int blocks_x = unfused ? blocks_x16 : (blocks_x16 + ORBX_DF_ITERS - 1) / ORBX_DF_ITERS;
-      if (unfused)
-        hipLaunchKernelGGL(describe_kernel, xcd_grid(blocks_x, n), dim3(256), 0, st, s, g, n, xcd_map(blocks_x), blocks_x,
-                           (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp + (size_t)img0 * cap_kp, d_desc + (size_t)img0 * cap_kp * 32,
-                           d_nkp + img0, cap_kp, (float)h->orb.patch_size, h->d_status);
-      else
-        hipLaunchKernelGGL(describe_fused_kernel, xcd_grid(blocks_x, n), dim3(256), 0, st, s, g, n, xcd_map(blocks_x), blocks_x,
-                           (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp + (size_t)img0 * cap_kp, d_desc + (size_t)img0 * cap_kp * 32,
-                           d_nkp + img0, cap_kp, (float)h->orb.patch_size, h->d_status);
-    }
-  }
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
-}
-
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px, size_t stride,
                        orbx_keypoint* d_kp, uint8_t* d_desc, int* d_nkp, int cap_kp) {
   if (n_images <= 0) return ORBX_OK;
-  if (int rc = orb_extract_prepare(h, n_images, w, h_px)) return rc;
+  if (int rc = orb_prepare_geometry(h, w, h_px)) return rc;
+  const OrbGeom& g = h->geom;
+  const int n = n_images, nl = g.n_levels;
+  const size_t n_il = (size_t)n * nl;
+  const hipStream_t st = h->stream;
+  if (int rc = orbx_reserve(h, h->ws_pyr, (size_t)g.slot_bytes * n)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_cand, sizeof(unsigned) * (size_t)g.cand_total * n)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_sel, sizeof(unsigned long long) * (size_t)g.cand_total * n)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_sel2, sizeof(unsigned long long) * (size_t)g.cand_total * n)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_dtile, sizeof(uint2) * (size_t)std::max(g.dt_total, 1) * n)) return rc;
+  // counters: cand_count[n_il], sel_count[n_il], kept[n_il], hist[n_il*256]
+  const size_t n_cnt = n_il * (3 + 256);
+  if (int rc = orbx_reserve(h, h->ws_counters, sizeof(unsigned) * n_cnt)) return rc;
+  ORBX_HIP(h, hipMemsetAsync(h->ws_counters.p, 0, sizeof(unsigned) * n_cnt, st));
+  unsigned* cc = (unsigned*)h->ws_counters.p;
+  unsigned* sc = cc + n_il;
+  unsigned* kp = sc + n_il;
+  unsigned* hs = kp + n_il;
+  unsigned* cand = (unsigned*)h->ws_cand.p;
+  unsigned long long* sel = (unsigned long long*)h->ws_sel.p;
+  unsigned long long* sel2 = (unsigned long long*)h->ws_sel2.p;
+  uint2* dtile = (uint2*)h->ws_dtile.p;
+  const bool aligned = ((uintptr_t)d_images % 4 == 0) && (stride % 4 == 0) && (((size_t)h_px * stride) % 4 == 0);
+  const unsigned* tab = (const unsigned*)h->resize_tab.p;
+  OrbSrc s{};
+  s.pyr = (uint8_t*)h->ws_pyr.p;
+  if (aligned) {
+    s.l0 = d_images; s.l0_img_stride = (size_t)h_px * stride; s.l0_pitch = (int)stride;
+  } else {
+    ProfScope ps(h, "copy_l0_kernel");
+    hipLaunchKernelGGL(copy_l0_kernel, dim3(1, h_px, n), dim3(256), 0, st, d_images, (size_t)h_px * stride, stride, w, h_px, s.pyr,
+                       g.slot_bytes, g.lv[0].pitch);
+    s.l0 = s.pyr; s.l0_img_stride = g.slot_bytes; s.l0_pitch = g.lv[0].pitch;
+  }
+  h->last_src = s; h->last_n_images = n;     // (orbx_debug_read_level addresses these images)
+  {
+    ProfScope ps(h, "resize_kernel");
+    for (int l = 1; l < nl; ++l) {
+      const bool small = n < 64;                       // up to 32 pairs: latency counts, keep the blocks short and many (4 / 8 / 16 pairs: 1-2 % over the 6-row form)
+      // (rows chosen per level to waste least of its last tile row, among 3..6: 0.262 against 0.258 ms with 6 everywhere)
+      const int rows = small ? RESIZE_ROWS_SMALL : RESIZE_ROWS;
+      const int tx = (g.lv[l].w + 63) / 64, ty = (g.lv[l].h + 16 * rows - 1) / (16 * rows);
+      const int chains = (tx * ty + RESIZE_CHAIN - 1) / RESIZE_CHAIN;
+      if (small)
+        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS_SMALL>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
+                           tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
+      else
+        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
+                           tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
+    }
+  }
+  // Round 4: describe_fused_kernel blurs each keypoint's patch itself (matrix pipe): no blurred pyramid, no blur launch;
+  // orbx_debug_read_level(which = 1) blurs on demand.
+  if (g.ftiles_total > 0) {
+    ProfScope ps(h, "fast_kernel", true);
+    // chains of FAST_CHAIN tiles per block once there are blocks to spare (each CU holds 8): for a pair one tile per block
+    const int chain_len = (size_t)g.ftiles_total * n >= (size_t)4 * 8 * h->n_cu ? FAST_CHAIN : 1;
+    const int chains = (g.ftiles_total + chain_len - 1) / chain_len;
+    if (g.fast_threshold < 128)
+      hipLaunchKernelGGL(fast_kernel<true>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
+    else
+      hipLaunchKernelGGL(fast_kernel<false>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
+  }
+  {
+    ProfScope ps(h, "harris_select_kernel", true);
+    // (round 3: the first round's candidates requested before the histogram, which they do not depend on — one round trip less on the
+    // block's chain —: 0.152 -> 0.165 ms per 256 pairs; not kept)
+    // 8 blocks per (image, level).  1 / 2 / 4 / 8 / 16 / 32 blocks: 0.210 / 0.169 / 0.153 / 0.150 / 0.204 / 0.375 ms per 256 pairs:
+    // a level's 2 x quota survivors are a few hundred, so a block is one latency chain (histogram -> candidates -> 27 loads per
+    // response -> store) and the kernel lives on how many of them are in flight
+    // Round 5: the blocks dealt to the levels in proportion to their area (candidates follow the area: level 0 holds 12.8 x level 7's, and
+    // with 8 blocks each a level-7 block held ~10 candidates for its 256 threads), at least one each.  Same box, ms per 256 pairs: 8 per
+    // level 0.153; 64 / 40 / 24 / 16 blocks per image by area: 0.146 / 0.141 / 0.144 / 0.149 (profiles/r05_harris_blocks_by_area_ab.txt).
+    HarrisPlan hp{};
+    // (the 40 is per 2000 features: 4000 features on 1920x1080 with 40 blocks ran 0.148 against 0.128 ms per 64 pairs with round 4's 64)
+    const int hb_total = std::min(512, std::max(16, (40 * h->orb.n_features + 1000) / 2000));
+    double area = 0;
+    for (int l = 0; l < nl; ++l) area += (double)g.lv[l].w * g.lv[l].h;
+    for (int l = 0; l < nl; ++l) hp.start[l + 1] = hp.start[l] + std::max(1, (int)lrint(hb_total * ((double)g.lv[l].w * g.lv[l].h) / area));
+    for (int l = nl; l < ORBX_MAX_LEVELS; ++l) hp.start[l + 1] = hp.start[nl];
+    const int hblocks = hp.start[nl];
+    hipLaunchKernelGGL(harris_select_kernel, xcd_grid(hblocks, n), dim3(256), 0, st, s, g, n, xcd_map(hblocks),
+                       (const unsigned*)cand, cc, hs, sel, sc, hp);
+  }
+  {
+    ProfScope ps(h, "rank_select_kernel", true);
+    hipLaunchKernelGGL(rank_select_kernel, xcd_grid(nl, n), dim3(RK_NT), 0, st, g, n, xcd_map(nl), sel, sc,
+                       sel2, kp, dtile);
+  }
+  // Round 5: one workgroup per describe tile, the patch blur shared by the tile's keypoints (describe_tile_kernel); ORBX_DESC_TILE=0 (read when
+  // the geometry is prepared) or a level too small for a 64 x 64 window keeps the per-keypoint form
+  // Small calls keep the per-keypoint form: a pair is 104 tiles — 104 workgroups that each walk ~4 window rounds and ~3 keypoint rounds one after
+  // the other — against 126 workgroups of 32 keypoints; one pair per call 0.319 against 0.272 ms, 8 pairs 50.9 against 52.7 k frames/s, 64 pairs
+  // 133 against 126 k (profiles/r05_bench_b512_mid.json against round 4's line).  ORBX_DESC_TILE=1 forces the tile form (tests).
+  static const bool dt_force = [] { const char* e = getenv("ORBX_DESC_TILE"); return e && atoi(e) == 1; }();
+  if (g.dt_total > 0 && (dt_force || (size_t)g.dt_total * (size_t)n >= (size_t)8 * (size_t)h->n_cu)) {
+    ProfScope ps(h, "describe_tile_kernel", true);
+    // the level's bytes of a window are read where the level lives: level 0 may be the caller's image (row pitch s.l0_pitch >= w >= 64)
+    hipLaunchKernelGGL(describe_tile_kernel, xcd_grid(g.dt_total, n), dim3(256), 0, st, s, g, n, xcd_map(g.dt_total), tab + h->dtile_tab_off,
+                       (const uint2*)dtile, (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp,
+                       d_desc, d_nkp, cap_kp, (float)h->orb.patch_size, h->d_status);
+  } else {
+    ProfScope ps(h, "describe_fused_kernel", true);
+    const int blocks_x16 = (h->orb.n_features + 64 + 15) / 16;   // 16 keypoints per block and round
+    const int blocks_x = (blocks_x16 + ORBX_DF_ITERS - 1) / ORBX_DF_ITERS;
+    hipLaunchKernelGGL(describe_fused_kernel, xcd_grid(blocks_x, n), dim3(256), 0, st, s, g, n, xcd_map(blocks_x), blocks_x,
+                       (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp, d_desc,
+                       d_nkp, cap_kp, (float)h->orb.patch_size, h->d_status);
+  }
   // (Round 3: the previous batch's stereo matcher on a stream of its own, so that its latency-bound launches run under this batch's resize
   // launches — describe waiting for it, since it rewrites what the matcher reads —: both stretch by what the other takes (resize 0.264 ->
   // 0.360, matcher 0.091 -> 0.155 ms per 256 pairs), frames/s unchanged; withdrawn.)
   // (Two half-batches on two streams were measured: +0.3 % in round 1; again at the end of round 2, when FAST's 7 blocks per CU leave wave
   // slots free: 2 / 3 / 4 / 6 / 8 chunks alternating over two streams: +0.5 ... +2 % / -3 % / 0 / -3 % / -5 % without per-kernel events — so one stream.
-  // Round 5: the same with the second stream STAGGERED by a phase, orbx_process_stereo_batch_device.)
-  return orb_extract_range(h, h->stream, d_images, n_images, 0, n_images, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp, nullptr);
+  // Round 5: the same with the second stream staggered by a phase, each range starting behind the previous one's pyramid: 145.2 k frames/s on
+  // one stream, 144.6 k as 2 ranges, 139.5 k as 4 — every kernel stretches by what the other stream takes (profiles/r05_stagger_two_streams_negative.txt);
+  // removed.  The whole-level blur on a second stream beside the FAST chain, while the descriptors still read a blurred pyramid: +2-3 %; moot since round 4.)
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
 }
 
 // ---- stage inspection --------------------------------------------------------------------------------------

@@ -54,8 +54,7 @@ static hipEvent_t prof_event(orbx_handle* h) {
   }
   return h->event_pool[h->event_next++];
 }
-ProfScope::ProfScope(orbx_handle* h_, const char* name, hipStream_t stream_, bool chained)
-    : h(h_), idx(-1), stream(stream_ ? stream_ : h_->stream) {
+ProfScope::ProfScope(orbx_handle* h_, const char* name, bool chained) : h(h_), idx(-1) {
   if (!h->profiling) return;
   if (!h->prof_only.empty() && h->prof_only != name) { h->prof_tail = nullptr; return; }   // (launches follow that no scope brackets: the next bracketed one records its own start)
   for (size_t i = 0; i < h->timers.size(); ++i)
@@ -66,23 +65,22 @@ ProfScope::ProfScope(orbx_handle* h_, const char* name, hipStream_t stream_, boo
     h->timers.push_back(t);
     idx = (int)h->timers.size() - 1;
   }
-  // chained: nothing was enqueued on this stream since the previous scope ended, so that scope's end event is this
+  // chained: nothing was enqueued on the stream since the previous scope ended, so that scope's end event is this
   // one's start (half the events in a back-to-back kernel sequence: every event costs the stream ~1 us)
-  if (chained && h->prof_tail && h->prof_tail_stream == stream) {
+  if (chained && h->prof_tail) {
     h->timers[idx].ev.push_back(h->prof_tail);
     return;
   }
   hipEvent_t e = prof_event(h);
-  hipEventRecord(e, stream);
+  hipEventRecord(e, h->stream);
   h->timers[idx].ev.push_back(e);
 }
 ProfScope::~ProfScope() {
   if (idx < 0) return;
   hipEvent_t e = prof_event(h);
-  hipEventRecord(e, stream);
+  hipEventRecord(e, h->stream);
   h->timers[idx].ev.push_back(e);
   h->prof_tail = e;
-  h->prof_tail_stream = stream;
 }
 void orbx_prof_begin_call(orbx_handle* h) { (void)h; }   // events accumulate until they are read
 void orbx_prof_end_call(orbx_handle* h) { (void)h; }
@@ -165,11 +163,7 @@ void orbx_destroy(orbx_handle* h) {
   for (DevBuf& b : h->ws_pnp) if (b.p) hipFree(b.p);
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
   for (int i = 0; i < 2; ++i) { if (h->ev_in[i]) hipEventDestroy(h->ev_in[i]); if (h->ev_comp[i]) hipEventDestroy(h->ev_comp[i]); if (h->ev_out[i]) hipEventDestroy(h->ev_out[i]); }
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  if (h->ev_join) hipEventDestroy(h->ev_join);
   if (h->ba_up_event) hipEventDestroy(h->ba_up_event);
-  for (hipEvent_t e : h->ev_stag) if (e) hipEventDestroy(e);
-  if (h->s_aux) hipStreamDestroy(h->s_aux);
   if (h->s_in) hipStreamDestroy(h->s_in);
   if (h->s_out) hipStreamDestroy(h->s_out);
   for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
@@ -230,7 +224,6 @@ int orbx_get_kernel_times(orbx_handle* h, orbx_kernel_time* out, int cap) {
   if (!h) return ORBX_ERR_INVALID;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
-  if (h->s_aux) hipStreamSynchronize(h->s_aux);
   int n = 0;
   for (auto& t : h->timers) {
     if (t.ev.empty()) continue;
@@ -678,47 +671,6 @@ int orbx_process_stereo_batch_device(orbx_handle* h, const uint8_t* d_images, in
     return orbx_fail(h, ORBX_ERR_INVALID, "batch %d outside 0..max_batch %d", batch, h->max_batch);
   if (!d_matches || !d_nmatches || !d_points || !d_has_point)
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch_device: bad argument");
-  // Two-stream form (ORBX_STAGGER=<chunks>, 2..8; experimental, round 5): the batch as `chunks` ranges of pairs dealt alternately to the
-  // handle's stream and a second one, chunk c + 1 starting behind chunk c's pyramid launches, so that one range's latency-bound
-  // launches (resize chain, Harris, ordering, the matcher's three) are in flight while the other range is in its issue-bound FAST /
-  // describe kernels.  Pairs are independent and every workspace is indexed by image or pair: the results are those of one range over
-  // the whole batch, bit for bit.  The handle's stream waits for the second one before the call returns (work the caller enqueues on
-  // orbx_stream() afterwards sees every result).  MEASURED NEGATIVE (profiles/r05_stagger_two_streams_negative.txt): 145.2 k frames/s on one
-  // stream, 144.6 k as 2 ranges, 139.5 k as 4 — under overlap every kernel stretches by what the other stream takes (describe x 2.1, FAST
-  // x 1.6, Harris x 1.5, resize x 1.8): the latency-bound launches do not hide under the issue-bound ones, the chip is shared.  Off by default.
-  const int stagger = [] { const char* e = getenv("ORBX_STAGGER"); const int v = e ? atoi(e) : 0; return v >= 2 && v <= 8 ? v : 0; }();   // (read per call, as ORBX_FORK_BLUR)
-  static const bool stagger_prof = getenv("ORBX_STAGGER_PROFILE") != nullptr;    // (per-kernel events on both streams: they then time the overlap, not the kernels)
-  static const bool desc_unfused = getenv("ORBX_DESC_UNFUSED") != nullptr;
-  if (stagger && batch >= 2 * stagger && (!h->profiling || stagger_prof) && !desc_unfused) {
-    if (!d_images || !d_kp || !d_desc || !d_nkp || cap_kp < 1)
-      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch_device: bad argument");
-    if (w < 64 || h_px < 64 || w > h->max_w || h_px > h->max_h || stride < (size_t)w)
-      return orbx_fail(h, ORBX_ERR_INVALID, "image %dx%d (stride %zu) outside the handle's bounds %dx%d", w, h_px, stride, h->max_w, h->max_h);
-    ORBX_HIP(h, hipSetDevice(h->device));
-    if (!h->s_aux) {
-      ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_aux, hipStreamNonBlocking));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-    for (auto& e : h->ev_stag) if (!e) ORBX_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (int rc = orb_extract_prepare(h, 2 * batch, w, h_px)) return rc;
-    // (the matcher's workspace is sized before the streams fork: orbx_reserve may synchronise)
-    if (int rc = launch_stereo_match_range(h, h->stream, batch, 0, 0, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point)) return rc;
-    ORBX_HIP(h, hipEventRecord(h->ev_fork, h->stream));
-    ORBX_HIP(h, hipStreamWaitEvent(h->s_aux, h->ev_fork, 0));
-    int p0 = 0;
-    for (int c = 0; c < stagger; ++c) {
-      const int p1 = (int)((long long)batch * (c + 1) / stagger);
-      hipStream_t st = (c & 1) ? h->s_aux : h->stream;
-      if (c > 0) ORBX_HIP(h, hipStreamWaitEvent(st, h->ev_stag[(c - 1) & 3], 0));     // behind the previous chunk's pyramid
-      if (int rc = orb_extract_range(h, st, d_images, 2 * batch, 2 * p0, 2 * (p1 - p0), w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp, h->ev_stag[c & 3])) return rc;
-      if (int rc = launch_stereo_match_range(h, st, batch, p0, p1 - p0, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point)) return rc;
-      p0 = p1;
-    }
-    ORBX_HIP(h, hipEventRecord(h->ev_join, h->s_aux));
-    ORBX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    return ORBX_OK;
-  }
   if (int rc = orbx_extract_batch_device(h, d_images, 2 * batch, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp))
     return rc;
   return launch_stereo_match(h, batch, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point);
@@ -1090,11 +1042,10 @@ int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orb
     if (split) {
       size_t total = 0, run = 0;
       for (int i = 0; i < n_windows; ++i) total += (size_t)w[i].N;
-      // the first part's upload is the one nothing hides (the second part's travels under the first part's kernels): ORBX_BA_SPLIT_FRAC
-      // (default 0.5) moves the cut for A/B runs
-      static const double split_frac = [] { const char* e = getenv("ORBX_BA_SPLIT_FRAC"); const double f = e ? atof(e) : 0.5; return f > 0.05 && f < 0.95 ? f : 0.5; }();
+      // the first part's upload is the one nothing hides (the second part's travels under the first part's kernels); the cut at half the
+      // observations
       int n0 = 0;
-      while (n0 < n_windows - 1 && (double)(run + (size_t)w[n0].N) - 0.5 * (double)w[n0].N <= split_frac * (double)total) run += (size_t)w[n0++].N;
+      while (n0 < n_windows - 1 && (double)(run + (size_t)w[n0].N) - 0.5 * (double)w[n0].N <= 0.5 * (double)total) run += (size_t)w[n0++].N;
       n0 = std::max(1, std::min(n_windows - 1, n0));
       int rc1 = ORBX_OK;
       // the two halves preprocess at the same time: half the cores each  (one after the other with all the cores each, so that the first

@@ -152,7 +152,7 @@ struct OrbSrc {
   int l0_pitch;
   int pad_;
   uint8_t* pyr;
-  uint8_t* blur;
+  uint8_t* blur;          // blurred levels: set by orbx_debug_read_level(which = 1) only (the product path keeps no blurred pyramid)
 };
 
 // device status word bits (sticky, cleared by orbx_check_status)
@@ -207,10 +207,6 @@ struct orbx_handle {
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
   DevBuf ws_pipe[2][8];
-  // second stream of the extractor: the blur runs beside the FAST -> Harris -> ordering chain (launch_orb_extract)
-  hipStream_t s_aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_stag[4] = {nullptr, nullptr, nullptr, nullptr};   // two-stream form of orbx_process_stereo_batch_device: chunk c + 1 starts behind chunk c's pyramid
   // BA
   orbx_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
@@ -238,7 +234,6 @@ struct orbx_handle {
   std::vector<hipEvent_t> event_pool;
   size_t event_next = 0;
   hipEvent_t prof_tail = nullptr;          // end event of the last profiling scope (may start the next one)
-  hipStream_t prof_tail_stream = nullptr;
 };
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
@@ -252,12 +247,11 @@ int orbx_reserve(orbx_handle* h, DevBuf& b, size_t bytes);
                        __FILE__, __LINE__);                                                 \
   } while (0)
 
-// profiling scope: records a start/stop event pair around a launch when profiling is on
+// profiling scope: records a start/stop event pair on the handle's stream around a launch when profiling is on
 struct ProfScope {
   orbx_handle* h;
   int idx;
-  hipStream_t stream;   // the stream the bracketed launches go to (default: the handle's)
-  ProfScope(orbx_handle* h, const char* name, hipStream_t stream = nullptr, bool chained = false);
+  ProfScope(orbx_handle* h, const char* name, bool chained = false);
   ~ProfScope();
 };
 void orbx_prof_begin_call(orbx_handle* h);
@@ -268,9 +262,6 @@ void orbx_prof_end_call(orbx_handle* h);
 int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
                         const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
                         double* d_points, uint8_t* d_has_point);
-int launch_stereo_match_range(orbx_handle* h, hipStream_t st, int batch_total, int pair0, int batch, const orbx_keypoint* d_kp,
-                              const uint8_t* d_desc, const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
-                              double* d_points, uint8_t* d_has_point);
 int launch_crosscheck(orbx_handle* h, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                       orbx_dmatch* d_out, int* d_n_out);
 int launch_hamming_batch(orbx_handle* h, const uint8_t* d_a, const uint8_t* d_b, int n, uint32_t* d_out);
@@ -293,12 +284,6 @@ int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_p
 int orb_prepare_geometry(orbx_handle* h, int w, int h_px);
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,
                        size_t stride, orbx_keypoint* d_kp, uint8_t* d_desc, int* d_nkp, int cap_kp);
-// The same over the images [img0, img0 + n) of a call that carries n_images in all, on stream `st`: orb_extract_prepare sizes the
-// workspaces for the whole call and clears its counters (on the handle's stream), orb_extract_range then runs one range of it; `after_resize`
-// (optional) is recorded on `st` behind the range's pyramid launches.
-int orb_extract_prepare(orbx_handle* h, int n_images, int w, int h_px);
-int orb_extract_range(orbx_handle* h, hipStream_t st, const uint8_t* d_images, int n_images, int img0, int n, int w, int h_px, size_t stride,
-                      orbx_keypoint* d_kp, uint8_t* d_desc, int* d_nkp, int cap_kp, hipEvent_t after_resize);
 // BA (ba_kernels.hip)
 int ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
                     const double* poses_cw, int F, const double* fixed_poses_cw, int M,

@@ -97,51 +97,6 @@ def test_large_batch_equals_single_pair_other_sizes(pkg, w, hh, B):
         hb.close(); h1.close()
 
 
-def test_optional_blur_fork_gives_identical_results(full_batch):
-    """ORBX_FORK_BLUR=1 runs the blur on a second stream beside the FAST chain (read at launch time): same bytes out."""
-    import os
-    import torch
-    h, imgs, out, snap, B, cap = full_batch
-    os.environ["ORBX_FORK_BLUR"] = "1"
-    try:
-        for _ in range(3):
-            h.process_stereo_batch_device(imgs, out)
-        h.check_status()
-    finally:
-        del os.environ["ORBX_FORK_BLUR"]
-    nk = snap["nkp"].cpu().numpy(); nm = snap["nmatches"].cpu().numpy()
-    assert torch.equal(out["nkp"], snap["nkp"]) and torch.equal(out["nmatches"], snap["nmatches"])
-    for b in range(0, B, 9):
-        for s in range(2):
-            assert torch.equal(out["kp"][b, s, :nk[b, s]].view(torch.int32), snap["kp"][b, s, :nk[b, s]].view(torch.int32))
-            assert torch.equal(out["desc"][b, s, :nk[b, s]], snap["desc"][b, s, :nk[b, s]])
-        assert torch.equal(out["matches"][b, :nm[b]], snap["matches"][b, :nm[b]])
-
-
-def test_two_stream_ranges_give_identical_results(full_batch):
-    """ORBX_STAGGER=<n> (read at call time): the batch as n ranges of pairs on two streams, each range started behind the previous one's
-    pyramid launches (a measured negative for throughput, kept opt-in): same bytes out as the one-stream call."""
-    import os
-    import torch
-    h, imgs, out, snap, B, cap = full_batch
-    nk = snap["nkp"].cpu().numpy(); nm = snap["nmatches"].cpu().numpy()
-    for n in ("2", "3"):
-        os.environ["ORBX_STAGGER"] = n
-        try:
-            for _ in range(2):
-                h.process_stereo_batch_device(imgs, out)
-            h.check_status()
-        finally:
-            del os.environ["ORBX_STAGGER"]
-        assert torch.equal(out["nkp"], snap["nkp"]) and torch.equal(out["nmatches"], snap["nmatches"])
-        for b in range(0, B, 7):
-            for s in range(2):
-                assert torch.equal(out["kp"][b, s, :nk[b, s]].view(torch.int32), snap["kp"][b, s, :nk[b, s]].view(torch.int32))
-                assert torch.equal(out["desc"][b, s, :nk[b, s]], snap["desc"][b, s, :nk[b, s]])
-            assert torch.equal(out["matches"][b, :nm[b]], snap["matches"][b, :nm[b]])
-            assert torch.equal(out["has_point"][b, :nk[b, 0]], snap["has_point"][b, :nk[b, 0]])
-
-
 def test_pair_result_independent_of_batch_position(full_batch, pkg):
     """reversing the batch order permutes the results and nothing else (no cross-talk through shared workspaces,
     the XCD-aware block mapping or the atomically appended candidate lists)"""
