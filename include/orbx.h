@@ -594,6 +594,70 @@ int orbx_pnp_ransac_batch_device(orbx_handle* h, const orbx_camera* cam, const o
                                  const int* d_offsets, const double* d_pts3d, const float* d_pts2d, const double* d_priors_wc,
                                  double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_results);
 
+/* ---- pose-inertial optimization for tracking (src/optimizer/pose_inertial_optim.rs) ------------------------------
+ * pose_inertial_optimization (:94-216), as the tracker's refine_with_imu calls it (src/tracking/tracker.rs:476-546): the current
+ * frame's 15 parameters [scaled_axis(q_wc) | t_wc | v | b_g | b_a] refined against fixed map points and the IMU preintegration
+ * from the previous keyframe.  Per iteration (at most max_iterations): chi2 thresholds interpolated from *_init to *_final; two
+ * visual rows per masked-in observation, e = uv - proj(T_wc^-1 X) with the reference's 2x6 camera-frame block (:250-349; (100,100)
+ * and a zero block where z_c <= 0.001); the 9 rows of compute_imu_residual times imu_weight with a forward-difference Jacobian over
+ * all 15 parameters (eps 1e-6); fewer than 5 masked-in observations end the loop before the solve; H = J^T J damped by
+ * H_ii += 1e-3 max(H_ii, 1e-6), solved by partial-pivoting LU (an exactly zero pivot ends the loop); params += delta; every
+ * observation reclassified: inlier = |e|^2 < (is_stereo ? chi2_stereo : chi2_mono).  Gravity (0, 0, -9.81).  The residual does
+ * not depend on the bias, so the bias comes back with its input value.  The reference's visual block is the true derivative only
+ * at R_wc = I; it is reproduced as written.
+ * Poses are 7 doubles (qw,qx,qy,qz,tx,ty,tz), T_wc.  bias: gyro (3) then accel (3).  preint [11]: delta_rot qw,qx,qy,qz |
+ * delta_vel | delta_pos | dt (the layout of orbx_ba_solve_inertial).  The tracker's own guard (fewer than 10 observations: no call)
+ * stays the caller's. */
+enum {
+  ORBX_POSE_INERTIAL_OK = 0,        /* all max_iterations iterations ran                                   */
+  ORBX_POSE_INERTIAL_TOO_FEW = 1,   /* the loop ended with fewer than 5 masked-in observations              */
+  ORBX_POSE_INERTIAL_SINGULAR = 2   /* the loop ended on an exactly zero pivot of the LU                    */
+};
+/* orbx_default_pose_inertial_config: 4 iterations, chi2 12.0 / 15.6 (mono / stereo) falling to 5.991 / 7.815, imu_weight 1.0
+ * (pose_inertial_optim.rs:34-45).  Accepted ranges: 0 <= max_iterations <= 64, thresholds > 0, imu_weight finite and >= 0;
+ * other values -> ORBX_ERR_INVALID. */
+typedef struct {
+  int max_iterations;
+  double chi2_mono_init, chi2_stereo_init, chi2_mono_final, chi2_stereo_final, imu_weight;
+} orbx_pose_inertial_config;
+/* One problem's record: why the loop ended (ORBX_POSE_INERTIAL_*), the popcount of the final mask (n when no reclassification
+ * ran), n, and the iterations begun (a break counts its iteration). */
+typedef struct {
+  int status, num_inliers, num_observations, iterations;
+} orbx_pose_inertial_result;
+void orbx_default_pose_inertial_config(orbx_pose_inertial_config* cfg);
+
+/* One problem in host memory, synchronous.  pose_wc [7], velocity [3], bias [6]: the initial state; prev_kf_pose_wc [7],
+ * prev_kf_velocity [3], preint [11]; pts3d [n][3] f64 world points, pts2d [n][2] f32 pixels (the keypoints' positions), is_stereo
+ * [n] u8 (nonzero: the feature has a camera-frame point).  Outputs pose_out [7], velocity_out [3], bias_out [6], inlier_out [n] u8
+ * (the final mask; may be NULL), result [1]. */
+int orbx_pose_inertial_optimize(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, const double* pose_wc,
+                                const double* velocity, const double* bias, const double* prev_kf_pose_wc, const double* prev_kf_velocity,
+                                const double* preint, int n, const double* pts3d, const float* pts2d, const uint8_t* is_stereo,
+                                double* pose_out, double* velocity_out, double* bias_out, uint8_t* inlier_out,
+                                orbx_pose_inertial_result* result);
+/* n_problems independent problems in host memory, one upload and one download: problem p owns observations
+ * [offsets[p], offsets[p+1]) of pts3d / pts2d / is_stereo / inlier_out (offsets [n_problems+1], ascending from 0, as
+ * orbx_pnp_ransac_batch); poses_wc / prev_kf_poses_wc / poses_out [n_problems][7], velocities / prev_kf_velocities /
+ * velocities_out [n_problems][3], biases / biases_out [n_problems][6], preints [n_problems][11], results [n_problems].  inlier_out
+ * may be NULL.  Each problem's result equals orbx_pose_inertial_optimize on it, byte for byte.  Synchronous; caller-owned buffers. */
+int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, int n_problems,
+                             const int* offsets, const double* pts3d, const float* pts2d, const uint8_t* is_stereo,
+                             const double* poses_wc, const double* velocities, const double* biases, const double* prev_kf_poses_wc,
+                             const double* prev_kf_velocities, const double* preints, double* poses_out, double* velocities_out,
+                             double* biases_out, uint8_t* inlier_out, orbx_pose_inertial_result* results);
+/* The same with every array in device memory (the caller's; the library only reads the inputs and writes the outputs),
+ * asynchronous on the handle's stream.  d_inlier_out is required: it holds the mask between iterations.  The layout is PnP's:
+ * d_offsets / d_pts3d / d_pts2d of an orbx_pnp_ransac_batch_device call and its d_poses_wc_out (as d_poses_wc) can be passed
+ * straight in, with no host round trip.  One workgroup per problem; no limit on n.  d_offsets must be ascending from 0 (they are
+ * trusted: they index the observation arrays). */
+int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, int n_problems,
+                                    const int* d_offsets, const double* d_pts3d, const float* d_pts2d, const uint8_t* d_is_stereo,
+                                    const double* d_poses_wc, const double* d_velocities, const double* d_biases,
+                                    const double* d_prev_kf_poses_wc, const double* d_prev_kf_velocities, const double* d_preints,
+                                    double* d_poses_out, double* d_velocities_out, double* d_biases_out, uint8_t* d_inlier_out,
+                                    orbx_pose_inertial_result* d_results);
+
 /* Per-kernel device time for bench.py's roofline block.  While profiling is on
  * (orbx_set_profiling), every launch is bracketed by HIP events on the handle's stream;
  * orbx_get_kernel_times synchronises, fills up to `cap` entries with the durations summed

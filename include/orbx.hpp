@@ -14,6 +14,7 @@
 //   orbx::VisualObservation/ProblemData/ResultData   local_ba_lm.rs:48-93
 //   orbx::solve_visual_ba                   local_ba_lm.rs:912-1098
 //   orbx::PnPResult / solve_pnp_ransac_detailed    src/geometry/pnp.rs:12-20, :100-134
+//   orbx::PoseInertialConfig/Result, PoseObservation, pose_inertial_optimization   src/optimizer/pose_inertial_optim.rs:19-216
 //
 // Errors: the reference propagates `anyhow::Error` with `?` — here orbx::Error is thrown; where the
 // reference returns `None` (solve_visual_ba) std::nullopt is returned.  Everything computes on the GPU.
@@ -708,6 +709,72 @@ inline std::optional<InertialBAResultData> solve_inertial_ba(Handle& h, const In
   }
   for (int j = 0; j < M; ++j) r.optimized_points[problem.mp_ids[(size_t)j]] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
   r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
+  return r;
+}
+
+// ---- pose-inertial optimization for tracking (src/optimizer/pose_inertial_optim.rs) ----------------------------------
+struct PoseInertialConfig {   // pose_inertial_optim.rs:19-45
+  size_t max_iterations = 4;
+  double chi2_mono_init = 12.0, chi2_stereo_init = 15.6, chi2_mono_final = 5.991, chi2_stereo_final = 7.815, imu_weight = 1.0;
+};
+
+struct PoseInertialResult {   // :48-62; pose is T_wc
+  SE3 pose;
+  std::array<double, 3> velocity{0, 0, 0};
+  ImuBias bias;
+  size_t num_inliers = 0, num_observations = 0, iterations = 0;
+};
+
+struct PoseObservation {   // :65-74.  uv: the keypoint's position, an f32 pair (refine_with_imu widens kp.pt() to f64, tracker.rs:508)
+  std::array<float, 2> uv;
+  std::array<double, 3> point_world;
+  bool is_stereo;
+  size_t index;
+};
+
+// pose_inertial_optim.rs:94-216, the specification of orbx_pose_inertial_optimize (orbx.h).  prev_kf_bias is ignored, as in the
+// reference.  An out-of-range config (max_iterations > 64, thresholds <= 0, imu_weight negative or not finite) throws orbx::Error.
+inline PoseInertialResult pose_inertial_optimization(Handle& h, const SE3& initial_pose, const std::array<double, 3>& initial_velocity,
+                                                     const ImuBias& initial_bias, const SE3& prev_kf_pose,
+                                                     const std::array<double, 3>& prev_kf_velocity, const ImuBias& /*prev_kf_bias*/,
+                                                     const PreintegratedState& preintegrated, const std::vector<PoseObservation>& observations,
+                                                     const CameraModel& camera, const PoseInertialConfig& config) {
+  const int n = (int)observations.size();
+  const orbx_camera cam = camera.c();
+  const orbx_pose_inertial_config cfg{(int)std::min<size_t>(config.max_iterations, 1u << 30), config.chi2_mono_init, config.chi2_stereo_init,
+                                      config.chi2_mono_final, config.chi2_stereo_final, config.imu_weight};
+  const auto pose7 = [](const SE3& s, double* o) {
+    for (int k = 0; k < 4; ++k) o[k] = s.rotation[k];
+    for (int k = 0; k < 3; ++k) o[4 + k] = s.translation[k];
+  };
+  double pose[7], prev[7], bias[6], pre[11];
+  pose7(initial_pose, pose);
+  pose7(prev_kf_pose, prev);
+  for (int k = 0; k < 3; ++k) { bias[k] = initial_bias.gyro[k]; bias[3 + k] = initial_bias.accel[k]; }
+  for (int k = 0; k < 4; ++k) pre[k] = preintegrated.delta_rot[k];
+  for (int k = 0; k < 3; ++k) { pre[4 + k] = preintegrated.delta_vel[k]; pre[7 + k] = preintegrated.delta_pos[k]; }
+  pre[10] = preintegrated.dt;
+  std::vector<double> p3(3 * (size_t)std::max(n, 1));
+  std::vector<float> p2(2 * (size_t)std::max(n, 1));
+  std::vector<uint8_t> st(std::max(n, 1));
+  for (int i = 0; i < n; ++i) {
+    const PoseObservation& o = observations[(size_t)i];
+    for (int k = 0; k < 3; ++k) p3[3 * (size_t)i + k] = o.point_world[k];
+    p2[2 * (size_t)i] = o.uv[0]; p2[2 * (size_t)i + 1] = o.uv[1];
+    st[(size_t)i] = o.is_stereo ? 1 : 0;
+  }
+  double po[7], vo[3], bo[6];
+  orbx_pose_inertial_result res;
+  h.check(orbx_pose_inertial_optimize(h.get(), &cam, &cfg, pose, initial_velocity.data(), bias, prev, prev_kf_velocity.data(), pre, n,
+                                      p3.data(), p2.data(), st.data(), po, vo, bo, nullptr, &res));
+  PoseInertialResult r;
+  r.pose.rotation = {po[0], po[1], po[2], po[3]};
+  r.pose.translation = {po[4], po[5], po[6]};
+  r.velocity = {vo[0], vo[1], vo[2]};
+  for (int k = 0; k < 3; ++k) { r.bias.gyro[k] = bo[k]; r.bias.accel[k] = bo[3 + k]; }
+  r.num_inliers = (size_t)res.num_inliers;
+  r.num_observations = (size_t)res.num_observations;
+  r.iterations = (size_t)res.iterations;
   return r;
 }
 

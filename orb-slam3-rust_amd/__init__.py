@@ -12,5 +12,7 @@ from .api import (  # noqa: F401
     solve_visual_ba, GlobalBAObservation, GlobalBAProblemData, GlobalBAResult, flatten_global_ba_problem, se3_inverse,
     solve_global_ba, OrbVocabulary, EurocDataset, png_decode_gray8, LocalInertialBAConfig, InertialVisualObs, ImuEdgeData, InertialBAProblemData,
     InertialBAResultData, flatten_inertial_ba_problem, solve_inertial_ba, MapSnapshot, local_bundle_adjustment, run_global_ba, KeyFrame, BaBatch,
-    PnPConfig, PnPResult, PNP_RESULT, PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N, solve_pnp_ransac, solve_pnp_ransac_detailed)
+    PnPConfig, PnPResult, PNP_RESULT, PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N, solve_pnp_ransac, solve_pnp_ransac_detailed,
+    PoseInertialConfig, PoseInertialResult, POSE_INERTIAL_RESULT, POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR,
+    pose_inertial_optimization)
 from .build import LIB_PATH, build  # noqa: F401

@@ -14,6 +14,8 @@ written in Python with the reference's own names and argument meaning:
     VisualBAProblemData/Result   local_ba_lm.rs:48-93    VisualBAProblemData / VisualBAResultData
     solve_visual_ba              local_ba_lm.rs:912      solve_visual_ba
     solve_pnp_ransac[_detailed]  pnp.rs:29-134           solve_pnp_ransac[_detailed] / Handle.solve_pnp_ransac_batch
+    PoseInertialConfig/Result    pose_inertial_optim.rs:19-62    PoseInertialConfig / PoseInertialResult
+    pose_inertial_optimization   pose_inertial_optim.rs:94-216   pose_inertial_optimization / Handle.pose_inertial_optimization[_batch]
 
 Everything computes on the GPU through liborbx_hip.so; there is no CPU fallback, and a missing
 library or device raises.
@@ -82,6 +84,7 @@ ABI_SYMBOLS = [
     "orbx_set_profiling", "orbx_set_profiling_only", "orbx_get_kernel_times", "orbx_debug_read_level",
     "orbx_debug_read_candidates",
     "orbx_default_pnp_config", "orbx_pnp_ransac", "orbx_pnp_ransac_batch", "orbx_pnp_ransac_batch_device",
+    "orbx_default_pose_inertial_config", "orbx_pose_inertial_optimize", "orbx_pose_inertial_batch", "orbx_pose_inertial_batch_device",
 ]
 
 
@@ -151,6 +154,22 @@ class _PnpResult(C.Structure):
 PNP_RESULT = np.dtype([("status", "<i4"), ("n_inliers", "<i4"), ("ransac_inliers", "<i4"), ("best_hypothesis", "<i4"),
                        ("hypotheses_evaluated", "<i4"), ("refine_iterations", "<i4"), ("final_rms", "<f8")])
 PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N = 0, 1, 2, 3
+
+
+class _PoseInertialConfig(C.Structure):
+    """orbx_pose_inertial_config (include/orbx.h)"""
+    _fields_ = [("max_iterations", C.c_int), ("chi2_mono_init", C.c_double), ("chi2_stereo_init", C.c_double),
+                ("chi2_mono_final", C.c_double), ("chi2_stereo_final", C.c_double), ("imu_weight", C.c_double)]
+
+
+class _PoseInertialResult(C.Structure):
+    """orbx_pose_inertial_result (include/orbx.h)"""
+    _fields_ = [("status", C.c_int), ("num_inliers", C.c_int), ("num_observations", C.c_int), ("iterations", C.c_int)]
+
+
+# orbx_pose_inertial_result as a numpy record (the batch forms' results array)
+POSE_INERTIAL_RESULT = np.dtype([("status", "<i4"), ("num_inliers", "<i4"), ("num_observations", "<i4"), ("iterations", "<i4")])
+POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR = 0, 1, 2
 
 
 SHOULD_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -317,6 +336,40 @@ class PnPResult:
 
 def _pnp_stats(rec):
     return {k: (float(rec[k]) if k == "final_rms" else int(rec[k])) for k in PNP_RESULT.names}
+
+
+@dataclass
+class PoseInertialConfig:
+    """pose_inertial_optim.rs:19-45: 4 iterations, chi2 12.0 / 15.6 (mono / stereo) falling to 5.991 / 7.815, imu_weight 1.0."""
+    max_iterations: int = 4
+    chi2_mono_init: float = 12.0
+    chi2_stereo_init: float = 15.6
+    chi2_mono_final: float = 5.991
+    chi2_stereo_final: float = 7.815
+    imu_weight: float = 1.0
+
+    def _c(self):
+        return _PoseInertialConfig(self.max_iterations, self.chi2_mono_init, self.chi2_stereo_init, self.chi2_mono_final,
+                                   self.chi2_stereo_final, self.imu_weight)
+
+
+@dataclass
+class PoseInertialResult:
+    """pose_inertial_optim.rs:48-62: pose (T_wc, 7 doubles qw,qx,qy,qz,tx,ty,tz), velocity [3], bias [6] (gyro, accel), num_inliers,
+    num_observations, iterations; inlier_mask [n] bool (the final mask) and status (POSE_INERTIAL_*: why the loop ended) besides."""
+    pose: np.ndarray
+    velocity: np.ndarray
+    bias: np.ndarray
+    num_inliers: int
+    num_observations: int
+    iterations: int
+    inlier_mask: np.ndarray
+    status: int
+
+
+def _pose_inertial_state(problem):
+    """(pose_wc [7], velocity [3], bias [6], prev_kf_pose_wc [7], prev_kf_velocity [3], preint [11]) as f64 arrays"""
+    return [np.ascontiguousarray(np.asarray(x, np.float64).reshape(k)) for x, k in zip(problem, (7, 3, 6, 7, 3, 11))]
 
 
 @dataclass
@@ -515,6 +568,63 @@ class Handle:
                                                          _vp(points3d), _vp(points2d), _vp(priors_wc), _vp(poses), _vp(inl), _vp(err),
                                                          _vp(res)))
         return poses[:P], inl[:N], err[:N], res[:P]
+
+    def pose_inertial_optimization(self, camera, pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d, points2d,
+                                   is_stereo, cfg: PoseInertialConfig = None) -> PoseInertialResult:
+        """pose_inertial_optim.rs:94-216 on one problem: the initial state pose_wc [7] (T_wc), velocity [3], bias [6]; the previous
+        keyframe's pose [7] and velocity [3]; preint [11] (delta_rot qw,qx,qy,qz | delta_vel | delta_pos | dt); points3d [n,3] f64 world
+        points, points2d [n,2] (taken as f32, the keypoints' positions), is_stereo [n] bool."""
+        return self.pose_inertial_optimization_batch(camera, [(pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d,
+                                                               points2d, is_stereo)], cfg)[0]
+
+    def pose_inertial_optimization_batch(self, camera, problems, cfg: PoseInertialConfig = None) -> List[PoseInertialResult]:
+        """Many problems [(pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d, points2d, is_stereo), ...] in
+        one call (one upload, one download); each result equals the single-problem call's byte for byte."""
+        P = len(problems)
+        states = [_pose_inertial_state(pr[:6]) for pr in problems]
+        pts3d = [np.ascontiguousarray(pr[6], np.float64).reshape(-1, 3) for pr in problems]
+        pts2d = [np.ascontiguousarray(pr[7], np.float32).reshape(-1, 2) for pr in problems]
+        stereo = [np.ascontiguousarray(np.asarray(pr[8]).reshape(-1) != 0, np.uint8) for pr in problems]
+        if any(len(a) != len(b) or len(a) != len(c) for a, b, c in zip(pts3d, pts2d, stereo)):
+            raise ValueError("points3d, points2d and is_stereo differ in length")
+        off = np.zeros(P + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in pts3d])
+        N = int(off[-1])
+        p3 = np.concatenate(pts3d) if N else np.zeros((1, 3), np.float64)
+        p2 = np.concatenate(pts2d) if N else np.zeros((1, 2), np.float32)
+        st = np.concatenate(stereo) if N else np.zeros(1, np.uint8)
+        ins = [np.ascontiguousarray(np.stack([s[k] for s in states]) if P else np.zeros((1, w)), np.float64)
+               for k, w in enumerate((7, 3, 6, 7, 3, 11))]
+        poses = np.zeros((max(P, 1), 7)); vel = np.zeros((max(P, 1), 3)); bias = np.zeros((max(P, 1), 6))
+        inl = np.zeros(max(N, 1), np.uint8)
+        res = np.zeros(max(P, 1), POSE_INERTIAL_RESULT)
+        c = (cfg or PoseInertialConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_pose_inertial_batch(self._h, C.byref(cam), C.byref(c), C.c_int(P), _vp(off), _vp(p3), _vp(p2), _vp(st),
+                                                     *[_vp(a) for a in ins], _vp(poses), _vp(vel), _vp(bias), _vp(inl), _vp(res)))
+        return [PoseInertialResult(poses[p].copy(), vel[p].copy(), bias[p].copy(), int(res[p]["num_inliers"]), int(res[p]["num_observations"]),
+                                   int(res[p]["iterations"]), inl[off[p]:off[p + 1]].astype(bool), int(res[p]["status"])) for p in range(P)]
+
+    def pose_inertial_optimization_batch_device(self, camera, offsets, points3d, points2d, is_stereo, poses_wc, velocities, biases,
+                                                prev_kf_poses_wc, prev_kf_velocities, preints, cfg: PoseInertialConfig = None):
+        """Device-resident batch: torch CUDA tensors offsets [P+1] int32 (ascending from 0), points3d [N,3] f64, points2d [N,2] f32,
+        is_stereo [N] u8, poses_wc [P,7], velocities [P,3], biases [P,6], prev_kf_poses_wc [P,7], prev_kf_velocities [P,3], preints
+        [P,11] f64 — the layout of solve_pnp_ransac_batch_device, whose offsets / points and output poses can be passed straight in.
+        Returns (poses [P,7], velocities [P,3], biases [P,6] f64, inlier [N] u8, results [P,16] u8 — view the bytes as
+        POSE_INERTIAL_RESULT); asynchronous on the handle's stream."""
+        import torch
+        P, N = int(offsets.shape[0]) - 1, int(points3d.shape[0])
+        dev = points3d.device
+        poses = torch.empty((max(P, 1), 7), dtype=torch.float64, device=dev)
+        vel = torch.empty((max(P, 1), 3), dtype=torch.float64, device=dev)
+        bias = torch.empty((max(P, 1), 6), dtype=torch.float64, device=dev)
+        inl = torch.empty(max(N, 1), dtype=torch.uint8, device=dev)
+        res = torch.empty((max(P, 1), POSE_INERTIAL_RESULT.itemsize), dtype=torch.uint8, device=dev)
+        ins = (offsets, points3d, points2d, is_stereo, poses_wc, velocities, biases, prev_kf_poses_wc, prev_kf_velocities, preints)
+        c = (cfg or PoseInertialConfig())._c(); cam = camera._c()
+        self._after_torch(*ins, poses, vel, bias, inl, res)
+        self._check(self._L.orbx_pose_inertial_batch_device(self._h, C.byref(cam), C.byref(c), C.c_int(P), *[_vp(t) for t in ins], _vp(poses),
+                                                            _vp(vel), _vp(bias), _vp(inl), _vp(res)))
+        return poses[:P], vel[:P], bias[:P], inl[:N], res[:P]
 
     def search_for_triangulation(self, camera, kp1, desc1, mp1, stereo1, kp2, desc2, mp2, pose1_wc, pose2_wc, max_dist=50):
         """triangulation.rs:401-527.  Returns [(idx1, idx2)] as an int32 [n,2] array, ascending idx1."""
@@ -959,6 +1069,17 @@ def solve_pnp_ransac_detailed(points3d, points2d, camera: CameraModel, prior=Non
 def solve_pnp_ransac(points3d, points2d, camera: CameraModel, prior=None) -> np.ndarray:
     """pnp.rs:29-97: the pose (T_wc, 7 doubles) alone."""
     return solve_pnp_ransac_detailed(points3d, points2d, camera, prior).pose
+
+
+def pose_inertial_optimization(initial_pose, initial_velocity, initial_bias, prev_kf_pose, prev_kf_velocity, prev_kf_bias, preintegrated,
+                               observations, camera: CameraModel, config: PoseInertialConfig = None) -> PoseInertialResult:
+    """pose_inertial_optim.rs:94-216 in the reference's argument order.  Poses T_wc (7 doubles), biases [6] (gyro, accel), preintegrated
+    [11] (delta_rot qw,qx,qy,qz | delta_vel | delta_pos | dt); observations = (points3d [n,3], points2d [n,2], is_stereo [n]) — the
+    PoseObservation fields uv / point_world / is_stereo as arrays.  prev_kf_bias is accepted and ignored, as in the reference."""
+    del prev_kf_bias
+    points3d, points2d, is_stereo = observations
+    return _handle().pose_inertial_optimization(camera, initial_pose, initial_velocity, initial_bias, prev_kf_pose, prev_kf_velocity,
+                                                preintegrated, points3d, points2d, is_stereo, config)
 
 
 @dataclass

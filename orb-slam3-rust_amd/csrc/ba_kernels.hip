@@ -3107,41 +3107,6 @@ __global__ __launch_bounds__(BA_DECIDE_THREADS) void ba_decide_kernel(const BaWi
 // ---- inertial terms (src/optimizer/local_inertial_ba.rs:661-698, :806-880; src/optimizer/imu_factors.rs:66-103) --------------------
 // Device parameter layout in inertial mode: [6K T_wc pose | 3M points | 9K velocity, gyro bias, accel bias].
 
-__device__ __forceinline__ void dev_scaled_axis(const double* q, double* o) {   // nalgebra UnitQuaternion::scaled_axis
-  double v0 = q[1], v1 = q[2], v2 = q[3];
-  if (!(q[0] >= 0.0)) { v0 = -v0; v1 = -v1; v2 = -v2; }
-  const double n = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-  if (n > 0.0) {
-    const double ang = atan2(n, fabs(q[0])) * 2.0;
-    o[0] = v0 / n * ang; o[1] = v1 / n * ang; o[2] = v2 / n * ang;
-  } else { o[0] = o[1] = o[2] = 0.0; }
-}
-
-// si / sj: pose (6) + velocity (3) of the two keyframes
-__device__ __forceinline__ void imu_residual_dev(const double* si, const double* sj, const double* pre, double* r9) {
-  const double dt = pre[10];
-  double ri[4], rj[4];
-  dev_q_from_scaled_axis(si, ri);
-  dev_q_from_scaled_axis(sj, rj);
-  const double ric[4] = {ri[0], -ri[1], -ri[2], -ri[3]}, drc[4] = {pre[0], -pre[1], -pre[2], -pre[3]};
-  double t[4], err[4];
-  dev_q_mul(drc, ric, t);
-  dev_q_mul(t, rj, err);                                                  // imu_factors.rs:85
-  dev_scaled_axis(err, r9);
-  const double g[3] = {0.0, 0.0, -9.81};                                  // imu/sample.rs:6
-  double a[3], b[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) a[i] = sj[6 + i] - si[6 + i] - g[i] * dt;   // :89
-  dev_q_rot(ric, a, b);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) r9[3 + i] = b[i] - pre[4 + i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) a[i] = sj[3 + i] - si[3 + i] - si[6 + i] * dt - 0.5 * g[i] * dt * dt;   // :93-94
-  dev_q_rot(ric, a, b);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) r9[6 + i] = b[i] - pre[7 + i];
-}
-
 // One block (64 threads) per IMU edge.  full: residual, forward-difference Jacobian (eps 1e-6, 18 columns = pose and
 // velocity of both keyframes), J^T J, J^T r; always: chi2 of the IMU and bias-random-walk residuals of the edge.
 __global__ __launch_bounds__(64) void ba_imu_kernel(const BaState* S, double* P0, double* P1, int which, int full, BaInertialDev in,

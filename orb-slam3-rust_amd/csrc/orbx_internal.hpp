@@ -203,6 +203,8 @@ struct orbx_handle {
   DevBuf ws_ba[28];
   DevBuf ws_pnp[2];                      // PnP-RANSAC: [0] hypotheses + counts (pnp_kernels.hip), [1] the host forms' input / output blobs
   void* h_pnp = nullptr; size_t h_pnp_bytes = 0;   // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
+  DevBuf ws_pi;                          // pose-inertial optimization: the host forms' input / output blob (pose_inertial_kernels.hip)
+  void* h_pi = nullptr; size_t h_pi_bytes = 0;     // pinned staging of orbx_pose_inertial_batch
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};

@@ -1,5 +1,6 @@
-// pose_dev.hpp — device math shared by the bundle-adjustment kernels (ba_kernels.hip) and the PnP-RANSAC kernels
-// (pnp_kernels.hip): the camera descriptor, quaternion / rotation helpers and the 2x6 pose block of one observation.
+// pose_dev.hpp — device math shared by the bundle-adjustment kernels (ba_kernels.hip), the PnP-RANSAC kernels (pnp_kernels.hip)
+// and pose-inertial optimization (pose_inertial_kernels.hip): the camera descriptor, quaternion / rotation helpers, the 2x6 pose
+// block of one observation and the 9-d IMU preintegration residual.
 // Device code only, inside an anonymous namespace: each translation unit that includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,6 +76,72 @@ __device__ __forceinline__ void obs_jac_from_proj(const BaCam& cam, const double
   A[3] = -fza;                       A[4] = 0.0;                        A[5] = xz * fza;
   A[8] = -(xz * ga);                 A[7] = yz * A[8];                  A[6] = fma(yz, yz, 1.0) * ga;
   A[9] = 0.0;                        A[10] = -gza;                      A[11] = yz * gza;
+}
+
+// ---- inertial terms shared by the inertial BA (ba_kernels.hip) and pose-inertial optimization (pose_inertial_kernels.hip) --------
+// src/optimizer/imu_factors.rs:66-103
+
+__device__ __forceinline__ void dev_scaled_axis(const double* q, double* o) {   // nalgebra UnitQuaternion::scaled_axis
+  double v0 = q[1], v1 = q[2], v2 = q[3];
+  if (!(q[0] >= 0.0)) { v0 = -v0; v1 = -v1; v2 = -v2; }
+  const double n = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+  if (n > 0.0) {
+    const double ang = atan2(n, fabs(q[0])) * 2.0;
+    o[0] = v0 / n * ang; o[1] = v1 / n * ang; o[2] = v2 / n * ang;
+  } else { o[0] = o[1] = o[2] = 0.0; }
+}
+
+// si / sj: pose (6) + velocity (3) of the two keyframes
+__device__ __forceinline__ void imu_residual_dev(const double* si, const double* sj, const double* pre, double* r9) {
+  const double dt = pre[10];
+  double ri[4], rj[4];
+  dev_q_from_scaled_axis(si, ri);
+  dev_q_from_scaled_axis(sj, rj);
+  const double ric[4] = {ri[0], -ri[1], -ri[2], -ri[3]}, drc[4] = {pre[0], -pre[1], -pre[2], -pre[3]};
+  double t[4], err[4];
+  dev_q_mul(drc, ric, t);
+  dev_q_mul(t, rj, err);                                                  // imu_factors.rs:85
+  dev_scaled_axis(err, r9);
+  const double g[3] = {0.0, 0.0, -9.81};                                  // imu/sample.rs:6
+  double a[3], b[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) a[i] = sj[6 + i] - si[6 + i] - g[i] * dt;   // :89
+  dev_q_rot(ric, a, b);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r9[3 + i] = b[i] - pre[4 + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) a[i] = sj[3 + i] - si[3 + i] - si[6 + i] * dt - 0.5 * g[i] * dt * dt;   // :93-94
+  dev_q_rot(ric, a, b);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r9[6 + i] = b[i] - pre[7 + i];
+}
+
+// The same residual with keyframe i's rotation given as the unit quaternion qi (w,x,y,z) instead of a scaled axis: the previous
+// keyframe's pose reaches pose_inertial_optimization as an SE3 (pose_inertial_optim.rs:94-216), and a round trip through the scaled
+// axis would not return its bits.  si supplies translation (3..5) and velocity (6..8).  The body is imu_residual_dev's after its
+// first conversion; it is written out rather than shared because routing imu_residual_dev through it reorders the operands of two
+// additions in the BA kernels' code.
+__device__ __forceinline__ void imu_residual_qi(const double* qi, const double* si, const double* sj, const double* pre, double* r9) {
+  const double dt = pre[10];
+  double rj[4];
+  dev_q_from_scaled_axis(sj, rj);
+  const double ric[4] = {qi[0], -qi[1], -qi[2], -qi[3]}, drc[4] = {pre[0], -pre[1], -pre[2], -pre[3]};
+  double t[4], err[4];
+  dev_q_mul(drc, ric, t);
+  dev_q_mul(t, rj, err);
+  dev_scaled_axis(err, r9);
+  const double g[3] = {0.0, 0.0, -9.81};
+  double a[3], b[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) a[i] = sj[6 + i] - si[6 + i] - g[i] * dt;
+  dev_q_rot(ric, a, b);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r9[3 + i] = b[i] - pre[4 + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) a[i] = sj[3 + i] - si[3 + i] - si[6 + i] * dt - 0.5 * g[i] * dt * dt;
+  dev_q_rot(ric, a, b);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r9[6 + i] = b[i] - pre[7 + i];
 }
 
 }  // namespace

@@ -511,3 +511,89 @@ def pnp_problem(seed, n, outlier_frac, prior_rot_deg, prior_trans_m, noise_px=0.
     q_prior = _quat_mul(dq, q_wc)
     return dict(points3d=Xw, points2d=uv.astype(np.float32), pose_wc=np.concatenate([q_wc, t_wc]),
                 prior_wc=np.concatenate([q_prior / np.linalg.norm(q_prior), t_wc + dt]), inliers=inliers, camera=dict(cam))
+
+
+# EuRoC cam0 in the world frame, roughly: the optical axis horizontal (camera z -> world x), image right -> world -y, image down ->
+# world -z
+_EUROC_R_WC = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
+
+
+def _quat_from_R(R):
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
+    x = np.copysign(np.sqrt(max(0.0, 1.0 + R[0, 0] - R[1, 1] - R[2, 2])) / 2.0, R[2, 1] - R[1, 2])
+    y = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] + R[1, 1] - R[2, 2])) / 2.0, R[0, 2] - R[2, 0])
+    z = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] - R[1, 1] + R[2, 2])) / 2.0, R[1, 0] - R[0, 1])
+    q = np.array([w, x, y, z])
+    return q / np.linalg.norm(q)
+
+
+def _quat_conj(q):
+    return np.array([q[0], -q[1], -q[2], -q[3]])
+
+
+def pose_inertial_problem(seed, n, outlier_frac, stereo_frac, init_rot_deg, init_trans_m, near_identity=False, noise_px=0.5, dt=0.05,
+                          imu_noise=0.0, camera=EUROC_CAMERA, w=752, h=480):
+    """A pose-inertial scene (pose_inertial_optimization, src/optimizer/pose_inertial_optim.rs:94-216; the tracker's call,
+    src/tracking/tracker.rs:476-546).  The previous keyframe: R_i within 0.05 rad of the identity (near_identity) or a EuRoC-like
+    orientation (optical axis horizontal, any heading, up to 0.2 rad of tilt), position U[-2,2]^3 m, velocity N(0, 0.5) m/s.  The true
+    motion over dt: angular velocity N(0, 0.5) rad/s per axis, acceleration N(0, 1) m/s^2 (0.2 times that near the identity, where
+    R_j stays within 0.05 rad), so R_j = R_i Exp(omega dt), v_j = v_i + a dt, p_j = p_i + v_i dt + a dt^2 / 2.  The preintegration
+    is the exact one of that motion — delta_rot = R_i^T R_j, delta_vel = R_i^T (v_j - v_i - g dt), delta_pos = R_i^T (p_j - p_i -
+    v_i dt - g dt^2 / 2) (imu_factors.rs:84-95), so the truth has a zero IMU residual — plus N(0, imu_noise) on delta_vel / delta_pos.
+    Observations of frame j are drawn as pnp_problem draws them (pixels over the image at depth U[1,20] m, inlier noise of sigma
+    noise_px clipped at 2 px, round(outlier_frac * n) outliers displaced 30-200 px); round(stereo_frac * n) of them are stereo.  The
+    initial pose is the truth turned by init_rot_deg about a random axis and moved by init_trans_m; the initial velocity is the truth
+    plus N(0, 0.05); the bias N(0, 1e-3) gyro / N(0, 1e-2) accel (never zero).
+    Returns pose_wc / velocity / bias (initial state), prev_kf_pose_wc / prev_kf_velocity, preint [11] (delta_rot qw,qx,qy,qz |
+    delta_vel | delta_pos | dt), points3d [n,3] f64, points2d [n,2] f32, is_stereo [n] u8, true_pose_wc / true_velocity, inliers [n]
+    bool, camera."""
+    rng = np.random.default_rng(seed)
+    cam = camera
+    g = np.array([0.0, 0.0, -9.81])
+    if near_identity:
+        q_i = _quat_from_axis_angle(rng.normal(size=3), rng.uniform(0.0, 0.02))
+    else:
+        yaw = _quat_from_axis_angle([0.0, 0.0, 1.0], rng.uniform(-np.pi, np.pi))
+        tilt = _quat_from_axis_angle(rng.normal(size=3), rng.uniform(0.0, 0.2))
+        q_i = _quat_mul(_quat_mul(yaw, tilt), _quat_from_R(_EUROC_R_WC))
+    p_i = rng.uniform(-2.0, 2.0, 3)
+    v_i = rng.normal(0.0, 0.5, 3)
+    sc = 0.2 if near_identity else 1.0
+    omega = rng.normal(0.0, 0.5 * sc, 3)
+    acc = rng.normal(0.0, sc, 3)
+    ang = np.linalg.norm(omega) * dt
+    q_j = _quat_mul(q_i, _quat_from_axis_angle(omega, ang)) if ang > 0 else q_i.copy()
+    q_j = q_j / np.linalg.norm(q_j)
+    v_j = v_i + acc * dt
+    p_j = p_i + v_i * dt + 0.5 * acc * dt * dt
+    qic = _quat_conj(q_i)
+    dq = _quat_mul(qic, q_j)
+    dv = _quat_rot(qic, v_j - v_i - g * dt) + rng.normal(0.0, imu_noise, 3)
+    dp = _quat_rot(qic, p_j - p_i - v_i * dt - 0.5 * g * dt * dt) + rng.normal(0.0, imu_noise, 3)
+    preint = np.concatenate([dq / np.linalg.norm(dq), dv, dp, [dt]])
+    u = rng.uniform(4.0, w - 4.0, n); v = rng.uniform(4.0, h - 4.0, n); d = rng.uniform(1.0, 20.0, n)
+    Xc = np.stack([(u - cam["cx"]) / cam["fx"] * d, (v - cam["cy"]) / cam["fy"] * d, d], 1)
+    Xw = _quat_rot(q_j, Xc) + p_j
+    e = rng.normal(0.0, noise_px, (n, 2))
+    e *= np.minimum(1.0, 2.0 / np.maximum(np.linalg.norm(e, axis=1), 1e-300))[:, None]
+    uv = np.stack([u, v], 1) + e
+    inliers = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        idx = rng.choice(n, n_out, replace=False)
+        a = rng.uniform(0.0, 2.0 * np.pi, n_out); mag = rng.uniform(30.0, 200.0, n_out)
+        uv[idx] = np.stack([u[idx], v[idx]], 1) + np.stack([np.cos(a), np.sin(a)], 1) * mag[:, None]
+        inliers[idx] = False
+    stereo = np.zeros(n, np.uint8)
+    n_st = int(round(stereo_frac * n))
+    if n_st:
+        stereo[rng.choice(n, n_st, replace=False)] = 1
+    q0 = _quat_mul(_quat_from_axis_angle(rng.normal(size=3), np.deg2rad(init_rot_deg)), q_j)
+    dt0 = rng.normal(size=3)
+    dt0 *= init_trans_m / np.linalg.norm(dt0)
+    bias = np.concatenate([rng.normal(0.0, 1e-3, 3), rng.normal(0.0, 1e-2, 3)])
+    bias[bias == 0.0] = 1e-6
+    return dict(pose_wc=np.concatenate([q0 / np.linalg.norm(q0), p_j + dt0]), velocity=v_j + rng.normal(0.0, 0.05, 3), bias=bias,
+                prev_kf_pose_wc=np.concatenate([q_i, p_i]), prev_kf_velocity=v_i, preint=preint, points3d=Xw,
+                points2d=uv.astype(np.float32), is_stereo=stereo, true_pose_wc=np.concatenate([q_j, p_j]), true_velocity=v_j,
+                inliers=inliers, camera=dict(cam))
