@@ -119,13 +119,78 @@ def _quat_rot(q, v):
     return v @ R.T
 
 
+def _unit_G(G):
+    """the world rotation G (w,x,y,z) of a generator, as given; only its norm is checked — its sign is the caller's choice"""
+    G = np.asarray(G, np.float64).reshape(4)
+    assert abs(np.linalg.norm(G) - 1.0) < 1e-12, "G must be a unit quaternion"
+    return G
+
+
+def _rotate_cw(G, pose_cw):
+    """T_cw [..., 7] of a scene turned by G: q_cw G^-1; t_cw is unchanged (R_cw G^T (G X) + t_cw = R_cw X + t_cw)"""
+    out = np.array(pose_cw, np.float64, copy=True).reshape(-1, 7)
+    Gc = G * np.array([1, -1, -1, -1.0])
+    for k in range(len(out)):
+        out[k, :4] = _quat_mul(out[k, :4], Gc)
+    return out.reshape(np.shape(pose_cw))
+
+
+def _rotate_wc(G, pose_wc):
+    """T_wc [..., 7] of a scene turned by G: (G q_wc, G t_wc)"""
+    out = np.array(pose_wc, np.float64, copy=True).reshape(-1, 7)
+    for k in range(len(out)):
+        out[k, :4] = _quat_mul(G, out[k, :4])
+    out[:, 4:] = _quat_rot(G, out[:, 4:])
+    return out.reshape(np.shape(pose_wc))
+
+
+def world_rotation(axis, angle):
+    """G for the generators' `G` argument: the rotation by `angle` rad about `axis`, (cos(angle / 2), axis sin(angle / 2)) with no
+    sign canonicalisation — angles in (pi, 2 pi) give w < 0 — and w exactly 0 at angle == pi."""
+    G = _quat_from_axis_angle(axis, angle)
+    if angle == np.pi:
+        G[0] = 0.0
+    return G
+
+
+def euroc_orientation(yaw):
+    """G that turns a generator's camera (looking along world +z) into EuRoC cam0's (_EUROC_R_WC: optical axis horizontal, image down
+    = world down), then turns it by `yaw` rad about world z"""
+    return _quat_mul(_quat_from_axis_angle([0.0, 0.0, 1.0], yaw), _quat_from_R(_EUROC_R_WC))
+
+
+# the quaternion-carrying inputs of each generator: field -> slice of the quaternion in the last axis
+_QUAT_FIELDS = dict(poses_cw=slice(0, 4), fixed_cw=slice(0, 4), poses_wc=slice(0, 4), preint=slice(0, 4), prior_wc=slice(0, 4),
+                    pose_wc=slice(0, 4), prev_kf_pose_wc=slice(0, 4))
+
+
+def with_quaternion_signs(scene, signs=-1.0, fields=None):
+    """A copy of a generator's scene with the quaternions of its solver inputs multiplied by `signs` — +1 or -1, one number for every
+    quaternion or, per field, an array with one sign per row — so that a test can hand a solver either of the two quaternions of each
+    rotation (nalgebra does not canonicalise).  `fields` defaults to every input field of _QUAT_FIELDS the scene has (for
+    pose_inertial_problem the `preint` field is one row; for inertial_window one row per edge).  Negation is exact: no other bit
+    changes."""
+    out = dict(scene)
+    for f in (fields if fields is not None else [f for f in _QUAT_FIELDS if f in scene]):
+        a = np.array(scene[f], np.float64, copy=True)
+        rows = a.reshape(-1, a.shape[-1])
+        sg = signs[f] if isinstance(signs, dict) else signs
+        sg = np.broadcast_to(np.asarray(sg, np.float64).reshape(-1), (len(rows),))
+        assert np.all(np.abs(sg) == 1.0)
+        rows[:, _QUAT_FIELDS[f]] *= sg[:, None]
+        out[f] = rows.reshape(a.shape)
+    return out
+
+
 def ba_window(seed, K, M, obs_dtype, n_fixed_extra=0, w=752, h=480, camera=None, noise_px=1.0,
-              perturb=True):
+              perturb=True, G=None):
     """A local-BA window: keyframe k at (0.15k, 0.02 sin k, 0) m with yaw
     0.01k rad; points U[-6,6]xU[-3,3]xU[3,15] m; an observation wherever the projection lands
     inside the image; pixel noise N(0, noise_px); initial poses perturbed (rot N(0,0.5 deg), trans
     N(0,2 cm)), points N(0,3 cm).  Keyframe 0 is the anchor (fixed, fixed_idx 0); the next
     `n_fixed_extra` keyframes are fixed observers too; the remaining K-1-n_fixed_extra are optimised.
+    G (a unit quaternion, w x y z) turns the finished scene about the world origin: q_wc -> G q_wc, t_wc -> G t_wc, X -> G X; the
+    observations do not change.  G=None leaves the scene as it always was, bit for bit.
 
     Returns dict(poses_cw [Kopt,7], fixed_cw [F,7], points [M,3], obs, gt_poses_cw, gt_points).
     """
@@ -162,6 +227,10 @@ def ba_window(seed, K, M, obs_dtype, n_fixed_extra=0, w=752, h=480, camera=None,
             init[i, :4] = _quat_mul(dq, init[i, :4])
             init[i, 4:] += rng.normal(0, 0.02, 3)
         init_pts += rng.normal(0, 0.03, init_pts.shape)
+    if G is not None:
+        G = _unit_G(G)
+        poses_cw, init = _rotate_cw(G, poses_cw), _rotate_cw(G, init)
+        pts, init_pts = _quat_rot(G, pts), _quat_rot(G, init_pts)
     return dict(poses_cw=init, fixed_cw=poses_cw[:F].copy(), points=init_pts, obs=obs,
                 gt_poses_cw=poses_cw[F:].copy(), gt_points=pts, camera=cam)
 
@@ -377,12 +446,18 @@ def write_euroc_mav0(root, n_frames, seed=0, w=752, h=480, camera=None):
     return pairs
 
 
-def inertial_window(seed, K, M, obs_dtype, n_fixed=2, dt=0.25, w=752, h=480, camera=None, noise_px=1.0, stereo_fraction=0.5):
+def inertial_window(seed, K, M, obs_dtype, n_fixed=2, dt=0.25, w=752, h=480, camera=None, noise_px=1.0, stereo_fraction=0.5, G=None,
+                    euroc_yaw=None):
     """A local inertial-BA window (local_inertial_ba.rs): K consecutive keyframes dt apart on a smooth accelerating
     trajectory (T_wc poses, world velocities, per-keyframe biases), `n_fixed` older keyframes that only observe (T_cw),
     M points.  The preintegrated deltas of edge (k, k+1) are the exact ones of the ground-truth states
     (dR = Ri^T Rj, dv = Ri^T (vj - vi - g dt), dp = Ri^T (pj - pi - vi dt - g dt^2 / 2), imu_factors.rs:66-103) plus a
     little noise; initial states are perturbed.  obs[i]["_pad"] bit 0 marks stereo observations.
+    G (a unit quaternion) turns the finished window about the world origin — poses, velocities, fixed observers and points — and the
+    deltas dv, dp are then computed again from the turned ground truth against the same world gravity (0, 0, -9.81), with the same
+    noise, so the IMU edges stay consistent (dR does not change).  euroc_yaw = a yaw in rad turns it by G euroc_orientation(yaw)
+    instead: the cameras then look horizontally and gravity lies in the image plane, as on EuRoC.  G=None and euroc_yaw=None leave the
+    window as it always was, bit for bit.
     Returns dict(poses_wc, velocities, biases, fixed_cw, points, obs, edge_kf, preint, camera, gt_*)."""
     cam = dict(EUROC_CAMERA if camera is None else camera)
     rng = np.random.default_rng([0x1BA, seed])
@@ -417,16 +492,23 @@ def inertial_window(seed, K, M, obs_dtype, n_fixed=2, dt=0.25, w=752, h=480, cam
         fixed_cw.append(np.concatenate([qi, -_quat_rot(qi, p_wc[idx])]))
     gt_poses = np.array([np.concatenate([q_wc[n_fixed + k], p_wc[n_fixed + k]]) for k in range(K)])
     gt_vel = np.array(v_w[n_fixed:])
-    edge_kf, preint = [], []
+    edge_kf, preint, noise = [], [], []
+
+    def deltas(gt_poses, gt_vel, k):
+        qic = gt_poses[k, :4] * np.array([1, -1, -1, -1.0])
+        dv = _quat_rot(qic, gt_vel[k + 1] - gt_vel[k] - g * dt)
+        dp = _quat_rot(qic, gt_poses[k + 1, 4:] - gt_poses[k, 4:] - gt_vel[k] * dt - 0.5 * g * dt * dt)
+        return dv, dp
+
     for k in range(K - 1):
         qi, qj = gt_poses[k, :4], gt_poses[k + 1, :4]
         qic = qi * np.array([1, -1, -1, -1.0])
         dR = _quat_mul(qic, qj)
-        dv = _quat_rot(qic, gt_vel[k + 1] - gt_vel[k] - g * dt)
-        dp = _quat_rot(qic, gt_poses[k + 1, 4:] - gt_poses[k, 4:] - gt_vel[k] * dt - 0.5 * g * dt * dt)
+        dv, dp = deltas(gt_poses, gt_vel, k)
         dR = _quat_mul(dR, _quat_from_axis_angle(rng.normal(0, 1, 3), rng.normal(0, 2e-3)))
         edge_kf.append((k, k + 1))
-        preint.append(np.concatenate([dR / np.linalg.norm(dR), dv + rng.normal(0, 5e-3, 3), dp + rng.normal(0, 2e-3, 3), [dt]]))
+        noise.append((rng.normal(0, 5e-3, 3), rng.normal(0, 2e-3, 3)))
+        preint.append(np.concatenate([dR / np.linalg.norm(dR), dv + noise[k][0], dp + noise[k][1], [dt]]))
     poses = gt_poses.copy()
     for k in range(K):
         dq = _quat_from_axis_angle(rng.normal(0, 1, 3), np.deg2rad(rng.normal(0, 0.4)))
@@ -434,7 +516,20 @@ def inertial_window(seed, K, M, obs_dtype, n_fixed=2, dt=0.25, w=752, h=480, cam
         poses[k, 4:] += rng.normal(0, 0.02, 3)
     vel = gt_vel + rng.normal(0, 0.05, (K, 3))
     bias = np.concatenate([rng.normal(0, 2e-3, (K, 3)), rng.normal(0, 2e-2, (K, 3))], 1)
-    return dict(poses_wc=poses, velocities=vel, biases=bias, fixed_cw=np.array(fixed_cw).reshape(-1, 7), points=pts + rng.normal(0, 0.03, (M, 3)),
+    fixed_cw = np.array(fixed_cw).reshape(-1, 7)
+    init_pts = pts + rng.normal(0, 0.03, (M, 3))
+    if euroc_yaw is not None:
+        G = _quat_mul(np.array([1.0, 0.0, 0.0, 0.0]) if G is None else _unit_G(G), euroc_orientation(euroc_yaw))
+    if G is not None:
+        G = _unit_G(G)
+        gt_poses, poses, fixed_cw = _rotate_wc(G, gt_poses), _rotate_wc(G, poses), _rotate_cw(G, fixed_cw)
+        gt_vel, vel = _quat_rot(G, gt_vel), _quat_rot(G, vel)
+        pts, init_pts = _quat_rot(G, pts), _quat_rot(G, init_pts)
+        for k in range(K - 1):
+            dv, dp = deltas(gt_poses, gt_vel, k)
+            preint[k][4:7] = dv + noise[k][0]
+            preint[k][7:10] = dp + noise[k][1]
+    return dict(poses_wc=poses, velocities=vel, biases=bias, fixed_cw=fixed_cw, points=init_pts,
                 obs=obs, edge_kf=np.array(edge_kf, np.int32).reshape(-1, 2), preint=np.array(preint).reshape(-1, 11), camera=cam,
                 gt_poses_wc=gt_poses, gt_velocities=gt_vel, gt_points=pts)
 
@@ -480,13 +575,14 @@ def read_ba_batch_results(path, windows):
     return out
 
 
-def pnp_problem(seed, n, outlier_frac, prior_rot_deg, prior_trans_m, noise_px=0.5, camera=EUROC_CAMERA, w=752, h=480):
+def pnp_problem(seed, n, outlier_frac, prior_rot_deg, prior_trans_m, noise_px=0.5, camera=EUROC_CAMERA, w=752, h=480, G=None):
     """A PnP-RANSAC scene (solve_pnp_ransac_detailed, src/geometry/pnp.rs:100-134).  Ground truth T_wc: a rotation of up to 0.5 rad
     about a random axis, position U[-2,2]^3 m.  Each point is drawn as a pixel U[4, w-4] x U[4, h-4] at depth U[1,20] m and
     back-projected, so the points cover the image.  Inlier observations carry Gaussian noise of sigma noise_px with its length
     clipped at 2 px; round(outlier_frac * n) outliers are displaced 30-200 px from their true projection in a random direction —
     a wide margin on both sides of the 8-px threshold.  The prior is the truth turned by prior_rot_deg about a random axis and
-    moved by prior_trans_m in a random direction.
+    moved by prior_trans_m in a random direction.  G (a unit quaternion) turns the finished scene about the world origin (truth,
+    prior and points; the observations do not change); G=None leaves it as it always was, bit for bit.
     Returns points3d [n,3] f64 (world), points2d [n,2] f32, prior_wc / pose_wc [7] (qw,qx,qy,qz,tx,ty,tz), inliers [n] bool, camera."""
     rng = np.random.default_rng(seed)
     cam = camera
@@ -509,8 +605,11 @@ def pnp_problem(seed, n, outlier_frac, prior_rot_deg, prior_trans_m, noise_px=0.
     dt = rng.normal(size=3)
     dt *= prior_trans_m / np.linalg.norm(dt)
     q_prior = _quat_mul(dq, q_wc)
-    return dict(points3d=Xw, points2d=uv.astype(np.float32), pose_wc=np.concatenate([q_wc, t_wc]),
-                prior_wc=np.concatenate([q_prior / np.linalg.norm(q_prior), t_wc + dt]), inliers=inliers, camera=dict(cam))
+    pose_wc, prior_wc = np.concatenate([q_wc, t_wc]), np.concatenate([q_prior / np.linalg.norm(q_prior), t_wc + dt])
+    if G is not None:
+        G = _unit_G(G)
+        pose_wc, prior_wc, Xw = _rotate_wc(G, pose_wc), _rotate_wc(G, prior_wc), _quat_rot(G, Xw)
+    return dict(points3d=Xw, points2d=uv.astype(np.float32), pose_wc=pose_wc, prior_wc=prior_wc, inliers=inliers, camera=dict(cam))
 
 
 # EuRoC cam0 in the world frame, roughly: the optical axis horizontal (camera z -> world x), image right -> world -y, image down ->
@@ -532,7 +631,7 @@ def _quat_conj(q):
 
 
 def pose_inertial_problem(seed, n, outlier_frac, stereo_frac, init_rot_deg, init_trans_m, near_identity=False, noise_px=0.5, dt=0.05,
-                          imu_noise=0.0, camera=EUROC_CAMERA, w=752, h=480):
+                          imu_noise=0.0, camera=EUROC_CAMERA, w=752, h=480, G=None):
     """A pose-inertial scene (pose_inertial_optimization, src/optimizer/pose_inertial_optim.rs:94-216; the tracker's call,
     src/tracking/tracker.rs:476-546).  The previous keyframe: R_i within 0.05 rad of the identity (near_identity) or a EuRoC-like
     orientation (optical axis horizontal, any heading, up to 0.2 rad of tilt), position U[-2,2]^3 m, velocity N(0, 0.5) m/s.  The true
@@ -543,7 +642,10 @@ def pose_inertial_problem(seed, n, outlier_frac, stereo_frac, init_rot_deg, init
     Observations of frame j are drawn as pnp_problem draws them (pixels over the image at depth U[1,20] m, inlier noise of sigma
     noise_px clipped at 2 px, round(outlier_frac * n) outliers displaced 30-200 px); round(stereo_frac * n) of them are stereo.  The
     initial pose is the truth turned by init_rot_deg about a random axis and moved by init_trans_m; the initial velocity is the truth
-    plus N(0, 0.05); the bias N(0, 1e-3) gyro / N(0, 1e-2) accel (never zero).
+    plus N(0, 0.05); the bias N(0, 1e-3) gyro / N(0, 1e-2) accel (never zero).  G (a unit quaternion) turns the finished scene about
+    the world origin (both frames' poses and velocities, the truth, the points) and computes delta_vel / delta_pos again from the turned
+    states against the same world gravity, with the same noise (delta_rot does not change); G=None leaves it as it always was, bit for
+    bit.
     Returns pose_wc / velocity / bias (initial state), prev_kf_pose_wc / prev_kf_velocity, preint [11] (delta_rot qw,qx,qy,qz |
     delta_vel | delta_pos | dt), points3d [n,3] f64, points2d [n,2] f32, is_stereo [n] u8, true_pose_wc / true_velocity, inliers [n]
     bool, camera."""
@@ -568,8 +670,10 @@ def pose_inertial_problem(seed, n, outlier_frac, stereo_frac, init_rot_deg, init
     p_j = p_i + v_i * dt + 0.5 * acc * dt * dt
     qic = _quat_conj(q_i)
     dq = _quat_mul(qic, q_j)
-    dv = _quat_rot(qic, v_j - v_i - g * dt) + rng.normal(0.0, imu_noise, 3)
-    dp = _quat_rot(qic, p_j - p_i - v_i * dt - 0.5 * g * dt * dt) + rng.normal(0.0, imu_noise, 3)
+    nv = rng.normal(0.0, imu_noise, 3)
+    dv = _quat_rot(qic, v_j - v_i - g * dt) + nv
+    npos = rng.normal(0.0, imu_noise, 3)
+    dp = _quat_rot(qic, p_j - p_i - v_i * dt - 0.5 * g * dt * dt) + npos
     preint = np.concatenate([dq / np.linalg.norm(dq), dv, dp, [dt]])
     u = rng.uniform(4.0, w - 4.0, n); v = rng.uniform(4.0, h - 4.0, n); d = rng.uniform(1.0, 20.0, n)
     Xc = np.stack([(u - cam["cx"]) / cam["fx"] * d, (v - cam["cy"]) / cam["fy"] * d, d], 1)
@@ -593,7 +697,16 @@ def pose_inertial_problem(seed, n, outlier_frac, stereo_frac, init_rot_deg, init
     dt0 *= init_trans_m / np.linalg.norm(dt0)
     bias = np.concatenate([rng.normal(0.0, 1e-3, 3), rng.normal(0.0, 1e-2, 3)])
     bias[bias == 0.0] = 1e-6
-    return dict(pose_wc=np.concatenate([q0 / np.linalg.norm(q0), p_j + dt0]), velocity=v_j + rng.normal(0.0, 0.05, 3), bias=bias,
-                prev_kf_pose_wc=np.concatenate([q_i, p_i]), prev_kf_velocity=v_i, preint=preint, points3d=Xw,
-                points2d=uv.astype(np.float32), is_stereo=stereo, true_pose_wc=np.concatenate([q_j, p_j]), true_velocity=v_j,
+    pose_wc, velocity = np.concatenate([q0 / np.linalg.norm(q0), p_j + dt0]), v_j + rng.normal(0.0, 0.05, 3)
+    prev_wc, true_wc = np.concatenate([q_i, p_i]), np.concatenate([q_j, p_j])
+    if G is not None:
+        G = _unit_G(G)
+        pose_wc, prev_wc, true_wc = _rotate_wc(G, pose_wc), _rotate_wc(G, prev_wc), _rotate_wc(G, true_wc)
+        velocity, v_i, v_j, Xw = _quat_rot(G, velocity), _quat_rot(G, v_i), _quat_rot(G, v_j), _quat_rot(G, Xw)
+        qic = _quat_conj(prev_wc[:4])
+        preint = preint.copy()
+        preint[4:7] = _quat_rot(qic, v_j - v_i - g * dt) + nv
+        preint[7:10] = _quat_rot(qic, true_wc[4:] - prev_wc[4:] - v_i * dt - 0.5 * g * dt * dt) + npos
+    return dict(pose_wc=pose_wc, velocity=velocity, bias=bias, prev_kf_pose_wc=prev_wc, prev_kf_velocity=v_i, preint=preint, points3d=Xw,
+                points2d=uv.astype(np.float32), is_stereo=stereo, true_pose_wc=true_wc, true_velocity=v_j,
                 inliers=inliers, camera=dict(cam))
