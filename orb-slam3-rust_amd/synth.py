@@ -191,6 +191,7 @@ def ba_window(seed, K, M, obs_dtype, n_fixed_extra=0, w=752, h=480, camera=None,
     `n_fixed_extra` keyframes are fixed observers too; the remaining K-1-n_fixed_extra are optimised.
     G (a unit quaternion, w x y z) turns the finished scene about the world origin: q_wc -> G q_wc, t_wc -> G t_wc, X -> G X; the
     observations do not change.  G=None leaves the scene as it always was, bit for bit.
+    This is the DENSE window (nearly every keyframe sees every point, sorted observations); tests/covis_windows.py makes the sparse, shuffled kind.
 
     Returns dict(poses_cw [Kopt,7], fixed_cw [F,7], points [M,3], obs, gt_poses_cw, gt_points).
     """
