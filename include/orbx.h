@@ -658,6 +658,76 @@ int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, cons
                                     double* d_poses_out, double* d_velocities_out, double* d_biases_out, uint8_t* d_inlier_out,
                                     orbx_pose_inertial_result* d_results);
 
+/* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
+ * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
+ * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).
+ * The BowVectors live in device memory as orbx_bow_vectors[_device] returns them (ascending u32 word ids, f64 weights, at most
+ * 8192 words); a call scores one query or a batch of queries against every entry in one launch.  Two scorings
+ * (compute_bow_score with and without a vocabulary, detector.rs:371-388):
+ *   ORBX_KFDB_SCORE_L1   OrbVocabulary::score (vocabulary/mod.rs:357-374): exactly orbx_bow_score of the pair;
+ *   ORBX_KFDB_SCORE_DOT  sum of w1 * w2 over the common words (keyframe_db.rs:73-79, detector.rs:380-386), product then add,
+ *                        [spec] in ascending word id (the reference walks a HashMap).
+ * Every score is one serial f64 sum per pair, bit for bit the host arithmetic, so that every comparison and ordering below is the
+ * restatement's.  [spec] equal scores are ordered by ascending keyframe id (the reference's stable sort leaves them in HashMap
+ * order).  An entry also carries its map index and the keyframe's is_bad flag (detector.rs:334).
+ * A database belongs to the handle it was made with and works on that handle's stream; it is not thread-safe.  erase / replace
+ * leave tombstones that a later query call compacts away once they outnumber the entries (or orbx_kfdb_compact at once). */
+typedef struct orbx_kfdb orbx_kfdb;
+enum { ORBX_KFDB_SCORE_L1 = 0, ORBX_KFDB_SCORE_DOT = 1 };
+/* = LoopDetectorConfig, detector.rs:17-46; orbx_default_loop_detector_config: 0.75, 3, 5, 10, 30.  The integer fields must be
+ * >= 0 and min_score_ratio not NaN; other values -> ORBX_ERR_INVALID.  consistency_threshold is the ConsistencyChecker's (host
+ * code of the mirrors); the searches do not read it. */
+typedef struct {
+  double min_score_ratio;
+  int consistency_threshold, min_covisibles_for_threshold, max_covisibles_to_check, min_temporal_gap;
+} orbx_loop_detector_config;
+void orbx_default_loop_detector_config(orbx_loop_detector_config* cfg);
+
+int orbx_kfdb_create(orbx_handle* h, orbx_kfdb** out);
+void orbx_kfdb_destroy(orbx_kfdb* db);
+/* KeyFrameDatabase::add (keyframe_db.rs:45-47): an id that exists is replaced.  word [n] strictly ascending (else
+ * ORBX_ERR_INVALID, as orbx_bow_score), weight [n], 0 <= n <= 8192, map_index >= 0.  Host pointers; synchronous. */
+int orbx_kfdb_add(orbx_kfdb* db, uint64_t keyframe_id, int map_index, int is_bad, const uint32_t* word, const double* weight, int n);
+/* The same from device memory, with the word count a device value: d_word / d_weight [max_n], n = *d_count clamped to
+ * [0, max_n].  The outputs of orbx_bow_vectors_device go straight in (d_bow_word, d_bow_weight, d_counts).  Asynchronous on the
+ * handle's stream, no host synchronisation; the word ids are trusted to ascend. */
+int orbx_kfdb_add_device(orbx_kfdb* db, uint64_t keyframe_id, int map_index, int is_bad, const uint32_t* d_word, const double* d_weight,
+                         const int* d_count, int max_n);
+/* KeyFrameDatabase::erase (:50-52): an absent id is not an error. */
+int orbx_kfdb_erase(orbx_kfdb* db, uint64_t keyframe_id);
+int orbx_kfdb_set_bad(orbx_kfdb* db, uint64_t keyframe_id, int is_bad);
+/* n_entries: live entries; n_slots: table rows including tombstones (either may be NULL). */
+int orbx_kfdb_size(const orbx_kfdb* db, int* n_entries, int* n_slots);
+int orbx_kfdb_compact(orbx_kfdb* db);
+/* Reads one entry back (synchronous): *n words into word / weight [cap] (ORBX_ERR_CAPACITY with *n set when cap is too small). */
+int orbx_kfdb_download(orbx_kfdb* db, uint64_t keyframe_id, uint32_t* word, double* weight, int cap, int* n, int* map_index, int* is_bad);
+/* The scores of one query vector against every entry: ids [cap] in ascending keyframe id and scores [cap], *n_out = entries
+ * (ORBX_ERR_CAPACITY when cap is smaller).  Synchronous. */
+int orbx_kfdb_score(orbx_kfdb* db, int scoring, const uint32_t* q_word, const double* q_weight, int nq, uint64_t* ids, double* scores, int cap,
+                    int* n_out);
+/* KeyFrameDatabase::detect_candidates (keyframe_db.rs:58-94): DOT score against every entry, entries of exclude_map skipped
+ * (exclude_map < 0: None), kept iff score > 0.0, score descending, truncated to max_results.  ids / scores [max_results],
+ * map_indices [max_results] or NULL; *n_out <= max_results. */
+int orbx_kfdb_detect_candidates(orbx_kfdb* db, const uint32_t* q_word, const double* q_weight, int nq, int exclude_map, int max_results,
+                                uint64_t* ids, int* map_indices, double* scores, int* n_out);
+/* detect_loop_candidates (detector.rs:185-368) for a current keyframe that is an entry (an unknown id: *count = 0, :195-204).
+ * connected [n_connected]: the ids of get_connected_keyframes (:232-262) in the order the caller iterates them — map bookkeeping
+ * that stays on the host.  Threshold (:265-298): connected[] is walked as given (a repeated id counts again), ids that are not
+ * entries of the current keyframe's map are skipped, each other one is scored, bad or not, until max_covisibles_to_check are;
+ * fewer than min_covisibles_for_threshold scored: threshold 0; else best * min_score_ratio; a threshold < 0.01: no candidates
+ * (:212-215).  get_connected_keyframes inserts the current keyframe itself (:234) and compute_min_score does not exclude it: the
+ * library scores whatever the caller lists.  Candidates (:301-358): entries of the current keyframe's map, not in
+ * connected[], |id - current| >= min_temporal_gap as u64, not bad, score >= threshold; score descending (:361-365).
+ * ids / scores [cap]: the first min(*count, cap) candidates; *count: all of them (it may exceed cap). */
+int orbx_kfdb_detect_loop_candidates(orbx_kfdb* db, const orbx_loop_detector_config* cfg, int scoring, uint64_t current_id, const uint64_t* connected,
+                                     int n_connected, int cap, uint64_t* ids, double* scores, int* count);
+/* n_queries current keyframes in one call: query q owns connected [connected_offsets[q], connected_offsets[q+1]) (offsets
+ * [n_queries+1], ascending from 0); ids / scores [n_queries][cap], counts [n_queries].  A query's result is the same bytes alone
+ * and inside any batch. */
+int orbx_kfdb_detect_loop_candidates_batch(orbx_kfdb* db, const orbx_loop_detector_config* cfg, int scoring, int n_queries, const uint64_t* current_ids,
+                                           const int* connected_offsets, const uint64_t* connected, int cap, uint64_t* ids, double* scores,
+                                           int* counts);
+
 /* Per-kernel device time for bench.py's roofline block.  While profiling is on
  * (orbx_set_profiling), every launch is bracketed by HIP events on the handle's stream;
  * orbx_get_kernel_times synchronises, fills up to `cap` entries with the durations summed

@@ -15,6 +15,9 @@
 //   orbx::solve_visual_ba                   local_ba_lm.rs:912-1098
 //   orbx::PnPResult / solve_pnp_ransac_detailed    src/geometry/pnp.rs:12-20, :100-134
 //   orbx::PoseInertialConfig/Result, PoseObservation, pose_inertial_optimization   src/optimizer/pose_inertial_optim.rs:19-216
+//   orbx::KeyFrameDatabase / Candidate       src/atlas/keyframe_db.rs:22-95
+//   orbx::LoopDetectorConfig / LoopCandidate / ConsistencyChecker / KeyFrameDatabase::detect_loop_candidates
+//                                           src/loop_closing/detector.rs:17-167, :185-368
 //
 // Errors: the reference propagates `anyhow::Error` with `?` — here orbx::Error is thrown; where the
 // reference returns `None` (solve_visual_ba) std::nullopt is returned.  Everything computes on the GPU.
@@ -23,11 +26,13 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <deque>
 #include <functional>
 #include <optional>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "orbx.h"
@@ -777,5 +782,136 @@ inline PoseInertialResult pose_inertial_optimization(Handle& h, const SE3& initi
   r.iterations = (size_t)res.iterations;
   return r;
 }
+
+// ---- place recognition (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) -------------------------------------------------
+using KeyFrameId = uint64_t;
+
+struct LoopDetectorConfig {   // detector.rs:17-46
+  double min_score_ratio = 0.75;
+  size_t consistency_threshold = 3, min_covisibles_for_threshold = 5, max_covisibles_to_check = 10, min_temporal_gap = 30;
+  orbx_loop_detector_config c() const {
+    return orbx_loop_detector_config{min_score_ratio, (int)consistency_threshold, (int)min_covisibles_for_threshold, (int)max_covisibles_to_check,
+                                     (int)min_temporal_gap};
+  }
+};
+
+struct Candidate {   // keyframe_db.rs:22-28
+  KeyFrameId keyframe_id;
+  size_t map_index;
+  double score;
+};
+
+struct LoopCandidate {   // detector.rs:49-62; loop_covisibles is map bookkeeping, filled by the caller
+  KeyFrameId current_kf_id, loop_kf_id;
+  double bow_score;
+  std::vector<KeyFrameId> loop_covisibles;
+};
+
+enum class BowScoring { L1 = ORBX_KFDB_SCORE_L1, Dot = ORBX_KFDB_SCORE_DOT };   // compute_bow_score with / without a vocabulary (detector.rs:371-388)
+
+// KeyFrameDatabase (keyframe_db.rs:31-95) with the BowVectors in device memory (orbx_kfdb), and detect_loop_candidates over it.
+class KeyFrameDatabase {
+ public:
+  explicit KeyFrameDatabase(Handle& h) : h_(&h) { h.check(orbx_kfdb_create(h.get(), &db_)); }
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase(KeyFrameDatabase&& o) noexcept : h_(o.h_), db_(o.db_) { o.db_ = nullptr; }
+  ~KeyFrameDatabase() { if (db_) orbx_kfdb_destroy(db_); }
+  orbx_kfdb* get() const { return db_; }
+
+  void add(KeyFrameId kf_id, const BowVector& bow, size_t map_idx, bool is_bad = false) {   // keyframe_db.rs:45-47
+    std::vector<uint32_t> k; std::vector<double> w;
+    flat(bow, k, w);
+    h_->check(orbx_kfdb_add(db_, kf_id, (int)map_idx, is_bad ? 1 : 0, k.data(), w.data(), (int)k.size()));
+  }
+  // the same from sorted arrays, as orbx_bow_vectors returns them
+  void add(KeyFrameId kf_id, const std::vector<uint32_t>& words, const std::vector<double>& weights, size_t map_idx, bool is_bad = false) {
+    if (words.size() != weights.size()) throw std::invalid_argument("KeyFrameDatabase::add: words / weights differ in length");
+    h_->check(orbx_kfdb_add(db_, kf_id, (int)map_idx, is_bad ? 1 : 0, words.data(), weights.data(), (int)words.size()));
+  }
+  void erase(KeyFrameId kf_id) { h_->check(orbx_kfdb_erase(db_, kf_id)); }                  // :50-52
+  void set_bad(KeyFrameId kf_id, bool is_bad) { h_->check(orbx_kfdb_set_bad(db_, kf_id, is_bad ? 1 : 0)); }
+  size_t size() const { int n = 0; orbx_kfdb_size(db_, &n, nullptr); return (size_t)n; }
+
+  // keyframe_db.rs:58-94
+  std::vector<Candidate> detect_candidates(const BowVector& query, std::optional<size_t> exclude_map, size_t max_results) const {
+    std::vector<uint32_t> k; std::vector<double> w;
+    flat(query, k, w);
+    return detect_candidates(k, w, exclude_map, max_results);
+  }
+  std::vector<Candidate> detect_candidates(const std::vector<uint32_t>& words, const std::vector<double>& weights, std::optional<size_t> exclude_map,
+                                           size_t max_results) const {
+    const int cap = (int)std::min(max_results, size());
+    std::vector<uint64_t> ids((size_t)std::max(cap, 1)); std::vector<int> maps((size_t)std::max(cap, 1)); std::vector<double> sc((size_t)std::max(cap, 1));
+    int n = 0;
+    h_->check(orbx_kfdb_detect_candidates(db_, words.data(), weights.data(), (int)words.size(), exclude_map ? (int)*exclude_map : -1, cap, ids.data(),
+                                          maps.data(), sc.data(), &n));
+    std::vector<Candidate> out;
+    for (int i = 0; i < n; ++i) out.push_back(Candidate{ids[(size_t)i], (size_t)maps[(size_t)i], sc[(size_t)i]});
+    return out;
+  }
+  // detector.rs:185-368; connected: get_connected_keyframes(kf_id) in iteration order (:232-262).  Every candidate is returned.
+  std::vector<LoopCandidate> detect_loop_candidates(KeyFrameId kf_id, const std::vector<KeyFrameId>& connected, const LoopDetectorConfig& config,
+                                                    BowScoring scoring = BowScoring::L1) const {
+    const orbx_loop_detector_config c = config.c();
+    const int cap = (int)size();
+    std::vector<uint64_t> ids((size_t)std::max(cap, 1)); std::vector<double> sc((size_t)std::max(cap, 1));
+    int n = 0;
+    h_->check(orbx_kfdb_detect_loop_candidates(db_, &c, (int)scoring, kf_id, connected.data(), (int)connected.size(), cap, ids.data(), sc.data(), &n));
+    std::vector<LoopCandidate> out;
+    for (int i = 0; i < n && i < cap; ++i) out.push_back(LoopCandidate{kf_id, ids[(size_t)i], sc[(size_t)i], {}});
+    return out;
+  }
+
+ private:
+  static void flat(const BowVector& v, std::vector<uint32_t>& k, std::vector<double>& w) {
+    for (const auto& kv : v) k.push_back(kv.first);
+    std::sort(k.begin(), k.end());
+    for (uint32_t x : k) w.push_back(v.at(x));
+  }
+  Handle* h_;
+  orbx_kfdb* db_ = nullptr;
+};
+
+// detector.rs:68-167: host set logic, no device involved
+class ConsistencyChecker {
+ public:
+  explicit ConsistencyChecker(const LoopDetectorConfig& config) : config_(config) {}
+  std::optional<LoopCandidate> add_and_check(KeyFrameId kf_id, const std::vector<LoopCandidate>& candidates) {   // :94-146
+    std::unordered_set<KeyFrameId> candidate_set;
+    for (const LoopCandidate& c : candidates) {
+      candidate_set.insert(c.loop_kf_id);
+      for (KeyFrameId cov : c.loop_covisibles) candidate_set.insert(cov);
+    }
+    std::unordered_map<KeyFrameId, size_t> new_counts;
+    for (KeyFrameId id : candidate_set) new_counts[id] = region_count(id) + 1;
+    const LoopCandidate* best = nullptr;
+    for (const LoopCandidate& c : candidates) {
+      auto it = new_counts.find(c.loop_kf_id);
+      if (it != new_counts.end() && it->second >= config_.consistency_threshold && (!best || c.bow_score > best->bow_score)) best = &c;
+    }
+    history_.emplace_back(kf_id, std::move(candidate_set));
+    if (history_.size() > config_.consistency_threshold + 2) history_.pop_front();
+    consistent_counts_ = std::move(new_counts);
+    if (best) {
+      LoopCandidate result = *best;
+      clear();
+      return result;
+    }
+    return std::nullopt;
+  }
+  void clear() { history_.clear(); consistent_counts_.clear(); }                                               // :163-166
+  size_t history_len() const { return history_.size(); }
+
+ private:
+  size_t region_count(KeyFrameId id) const {                                                                  // :149-160
+    size_t n = 0;
+    for (const auto& h : history_) n += h.second.count(id);
+    return n;
+  }
+  LoopDetectorConfig config_;
+  std::deque<std::pair<KeyFrameId, std::unordered_set<KeyFrameId>>> history_;
+  std::unordered_map<KeyFrameId, size_t> consistent_counts_;
+};
 
 }  // namespace orbx

@@ -14,5 +14,6 @@ from .api import (  # noqa: F401
     InertialBAResultData, flatten_inertial_ba_problem, solve_inertial_ba, MapSnapshot, local_bundle_adjustment, run_global_ba, KeyFrame, BaBatch,
     PnPConfig, PnPResult, PNP_RESULT, PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N, solve_pnp_ransac, solve_pnp_ransac_detailed,
     PoseInertialConfig, PoseInertialResult, POSE_INERTIAL_RESULT, POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR,
-    pose_inertial_optimization)
+    pose_inertial_optimization, KeyFrameDatabase, LoopDetectorConfig, LoopCandidate, ConsistencyChecker, KFDB_SCORE_L1, KFDB_SCORE_DOT,
+    KFDB_MAX_WORDS)
 from .build import LIB_PATH, build  # noqa: F401

@@ -25,6 +25,7 @@ import ctypes as C
 import math
 import os
 import weakref
+from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional
 
@@ -85,6 +86,9 @@ ABI_SYMBOLS = [
     "orbx_debug_read_candidates",
     "orbx_default_pnp_config", "orbx_pnp_ransac", "orbx_pnp_ransac_batch", "orbx_pnp_ransac_batch_device",
     "orbx_default_pose_inertial_config", "orbx_pose_inertial_optimize", "orbx_pose_inertial_batch", "orbx_pose_inertial_batch_device",
+    "orbx_default_loop_detector_config", "orbx_kfdb_create", "orbx_kfdb_destroy", "orbx_kfdb_add", "orbx_kfdb_add_device", "orbx_kfdb_erase",
+    "orbx_kfdb_set_bad", "orbx_kfdb_size", "orbx_kfdb_compact", "orbx_kfdb_download", "orbx_kfdb_score", "orbx_kfdb_detect_candidates",
+    "orbx_kfdb_detect_loop_candidates", "orbx_kfdb_detect_loop_candidates_batch",
 ]
 
 
@@ -170,6 +174,16 @@ class _PoseInertialResult(C.Structure):
 # orbx_pose_inertial_result as a numpy record (the batch forms' results array)
 POSE_INERTIAL_RESULT = np.dtype([("status", "<i4"), ("num_inliers", "<i4"), ("num_observations", "<i4"), ("iterations", "<i4")])
 POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR = 0, 1, 2
+
+
+class _LoopDetectorConfig(C.Structure):
+    """orbx_loop_detector_config (include/orbx.h)"""
+    _fields_ = [("min_score_ratio", C.c_double), ("consistency_threshold", C.c_int), ("min_covisibles_for_threshold", C.c_int),
+                ("max_covisibles_to_check", C.c_int), ("min_temporal_gap", C.c_int)]
+
+
+KFDB_SCORE_L1, KFDB_SCORE_DOT = 0, 1      # ORBX_KFDB_SCORE_*
+KFDB_MAX_WORDS = 8192                     # words of one BowVector in the database
 
 
 SHOULD_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -1791,6 +1805,25 @@ class OrbVocabulary:
         h._check(h._L.orbx_bow_vectors(h._h, self._v, _vp(d), n, int(levels_up), _vp(bw), _vp(bv), C.byref(nb), _vp(fn), _vp(fs), _vp(fi), C.byref(nf)))
         return bw[:nb.value], bv[:nb.value], fn[:nf.value], fs[:nf.value + 1], fi[:n]
 
+    def vectors_device(self, d_desc, n, levels_up=4):
+        """orbx_bow_vectors_device on descriptors already in device memory (a torch uint8 tensor [n, 32] on the handle's device, n <=
+        BOW_VECTORS_MAX) -> dict of torch tensors left on the device: bow_word (int32 storage of the u32 ids), bow_weight, fv_node,
+        fv_start, fv_index, counts (n_bow, n_fv).  Asynchronous on the handle's stream: nothing is read on the host, so the result can go
+        straight into KeyFrameDatabase.add_device(id, r["bow_word"], r["bow_weight"], r["counts"], n)."""
+        import torch
+        h = self._handle
+        n = int(n)
+        dev = torch.device("cuda", h.device)
+        m = max(n, 1)
+        r = dict(bow_word=torch.empty(m, dtype=torch.int32, device=dev), bow_weight=torch.empty(m, dtype=torch.float64, device=dev),
+                 fv_node=torch.empty(m, dtype=torch.int32, device=dev), fv_start=torch.empty(m + 1, dtype=torch.int32, device=dev),
+                 fv_index=torch.empty(m, dtype=torch.int32, device=dev), counts=torch.zeros(2, dtype=torch.int32, device=dev))
+        h._after_torch(d_desc, *r.values())
+        h._L.orbx_bow_vectors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        h._check(h._L.orbx_bow_vectors_device(h._h, self._v, _vp(d_desc), n, int(levels_up), _vp(r["bow_word"]), _vp(r["bow_weight"]),
+                                              _vp(r["fv_node"]), _vp(r["fv_start"]), _vp(r["fv_index"]), _vp(r["counts"])))
+        return r
+
     def transform(self, descriptors, levels_up=4):
         """mod.rs:296-325 -> (BowVector dict word -> weight, FeatureVector dict node -> [feature indices]); descent, accumulation
         and L1 normalisation on the GPU (the norm is summed in ascending word id: the reference sums in HashMap order)."""
@@ -1820,6 +1853,194 @@ class OrbVocabulary:
         if self._v:
             self._handle._L.orbx_vocab_destroy(self._v)
             self._v = None
+
+    def __del__(self):
+        try:
+            if self._handle._h:
+                self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class LoopDetectorConfig:
+    """detector.rs:17-46"""
+    min_score_ratio: float = 0.75
+    consistency_threshold: int = 3
+    min_covisibles_for_threshold: int = 5
+    max_covisibles_to_check: int = 10
+    min_temporal_gap: int = 30
+
+    def _c(self):
+        return _LoopDetectorConfig(self.min_score_ratio, self.consistency_threshold, self.min_covisibles_for_threshold,
+                                   self.max_covisibles_to_check, self.min_temporal_gap)
+
+
+@dataclass
+class LoopCandidate:
+    """detector.rs:49-62.  loop_covisibles is map bookkeeping: the caller fills it (the searches return ids and scores)."""
+    current_kf_id: int
+    loop_kf_id: int
+    bow_score: float
+    loop_covisibles: list = field(default_factory=list)
+
+
+class ConsistencyChecker:
+    """detector.rs:68-167: a loop candidate counts once it was detected for consistency_threshold keyframes in a row.  Host code."""
+
+    def __init__(self, config: LoopDetectorConfig = None):
+        self.config = config or LoopDetectorConfig()
+        self.history = deque()              # (keyframe id, set of candidate ids)
+        self.consistent_counts = {}
+
+    def add_and_check(self, kf_id, candidates):
+        """:94-146 -> the consistent candidate with the largest score (the first of equals), or None."""
+        candidate_set = set()
+        for c in candidates:
+            candidate_set.add(c.loop_kf_id)
+            candidate_set.update(c.loop_covisibles)
+        new_counts = {cid: self._region_count(cid) + 1 for cid in candidate_set}
+        best = None
+        for c in candidates:
+            if new_counts.get(c.loop_kf_id, 0) >= self.config.consistency_threshold and (best is None or c.bow_score > best.bow_score):
+                best = c
+        self.history.append((kf_id, candidate_set))
+        if len(self.history) > self.config.consistency_threshold + 2:
+            self.history.popleft()
+        self.consistent_counts = new_counts
+        if best is not None:
+            self.clear()
+            return best
+        return None
+
+    def _region_count(self, candidate_id):
+        return sum(1 for _kf, cs in self.history if candidate_id in cs)      # :149-160
+
+    def clear(self):
+        self.history.clear()
+        self.consistent_counts = {}
+
+
+def _bow_arrays(bow):
+    """A BowVector as (ascending u32 word ids, f64 weights): from a dict word -> weight, or a (words, weights) pair kept as given."""
+    if isinstance(bow, dict):
+        k = np.array(sorted(bow), np.uint32)
+        return k, np.array([bow[int(x)] for x in k], np.float64)
+    w, v = bow
+    w = np.ascontiguousarray(w, np.uint32).reshape(-1); v = np.ascontiguousarray(v, np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("a BowVector needs as many weights as words")
+    return w, v
+
+
+class KeyFrameDatabase:
+    """orbx_kfdb: KeyFrameDatabase (atlas/keyframe_db.rs:36-95) with the BowVectors in device memory, and detect_loop_candidates
+    (loop_closing/detector.rs:185-368) over it.  Ids are keyframe ids (u64); an entry also carries its map index and is_bad."""
+
+    def __init__(self, handle: Handle = None):
+        h = handle or _handle()
+        self._handle = h
+        L = self._L = h._L
+        vp, i, u64 = C.c_void_p, C.c_int, C.c_uint64
+        L.orbx_kfdb_create.argtypes = [vp, vp]
+        L.orbx_kfdb_destroy.argtypes = [vp]; L.orbx_kfdb_destroy.restype = None
+        L.orbx_kfdb_add.argtypes = [vp, u64, i, i, vp, vp, i]
+        L.orbx_kfdb_add_device.argtypes = [vp, u64, i, i, vp, vp, vp, i]
+        L.orbx_kfdb_erase.argtypes = [vp, u64]
+        L.orbx_kfdb_set_bad.argtypes = [vp, u64, i]
+        L.orbx_kfdb_size.argtypes = [vp, vp, vp]
+        L.orbx_kfdb_compact.argtypes = [vp]
+        L.orbx_kfdb_download.argtypes = [vp, u64, vp, vp, i, vp, vp, vp]
+        L.orbx_kfdb_score.argtypes = [vp, i, vp, vp, i, vp, vp, i, vp]
+        L.orbx_kfdb_detect_candidates.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp]
+        L.orbx_kfdb_detect_loop_candidates.argtypes = [vp, vp, i, u64, vp, i, i, vp, vp, vp]
+        L.orbx_kfdb_detect_loop_candidates_batch.argtypes = [vp, vp, i, i, vp, vp, vp, i, vp, vp, vp]
+        self._p = C.c_void_p()
+        h._check(L.orbx_kfdb_create(h._h, C.byref(self._p)))
+
+    def add(self, kf_id, bow, map_idx=0, is_bad=False):
+        """keyframe_db.rs:45-47; bow: dict word -> weight, or (ascending words, weights)."""
+        w, v = _bow_arrays(bow)
+        self._handle._check(self._L.orbx_kfdb_add(self._p, int(kf_id), int(map_idx), int(bool(is_bad)), _vp(w), _vp(v), len(w)))
+
+    def add_device(self, kf_id, d_word, d_weight, d_count, max_n, map_idx=0, is_bad=False):
+        """The outputs of orbx_bow_vectors_device (torch tensors or device addresses) straight in; no host synchronisation."""
+        h = self._handle
+        h._after_torch(*[t for t in (d_word, d_weight, d_count) if not isinstance(t, int)])
+        h._check(self._L.orbx_kfdb_add_device(self._p, int(kf_id), int(map_idx), int(bool(is_bad)), _vp(d_word), _vp(d_weight), _vp(d_count), int(max_n)))
+
+    def erase(self, kf_id):
+        self._handle._check(self._L.orbx_kfdb_erase(self._p, int(kf_id)))
+
+    def set_bad(self, kf_id, is_bad=True):
+        self._handle._check(self._L.orbx_kfdb_set_bad(self._p, int(kf_id), int(bool(is_bad))))
+
+    def sizes(self):
+        """(live entries, table rows including tombstones)"""
+        n, s = C.c_int(), C.c_int()
+        self._handle._check(self._L.orbx_kfdb_size(self._p, C.byref(n), C.byref(s)))
+        return n.value, s.value
+
+    def __len__(self):
+        return self.sizes()[0]
+
+    def compact(self):
+        self._handle._check(self._L.orbx_kfdb_compact(self._p))
+
+    def download(self, kf_id):
+        """-> (words, weights, map index, is_bad) of one entry, read back from the device."""
+        w = np.zeros(KFDB_MAX_WORDS, np.uint32); v = np.zeros(KFDB_MAX_WORDS, np.float64)
+        n, m, b = C.c_int(), C.c_int(), C.c_int()
+        self._handle._check(self._L.orbx_kfdb_download(self._p, int(kf_id), _vp(w), _vp(v), KFDB_MAX_WORDS, C.byref(n), C.byref(m), C.byref(b)))
+        return w[:n.value].copy(), v[:n.value].copy(), m.value, bool(b.value)
+
+    def score(self, query, scoring=KFDB_SCORE_L1):
+        """-> (ids ascending, scores) of the query against every entry."""
+        w, v = _bow_arrays(query)
+        cap = max(len(self), 1)
+        ids = np.zeros(cap, np.uint64); sc = np.zeros(cap, np.float64); n = C.c_int()
+        self._handle._check(self._L.orbx_kfdb_score(self._p, int(scoring), _vp(w), _vp(v), len(w), _vp(ids), _vp(sc), cap, C.byref(n)))
+        return ids[:n.value], sc[:n.value]
+
+    def detect_candidates(self, query, exclude_map=None, max_results=10):
+        """keyframe_db.rs:58-94 -> (ids, map indices, scores), score descending."""
+        w, v = _bow_arrays(query)
+        cap = max(int(max_results), 1)
+        ids = np.zeros(cap, np.uint64); maps = np.zeros(cap, np.int32); sc = np.zeros(cap, np.float64); n = C.c_int()
+        self._handle._check(self._L.orbx_kfdb_detect_candidates(self._p, _vp(w), _vp(v), len(w), -1 if exclude_map is None else int(exclude_map),
+                                                                int(max_results), _vp(ids), _vp(maps), _vp(sc), C.byref(n)))
+        return ids[:n.value], maps[:n.value], sc[:n.value]
+
+    def detect_loop_candidates(self, kf_id, connected, config: LoopDetectorConfig = None, scoring=KFDB_SCORE_L1, cap=64):
+        """detector.rs:185-368 -> (ids, scores, total): the first min(total, cap) candidates, score descending."""
+        ids, sc, cnt = self.detect_loop_candidates_batch([kf_id], [connected], config, scoring, cap, _single=True)
+        m = max(min(int(cnt[0]), cap), 0)
+        return ids[0, :m], sc[0, :m], int(cnt[0])
+
+    def detect_loop_candidates_batch(self, kf_ids, connected_lists, config: LoopDetectorConfig = None, scoring=KFDB_SCORE_L1, cap=64, _single=False):
+        """Q current keyframes in one call -> (ids [Q][cap], scores [Q][cap], counts [Q]); row q holds min(counts[q], cap) candidates."""
+        cfg = (config or LoopDetectorConfig())._c()
+        Q = len(kf_ids)
+        cur = np.array([int(k) for k in kf_ids], np.uint64)
+        off = np.zeros(Q + 1, np.int32)
+        off[1:] = np.cumsum([len(c) for c in connected_lists])
+        conn = np.array([int(x) for c in connected_lists for x in c], np.uint64)
+        ids = np.zeros((Q, max(cap, 0)), np.uint64); sc = np.zeros((Q, max(cap, 0)), np.float64); cnt = np.zeros(max(Q, 1), np.int32)
+        h = self._handle
+        if _single:
+            c1 = C.c_int()
+            h._check(self._L.orbx_kfdb_detect_loop_candidates(self._p, C.byref(cfg), int(scoring), int(cur[0]), _vp(conn), len(conn), int(cap), _vp(ids),
+                                                              _vp(sc), C.byref(c1)))
+            cnt[0] = c1.value
+        else:
+            h._check(self._L.orbx_kfdb_detect_loop_candidates_batch(self._p, C.byref(cfg), int(scoring), Q, _vp(cur), _vp(off), _vp(conn), int(cap),
+                                                                    _vp(ids), _vp(sc), _vp(cnt)))
+        return ids, sc, cnt[:Q]
+
+    def close(self):
+        if self._p:
+            self._L.orbx_kfdb_destroy(self._p)
+            self._p = None
 
     def __del__(self):
         try:

@@ -350,6 +350,61 @@ def vocabulary(seed, k=10, depth=3, ragged=False):
     return parent, leaf, np.array(desc, np.uint8), np.array(weight, np.float64)
 
 
+def bow_database(seed, n_keyframes, words_per_kf=1000, n_words=100000, revisit=None, noise=0.08, n_duplicates=0, other_map_every=0,
+                 bad_every=0, short_lists_every=0, reach=6):
+    """BowVectors of keyframes along a trajectory, for place recognition at scale without descriptors.  Keyframe i stands at place p_i
+    (= i, except inside the revisited stretch `revisit` = (first id, length, place it returns to): there p_i = place + (i - first)).
+    Every place owns words_per_kf / 8 words of the vocabulary [0, n_words); a keyframe sees the words of the 8 places around its own, so
+    neighbours share 7/8 of them and a revisiting keyframe shares them with keyframes far back in id; a fraction `noise` of its words is
+    replaced by random ones.  Weights are a per-word IDF-like value times a per-observation jitter, L1-normalised in ascending word id.
+      n_duplicates: that many keyframes (outside the revisit stretch, spread over the ids) get the exact BowVector of their predecessor
+                    — equal scores for two ids;
+      other_map_every / bad_every: every such id (> 0) lies in map 1 / is bad;
+      short_lists_every: every such id has only itself and its predecessor in its connected list (too few for a threshold).
+    connected[i]: what get_connected_keyframes (detector.rs:232-262) holds for keyframe i — itself and the ids within `reach` of it —
+    in a seeded random order standing in for the HashSet's.
+    Returns dict(ids u64 [N], maps i32 [N], bad bool [N], words / weights: lists of N arrays, connected: list of N lists of int)."""
+    rng = np.random.default_rng([0xB0DB, seed])
+    N = int(n_keyframes)
+    per_place = max(words_per_kf // 8, 1)
+    place = np.arange(N, dtype=np.int64)
+    if revisit is not None:
+        first, length, back_to = revisit
+        place[first:first + length] = back_to + np.arange(min(length, N - first))
+    n_places = int(place.max()) + 8 if N else 8
+    idf = rng.uniform(0.5, 12.0, n_words)
+    # the words of place p: per_place draws (duplicates inside a keyframe's 8 places fall away in the union)
+    place_words = rng.integers(0, n_words, (n_places + 8, per_place), dtype=np.int64)
+    words, weights = [], []
+    for i in range(N):
+        w = place_words[place[i]:place[i] + 8].reshape(-1).copy()
+        swap = rng.random(len(w)) < noise
+        w[swap] = rng.integers(0, n_words, int(swap.sum()))
+        w = np.unique(w)
+        v = idf[w] * rng.uniform(0.9, 1.1, len(w))
+        t = float(np.cumsum(v)[-1]) if len(v) else 0.0      # the norm added in ascending word id (cumsum is sequential), as orbx_bow_vectors sums it
+        words.append(w.astype(np.uint32)); weights.append(v / t if t > 0.0 else v)
+    if n_duplicates and N > 2:
+        lo, hi = (1, N) if revisit is None else (1, revisit[0])
+        for j in np.linspace(lo, max(hi - 1, lo), n_duplicates).astype(int):
+            if 0 < j < N:
+                words[j] = words[j - 1].copy(); weights[j] = weights[j - 1].copy()
+    ids = np.arange(N, dtype=np.uint64)
+    maps = np.zeros(N, np.int32); bad = np.zeros(N, bool)
+    if other_map_every:
+        maps[other_map_every::other_map_every] = 1
+    if bad_every:
+        bad[bad_every::bad_every] = True
+    connected = []
+    for i in range(N):
+        if short_lists_every and i % short_lists_every == short_lists_every - 1:
+            c = [i] + ([i - 1] if i else [])
+        else:
+            c = list(range(max(0, i - reach), min(N, i + reach + 1)))
+        connected.append([int(c[k]) for k in rng.permutation(len(c))])
+    return dict(ids=ids, maps=maps, bad=bad, words=words, weights=weights, connected=connected)
+
+
 def write_vocabulary_text(path, parent, is_leaf, desc, weight, k=10, depth=3, junk_lines=True):
     """DBoW2 text format as load_from_text reads it (mod.rs:101-116): header 'k L scoring weighting', then
     'parent_id is_leaf d0..d31 weight' per node (root excluded).  junk_lines adds short lines that the loader skips."""
