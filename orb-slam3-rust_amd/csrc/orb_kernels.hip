@@ -13,8 +13,9 @@
 //                         candidate lists + score histograms                                  (A.5)
 //   harris_select_kernel  retainBest(2 n_l) by FAST score via the histogram, Harris response
 //                         of the survivors                                                    (A.6)
-//   rank_select_kernel    canonical order (response desc, y, x) by bitonic sort in LDS, retainBest(n_l)
-//                         incl. ties with the n-th; the kept keypoints again in spatial order  (A.6)
+//   rank_select_kernel    retainBest(n_l) incl. ties with the n-th by a radix select on the response, canonical order
+//                         (response desc, y, x) of the kept keys by bitonic sort in LDS; the kept keypoints again
+//                         in spatial order                                                    (A.6)
 //   describe_tile_kernel  one workgroup per describe tile: the tile's blurred rectangle on the matrix pipe in LDS,
 //                         intensity-centroid angle and 256 steered BRIEF tests per keypoint   (A.7, A.8)
 //   describe_fused_kernel the same per keypoint (small calls, levels too small for tiles): each keypoint's
@@ -844,6 +845,10 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
     unsigned P[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) P[k] = r[k] | (r[k + 8] << 16);
+    // (The pairs read straight into the halves of one register — ds_read_u8_d16 for r[k], ds_read_u8_d16_hi for r[k + 8], no v_lshl_or_b32 —
+    // do not exist on this chip: as two-element u16 vectors the compiler reads 16 plain bytes and packs them with v_perm_b32, the same 4-cycle
+    // class, because with SRAM ECC on a d16 read does not preserve the register's other half; written as inline assembly the second read
+    // of a pair cleared the first and the extractor lost its keypoints (tests/test_select_kept_gpu.py).  profiles/r06_fast_survivor_phases.txt)
 #ifdef ORBX_FAST_NO_LADDER
     // measurement build (NOT the specification): the 16 ring reads and their packing stay, the min / max ladder of the arc score is replaced by
     // two instructions — what ANY cheaper test in front of the ladder (a contiguity bit-mask) could save at the very most
@@ -856,6 +861,11 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
     ss[j][i] = (uint8_t)sc;
   }
   __syncthreads();
+  // (A block-wide CORNER LIST — phase 2 lists the positions that score above zero inside the tile a second time, downwards from the top of s_pos,
+  // by one ballot and one returning LDS add per wave round; phase 3 walks that list densely and aggregates its appends per wave round — was built,
+  // bit-exact (439 tests): fast_kernel 0.8989-0.8997 -> 0.8823-0.8845 ms per 512 pairs in every one of nine alternations, but 70 VGPRs instead of
+  // 65, and the step's gain (+0.15 to +0.8 % frames/s) stayed inside twice the spread of two runs of one build.  Withdrawn:
+  // profiles/r06_fast_survivor_phases.txt.)
   // phase 3: NMS (strictly greater than the 8 neighbours) + runByImageBorder, over the same list: corners inside the tile and the
   // border-filtered region (a few per cent of the survivors — the pre-test also passes every straight edge)
   for (int q = tid; q < npos; q += FT_THREADS) {
@@ -1061,14 +1071,21 @@ __global__ __launch_bounds__(256) void harris_select_kernel(OrbSrc s, OrbGeom g,
 // (Round 5: ONE 1024-thread workgroup per image — all levels' candidates in one flat index space, survivors in one LDS list with slots from the
 // histograms' suffix sums, dense responses — was built, bit-exact, and measured 0.152 against 0.138 ms per 256 pairs:
 // profiles/r05_harris_per_image_negative.txt.  Withdrawn.)
-// Canonical order of the survivors of one (image, level) + retainBest(n_l) with ties.  Up to 2048 keys: bitonic
-// sort in LDS (rank_select_kernel); more (heavy ties): rank sort — keys are unique (x,y differ), so rank = number
-// of smaller keys is a permutation.  E owned keys per thread per pass.
+// Canonical order of the survivors of one (image, level) + retainBest(n_l) with ties.  Up to 2048 keys of which up to
+// RK_CAP are kept: select, then bitonic sort of the kept keys in LDS (rank_select_kernel); more (heavy ties, huge quotas):
+// rank sort of all keys — keys are unique (x,y differ), so rank = number of smaller keys is a permutation.  E owned keys
+// per thread per pass.
 constexpr int RK_NT = 256;   // threads of rank_select_kernel: one block per (image, level) — most levels hold a few hundred keys
+// keys of rank_select_kernel's LDS array: the kept keys of a level are sorted there if they fit, by the rank sort otherwise
+#ifndef ORBX_RK_CAP
+#define ORBX_RK_CAP 1024
+#endif
+constexpr int RK_CAP = ORBX_RK_CAP;
+static_assert(RK_CAP == 1024 || RK_CAP == 2048, "a power of two, at least the 1024 counters the tile sort keeps in the array, at most the 2048 keys held in registers");
 template <int E>
 __device__ __forceinline__ void rank_pass(const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out,
                                           unsigned M, unsigned g0, unsigned long long* chunk, int quota, unsigned* s_thr) {
-  constexpr int CH = 2048;
+  constexpr int CH = RK_CAP;
   const int tid = threadIdx.x;
   unsigned long long my[E];
   unsigned rank[E];
@@ -1133,8 +1150,8 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
                                                            unsigned* __restrict__ kept, uint2* __restrict__ tile_rng) {
   // (Round 5: the Harris responses inside this kernel — survivors compacted into the key array, responses computed densely, sorted in place —
   // took 0.215-0.218 ms against 0.139 + 0.074 for the two launches: profiles/r05_select_fused_negative.txt.  Withdrawn.)
-  __shared__ unsigned long long chunk[2048];
-  __shared__ unsigned skey[1024 + 16];
+  __shared__ unsigned long long chunk[RK_CAP];
+  __shared__ __attribute__((aligned(16))) unsigned skey[1024 + 16];
   __shared__ unsigned s_thr, s_keep;
   int img, l;
   if (!xcd_decode(xm, n_img, img, l)) return;
@@ -1156,13 +1173,90 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
     for (unsigned t = tid; t < ntl; t += RK_NT) rng[t] = uint2{0u, 0u};
     return;
   }
+  constexpr int KL = 2048 / RK_NT;
+  unsigned long long my[KL];
+  unsigned Ksel = M;
   if (M <= 2048) {
-    // the usual case (M ~ 2 n_l): bitonic sort of the keys in LDS, padded with ~0 to a power of two.  A thread owns the
-    // compare-exchanges c = tid, tid + RK_NT, ... of a step; steps with stride <= 64 stay inside the 128 keys of one
-    // (wave, c / RK_NT) pair, so only the strides >= 128 need a block barrier (10 of the 55 steps at 1024 keys).
+    // the usual case (M ~ 2.2 n_l): SELECT, then sort what is kept.  Only the first kept[il] entries of the canonical list are read by
+    // anything (the spatial list holds kept keys only), so the n_l-th smallest high word is found first — a thread's <= 8 keys stay in
+    // registers — and only the K keys at or below it (ties with the n-th are kept, as before) go through the bitonic sort: half the width
+    // and ten steps fewer than sorting all M.  sel2 at and beyond kept[il] is left UNSPECIFIED.
+    const int lane = tid & 63;
+#pragma unroll
+    for (int e = 0; e < KL; ++e) {
+      const unsigned i = tid + (unsigned)RK_NT * e;
+      my[e] = i < M ? in[i] : ~0ull;
+    }
+    unsigned thr = 0xffffffffu;
+    if (M > (unsigned)quota) {
+      // MSB-first radix select on the high word, 8 bits per pass, one 256-bin histogram per pass in skey (cleared once).  Every wave
+      // scans the histogram itself (4 bins per lane, DPP prefix sum), so a pass costs one block barrier.  Responses share their top
+      // byte(s): a wave round whose active lanes hold one digit adds its count once instead of 64 times to one address.
+      for (int i = tid; i < 1024; i += RK_NT) skey[i] = 0u;
+      __syncthreads();
+      unsigned prefix = 0, want = (unsigned)quota, hsel = 0;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int shift = 24 - 8 * p;
+        unsigned* hist = skey + 256 * p;
+        const unsigned himask = p ? 0xffffffffu << (shift + 8) : 0u;
+#pragma unroll
+        for (int e = 0; e < KL; ++e) {
+          const unsigned hi = (unsigned)(my[e] >> 32);
+          const bool act = tid + (unsigned)RK_NT * e < M && ((hi ^ prefix) & himask) == 0u;
+          const unsigned d = (hi >> shift) & 255u;
+          const unsigned long long m = __ballot(act);
+          if (m) {
+            const int f = __ffsll((long long)m) - 1;
+            const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, f);
+            if (__ballot(act && d != d0) == 0ull) { if (lane == f) atomicAdd(&hist[d0], (unsigned)__popcll(m)); }
+            else if (act) atomicAdd(&hist[d], 1u);
+          }
+        }
+        __syncthreads();
+        // smallest bin whose inclusive count reaches `want`
+        const uint4 h4 = reinterpret_cast<const uint4*>(hist)[lane];
+        const unsigned tot = h4.x + h4.y + h4.z + h4.w;
+        const unsigned incl = (unsigned)wave_scan_incl((int)tot);
+        const int L = __ffsll((long long)__ballot(incl >= want)) - 1;      // (exists: the candidates of the pass number >= want)
+        unsigned w = want - (unsigned)__builtin_amdgcn_readlane((int)(incl - tot), L);
+        const unsigned b0 = (unsigned)__builtin_amdgcn_readlane((int)h4.x, L), b1 = (unsigned)__builtin_amdgcn_readlane((int)h4.y, L);
+        const unsigned b2 = (unsigned)__builtin_amdgcn_readlane((int)h4.z, L), b3 = (unsigned)__builtin_amdgcn_readlane((int)h4.w, L);
+        unsigned bin = 4u * (unsigned)L;
+        hsel = b0;
+        if (w > b0) { w -= b0; ++bin; hsel = b1; if (w > b1) { w -= b1; ++bin; hsel = b2; if (w > b2) { w -= b2; ++bin; hsel = b3; } } }
+        want = w;
+        prefix |= bin << shift;
+      }
+      thr = prefix;                                   // ~orderable(response of the n-th best)
+      Ksel = (unsigned)quota - want + hsel;           // #{high word < thr} + #{high word == thr}
+    }
+    if (Ksel <= (unsigned)RK_CAP) {
+    const unsigned K = Ksel;
     unsigned P = 128;
-    while (P < M) P <<= 1;
-    for (unsigned i = tid; i < P; i += RK_NT) chunk[i] = i < M ? in[i] : ~0ull;
+    while (P < K) P <<= 1;
+    // the kept keys into chunk[0..K) in any order: slots by ballot / mbcnt, one returning LDS add per wave
+    {
+      unsigned wtot = 0;
+#pragma unroll
+      for (int e = 0; e < KL; ++e)
+        wtot += (unsigned)__popcll(__ballot(tid + (unsigned)RK_NT * e < M && (unsigned)(my[e] >> 32) <= thr));
+      int base = 0;
+      if (lane == 0) base = lds_add_rtn(reinterpret_cast<int*>(&s_keep), (int)wtot);   // (as written: see lds_add_rtn)
+      base = __builtin_amdgcn_readfirstlane(base);
+#pragma unroll
+      for (int e = 0; e < KL; ++e) {
+        const bool keep = tid + (unsigned)RK_NT * e < M && (unsigned)(my[e] >> 32) <= thr;
+        const unsigned long long m = __ballot(keep);
+        const unsigned slot = (unsigned)base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (keep && slot < (unsigned)RK_CAP) chunk[slot] = my[e];        // (slot < K by construction; the bound keeps LDS writes inside the array whatever happens)
+        base += __popcll(m);
+      }
+      for (unsigned i = K + tid; i < P; i += RK_NT) chunk[i] = ~0ull;
+    }
+    // bitonic sort of the kept keys in LDS, padded with ~0 to a power of two.  A thread owns the
+    // compare-exchanges c = tid, tid + RK_NT, ... of a step; steps with stride <= 64 stay inside the 128 keys of one
+    // (wave, c / RK_NT) pair, so only the strides >= 128 need a block barrier (3 of the 45 steps at 512 keys).
     __syncthreads();
     unsigned pj = 128;
     for (unsigned k = 2; k <= P; k <<= 1) {
@@ -1179,24 +1273,16 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
       }
     }
     __syncthreads();
-    for (unsigned i = tid; i < M; i += RK_NT) out[i] = chunk[i];
-    if (M <= (unsigned)quota) {
-      if (tid == 0) { kept[il] = M; s_keep = M; }
-    } else {
-      const unsigned thr = (unsigned)(chunk[quota - 1] >> 32);   // ~orderable(response of the n-th best); ties with it are kept
-      for (unsigned i = tid; i < M; i += RK_NT)
-        if ((unsigned)(chunk[i] >> 32) <= thr && (i + 1 >= M || (unsigned)(chunk[i + 1] >> 32) > thr)) { kept[il] = i + 1; s_keep = i + 1; }
-    }
-    __syncthreads();
+    for (unsigned i = tid; i < K; i += RK_NT) out[i] = chunk[i];
+    if (tid == 0) kept[il] = K;
     // spatial order of the kept keypoints: counting sort by cell = (128-px column band, block of rows) — a walk down
     // each band; the order inside a cell is whatever the atomics give (processing order only, results are unaffected)
-    const unsigned K = s_keep;
     int rsh = 4;                                                   // 16-row blocks, coarser if the level is huge
     while ((unsigned)(((g.lv[l].w + 127) >> 7) * ((g.lv[l].h >> rsh) + 1)) > 1024u) ++rsh;
     const unsigned nrb = (unsigned)(g.lv[l].h >> rsh) + 1u;
     for (int i = tid; i < 1024; i += RK_NT) skey[i] = 0u;          // histogram in skey[0..1024), wave totals behind it
     __syncthreads();
-    constexpr int KE = 2048 / RK_NT;
+    constexpr int KE = RK_CAP / RK_NT;
     unsigned mycell[KE], mypos[KE];
 #pragma unroll
     for (int e = 0; e < KE; ++e) {
@@ -1217,6 +1303,8 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
     }
     for (unsigned t = tid; t < ntl; t += RK_NT) rng[t] = uint2{skey[t], t + 1 < ntl ? skey[t + 1] : K};
     return;
+    }
+    __syncthreads();   // more kept keys than the LDS array holds (heavy response ties, or a quota above it): the rank sort below
   }
   for (unsigned g0 = 0; g0 < M; g0 += 4 * RK_NT) rank_pass<4>(in, out, M, g0, chunk, quota, &s_thr);
   __syncthreads();
