@@ -6,7 +6,10 @@
 // forms a dense 2N x P Jacobian, a dense J^T J and solves with LU (:1019-1039); the same normal
 // equations are built here in their block structure (last bullet):
 //
-// Six launches per LM iteration (every block derives the keyframe rotations it needs itself):
+// The launches of one LM iteration (every block derives the keyframe rotations it needs itself).  A call of eight windows or more, a
+// partitioned solve and ORBX_BA_FUSED=0 run all six (seven in a batch, where the keyframe partials and the Schur product are two
+// launches).  A call of up to seven windows on one GPU runs the fused form: ba_step_kernel does the back-substitution and the NEXT
+// iteration's build pass in one launch, so ba_build_kernel runs for iteration 0 only and an iteration is five launches (six in a batch):
 //
 //   ba_build_kernel      one 32- or 16-lane group per map point: residual + Jacobian blocks of its
 //                        observations, V_j = sum B^T B, g_l, damped inverse V*_j^-1, V*_j^-1 g_l; per observation only six
@@ -27,6 +30,8 @@
 //                        one panel of look-ahead, the backward substitution in the same launch; beyond 320: one ba_big_step_kernel per panel
 //                        + ba_big_back_kernel)
 //   ba_backsub_kernel    delta_l = V*^-1 (-g_l - W^T delta_p), trial parameters and trial residuals
+//   ba_step_kernel       (the fused form, in place of ba_backsub_kernel and the next ba_build_kernel) the same back-substitution, then the
+//                        build pass at the trial parameters into the second set of build results (BaWin::dbl)
 //   ba_decide_kernel     sums, accept / reject, lambda, stop tests — the LM state lives on the device
 //
 // plus ba_chi2_kernel (initial error), ba_sum3_kernel (partitioned runs) and the inertial kernels (ba_imu_*,
@@ -3361,21 +3366,53 @@ void host_params_to_pose_wc(const double* p6, double* out7) {
   out7[0] = qi[0]; out7[1] = qi[1]; out7[2] = qi[2]; out7[3] = qi[3];
   out7[4] = -rt[0]; out7[5] = -rt[1]; out7[6] = -rt[2];
 }
+// R|t of the F fixed observers and, behind them, of the identity (the observer of an observation that names neither): Rt_fix [F + 1][12]
+void host_fixed_to_Rt(const double* fixed_poses_cw, int F, double* Rt_fix) {
+  for (int f = 0; f <= F; ++f) {
+    const double ident[7] = {1, 0, 0, 0, 0, 0, 0};
+    const double* p = f < F ? fixed_poses_cw + 7 * (size_t)f : ident;
+    host_quat_to_R(p, &Rt_fix[12 * (size_t)f]);
+    Rt_fix[12 * (size_t)f + 9] = p[4]; Rt_fix[12 * (size_t)f + 10] = p[5]; Rt_fix[12 * (size_t)f + 11] = p[6];
+  }
+}
+// extract_pose of the inertial solve (local_inertial_ba.rs:584-608): the rotation vector of T_wc as a unit quaternion, the translation as it is
+void host_params_to_pose_inertial(const double* p6, double* q) {
+  const double v[3] = {p6[0] / 2.0, p6[1] / 2.0, p6[2] / 2.0};
+  const double nn = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], eps = 2.220446049250313e-16;
+  if (nn <= eps * eps) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
+  else { const double nv = std::sqrt(nn), sn = 1.0 * std::sin(nv) / nv; q[0] = 1.0 * std::cos(nv); q[1] = v[0] * sn; q[2] = v[1] * sn; q[3] = v[2] * sn; }
+  q[4] = p6[3]; q[5] = p6[4]; q[6] = p6[5];
+}
 
 }  // namespace
 
 // ---- host side of the solver ------------------------------------------------------------------------------------------
+// ba_solve_batch (at the end) is the list of phases; each phase is one function below, and what they share travels in one BaCtx.
 namespace {
 
 constexpr size_t BA_LDS_STATIC = 22784;                              // static LDS of ba_solve_lds_kernel (sb, srinv, s_red, s_col, s_rv, ...), rounded up
 constexpr size_t BA_LDS_DYN_MAX = 160 * 1024 - BA_LDS_STATIC;
 static_assert(BA_TILED_LDS_MAX + BA_LDS_STATIC <= 160 * 1024 && BF_LDS_BYTES + 8 * 1024 <= 160 * 1024 && SCHW_LDS_BYTES + 8 * 1024 <= 160 * 1024,
-              "dynamic LDS of the tiled solve / one-launch factorisation / Schur kernels beside their static arrays (the exact check, against the code object, runs once per device in ba_solve_batch)");
+              "dynamic LDS of the tiled solve / one-launch factorisation / Schur kernels beside their static arrays (the exact check, against the code object, runs once per device in ba_set_func_attributes)");
 
 struct Carve {                                                       // byte offsets inside one buffer, 256-byte aligned pieces
   size_t off = 0;
   size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
 };
+
+// The two sub-layouts that more than one array pointer is cut from: each stated here once, the size beside the pointers.
+// per-point sums of the build / back-substitution kernels: pt_chi2 [dbl][m1] | pt_glsq [dbl][m1] | pt_dsq [m1] | pt_psq [m1]
+constexpr size_t pt_sums_doubles(size_t m1, size_t dbl) { return (2 * dbl + 2) * m1; }
+void bind_pt_sums(BaWin& b, double* base, size_t m1, size_t dbl) {
+  b.pt_chi2 = base; b.pt_glsq = b.pt_chi2 + dbl * m1; b.pt_dsq = b.pt_glsq + dbl * m1; b.pt_psq = b.pt_dsq + m1;
+}
+// a reduced system of size n (6K; 15K for the inertial window): dp [n pad 16] | S [n*n] | b [n] | 1/L_jj [n pad 16] | gradient slot [n pad 16] |
+// L11^-T rows [n / 16 + 1][256]
+constexpr size_t system_doubles(size_t n) { return n * n + 21 * n + 640; }
+double* bind_system(BaWin& b, double* base, int n) {                 // returns the gradient slot
+  b.dp = base; b.Sg = b.dp + ((n + 15) & ~15); b.bvec = b.Sg + (size_t)n * n; b.ginv = b.bvec + n;
+  return b.ginv + n;
+}
 
 // everything about one window that is known from its sizes alone
 struct WinPlan {
@@ -3389,12 +3426,57 @@ struct WinPlan {
   size_t a_p1, a_oP, a_rtcur, a_slot, a_next, a_kfobs, a_kfpt, a_vinv, a_gl, a_vg, a_pt, a_kfpart, a_part, a_rb, a_solve, a_res, a_vraw, a_rej;
   size_t a_ptstart, a_okf, a_ouv, a_oflag, a_tmp, a_mz;
   size_t o_out;
-  int n_kfobs = 0;
   double n_res = 0.0;
 };
 static_assert(sizeof(orbx_ba_obs) == 32 && offsetof(orbx_ba_obs, mp_idx) == 8 && offsetof(orbx_ba_obs, u) == 16,
               "ba_prep_*_kernel read an observation as one int4 (kf_idx, fixed_idx, mp_idx, _pad) and one double2 (u, v)");
 static_assert(sizeof(orbx_ba_obs32) == 16 && offsetof(orbx_ba_obs32, mp_idx) == 4 && offsetof(orbx_ba_obs32, u) == 8, "... or one int2 and one float2");
+
+// windows whose observations follow each other in the caller's memory: one copy
+struct Run { int w0, w1; size_t off, bytes; const void* src; bool direct; };
+
+// grids and kernel choices of the LM loop's launches: functions of the windows' sizes, the batch and the device (ba_launch_shape)
+struct BaShape {
+  int ppg = 1, ptl = 32, ppg_build = 1, pt_groups = 0;
+  int any_lds = 0, any_tiled = 0, any_big = 0, any_one = 0, n_big_max = 0;
+  size_t lds_max = 0, tiled_lds_max = 0;
+  int maxM = 0, maxK = 0, max_schur_blocks = 1, all_diag = 1, max_gather = 1, max_back = 1, max_asm = 1;
+  bool schur_sums = false;
+  int schur_spb = 1;
+};
+constexpr int BA_ONE_LAUNCH_MAX_N = BF_MAX_N;   // reduced systems up to this size: the one-launch factorisation, larger ones one launch per panel
+
+// what the phases of one ba_solve_batch call share
+struct BaCtx {
+  // the call
+  orbx_handle* h; hipStream_t st;
+  const orbx_camera* cam; const orbx_ba_config* cfg;
+  int W; BaWinHost* win;
+  orbx_should_stop_fn should_stop; void* user;
+  const BaInertialHost* inr; const BaCallOpts* opts;
+  bool global_mode, single_call, inertial, dist, fused;
+  // plan
+  std::vector<WinPlan> plan;
+  size_t i_wins = 0, i_wins15 = 0, i_outoff = 0;                        // input blob: descriptors | the inertial window as the 15-d solve sees it | output offsets
+  size_t small_bytes = 0, obs_bytes = 0, arena_bytes = 0, a_cnt = 0, cnt_bytes = 0, out_bytes = 0;
+  int live = 0, maxN = 0;
+  int K0 = 0, M0 = 0, n15 = 0;                                          // inertial / partitioned: the one window
+  std::vector<Run> runs;
+  bool any_stage = false;
+  // base pointers (ba_reserve)
+  uint8_t *hin = nullptr, *hobs = nullptr, *din = nullptr, *dobs = nullptr, *dar = nullptr;
+  double *dout = nullptr, *hout = nullptr;
+  BaWin *hw = nullptr, *d_wins = nullptr, *d_wins15 = nullptr;          // descriptors: in the pinned blob (host copies of the device pointers), on the device
+  bool direct_sent = false, drained = false;                             // (see DrainOnLeave in ba_solve_batch)
+  BaShape s;
+  BaCam bc{};
+  BaInertialDev ind{};
+  double *imu_buf = nullptr, *dp15 = nullptr, *gfull = nullptr;
+  // the partitioned solve's collective decisions (ba_partition_head)
+  double n_res = 0.0;
+  bool my_stop = false, stopped = false;
+  std::vector<double> votes;
+};
 
 // Is [p, p + bytes) pinned (hipHostMalloc / hipHostRegister) host memory — something the copy engine can read where it lies?
 bool host_is_pinned(const void* p, size_t bytes) {
@@ -3420,9 +3502,8 @@ int pinned_reserve(orbx_handle* h, void** p, size_t* have, size_t need) {
 // The O(K + M) host part of one window, straight into the (pinned) input blob: pose parameters, map points, fixed poses.  Everything
 // per observation happens on the device (ba_prep_*_kernel).
 void prep_window(const BaWinHost& w, const WinPlan& pl, uint8_t* blob, bool inertial, const BaInertialHost* inr) {
-  const int K = w.K, F = w.F, M = w.M;
+  const int K = w.K, M = w.M;
   double* params = (double*)(blob + pl.i_params);
-  double* Rt_fix = (double*)(blob + pl.i_rtfix);
   for (int k = 0; k < K; ++k) host_se3_to_params(w.poses_cw + 7 * (size_t)k, &params[6 * (size_t)k]);   // scaled axis + translation
   if (M > 0) memcpy(&params[6 * (size_t)K], w.points, 24 * (size_t)M);
   if (inertial)                                                          // :1154-1173
@@ -3431,47 +3512,31 @@ void prep_window(const BaWinHost& w, const WinPlan& pl, uint8_t* blob, bool iner
       for (int i = 0; i < 3; ++i) ex[i] = inr->velocities[3 * (size_t)k + i];
       for (int i = 0; i < 6; ++i) ex[3 + i] = inr->biases[6 * (size_t)k + i];
     }
-  for (int f = 0; f <= F; ++f) {
-    const double ident[7] = {1, 0, 0, 0, 0, 0, 0};
-    const double* p = f < F ? w.fixed_poses_cw + 7 * (size_t)f : ident;
-    host_quat_to_R(p, &Rt_fix[12 * (size_t)f]);
-    Rt_fix[12 * (size_t)f + 9] = p[4]; Rt_fix[12 * (size_t)f + 10] = p[5]; Rt_fix[12 * (size_t)f + 11] = p[6];
-  }
+  host_fixed_to_Rt(w.fixed_poses_cw, w.F, (double*)(blob + pl.i_rtfix));
 }
 
-}  // namespace
-
-// W windows at once (W = 1: orbx_ba_solve_visual / global / inertial).  The all-reduce hook and the inertial mode apply to a
-// single window only.
-int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int W, BaWinHost* win,
-                   orbx_should_stop_fn should_stop, void* user, bool global_mode, const BaInertialHost* inr, bool single_call) {
-  // single_call: the one-window entry points (orbx_ba_solve_visual / global / inertial) answer ORBX_ERR_EMPTY as their return
-  // value where the reference returns None; the batch entry point reports it in the window's status and returns ORBX_OK,
-  // also for a batch of one (orbx.h; ADVICE r2)
-  // inr != nullptr: solve_inertial_ba (local_inertial_ba.rs:1074-1275).  `poses_cw` then holds the T_wc poses of the window
-  // and cfg carries max_iterations only; the point elimination, the per-keyframe 6x6 blocks and the Schur product are the
-  // visual solver's kernels, the 15-d keyframe states are assembled and solved on top of them.
-  const bool inertial = inr != nullptr;
-  const bool have_coll = h->allreduce != nullptr || h->rccl_comm != nullptr;
-  const bool dist = have_coll && !inertial && W == 1;
-  if (W <= 0) return ORBX_OK;
-  if ((inertial || have_coll) && W != 1)
-    return orbx_fail(h, ORBX_ERR_INVALID, "the inertial mode and the all-reduce hook take one window per call");
-  for (int w = 0; w < W; ++w) { *win[w].iterations = 0; *win[w].initial_error = 0.0; *win[w].final_error = 0.0; win[w].status = ORBX_OK; }
-  hipStream_t st = h->stream;
-  // ORBX_BA_TIMING=1: host-side phase times of this call on stderr (plan, preprocessing, descriptors + upload enqueue, launch
-  // enqueue, drain, unpack)
-  static const bool timing = getenv("ORBX_BA_TIMING") != nullptr;
-  double t_mark[8] = {0};
-  auto mark = [&](int i) { if (timing) t_mark[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  mark(0);
-
-  // ---- plan: dimensions and the layout of the buffers
-  std::vector<WinPlan> plan(W);
-  Carve cin, car, cout, ccnt;
-  // the fused loop (ba_step_kernel: back-substitution + the next iteration's build pass in one launch): the visual solve on one GPU.
-  // ORBX_BA_FUSED=0 keeps the six-launch iteration (A/B runs); the partitioned solve (its trial chi2 is a collective) keeps it always.
-  // (The inertial solve scatters its 15-d steps into the pose steps before this pass and adds its IMU terms in the decision: both outside it.)
+// ---- validate: the size limits of the kernels
+int ba_check_sizes(BaCtx& c) {
+  for (int w = 0; w < c.W; ++w)
+    if (6 * c.win[w].K > BA_MAX_N || c.win[w].K > BA_MAX_K)
+      return orbx_fail(c.h, ORBX_ERR_INVALID, "window %d: at most %d optimised keyframes per window", w, BA_MAX_N / 6);
+  return ORBX_OK;
+}
+// ... and of the inertial window, with its edge indices
+// (pure host validation comes before the first byte of the caller's memory is handed to the copy engine: ADVICE r4)
+int ba_check_inertial(BaCtx& c) {
+  if (!c.inertial) return ORBX_OK;
+  if (c.n15 > BA_MAX_N) return orbx_fail(c.h, ORBX_ERR_INVALID, "at most %d keyframes per inertial window", BA_MAX_N / 15);
+  const BaInertialHost* inr = c.inr;
+  for (int e = 0; e < inr->E; ++e)
+    if (inr->edge_kf[2 * e] < 0 || inr->edge_kf[2 * e] >= c.K0 || inr->edge_kf[2 * e + 1] < 0 || inr->edge_kf[2 * e + 1] >= c.K0)
+      return orbx_fail(c.h, ORBX_ERR_INVALID, "IMU edge %d: keyframe index out of range", e);
+  return ORBX_OK;
+}
+// The fused loop (ba_step_kernel: back-substitution + the next iteration's build pass in one launch): the visual solve on one GPU.
+// ORBX_BA_FUSED=0 keeps the six-launch iteration (A/B runs); the partitioned solve (its trial chi2 is a collective) keeps it always.
+// (The inertial solve scatters its 15-d steps into the pose steps before this pass and adds its IMU terms in the decision: both outside it.)
+bool ba_use_fused(bool dist, int W) {
   static const bool fused_off = [] { const char* e = getenv("ORBX_BA_FUSED"); return e && e[0] == '0'; }();
   // In a batch of 8 windows or more (16 lanes per point, several points per lane group) the two separate kernels stay.  Two fused forms
   // were measured there, both the same bits: point by point (no room for the build kernel's software pipeline over a group's points at
@@ -3479,54 +3544,62 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   // group's points inside one launch (back-substitution of all of them, trial positions parked in LDS, then the build kernel's own
   // pipelined loop; 161 VGPRs, no spills) 67.0 against 28.8 + 37.8 — the trial-chi2 pass it drops is what the second set's footprint
   // and the rejected step's matrices cost.  For one window the fused pass is 10.4 us against 6.1 + 7.7 and a launch less.
-  const bool fused = !fused_off && !dist && W < 8;
+  return !fused_off && !dist && W < 8;
+}
+// ---- plan: the dimensions of one window and how its reduced system is solved
+void ba_plan_dims(const BaWinHost& ww, bool inertial, WinPlan& pl) {
+  const int K = ww.K, M = ww.M;
+  BaDims& d = pl.d;
+  d.K = K; d.F = ww.F; d.M = M; d.N = ww.N;
+  d.P = std::max(16, (6 * K + 15) & ~15);
+  d.ntile = d.P / 16;
+  d.ncb = (d.ntile + 7) / 8;
+  // k-splits of the Schur product: ~32 map points each, at most 128 of them; a function of the window alone (never of the
+  // batch it travels in: the split fixes the summation order of S_red)
+  // (24 points per split measured best for one window of 20 keyframes / 2000 points — 8, 16, 24, 32, 48, 96, 192 tried: the
+  // Schur blocks take 8.5 us + 3.6 us per 8 points, the reduction of the partials grows with the number of splits)
+  d.ksplit = std::max(1, std::min(128, (M + BA_PPS_TARGET - 1) / BA_PPS_TARGET));
+  // (configs[4], 6 column-block pairs x 128 splits = 768 workgroups at 2 per CU: capping the splits at 100 / 85 / 64 / 48 / 32 to fit one
+  // round of workgroups measured 95.7 / 99.2 / 102.8 / 120.7 / 180.0 us against 94.1 — many short workgroups it stays)
+  d.pps = std::max(16, (((M + d.ksplit - 1) / d.ksplit) + 15) & ~15);   // (whole tiles of both Schur bodies: 8 and 16 points)
+  d.rows = 3 * d.pps * d.ksplit;
+  pl.n = 6 * K;
+  pl.np = 6 * (size_t)K + 3 * (size_t)M + (inertial ? 9 * (size_t)K : 0);
+  pl.n_upper = (size_t)d.ntile * (d.ntile + 1) / 2;
+  pl.rb_len = (size_t)pl.n * pl.n + 36 * (size_t)K + 2 * (size_t)pl.n + 2;
+  pl.lds_need = 8 * ((size_t)pl.n * pl.n + BA_SOLVE_THREADS);
+  pl.use_lds = (pl.lds_need <= BA_LDS_DYN_MAX && pl.n % 2 == 0 && pl.n <= 128) ? 1 : 0;   // (the LDS solve reads pairs of entries — even n, which 6K is — and lays its threads over a 128 x 128 grid)
+  if (!pl.use_lds && pl.n <= BA_TILED_MAX_N) {                          // lower 16 x 16 tiles in LDS: one launch where the multi-launch path takes n / 16 + 1
+    const size_t nt = (size_t)(pl.n + 15) / 16;
+    pl.use_lds = 2;
+    pl.lds_need = 8 * 256 * (nt * (nt + 1) / 2);
+  }
+  pl.n_res = 2.0 * (double)ww.N;
+}
+// ---- plan: per-window dimensions, the skip / ORBX_ERR_EMPTY rule and the layout of the buffers — pure, from sizes and mode flags
+void ba_plan(BaCtx& c) {
+  const bool inertial = c.inertial, fused = c.fused;
   const size_t dbl = fused ? 2 : 1;
-  const size_t i_wins = cin.take(sizeof(BaWin) * (size_t)W);
-  const size_t i_wins15 = cin.take(sizeof(BaWin));                      // inertial: the same window seen by the 15-d solve
-  const size_t i_outoff = cin.take(sizeof(size_t) * (size_t)W);
-  int live = 0, maxN = 0;
-  size_t obs_bytes = 0;
-  for (int w = 0; w < W; ++w) {
-    const BaWinHost& ww = win[w];
-    WinPlan& pl = plan[w];
+  Carve cin, car, cout, ccnt;
+  c.plan.assign((size_t)c.W, WinPlan{});
+  c.i_wins = cin.take(sizeof(BaWin) * (size_t)c.W);
+  c.i_wins15 = cin.take(sizeof(BaWin));                                // inertial: the same window seen by the 15-d solve
+  c.i_outoff = cin.take(sizeof(size_t) * (size_t)c.W);
+  for (int w = 0; w < c.W; ++w) {
+    const BaWinHost& ww = c.win[w];
+    WinPlan& pl = c.plan[(size_t)w];
     const int K = ww.K, F = ww.F, M = ww.M, N = ww.N;
     // local_ba_lm.rs:923-925 (with a partition the local N may be 0 while the global problem is not)
-    if ((6 * (size_t)K + 3 * (size_t)M == 0) || (N == 0 && !dist && !inertial)) {
-      win[w].status = ORBX_ERR_EMPTY;
+    if ((6 * (size_t)K + 3 * (size_t)M == 0) || (N == 0 && !c.dist && !inertial)) {
+      c.win[w].status = ORBX_ERR_EMPTY;
       pl.skip = 1;
-    } else { ++live; maxN = std::max(maxN, N); }
-    if (6 * K > BA_MAX_N || K > BA_MAX_K) return orbx_fail(h, ORBX_ERR_INVALID, "window %d: at most %d optimised keyframes per window", w, BA_MAX_N / 6);
-    BaDims& d = pl.d;
-    d.K = K; d.F = F; d.M = M; d.N = N;
-    d.P = std::max(16, (6 * K + 15) & ~15);
-    d.ntile = d.P / 16;
-    d.ncb = (d.ntile + 7) / 8;
-    // k-splits of the Schur product: ~32 map points each, at most 128 of them; a function of the window alone (never of the
-    // batch it travels in: the split fixes the summation order of S_red)
-    // (24 points per split measured best for one window of 20 keyframes / 2000 points — 8, 16, 24, 32, 48, 96, 192 tried: the
-    // Schur blocks take 8.5 us + 3.6 us per 8 points, the reduction of the partials grows with the number of splits)
-    d.ksplit = std::max(1, std::min(128, (M + BA_PPS_TARGET - 1) / BA_PPS_TARGET));
-    // (configs[4], 6 column-block pairs x 128 splits = 768 workgroups at 2 per CU: capping the splits at 100 / 85 / 64 / 48 / 32 to fit one
-    // round of workgroups measured 95.7 / 99.2 / 102.8 / 120.7 / 180.0 us against 94.1 — many short workgroups it stays)
-    d.pps = std::max(16, (((M + d.ksplit - 1) / d.ksplit) + 15) & ~15);   // (whole tiles of both Schur bodies: 8 and 16 points)
-    d.rows = 3 * d.pps * d.ksplit;
-    pl.n = 6 * K;
-    pl.np = 6 * (size_t)K + 3 * (size_t)M + (inertial ? 9 * (size_t)K : 0);
-    pl.n_upper = (size_t)d.ntile * (d.ntile + 1) / 2;
-    pl.rb_len = (size_t)pl.n * pl.n + 36 * (size_t)K + 2 * (size_t)pl.n + 2;
-    pl.lds_need = 8 * ((size_t)pl.n * pl.n + BA_SOLVE_THREADS);
-    pl.use_lds = (pl.lds_need <= BA_LDS_DYN_MAX && pl.n % 2 == 0 && pl.n <= 128) ? 1 : 0;   // (the LDS solve reads pairs of entries — even n, which 6K is — and lays its threads over a 128 x 128 grid)
-    if (!pl.use_lds && pl.n <= BA_TILED_MAX_N) {                          // lower 16 x 16 tiles in LDS: one launch where the multi-launch path takes n / 16 + 1
-      const size_t nt = (size_t)(pl.n + 15) / 16;
-      pl.use_lds = 2;
-      pl.lds_need = 8 * 256 * (nt * (nt + 1) / 2);
-    }
-    pl.n_res = 2.0 * (double)N;
+    } else { ++c.live; c.maxN = std::max(c.maxN, N); }
+    ba_plan_dims(ww, inertial, pl);
     const size_t n1 = (size_t)std::max(N, 1), m1 = (size_t)std::max(M, 1), k1 = (size_t)std::max(K, 1);
     pl.i_state = cin.take(sizeof(BaState));
     pl.i_params = cin.take(8 * std::max<size_t>(pl.np, 1));
     pl.i_rtfix = cin.take(8 * 12 * (size_t)(F + 1));
-    pl.i_obs = obs_bytes; obs_bytes += (ww.obs32 ? sizeof(orbx_ba_obs32) : sizeof(orbx_ba_obs)) * (size_t)(pl.skip ? 0 : N);   // (relative to the observation region, packed; multiples of 16)
+    pl.i_obs = c.obs_bytes; c.obs_bytes += (ww.obs32 ? sizeof(orbx_ba_obs32) : sizeof(orbx_ba_obs)) * (size_t)(pl.skip ? 0 : N);   // (relative to the observation region, packed; multiples of 16)
     pl.c_fill = ccnt.take(4 * m1); pl.c_kfstart = ccnt.take(4 * (k1 + 1));
     pl.a_ptstart = car.take(4 * (m1 + 1)); pl.a_okf = car.take(4 * n1); pl.a_ouv = car.take(16 * n1);
     pl.a_oflag = inertial ? car.take(4 * n1) : 0; pl.a_tmp = car.take(4 * n1);
@@ -3535,515 +3608,630 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
     pl.a_slot = car.take(4 * m1 * k1); pl.a_next = car.take(4 * n1); pl.a_kfobs = car.take(4 * n1); pl.a_kfpt = car.take(4 * n1);
     pl.a_mz = car.take(48 * m1 * dbl);
     pl.a_vinv = car.take(72 * m1 * dbl); pl.a_gl = car.take(24 * m1 * dbl); pl.a_vg = car.take(24 * m1 * dbl);
-    pl.a_pt = car.take(8 * (2 * dbl + 2) * m1);                            // pt_chi2 [dbl][m1] | pt_glsq [dbl][m1] | pt_dsq [m1] | pt_psq [m1]
+    pl.a_pt = car.take(8 * pt_sums_doubles(m1, dbl));
     pl.a_vraw = fused ? car.take(48 * m1 * dbl) : 0; pl.a_rej = fused ? car.take(8 * 18 * m1) : 0;
     pl.a_kfpart = car.take(8 * 33 * BA_KFSPLIT * k1);
-    pl.a_part = car.take(8 * pl.n_upper * d.ksplit * 256);
+    pl.a_part = car.take(8 * pl.n_upper * pl.d.ksplit * 256);
     pl.a_rb = car.take(8 * (pl.rb_len + 8));
-    pl.a_solve = car.take(8 * ((size_t)pl.n * pl.n + 21 * (size_t)pl.n + 640 + BA_SOLVE_THREADS));   // dp [n pad 16] | S [n*n] | b [n] | 1/L_jj [n pad 16] | (gradient slot [n pad 16]) | L11^-T rows [n / 16 + 1][256]
+    pl.a_solve = car.take(8 * (system_doubles((size_t)pl.n) + BA_SOLVE_THREADS));
     pl.a_res = car.take(8 * 16);
     pl.o_out = cout.take(8 * (8 + pl.np));
   }
-  if (live == 0) {
-    if (single_call) return orbx_fail(h, ORBX_ERR_EMPTY, "no parameters or no residuals");
-    return ORBX_OK;                                                      // every window reports ORBX_ERR_EMPTY in its status
-  }
-  const size_t small_bytes = cin.take(0);                                // descriptors, LM states, parameters, fixed poses of every window: ONE upload
-  const size_t a_cnt = car.take(ccnt.off);                               // per-point / per-keyframe counters of every window: ONE memset
-  // Where each window's observations come from: straight out of the caller's memory when that is pinned (the copy engine reads it where
-  // it lies: no host pass over the observations at all), else through the pinned blob (a plain copy, on the handle's workers when it is
-  // large).  Windows whose observations follow each other in memory travel as one copy.
-  struct Run { int w0, w1; size_t off, bytes; const void* src; bool direct; };
-  std::vector<Run> runs;
-  bool any_stage = false;
-  for (int w = 0; w < W; ++w) {
-    if (plan[w].skip || win[w].N == 0) continue;
-    const void* src = win[w].obs32 ? (const void*)win[w].obs32 : (const void*)win[w].obs;
-    const size_t bytes = (win[w].obs32 ? sizeof(orbx_ba_obs32) : sizeof(orbx_ba_obs)) * (size_t)win[w].N;
-    if (!runs.empty() && (const char*)runs.back().src + runs.back().bytes == (const char*)src && runs.back().off + runs.back().bytes == plan[w].i_obs) {
+  c.small_bytes = cin.off;                                               // descriptors, LM states, parameters, fixed poses of every window: ONE upload
+  c.cnt_bytes = ccnt.off;
+  c.a_cnt = car.take(ccnt.off);                                          // per-point / per-keyframe counters of every window: ONE memset
+  c.arena_bytes = car.off;
+  c.out_bytes = cout.off;
+  c.K0 = c.win[0].K; c.M0 = c.win[0].M; c.n15 = 15 * c.K0;
+}
+// ---- upload, planned: where each window's observations come from: straight out of the caller's memory when that is pinned (the copy
+// engine reads it where it lies: no host pass over the observations at all), else through the pinned blob (a plain copy, on the handle's
+// workers when it is large).  Windows whose observations follow each other in memory travel as one copy.
+void ba_plan_uploads(BaCtx& c) {
+  std::vector<Run>& runs = c.runs;
+  for (int w = 0; w < c.W; ++w) {
+    const BaWinHost& ww = c.win[w];
+    if (c.plan[(size_t)w].skip || ww.N == 0) continue;
+    const void* src = ww.obs32 ? (const void*)ww.obs32 : (const void*)ww.obs;
+    const size_t bytes = (ww.obs32 ? sizeof(orbx_ba_obs32) : sizeof(orbx_ba_obs)) * (size_t)ww.N;
+    if (!runs.empty() && (const char*)runs.back().src + runs.back().bytes == (const char*)src && runs.back().off + runs.back().bytes == c.plan[(size_t)w].i_obs) {
       runs.back().bytes += bytes; runs.back().w1 = w + 1;
-    } else runs.push_back(Run{w, w + 1, plan[w].i_obs, bytes, src, false});
+    } else runs.push_back(Run{w, w + 1, c.plan[(size_t)w].i_obs, bytes, src, false});
   }
   for (Run& r : runs) {
     r.direct = host_is_pinned(r.src, r.bytes);
-    if (!r.direct) any_stage = true;
+    if (!r.direct) c.any_stage = true;
   }
-  enum { B_IN, B_ARENA, B_OUT, B_IMU, B_S15 };
-  const int K0 = win[0].K, M0 = win[0].M;                               // inertial / partitioned: the one window
-  const int n15 = 15 * K0;
-  if (inertial && n15 > BA_MAX_N) return orbx_fail(h, ORBX_ERR_INVALID, "at most %d keyframes per inertial window", BA_MAX_N / 15);
-  // (pure host validation comes before the first byte of the caller's memory is handed to the copy engine: ADVICE r4)
-  if (inertial)
-    for (int e = 0; e < inr->E; ++e)
-      if (inr->edge_kf[2 * e] < 0 || inr->edge_kf[2 * e] >= K0 || inr->edge_kf[2 * e + 1] < 0 || inr->edge_kf[2 * e + 1] >= K0)
-        return orbx_fail(h, ORBX_ERR_INVALID, "IMU edge %d: keyframe index out of range", e);
-  if (int rc = orbx_reserve(h, h->ws_ba[B_IN], small_bytes + obs_bytes + 256)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_ba[B_ARENA], car.off)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_ba[B_OUT], cout.off)) return rc;
-  // inertial: edges (int [E][2]) | preint [E][11] | per-edge J^T J records;  dp15 [n15 pad 16] | S [n15^2] | b | 1/L_jj | gradient
-  if (int rc = orbx_reserve(h, h->ws_ba[B_IMU], inertial ? 8 * ((size_t)inr->E * (1 + 11 + IMU_REC) + 8) : 8)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_ba[B_S15], inertial ? 8 * ((size_t)n15 * n15 + 21 * (size_t)n15 + 640) : 8)) return rc;
-  if (int rc = pinned_reserve(h, &h->h_ba_in, &h->h_ba_in_bytes, small_bytes + (any_stage ? obs_bytes : 0))) return rc;
-  if (int rc = pinned_reserve(h, &h->h_ba_out, &h->h_ba_out_bytes, cout.off)) return rc;
+}
+// ---- reserve: the device workspaces and pinned blobs, and the base pointers into them
+int ba_reserve(BaCtx& c) {
+  orbx_handle* h = c.h;
+  if (int rc = orbx_reserve(h, h->ws_ba_in, c.small_bytes + c.obs_bytes + 256)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_ba_arena, c.arena_bytes)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_ba_out, c.out_bytes)) return rc;
+  // inertial: edges (int [E][2]) | preint [E][11] | per-edge J^T J records;  the 15-d reduced system
+  if (int rc = orbx_reserve(h, h->ws_ba_imu, c.inertial ? 8 * ((size_t)c.inr->E * (1 + 11 + IMU_REC) + 8) : 8)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_ba_s15, c.inertial ? 8 * system_doubles((size_t)c.n15) : 8)) return rc;
+  if (int rc = pinned_reserve(h, &h->h_ba_in, &h->h_ba_in_bytes, c.small_bytes + (c.any_stage ? c.obs_bytes : 0))) return rc;
+  if (int rc = pinned_reserve(h, &h->h_ba_out, &h->h_ba_out_bytes, c.out_bytes)) return rc;
   if (!h->h_abort) {
     ORBX_HIP(h, hipHostMalloc((void**)&h->h_abort, 64));
     ORBX_HIP(h, hipHostGetDevicePointer((void**)&h->d_abort, h->h_abort, 0));
   }
   *h->h_abort = 0;
-  uint8_t* hin = (uint8_t*)h->h_ba_in;
-  uint8_t* din = (uint8_t*)h->ws_ba[B_IN].p;
-  uint8_t* dar = (uint8_t*)h->ws_ba[B_ARENA].p;
-  double* dout = (double*)h->ws_ba[B_OUT].p;
-  uint8_t* dobs = din + small_bytes;                                     // the observation region of the device blob
-  uint8_t* hobs = hin + small_bytes;                                     // ... and of the pinned one (staged windows only)
-
-  // The second half of a batch (orbx_ba_solve_visual_batch) orders its uploads behind the first half's: both share one PCIe link, and the
-  // first half's kernels start when ITS bytes have arrived.  Whatever happens below, the first half opens the gate when it leaves.
-  struct GateOpen { std::atomic<int>* g; ~GateOpen() { if (g) g->store(1, std::memory_order_release); } } gate_open{h->ba_gate_signal};
-  bool direct_sent = false, drained = false;
-  // Once the copy engine has been pointed at the caller's page-locked observations, no return path may leave them in flight: an error
-  // return below (a HIP failure, the pool, the attribute check, the collective) first drains the stream, so the caller may reuse or free
-  // its buffer the moment the call is back, whatever it answered (ADVICE r4).
-  struct DrainOnLeave { hipStream_t st; const bool* sent; const bool* done; ~DrainOnLeave() { if (*sent && !*done) (void)hipStreamSynchronize(st); } } drain_on_leave{st, &direct_sent, &drained};
-  auto send_direct = [&]() -> int {
-    if (h->ba_gate_wait) {
-      while (h->ba_gate_wait->load(std::memory_order_acquire) == 0) std::this_thread::yield();
-      if (h->ba_gate_event) ORBX_HIP(h, hipStreamWaitEvent(st, h->ba_gate_event, 0));
-    }
-    direct_sent = true;                                                  // (set first: a failure part-way has already enqueued the earlier runs)
-    for (const Run& r : runs)
-      if (r.direct) ORBX_HIP(h, hipMemcpyAsync(dobs + r.off, r.src, r.bytes, hipMemcpyHostToDevice, st));
-    return ORBX_OK;
-  };
-  mark(1);
-  if (!h->ba_gate_wait) { if (int rc = send_direct()) return rc; }        // the copy engine starts at once; the host's O(K + M) part runs under it
-
-  // ---- host part, one window per task: LM state, pose parameters, points, fixed poses — and the observations of a window whose memory
-  // the copy engine cannot read, copied into the pinned blob (threads when that is large enough to pay for them)
-  {
-    auto work = [&](int w) {
-      const WinPlan& pl = plan[w];
-      BaState& s0 = *(BaState*)(hin + pl.i_state);
-      memset(&s0, 0, sizeof(s0));
-      s0.lambda = inertial ? inr->cfg->initial_lambda : 1e-3;            // :1006-1010 / local_inertial_ba.rs:1195
-      s0.gtol = inertial ? 1e-8 : cfg->gradient_tolerance;              // local_inertial_ba.rs:1213
-      s0.ptol = inertial ? 0.0 : cfg->param_tolerance;                  // the inertial loop has no step-size test
-      s0.done = pl.skip;                                                 // a window the reference answers None for (:923-925) never runs
-      if (!pl.skip) prep_window(win[w], pl, hin, inertial, inr);
-    };
-    size_t staged = 0;
-    std::vector<int> stage_w;
-    for (const Run& r : runs) if (!r.direct) { staged += r.bytes; for (int w = r.w0; w < r.w1; ++w) if (!plan[w].skip && win[w].N > 0) stage_w.push_back(w); }
-    auto stage = [&](int i) {
-      const int w = stage_w[(size_t)i];
-      if (win[w].obs32) memcpy(hobs + plan[w].i_obs, win[w].obs32, sizeof(orbx_ba_obs32) * (size_t)win[w].N);
-      else memcpy(hobs + plan[w].i_obs, win[w].obs, sizeof(orbx_ba_obs) * (size_t)win[w].N);
-    };
-    int nthr = (int)std::min<size_t>({stage_w.size(), (size_t)std::max(1u, std::thread::hardware_concurrency()), (size_t)16, staged / (1u << 20) + 1});
-    if (h->ba_pool_cap > 0) nthr = std::min(nthr, h->ba_pool_cap);
-    if (nthr > 1 && !h->ba_pool) {
-      try { h->ba_pool = new OrbxWorkPool((int)std::min<size_t>(15, std::max(1u, std::thread::hardware_concurrency()) - 1)); }
-      catch (...) { h->ba_pool = nullptr; }                              // no workers: this thread does it all
-    }
-    if (nthr > 1 && h->ba_pool) {
-      // the workers copy observations while this thread does the small per-window part: item 0 = that part, items 1.. = staged windows
-      const std::function<void(int)> job = [&](int i) { if (i == 0) { for (int w = 0; w < W; ++w) work(w); } else stage(i - 1); };
-      if (!h->ba_pool->run((int)stage_w.size() + 1, nthr - 1, job)) return orbx_fail(h, ORBX_ERR_HIP, "batch preprocessing: out of host memory");
-    } else {
-      for (int w = 0; w < W; ++w) work(w);
-      for (int i = 0; i < (int)stage_w.size(); ++i) stage(i);
-    }
+  c.hin = (uint8_t*)h->h_ba_in;
+  c.din = (uint8_t*)h->ws_ba_in.p;
+  c.dar = (uint8_t*)h->ws_ba_arena.p;
+  c.dout = (double*)h->ws_ba_out.p;
+  c.hout = (double*)h->h_ba_out;
+  c.dobs = c.din + c.small_bytes;                                        // the observation region of the device blob
+  c.hobs = c.hin + c.small_bytes;                                        // ... and of the pinned one (staged windows only)
+  c.hw = (BaWin*)(c.hin + c.i_wins);
+  c.d_wins = (BaWin*)(c.din + c.i_wins);
+  c.d_wins15 = (BaWin*)(c.din + c.i_wins15);
+  return ORBX_OK;
+}
+// ---- upload: the runs the copy engine reads out of the caller's memory.  The second half of a batch (orbx_ba_solve_visual_batch) orders
+// its uploads behind the first half's: both share one PCIe link, and the first half's kernels start when ITS bytes have arrived.
+int ba_send_direct(BaCtx& c) {
+  orbx_handle* h = c.h;
+  if (c.opts->gate_wait) {
+    while (c.opts->gate_wait->load(std::memory_order_acquire) == 0) std::this_thread::yield();
+    if (c.opts->gate_event) ORBX_HIP(h, hipStreamWaitEvent(c.st, c.opts->gate_event, 0));
   }
-  mark(2);
-  if (!direct_sent) { if (int rc = send_direct()) return rc; }
-  for (const Run& r : runs)
-    if (!r.direct) ORBX_HIP(h, hipMemcpyAsync(dobs + r.off, hobs + r.off, r.bytes, hipMemcpyHostToDevice, st));
-  // window descriptors + LM states into the blob
-  BaWin* hw = (BaWin*)(hin + i_wins);
-  size_t* hoff = (size_t*)(hin + i_outoff);
-  size_t lds_max = 0, tiled_lds_max = 0;
-  int any_tiled = 0;
+  c.direct_sent = true;                                                  // (set first: a failure part-way has already enqueued the earlier runs)
+  for (const Run& r : c.runs)
+    if (r.direct) ORBX_HIP(h, hipMemcpyAsync(c.dobs + r.off, r.src, r.bytes, hipMemcpyHostToDevice, c.st));
+  return ORBX_OK;
+}
+// ---- upload, host part, one window per task: LM state, pose parameters, points, fixed poses — and the observations of a window whose
+// memory the copy engine cannot read, copied into the pinned blob (threads when that is large enough to pay for them)
+int ba_host_prep(BaCtx& c) {
+  orbx_handle* h = c.h;
+  auto work = [&](int w) {
+    const WinPlan& pl = c.plan[(size_t)w];
+    BaState& s0 = *(BaState*)(c.hin + pl.i_state);
+    memset(&s0, 0, sizeof(s0));
+    s0.lambda = c.inertial ? c.inr->cfg->initial_lambda : 1e-3;          // :1006-1010 / local_inertial_ba.rs:1195
+    s0.gtol = c.inertial ? 1e-8 : c.cfg->gradient_tolerance;            // local_inertial_ba.rs:1213
+    s0.ptol = c.inertial ? 0.0 : c.cfg->param_tolerance;                // the inertial loop has no step-size test
+    s0.done = pl.skip;                                                   // a window the reference answers None for (:923-925) never runs
+    if (!pl.skip) prep_window(c.win[w], pl, c.hin, c.inertial, c.inr);
+  };
+  size_t staged = 0;
+  std::vector<int> stage_w;
+  for (const Run& r : c.runs) if (!r.direct) { staged += r.bytes; for (int w = r.w0; w < r.w1; ++w) if (!c.plan[(size_t)w].skip && c.win[w].N > 0) stage_w.push_back(w); }
+  auto stage = [&](int i) {
+    const int w = stage_w[(size_t)i];
+    const BaWinHost& ww = c.win[w];
+    if (ww.obs32) memcpy(c.hobs + c.plan[(size_t)w].i_obs, ww.obs32, sizeof(orbx_ba_obs32) * (size_t)ww.N);
+    else memcpy(c.hobs + c.plan[(size_t)w].i_obs, ww.obs, sizeof(orbx_ba_obs) * (size_t)ww.N);
+  };
+  int nthr = (int)std::min<size_t>({stage_w.size(), (size_t)std::max(1u, std::thread::hardware_concurrency()), (size_t)16, staged / (1u << 20) + 1});
+  if (c.opts->pool_cap > 0) nthr = std::min(nthr, c.opts->pool_cap);     // (the two halves of a batch share the cores)
+  if (nthr > 1 && !h->ba_pool) {
+    try { h->ba_pool = new OrbxWorkPool((int)std::min<size_t>(15, std::max(1u, std::thread::hardware_concurrency()) - 1)); }
+    catch (...) { h->ba_pool = nullptr; }                                // no workers: this thread does it all
+  }
+  if (nthr > 1 && h->ba_pool) {
+    // the workers copy observations while this thread does the small per-window part: item 0 = that part, items 1.. = staged windows
+    const std::function<void(int)> job = [&](int i) { if (i == 0) { for (int w = 0; w < c.W; ++w) work(w); } else stage(i - 1); };
+    if (!h->ba_pool->run((int)stage_w.size() + 1, nthr - 1, job)) return orbx_fail(h, ORBX_ERR_HIP, "batch preprocessing: out of host memory");
+  } else {
+    for (int w = 0; w < c.W; ++w) work(w);
+    for (int i = 0; i < (int)stage_w.size(); ++i) stage(i);
+  }
+  return ORBX_OK;
+}
+// ---- upload: the direct runs of a half that had to wait for the gate, then the staged runs
+int ba_send_staged(BaCtx& c) {
+  if (!c.direct_sent) { if (int rc = ba_send_direct(c)) return rc; }
+  for (const Run& r : c.runs)
+    if (!r.direct) ORBX_HIP(c.h, hipMemcpyAsync(c.dobs + r.off, c.hobs + r.off, r.bytes, hipMemcpyHostToDevice, c.st));
+  return ORBX_OK;
+}
+// ---- launch shape: one pass over the plans of the windows that run
+void ba_launch_shape(BaCtx& c) {
+  BaShape& s = c.s;
+  const int W = c.W, n_cu = c.h->n_cu;
+  const size_t wt = (size_t)(W + c.opts->peer_windows);                 // with the windows of a batch's other half, running on the peer stream at the same time
   // points per 32-lane group of the build / back-substitution launches: 1 for a few windows, 4 in a large batch (one block prologue —
   // the K rotations — per 32 points instead of per 8; 32-window batch: build 0.103 -> 0.096, back-substitution 0.068 -> 0.064 ms per iteration)
-  const int ppg = W >= 8 ? 4 : 1;
-  const int ptl = W >= 8 ? 16 : 32;   // lanes per point in those two kernels (group_sum<>: the sums do not depend on it)
-  const int one_launch_max_n = BF_MAX_N;   // reduced systems up to this size: the one-launch factorisation, larger ones one launch per panel
-  int any_one = 0;
-  int any_lds = 0, any_big = 0, n_big_max = 0, maxM = 0, maxK = 0, max_schur_blocks = 1, all_diag = 1, max_gather = 1, max_back = 1, max_asm = 1;
+  s.ppg = W >= 8 ? 4 : 1;
+  s.ptl = W >= 8 ? 16 : 32;   // lanes per point in those two kernels (group_sum<>: the sums do not depend on it)
   for (int w = 0; w < W; ++w) {
-    const WinPlan& pl = plan[w];
-    BaWin& b = hw[w];
-    memset(&b, 0, sizeof(b));
-    b.d = pl.d; b.n = pl.n; b.use_lds = pl.use_lds;
-    b.S = (BaState*)(din + pl.i_state);
-    b.P0 = (double*)(din + pl.i_params); b.P1 = (double*)(dar + pl.a_p1);
-    b.Rt_fix = (const double*)(din + pl.i_rtfix);
-    b.pt_start = (const int*)(dar + pl.a_ptstart); b.o_kf = (const int*)(dar + pl.a_okf);
-    b.o_uv = (const double*)(dar + pl.a_ouv);
-    b.kf_start = (const int*)(dar + a_cnt + pl.c_kfstart); b.kf_obs = (int*)(dar + pl.a_kfobs); b.kf_pt = (int*)(dar + pl.a_kfpt);
-    b.obs_raw = (const orbx_ba_obs*)(dobs + pl.i_obs); b.obs32 = win[w].obs32 ? 1 : 0; b.pt_fill = (int*)(dar + a_cnt + pl.c_fill); b.obs_tmp = (int*)(dar + pl.a_tmp);
-    b.o_flag = inertial ? (int*)(dar + pl.a_oflag) : nullptr;
-    b.Mz = (double*)(dar + pl.a_mz);
-    b.Vinv = (double*)(dar + pl.a_vinv); b.gl = (double*)(dar + pl.a_gl); b.vg = (double*)(dar + pl.a_vg);
-    const size_t m1 = (size_t)std::max(pl.d.M, 1);
-    b.pt_chi2 = (double*)(dar + pl.a_pt); b.pt_glsq = b.pt_chi2 + dbl * m1; b.pt_dsq = b.pt_glsq + dbl * m1; b.pt_psq = b.pt_dsq + m1;
-    b.dbl = fused ? 1 : 0; b.pad2_ = 0;
-    b.Vraw = fused ? (double*)(dar + pl.a_vraw) : nullptr; b.rej = fused ? (double*)(dar + pl.a_rej) : nullptr;
-    b.oP = (double*)(dar + pl.a_oP); b.Rt_cur = (double*)(dar + pl.a_rtcur);
-    b.slot_first = (int*)(dar + pl.a_slot); b.obs_next = (int*)(dar + pl.a_next);
-    b.kfpart = (double*)(dar + pl.a_kfpart); b.part = (double*)(dar + pl.a_part); b.rb = (double*)(dar + pl.a_rb);
-    b.dp = (double*)(dar + pl.a_solve);
-    b.Sg = b.dp + ((pl.n + 15) & ~15); b.bvec = b.Sg + (size_t)pl.n * pl.n; b.ginv = b.bvec + pl.n;
-    b.res = (double*)(dar + pl.a_res);
-    hoff[w] = pl.o_out / 8;
+    const WinPlan& pl = c.plan[(size_t)w];
     if (pl.skip) continue;                                             // (its LM state says done: set with the window's preprocessing)
-    if (pl.use_lds == 1 && !inertial) { any_lds = 1; lds_max = std::max(lds_max, pl.lds_need); }
-    else if (pl.use_lds == 2 && !inertial) { any_tiled = 1; tiled_lds_max = std::max(tiled_lds_max, pl.lds_need); }
-    else if (!inertial) { any_big = 1; if (pl.n > one_launch_max_n) n_big_max = std::max(n_big_max, pl.n); else any_one = 1; }
-    maxM = std::max(maxM, pl.d.M); maxK = std::max(maxK, pl.d.K);
-    max_schur_blocks = std::max(max_schur_blocks, pl.d.ncb * (pl.d.ncb + 1) / 2 * pl.d.ksplit);
-    if (pl.d.ncb != 1) all_diag = 0;
-    max_gather = std::max(max_gather, std::min(BA_GATHER_MAX_BLOCKS, (BA_GATHER_LANES * pl.n * ((pl.n + 1) / 2) + 255) / 256));
-    max_back = std::max(max_back, (std::max(ptl * ((pl.d.M + ppg - 1) / ppg), pl.n) + 255) / 256);
-    max_asm = std::max(max_asm, std::min(512, (pl.n * pl.n + 255) / 256));
+    if (pl.use_lds == 1 && !c.inertial) { s.any_lds = 1; s.lds_max = std::max(s.lds_max, pl.lds_need); }
+    else if (pl.use_lds == 2 && !c.inertial) { s.any_tiled = 1; s.tiled_lds_max = std::max(s.tiled_lds_max, pl.lds_need); }
+    else if (!c.inertial) { s.any_big = 1; if (pl.n > BA_ONE_LAUNCH_MAX_N) s.n_big_max = std::max(s.n_big_max, pl.n); else s.any_one = 1; }
+    s.maxM = std::max(s.maxM, pl.d.M); s.maxK = std::max(s.maxK, pl.d.K);
+    s.max_schur_blocks = std::max(s.max_schur_blocks, pl.d.ncb * (pl.d.ncb + 1) / 2 * pl.d.ksplit);
+    if (pl.d.ncb != 1) s.all_diag = 0;
+    s.max_gather = std::max(s.max_gather, std::min(BA_GATHER_MAX_BLOCKS, (BA_GATHER_LANES * pl.n * ((pl.n + 1) / 2) + 255) / 256));
+    s.max_back = std::max(s.max_back, (std::max(s.ptl * ((pl.d.M + s.ppg - 1) / s.ppg), pl.n) + 255) / 256);
+    s.max_asm = std::max(s.max_asm, std::min(512, (pl.n * pl.n + 255) / 256));
   }
   // the build launch holds 3 workgroups per CU (166 VGPRs): a grid past that runs a second, mostly empty round of workgroups, so a large
   // batch gives each group as many points as keep the grid (with the peer half's windows) within one round
-  int ppg_build = ppg;
-  if (ptl == 16) {
-    const size_t cap = 3 * (size_t)h->n_cu, wt = (size_t)(W + h->ba_peer_windows);
-    while (ppg_build < 16 && wt * (size_t)((((maxM + ppg_build - 1) / ppg_build) * ptl + 255) / 256) > cap) ++ppg_build;
+  s.ppg_build = s.ppg;
+  if (s.ptl == 16) {
+    const size_t cap = 3 * (size_t)n_cu;
+    while (s.ppg_build < 16 && wt * (size_t)((((s.maxM + s.ppg_build - 1) / s.ppg_build) * s.ptl + 255) / 256) > cap) ++s.ppg_build;
   }
-  const int pt_groups = (maxM + ppg_build - 1) / ppg_build;
+  s.pt_groups = (s.maxM + s.ppg_build - 1) / s.ppg_build;
   // a batch large enough to fill the chip with one workgroup per (window, gather share): the Schur workgroups add their share's partials
   // themselves (BaWin::part_sums) and the gather reads one tile set per share
   // (the windows of a batch's other half, running on the peer stream at the same time, count: together they fill the chip)
-  const bool schur_sums = all_diag && W > 1 && (size_t)(W + h->ba_peer_windows) * BA_GATHER_LANES >= (size_t)h->n_cu;
-  if (schur_sums) for (int w = 0; w < W; ++w) hw[w].part_sums = 1;
-  BaCam bc{cam->fx, cam->fy, cam->cx, cam->cy, inertial ? inr->cfg->huber_threshold_mono : cfg->huber_threshold, global_mode ? 1 : 0,
-           inertial ? 1 : 0, inertial ? inr->cfg->huber_threshold_stereo : 0.0, nullptr};
-  BaInertialDev ind{};
-  double* imu_buf = nullptr;
-  BaWin* d_wins = (BaWin*)(din + i_wins);
-  BaWin* d_wins15 = (BaWin*)(din + i_wins15);
-  double *dp15 = nullptr, *gfull = nullptr;
-  if (inertial) {
-    bc.o_flag = hw[0].o_flag;
-    int* d_edges = (int*)h->ws_ba[B_IMU].p;
-    double* d_pre = (double*)h->ws_ba[B_IMU].p + inr->E;               // 2 ints per edge = 1 double slot per edge
-    imu_buf = d_pre + 11 * (size_t)inr->E;
-    if (inr->E > 0) {
-      ORBX_HIP(h, hipMemcpyAsync(d_edges, inr->edge_kf, 8 * (size_t)inr->E, hipMemcpyHostToDevice, st));
-      ORBX_HIP(h, hipMemcpyAsync(d_pre, inr->preint, 88 * (size_t)inr->E, hipMemcpyHostToDevice, st));
-    }
-    ind.K = K0; ind.M = M0; ind.E = inr->E;
-    ind.gw = std::sqrt(inr->cfg->gyro_rw_info); ind.aw = std::sqrt(inr->cfg->accel_rw_info);
-    ind.edge_kf = d_edges; ind.preint = d_pre;
-    // the 15-d system: dp15 [n15 pad 16] | S [n15^2] | b [n15] | 1/L_jj [n15] | gradient [n15]
-    BaWin& b15 = *(BaWin*)(hin + i_wins15);
-    b15 = hw[0];
-    b15.n = n15; b15.use_lds = n15 <= BA_TILED_MAX_N ? 2 : 0;             // (the 15-d system of up to 11 keyframes: the tiled LDS solve)
-    if (b15.use_lds == 2) { const size_t nt = (size_t)(n15 + 15) / 16; tiled_lds_max = 8 * 256 * (nt * (nt + 1) / 2); }
-    dp15 = (double*)h->ws_ba[B_S15].p;
-    b15.dp = dp15;
-    b15.Sg = dp15 + ((n15 + 15) & ~15); b15.bvec = b15.Sg + (size_t)n15 * n15; b15.ginv = b15.bvec + n15;
-    gfull = b15.ginv + n15;
-  }
-  // the window descriptors, LM states, parameters and fixed poses of every window: one upload
-  ORBX_HIP(h, hipMemcpyAsync(din, hin, small_bytes, hipMemcpyHostToDevice, st));
-  if (h->ba_gate_signal) {                                                // this half's bytes are on their way: the other half's may follow
-    if (h->ba_up_event) ORBX_HIP(h, hipEventRecord(h->ba_up_event, st));
-    h->ba_gate_signal->store(1, std::memory_order_release);
-  }
-  mark(3);
-  {
-    // process-wide function attributes, set once per device to the largest size any window may ask for.  The result is kept per
-    // device: a failed attempt is reported by every call that finds it, and retried — never a launch with the attribute unset.
-    static std::mutex attr_m;
-    static int attr_state[64];                                         // 0 = not yet, 1 = set
-    std::lock_guard<std::mutex> g(attr_m);
-    if (attr_state[h->device & 63] != 1) {
-      hipError_t e_attr = hipFuncSetAttribute((const void*)ba_solve_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_LDS_DYN_MAX);
-      if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_solve_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_TILED_LDS_MAX);
-      if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_solve_inertial_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_TILED_LDS_MAX);
-      if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_kf_schur_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCHW_LDS_BYTES);
-      if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_schur_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCHW_LDS_BYTES);
-      if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_big_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_LDS_BYTES);
-      ORBX_HIP(h, e_attr);
-      // what the kernels declare statically plus the largest dynamic size must fit the CU's 160 KB — checked against the code object itself,
-      // so a static array that grows fails here, by name, and not as a launch error of the one window size that needs the maximum
-      const struct { const void* f; size_t dyn; const char* name; } lds[] = {
-          {(const void*)ba_solve_lds_kernel, BA_LDS_DYN_MAX, "ba_solve_lds_kernel"}, {(const void*)ba_solve_tiled_kernel, BA_TILED_LDS_MAX, "ba_solve_tiled_kernel"},
-          {(const void*)ba_solve_inertial_tiled_kernel, BA_TILED_LDS_MAX, "ba_solve_inertial_tiled_kernel"}, {(const void*)ba_kf_schur_kernel<true>, SCHW_LDS_BYTES, "ba_kf_schur_kernel"},
-          {(const void*)ba_schur_kernel<true>, SCHW_LDS_BYTES, "ba_schur_kernel"}, {(const void*)ba_big_factor_kernel, BF_LDS_BYTES, "ba_big_factor_kernel"}};
-      for (const auto& k : lds) {
-        hipFuncAttributes fa;
-        ORBX_HIP(h, hipFuncGetAttributes(&fa, k.f));
-        if (fa.sharedSizeBytes + k.dyn > 160 * 1024)
-          return orbx_fail(h, ORBX_ERR_INVALID, "internal: %s needs %zu B static + %zu B dynamic LDS, more than the 160 KB of a CU", k.name, (size_t)fa.sharedSizeBytes, k.dyn);
-      }
-      attr_state[h->device & 63] = 1;
-    }
-  }
+  s.schur_sums = s.all_diag && W > 1 && wt * BA_GATHER_LANES >= (size_t)n_cu;
   // k-splits per workgroup of the batch's one-column-block Schur launch: as many as make the launch about one workgroup per CU (a
   // workgroup owns its CU: 102 KB of LDS); the partials do not depend on it
-  int schur_spb = all_diag ? std::max(1, std::min(16, (int)(((size_t)(W + h->ba_peer_windows) * max_schur_blocks + h->n_cu - 1) / std::max(1, h->n_cu)))) : 1;
-  if (schur_sums) schur_spb = 1;                                          // (a workgroup's range is its window's share: set in the kernel)
-  const BaWin& w0 = hw[0];                                              // host copies of the device pointers of window 0
-  double* res0 = w0.res;
+  s.schur_spb = s.all_diag ? std::max(1, std::min(16, (int)((wt * s.max_schur_blocks + n_cu - 1) / std::max(1, n_cu)))) : 1;
+  if (s.schur_sums) s.schur_spb = 1;                                      // (a workgroup's range is its window's share: set in the kernel)
+  // the 15-d system of up to 11 keyframes: the tiled LDS solve
+  if (c.inertial && c.n15 <= BA_TILED_MAX_N) { const size_t nt = (size_t)(c.n15 + 15) / 16; s.tiled_lds_max = 8 * 256 * (nt * (nt + 1) / 2); }
+}
+// ---- bind: a window's plan and the base pointers -> its descriptor
+void ba_bind_window(const BaCtx& c, int w, BaWin& b) {
+  const WinPlan& pl = c.plan[(size_t)w];
+  uint8_t *din = c.din, *dar = c.dar, *dcnt = c.dar + c.a_cnt;
+  const size_t dbl = c.fused ? 2 : 1;
+  memset(&b, 0, sizeof(b));
+  b.d = pl.d; b.n = pl.n; b.use_lds = pl.use_lds; b.part_sums = c.s.schur_sums ? 1 : 0;
+  b.S = (BaState*)(din + pl.i_state);
+  b.P0 = (double*)(din + pl.i_params); b.P1 = (double*)(dar + pl.a_p1);
+  b.Rt_fix = (const double*)(din + pl.i_rtfix);
+  b.pt_start = (const int*)(dar + pl.a_ptstart); b.o_kf = (const int*)(dar + pl.a_okf);
+  b.o_uv = (const double*)(dar + pl.a_ouv);
+  b.kf_start = (const int*)(dcnt + pl.c_kfstart); b.kf_obs = (int*)(dar + pl.a_kfobs); b.kf_pt = (int*)(dar + pl.a_kfpt);
+  b.obs_raw = (const orbx_ba_obs*)(c.dobs + pl.i_obs); b.obs32 = c.win[w].obs32 ? 1 : 0; b.pt_fill = (int*)(dcnt + pl.c_fill); b.obs_tmp = (int*)(dar + pl.a_tmp);
+  b.o_flag = c.inertial ? (int*)(dar + pl.a_oflag) : nullptr;
+  b.Mz = (double*)(dar + pl.a_mz);
+  b.Vinv = (double*)(dar + pl.a_vinv); b.gl = (double*)(dar + pl.a_gl); b.vg = (double*)(dar + pl.a_vg);
+  bind_pt_sums(b, (double*)(dar + pl.a_pt), (size_t)std::max(pl.d.M, 1), dbl);
+  b.dbl = c.fused ? 1 : 0; b.pad2_ = 0;
+  b.Vraw = c.fused ? (double*)(dar + pl.a_vraw) : nullptr; b.rej = c.fused ? (double*)(dar + pl.a_rej) : nullptr;
+  b.oP = (double*)(dar + pl.a_oP); b.Rt_cur = (double*)(dar + pl.a_rtcur);
+  b.slot_first = (int*)(dar + pl.a_slot); b.obs_next = (int*)(dar + pl.a_next);
+  b.kfpart = (double*)(dar + pl.a_kfpart); b.part = (double*)(dar + pl.a_part); b.rb = (double*)(dar + pl.a_rb);
+  bind_system(b, (double*)(dar + pl.a_solve), pl.n);
+  b.res = (double*)(dar + pl.a_res);
+}
+// ... of every window, with the output offsets and the camera, into the pinned blob
+void ba_bind(BaCtx& c) {
+  size_t* hoff = (size_t*)(c.hin + c.i_outoff);
+  for (int w = 0; w < c.W; ++w) {
+    ba_bind_window(c, w, c.hw[w]);
+    hoff[w] = c.plan[(size_t)w].o_out / 8;
+  }
+  const orbx_camera* cam = c.cam;
+  c.bc = BaCam{cam->fx, cam->fy, cam->cx, cam->cy, c.inertial ? c.inr->cfg->huber_threshold_mono : c.cfg->huber_threshold, c.global_mode ? 1 : 0,
+               c.inertial ? 1 : 0, c.inertial ? c.inr->cfg->huber_threshold_stereo : 0.0, nullptr};
+}
+// ... and of the inertial window: its IMU edges and preintegrations (uploaded here), and the window as the 15-d solve sees it
+int ba_bind_inertial(BaCtx& c) {
+  if (!c.inertial) return ORBX_OK;
+  orbx_handle* h = c.h;
+  const BaInertialHost* inr = c.inr;
+  c.bc.o_flag = c.hw[0].o_flag;
+  int* d_edges = (int*)h->ws_ba_imu.p;
+  double* d_pre = (double*)h->ws_ba_imu.p + inr->E;                    // 2 ints per edge = 1 double slot per edge
+  c.imu_buf = d_pre + 11 * (size_t)inr->E;
+  if (inr->E > 0) {
+    ORBX_HIP(h, hipMemcpyAsync(d_edges, inr->edge_kf, 8 * (size_t)inr->E, hipMemcpyHostToDevice, c.st));
+    ORBX_HIP(h, hipMemcpyAsync(d_pre, inr->preint, 88 * (size_t)inr->E, hipMemcpyHostToDevice, c.st));
+  }
+  BaInertialDev& ind = c.ind;
+  ind.K = c.K0; ind.M = c.M0; ind.E = inr->E;
+  ind.gw = std::sqrt(inr->cfg->gyro_rw_info); ind.aw = std::sqrt(inr->cfg->accel_rw_info);
+  ind.edge_kf = d_edges; ind.preint = d_pre;
+  BaWin& b15 = *(BaWin*)(c.hin + c.i_wins15);
+  b15 = c.hw[0];
+  b15.n = c.n15; b15.use_lds = c.n15 <= BA_TILED_MAX_N ? 2 : 0;         // (the 15-d system of up to 11 keyframes: the tiled LDS solve)
+  c.dp15 = (double*)h->ws_ba_s15.p;
+  c.gfull = bind_system(b15, c.dp15, c.n15);
+  return ORBX_OK;
+}
+// ---- upload: the window descriptors, LM states, parameters and fixed poses of every window: one upload.  With it this half's bytes are
+// on their way: the other half's may follow.
+int ba_send_small(BaCtx& c) {
+  orbx_handle* h = c.h;
+  ORBX_HIP(h, hipMemcpyAsync(c.din, c.hin, c.small_bytes, hipMemcpyHostToDevice, c.st));
+  if (c.opts->gate_signal) {
+    if (h->ba_up_event) ORBX_HIP(h, hipEventRecord(h->ba_up_event, c.st));
+    c.opts->gate_signal->store(1, std::memory_order_release);
+  }
+  return ORBX_OK;
+}
+// ---- function attributes: process-wide, set once per device to the largest size any window may ask for.  The result is kept
+// per device: a failed attempt is reported by every call that finds it, and retried — never a launch with the attribute unset.
+int ba_set_func_attributes(orbx_handle* h) {
+  static std::mutex attr_m;
+  static int attr_state[64];                                           // 0 = not yet, 1 = set
+  std::lock_guard<std::mutex> g(attr_m);
+  if (attr_state[h->device & 63] == 1) return ORBX_OK;
+  hipError_t e_attr = hipFuncSetAttribute((const void*)ba_solve_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_LDS_DYN_MAX);
+  if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_solve_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_TILED_LDS_MAX);
+  if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_solve_inertial_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_TILED_LDS_MAX);
+  if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_kf_schur_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCHW_LDS_BYTES);
+  if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_schur_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCHW_LDS_BYTES);
+  if (e_attr == hipSuccess) e_attr = hipFuncSetAttribute((const void*)ba_big_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_LDS_BYTES);
+  ORBX_HIP(h, e_attr);
+  // what the kernels declare statically plus the largest dynamic size must fit the CU's 160 KB — checked against the code object itself,
+  // so a static array that grows fails here, by name, and not as a launch error of the one window size that needs the maximum
+  const struct { const void* f; size_t dyn; const char* name; } lds[] = {
+      {(const void*)ba_solve_lds_kernel, BA_LDS_DYN_MAX, "ba_solve_lds_kernel"}, {(const void*)ba_solve_tiled_kernel, BA_TILED_LDS_MAX, "ba_solve_tiled_kernel"},
+      {(const void*)ba_solve_inertial_tiled_kernel, BA_TILED_LDS_MAX, "ba_solve_inertial_tiled_kernel"}, {(const void*)ba_kf_schur_kernel<true>, SCHW_LDS_BYTES, "ba_kf_schur_kernel"},
+      {(const void*)ba_schur_kernel<true>, SCHW_LDS_BYTES, "ba_schur_kernel"}, {(const void*)ba_big_factor_kernel, BF_LDS_BYTES, "ba_big_factor_kernel"}};
+  for (const auto& k : lds) {
+    hipFuncAttributes fa;
+    ORBX_HIP(h, hipFuncGetAttributes(&fa, k.f));
+    if (fa.sharedSizeBytes + k.dyn > 160 * 1024)
+      return orbx_fail(h, ORBX_ERR_INVALID, "internal: %s needs %zu B static + %zu B dynamic LDS, more than the 160 KB of a CU", k.name, (size_t)fa.sharedSizeBytes, k.dyn);
+  }
+  attr_state[h->device & 63] = 1;
+  return ORBX_OK;
+}
+// in-place sum over the ranks of a partitioned solve, ordered on the stream
+int ba_allreduce(BaCtx& c, double* dptr, size_t cnt) {
+  orbx_handle* h = c.h;
+  if (!c.dist) return ORBX_OK;
+  if (h->rccl_comm) return orbx_rccl_allreduce_sum(h, dptr, cnt, c.st);       // native: ncclAllReduce(ncclDouble, ncclSum) on this stream
+  if (h->allreduce(h->allreduce_user, dptr, cnt, (void*)c.st) != 0) return orbx_fail(h, ORBX_ERR_HIP, "all-reduce hook failed");
+  return ORBX_OK;
+}
+void ba_enqueue_chi2_sum(BaCtx& c, int which, int three) {
+  const BaWin& w0 = c.hw[0];
+  hipLaunchKernelGGL(ba_sum3_kernel, dim3(1, c.W), dim3(256), 0, c.st, c.d_wins, three);
+  if (c.inertial && c.inr->E > 0) {                                      // + IMU and bias-random-walk residuals (:661-698)
+    hipLaunchKernelGGL(ba_imu_kernel, dim3(c.inr->E), dim3(64), 0, c.st, w0.S, w0.P0, w0.P1, which, 0, c.ind, c.imu_buf);
+    hipLaunchKernelGGL(ba_imu_addchi_kernel, dim3(1), dim3(1), 0, c.st, w0.S, c.inr->E, c.imu_buf, w0.res + (three ? 5 : 12), 0);
+  }
+}
+// ---- enqueue prep: the observation CSR of every window (see ba_prep_count_kernel)
+int ba_enqueue_csr(BaCtx& c) {
+  ORBX_HIP(c.h, hipMemsetAsync(c.dar + c.a_cnt, 0, c.cnt_bytes, c.st));
+  if (c.maxN > 0) {
+    ProfScope ps(c.h, "ba_prep");
+    const dim3 go((c.maxN + BA_PREP_OPB - 1) / BA_PREP_OPB, c.W);
+    hipLaunchKernelGGL(ba_prep_count_kernel, go, dim3(256), 0, c.st, c.d_wins);
+    hipLaunchKernelGGL(ba_prep_scan_kernel, dim3(1, c.W), dim3(1024), 0, c.st, c.d_wins);
+    hipLaunchKernelGGL(ba_prep_place_kernel, go, dim3(256), 0, c.st, c.d_wins);
+    if (c.s.maxM > 0) hipLaunchKernelGGL(ba_prep_order_kernel, dim3((c.s.maxM * 16 + 255) / 256, c.W), dim3(256), 0, c.st, c.d_wins);
+  }
+  return ORBX_OK;
+}
+// ---- partition head.  Partitioned over ranks: every rank must issue the same sequence of collectives, whatever its own should_stop() or
+// its own partition says — so the decisions travel with the collectives.  [total residual count | stop votes for
+// iteration 0 | ranks with a bad observation index] first (host-read), then the votes for iteration i+1 ride on the second
+// all-reduce of iteration i (res[8], read by ba_decide_kernel); a rank whose should_stop() fired keeps enqueueing.
+int ba_partition_head(BaCtx& c) {
+  c.n_res = c.plan[0].n_res;
+  c.votes.assign((size_t)std::max(c.cfg->max_iterations, 0) + 2, 0.0);
+  if (!c.dist) return ORBX_OK;
+  orbx_handle* h = c.h;
+  double* res0 = c.hw[0].res;
+  c.my_stop = c.should_stop && c.should_stop(c.user);
+  int bad0 = 0;                                                           // this rank's index check, from the device (the stream is drained here anyway)
+  ORBX_HIP(h, hipMemcpyAsync(&bad0, &c.hw[0].S->bad, sizeof(int), hipMemcpyDeviceToHost, c.st));
+  ORBX_HIP(h, hipStreamSynchronize(c.st));
+  const double head[3] = {c.n_res, c.my_stop ? 1.0 : 0.0, bad0 != 0 ? 1.0 : 0.0};
+  ORBX_HIP(h, hipMemcpyAsync(res0 + 8, head, 24, hipMemcpyHostToDevice, c.st));
+  ORBX_HIP(h, hipStreamSynchronize(c.st));
+  if (int rc = ba_allreduce(c, res0 + 8, 3)) return rc;
+  double tot[3];
+  ORBX_HIP(h, hipMemcpyAsync(tot, res0 + 8, 24, hipMemcpyDeviceToHost, c.st));
+  ORBX_HIP(h, hipStreamSynchronize(c.st));
+  if (tot[2] > 0.0) return orbx_fail(h, ORBX_ERR_INVALID, "an observation index is out of range on %d rank(s)%s", (int)tot[2], bad0 != 0 ? " (this one too)" : "");
+  c.n_res = tot[0];
+  if (c.n_res == 0.0) return orbx_fail(h, ORBX_ERR_EMPTY, "no residuals on any rank");
+  c.my_stop = tot[1] > 0.0;                                              // the collective decision for iteration 0
+  return ORBX_OK;
+}
+// ---- enqueue prep: per (point, keyframe) slots and the keyframes' observation lists
+void ba_enqueue_slots(BaCtx& c) {
+  if (c.s.maxM <= 0 || c.s.maxK <= 0) return;
+  ProfScope ps(c.h, "ba_slots_kflist");
+  hipLaunchKernelGGL(ba_slots_kernel, dim3((c.s.maxM + BA_SLOT_PPB - 1) / BA_SLOT_PPB, c.W), dim3(256), 0, c.st, c.d_wins);
+  hipLaunchKernelGGL(ba_kflist_kernel, dim3(c.s.maxK, c.W), dim3(BA_KFL_THREADS), 0, c.st, c.d_wins);
+}
+// initial error (:1000-1001) -> res[12]
+void ba_enqueue_initial_error(BaCtx& c) {
+  ProfScope ps(c.h, "ba_chi2");
+  if (c.s.maxM > 0) hipLaunchKernelGGL(ba_chi2_kernel, dim3((c.s.maxM * 32 + 255) / 256, c.W), dim3(256), 0, c.st, c.d_wins, c.bc, 0);
+  ba_enqueue_chi2_sum(c, 0, 0);
+}
+// ---- enqueue reduced solve, systems in global memory (assembled by the caller): the one-launch factorisation with its back-substitution
+// for the windows up to BA_ONE_LAUNCH_MAX_N (any_one), one launch per panel and a back-substitution launch for the larger ones
+// (n_big_max: the largest of them, 0 = none).  wins / gy: the visual windows of the batch, or the inertial window's 15-d descriptor alone.
+void ba_enqueue_big_solve(hipStream_t st, BaWin* wins, int gy, bool any_one, int n_big_max) {
+  if (any_one) hipLaunchKernelGGL(ba_big_factor_kernel, dim3(1, gy), dim3(BF_THREADS), BF_LDS_BYTES, st, wins);
+  for (int c0 = 0; c0 < n_big_max; c0 += BB_NB) {
+    const int nt = (n_big_max - c0 + 15) / 16, units = c0 > 0 ? nt * (nt - 1) / 2 : 0;
+    hipLaunchKernelGGL(ba_big_step_kernel, dim3(1 + (units + BB_STEP_WAVES - 1) / BB_STEP_WAVES, gy), dim3(BB_STEP_THREADS), 0, st, wins, c0, BA_ONE_LAUNCH_MAX_N);
+  }
+  if (n_big_max > 0) hipLaunchKernelGGL(ba_big_back_kernel, dim3(1, gy), dim3(256), 0, st, wins, BA_ONE_LAUNCH_MAX_N);
+}
+void ba_enqueue_solve_inertial(BaCtx& c) {
+  ProfScope ps(c.h, "ba_inertial_solve");
+  const BaWin& w0 = c.hw[0];
+  const BaWin& b15 = *(const BaWin*)(c.hin + c.i_wins15);
+  const int n15 = c.n15;
+  if (c.inr->E > 0) hipLaunchKernelGGL(ba_imu_kernel, dim3(c.inr->E), dim3(64), 0, c.st, w0.S, w0.P0, w0.P1, 0, 1, c.ind, c.imu_buf);
+  if (n15 <= BA_TILED_MAX_N) hipLaunchKernelGGL(ba_solve_inertial_tiled_kernel, dim3(1, 1), dim3(BA_SOLVE_THREADS), c.s.tiled_lds_max, c.st, c.d_wins15, c.ind, (const double*)c.imu_buf);
+  else {
+    hipLaunchKernelGGL(ba_inertial_assemble_kernel, dim3(1), dim3(256), 0, c.st, w0.S, w0.P0, w0.P1, c.ind, w0.rb, c.imu_buf, b15.Sg, b15.bvec, c.gfull, w0.res);
+    ba_enqueue_big_solve(c.st, c.d_wins15, 1, n15 <= BA_ONE_LAUNCH_MAX_N, n15 > BA_ONE_LAUNCH_MAX_N ? n15 : 0);
+  }
+  hipLaunchKernelGGL(ba_inertial_scatter_kernel, dim3(1), dim3(256), 0, c.st, w0.S, w0.P0, w0.P1, c.K0, c.M0, c.dp15, w0.dp);
+}
+void ba_enqueue_solve_visual(BaCtx& c) {
+  ProfScope ps(c.h, "ba_solve_kernel");
+  const BaShape& s = c.s;
+  const dim3 gW1(1, c.W);
+  if (s.any_lds) hipLaunchKernelGGL(ba_solve_lds_kernel, gW1, dim3(BA_SOLVE_THREADS), s.lds_max, c.st, c.d_wins);
+  if (s.any_big || s.any_tiled) hipLaunchKernelGGL(ba_big_assemble_kernel, dim3(s.max_asm, c.W), dim3(256), 0, c.st, c.d_wins);
+  if (s.any_tiled) hipLaunchKernelGGL(ba_solve_tiled_kernel, gW1, dim3(BA_SOLVE_THREADS), s.tiled_lds_max, c.st, c.d_wins);
+  if (s.any_big) ba_enqueue_big_solve(c.st, c.d_wins, c.W, s.any_one != 0, s.n_big_max);
+}
+// ---- enqueue iteration: build (unless the step kernel of the iteration before has done it), keyframe partials + Schur product, gather,
+// reduced solve, back-substitution (fused: with the next build pass), decision
+int ba_enqueue_iteration(BaCtx& c, int iter, bool init_from_first) {
+  orbx_handle* h = c.h;
+  hipStream_t st = c.st;
+  const BaShape& s = c.s;
+  const int W = c.W;
   const dim3 gW1(1, W);
-  auto allreduce = [&](double* dptr, size_t cnt) -> int {
-    if (!dist) return ORBX_OK;
-    if (h->rccl_comm) return orbx_rccl_allreduce_sum(h, dptr, cnt, st);       // native: ncclAllReduce(ncclDouble, ncclSum) on this stream
-    if (h->allreduce(h->allreduce_user, dptr, cnt, (void*)st) != 0) return orbx_fail(h, ORBX_ERR_HIP, "all-reduce hook failed");
-    return ORBX_OK;
-  };
-  auto chi2_sum = [&](int which, int three) {
-    hipLaunchKernelGGL(ba_sum3_kernel, gW1, dim3(256), 0, st, d_wins, three);
-    if (inertial && inr->E > 0) {                                        // + IMU and bias-random-walk residuals (:661-698)
-      hipLaunchKernelGGL(ba_imu_kernel, dim3(inr->E), dim3(64), 0, st, w0.S, w0.P0, w0.P1, which, 0, ind, imu_buf);
-      hipLaunchKernelGGL(ba_imu_addchi_kernel, dim3(1), dim3(1), 0, st, w0.S, inr->E, imu_buf, res0 + (three ? 5 : 12), 0);
+  BaWin* d_wins = c.d_wins;
+  const BaWin& w0 = c.hw[0];                                            // host copies of the device pointers of window 0
+  const bool fused_loop = c.fused && s.maxM > 0;                           // (iterations 1, 2, ...: the step kernel of the iteration before has built them)
+  if (!fused_loop || iter == 0) {
+    ProfScope ps(h, "ba_build_kernel");
+    if (s.maxM > 0) {
+      const dim3 g((s.pt_groups * s.ptl + 255) / 256, W);
+      if (s.ptl == 16) hipLaunchKernelGGL(ba_build_kernel<16>, g, dim3(256), 0, st, d_wins, c.bc, iter);
+      else hipLaunchKernelGGL(ba_build_kernel<32>, g, dim3(256), 0, st, d_wins, c.bc, iter);
     }
-  };
-  // Partitioned over ranks: every rank must issue the same sequence of collectives, whatever its own should_stop() or its
-  // own partition says — so the decisions travel with the collectives.  [total residual count | stop votes for
-  // iteration 0 | ranks with a bad observation index] first (host-read), then the votes for iteration i+1 ride on the second
-  // all-reduce of iteration i (res[8], read by ba_decide_kernel); a rank whose should_stop() fired keeps enqueueing.
-  double n_res = plan[0].n_res;
-  std::vector<double> votes((size_t)std::max(cfg->max_iterations, 0) + 2, 0.0);
-  bool my_stop = false;
-  // the observation CSR of every window (see ba_prep_count_kernel)
-  ORBX_HIP(h, hipMemsetAsync(dar + a_cnt, 0, ccnt.off, st));
-  if (maxN > 0) {
-    ProfScope ps(h, "ba_prep");
-    const dim3 go((maxN + BA_PREP_OPB - 1) / BA_PREP_OPB, W);
-    hipLaunchKernelGGL(ba_prep_count_kernel, go, dim3(256), 0, st, d_wins);
-    hipLaunchKernelGGL(ba_prep_scan_kernel, gW1, dim3(1024), 0, st, d_wins);
-    hipLaunchKernelGGL(ba_prep_place_kernel, go, dim3(256), 0, st, d_wins);
-    if (maxM > 0) hipLaunchKernelGGL(ba_prep_order_kernel, dim3((maxM * 16 + 255) / 256, W), dim3(256), 0, st, d_wins);
+    else hipLaunchKernelGGL(ba_iter_kernel, gW1, dim3(1), 0, st, d_wins, iter);
   }
-  if (dist) {
-    my_stop = should_stop && should_stop(user);
-    int bad0 = 0;                                                         // this rank's index check, from the device (the stream is drained here anyway)
-    ORBX_HIP(h, hipMemcpyAsync(&bad0, &w0.S->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    ORBX_HIP(h, hipStreamSynchronize(st));
-    const double head[3] = {n_res, my_stop ? 1.0 : 0.0, bad0 != 0 ? 1.0 : 0.0};
-    ORBX_HIP(h, hipMemcpyAsync(res0 + 8, head, 24, hipMemcpyHostToDevice, st));
-    ORBX_HIP(h, hipStreamSynchronize(st));
-    if (int rc = allreduce(res0 + 8, 3)) return rc;
-    double tot[3];
-    ORBX_HIP(h, hipMemcpyAsync(tot, res0 + 8, 24, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(h, hipStreamSynchronize(st));
-    if (tot[2] > 0.0) return orbx_fail(h, ORBX_ERR_INVALID, "an observation index is out of range on %d rank(s)%s", (int)tot[2], bad0 != 0 ? " (this one too)" : "");
-    n_res = tot[0];
-    if (n_res == 0.0) return orbx_fail(h, ORBX_ERR_EMPTY, "no residuals on any rank");
-    my_stop = tot[1] > 0.0;                                              // the collective decision for iteration 0
+  if (s.maxK > 0 && W == 1) {
+    ProfScope ps(h, "ba_kf_schur_kernel");
+    const dim3 g(s.maxK * BA_KFSPLIT + s.max_schur_blocks, 1);
+    if (s.all_diag) hipLaunchKernelGGL(ba_kf_schur_kernel<true>, g, dim3(SCHW_THREADS), SCHW_LDS_BYTES, st, d_wins, c.bc);
+    else hipLaunchKernelGGL(ba_kf_schur_kernel<false>, g, dim3(BA_KFS_GEN_THREADS), 0, st, d_wins, c.bc);
+  } else if (s.maxK > 0) {
+    {
+      ProfScope ps(h, "ba_kf_kernel");
+      hipLaunchKernelGGL(ba_kf_kernel, dim3(s.maxK * BA_KFSPLIT, W), dim3(BA_KF_THREADS), 0, st, d_wins, c.bc);
+    }
+    ProfScope ps(h, "ba_schur_kernel", true);
+    if (s.all_diag) hipLaunchKernelGGL(ba_schur_kernel<true>, dim3(s.schur_sums ? BA_GATHER_LANES : (s.max_schur_blocks + s.schur_spb - 1) / s.schur_spb, W), dim3(SCHW_THREADS), SCHW_LDS_BYTES, st, d_wins, c.bc, s.schur_spb);
+    else hipLaunchKernelGGL(ba_schur_kernel<false>, dim3(s.max_schur_blocks, W), dim3(256), 0, st, d_wins, c.bc, 1);
   }
-
-  if (maxM > 0 && maxK > 0) {
-    ProfScope ps(h, "ba_slots_kflist");
-    hipLaunchKernelGGL(ba_slots_kernel, dim3((maxM + BA_SLOT_PPB - 1) / BA_SLOT_PPB, W), dim3(256), 0, st, d_wins);
-    hipLaunchKernelGGL(ba_kflist_kernel, dim3(maxK, W), dim3(BA_KFL_THREADS), 0, st, d_wins);
+  {
+    ProfScope ps(h, "ba_gather_kernel");
+    // (with the shares already summed by the Schur launch a lane reads ONE pair per element: a block per 32 element pairs was 7 200 blocks of a
+    // few hundred cycles each for 32 windows; 4 elements per thread: 1 / 2 / 4 / 8 / 16 measured 14.7 / 13.4 / 12.8 / 15.1 / 18.5 us)
+    hipLaunchKernelGGL(ba_gather_kernel, dim3(s.schur_sums ? std::max(1, s.max_gather / 4) : s.max_gather, W), dim3(256), 0, st, d_wins, fused_loop && iter > 0 ? iter : -1);
   }
+  if (int rc = ba_allreduce(c, w0.rb, c.plan[0].rb_len)) return rc;
+  if (c.inertial) ba_enqueue_solve_inertial(c);
+  else ba_enqueue_solve_visual(c);
+  if (fused_loop) {
+    ProfScope ps(h, "ba_step_kernel");
+    if (s.ptl == 16) hipLaunchKernelGGL(ba_step_kernel<16>, dim3(s.max_back, W), dim3(256), 0, st, d_wins, c.bc);
+    else hipLaunchKernelGGL(ba_step_kernel<32>, dim3(s.max_back, W), dim3(256), 0, st, d_wins, c.bc);
+  } else {
+    ProfScope ps(h, "ba_backsub_kernel");
+    if (s.ptl == 16) hipLaunchKernelGGL(ba_backsub_kernel<16>, dim3(s.max_back, W), dim3(256), 0, st, d_wins, c.bc, (const double*)nullptr, c.dist ? 1 : 0);
+    else hipLaunchKernelGGL(ba_backsub_kernel<32>, dim3(s.max_back, W), dim3(256), 0, st, d_wins, c.bc, (const double*)nullptr, c.dist ? 1 : 0);
+  }
+  // trial residuals (:1047-1048): res[5] = chi2(trial), res[6] = |delta_l|^2, res[7] = |p_l|^2 from the per-point parts the
+  // back-substitution kernel left; then the accept / reject / stop decision (:1041-1055)
+  if (c.dist) {
+    {
+      ProfScope ps(h, "ba_chi2");
+      ba_enqueue_chi2_sum(c, 1, 1);
+    }
+    // this rank's vote on running iteration iter + 1 (polled here, once per iteration as :1013)
+    if (!c.stopped && iter + 1 < c.cfg->max_iterations && c.should_stop && c.should_stop(c.user)) c.stopped = true;
+    c.votes[(size_t)iter] = c.stopped ? 1.0 : 0.0;
+    ORBX_HIP(h, hipMemcpyAsync(w0.res + 8, &c.votes[(size_t)iter], 8, hipMemcpyHostToDevice, st));
+    if (int rc = ba_allreduce(c, w0.res + 5, 4)) return rc;
+    ProfScope ps(h, "ba_decide_kernel");
+    hipLaunchKernelGGL(ba_decide_kernel, gW1, dim3(BA_DECIDE_THREADS), 0, st, d_wins, 0, (const double*)nullptr, 0, (const volatile int*)nullptr, 1, 0);
+  } else {
+    ProfScope ps(h, "ba_decide_kernel");
+    const int E = c.inertial ? c.inr->E : 0;
+    if (E > 0) hipLaunchKernelGGL(ba_imu_kernel, dim3(E), dim3(64), 0, st, w0.S, w0.P0, w0.P1, 1, 0, c.ind, c.imu_buf);
+    hipLaunchKernelGGL(ba_decide_kernel, gW1, dim3(BA_DECIDE_THREADS), 0, st, d_wins, 1, (const double*)c.imu_buf, E, (const volatile int*)h->d_abort, 0, init_from_first ? 1 : 0);
+  }
+  return ORBX_OK;
+}
+// ---- the LM loop: it only polls should_stop (:1013) and enqueues; nothing here waits for the GPU
+int ba_enqueue_lm(BaCtx& c) {
   // initial error (:1000-1001) -> res[12].  The visual solve on one GPU takes it from its first iteration (the current error the gather
   // assembles from the build kernel's per-point sums, ba_decide_kernel) — a pass over every observation and a reduction less per call;
   // a call that enqueues no iteration, the partitioned solve (the sum is a collective) and the inertial one (IMU terms) compute it here.
-  const bool init_from_first = !dist && !inertial;
-  auto initial_error_pass = [&]() {
-    ProfScope ps(h, "ba_chi2");
-    if (maxM > 0) hipLaunchKernelGGL(ba_chi2_kernel, dim3((maxM * 32 + 255) / 256, W), dim3(256), 0, st, d_wins, bc, 0);
-    chi2_sum(0, 0);
-  };
+  const bool init_from_first = !c.dist && !c.inertial;
   if (!init_from_first) {
-    initial_error_pass();
-    if (int rc = allreduce(res0 + 12, 1)) return rc;
+    ba_enqueue_initial_error(c);
+    if (int rc = ba_allreduce(c, c.hw[0].res + 12, 1)) return rc;
   }
   bool any_iteration = false;
-
-  // The loop only polls should_stop (:1013) and enqueues; nothing below waits for the GPU.
-  bool stopped = my_stop;
-  for (int iter = 0; iter < cfg->max_iterations && !(dist && iter == 0 && my_stop); ++iter) {           // :1012
-    if (!dist && should_stop && should_stop(user)) { stopped = true; break; }                           // :1013
+  c.stopped = c.my_stop;
+  for (int iter = 0; iter < c.cfg->max_iterations && !(c.dist && iter == 0 && c.my_stop); ++iter) {     // :1012
+    if (!c.dist && c.should_stop && c.should_stop(c.user)) { c.stopped = true; break; }                 // :1013
     any_iteration = true;
-    const bool fused_loop = fused && maxM > 0;                               // (iterations 1, 2, ...: the step kernel of the iteration before has built them)
-    if (!fused_loop || iter == 0) {
-      ProfScope ps(h, "ba_build_kernel");
-      if (maxM > 0) {
-        const dim3 g((pt_groups * ptl + 255) / 256, W);
-        if (ptl == 16) hipLaunchKernelGGL(ba_build_kernel<16>, g, dim3(256), 0, st, d_wins, bc, iter);
-        else hipLaunchKernelGGL(ba_build_kernel<32>, g, dim3(256), 0, st, d_wins, bc, iter);
-      }
-      else hipLaunchKernelGGL(ba_iter_kernel, gW1, dim3(1), 0, st, d_wins, iter);
-    }
-    if (maxK > 0 && W == 1) {
-      ProfScope ps(h, "ba_kf_schur_kernel");
-      const dim3 g(maxK * BA_KFSPLIT + max_schur_blocks, 1);
-      if (all_diag) hipLaunchKernelGGL(ba_kf_schur_kernel<true>, g, dim3(SCHW_THREADS), SCHW_LDS_BYTES, st, d_wins, bc);
-      else hipLaunchKernelGGL(ba_kf_schur_kernel<false>, g, dim3(BA_KFS_GEN_THREADS), 0, st, d_wins, bc);
-    } else if (maxK > 0) {
-      {
-        ProfScope ps(h, "ba_kf_kernel");
-        hipLaunchKernelGGL(ba_kf_kernel, dim3(maxK * BA_KFSPLIT, W), dim3(BA_KF_THREADS), 0, st, d_wins, bc);
-      }
-      ProfScope ps(h, "ba_schur_kernel", true);
-      if (all_diag) hipLaunchKernelGGL(ba_schur_kernel<true>, dim3(schur_sums ? BA_GATHER_LANES : (max_schur_blocks + schur_spb - 1) / schur_spb, W), dim3(SCHW_THREADS), SCHW_LDS_BYTES, st, d_wins, bc, schur_spb);
-      else hipLaunchKernelGGL(ba_schur_kernel<false>, dim3(max_schur_blocks, W), dim3(256), 0, st, d_wins, bc, 1);
-    }
-    {
-      ProfScope ps(h, "ba_gather_kernel");
-      // (with the shares already summed by the Schur launch a lane reads ONE pair per element: a block per 32 element pairs was 7 200 blocks of a
-      // few hundred cycles each for 32 windows; 4 elements per thread: 1 / 2 / 4 / 8 / 16 measured 14.7 / 13.4 / 12.8 / 15.1 / 18.5 us)
-      hipLaunchKernelGGL(ba_gather_kernel, dim3(schur_sums ? std::max(1, max_gather / 4) : max_gather, W), dim3(256), 0, st, d_wins, fused_loop && iter > 0 ? iter : -1);
-    }
-    if (int rc = allreduce(w0.rb, plan[0].rb_len)) return rc;
-    if (inertial) {
-      ProfScope ps(h, "ba_inertial_solve");
-      const BaWin& b15 = *(const BaWin*)(hin + i_wins15);
-      if (inr->E > 0) hipLaunchKernelGGL(ba_imu_kernel, dim3(inr->E), dim3(64), 0, st, w0.S, w0.P0, w0.P1, 0, 1, ind, imu_buf);
-      if (n15 <= BA_TILED_MAX_N) hipLaunchKernelGGL(ba_solve_inertial_tiled_kernel, dim3(1, 1), dim3(BA_SOLVE_THREADS), tiled_lds_max, st, d_wins15, ind, (const double*)imu_buf);
-      else {
-        hipLaunchKernelGGL(ba_inertial_assemble_kernel, dim3(1), dim3(256), 0, st, w0.S, w0.P0, w0.P1, ind, w0.rb, imu_buf, b15.Sg, b15.bvec, gfull, res0);
-        if (n15 <= one_launch_max_n) hipLaunchKernelGGL(ba_big_factor_kernel, dim3(1, 1), dim3(BF_THREADS), BF_LDS_BYTES, st, d_wins15);
-        else for (int c0 = 0; c0 < n15; c0 += BB_NB) {
-          const int nt = (n15 - c0 + 15) / 16, units = c0 > 0 ? nt * (nt - 1) / 2 : 0;
-          hipLaunchKernelGGL(ba_big_step_kernel, dim3(1 + (units + BB_STEP_WAVES - 1) / BB_STEP_WAVES, 1), dim3(BB_STEP_THREADS), 0, st, d_wins15, c0, one_launch_max_n);
-        }
-        if (n15 > one_launch_max_n) hipLaunchKernelGGL(ba_big_back_kernel, dim3(1, 1), dim3(256), 0, st, d_wins15, one_launch_max_n);
-      }
-      hipLaunchKernelGGL(ba_inertial_scatter_kernel, dim3(1), dim3(256), 0, st, w0.S, w0.P0, w0.P1, K0, M0, dp15, w0.dp);
-    } else {
-      ProfScope ps(h, "ba_solve_kernel");
-      if (any_lds) hipLaunchKernelGGL(ba_solve_lds_kernel, gW1, dim3(BA_SOLVE_THREADS), lds_max, st, d_wins);
-      if (any_big || any_tiled) hipLaunchKernelGGL(ba_big_assemble_kernel, dim3(max_asm, W), dim3(256), 0, st, d_wins);
-      if (any_tiled) hipLaunchKernelGGL(ba_solve_tiled_kernel, gW1, dim3(BA_SOLVE_THREADS), tiled_lds_max, st, d_wins);
-      if (any_big) {
-        if (any_one) hipLaunchKernelGGL(ba_big_factor_kernel, gW1, dim3(BF_THREADS), BF_LDS_BYTES, st, d_wins);
-        for (int c0 = 0; c0 < n_big_max; c0 += BB_NB) {
-          const int nt = (n_big_max - c0 + 15) / 16, units = c0 > 0 ? nt * (nt - 1) / 2 : 0;
-          hipLaunchKernelGGL(ba_big_step_kernel, dim3(1 + (units + BB_STEP_WAVES - 1) / BB_STEP_WAVES, W), dim3(BB_STEP_THREADS), 0, st, d_wins, c0, one_launch_max_n);
-        }
-        if (n_big_max > 0) hipLaunchKernelGGL(ba_big_back_kernel, gW1, dim3(256), 0, st, d_wins, one_launch_max_n);
-      }
-    }
-    if (fused_loop) {
-      ProfScope ps(h, "ba_step_kernel");
-      if (ptl == 16) hipLaunchKernelGGL(ba_step_kernel<16>, dim3(max_back, W), dim3(256), 0, st, d_wins, bc);
-      else hipLaunchKernelGGL(ba_step_kernel<32>, dim3(max_back, W), dim3(256), 0, st, d_wins, bc);
-    } else {
-      ProfScope ps(h, "ba_backsub_kernel");
-      if (ptl == 16) hipLaunchKernelGGL(ba_backsub_kernel<16>, dim3(max_back, W), dim3(256), 0, st, d_wins, bc, (const double*)nullptr, dist ? 1 : 0);
-      else hipLaunchKernelGGL(ba_backsub_kernel<32>, dim3(max_back, W), dim3(256), 0, st, d_wins, bc, (const double*)nullptr, dist ? 1 : 0);
-    }
-    // trial residuals (:1047-1048): res[5] = chi2(trial), res[6] = |delta_l|^2, res[7] = |p_l|^2 from the per-point parts the
-    // back-substitution kernel left; then the accept / reject / stop decision (:1041-1055)
-    if (dist) {
-      {
-        ProfScope ps(h, "ba_chi2");
-        chi2_sum(1, 1);
-      }
-      // this rank's vote on running iteration iter + 1 (polled here, once per iteration as :1013)
-      if (!stopped && iter + 1 < cfg->max_iterations && should_stop && should_stop(user)) stopped = true;
-      votes[(size_t)iter] = stopped ? 1.0 : 0.0;
-      ORBX_HIP(h, hipMemcpyAsync(res0 + 8, &votes[(size_t)iter], 8, hipMemcpyHostToDevice, st));
-      if (int rc = allreduce(res0 + 5, 4)) return rc;
-      ProfScope ps(h, "ba_decide_kernel");
-      hipLaunchKernelGGL(ba_decide_kernel, gW1, dim3(BA_DECIDE_THREADS), 0, st, d_wins, 0, (const double*)nullptr, 0, (const volatile int*)nullptr, 1, 0);
-    } else {
-      ProfScope ps(h, "ba_decide_kernel");
-      const int E = inertial ? inr->E : 0;
-      if (E > 0) hipLaunchKernelGGL(ba_imu_kernel, dim3(E), dim3(64), 0, st, w0.S, w0.P0, w0.P1, 1, 0, ind, imu_buf);
-      hipLaunchKernelGGL(ba_decide_kernel, gW1, dim3(BA_DECIDE_THREADS), 0, st, d_wins, 1, (const double*)imu_buf, E, (const volatile int*)h->d_abort, 0, init_from_first ? 1 : 0);
-    }
+    if (int rc = ba_enqueue_iteration(c, iter, init_from_first)) return rc;
   }
-  if (init_from_first && !any_iteration) initial_error_pass();
-  {
-    size_t np_max = 1;
-    for (int w = 0; w < W; ++w) np_max = std::max(np_max, plan[w].np);
-    hipLaunchKernelGGL(ba_finish_kernel, dim3((unsigned)std::min<size_t>(64, (np_max + 255) / 256), W), dim3(256), 0, st, d_wins, dout,
-                       (const size_t*)(din + i_outoff), inertial ? 9 : 0);
+  if (init_from_first && !any_iteration) ba_enqueue_initial_error(c);
+  return ORBX_OK;
+}
+// ---- finish: the results of every window into the output blob, ONE download
+int ba_enqueue_finish(BaCtx& c) {
+  size_t np_max = 1;
+  for (int w = 0; w < c.W; ++w) np_max = std::max(np_max, c.plan[(size_t)w].np);
+  hipLaunchKernelGGL(ba_finish_kernel, dim3((unsigned)std::min<size_t>(64, (np_max + 255) / 256), c.W), dim3(256), 0, c.st, c.d_wins, c.dout,
+                     (const size_t*)(c.din + c.i_outoff), c.inertial ? 9 : 0);
+  ORBX_HIP(c.h, hipMemcpyAsync(c.hout, c.dout, c.out_bytes, hipMemcpyDeviceToHost, c.st));
+  return ORBX_OK;
+}
+// ---- drain.  While the enqueued iterations drain, keep asking should_stop: a stop requested now (the local mapper's "new keyframe
+// arrived") ends the solve at the next iteration boundary, as in the reference, instead of being seen only by the polls
+// at enqueue time, which are all over within the first few hundred microseconds.
+int ba_drain(BaCtx& c) {
+  orbx_handle* h = c.h;
+  if (c.should_stop && !c.dist && !c.stopped) {
+    while (hipStreamQuery(c.st) == hipErrorNotReady)
+      if (c.should_stop(c.user)) { *(volatile int*)h->h_abort = 1; break; }
   }
-  double* hout = (double*)h->h_ba_out;
-  ORBX_HIP(h, hipMemcpyAsync(hout, dout, cout.off, hipMemcpyDeviceToHost, st));   // ONE download
-  mark(4);
-  // While the enqueued iterations drain, keep asking should_stop: a stop requested now (the local mapper's "new keyframe
-  // arrived") ends the solve at the next iteration boundary, as in the reference, instead of being seen only by the polls
-  // at enqueue time, which are all over within the first few hundred microseconds.
-  if (should_stop && !dist && !stopped) {
-    while (hipStreamQuery(st) == hipErrorNotReady)
-      if (should_stop(user)) { *(volatile int*)h->h_abort = 1; break; }
-  }
-  ORBX_HIP(h, hipStreamSynchronize(st));
-  drained = true;
+  ORBX_HIP(h, hipStreamSynchronize(c.st));
+  c.drained = true;
   ORBX_HIP(h, hipGetLastError());
-  mark(5);
-
-  for (int w = 0; w < W; ++w) {                                          // an observation index out of range (found by ba_prep_count_kernel): the call fails, nothing is written
-    if (plan[w].skip) continue;
-    const int code = (int)hout[plan[w].o_out / 8 + 5];
+  return ORBX_OK;
+}
+// ---- unpack: an observation index out of range (found by ba_prep_count_kernel): the call fails, nothing is written
+int ba_report_bad_index(BaCtx& c) {
+  for (int w = 0; w < c.W; ++w) {
+    if (c.plan[(size_t)w].skip) continue;
+    const int code = (int)c.hout[c.plan[(size_t)w].o_out / 8 + 5];
     if (code == 0) continue;
+    const BaWinHost& ww = c.win[w];
     const int i = 0x7fffffff - code;
     int kf, fx, mp;
-    if (win[w].obs32) { const orbx_ba_obs32& o = win[w].obs32[i]; kf = o.kf_idx >= 0 ? o.kf_idx : -1; fx = o.kf_idx >= 0 ? -1 : -1 - o.kf_idx; mp = o.mp_idx; }
-    else { const orbx_ba_obs& o = win[w].obs[i]; kf = o.kf_idx; fx = o.fixed_idx; mp = o.mp_idx; }
-    return orbx_fail(h, ORBX_ERR_INVALID, "window %d observation %d: index out of range (kf %d/%d, fixed %d/%d, mp %d/%d)", w, i, kf,
-                     win[w].K, fx, win[w].F, mp, win[w].M);
+    if (ww.obs32) { const orbx_ba_obs32& o = ww.obs32[i]; kf = o.kf_idx >= 0 ? o.kf_idx : -1; fx = o.kf_idx >= 0 ? -1 : -1 - o.kf_idx; mp = o.mp_idx; }
+    else { const orbx_ba_obs& o = ww.obs[i]; kf = o.kf_idx; fx = o.fixed_idx; mp = o.mp_idx; }
+    return orbx_fail(c.h, ORBX_ERR_INVALID, "window %d observation %d: index out of range (kf %d/%d, fixed %d/%d, mp %d/%d)", w, i, kf,
+                     ww.K, fx, ww.F, mp, ww.M);
   }
-  for (int w = 0; w < W; ++w) {
-    if (plan[w].skip) continue;
-    const WinPlan& pl = plan[w];
-    const BaWinHost& ww = win[w];
-    const int K = ww.K, M = ww.M;
-    const double* o = hout + pl.o_out / 8;
-    const int iters = (int)o[0];
-    *ww.iterations = iters;
-    const double init_sq = o[2], final_sq = iters > 0 ? o[1] : o[2];
-    if (inertial) {                                                      // |r|, not RMS (local_inertial_ba.rs:1191, :1244)
-      *ww.initial_error = std::sqrt(init_sq);
-      *ww.final_error = std::sqrt(final_sq);
-    } else {
-      const double nr = dist ? n_res : pl.n_res;
-      *ww.initial_error = std::sqrt(init_sq) / std::sqrt(nr);
-      *ww.final_error = std::sqrt(final_sq) / std::sqrt(nr);           // :1059-1060
-    }
-    std::vector<double> merged;
-    const double* params = o + 8;
-    if (dist && M > 0) {
-      // every point moved only on the rank that owns it: sum the per-rank updates
-      const double* init_pts = (const double*)(hin + pl.i_params) + 6 * (size_t)K;   // the blob still holds the initial parameters
-      double* cur = o[3] != 0.0 ? w0.P1 : w0.P0;
-      double* other = o[3] != 0.0 ? w0.P0 : w0.P1;
-      ORBX_HIP(h, hipMemcpyAsync(other, init_pts, 8 * 3 * (size_t)M, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(ba_diff_kernel, dim3(64), dim3(256), 0, st, 3 * (size_t)M, cur + 6 * (size_t)K, other, other + 3 * (size_t)M);
-      if (int rc = allreduce(other + 3 * (size_t)M, 3 * (size_t)M)) return rc;
-      std::vector<double> upd(3 * (size_t)M);
-      ORBX_HIP(h, hipMemcpyAsync(upd.data(), other + 3 * (size_t)M, 8 * 3 * (size_t)M, hipMemcpyDeviceToHost, st));
-      ORBX_HIP(h, hipStreamSynchronize(st));
-      merged.assign(params, params + pl.np);
-      for (size_t j = 0; j < 3 * (size_t)M; ++j) merged[6 * (size_t)K + j] = init_pts[j] + upd[j];
-      params = merged.data();
-    }
-    if (inertial) {                                                      // extract_pose / velocity / bias (:584-608, :1250-1254)
-      for (int k = 0; k < K; ++k) {
-        const double* p6 = &params[6 * (size_t)k];
-        double* q = ww.poses_wc_out + 7 * (size_t)k;
-        const double v[3] = {p6[0] / 2.0, p6[1] / 2.0, p6[2] / 2.0};
-        const double nn = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], eps = 2.220446049250313e-16;
-        if (nn <= eps * eps) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
-        else { const double nv = std::sqrt(nn), sn = 1.0 * std::sin(nv) / nv; q[0] = 1.0 * std::cos(nv); q[1] = v[0] * sn; q[2] = v[1] * sn; q[3] = v[2] * sn; }
-        q[4] = p6[3]; q[5] = p6[4]; q[6] = p6[5];
-        const double* ex = &params[6 * (size_t)K + 3 * (size_t)M + 9 * (size_t)k];
-        for (int i = 0; i < 3; ++i) inr->vel_out[3 * (size_t)k + i] = ex[i];
-        for (int i = 0; i < 6; ++i) inr->bias_out[6 * (size_t)k + i] = ex[3 + i];
-      }
-    } else {
-      for (int k = 0; k < K; ++k) host_params_to_pose_wc(&params[6 * (size_t)k], ww.poses_wc_out + 7 * (size_t)k);
-    }
-    for (int j = 0; j < 3 * M; ++j) ww.points[j] = params[6 * (size_t)K + j];
+  return ORBX_OK;
+}
+// the partition merge: every point moved only on the rank that owns it: sum the per-rank updates.  `merged`: the window's parameters
+// with the summed points
+int ba_merge_partition(BaCtx& c, const WinPlan& pl, const double* o, std::vector<double>& merged) {
+  orbx_handle* h = c.h;
+  const BaWin& w0 = c.hw[0];
+  const size_t K = (size_t)pl.d.K, M = (size_t)pl.d.M;
+  const double* init_pts = (const double*)(c.hin + pl.i_params) + 6 * K;     // the blob still holds the initial parameters
+  double* cur = o[3] != 0.0 ? w0.P1 : w0.P0;
+  double* other = o[3] != 0.0 ? w0.P0 : w0.P1;
+  ORBX_HIP(h, hipMemcpyAsync(other, init_pts, 8 * 3 * M, hipMemcpyHostToDevice, c.st));
+  hipLaunchKernelGGL(ba_diff_kernel, dim3(64), dim3(256), 0, c.st, 3 * M, cur + 6 * K, other, other + 3 * M);
+  if (int rc = ba_allreduce(c, other + 3 * M, 3 * M)) return rc;
+  std::vector<double> upd(3 * M);
+  ORBX_HIP(h, hipMemcpyAsync(upd.data(), other + 3 * M, 8 * 3 * M, hipMemcpyDeviceToHost, c.st));
+  ORBX_HIP(h, hipStreamSynchronize(c.st));
+  merged.assign(o + 8, o + 8 + pl.np);
+  for (size_t j = 0; j < 3 * M; ++j) merged[6 * K + j] = init_pts[j] + upd[j];
+  return ORBX_OK;
+}
+// ---- unpack: iterations, errors, poses and points of one window
+int ba_unpack_window(BaCtx& c, int w) {
+  const WinPlan& pl = c.plan[(size_t)w];
+  const BaWinHost& ww = c.win[w];
+  const int K = ww.K, M = ww.M;
+  const double* o = c.hout + pl.o_out / 8;
+  const int iters = (int)o[0];
+  *ww.iterations = iters;
+  const double init_sq = o[2], final_sq = iters > 0 ? o[1] : o[2];
+  if (c.inertial) {                                                      // |r|, not RMS (local_inertial_ba.rs:1191, :1244)
+    *ww.initial_error = std::sqrt(init_sq);
+    *ww.final_error = std::sqrt(final_sq);
+  } else {
+    const double nr = c.dist ? c.n_res : pl.n_res;
+    *ww.initial_error = std::sqrt(init_sq) / std::sqrt(nr);
+    *ww.final_error = std::sqrt(final_sq) / std::sqrt(nr);             // :1059-1060
   }
+  std::vector<double> merged;
+  const double* params = o + 8;
+  if (c.dist && M > 0) {
+    if (int rc = ba_merge_partition(c, pl, o, merged)) return rc;
+    params = merged.data();
+  }
+  if (c.inertial) {                                                      // extract_pose / velocity / bias (:584-608, :1250-1254)
+    for (int k = 0; k < K; ++k) {
+      host_params_to_pose_inertial(&params[6 * (size_t)k], ww.poses_wc_out + 7 * (size_t)k);
+      const double* ex = &params[6 * (size_t)K + 3 * (size_t)M + 9 * (size_t)k];
+      for (int i = 0; i < 3; ++i) c.inr->vel_out[3 * (size_t)k + i] = ex[i];
+      for (int i = 0; i < 6; ++i) c.inr->bias_out[6 * (size_t)k + i] = ex[3 + i];
+    }
+  } else {
+    for (int k = 0; k < K; ++k) host_params_to_pose_wc(&params[6 * (size_t)k], ww.poses_wc_out + 7 * (size_t)k);
+  }
+  for (int j = 0; j < 3 * M; ++j) ww.points[j] = params[6 * (size_t)K + j];
+  return ORBX_OK;
+}
+}  // namespace
+
+// W windows at once (W = 1: orbx_ba_solve_visual / global / inertial).  The all-reduce hook and the inertial mode apply to a
+// single window only.
+int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int W, BaWinHost* win,
+                   orbx_should_stop_fn should_stop, void* user, bool global_mode, const BaInertialHost* inr, bool single_call,
+                   const BaCallOpts& opts) {
+  // single_call: the one-window entry points (orbx_ba_solve_visual / global / inertial) answer ORBX_ERR_EMPTY as their return
+  // value where the reference returns None; the batch entry point reports it in the window's status and returns ORBX_OK,
+  // also for a batch of one (orbx.h; ADVICE r2)
+  // inr != nullptr: solve_inertial_ba (local_inertial_ba.rs:1074-1275).  `poses_cw` then holds the T_wc poses of the window
+  // and cfg carries max_iterations only; the point elimination, the per-keyframe 6x6 blocks and the Schur product are the
+  // visual solver's kernels, the 15-d keyframe states are assembled and solved on top of them.
+  // Whatever happens below — the early returns taken before any GPU work included — the first half of a split batch opens the gate for
+  // the second when it leaves.
+  struct GateOpen { std::atomic<int>* g; ~GateOpen() { if (g) g->store(1, std::memory_order_release); } } gate_open{opts.gate_signal};
+  const bool inertial = inr != nullptr;
+  const bool have_coll = h->allreduce != nullptr || h->rccl_comm != nullptr;
+  const bool dist = have_coll && !inertial && W == 1;
+  if (W <= 0) return ORBX_OK;
+  if ((inertial || have_coll) && W != 1)
+    return orbx_fail(h, ORBX_ERR_INVALID, "the inertial mode and the all-reduce hook take one window per call");
+  for (int w = 0; w < W; ++w) { *win[w].iterations = 0; *win[w].initial_error = 0.0; *win[w].final_error = 0.0; win[w].status = ORBX_OK; }
+  // ORBX_BA_TIMING=1: host-side phase times of this call on stderr (plan, preprocessing, descriptors + upload enqueue, launch
+  // enqueue, drain, unpack)
+  static const bool timing = getenv("ORBX_BA_TIMING") != nullptr;
+  double t_mark[8] = {0};
+  auto mark = [&](int i) { if (timing) t_mark[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  mark(0);
+
+  BaCtx c{h, h->stream, cam, cfg, W, win, should_stop, user, inr, &opts, global_mode, single_call, inertial, dist, ba_use_fused(dist, W)};
+  if (int rc = ba_check_sizes(c)) return rc;
+  ba_plan(c);
+  if (c.live == 0) {
+    if (single_call) return orbx_fail(h, ORBX_ERR_EMPTY, "no parameters or no residuals");
+    return ORBX_OK;                                                      // every window reports ORBX_ERR_EMPTY in its status
+  }
+  ba_plan_uploads(c);
+  if (int rc = ba_check_inertial(c)) return rc;
+  if (int rc = ba_reserve(c)) return rc;
+  // Once the copy engine has been pointed at the caller's page-locked observations, no return path may leave them in flight: an error
+  // return below (a HIP failure, the pool, the attribute check, the collective) first drains the stream, so the caller may reuse or free
+  // its buffer the moment the call is back, whatever it answered (ADVICE r4).
+  struct DrainOnLeave { const BaCtx* c; ~DrainOnLeave() { if (c->direct_sent && !c->drained) (void)hipStreamSynchronize(c->st); } } drain_on_leave{&c};
+  mark(1);
+  if (!opts.gate_wait) { if (int rc = ba_send_direct(c)) return rc; }     // the copy engine starts at once; the host's O(K + M) part runs under it
+  if (int rc = ba_host_prep(c)) return rc;
+  mark(2);
+  if (int rc = ba_send_staged(c)) return rc;
+  ba_launch_shape(c);
+  ba_bind(c);
+  if (int rc = ba_bind_inertial(c)) return rc;
+  if (int rc = ba_send_small(c)) return rc;
+  mark(3);
+  if (int rc = ba_set_func_attributes(h)) return rc;
+  if (int rc = ba_enqueue_csr(c)) return rc;
+  if (int rc = ba_partition_head(c)) return rc;
+  ba_enqueue_slots(c);
+  if (int rc = ba_enqueue_lm(c)) return rc;
+  if (int rc = ba_enqueue_finish(c)) return rc;
+  mark(4);
+  if (int rc = ba_drain(c)) return rc;
+  mark(5);
+  if (int rc = ba_report_bad_index(c)) return rc;
+  for (int w = 0; w < W; ++w)
+    if (!c.plan[(size_t)w].skip) { if (int rc = ba_unpack_window(c, w)) return rc; }
   if (timing) {
     mark(6);
     fprintf(stderr, "[orbx ba] W=%d in=%.1f MB: plan %.3f | prep %.3f | descriptors+upload enqueue %.3f | iteration enqueue %.3f | drain %.3f | unpack %.3f ms\n",
-            W, cin.off / 1e6, t_mark[1] - t_mark[0], t_mark[2] - t_mark[1], t_mark[3] - t_mark[2], t_mark[4] - t_mark[3], t_mark[5] - t_mark[4], t_mark[6] - t_mark[5]);
+            W, c.small_bytes / 1e6, t_mark[1] - t_mark[0], t_mark[2] - t_mark[1], t_mark[3] - t_mark[2], t_mark[4] - t_mark[3], t_mark[5] - t_mark[4], t_mark[6] - t_mark[5]);
   }
   return ORBX_OK;
 }
@@ -4070,8 +4258,8 @@ int ba_debug_imu_residual(orbx_handle* h, int K, const double* poses_wc, const d
   }
   Carve c;
   const size_t o_s = c.take(8 * st.size()), o_e = c.take(8 * (size_t)E), o_p = c.take(88 * (size_t)E), o_o = c.take(72 * (size_t)E);
-  if (int rc = orbx_reserve(h, h->ws_ba[6], c.off)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_ba[6].p;
+  if (int rc = orbx_reserve(h, h->ws_ba_debug, c.off)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_ba_debug.p;
   hipStream_t s = h->stream;
   ORBX_HIP(h, hipMemcpyAsync(d + o_s, st.data(), 8 * st.size(), hipMemcpyHostToDevice, s));
   ORBX_HIP(h, hipMemcpyAsync(d + o_e, edge_kf, 8 * (size_t)E, hipMemcpyHostToDevice, s));
@@ -4098,12 +4286,7 @@ int ba_debug_blocks(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config
   std::vector<int> okf(N), ofix(N), omp(N);
   for (int k = 0; k < K; ++k) host_se3_to_params(poses_cw + 7 * (size_t)k, &params[6 * (size_t)k]);
   for (int j = 0; j < 3 * M; ++j) params[6 * (size_t)K + j] = points[j];
-  for (int f = 0; f <= F; ++f) {
-    const double ident[7] = {1, 0, 0, 0, 0, 0, 0};
-    const double* p = f < F ? fixed_poses_cw + 7 * (size_t)f : ident;
-    host_quat_to_R(p, &Rt_fix[12 * (size_t)f]);
-    Rt_fix[12 * (size_t)f + 9] = p[4]; Rt_fix[12 * (size_t)f + 10] = p[5]; Rt_fix[12 * (size_t)f + 11] = p[6];
-  }
+  host_fixed_to_Rt(fixed_poses_cw, F, Rt_fix.data());
   for (int i = 0; i < N; ++i) {
     okf[i] = obs[i].kf_idx >= 0 ? obs[i].kf_idx : -1;
     ofix[i] = obs[i].kf_idx >= 0 ? 0 : (obs[i].fixed_idx >= 0 ? obs[i].fixed_idx : F);
@@ -4112,8 +4295,8 @@ int ba_debug_blocks(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config
   Carve c;
   const size_t o_p = c.take(8 * params.size()), o_r = c.take(8 * Rt_fix.size()), o_k = c.take(4 * (size_t)N), o_f = c.take(4 * (size_t)N),
                o_m = c.take(4 * (size_t)N), o_u = c.take(16 * (size_t)N), o_o = c.take(160 * (size_t)N);
-  if (int rc = orbx_reserve(h, h->ws_ba[6], c.off)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_ba[6].p;
+  if (int rc = orbx_reserve(h, h->ws_ba_debug, c.off)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_ba_debug.p;
   hipStream_t st = h->stream;
   ORBX_HIP(h, hipMemcpyAsync(d + o_p, params.data(), 8 * params.size(), hipMemcpyHostToDevice, st));
   ORBX_HIP(h, hipMemcpyAsync(d + o_r, Rt_fix.data(), 8 * Rt_fix.size(), hipMemcpyHostToDevice, st));

@@ -156,10 +156,10 @@ void orbx_destroy(orbx_handle* h) {
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
   DevBuf* bufs[] = {&h->resize_tab, &h->ws_pyr, &h->ws_blur, &h->ws_cand, &h->ws_counters,
-                    &h->ws_sel, &h->ws_sel2, &h->ws_match, &h->ws_dtile};
+                    &h->ws_sel, &h->ws_sel2, &h->ws_match, &h->ws_dtile,
+                    &h->ws_ba_in, &h->ws_ba_arena, &h->ws_ba_out, &h->ws_ba_imu, &h->ws_ba_s15, &h->ws_ba_debug};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (DevBuf& b : h->ws_io) if (b.p) hipFree(b.p);
-  for (DevBuf& b : h->ws_ba) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_pnp) if (b.p) hipFree(b.p);
   if (h->ws_pi.p) hipFree(h->ws_pi.p);
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
@@ -1054,29 +1054,24 @@ int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orb
       // half's kernels run under the second half's preprocessing, was built: 16 threads sort a half in 0.33 ms where 8 take 0.41, so the
       // second half was ready at 0.7 ms instead of 0.45 — no gain)
       const int half_cores = std::max(1, (int)std::thread::hardware_concurrency() / 2);
-      h->ba_pool_cap = half_cores; h->ba_aux->ba_pool_cap = half_cores;
-      h->ba_peer_windows = n_windows - n0; h->ba_aux->ba_peer_windows = n0;
-      // one PCIe link: the second half's uploads go behind the first half's (orbx_internal.hpp: ba_gate_*)
+      // one PCIe link: the second half's uploads go behind the first half's (orbx_internal.hpp: BaCallOpts)
       std::atomic<int> gate{0};
       if (!h->ba_up_event && hipEventCreateWithFlags(&h->ba_up_event, hipEventDisableTiming) != hipSuccess) h->ba_up_event = nullptr;
-      h->ba_gate_signal = &gate; h->ba_aux->ba_gate_wait = &gate; h->ba_aux->ba_gate_event = h->ba_up_event;
-      struct Uncap { orbx_handle* h; ~Uncap() { h->ba_pool_cap = 0; h->ba_aux->ba_pool_cap = 0; h->ba_peer_windows = 0; h->ba_aux->ba_peer_windows = 0;
-                                                h->ba_gate_signal = nullptr; h->ba_aux->ba_gate_wait = nullptr; h->ba_aux->ba_gate_event = nullptr; } } uncap{h};
+      const BaCallOpts first{half_cores, n_windows - n0, &gate, nullptr, nullptr}, second{half_cores, n0, nullptr, &gate, h->ba_up_event};
       if (!h->ba_helper) {
         try { h->ba_helper = new OrbxHelperThread(); } catch (...) { h->ba_helper = nullptr; }
       }
       if (h->ba_helper) {
         h->ba_helper->start([&] {
           hipSetDevice(h->device);
-          try { rc1 = ba_solve_batch(h->ba_aux, cam, cfg, n_windows - n0, w.data() + n0, nullptr, nullptr); }
+          try { rc1 = ba_solve_batch(h->ba_aux, cam, cfg, n_windows - n0, w.data() + n0, nullptr, nullptr, false, nullptr, false, second); }
           catch (...) { rc1 = ORBX_ERR_HIP; }
         });
-        try { rc = ba_solve_batch(h, cam, cfg, n0, w.data(), nullptr, nullptr); }
+        try { rc = ba_solve_batch(h, cam, cfg, n0, w.data(), nullptr, nullptr, false, nullptr, false, first); }
         catch (...) { rc = orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_batch: out of host memory"); }
         gate.store(1, std::memory_order_release);                              // (however the first half ended, the second must not wait for it)
         h->ba_helper->wait();
       } else {                                                              // no thread: the whole batch here, on one stream
-        h->ba_gate_signal = nullptr; h->ba_peer_windows = 0; h->ba_pool_cap = 0;
         rc = ba_solve_batch(h, cam, cfg, n_windows, w.data(), nullptr, nullptr);
       }
       if (rc == ORBX_OK && rc1 != ORBX_OK) rc = orbx_fail(h, rc1, "(windows %d..%d, numbered from %d) %s", n0, n_windows - 1, n0, orbx_last_error(h->ba_aux));

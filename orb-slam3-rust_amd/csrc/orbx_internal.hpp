@@ -200,7 +200,9 @@ struct orbx_handle {
   // grow-only workspaces
   DevBuf ws_pyr, ws_blur, ws_cand, ws_counters, ws_sel, ws_sel2, ws_match, ws_io[12];
   DevBuf ws_dtile;                       // [image][describe tile] (begin, end) inside the level's spatially ordered keypoint list (rank_select_kernel)
-  DevBuf ws_ba[28];
+  DevBuf ws_ba_in, ws_ba_arena, ws_ba_out;   // ba_solve_batch: input blob (descriptors, states, parameters | observations), scratch arena, output blob
+  DevBuf ws_ba_imu, ws_ba_s15;             // ... inertial: IMU edges, preintegrations and records; the 15-d reduced system
+  DevBuf ws_ba_debug;                      // ba_debug_blocks / ba_debug_imu_residual
   DevBuf ws_pnp[2];                      // PnP-RANSAC: [0] hypotheses + counts (pnp_kernels.hip), [1] the host forms' input / output blobs
   void* h_pnp = nullptr; size_t h_pnp_bytes = 0;   // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
   DevBuf ws_pi;                          // pose-inertial optimization: the host forms' input / output blob (pose_inertial_kernels.hip)
@@ -220,15 +222,7 @@ struct orbx_handle {
   int* h_abort = nullptr;    int* d_abort = nullptr;       // pinned, device-visible: should_stop() seen while the iterations drain
   OrbxWorkPool* ba_pool = nullptr;                         // host workers of the batch preprocessing (created by the first large batch)
   OrbxHelperThread* ba_helper = nullptr;                   // drives the second half of a large batch (orbx_ba_solve_visual_batch)
-  int ba_pool_cap = 0;                                     // > 0: at most this many threads for the next preprocessing (two halves share the cores)
-  int ba_peer_windows = 0;                                 // windows of the other half of a batch, solved at the same time on the peer handle's stream (launch-shape heuristics count them)
-  // the two halves of a batch share one PCIe link: the second half's uploads are ordered behind the first half's (its kernels then start
-  // as early as they can, and the second half's bytes travel under them).  The first half records ba_up_event on its stream once its
-  // uploads are enqueued and sets *ba_gate_signal; the second half waits for *ba_gate_wait, then makes its stream wait for ba_gate_event.
-  hipEvent_t ba_up_event = nullptr;
-  std::atomic<int>* ba_gate_signal = nullptr;
-  std::atomic<int>* ba_gate_wait = nullptr;
-  hipEvent_t ba_gate_event = nullptr;
+  hipEvent_t ba_up_event = nullptr;                        // recorded by the first half of a batch once its uploads are enqueued (BaCallOpts)
   // profiling
   bool profiling = false;
   std::string prof_only;   // non-empty: only this kernel's launches are bracketed (orbx_set_profiling_only)
@@ -301,9 +295,20 @@ struct BaWinHost {
   int status;
   const orbx_ba_obs32* obs32 = nullptr;       // the 16-byte form of the observations (orbx.h): used instead of obs when given
 };
+// What one ba_solve_batch call is told about the batch it is a half of (orbx_ba_solve_visual_batch builds one per half; default: none).
+// The two halves of a batch share one PCIe link: the second half's uploads are ordered behind the first half's (its kernels then start
+// as early as they can, and the second half's bytes travel under them).  The first half records its handle's ba_up_event on its stream
+// once its uploads are enqueued and sets *gate_signal; the second half waits for *gate_wait, then makes its stream wait for gate_event.
+struct BaCallOpts {
+  int pool_cap = 0;                          // > 0: at most this many threads for the preprocessing (two halves share the cores)
+  int peer_windows = 0;                      // windows of the other half, solved at the same time on the peer handle's stream (launch-shape heuristics count them)
+  std::atomic<int>* gate_signal = nullptr;
+  std::atomic<int>* gate_wait = nullptr;
+  hipEvent_t gate_event = nullptr;
+};
 int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int W, BaWinHost* win,
                    orbx_should_stop_fn should_stop, void* user, bool global_mode = false, const struct BaInertialHost* inr = nullptr,
-                   bool single_call = false);
+                   bool single_call = false, const BaCallOpts& opts = BaCallOpts());
 // in-place sum of `n` doubles over the ranks of the handle's communicator, ordered on `st` (ncclAllReduce, orbx_api.hip)
 int orbx_rccl_allreduce_sum(orbx_handle* h, double* d_buf, size_t n, hipStream_t st);
 // destroys the handle's communicator if the library owns it, and clears it

@@ -393,6 +393,26 @@ def test_ba_batch_two_streams_path(gpu_handle, pkg):
     assert np.array_equal(again[17]["poses_wc"], batch[17]["poses_wc"])
 
 
+def test_ba_batch_half_refused_while_planning_leaves_nothing_behind(gpu_handle, pkg):
+    """16 tiny windows run as two halves.  Window 2, in the first half, hands in 129 optimised keyframes: that half is refused by the size
+    check, before any GPU work and before the point at which it would open the upload gate for the second half — the call must come back
+    (the second half never waits for a gate nobody opens) with ORBX_ERR_INVALID and the library's text.  What a half is told about the
+    batch (thread cap, peer windows, gate) is an argument of that one call: the same batch without the oversized window then solves on the
+    same handle, and its window 15 equals its own single-window solve bit for bit."""
+    cam = pkg.CameraModel(**pkg.synth.EUROC_CAMERA); cfg = pkg.LocalBAConfigLM()
+    wins = [pkg.synth.ba_window(3100 + i, 3, 40, pkg.BA_OBS) for i in range(16)]
+    bad = list(wins)
+    bad[2] = dict(wins[2], poses_cw=np.repeat(wins[2]["poses_cw"][:1], 129, axis=0))
+    with pytest.raises(pkg.OrbxError) as e:
+        gpu_handle.ba_solve_visual_batch(cam, cfg, bad)
+    assert e.value.code == -1 and "window 2: at most 128 optimised keyframes per window" in str(e.value)      # ORBX_ERR_INVALID
+    batch = gpu_handle.ba_solve_visual_batch(cam, cfg, wins)
+    w = wins[15]
+    s = gpu_handle.ba_solve_visual(cam, cfg, w["poses_cw"], w["fixed_cw"], w["points"], w["obs"])
+    assert batch[15]["iterations"] == s["iterations"] and batch[15]["initial_error"] == s["initial_error"] and batch[15]["final_error"] == s["final_error"]
+    assert np.array_equal(batch[15]["poses_wc"], s["poses_wc"]) and np.array_equal(batch[15]["points"], s["points"])
+
+
 def test_ba_observations_from_pinned_memory_equal_staged(gpu_handle, pkg):
     """The observation CSR is built on the device from the observations as handed over (ba_prep_*_kernel).  Windows whose `obs` arrays are
     consecutive slices of one page-locked buffer are read by the copy engine where they lie, one copy per half (Handle.pack_ba_windows);
