@@ -329,6 +329,67 @@ int orbx_keyframe_fuse_search(orbx_handle* h, const orbx_camera* cam, const doub
                               const orbx_keyframe* const* kfs, int T, double radius_scale, unsigned desc_threshold,
                               int* out_idx, uint32_t* out_dist);
 
+/* ---- new map points from neighbour keyframes (src/local_mapping/triangulation.rs) ------------------------------------------
+ * The pair loop of triangulate_from_neighbors (CreateNewMapPoints, :117-294): for every (idx1, idx2) a search returned — the
+ * parallax test (:186-224), the choice between a DLT point and a stereo-depth point (:226-253), triangulate_dlt (:715-760; the
+ * null vector of the 4x4 system by one-sided Jacobi in f64) and validate_triangulation (:776-850).  All arithmetic is f64 on the
+ * device; keypoint coordinates are the f32 of orbx_keypoint widened. */
+/* = TriangulationConfig, triangulation.rs:20-52.  num_neighbors and min_baseline_ratio are carried for the caller (the reference's
+ * loop does not read them either); max_descriptor_dist goes to the search and must be <= 256 (the largest Hamming distance of two
+ * 256-bit descriptors; the limit of orbx_search_for_triangulation's max_dist), else ORBX_ERR_INVALID. */
+typedef struct {
+  int num_neighbors;
+  unsigned max_descriptor_dist;
+  double min_baseline_ratio, min_parallax_inertial, min_parallax_visual, max_reproj_error_mono, max_reproj_error_stereo,
+      scale_ratio_factor;
+} orbx_triangulation_config;
+/* 10, TH_LOW = 50, 0.01, acos(0.9996), acos(0.9998), 5.991, 7.8, 1.5 (:39-52) */
+void orbx_default_triangulation_config(orbx_triangulation_config* cfg);
+/* what became of a pair: out_status = ORBX_TRI_* | ORBX_TRI_METHOD_* << 8 */
+enum {
+  ORBX_TRI_CREATED = 0,          /* point accepted                                              */
+  ORBX_TRI_SKIPPED = 1,          /* no triangulation method (:245, :252)                        */
+  ORBX_TRI_DLT_DEGENERATE = 2,   /* |w| < 1e-10 (:751)                                          */
+  ORBX_TRI_REJ_DEPTH = 3,        /* depth not positive in a camera (:794)                       */
+  ORBX_TRI_REJ_REPROJ1 = 4,      /* reprojection error in camera 1 (:808)                       */
+  ORBX_TRI_REJ_REPROJ2 = 5,      /* ... in camera 2 (:821)                                      */
+  ORBX_TRI_REJ_DIST = 6,         /* closer than 1e-6 to a camera centre (:831)                  */
+  ORBX_TRI_REJ_SCALE = 7,        /* distance ratio against octave ratio (:843)                  */
+  ORBX_TRI_BAD_INDEX = 8         /* device form: pair index out of range, nothing was read      */
+};
+enum { ORBX_TRI_METHOD_DLT = 0, ORBX_TRI_METHOD_STEREO_CURRENT = 1, ORBX_TRI_METHOD_STEREO_NEIGHBOUR = 2 };
+/* Pairs from any search (orbx_search_for_triangulation[_bow], ...) between keyframe 1 (the current one) and keyframe 2.
+ *   kp [n], points_cam [n][3] + has_point [n] (1 = Some; both may be NULL: every point None), pose_wc [7] (qw,qx,qy,qz,tx,ty,tz);
+ *   pairs [n_pairs][2] = (idx1, idx2); out_points [n_pairs][3] (the point wherever one was formed, else 0), out_status [n_pairs].
+ * The host form rejects an index out of range with ORBX_ERR_INVALID; the device form (every array in device memory, poses on the
+ * host, asynchronous on the handle's stream) marks such a pair ORBX_TRI_BAD_INDEX without reading anything for it. */
+int orbx_triangulate_pairs(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                           const orbx_keypoint* kp1, const double* points_cam1, const uint8_t* has_point1, int n1, const double* pose1_wc,
+                           const orbx_keypoint* kp2, const double* points_cam2, const uint8_t* has_point2, int n2, const double* pose2_wc,
+                           const int* pairs, int n_pairs, double* out_points, uint16_t* out_status);
+int orbx_triangulate_pairs_device(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                                  const orbx_keypoint* d_kp1, const double* d_points_cam1, const uint8_t* d_has_point1, int n1,
+                                  const double* pose1_wc, const orbx_keypoint* d_kp2, const double* d_points_cam2,
+                                  const uint8_t* d_has_point2, int n2, const double* pose2_wc, const int* d_pairs, int n_pairs,
+                                  double* d_out_points, uint16_t* d_out_status);
+/* The keyframe's FeatureVector as one node id per feature (the out_node of orbx_bow_transform, 0xffffffff = in no list): the
+ * encoding orbx_search_for_triangulation_bow takes.  The keyframe keeps a host copy and the node-sorted index the search needs.
+ * NULL clears it. */
+int orbx_keyframe_set_feature_nodes(orbx_keyframe* kf, const uint32_t* node);
+/* triangulate_from_neighbors (:71-308) for a device-resident current keyframe and its T <= 256 neighbours, in the given order, in
+ * one call: the host does the baseline test (:137-141) and the epipolar geometry; the device then runs the T searches side by side
+ * (the FeatureVector form where both keyframes carry nodes, :145, else the grid form; max_dist = cfg->max_descriptor_dist), the pair
+ * loop over every match, and an ordered compaction of the accepted points — one upload, one download, one synchronisation.  The
+ * searches read the current keyframe's map-point flags as they are at the call (the reference clones them before the loop, :94-107).
+ *   out_neighbour / out_idx1 / out_idx2 [cap], out_points [cap][3]: the new points in the reference's creation order (neighbour,
+ *   then the search's pair order); *n_out: how many there are — when it exceeds cap only the first cap were written and the caller
+ *   calls again with more room (the convention of orbx_kfdb_detect_loop_candidates).
+ *   stats [T][4] = searched (0: skipped by the baseline test or an empty keyframe), matches_found, triangulated, validated.
+ * The caller then does create_map_point + the two associate calls per entry, in list order (:286-290). */
+int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                                             const orbx_keyframe* kf_current, const orbx_keyframe* const* kfs, int T, int cap,
+                                             int* out_neighbour, int* out_idx1, int* out_idx2, double* out_points, int* n_out, int* stats);
+
 /* ---- input side (src/io/euroc.rs) ------------------------------------------------------------------------------
  * Host code: the EuRoC `mav0` reader of EurocDataset::new / len / frame_timestamp / stereo_pair (:64-132,
  * load_image_list :189-211, the camera part of load_stereo_calibration :325-360) and the PNG decode that

@@ -451,6 +451,78 @@ inline std::vector<std::pair<size_t, size_t>> search_for_triangulation_bow(
   return out;
 }
 
+// ---- new map points from neighbour keyframes (src/local_mapping/triangulation.rs) ---------------------------------------
+struct TriangulationConfig {   // triangulation.rs:20-52
+  size_t num_neighbors = 10;
+  uint32_t max_descriptor_dist = 50;                  // TH_LOW
+  double min_baseline_ratio = 0.01;
+  double min_parallax_inertial = std::acos(0.9996), min_parallax_visual = std::acos(0.9998);
+  double max_reproj_error_mono = 5.991, max_reproj_error_stereo = 7.8, scale_ratio_factor = 1.5;
+  orbx_triangulation_config c() const {
+    return orbx_triangulation_config{(int)num_neighbors, max_descriptor_dist, min_baseline_ratio, min_parallax_inertial, min_parallax_visual,
+                                     max_reproj_error_mono, max_reproj_error_stereo, scale_ratio_factor};
+  }
+};
+struct TriangulationResult {   // triangulation.rs:55-61
+  size_t num_new_points = 0, num_pairs_checked = 0, num_matches_found = 0, num_triangulated = 0, num_validated = 0;
+};
+struct NewMapPoint {           // what :286-290 consumes: create_map_point(position, descriptor_of(idx1), current) + two associate calls
+  size_t neighbour_index, idx1, idx2;
+  std::array<double, 3> position;
+};
+// The pair loop (:184-293) on pairs from any search; status[i] = ORBX_TRI_* | ORBX_TRI_METHOD_* << 8.  points_cam may be empty
+// (every point None), else has_point marks the Some entries.
+inline std::vector<uint16_t> triangulate_pairs(Handle& h, const CameraModel& camera, const TriangulationConfig& config, bool is_inertial,
+                                               const FeatureSet& f1, const std::vector<std::array<double, 3>>& points_cam1,
+                                               const std::vector<uint8_t>& has_point1, const SE3& pose1, const FeatureSet& f2,
+                                               const std::vector<std::array<double, 3>>& points_cam2, const std::vector<uint8_t>& has_point2,
+                                               const SE3& pose2, const std::vector<std::pair<size_t, size_t>>& pairs,
+                                               std::vector<std::array<double, 3>>& points_out) {
+  const double p1[7] = {pose1.rotation[0], pose1.rotation[1], pose1.rotation[2], pose1.rotation[3], pose1.translation[0], pose1.translation[1], pose1.translation[2]};
+  const double p2[7] = {pose2.rotation[0], pose2.rotation[1], pose2.rotation[2], pose2.rotation[3], pose2.translation[0], pose2.translation[1], pose2.translation[2]};
+  const int n = (int)pairs.size();
+  std::vector<int> pr((size_t)std::max(n, 1) * 2);
+  for (int i = 0; i < n; ++i) { pr[2 * (size_t)i] = (int)pairs[(size_t)i].first; pr[2 * (size_t)i + 1] = (int)pairs[(size_t)i].second; }
+  std::vector<uint16_t> status((size_t)std::max(n, 1));
+  points_out.assign((size_t)std::max(n, 1), std::array<double, 3>{0, 0, 0});
+  const orbx_camera cam = camera.c();
+  const orbx_triangulation_config cfg = config.c();
+  h.check(orbx_triangulate_pairs(h.get(), &cam, &cfg, is_inertial ? 1 : 0, f1.keypoints.data(), points_cam1.empty() ? nullptr : points_cam1[0].data(),
+                                 points_cam1.empty() ? nullptr : has_point1.data(), (int)f1.keypoints.size(), p1, f2.keypoints.data(),
+                                 points_cam2.empty() ? nullptr : points_cam2[0].data(), points_cam2.empty() ? nullptr : has_point2.data(),
+                                 (int)f2.keypoints.size(), p2, pr.data(), n, points_out[0].data(), status.data()));
+  status.resize((size_t)n); points_out.resize((size_t)n);
+  return status;
+}
+// triangulate_from_neighbors (:71-308) on device-resident keyframes (orbx_keyframe_create): `neighbours` in the order
+// get_neighbor_keyframes returned them.  One library call; the list comes back in the reference's creation order.
+inline std::vector<NewMapPoint> triangulate_from_neighbors(Handle& h, const CameraModel& camera, const TriangulationConfig& config, bool is_inertial,
+                                                           const orbx_keyframe* current, const std::vector<const orbx_keyframe*>& neighbours,
+                                                           TriangulationResult& result) {
+  const int T = (int)neighbours.size();
+  const orbx_camera cam = camera.c();
+  const orbx_triangulation_config cfg = config.c();
+  std::vector<int> stats((size_t)std::max(T, 1) * 4), nb, i1, i2;
+  std::vector<double> pts;
+  int n = 0;
+  for (int cap = 1024;; cap = n) {
+    nb.assign((size_t)cap, 0); i1.assign((size_t)cap, 0); i2.assign((size_t)cap, 0); pts.assign(3 * (size_t)cap, 0.0);
+    h.check(orbx_keyframe_triangulate_from_neighbors(h.get(), &cam, &cfg, is_inertial ? 1 : 0, current, neighbours.data(), T, cap, nb.data(), i1.data(),
+                                                     i2.data(), pts.data(), &n, stats.data()));
+    if (n <= cap) break;
+  }
+  result = TriangulationResult{};
+  result.num_new_points = (size_t)n; result.num_pairs_checked = (size_t)T;
+  for (int t = 0; t < T; ++t) {
+    result.num_matches_found += (size_t)stats[4 * (size_t)t + 1]; result.num_triangulated += (size_t)stats[4 * (size_t)t + 2];
+    result.num_validated += (size_t)stats[4 * (size_t)t + 3];
+  }
+  std::vector<NewMapPoint> out((size_t)n);
+  for (int i = 0; i < n; ++i)
+    out[(size_t)i] = NewMapPoint{(size_t)nb[(size_t)i], (size_t)i1[(size_t)i], (size_t)i2[(size_t)i], {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]}};
+  return out;
+}
+
 // ---- global bundle adjustment (src/optimizer/global_ba.rs) --------------------------------------------------------
 struct GlobalBAConfig {   // global_ba.rs:21-46
   int max_iterations = 10;

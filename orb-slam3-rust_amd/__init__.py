@@ -15,5 +15,7 @@ from .api import (  # noqa: F401
     PnPConfig, PnPResult, PNP_RESULT, PNP_OK, PNP_NO_MODEL, PNP_TOO_FEW, PNP_OVER_MAX_N, solve_pnp_ransac, solve_pnp_ransac_detailed,
     PoseInertialConfig, PoseInertialResult, POSE_INERTIAL_RESULT, POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR,
     pose_inertial_optimization, KeyFrameDatabase, LoopDetectorConfig, LoopCandidate, ConsistencyChecker, KFDB_SCORE_L1, KFDB_SCORE_DOT,
-    KFDB_MAX_WORDS)
+    KFDB_MAX_WORDS, TriangulationConfig, TriangulationResult, TRI_CREATED, TRI_SKIPPED, TRI_DLT_DEGENERATE, TRI_REJ_DEPTH, TRI_REJ_REPROJ1,
+    TRI_REJ_REPROJ2, TRI_REJ_DIST, TRI_REJ_SCALE, TRI_BAD_INDEX, TRI_METHOD_DLT, TRI_METHOD_STEREO_CURRENT, TRI_METHOD_STEREO_NEIGHBOUR,
+    TRI_MAX_NEIGHBOURS, FEATURE_NODE_NONE)
 from .build import LIB_PATH, build  # noqa: F401

@@ -89,6 +89,8 @@ ABI_SYMBOLS = [
     "orbx_default_loop_detector_config", "orbx_kfdb_create", "orbx_kfdb_destroy", "orbx_kfdb_add", "orbx_kfdb_add_device", "orbx_kfdb_erase",
     "orbx_kfdb_set_bad", "orbx_kfdb_size", "orbx_kfdb_compact", "orbx_kfdb_download", "orbx_kfdb_score", "orbx_kfdb_detect_candidates",
     "orbx_kfdb_detect_loop_candidates", "orbx_kfdb_detect_loop_candidates_batch",
+    "orbx_default_triangulation_config", "orbx_triangulate_pairs", "orbx_triangulate_pairs_device", "orbx_keyframe_set_feature_nodes",
+    "orbx_keyframe_triangulate_from_neighbors",
 ]
 
 
@@ -180,6 +182,21 @@ class _LoopDetectorConfig(C.Structure):
     """orbx_loop_detector_config (include/orbx.h)"""
     _fields_ = [("min_score_ratio", C.c_double), ("consistency_threshold", C.c_int), ("min_covisibles_for_threshold", C.c_int),
                 ("max_covisibles_to_check", C.c_int), ("min_temporal_gap", C.c_int)]
+
+
+class _TriangulationConfig(C.Structure):
+    """orbx_triangulation_config (include/orbx.h)"""
+    _fields_ = [("num_neighbors", C.c_int), ("max_descriptor_dist", C.c_uint), ("min_baseline_ratio", C.c_double),
+                ("min_parallax_inertial", C.c_double), ("min_parallax_visual", C.c_double), ("max_reproj_error_mono", C.c_double),
+                ("max_reproj_error_stereo", C.c_double), ("scale_ratio_factor", C.c_double)]
+
+
+# ORBX_TRI_* / ORBX_TRI_METHOD_*: a pair's status word is status | method << 8
+(TRI_CREATED, TRI_SKIPPED, TRI_DLT_DEGENERATE, TRI_REJ_DEPTH, TRI_REJ_REPROJ1, TRI_REJ_REPROJ2, TRI_REJ_DIST, TRI_REJ_SCALE,
+ TRI_BAD_INDEX) = range(9)
+TRI_METHOD_DLT, TRI_METHOD_STEREO_CURRENT, TRI_METHOD_STEREO_NEIGHBOUR = 0, 1, 2
+TRI_MAX_NEIGHBOURS = 256
+FEATURE_NODE_NONE = 0xFFFFFFFF            # orbx_keyframe_set_feature_nodes: the feature is in no FeatureVector list
 
 
 KFDB_SCORE_L1, KFDB_SCORE_DOT = 0, 1      # ORBX_KFDB_SCORE_*
@@ -384,6 +401,34 @@ class PoseInertialResult:
 def _pose_inertial_state(problem):
     """(pose_wc [7], velocity [3], bias [6], prev_kf_pose_wc [7], prev_kf_velocity [3], preint [11]) as f64 arrays"""
     return [np.ascontiguousarray(np.asarray(x, np.float64).reshape(k)) for x, k in zip(problem, (7, 3, 6, 7, 3, 11))]
+
+
+@dataclass
+class TriangulationConfig:
+    """TriangulationConfig, triangulation.rs:20-52"""
+    num_neighbors: int = 10
+    max_descriptor_dist: int = TH_LOW
+    min_baseline_ratio: float = 0.01
+    min_parallax_inertial: float = math.acos(0.9996)
+    min_parallax_visual: float = math.acos(0.9998)
+    max_reproj_error_mono: float = 5.991
+    max_reproj_error_stereo: float = 7.8
+    scale_ratio_factor: float = 1.5
+
+    def _c(self):
+        return _TriangulationConfig(self.num_neighbors, self.max_descriptor_dist, self.min_baseline_ratio, self.min_parallax_inertial,
+                                    self.min_parallax_visual, self.max_reproj_error_mono, self.max_reproj_error_stereo, self.scale_ratio_factor)
+
+
+@dataclass
+class TriangulationResult:
+    """TriangulationResult, triangulation.rs:55-61; per_neighbour [T,4] = searched, matches_found, triangulated, validated."""
+    num_new_points: int = 0
+    num_pairs_checked: int = 0
+    num_matches_found: int = 0
+    num_triangulated: int = 0
+    num_validated: int = 0
+    per_neighbour: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -669,6 +714,40 @@ class Handle:
             self._h, C.byref(cam), _vp(kp1), _vp(desc1), _vp(mp1), _vp(stereo1), C.c_int(n1), _vp(kp2), _vp(desc2), _vp(mp2), C.c_int(n2),
             _vp(p1), _vp(p2), C.c_uint(max_dist), _vp(pairs), _vp(cnt)))
         return pairs, cnt
+
+    def triangulate_pairs(self, camera, kp1, points_cam1, has_point1, pose1_wc, kp2, points_cam2, has_point2, pose2_wc, pairs,
+                          config: "TriangulationConfig" = None, is_inertial=False):
+        """The pair loop of triangulate_from_neighbors (triangulation.rs:184-293) on host arrays.  Returns (points [n,3] f64,
+        status [n] u16 = TRI_* | TRI_METHOD_* << 8).  points_cam / has_point may both be None (every point None)."""
+        kp1 = np.ascontiguousarray(kp1, KEYPOINT); kp2 = np.ascontiguousarray(kp2, KEYPOINT)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        f = lambda a, t, shape: None if a is None else np.ascontiguousarray(a, t).reshape(shape)
+        p1, h1, p2, h2 = f(points_cam1, np.float64, (-1, 3)), f(has_point1, np.uint8, -1), f(points_cam2, np.float64, (-1, 3)), f(has_point2, np.uint8, -1)
+        q1 = np.ascontiguousarray(pose1_wc, np.float64).reshape(7); q2 = np.ascontiguousarray(pose2_wc, np.float64).reshape(7)
+        n = len(pairs)
+        pts = np.zeros((max(n, 1), 3)); st = np.zeros(max(n, 1), np.uint16)
+        cam = camera._c(); cfg = (config or TriangulationConfig())._c()
+        self._check(self._L.orbx_triangulate_pairs(self._h, C.byref(cam), C.byref(cfg), C.c_int(int(bool(is_inertial))), _vp(kp1), _vp(p1), _vp(h1),
+                                                   C.c_int(len(kp1)), _vp(q1), _vp(kp2), _vp(p2), _vp(h2), C.c_int(len(kp2)), _vp(q2), _vp(pairs),
+                                                   C.c_int(n), _vp(pts), _vp(st)))
+        return pts[:n], st[:n]
+
+    def triangulate_pairs_device(self, camera, kp1, points_cam1, has_point1, pose1_wc, kp2, points_cam2, has_point2, pose2_wc, pairs,
+                                 config: "TriangulationConfig" = None, is_inertial=False):
+        """Device-resident form: torch CUDA tensors (kp [n,7] f32 as the extractor writes them, points [n,3] f64, flags [n] u8, pairs
+        [m,2] int32), poses on the host.  Returns (points [m,3] f64, status [m] int16 view of u16) tensors; asynchronous.  A pair
+        whose index is out of range comes back TRI_BAD_INDEX."""
+        import torch
+        n1, n2, n = kp1.shape[0], kp2.shape[0], pairs.shape[0]
+        pts = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=pairs.device)
+        st = torch.zeros(max(n, 1), dtype=torch.int16, device=pairs.device)
+        q1 = np.ascontiguousarray(pose1_wc, np.float64).reshape(7); q2 = np.ascontiguousarray(pose2_wc, np.float64).reshape(7)
+        cam = camera._c(); cfg = (config or TriangulationConfig())._c()
+        self._after_torch(kp1, kp2, pairs, pts, st, *[t for t in (points_cam1, has_point1, points_cam2, has_point2) if t is not None])
+        self._check(self._L.orbx_triangulate_pairs_device(self._h, C.byref(cam), C.byref(cfg), C.c_int(int(bool(is_inertial))), _vp(kp1),
+                                                          _vp(points_cam1), _vp(has_point1), C.c_int(n1), _vp(q1), _vp(kp2), _vp(points_cam2),
+                                                          _vp(has_point2), C.c_int(n2), _vp(q2), _vp(pairs), C.c_int(n), _vp(pts), _vp(st)))
+        return pts[:n], st[:n]
 
     def fuse_search_device(self, camera, positions, mp_desc, kf_poses_wc, kf_feat_offset, kps, descs, radius_scale, desc_threshold=TH_LOW):
         """Device-resident form of fuse_search: torch CUDA tensors except the poses.  Returns (idx [P,T] int32, dist [P,T] int32 view of u32)."""
@@ -1188,6 +1267,9 @@ class KeyFrame:
         L.orbx_keyframe_guided_match.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                                  C.c_int, C.c_void_p, C.c_void_p]
         L.orbx_keyframe_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+        L.orbx_keyframe_set_feature_nodes.argtypes = [C.c_void_p, C.c_void_p]
+        L.orbx_keyframe_triangulate_from_neighbors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + \
+            [C.c_void_p] * 6
         L.orbx_keyframe_fuse_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_uint,
                                                 C.c_void_p, C.c_void_p]
         self._p = C.c_void_p()
@@ -1243,6 +1325,40 @@ class KeyFrame:
         self._handle._check(self._L.orbx_keyframe_search_for_triangulation(self._handle._h, C.byref(cam), self._p, other._p, int(max_dist),
                                                                            _vp(pairs), C.byref(n)))
         return pairs[:n.value].copy()
+
+    def set_feature_nodes(self, node):
+        """The FeatureVector as one node id per feature (OrbVocabulary.transform_arrays' out_node; FEATURE_NODE_NONE = in no list);
+        None clears it.  With nodes on both keyframes triangulate_from_neighbors searches by node (triangulation.rs:145)."""
+        if node is None:
+            self._handle._check(self._L.orbx_keyframe_set_feature_nodes(self._p, None))
+            return
+        a = np.ascontiguousarray(node, np.uint32).reshape(-1)
+        assert len(a) == self.n
+        self._handle._check(self._L.orbx_keyframe_set_feature_nodes(self._p, _vp(a)))
+
+    def triangulate_from_neighbors(self, camera, neighbours, config: "TriangulationConfig" = None, is_inertial=False, cap=None):
+        """triangulate_from_neighbors (triangulation.rs:71-308) with this keyframe as the current one and `neighbours` in the order
+        get_neighbor_keyframes gave them: one library call.  Returns (neighbour [m] int32 index into `neighbours`, idx1 [m], idx2 [m],
+        points [m,3] f64, TriangulationResult) in the reference's creation order; the caller then does create_map_point + the two
+        associate calls per entry.  cap: room for the first try (default 1024; the call is repeated when more points were made)."""
+        T = len(neighbours)
+        arr = (C.c_void_p * max(T, 1))(*[k._p for k in neighbours])
+        cam = camera._c(); cfg = (config or TriangulationConfig())._c()
+        stats = np.zeros((max(T, 1), 4), np.int32)
+        cap = 1024 if cap is None else int(cap)
+        while True:
+            nb = np.zeros(max(cap, 1), np.int32); i1 = np.zeros(max(cap, 1), np.int32); i2 = np.zeros(max(cap, 1), np.int32)
+            pts = np.zeros((max(cap, 1), 3)); n = C.c_int()
+            self._handle._check(self._L.orbx_keyframe_triangulate_from_neighbors(
+                self._handle._h, C.byref(cam), C.byref(cfg), C.c_int(int(bool(is_inertial))), self._p, arr, C.c_int(T), C.c_int(cap), _vp(nb), _vp(i1),
+                _vp(i2), _vp(pts), C.byref(n), _vp(stats)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        m = n.value
+        stats = stats[:T]
+        res = TriangulationResult(m, T, int(stats[:, 1].sum()), int(stats[:, 2].sum()), int(stats[:, 3].sum()), stats)
+        return nb[:m], i1[:m], i2[:m], pts[:m], res
 
     @staticmethod
     def fuse_search(handle, camera, positions, mp_desc, keyframes, radius_scale, desc_threshold=50):

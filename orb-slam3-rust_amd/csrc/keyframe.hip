@@ -3,6 +3,8 @@
 // associations of a processed frame — feeds the descriptor searches of local mapping (guided match, triangulation search,
 // fuse search: SURVEY.md §8f rows 1 and 3) without a D2H / H2D round trip of 60 bytes per feature per search.
 // Host code only: the searches themselves are the *_device entry points of orbx_api.hip.
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "orbx_internal.hpp"
@@ -19,6 +21,12 @@ struct orbx_keyframe {
   uint8_t* d_has_point = nullptr;
   uint8_t* d_mp_flag = nullptr;
   std::vector<int64_t> mp_ids;       // matched_map_points (host side: ids are map bookkeeping), -1 = None
+  // FeatureVector as one node id per feature (orbx_keyframe_set_feature_nodes): host copy, and the feature indices sorted by
+  // (node, index) with the features in no list cut off the end — every node's list in push order (vocabulary/mod.rs:309)
+  bool has_nodes = false;
+  std::vector<uint32_t> node;
+  std::vector<int> node_sorted;
+  int node_m = 0;
 };
 
 extern "C" {
@@ -153,6 +161,159 @@ int orbx_keyframe_search_for_triangulation(orbx_handle* h, const orbx_camera* ca
   ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   ORBX_HIP(h, hipStreamSynchronize(h->stream));
   if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+int orbx_keyframe_set_feature_nodes(orbx_keyframe* kf, const uint32_t* node) {
+  if (!kf) return ORBX_ERR_INVALID;
+  kf->has_nodes = false; kf->node.clear(); kf->node_sorted.clear(); kf->node_m = 0;
+  if (!node) return ORBX_OK;
+  const int n = kf->n;
+  kf->node.assign(node, node + n);
+  kf->node_sorted.resize((size_t)n);
+  for (int i = 0; i < n; ++i) kf->node_sorted[(size_t)i] = i;
+  std::stable_sort(kf->node_sorted.begin(), kf->node_sorted.end(), [&](int a, int b) { return node[a] < node[b]; });
+  int m = n;
+  while (m > 0 && node[kf->node_sorted[(size_t)m - 1]] == 0xffffffffu) --m;
+  kf->node_m = m;
+  kf->has_nodes = true;
+  return ORBX_OK;
+}
+
+// triangulate_from_neighbors (triangulation.rs:71-308) without get_neighbor_keyframes and the map mutation: see include/orbx.h.
+int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                                             const orbx_keyframe* cur, const orbx_keyframe* const* kfs, int T, int cap, int* out_neighbour,
+                                             int* out_idx1, int* out_idx2, double* out_points, int* n_out, int* stats) {
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || !cur || cur->h != h || !n_out || T < 0 || T > 256 || cap < 0 || cfg->max_descriptor_dist > 256 || (T > 0 && (!kfs || !stats)) ||
+      (cap > 0 && (!out_neighbour || !out_idx1 || !out_idx2 || !out_points)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: bad argument (T <= 256; max_descriptor_dist <= 256; a keyframe belongs to the handle that made it)");
+  *n_out = 0;
+  for (int t = 0; t < T; ++t)
+    if (!kfs[t] || kfs[t]->h != h)
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: keyframe %d is null or of another handle", t);
+  if (T == 0) return ORBX_OK;
+  memset(stats, 0, sizeof(int) * 4 * (size_t)T);
+  const int n1 = cur->n;
+  int cols = 0, rows = 0;
+  const bool grid_ok = tri_grid_dims(cam, &cols, &rows);
+  std::vector<int> orig;                                                 // searched neighbour k -> index in kfs
+  int max_n2 = 0;
+  for (int t = 0; t < T; ++t) {
+    const double dx = kfs[t]->pose_wc[4] - cur->pose_wc[4], dy = kfs[t]->pose_wc[5] - cur->pose_wc[5], dz = kfs[t]->pose_wc[6] - cur->pose_wc[6];
+    if (std::sqrt(dx * dx + dy * dy + dz * dz) < cam->baseline) continue;                  // :137-141
+    if (n1 == 0 || kfs[t]->n == 0) continue;
+    const bool bow = cur->has_nodes && kfs[t]->has_nodes;                                   // :145
+    if (!bow && !grid_ok) continue;
+    orig.push_back(t);
+    max_n2 = std::max(max_n2, kfs[t]->n);
+  }
+  const int Ts = (int)orig.size();
+  if (Ts == 0) return ORBX_OK;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // ---- layout of the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch] [status | points] [result blob]
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+  struct Slices { size_t sorted, lo, hi, cell_start, prop, owner, pairs, n_out, cell_of, taken; bool bow; };
+  std::vector<Slices> sl((size_t)Ts);
+  const size_t o_items = take(sizeof(TriBatchItem) * (size_t)Ts), o_nbs = take(sizeof(TriNeighbour) * (size_t)Ts);
+  for (int k = 0; k < Ts; ++k) {
+    const orbx_keyframe* kf = kfs[orig[(size_t)k]];
+    sl[(size_t)k].bow = cur->has_nodes && kf->has_nodes;
+    if (sl[(size_t)k].bow) { sl[(size_t)k].sorted = take(4 * (size_t)kf->n); sl[(size_t)k].lo = take(4 * (size_t)n1); sl[(size_t)k].hi = take(4 * (size_t)n1); }
+  }
+  const size_t up_bytes = off;
+  for (int k = 0; k < Ts; ++k) {
+    const size_t n2 = (size_t)kfs[orig[(size_t)k]]->n;
+    Slices& s = sl[(size_t)k];
+    if (!s.bow) { s.cell_start = take(4 * 4100); s.sorted = take(4 * n2); s.cell_of = take(2 * n2); }
+    s.prop = take(4 * (size_t)n1); s.owner = take(4 * n2); s.pairs = take(8 * (size_t)n1); s.n_out = take(16); s.taken = take(n2);
+  }
+  const size_t slots = (size_t)Ts * (size_t)n1;
+  const size_t o_status = take(2 * slots), o_points = take(24 * slots);
+  const size_t capd = std::min((size_t)cap, slots);
+  const size_t o_res = off, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd, r_i1 = r_nb + 4 * capd,
+               r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
+  off += res_bytes;
+  if (int rc = orbx_reserve(h, h->ws_io[10], off)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_io[10].p;
+  // ---- host side of the step: epipolar geometry per neighbour, candidate ranges where both keyframes carry nodes
+  std::vector<uint8_t> up(up_bytes), down(res_bytes);
+  TriBatchItem* items = (TriBatchItem*)(up.data() + o_items);
+  TriNeighbour* nbs = (TriNeighbour*)(up.data() + o_nbs);
+  for (int k = 0; k < Ts; ++k) {
+    const orbx_keyframe* kf = kfs[orig[(size_t)k]];
+    const Slices& s = sl[(size_t)k];
+    TriBatchItem it{};
+    double ep[2];
+    orbx_triangulation_geometry(cam, cur->pose_wc, kf->pose_wc, ep, it.A.F);
+    it.A.epx = ep[0]; it.A.epy = ep[1];
+    it.A.cols = s.bow ? 0 : cols; it.A.rows = s.bow ? 0 : rows; it.A.max_dist = cfg->max_descriptor_dist; it.A.n1 = n1; it.A.n2 = kf->n;
+    it.A.kp1 = cur->d_kp; it.A.desc1 = cur->d_desc; it.A.mp1 = cur->d_mp_flag; it.A.stereo1 = cur->d_has_point;
+    it.A.kp2 = kf->d_kp; it.A.desc2 = kf->d_desc;
+    it.A.sorted_idx = (const int*)(d + s.sorted);
+    it.A.taken = d + s.taken;
+    if (s.bow) {
+      it.A.rng_lo = (const int*)(d + s.lo); it.A.rng_hi = (const int*)(d + s.hi);
+      int* sorted = (int*)(up.data() + s.sorted); int* lo = (int*)(up.data() + s.lo); int* hi = (int*)(up.data() + s.hi);
+      if (kf->n > 0) memcpy(sorted, kf->node_sorted.data(), 4 * (size_t)kf->n);
+      const uint32_t* node2 = kf->node.data();
+      const int* sb = kf->node_sorted.data(); const int* se = sb + kf->node_m;
+      for (int i = 0; i < n1; ++i) {                                                       // the features of keyframe 2 in feature i's node (:577-581)
+        lo[i] = hi[i] = 0;
+        const uint32_t key = cur->node[(size_t)i];
+        if (key == 0xffffffffu) continue;
+        const int* b = std::lower_bound(sb, se, key, [&](int a, uint32_t kk) { return node2[a] < kk; });
+        const int* e = std::upper_bound(b, se, key, [&](uint32_t kk, int a) { return kk < node2[a]; });
+        lo[i] = (int)(b - sb); hi[i] = (int)(e - sb);
+      }
+    } else {
+      it.A.cell_start = (const int*)(d + s.cell_start); it.A.cell_of = (const unsigned short*)(d + s.cell_of);
+    }
+    it.mp2 = kf->d_mp_flag;
+    it.prop = (int*)(d + s.prop); it.owner = (int*)(d + s.owner); it.pairs = (int*)(d + s.pairs); it.n_out = (int*)(d + s.n_out);
+    items[k] = it;
+    TriNeighbour nb{};
+    nb.kp2 = kf->d_kp; nb.pts2 = kf->d_points; nb.has2 = kf->d_has_point; nb.n2 = kf->n;
+    memcpy(nb.pose2, kf->pose_wc, sizeof(nb.pose2));
+    nb.pairs = it.pairs; nb.n_pairs_dev = it.n_out; nb.n_pairs = 0; nb.out_base = k * n1;
+    nbs[k] = nb;
+  }
+  TriCommon c{};
+  tri_common_fill(&c, cam, cfg, is_inertial);
+  c.kp1 = cur->d_kp; c.pts1 = cur->d_points; c.has1 = cur->d_has_point; c.n1 = n1;
+  memcpy(c.pose1, cur->pose_wc, sizeof(c.pose1));
+  // ---- one upload, the launches, one download, one synchronisation
+  hipStream_t st = h->stream;
+  hipError_t e = hipMemcpyAsync(d, up.data(), up_bytes, hipMemcpyHostToDevice, st);
+  int rc = ORBX_OK;
+  if (e == hipSuccess) {
+    orbx_prof_begin_call(h);
+    rc = launch_search_for_triangulation_batch(h, (const TriBatchItem*)(d + o_items), Ts, n1, max_n2);
+    if (!rc) rc = launch_triangulate_pairs(h, c, TriNeighbour{}, (const TriNeighbour*)(d + o_nbs), Ts, n1, (uint16_t*)(d + o_status), (double*)(d + o_points));
+    if (!rc) rc = launch_triangulate_compact(h, (const TriNeighbour*)(d + o_nbs), Ts, (const uint16_t*)(d + o_status), (const double*)(d + o_points), (int)capd,
+                                             (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1), (int*)(d + o_res + r_i2),
+                                             (double*)(d + o_res + r_pts));
+    if (!rc) e = hipMemcpyAsync(down.data(), d + o_res, res_bytes, hipMemcpyDeviceToHost, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);                       // also on the error paths: `up` / `down` are locals
+  if (rc) return rc;
+  if (e != hipSuccess || es != hipSuccess)
+    return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_triangulate_from_neighbors: %s", hipGetErrorString(e != hipSuccess ? e : es));
+  const int* head = (const int*)(down.data() + r_head);
+  for (int k = 0; k < Ts; ++k) {
+    int* s4 = stats + 4 * (size_t)orig[(size_t)k];
+    s4[0] = 1; s4[1] = head[2 + 4 * k]; s4[2] = head[3 + 4 * k]; s4[3] = head[4 + 4 * k];
+  }
+  *n_out = head[0];
+  const size_t nw = std::min((size_t)head[0], capd);
+  const int* nb_k = (const int*)(down.data() + r_nb);
+  for (size_t i = 0; i < nw; ++i) out_neighbour[i] = orig[(size_t)nb_k[i]];
+  if (nw > 0) {
+    memcpy(out_idx1, down.data() + r_i1, 4 * nw);
+    memcpy(out_idx2, down.data() + r_i2, 4 * nw);
+    memcpy(out_points, down.data() + r_pts, 24 * nw);
+  }
   return ORBX_OK;
 }
 

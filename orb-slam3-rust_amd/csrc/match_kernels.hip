@@ -662,29 +662,15 @@ __global__ __launch_bounds__(256) void guided_match_kernel(const uint8_t* __rest
 // partner in parallel, ignoring the others; (2) one block walks the proposals in index order — a proposal whose
 // partner is still free is final; one whose partner was taken by an earlier feature is recomputed cooperatively
 // by the whole block against the current `taken` set, then the walk continues.  Only conflicts cost extra work.
-struct TriArgs {
-  double F[9];                 // fundamental matrix, row-major (host, triangulation.rs:670-683)
-  double epx, epy;             // epipole of camera 1 in image 2 (:418-426)
-  int cols, rows;              // 32-px grid over image 2 (:339-346, :437-438)
-  unsigned max_dist;
-  int n1, n2;
-  const orbx_keypoint* kp1; const uint8_t* desc1; const uint8_t* mp1; const uint8_t* stereo1;
-  const orbx_keypoint* kp2; const uint8_t* desc2;
-  const int* cell_start; const int* sorted_idx; const unsigned short* cell_of;
-  uint8_t* taken;              // per feature of keyframe 2: has a map point (mp2) or has been matched
-  // FeatureVector mode (search_for_triangulation_bow, :541-658): candidates of feature i1 are sorted_idx[rng_lo[i1] ..
-  // rng_hi[i1]) = the features of keyframe 2 in the same vocabulary node, ascending; no grid (cell_of == nullptr)
-  const int* rng_lo; const int* rng_hi;
-};
 
 __device__ __forceinline__ int f32_as_cell(float v, int last) {          // Rust `f32 as usize` then .min(last)
   return (v > 0.0f) ? (v >= (float)(last + 1) ? last : (int)v) : 0;
 }
 
-__global__ __launch_bounds__(1024) void tri_grid_build_kernel(const orbx_keypoint* __restrict__ kp, int n, int cols, int rows,
-                                                              const uint8_t* __restrict__ mp2, int* __restrict__ cell_start,
-                                                              int* __restrict__ sorted_idx, unsigned short* __restrict__ cell_of,
-                                                              uint8_t* __restrict__ taken) {
+__device__ __forceinline__ void tri_grid_build_body(const orbx_keypoint* __restrict__ kp, int n, int cols, int rows,
+                                                    const uint8_t* __restrict__ mp2, int* __restrict__ cell_start,
+                                                    int* __restrict__ sorted_idx, unsigned short* __restrict__ cell_of,
+                                                    uint8_t* __restrict__ taken) {
   __shared__ int cnt[4096];
   __shared__ int wsum[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -714,6 +700,13 @@ __global__ __launch_bounds__(1024) void tri_grid_build_kernel(const orbx_keypoin
   for (int k = 0; k < 4; ++k) { if (4 * tid + k <= ncell) cell_start[4 * tid + k] = base; cnt[4 * tid + k] = base; base += c4[k]; }
   __syncthreads();
   for (int i = tid; i < n; i += 1024) sorted_idx[atomicAdd(&cnt[cell_of[i]], 1)] = i;
+}
+
+__global__ __launch_bounds__(1024) void tri_grid_build_kernel(const orbx_keypoint* __restrict__ kp, int n, int cols, int rows,
+                                                              const uint8_t* __restrict__ mp2, int* __restrict__ cell_start,
+                                                              int* __restrict__ sorted_idx, unsigned short* __restrict__ cell_of,
+                                                              uint8_t* __restrict__ taken) {
+  tri_grid_build_body(kp, n, cols, rows, mp2, cell_start, sorted_idx, cell_of, taken);
 }
 
 // best admissible partner of feature i1 over the candidates this thread visits (t, t+stride, ...):
@@ -763,7 +756,7 @@ __device__ __forceinline__ unsigned long long tri_scan(const TriArgs& A, TakenPt
   return best;
 }
 
-__global__ __launch_bounds__(256) void tri_propose_kernel(TriArgs A, int* __restrict__ prop) {
+__device__ __forceinline__ void tri_propose_body(const TriArgs& A, int* __restrict__ prop) {
   const int lane = threadIdx.x & 63;
   const int i1 = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i1 >= A.n1) return;
@@ -774,6 +767,8 @@ __global__ __launch_bounds__(256) void tri_propose_kernel(TriArgs A, int* __rest
   if (lane == 0) prop[i1] = key == ~0ull ? -1 : (int)(unsigned)(key & 0xffffffffull);
 }
 
+__global__ __launch_bounds__(256) void tri_propose_kernel(TriArgs A, int* __restrict__ prop) { tri_propose_body(A, prop); }
+
 // Ordered resolve.  A round looks at the next 256 features at once: a proposal is safe when its partner is free
 // and no earlier feature of the round wants the same partner (owner[] = smallest proposing index, atomicMin).
 // Everything before the first unsafe feature f is committed in order; f is recomputed by the whole block against
@@ -781,8 +776,8 @@ __global__ __launch_bounds__(256) void tri_propose_kernel(TriArgs A, int* __rest
 // owner[] entries left behind by features that are re-examined later stay valid: a feature only changes its
 // proposal when it is the first unsafe one, and then its old partner is already taken.
 template <bool kLds>
-__global__ __launch_bounds__(256) void tri_resolve_kernel(TriArgs A, int* __restrict__ prop, int* __restrict__ owner_g,
-                                                          int* __restrict__ pairs, int* __restrict__ n_out) {
+__device__ __forceinline__ void tri_resolve_body(const TriArgs& A, int* __restrict__ prop, int* __restrict__ owner_g,
+                                                 int* __restrict__ pairs, int* __restrict__ n_out) {
   extern __shared__ __align__(16) unsigned char tri_smem[];
   __shared__ int s_i1, s_n, s_first[4], s_cnt[4];
   __shared__ unsigned long long red[4];
@@ -851,6 +846,39 @@ __global__ __launch_bounds__(256) void tri_resolve_kernel(TriArgs A, int* __rest
     __syncthreads();
   }
   if (tid == 0) *n_out = s_n;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void tri_resolve_kernel(TriArgs A, int* __restrict__ prop, int* __restrict__ owner_g,
+                                                          int* __restrict__ pairs, int* __restrict__ n_out) {
+  tri_resolve_body<kLds>(A, prop, owner_g, pairs, n_out);
+}
+
+// ---- the same search for T neighbours of one keyframe in one set of launches (triangulate_from_neighbors, :117-294) ----
+// The reference clones the current keyframe's map_point_ids before the neighbour loop (:94-107), so nothing one neighbour's search
+// produces is seen by the next: the T searches are independent.  The neighbour is a grid dimension; its TriArgs and workspace
+// slices come from a device array filled by one upload.  Neighbours the host skips (baseline test, empty keyframe) are not in
+// the array: every item has n1 > 0 and n2 > 0.
+__global__ __launch_bounds__(1024) void tri_grid_build_batch_kernel(const TriBatchItem* __restrict__ items) {
+  const TriBatchItem& it = items[blockIdx.x];
+  const int n2 = it.A.n2;
+  if (it.A.rng_lo) {                                                      // FeatureVector form: no grid, only the taken flags (:606-608)
+    for (int i = threadIdx.x; i < n2; i += 1024) it.A.taken[i] = it.mp2[i];
+    return;
+  }
+  tri_grid_build_body(it.A.kp2, n2, it.A.cols, it.A.rows, it.mp2, const_cast<int*>(it.A.cell_start), const_cast<int*>(it.A.sorted_idx),
+                      const_cast<unsigned short*>(it.A.cell_of), it.A.taken);
+}
+
+__global__ __launch_bounds__(256) void tri_propose_batch_kernel(const TriBatchItem* __restrict__ items) {
+  const TriArgs A = items[blockIdx.y].A;
+  tri_propose_body(A, items[blockIdx.y].prop);                            // (blocks past this neighbour's n1 leave in the body)
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void tri_resolve_batch_kernel(const TriBatchItem* __restrict__ items) {
+  const TriBatchItem it = items[blockIdx.x];
+  tri_resolve_body<kLds>(it.A, it.prop, it.owner, it.pairs, it.n_out);
 }
 
 // ---- fuse search (src/local_mapping/search_in_neighbors.rs:273-343, src/atlas/map/keyframe.rs:408-443) ---------
@@ -1069,6 +1097,39 @@ int launch_guided_match(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t
   return ORBX_OK;
 }
 
+bool tri_grid_dims(const orbx_camera* cam, int* cols, int* rows) {
+  auto f64_as_u32 = [](double v) -> unsigned { return v > 0 ? (v >= 4294967295.0 ? 4294967295u : (unsigned)v) : 0u; };
+  const unsigned iw = f64_as_u32(cam->cx * 2.0), ih = f64_as_u32(cam->cy * 2.0);               // triangulation.rs:434-435
+  const float fc = std::ceil((float)iw / 32.0f), fr = std::ceil((float)ih / 32.0f);
+  *cols = (int)std::min(64.0f, std::max(fc, 0.0f)); *rows = (int)std::min(64.0f, std::max(fr, 0.0f));   // :437-438
+  return *cols >= 1 && *rows >= 1;
+}
+
+int launch_search_for_triangulation_batch(orbx_handle* h, const TriBatchItem* d_items, int T, int max_n1, int max_n2) {
+  if (T <= 0) return ORBX_OK;
+  {
+    ProfScope ps(h, "tri_grid_build_batch_kernel");
+    hipLaunchKernelGGL(tri_grid_build_batch_kernel, dim3(T), dim3(1024), 0, h->stream, d_items);
+  }
+  if (max_n1 > 0) {
+    ProfScope ps(h, "tri_propose_batch_kernel");
+    hipLaunchKernelGGL(tri_propose_batch_kernel, dim3((max_n1 + 3) / 4, T), dim3(256), 0, h->stream, d_items);
+  }
+  {
+    ProfScope ps(h, "tri_resolve_batch_kernel");
+    const size_t lds = 5 * (size_t)std::max(max_n2, 0) + 16;                // sized by the largest neighbour of the call
+    if (lds <= 150 * 1024) {
+      if (lds > 64 * 1024)
+        ORBX_HIP(h, hipFuncSetAttribute((const void*)tri_resolve_batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      hipLaunchKernelGGL(tri_resolve_batch_kernel<true>, dim3(T), dim3(256), lds, h->stream, d_items);
+    } else {
+      hipLaunchKernelGGL(tri_resolve_batch_kernel<false>, dim3(T), dim3(256), 0, h->stream, d_items);
+    }
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
 int launch_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const double* F9, const double* epipole,
                                     const orbx_keypoint* d_kp1, const uint8_t* d_desc1, const uint8_t* d_mp1,
                                     const uint8_t* d_stereo1, int n1, const orbx_keypoint* d_kp2, const uint8_t* d_desc2,
@@ -1077,11 +1138,8 @@ int launch_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, cons
     ORBX_HIP(h, hipMemsetAsync(d_n_out, 0, sizeof(int), h->stream));
     return ORBX_OK;
   }
-  auto f64_as_u32 = [](double v) -> unsigned { return v > 0 ? (v >= 4294967295.0 ? 4294967295u : (unsigned)v) : 0u; };
-  const unsigned iw = f64_as_u32(cam->cx * 2.0), ih = f64_as_u32(cam->cy * 2.0);               // triangulation.rs:434-435
-  const float fc = std::ceil((float)iw / 32.0f), fr = std::ceil((float)ih / 32.0f);
-  const int cols = (int)std::min(64.0f, std::max(fc, 0.0f)), rows = (int)std::min(64.0f, std::max(fr, 0.0f));   // :437-438
-  if (cols < 1 || rows < 1) {
+  int cols, rows;
+  if (!tri_grid_dims(cam, &cols, &rows)) {
     ORBX_HIP(h, hipMemsetAsync(d_n_out, 0, sizeof(int), h->stream));
     return ORBX_OK;
   }

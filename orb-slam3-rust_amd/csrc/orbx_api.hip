@@ -459,6 +459,10 @@ void triangulation_geometry(const orbx_camera& cam, const double* p1, const doub
 }
 }  // namespace
 
+extern "C++" void orbx_triangulation_geometry(const orbx_camera* cam, const double* pose1_wc, const double* pose2_wc, double* ep2, double* F9) {
+  triangulation_geometry(*cam, pose1_wc, pose2_wc, ep2, F9);
+}
+
 int orbx_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const orbx_keypoint* kp1, const uint8_t* desc1,
                                   const uint8_t* mp1, const uint8_t* stereo1, int n1, const orbx_keypoint* kp2,
                                   const uint8_t* desc2, const uint8_t* mp2, int n2, const double* pose1_wc,

@@ -273,6 +273,59 @@ int launch_search_for_triangulation_bow(orbx_handle* h, const double* F9, const 
                                         const orbx_keypoint* d_kp2, const uint8_t* d_desc2, const uint8_t* d_mp2, int n2,
                                         const int* d_sorted_idx, const int* d_rng_lo, const int* d_rng_hi, unsigned max_dist,
                                         int* d_pairs, int* d_n_out);
+struct TriArgs {
+  double F[9];                 // fundamental matrix, row-major (host, triangulation.rs:670-683)
+  double epx, epy;             // epipole of camera 1 in image 2 (:418-426)
+  int cols, rows;              // 32-px grid over image 2 (:339-346, :437-438)
+  unsigned max_dist;
+  int n1, n2;
+  const orbx_keypoint* kp1; const uint8_t* desc1; const uint8_t* mp1; const uint8_t* stereo1;
+  const orbx_keypoint* kp2; const uint8_t* desc2;
+  const int* cell_start; const int* sorted_idx; const unsigned short* cell_of;
+  uint8_t* taken;              // per feature of keyframe 2: has a map point (mp2) or has been matched
+  // FeatureVector mode (search_for_triangulation_bow, :541-658): candidates of feature i1 are sorted_idx[rng_lo[i1] ..
+  // rng_hi[i1]) = the features of keyframe 2 in the same vocabulary node, ascending; no grid (cell_of == nullptr)
+  const int* rng_lo; const int* rng_hi;
+};
+// One neighbour of the batched search (launch_search_for_triangulation_batch): the single search's arguments plus the workspace slices
+// the three kernels use.  Only neighbours that are searched are listed (n1 > 0, n2 > 0): the caller leaves the skipped ones out.
+struct TriBatchItem {
+  TriArgs A;
+  const uint8_t* mp2;          // the neighbour's map-point flags (copied into A.taken by the build step)
+  int* prop; int* owner; int* pairs; int* n_out;
+};
+// grid side of image 2 (triangulation.rs:434-438); false when the image is empty
+bool tri_grid_dims(const orbx_camera* cam, int* cols, int* rows);
+// epipole of camera 1 in image 2 and the fundamental matrix (orbx_api.hip; triangulation.rs:418-431, :661-683)
+void orbx_triangulation_geometry(const orbx_camera* cam, const double* pose1_wc, const double* pose2_wc, double* ep2, double* F9);
+// d_items [T] in device memory (already uploaded on the handle's stream), every one with n1 > 0 and n2 > 0; max_n1 / max_n2 over them
+int launch_search_for_triangulation_batch(orbx_handle* h, const TriBatchItem* d_items, int T, int max_n1, int max_n2);
+
+// ---- pair triangulation (triangulate_kernels.hip; triangulation.rs:186-277, :715-850) ----
+// what all pairs of a call share: camera, gates, keyframe 1
+struct TriCommon {
+  orbx_camera cam;
+  double min_parallax_cos, reproj_mono, reproj_stereo, scale_factor;
+  double pow12[32];            // 1.2^octave from the host's pow, so that the scale gate compares the host's bits
+  const orbx_keypoint* kp1; const double* pts1; const uint8_t* has1; int n1;
+  double pose1[7];
+};
+// keyframe 2 and the pairs to evaluate; results go to slots [out_base, out_base + n_pairs) of the status / point arrays
+struct TriNeighbour {
+  const orbx_keypoint* kp2; const double* pts2; const uint8_t* has2; int n2;
+  double pose2[7];
+  const int* pairs;            // [n][2] (idx1, idx2)
+  const int* n_pairs_dev;      // the count where a search left it on the device, else NULL and n_pairs holds it
+  int n_pairs, out_base;
+};
+void tri_common_fill(TriCommon* c, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial);
+// `one` by value (d_many = NULL, T = 1) or T neighbours in device memory; max_pairs bounds every neighbour's pair count
+int launch_triangulate_pairs(orbx_handle* h, const TriCommon& c, const TriNeighbour& one, const TriNeighbour* d_many, int T, int max_pairs,
+                             uint16_t* d_status, double* d_points);
+// ordered compaction of the CREATED pairs (neighbour, then pair order) and the per-neighbour counters:
+// d_head [1 + 4T] = n_created | per neighbour (unused, matches_found, triangulated, validated); lists of `cap` entries
+int launch_triangulate_compact(orbx_handle* h, const TriNeighbour* d_many, int T, const uint16_t* d_status, const double* d_points, int cap,
+                               int* d_head, int* d_out_nb, int* d_out_idx1, int* d_out_idx2, double* d_out_points);
 int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_positions, const uint8_t* d_mp_desc, int P,
                        const double* d_kf_pose_cw, const int* d_kf_off, const orbx_keypoint* d_kps, const uint8_t* d_descs,
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist);
