@@ -719,6 +719,82 @@ int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, cons
                                     double* d_poses_out, double* d_velocities_out, double* d_biases_out, uint8_t* d_inlier_out,
                                     orbx_pose_inertial_result* d_results);
 
+/* ---- frame tracking against map points (src/tracking/tracker.rs) ---------------------------------------------------
+ * One call = the numeric part of track_local_map (tracker.rs:863-988, mode 1) or track_with_motion_model (:1086-1192, mode 0) for
+ * n_frames frames at once, with no host synchronisation inside: project each frame's map points with that frame's search pose,
+ * search the frame's FeatureGrid (orbx_guided_match's search, casts and tie rule included), gather the matches in map-point order
+ * into PnP's layout, run orbx_pnp_ransac_batch_device on them with the per-frame prior, and write the tracker's per-feature result.
+ * For every map point of a frame's list, in list order:
+ *   p_cam = pose.inverse().transform_point(position) — the inverse with se3.rs:56-63's operation order, then nalgebra's
+ *   quaternion-vector product plus the translation, one IEEE operation at a time; skipped if p_cam.z <= 0;
+ *   u = fx * x / z + cx, v = fy * y / z + cy (camera: the one given to the call);
+ *   mode 0: skipped if u < 0 || u >= 2cx || v < 0 || v >= 2cy; accepted: the smallest distance < 100;
+ *   mode 1: no bounds test; accepted: best <= 100 and, with more than one candidate, !(best as f32 > 0.75 * second as f32).
+ * Accepted points become correspondences in ascending list order: pts3d = the position, pts2d = the matched keypoint's (x, y),
+ * mp_idx = the point's index in the frame's list, feat_idx = the keypoint's index in the frame.  Frame b owns
+ * [offsets[b], offsets[b+1]) of them, packed from 0 — the layout of orbx_pnp_ransac_batch_device, whose outputs (pose, inlier mask,
+ * errors, records) this call hands through.  Two map points may match one feature; both are kept.  Then
+ *   matched[feat] = mp_idx of the inlier correspondence on that feature (the later correspondence where two share it), else -1.
+ * Per-frame status, first condition that holds:
+ *   TOO_FEW_CORRESPONDENCES  n_correspondences < min_correspondences: pose = the prior's bytes, matched all -1, n_inliers 0;
+ *   TOO_FEW_INLIERS          n_inliers < min_inliers: pose = the prior's bytes;
+ *   NO_MODEL                 PnP's ORBX_PNP_NO_MODEL (pose = the prior, mask and errors under it, as PnP reports them);
+ *   OK.
+ * The tracker's state machine, the choice of local map points and refine_with_imu's guard stay with the caller. */
+enum {
+  ORBX_TRACK_OK = 0,
+  ORBX_TRACK_NO_MODEL = 1,
+  ORBX_TRACK_TOO_FEW_CORRESPONDENCES = 2,
+  ORBX_TRACK_TOO_FEW_INLIERS = 3
+};
+/* orbx_default_track_config(mode): radius 15.0 (tracker.rs:881, :1091), the grid's image 752 x 480, and the reference's guards:
+ * mode 1: min_correspondences 4, min_inliers 0 (:937); mode 0: 10 and 10 (:1173, :1186).  Accepted: mode 0 or 1, radius >= 0 and
+ * finite, img_w / img_h > 0 and finite, min_correspondences >= 4 (PnP's own minimum), min_inliers >= 0; else ORBX_ERR_INVALID.
+ * Both configurations (this one and orbx_pnp_config) are checked before anything is enqueued. */
+typedef struct {
+  int mode;
+  double radius, img_w, img_h;
+  int min_correspondences, min_inliers;
+} orbx_track_config;
+/* n_in_front: map points with p_cam.z > 0; n_correspondences: accepted matches; n_inliers: PnP's final mask. */
+typedef struct {
+  int status, n_in_front, n_correspondences, n_inliers;
+} orbx_track_result;
+void orbx_default_track_config(int mode, orbx_track_config* cfg);
+
+/* Every array in device memory (the caller's), asynchronous on the handle's stream; mp_offsets alone is a host array.
+ *   features: frame b's keypoints / descriptors are d_kp / d_desc [d_feat_start[b] .. + n_b), n_b = d_feat_count[b *
+ *     feat_count_stride] — start and count are read on the device, by kernels on the handle's stream, so the extractor's slots
+ *     and its device-side counts serve as they are, ordered behind the extraction with no copy and no host round trip (the left
+ *     images of orbx_process_stereo_batch_device: d_feat_start[b] = 2 b cap_kp, d_feat_count = d_nkp, feat_count_stride = 2; the
+ *     right images: d_nkp + 1).  feat_count_stride >= 1, in ints.  max_feat: a host-known bound on a frame's count; a frame whose
+ *     count is negative or above it is searched as if it had no features (TOO_FEW_CORRESPONDENCES, zero correspondences) instead
+ *     of being read past the bound;
+ *   map points: d_positions [M][3] f64, d_mp_desc [M][32]; frame b's list is [mp_offsets[b], mp_offsets[b+1]), ascending from 0,
+ *     M = mp_offsets[n_frames]; the array is copied before the call returns (the caller may change or free it at once);
+ *   d_search_poses_wc / d_priors_wc [n_frames][7] T_wc: the pose the points are projected with and PnP's prior (mode 1: self.pose
+ *     and imu_prior; mode 0: the predicted pose twice — the same pointer may be given);
+ *   outputs: d_offsets [n_frames+1]; d_pts3d [M][3], d_pts2d [M][2], d_mp_idx / d_feat_idx [M], d_inlier_out [M], d_err_out [M]
+ *     (entries [0, d_offsets[n_frames]) are written); d_poses_wc_out [n_frames][7]; d_pnp_results [n_frames];
+ *     d_matched [n_frames][max_feat] (all of it is written); d_results [n_frames].
+ * d_offsets / d_pts3d / d_pts2d / d_poses_wc_out can be passed straight into orbx_pose_inertial_batch_device. */
+int orbx_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                             int n_frames, const orbx_keypoint* d_kp, const uint8_t* d_desc, const int* d_feat_start,
+                             const int* d_feat_count, int feat_count_stride, int max_feat, const double* d_positions,
+                             const uint8_t* d_mp_desc,
+                             const int* mp_offsets, const double* d_search_poses_wc, const double* d_priors_wc, int* d_offsets,
+                             double* d_pts3d, float* d_pts2d, int* d_mp_idx, int* d_feat_idx, double* d_poses_wc_out,
+                             uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_pnp_results, int* d_matched,
+                             orbx_track_result* d_results);
+/* The same in host memory, synchronous, one upload and one download.  Frame b's features are kp / desc
+ * [feat_offsets[b], feat_offsets[b+1]) (ascending from 0); matched is packed the same way ([feat_offsets[n_frames]]); the
+ * other arrays as above.  Each frame's result equals the device form's, byte for byte. */
+int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                      int n_frames, const orbx_keypoint* kp, const uint8_t* desc, const int* feat_offsets, const double* positions,
+                      const uint8_t* mp_desc, const int* mp_offsets, const double* search_poses_wc, const double* priors_wc,
+                      int* offsets, double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out,
+                      uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched, orbx_track_result* results);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

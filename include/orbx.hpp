@@ -595,6 +595,110 @@ inline PnPResult solve_pnp_ransac_detailed(Handle& h, const std::vector<std::arr
   return r;
 }
 
+// ---- the tracker's per-frame step (orbx_track_frames, orbx.h): project the map points, search the frame's grid, gather, PnP ----
+// One frame's input: its features, the map points to look for (positions and descriptors in list order), the pose they are
+// projected with and PnP's prior (both T_wc).
+struct TrackFrame {
+  const FeatureSet* features = nullptr;
+  std::vector<std::array<double, 3>> positions;
+  std::vector<uint8_t> mp_descriptors;            // positions.size() rows of 32 bytes
+  SE3 search_pose, prior;
+};
+
+// The tuple track_local_map returns (tracker.rs:981-988) with the arrays behind it.  matched_map_points[feature] = the index of
+// the map point in the frame's list (the caller's list holds the ids).  In mode 0 (track_with_motion_model, which returns
+// Option<SE3>) the pose is Some exactly when status == ORBX_TRACK_OK or ORBX_TRACK_NO_MODEL.
+struct TrackResult {
+  SE3 pose;
+  size_t n_inliers = 0;                                         // n_correspondences where there were too few (:937-946)
+  std::vector<std::optional<size_t>> matched_map_points;        // per feature
+  std::vector<double> reproj_errors_full;                       // per correspondence
+  std::vector<size_t> inlier_indices, outlier_indices;          // into the correspondences
+  std::vector<std::array<double, 3>> points3d;                  // the correspondences, ascending map-point order
+  std::vector<std::array<float, 2>> points2d;
+  std::vector<int> mp_idx, feat_idx;
+  orbx_track_result record{};
+  orbx_pnp_result pnp{};
+};
+
+// The batch form: one upload, one download.  mode 1 = track_local_map, mode 0 = track_with_motion_model; cfg == nullptr takes
+// orbx_default_track_config(mode).
+inline std::vector<TrackResult> track_frames(Handle& h, const CameraModel& camera, const std::vector<TrackFrame>& frames, int mode,
+                                             const orbx_track_config* cfg = nullptr) {
+  const int B = (int)frames.size();
+  orbx_track_config tc;
+  orbx_default_track_config(mode, &tc);
+  if (cfg) tc = *cfg;
+  orbx_pnp_config pc;
+  orbx_default_pnp_config(&pc);
+  std::vector<int> fo(B + 1, 0), mo(B + 1, 0);
+  std::vector<KeyPoint> kp;
+  std::vector<uint8_t> desc, md;
+  std::vector<double> pos, sp, pr;
+  auto push7 = [](std::vector<double>& v, const SE3& p) {
+    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
+    v.insert(v.end(), p.translation.begin(), p.translation.end());
+  };
+  for (int b = 0; b < B; ++b) {
+    const TrackFrame& f = frames[b];
+    if (!f.features || f.features->descriptors.size() != 32 * f.features->keypoints.size() || f.mp_descriptors.size() != 32 * f.positions.size())
+      throw std::invalid_argument("track_frames: a frame's descriptors do not match its keypoints / map points");
+    kp.insert(kp.end(), f.features->keypoints.begin(), f.features->keypoints.end());
+    desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
+    for (const auto& p : f.positions) pos.insert(pos.end(), p.begin(), p.end());
+    md.insert(md.end(), f.mp_descriptors.begin(), f.mp_descriptors.end());
+    push7(sp, f.search_pose); push7(pr, f.prior);
+    fo[b + 1] = (int)kp.size(); mo[b + 1] = (int)(pos.size() / 3);
+  }
+  const size_t NF = kp.size(), M = pos.size() / 3, Bz = (size_t)std::max(B, 1);
+  std::vector<int> off(B + 1, 0), mi(std::max<size_t>(M, 1)), fi(std::max<size_t>(M, 1)), matched(std::max<size_t>(NF, 1));
+  std::vector<double> p3(3 * std::max<size_t>(M, 1)), poses(7 * Bz), err(std::max<size_t>(M, 1));
+  std::vector<float> p2(2 * std::max<size_t>(M, 1));
+  std::vector<uint8_t> inl(std::max<size_t>(M, 1));
+  std::vector<orbx_pnp_result> pres(Bz);
+  std::vector<orbx_track_result> res(Bz);
+  const orbx_camera cam = camera.c();
+  h.check(orbx_track_frames(h.get(), &cam, &tc, &pc, B, kp.data(), desc.data(), fo.data(), pos.data(), md.data(), mo.data(), sp.data(), pr.data(),
+                            off.data(), p3.data(), p2.data(), mi.data(), fi.data(), poses.data(), inl.data(), err.data(), pres.data(),
+                            matched.data(), res.data()));
+  std::vector<TrackResult> out(B);
+  for (int b = 0; b < B; ++b) {
+    TrackResult& r = out[b];
+    const double* o7 = &poses[7 * (size_t)b];
+    r.pose.rotation = {o7[0], o7[1], o7[2], o7[3]};
+    r.pose.translation = {o7[4], o7[5], o7[6]};
+    r.record = res[b]; r.pnp = pres[b];
+    const bool too_few = res[b].status == ORBX_TRACK_TOO_FEW_CORRESPONDENCES;
+    r.n_inliers = too_few ? (size_t)res[b].n_correspondences : (size_t)res[b].n_inliers;
+    for (int f = fo[b]; f < fo[b + 1]; ++f)
+      r.matched_map_points.push_back(matched[f] >= 0 ? std::optional<size_t>((size_t)matched[f]) : std::nullopt);
+    for (int i = off[b]; i < off[b + 1]; ++i) {
+      r.points3d.push_back({p3[3 * (size_t)i], p3[3 * (size_t)i + 1], p3[3 * (size_t)i + 2]});
+      r.points2d.push_back({p2[2 * (size_t)i], p2[2 * (size_t)i + 1]});
+      r.mp_idx.push_back(mi[i]); r.feat_idx.push_back(fi[i]);
+      if (too_few) continue;                                    // :937-946: the three vectors stay empty
+      r.reproj_errors_full.push_back(err[i]);
+      (inl[i] ? r.inlier_indices : r.outlier_indices).push_back((size_t)(i - off[b]));
+    }
+  }
+  return out;
+}
+
+// tracker.rs:863-988 on one frame: (pose, n_inliers, matched_map_points, reproj_errors_full, inlier_indices, outlier_indices).
+inline TrackResult track_local_map(Handle& h, const CameraModel& camera, const FeatureSet& features,
+                                   const std::vector<std::array<double, 3>>& positions, const std::vector<uint8_t>& mp_descriptors,
+                                   const SE3& pose, const SE3& imu_prior) {
+  return track_frames(h, camera, {TrackFrame{&features, positions, mp_descriptors, pose, imu_prior}}, 1)[0];
+}
+
+// tracker.rs:1086-1192 on one frame; the reference's Option<SE3> is Some(result.pose) when result.record.status is ORBX_TRACK_OK
+// or ORBX_TRACK_NO_MODEL (fewer than 10 correspondences or inliers: None).
+inline TrackResult track_with_motion_model(Handle& h, const CameraModel& camera, const FeatureSet& features,
+                                           const std::vector<std::array<double, 3>>& positions, const std::vector<uint8_t>& mp_descriptors,
+                                           const SE3& predicted_pose) {
+  return track_frames(h, camera, {TrackFrame{&features, positions, mp_descriptors, predicted_pose, predicted_pose}}, 0)[0];
+}
+
 // global_ba.rs:184-418.  The id -> index re-keying is the reference's own (:198-229).  Observations of a map point
 // that is not in mp_ids are rejected (collect_global_ba_data never emits one, :160).
 inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAProblemData& problem, const CameraModel& camera,

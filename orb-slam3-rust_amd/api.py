@@ -91,6 +91,7 @@ ABI_SYMBOLS = [
     "orbx_kfdb_detect_loop_candidates", "orbx_kfdb_detect_loop_candidates_batch",
     "orbx_default_triangulation_config", "orbx_triangulate_pairs", "orbx_triangulate_pairs_device", "orbx_keyframe_set_feature_nodes",
     "orbx_keyframe_triangulate_from_neighbors",
+    "orbx_default_track_config", "orbx_track_frames", "orbx_track_frames_device",
 ]
 
 
@@ -176,6 +177,18 @@ class _PoseInertialResult(C.Structure):
 # orbx_pose_inertial_result as a numpy record (the batch forms' results array)
 POSE_INERTIAL_RESULT = np.dtype([("status", "<i4"), ("num_inliers", "<i4"), ("num_observations", "<i4"), ("iterations", "<i4")])
 POSE_INERTIAL_OK, POSE_INERTIAL_TOO_FEW, POSE_INERTIAL_SINGULAR = 0, 1, 2
+
+
+class _TrackConfig(C.Structure):
+    """orbx_track_config (include/orbx.h)"""
+    _fields_ = [("mode", C.c_int), ("radius", C.c_double), ("img_w", C.c_double), ("img_h", C.c_double), ("min_correspondences", C.c_int),
+                ("min_inliers", C.c_int)]
+
+
+# orbx_track_result as a numpy record (the results array of track_frames[_device])
+TRACK_RESULT = np.dtype([("status", "<i4"), ("n_in_front", "<i4"), ("n_correspondences", "<i4"), ("n_inliers", "<i4")])
+TRACK_OK, TRACK_NO_MODEL, TRACK_TOO_FEW_CORRESPONDENCES, TRACK_TOO_FEW_INLIERS = 0, 1, 2, 3
+TRACK_MOTION_MODEL, TRACK_LOCAL_MAP = 0, 1      # orbx_track_config.mode
 
 
 class _LoopDetectorConfig(C.Structure):
@@ -367,6 +380,54 @@ class PnPResult:
 
 def _pnp_stats(rec):
     return {k: (float(rec[k]) if k == "final_rms" else int(rec[k])) for k in PNP_RESULT.names}
+
+
+@dataclass
+class TrackConfig:
+    """orbx_track_config (include/orbx.h).  TrackConfig.for_mode(mode) = orbx_default_track_config: radius 15 px, the grid's image
+    752 x 480 and the reference's guards — track_local_map (mode 1, tracker.rs:937) 4 correspondences, no inlier guard;
+    track_with_motion_model (mode 0, :1173, :1186) 10 and 10."""
+    mode: int = TRACK_LOCAL_MAP
+    radius: float = 15.0
+    img_w: float = 752.0
+    img_h: float = 480.0
+    min_correspondences: int = 4
+    min_inliers: int = 0
+
+    @classmethod
+    def for_mode(cls, mode, **kw):
+        return cls(mode=mode, min_correspondences=10 if mode == TRACK_MOTION_MODEL else 4, min_inliers=10 if mode == TRACK_MOTION_MODEL else 0, **kw)
+
+    def _c(self):
+        return _TrackConfig(self.mode, self.radius, self.img_w, self.img_h, self.min_correspondences, self.min_inliers)
+
+
+@dataclass
+class TrackFrameResult:
+    """One frame of Handle.track_frames — the tuple track_local_map returns (tracker.rs:981-988) and the arrays behind it:
+    pose (T_wc), n_inliers, matched [n_features] int32 (the index of the map point in the frame's list, -1 = None), reproj_errors
+    [n_corr] f64, inlier_mask [n_corr] bool; the correspondences points3d [n_corr,3] f64, points2d [n_corr,2] f32, mp_idx / feat_idx
+    [n_corr] int32 in ascending map-point order; status (TRACK_*), n_in_front, and PnP's record as a dict."""
+    pose: np.ndarray
+    n_inliers: int
+    matched: np.ndarray
+    reproj_errors: np.ndarray
+    inlier_mask: np.ndarray
+    points3d: np.ndarray
+    points2d: np.ndarray
+    mp_idx: np.ndarray
+    feat_idx: np.ndarray
+    status: int = 0
+    n_in_front: int = 0
+    pnp_stats: Dict[str, float] = field(default_factory=dict)
+
+    @property
+    def inlier_indices(self):
+        return np.flatnonzero(self.inlier_mask)
+
+    @property
+    def outlier_indices(self):
+        return np.flatnonzero(~self.inlier_mask)
 
 
 @dataclass
@@ -627,6 +688,92 @@ class Handle:
                                                          _vp(points3d), _vp(points2d), _vp(priors_wc), _vp(poses), _vp(inl), _vp(err),
                                                          _vp(res)))
         return poses[:P], inl[:N], err[:N], res[:P]
+
+    def track_frames(self, camera, frames, cfg: "TrackConfig" = None, pnp_cfg: PnPConfig = None) -> List["TrackFrameResult"]:
+        """The tracker's per-frame step (tracker.rs:863-988 mode 1, :1086-1192 mode 0) for many frames in one call, host arrays, one
+        upload and one download.  frames: [(kp, desc, positions, mp_desc, search_pose_wc, prior_wc), ...] — the frame's keypoints
+        (KEYPOINT) and descriptors [n,32], its map points' positions [m,3] f64 and descriptors [m,32], the pose the points are
+        projected with and PnP's prior (both T_wc; mode 0 passes the predicted pose twice)."""
+        B = len(frames)
+        kps = [np.ascontiguousarray(f[0], KEYPOINT).reshape(-1) for f in frames]
+        des = [np.ascontiguousarray(f[1], np.uint8).reshape(-1, 32) for f in frames]
+        pos = [np.ascontiguousarray(f[2], np.float64).reshape(-1, 3) for f in frames]
+        mds = [np.ascontiguousarray(f[3], np.uint8).reshape(-1, 32) for f in frames]
+        if any(len(a) != len(b) for a, b in zip(kps, des)) or any(len(a) != len(b) for a, b in zip(pos, mds)):
+            raise ValueError("keypoints / descriptors or positions / map-point descriptors differ in length")
+        fo = np.zeros(B + 1, np.int32); fo[1:] = np.cumsum([len(a) for a in kps])
+        mo = np.zeros(B + 1, np.int32); mo[1:] = np.cumsum([len(a) for a in pos])
+        NF, M = int(fo[-1]), int(mo[-1])
+        kp = np.concatenate(kps) if NF else np.zeros(1, KEYPOINT)
+        de = np.concatenate(des) if NF else np.zeros((1, 32), np.uint8)
+        po = np.concatenate(pos) if M else np.zeros((1, 3), np.float64)
+        md = np.concatenate(mds) if M else np.zeros((1, 32), np.uint8)
+        sp = np.ascontiguousarray(np.stack([np.asarray(f[4], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        pr = np.ascontiguousarray(np.stack([np.asarray(f[5], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        off = np.zeros(B + 1, np.int32)
+        p3 = np.zeros((max(M, 1), 3)); p2 = np.zeros((max(M, 1), 2), np.float32)
+        mi = np.zeros(max(M, 1), np.int32); fi = np.zeros(max(M, 1), np.int32)
+        poses = np.zeros((max(B, 1), 7)); inl = np.zeros(max(M, 1), np.uint8); err = np.zeros(max(M, 1))
+        pres = np.zeros(max(B, 1), PNP_RESULT); matched = np.zeros(max(NF, 1), np.int32); res = np.zeros(max(B, 1), TRACK_RESULT)
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_track_frames(self._h, C.byref(cam), C.byref(c), C.byref(pc), C.c_int(B), _vp(kp), _vp(de), _vp(fo), _vp(po),
+                                              _vp(md), _vp(mo), _vp(sp), _vp(pr), _vp(off), _vp(p3), _vp(p2), _vp(mi), _vp(fi), _vp(poses),
+                                              _vp(inl), _vp(err), _vp(pres), _vp(matched), _vp(res)))
+        out = []
+        for b in range(B):
+            s = slice(int(off[b]), int(off[b + 1]))
+            out.append(TrackFrameResult(poses[b].copy(), int(res[b]["n_inliers"]), matched[fo[b]:fo[b + 1]].copy(), err[s].copy(),
+                                        inl[s].astype(bool), p3[s].copy(), p2[s].copy(), mi[s].copy(), fi[s].copy(), int(res[b]["status"]),
+                                        int(res[b]["n_in_front"]), _pnp_stats(pres[b])))
+        return out
+
+    def track_frames_device(self, camera, kp, desc, feat_start, feat_count, max_feat, positions, mp_desc, mp_offsets, search_poses_wc,
+                            priors_wc, cfg: "TrackConfig" = None, pnp_cfg: PnPConfig = None):
+        """Device-resident form: torch CUDA tensors kp [*,7] f32 and desc [*,32] u8 as the extractor writes them, feat_start /
+        feat_count [B] int32 (frame b's features are rows feat_start[b] .. + feat_count[b]; feat_count may be a strided 1-d view,
+        such as the column of the extractor's counts that track_feature_slots returns: the kernels read it where it lies, on the
+        handle's stream, behind the extraction), positions [M,3] f64, mp_desc [M,32] u8, search_poses_wc / priors_wc [B,7] f64; mp_offsets [B+1] is a
+        host array (ascending from 0); max_feat bounds a frame's count.  Returns a dict of tensors: offsets [B+1] int32, points3d
+        [M,3] f64, points2d [M,2] f32, mp_idx / feat_idx [M] int32, poses [B,7] f64, inlier [M] u8, err [M] f64, pnp_results [B,32] u8
+        (PNP_RESULT), matched [B,max_feat] int32, results [B,16] u8 (TRACK_RESULT).  offsets / points3d / points2d / poses feed
+        pose_inertial_optimization_batch_device unchanged.  Asynchronous on the handle's stream."""
+        import torch
+        mo = np.ascontiguousarray(mp_offsets, np.int32).reshape(-1)
+        B, M = len(mo) - 1, int(mo[-1]) if len(mo) else 0
+        dev = search_poses_wc.device
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(offsets=mk(max(B, 0) + 1, torch.int32), points3d=mk((max(M, 1), 3), torch.float64), points2d=mk((max(M, 1), 2), torch.float32),
+                 mp_idx=mk(max(M, 1), torch.int32), feat_idx=mk(max(M, 1), torch.int32), poses=mk((max(B, 1), 7), torch.float64),
+                 inlier=mk(max(M, 1), torch.uint8), err=mk(max(M, 1), torch.float64), pnp_results=mk((max(B, 1), PNP_RESULT.itemsize), torch.uint8),
+                 matched=mk((max(B, 1), max(int(max_feat), 1)), torch.int32), results=mk((max(B, 1), TRACK_RESULT.itemsize), torch.uint8))
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        if feat_count.dim() != 1 or feat_count.dtype != torch.int32 or (B > 1 and feat_count.stride(0) < 1):
+            raise ValueError("feat_count must be a 1-d int32 tensor or view with a positive stride")
+        fc_stride = int(feat_count.stride(0)) if B > 1 else 1
+        ins = (kp, desc, feat_start, feat_count, positions, mp_desc, search_poses_wc, priors_wc)
+        self._after_torch(*ins, *o.values())
+        self._check(self._L.orbx_track_frames_device(
+            self._h, C.byref(cam), C.byref(c), C.byref(pc), C.c_int(B), _vp(kp), _vp(desc), _vp(feat_start), _vp(feat_count), C.c_int(fc_stride), C.c_int(int(max_feat)),
+            _vp(positions), _vp(mp_desc), _vp(mo), _vp(search_poses_wc), _vp(priors_wc), _vp(o["offsets"]), _vp(o["points3d"]), _vp(o["points2d"]),
+            _vp(o["mp_idx"]), _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]), _vp(o["err"]), _vp(o["pnp_results"]), _vp(o["matched"]),
+            _vp(o["results"])))
+        o["matched"] = o["matched"][:, :int(max_feat)]
+        for k in ("points3d", "points2d", "mp_idx", "feat_idx", "inlier", "err"):
+            o[k] = o[k][:M]
+        return o
+
+    @staticmethod
+    def track_feature_slots(out, batch=None, side=0):
+        """feat_start / feat_count for track_frames_device from an alloc_batch_outputs() dict: frame b is the left (side 0) or right
+        (side 1) image of pair b; its slot starts at row (2 b + side) * cap_kp of out['kp'].view(-1, 7) / out['desc'].view(-1, 32).
+        feat_count is out['nkp'][:batch, side] itself — a strided view of the extractor's device-side counts, not a copy: nothing
+        is read here, so it may be taken before or after process_stereo_batch_device is enqueued, and track_frames_device's kernels
+        read the counts on the handle's stream behind the extraction.  feat_start does not depend on the frame and can be kept.
+        max_feat = out['cap_kp']."""
+        import torch
+        b = batch or out["batch"]
+        start = (torch.arange(b, dtype=torch.int32, device=out["nkp"].device) * 2 + side) * out["cap_kp"]
+        return start, out["nkp"][:b, side]
 
     def pose_inertial_optimization(self, camera, pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d, points2d,
                                    is_stereo, cfg: PoseInertialConfig = None) -> PoseInertialResult:

@@ -16,33 +16,17 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "guided_search_dev.hpp"
 #include "orbx_internal.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int SM_THREADS = 256;
 #ifndef ORBX_SM_LPW
 #define ORBX_SM_LPW 8
 #endif
 constexpr int SM_LEFT_PER_WAVE = ORBX_SM_LPW;   // multiple of 4: four left keypoints share a wave
 constexpr int SM_LEFT_PER_BLOCK = SM_LEFT_PER_WAVE * (SM_THREADS / kWave);
-constexpr unsigned TH_HIGH = 100;  // stereo.rs:10
-
-struct Desc256 {
-  unsigned long long w[4];
-};
-
-__device__ __forceinline__ Desc256 load_desc(const uint8_t* p) {
-  const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
-  Desc256 d;
-  d.w[0] = q[0]; d.w[1] = q[1]; d.w[2] = q[2]; d.w[3] = q[3];
-  return d;
-}
-__device__ __forceinline__ unsigned hamming(const Desc256& a, const Desc256& b) {
-  return (unsigned)(__popcll(a.w[0] ^ b.w[0]) + __popcll(a.w[1] ^ b.w[1]) +
-                    __popcll(a.w[2] ^ b.w[2]) + __popcll(a.w[3] ^ b.w[3]));
-}
 
 // merge two (best, best_idx, second) triples: two smallest of the union, lowest index on ties
 __device__ __forceinline__ void merge_top2(unsigned& b, int& bi, unsigned& s, unsigned ob, int obi,
@@ -543,60 +527,14 @@ __global__ __launch_bounds__(256) void crosscheck_compact_kernel(const int* __re
   if (tid == 0) *n_out = running;
 }
 
-// ---- guided matching: FeatureGrid (tracking_frame.rs:52-128) + the tracker's two search rules -----------------
-constexpr int GG_COLS = 64, GG_ROWS = 48, GG_CELLS = GG_COLS * GG_ROWS;   // tracking_frame.rs:43-44
-
-// Rust `f64 as usize`: truncation, negative / NaN -> 0
-__device__ __forceinline__ int sat_cell(double v, int last) {
-  return (v > 0.0) ? (v >= (double)(last + 1) ? last : (int)v) : 0;
-}
-// Rust `f64 as i32`: saturating, NaN -> 0
-__device__ __forceinline__ int sat_i32(double v) {
-  if (v != v) return 0;
-  if (v <= -2147483648.0) return INT_MIN;
-  if (v >= 2147483647.0) return INT_MAX;
-  return (int)v;
+// ---- guided matching: the grid and the search are guided_search_dev.hpp's (shared with track_kernels.hip) -----------------
+__global__ __launch_bounds__(GG_THREADS) void grid_build_kernel(const orbx_keypoint* __restrict__ kp, int n, double winv, double hinv,
+                                                                int* __restrict__ cell_start, int* __restrict__ sorted_idx,
+                                                                unsigned short* __restrict__ cell_of) {
+  grid_build_body(kp, n, winv, hinv, cell_start, sorted_idx, cell_of);
 }
 
-// One block: counting sort of the keypoints by grid cell (CSR: cell_start[GG_CELLS+1], sorted_idx[n]) and the
-// cell of every keypoint.  The order inside a cell is irrelevant: ties are broken on (cell, index) explicitly.
-__global__ __launch_bounds__(1024) void grid_build_kernel(const orbx_keypoint* __restrict__ kp, int n, double winv, double hinv,
-                                                          int* __restrict__ cell_start, int* __restrict__ sorted_idx,
-                                                          unsigned short* __restrict__ cell_of) {
-  __shared__ int cnt[GG_CELLS];
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < GG_CELLS; i += 1024) cnt[i] = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += 1024) {
-    const int cx = sat_cell(((double)kp[i].x - 0.0) * winv, GG_COLS - 1);     // tracking_frame.rs:66-75
-    const int cy = sat_cell(((double)kp[i].y - 0.0) * hinv, GG_ROWS - 1);
-    const int c = cy * GG_COLS + cx;
-    cell_of[i] = (unsigned short)c;
-    atomicAdd(&cnt[c], 1);
-  }
-  __syncthreads();
-  int c3[3], tot = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { c3[k] = cnt[3 * tid + k]; tot += c3[k]; }
-  int inc = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = inc - tot;
-  for (int wv = 0; wv < wave; ++wv) base += wsum[wv];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { cell_start[3 * tid + k] = base; cnt[3 * tid + k] = base; base += c3[k]; }
-  if (tid == 1023) cell_start[GG_CELLS] = base;
-  __syncthreads();
-  for (int i = tid; i < n; i += 1024) sorted_idx[atomicAdd(&cnt[cell_of[i]], 1)] = i;
-}
-
-// One wave per query.  key = (distance << 48 | cell << 32 | index): the minimum key is the smallest distance,
-// and among equal distances the first candidate in the reference's visiting order (cells row-major, indices
-// ascending inside a cell).  `second` is the second smallest distance of the multiset.
+// One wave per query (guided_search_wave).
 __global__ __launch_bounds__(256) void guided_match_kernel(const uint8_t* __restrict__ desc, const int* __restrict__ cell_start,
                                                            const int* __restrict__ sorted_idx,
                                                            const unsigned short* __restrict__ cell_of,
@@ -607,49 +545,10 @@ __global__ __launch_bounds__(256) void guided_match_kernel(const uint8_t* __rest
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nq) return;
   const double x = q_uv[2 * (size_t)q], y = q_uv[2 * (size_t)q + 1];
-  // tracking_frame.rs:107-117, including `(max as usize).min(cols - 1)`: a negative max wraps -> last cell
-  const int mnx = sat_i32(floor((x - 0.0 - radius) * winv)), mxx = sat_i32(ceil((x - 0.0 + radius) * winv));
-  const int mny = sat_i32(floor((y - 0.0 - radius) * hinv)), mxy = sat_i32(ceil((y - 0.0 + radius) * hinv));
-  const int x0 = max(mnx, 0), y0 = max(mny, 0);
-  const int x1 = (mxx < 0 || mxx > GG_COLS - 1) ? GG_COLS - 1 : mxx;
-  const int y1 = (mxy < 0 || mxy > GG_ROWS - 1) ? GG_ROWS - 1 : mxy;
   const Desc256 dq = load_desc(q_desc + (size_t)q * 32);
-  unsigned long long bk = ~0ull;
-  unsigned s = 0xffffffffu;
-  int total = 0;
-  if (x0 <= x1) {
-    for (int cy = y0; cy <= y1; ++cy) {
-      const int lo = cell_start[cy * GG_COLS + x0], hi = cell_start[cy * GG_COLS + x1 + 1];
-      total += hi - lo;
-      for (int t = lo + lane; t < hi; t += kWave) {
-        const int i = sorted_idx[t];
-        const unsigned d = hamming(dq, load_desc(desc + (size_t)i * 32));
-        if (mode == 0 && d >= TH_HIGH) continue;                          // tracker.rs:1146
-        const unsigned long long key = ((unsigned long long)d << 48) | ((unsigned long long)cell_of[i] << 32) | (unsigned)i;
-        if (key < bk) { s = min(s, (unsigned)(bk >> 48)); if (bk == ~0ull) s = 0xffffffffu; bk = key; }
-        else s = min(s, d);
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned long long ok = __shfl_xor(bk, off);
-    const unsigned os = __shfl_xor(s, off);
-    const unsigned long long mn = ok < bk ? ok : bk, mx = ok < bk ? bk : ok;
-    unsigned ns = min(s, os);
-    if (mx != ~0ull) ns = min(ns, (unsigned)(mx >> 48));
-    bk = mn; s = ns;
-  }
+  unsigned rd;
+  const int res = guided_search_wave(desc, cell_start, sorted_idx, cell_of, x, y, dq, radius, winv, hinv, mode, lane, &rd);
   if (lane == 0) {
-    int res = -1;
-    unsigned rd = 0;
-    if (bk != ~0ull) {
-      const unsigned best = (unsigned)(bk >> 48);
-      const int bi = (int)(unsigned)(bk & 0xffffffffull);
-      if (mode == 0) { res = bi; rd = best; }
-      else if (total > 0 && best <= TH_HIGH &&                                        // tracker.rs:884-886, :907-909
-               !(total > 1 && (float)best > 0.75f * (float)s)) { res = bi; rd = best; }   // :911-915
-    }
     out_idx[q] = res;
     out_dist[q] = rd;
   }
@@ -1086,7 +985,7 @@ int launch_guided_match(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t
   const double winv = (double)GG_COLS / (img_w - 0.0), hinv = (double)GG_ROWS / (img_h - 0.0);   // tracking_frame.rs:58-59
   {
     ProfScope ps(h, "grid_build_kernel");
-    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, h->stream, d_kp, n, winv, hinv, cell_start, sorted_idx, cell_of);
+    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(GG_THREADS), 0, h->stream, d_kp, n, winv, hinv, cell_start, sorted_idx, cell_of);
   }
   {
     ProfScope ps(h, "guided_match_kernel");

@@ -207,6 +207,10 @@ struct orbx_handle {
   void* h_pnp = nullptr; size_t h_pnp_bytes = 0;   // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
   DevBuf ws_pi;                          // pose-inertial optimization: the host forms' input / output blob (pose_inertial_kernels.hip)
   void* h_pi = nullptr; size_t h_pi_bytes = 0;     // pinned staging of orbx_pose_inertial_batch
+  DevBuf ws_track[3];                    // frame tracking (track_kernels.hip): [0] grids, matches and counters, [1] the host form's input / output blobs, [2] mp_offsets of the device form
+  void* h_track = nullptr; size_t h_track_bytes = 0;   // pinned staging of orbx_track_frames
+  void* h_track_off[2] = {nullptr, nullptr}; size_t h_track_off_bytes[2] = {0, 0};   // pinned copies of orbx_track_frames_device's mp_offsets, used in turn
+  hipEvent_t ev_track_off[2] = {nullptr, nullptr}; int track_off_next = 0;           // ... and the event behind each slot's upload
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -329,6 +333,8 @@ int launch_triangulate_compact(orbx_handle* h, const TriNeighbour* d_many, int T
 int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_positions, const uint8_t* d_mp_desc, int P,
                        const double* d_kf_pose_cw, const int* d_kf_off, const orbx_keypoint* d_kps, const uint8_t* d_descs,
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist);
+// orbx_pnp_config's range check (pnp_kernels.hip), for callers that enqueue work ahead of PnP's own launches
+int orbx_pnp_check_config(orbx_handle* h, const orbx_pnp_config* c, const char* who);
 // extractor (orb_kernels.hip)
 int orb_prepare_geometry(orbx_handle* h, int w, int h_px);
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,

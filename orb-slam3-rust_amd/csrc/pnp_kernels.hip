@@ -526,6 +526,8 @@ size_t pnp_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
+int orbx_pnp_check_config(orbx_handle* h, const orbx_pnp_config* c, const char* who) { return pnp_check_config(h, c, who); }
+
 extern "C" {
 
 void orbx_default_pnp_config(orbx_pnp_config* c) {
