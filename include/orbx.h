@@ -207,7 +207,8 @@ int orbx_guided_match_device(orbx_handle* h, const orbx_keypoint* d_kp, const ui
  *   mp1 [n1] / mp2 [n2]: 1 = the feature already has a map point; stereo1 [n1]: 1 = points_cam is Some;
  *   pose1_wc / pose2_wc: 7 doubles (qw,qx,qy,qz,tx,ty,tz), camera-to-world as the Map stores them;
  *   out_pairs [n1][2] = (idx1, idx2) ascending idx1.  Host memory.  Uses the camera given here (image size is
- *   2cx x 2cy as in the reference, :434-435). */
+ *   2cx x 2cy as in the reference, :434-435).  A camera whose image has no 32-px cell (u32(2cx) or u32(2cy) == 0) is
+ *   refused with ORBX_ERR_INVALID, here and in the device-resident and keyframe forms. */
 int orbx_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const orbx_keypoint* kp1,
                                   const uint8_t* desc1, const uint8_t* mp1, const uint8_t* stereo1, int n1,
                                   const orbx_keypoint* kp2, const uint8_t* desc2, const uint8_t* mp2, int n2,

@@ -597,6 +597,7 @@ __device__ __forceinline__ void tri_grid_build_body(const orbx_keypoint* __restr
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 4; ++k) { if (4 * tid + k <= ncell) cell_start[4 * tid + k] = base; cnt[4 * tid + k] = base; base += c4[k]; }
+  if (tid == 1023 && ncell == 4096) cell_start[4096] = base;           // 64 x 64: the end sentinel lies past the last thread's four slots
   __syncthreads();
   for (int i = tid; i < n; i += 1024) sorted_idx[atomicAdd(&cnt[cell_of[i]], 1)] = i;
 }
@@ -1038,10 +1039,8 @@ int launch_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, cons
     return ORBX_OK;
   }
   int cols, rows;
-  if (!tri_grid_dims(cam, &cols, &rows)) {
-    ORBX_HIP(h, hipMemsetAsync(d_n_out, 0, sizeof(int), h->stream));
-    return ORBX_OK;
-  }
+  if (!tri_grid_dims(cam, &cols, &rows))                                  // u32(2cx) or u32(2cy) == 0: the reference's grid has no cell
+    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_search_for_triangulation: the camera's image (2cx x 2cy) has no grid cell");
   // workspace: cell_start int[4100] | sorted_idx int[n2] | prop int[n1] | owner int[n2] | cell_of u16[n2] | taken u8[n2]
   const size_t bytes = sizeof(int) * (4100 + 2 * (size_t)n2 + (size_t)n1) + 2 * (size_t)n2 + (size_t)n2 + 64;
   if (int rc = orbx_reserve(h, h->ws_match, bytes)) return rc;

@@ -58,18 +58,21 @@ def flip(rng, d, nbits):
     return np.packbits(bits)
 
 
-def frame(seed, n_mp, n_feat, noise_px=0.5, max_flip=20, behind=0, x_range=(20.0, 710.0), y_range=(20.0, 460.0)):
+def frame(seed, n_mp, n_feat, noise_px=0.5, max_flip=20, behind=0, x_range=(20.0, 710.0), y_range=(20.0, 460.0), camera=None, w=None, h=None):
     """min(n_mp - behind, n_feat) map points with a feature at their noisy projection, `behind` points behind the camera (placed
-    first in the list), the other features distractors anywhere in the image."""
+    first in the list), the other features distractors anywhere in the image.  camera / w / h: another camera and image size (the
+    defaults are EuRoC cam0 and 752 x 480; x_range / y_range then have to be given to suit)."""
     rng = np.random.default_rng(seed)
+    cam = CAMERA if camera is None else camera
+    w = W if w is None else float(w); h = H if h is None else float(h)
     T = pose(rng)
     n_vis = max(n_mp - behind, 0)
     uv = np.stack([rng.uniform(*x_range, n_vis), rng.uniform(*y_range, n_vis)], 1)
-    X = np.concatenate([backproject(T, np.stack([rng.uniform(100.0, 600.0, behind), rng.uniform(100.0, 400.0, behind)], 1), -rng.uniform(1.0, 5.0, behind)),
-                        backproject(T, uv, rng.uniform(2.0, 12.0, n_vis))])
+    X = np.concatenate([backproject(T, np.stack([rng.uniform(100.0, 600.0, behind), rng.uniform(100.0, 400.0, behind)], 1), -rng.uniform(1.0, 5.0, behind), cam),
+                        backproject(T, uv, rng.uniform(2.0, 12.0, n_vis), cam)])
     n_hit = min(n_vis, n_feat)
     xy = np.concatenate([uv[:n_hit] + np.clip(rng.normal(0.0, noise_px, (n_hit, 2)), -2.0, 2.0),
-                         np.stack([rng.uniform(1.0, W - 1.0, n_feat - n_hit), rng.uniform(1.0, H - 1.0, n_feat - n_hit)], 1)])
+                         np.stack([rng.uniform(1.0, w - 1.0, n_feat - n_hit), rng.uniform(1.0, h - 1.0, n_feat - n_hit)], 1)])
     perm = rng.permutation(n_feat)                      # feature f holds row perm[f]
     inv = np.argsort(perm)
     kp = keypoints(xy[perm])
