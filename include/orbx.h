@@ -796,6 +796,68 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
                       int* offsets, double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out,
                       uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched, orbx_track_result* results);
 
+/* ---- frame tracking against the reference keyframe (src/tracking/tracker.rs:992-1064) --------------------------------
+ * One call = the numeric part of track_with_reference_kf for n_frames frames at once, each against its own reference keyframe,
+ * with no host synchronisation inside:
+ *   1. BFMatcher(NORM_HAMMING, crossCheck = true).train_match(kf.descriptors, frame.descriptors) — query = keyframe feature,
+ *      train = frame feature: the mutual nearest neighbours in ascending query index, the lowest index winning a distance tie in
+ *      both directions (exactly orbx_hamming_match_crosscheck of the pair).  [spec] an empty side gives no matches (OpenCV
+ *      raises an error there);
+ *   2. for each match in that order: skipped unless valid[query_idx] != 0, else pts3d = positions[query_idx], pts2d = the
+ *      frame keypoint's (x, y) at train_idx.  The map lookups stay with the caller: valid[i] = 1 only when
+ *      kf.get_map_point(i) is Some and the map still holds that point (:1024-1036), positions[i] = that point's position;
+ *   3. fewer than min_correspondences (>= 4, :1051): TOO_FEW_CORRESPONDENCES, pose = the prior's bytes, n_inliers 0;
+ *   4. orbx_pnp_ransac_batch_device with the per-frame prior (:1057): NO_MODEL (pose = the prior) or OK.
+ * ORBX_TRACK_TOO_FEW_INLIERS is never produced: the reference has no such guard here.  The reference's Option<SE3> is Some(pose)
+ * for OK and NO_MODEL.  Every frame's result is the same bytes alone, inside any batch, and in the host form.
+ * n_matches: mutual matches (with or without a map point); n_correspondences: those with valid != 0; n_inliers: PnP's mask. */
+typedef struct {
+  int status, n_matches, n_correspondences, n_inliers;
+} orbx_track_ref_result;
+
+/* Every array in device memory (the caller's), asynchronous on the handle's stream; kf_offsets alone is a host array.
+ *   frames: d_kp / d_desc / d_feat_start / d_feat_count / feat_count_stride / max_feat as orbx_track_frames_device (counts are
+ *     read on the device; a count that is negative or above max_feat is a frame without features).  max_feat <= 4194304;
+ *   keyframes, packed: frame b's reference keyframe owns rows [kf_offsets[b], kf_offsets[b+1]) of d_kf_desc [K][32],
+ *     d_kf_positions [K][3] f64 and d_kf_valid [K] u8 (kf_offsets [n_frames+1] ascending from 0, K = kf_offsets[n_frames]; the
+ *     array is copied before the call returns).  Frames that share a keyframe repeat its rows;
+ *   d_priors_wc [n_frames][7] T_wc (self.pose, :1057);
+ *   outputs: d_matches [K]: frame b's mutual matches from kf_offsets[b], results[b].n_matches of them (distance = the integer
+ *     distance as f32, img_idx 0); d_offsets [n_frames+1]; d_pts3d [K][3], d_pts2d [K][2], d_kf_idx / d_feat_idx [K] (the
+ *     match's query_idx / train_idx), d_inlier_out [K], d_err_out [K]: frame b's correspondences are
+ *     [d_offsets[b], d_offsets[b+1]), packed from 0 in ascending keyframe-feature index (entries [0, d_offsets[n_frames]) are
+ *     written); d_poses_wc_out [n_frames][7]; d_pnp_results / d_results [n_frames].
+ * min_correspondences < 4, n_frames < 0 or an orbx_pnp_config out of range -> ORBX_ERR_INVALID before anything is enqueued;
+ * n_frames = 0 does nothing.  d_offsets / d_pts3d / d_pts2d / d_poses_wc_out can be passed straight into
+ * orbx_pose_inertial_batch_device. */
+int orbx_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                                int n_frames, const orbx_keypoint* d_kp, const uint8_t* d_desc, const int* d_feat_start,
+                                const int* d_feat_count, int feat_count_stride, int max_feat, const uint8_t* d_kf_desc,
+                                const double* d_kf_positions, const uint8_t* d_kf_valid, const int* kf_offsets,
+                                const double* d_priors_wc, orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d,
+                                int* d_kf_idx, int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
+/* The same in host memory, synchronous, one upload and one download.  Frame b's features are kp / desc
+ * [feat_offsets[b], feat_offsets[b+1]) (ascending from 0); the other arrays as above. */
+int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences, int n_frames,
+                         const orbx_keypoint* kp, const uint8_t* desc, const int* feat_offsets, const uint8_t* kf_desc,
+                         const double* kf_positions, const uint8_t* kf_valid, const int* kf_offsets, const double* priors_wc,
+                         orbx_dmatch* matches, int* offsets, double* pts3d, float* pts2d, int* kf_idx, int* feat_idx,
+                         double* poses_wc_out, uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results,
+                         orbx_track_ref_result* results);
+/* The device form with the reference keyframes resident (orbx_keyframe): frame b is matched against kfs[b]'s descriptors where
+ * they lie; a handle may be repeated.  kf_positions / kf_valid are HOST arrays packed in kfs[] order by kf_offsets (host), and
+ * kf_offsets[b+1] - kf_offsets[b] must equal kfs[b]'s feature count (else ORBX_ERR_INVALID); the three and kfs are copied before
+ * the call returns and travel in one upload on the handle's stream.  Frames, the prior and every output are device arrays as in
+ * orbx_track_reference_device; the result equals that call's on the same rows, byte for byte. */
+int orbx_keyframe_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                                  int n_frames, const orbx_keyframe* const* kfs, const orbx_keypoint* d_kp, const uint8_t* d_desc,
+                                  const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                  const double* kf_positions, const uint8_t* kf_valid, const int* kf_offsets, const double* d_priors_wc,
+                                  orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d, int* d_kf_idx,
+                                  int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                  orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

@@ -699,6 +699,95 @@ inline TrackResult track_with_motion_model(Handle& h, const CameraModel& camera,
   return track_frames(h, camera, {TrackFrame{&features, positions, mp_descriptors, predicted_pose, predicted_pose}}, 0)[0];
 }
 
+// ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
+// One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
+// validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).
+struct TrackReferenceFrame {
+  const FeatureSet* features = nullptr;
+  const std::vector<uint8_t>* kf_descriptors = nullptr;   // kf_positions.size() rows of 32 bytes
+  std::vector<std::array<double, 3>> kf_positions;
+  std::vector<uint8_t> kf_valid;
+  SE3 prior;
+};
+
+struct TrackReferenceResult {
+  SE3 pose;                                                     // the prior where there were too few correspondences or no model
+  std::vector<DMatch> matches;                                  // every mutual match: query = keyframe feature, train = frame feature
+  std::vector<std::array<double, 3>> points3d;                  // the correspondences, ascending keyframe-feature index
+  std::vector<std::array<float, 2>> points2d;
+  std::vector<int> kf_idx, feat_idx;
+  std::vector<double> reproj_errors;                            // per correspondence
+  std::vector<bool> inlier_mask;
+  orbx_track_ref_result record{};
+  orbx_pnp_result pnp{};
+  // the reference's Option<SE3> (:1051-1063)
+  std::optional<SE3> pose_or_none() const {
+    return record.status == ORBX_TRACK_OK || record.status == ORBX_TRACK_NO_MODEL ? std::optional<SE3>(pose) : std::nullopt;
+  }
+};
+
+// The batch form: one upload, one download.  min_correspondences below 4 throws orbx::Error (ORBX_ERR_INVALID).
+inline std::vector<TrackReferenceResult> track_reference(Handle& h, const CameraModel& camera, const std::vector<TrackReferenceFrame>& frames,
+                                                         int min_correspondences = 4) {
+  const int B = (int)frames.size();
+  orbx_pnp_config pc;
+  orbx_default_pnp_config(&pc);
+  std::vector<int> fo(B + 1, 0), ko(B + 1, 0);
+  std::vector<KeyPoint> kp;
+  std::vector<uint8_t> desc, kd, valid;
+  std::vector<double> pos, pr;
+  for (int b = 0; b < B; ++b) {
+    const TrackReferenceFrame& f = frames[b];
+    if (!f.features || !f.kf_descriptors || f.features->descriptors.size() != 32 * f.features->keypoints.size() ||
+        f.kf_descriptors->size() != 32 * f.kf_positions.size() || f.kf_valid.size() != f.kf_positions.size())
+      throw std::invalid_argument("track_reference: a frame's descriptors / positions / valid do not match in length");
+    kp.insert(kp.end(), f.features->keypoints.begin(), f.features->keypoints.end());
+    desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
+    kd.insert(kd.end(), f.kf_descriptors->begin(), f.kf_descriptors->end());
+    for (const auto& p : f.kf_positions) pos.insert(pos.end(), p.begin(), p.end());
+    valid.insert(valid.end(), f.kf_valid.begin(), f.kf_valid.end());
+    pr.insert(pr.end(), f.prior.rotation.begin(), f.prior.rotation.end());
+    pr.insert(pr.end(), f.prior.translation.begin(), f.prior.translation.end());
+    fo[b + 1] = (int)kp.size(); ko[b + 1] = (int)valid.size();
+  }
+  const size_t K = valid.size(), Kz = std::max<size_t>(K, 1), Bz = (size_t)std::max(B, 1);
+  std::vector<DMatch> ma(Kz);
+  std::vector<int> off(B + 1, 0), ki(Kz), fi(Kz);
+  std::vector<double> p3(3 * Kz), poses(7 * Bz), err(Kz);
+  std::vector<float> p2(2 * Kz);
+  std::vector<uint8_t> inl(Kz);
+  std::vector<orbx_pnp_result> pres(Bz);
+  std::vector<orbx_track_ref_result> res(Bz);
+  const orbx_camera cam = camera.c();
+  h.check(orbx_track_reference(h.get(), &cam, &pc, min_correspondences, B, kp.data(), desc.data(), fo.data(), kd.data(), pos.data(), valid.data(),
+                               ko.data(), pr.data(), ma.data(), off.data(), p3.data(), p2.data(), ki.data(), fi.data(), poses.data(), inl.data(),
+                               err.data(), pres.data(), res.data()));
+  std::vector<TrackReferenceResult> out(B);
+  for (int b = 0; b < B; ++b) {
+    TrackReferenceResult& r = out[b];
+    const double* o7 = &poses[7 * (size_t)b];
+    r.pose.rotation = {o7[0], o7[1], o7[2], o7[3]};
+    r.pose.translation = {o7[4], o7[5], o7[6]};
+    r.record = res[b]; r.pnp = pres[b];
+    r.matches.assign(ma.begin() + ko[b], ma.begin() + ko[b] + res[b].n_matches);
+    for (int i = off[b]; i < off[b + 1]; ++i) {
+      r.points3d.push_back({p3[3 * (size_t)i], p3[3 * (size_t)i + 1], p3[3 * (size_t)i + 2]});
+      r.points2d.push_back({p2[2 * (size_t)i], p2[2 * (size_t)i + 1]});
+      r.kf_idx.push_back(ki[i]); r.feat_idx.push_back(fi[i]);
+      r.reproj_errors.push_back(err[i]); r.inlier_mask.push_back(inl[i] != 0);
+    }
+  }
+  return out;
+}
+
+// tracker.rs:992-1064 on one frame: Some(pose), or None with fewer than 4 correspondences.
+inline std::optional<SE3> track_with_reference_kf(Handle& h, const CameraModel& camera, const FeatureSet& frame,
+                                                  const std::vector<uint8_t>& kf_descriptors,
+                                                  const std::vector<std::array<double, 3>>& kf_positions, const std::vector<uint8_t>& kf_valid,
+                                                  const SE3& pose) {
+  return track_reference(h, camera, {TrackReferenceFrame{&frame, &kf_descriptors, kf_positions, kf_valid, pose}})[0].pose_or_none();
+}
+
 // global_ba.rs:184-418.  The id -> index re-keying is the reference's own (:198-229).  Observations of a map point
 // that is not in mp_ids are rejected (collect_global_ba_data never emits one, :160).
 inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAProblemData& problem, const CameraModel& camera,

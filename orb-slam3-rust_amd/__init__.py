@@ -18,5 +18,6 @@ from .api import (  # noqa: F401
     KFDB_MAX_WORDS, TriangulationConfig, TriangulationResult, TRI_CREATED, TRI_SKIPPED, TRI_DLT_DEGENERATE, TRI_REJ_DEPTH, TRI_REJ_REPROJ1,
     TRI_REJ_REPROJ2, TRI_REJ_DIST, TRI_REJ_SCALE, TRI_BAD_INDEX, TRI_METHOD_DLT, TRI_METHOD_STEREO_CURRENT, TRI_METHOD_STEREO_NEIGHBOUR,
     TRI_MAX_NEIGHBOURS, FEATURE_NODE_NONE, TrackConfig, TrackFrameResult, TRACK_RESULT, TRACK_OK, TRACK_NO_MODEL,
-    TRACK_TOO_FEW_CORRESPONDENCES, TRACK_TOO_FEW_INLIERS, TRACK_MOTION_MODEL, TRACK_LOCAL_MAP)
+    TRACK_TOO_FEW_CORRESPONDENCES, TRACK_TOO_FEW_INLIERS, TRACK_MOTION_MODEL, TRACK_LOCAL_MAP, TRACK_REF_RESULT, TrackReferenceResult,
+    track_with_reference_kf)
 from .build import LIB_PATH, build  # noqa: F401

@@ -10,6 +10,7 @@ written in Python with the reference's own names and argument meaning:
     FeatureSet / StereoFrame     stereo.rs:15-29         FeatureSet / StereoFrame
     descriptor_distance          stereo.rs:166           descriptor_distance
     BFMatcher(HAMMING,true)      tracker.rs:1001-1010    bf_match_crosscheck
+    track_with_reference_kf      tracker.rs:992-1064     track_with_reference_kf / Handle.track_reference[_device]
     LocalBAConfigLM              local_ba_lm.rs:96-119   LocalBAConfigLM
     VisualBAProblemData/Result   local_ba_lm.rs:48-93    VisualBAProblemData / VisualBAResultData
     solve_visual_ba              local_ba_lm.rs:912      solve_visual_ba
@@ -92,6 +93,7 @@ ABI_SYMBOLS = [
     "orbx_default_triangulation_config", "orbx_triangulate_pairs", "orbx_triangulate_pairs_device", "orbx_keyframe_set_feature_nodes",
     "orbx_keyframe_triangulate_from_neighbors",
     "orbx_default_track_config", "orbx_track_frames", "orbx_track_frames_device",
+    "orbx_track_reference", "orbx_track_reference_device", "orbx_keyframe_track_reference",
 ]
 
 
@@ -189,6 +191,8 @@ class _TrackConfig(C.Structure):
 TRACK_RESULT = np.dtype([("status", "<i4"), ("n_in_front", "<i4"), ("n_correspondences", "<i4"), ("n_inliers", "<i4")])
 TRACK_OK, TRACK_NO_MODEL, TRACK_TOO_FEW_CORRESPONDENCES, TRACK_TOO_FEW_INLIERS = 0, 1, 2, 3
 TRACK_MOTION_MODEL, TRACK_LOCAL_MAP = 0, 1      # orbx_track_config.mode
+# orbx_track_ref_result as a numpy record (the results array of track_reference[_device]); statuses are TRACK_*
+TRACK_REF_RESULT = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_correspondences", "<i4"), ("n_inliers", "<i4")])
 
 
 class _LoopDetectorConfig(C.Structure):
@@ -428,6 +432,29 @@ class TrackFrameResult:
     @property
     def outlier_indices(self):
         return np.flatnonzero(~self.inlier_mask)
+
+
+@dataclass
+class TrackReferenceResult:
+    """One frame of Handle.track_reference — track_with_reference_kf (tracker.rs:992-1064) with the arrays behind it: pose (T_wc;
+    the prior where status is TRACK_TOO_FEW_CORRESPONDENCES or TRACK_NO_MODEL), matches (DMATCH: every mutual match, query =
+    keyframe feature, train = frame feature), the correspondences points3d [n,3] f64 / points2d [n,2] f32 / kf_idx / feat_idx [n]
+    int32 in ascending keyframe-feature order, PnP's inlier mask and errors over them, status (TRACK_*) and PnP's record."""
+    pose: np.ndarray
+    n_inliers: int
+    matches: np.ndarray
+    reproj_errors: np.ndarray
+    inlier_mask: np.ndarray
+    points3d: np.ndarray
+    points2d: np.ndarray
+    kf_idx: np.ndarray
+    feat_idx: np.ndarray
+    status: int
+    pnp_stats: dict
+
+    def pose_or_none(self):
+        """the reference's Option<SE3>: Some(pose) unless there were too few correspondences (:1051-1063)"""
+        return self.pose if self.status in (TRACK_OK, TRACK_NO_MODEL) else None
 
 
 @dataclass
@@ -747,9 +774,7 @@ class Handle:
                  inlier=mk(max(M, 1), torch.uint8), err=mk(max(M, 1), torch.float64), pnp_results=mk((max(B, 1), PNP_RESULT.itemsize), torch.uint8),
                  matched=mk((max(B, 1), max(int(max_feat), 1)), torch.int32), results=mk((max(B, 1), TRACK_RESULT.itemsize), torch.uint8))
         c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
-        if feat_count.dim() != 1 or feat_count.dtype != torch.int32 or (B > 1 and feat_count.stride(0) < 1):
-            raise ValueError("feat_count must be a 1-d int32 tensor or view with a positive stride")
-        fc_stride = int(feat_count.stride(0)) if B > 1 else 1
+        fc_stride = self._feat_count_stride(feat_count, B)
         ins = (kp, desc, feat_start, feat_count, positions, mp_desc, search_poses_wc, priors_wc)
         self._after_torch(*ins, *o.values())
         self._check(self._L.orbx_track_frames_device(
@@ -774,6 +799,114 @@ class Handle:
         b = batch or out["batch"]
         start = (torch.arange(b, dtype=torch.int32, device=out["nkp"].device) * 2 + side) * out["cap_kp"]
         return start, out["nkp"][:b, side]
+
+    def track_reference(self, camera, frames, min_correspondences=4, pnp_cfg: PnPConfig = None) -> List["TrackReferenceResult"]:
+        """track_with_reference_kf (tracker.rs:992-1064) for many frames in one call, host arrays, one upload and one download.
+        frames: [(kp, desc, kf_desc, kf_positions, kf_valid, prior_wc), ...] — the frame's keypoints (KEYPOINT) and descriptors [n,32];
+        its reference keyframe's descriptors [m,32], per keyframe feature the map point's position [m,3] f64 and a validity byte [m]
+        (1: the feature has a map point the map still holds); PnP's prior (T_wc, self.pose)."""
+        B = len(frames)
+        kps = [np.ascontiguousarray(f[0], KEYPOINT).reshape(-1) for f in frames]
+        des = [np.ascontiguousarray(f[1], np.uint8).reshape(-1, 32) for f in frames]
+        kds = [np.ascontiguousarray(f[2], np.uint8).reshape(-1, 32) for f in frames]
+        pos = [np.ascontiguousarray(f[3], np.float64).reshape(-1, 3) for f in frames]
+        val = [np.ascontiguousarray(f[4], np.uint8).reshape(-1) for f in frames]
+        if any(len(a) != len(b) for a, b in zip(kps, des)) or any(not (len(a) == len(b) == len(c)) for a, b, c in zip(kds, pos, val)):
+            raise ValueError("keypoints / descriptors or keyframe descriptors / positions / valid differ in length")
+        fo = np.zeros(B + 1, np.int32); fo[1:] = np.cumsum([len(a) for a in kps])
+        ko = np.zeros(B + 1, np.int32); ko[1:] = np.cumsum([len(a) for a in kds])
+        NF, K = int(fo[-1]), int(ko[-1])
+        kp = np.concatenate(kps) if NF else np.zeros(1, KEYPOINT)
+        de = np.concatenate(des) if NF else np.zeros((1, 32), np.uint8)
+        kd = np.concatenate(kds) if K else np.zeros((1, 32), np.uint8)
+        po = np.concatenate(pos) if K else np.zeros((1, 3), np.float64)
+        va = np.concatenate(val) if K else np.zeros(1, np.uint8)
+        pr = np.ascontiguousarray(np.stack([np.asarray(f[5], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        Kz, Bz = max(K, 1), max(B, 1)
+        ma = np.zeros(Kz, DMATCH); off = np.zeros(B + 1, np.int32); p3 = np.zeros((Kz, 3)); p2 = np.zeros((Kz, 2), np.float32)
+        ki = np.zeros(Kz, np.int32); fi = np.zeros(Kz, np.int32); poses = np.zeros((Bz, 7)); inl = np.zeros(Kz, np.uint8); err = np.zeros(Kz)
+        pres = np.zeros(Bz, PNP_RESULT); res = np.zeros(Bz, TRACK_REF_RESULT)
+        pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_track_reference(self._h, C.byref(cam), C.byref(pc), C.c_int(int(min_correspondences)), C.c_int(B), _vp(kp), _vp(de),
+                                                 _vp(fo), _vp(kd), _vp(po), _vp(va), _vp(ko), _vp(pr), _vp(ma), _vp(off), _vp(p3), _vp(p2), _vp(ki),
+                                                 _vp(fi), _vp(poses), _vp(inl), _vp(err), _vp(pres), _vp(res)))
+        out = []
+        for b in range(B):
+            s = slice(int(off[b]), int(off[b + 1]))
+            out.append(TrackReferenceResult(poses[b].copy(), int(res[b]["n_inliers"]), ma[ko[b]:ko[b] + int(res[b]["n_matches"])].copy(), err[s].copy(),
+                                            inl[s].astype(bool), p3[s].copy(), p2[s].copy(), ki[s].copy(), fi[s].copy(), int(res[b]["status"]),
+                                            _pnp_stats(pres[b])))
+        return out
+
+    def _track_reference_outputs(self, B, K, dev):
+        import torch
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        Kz, Bz = max(K, 1), max(B, 1)
+        return dict(matches=mk((Kz, DMATCH.itemsize), torch.uint8), offsets=mk(max(B, 0) + 1, torch.int32), points3d=mk((Kz, 3), torch.float64),
+                    points2d=mk((Kz, 2), torch.float32), kf_idx=mk(Kz, torch.int32), feat_idx=mk(Kz, torch.int32), poses=mk((Bz, 7), torch.float64),
+                    inlier=mk(Kz, torch.uint8), err=mk(Kz, torch.float64), pnp_results=mk((Bz, PNP_RESULT.itemsize), torch.uint8),
+                    results=mk((Bz, TRACK_REF_RESULT.itemsize), torch.uint8))
+
+    @staticmethod
+    def _feat_count_stride(feat_count, B):
+        import torch
+        if feat_count.dim() != 1 or feat_count.dtype != torch.int32 or (B > 1 and feat_count.stride(0) < 1):
+            raise ValueError("feat_count must be a 1-d int32 tensor or view with a positive stride")
+        return int(feat_count.stride(0)) if B > 1 else 1
+
+    def track_reference_device(self, camera, kp, desc, feat_start, feat_count, max_feat, kf_desc, kf_positions, kf_valid, kf_offsets, priors_wc,
+                               min_correspondences=4, pnp_cfg: PnPConfig = None):
+        """Device-resident form: torch CUDA tensors kp [*,7] f32 / desc [*,32] u8 / feat_start / feat_count [B] int32 / max_feat as
+        track_frames_device (feat_count may be the strided view track_feature_slots returns); the reference keyframes packed: kf_desc
+        [K,32] u8, kf_positions [K,3] f64, kf_valid [K] u8, frame b's keyframe owning rows kf_offsets[b] .. kf_offsets[b+1] (a host
+        array, ascending from 0); priors_wc [B,7] f64.  Returns a dict of tensors: matches [K,16] u8 (DMATCH; frame b's from row
+        kf_offsets[b], results n_matches of them), offsets [B+1] int32, points3d [K,3] f64, points2d [K,2] f32, kf_idx / feat_idx [K]
+        int32, poses [B,7] f64, inlier [K] u8, err [K] f64, pnp_results [B,32] u8 (PNP_RESULT), results [B,16] u8 (TRACK_REF_RESULT).
+        offsets / points3d / points2d / poses feed pose_inertial_optimization_batch_device unchanged.  Asynchronous on the handle's
+        stream."""
+        ko = np.ascontiguousarray(kf_offsets, np.int32).reshape(-1)
+        B, K = len(ko) - 1, int(ko[-1]) if len(ko) else 0
+        o = self._track_reference_outputs(B, K, priors_wc.device)
+        pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        fc_stride = self._feat_count_stride(feat_count, B)
+        self._after_torch(kp, desc, feat_start, feat_count, kf_desc, kf_positions, kf_valid, priors_wc, *o.values())
+        self._check(self._L.orbx_track_reference_device(
+            self._h, C.byref(cam), C.byref(pc), C.c_int(int(min_correspondences)), C.c_int(B), _vp(kp), _vp(desc), _vp(feat_start), _vp(feat_count),
+            C.c_int(fc_stride), C.c_int(int(max_feat)), _vp(kf_desc), _vp(kf_positions), _vp(kf_valid), _vp(ko), _vp(priors_wc), _vp(o["matches"]),
+            _vp(o["offsets"]), _vp(o["points3d"]), _vp(o["points2d"]), _vp(o["kf_idx"]), _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]),
+            _vp(o["err"]), _vp(o["pnp_results"]), _vp(o["results"])))
+        for k in ("matches", "points3d", "points2d", "kf_idx", "feat_idx", "inlier", "err"):
+            o[k] = o[k][:K]
+        return o
+
+    def keyframe_track_reference(self, camera, keyframes, kp, desc, feat_start, feat_count, max_feat, kf_positions, kf_valid, priors_wc,
+                                 min_correspondences=4, pnp_cfg: PnPConfig = None):
+        """track_reference_device against resident keyframes: frame b is matched against keyframes[b] (KeyFrame; one may be listed
+        several times), whose descriptors are read where they lie.  kf_positions / kf_valid are HOST arrays, one [n_b,3] f64 / [n_b] u8
+        pair per frame in a list (n_b = the keyframe's feature count); they travel in the call's one upload.  Frames, priors_wc and
+        the returned dict as track_reference_device."""
+        B = len(keyframes)
+        pos = [np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a in kf_positions]
+        val = [np.ascontiguousarray(a, np.uint8).reshape(-1) for a in kf_valid]
+        if len(pos) != B or len(val) != B or any(len(a) != len(b) for a, b in zip(pos, val)):
+            raise ValueError("one positions / valid pair per keyframe, of equal length")
+        ko = np.zeros(B + 1, np.int32); ko[1:] = np.cumsum([len(a) for a in pos])
+        K = int(ko[-1])
+        po = np.concatenate(pos) if K else np.zeros((1, 3), np.float64)
+        va = np.concatenate(val) if K else np.zeros(1, np.uint8)
+        arr = (C.c_void_p * max(B, 1))(*[k._p for k in keyframes])
+        o = self._track_reference_outputs(B, K, priors_wc.device)
+        pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        fc_stride = self._feat_count_stride(feat_count, B)
+        self._after_torch(kp, desc, feat_start, feat_count, priors_wc, *o.values())
+        self._check(self._L.orbx_keyframe_track_reference(
+            self._h, C.byref(cam), C.byref(pc), C.c_int(int(min_correspondences)), C.c_int(B), arr, _vp(kp), _vp(desc), _vp(feat_start), _vp(feat_count),
+            C.c_int(fc_stride), C.c_int(int(max_feat)), _vp(po), _vp(va), _vp(ko), _vp(priors_wc), _vp(o["matches"]), _vp(o["offsets"]),
+            _vp(o["points3d"]), _vp(o["points2d"]), _vp(o["kf_idx"]), _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]), _vp(o["err"]),
+            _vp(o["pnp_results"]), _vp(o["results"])))
+        for k in ("matches", "points3d", "points2d", "kf_idx", "feat_idx", "inlier", "err"):
+            o[k] = o[k][:K]
+        return o
 
     def pose_inertial_optimization(self, camera, pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d, points2d,
                                    is_stereo, cfg: PoseInertialConfig = None) -> PoseInertialResult:
@@ -1309,6 +1442,19 @@ def solve_pnp_ransac_detailed(points3d, points2d, camera: CameraModel, prior=Non
 def solve_pnp_ransac(points3d, points2d, camera: CameraModel, prior=None) -> np.ndarray:
     """pnp.rs:29-97: the pose (T_wc, 7 doubles) alone."""
     return solve_pnp_ransac_detailed(points3d, points2d, camera, prior).pose
+
+
+def track_with_reference_kf(frame_keypoints, frame_descriptors, kf_descriptors, kf_positions, kf_valid, camera: CameraModel, pose,
+                            min_correspondences=4):
+    """tracker.rs:992-1064: the frame against its reference keyframe — cross-checked brute-force matching (query = keyframe
+    feature), the matches whose keyframe feature has a live map point (kf_valid[i] = 1, position kf_positions[i]) gathered in
+    match order, PnP-RANSAC from `pose` (self.pose, T_wc).  Returns the pose, or None where the reference does (fewer than
+    min_correspondences correspondences, :1051).  min_correspondences below 4 is refused, as the library refuses it."""
+    if int(min_correspondences) < 4:
+        raise OrbxError(ORBX_ERR_INVALID, "track_with_reference_kf: min_correspondences must be at least 4 (tracker.rs:1051; PnP's own minimum)")
+    r = _handle().track_reference(camera, [(frame_keypoints, frame_descriptors, kf_descriptors, kf_positions, kf_valid, pose)],
+                                  min_correspondences)[0]
+    return r.pose_or_none()
 
 
 def pose_inertial_optimization(initial_pose, initial_velocity, initial_bias, prev_kf_pose, prev_kf_velocity, prev_kf_bias, preintegrated,

@@ -317,6 +317,35 @@ int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* 
   return ORBX_OK;
 }
 
+// track_with_reference_kf (tracker.rs:992-1064) against resident keyframes: see include/orbx.h.  The launches are
+// track_ref_kernels.hip's; each frame's item points at its keyframe's descriptors where they lie.
+int orbx_keyframe_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                                  int n_frames, const orbx_keyframe* const* kfs, const orbx_keypoint* d_kp, const uint8_t* d_desc,
+                                  const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                  const double* kf_positions, const uint8_t* kf_valid, const int* kf_offsets, const double* d_priors_wc,
+                                  orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d, int* d_kf_idx,
+                                  int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                  orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results) {
+  static const char* who = "orbx_keyframe_track_reference";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
+  if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && (!kfs || !kf_offsets)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
+  if (n_frames == 0) return ORBX_OK;
+  if (kf_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets[0] must be 0", who);
+  std::vector<TrackRefItem> items((size_t)n_frames);
+  for (int b = 0; b < n_frames; ++b) {
+    const orbx_keyframe* kf = kfs[b];
+    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, b);
+    if (kf_offsets[b + 1] - kf_offsets[b] != kf->n)
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets gives keyframe %d %d rows, it has %d features", who, b, kf_offsets[b + 1] - kf_offsets[b], kf->n);
+    items[(size_t)b].kf_desc = kf->d_desc; items[(size_t)b].kf_off = kf_offsets[b]; items[(size_t)b].n = kf->n;
+  }
+  return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
+                                 max_feat, items.data(), kf_positions, kf_valid, true, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
+                                 d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+}
+
 int orbx_keyframe_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* positions, const uint8_t* mp_desc, int P,
                               const orbx_keyframe* const* kfs, int T, double radius_scale, unsigned desc_threshold, int* out_idx,
                               uint32_t* out_dist) {

@@ -211,6 +211,10 @@ struct orbx_handle {
   void* h_track = nullptr; size_t h_track_bytes = 0;   // pinned staging of orbx_track_frames
   void* h_track_off[2] = {nullptr, nullptr}; size_t h_track_off_bytes[2] = {0, 0};   // pinned copies of orbx_track_frames_device's mp_offsets, used in turn
   hipEvent_t ev_track_off[2] = {nullptr, nullptr}; int track_off_next = 0;           // ... and the event behind each slot's upload
+  DevBuf ws_tref[3];                     // reference-keyframe tracking (track_ref_kernels.hip): [0] minima, pairs and counters, [1] the host form's input / output blobs, [2] the call's item table (and the keyframe form's positions / valid)
+  void* h_tref = nullptr; size_t h_tref_bytes = 0;     // pinned staging of orbx_track_reference
+  void* h_tref_items[2] = {nullptr, nullptr}; size_t h_tref_items_bytes[2] = {0, 0};   // pinned copies of the device forms' item table, used in turn
+  hipEvent_t ev_tref_items[2] = {nullptr, nullptr}; int tref_items_next = 0;           // ... and the event behind each slot's upload
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -335,6 +339,21 @@ int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_p
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist);
 // orbx_pnp_config's range check (pnp_kernels.hip), for callers that enqueue work ahead of PnP's own launches
 int orbx_pnp_check_config(orbx_handle* h, const orbx_pnp_config* c, const char* who);
+// ---- tracking against the reference keyframe (track_ref_kernels.hip; tracker.rs:992-1064) ----
+// Frame b's reference keyframe: its descriptors wherever they lie in device memory (a slice of a packed array or a resident
+// orbx_keyframe's block) and where its rows start in the packed per-keyframe-feature arrays (positions, valid, matches).
+struct TrackRefItem {
+  const uint8_t* kf_desc;
+  int kf_off, n;
+};
+// The device forms behind orbx_track_reference_device / orbx_keyframe_track_reference: items [B] is a host array (copied before
+// the call returns); positions / valid [K] are device arrays, or host arrays that travel with the items (pos_on_host).
+int track_reference_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                            int B, const orbx_keypoint* d_kp, const uint8_t* d_desc, const int* d_feat_start, const int* d_feat_count,
+                            int feat_count_stride, int max_feat, const TrackRefItem* items, const double* positions, const uint8_t* valid,
+                            bool pos_on_host, const double* d_priors_wc, orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d,
+                            int* d_kf_idx, int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                            orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
 // extractor (orb_kernels.hip)
 int orb_prepare_geometry(orbx_handle* h, int w, int h_px);
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,
