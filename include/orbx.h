@@ -858,6 +858,113 @@ int orbx_keyframe_track_reference(orbx_handle* h, const orbx_camera* cam, const 
                                   int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
                                   orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
 
+/* ---- loop-candidate verification (src/loop_closing/corrector.rs:116-204, src/loop_closing/sim3_solver.rs) -----------------
+ * verify_loop_candidate for a batch of (current keyframe, loop keyframe) pairs in one call with no host synchronisation inside;
+ * tests/loop_verify_spec.py restates it in numpy, DESIGN.md §2 lists the [spec] choices.  Per pair:
+ *   0. has_point counts of both keyframes, either below min_stereo_points (:132): TOO_FEW_POINTS;
+ *   1. match_features_bow (:229-306): for every current feature the best and the second-best Hamming distance over the loop
+ *      keyframe's features (strict <, so the lowest index keeps the best and a repeated best distance becomes the second), kept iff
+ *      best < match_max_dist && (double)best < match_ratio * (double)second (second = 4294967295 with a single candidate).  With
+ *      node ids on both keyframes the candidates of a feature are the loop features of its node in ascending index (node
+ *      0xffffffff, or a node the loop keyframe lacks: no match); else brute force.  [spec] matches come out in ascending
+ *      current-feature index (the reference walks a HashMap).  Fewer than min_matches (:139): TOO_FEW_MATCHES;
+ *   2. gather (:149-180): the matches whose two features both have a stereo point, world = pose_wc * points_cam (nalgebra's
+ *      quaternion-vector product, then + t).  Fewer than min_pairs (:178): TOO_FEW_PAIRS;
+ *   3. compute_sim3_ransac (sim3_solver.rs:63-145): see orbx_sim3_ransac_batch.  None: NO_MODEL; fewer than min_inliers
+ *      (corrector.rs:185): TOO_FEW_INLIERS;
+ *   4. verify_by_reprojection (:330-378) over ALL gathered matches: p = pose_loop^-1 * (M x + t); z <= 0 skipped; counted iff
+ *      du^2 + dv^2 < chi2 * s * s, s = scale_factor^octave of the loop keypoint (octave clamped to 0..31).  Fewer than
+ *      min_verified (:193): TOO_FEW_VERIFIED.
+ * Status = the first failing guard, else OK (the reference's Some).  The outputs of the stages up to and including the failing
+ * one are written; later record fields are 0, the Sim3 is the identity (1,0,0,0, 0,0,0, 1) and the mask is 0.
+ * A pair's result is the same bytes alone, inside any batch, and in every form below. */
+enum {
+  ORBX_LOOP_OK = 0, ORBX_LOOP_TOO_FEW_POINTS = 1, ORBX_LOOP_TOO_FEW_MATCHES = 2, ORBX_LOOP_TOO_FEW_PAIRS = 3, ORBX_LOOP_NO_MODEL = 4,
+  ORBX_LOOP_TOO_FEW_INLIERS = 5, ORBX_LOOP_TOO_FEW_VERIFIED = 6
+};
+enum { ORBX_SIM3_OK = 0, ORBX_SIM3_NO_MODEL = 1 };
+/* = Sim3SolverConfig, sim3_solver.rs:13-36; orbx_default_sim3_config: 300, 0.075, 15, fix_scale 1, 0.99, seed 0.  probability is
+ * carried and has no effect: the reference's loop range is built before its adaptive bound is lowered (:84, :113), so all
+ * max_iterations hypotheses are always evaluated.  Accepted: 1 <= max_iterations <= 1024, inlier_threshold > 0, min_inliers >= 3,
+ * 0 <= probability <= 1; other values -> ORBX_ERR_INVALID. */
+typedef struct {
+  int max_iterations;
+  double inlier_threshold;
+  int min_inliers, fix_scale;
+  double probability;
+  uint64_t seed;
+} orbx_sim3_config;
+/* The guards of corrector.rs:132 / :139 / :178 / :185 / :193 (20, 15, 15, 15, 50), the matcher's constants (:266: 50, 0.7), the
+ * reprojection test's (:338, :368: 5.991, 1.2) and the solver's configuration (fix_scale = 1, :183).  Accepted: counts >= 0,
+ * match_max_dist <= 256, match_ratio > 0, chi2 > 0, scale_factor > 0 and a valid sim3; else ORBX_ERR_INVALID. */
+typedef struct {
+  int min_stereo_points, min_matches, min_pairs, min_inliers, min_verified;
+  unsigned match_max_dist;
+  double match_ratio, chi2, scale_factor;
+  orbx_sim3_config sim3;
+} orbx_loop_verify_config;
+/* best_hypothesis: the winner's index (-1: none had an inlier); ransac_inliers: its count; n_inliers: of the returned model;
+ * refined: 1 when the refit over the winner's inliers was kept (:133); mse: mean squared error over the returned inliers. */
+typedef struct {
+  int status, best_hypothesis, ransac_inliers, n_inliers, refined, reserved_;
+  double mse;
+} orbx_sim3_result;
+typedef struct {
+  int status, n_matches, n_pairs, best_hypothesis, ransac_inliers, n_inliers, refined, n_verified;
+  double mse;
+} orbx_loop_verify_result;
+void orbx_default_sim3_config(orbx_sim3_config* cfg);
+void orbx_default_loop_verify_config(orbx_loop_verify_config* cfg);
+
+/* compute_sim3_ransac for n_problems point sets: problem p owns rows [offsets[p], offsets[p+1]) of pts1 / pts2 [N][3] f64 and of
+ * inlier [N] u8; it finds S with pts2 ~ S pts1.  sim3 [n_problems][8] = (qw,qx,qy,qz, tx,ty,tz, scale), qw >= 0 [spec].
+ *   [spec] hypothesis h = the first three distinct indices of PnP's counter-based sampler (64 draws; none: no hypothesis);
+ *   Horn on the sample: centroids, H = sum (p1-c1)(p2-c2)^T in sample order, R = V diag(1,1,det(V U^T)) U^T by a one-sided Jacobi
+ *   SVD in f64 that completes the basis of a rank-deficient H (a 3-point H has rank <= 2; collinear points rank 1): always a
+ *   proper rotation; scale 1 or sqrt(sum|b|^2 / sum|a|^2) (no hypothesis below 1e-10); M = scale * R; t = c2 - M c1;
+ *   inlier: |M p1 + t - p2|^2 < inlier_threshold^2.  Winner: most inliers, lowest h on ties (:100).  With >= min_inliers: Horn
+ *   over the winner's inliers, recount, kept iff the count did not fall (:133).  Fewer than min_inliers then, n < 3 or
+ *   n < min_inliers (:69-75): NO_MODEL, identity, mask 0.
+ * Host form: synchronous, one upload and one download.  Device form: every array in device memory, asynchronous on the
+ * handle's stream; max_n bounds a problem's size (a larger one gets NO_MODEL); d_offsets ascending from 0, trusted. */
+int orbx_sim3_ransac_batch(orbx_handle* h, const orbx_sim3_config* cfg, int n_problems, const int* offsets, const double* pts1,
+                           const double* pts2, double* sim3, uint8_t* inlier, orbx_sim3_result* results);
+int orbx_sim3_ransac_batch_device(orbx_handle* h, const orbx_sim3_config* cfg, int n_problems, int max_n, const int* d_offsets,
+                                  const double* d_pts1, const double* d_pts2, double* d_sim3, uint8_t* d_inlier,
+                                  orbx_sim3_result* d_results);
+/* The whole verification.  Keyframes are packed: pair b's current keyframe owns rows [cur_offsets[b], cur_offsets[b+1]) of
+ * cur_desc [N1][32], cur_points_cam [N1][3] f64, cur_has_point [N1] u8 and cur_node [N1] u32; its loop keyframe rows
+ * [loop_offsets[b], loop_offsets[b+1]) of loop_kp, loop_desc, loop_points_cam, loop_has_point, loop_node (keyframes shared by
+ * pairs repeat their rows).  cur_node / loop_node are HOST arrays in every form and may be NULL (brute force everywhere); a pair
+ * uses the FeatureVector matcher iff both are given (an all-0xffffffff array is a keyframe whose FeatureVector is empty).  The
+ * current keyframe's keypoints are not read.  cur_poses_wc / loop_poses_wc [n_pairs][7] and both offset arrays are host arrays.
+ * Outputs, all packed from cur_offsets[b]: matches [N1] (results[b].n_matches of them: query_idx = current feature, train_idx =
+ * loop feature, distance = the integer distance as f32), feature_matches [N1][2], pts_current / pts_loop [N1][3] and inlier [N1]
+ * (results[b].n_pairs of them); sim3 [n_pairs][8]; results [n_pairs].  At most 4194304 features per keyframe.
+ * The device form is asynchronous on the handle's stream; the host arrays are copied before it returns. */
+int orbx_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
+                                const uint8_t* cur_desc, const double* cur_points_cam, const uint8_t* cur_has_point,
+                                const uint32_t* cur_node, const int* cur_offsets, const double* cur_poses_wc, const orbx_keypoint* loop_kp,
+                                const uint8_t* loop_desc, const double* loop_points_cam, const uint8_t* loop_has_point,
+                                const uint32_t* loop_node, const int* loop_offsets, const double* loop_poses_wc, orbx_dmatch* matches,
+                                int* feature_matches, double* pts_current, double* pts_loop, uint8_t* inlier, double* sim3,
+                                orbx_loop_verify_result* results);
+int orbx_verify_loop_candidates_device(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
+                                       const uint8_t* d_cur_desc, const double* d_cur_points_cam, const uint8_t* d_cur_has_point,
+                                       const uint32_t* cur_node, const int* cur_offsets, const double* cur_poses_wc,
+                                       const orbx_keypoint* d_loop_kp, const uint8_t* d_loop_desc, const double* d_loop_points_cam,
+                                       const uint8_t* d_loop_has_point, const uint32_t* loop_node, const int* loop_offsets,
+                                       const double* loop_poses_wc, orbx_dmatch* d_matches, int* d_feature_matches,
+                                       double* d_pts_current, double* d_pts_loop, uint8_t* d_inlier, double* d_sim3,
+                                       orbx_loop_verify_result* d_results);
+/* The same on resident keyframes (handles may repeat): features, stereo points, poses and FeatureVectors
+ * (orbx_keyframe_set_feature_nodes) are the keyframes' own.  Outputs are HOST arrays packed from the running sum of the current
+ * keyframes' feature counts; only they cross PCIe.  Synchronous.  Bytes equal the packed forms' on the same rows. */
+int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
+                                         const orbx_keyframe* const* cur_kfs, const orbx_keyframe* const* loop_kfs, orbx_dmatch* matches,
+                                         int* feature_matches, double* pts_current, double* pts_loop, uint8_t* inlier, double* sim3,
+                                         orbx_loop_verify_result* results);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

@@ -788,6 +788,130 @@ inline std::optional<SE3> track_with_reference_kf(Handle& h, const CameraModel& 
   return track_reference(h, camera, {TrackReferenceFrame{&frame, &kf_descriptors, kf_positions, kf_valid, pose}})[0].pose_or_none();
 }
 
+// ---- loop-candidate verification (orbx_verify_loop_candidates, orbx_sim3_ransac_batch; corrector.rs:116-204, sim3_solver.rs) ----
+// sim3_solver.rs:13-36 and the sampler's seed; probability is carried and has no effect, as in the reference
+struct Sim3SolverConfig {
+  size_t max_iterations = 300;
+  double inlier_threshold = 0.075;
+  size_t min_inliers = 15;
+  bool fix_scale = true;
+  double probability = 0.99;
+  uint64_t seed = 0;
+  orbx_sim3_config c() const {
+    orbx_sim3_config o;
+    o.max_iterations = (int)max_iterations; o.inlier_threshold = inlier_threshold; o.min_inliers = (int)min_inliers;
+    o.fix_scale = fix_scale ? 1 : 0; o.probability = probability; o.seed = seed;
+    return o;
+  }
+};
+// geometry/sim3.rs:16-21: p' = scale * (rotation * p) + translation; rotation (w, x, y, z) with w >= 0
+struct Sim3 {
+  std::array<double, 4> rotation{1.0, 0.0, 0.0, 0.0};
+  std::array<double, 3> translation{0.0, 0.0, 0.0};
+  double scale = 1.0;
+};
+// sim3_solver.rs:39-49
+struct Sim3Result {
+  Sim3 sim3;
+  std::vector<size_t> inliers;
+  size_t num_inliers = 0;
+  double mse = 0.0;
+  orbx_sim3_result record{};
+};
+
+// sim3_solver.rs:63-145: the Sim3 S with points2 ~ S points1, or nullopt where the reference returns None
+inline std::optional<Sim3Result> compute_sim3_ransac(Handle& h, const std::vector<std::array<double, 3>>& points1,
+                                                     const std::vector<std::array<double, 3>>& points2, const Sim3SolverConfig& config) {
+  if (points1.size() != points2.size()) return std::nullopt;                       // :69
+  const int n = (int)points1.size();
+  const int off[2] = {0, n};
+  const orbx_sim3_config c = config.c();
+  double s8[8];
+  std::vector<uint8_t> inl((size_t)std::max(n, 1));
+  orbx_sim3_result rec{};
+  h.check(orbx_sim3_ransac_batch(h.get(), &c, 1, off, n ? points1[0].data() : nullptr, n ? points2[0].data() : nullptr, s8, inl.data(), &rec));
+  if (rec.status != ORBX_SIM3_OK) return std::nullopt;
+  Sim3Result r;
+  r.sim3.rotation = {s8[0], s8[1], s8[2], s8[3]}; r.sim3.translation = {s8[4], s8[5], s8[6]}; r.sim3.scale = s8[7];
+  for (int i = 0; i < n; ++i) if (inl[(size_t)i]) r.inliers.push_back((size_t)i);
+  r.num_inliers = (size_t)rec.n_inliers; r.mse = rec.mse; r.record = rec;
+  return r;
+}
+// sim3_solver.rs:318-328
+inline std::optional<Sim3Result> compute_sim3_from_matches(Handle& h, const std::vector<std::array<double, 3>>& points1,
+                                                           const std::vector<std::array<double, 3>>& points2, bool fix_scale) {
+  Sim3SolverConfig c;
+  c.fix_scale = fix_scale;
+  return compute_sim3_ransac(h, points1, points2, c);
+}
+
+// What verify_loop_candidate reads of a keyframe (atlas/map.rs KeyFrame): features, stereo points (points_cam with has_point = Some),
+// pose, the FeatureVector as one node id per feature (empty: none) and the map-point ids (-1 = None; empty: none)
+struct LoopKeyFrame {
+  const FeatureSet* features = nullptr;
+  std::vector<std::array<double, 3>> points_cam;
+  std::vector<uint8_t> has_point;
+  SE3 pose;
+  std::vector<uint32_t> feature_nodes;
+  std::vector<int64_t> map_points;
+};
+// corrector.rs:33-45
+struct VerifiedLoop {
+  uint64_t current_kf_id = 0, loop_kf_id = 0;
+  Sim3 sim3_current_to_loop;
+  std::vector<std::pair<int64_t, int64_t>> matched_map_points;
+  std::vector<std::pair<size_t, size_t>> feature_matches;
+  std::vector<DMatch> matches;                                  // every ratio-test match, with or without stereo points
+  std::vector<bool> inlier_mask;                                // Sim3's mask over feature_matches
+  orbx_loop_verify_result record{};
+};
+
+// corrector.rs:116-204 for one candidate: the record is always written to *record_out when given; nullopt where the reference
+// returns None.  Both keyframes with feature_nodes: the FeatureVector matcher, else brute force.
+inline std::optional<VerifiedLoop> verify_loop_candidate(Handle& h, const CameraModel& camera, const LoopKeyFrame& current, const LoopKeyFrame& loop,
+                                                         uint64_t current_kf_id = 0, uint64_t loop_kf_id = 0,
+                                                         const orbx_loop_verify_config* config = nullptr, VerifiedLoop* all_out = nullptr) {
+  if (!current.features || !loop.features) throw std::invalid_argument("verify_loop_candidate: a keyframe without features");
+  const size_t n1 = current.features->keypoints.size(), n2 = loop.features->keypoints.size();
+  if (current.features->descriptors.size() != 32 * n1 || loop.features->descriptors.size() != 32 * n2 || current.points_cam.size() != n1 ||
+      current.has_point.size() != n1 || loop.points_cam.size() != n2 || loop.has_point.size() != n2 ||
+      (!current.feature_nodes.empty() && current.feature_nodes.size() != n1) || (!loop.feature_nodes.empty() && loop.feature_nodes.size() != n2))
+    throw std::invalid_argument("verify_loop_candidate: a keyframe's arrays do not match in length");
+  orbx_loop_verify_config cfg;
+  if (config) cfg = *config; else orbx_default_loop_verify_config(&cfg);
+  const bool fv = !current.feature_nodes.empty() && !loop.feature_nodes.empty();
+  const int co[2] = {0, (int)n1}, lo[2] = {0, (int)n2};
+  double cp[7], lp[7], s8[8];
+  for (int k = 0; k < 4; ++k) { cp[k] = current.pose.rotation[k]; lp[k] = loop.pose.rotation[k]; }
+  for (int k = 0; k < 3; ++k) { cp[4 + k] = current.pose.translation[k]; lp[4 + k] = loop.pose.translation[k]; }
+  const size_t nz = std::max<size_t>(n1, 1);
+  std::vector<DMatch> ma(nz);
+  std::vector<int> fm(2 * nz);
+  std::vector<double> pc(3 * nz), pl(3 * nz);
+  std::vector<uint8_t> inl(nz);
+  orbx_loop_verify_result rec{};
+  const orbx_camera cam = camera.c();
+  h.check(orbx_verify_loop_candidates(h.get(), &cam, &cfg, 1, current.features->descriptors.data(), n1 ? current.points_cam[0].data() : nullptr,
+                                      current.has_point.data(), fv ? current.feature_nodes.data() : nullptr, co, cp, loop.features->keypoints.data(),
+                                      loop.features->descriptors.data(), n2 ? loop.points_cam[0].data() : nullptr, loop.has_point.data(),
+                                      fv ? loop.feature_nodes.data() : nullptr, lo, lp, ma.data(), fm.data(), pc.data(), pl.data(), inl.data(), s8,
+                                      &rec));
+  VerifiedLoop v;
+  v.current_kf_id = current_kf_id; v.loop_kf_id = loop_kf_id; v.record = rec;
+  v.sim3_current_to_loop.rotation = {s8[0], s8[1], s8[2], s8[3]}; v.sim3_current_to_loop.translation = {s8[4], s8[5], s8[6]};
+  v.sim3_current_to_loop.scale = s8[7];
+  v.matches.assign(ma.begin(), ma.begin() + rec.n_matches);
+  for (int k = 0; k < rec.n_pairs; ++k) {
+    const size_t i = (size_t)fm[2 * (size_t)k], j = (size_t)fm[2 * (size_t)k + 1];
+    v.feature_matches.emplace_back(i, j);
+    v.inlier_mask.push_back(inl[(size_t)k] != 0);
+    if (!current.map_points.empty() && !loop.map_points.empty() && current.map_points[i] >= 0 && loop.map_points[j] >= 0)   // :168-173
+      v.matched_map_points.emplace_back(current.map_points[i], loop.map_points[j]);
+  }
+  if (all_out) *all_out = v;
+  return rec.status == ORBX_LOOP_OK ? std::optional<VerifiedLoop>(v) : std::nullopt;
+}
+
 // global_ba.rs:184-418.  The id -> index re-keying is the reference's own (:198-229).  Observations of a map point
 // that is not in mp_ids are rejected (collect_global_ba_data never emits one, :160).
 inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAProblemData& problem, const CameraModel& camera,

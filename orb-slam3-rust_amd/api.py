@@ -28,7 +28,7 @@ import os
 import weakref
 from collections import deque
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -94,6 +94,8 @@ ABI_SYMBOLS = [
     "orbx_keyframe_triangulate_from_neighbors",
     "orbx_default_track_config", "orbx_track_frames", "orbx_track_frames_device",
     "orbx_track_reference", "orbx_track_reference_device", "orbx_keyframe_track_reference",
+    "orbx_default_sim3_config", "orbx_default_loop_verify_config", "orbx_sim3_ransac_batch", "orbx_sim3_ransac_batch_device",
+    "orbx_verify_loop_candidates", "orbx_verify_loop_candidates_device", "orbx_keyframe_verify_loop_candidates",
 ]
 
 
@@ -193,6 +195,30 @@ TRACK_OK, TRACK_NO_MODEL, TRACK_TOO_FEW_CORRESPONDENCES, TRACK_TOO_FEW_INLIERS =
 TRACK_MOTION_MODEL, TRACK_LOCAL_MAP = 0, 1      # orbx_track_config.mode
 # orbx_track_ref_result as a numpy record (the results array of track_reference[_device]); statuses are TRACK_*
 TRACK_REF_RESULT = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_correspondences", "<i4"), ("n_inliers", "<i4")])
+
+
+class _Sim3Config(C.Structure):
+    """orbx_sim3_config (include/orbx.h)"""
+    _fields_ = [("max_iterations", C.c_int), ("inlier_threshold", C.c_double), ("min_inliers", C.c_int), ("fix_scale", C.c_int),
+                ("probability", C.c_double), ("seed", C.c_uint64)]
+
+
+class _LoopVerifyConfig(C.Structure):
+    """orbx_loop_verify_config (include/orbx.h)"""
+    _fields_ = [("min_stereo_points", C.c_int), ("min_matches", C.c_int), ("min_pairs", C.c_int), ("min_inliers", C.c_int),
+                ("min_verified", C.c_int), ("match_max_dist", C.c_uint), ("match_ratio", C.c_double), ("chi2", C.c_double),
+                ("scale_factor", C.c_double), ("sim3", _Sim3Config)]
+
+
+# orbx_sim3_result / orbx_loop_verify_result as numpy records (the results arrays of the Sim3 and loop-verification calls)
+SIM3_RESULT = np.dtype([("status", "<i4"), ("best_hypothesis", "<i4"), ("ransac_inliers", "<i4"), ("n_inliers", "<i4"), ("refined", "<i4"),
+                        ("reserved_", "<i4"), ("mse", "<f8")])
+LOOP_VERIFY_RESULT = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_pairs", "<i4"), ("best_hypothesis", "<i4"),
+                               ("ransac_inliers", "<i4"), ("n_inliers", "<i4"), ("refined", "<i4"), ("n_verified", "<i4"), ("mse", "<f8")])
+SIM3_OK, SIM3_NO_MODEL = 0, 1
+(LOOP_OK, LOOP_TOO_FEW_POINTS, LOOP_TOO_FEW_MATCHES, LOOP_TOO_FEW_PAIRS, LOOP_NO_MODEL, LOOP_TOO_FEW_INLIERS,
+ LOOP_TOO_FEW_VERIFIED) = range(7)
+LOOP_VERIFY_MAX_FEAT = 1 << 22            # features per keyframe (loop_verify_kernels.hip: LV_MAX_FEAT)
 
 
 class _LoopDetectorConfig(C.Structure):
@@ -384,6 +410,68 @@ class PnPResult:
 
 def _pnp_stats(rec):
     return {k: (float(rec[k]) if k == "final_rms" else int(rec[k])) for k in PNP_RESULT.names}
+
+
+@dataclass
+class Sim3SolverConfig:
+    """sim3_solver.rs:13-36 and the sampler's seed [spec].  probability is carried and has no effect, as in the reference."""
+    max_iterations: int = 300
+    inlier_threshold: float = 0.075
+    min_inliers: int = 15
+    fix_scale: bool = True
+    probability: float = 0.99
+    seed: int = 0
+
+    def _c(self):
+        return _Sim3Config(self.max_iterations, self.inlier_threshold, self.min_inliers, 1 if self.fix_scale else 0, self.probability, self.seed)
+
+
+@dataclass
+class LoopVerifyConfig:
+    """The constants of verify_loop_candidate (corrector.rs:132-193, :266, :338, :368) and its solver's configuration (:183)."""
+    min_stereo_points: int = 20
+    min_matches: int = 15
+    min_pairs: int = 15
+    min_inliers: int = 15
+    min_verified: int = 50
+    match_max_dist: int = 50
+    match_ratio: float = 0.7
+    chi2: float = 5.991
+    scale_factor: float = 1.2
+    sim3: Sim3SolverConfig = field(default_factory=Sim3SolverConfig)
+
+    def _c(self):
+        return _LoopVerifyConfig(self.min_stereo_points, self.min_matches, self.min_pairs, self.min_inliers, self.min_verified,
+                                 self.match_max_dist, self.match_ratio, self.chi2, self.scale_factor, self.sim3._c())
+
+
+@dataclass
+class Sim3Result:
+    """sim3_solver.rs:39-49: sim3 = (qw,qx,qy,qz, tx,ty,tz, scale) with qw >= 0, inliers = the indices of the inlier
+    correspondences, num_inliers, mse; stats = the orbx_sim3_result record as a dict."""
+    sim3: np.ndarray
+    inliers: np.ndarray
+    num_inliers: int
+    mse: float
+    stats: Dict[str, float] = field(default_factory=dict)
+
+
+@dataclass
+class VerifiedLoop:
+    """corrector.rs:33-45.  matched_map_points: the (current, loop) map-point ids of the gathered matches where both features have
+    one (:168-173), filtered on the host; feature_matches [k,2] (current feature, loop feature).  stats = the
+    orbx_loop_verify_result record as a dict, inlier_mask = Sim3's mask over feature_matches."""
+    current_kf_id: int
+    loop_kf_id: int
+    sim3_current_to_loop: np.ndarray
+    matched_map_points: List[Tuple[int, int]]
+    feature_matches: np.ndarray
+    inlier_mask: np.ndarray = None
+    stats: Dict[str, float] = field(default_factory=dict)
+
+
+def _rec_dict(rec):
+    return {k: (float(rec[k]) if k == "mse" else int(rec[k])) for k in rec.dtype.names if k != "reserved_"}
 
 
 @dataclass
@@ -906,6 +994,122 @@ class Handle:
             _vp(o["pnp_results"]), _vp(o["results"])))
         for k in ("matches", "points3d", "points2d", "kf_idx", "feat_idx", "inlier", "err"):
             o[k] = o[k][:K]
+        return o
+
+    def compute_sim3_ransac_batch(self, problems, cfg: "Sim3SolverConfig" = None):
+        """compute_sim3_ransac (sim3_solver.rs:63-145) for many point sets [(points1 [n,3], points2 [n,3]), ...] in one call (one
+        upload, one download).  Returns (sim3 [P,8], inlier masks (list of [n] u8), results [P] SIM3_RESULT); each problem's bytes
+        equal its single call's."""
+        a = [np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x, _ in problems]
+        b = [np.ascontiguousarray(y, np.float64).reshape(-1, 3) for _, y in problems]
+        if any(len(x) != len(y) for x, y in zip(a, b)):
+            raise ValueError("points1 and points2 differ in length")
+        P = len(problems)
+        off = np.zeros(P + 1, np.int32); off[1:] = np.cumsum([len(x) for x in a])
+        N = int(off[-1])
+        p1 = np.concatenate(a) if N else np.zeros((1, 3)); p2 = np.concatenate(b) if N else np.zeros((1, 3))
+        sim3 = np.zeros((max(P, 1), 8)); inl = np.zeros(max(N, 1), np.uint8); res = np.zeros(max(P, 1), SIM3_RESULT)
+        c = (cfg or Sim3SolverConfig())._c()
+        self._check(self._L.orbx_sim3_ransac_batch(self._h, C.byref(c), C.c_int(P), _vp(off), _vp(p1), _vp(p2), _vp(sim3), _vp(inl), _vp(res)))
+        return sim3[:P], [inl[off[p]:off[p + 1]].copy() for p in range(P)], res[:P]
+
+    def compute_sim3_ransac_batch_device(self, offsets, points1, points2, max_n, cfg: "Sim3SolverConfig" = None):
+        """Device-resident batch: torch CUDA tensors offsets [P+1] int32 (ascending from 0), points1 / points2 [N,3] f64.  Returns
+        (sim3 [P,8] f64, inlier [N] u8, results [P,32] u8 — view as SIM3_RESULT); asynchronous on the handle's stream."""
+        import torch
+        P, N = int(offsets.shape[0]) - 1, int(points1.shape[0])
+        dev = points1.device
+        sim3 = torch.empty((max(P, 1), 8), dtype=torch.float64, device=dev)
+        inl = torch.zeros(max(N, 1), dtype=torch.uint8, device=dev)
+        res = torch.empty((max(P, 1), SIM3_RESULT.itemsize), dtype=torch.uint8, device=dev)
+        c = (cfg or Sim3SolverConfig())._c()
+        self._after_torch(offsets, points1, points2, sim3, inl, res)
+        self._check(self._L.orbx_sim3_ransac_batch_device(self._h, C.byref(c), C.c_int(P), C.c_int(int(max_n)), _vp(offsets), _vp(points1),
+                                                          _vp(points2), _vp(sim3), _vp(inl), _vp(res)))
+        return sim3[:P], inl[:N], res[:P]
+
+    @staticmethod
+    def _loop_verify_unpack(B, co, ma, fm, pc, pl, inl, sim3, res):
+        out = []
+        for b in range(B):
+            k0, nm, npair = int(co[b]), int(res[b]["n_matches"]), int(res[b]["n_pairs"])
+            out.append(dict(status=int(res[b]["status"]), matches=ma[k0:k0 + nm].copy(), feature_matches=fm[k0:k0 + npair].copy(),
+                            pts_current=pc[k0:k0 + npair].copy(), pts_loop=pl[k0:k0 + npair].copy(), inlier=inl[k0:k0 + npair].copy(),
+                            sim3=sim3[b].copy(), record=res[b].copy(), stats=_rec_dict(res[b])))
+        return out
+
+    @staticmethod
+    def _loop_verify_pack(pairs):
+        """pairs: [(cur, loop), ...], each a dict with desc [n,32] u8, points_cam [n,3] f64, has_point [n] u8, pose_wc [7], optional
+        node [n] u32; loop also kp (KEYPOINT)."""
+        B = len(pairs)
+        cd = [np.ascontiguousarray(c["desc"], np.uint8).reshape(-1, 32) for c, _ in pairs]
+        ld = [np.ascontiguousarray(l["desc"], np.uint8).reshape(-1, 32) for _, l in pairs]
+        co = np.zeros(B + 1, np.int32); co[1:] = np.cumsum([len(x) for x in cd])
+        lo = np.zeros(B + 1, np.int32); lo[1:] = np.cumsum([len(x) for x in ld])
+        N1, N2 = int(co[-1]), int(lo[-1])
+
+        def cat(side, key, dt, shape, n):
+            parts = [np.ascontiguousarray(p[side][key], dt).reshape(shape) for p in pairs]
+            return np.concatenate(parts) if n else np.zeros((1,) + tuple(shape[1:]), dt)
+        a = dict(cur_desc=cat(0, "desc", np.uint8, (-1, 32), N1), cur_pts=cat(0, "points_cam", np.float64, (-1, 3), N1),
+                 cur_has=cat(0, "has_point", np.uint8, (-1,), N1), loop_kp=cat(1, "kp", KEYPOINT, (-1,), N2),
+                 loop_desc=cat(1, "desc", np.uint8, (-1, 32), N2), loop_pts=cat(1, "points_cam", np.float64, (-1, 3), N2),
+                 loop_has=cat(1, "has_point", np.uint8, (-1,), N2))
+        # node ids travel as one array per side; a pair without them on either side gets brute force, which the library selects per
+        # pair from both arrays being present — so a mixed batch is passed pair by pair through the keyframe form or split by the caller
+        has_nodes = [c.get("node") is not None and l.get("node") is not None for c, l in pairs]
+        if any(has_nodes) and not all(has_nodes):
+            raise ValueError("the packed forms take node ids for every pair or for none; use KeyFrame.verify_loop_candidates for a mixed batch")
+        cn = cat(0, "node", np.uint32, (-1,), N1) if all(has_nodes) and B else None
+        ln = cat(1, "node", np.uint32, (-1,), N2) if all(has_nodes) and B else None
+        cp = np.ascontiguousarray(np.stack([np.asarray(c["pose_wc"], np.float64).reshape(7) for c, _ in pairs]) if B else np.zeros((1, 7)))
+        lp = np.ascontiguousarray(np.stack([np.asarray(l["pose_wc"], np.float64).reshape(7) for _, l in pairs]) if B else np.zeros((1, 7)))
+        return a, cn, ln, co, lo, cp, lp
+
+    def verify_loop_candidates(self, camera, pairs, cfg: "LoopVerifyConfig" = None):
+        """verify_loop_candidate's numeric part (corrector.rs:127-195) for many (current, loop) keyframe pairs in one call, host
+        arrays, one upload and one download.  pairs as _loop_verify_pack describes.  Returns one dict per pair: status (LOOP_*),
+        matches (DMATCH), feature_matches [k,2] int32, pts_current / pts_loop [k,3], inlier [k] u8, sim3 [8], record
+        (LOOP_VERIFY_RESULT), stats."""
+        B = len(pairs)
+        a, cn, ln, co, lo, cp, lp = self._loop_verify_pack(pairs)
+        N1 = max(int(co[-1]), 1)
+        ma = np.zeros(N1, DMATCH); fm = np.zeros((N1, 2), np.int32); pc = np.zeros((N1, 3)); pl = np.zeros((N1, 3)); inl = np.zeros(N1, np.uint8)
+        sim3 = np.zeros((max(B, 1), 8)); res = np.zeros(max(B, 1), LOOP_VERIFY_RESULT)
+        c = (cfg or LoopVerifyConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_verify_loop_candidates(
+            self._h, C.byref(cam), C.byref(c), C.c_int(B), _vp(a["cur_desc"]), _vp(a["cur_pts"]), _vp(a["cur_has"]), _vp(cn), _vp(co), _vp(cp),
+            _vp(a["loop_kp"]), _vp(a["loop_desc"]), _vp(a["loop_pts"]), _vp(a["loop_has"]), _vp(ln), _vp(lo), _vp(lp), _vp(ma), _vp(fm), _vp(pc),
+            _vp(pl), _vp(inl), _vp(sim3), _vp(res)))
+        return self._loop_verify_unpack(B, co, ma, fm, pc, pl, inl, sim3, res)
+
+    def verify_loop_candidates_device(self, camera, cur_desc, cur_points_cam, cur_has_point, cur_offsets, cur_poses_wc, loop_kp, loop_desc,
+                                      loop_points_cam, loop_has_point, loop_offsets, loop_poses_wc, cur_node=None, loop_node=None,
+                                      cfg: "LoopVerifyConfig" = None):
+        """Device-resident form: torch CUDA tensors cur_desc [N1,32] u8, cur_points_cam [N1,3] f64, cur_has_point [N1] u8, loop_kp [N2,7]
+        f32 (KEYPOINT rows), loop_desc / loop_points_cam / loop_has_point likewise; HOST arrays cur_offsets / loop_offsets [B+1],
+        cur_poses_wc / loop_poses_wc [B,7] and, optionally, cur_node [N1] / loop_node [N2] u32.  Returns a dict of tensors packed from
+        cur_offsets[b]: matches [N1,16] u8 (DMATCH), feature_matches [N1,2] int32, pts_current / pts_loop [N1,3] f64, inlier [N1] u8;
+        sim3 [B,8] f64, results [B,40] u8 (LOOP_VERIFY_RESULT).  Asynchronous on the handle's stream."""
+        import torch
+        co = np.ascontiguousarray(cur_offsets, np.int32).reshape(-1); lo = np.ascontiguousarray(loop_offsets, np.int32).reshape(-1)
+        B = len(co) - 1
+        N1 = max(int(co[-1]), 1)
+        dev = cur_desc.device
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(matches=mk((N1, DMATCH.itemsize), torch.uint8), feature_matches=mk((N1, 2), torch.int32), pts_current=mk((N1, 3), torch.float64),
+                 pts_loop=mk((N1, 3), torch.float64), inlier=mk(N1, torch.uint8), sim3=mk((max(B, 1), 8), torch.float64),
+                 results=mk((max(B, 1), LOOP_VERIFY_RESULT.itemsize), torch.uint8))
+        cp = np.ascontiguousarray(cur_poses_wc, np.float64).reshape(-1, 7); lp = np.ascontiguousarray(loop_poses_wc, np.float64).reshape(-1, 7)
+        cn = None if cur_node is None else np.ascontiguousarray(cur_node, np.uint32).reshape(-1)
+        ln = None if loop_node is None else np.ascontiguousarray(loop_node, np.uint32).reshape(-1)
+        c = (cfg or LoopVerifyConfig())._c(); cam = camera._c()
+        self._after_torch(cur_desc, cur_points_cam, cur_has_point, loop_kp, loop_desc, loop_points_cam, loop_has_point, *o.values())
+        self._check(self._L.orbx_verify_loop_candidates_device(
+            self._h, C.byref(cam), C.byref(c), C.c_int(B), _vp(cur_desc), _vp(cur_points_cam), _vp(cur_has_point), _vp(cn), _vp(co), _vp(cp),
+            _vp(loop_kp), _vp(loop_desc), _vp(loop_points_cam), _vp(loop_has_point), _vp(ln), _vp(lo), _vp(lp), _vp(o["matches"]),
+            _vp(o["feature_matches"]), _vp(o["pts_current"]), _vp(o["pts_loop"]), _vp(o["inlier"]), _vp(o["sim3"]), _vp(o["results"])))
         return o
 
     def pose_inertial_optimization(self, camera, pose_wc, velocity, bias, prev_kf_pose_wc, prev_kf_velocity, preint, points3d, points2d,
@@ -1457,6 +1661,33 @@ def track_with_reference_kf(frame_keypoints, frame_descriptors, kf_descriptors, 
     return r.pose_or_none()
 
 
+def compute_sim3_ransac(points1, points2, config: Sim3SolverConfig = None) -> Optional[Sim3Result]:
+    """sim3_solver.rs:63-145: the Sim3 S with points2 ~ S points1, or None where the reference returns None."""
+    sim3, inl, res = _handle().compute_sim3_ransac_batch([(points1, points2)], config)
+    if int(res[0]["status"]) != SIM3_OK:
+        return None
+    return Sim3Result(sim3[0].copy(), np.flatnonzero(inl[0]), int(res[0]["n_inliers"]), float(res[0]["mse"]), _rec_dict(res[0]))
+
+
+def compute_sim3_from_matches(points1, points2, fix_scale: bool) -> Optional[Sim3Result]:
+    """sim3_solver.rs:318-328: the default configuration with fix_scale set"""
+    return compute_sim3_ransac(points1, points2, Sim3SolverConfig(fix_scale=fix_scale))
+
+
+def verify_loop_candidate(current_kf, loop_kf, camera: CameraModel, current_kf_id=0, loop_kf_id=0, config: LoopVerifyConfig = None,
+                          handle: "Handle" = None) -> Optional[VerifiedLoop]:
+    """corrector.rs:116-204 for one candidate.  current_kf / loop_kf: dicts as Handle.verify_loop_candidates takes them, optionally
+    with map_points (a sequence of ids or None per feature).  None where the reference returns None."""
+    r = (handle or _handle()).verify_loop_candidates(camera, [(current_kf, loop_kf)], config)[0]
+    if r["status"] != LOOP_OK:
+        return None
+    cm, lm = current_kf.get("map_points"), loop_kf.get("map_points")
+    mmp = []
+    if cm is not None and lm is not None:
+        mmp = [(int(cm[i]), int(lm[j])) for i, j in r["feature_matches"] if cm[i] is not None and lm[j] is not None and cm[i] >= 0 and lm[j] >= 0]
+    return VerifiedLoop(int(current_kf_id), int(loop_kf_id), r["sim3"], mmp, r["feature_matches"], r["inlier"].astype(bool), r["stats"])
+
+
 def pose_inertial_optimization(initial_pose, initial_velocity, initial_bias, prev_kf_pose, prev_kf_velocity, prev_kf_bias, preintegrated,
                                observations, camera: CameraModel, config: PoseInertialConfig = None) -> PoseInertialResult:
     """pose_inertial_optim.rs:94-216 in the reference's argument order.  Poses T_wc (7 doubles), biases [6] (gyro, accel), preintegrated
@@ -1652,6 +1883,25 @@ class KeyFrame:
         stats = stats[:T]
         res = TriangulationResult(m, T, int(stats[:, 1].sum()), int(stats[:, 2].sum()), int(stats[:, 3].sum()), stats)
         return nb[:m], i1[:m], i2[:m], pts[:m], res
+
+    @staticmethod
+    def verify_loop_candidates(handle, camera, current_kfs, loop_kfs, cfg: "LoopVerifyConfig" = None):
+        """Handle.verify_loop_candidates on resident keyframes (features, stereo points, poses and FeatureVectors are the keyframes'
+        own; a keyframe may be listed several times): only the results cross PCIe.  A pair uses the FeatureVector matcher iff both of
+        its keyframes carry nodes (set_feature_nodes).  Returns the same list of dicts, byte for byte."""
+        B = len(current_kfs)
+        if len(loop_kfs) != B:
+            raise ValueError("one loop keyframe per current keyframe")
+        co = np.zeros(B + 1, np.int32); co[1:] = np.cumsum([k.n for k in current_kfs])
+        N1 = max(int(co[-1]), 1)
+        ma = np.zeros(N1, DMATCH); fm = np.zeros((N1, 2), np.int32); pc = np.zeros((N1, 3)); pl = np.zeros((N1, 3)); inl = np.zeros(N1, np.uint8)
+        sim3 = np.zeros((max(B, 1), 8)); res = np.zeros(max(B, 1), LOOP_VERIFY_RESULT)
+        ca = (C.c_void_p * max(B, 1))(*[k._p for k in current_kfs]); la = (C.c_void_p * max(B, 1))(*[k._p for k in loop_kfs])
+        c = (cfg or LoopVerifyConfig())._c(); cam = camera._c()
+        handle._after_torch()
+        handle._check(handle._L.orbx_keyframe_verify_loop_candidates(handle._h, C.byref(cam), C.byref(c), C.c_int(B), ca, la, _vp(ma), _vp(fm),
+                                                                     _vp(pc), _vp(pl), _vp(inl), _vp(sim3), _vp(res)))
+        return Handle._loop_verify_unpack(B, co, ma, fm, pc, pl, inl, sim3, res)
 
     @staticmethod
     def fuse_search(handle, camera, positions, mp_desc, keyframes, radius_scale, desc_threshold=50):

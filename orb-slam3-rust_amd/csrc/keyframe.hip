@@ -389,4 +389,57 @@ int orbx_keyframe_fuse_search(orbx_handle* h, const orbx_camera* cam, const doub
   return ORBX_OK;
 }
 
+int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
+                                         const orbx_keyframe* const* cur_kfs, const orbx_keyframe* const* loop_kfs, orbx_dmatch* matches,
+                                         int* feature_matches, double* pts_current, double* pts_loop, uint8_t* inlier, double* sim3,
+                                         orbx_loop_verify_result* results) {
+  static const char* who = "orbx_keyframe_verify_loop_candidates";
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || n_pairs < 0 || (n_pairs > 0 && (!cur_kfs || !loop_kfs || !sim3 || !results)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (n_pairs == 0) return ORBX_OK;
+  const size_t B = (size_t)n_pairs;
+  std::vector<LoopVerifyPair> pairs(B);
+  size_t N1 = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const orbx_keyframe* c = cur_kfs[b];
+    const orbx_keyframe* l = loop_kfs[b];
+    if (!c || !l || c->h != h || l->h != h || N1 + (size_t)c->n > 0x7fffffffu)
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad keyframe at pair %d (a keyframe belongs to the handle that made it)", who, (int)b);
+    LoopVerifyPair& p = pairs[b];
+    p.c_desc = c->d_desc; p.c_pts = c->d_points; p.c_has = c->d_has_point; p.c_node = c->has_nodes ? c->node.data() : nullptr; p.n1 = c->n;
+    p.l_kp = l->d_kp; p.l_desc = l->d_desc; p.l_pts = l->d_points; p.l_has = l->d_has_point; p.l_node = l->has_nodes ? l->node.data() : nullptr;
+    p.n2 = l->n;
+    memcpy(p.pose_c, c->pose_wc, sizeof(p.pose_c)); memcpy(p.pose_l, l->pose_wc, sizeof(p.pose_l));
+    p.out_off = (int)N1;
+    N1 += (size_t)c->n;
+  }
+  if (N1 > 0 && (!matches || !feature_matches || !pts_current || !pts_loop || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // the outputs in one device block: [sim3 | records | matches | feature matches | pts current | pts loop | inliers]
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_s3 = 0, o_rs = al(o_s3 + 64 * B), o_ma = al(o_rs + sizeof(orbx_loop_verify_result) * B), o_fm = al(o_ma + sizeof(orbx_dmatch) * N1),
+               o_pc = al(o_fm + 8 * N1), o_pl = al(o_pc + 24 * N1), o_in = al(o_pl + 24 * N1), out_bytes = al(o_in + N1);
+  if (int rc = orbx_reserve(h, h->ws_lv[1], out_bytes)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_lv[1].p;
+  if (int rc = loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), (orbx_dmatch*)(d + o_ma), (int*)(d + o_fm), (double*)(d + o_pc),
+                                   (double*)(d + o_pl), d + o_in, (double*)(d + o_s3), (orbx_loop_verify_result*)(d + o_rs)))
+    return rc;
+  ORBX_HIP(h, hipMemcpyAsync(sim3, d + o_s3, 64 * B, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(results, d + o_rs, sizeof(orbx_loop_verify_result) * B, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  for (size_t b = 0; b < B; ++b) {                                          // only what the records count travels
+    const size_t k0 = (size_t)pairs[b].out_off, nm = (size_t)results[b].n_matches, np = (size_t)results[b].n_pairs;
+    if (nm) ORBX_HIP(h, hipMemcpyAsync(matches + k0, d + o_ma + sizeof(orbx_dmatch) * k0, sizeof(orbx_dmatch) * nm, hipMemcpyDeviceToHost, h->stream));
+    if (np) {
+      ORBX_HIP(h, hipMemcpyAsync(feature_matches + 2 * k0, d + o_fm + 8 * k0, 8 * np, hipMemcpyDeviceToHost, h->stream));
+      ORBX_HIP(h, hipMemcpyAsync(pts_current + 3 * k0, d + o_pc + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
+      ORBX_HIP(h, hipMemcpyAsync(pts_loop + 3 * k0, d + o_pl + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
+      ORBX_HIP(h, hipMemcpyAsync(inlier + k0, d + o_in + k0, np, hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  return ORBX_OK;
+}
+
 }  // extern "C"

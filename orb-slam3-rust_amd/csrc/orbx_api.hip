@@ -164,6 +164,7 @@ void orbx_destroy(orbx_handle* h) {
   if (h->ws_pi.p) hipFree(h->ws_pi.p);
   for (DevBuf& b : h->ws_track) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_tref) if (b.p) hipFree(b.p);
+  for (DevBuf& b : h->ws_lv) if (b.p) hipFree(b.p);
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
   for (int i = 0; i < 2; ++i) { if (h->ev_in[i]) hipEventDestroy(h->ev_in[i]); if (h->ev_comp[i]) hipEventDestroy(h->ev_comp[i]); if (h->ev_out[i]) hipEventDestroy(h->ev_out[i]); }
   if (h->ba_up_event) hipEventDestroy(h->ba_up_event);
@@ -181,6 +182,8 @@ void orbx_destroy(orbx_handle* h) {
   for (int i = 0; i < 2; ++i) { if (h->h_track_off[i]) hipHostFree(h->h_track_off[i]); if (h->ev_track_off[i]) hipEventDestroy(h->ev_track_off[i]); }
   if (h->h_tref) hipHostFree(h->h_tref);
   for (int i = 0; i < 2; ++i) { if (h->h_tref_items[i]) hipHostFree(h->h_tref_items[i]); if (h->ev_tref_items[i]) hipEventDestroy(h->ev_tref_items[i]); }
+  if (h->h_lv) hipHostFree(h->h_lv);
+  for (int i = 0; i < 2; ++i) { if (h->h_lv_items[i]) hipHostFree(h->h_lv_items[i]); if (h->ev_lv_items[i]) hipEventDestroy(h->ev_lv_items[i]); }
   if (h->h_abort) hipHostFree(h->h_abort);
   if (h->d_status) hipFree(h->d_status);
   if (h->h_status) hipHostFree(h->h_status);

@@ -215,6 +215,10 @@ struct orbx_handle {
   void* h_tref = nullptr; size_t h_tref_bytes = 0;     // pinned staging of orbx_track_reference
   void* h_tref_items[2] = {nullptr, nullptr}; size_t h_tref_items_bytes[2] = {0, 0};   // pinned copies of the device forms' item table, used in turn
   hipEvent_t ev_tref_items[2] = {nullptr, nullptr}; int tref_items_next = 0;           // ... and the event behind each slot's upload
+  DevBuf ws_lv[4];                       // loop verification (loop_verify_kernels.hip): [0] minima, counters, hypotheses and models, [1] the host forms' input / output blobs, [2] the call's item table and node ids, [3] the standalone Sim3 host form's blobs
+  void* h_lv = nullptr; size_t h_lv_bytes = 0;         // pinned staging of the host forms
+  void* h_lv_items[2] = {nullptr, nullptr}; size_t h_lv_items_bytes[2] = {0, 0};   // pinned copies of the item table, used in turn
+  hipEvent_t ev_lv_items[2] = {nullptr, nullptr}; int lv_items_next = 0;           // ... and the event behind each slot's upload
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -354,6 +358,20 @@ int track_reference_enqueue(orbx_handle* h, const char* who, const orbx_camera* 
                             bool pos_on_host, const double* d_priors_wc, orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d,
                             int* d_kf_idx, int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
                             orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
+// ---- loop-candidate verification (loop_verify_kernels.hip; corrector.rs:116-204) ----
+// One (current keyframe, loop keyframe) pair: where its feature arrays lie in device memory, its poses, its FeatureVectors as
+// host arrays (both given: the FeatureVector matcher, else brute force) and where its rows start in the packed outputs.
+struct LoopVerifyPair {
+  const uint8_t* c_desc; const double* c_pts; const uint8_t* c_has; const uint32_t* c_node; int n1;
+  const orbx_keypoint* l_kp; const uint8_t* l_desc; const double* l_pts; const uint8_t* l_has; const uint32_t* l_node; int n2;
+  double pose_c[7], pose_l[7];
+  int out_off;
+};
+// The device form behind orbx_verify_loop_candidates_device / orbx_keyframe_verify_loop_candidates: pairs [B] is a host array
+// (copied, with the node ids, before the call returns); every output is device memory.
+int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int B,
+                        const LoopVerifyPair* pairs, orbx_dmatch* d_matches, int* d_feature_matches, double* d_pts_current,
+                        double* d_pts_loop, uint8_t* d_inlier, double* d_sim3, orbx_loop_verify_result* d_results);
 // extractor (orb_kernels.hip)
 int orb_prepare_geometry(orbx_handle* h, int w, int h_px);
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,
