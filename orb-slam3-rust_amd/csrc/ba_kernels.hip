@@ -3395,11 +3395,6 @@ constexpr size_t BA_LDS_DYN_MAX = 160 * 1024 - BA_LDS_STATIC;
 static_assert(BA_TILED_LDS_MAX + BA_LDS_STATIC <= 160 * 1024 && BF_LDS_BYTES + 8 * 1024 <= 160 * 1024 && SCHW_LDS_BYTES + 8 * 1024 <= 160 * 1024,
               "dynamic LDS of the tiled solve / one-launch factorisation / Schur kernels beside their static arrays (the exact check, against the code object, runs once per device in ba_set_func_attributes)");
 
-struct Carve {                                                       // byte offsets inside one buffer, 256-byte aligned pieces
-  size_t off = 0;
-  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-
 // The two sub-layouts that more than one array pointer is cut from: each stated here once, the size beside the pointers.
 // per-point sums of the build / back-substitution kernels: pt_chi2 [dbl][m1] | pt_glsq [dbl][m1] | pt_dsq [m1] | pt_psq [m1]
 constexpr size_t pt_sums_doubles(size_t m1, size_t dbl) { return (2 * dbl + 2) * m1; }
@@ -3488,15 +3483,6 @@ bool host_is_pinned(const void* p, size_t bytes) {
     return a.type == hipMemoryTypeHost;
   };
   return one(p) && one((const char*)p + bytes - 1);
-}
-
-int pinned_reserve(orbx_handle* h, void** p, size_t* have, size_t need) {
-  if (need <= *have) return ORBX_OK;
-  if (*p) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); ORBX_HIP(h, hipHostFree(*p)); *p = nullptr; *have = 0; }
-  const size_t want = (need + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
-  ORBX_HIP(h, hipHostMalloc(p, want));
-  *have = want;
-  return ORBX_OK;
 }
 
 // The O(K + M) host part of one window, straight into the (pinned) input blob: pose parameters, map points, fixed poses.  Everything
@@ -3652,18 +3638,18 @@ int ba_reserve(BaCtx& c) {
   // inertial: edges (int [E][2]) | preint [E][11] | per-edge J^T J records;  the 15-d reduced system
   if (int rc = orbx_reserve(h, h->ws_ba_imu, c.inertial ? 8 * ((size_t)c.inr->E * (1 + 11 + IMU_REC) + 8) : 8)) return rc;
   if (int rc = orbx_reserve(h, h->ws_ba_s15, c.inertial ? 8 * system_doubles((size_t)c.n15) : 8)) return rc;
-  if (int rc = pinned_reserve(h, &h->h_ba_in, &h->h_ba_in_bytes, c.small_bytes + (c.any_stage ? c.obs_bytes : 0))) return rc;
-  if (int rc = pinned_reserve(h, &h->h_ba_out, &h->h_ba_out_bytes, c.out_bytes)) return rc;
+  if (int rc = orbx_reserve_pinned(h, h->pin_ba_in, c.small_bytes + (c.any_stage ? c.obs_bytes : 0))) return rc;
+  if (int rc = orbx_reserve_pinned(h, h->pin_ba_out, c.out_bytes)) return rc;
   if (!h->h_abort) {
     ORBX_HIP(h, hipHostMalloc((void**)&h->h_abort, 64));
     ORBX_HIP(h, hipHostGetDevicePointer((void**)&h->d_abort, h->h_abort, 0));
   }
   *h->h_abort = 0;
-  c.hin = (uint8_t*)h->h_ba_in;
+  c.hin = (uint8_t*)h->pin_ba_in.p;
   c.din = (uint8_t*)h->ws_ba_in.p;
   c.dar = (uint8_t*)h->ws_ba_arena.p;
   c.dout = (double*)h->ws_ba_out.p;
-  c.hout = (double*)h->h_ba_out;
+  c.hout = (double*)h->pin_ba_out.p;
   c.dobs = c.din + c.small_bytes;                                        // the observation region of the device blob
   c.hobs = c.hin + c.small_bytes;                                        // ... and of the pinned one (staged windows only)
   c.hw = (BaWin*)(c.hin + c.i_wins);

@@ -44,8 +44,9 @@ int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_
   if (pose_wc) memcpy(kf->pose_wc, pose_wc, sizeof(kf->pose_wc));
   kf->mp_ids.assign((size_t)n, -1);
   const size_t n1 = (size_t)(n > 0 ? n : 1);
-  const size_t o_kp = 0, o_desc = (o_kp + sizeof(orbx_keypoint) * n1 + 255) & ~(size_t)255, o_pts = (o_desc + 32 * n1 + 255) & ~(size_t)255,
-               o_has = (o_pts + 24 * n1 + 255) & ~(size_t)255, o_mp = (o_has + n1 + 255) & ~(size_t)255, total = o_mp + ((n1 + 255) & ~(size_t)255);
+  Carve blk;
+  const size_t o_kp = blk.take(sizeof(orbx_keypoint) * n1), o_desc = blk.take(32 * n1), o_pts = blk.take(24 * n1), o_has = blk.take(n1), o_mp = blk.take(n1),
+               total = blk.off;
   if (hipMalloc((void**)&kf->block, total) != hipSuccess) { delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: out of device memory"); }
   kf->d_kp = (orbx_keypoint*)(kf->block + o_kp); kf->d_desc = kf->block + o_desc; kf->d_points = (double*)(kf->block + o_pts);
   kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp;
@@ -417,10 +418,10 @@ int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam,
   if (N1 > 0 && (!matches || !feature_matches || !pts_current || !pts_loop || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   ORBX_HIP(h, hipSetDevice(h->device));
   // the outputs in one device block: [sim3 | records | matches | feature matches | pts current | pts loop | inliers]
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_s3 = 0, o_rs = al(o_s3 + 64 * B), o_ma = al(o_rs + sizeof(orbx_loop_verify_result) * B), o_fm = al(o_ma + sizeof(orbx_dmatch) * N1),
-               o_pc = al(o_fm + 8 * N1), o_pl = al(o_pc + 24 * N1), o_in = al(o_pl + 24 * N1), out_bytes = al(o_in + N1);
-  if (int rc = orbx_reserve(h, h->ws_lv[1], out_bytes)) return rc;
+  Carve out;
+  const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
+               o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
+  if (int rc = orbx_reserve(h, h->ws_lv[1], out.off)) return rc;
   uint8_t* d = (uint8_t*)h->ws_lv[1].p;
   if (int rc = loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), (orbx_dmatch*)(d + o_ma), (int*)(d + o_fm), (double*)(d + o_pc),
                                    (double*)(d + o_pl), d + o_in, (double*)(d + o_s3), (orbx_loop_verify_result*)(d + o_rs)))

@@ -672,8 +672,6 @@ __global__ __launch_bounds__(LV_THREADS) void lv_finish_kernel(LvArgs A) {
   }
 }
 
-size_t lv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int s3_check_config(orbx_handle* h, const orbx_sim3_config* c, const char* who) {
   if (!c || c->max_iterations < 1 || c->max_iterations > S3_MAX_H || !(c->inlier_threshold > 0.0) || c->min_inliers < 3 ||
       !(c->probability >= 0.0 && c->probability <= 1.0))
@@ -688,19 +686,27 @@ int lv_check_config(orbx_handle* h, const orbx_loop_verify_config* c, const char
   return s3_check_config(h, &c->sim3, who);
 }
 
-size_t s3_ws_bytes(int P, int H) {
+// The workspace of s3_launch for P problems of H hypotheses: hyp [P * H][S3_HS] | hcnt [P * H], hok [P * H] | model [P][12].
+struct S3Ws {
+  size_t hyp, hcnt, model, bytes;
+};
+S3Ws s3_ws(int P, int H) {
   const size_t slots = (size_t)P * H;
-  return lv_align(slots * S3_HS * sizeof(double)) + lv_align(slots * 2 * sizeof(int)) + lv_align((size_t)P * 12 * sizeof(double));
+  Carve c;
+  S3Ws w;
+  w.hyp = c.take(slots * S3_HS * sizeof(double)); w.hcnt = c.take(slots * 2 * sizeof(int)); w.model = c.take((size_t)P * 12 * sizeof(double));
+  w.bytes = c.off;
+  return w;
 }
 
-// The three launches on the handle's stream; ws has s3_ws_bytes(P, H) bytes; every pointer is device memory.
+// The three launches on the handle's stream; ws has s3_ws(P, H).bytes bytes; every pointer is device memory.
 int s3_launch(orbx_handle* h, S3Args S, int P, uint8_t* ws) {
   const int H = S.cfg.max_iterations;
-  const size_t slots = (size_t)P * H;
-  S.hyp = (double*)ws;
-  S.hcnt = (int*)(ws + lv_align(slots * S3_HS * sizeof(double)));
-  S.hok = S.hcnt + slots;
-  S.model = (double*)(ws + lv_align(slots * S3_HS * sizeof(double)) + lv_align(slots * 2 * sizeof(int)));
+  const S3Ws lay = s3_ws(P, H);
+  S.hyp = (double*)(ws + lay.hyp);
+  S.hcnt = (int*)(ws + lay.hcnt);
+  S.hok = S.hcnt + (size_t)P * H;
+  S.model = (double*)(ws + lay.model);
   const double thr2 = S.cfg.inlier_threshold * S.cfg.inlier_threshold;      // :245
   {
     ProfScope ps(h, "sim3_hypothesis_kernel");
@@ -716,26 +722,6 @@ int s3_launch(orbx_handle* h, S3Args S, int P, uint8_t* ws) {
     hipLaunchKernelGGL(sim3_final_kernel, dim3(P), dim3(S3_THREADS), 0, h->stream, S, thr2);
   }
   ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
-}
-
-int lv_check_offsets(orbx_handle* h, int B, const int* off, const char* name, const char* who) {
-  if (!off) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (off[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s[0] must be 0", who, name);
-  for (int b = 0; b < B; ++b) {
-    if (off[b + 1] < off[b]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s not ascending at pair %d", who, name, b);
-    if (off[b + 1] - off[b] > LV_MAX_FEAT) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most %d features per keyframe", who, LV_MAX_FEAT);
-  }
-  return ORBX_OK;
-}
-
-// pinned staging of a host form, grown on demand
-int lv_stage(orbx_handle* h, size_t bytes) {
-  if (h->h_lv_bytes < bytes) {
-    if (h->h_lv) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); hipHostFree(h->h_lv); h->h_lv = nullptr; h->h_lv_bytes = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_lv, bytes, hipHostMallocDefault));
-    h->h_lv_bytes = bytes;
-  }
   return ORBX_OK;
 }
 
@@ -761,21 +747,12 @@ int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam,
   if (!d_sim3 || !d_results || (N1 > 0 && (!d_matches || !d_feature_matches || !d_pts_current || !d_pts_loop || !d_inlier)))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   ORBX_HIP(h, hipSetDevice(h->device));
-  // the item table and the FeatureVector tables go up from one of two pinned slots, so that the caller's arrays are free when the
-  // call returns; a slot is reused once the copy that read it has run (its event)
-  const size_t o_it = 0, o_node = lv_align(o_it + sizeof(LvItem) * (size_t)B), bytes = lv_align(o_node + 4 * (fv_n1 + fv_n2));
-  const int slot = h->lv_items_next;
-  h->lv_items_next ^= 1;
-  if (!h->ev_lv_items[slot]) ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_lv_items[slot], hipEventDisableTiming));
-  else ORBX_HIP(h, hipEventSynchronize(h->ev_lv_items[slot]));
-  if (h->h_lv_items_bytes[slot] < bytes) {
-    if (h->h_lv_items[slot]) { hipHostFree(h->h_lv_items[slot]); h->h_lv_items[slot] = nullptr; h->h_lv_items_bytes[slot] = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_lv_items[slot], bytes, hipHostMallocDefault));
-    h->h_lv_items_bytes[slot] = bytes;
-  }
-  if (int rc = orbx_reserve(h, h->ws_lv[2], bytes)) return rc;
-  uint8_t* hs = (uint8_t*)h->h_lv_items[slot];
-  uint8_t* ds = (uint8_t*)h->ws_lv[2].p;
+  // the item table and the FeatureVector tables go up through the upload ring, so that the caller's arrays are free when the call
+  // returns
+  Carve up;
+  const size_t o_it = up.take(sizeof(LvItem) * (size_t)B), o_node = up.take(4 * (fv_n1 + fv_n2));
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_lv, h->ws_lv[2], up.off, &hs, &ds)) return rc;
   size_t n_at = 0;
   for (int b = 0; b < B; ++b) {
     const LoopVerifyPair& p = pairs[b];
@@ -794,12 +771,12 @@ int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam,
     }
     ((LvItem*)(hs + o_it))[b] = it;
   }
-  ORBX_HIP(h, hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipEventRecord(h->ev_lv_items[slot], h->stream));
-  const int H = cfg->sim3.max_iterations;
-  const size_t o_best = 0, o_pre = lv_align(o_best + 8 * N1), o_sres = lv_align(o_pre + 4 * LV_PRE * (size_t)B),
-               o_s3 = lv_align(o_sres + sizeof(orbx_sim3_result) * (size_t)B);
-  if (int rc = orbx_reserve(h, h->ws_lv[0], o_s3 + s3_ws_bytes(B, H))) return rc;
+  if (int rc = orbx_ring_commit(h, h->ring_lv, h->ws_lv[2], up.off)) return rc;
+  const S3Ws s3 = s3_ws(B, cfg->sim3.max_iterations);
+  Carve ws;
+  const size_t o_best = ws.take(8 * N1), o_pre = ws.take(4 * LV_PRE * (size_t)B), o_sres = ws.take(sizeof(orbx_sim3_result) * (size_t)B),
+               o_s3 = ws.take(s3.bytes);
+  if (int rc = orbx_reserve(h, h->ws_lv[0], ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_lv[0].p;
   LvArgs A{};
   A.cam = *cam; A.cfg = *cfg;
@@ -811,7 +788,7 @@ int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam,
   S3Args S{};
   S.cfg = cfg->sim3; S.max_n = max_n1; S.stride = LV_PRE; S.start = A.pre + 3; S.count = A.pre + 4;
   S.pts1 = d_pts_current; S.pts2 = d_pts_loop; S.sim3 = d_sim3; S.inl = d_inlier; S.results = (orbx_sim3_result*)(w + o_sres);
-  A.model = (const double*)(w + o_s3 + lv_align((size_t)B * H * S3_HS * sizeof(double)) + lv_align((size_t)B * H * 2 * sizeof(int)));
+  A.model = (const double*)(w + o_s3 + s3.model);
   orbx_prof_begin_call(h);
   if (any_bf && max_n1 > 0) {
     ProfScope ps(h, "lv_match_kernel");
@@ -871,7 +848,7 @@ int orbx_sim3_ransac_batch_device(orbx_handle* h, const orbx_sim3_config* cfg, i
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   if (n_problems == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve(h, h->ws_lv[0], s3_ws_bytes(n_problems, cfg->max_iterations))) return rc;
+  if (int rc = orbx_reserve(h, h->ws_lv[0], s3_ws(n_problems, cfg->max_iterations).bytes)) return rc;
   S3Args S{};
   S.cfg = *cfg; S.max_n = max_n; S.stride = 1; S.start = d_offsets; S.count = nullptr;
   S.pts1 = d_pts1; S.pts2 = d_pts2; S.sim3 = d_sim3; S.inl = d_inlier; S.results = d_results;
@@ -886,33 +863,25 @@ int orbx_sim3_ransac_batch(orbx_handle* h, const orbx_sim3_config* cfg, int n_pr
   if (int rc = s3_check_config(h, cfg, who)) return rc;
   if (n_problems < 0 || (n_problems > 0 && (!offsets || !sim3 || !results))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   if (n_problems == 0) return ORBX_OK;
-  if (offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: offsets[0] must be 0", who);
   int max_n = 0;
-  for (int p = 0; p < n_problems; ++p) {
-    const int n = offsets[p + 1] - offsets[p];
-    if (n < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: offsets not ascending at problem %d", who, p);
-    max_n = std::max(max_n, n);
-  }
+  if (int rc = orbx_check_offsets(h, who, "offsets", "problem", n_problems, offsets, &max_n)) return rc;
   const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
   if (N > 0 && (!pts1 || !pts2 || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [offsets | pts1 | pts2] up, [sim3 | results | inliers] down
-  const size_t i_of = 0, i_p1 = lv_align(i_of + 4 * (P + 1)), i_p2 = lv_align(i_p1 + 24 * N), in_bytes = lv_align(i_p2 + 24 * N);
-  const size_t o_s3 = 0, o_rs = lv_align(o_s3 + 64 * P), o_in = lv_align(o_rs + sizeof(orbx_sim3_result) * P), out_bytes = lv_align(o_in + N);
-  if (int rc = lv_stage(h, in_bytes + out_bytes)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_lv[3], in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_lv;
-  uint8_t* ho = hi + in_bytes;
-  uint8_t* di = (uint8_t*)h->ws_lv[3].p;
-  uint8_t* dout = di + in_bytes;
+  Carve in, out;
+  const size_t i_of = in.take(4 * (P + 1)), i_p1 = in.take(24 * N), i_p2 = in.take(24 * N);
+  const size_t o_s3 = out.take(64 * P), o_rs = out.take(sizeof(orbx_sim3_result) * P), o_in = out.take(N);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[3], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   std::memcpy(hi + i_of, offsets, 4 * (P + 1));
   if (N) { std::memcpy(hi + i_p1, pts1, 24 * N); std::memcpy(hi + i_p2, pts2, 24 * N); }
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   if (int rc = orbx_sim3_ransac_batch_device(h, cfg, n_problems, max_n, (const int*)(di + i_of), (const double*)(di + i_p1),
                                              (const double*)(di + i_p2), (double*)(dout + o_s3), dout + o_in, (orbx_sim3_result*)(dout + o_rs)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
   std::memcpy(sim3, ho + o_s3, 64 * P);
   std::memcpy(results, ho + o_rs, sizeof(orbx_sim3_result) * P);
   if (N) std::memcpy(inlier, ho + o_in, N);
@@ -932,8 +901,8 @@ int orbx_verify_loop_candidates_device(orbx_handle* h, const orbx_camera* cam, c
   if (int rc = lv_check_config(h, cfg, who)) return rc;
   if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   if (n_pairs == 0) return ORBX_OK;
-  if (int rc = lv_check_offsets(h, n_pairs, cur_offsets, "cur_offsets", who)) return rc;
-  if (int rc = lv_check_offsets(h, n_pairs, loop_offsets, "loop_offsets", who)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
   if (!cur_poses_wc || !loop_poses_wc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   std::vector<LoopVerifyPair> pairs((size_t)n_pairs);
   for (int b = 0; b < n_pairs; ++b) {
@@ -965,8 +934,8 @@ int orbx_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const or
   if (int rc = lv_check_config(h, cfg, who)) return rc;
   if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   if (n_pairs == 0) return ORBX_OK;
-  if (int rc = lv_check_offsets(h, n_pairs, cur_offsets, "cur_offsets", who)) return rc;
-  if (int rc = lv_check_offsets(h, n_pairs, loop_offsets, "loop_offsets", who)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
   const size_t B = (size_t)n_pairs, N1 = (size_t)cur_offsets[B], N2 = (size_t)loop_offsets[B];
   if (!cur_poses_wc || !loop_poses_wc || !sim3 || !results || (N1 > 0 && (!cur_desc || !cur_points_cam || !cur_has_point || !matches ||
       !feature_matches || !pts_current || !pts_loop || !inlier)) || (N2 > 0 && (!loop_kp || !loop_desc || !loop_points_cam || !loop_has_point)))
@@ -974,32 +943,27 @@ int orbx_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const or
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [cur desc | cur points | cur has | loop kp | loop desc | loop points | loop has] up,
   // [sim3 | records | matches | feature matches | pts current | pts loop | inliers] down
-  const size_t i_cd = 0, i_cp = lv_align(i_cd + 32 * N1), i_ch = lv_align(i_cp + 24 * N1), i_lk = lv_align(i_ch + N1),
-               i_ld = lv_align(i_lk + sizeof(orbx_keypoint) * N2), i_lp = lv_align(i_ld + 32 * N2), i_lh = lv_align(i_lp + 24 * N2),
-               in_bytes = lv_align(i_lh + N2);
-  const size_t o_s3 = 0, o_rs = lv_align(o_s3 + 64 * B), o_ma = lv_align(o_rs + sizeof(orbx_loop_verify_result) * B),
-               o_fm = lv_align(o_ma + sizeof(orbx_dmatch) * N1), o_pc = lv_align(o_fm + 8 * N1), o_pl = lv_align(o_pc + 24 * N1),
-               o_in = lv_align(o_pl + 24 * N1), out_bytes = lv_align(o_in + N1);
-  if (int rc = lv_stage(h, in_bytes + out_bytes)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_lv[1], in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_lv;
-  uint8_t* ho = hi + in_bytes;
-  uint8_t* di = (uint8_t*)h->ws_lv[1].p;
-  uint8_t* dout = di + in_bytes;
+  Carve in, out;
+  const size_t i_cd = in.take(32 * N1), i_cp = in.take(24 * N1), i_ch = in.take(N1), i_lk = in.take(sizeof(orbx_keypoint) * N2), i_ld = in.take(32 * N2),
+               i_lp = in.take(24 * N2), i_lh = in.take(N2);
+  const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
+               o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   if (N1) { std::memcpy(hi + i_cd, cur_desc, 32 * N1); std::memcpy(hi + i_cp, cur_points_cam, 24 * N1); std::memcpy(hi + i_ch, cur_has_point, N1); }
   if (N2) {
     std::memcpy(hi + i_lk, loop_kp, sizeof(orbx_keypoint) * N2); std::memcpy(hi + i_ld, loop_desc, 32 * N2);
     std::memcpy(hi + i_lp, loop_points_cam, 24 * N2); std::memcpy(hi + i_lh, loop_has_point, N2);
   }
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   if (int rc = orbx_verify_loop_candidates_device(h, cam, cfg, n_pairs, di + i_cd, (const double*)(di + i_cp), di + i_ch, cur_node, cur_offsets,
                                                   cur_poses_wc, (const orbx_keypoint*)(di + i_lk), di + i_ld, (const double*)(di + i_lp), di + i_lh,
                                                   loop_node, loop_offsets, loop_poses_wc, (orbx_dmatch*)(dout + o_ma), (int*)(dout + o_fm),
                                                   (double*)(dout + o_pc), (double*)(dout + o_pl), dout + o_in, (double*)(dout + o_s3),
                                                   (orbx_loop_verify_result*)(dout + o_rs)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
   std::memcpy(sim3, ho + o_s3, 64 * B);
   std::memcpy(results, ho + o_rs, sizeof(orbx_loop_verify_result) * B);
   for (size_t b = 0; b < B; ++b) {

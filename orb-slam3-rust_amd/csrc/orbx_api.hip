@@ -44,6 +44,76 @@ int orbx_reserve(orbx_handle* h, DevBuf& b, size_t bytes) {
   return ORBX_OK;
 }
 
+// ---- host staging (orbx_internal.hpp; DESIGN.md, "Host staging") --------------------------------------
+// frees and re-allocates; the caller has made sure that nothing in flight touches the old buffer
+static int pinned_regrow(orbx_handle* h, PinnedBuf& b, size_t bytes) {
+  if (b.p) { ORBX_HIP(h, hipHostFree(b.p)); b.p = nullptr; b.bytes = 0; }
+  const size_t want = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
+  ORBX_HIP(h, hipHostMalloc(&b.p, want, hipHostMallocDefault));
+  b.bytes = want;
+  return ORBX_OK;
+}
+
+int orbx_reserve_pinned(orbx_handle* h, PinnedBuf& b, size_t bytes) {
+  if (bytes <= b.bytes) return ORBX_OK;
+  if (b.p) ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  return pinned_regrow(h, b, bytes);
+}
+
+int orbx_ring_begin(orbx_handle* h, UploadRing& r, DevBuf& dev, size_t bytes, uint8_t** host, uint8_t** device) {
+  const int s = r.next;
+  r.next ^= 1;
+  if (!r.ev[s]) ORBX_HIP(h, hipEventCreateWithFlags(&r.ev[s], hipEventDisableTiming));
+  else ORBX_HIP(h, hipEventSynchronize(r.ev[s]));
+  if (r.slot[s].bytes < bytes)
+    if (int rc = pinned_regrow(h, r.slot[s], bytes)) return rc;
+  if (int rc = orbx_reserve(h, dev, bytes)) return rc;
+  *host = (uint8_t*)r.slot[s].p;
+  *device = (uint8_t*)dev.p;
+  return ORBX_OK;
+}
+
+int orbx_ring_commit(orbx_handle* h, UploadRing& r, const DevBuf& dev, size_t bytes) {
+  const int s = r.next ^ 1;                                              // the slot begin handed out
+  ORBX_HIP(h, hipMemcpyAsync(dev.p, r.slot[s].p, bytes, hipMemcpyHostToDevice, h->stream));
+  ORBX_HIP(h, hipEventRecord(r.ev[s], h->stream));
+  return ORBX_OK;
+}
+
+int orbx_host_call_begin(orbx_handle* h, PinnedBuf& pin, DevBuf& dev, size_t in_bytes, size_t out_bytes, HostCall& c) {
+  if (int rc = orbx_reserve_pinned(h, pin, in_bytes + out_bytes)) return rc;
+  if (int rc = orbx_reserve(h, dev, in_bytes + out_bytes)) return rc;
+  c.hi = (uint8_t*)pin.p; c.ho = c.hi + in_bytes;
+  c.di = (uint8_t*)dev.p; c.dout = c.di + in_bytes;
+  c.in_bytes = in_bytes;
+  return ORBX_OK;
+}
+
+int orbx_host_call_upload(orbx_handle* h, const HostCall& c) {
+  ORBX_HIP(h, hipMemcpyAsync(c.di, c.hi, c.in_bytes, hipMemcpyHostToDevice, h->stream));
+  return ORBX_OK;
+}
+
+int orbx_host_call_download(orbx_handle* h, const HostCall& c, size_t bytes) {
+  ORBX_HIP(h, hipMemcpyAsync(c.ho, c.dout, bytes, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  return ORBX_OK;
+}
+
+int orbx_check_offsets(orbx_handle* h, const char* who, const char* name, const char* unit, int n, const int* off, int* max_span, int cap) {
+  if (!off) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (off[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s[0] must be 0", who, name);
+  int widest = 0;
+  for (int i = 0; i < n; ++i) {
+    const int span = off[i + 1] - off[i];
+    if (span < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s not ascending at %s %d", who, name, unit, i);
+    if (span > cap) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s gives %s %d more than %d rows", who, name, unit, i, cap);
+    widest = std::max(widest, span);
+  }
+  if (max_span) *max_span = widest;
+  return ORBX_OK;
+}
+
 // ---- profiling --------------------------------------------------------------------------------------
 static hipEvent_t prof_event(orbx_handle* h) {
   if (h->event_next == h->event_pool.size()) {
@@ -173,17 +243,13 @@ void orbx_destroy(orbx_handle* h) {
   for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
   if (h->pair_graph) hipGraphExecDestroy(h->pair_graph);
   orbx_rccl_drop(h);
-  if (h->h_stage) hipHostFree(h->h_stage);
-  if (h->h_ba_in) hipHostFree(h->h_ba_in);
-  if (h->h_ba_out) hipHostFree(h->h_ba_out);
-  if (h->h_pnp) hipHostFree(h->h_pnp);
-  if (h->h_pi) hipHostFree(h->h_pi);
-  if (h->h_track) hipHostFree(h->h_track);
-  for (int i = 0; i < 2; ++i) { if (h->h_track_off[i]) hipHostFree(h->h_track_off[i]); if (h->ev_track_off[i]) hipEventDestroy(h->ev_track_off[i]); }
-  if (h->h_tref) hipHostFree(h->h_tref);
-  for (int i = 0; i < 2; ++i) { if (h->h_tref_items[i]) hipHostFree(h->h_tref_items[i]); if (h->ev_tref_items[i]) hipEventDestroy(h->ev_tref_items[i]); }
-  if (h->h_lv) hipHostFree(h->h_lv);
-  for (int i = 0; i < 2; ++i) { if (h->h_lv_items[i]) hipHostFree(h->h_lv_items[i]); if (h->ev_lv_items[i]) hipEventDestroy(h->ev_lv_items[i]); }
+  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv};
+  UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv};
+  for (PinnedBuf* b : pins) if (b->p) hipHostFree(b->p);
+  for (UploadRing* r : rings) {
+    for (PinnedBuf& b : r->slot) if (b.p) hipHostFree(b.p);
+    for (hipEvent_t e : r->ev) if (e) hipEventDestroy(e);
+  }
   if (h->h_abort) hipHostFree(h->h_abort);
   if (h->d_status) hipFree(h->d_status);
   if (h->h_status) hipHostFree(h->h_status);
@@ -618,9 +684,7 @@ int orbx_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* posit
       (P > 0 && T > 0 && (!out_idx || !out_dist)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
   if (P == 0 || T == 0) return ORBX_OK;
-  if (kf_feat_offset[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: kf_feat_offset[0] must be 0");
-  for (int t = 0; t < T; ++t)
-    if (kf_feat_offset[t + 1] < kf_feat_offset[t]) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: kf_feat_offset not ascending");
+  if (int rc = orbx_check_offsets(h, "orbx_fuse_search", "kf_feat_offset", "keyframe", T, kf_feat_offset)) return rc;
   const int n = kf_feat_offset[T];
   if (n > 0 && (!kps || !descs)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
@@ -712,12 +776,7 @@ int orbx_process_stereo(orbx_handle* h, const uint8_t* left, size_t lstride, con
   const size_t total = (o_has + cp + 63) & ~(size_t)63;
   if (int rc = orbx_reserve(h, h->ws_io[6], 2 * img)) return rc;
   if (int rc = orbx_reserve(h, h->ws_io[7], total)) return rc;
-  if (h->h_stage_bytes < total) {
-    if (h->h_stage) ORBX_HIP(h, hipHostFree(h->h_stage));
-    h->h_stage = nullptr; h->h_stage_bytes = 0;
-    ORBX_HIP(h, hipHostMalloc((void**)&h->h_stage, total));
-    h->h_stage_bytes = total;
-  }
+  if (int rc = orbx_reserve_pinned(h, h->pin_stage, total)) return rc;
   uint8_t* d_img = (uint8_t*)h->ws_io[6].p;
   uint8_t* d_out = (uint8_t*)h->ws_io[7].p;
   ORBX_HIP(h, hipMemcpy2DAsync(d_img, w, left, lstride, w, h_px, hipMemcpyHostToDevice, h->stream));
@@ -768,9 +827,9 @@ int orbx_process_stereo(orbx_handle* h, const uint8_t* left, size_t lstride, con
       else ORBX_HIP(h, hipGraphLaunch(h->pair_graph, h->stream));
     }
   }
-  ORBX_HIP(h, hipMemcpyAsync(h->h_stage, d_out, total, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(h->pin_stage.p, d_out, total, hipMemcpyDeviceToHost, h->stream));
   ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  const uint8_t* S = h->h_stage;
+  const uint8_t* S = (const uint8_t*)h->pin_stage.p;
   const int* cnt = (const int*)(S + o_cnt);
   const unsigned st = (unsigned)cnt[3];
   if (st & ORBX_ST_KP_OVERFLOW) return orbx_fail(h, ORBX_ERR_CAPACITY, "an image produced more keypoints than cap_kp");

@@ -164,6 +164,30 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// ---- host staging shared by the batched forms ("Host staging"; the functions are beside orbx_reserve in orbx_api.hip) ----
+// Byte offsets inside one buffer, 256-byte aligned pieces: take(bytes) answers where the piece starts, `off` is the total so far.
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+// Grow-only pinned host memory (orbx_reserve_pinned).
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+// Two pinned slots used in turn for the small host tables of a device form, so that the caller's arrays are free when the call
+// returns; ev[i] is recorded behind the upload that read slot i (orbx_ring_begin / orbx_ring_commit).
+struct UploadRing {
+  PinnedBuf slot[2];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int next = 0;
+};
+// One host form's blobs: [in_bytes | out_bytes] in a pinned buffer (hi, ho) and at the same offsets in a workspace (di, dout).
+struct HostCall {
+  uint8_t* hi; uint8_t* ho; uint8_t* di; uint8_t* dout;
+  size_t in_bytes;
+};
+
 struct KernelTimer {
   std::string name;
   std::vector<hipEvent_t> ev;  // start/stop pairs of the current call
@@ -181,8 +205,7 @@ struct orbx_handle {
   std::string err;
   unsigned* d_status = nullptr;
   unsigned* h_status = nullptr;   // pinned
-  uint8_t* h_stage = nullptr;     // pinned mirror of the single-pair output block (orbx_process_stereo)
-  size_t h_stage_bytes = 0;
+  PinnedBuf pin_stage;            // pinned mirror of the single-pair output block (orbx_process_stereo)
   // hipGraph of the device part of orbx_process_stereo (launch-bound: ~20 short launches per frame); valid for
   // one (w, h, cap, buffer addresses) configuration, re-captured when any of them changes
   hipGraphExec_t pair_graph = nullptr;
@@ -204,21 +227,18 @@ struct orbx_handle {
   DevBuf ws_ba_imu, ws_ba_s15;             // ... inertial: IMU edges, preintegrations and records; the 15-d reduced system
   DevBuf ws_ba_debug;                      // ba_debug_blocks / ba_debug_imu_residual
   DevBuf ws_pnp[2];                      // PnP-RANSAC: [0] hypotheses + counts (pnp_kernels.hip), [1] the host forms' input / output blobs
-  void* h_pnp = nullptr; size_t h_pnp_bytes = 0;   // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
+  PinnedBuf pin_pnp;                     // pinned staging of orbx_pnp_ransac_batch (one upload, one download)
   DevBuf ws_pi;                          // pose-inertial optimization: the host forms' input / output blob (pose_inertial_kernels.hip)
-  void* h_pi = nullptr; size_t h_pi_bytes = 0;     // pinned staging of orbx_pose_inertial_batch
+  PinnedBuf pin_pi;                      // pinned staging of orbx_pose_inertial_batch
   DevBuf ws_track[3];                    // frame tracking (track_kernels.hip): [0] grids, matches and counters, [1] the host form's input / output blobs, [2] mp_offsets of the device form
-  void* h_track = nullptr; size_t h_track_bytes = 0;   // pinned staging of orbx_track_frames
-  void* h_track_off[2] = {nullptr, nullptr}; size_t h_track_off_bytes[2] = {0, 0};   // pinned copies of orbx_track_frames_device's mp_offsets, used in turn
-  hipEvent_t ev_track_off[2] = {nullptr, nullptr}; int track_off_next = 0;           // ... and the event behind each slot's upload
+  PinnedBuf pin_track;                   // pinned staging of orbx_track_frames
+  UploadRing ring_track;                 // orbx_track_frames_device's mp_offsets on their way to ws_track[2]
   DevBuf ws_tref[3];                     // reference-keyframe tracking (track_ref_kernels.hip): [0] minima, pairs and counters, [1] the host form's input / output blobs, [2] the call's item table (and the keyframe form's positions / valid)
-  void* h_tref = nullptr; size_t h_tref_bytes = 0;     // pinned staging of orbx_track_reference
-  void* h_tref_items[2] = {nullptr, nullptr}; size_t h_tref_items_bytes[2] = {0, 0};   // pinned copies of the device forms' item table, used in turn
-  hipEvent_t ev_tref_items[2] = {nullptr, nullptr}; int tref_items_next = 0;           // ... and the event behind each slot's upload
+  PinnedBuf pin_tref;                    // pinned staging of orbx_track_reference
+  UploadRing ring_tref;                  // the device forms' item table (and the keyframe form's positions / valid) on their way to ws_tref[2]
   DevBuf ws_lv[4];                       // loop verification (loop_verify_kernels.hip): [0] minima, counters, hypotheses and models, [1] the host forms' input / output blobs, [2] the call's item table and node ids, [3] the standalone Sim3 host form's blobs
-  void* h_lv = nullptr; size_t h_lv_bytes = 0;         // pinned staging of the host forms
-  void* h_lv_items[2] = {nullptr, nullptr}; size_t h_lv_items_bytes[2] = {0, 0};   // pinned copies of the item table, used in turn
-  hipEvent_t ev_lv_items[2] = {nullptr, nullptr}; int lv_items_next = 0;           // ... and the event behind each slot's upload
+  PinnedBuf pin_lv;                      // pinned staging of the host forms
+  UploadRing ring_lv;                    // the item table and the node ids on their way to ws_lv[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -229,8 +249,7 @@ struct orbx_handle {
   void* rccl_comm = nullptr;                               // ncclComm_t of the point-partitioned solve (orbx_ba_init_rccl / orbx_ba_set_rccl_comm)
   orbx_handle* ba_aux = nullptr;                           // second stream + workspaces of orbx_ba_solve_visual_batch (half of a large batch runs there)
   bool rccl_owned = false;
-  void* h_ba_in = nullptr;   size_t h_ba_in_bytes = 0;    // pinned mirrors of the batch input / output blobs (ba_solve_batch)
-  void* h_ba_out = nullptr;  size_t h_ba_out_bytes = 0;
+  PinnedBuf pin_ba_in, pin_ba_out;                         // pinned mirrors of the batch input / output blobs (ba_solve_batch)
   int* h_abort = nullptr;    int* d_abort = nullptr;       // pinned, device-visible: should_stop() seen while the iterations drain
   OrbxWorkPool* ba_pool = nullptr;                         // host workers of the batch preprocessing (created by the first large batch)
   OrbxHelperThread* ba_helper = nullptr;                   // drives the second half of a large batch (orbx_ba_solve_visual_batch)
@@ -246,6 +265,23 @@ struct orbx_handle {
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
 int orbx_reserve(orbx_handle* h, DevBuf& b, size_t bytes);
+// Grow-only, in steps of 1 MiB.  A buffer that is replaced may still be read or written by a copy on the handle's stream: the stream is
+// synchronised before it is freed (so a host form may call this, a device form may not).
+int orbx_reserve_pinned(orbx_handle* h, PinnedBuf& b, size_t bytes);
+// begin: takes the ring's next slot, waits for the upload that last read it (the only wait: the slot is then idle and grows without
+// synchronising the stream), reserves `dev` and answers both bases; the caller fills host[0, bytes), where it may store pointers into
+// device[0, bytes).  commit: enqueues the copy on the handle's stream, then records the slot's event behind it.
+int orbx_ring_begin(orbx_handle* h, UploadRing& r, DevBuf& dev, size_t bytes, uint8_t** host, uint8_t** device);
+int orbx_ring_commit(orbx_handle* h, UploadRing& r, const DevBuf& dev, size_t bytes);
+// The skeleton of a host form: begin reserves pin and dev for in_bytes + out_bytes and sets c; the caller fills c.hi; upload is the one
+// host-to-device copy of the input blob; download copies out[0, bytes) back and synchronises the stream, the call's only wait.
+int orbx_host_call_begin(orbx_handle* h, PinnedBuf& pin, DevBuf& dev, size_t in_bytes, size_t out_bytes, HostCall& c);
+int orbx_host_call_upload(orbx_handle* h, const HostCall& c);
+int orbx_host_call_download(orbx_handle* h, const HostCall& c, size_t bytes);
+// CSR offsets off[0..n]: non-null, off[0] == 0, ascending, no span above `cap`; ORBX_OK or ORBX_ERR_INVALID (the message names who, the
+// array and the `unit` counted, such as "frame").  *max_span, when given, receives the largest off[i + 1] - off[i].
+int orbx_check_offsets(orbx_handle* h, const char* who, const char* name, const char* unit, int n, const int* off, int* max_span = nullptr,
+                       int cap = 0x7fffffff);
 
 #define ORBX_HIP(h, call)                                                                   \
   do {                                                                                      \

@@ -522,8 +522,6 @@ int pnp_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* cf
   return ORBX_OK;
 }
 
-size_t pnp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int orbx_pnp_check_config(orbx_handle* h, const orbx_pnp_config* c, const char* who) { return pnp_check_config(h, c, who); }
@@ -563,43 +561,29 @@ int orbx_pnp_ransac_batch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp
   if (!cam || n_problems < 0 || (n_problems > 0 && (!offsets || !priors_wc || !poses_wc_out || !results)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pnp_ransac_batch: bad argument");
   if (n_problems == 0) return ORBX_OK;
-  if (offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pnp_ransac_batch: offsets[0] must be 0");
   int max_n = 0;
-  for (int p = 0; p < n_problems; ++p) {
-    const int n = offsets[p + 1] - offsets[p];
-    if (n < 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pnp_ransac_batch: offsets not ascending at problem %d", p);
-    max_n = std::max(max_n, n);
-  }
+  if (int rc = orbx_check_offsets(h, "orbx_pnp_ransac_batch", "offsets", "problem", n_problems, offsets, &max_n)) return rc;
   const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
   if (N > 0 && (!pts3d || !pts2d || !inlier_out || !err_out)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pnp_ransac_batch: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [offsets | pts3d | priors | pts2d] up, [poses | err | results | inliers] down
-  const size_t o_off = 0, o_p3 = pnp_align(o_off + 4 * (P + 1)), o_pr = pnp_align(o_p3 + 24 * N), o_p2 = pnp_align(o_pr + 56 * P);
-  const size_t in_bytes = pnp_align(o_p2 + 8 * N);
-  const size_t o_po = 0, o_er = pnp_align(o_po + 56 * P), o_rs = pnp_align(o_er + 8 * N), o_in = pnp_align(o_rs + sizeof(orbx_pnp_result) * P);
-  const size_t out_bytes = pnp_align(o_in + N);
-  if (h->h_pnp_bytes < in_bytes + out_bytes) {
-    if (h->h_pnp) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); hipHostFree(h->h_pnp); h->h_pnp = nullptr; h->h_pnp_bytes = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_pnp, in_bytes + out_bytes, hipHostMallocDefault));
-    h->h_pnp_bytes = in_bytes + out_bytes;
-  }
-  if (int rc = orbx_reserve(h, h->ws_pnp[1], in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_pnp;
-  uint8_t* ho = hi + in_bytes;
+  Carve in, out;
+  const size_t o_off = in.take(4 * (P + 1)), o_p3 = in.take(24 * N), o_pr = in.take(56 * P), o_p2 = in.take(8 * N);
+  const size_t o_po = out.take(56 * P), o_er = out.take(8 * N), o_rs = out.take(sizeof(orbx_pnp_result) * P), o_in = out.take(N);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_pnp, h->ws_pnp[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   std::memcpy(hi + o_off, offsets, 4 * (P + 1));
   if (N) std::memcpy(hi + o_p3, pts3d, 24 * N);
   std::memcpy(hi + o_pr, priors_wc, 56 * P);
   if (N) std::memcpy(hi + o_p2, pts2d, 8 * N);
-  uint8_t* di = (uint8_t*)h->ws_pnp[1].p;
-  uint8_t* dout = di + in_bytes;
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   orbx_prof_begin_call(h);
   if (int rc = pnp_launch(h, cam, cfg, n_problems, max_n, (const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2),
                           (const double*)(di + o_pr), (double*)(dout + o_po), dout + o_in, (double*)(dout + o_er),
                           (orbx_pnp_result*)(dout + o_rs)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
   std::memcpy(poses_wc_out, ho + o_po, 56 * P);
   std::memcpy(results, ho + o_rs, sizeof(orbx_pnp_result) * P);
   if (N) { std::memcpy(err_out, ho + o_er, 8 * N); std::memcpy(inlier_out, ho + o_in, N); }

@@ -313,8 +313,6 @@ int pi_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_c
   return ORBX_OK;
 }
 
-size_t pi_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {
@@ -362,29 +360,20 @@ int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_
                           !poses_out || !velocities_out || !biases_out || !results)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
   if (n_problems == 0) return ORBX_OK;
-  if (offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: offsets[0] must be 0");
-  for (int p = 0; p < n_problems; ++p)
-    if (offsets[p + 1] < offsets[p]) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: offsets not ascending at problem %d", p);
+  if (int rc = orbx_check_offsets(h, "orbx_pose_inertial_batch", "offsets", "problem", n_problems, offsets)) return rc;
   const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
   if (N > 0 && (!pts3d || !pts2d || !is_stereo)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [offsets | pts3d | poses | velocities | biases | prev poses | prev velocities | preints | pts2d | is_stereo] up,
   // [poses | velocities | biases | results | inliers] down
-  const size_t o_off = 0, o_p3 = pi_align(o_off + 4 * (P + 1)), o_po = pi_align(o_p3 + 24 * N), o_ve = pi_align(o_po + 56 * P);
-  const size_t o_bi = pi_align(o_ve + 24 * P), o_pp = pi_align(o_bi + 48 * P), o_pv = pi_align(o_pp + 56 * P), o_pr = pi_align(o_pv + 24 * P);
-  const size_t o_p2 = pi_align(o_pr + 88 * P), o_st = pi_align(o_p2 + 8 * N);
-  const size_t in_bytes = pi_align(o_st + N);
-  const size_t d_po = 0, d_ve = pi_align(56 * P), d_bi = pi_align(d_ve + 24 * P), d_rs = pi_align(d_bi + 48 * P);
-  const size_t d_in = pi_align(d_rs + sizeof(orbx_pose_inertial_result) * P);
-  const size_t out_bytes = pi_align(d_in + N);
-  if (h->h_pi_bytes < in_bytes + out_bytes) {
-    if (h->h_pi) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); hipHostFree(h->h_pi); h->h_pi = nullptr; h->h_pi_bytes = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_pi, in_bytes + out_bytes, hipHostMallocDefault));
-    h->h_pi_bytes = in_bytes + out_bytes;
-  }
-  if (int rc = orbx_reserve(h, h->ws_pi, in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_pi;
-  uint8_t* ho = hi + in_bytes;
+  Carve in, out;
+  const size_t o_off = in.take(4 * (P + 1)), o_p3 = in.take(24 * N), o_po = in.take(56 * P), o_ve = in.take(24 * P), o_bi = in.take(48 * P),
+               o_pp = in.take(56 * P), o_pv = in.take(24 * P), o_pr = in.take(88 * P), o_p2 = in.take(8 * N), o_st = in.take(N);
+  const size_t d_po = out.take(56 * P), d_ve = out.take(24 * P), d_bi = out.take(48 * P), d_rs = out.take(sizeof(orbx_pose_inertial_result) * P),
+               d_in = out.take(N);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_pi, h->ws_pi, in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   std::memcpy(hi + o_off, offsets, 4 * (P + 1));
   if (N) std::memcpy(hi + o_p3, pts3d, 24 * N);
   std::memcpy(hi + o_po, poses_wc, 56 * P);
@@ -394,18 +383,14 @@ int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_
   std::memcpy(hi + o_pv, prev_kf_velocities, 24 * P);
   std::memcpy(hi + o_pr, preints, 88 * P);
   if (N) { std::memcpy(hi + o_p2, pts2d, 8 * N); std::memcpy(hi + o_st, is_stereo, N); }
-  uint8_t* di = (uint8_t*)h->ws_pi.p;
-  uint8_t* dout = di + in_bytes;
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   orbx_prof_begin_call(h);
   const PiArgs a{(const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2), di + o_st, (const double*)(di + o_po),
                  (const double*)(di + o_ve), (const double*)(di + o_bi), (const double*)(di + o_pp), (const double*)(di + o_pv),
                  (const double*)(di + o_pr), (double*)(dout + d_po), (double*)(dout + d_ve), (double*)(dout + d_bi), dout + d_in,
                  (orbx_pose_inertial_result*)(dout + d_rs)};
   if (int rc = pi_launch(h, cam, cfg, n_problems, a)) return rc;
-  const size_t down = inlier_out ? out_bytes : d_in;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, down, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, inlier_out ? out.off : d_in)) return rc;   // the inlier flags travel only when asked for
   std::memcpy(poses_out, ho + d_po, 56 * P);
   std::memcpy(velocities_out, ho + d_ve, 24 * P);
   std::memcpy(biases_out, ho + d_bi, 48 * P);

@@ -169,29 +169,25 @@ __global__ __launch_bounds__(TRK_THREADS) void track_finish_kernel(TrackArgs A) 
   }
 }
 
-size_t trk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// what can be refused before anything is enqueued; *max_mp: the most map points of a frame
 int track_check(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* c, const orbx_pnp_config* pnp_cfg, int B, const int* mp_offsets,
-                const char* who) {
+                int* max_mp, const char* who) {
   if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
   if (!cam || !c || (c->mode != 0 && c->mode != 1) || !(c->radius >= 0.0) || !std::isfinite(c->radius) || !(c->img_w > 0.0) ||
       !std::isfinite(c->img_w) || !(c->img_h > 0.0) || !std::isfinite(c->img_h) || c->min_correspondences < 4 || c->min_inliers < 0)
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: configuration out of range (include/orbx.h: orbx_track_config)", who);
   if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
-  if (!mp_offsets) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (mp_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: mp_offsets[0] must be 0", who);
-  for (int b = 0; b < B; ++b)
-    if (mp_offsets[b + 1] < mp_offsets[b]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: mp_offsets not ascending at frame %d", who, b);
-  return ORBX_OK;
+  return orbx_check_offsets(h, who, "mp_offsets", "frame", B, mp_offsets, max_mp);
 }
 
 // The launches on the handle's stream; every pointer is device memory (d_mp_off included: the callers upload it).
 int track_launch(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, int B, int max_mp,
                  size_t M, TrackArgs A, uint8_t* d_inl, double* d_err, orbx_pnp_result* d_pnp) {
   const size_t mf = (size_t)A.max_feat;
-  const size_t o_cs = 0, o_si = trk_align(o_cs + 4 * (size_t)B * (GG_CELLS + 1)), o_ow = trk_align(o_si + 4 * B * mf),
-               o_cn = trk_align(o_ow + 4 * B * mf), o_ma = trk_align(o_cn + 8 * (size_t)B), o_co = trk_align(o_ma + 4 * M);
-  if (int rc = orbx_reserve(h, h->ws_track[0], trk_align(o_co + 2 * B * mf))) return rc;
+  Carve ws;
+  const size_t o_cs = ws.take(4 * (size_t)B * (GG_CELLS + 1)), o_si = ws.take(4 * B * mf), o_ow = ws.take(4 * B * mf), o_cn = ws.take(8 * (size_t)B),
+               o_ma = ws.take(4 * M), o_co = ws.take(2 * B * mf);
+  if (int rc = orbx_reserve(h, h->ws_track[0], ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_track[0].p;
   A.cell_start = (int*)(w + o_cs); A.sorted_idx = (int*)(w + o_si); A.owner = (int*)(w + o_ow); A.counts = (int*)(w + o_cn);
   A.match = (int*)(w + o_ma); A.cell_of = (unsigned short*)(w + o_co);
@@ -243,7 +239,8 @@ int orbx_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_
                              uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_pnp_results, int* d_matched,
                              orbx_track_result* d_results) {
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, mp_offsets, "orbx_track_frames_device")) return rc;
+  int max_mp = 0;
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, mp_offsets, &max_mp, "orbx_track_frames_device")) return rc;
   const int B = n_frames;
   const int M = mp_offsets[B];
   if (max_feat < 0 || feat_count_stride < 1 || !d_feat_start || !d_feat_count || !d_search_poses_wc || !d_priors_wc || !d_offsets || !d_poses_wc_out ||
@@ -251,28 +248,16 @@ int orbx_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_
       (M > 0 && (!d_positions || !d_mp_desc || !d_pts3d || !d_pts2d || !d_mp_idx || !d_feat_idx || !d_inlier_out || !d_err_out)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_track_frames_device: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  int max_mp = 0;
-  for (int b = 0; b < B; ++b) max_mp = std::max(max_mp, mp_offsets[b + 1] - mp_offsets[b]);
-  // mp_offsets goes up from one of two pinned slots, so that the caller's array is free when the call returns; a slot is reused
-  // once the copy that read it has run (its event)
+  // mp_offsets goes up through the upload ring, so that the caller's array is free when the call returns
   const size_t ob = 4 * ((size_t)B + 1);
-  const int slot = h->track_off_next;
-  h->track_off_next ^= 1;
-  if (!h->ev_track_off[slot]) ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_track_off[slot], hipEventDisableTiming));
-  else ORBX_HIP(h, hipEventSynchronize(h->ev_track_off[slot]));
-  if (h->h_track_off_bytes[slot] < ob) {
-    if (h->h_track_off[slot]) { hipHostFree(h->h_track_off[slot]); h->h_track_off[slot] = nullptr; h->h_track_off_bytes[slot] = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_track_off[slot], ob, hipHostMallocDefault));
-    h->h_track_off_bytes[slot] = ob;
-  }
-  std::memcpy(h->h_track_off[slot], mp_offsets, ob);
-  if (int rc = orbx_reserve(h, h->ws_track[2], ob)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_track[2].p, h->h_track_off[slot], ob, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipEventRecord(h->ev_track_off[slot], h->stream));
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_track, h->ws_track[2], ob, &hs, &ds)) return rc;
+  std::memcpy(hs, mp_offsets, ob);
+  if (int rc = orbx_ring_commit(h, h->ring_track, h->ws_track[2], ob)) return rc;
   TrackArgs A{};
   A.max_feat = max_feat; A.fc_stride = feat_count_stride;
   A.kp = d_kp; A.desc = d_desc; A.feat_start = d_feat_start; A.feat_count = d_feat_count;
-  A.positions = d_positions; A.mp_desc = d_mp_desc; A.mp_off = (const int*)h->ws_track[2].p;
+  A.positions = d_positions; A.mp_desc = d_mp_desc; A.mp_off = (const int*)ds;
   A.search_poses = d_search_poses_wc; A.priors = d_priors_wc;
   A.offsets = d_offsets; A.pts3d = d_pts3d; A.pts2d = d_pts2d; A.mp_idx = d_mp_idx; A.feat_idx = d_feat_idx;
   A.poses_out = d_poses_wc_out; A.matched = d_matched; A.results = d_results;
@@ -286,15 +271,10 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
                       int* offsets, double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out,
                       uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched, orbx_track_result* results) {
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, mp_offsets, "orbx_track_frames")) return rc;
-  const size_t B = (size_t)n_frames;
-  if (!feat_offsets || feat_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_track_frames: feat_offsets[0] must be 0");
   int max_feat = 0, max_mp = 0;
-  for (size_t b = 0; b < B; ++b) {
-    if (feat_offsets[b + 1] < feat_offsets[b]) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_track_frames: feat_offsets not ascending at frame %d", (int)b);
-    max_feat = std::max(max_feat, feat_offsets[b + 1] - feat_offsets[b]);
-    max_mp = std::max(max_mp, mp_offsets[b + 1] - mp_offsets[b]);
-  }
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, mp_offsets, &max_mp, "orbx_track_frames")) return rc;
+  if (int rc = orbx_check_offsets(h, "orbx_track_frames", "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
+  const size_t B = (size_t)n_frames;
   const size_t NF = (size_t)feat_offsets[B], M = (size_t)mp_offsets[B], mf = (size_t)max_feat;
   if (!search_poses_wc || !priors_wc || !offsets || !poses_wc_out || !pnp_results || !results || (NF > 0 && (!kp || !desc || !matched)) ||
       (M > 0 && (!positions || !mp_desc || !pts3d || !pts2d || !mp_idx || !feat_idx || !inlier_out || !err_out)))
@@ -302,21 +282,15 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [kp | desc | positions | mp_desc | search poses | priors | feat_start | feat_count | mp_offsets] up,
   // [offsets | pts3d | pts2d | mp_idx | feat_idx | poses | err | pnp records | matched | records | inliers] down
-  const size_t i_kp = 0, i_de = trk_align(i_kp + sizeof(orbx_keypoint) * NF), i_po = trk_align(i_de + 32 * NF), i_md = trk_align(i_po + 24 * M),
-               i_sp = trk_align(i_md + 32 * M), i_pr = trk_align(i_sp + 56 * B), i_fs = trk_align(i_pr + 56 * B), i_fc = trk_align(i_fs + 4 * B),
-               i_mo = trk_align(i_fc + 4 * B), in_bytes = trk_align(i_mo + 4 * (B + 1));
-  const size_t o_of = 0, o_p3 = trk_align(o_of + 4 * (B + 1)), o_p2 = trk_align(o_p3 + 24 * M), o_mi = trk_align(o_p2 + 8 * M),
-               o_fi = trk_align(o_mi + 4 * M), o_ps = trk_align(o_fi + 4 * M), o_er = trk_align(o_ps + 56 * B), o_pn = trk_align(o_er + 8 * M),
-               o_ma = trk_align(o_pn + sizeof(orbx_pnp_result) * B), o_rs = trk_align(o_ma + 4 * B * mf),
-               o_in = trk_align(o_rs + sizeof(orbx_track_result) * B), out_bytes = trk_align(o_in + M);
-  if (h->h_track_bytes < in_bytes + out_bytes) {
-    if (h->h_track) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); hipHostFree(h->h_track); h->h_track = nullptr; h->h_track_bytes = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_track, in_bytes + out_bytes, hipHostMallocDefault));
-    h->h_track_bytes = in_bytes + out_bytes;
-  }
-  if (int rc = orbx_reserve(h, h->ws_track[1], in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_track;
-  uint8_t* ho = hi + in_bytes;
+  Carve in, out;
+  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_po = in.take(24 * M), i_md = in.take(32 * M),
+               i_sp = in.take(56 * B), i_pr = in.take(56 * B), i_fs = in.take(4 * B), i_fc = in.take(4 * B), i_mo = in.take(4 * (B + 1));
+  const size_t o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * M), o_p2 = out.take(8 * M), o_mi = out.take(4 * M), o_fi = out.take(4 * M),
+               o_ps = out.take(56 * B), o_er = out.take(8 * M), o_pn = out.take(sizeof(orbx_pnp_result) * B), o_ma = out.take(4 * B * mf),
+               o_rs = out.take(sizeof(orbx_track_result) * B), o_in = out.take(M);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_track, h->ws_track[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
   if (M) { std::memcpy(hi + i_po, positions, 24 * M); std::memcpy(hi + i_md, mp_desc, 32 * M); }
   std::memcpy(hi + i_sp, search_poses_wc, 56 * B);
@@ -326,9 +300,7 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
     ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
   }
   std::memcpy(hi + i_mo, mp_offsets, 4 * (B + 1));
-  uint8_t* di = (uint8_t*)h->ws_track[1].p;
-  uint8_t* dout = di + in_bytes;
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   TrackArgs A{};
   A.max_feat = max_feat; A.fc_stride = 1;
   A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
@@ -340,8 +312,7 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
   orbx_prof_begin_call(h);
   if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
   std::memcpy(offsets, ho + o_of, 4 * (B + 1));
   std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
   std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);

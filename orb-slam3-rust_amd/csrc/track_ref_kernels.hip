@@ -199,8 +199,6 @@ __global__ __launch_bounds__(64) void tref_finish_kernel(TrefArgs A, int B) {
   }
 }
 
-size_t tref_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // what can be refused before anything is enqueued
 int tref_check(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_corr, int B, const char* who) {
   if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
@@ -210,20 +208,13 @@ int tref_check(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pn
   return ORBX_OK;
 }
 
-int tref_check_offsets(orbx_handle* h, int B, const int* off, const char* name, const char* who) {
-  if (!off) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (off[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s[0] must be 0", who, name);
-  for (int b = 0; b < B; ++b)
-    if (off[b + 1] < off[b]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s not ascending at frame %d", who, name, b);
-  return ORBX_OK;
-}
-
 // The launches on the handle's stream; every pointer of A is device memory.
 int tref_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int B, int max_kf, size_t K, TrefArgs A, uint8_t* d_inl,
                 double* d_err, orbx_pnp_result* d_pnp) {
   const size_t mf = (size_t)A.max_feat;
-  const size_t o_col = 0, o_row = tref_align(o_col + 8 * (size_t)B * mf), o_pairs = tref_align(o_row + 4 * K), o_cnt = tref_align(o_pairs + 8 * K);
-  if (int rc = orbx_reserve(h, h->ws_tref[0], tref_align(o_cnt + 8 * (size_t)B))) return rc;
+  Carve ws;
+  const size_t o_col = ws.take(8 * (size_t)B * mf), o_row = ws.take(4 * K), o_pairs = ws.take(8 * K), o_cnt = ws.take(8 * (size_t)B);
+  if (int rc = orbx_reserve(h, h->ws_tref[0], ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_tref[0].p;
   A.col_best = (unsigned long long*)(w + o_col); A.row_best = (unsigned*)(w + o_row); A.pairs = (int*)(w + o_pairs); A.counts = (int*)(w + o_cnt);
   A.pnp_res = d_pnp;
@@ -270,26 +261,15 @@ int track_reference_enqueue(orbx_handle* h, const char* who, const orbx_camera* 
       (K > 0 && (!positions || !valid || !d_matches || !d_pts3d || !d_pts2d || !d_kf_idx || !d_feat_idx || !d_inlier_out || !d_err_out)))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (max_feat <= %d)", who, TREF_MAX_FEAT);
   ORBX_HIP(h, hipSetDevice(h->device));
-  // the item table (and host-side positions / valid) go up from one of two pinned slots, so that the caller's arrays are free when
-  // the call returns; a slot is reused once the copy that read it has run (its event)
-  const size_t o_it = 0, o_pos = tref_align(o_it + sizeof(TrackRefItem) * (size_t)B), o_val = tref_align(o_pos + (pos_on_host ? 24 * K : 0)),
-               bytes = tref_align(o_val + (pos_on_host ? K : 0));
-  const int slot = h->tref_items_next;
-  h->tref_items_next ^= 1;
-  if (!h->ev_tref_items[slot]) ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_tref_items[slot], hipEventDisableTiming));
-  else ORBX_HIP(h, hipEventSynchronize(h->ev_tref_items[slot]));
-  if (h->h_tref_items_bytes[slot] < bytes) {
-    if (h->h_tref_items[slot]) { hipHostFree(h->h_tref_items[slot]); h->h_tref_items[slot] = nullptr; h->h_tref_items_bytes[slot] = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_tref_items[slot], bytes, hipHostMallocDefault));
-    h->h_tref_items_bytes[slot] = bytes;
-  }
-  uint8_t* hs = (uint8_t*)h->h_tref_items[slot];
+  // the item table (and host-side positions / valid) go up through the upload ring, so that the caller's arrays are free when the
+  // call returns
+  Carve up;
+  const size_t o_it = up.take(sizeof(TrackRefItem) * (size_t)B), o_pos = up.take(pos_on_host ? 24 * K : 0), o_val = up.take(pos_on_host ? K : 0);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_tref, h->ws_tref[2], up.off, &hs, &ds)) return rc;
   std::memcpy(hs + o_it, items, sizeof(TrackRefItem) * (size_t)B);
   if (pos_on_host && K) { std::memcpy(hs + o_pos, positions, 24 * K); std::memcpy(hs + o_val, valid, K); }
-  if (int rc = orbx_reserve(h, h->ws_tref[2], bytes)) return rc;
-  uint8_t* ds = (uint8_t*)h->ws_tref[2].p;
-  ORBX_HIP(h, hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipEventRecord(h->ev_tref_items[slot], h->stream));
+  if (int rc = orbx_ring_commit(h, h->ring_tref, h->ws_tref[2], up.off)) return rc;
   TrefArgs A{};
   A.min_corr = min_correspondences; A.max_feat = max_feat; A.fc_stride = feat_count_stride;
   A.kp = d_kp; A.desc = d_desc; A.feat_start = d_feat_start; A.feat_count = d_feat_count;
@@ -316,7 +296,7 @@ int orbx_track_reference_device(orbx_handle* h, const orbx_camera* cam, const or
   if (!h) return ORBX_ERR_INVALID;
   if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
   if (n_frames == 0) return ORBX_OK;
-  if (int rc = tref_check_offsets(h, n_frames, kf_offsets, "kf_offsets", who)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets)) return rc;
   if (kf_offsets[n_frames] > 0 && !d_kf_desc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   std::vector<TrackRefItem> items((size_t)n_frames);
   for (int b = 0; b < n_frames; ++b) {
@@ -339,14 +319,10 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
   if (!h) return ORBX_ERR_INVALID;
   if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
   if (n_frames == 0) return ORBX_OK;
-  if (int rc = tref_check_offsets(h, n_frames, kf_offsets, "kf_offsets", who)) return rc;
-  if (int rc = tref_check_offsets(h, n_frames, feat_offsets, "feat_offsets", who)) return rc;
-  const size_t B = (size_t)n_frames;
   int max_feat = 0, max_kf = 0;
-  for (size_t b = 0; b < B; ++b) {
-    max_feat = std::max(max_feat, feat_offsets[b + 1] - feat_offsets[b]);
-    max_kf = std::max(max_kf, kf_offsets[b + 1] - kf_offsets[b]);
-  }
+  if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets, &max_kf)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
+  const size_t B = (size_t)n_frames;
   const size_t NF = (size_t)feat_offsets[B], K = (size_t)kf_offsets[B];
   if (max_feat > TREF_MAX_FEAT || !priors_wc || !offsets || !poses_wc_out || !pnp_results || !results || (NF > 0 && (!kp || !desc)) ||
       (K > 0 && (!kf_desc || !kf_positions || !kf_valid || !matches || !pts3d || !pts2d || !kf_idx || !feat_idx || !inlier_out || !err_out)))
@@ -354,23 +330,15 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
   ORBX_HIP(h, hipSetDevice(h->device));
   // one blob each way: [kp | desc | keyframe desc | positions | valid | priors | feat_start | feat_count | items] up,
   // [offsets | pts3d | pts2d | kf_idx | feat_idx | poses | err | pnp records | records | matches | inliers] down
-  const size_t i_kp = 0, i_de = tref_align(i_kp + sizeof(orbx_keypoint) * NF), i_kd = tref_align(i_de + 32 * NF), i_po = tref_align(i_kd + 32 * K),
-               i_va = tref_align(i_po + 24 * K), i_pr = tref_align(i_va + K), i_fs = tref_align(i_pr + 56 * B), i_fc = tref_align(i_fs + 4 * B),
-               i_it = tref_align(i_fc + 4 * B), in_bytes = tref_align(i_it + sizeof(TrackRefItem) * B);
-  const size_t o_of = 0, o_p3 = tref_align(o_of + 4 * (B + 1)), o_p2 = tref_align(o_p3 + 24 * K), o_ki = tref_align(o_p2 + 8 * K),
-               o_fi = tref_align(o_ki + 4 * K), o_ps = tref_align(o_fi + 4 * K), o_er = tref_align(o_ps + 56 * B), o_pn = tref_align(o_er + 8 * K),
-               o_rs = tref_align(o_pn + sizeof(orbx_pnp_result) * B), o_ma = tref_align(o_rs + sizeof(orbx_track_ref_result) * B),
-               o_in = tref_align(o_ma + sizeof(orbx_dmatch) * K), out_bytes = tref_align(o_in + K);
-  if (h->h_tref_bytes < in_bytes + out_bytes) {
-    if (h->h_tref) { ORBX_HIP(h, hipStreamSynchronize(h->stream)); hipHostFree(h->h_tref); h->h_tref = nullptr; h->h_tref_bytes = 0; }
-    ORBX_HIP(h, hipHostMalloc(&h->h_tref, in_bytes + out_bytes, hipHostMallocDefault));
-    h->h_tref_bytes = in_bytes + out_bytes;
-  }
-  if (int rc = orbx_reserve(h, h->ws_tref[1], in_bytes + out_bytes)) return rc;
-  uint8_t* hi = (uint8_t*)h->h_tref;
-  uint8_t* ho = hi + in_bytes;
-  uint8_t* di = (uint8_t*)h->ws_tref[1].p;
-  uint8_t* dout = di + in_bytes;
+  Carve in, out;
+  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_kd = in.take(32 * K), i_po = in.take(24 * K), i_va = in.take(K),
+               i_pr = in.take(56 * B), i_fs = in.take(4 * B), i_fc = in.take(4 * B), i_it = in.take(sizeof(TrackRefItem) * B);
+  const size_t o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * K), o_p2 = out.take(8 * K), o_ki = out.take(4 * K), o_fi = out.take(4 * K),
+               o_ps = out.take(56 * B), o_er = out.take(8 * K), o_pn = out.take(sizeof(orbx_pnp_result) * B),
+               o_rs = out.take(sizeof(orbx_track_ref_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * K), o_in = out.take(K);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_tref, h->ws_tref[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
   if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
   if (K) { std::memcpy(hi + i_kd, kf_desc, 32 * K); std::memcpy(hi + i_po, kf_positions, 24 * K); std::memcpy(hi + i_va, kf_valid, K); }
   std::memcpy(hi + i_pr, priors_wc, 56 * B);
@@ -381,7 +349,7 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
     it.kf_desc = di + i_kd + 32 * (size_t)kf_offsets[b]; it.kf_off = kf_offsets[b]; it.n = kf_offsets[b + 1] - kf_offsets[b];
     ((TrackRefItem*)(hi + i_it))[b] = it;
   }
-  ORBX_HIP(h, hipMemcpyAsync(di, hi, in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
   TrefArgs A{};
   A.min_corr = min_correspondences; A.max_feat = max_feat; A.fc_stride = 1;
   A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
@@ -391,8 +359,7 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
   A.results = (orbx_track_ref_result*)(dout + o_rs);
   orbx_prof_begin_call(h);
   if (int rc = tref_launch(h, cam, pnp_cfg, n_frames, max_kf, K, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn))) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
   std::memcpy(offsets, ho + o_of, 4 * (B + 1));
   std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
   std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
