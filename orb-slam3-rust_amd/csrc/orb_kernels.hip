@@ -542,7 +542,8 @@ constexpr int FAST_CHAIN = ORBX_FAST_CHAIN;   // tiles per block
 constexpr int FAST_ST_RPP = FT_THREADS / 9;                                   // rows staged per pass: 9 lanes x 8 bytes per 72-byte row
 constexpr int FAST_ST_PASS = (FP_ROWS + FAST_ST_RPP - 1) / FAST_ST_RPP;       // passes (one 8-byte register per pass and thread)
 constexpr int FAST_LIST_CAP = ((FT_W + 1) / 2) * ((FT_H + 1) / 2);            // 3x3-NMS survivors of a tile: at most one per 2x2 positions
-constexpr int FAST_LDS_BYTES = FP_ROWS * FP_PITCH + FS_H * FS_W + 2 * FS_W * FS_H + 4 * (FAST_LIST_CAP + 1) + 12;
+constexpr int FAST_POS_HALF = FS_W * FS_H / 2;                                // survivors beside which s_pos still holds the corner list (counted down from its top)
+constexpr int FAST_LDS_BYTES = FP_ROWS * FP_PITCH + FS_H * FS_W + 2 * FS_W * FS_H + 4 * (FAST_LIST_CAP + 1) + 16;
 static_assert(FT_W == 62 && FS_W == 64, "a position is stored as j * 64 + i and split by >> 6 / & 63; a task is 16 positions of a 64-wide row");
 static_assert(FT_THREADS % 64 == 0 && FT_THREADS >= 128 && FT_THREADS <= 1024, "whole waves; the wave-level scans and ballots assume full waves");
 static_assert(FT_H >= 8 && FT_H % 2 == 0 && FT_H <= 126, "tile height: even (2x2 NMS bound), score rows j < 128 so that j * 64 + i fits the 16-bit list");
@@ -652,7 +653,7 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
   __shared__ __attribute__((aligned(16))) uint8_t ss[FS_H][FS_W];
   __shared__ __attribute__((aligned(4))) unsigned short s_pos[FS_W * FS_H];
   __shared__ unsigned s_list[FAST_LIST_CAP + 1];   // NMS survivors: at most one per 2x2 positions
-  __shared__ int s_npos, s_cnt;
+  __shared__ int s_npos, s_cnt, s_ncor;
   __shared__ unsigned s_base;
   // A block works through FAST_CHAIN consecutive tiles of one image and loads the NEXT tile's pixels into registers while it works
   // on the current one: with one tile per block the chain  kernel arguments -> tile table -> pixels  (about 2 us) is exposed in
@@ -716,7 +717,7 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
   if (tid == 0) s_cnt = 0;
   for (int tile = tile0; tile < tile_end; ++tile) {
   const int img = cur.img, l = cur.l, x0 = cur.x0, y0 = cur.y0, w = cur.w, h = cur.h, aw = cur.aw, ah = cur.ah;
-  if (tid == 0) s_npos = 0;
+  if (tid == 0) { s_npos = 0; s_ncor = 0; }
   const int qpr = (aw + 3) >> 2;                                   // 4-position tasks per row, 1..16
   const int ntask = qpr * ah;
   const unsigned inv = (unsigned)(65536.f / (float)qpr) + 1u;      // task / qpr = (task * inv) >> 16, exact for task < 512
@@ -824,7 +825,11 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
   __syncthreads();
   const int npos = s_npos;
   if (acc_cnt > 0 && (acc_il != img * g.n_levels + l || acc_cnt + min(npos, FAST_LIST_CAP) > FAST_LIST_CAP)) append();
-  // phase 2: full score of the pre-test survivors
+  // phase 2: full score of the pre-test survivors.  The positions that score above zero inside the tile and the border-filtered region (two in
+  // five of the survivors on the bench's scenes — the pre-test also passes every straight edge) are listed a second time, block-wide, from the top of s_pos
+  // downwards: one ballot and one returning LDS add per wave round.  A tile whose survivors fill more than half of s_pos has no room for that
+  // list and keeps phase 3 over the survivors (block-uniform).
+  const bool corner_list = npos <= FAST_POS_HALF;
   for (int q = tid; q < npos; q += FT_THREADS) {
     const int p = s_pos[q], j = p >> 6, i = p & 63;
     const int cy = j + 3, cx = i + 4;
@@ -859,15 +864,43 @@ __global__ __launch_bounds__(FT_THREADS) void fast_kernel(OrbSrc s, OrbGeom g, i
 #endif
     const int sc = b > t ? b - 1 : 0;
     ss[j][i] = (uint8_t)sc;
+    if (corner_list) {
+      // i >= 1 && i <= FT_W && x < w - EDGE  <=>  0 <= i - 1 < aw - 2 (aw - 2 = min(FT_W, w - EDGE - x0)), rows likewise: two unsigned compares
+      const bool in = sc > 0 && (unsigned)(i - 1) < (unsigned)(aw - 2) && (unsigned)(j - 1) < (unsigned)(ah - 2);
+      const unsigned long long bal = __ballot(in);
+      if (bal) {                                                     // wave-uniform; lane 0 has the round's smallest q: it is active
+        int base = 0;
+        if (lane == 0) base = lds_add_rtn(&s_ncor, __popcll(bal));
+        const int k = __builtin_amdgcn_readfirstlane(base) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+        if (in) s_pos[FS_W * FS_H - 1 - k] = (unsigned short)p;      // (k < npos <= half of s_pos: above every survivor entry)
+      }
+    }
   }
   __syncthreads();
-  // (A block-wide CORNER LIST — phase 2 lists the positions that score above zero inside the tile a second time, downwards from the top of s_pos,
-  // by one ballot and one returning LDS add per wave round; phase 3 walks that list densely and aggregates its appends per wave round — was built,
-  // bit-exact (439 tests): fast_kernel 0.8989-0.8997 -> 0.8823-0.8845 ms per 512 pairs in every one of nine alternations, but 70 VGPRs instead of
-  // 65, and the step's gain (+0.15 to +0.8 % frames/s) stayed inside twice the spread of two runs of one build.  Withdrawn:
-  // profiles/r06_fast_survivor_phases.txt.)
-  // phase 3: NMS (strictly greater than the 8 neighbours) + runByImageBorder, over the same list: corners inside the tile and the
-  // border-filtered region (a few per cent of the survivors — the pre-test also passes every straight edge)
+  // phase 3: NMS (strictly greater than the 8 neighbours) + runByImageBorder.  Over the corner list, densely, the appends to s_list aggregated
+  // per wave round (ballot, mbcnt, one returning LDS add) — profiles/r06_fast_survivor_phases.txt (c), profiles/r07_describe_shared_orientation.txt
+  if (corner_list) {
+    const int ncor = s_ncor;
+    for (int q = tid; q < ncor; q += FT_THREADS) {
+      const int p = s_pos[FS_W * FS_H - 1 - q];
+      const int j = p >> 6, i = p & 63;
+      const int sc = ss[j][i];
+      const int m = max(max(max((int)ss[j - 1][i - 1], (int)ss[j - 1][i]), max((int)ss[j - 1][i + 1], (int)ss[j][i - 1])),
+                        max(max((int)ss[j][i + 1], (int)ss[j + 1][i - 1]), max((int)ss[j + 1][i], (int)ss[j + 1][i + 1])));
+      const bool keep = sc > m;
+      const unsigned long long bal = __ballot(keep);
+      if (bal) {
+        int base = 0;
+        if (lane == 0) base = lds_add_rtn(&s_cnt, __popcll(bal));
+        const int pos = __builtin_amdgcn_readfirstlane(base) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+        if (keep) {
+          if (pos < FAST_LIST_CAP) s_list[pos] = ((unsigned)sc << 24) | ((unsigned)(y0 + j - 1) << 12) | (unsigned)(x0 + i - 1);
+          else atomicOr(status, ORBX_ST_INTERNAL);  // (cannot happen: strict maxima of a 62 x FT_H tile are at most one per 2x2)
+        }
+      }
+    }
+  } else
+  // the same over the survivor list: corners inside the tile and the border-filtered region
   for (int q = tid; q < npos; q += FT_THREADS) {
     const int p = s_pos[q];
     const int j = p >> 6, i = p & 63;
@@ -1677,9 +1710,11 @@ __global__ __launch_bounds__(256) void describe_fused_kernel(OrbSrc s, OrbGeom g
 //      as the per-keypoint form: a window is 64 rows x 64 bytes of the level read straight from global memory as the A operands
 //      (row 16 mb + m, bytes 16 q .. 16 q + 15: no staging) and yields 48 x 48 blurred pixels (30 MFMAs); windows sit 48 apart, the last one
 //      of a row / column pulled back inside the level (it then repeats pixels of its neighbour: same integers);
-//   2. walks the tile's keypoints in chunks of 16 per wave: intensity centroids from the level (global loads: the level's bytes are not staged) four
-//      keypoints per round, ONE evaluation of the angle and its sin / cos for the chunk, then the 256 tests on the LDS tile at
-//      (kx - ox + dx) * DT_PITCH + (ky - oy + dy) two keypoints per round, 32 lanes each, a lane's eight tests in registers as floats.
+//   2. walks the tile's keypoints in evaluation rounds of 64: intensity centroids from the level (global loads: the level's bytes are not staged) four
+//      keypoints per wave round, into a 16-byte LDS record per keypoint; ONE wave evaluates the angle and its f64 sin / cos, one lane per keypoint
+//      (once per tile of up to 64 keypoints, where every wave used to spend a whole 64-lane evaluation on its 8-12 keypoints), and leaves
+//      (cos, sin, tile offset, output slot) in the record; then the 256 tests on the LDS tile at (kx - ox + dx) * DT_PITCH + (ky - oy + dy),
+//      two keypoints per wave round, 32 lanes each, a lane's eight tests in registers as floats.
 // Same integers as the per-keypoint blur and as the whole-level specification (A.8), so the descriptors are bit-identical; tiles without
 // keypoints return at once.  Levels too small for a 64 x 64 window use describe_fused_kernel (g.dt_total == 0).
 #ifndef ORBX_DT_NWX
@@ -1702,6 +1737,7 @@ constexpr int DT_TILE_BYTES = DT_PITCH * DT_COLS;
 constexpr int DT_TW_MAX = 48 * DT_NWX - 39;
 constexpr int DT_TH_MAX = 48 * DT_NWY - 39;
 static_assert(DT_NWX >= 1 && DT_NWY >= 1 && DT_TILE_BYTES + 3072 <= 65536, "LDS per workgroup");
+constexpr int DT_EVAL = 64;                       // keypoints per evaluation round: one lane of one wave each
 __constant__ __attribute__((aligned(16))) unsigned c_blur_band_t[6 * 64 * 4];   // T1 for output-column block 0..2, T2 for output-row block 0..2 (64 real k-slots)
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void describe_tile_kernel(OrbSrc s, OrbGeom g, int n_img, XcdMap xm, const unsigned* __restrict__ tile_tab,
@@ -1712,13 +1748,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                             orbx_keypoint* __restrict__ kp_out, uint8_t* __restrict__ desc_out,
                                                             int* __restrict__ nkp, int cap_kp, float patch_size,
                                                             unsigned* __restrict__ status) {
-  __shared__ __attribute__((aligned(16))) unsigned char s_tile[DT_TILE_BYTES + 3 * 1024];
-  int* s_pat = reinterpret_cast<int*>(s_tile + DT_TILE_BYTES + 2048);
+  // behind the tile: the two centroid weight tables and the keypoint records of one evaluation round (DT_EVAL x 16 bytes)
+  __shared__ __attribute__((aligned(16))) unsigned char s_tile[DT_TILE_BYTES + 2 * 1024 + DT_EVAL * 16];
+  static_assert(sizeof(s_tile) <= 40960, "four workgroups per CU (160 KB of LDS)");
+  df_i4* s_rec = reinterpret_cast<df_i4*>(s_tile + DT_TILE_BYTES + 2048);
   unsigned* s_ones = reinterpret_cast<unsigned*>(s_tile + DT_TILE_BYTES);
   unsigned* s_col = s_ones + 256;
   int img, tile;
   if (!xcd_decode(xm, n_img, img, tile)) return;
   const int tid = threadIdx.x, lane = tid & 63;
+  const unsigned t_ones = c_ic_ones[tid], t_col = c_ic_col[tid];   // (first in the load queue: the LDS tables wait for nothing else)
   int l, tx, ty;
   decode_tile(tile_tab, tile, l, tx, ty);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1767,19 +1806,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const uint2 rng = tile_rng[(size_t)img * (size_t)g.dt_total + tile];
   const unsigned n_kp = rng.y - rng.x;
   if (n_kp == 0) return;
-  s_pat[tid] = reinterpret_cast<const int*>(c_pattern)[tid];
-  s_ones[tid] = c_ic_ones[tid];
-  s_col[tid] = c_ic_col[tid];
+  s_ones[tid] = t_ones;
+  s_col[tid] = t_col;
   const int grp = lane >> 4, li = lane & 15;
   const size_t lofs = (size_t)img * g.cand_total + g.lv[l].cand_off;
-  const unsigned ngrp = (n_kp + DG_PER_WAVE - 1) / DG_PER_WAVE;
   const unsigned long long* sp0 = spatial + lofs + rng.x;
-  auto entry = [&](unsigned gi) {
-    const unsigned pos_raw = gi * DG_PER_WAVE + (unsigned)grp;
-    return sp0[pos_raw < n_kp ? pos_raw : (gi < ngrp ? gi * DG_PER_WAVE : 0u)];   // idle groups shadow the wave's first keypoint
+  // The tile's keypoints go through in evaluation rounds of DT_EVAL (keypoint k of a round = LDS record k).  Inside a round the keypoints are dealt
+  // to the waves in pairs, round-robin: wave w owns the records k with (k >> 1) & 3 == w, for the centroids (four per wave round, 16 lanes each:
+  // group grp of chunk c has record 16 c + kl0) and for the tests (two per wave round) alike — so only the owner touches a record between the
+  // second barrier of a round and the first one of the next.
+  const unsigned kl0 = 2u * (unsigned)wave + 8u * (unsigned)(grp >> 1) + (unsigned)(grp & 1);
+  auto entry = [&](unsigned base, unsigned c) {               // (the centroids need the position only: the entry's low half)
+    const unsigned k = base + 16u * c + kl0;
+    return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(sp0) + 8u * (k < n_kp ? k : base));   // idle groups shadow the round's first keypoint (uniform base + 32-bit lane offset)
   };
-  unsigned long long ent = entry((unsigned)wave), ent_n = entry((unsigned)wave + 4u);   // (requested here: they arrive under the blur)
-  const unsigned long long ent_2 = entry((unsigned)wave + 8u), ent_3 = entry((unsigned)wave + 12u);
+  auto entry_eval = [&](unsigned base) {
+    return *reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(sp0) + 8u * (base + (unsigned)lane < n_kp ? base + (unsigned)lane : base));
+  };
+  // (requested here: they arrive under the blur)
+  unsigned e0 = entry(0u, 0u), e1 = entry(0u, 1u);
+  __syncthreads();                                            // the weight tables: the centroids are taken before the tile's barrier
   // ---- 1. the blurred rectangle, one 64 x 64 window per wave and round
   {
     // (s_setprio 1 / 3 for the blur phase, 0 for the keypoint phase: 1.07 against 1.047 ms per 512 pairs — profiles/r05_describe_tile_steps.txt)
@@ -1819,17 +1865,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
     }
   }
-  __syncthreads();
-  // ---- 2. the tile's keypoints, four per wave and round (16 lanes each)
-  // Two keypoint groups ahead: the list entry of group gi + 8 and the centroid pixels of group gi + 4 are requested while group gi is worked on
-  // (list entry -> pixels -> arithmetic is two dependent round trips to L2 per group otherwise, with four waves per SIMD to hide them).
+  // ---- 2. the tile's keypoints.  The centroids come BEFORE the tile's barrier (they read the level, not the tile), four per wave and round (16 lanes each)
+  // One keypoint group ahead: the centroid pixels of the next group are requested while a group is worked on (the list entries came under the blur).
   // Intensity centroid over the 749-pixel disc straight from the level image (integer, order independent): lane li takes rows
   // 4 it + (li >> 2), dwords 2 (li & 3) and 2 (li & 3) + 1 of the row as ONE 8-byte load (row 31 does not exist: zero weights, re-reads row 30)
   const unsigned astep = 4u * (unsigned)pitch;
   // (each 8-byte piece as ONE 12-byte load on a 4-byte boundary, shifted into place by two v_alignbyte_b32: loads at odd addresses go through
   // the address path lane by lane — 0.065 of this kernel's 0.55 ms per 256 pairs; ORBX_DT_CENTROID_UNALIGNED keeps the 8-byte form for A/B builds)
   struct alignas(4) Row12 { unsigned d[3]; };
-  auto pixels = [&](unsigned long long e, unsigned long long (&px)[8]) {
+  auto pixels = [&](unsigned e, unsigned long long (&px)[8]) {
     const int kx = (int)(e & 0xffffu), ky = (int)((e >> 16) & 0xffffu);
 #ifdef ORBX_DT_CENTROID_UNALIGNED
     const uint8_t* a0 = src + (unsigned)(__umul24((unsigned)(ky - 15 + (li >> 2)), (unsigned)pitch) + (unsigned)(kx - 15 + 8 * (li & 3)));
@@ -1854,13 +1898,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                ((unsigned long long)__builtin_amdgcn_alignbyte(rw[it].d[2], rw[it].d[1], sh) << 32);
 #endif
   };
-  // Chunks of 16 keypoints per wave:
-  //  (a) the centroid sums, four keypoints per round (16 lanes each), every group's sums of round k kept by its lane k;
-  //  (b) ONE evaluation of the angle and its f64 sin / cos for the chunk (lanes 0..3 of each group), and the keypoint records from those lanes;
-  //  (c) the 256 tests, two keypoints per round (32 lanes each): a lane keeps its eight tests — test 8 l + r, the lane's own descriptor byte —
-  //      in registers as floats (32 VGPRs, read from the LDS byte table and converted ONCE per chunk: not live under the centroid's loads; the
-  //      same floats from a global table cost 0.97 against 0.895 ms per 512 pairs — a chunk's first round waits for them) and shifts the sign
-  //      of t0 - t1 into its byte: no conversions, no pattern reads and no ballot inside the rounds.
+  // An evaluation round of up to DT_EVAL keypoints:
+  //  (a) every wave: the centroid sums of its keypoints, (m10, m01) into the keypoint's record;                         -- barrier --
+  //  (b) ONE wave (round R: wave R & 3), one lane per keypoint: the angle and its f64 sin / cos ONCE per keypoint, the keypoint's output record,
+  //      and (cos, sin, tile byte offset, output slot) into the keypoint's record;                                       -- barrier --
+  //  (c) every wave: the 256 tests of its keypoints, two per round (32 lanes each), the round's record as ONE broadcast 16-byte LDS read.  A
+  //      lane keeps its eight tests — test 8 l + r, the lane's own descriptor byte — in registers as floats (32 VGPRs, converted once per
+  //      evaluation round from 8 packed dwords that were requested before the barriers: not live under the centroid's loads) and shifts
+  //      the sign of t0 - t1 into its byte: no conversions, no pattern reads and no ballot inside the rounds.
   typedef float desc_f4 __attribute__((ext_vector_type(4)));
   auto centroid = [&](const unsigned long long (&px)[8], int& m10, int& m01) {
     int sA = 0, sB = 0, sC = 0;
@@ -1880,96 +1925,111 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     m10 = sA - 15 * sB; m01 = sC;
   };
   const int l32 = lane & 31, hf = lane >> 5;
-  unsigned long long e0 = ent, e1 = ent_n, e2 = ent_2, e3 = ent_3;
-  for (unsigned g0 = (unsigned)wave; g0 < ngrp; g0 += 16) {
-    int sel10, sel01;
-    {
+  uint8_t* desc_img = desc_out + (size_t)img * cap_kp * 32;
+  unsigned e2 = entry(0u, 2u), e3 = entry(0u, 3u);           // (not held under the blur: they arrive under the first centroids)
+  for (unsigned base = 0, R = 0; base < n_kp; base += DT_EVAL, ++R) {
+    const unsigned cnt = min((unsigned)DT_EVAL, n_kp - base), w2 = 2u * (unsigned)wave;
+    const bool evaluates = (unsigned)wave == (R & 3u);
+    unsigned long long es = 0;                                // the evaluating wave's list entries, one keypoint per lane
+    if (evaluates) es = entry_eval(base);
+    // (a) chunk c holds the wave's keypoints w2 + 16 c (+ 1, + 8, + 9) of the round
+    if (w2 < cnt) {
       unsigned long long pxa[8], pxb[8];
       int m10, m01;
+      auto put = [&](unsigned c) { if (li == 0) *reinterpret_cast<int2*>(&s_rec[16u * c + kl0]) = int2{m10, m01}; };
       pixels(e0, pxa);
-      if (g0 + 4 < ngrp) pixels(e1, pxb);
+      if (w2 + 16u < cnt) pixels(e1, pxb);
       centroid(pxa, m10, m01);
-      sel10 = m10; sel01 = m01;                                // (lane 0 of the group is what matters of round 0; lanes 1..3 are overwritten or unused)
-      if (g0 + 4 < ngrp) {
-        if (g0 + 8 < ngrp) pixels(e2, pxa);
+      put(0u);
+      if (w2 + 16u < cnt) {
+        if (w2 + 32u < cnt) pixels(e2, pxa);
         centroid(pxb, m10, m01);
-        if (li == 1) { sel10 = m10; sel01 = m01; }
-        if (g0 + 8 < ngrp) {
-          if (g0 + 12 < ngrp) pixels(e3, pxb);
+        put(1u);
+        if (w2 + 32u < cnt) {
+          if (w2 + 48u < cnt) pixels(e3, pxb);
           centroid(pxa, m10, m01);
-          if (li == 2) { sel10 = m10; sel01 = m01; }
-          if (g0 + 12 < ngrp) {
+          put(2u);
+          if (w2 + 48u < cnt) {
             centroid(pxb, m10, m01);
-            if (li == 3) { sel10 = m10; sel01 = m01; }
+            put(3u);
           }
         }
       }
     }
-    // the lane's tests (the index goes through an empty asm so that the reads and conversions stay inside the chunk loop)
-    int pidx = 8 * l32;
+    // the lane's tests as packed bytes, the evaluating wave's responses and the next round's first list entries travel under the barriers
+    // (the index goes through an empty asm so that the loads and the conversions stay inside the round: 32 floats must not live under the centroids)
+    int pidx = 2 * l32;
     asm volatile("" : "+v"(pidx));
-    desc_f4 pat[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int pr = s_pat[pidx + r];
-      pat[r] = (desc_f4){(float)(signed char)(pr & 0xff), (float)(signed char)((pr >> 16) & 0xff), (float)(signed char)((pr >> 8) & 0xff), (float)(signed char)((pr >> 24) & 0xff)};
-    }
-    // (b) lane k < 4 of group grp stands for the keypoint of round k of that group
-    const unsigned long long es = li == 1 ? e1 : li == 2 ? e2 : li == 3 ? e3 : e0;
-    const unsigned j2_s = (unsigned)(es >> 32) & 0xffffu;
-    const unsigned gi_s = g0 + 4u * (unsigned)(li & 3);
-    const int kx_s = (int)(es & 0xffffu), ky_s = (int)((es >> 16) & 0xffffu);
-    const unsigned slot_s = lbase + j2_s;
-    const bool active_s = li < 4 && gi_s < ngrp && gi_s * DG_PER_WAVE + (unsigned)grp < n_kp && slot_s < limit;
-    const float resp = from_orderable(~(unsigned)(sel2[lofs + j2_s] >> 32));   // only needed for the output record
-    // the next chunk's list entries travel under the tests
-    const unsigned long long n0 = entry(g0 + 16u), n1 = entry(g0 + 20u);
-    const float angle16 = fast_atan2_deg((float)sel01, (float)sel10);
-    float ca16, sa16;
-    sincos_deg(angle16, ca16, sa16);
-    // byte (kx - (ox + 3) + col) * DT_PITCH + (ky - (oy + 3) + row) of the column-major tile from the raw float bits: the 24-bit multiply sees
-    // 0x400000 + col, the row term carries the whole 0x4B400000 + row
-    constexpr unsigned kBias = 0x400000u * DT_PITCH + 0x4B400000u;
-    const unsigned kbase16 = (unsigned)((kx_s - (ox + 3)) * DT_PITCH + (ky_s - (oy + 3))) - kBias;
-    const unsigned slot16 = active_s ? slot_s : 0xffffffffu;
-    if (active_s) {
-      const float sc = g.lv[l].scale;
-      orbx_keypoint o;
-      o.x = __fmul_rn((float)kx_s, sc);
-      o.y = __fmul_rn((float)ky_s, sc);
-      o.size = __fmul_rn(patch_size, sc);
-      o.angle = angle16;
-      o.response = resp;
-      o.octave = l;
-      o.class_id = -1;
-      kp_out[(size_t)img * cap_kp + slot_s] = o;
-    }
-    // (c) round k2: the half-wave hf takes the chunk's keypoint 2 k2 + hf = round k2 >> 1 of group 2 (k2 & 1) + hf
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) {
-      if (g0 + 4u * (unsigned)(k2 >> 1) >= ngrp) break;
-      const int from = (16 * (2 * (k2 & 1) + hf) + (k2 >> 1)) << 2;
-      const float ca = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(ca16)));
-      const float sa = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(sa16)));
-      const unsigned kbase = (unsigned)__builtin_amdgcn_ds_bpermute(from, (int)kbase16);
-      const unsigned slot = (unsigned)__builtin_amdgcn_ds_bpermute(from, (int)slot16);
-      const desc_f2 ca2 = {ca, ca}, sa2 = {sa, sa}, magic2 = {12582912.f, 12582912.f};
-      unsigned acc = 0;
-#pragma unroll
-      for (int r = 7; r >= 0; --r) {
-        const desc_f2 X = {pat[r][0], pat[r][1]}, Y = {pat[r][2], pat[r][3]};
-        const desc_f2 fx = X * ca2 - Y * sa2 + magic2;
-        const desc_f2 fy = X * sa2 + Y * ca2 + magic2;
-        unsigned a0, a1;
-        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a0) : "v"(__float_as_uint(fx[0])), "v"((unsigned)DT_PITCH), "v"(__float_as_uint(fy[0])));
-        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a1) : "v"(__float_as_uint(fx[1])), "v"((unsigned)DT_PITCH), "v"(__float_as_uint(fy[1])));
-        const unsigned t0 = s_tile[a0 + kbase];
-        const unsigned t1 = s_tile[a1 + kbase];
-        acc = __builtin_amdgcn_alignbit(acc, t0 - t1, 31);       // (acc << 1) | (t0 < t1): test 8 l + r ends as bit r
+    const df_i4* patp = reinterpret_cast<const df_i4*>(c_pattern) + pidx;
+    const df_i4 pr_lo = patp[0], pr_hi = patp[1];
+    float resp = 0.f;
+    if (evaluates) resp = from_orderable(~(unsigned)(sel2[lofs + ((unsigned)(es >> 32) & 0xffffu)] >> 32));   // only needed for the output record
+    const bool more = base + DT_EVAL < n_kp;
+    if (more) { e0 = entry(base + DT_EVAL, 0u); e1 = entry(base + DT_EVAL, 1u); }
+    __syncthreads();                                          // the records' centroids — and, in round 0, the blurred tile
+    // (b) lane k stands for keypoint k of the round (lanes past the count shadow keypoint 0: a whole record, no output slot)
+    if (evaluates) {
+      const int2 mm = *reinterpret_cast<const int2*>(&s_rec[(unsigned)lane < cnt ? (unsigned)lane : 0u]);
+      const unsigned j2_s = (unsigned)(es >> 32) & 0xffffu;
+      const int kx_s = (int)(es & 0xffffu), ky_s = (int)((es >> 16) & 0xffffu);
+      const unsigned slot_s = lbase + j2_s;
+      const bool active_s = (unsigned)lane < cnt && slot_s < limit;
+      const float angle = fast_atan2_deg((float)mm.y, (float)mm.x);
+      float ca, sa;
+      sincos_deg(angle, ca, sa);
+      // byte (kx - (ox + 3) + col) * DT_PITCH + (ky - (oy + 3) + row) of the column-major tile from the raw float bits: the 24-bit multiply sees
+      // 0x400000 + col, the row term carries the whole 0x4B400000 + row
+      constexpr unsigned kBias = 0x400000u * DT_PITCH + 0x4B400000u;
+      const unsigned kbase = (unsigned)((kx_s - (ox + 3)) * DT_PITCH + (ky_s - (oy + 3))) - kBias;
+      if (active_s) {
+        const float sc = g.lv[l].scale;
+        orbx_keypoint o;
+        o.x = __fmul_rn((float)kx_s, sc);
+        o.y = __fmul_rn((float)ky_s, sc);
+        o.size = __fmul_rn(patch_size, sc);
+        o.angle = angle;
+        o.response = resp;
+        o.octave = l;
+        o.class_id = -1;
+        kp_out[(size_t)img * cap_kp + slot_s] = o;
       }
-      if (slot != 0xffffffffu) desc_out[((size_t)img * cap_kp + slot) * 32 + l32] = (uint8_t)acc;
+      s_rec[lane] = (df_i4){__float_as_int(ca), __float_as_int(sa), (int)kbase, active_s ? (int)slot_s : -1};
     }
-    e0 = n0; e1 = n1; e2 = entry(g0 + 24u); e3 = entry(g0 + 28u);
+    __syncthreads();
+    // (c) round k2: the half-wave hf takes the round's keypoint w2 + 8 k2 + hf
+    if (w2 < cnt) {
+      desc_f4 pat[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int pr = r < 4 ? pr_lo[r] : pr_hi[r - 4];
+        pat[r] = (desc_f4){(float)(signed char)(pr & 0xff), (float)(signed char)((pr >> 16) & 0xff), (float)(signed char)((pr >> 8) & 0xff), (float)(signed char)((pr >> 24) & 0xff)};
+      }
+#pragma unroll
+      for (int k2 = 0; k2 < 8; ++k2) {
+        if (w2 + 8u * (unsigned)k2 >= cnt) break;
+        const df_i4 rec = s_rec[w2 + 8u * (unsigned)k2 + (unsigned)hf];
+        const float ca = __int_as_float(rec[0]), sa = __int_as_float(rec[1]);
+        const unsigned kbase = (unsigned)rec[2], slot = (unsigned)rec[3];
+        const desc_f2 ca2 = {ca, ca}, sa2 = {sa, sa}, magic2 = {12582912.f, 12582912.f};
+        unsigned acc = 0;
+#pragma unroll
+        for (int r = 7; r >= 0; --r) {
+          const desc_f2 X = {pat[r][0], pat[r][1]}, Y = {pat[r][2], pat[r][3]};
+          const desc_f2 fx = X * ca2 - Y * sa2 + magic2;
+          const desc_f2 fy = X * sa2 + Y * ca2 + magic2;
+          unsigned a0, a1;
+          asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a0) : "v"(__float_as_uint(fx[0])), "v"((unsigned)DT_PITCH), "v"(__float_as_uint(fy[0])));
+          asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a1) : "v"(__float_as_uint(fx[1])), "v"((unsigned)DT_PITCH), "v"(__float_as_uint(fy[1])));
+          const unsigned t0 = s_tile[a0 + kbase];
+          const unsigned t1 = s_tile[a1 + kbase];
+          acc = __builtin_amdgcn_alignbit(acc, t0 - t1, 31);       // (acc << 1) | (t0 < t1): test 8 l + r ends as bit r
+        }
+        if (slot != 0xffffffffu) desc_img[slot * 32u + (unsigned)l32] = (uint8_t)acc;       // (uniform base + 32-bit lane offset)
+      }
+    }
+    if (more) {
+      e2 = entry(base + DT_EVAL, 2u); e3 = entry(base + DT_EVAL, 3u);
+    }
   }
 }
 
