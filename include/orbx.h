@@ -965,6 +965,47 @@ int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam,
                                          int* feature_matches, double* pts_current, double* pts_loop, uint8_t* inlier, double* sim3,
                                          orbx_loop_verify_result* results);
 
+/* ---- map-point refresh: distinctive descriptor, normal and depth range (search_in_neighbors.rs:139-150) ------------
+ * Phase 4 of search_in_neighbors for M map points in one call: Map::compute_distinctive_descriptors (src/atlas/map/map.rs:880-944)
+ * and Map::update_map_point_normal_and_depth (map.rs:716-742, src/atlas/map/map_point.rs:173-203).  The map mutation of phases 2-3
+ * stays with the caller; this call takes the observation lists as they are afterwards.  Point p owns observations
+ * [obs_start[p], obs_start[p+1]) of obs_kf (index into the T keyframes of the call) and obs_feat (feature index in that keyframe).
+ *   [spec] the reference iterates HashMaps here; the order is the order of the point's observation list as given.
+ * Descriptor: the rows of the observations whose keyframe exists (0 <= obs_kf < T; else keyframes.get -> None) and whose feature
+ * index is inside it (0 <= obs_feat < its feature count; else row() -> Err) are collected in order.  None: the point keeps its
+ * descriptor, chosen = -1, best_max_dist = 0.  One: that row, best_max_dist = 0.  More: for every collected row the largest Hamming
+ * distance to the other collected rows (other by position: equal rows are 0 apart); the row with the smallest such maximum, the
+ * earliest on ties.  chosen is its position in the point's OBSERVATION list; n_desc the number collected.
+ * Normal and depth: over every observation whose keyframe exists (the feature index does not matter), in order:
+ * d = position - t_wc(keyframe), dist = sqrt((dx*dx + dy*dy) + dz*dz); if dist > 1e-10: sum += d / dist component by component,
+ * min / max of dist (from +inf / 0).  norm = sqrt((sx*sx + sy*sy) + sz*sz); if norm > 1e-10 the normal becomes sum / norm, else it
+ * keeps its value.  min_distance = min / scale_range, max_distance = max * scale_range, so a point without observers gets +inf and
+ * 0.  scale_range = scale_factor^(num_levels - 1), computed by the caller (powi, map_point.rs:200).  n_observers = keyframes found.
+ * Out-of-range obs_kf / obs_feat are not errors.  One IEEE operation at a time, no fused multiply-add. */
+typedef struct {
+  int32_t chosen;
+  uint32_t best_max_dist, n_desc, n_observers;
+} orbx_mp_refresh_record; /* 16 B */
+/* Host form: synchronous, one upload and one download.  positions [M][3], obs_start [M+1] ascending from 0 (else ORBX_ERR_INVALID),
+ * kf_poses_wc [T][7], kf_feat_offset [T+1] ascending from 0: keyframe t owns rows [kf_feat_offset[t], kf_feat_offset[t+1]) of descs
+ * [..][32].  mp_desc [M][32] and normals [M][3] are in/out; min_distance / max_distance [M], records [M].  M == 0: ORBX_OK. */
+int orbx_refresh_map_points(orbx_handle* h, int M, const double* positions, const int* obs_start, const int* obs_kf, const int* obs_feat,
+                            int T, const double* kf_poses_wc, const int* kf_feat_offset, const uint8_t* descs, double scale_range,
+                            uint8_t* mp_desc, double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
+/* Device form: the same arrays in device memory (descriptor arrays 8-byte aligned), asynchronous on the handle's stream.  The
+ * keyframe table — kf_poses_wc and kf_feat_offset — is HOST memory, copied before the call returns.  n_obs = obs_start[M], which
+ * the host cannot read here; d_obs_start is trusted to ascend from 0 to it. */
+int orbx_refresh_map_points_device(orbx_handle* h, int M, int n_obs, const double* d_positions, const int* d_obs_start, const int* d_obs_kf,
+                                   const int* d_obs_feat, int T, const double* kf_poses_wc, const int* kf_feat_offset, const uint8_t* d_descs,
+                                   double scale_range, uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance,
+                                   orbx_mp_refresh_record* d_records);
+/* The same on resident keyframes: descriptors and poses (camera centre = translation of T_wc) are the keyframes' own, read where
+ * they lie; the other arrays are HOST memory as in the host form.  Only the points, their lists and the results cross PCIe.
+ * Synchronous.  A keyframe of another handle: ORBX_ERR_INVALID.  Bytes equal the packed forms' on the same rows. */
+int orbx_keyframe_refresh_map_points(orbx_handle* h, int M, const double* positions, const int* obs_start, const int* obs_kf,
+                                     const int* obs_feat, const orbx_keyframe* const* kfs, int T, double scale_range, uint8_t* mp_desc,
+                                     double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

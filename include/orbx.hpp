@@ -216,6 +216,56 @@ inline std::vector<int> fuse_search(Handle& h, const std::vector<std::array<doub
   return idx;
 }
 
+// Phase 4 of search_in_neighbors (search_in_neighbors.rs:139-150) for M map points in one call: compute_distinctive_descriptors
+// (map.rs:880-944) and update_map_point_normal_and_depth (map.rs:716-742, map_point.rs:173-203); orbx.h has the specification.
+// Point p owns observations [obs_start[p], obs_start[p+1]) of obs_kf (index into `keyframes`) / obs_feat; mp_descriptors [M*32] and
+// normals [M] are the points' current values, kept where a point is not updated.  scale_range = scale_factor.powi(num_levels - 1).
+struct MapPointRefresh {
+  std::vector<uint8_t> mp_descriptors;                    // [M*32]
+  std::vector<std::array<double, 3>> normals;
+  std::vector<double> min_distance, max_distance;
+  std::vector<orbx_mp_refresh_record> records;            // chosen = position in the point's observation list, -1: not updated
+  size_t num_descriptors_updated() const { size_t n = 0; for (const auto& r : records) n += r.chosen >= 0; return n; }
+};
+inline MapPointRefresh refresh_map_points(Handle& h, const std::vector<std::array<double, 3>>& positions, const std::vector<int>& obs_start,
+                                          const std::vector<int>& obs_kf, const std::vector<int>& obs_feat,
+                                          const std::vector<std::pair<SE3, const FeatureSet*>>& keyframes, double scale_range,
+                                          const std::vector<uint8_t>& mp_descriptors, const std::vector<std::array<double, 3>>& normals) {
+  const int M = (int)positions.size(), T = (int)keyframes.size();
+  if (obs_start.size() != (size_t)M + 1 || mp_descriptors.size() != 32 * (size_t)M || normals.size() != (size_t)M || obs_kf.size() != obs_feat.size())
+    throw Error(ORBX_ERR_INVALID, "refresh_map_points: inconsistent array lengths");
+  std::vector<double> poses(7 * (size_t)T);
+  std::vector<int> off((size_t)T + 1, 0);
+  std::vector<uint8_t> descs;
+  for (int t = 0; t < T; ++t) {
+    const SE3& s = keyframes[(size_t)t].first;
+    for (int i = 0; i < 4; ++i) poses[7 * (size_t)t + i] = s.rotation[i];
+    for (int i = 0; i < 3; ++i) poses[7 * (size_t)t + 4 + i] = s.translation[i];
+    const FeatureSet& f = *keyframes[(size_t)t].second;
+    descs.insert(descs.end(), f.descriptors.begin(), f.descriptors.end());
+    off[(size_t)t + 1] = (int)(descs.size() / 32);
+  }
+  MapPointRefresh r{mp_descriptors, normals, std::vector<double>((size_t)M), std::vector<double>((size_t)M), std::vector<orbx_mp_refresh_record>((size_t)M)};
+  h.check(orbx_refresh_map_points(h.get(), M, M ? positions[0].data() : nullptr, obs_start.data(), obs_kf.data(), obs_feat.data(), T, poses.data(),
+                                  off.data(), descs.data(), scale_range, r.mp_descriptors.data(), M ? r.normals[0].data() : nullptr,
+                                  r.min_distance.data(), r.max_distance.data(), r.records.data()));
+  return r;
+}
+// The same on resident keyframes (orbx_keyframe_create): their descriptors and poses are read where they lie.
+inline MapPointRefresh refresh_map_points(Handle& h, const std::vector<std::array<double, 3>>& positions, const std::vector<int>& obs_start,
+                                          const std::vector<int>& obs_kf, const std::vector<int>& obs_feat,
+                                          const std::vector<const orbx_keyframe*>& keyframes, double scale_range,
+                                          const std::vector<uint8_t>& mp_descriptors, const std::vector<std::array<double, 3>>& normals) {
+  const int M = (int)positions.size();
+  if (obs_start.size() != (size_t)M + 1 || mp_descriptors.size() != 32 * (size_t)M || normals.size() != (size_t)M || obs_kf.size() != obs_feat.size())
+    throw Error(ORBX_ERR_INVALID, "refresh_map_points: inconsistent array lengths");
+  MapPointRefresh r{mp_descriptors, normals, std::vector<double>((size_t)M), std::vector<double>((size_t)M), std::vector<orbx_mp_refresh_record>((size_t)M)};
+  h.check(orbx_keyframe_refresh_map_points(h.get(), M, M ? positions[0].data() : nullptr, obs_start.data(), obs_kf.data(), obs_feat.data(),
+                                           keyframes.data(), (int)keyframes.size(), scale_range, r.mp_descriptors.data(),
+                                           M ? r.normals[0].data() : nullptr, r.min_distance.data(), r.max_distance.data(), r.records.data()));
+  return r;
+}
+
 struct LocalBAConfigLM {   // local_ba_lm.rs:96-119, Default :109-119
   int max_iterations = 10;
   double param_tolerance = 1e-8, gradient_tolerance = 1e-8, huber_threshold = std::sqrt(5.991);

@@ -345,6 +345,61 @@ inline size_t apply_inertial_ba_results(MapSnapshot& m, const InertialBAResultDa
   return updated;
 }
 
+// ---- phase 4 of search_in_neighbors (src/local_mapping/search_in_neighbors.rs:139-150): which points, and their arrays ---------------
+// search_in_neighbors.rs:93-102, :116-120, :141-143: the current keyframe's map points, then the neighbours', as a set.  ORDER: the
+// reference collects them in a HashSet; here first seen, walking the current keyframe, then the neighbours as given, features in order.
+// A current keyframe the snapshot does not hold: none (:100); a neighbour it does not hold is skipped (:118).  The ids are not looked
+// up (a point that is gone is left out by collect_map_point_refresh, as both reference functions do nothing for it).
+inline std::vector<MapPointId> search_in_neighbors_affected(const MapSnapshot& m, KeyFrameId current, const std::vector<KeyFrameId>& neighbours) {
+  std::vector<MapPointId> out;
+  if (m.kf_index(current) < 0) return out;
+  std::unordered_set<MapPointId> seen;
+  auto walk = [&](KeyFrameId id) {
+    const int k = m.kf_index(id);
+    if (k < 0) return;
+    for (int f = m.kf_feat_start[(size_t)k]; f < m.kf_feat_start[(size_t)k + 1]; ++f) {
+      const int64_t mp_id = m.feat_mp_id[(size_t)f];
+      if (mp_id >= 0 && seen.insert((MapPointId)mp_id).second) out.push_back((MapPointId)mp_id);
+    }
+  };
+  walk(current);
+  for (KeyFrameId id : neighbours) walk(id);
+  return out;
+}
+
+// The arrays of refresh_map_points (orbx.hpp) for the given map points: those the snapshot holds, in order, with their positions, their
+// observation lists as they stand (mp_obs_start / mp_obs_kf_id / mp_obs_feat_idx; a snapshot without feature indices gives -1) and the
+// distinct observing keyframes in first-seen order, which obs_kf indexes — -1 for an id the snapshot does not hold (keyframes.get -> None).
+struct MapPointRefreshData {
+  std::vector<MapPointId> mp_ids;
+  std::vector<std::array<double, 3>> positions;
+  std::vector<int> obs_start, obs_kf, obs_feat;
+  std::vector<KeyFrameId> kf_ids;
+};
+inline MapPointRefreshData collect_map_point_refresh(const MapSnapshot& m, const std::vector<MapPointId>& mp_ids) {
+  MapPointRefreshData d;
+  d.obs_start.push_back(0);
+  std::unordered_map<KeyFrameId, int> at;
+  for (MapPointId id : mp_ids) {
+    const int j = m.mp_index(id);
+    if (j < 0) continue;
+    d.mp_ids.push_back(id);
+    d.positions.push_back({m.mp_pos[3 * (size_t)j], m.mp_pos[3 * (size_t)j + 1], m.mp_pos[3 * (size_t)j + 2]});
+    for (int o = m.mp_obs_start[(size_t)j]; o < m.mp_obs_start[(size_t)j + 1]; ++o) {
+      const KeyFrameId kf = m.mp_obs_kf_id[(size_t)o];
+      if (m.kf_index(kf) < 0) d.obs_kf.push_back(-1);
+      else {
+        auto it = at.find(kf);
+        if (it == at.end()) { it = at.emplace(kf, (int)d.kf_ids.size()).first; d.kf_ids.push_back(kf); }
+        d.obs_kf.push_back(it->second);
+      }
+      d.obs_feat.push_back((size_t)o < m.mp_obs_feat_idx.size() ? m.mp_obs_feat_idx[(size_t)o] : -1);
+    }
+    d.obs_start.push_back((int)d.obs_kf.size());
+  }
+  return d;
+}
+
 // LocalMapper::local_bundle_adjustment (local_mapper.rs:334-410), both branches.  The reference takes the map's read
 // lock around phase 1 and its write lock around phase 3 and holds none while solving; `lock_read` / `lock_write` wrap the
 // two phases the same way (pass no-ops for a snapshot nobody else touches), plus the short read lock in which the reference asks

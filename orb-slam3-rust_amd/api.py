@@ -96,6 +96,7 @@ ABI_SYMBOLS = [
     "orbx_track_reference", "orbx_track_reference_device", "orbx_keyframe_track_reference",
     "orbx_default_sim3_config", "orbx_default_loop_verify_config", "orbx_sim3_ransac_batch", "orbx_sim3_ransac_batch_device",
     "orbx_verify_loop_candidates", "orbx_verify_loop_candidates_device", "orbx_keyframe_verify_loop_candidates",
+    "orbx_refresh_map_points", "orbx_refresh_map_points_device", "orbx_keyframe_refresh_map_points",
 ]
 
 
@@ -218,6 +219,9 @@ LOOP_VERIFY_RESULT = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_pair
 SIM3_OK, SIM3_NO_MODEL = 0, 1
 (LOOP_OK, LOOP_TOO_FEW_POINTS, LOOP_TOO_FEW_MATCHES, LOOP_TOO_FEW_PAIRS, LOOP_NO_MODEL, LOOP_TOO_FEW_INLIERS,
  LOOP_TOO_FEW_VERIFIED) = range(7)
+# orbx_mp_refresh_record
+MP_REFRESH_RECORD = np.dtype([("chosen", "<i4"), ("best_max_dist", "<u4"), ("n_desc", "<u4"), ("n_observers", "<u4")])
+assert MP_REFRESH_RECORD.itemsize == 16
 LOOP_VERIFY_MAX_FEAT = 1 << 22            # features per keyframe (loop_verify_kernels.hip: LV_MAX_FEAT)
 
 
@@ -468,6 +472,36 @@ class VerifiedLoop:
     feature_matches: np.ndarray
     inlier_mask: np.ndarray = None
     stats: Dict[str, float] = field(default_factory=dict)
+
+
+@dataclass
+class MapPointRefresh:
+    """What orbx_refresh_map_points leaves for M map points: mp_desc [M,32] u8 and normals [M,3] (the inputs where a point was not
+    updated), min_distance / max_distance [M] and records [M] (MP_REFRESH_RECORD: chosen = position of the kept descriptor in the
+    point's observation list or -1, best_max_dist, n_desc, n_observers)."""
+    mp_desc: np.ndarray
+    normals: np.ndarray
+    min_distance: np.ndarray
+    max_distance: np.ndarray
+    records: np.ndarray
+
+    @property
+    def num_descriptors_updated(self):
+        """SearchInNeighborsResult::num_descriptors_updated (search_in_neighbors.rs:146-148)."""
+        return int((self.records["chosen"] >= 0).sum())
+
+
+@dataclass
+class MapPointRefreshData:
+    """MapSnapshot.collect_map_point_refresh: the arrays of a refresh call.  mp_ids: the requested points the snapshot holds, in
+    order; positions [M,3]; obs_start [M+1], obs_kf, obs_feat: their observation lists, obs_kf indexing kf_ids (-1: a keyframe the
+    snapshot does not hold); kf_ids: the distinct observing keyframes in first-seen order."""
+    mp_ids: List[int]
+    positions: np.ndarray
+    obs_start: np.ndarray
+    obs_kf: np.ndarray
+    obs_feat: np.ndarray
+    kf_ids: List[int]
 
 
 def _rec_dict(rec):
@@ -1281,6 +1315,59 @@ class Handle:
                                              _vp(idx), _vp(dist)))
         return idx, dist
 
+    @staticmethod
+    def _refresh_inputs(positions, obs_start, obs_kf, obs_feat, mp_desc, normals):
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        obs_start = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+        obs_kf = np.ascontiguousarray(obs_kf, np.int32).reshape(-1); obs_feat = np.ascontiguousarray(obs_feat, np.int32).reshape(-1)
+        M = len(positions)
+        mp_desc = np.array(mp_desc, np.uint8).reshape(-1, 32); normals = np.array(normals, np.float64).reshape(-1, 3)       # copies: in/out
+        if len(obs_start) != M + 1 or len(mp_desc) != M or len(normals) != M or len(obs_kf) != len(obs_feat) or \
+                (M > 0 and len(obs_kf) != int(obs_start[-1])):
+            raise ValueError("refresh_map_points: inconsistent array lengths")
+        out = MapPointRefresh(mp_desc, normals, np.zeros(M), np.zeros(M), np.zeros(M, MP_REFRESH_RECORD))
+        return positions, obs_start, obs_kf, obs_feat, out
+
+    def refresh_map_points(self, positions, obs_start, obs_kf, obs_feat, kf_poses_wc, kf_feat_offset, descs, scale_range, mp_desc,
+                           normals) -> "MapPointRefresh":
+        """Phase 4 of search_in_neighbors (search_in_neighbors.rs:139-150) for M map points: compute_distinctive_descriptors and
+        update_map_point_normal_and_depth (orbx.h: orbx_refresh_map_points).  Point p owns observations obs_start[p]..obs_start[p+1] of
+        obs_kf (index into the T keyframes) / obs_feat; keyframe t owns rows kf_feat_offset[t]..kf_feat_offset[t+1] of descs [F,32].
+        scale_range = scale_factor ** (num_levels - 1).  mp_desc / normals are the points' current values (not modified)."""
+        positions, obs_start, obs_kf, obs_feat, out = self._refresh_inputs(positions, obs_start, obs_kf, obs_feat, mp_desc, normals)
+        poses = np.ascontiguousarray(kf_poses_wc, np.float64).reshape(-1, 7)
+        off = np.ascontiguousarray(kf_feat_offset, np.int32).reshape(-1)
+        descs = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        T = len(poses)
+        if len(off) != T + 1 or (T > 0 and len(descs) != int(off[-1])):
+            raise ValueError("refresh_map_points: inconsistent keyframe arrays")
+        self._check(self._L.orbx_refresh_map_points(self._h, C.c_int(len(positions)), _vp(positions), _vp(obs_start), _vp(obs_kf), _vp(obs_feat),
+                                                    C.c_int(T), _vp(poses), _vp(off), _vp(descs), C.c_double(scale_range), _vp(out.mp_desc),
+                                                    _vp(out.normals), _vp(out.min_distance), _vp(out.max_distance), _vp(out.records)))
+        return out
+
+    def refresh_map_points_device(self, positions, obs_start, obs_kf, obs_feat, n_obs, kf_poses_wc, kf_feat_offset, descs, scale_range,
+                                  mp_desc, normals):
+        """Device-resident form: torch CUDA tensors positions [M,3] f64, obs_start [M+1] / obs_kf / obs_feat int32, descs [F,32] u8,
+        mp_desc [M,32] u8 and normals [M,3] f64 (both updated IN PLACE); HOST arrays kf_poses_wc [T,7] and kf_feat_offset [T+1];
+        n_obs = obs_start[M] as the host knows it.  Returns a dict of tensors: min_distance / max_distance [M] f64, records [M,16] u8
+        (MP_REFRESH_RECORD).  Asynchronous on the handle's stream."""
+        import torch
+        M = positions.shape[0]
+        poses = np.ascontiguousarray(kf_poses_wc, np.float64).reshape(-1, 7)
+        off = np.ascontiguousarray(kf_feat_offset, np.int32).reshape(-1)
+        if len(off) != len(poses) + 1:
+            raise ValueError("refresh_map_points_device: inconsistent keyframe arrays")
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=positions.device)
+        o = dict(min_distance=mk(max(M, 1), torch.float64), max_distance=mk(max(M, 1), torch.float64),
+                 records=mk((max(M, 1), MP_REFRESH_RECORD.itemsize), torch.uint8))
+        self._after_torch(positions, obs_start, obs_kf, obs_feat, descs, mp_desc, normals, *o.values())
+        self._check(self._L.orbx_refresh_map_points_device(self._h, C.c_int(M), C.c_int(int(n_obs)), _vp(positions), _vp(obs_start), _vp(obs_kf),
+                                                           _vp(obs_feat), C.c_int(len(poses)), _vp(poses), _vp(off), _vp(descs),
+                                                           C.c_double(scale_range), _vp(mp_desc), _vp(normals), _vp(o["min_distance"]),
+                                                           _vp(o["max_distance"]), _vp(o["records"])))
+        return {k: v[:M] for k, v in o.items()}
+
     def hamming_batch(self, a, b):
         a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32)
         b = np.ascontiguousarray(b, np.uint8).reshape(-1, 32)
@@ -1914,6 +2001,19 @@ class KeyFrame:
                                                           int(desc_threshold), _vp(idx), _vp(dist)))
         return idx[:P, :T], dist[:P, :T]
 
+    @staticmethod
+    def refresh_map_points(handle, keyframes, positions, obs_start, obs_kf, obs_feat, scale_range, mp_desc, normals) -> "MapPointRefresh":
+        """Handle.refresh_map_points on resident keyframes: obs_kf indexes `keyframes`, whose descriptors and poses are their own;
+        only the points, their observation lists and the results cross PCIe.  The same bytes as the packed form."""
+        positions, obs_start, obs_kf, obs_feat, out = Handle._refresh_inputs(positions, obs_start, obs_kf, obs_feat, mp_desc, normals)
+        T = len(keyframes)
+        arr = (C.c_void_p * max(T, 1))(*[k._p for k in keyframes])
+        handle._after_torch()
+        handle._check(handle._L.orbx_keyframe_refresh_map_points(handle._h, C.c_int(len(positions)), _vp(positions), _vp(obs_start), _vp(obs_kf),
+                                                                 _vp(obs_feat), arr, C.c_int(T), C.c_double(scale_range), _vp(out.mp_desc),
+                                                                 _vp(out.normals), _vp(out.min_distance), _vp(out.max_distance), _vp(out.records)))
+        return out
+
     def close(self):
         if self._p:
             self._L.orbx_keyframe_destroy(self._p)
@@ -2255,6 +2355,47 @@ class MapSnapshot:
                 self.mp_pos[j] = pos
                 updated += 1
         return updated
+
+    # ---- search_in_neighbors.rs:93-102, :116-120, :141-143 --------------------------------------------------------
+    def search_in_neighbors_affected(self, current_kf_id, neighbour_ids) -> List[int]:
+        """The map points phase 4 of search_in_neighbors refreshes: the current keyframe's (:93-102), then the neighbours' (:116-120),
+        as a set in first-seen order (:141-143; the reference's HashSet order is unspecified).  A current keyframe the snapshot does
+        not hold: none (:100); a neighbour it does not hold is skipped (:118).  The ids are not looked up: a point that is gone is
+        left out by collect_map_point_refresh, as both reference functions do nothing for it."""
+        if self._kf.get(int(current_kf_id), -1) < 0:
+            return []
+        seen = {}
+        for kid in [int(current_kf_id)] + [int(n) for n in neighbour_ids]:
+            k = self._kf.get(kid, -1)
+            if k < 0:
+                continue
+            for mp_id in self.feat_mp_id[int(self.kf_feat_start[k]):int(self.kf_feat_start[k + 1])]:
+                if mp_id >= 0:
+                    seen.setdefault(int(mp_id), True)
+        return list(seen)
+
+    def collect_map_point_refresh(self, mp_ids) -> "MapPointRefreshData":
+        """The arrays of refresh_map_points for the given map points (those the snapshot holds, in order): positions, the observation
+        lists as they stand in mp_obs_start / mp_obs_kf_id / mp_obs_feat_idx, and the distinct observing keyframes in first-seen
+        order, which obs_kf indexes (-1 for a keyframe the snapshot does not hold: keyframes.get -> None)."""
+        kept, pos, start, okf, ofeat, kf_ids, kf_at = [], [], [0], [], [], [], {}
+        for mid in mp_ids:
+            j = self._mp.get(int(mid), -1)
+            if j < 0:
+                continue
+            kept.append(int(mid)); pos.append(self.mp_pos[j])
+            for o in range(int(self.mp_obs_start[j]), int(self.mp_obs_start[j + 1])):
+                kid = int(self.mp_obs_kf_id[o])
+                if kid not in self._kf:
+                    okf.append(-1)
+                else:
+                    if kid not in kf_at:
+                        kf_at[kid] = len(kf_ids); kf_ids.append(kid)
+                    okf.append(kf_at[kid])
+                ofeat.append(int(self.mp_obs_feat_idx[o]) if o < len(self.mp_obs_feat_idx) else -1)
+            start.append(len(okf))
+        return MapPointRefreshData(kept, np.array(pos, np.float64).reshape(-1, 3), np.array(start, np.int32), np.array(okf, np.int32),
+                                   np.array(ofeat, np.int32), kf_ids)
 
 
 def local_bundle_adjustment(snapshot: MapSnapshot, kf_id, camera: "CameraModel", should_stop: Callable[[], bool] = None,

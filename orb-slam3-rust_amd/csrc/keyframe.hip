@@ -443,4 +443,23 @@ int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam,
   return ORBX_OK;
 }
 
+// phase 4 of search_in_neighbors (search_in_neighbors.rs:139-150) on resident keyframes: see include/orbx.h.  The launches are
+// mappoint_kernels.hip's; the keyframe table points at every keyframe's descriptors where they lie.
+int orbx_keyframe_refresh_map_points(orbx_handle* h, int M, const double* positions, const int* obs_start, const int* obs_kf,
+                                     const int* obs_feat, const orbx_keyframe* const* kfs, int T, double scale_range, uint8_t* mp_desc,
+                                     double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
+  static const char* who = "orbx_keyframe_refresh_map_points";
+  if (!h) return ORBX_ERR_INVALID;
+  if (M < 0 || T < 0 || (T > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  std::vector<MapPointKf> tab((size_t)T);
+  for (int t = 0; t < T; ++t) {
+    if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
+    tab[(size_t)t].desc = kfs[t]->d_desc; tab[(size_t)t].n = kfs[t]->n; tab[(size_t)t].pad_ = 0;
+    memcpy(tab[(size_t)t].centre, kfs[t]->pose_wc + 4, sizeof(tab[(size_t)t].centre));
+  }
+  if (M == 0) return ORBX_OK;
+  return mp_refresh_host_call(h, who, M, positions, obs_start, obs_kf, obs_feat, T, tab.data(), nullptr, nullptr, scale_range, mp_desc, normals,
+                              min_distance, max_distance, records);
+}
+
 }  // extern "C"

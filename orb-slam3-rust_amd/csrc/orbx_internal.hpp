@@ -239,6 +239,9 @@ struct orbx_handle {
   DevBuf ws_lv[4];                       // loop verification (loop_verify_kernels.hip): [0] minima, counters, hypotheses and models, [1] the host forms' input / output blobs, [2] the call's item table and node ids, [3] the standalone Sim3 host form's blobs
   PinnedBuf pin_lv;                      // pinned staging of the host forms
   UploadRing ring_lv;                    // the item table and the node ids on their way to ws_lv[2]
+  DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
+  PinnedBuf pin_mp;                      // pinned staging of the host forms
+  UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -408,6 +411,26 @@ struct LoopVerifyPair {
 int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int B,
                         const LoopVerifyPair* pairs, orbx_dmatch* d_matches, int* d_feature_matches, double* d_pts_current,
                         double* d_pts_loop, uint8_t* d_inlier, double* d_sim3, orbx_loop_verify_result* d_results);
+// ---- map-point refresh (mappoint_kernels.hip; search_in_neighbors.rs:139-150, map.rs:716-742, :880-944) ----
+// One keyframe of a call: its descriptor rows wherever they lie in device memory (a slice of a packed array or a resident
+// orbx_keyframe's block), how many there are, and its camera centre (the translation of T_wc).
+struct MapPointKf {
+  const uint8_t* desc;
+  int n, pad_;
+  double centre[3];
+};
+// The device form behind orbx_refresh_map_points_device and the host forms: kfs [T] is a host array (copied before the call
+// returns), everything else device memory.  A point keeps d_desc_in / d_normals_in where it is not updated; they may be the
+// outputs themselves.  n_obs = obs_start[M].
+int mp_refresh_enqueue(orbx_handle* h, const char* who, int M, int n_obs, const double* d_positions, const int* d_obs_start,
+                       const int* d_obs_kf, const int* d_obs_feat, int T, const MapPointKf* kfs, double scale_range,
+                       const uint8_t* d_desc_in, const double* d_normals_in, uint8_t* d_mp_desc, double* d_normals, double* d_min_distance,
+                       double* d_max_distance, orbx_mp_refresh_record* d_records);
+// The host forms: one upload, the launches, one download.  kfs [T] carries counts and centres; with kf_feat_offset / descs given
+// (the packed form) the rows travel too and kfs[t].desc is set here, else (resident keyframes) it is set by the caller.
+int mp_refresh_host_call(orbx_handle* h, const char* who, int M, const double* positions, const int* obs_start, const int* obs_kf,
+                         const int* obs_feat, int T, MapPointKf* kfs, const int* kf_feat_offset, const uint8_t* descs, double scale_range,
+                         uint8_t* mp_desc, double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
 // extractor (orb_kernels.hip)
 int orb_prepare_geometry(orbx_handle* h, int w, int h_px);
 int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,
