@@ -588,6 +588,12 @@ void orbx_default_inertial_ba_config(orbx_inertial_ba_config* cfg);
  *   poses_wc [K][7], velocities [K][3], biases [K][6] (gyro xyz, accel xyz); fixed_poses_cw [F][7] (T_cw);
  *   obs: kf_idx = index into the window or -1 (+ fixed_idx); edge_kf [E][2] window indices (i earlier, j later);
  *   preint [E][11] = delta_rot (qw,qx,qy,qz), delta_vel, delta_pos, dt of PreintegratedState (preintegration.rs:85-98).
+ *   The edges are any list of index pairs: i > j as well as i < j (earlier / later is time, not index order), in any
+ *   order, E = 0, keyframes without an edge, a pair listed twice (its terms are then added twice, as the reference's
+ *   loop over imu_edges does).  The two ends of an edge are DISTINCT keyframes: an edge with i == j is refused with
+ *   ORBX_ERR_INVALID ("IMU edge %d: both ends are keyframe %d") before anything is enqueued — the reference never
+ *   builds one (it pairs opt_kf_ids[i] with opt_kf_ids[i + 1]), and the entries of its 18 x 18 block would fall on
+ *   each other in the system.  (orbx_debug_imu_residual, which assembles nothing, takes such an edge.)
  *   Outputs for ALL K keyframes (the reference's result maps skip index 0, :1250 — the caller's business).
  * ORBX_ERR_EMPTY where the reference returns None (K < 2, :1080-1082). */
 int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K,

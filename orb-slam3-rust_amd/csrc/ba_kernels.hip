@@ -3136,8 +3136,7 @@ __global__ __launch_bounds__(64) void ba_imu_kernel(const BaState* S, double* P0
     for (int j = 0; j < 9; ++j) { a[j] = st[0][j]; b[j] = st[1][j]; }
     if (tid > 0) {                                                        // params_plus[col] += eps (:822-824)
       const int c = tid - 1;
-      if (c < 9) a[c] += 1e-6; else b[c - 9] += 1e-6;
-      if (ki == kj) { if (c < 9) b[c] += 1e-6; else a[c - 9] += 1e-6; }  // one parameter vector: both views move
+      if (c < 9) a[c] += 1e-6; else b[c - 9] += 1e-6;                    // (ki != kj: ba_check_inertial)
     }
     double rr[9];
     imu_residual_dev(a, b, pre, rr);
@@ -3514,9 +3513,14 @@ int ba_check_inertial(BaCtx& c) {
   if (!c.inertial) return ORBX_OK;
   if (c.n15 > BA_MAX_N) return orbx_fail(c.h, ORBX_ERR_INVALID, "at most %d keyframes per inertial window", BA_MAX_N / 15);
   const BaInertialHost* inr = c.inr;
-  for (int e = 0; e < inr->E; ++e)
+  for (int e = 0; e < inr->E; ++e) {
     if (inr->edge_kf[2 * e] < 0 || inr->edge_kf[2 * e] >= c.K0 || inr->edge_kf[2 * e + 1] < 0 || inr->edge_kf[2 * e + 1] >= c.K0)
       return orbx_fail(c.h, ORBX_ERR_INVALID, "IMU edge %d: keyframe index out of range", e);
+    // an edge links two DISTINCT keyframes: with ki == kj several entries of its 18 x 18 record fall on one entry of the system, which
+    // the assemblies add without an order between them (the reference pairs opt_kf_ids[i] with opt_kf_ids[i + 1] and never builds one)
+    if (inr->edge_kf[2 * e] == inr->edge_kf[2 * e + 1])
+      return orbx_fail(c.h, ORBX_ERR_INVALID, "IMU edge %d: both ends are keyframe %d", e, inr->edge_kf[2 * e]);
+  }
   return ORBX_OK;
 }
 // The fused loop (ba_step_kernel: back-substitution + the next iteration's build pass in one launch): the visual solve on one GPU.
