@@ -747,7 +747,8 @@ int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, cons
  *   TOO_FEW_INLIERS          n_inliers < min_inliers: pose = the prior's bytes;
  *   NO_MODEL                 PnP's ORBX_PNP_NO_MODEL (pose = the prior, mask and errors under it, as PnP reports them);
  *   OK.
- * The tracker's state machine, the choice of local map points and refine_with_imu's guard stay with the caller. */
+ * The tracker's state machine, the choice of local keyframes and refine_with_imu's guard stay with the caller; the lists can be
+ * made on the device from resident map points (orbx_map_track_frames_device, below). */
 enum {
   ORBX_TRACK_OK = 0,
   ORBX_TRACK_NO_MODEL = 1,
@@ -1011,6 +1012,88 @@ int orbx_refresh_map_points_device(orbx_handle* h, int M, int n_obs, const doubl
 int orbx_keyframe_refresh_map_points(orbx_handle* h, int M, const double* positions, const int* obs_start, const int* obs_kf,
                                      const int* obs_feat, const orbx_keyframe* const* kfs, int T, double scale_range, uint8_t* mp_desc,
                                      double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
+
+/* ---- resident map points: store, local-map selection, tracking (tracker.rs:826-867, :1024-1036, :1093-1102) ----------------
+ * orbx_map_points keeps map points in device memory, so that a frame's list of map points is made where the tracker reads it.
+ * A store has a fixed capacity; a point lives in a SLOT, an int in [0, capacity).  The caller owns the id -> slot assignment (ids
+ * are map bookkeeping and stay on the host, as they do for orbx_keyframe).  Per slot: position f64[3], descriptor u8[32] and a
+ * live byte — live means map.get_map_point(id) is Some; is_bad is not consulted (neither tracker.rs:864-867 nor :1099-1102 reads
+ * it).  A store belongs to its handle; all its work is ordered on the handle's stream.
+ *   set: rows i of positions [n][3] / desc [n][32] go to slots[i]; one upload, one launch.  Either array may be NULL: that field
+ *     stays as it is (positions only: BA's apply; descriptors only: the refresh).  A slot that is not live becomes live and needs
+ *     both.  ORBX_ERR_INVALID before anything is enqueued, the store unchanged: a slot outside [0, capacity), a slot listed twice
+ *     in the call, a first set with a field missing.
+ *   set_device: the same with the rows in device memory (the outputs of orbx_refresh_map_points_device, BA's point array, the
+ *     points of orbx_keyframe_triangulate_from_neighbors), asynchronous.  slots stays a HOST array (copied before the call returns):
+ *     the assignment is the caller's, and so every check of set is made here too.  d_desc 4-byte, d_positions 8-byte aligned.
+ *   erase: clears live (a slot may repeat; one that is not live stays so).  download: rows of the listed slots (any of the three
+ *     outputs may be NULL), synchronous; for tests and debugging.  info: capacity and the number of live slots.
+ *   orbx_keyframe_set_map_point_slots: the keyframe's per-feature slot table [n], -1 = None, kept in the keyframe's device block;
+ *     NULL clears it (a keyframe without a table counts as all -1).  Values < -1 or >= capacity: ORBX_ERR_INVALID.  The table is
+ *     bound to the store it was set against (which must outlive it); orbx_keyframe_set_map_points and the ids are untouched.
+ *
+ * orbx_map_select_points_device makes, for each of n_frames frames, its list of map points, with no host synchronisation inside.
+ *   ORBX_MAP_SOURCE_KEYFRAMES (track_local_map, :826-867): frame b names kfs[kf_offsets[b] .. kf_offsets[b+1]) (host arrays,
+ *     copied before the call returns).  Its list is the DISTINCT LIVE slots in FIRST-SEEN order, walking the keyframes in the order
+ *     given and each keyframe's features in index order (get_map_point_indices, keyframe.rs:249-254); -1 and slots not live when
+ *     the kernels run are skipped.  [spec] the reference collects into a HashSet, whose order is unspecified and changes between
+ *     runs; the order matters because it is the order of PnP's correspondences.
+ *   ORBX_MAP_SOURCE_SLOTS (track_with_motion_model, :1093-1102): frame b's source is d_src_slots[src_offsets[b] ..
+ *     src_offsets[b+1]) (a device array, host offsets), walked in order; -1 and slots not live are skipped; NO de-duplication (the
+ *     reference pushes a point once per feature that carries it).
+ *   The arguments of the other kind are ignored (NULL).  Outputs, device memory: d_list_offsets [n_frames+1] packed from 0,
+ *   d_list_slot, d_positions [.][3], d_mp_desc [.][32] (16-byte aligned) — the last two in the layout orbx_track_frames_device reads.
+ *   list_cap is the number of rows the three hold; it must reach the host-known bound: the sum over the frames of their candidates
+ *   (features of the frame's keyframes, or entries of its source), per frame at most the capacity where keyframes are the source.
+ *   A list is never truncated.  The result is the same bytes on every run and in any batch composition.
+ *
+ * orbx_map_track_frames_device = that selection, then orbx_track_frames_device's launches on the lists as they lie.  Frames, poses,
+ * cfg and the outputs d_offsets .. d_results are those of orbx_track_frames_device, sized by list_cap where that call says M (mp_idx
+ * indexes the frame's list).  Added: the lists themselves and d_matched_slot [n_frames][max_feat]: matched mapped through the list
+ * to slots, -1 where none.  d_matched_slot of frame t is a valid SLOTS source for frame t+1 (src_offsets[b] = b * max_feat).  Every
+ * output equals orbx_track_frames_device's on the same lists, byte for byte.  orbx_map_track_frames: the same with the features,
+ * the slot source and every output in host memory (matched / matched_slot packed by feat_offsets), synchronous.
+ *
+ * orbx_map_track_reference_device = orbx_keyframe_track_reference with kf_positions / kf_valid made on the device from kfs[b]'s slot
+ * table and the store: valid[i] = slot[i] >= 0 && live[slot[i]], positions[i] = that slot's position, else zeros.  They are
+ * written to d_kf_positions [K][3] / d_kf_valid [K], K = the keyframes' feature counts summed in kfs order (frame b's rows start
+ * where the earlier keyframes' end); the other outputs are sized by K as in orbx_track_reference_device. */
+typedef struct orbx_map_points orbx_map_points;
+enum { ORBX_MAP_SOURCE_KEYFRAMES = 0, ORBX_MAP_SOURCE_SLOTS = 1 };
+int orbx_map_points_create(orbx_handle* h, int capacity, orbx_map_points** out);
+void orbx_map_points_destroy(orbx_map_points* mp);
+int orbx_map_points_info(const orbx_map_points* mp, int* capacity, int* n_live);
+int orbx_map_points_set(orbx_map_points* mp, const int* slots, int n, const double* positions, const uint8_t* desc);
+int orbx_map_points_set_device(orbx_map_points* mp, const int* slots, int n, const double* d_positions, const uint8_t* d_desc);
+int orbx_map_points_erase(orbx_map_points* mp, const int* slots, int n);
+int orbx_map_points_download(orbx_map_points* mp, const int* slots, int n, double* positions, uint8_t* desc, uint8_t* live);
+int orbx_keyframe_set_map_point_slots(orbx_keyframe* kf, const orbx_map_points* mp, const int* slots);
+int orbx_map_select_points_device(orbx_handle* h, orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs,
+                                  const int* kf_offsets, const int* d_src_slots, const int* src_offsets, int list_cap,
+                                  int* d_list_offsets, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc);
+int orbx_map_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                                 orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets,
+                                 const int* d_src_slots, const int* src_offsets, const orbx_keypoint* d_kp, const uint8_t* d_desc,
+                                 const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                 const double* d_search_poses_wc, const double* d_priors_wc, int list_cap, int* d_list_offsets,
+                                 int* d_list_slot, double* d_positions, uint8_t* d_mp_desc, int* d_offsets, double* d_pts3d,
+                                 float* d_pts2d, int* d_mp_idx, int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out,
+                                 double* d_err_out, orbx_pnp_result* d_pnp_results, int* d_matched, int* d_matched_slot,
+                                 orbx_track_result* d_results);
+int orbx_map_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                          orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets,
+                          const int* src_slots, const int* src_offsets, const orbx_keypoint* kp, const uint8_t* desc,
+                          const int* feat_offsets, const double* search_poses_wc, const double* priors_wc, int list_cap,
+                          int* list_offsets, int* list_slot, int* offsets, double* pts3d, float* pts2d, int* mp_idx, int* feat_idx,
+                          double* poses_wc_out, uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched,
+                          int* matched_slot, orbx_track_result* results);
+int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                                    orbx_map_points* mp, int n_frames, const orbx_keyframe* const* kfs, const orbx_keypoint* d_kp,
+                                    const uint8_t* d_desc, const int* d_feat_start, const int* d_feat_count, int feat_count_stride,
+                                    int max_feat, const double* d_priors_wc, double* d_kf_positions, uint8_t* d_kf_valid,
+                                    orbx_dmatch* d_matches, int* d_offsets, double* d_pts3d, float* d_pts2d, int* d_kf_idx,
+                                    int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                    orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
 
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and

@@ -749,6 +749,148 @@ inline TrackResult track_with_motion_model(Handle& h, const CameraModel& camera,
   return track_frames(h, camera, {TrackFrame{&features, positions, mp_descriptors, predicted_pose, predicted_pose}}, 0)[0];
 }
 
+// ---- resident map points (orbx_map_points, orbx.h): the store, and the tracker's step with its lists made on the device ----
+// A slot is an int in [0, capacity); the caller owns the id -> slot assignment (a HashMap<MapPointId, u32> with a free list).
+class MapPointStore {
+ public:
+  MapPointStore(Handle& h, int capacity) : h_(&h) { h.check(orbx_map_points_create(h.get(), capacity, &mp_)); }
+  MapPointStore(const MapPointStore&) = delete;
+  MapPointStore& operator=(const MapPointStore&) = delete;
+  ~MapPointStore() { if (mp_) orbx_map_points_destroy(mp_); }
+  orbx_map_points* get() const { return mp_; }
+  // rows into slots; an empty positions / descriptors vector leaves that field as it is (a slot's first set needs both)
+  void set(const std::vector<int>& slots, const std::vector<std::array<double, 3>>& positions, const std::vector<uint8_t>& descriptors) {
+    if ((!positions.empty() && positions.size() != slots.size()) || (!descriptors.empty() && descriptors.size() != 32 * slots.size()))
+      throw std::invalid_argument("MapPointStore::set: one row per slot");
+    h_->check(orbx_map_points_set(mp_, slots.data(), (int)slots.size(), positions.empty() ? nullptr : positions[0].data(),
+                                  descriptors.empty() ? nullptr : descriptors.data()));
+  }
+  // the same with the rows in device memory (either may be nullptr), asynchronous on the handle's stream
+  void set_device(const std::vector<int>& slots, const double* d_positions, const uint8_t* d_descriptors) {
+    h_->check(orbx_map_points_set_device(mp_, slots.data(), (int)slots.size(), d_positions, d_descriptors));
+  }
+  void erase(const std::vector<int>& slots) { h_->check(orbx_map_points_erase(mp_, slots.data(), (int)slots.size())); }
+  void download(const std::vector<int>& slots, std::vector<std::array<double, 3>>& positions, std::vector<uint8_t>& descriptors,
+                std::vector<uint8_t>& live) const {
+    const size_t n = slots.size();
+    positions.resize(n); descriptors.resize(32 * n); live.resize(n);
+    h_->check(orbx_map_points_download(mp_, slots.data(), (int)n, n ? positions[0].data() : nullptr, descriptors.data(), live.data()));
+  }
+  int capacity() const { int c = 0; h_->check(orbx_map_points_info(mp_, &c, nullptr)); return c; }
+  int n_live() const { int n = 0; h_->check(orbx_map_points_info(mp_, nullptr, &n)); return n; }
+
+ private:
+  Handle* h_;
+  orbx_map_points* mp_ = nullptr;
+};
+
+// One frame's input: its features, the pose its points are projected with and PnP's prior (both T_wc), and where its map points
+// come from: resident keyframes with slot tables (orbx_keyframe_set_map_point_slots), or slots (the previous frame's matched_slot).
+struct MapTrackFrame {
+  const FeatureSet* features = nullptr;
+  std::vector<const orbx_keyframe*> keyframes;
+  std::vector<int> slots;
+  SE3 search_pose, prior;
+};
+
+// TrackResult (mp_idx and matched_map_points index the frame's list) with the list's slots and matched as slots, -1 = none.
+struct MapTrackResult : TrackResult {
+  std::vector<int> list_slot, matched_slot;
+};
+
+// The batch form: source = ORBX_MAP_SOURCE_KEYFRAMES or ORBX_MAP_SOURCE_SLOTS for every frame of the call; mode as track_frames.
+inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel& camera, MapPointStore& store, const std::vector<MapTrackFrame>& frames,
+                                                    int source, int mode, const orbx_track_config* cfg = nullptr) {
+  const int B = (int)frames.size();
+  orbx_track_config tc;
+  orbx_default_track_config(mode, &tc);
+  if (cfg) tc = *cfg;
+  orbx_pnp_config pc;
+  orbx_default_pnp_config(&pc);
+  const int capacity = store.capacity();
+  std::vector<int> fo(B + 1, 0), ko(B + 1, 0), so(B + 1, 0), src;
+  std::vector<const orbx_keyframe*> kfs;
+  std::vector<KeyPoint> kp;
+  std::vector<uint8_t> desc;
+  std::vector<double> sp, pr;
+  auto push7 = [](std::vector<double>& v, const SE3& p) {
+    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
+    v.insert(v.end(), p.translation.begin(), p.translation.end());
+  };
+  size_t M = 0;                                                   // the lists' host-known bound
+  for (int b = 0; b < B; ++b) {
+    const MapTrackFrame& f = frames[b];
+    if (!f.features || f.features->descriptors.size() != 32 * f.features->keypoints.size())
+      throw std::invalid_argument("map_track_frames: a frame's descriptors do not match its keypoints");
+    kp.insert(kp.end(), f.features->keypoints.begin(), f.features->keypoints.end());
+    desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
+    push7(sp, f.search_pose); push7(pr, f.prior);
+    fo[b + 1] = (int)kp.size();
+    if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
+      size_t cand = 0;
+      for (const orbx_keyframe* k : f.keyframes) {
+        int n = 0;
+        h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+        cand += (size_t)n;
+        kfs.push_back(k);
+      }
+      M += std::min(cand, (size_t)capacity);
+    } else {
+      src.insert(src.end(), f.slots.begin(), f.slots.end());
+      M += f.slots.size();
+    }
+    ko[b + 1] = (int)kfs.size(); so[b + 1] = (int)src.size();
+  }
+  const size_t NF = kp.size(), Mz = std::max<size_t>(M, 1), Bz = (size_t)std::max(B, 1);
+  std::vector<int> lo(B + 1, 0), ls(Mz), off(B + 1, 0), mi(Mz), fi(Mz), matched(std::max<size_t>(NF, 1)), mslot(std::max<size_t>(NF, 1));
+  std::vector<double> p3(3 * Mz), poses(7 * Bz), err(Mz);
+  std::vector<float> p2(2 * Mz);
+  std::vector<uint8_t> inl(Mz);
+  std::vector<orbx_pnp_result> pres(Bz);
+  std::vector<orbx_track_result> res(Bz);
+  const orbx_camera cam = camera.c();
+  h.check(orbx_map_track_frames(h.get(), &cam, &tc, &pc, store.get(), source, B, kfs.data(), ko.data(), src.data(), so.data(), kp.data(), desc.data(),
+                                fo.data(), sp.data(), pr.data(), (int)M, lo.data(), ls.data(), off.data(), p3.data(), p2.data(), mi.data(), fi.data(),
+                                poses.data(), inl.data(), err.data(), pres.data(), matched.data(), mslot.data(), res.data()));
+  std::vector<MapTrackResult> out(B);
+  for (int b = 0; b < B; ++b) {
+    MapTrackResult& r = out[b];
+    const double* o7 = &poses[7 * (size_t)b];
+    r.pose.rotation = {o7[0], o7[1], o7[2], o7[3]};
+    r.pose.translation = {o7[4], o7[5], o7[6]};
+    r.record = res[b]; r.pnp = pres[b];
+    const bool too_few = res[b].status == ORBX_TRACK_TOO_FEW_CORRESPONDENCES;
+    r.n_inliers = too_few ? (size_t)res[b].n_correspondences : (size_t)res[b].n_inliers;
+    r.list_slot.assign(ls.begin() + lo[b], ls.begin() + lo[b + 1]);
+    for (int f = fo[b]; f < fo[b + 1]; ++f) {
+      r.matched_map_points.push_back(matched[f] >= 0 ? std::optional<size_t>((size_t)matched[f]) : std::nullopt);
+      r.matched_slot.push_back(mslot[f]);
+    }
+    for (int i = off[b]; i < off[b + 1]; ++i) {
+      r.points3d.push_back({p3[3 * (size_t)i], p3[3 * (size_t)i + 1], p3[3 * (size_t)i + 2]});
+      r.points2d.push_back({p2[2 * (size_t)i], p2[2 * (size_t)i + 1]});
+      r.mp_idx.push_back(mi[i]); r.feat_idx.push_back(fi[i]);
+      if (too_few) continue;                                    // :937-946: the three vectors stay empty
+      r.reproj_errors_full.push_back(err[i]);
+      (inl[i] ? r.inlier_indices : r.outlier_indices).push_back((size_t)(i - off[b]));
+    }
+  }
+  return out;
+}
+
+// tracker.rs:826-988 on one frame with the local map taken from the store: the distinct live slots of `keyframes` (K1 u K2, chosen
+// by the caller) in first-seen order.
+inline MapTrackResult track_local_map(Handle& h, const CameraModel& camera, MapPointStore& store, const FeatureSet& features,
+                                      const std::vector<const orbx_keyframe*>& keyframes, const SE3& pose, const SE3& imu_prior) {
+  return map_track_frames(h, camera, store, {MapTrackFrame{&features, keyframes, {}, pose, imu_prior}}, ORBX_MAP_SOURCE_KEYFRAMES, 1)[0];
+}
+
+// tracker.rs:1086-1192 on one frame: `slots` = the previous frame's matched_slot (-1 entries and slots no longer live are skipped).
+inline MapTrackResult track_with_motion_model(Handle& h, const CameraModel& camera, MapPointStore& store, const FeatureSet& features,
+                                              const std::vector<int>& slots, const SE3& predicted_pose) {
+  return map_track_frames(h, camera, store, {MapTrackFrame{&features, {}, slots, predicted_pose, predicted_pose}}, ORBX_MAP_SOURCE_SLOTS, 0)[0];
+}
+
 // ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
 // One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
 // validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).

@@ -97,7 +97,11 @@ ABI_SYMBOLS = [
     "orbx_default_sim3_config", "orbx_default_loop_verify_config", "orbx_sim3_ransac_batch", "orbx_sim3_ransac_batch_device",
     "orbx_verify_loop_candidates", "orbx_verify_loop_candidates_device", "orbx_keyframe_verify_loop_candidates",
     "orbx_refresh_map_points", "orbx_refresh_map_points_device", "orbx_keyframe_refresh_map_points",
+    "orbx_map_points_create", "orbx_map_points_destroy", "orbx_map_points_info", "orbx_map_points_set", "orbx_map_points_set_device",
+    "orbx_map_points_erase", "orbx_map_points_download", "orbx_keyframe_set_map_point_slots", "orbx_map_select_points_device",
+    "orbx_map_track_frames_device", "orbx_map_track_frames", "orbx_map_track_reference_device",
 ]
+MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 
 
 BOW_VECTORS_MAX = 8192      # descriptors per orbx_bow_vectors call (bow_kernels.hip: BOWV_MAX)
@@ -1030,6 +1034,143 @@ class Handle:
             o[k] = o[k][:K]
         return o
 
+    # ---- resident map points (include/orbx.h, "resident map points") ----
+    def _map_source(self, mp, keyframes, src_slots, src_offsets):
+        """The source arguments of the orbx_map_* calls and the host-known bound of every frame's list: keyframes = one list of
+        KeyFrame per frame (MAP_SOURCE_KEYFRAMES), or src_slots (int32, one array of all frames' entries) with src_offsets [B+1]
+        (MAP_SOURCE_SLOTS).  -> (source, kfs, kf_offsets, src_slots, src_offsets, bounds [B], keep-alive)"""
+        if (keyframes is None) == (src_slots is None):
+            raise ValueError("give keyframes (one list per frame) or src_slots with src_offsets")
+        if keyframes is not None:
+            flat = [k for ks in keyframes for k in ks]
+            ko = np.zeros(len(keyframes) + 1, np.int32); ko[1:] = np.cumsum([len(ks) for ks in keyframes])
+            arr = (C.c_void_p * max(len(flat), 1))(*[k._p for k in flat])
+            bounds = [min(sum(k.n for k in ks), mp.capacity) for ks in keyframes]
+            return MAP_SOURCE_KEYFRAMES, arr, _vp(ko), None, None, bounds, (arr, ko)
+        so = np.ascontiguousarray(src_offsets, np.int32).reshape(-1)
+        return MAP_SOURCE_SLOTS, None, None, _vp(src_slots), _vp(so), [int(x) for x in np.diff(so)], (so, src_slots)
+
+    def _map_list_outputs(self, B, cap, dev):
+        import torch
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        return dict(list_offsets=mk(max(B, 0) + 1, torch.int32), list_slot=mk(max(cap, 1), torch.int32), positions=mk((max(cap, 1), 3), torch.float64),
+                    mp_desc=mk((max(cap, 1), 32), torch.uint8))
+
+    def map_select_points_device(self, mp: "MapPointStore", keyframes=None, src_slots=None, src_offsets=None, device=None):
+        """Every frame's list of map points from the resident store, made on the device (orbx_map_select_points_device): the distinct
+        live slots of the frame's keyframes in first-seen order (keyframes: one list of KeyFrame per frame), or the live entries of
+        the frame's slot array in order, repeats kept (src_slots: an int32 CUDA tensor, src_offsets: host [B+1]).  Returns a dict of
+        tensors: list_offsets [B+1] int32, list_slot [cap] int32, positions [cap,3] f64, mp_desc [cap,32] u8, cap = the sum of the
+        frames' bounds; rows [0, list_offsets[B]) are written.  Asynchronous on the handle's stream."""
+        import torch
+        src, kfs, ko, ss, so, bounds, keep = self._map_source(mp, keyframes, src_slots, src_offsets)
+        B, cap = len(bounds), int(sum(bounds))
+        dev = device or (src_slots.device if src_slots is not None else torch.device("cuda", self.device))
+        o = self._map_list_outputs(B, cap, dev)
+        self._after_torch(*([src_slots] if src_slots is not None else []), *o.values())
+        self._check(self._L.orbx_map_select_points_device(self._h, mp._p, C.c_int(src), C.c_int(B), kfs, ko, ss, so, C.c_int(cap), _vp(o["list_offsets"]),
+                                                          _vp(o["list_slot"]), _vp(o["positions"]), _vp(o["mp_desc"])))
+        return o
+
+    def map_track_frames_device(self, camera, mp: "MapPointStore", kp, desc, feat_start, feat_count, max_feat, search_poses_wc, priors_wc,
+                                keyframes=None, src_slots=None, src_offsets=None, cfg: "TrackConfig" = None, pnp_cfg: PnPConfig = None):
+        """track_frames_device with the map points taken from the resident store: the selection of map_select_points_device, then the
+        tracker's launches on the lists where they lie.  Frames, poses and configurations as track_frames_device; the source as
+        map_select_points_device.  Returns that call's dict (arrays sized by the lists' bound instead of M) plus list_offsets,
+        list_slot, positions, mp_desc and matched_slot [B,max_feat] int32: matched mapped through the list to slots, -1 = none —
+        matched_slot.view(-1) with src_offsets = arange(B+1) * max_feat is the next frame's slot source."""
+        import torch
+        src, kfs, ko, ss, so, bounds, keep = self._map_source(mp, keyframes, src_slots, src_offsets)
+        B, M = len(bounds), int(sum(bounds))
+        dev = search_poses_wc.device
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(offsets=mk(max(B, 0) + 1, torch.int32), points3d=mk((max(M, 1), 3), torch.float64), points2d=mk((max(M, 1), 2), torch.float32),
+                 mp_idx=mk(max(M, 1), torch.int32), feat_idx=mk(max(M, 1), torch.int32), poses=mk((max(B, 1), 7), torch.float64),
+                 inlier=mk(max(M, 1), torch.uint8), err=mk(max(M, 1), torch.float64), pnp_results=mk((max(B, 1), PNP_RESULT.itemsize), torch.uint8),
+                 matched=mk((max(B, 1), max(int(max_feat), 1)), torch.int32), matched_slot=mk((max(B, 1), max(int(max_feat), 1)), torch.int32),
+                 results=mk((max(B, 1), TRACK_RESULT.itemsize), torch.uint8))
+        o.update(self._map_list_outputs(B, M, dev))
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        fc_stride = self._feat_count_stride(feat_count, B)
+        self._after_torch(kp, desc, feat_start, feat_count, search_poses_wc, priors_wc, *([src_slots] if src_slots is not None else []), *o.values())
+        self._check(self._L.orbx_map_track_frames_device(
+            self._h, C.byref(cam), C.byref(c), C.byref(pc), mp._p, C.c_int(src), C.c_int(B), kfs, ko, ss, so, _vp(kp), _vp(desc), _vp(feat_start),
+            _vp(feat_count), C.c_int(fc_stride), C.c_int(int(max_feat)), _vp(search_poses_wc), _vp(priors_wc), C.c_int(M), _vp(o["list_offsets"]),
+            _vp(o["list_slot"]), _vp(o["positions"]), _vp(o["mp_desc"]), _vp(o["offsets"]), _vp(o["points3d"]), _vp(o["points2d"]), _vp(o["mp_idx"]),
+            _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]), _vp(o["err"]), _vp(o["pnp_results"]), _vp(o["matched"]), _vp(o["matched_slot"]),
+            _vp(o["results"])))
+        o["matched"] = o["matched"][:, :int(max_feat)]; o["matched_slot"] = o["matched_slot"][:, :int(max_feat)]
+        for k in ("points3d", "points2d", "mp_idx", "feat_idx", "inlier", "err", "list_slot", "positions", "mp_desc"):
+            o[k] = o[k][:M]
+        return o
+
+    def map_track_frames(self, camera, mp: "MapPointStore", frames, keyframes=None, src_slots=None, cfg: "TrackConfig" = None,
+                         pnp_cfg: PnPConfig = None):
+        """The host form (orbx_map_track_frames): frames = [(kp, desc, search_pose_wc, prior_wc), ...] in host arrays; the source is
+        keyframes (one list of KeyFrame per frame) or src_slots (one host int32 array per frame).  One upload, one download.
+        Returns [(TrackFrameResult, list_slot, matched_slot), ...]: the frame's result as track_frames gives it (mp_idx and matched
+        index the frame's list), the list's slots and matched as slots."""
+        B = len(frames)
+        so = None
+        if src_slots is not None:
+            parts = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in src_slots]
+            so = np.zeros(B + 1, np.int32); so[1:] = np.cumsum([len(a) for a in parts])
+            src_slots = np.concatenate(parts + [np.zeros(1, np.int32)])
+        src, kfs, ko, ss, so_p, bounds, keep = self._map_source(mp, keyframes, src_slots, so)
+        if len(bounds) != B:
+            raise ValueError("one source per frame")
+        kps = [np.ascontiguousarray(f[0], KEYPOINT).reshape(-1) for f in frames]
+        des = [np.ascontiguousarray(f[1], np.uint8).reshape(-1, 32) for f in frames]
+        if any(len(a) != len(b) for a, b in zip(kps, des)):
+            raise ValueError("keypoints / descriptors differ in length")
+        fo = np.zeros(B + 1, np.int32); fo[1:] = np.cumsum([len(a) for a in kps])
+        NF, M = int(fo[-1]), int(sum(bounds))
+        kp = np.concatenate(kps) if NF else np.zeros(1, KEYPOINT)
+        de = np.concatenate(des) if NF else np.zeros((1, 32), np.uint8)
+        sp = np.ascontiguousarray(np.stack([np.asarray(f[2], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        pr = np.ascontiguousarray(np.stack([np.asarray(f[3], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        Mz, Bz = max(M, 1), max(B, 1)
+        lo = np.zeros(B + 1, np.int32); ls = np.zeros(Mz, np.int32); off = np.zeros(B + 1, np.int32)
+        p3 = np.zeros((Mz, 3)); p2 = np.zeros((Mz, 2), np.float32); mi = np.zeros(Mz, np.int32); fi = np.zeros(Mz, np.int32)
+        poses = np.zeros((Bz, 7)); inl = np.zeros(Mz, np.uint8); err = np.zeros(Mz)
+        pres = np.zeros(Bz, PNP_RESULT); matched = np.zeros(max(NF, 1), np.int32); mslot = np.zeros(max(NF, 1), np.int32); res = np.zeros(Bz, TRACK_RESULT)
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_map_track_frames(
+            self._h, C.byref(cam), C.byref(c), C.byref(pc), mp._p, C.c_int(src), C.c_int(B), kfs, ko, ss, so_p, _vp(kp), _vp(de), _vp(fo), _vp(sp), _vp(pr),
+            C.c_int(M), _vp(lo), _vp(ls), _vp(off), _vp(p3), _vp(p2), _vp(mi), _vp(fi), _vp(poses), _vp(inl), _vp(err), _vp(pres), _vp(matched), _vp(mslot),
+            _vp(res)))
+        out = []
+        for b in range(B):
+            s = slice(int(off[b]), int(off[b + 1]))
+            t = TrackFrameResult(poses[b].copy(), int(res[b]["n_inliers"]), matched[fo[b]:fo[b + 1]].copy(), err[s].copy(), inl[s].astype(bool), p3[s].copy(),
+                                 p2[s].copy(), mi[s].copy(), fi[s].copy(), int(res[b]["status"]), int(res[b]["n_in_front"]), _pnp_stats(pres[b]))
+            out.append((t, ls[lo[b]:lo[b + 1]].copy(), mslot[fo[b]:fo[b + 1]].copy()))
+        return out
+
+    def map_track_reference_device(self, camera, mp: "MapPointStore", keyframes, kp, desc, feat_start, feat_count, max_feat, priors_wc,
+                                   min_correspondences=4, pnp_cfg: PnPConfig = None):
+        """keyframe_track_reference with kf_positions / kf_valid made on the device from every keyframe's slot table and the store
+        (valid = the feature has a slot and the slot is live; positions = that slot's, else zeros).  Returns that call's dict plus
+        kf_positions [K,3] f64 and kf_valid [K] u8 as the kernels read them."""
+        import torch
+        B = len(keyframes)
+        K = int(sum(k.n for k in keyframes))
+        arr = (C.c_void_p * max(B, 1))(*[k._p for k in keyframes])
+        o = self._track_reference_outputs(B, K, priors_wc.device)
+        o["kf_positions"] = torch.empty((max(K, 1), 3), dtype=torch.float64, device=priors_wc.device)
+        o["kf_valid"] = torch.empty(max(K, 1), dtype=torch.uint8, device=priors_wc.device)
+        pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        fc_stride = self._feat_count_stride(feat_count, B)
+        self._after_torch(kp, desc, feat_start, feat_count, priors_wc, *o.values())
+        self._check(self._L.orbx_map_track_reference_device(
+            self._h, C.byref(cam), C.byref(pc), C.c_int(int(min_correspondences)), mp._p, C.c_int(B), arr, _vp(kp), _vp(desc), _vp(feat_start),
+            _vp(feat_count), C.c_int(fc_stride), C.c_int(int(max_feat)), _vp(priors_wc), _vp(o["kf_positions"]), _vp(o["kf_valid"]), _vp(o["matches"]),
+            _vp(o["offsets"]), _vp(o["points3d"]), _vp(o["points2d"]), _vp(o["kf_idx"]), _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]),
+            _vp(o["err"]), _vp(o["pnp_results"]), _vp(o["results"])))
+        for k in ("matches", "points3d", "points2d", "kf_idx", "feat_idx", "inlier", "err", "kf_positions", "kf_valid"):
+            o[k] = o[k][:K]
+        return o
+
     def compute_sim3_ransac_batch(self, problems, cfg: "Sim3SolverConfig" = None):
         """compute_sim3_ransac (sim3_solver.rs:63-145) for many point sets [(points1 [n,3], points2 [n,3]), ...] in one call (one
         upload, one download).  Returns (sim3 [P,8], inlier masks (list of [n] u8), results [P] SIM3_RESULT); each problem's bytes
@@ -1906,6 +2047,16 @@ class KeyFrame:
         assert len(a) == self.n
         self._handle._check(self._L.orbx_keyframe_set_map_points(self._p, _vp(a)))
 
+    def set_map_point_slots(self, mp: "MapPointStore", slots):
+        """The per-feature slot table [n] (int, -1 or None = no map point) against the resident store `mp`, kept in the keyframe's
+        device block; slots=None clears it.  set_map_points and the ids are untouched."""
+        if slots is None:
+            self._handle._check(self._L.orbx_keyframe_set_map_point_slots(self._p, None, None))
+            return
+        a = np.array([-1 if m is None else int(m) for m in slots], np.int32)
+        assert len(a) == self.n
+        self._handle._check(self._L.orbx_keyframe_set_map_point_slots(self._p, mp._p, _vp(a if self.n else np.zeros(1, np.int32))))
+
     def map_points(self):
         a = np.zeros(max(self.n, 1), np.int64)
         self._handle._check(self._L.orbx_keyframe_get_map_points(self._p, _vp(a)))
@@ -2017,6 +2168,76 @@ class KeyFrame:
     def close(self):
         if self._p:
             self._L.orbx_keyframe_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            if self._handle._h:
+                self.close()
+        except Exception:
+            pass
+
+
+class MapPointStore:
+    """orbx_map_points: map points resident on the GPU — per slot a position, a descriptor and a live byte.  capacity is fixed; the
+    caller owns the id -> slot assignment.  All work is ordered on the handle's stream."""
+
+    def __init__(self, handle: "Handle", capacity: int):
+        self._handle = handle
+        self._L = handle._L
+        L = self._L
+        L.orbx_map_points_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.orbx_map_points_destroy.argtypes = [C.c_void_p]; L.orbx_map_points_destroy.restype = None
+        L.orbx_map_points_info.argtypes = [C.c_void_p] * 3
+        for name in ("orbx_map_points_set", "orbx_map_points_set_device"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orbx_map_points_erase.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.orbx_map_points_download.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orbx_keyframe_set_map_point_slots.argtypes = [C.c_void_p] * 3
+        self._p = C.c_void_p()
+        handle._check(L.orbx_map_points_create(handle._h, int(capacity), C.byref(self._p)))
+        self.capacity = int(capacity)
+
+    @staticmethod
+    def _slots(slots):
+        a = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        return a, (a if len(a) else np.zeros(1, np.int32))
+
+    def set(self, slots, positions=None, descriptors=None):
+        """rows of positions [n,3] f64 / descriptors [n,32] u8 (host arrays; either may be None: the field stays) into slots [n]"""
+        a, ap = self._slots(slots)
+        po = None if positions is None else np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        de = None if descriptors is None else np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        if (po is not None and len(po) != len(a)) or (de is not None and len(de) != len(a)):
+            raise ValueError("one row per slot")
+        self._handle._check(self._L.orbx_map_points_set(self._p, _vp(ap), len(a), _vp(po), _vp(de)))
+
+    def set_device(self, slots, positions=None, descriptors=None):
+        """the same from CUDA tensors (positions [n,3] f64, descriptors [n,32] u8, contiguous); slots stays a host array.  Asynchronous."""
+        a, ap = self._slots(slots)
+        self._handle._after_torch(*[t for t in (positions, descriptors) if t is not None])
+        self._handle._check(self._L.orbx_map_points_set_device(self._p, _vp(ap), len(a), _vp(positions), _vp(descriptors)))
+
+    def erase(self, slots):
+        a, ap = self._slots(slots)
+        self._handle._check(self._L.orbx_map_points_erase(self._p, _vp(ap), len(a)))
+
+    def download(self, slots=None):
+        """(positions [n,3], descriptors [n,32], live [n]) of the listed slots (default: all).  Synchronous."""
+        a, ap = self._slots(np.arange(self.capacity) if slots is None else slots)
+        n = len(a)
+        po = np.zeros((max(n, 1), 3)); de = np.zeros((max(n, 1), 32), np.uint8); li = np.zeros(max(n, 1), np.uint8)
+        self._handle._check(self._L.orbx_map_points_download(self._p, _vp(ap), n, _vp(po), _vp(de), _vp(li)))
+        return po[:n], de[:n], li[:n]
+
+    def info(self):
+        cap = C.c_int(); live = C.c_int()
+        self._handle._check(self._L.orbx_map_points_info(self._p, C.byref(cap), C.byref(live)))
+        return dict(capacity=cap.value, n_live=live.value)
+
+    def close(self):
+        if self._p:
+            self._L.orbx_map_points_destroy(self._p)
             self._p = None
 
     def __del__(self):

@@ -9,26 +9,6 @@
 
 #include "orbx_internal.hpp"
 
-struct orbx_keyframe {
-  orbx_handle* h = nullptr;
-  uint64_t id = 0, timestamp_ns = 0;
-  double pose_wc[7] = {1, 0, 0, 0, 0, 0, 0};
-  int n = 0;
-  uint8_t* block = nullptr;          // one device allocation: kp | desc | points_cam | has_point | mp_flag
-  orbx_keypoint* d_kp = nullptr;
-  uint8_t* d_desc = nullptr;
-  double* d_points = nullptr;
-  uint8_t* d_has_point = nullptr;
-  uint8_t* d_mp_flag = nullptr;
-  std::vector<int64_t> mp_ids;       // matched_map_points (host side: ids are map bookkeeping), -1 = None
-  // FeatureVector as one node id per feature (orbx_keyframe_set_feature_nodes): host copy, and the feature indices sorted by
-  // (node, index) with the features in no list cut off the end — every node's list in push order (vocabulary/mod.rs:309)
-  bool has_nodes = false;
-  std::vector<uint32_t> node;
-  std::vector<int> node_sorted;
-  int node_m = 0;
-};
-
 extern "C" {
 
 int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t* d_desc, int n, const double* d_points_cam,
@@ -46,10 +26,10 @@ int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_
   const size_t n1 = (size_t)(n > 0 ? n : 1);
   Carve blk;
   const size_t o_kp = blk.take(sizeof(orbx_keypoint) * n1), o_desc = blk.take(32 * n1), o_pts = blk.take(24 * n1), o_has = blk.take(n1), o_mp = blk.take(n1),
-               total = blk.off;
+               o_slot = blk.take(4 * n1), total = blk.off;
   if (hipMalloc((void**)&kf->block, total) != hipSuccess) { delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: out of device memory"); }
   kf->d_kp = (orbx_keypoint*)(kf->block + o_kp); kf->d_desc = kf->block + o_desc; kf->d_points = (double*)(kf->block + o_pts);
-  kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp;
+  kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp; kf->d_mp_slot = (int*)(kf->block + o_slot);
   hipStream_t st = h->stream;
   hipError_t e = hipMemsetAsync(kf->block + o_pts, 0, total - o_pts, st);       // points (0,0,0), no stereo point, no map point
   if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_kp, d_kp, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyDeviceToDevice, st);

@@ -1,0 +1,645 @@
+// map_store_kernels.hip — orbx_map_points: map points resident on the device, and the calls that turn "these keyframes" or "these
+// slots" into a frame's list of map points without a host round trip (include/orbx.h, "resident map points").
+//
+// Replaces, per frame and with no host synchronisation inside:
+//   src/tracking/tracker.rs:826-867    track_local_map: get_map_points_from_keyframes (map.rs:492-504), the lookups, the two arrays
+//   src/tracking/tracker.rs:1093-1102  track_with_motion_model: the previous frame's matched points, looked up
+//   src/tracking/tracker.rs:1024-1036  track_with_reference_kf: kf.get_map_point(i) and the map lookup per keyframe feature
+//
+// The selection is three launches over (chunk of MS_CHUNK candidates, frame); a candidate is one feature of one of the frame's
+// keyframes (or one entry of its slot array), numbered in walking order:
+//   map_mark_kernel   (keyframes only) slot of every candidate; first[frame][slot] = atomicMin(candidate number) — the table says
+//                     where a slot was first seen, whatever the execution order
+//   map_flag_kernel   a candidate survives iff the table holds its own number; the survivor puts the table's entry back to EMPTY,
+//                     so that a call leaves the table as it found it and costs what its candidates cost, not what the map holds;
+//                     per chunk the number of survivors
+//   map_emit_kernel   a chunk's base = the survivors of all chunks before it (earlier frames, then earlier chunks); ordered
+//                     compaction inside the chunk by ballot / prefix; list_slot, positions and descriptors gathered
+// Every frame has a table of its own ([frame][capacity]), so frames of one call that share keyframes do not meet.  The only atomics
+// are that integer min: every output is a deterministic function of the inputs.
+#include <algorithm>
+#include <vector>
+
+#include "orbx_internal.hpp"
+
+struct orbx_map_points {
+  orbx_handle* h = nullptr;
+  int capacity = 0, n_live = 0;
+  uint8_t* block = nullptr;            // one device allocation: positions | descriptors | live
+  double* d_pos = nullptr;
+  uint8_t* d_desc = nullptr;
+  uint8_t* d_live = nullptr;
+  std::vector<uint8_t> live;           // host mirror of d_live: every change goes through set / set_device / erase, whose slots are host arrays
+  std::vector<unsigned> stamp;         // per slot the last call that named it (a slot listed twice in one call is refused)
+  unsigned gen = 0;
+  DevBuf first;                        // [frames][capacity] first-sighting tables, EMPTY between calls
+};
+
+namespace {
+
+constexpr int MS_THREADS = 256;
+constexpr int MS_PER = 4;                        // consecutive candidates per thread
+constexpr int MS_CHUNK = MS_THREADS * MS_PER;    // candidates per workgroup
+constexpr int MS_EMPTY = 0x7f7f7f7f;             // (one byte repeated: the tables are filled by a memset when they are allocated)
+
+// One keyframe of one frame: its slot table (NULL: no table, every feature -1), the number of its first candidate, its features.
+struct MapSeg {
+  const int* slots;
+  int base, n;
+};
+struct MapRefItem {
+  const int* slots;
+  int off, n;
+};
+
+struct SelArgs {
+  int source, capacity, n_chunk;
+  const uint8_t* live; const double* pos; const uint8_t* desc;
+  const MapSeg* segs; const int* seg_off;        // keyframes: frame b's segments are [seg_off[b], seg_off[b+1])
+  const int* src; const int* src_off;            // slots: frame b's entries are src[src_off[b] .. src_off[b+1])
+  const int* n_cand;                             // [B]
+  int* first; int* cand; int* chunk_count;
+  int* list_off; int* list_slot; double* out_pos; uint8_t* out_desc;
+};
+
+__device__ __forceinline__ int ms_block_sum(int v, int* wave_tot) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();                                                        // (wave_tot may still be read from an earlier use)
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void map_mark_kernel(SelArgs A) {
+  const int b = blockIdx.y, C = A.n_cand[b];
+  const int p0 = blockIdx.x * MS_CHUNK + threadIdx.x * MS_PER;
+  int* cand = A.cand + (size_t)b * A.n_chunk * MS_CHUNK;
+  int* first = A.first + (size_t)b * A.capacity;
+  int s = A.seg_off[b];
+  const int s1 = A.seg_off[b + 1];
+#pragma unroll
+  for (int k = 0; k < MS_PER; ++k) {
+    const int p = p0 + k;
+    int slot = -1;
+    if (p < C) {
+      while (s < s1 && p >= A.segs[s].base + A.segs[s].n) ++s;            // (p < C: it ends inside the frame's segments)
+      if (s < s1) {
+        const MapSeg g = A.segs[s];
+        if (g.slots) slot = g.slots[p - g.base];
+      }
+      if (slot < 0 || slot >= A.capacity || !A.live[slot]) slot = -1;
+      else atomicMin(&first[slot], p);
+    }
+    cand[p] = slot;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void map_flag_kernel(SelArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int b = blockIdx.y, C = A.n_cand[b];
+  const int p0 = blockIdx.x * MS_CHUNK + threadIdx.x * MS_PER;
+  int* cand = A.cand + (size_t)b * A.n_chunk * MS_CHUNK;
+  int n = 0;
+  if (A.source == ORBX_MAP_SOURCE_KEYFRAMES) {
+    int* first = A.first + (size_t)b * A.capacity;
+#pragma unroll
+    for (int k = 0; k < MS_PER; ++k) {
+      const int p = p0 + k, slot = cand[p];
+      if (slot < 0) continue;
+      // only the candidate the table names writes it (back to EMPTY); the others read its number or EMPTY, never their own
+      if (__hip_atomic_load(&first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p) {
+        __hip_atomic_store(&first[slot], MS_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ++n;
+      } else {
+        cand[p] = -1;
+      }
+    }
+  } else {
+    const int* src = A.src + A.src_off[b];
+#pragma unroll
+    for (int k = 0; k < MS_PER; ++k) {
+      const int p = p0 + k;
+      int slot = p < C ? src[p] : -1;
+      if (slot < 0 || slot >= A.capacity || !A.live[slot]) slot = -1;
+      cand[p] = slot;
+      n += slot >= 0;
+    }
+  }
+  n = ms_block_sum(n, wave_tot);
+  if (threadIdx.x == 0) A.chunk_count[b * A.n_chunk + blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void map_emit_kernel(SelArgs A, int B) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int me = b * A.n_chunk + blockIdx.x;
+  int part = 0;
+  for (int j = tid; j < me; j += MS_THREADS) part += A.chunk_count[j];
+  const int base = ms_block_sum(part, wave_tot);
+  if (tid == 0) {
+    if (blockIdx.x == 0) A.list_off[b] = base;
+    if (me == B * A.n_chunk - 1) A.list_off[B] = base + A.chunk_count[me];
+  }
+  const int* cand = A.cand + (size_t)b * A.n_chunk * MS_CHUNK + (size_t)blockIdx.x * MS_CHUNK + tid * MS_PER;
+  int slot[MS_PER], n = 0;
+#pragma unroll
+  for (int k = 0; k < MS_PER; ++k) { slot[k] = cand[k]; n += slot[k] >= 0; }
+  int incl = n;                                                            // inclusive scan of the threads' counts over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d);
+    if (lane >= d) incl += t;
+  }
+  __syncthreads();
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  size_t o = (size_t)base + (incl - n);
+  for (int w = 0; w < wave; ++w) o += wave_tot[w];
+#pragma unroll
+  for (int k = 0; k < MS_PER; ++k) {
+    const int s = slot[k];
+    if (s < 0) continue;
+    A.list_slot[o] = s;
+    A.out_pos[3 * o] = A.pos[3 * (size_t)s]; A.out_pos[3 * o + 1] = A.pos[3 * (size_t)s + 1]; A.out_pos[3 * o + 2] = A.pos[3 * (size_t)s + 2];
+    const uint4* d = (const uint4*)(A.desc + 32 * (size_t)s);
+    uint4* q = (uint4*)(A.out_desc + 32 * o);
+    q[0] = d[0]; q[1] = d[1];
+    ++o;
+  }
+}
+
+// matched (an index into the frame's list, -1 = none) mapped through the list to slots
+__global__ __launch_bounds__(MS_THREADS) void map_matched_slot_kernel(const int* matched, const int* list_off, const int* list_slot, int max_feat,
+                                                                      int* matched_slot) {
+  const int b = blockIdx.y, f = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (f >= max_feat) return;
+  const size_t i = (size_t)b * max_feat + f;
+  const int m = matched[i];
+  matched_slot[i] = m >= 0 ? list_slot[list_off[b] + m] : -1;
+}
+
+// set / erase: row i of the call goes to slot slots[i] (no slot twice: the host has checked)
+__global__ __launch_bounds__(MS_THREADS) void map_scatter_kernel(const int* slots, int n, const double* pos_in, const uint8_t* desc_in, int live_value,
+                                                                 double* pos, uint8_t* desc, uint8_t* live) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const size_t s = (size_t)slots[i];
+  if (pos_in) { pos[3 * s] = pos_in[3 * (size_t)i]; pos[3 * s + 1] = pos_in[3 * (size_t)i + 1]; pos[3 * s + 2] = pos_in[3 * (size_t)i + 2]; }
+  if (desc_in) {
+    const uint32_t* d = (const uint32_t*)(desc_in + 32 * (size_t)i);       // (the caller's rows: 4-byte aligned, no more is asked)
+    uint32_t* q = (uint32_t*)(desc + 32 * s);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q[k] = d[k];
+  }
+  live[s] = (uint8_t)live_value;
+}
+
+// tracker.rs:1024-1036 per keyframe feature: valid = the feature has a slot and the slot is live; its position, else zeros
+__global__ __launch_bounds__(MS_THREADS) void map_ref_gather_kernel(const MapRefItem* items, const uint8_t* live, const double* pos, int capacity,
+                                                                    double* out_pos, uint8_t* out_valid) {
+  const MapRefItem it = items[blockIdx.y];
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i >= it.n) return;
+  const int s = it.slots ? it.slots[i] : -1;
+  const bool ok = s >= 0 && s < capacity && live[s];
+  const size_t o = (size_t)it.off + i;
+  out_valid[o] = ok ? 1 : 0;
+  out_pos[3 * o] = ok ? pos[3 * (size_t)s] : 0.0; out_pos[3 * o + 1] = ok ? pos[3 * (size_t)s + 1] : 0.0; out_pos[3 * o + 2] = ok ? pos[3 * (size_t)s + 2] : 0.0;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+// slots [n] of a set / erase call: in range, and (once) none twice
+int ms_check_slots(orbx_map_points* mp, const char* who, const int* slots, int n, bool once) {
+  orbx_handle* h = mp->h;
+  if (n < 0 || (n > 0 && !slots)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (++mp->gen == 0) { std::fill(mp->stamp.begin(), mp->stamp.end(), 0u); mp->gen = 1; }
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= mp->capacity) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d (entry %d) is outside [0, %d)", who, slots[i], i, mp->capacity);
+    if (once && mp->stamp[(size_t)slots[i]] == mp->gen) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d is listed twice (entry %d)", who, slots[i], i);
+    mp->stamp[(size_t)slots[i]] = mp->gen;
+  }
+  return ORBX_OK;
+}
+
+// set and set_device: the slots (and the host form's rows) go up through the upload ring, then one scatter launch
+int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const double* positions, const uint8_t* desc, bool on_host) {
+  orbx_handle* h = mp->h;
+  if (int rc = ms_check_slots(mp, who, slots, n, true)) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!mp->live[(size_t)slots[i]] && (!positions || !desc))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d is not live yet: its first set needs positions and descriptors", who, slots[i]);
+  if (n == 0 || (!positions && !desc)) return ORBX_OK;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  Carve up;
+  const size_t N = (size_t)n, o_sl = up.take(4 * N), o_po = up.take(on_host && positions ? 24 * N : 0), o_de = up.take(on_host && desc ? 32 * N : 0);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
+  std::memcpy(hs + o_sl, slots, 4 * N);
+  if (on_host && positions) std::memcpy(hs + o_po, positions, 24 * N);
+  if (on_host && desc) std::memcpy(hs + o_de, desc, 32 * N);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
+  const double* d_pos = !positions ? nullptr : on_host ? (const double*)(ds + o_po) : positions;
+  const uint8_t* d_desc = !desc ? nullptr : on_host ? ds + o_de : desc;
+  {
+    ProfScope ps(h, "map_scatter_kernel");
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, (const int*)(ds + o_sl), n, d_pos, d_desc, 1,
+                       mp->d_pos, mp->d_desc, mp->d_live);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  for (int i = 0; i < n; ++i)
+    if (!mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 1; ++mp->n_live; }
+  return ORBX_OK;
+}
+
+// What a selection call is, checked and sized on the host: per frame the candidates and the bound of its list.
+struct SelPlan {
+  std::vector<MapSeg> segs;
+  std::vector<int> seg_off, n_cand, bound_off;       // bound_off [B+1]: offsets of the lists' host-known bounds
+  int max_cand = 0, max_bound = 0;
+};
+
+int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int source, int B, const orbx_keyframe* const* kfs, const int* kf_offsets,
+            const int* src_offsets, SelPlan& P) {
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
+  if (source != ORBX_MAP_SOURCE_KEYFRAMES && source != ORBX_MAP_SOURCE_SLOTS) return orbx_fail(h, ORBX_ERR_INVALID, "%s: unknown source kind %d", who, source);
+  P.n_cand.assign((size_t)B, 0); P.bound_off.assign((size_t)B + 1, 0); P.seg_off.assign((size_t)B + 1, 0);
+  long long total = 0;
+  if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
+    if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", B, kf_offsets)) return rc;
+    if (kf_offsets[B] > 0 && !kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    P.segs.reserve((size_t)kf_offsets[B]);
+    for (int b = 0; b < B; ++b) {
+      long long c = 0;
+      for (int t = kf_offsets[b]; t < kf_offsets[b + 1]; ++t) {
+        const orbx_keyframe* kf = kfs[t];
+        if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
+        if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+        P.segs.push_back(MapSeg{kf->slot_store ? kf->d_mp_slot : nullptr, (int)c, kf->n});
+        c += kf->n;
+        if (c >= MS_EMPTY) return orbx_fail(h, ORBX_ERR_INVALID, "%s: frame %d has too many candidates", who, b);
+      }
+      P.seg_off[(size_t)b + 1] = (int)P.segs.size();
+      P.n_cand[(size_t)b] = (int)c;
+      const int bound = (int)std::min<long long>(c, mp->capacity);        // distinct slots: never more than the store holds
+      total += bound;
+      P.max_cand = std::max(P.max_cand, (int)c); P.max_bound = std::max(P.max_bound, bound);
+      P.bound_off[(size_t)b + 1] = (int)std::min<long long>(total, 0x7fffffff);
+    }
+  } else {
+    if (int rc = orbx_check_offsets(h, who, "src_offsets", "frame", B, src_offsets, &P.max_cand)) return rc;
+    for (int b = 0; b < B; ++b) { P.n_cand[(size_t)b] = src_offsets[b + 1] - src_offsets[b]; P.bound_off[(size_t)b + 1] = src_offsets[b + 1]; }
+    P.max_bound = P.max_cand;                                               // no de-duplication: a list may be as long as its source
+    total = src_offsets[B];
+  }
+  if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the lists' bounds exceed 2^31 - 1 rows", who);
+  return ORBX_OK;
+}
+
+// The three launches on the handle's stream.  d_src_slots and every output are device memory; list_cap: rows the outputs hold.
+int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int source, int B, const SelPlan& P, const int* d_src_slots, const int* src_offsets,
+                      int list_cap, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
+  const int total = P.bound_off[(size_t)B];
+  if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (the sum over the frames of their candidates, "
+                                         "per frame at most the capacity where keyframes are the source)", who, list_cap, total);
+  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15) ||
+      (source == ORBX_MAP_SOURCE_SLOTS && total > 0 && !d_src_slots))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)B;
+  if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
+    const size_t need = 4 * Bz * (size_t)mp->capacity;
+    if (mp->first.bytes < need) {                                           // the one fill of the tables: calls leave them EMPTY
+      if (int rc = orbx_reserve(h, mp->first, need)) return rc;
+      ORBX_HIP(h, hipMemsetAsync(mp->first.p, MS_EMPTY & 0xff, mp->first.bytes, h->stream));
+    }
+  }
+  const int n_chunk = std::max(1, (P.max_cand + MS_CHUNK - 1) / MS_CHUNK);
+  Carve up, ws;
+  const size_t o_sg = up.take(sizeof(MapSeg) * P.segs.size()), o_so = up.take(4 * (Bz + 1)), o_nc = up.take(4 * Bz), o_sr = up.take(4 * (Bz + 1));
+  const size_t o_ca = ws.take(4 * Bz * (size_t)n_chunk * MS_CHUNK), o_cc = ws.take(4 * Bz * (size_t)n_chunk);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
+  if (!P.segs.empty()) std::memcpy(hs + o_sg, P.segs.data(), sizeof(MapSeg) * P.segs.size());
+  std::memcpy(hs + o_so, P.seg_off.data(), 4 * (Bz + 1));
+  std::memcpy(hs + o_nc, P.n_cand.data(), 4 * Bz);
+  if (source == ORBX_MAP_SOURCE_SLOTS) std::memcpy(hs + o_sr, src_offsets, 4 * (Bz + 1));
+  else std::memset(hs + o_sr, 0, 4 * (Bz + 1));
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_map[0], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[0].p;
+  SelArgs A{};
+  A.source = source; A.capacity = mp->capacity; A.n_chunk = n_chunk;
+  A.live = mp->d_live; A.pos = mp->d_pos; A.desc = mp->d_desc;
+  A.segs = (const MapSeg*)(ds + o_sg); A.seg_off = (const int*)(ds + o_so); A.n_cand = (const int*)(ds + o_nc);
+  A.src = d_src_slots; A.src_off = (const int*)(ds + o_sr);
+  A.first = (int*)mp->first.p; A.cand = (int*)(w + o_ca); A.chunk_count = (int*)(w + o_cc);
+  A.list_off = d_list_off; A.list_slot = d_list_slot; A.out_pos = d_positions; A.out_desc = d_mp_desc;
+  const dim3 grid(n_chunk, B), block(MS_THREADS);
+  if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
+    ProfScope ps(h, "map_mark_kernel");
+    hipLaunchKernelGGL(map_mark_kernel, grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "map_flag_kernel", source == ORBX_MAP_SOURCE_KEYFRAMES);
+    hipLaunchKernelGGL(map_flag_kernel, grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "map_emit_kernel", true);
+    hipLaunchKernelGGL(map_emit_kernel, grid, block, 0, h->stream, A, B);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+int ms_matched_slot_enqueue(orbx_handle* h, int B, int max_feat, const int* d_matched, const int* d_list_off, const int* d_list_slot, int* d_matched_slot) {
+  if (max_feat <= 0) return ORBX_OK;
+  ProfScope ps(h, "map_matched_slot_kernel", true);
+  hipLaunchKernelGGL(map_matched_slot_kernel, dim3((max_feat + MS_THREADS - 1) / MS_THREADS, B), dim3(MS_THREADS), 0, h->stream, d_matched, d_list_off,
+                     d_list_slot, max_feat, d_matched_slot);
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_map_points_create(orbx_handle* h, int capacity, orbx_map_points** out) {
+  if (!h) return ORBX_ERR_INVALID;
+  if (!out || capacity < 1 || capacity >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_map_points_create: bad argument (1 <= capacity < %d)", MS_EMPTY / 64);
+  *out = nullptr;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  orbx_map_points* mp = new orbx_map_points();
+  mp->h = h; mp->capacity = capacity;
+  mp->live.assign((size_t)capacity, 0); mp->stamp.assign((size_t)capacity, 0u);
+  Carve blk;
+  const size_t o_po = blk.take(24 * (size_t)capacity), o_de = blk.take(32 * (size_t)capacity), o_li = blk.take((size_t)capacity);
+  if (hipMalloc((void**)&mp->block, blk.off) != hipSuccess) { delete mp; return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: out of device memory"); }
+  mp->d_pos = (double*)(mp->block + o_po); mp->d_desc = mp->block + o_de; mp->d_live = mp->block + o_li;
+  if (hipMemsetAsync(mp->block, 0, blk.off, h->stream) != hipSuccess) { hipFree(mp->block); delete mp; return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: memset failed"); }
+  *out = mp;
+  return ORBX_OK;
+}
+
+void orbx_map_points_destroy(orbx_map_points* mp) {
+  if (!mp) return;
+  hipSetDevice(mp->h->device);
+  hipStreamSynchronize(mp->h->stream);
+  if (mp->block) hipFree(mp->block);
+  if (mp->first.p) hipFree(mp->first.p);
+  delete mp;
+}
+
+int orbx_map_points_info(const orbx_map_points* mp, int* capacity, int* n_live) {
+  if (!mp) return ORBX_ERR_INVALID;
+  if (capacity) *capacity = mp->capacity;
+  if (n_live) *n_live = mp->n_live;
+  return ORBX_OK;
+}
+
+int orbx_map_points_set(orbx_map_points* mp, const int* slots, int n, const double* positions, const uint8_t* desc) {
+  if (!mp) return ORBX_ERR_INVALID;
+  return ms_set(mp, "orbx_map_points_set", slots, n, positions, desc, true);
+}
+
+int orbx_map_points_set_device(orbx_map_points* mp, const int* slots, int n, const double* d_positions, const uint8_t* d_desc) {
+  if (!mp) return ORBX_ERR_INVALID;
+  if (((uintptr_t)d_desc & 3) || ((uintptr_t)d_positions & 7)) return orbx_fail(mp->h, ORBX_ERR_INVALID, "orbx_map_points_set_device: d_desc is 4-byte, d_positions 8-byte aligned");
+  return ms_set(mp, "orbx_map_points_set_device", slots, n, d_positions, d_desc, false);
+}
+
+int orbx_map_points_erase(orbx_map_points* mp, const int* slots, int n) {
+  static const char* who = "orbx_map_points_erase";
+  if (!mp) return ORBX_ERR_INVALID;
+  orbx_handle* h = mp->h;
+  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+  if (n == 0) return ORBX_OK;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], 4 * (size_t)n, &hs, &ds)) return rc;
+  std::memcpy(hs, slots, 4 * (size_t)n);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], 4 * (size_t)n)) return rc;
+  {
+    ProfScope ps(h, "map_scatter_kernel");
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, (const int*)ds, n, (const double*)nullptr,
+                       (const uint8_t*)nullptr, 0, mp->d_pos, mp->d_desc, mp->d_live);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  for (int i = 0; i < n; ++i)
+    if (mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 0; --mp->n_live; }
+  return ORBX_OK;
+}
+
+int orbx_map_points_download(orbx_map_points* mp, const int* slots, int n, double* positions, uint8_t* desc, uint8_t* live) {
+  static const char* who = "orbx_map_points_download";
+  if (!mp) return ORBX_ERR_INVALID;
+  orbx_handle* h = mp->h;
+  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+  if (n == 0) return ORBX_OK;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // tests and debugging: the whole store comes down, the rows asked for are picked on the host
+  const size_t cap = (size_t)mp->capacity, bytes = (size_t)((mp->d_live + cap) - mp->block);
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, bytes)) return rc;
+  uint8_t* hp = (uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(hp, mp->block, bytes, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  const double* hpos = (const double*)(hp + ((uint8_t*)mp->d_pos - mp->block));
+  const uint8_t* hdesc = hp + (mp->d_desc - mp->block);
+  const uint8_t* hlive = hp + (mp->d_live - mp->block);
+  for (int i = 0; i < n; ++i) {
+    const size_t s = (size_t)slots[i];
+    if (positions) std::memcpy(positions + 3 * (size_t)i, hpos + 3 * s, 24);
+    if (desc) std::memcpy(desc + 32 * (size_t)i, hdesc + 32 * s, 32);
+    if (live) live[i] = hlive[s];
+  }
+  return ORBX_OK;
+}
+
+int orbx_keyframe_set_map_point_slots(orbx_keyframe* kf, const orbx_map_points* mp, const int* slots) {
+  static const char* who = "orbx_keyframe_set_map_point_slots";
+  if (!kf) return ORBX_ERR_INVALID;
+  orbx_handle* h = kf->h;
+  if (!slots) { kf->slot_store = nullptr; return ORBX_OK; }
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  for (int i = 0; i < kf->n; ++i)
+    if (slots[i] < -1 || slots[i] >= mp->capacity) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d (feature %d) is outside [-1, %d)", who, slots[i], i, mp->capacity);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  if (kf->n > 0) {
+    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_slot, slots, 4 * (size_t)kf->n, hipMemcpyHostToDevice, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));                       // the caller's array is free when the call returns
+  }
+  kf->slot_store = mp;
+  return ORBX_OK;
+}
+
+int orbx_map_select_points_device(orbx_handle* h, orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets,
+                                  const int* d_src_slots, const int* src_offsets, int list_cap, int* d_list_offsets, int* d_list_slot,
+                                  double* d_positions, uint8_t* d_mp_desc) {
+  static const char* who = "orbx_map_select_points_device";
+  if (!h) return ORBX_ERR_INVALID;
+  SelPlan P;
+  if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+  return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+}
+
+int orbx_map_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                                 orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets,
+                                 const int* d_src_slots, const int* src_offsets, const orbx_keypoint* d_kp, const uint8_t* d_desc,
+                                 const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                 const double* d_search_poses_wc, const double* d_priors_wc, int list_cap, int* d_list_offsets, int* d_list_slot,
+                                 double* d_positions, uint8_t* d_mp_desc, int* d_offsets, double* d_pts3d, float* d_pts2d, int* d_mp_idx,
+                                 int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                 orbx_pnp_result* d_pnp_results, int* d_matched, int* d_matched_slot, orbx_track_result* d_results) {
+  static const char* who = "orbx_map_track_frames_device";
+  if (!h) return ORBX_ERR_INVALID;
+  SelPlan P;
+  if (n_frames > 0)
+    if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+  int max_mp = 0;
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, &max_mp, who)) return rc;
+  const int B = n_frames, M = P.bound_off[(size_t)B];
+  if (max_feat < 0 || feat_count_stride < 1 || !d_feat_start || !d_feat_count || !d_search_poses_wc || !d_priors_wc || !d_offsets || !d_poses_wc_out ||
+      !d_pnp_results || !d_results || (max_feat > 0 && (!d_kp || !d_desc || !d_matched || !d_matched_slot)) ||
+      (M > 0 && (!d_pts3d || !d_pts2d || !d_mp_idx || !d_feat_idx || !d_inlier_out || !d_err_out)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  orbx_prof_begin_call(h);
+  if (int rc = ms_select_enqueue(h, who, mp, source, B, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc)) return rc;
+  TrackArgs A{};
+  A.max_feat = max_feat; A.fc_stride = feat_count_stride;
+  A.kp = d_kp; A.desc = d_desc; A.feat_start = d_feat_start; A.feat_count = d_feat_count;
+  A.positions = d_positions; A.mp_desc = d_mp_desc; A.mp_off = d_list_offsets;
+  A.search_poses = d_search_poses_wc; A.priors = d_priors_wc;
+  A.offsets = d_offsets; A.pts3d = d_pts3d; A.pts2d = d_pts2d; A.mp_idx = d_mp_idx; A.feat_idx = d_feat_idx;
+  A.poses_out = d_poses_wc_out; A.matched = d_matched; A.results = d_results;
+  if (int rc = track_launch(h, cam, cfg, pnp_cfg, B, max_mp, (size_t)M, A, d_inlier_out, d_err_out, d_pnp_results)) return rc;
+  return ms_matched_slot_enqueue(h, B, max_feat, d_matched, d_list_offsets, d_list_slot, d_matched_slot);
+}
+
+int orbx_map_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, orbx_map_points* mp,
+                          int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets, const int* src_slots,
+                          const int* src_offsets, const orbx_keypoint* kp, const uint8_t* desc, const int* feat_offsets,
+                          const double* search_poses_wc, const double* priors_wc, int list_cap, int* list_offsets, int* list_slot, int* offsets,
+                          double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out, uint8_t* inlier_out, double* err_out,
+                          orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results) {
+  static const char* who = "orbx_map_track_frames";
+  if (!h) return ORBX_ERR_INVALID;
+  SelPlan P;
+  if (n_frames > 0)
+    if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+  int max_feat = 0, max_mp = 0;
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, &max_mp, who)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
+  const size_t B = (size_t)n_frames, NF = (size_t)feat_offsets[B], M = (size_t)P.bound_off[B], mf = (size_t)max_feat;
+  const size_t S = source == ORBX_MAP_SOURCE_SLOTS ? (size_t)src_offsets[B] : 0;
+  if (list_cap < 0 || (size_t)list_cap < M) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d", who, list_cap, (int)M);
+  if (!search_poses_wc || !priors_wc || !list_offsets || !offsets || !poses_wc_out || !pnp_results || !results || (S > 0 && !src_slots) ||
+      (NF > 0 && (!kp || !desc || !matched || !matched_slot)) ||
+      (M > 0 && (!list_slot || !pts3d || !pts2d || !mp_idx || !feat_idx || !inlier_out || !err_out)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // one blob each way: [kp | desc | search poses | priors | feat_start | feat_count | source slots] up,
+  // [list offsets | list slots | offsets | pts3d | pts2d | mp_idx | feat_idx | poses | err | pnp records | matched | matched slots |
+  //  records | inliers] down, and behind them the gathered positions and descriptors, which stay on the device
+  Carve in, out;
+  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_sp = in.take(56 * B), i_pr = in.take(56 * B), i_fs = in.take(4 * B),
+               i_fc = in.take(4 * B), i_ss = in.take(4 * S);
+  const size_t o_lo = out.take(4 * (B + 1)), o_ls = out.take(4 * M), o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * M), o_p2 = out.take(8 * M),
+               o_mi = out.take(4 * M), o_fi = out.take(4 * M), o_ps = out.take(56 * B), o_er = out.take(8 * M),
+               o_pn = out.take(sizeof(orbx_pnp_result) * B), o_ma = out.take(4 * B * mf), o_ms = out.take(4 * B * mf),
+               o_rs = out.take(sizeof(orbx_track_result) * B), o_in = out.take(M);
+  const size_t down_bytes = out.off;
+  const size_t o_gp = out.take(24 * M), o_gd = out.take(32 * M);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+  if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
+  std::memcpy(hi + i_sp, search_poses_wc, 56 * B);
+  std::memcpy(hi + i_pr, priors_wc, 56 * B);
+  for (size_t b = 0; b < B; ++b) {
+    ((int*)(hi + i_fs))[b] = feat_offsets[b];
+    ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
+  }
+  if (S) std::memcpy(hi + i_ss, src_slots, 4 * S);
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
+  orbx_prof_begin_call(h);
+  int* d_lo = (int*)(dout + o_lo); int* d_ls = (int*)(dout + o_ls);
+  if (int rc = ms_select_enqueue(h, who, mp, source, n_frames, P, (const int*)(di + i_ss), src_offsets, (int)M, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd))
+    return rc;
+  TrackArgs A{};
+  A.max_feat = max_feat; A.fc_stride = 1;
+  A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
+  A.positions = (const double*)(dout + o_gp); A.mp_desc = dout + o_gd; A.mp_off = d_lo;
+  A.search_poses = (const double*)(di + i_sp); A.priors = (const double*)(di + i_pr);
+  A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2); A.mp_idx = (int*)(dout + o_mi);
+  A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps); A.matched = (int*)(dout + o_ma);
+  A.results = (orbx_track_result*)(dout + o_rs);
+  if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
+    return rc;
+  if (int rc = ms_matched_slot_enqueue(h, n_frames, max_feat, A.matched, d_lo, d_ls, (int*)(dout + o_ms))) return rc;
+  if (int rc = orbx_host_call_download(h, c, down_bytes)) return rc;
+  std::memcpy(list_offsets, ho + o_lo, 4 * (B + 1));
+  std::memcpy(offsets, ho + o_of, 4 * (B + 1));
+  std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
+  std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
+  std::memcpy(results, ho + o_rs, sizeof(orbx_track_result) * B);
+  const size_t L = (size_t)list_offsets[B], N = (size_t)offsets[B];
+  if (L) std::memcpy(list_slot, ho + o_ls, 4 * L);
+  if (N) {
+    std::memcpy(pts3d, ho + o_p3, 24 * N); std::memcpy(pts2d, ho + o_p2, 8 * N); std::memcpy(mp_idx, ho + o_mi, 4 * N);
+    std::memcpy(feat_idx, ho + o_fi, 4 * N); std::memcpy(err_out, ho + o_er, 8 * N); std::memcpy(inlier_out, ho + o_in, N);
+  }
+  for (size_t b = 0; b < B; ++b) {
+    const size_t n = (size_t)(feat_offsets[b + 1] - feat_offsets[b]);
+    if (n) { std::memcpy(matched + feat_offsets[b], ho + o_ma + 4 * b * mf, 4 * n); std::memcpy(matched_slot + feat_offsets[b], ho + o_ms + 4 * b * mf, 4 * n); }
+  }
+  return ORBX_OK;
+}
+
+int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
+                                    orbx_map_points* mp, int n_frames, const orbx_keyframe* const* kfs, const orbx_keypoint* d_kp,
+                                    const uint8_t* d_desc, const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                    const double* d_priors_wc, double* d_kf_positions, uint8_t* d_kf_valid, orbx_dmatch* d_matches, int* d_offsets,
+                                    double* d_pts3d, float* d_pts2d, int* d_kf_idx, int* d_feat_idx, double* d_poses_wc_out,
+                                    uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results) {
+  static const char* who = "orbx_map_track_reference_device";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
+  if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && !kfs))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (n_frames == 0) return ORBX_OK;
+  const size_t B = (size_t)n_frames;
+  std::vector<TrackRefItem> items(B);
+  std::vector<MapRefItem> tab(B);
+  long long K = 0;
+  int max_n = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const orbx_keyframe* kf = kfs[b];
+    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, (int)b);
+    if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, (int)b);
+    if (K + kf->n > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: too many keyframe features", who);
+    items[b].kf_desc = kf->d_desc; items[b].kf_off = (int)K; items[b].n = kf->n;
+    tab[b] = MapRefItem{kf->slot_store ? kf->d_mp_slot : nullptr, (int)K, kf->n};
+    K += kf->n; max_n = std::max(max_n, kf->n);
+  }
+  if (K > 0 && (!d_kf_positions || !d_kf_valid)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  if (max_n > 0) {
+    uint8_t *hs, *ds;
+    if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B, &hs, &ds)) return rc;
+    std::memcpy(hs, tab.data(), sizeof(MapRefItem) * B);
+    if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B)) return rc;
+    ProfScope ps(h, "map_ref_gather_kernel");
+    hipLaunchKernelGGL(map_ref_gather_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, n_frames), dim3(MS_THREADS), 0, h->stream, (const MapRefItem*)ds,
+                       mp->d_live, mp->d_pos, mp->capacity, d_kf_positions, d_kf_valid);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
+                                 max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
+                                 d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+}
+
+}  // extern "C"

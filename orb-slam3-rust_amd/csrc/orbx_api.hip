@@ -236,6 +236,7 @@ void orbx_destroy(orbx_handle* h) {
   for (DevBuf& b : h->ws_tref) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_lv) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_mp) if (b.p) hipFree(b.p);
+  for (DevBuf& b : h->ws_map) if (b.p) hipFree(b.p);
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
   for (int i = 0; i < 2; ++i) { if (h->ev_in[i]) hipEventDestroy(h->ev_in[i]); if (h->ev_comp[i]) hipEventDestroy(h->ev_comp[i]); if (h->ev_out[i]) hipEventDestroy(h->ev_out[i]); }
   if (h->ba_up_event) hipEventDestroy(h->ba_up_event);
@@ -244,8 +245,8 @@ void orbx_destroy(orbx_handle* h) {
   for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
   if (h->pair_graph) hipGraphExecDestroy(h->pair_graph);
   orbx_rccl_drop(h);
-  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp};
-  UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv, &h->ring_mp};
+  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp, &h->pin_map};
+  UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv, &h->ring_mp, &h->ring_map};
   for (PinnedBuf* b : pins) if (b->p) hipHostFree(b->p);
   for (UploadRing* r : rings) {
     for (PinnedBuf& b : r->slot) if (b.p) hipHostFree(b.p);

@@ -242,6 +242,9 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
+  DevBuf ws_map[4];                      // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table
+  PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
+  UploadRing ring_map;                   // the tables on their way to ws_map[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -264,6 +267,30 @@ struct orbx_handle {
   std::vector<hipEvent_t> event_pool;
   size_t event_next = 0;
   hipEvent_t prof_tail = nullptr;          // end event of the last profiling scope (may start the next one)
+};
+
+// A keyframe with its feature arrays in device memory (keyframe.hip; the slot table: map_store_kernels.hip).
+struct orbx_map_points;
+struct orbx_keyframe {
+  orbx_handle* h = nullptr;
+  uint64_t id = 0, timestamp_ns = 0;
+  double pose_wc[7] = {1, 0, 0, 0, 0, 0, 0};
+  int n = 0;
+  uint8_t* block = nullptr;          // one device allocation: kp | desc | points_cam | has_point | mp_flag | mp_slot
+  orbx_keypoint* d_kp = nullptr;
+  uint8_t* d_desc = nullptr;
+  double* d_points = nullptr;
+  uint8_t* d_has_point = nullptr;
+  uint8_t* d_mp_flag = nullptr;
+  int* d_mp_slot = nullptr;          // per feature the slot of its map point in slot_store, -1 = None (orbx_keyframe_set_map_point_slots)
+  const orbx_map_points* slot_store = nullptr;   // the store the table was set against; NULL: no table (every feature -1)
+  std::vector<int64_t> mp_ids;       // matched_map_points (host side: ids are map bookkeeping), -1 = None
+  // FeatureVector as one node id per feature (orbx_keyframe_set_feature_nodes): host copy, and the feature indices sorted by
+  // (node, index) with the features in no list cut off the end — every node's list in push order (vocabulary/mod.rs:309)
+  bool has_nodes = false;
+  std::vector<uint32_t> node;
+  std::vector<int> node_sorted;
+  int node_m = 0;
 };
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
@@ -380,6 +407,29 @@ int launch_triangulate_compact(orbx_handle* h, const TriNeighbour* d_many, int T
 int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_positions, const uint8_t* d_mp_desc, int P,
                        const double* d_kf_pose_cw, const int* d_kf_off, const orbx_keypoint* d_kps, const uint8_t* d_descs,
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist);
+// ---- frame tracking against map points (track_kernels.hip; tracker.rs:863-988, :1086-1192) ----
+// What the four launches around PnP read and write; every pointer is device memory.
+struct TrackArgs {
+  orbx_camera cam;
+  int mode, min_corr, min_inl, max_feat, fc_stride;
+  double radius, winv, hinv;
+  // inputs
+  const orbx_keypoint* kp; const uint8_t* desc; const int* feat_start; const int* feat_count;
+  const double* positions; const uint8_t* mp_desc; const int* mp_off;
+  const double* search_poses; const double* priors;
+  // workspace: per frame cell_start [GG_CELLS+1], sorted_idx / cell_of / owner [max_feat], counts (n_corr, n_front); match [M]
+  int* cell_start; int* sorted_idx; unsigned short* cell_of; int* owner; int* counts; int* match;
+  // outputs
+  int* offsets; double* pts3d; float* pts2d; int* mp_idx; int* feat_idx; double* poses_out;
+  const uint8_t* inl; const orbx_pnp_result* pnp_res; int* matched; orbx_track_result* results;
+};
+// what can be refused before anything is enqueued; *max_mp: the most map points of a frame (mp_offsets is a host array: the lists'
+// offsets, or where the lists are made on the device the offsets of their host-known bounds)
+int track_check(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* c, const orbx_pnp_config* pnp_cfg, int B, const int* mp_offsets,
+                int* max_mp, const char* who);
+// The launches on the handle's stream (A.mp_off is device memory); max_mp bounds a frame's list, M the sum of the lists.
+int track_launch(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, int B, int max_mp,
+                 size_t M, TrackArgs A, uint8_t* d_inl, double* d_err, orbx_pnp_result* d_pnp);
 // orbx_pnp_config's range check (pnp_kernels.hip), for callers that enqueue work ahead of PnP's own launches
 int orbx_pnp_check_config(orbx_handle* h, const orbx_pnp_config* c, const char* who);
 // ---- tracking against the reference keyframe (track_ref_kernels.hip; tracker.rs:992-1064) ----

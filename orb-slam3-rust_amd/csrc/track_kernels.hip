@@ -24,21 +24,6 @@ namespace {
 
 constexpr int TRK_THREADS = 256;
 
-struct TrackArgs {
-  orbx_camera cam;
-  int mode, min_corr, min_inl, max_feat, fc_stride;
-  double radius, winv, hinv;
-  // inputs
-  const orbx_keypoint* kp; const uint8_t* desc; const int* feat_start; const int* feat_count;
-  const double* positions; const uint8_t* mp_desc; const int* mp_off;
-  const double* search_poses; const double* priors;
-  // workspace: per frame cell_start [GG_CELLS+1], sorted_idx / cell_of / owner [max_feat], counts (n_corr, n_front); match [M]
-  int* cell_start; int* sorted_idx; unsigned short* cell_of; int* owner; int* counts; int* match;
-  // outputs
-  int* offsets; double* pts3d; float* pts2d; int* mp_idx; int* feat_idx; double* poses_out;
-  const uint8_t* inl; const orbx_pnp_result* pnp_res; int* matched; orbx_track_result* results;
-};
-
 // a count outside [0, max_feat] is searched as no features at all
 __device__ __forceinline__ int track_feat_count(const TrackArgs& A, int b) {
   const int n = A.feat_count[(size_t)b * A.fc_stride];
@@ -169,6 +154,8 @@ __global__ __launch_bounds__(TRK_THREADS) void track_finish_kernel(TrackArgs A) 
   }
 }
 
+}  // namespace
+
 // what can be refused before anything is enqueued; *max_mp: the most map points of a frame
 int track_check(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* c, const orbx_pnp_config* pnp_cfg, int B, const int* mp_offsets,
                 int* max_mp, const char* who) {
@@ -217,8 +204,6 @@ int track_launch(orbx_handle* h, const orbx_camera* cam, const orbx_track_config
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
