@@ -11,8 +11,8 @@
 //                         out (node ids in LDS / one per lane): :252-263 is the same walk over fewer candidates.  A per-node walk
 //                         needs the loop keyframe's features sorted by node, which cost more on the host than the masked pass
 //                         costs on the device
-//   lv_resolve_kernel     one workgroup per pair: the stereo-point guard, the ratio test, the matches in ascending current index by
-//                         ballot / prefix, those with two stereo points into the pair list with their world points
+//   lv_resolve_kernel     one workgroup per pair: the stereo-point guard, the ratio test, the matches in ascending current index
+//                         (BlockAppend, block_dev.hpp), those with two stereo points into the pair list with their world points
 //   sim3_hypothesis_kernel  one lane per (problem, hypothesis): sampler, Horn with a one-sided Jacobi SVD in registers, M | t
 //   sim3_score_kernel     workgroups over (tiles of a problem's points) x (chunks of its hypotheses, staged in LDS), ballot + popcount
 //                         per wave, one integer add per hypothesis and workgroup
@@ -24,9 +24,11 @@
 #include <cmath>
 #include <cstdint>
 
+#include "block_dev.hpp"
 #include "guided_search_dev.hpp"
 #include "orbx_internal.hpp"
 #include "pose_dev.hpp"
+#include "ransac_dev.hpp"
 
 namespace {
 
@@ -37,7 +39,6 @@ constexpr int LV_MAX_FEAT = 1 << LV_IDX_BITS;
 constexpr unsigned LV_IDX_MASK = (unsigned)LV_MAX_FEAT - 1u;
 constexpr unsigned LV_NONE = 1023u;       // the distance field of "no candidate yet" (a real distance is <= 256): u32::MAX of :281-282
 constexpr int S3_MAX_H = 1024;            // hypotheses per problem (max_iterations)
-constexpr int S3_DRAWS = 64;              // sampler draws per hypothesis
 constexpr int S3_HS = 12;                 // doubles per hypothesis: M = scale * R (9, row-major) | t (3)
 constexpr int S3_CHUNK = 32;              // hypotheses per scoring workgroup, staged in LDS (3 KB)
 constexpr int S3_THREADS = 256;
@@ -130,12 +131,8 @@ __global__ __launch_bounds__(LV_THREADS) void lv_match_kernel(LvArgs A) {
 
 // ---- stages 0 and 2 --------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void lv_world(const double* pose, const double* p, double* o) {   // se3.rs transform_point
-  double r[3];
-  dev_q_rot(pose, p, r);
-  o[0] = r[0] + pose[4]; o[1] = r[1] + pose[5]; o[2] = r[2] + pose[6];
-}
-
+// (the two-flag append and the block sums are written out here: on BlockAppend / block_sum (block_dev.hpp) this kernel measured
+// 0.5 us, 3 %, slower than this text — profiles/block_primitives_ab.txt)
 __global__ __launch_bounds__(LV_THREADS) void lv_resolve_kernel(LvArgs A) {
   __shared__ int wave_m[LV_THREADS / 64], wave_c[LV_THREADS / 64];
   __shared__ int run_m, run_c;
@@ -187,9 +184,9 @@ __global__ __launch_bounds__(LV_THREADS) void lv_resolve_kernel(LvArgs A) {
       const size_t o = k0 + oc + __popcll(mc & below);
       A.fm[2 * o] = i; A.fm[2 * o + 1] = j;
       double w3[3];
-      lv_world(it->pose_c, it->c_pts + 3 * (size_t)i, w3);                     // :161
+      se3_transform_point(it->pose_c, it->c_pts + 3 * (size_t)i, w3);                     // :161
       A.pts_c[3 * o] = w3[0]; A.pts_c[3 * o + 1] = w3[1]; A.pts_c[3 * o + 2] = w3[2];
-      lv_world(it->pose_l, it->l_pts + 3 * (size_t)j, w3);                     // :162
+      se3_transform_point(it->pose_l, it->l_pts + 3 * (size_t)j, w3);                     // :162
       A.pts_l[3 * o] = w3[0]; A.pts_l[3 * o + 1] = w3[1]; A.pts_l[3 * o + 2] = w3[2];
     }
     __syncthreads();
@@ -226,22 +223,6 @@ __device__ __forceinline__ void s3_problem(const S3Args& S, int p, int& base, in
 }
 __device__ __forceinline__ bool s3_runs(const S3Args& S, int n) {            // sim3_solver.rs:69-75
   return n >= 3 && n >= S.cfg.min_inliers && n <= S.max_n;
-}
-
-// PnP's sampler with three indices
-__device__ __forceinline__ bool s3_sample(uint64_t seed, int h, int n, int (&idx)[3]) {
-  int k = 0;
-  for (int a = 0; a < S3_DRAWS && k < 3; ++a) {
-    const uint64_t x = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(h * 64 + a + 1);
-    uint64_t z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const int i = (int)(((z >> 32) * (uint64_t)n) >> 32);
-    if ((k > 0 && idx[0] == i) || (k > 1 && idx[1] == i)) continue;
-    if (k == 0) idx[0] = i; else if (k == 1) idx[1] = i; else idx[2] = i;
-    ++k;
-  }
-  return k == 3;
 }
 
 #define S3_ROT(p, q)                                                                                       \
@@ -354,7 +335,7 @@ __global__ __launch_bounds__(64) void sim3_hypothesis_kernel(S3Args S) {
   s3_problem(S, p, base, n);
   const size_t slot = (size_t)p * H + h;
   int idx[3] = {0, 0, 0};
-  bool valid = s3_runs(S, n) && s3_sample(S.cfg.seed, h, n, idx);
+  bool valid = s3_runs(S, n) && ransac_sample<3>(S.cfg.seed, h, n, 3, idx);
   double Mt[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) Mt[k] = 0.0;
@@ -428,30 +409,6 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_score_kernel(S3Args S, double
   }
 }
 
-// fixed-order sum of NV values over the workgroup: shuffle tree inside each wave, then every thread adds the wave totals in wave
-// order (the same bits in every thread, whatever the batch)
-template <int NV>
-__device__ __forceinline__ void s3_block_sum(double (&v)[NV], double* __restrict__ s_w /* [waves][NV] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s_w[wave * NV + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double t = 0.0;
-    for (int w = 0; w < S3_THREADS / 64; ++w) t += s_w[w * NV + k];
-    v[k] = t;
-  }
-}
-
 // UnitQuaternion::from_rotation_matrix's branches, normalised, [spec] w >= 0
 __device__ __forceinline__ void s3_quat(const double* R, double* q) {
   const double tr = R[0] + R[4] + R[8];
@@ -513,7 +470,7 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_final_kernel(S3Args S, double
       S.inl[g] = in ? 1 : 0;
       if (in) { acc[0] += 1.0; acc[1] += e; }
     }
-    s3_block_sum<2>(acc, s_w);
+    block_sum<S3_THREADS, 2>(acc, s_w);
     n_inl = (int)acc[0];
     double err_sum = acc[1];
     if (n_inl >= S.cfg.min_inliers) {                                       // :120: Horn over the inliers
@@ -525,7 +482,7 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_final_kernel(S3Args S, double
           for (int r = 0; r < 3; ++r) { cs[r] += S.pts1[3 * g + r]; cs[3 + r] += S.pts2[3 * g + r]; }
         }
       }
-      s3_block_sum<6>(cs, s_w);
+      block_sum<S3_THREADS, 6>(cs, s_w);
 #pragma unroll
       for (int r = 0; r < 6; ++r) cs[r] = cs[r] / (double)n_inl;
       double hs[11];
@@ -546,7 +503,7 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_final_kernel(S3Args S, double
           hs[10] += bb[0] * bb[0] + bb[1] * bb[1] + bb[2] * bb[2];
         }
       }
-      s3_block_sum<11>(hs, s_w);
+      block_sum<S3_THREADS, 11>(hs, s_w);
       if (tid == 0) {
         double R[9], scale, Mt[12];
         if (s3_model(hs, hs[9], hs[10], cs, cs + 3, S.cfg.fix_scale != 0, R, scale, Mt)) {
@@ -566,7 +523,7 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_final_kernel(S3Args S, double
           const double e = s3_err2(s_M2, S.pts1 + 3 * g, S.pts2 + 3 * g);
           if (e < thr2) { acc2[0] += 1.0; acc2[1] += e; }
         }
-        s3_block_sum<2>(acc2, s_w);
+        block_sum<S3_THREADS, 2>(acc2, s_w);
         if ((int)acc2[0] >= n_inl) {                                        // :133
           refined = 1; n_inl = (int)acc2[0]; err_sum = acc2[1];
           for (int i = tid; i < n; i += S3_THREADS) {
@@ -618,7 +575,7 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_final_kernel(S3Args S, double
 
 __global__ __launch_bounds__(LV_THREADS) void lv_finish_kernel(LvArgs A) {
   __shared__ int wave_c[LV_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const LvItem* it = A.items + b;
   const int* pre = A.pre + (size_t)b * LV_PRE;
   const size_t k0 = (size_t)it->out_off;
@@ -632,19 +589,15 @@ __global__ __launch_bounds__(LV_THREADS) void lv_finish_kernel(LvArgs A) {
   int verified = 0;
   if (status == ORBX_LOOP_OK) {                                             // (uniform over the workgroup)
     const double* Mt = A.model + 12 * (size_t)b;
-    const double* pl = it->pose_l;
-    const double qi[4] = {pl[0], -pl[1], -pl[2], -pl[3]};                   // loop_kf.pose.inverse() (se3.rs:56-63)
-    double ti[3];
-    dev_q_rot(qi, pl + 4, ti);
-    ti[0] = -ti[0]; ti[1] = -ti[1]; ti[2] = -ti[2];
+    double cw[7];
+    se3_inverse7(it->pose_l, cw, cw + 4);                                   // loop_kf.pose.inverse()
     int c = 0;
     for (int k = tid; k < n_pairs; k += LV_THREADS) {                       // :340-375, over all gathered matches
       const double* x = A.pts_c + 3 * (k0 + k);
       const double y[3] = {Mt[0] * x[0] + Mt[1] * x[1] + Mt[2] * x[2] + Mt[9], Mt[3] * x[0] + Mt[4] * x[1] + Mt[5] * x[2] + Mt[10],
                            Mt[6] * x[0] + Mt[7] * x[1] + Mt[8] * x[2] + Mt[11]};
       double pc[3];
-      dev_q_rot(qi, y, pc);
-      pc[0] = pc[0] + ti[0]; pc[1] = pc[1] + ti[1]; pc[2] = pc[2] + ti[2];
+      se3_transform_point(cw, y, pc);
       if (pc[2] <= 0.0) continue;
       const double u = A.cam.fx * pc[0] / pc[2] + A.cam.cx, v = A.cam.fy * pc[1] / pc[2] + A.cam.cy;
       const orbx_keypoint kp = it->l_kp[A.fm[2 * (k0 + k) + 1]];
@@ -652,11 +605,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_finish_kernel(LvArgs A) {
       const double s = A.pow_scale[min(max(kp.octave, 0), 31)];
       if (du * du + dv * dv < A.cfg.chi2 * s * s) ++c;                       // :368-371
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
-    if (lane == 0) wave_c[wave] = c;
-    __syncthreads();
-    verified = wave_c[0] + wave_c[1] + wave_c[2] + wave_c[3];
+    verified = block_sum<LV_THREADS>(c, wave_c);
     if (verified < A.cfg.min_verified) status = ORBX_LOOP_TOO_FEW_VERIFIED;  // :193
   } else if (status <= ORBX_LOOP_TOO_FEW_PAIRS) {
     for (int k = tid; k < n_pairs; k += LV_THREADS) A.inl[k0 + k] = 0;

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_dev.hpp"
 #include "orbx_internal.hpp"
 
 struct orbx_map_points {
@@ -61,15 +62,6 @@ struct SelArgs {
   int* first; int* cand; int* chunk_count;
   int* list_off; int* list_slot; double* out_pos; uint8_t* out_desc;
 };
-
-__device__ __forceinline__ int ms_block_sum(int v, int* wave_tot) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();                                                        // (wave_tot may still be read from an earlier use)
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-}
 
 __global__ __launch_bounds__(MS_THREADS) void map_mark_kernel(SelArgs A) {
   const int b = blockIdx.y, C = A.n_cand[b];
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(MS_THREADS) void map_flag_kernel(SelArgs A) {
       n += slot >= 0;
     }
   }
-  n = ms_block_sum(n, wave_tot);
+  n = block_sum<MS_THREADS>(n, wave_tot);
   if (threadIdx.x == 0) A.chunk_count[b * A.n_chunk + blockIdx.x] = n;
 }
 
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(MS_THREADS) void map_emit_kernel(SelArgs A, int B) 
   const int me = b * A.n_chunk + blockIdx.x;
   int part = 0;
   for (int j = tid; j < me; j += MS_THREADS) part += A.chunk_count[j];
-  const int base = ms_block_sum(part, wave_tot);
+  const int base = block_sum<MS_THREADS>(part, wave_tot);
   if (tid == 0) {
     if (blockIdx.x == 0) A.list_off[b] = base;
     if (me == B * A.n_chunk - 1) A.list_off[B] = base + A.chunk_count[me];

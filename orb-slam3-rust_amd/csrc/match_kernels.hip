@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "block_dev.hpp"
 #include "guided_search_dev.hpp"
 #include "orbx_internal.hpp"
 
@@ -397,31 +398,24 @@ __global__ __launch_bounds__(256) void stereo_compact_kernel(
     const int2* __restrict__ tmp, orbx_camera cam, orbx_dmatch* __restrict__ matches,
     int* __restrict__ nmatches, double* __restrict__ points, uint8_t* __restrict__ has_point) {
   __shared__ int wave_tot[4];
-  __shared__ int running;
   const int pair = blockIdx.x;
   const orbx_keypoint* kpL = kp + (size_t)(2 * pair) * cap;
   const orbx_keypoint* kpR = kpL + cap;
   const int nL = min(nkp[2 * pair], cap);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) running = 0;
-  __syncthreads();
+  const int tid = threadIdx.x;
+  BlockAppend<256, 1> app(wave_tot);
   for (int base = 0; base < nL; base += 256) {
     const int li = base + tid;
     int2 t = make_int2(-1, 0);
     if (li < nL) t = tmp[(size_t)pair * cap + li];
     const bool flag = t.x >= 0;
-    const unsigned long long m = __ballot(flag);
-    const int prefix = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int off = running;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    const int at = app.round(flag);
     if (li < nL) {
       uint8_t hp = 0;
       if (flag) {
         orbx_dmatch dm;
         dm.query_idx = li; dm.train_idx = t.x; dm.img_idx = 0; dm.distance = (float)t.y;
-        matches[(size_t)pair * cap + off + prefix] = dm;
+        matches[(size_t)pair * cap + at] = dm;
         const double lx = (double)kpL[li].x, ly = (double)kpL[li].y, rx = (double)kpR[t.x].x;
         const double disparity = lx - rx;                                 // stereo.rs:204
         if (!(fabs(disparity) < 0.5)) {                                   // stereo.rs:205
@@ -439,11 +433,8 @@ __global__ __launch_bounds__(256) void stereo_compact_kernel(
       }
       has_point[(size_t)pair * cap + li] = hp;
     }
-    __syncthreads();
-    if (tid == 0) running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
   }
-  if (tid == 0) nmatches[pair] = running;
+  if (tid == 0) nmatches[pair] = app.total[0];
 }
 
 // ---- brute-force nearest neighbour (one direction of the cross-check matcher) -----------------------
@@ -500,31 +491,21 @@ __global__ __launch_bounds__(256) void crosscheck_compact_kernel(const int* __re
                                                                  orbx_dmatch* __restrict__ out,
                                                                  int* __restrict__ n_out) {
   __shared__ int wave_tot[4];
-  __shared__ int running;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) running = 0;
-  __syncthreads();
+  const int tid = threadIdx.x;
+  BlockAppend<256, 1> app(wave_tot);
   for (int base = 0; base < nq; base += 256) {
     const int i = base + tid;
     bool flag = false;
     int j = -1;
     if (i < nq) { j = fwd[i]; flag = bwd[j] == i; }
-    const unsigned long long m = __ballot(flag);
-    const int prefix = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int off = running;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    const int at = app.round(flag);
     if (flag) {
       orbx_dmatch dm;
       dm.query_idx = i; dm.train_idx = j; dm.img_idx = 0; dm.distance = (float)fdist[i];
-      out[off + prefix] = dm;
+      out[at] = dm;
     }
-    __syncthreads();
-    if (tid == 0) running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
   }
-  if (tid == 0) *n_out = running;
+  if (tid == 0) *n_out = app.total[0];
 }
 
 // ---- guided matching: the grid and the search are guided_search_dev.hpp's (shared with track_kernels.hip) -----------------

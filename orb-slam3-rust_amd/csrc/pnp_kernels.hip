@@ -24,14 +24,15 @@
 #include <cstdint>
 #include <cstring>
 
+#include "block_dev.hpp"
 #include "orbx_internal.hpp"
 #include "pose_dev.hpp"
+#include "ransac_dev.hpp"
 
 namespace {
 
 constexpr int PNP_MAX_H = 1024;          // hypotheses per problem (max_iterations)
 constexpr int PNP_MAX_M = 8;             // model_points
-constexpr int PNP_DRAWS = 64;            // sampler draws per hypothesis
 constexpr int PNP_HS = 16;               // doubles per hypothesis slot: R (9, row-major) | t (3) | q (4) of T_cw
 constexpr int PNP_SCORE_THREADS = 256;
 constexpr int PNP_CHUNK = 128;           // hypotheses staged in LDS at a time (12 KB)
@@ -49,10 +50,7 @@ __device__ __forceinline__ BaCam pnp_bacam(const orbx_camera& c) {
 // T_cw of a T_wc pose (se3.rs:56-63 with nalgebra's quaternion-vector product)
 __device__ __forceinline__ PnpPose pnp_inverse7(const double* wc) {
   PnpPose o;
-  o.q[0] = wc[0]; o.q[1] = -wc[1]; o.q[2] = -wc[2]; o.q[3] = -wc[3];
-  double r[3];
-  dev_q_rot(o.q, wc + 4, r);
-  o.t[0] = -r[0]; o.t[1] = -r[1]; o.t[2] = -r[2];
+  se3_inverse7(wc, o.q, o.t);
   return o;
 }
 
@@ -76,27 +74,6 @@ __device__ __forceinline__ bool pnp_is_inlier(const orbx_camera& cam, const doub
   const double iz = 1.0 / z;
   const double du = cam.fx * (x * iz) + cam.cx - u, dv = cam.fy * (y * iz) + cam.cy - v;
   return (float)(du * du + dv * dv) <= thr2;
-}
-
-// The sampler [spec]: hypothesis h, draw a -> splitmix64(seed + golden * (h*64 + a + 1)); idx = ((z >> 32) * n) >> 32; duplicates
-// skipped.  True when m distinct indices were drawn within 64 draws.
-__device__ __forceinline__ bool pnp_sample(uint64_t seed, int h, int n, int m, int (&idx)[PNP_MAX_M]) {
-  int k = 0;
-  for (int a = 0; a < PNP_DRAWS && k < m; ++a) {
-    const uint64_t x = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(h * 64 + a + 1);
-    uint64_t z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const int i = (int)(((z >> 32) * (uint64_t)n) >> 32);
-    bool dup = false;
-#pragma unroll
-    for (int j = 0; j < PNP_MAX_M; ++j) dup |= (j < k && idx[j] == i);
-    if (dup) continue;
-#pragma unroll
-    for (int j = 0; j < PNP_MAX_M; ++j) if (j == k) idx[j] = i;   // (constant register index: no scratch)
-    ++k;
-  }
-  return k == m;
 }
 
 // One correspondence's share of the normal equations at R|t: r = pi(R X + t) - (u, v), J = d r / d delta with delta = (omega, upsilon)
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(64) void pnp_hypothesis_kernel(orbx_camera cam, orb
 #pragma unroll
   for (int j = 0; j < PNP_MAX_M; ++j) idx[j] = j;
   bool valid = n >= 4 && n <= max_n;
-  if (valid) valid = n > m ? pnp_sample(cfg.seed, h, n, m, idx) : h == 0;   // 4 <= n <= m: one hypothesis from all points [spec]
+  if (valid) valid = n > m ? ransac_sample<PNP_MAX_M>(cfg.seed, h, n, m, idx) : h == 0;   // 4 <= n <= m: one hypothesis from all points [spec]
   const int mu = n > m ? m : n;
   const BaCam bc = pnp_bacam(cam);
   PnpPose cur = pnp_inverse7(priors + 7 * (size_t)p);
@@ -311,30 +288,6 @@ __global__ __launch_bounds__(PNP_SCORE_THREADS) void pnp_score_kernel(orbx_camer
   }
 }
 
-// fixed-order sum of NV values over the workgroup: shuffle tree inside each wave, then every thread adds the wave totals in wave
-// order (the same bits in every thread)
-template <int NV>
-__device__ __forceinline__ void pnp_block_sum(double (&v)[NV], double* __restrict__ s_w /* [waves][NV] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s_w[wave * NV + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double t = 0.0;
-    for (int w = 0; w < PNP_REFINE_THREADS / 64; ++w) t += s_w[w * NV + k];
-    v[k] = t;
-  }
-}
-
 // grid P, 256 threads: select + refine + detailed pass of one problem
 __global__ __launch_bounds__(PNP_REFINE_THREADS) void pnp_refine_kernel(orbx_camera cam, orbx_pnp_config cfg, int max_n, float thr2,
                                                                         const int* __restrict__ off, const double* __restrict__ pts3d,
@@ -400,7 +353,7 @@ __global__ __launch_bounds__(PNP_REFINE_THREADS) void pnp_refine_kernel(orbx_cam
         const size_t g = (size_t)base + i;
         if (inl_out[g]) pnp_accum(bc, s_Rt, pts3d[3 * g], pts3d[3 * g + 1], pts3d[3 * g + 2], (double)pts2d[2 * g], (double)pts2d[2 * g + 1], s);
       }
-      pnp_block_sum<PNP_NRED>(s, s_w);
+      block_sum<PNP_REFINE_THREADS, PNP_NRED>(s, s_w);
       if (tid == 0) {
         double d[6];
         s_go = 0;
@@ -417,7 +370,7 @@ __global__ __launch_bounds__(PNP_REFINE_THREADS) void pnp_refine_kernel(orbx_cam
         const size_t g = (size_t)base + i;
         if (inl_out[g]) tc[0] += pnp_cost(cam, s_tRt, pts3d[3 * g], pts3d[3 * g + 1], pts3d[3 * g + 2], (double)pts2d[2 * g], (double)pts2d[2 * g + 1]);
       }
-      pnp_block_sum<1>(tc, s_w);
+      block_sum<PNP_REFINE_THREADS, 1>(tc, s_w);
       if (tc[0] < s[27]) { if (tid == 0) s_cur = s_trial; lambda = fmax(lambda * 0.1, 1e-10); }
       else lambda = fmin(lambda * 10.0, 1e10);
     }
@@ -427,11 +380,8 @@ __global__ __launch_bounds__(PNP_REFINE_THREADS) void pnp_refine_kernel(orbx_cam
   double* po = poses_out + 7 * (size_t)p;
   if (tid == 0) {
     if (status == ORBX_PNP_OK) {                                          // T_wc = (q_cw^-1, -(q_cw^-1 t_cw))
-      const double qwc[4] = {s_cur.q[0], -s_cur.q[1], -s_cur.q[2], -s_cur.q[3]};
-      double r[3];
-      dev_q_rot(qwc, s_cur.t, r);
-      po[0] = qwc[0]; po[1] = qwc[1]; po[2] = qwc[2]; po[3] = qwc[3];
-      po[4] = -r[0]; po[5] = -r[1]; po[6] = -r[2];
+      const double cw[7] = {s_cur.q[0], s_cur.q[1], s_cur.q[2], s_cur.q[3], s_cur.t[0], s_cur.t[1], s_cur.t[2]};
+      se3_inverse7(cw, po, po + 4);
     } else {
       for (int k = 0; k < 7; ++k) po[k] = prior[k];
     }
@@ -460,7 +410,7 @@ __global__ __launch_bounds__(PNP_REFINE_THREADS) void pnp_refine_kernel(orbx_cam
     inl_out[g] = in ? 1 : 0;
     if (in) { acc[0] += 1.0; acc[1] += err * err; }
   }
-  pnp_block_sum<2>(acc, s_w);
+  block_sum<PNP_REFINE_THREADS, 2>(acc, s_w);
   if (tid == 0) {
     orbx_pnp_result r;
     r.status = status;

@@ -1,6 +1,7 @@
-// pose_dev.hpp — device math shared by the bundle-adjustment kernels (ba_kernels.hip), the PnP-RANSAC kernels (pnp_kernels.hip)
-// and pose-inertial optimization (pose_inertial_kernels.hip): the camera descriptor, quaternion / rotation helpers, the 2x6 pose
-// block of one observation and the 9-d IMU preintegration residual.
+// pose_dev.hpp — device math shared by the bundle-adjustment kernels (ba_kernels.hip), the PnP-RANSAC kernels (pnp_kernels.hip),
+// pose-inertial optimization (pose_inertial_kernels.hip), the tracker's projection (track_kernels.hip) and loop verification
+// (loop_verify_kernels.hip): the camera descriptor, quaternion / rotation / SE3 helpers, the 2x6 pose block of one observation
+// and the 9-d IMU preintegration residual.
 // Device code only, inside an anonymous namespace: each translation unit that includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,6 +42,20 @@ __device__ __forceinline__ void dev_q_rot(const double* q, const double* v, doub
   const double t0 = 2.0 * (q[2] * v[2] - q[3] * v[1]), t1 = 2.0 * (q[3] * v[0] - q[1] * v[2]), t2 = 2.0 * (q[1] * v[1] - q[2] * v[0]);
   const double c0 = q[2] * t2 - q[3] * t1, c1 = q[3] * t0 - q[1] * t2, c2 = q[1] * t1 - q[2] * t0;
   o[0] = t0 * q[0] + c0 + v[0]; o[1] = t1 * q[0] + c1 + v[1]; o[2] = t2 * q[0] + c2 + v[2];
+}
+// SE3::inverse (se3.rs:56-63) of the pose wc = (q | t): conjugate, then -(q^-1 * t).  q / t may be wc's own storage.
+__device__ __forceinline__ void se3_inverse7(const double* wc, double* q, double* t) {
+  const double qi[4] = {wc[0], -wc[1], -wc[2], -wc[3]};
+  double r[3];
+  dev_q_rot(qi, wc + 4, r);
+  q[0] = qi[0]; q[1] = qi[1]; q[2] = qi[2]; q[3] = qi[3];
+  t[0] = -r[0]; t[1] = -r[1]; t[2] = -r[2];
+}
+// SE3::transform_point: q * p + t
+__device__ __forceinline__ void se3_transform_point(const double* pose7, const double* p, double* o) {
+  double r[3];
+  dev_q_rot(pose7, p, r);
+  o[0] = r[0] + pose7[4]; o[1] = r[1] + pose7[5]; o[2] = r[2] + pose7[6];
 }
 __device__ __forceinline__ void dev_q_mul(const double* a, const double* b, double* o) {
   o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];

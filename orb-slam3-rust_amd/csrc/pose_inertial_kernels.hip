@@ -52,12 +52,10 @@ __device__ __forceinline__ double pi_lane(double x, int k) {
 
 // T_cw of the parameters' pose: q_cw = conj(from_scaled_axis(par[0..3])), t_cw = -(q_cw * t_wc)  (extract_pose, se3.rs:56-63)
 __device__ __forceinline__ void pi_pose_cw(const double* par, double* qcw, double* tcw) {
-  double q[4];
-  dev_q_from_scaled_axis(par, q);
-  qcw[0] = q[0]; qcw[1] = -q[1]; qcw[2] = -q[2]; qcw[3] = -q[3];
-  double r[3];
-  dev_q_rot(qcw, par + 3, r);
-  tcw[0] = -r[0]; tcw[1] = -r[1]; tcw[2] = -r[2];
+  double wc[7];
+  dev_q_from_scaled_axis(par, wc);
+  wc[4] = par[3]; wc[5] = par[4]; wc[6] = par[5];
+  se3_inverse7(wc, qcw, tcw);
 }
 
 // p_cam = q_cw * X + t_cw (SE3::transform_point)

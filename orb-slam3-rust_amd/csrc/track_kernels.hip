@@ -9,7 +9,7 @@
 //   track_search_kernel       one wave per map point, frames as grid.y: projection (one IEEE operation at a time, every lane
 //                             computes the same numbers) + guided_search_wave — the search guided_match_kernel runs
 //   track_gather_kernel       one workgroup per frame: offsets[b] = sum of the earlier frames' counts, then the ordered
-//                             compaction of the frame's matches by ballot / prefix into PnP's layout
+//                             compaction of the frame's matches (BlockAppend, block_dev.hpp) into PnP's layout
 //   (PnP)
 //   track_finish_kernel       one workgroup per frame: status, matched[feat] (the later inlier wins: atomicMax on the
 //                             correspondence index), the prior's bytes where the tracker falls back to it
@@ -17,8 +17,10 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_dev.hpp"
 #include "guided_search_dev.hpp"
 #include "orbx_internal.hpp"
+#include "pose_dev.hpp"
 
 namespace {
 
@@ -47,18 +49,10 @@ __global__ __launch_bounds__(TRK_THREADS) void track_search_kernel(TrackArgs A) 
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= nm) return;
   const size_t m = (size_t)m0 + i;
-  // pose.inverse() (se3.rs:56-63): conjugate, then -(q^-1 * t) with nalgebra's quaternion-vector product
-  const double* T = A.search_poses + 7 * (size_t)b;
-  const double qw = T[0], qx = -T[1], qy = -T[2], qz = -T[3];
-  const double v0 = T[4], v1 = T[5], v2 = T[6];
-  const double a0 = 2.0 * (qy * v2 - qz * v1), a1 = 2.0 * (qz * v0 - qx * v2), a2 = 2.0 * (qx * v1 - qy * v0);
-  const double e0 = qy * a2 - qz * a1, e1 = qz * a0 - qx * a2, e2 = qx * a1 - qy * a0;
-  const double tx = -(a0 * qw + e0 + v0), ty = -(a1 * qw + e1 + v1), tz = -(a2 * qw + e2 + v2);
-  // transform_point: q * p + t
-  const double px = A.positions[3 * m], py = A.positions[3 * m + 1], pz = A.positions[3 * m + 2];
-  const double t0 = 2.0 * (qy * pz - qz * py), t1 = 2.0 * (qz * px - qx * pz), t2 = 2.0 * (qx * py - qy * px);
-  const double c0 = qy * t2 - qz * t1, c1 = qz * t0 - qx * t2, c2 = qx * t1 - qy * t0;
-  const double x = (t0 * qw + c0 + px) + tx, y = (t1 * qw + c1 + py) + ty, z = (t2 * qw + c2 + pz) + tz;
+  double cw[7], pc[3];
+  se3_inverse7(A.search_poses + 7 * (size_t)b, cw, cw + 4);                 // pose.inverse()
+  se3_transform_point(cw, A.positions + 3 * m, pc);
+  const double x = pc[0], y = pc[1], z = pc[2];
   int res = -2;
   if (!(z <= 0.0)) {                                                        // tracker.rs:872, :1109
     res = -1;
@@ -84,43 +78,28 @@ __global__ __launch_bounds__(TRK_THREADS) void track_search_kernel(TrackArgs A) 
 
 __global__ __launch_bounds__(TRK_THREADS) void track_gather_kernel(TrackArgs A, int B) {
   __shared__ int wave_tot[TRK_THREADS / 64];
-  __shared__ int running;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   // offsets[b]: the correspondences of the frames before this one
   int part = 0;
   for (int j = tid; j < b; j += TRK_THREADS) part += A.counts[2 * j];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-  if (lane == 0) wave_tot[wave] = part;
-  __syncthreads();
+  BlockAppend<TRK_THREADS, 1> app(wave_tot);
+  app.total[0] = block_sum<TRK_THREADS>(part, wave_tot);
   if (tid == 0) {
-    const int base = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    running = base;
-    A.offsets[b] = base;
-    if (b == B - 1) A.offsets[B] = base + A.counts[2 * b];
+    A.offsets[b] = app.total[0];
+    if (b == B - 1) A.offsets[B] = app.total[0] + A.counts[2 * b];
   }
-  __syncthreads();
   const int m0 = A.mp_off[b], nm = A.mp_off[b + 1] - m0;
   const orbx_keypoint* kp = A.kp + (track_feat_count(A, b) > 0 ? (size_t)A.feat_start[b] : 0);
   for (int base = 0; base < nm; base += TRK_THREADS) {
     const int i = base + tid;
     const int f = i < nm ? A.match[(size_t)m0 + i] : -1;
-    const bool flag = f >= 0;
-    const unsigned long long mk = __ballot(flag);
-    const int prefix = __popcll(mk & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(mk);
-    __syncthreads();
-    int off = running;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    if (flag) {
-      const size_t o = (size_t)off + prefix, m = (size_t)m0 + i;
+    const size_t o = (size_t)app.round(f >= 0);
+    if (f >= 0) {
+      const size_t m = (size_t)m0 + i;
       A.pts3d[3 * o] = A.positions[3 * m]; A.pts3d[3 * o + 1] = A.positions[3 * m + 1]; A.pts3d[3 * o + 2] = A.positions[3 * m + 2];   // :919
       A.pts2d[2 * o] = kp[f].x; A.pts2d[2 * o + 1] = kp[f].y;                                                                        // :920
       A.mp_idx[o] = i; A.feat_idx[o] = f;                                                                                            // :921
     }
-    __syncthreads();
-    if (tid == 0) running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
   }
 }
 

@@ -9,7 +9,7 @@
 //                         column minimum (frame feature -> keyframe feature) is merged across blocks by atomicMin on a packed key
 //                         (distance << 32 | keyframe index).  A minimum over that key is "smallest distance, then lowest index"
 //                         whatever order the blocks arrive in: the result is the sequential rule's, bit for bit.
-//   tref_resolve_kernel   one workgroup per frame: the mutual pairs in ascending keyframe index by ballot / prefix into d_matches,
+//   tref_resolve_kernel   one workgroup per frame: the mutual pairs in ascending keyframe index (BlockAppend, block_dev.hpp) into d_matches,
 //                         those with a live map point into a pair list, and the two counts
 //   tref_gather_kernel    one workgroup per frame: offsets[b] = the earlier frames' correspondences, then the pair list into PnP's
 //                         layout (positions, keypoint positions, indices)
@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_dev.hpp"
 #include "guided_search_dev.hpp"
 #include "orbx_internal.hpp"
 
@@ -109,19 +110,18 @@ __global__ __launch_bounds__(TREF_THREADS) void tref_nn_kernel(TrefArgs A) {
 
 // (i, row_best[i]) is a match iff col_best[row_best[i]] == i; ascending i
 __global__ __launch_bounds__(TREF_THREADS) void tref_resolve_kernel(TrefArgs A) {
-  __shared__ int wave_m[TREF_THREADS / 64], wave_c[TREF_THREADS / 64];
-  __shared__ int run_m, run_c;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int wave_tot[(TREF_THREADS / 64) * 2];
+  const int b = blockIdx.x, tid = threadIdx.x;
   const TrackRefItem it = A.items[b];
   const int nt = tref_feat_count(A, b);
   const int nq = nt > 0 ? it.n : 0;
   const size_t k0 = (size_t)it.kf_off;
   const unsigned long long* col = A.col_best + (size_t)b * A.max_feat;
-  if (tid == 0) { run_m = 0; run_c = 0; }
-  __syncthreads();
+  BlockAppend<TREF_THREADS, 2> app(wave_tot);                                  // [0] matches, [1] correspondences
   for (int base = 0; base < nq; base += TREF_THREADS) {
     const int i = base + tid;
-    bool fm = false, fc = false;
+    bool fl[2] = {false, false};
+    bool &fm = fl[0], &fc = fl[1];
     int j = 0;
     unsigned d = 0;
     if (i < nq) {
@@ -130,42 +130,28 @@ __global__ __launch_bounds__(TREF_THREADS) void tref_resolve_kernel(TrefArgs A) 
       fm = (int)(unsigned)(col[j] & 0xffffffffull) == i;
       fc = fm && A.valid[k0 + i] != 0;
     }
-    const unsigned long long mm = __ballot(fm), mc = __ballot(fc);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (lane == 0) { wave_m[wave] = __popcll(mm); wave_c[wave] = __popcll(mc); }
-    __syncthreads();
-    int om = run_m, oc = run_c;
-    for (int w = 0; w < wave; ++w) { om += wave_m[w]; oc += wave_c[w]; }
+    int at[2];
+    app.round(fl, at);
     if (fm) {
       orbx_dmatch dm;
       dm.query_idx = i; dm.train_idx = j; dm.img_idx = 0; dm.distance = (float)d;
-      A.matches[k0 + om + __popcll(mm & below)] = dm;
+      A.matches[k0 + at[0]] = dm;
     }
     if (fc) {
-      const size_t o = k0 + oc + __popcll(mc & below);
+      const size_t o = k0 + at[1];
       A.pairs[2 * o] = i; A.pairs[2 * o + 1] = j;
     }
-    __syncthreads();
-    if (tid == 0) {
-      run_m += wave_m[0] + wave_m[1] + wave_m[2] + wave_m[3];
-      run_c += wave_c[0] + wave_c[1] + wave_c[2] + wave_c[3];
-    }
-    __syncthreads();
   }
-  if (tid == 0) { A.counts[2 * b] = run_m; A.counts[2 * b + 1] = run_c; }
+  if (tid == 0) { A.counts[2 * b] = app.total[0]; A.counts[2 * b + 1] = app.total[1]; }
 }
 
 __global__ __launch_bounds__(TREF_THREADS) void tref_gather_kernel(TrefArgs A, int B) {
   __shared__ int wave_tot[TREF_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   // offsets[b]: the correspondences of the frames before this one
   int part = 0;
   for (int j = tid; j < b; j += TREF_THREADS) part += A.counts[2 * j + 1];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-  if (lane == 0) wave_tot[wave] = part;
-  __syncthreads();
-  const int base = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  const int base = block_sum<TREF_THREADS>(part, wave_tot);
   const int n_corr = A.counts[2 * b + 1];
   if (tid == 0) {
     A.offsets[b] = base;

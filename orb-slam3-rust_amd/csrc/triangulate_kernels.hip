@@ -3,6 +3,7 @@
 // ordered compaction of the accepted points.  f64 throughout; -ffp-contract=off keeps every expression one IEEE operation at a time.
 #include <cmath>
 
+#include "block_dev.hpp"
 #include "orbx_internal.hpp"
 
 namespace {
@@ -164,45 +165,40 @@ __global__ __launch_bounds__(256) void tri_triangulate_kernel(TriCommon C, TriNe
 }
 
 // Ordered compaction: one workgroup walks the neighbours in order and each neighbour's pairs in the search's order, 1024 at a
-// time; a CREATED pair's place in the list is the running count plus its rank among the CREATED pairs of its chunk (ballot +
-// popcount, integer only), so the list has the reference's creation order and the same input gives the same bytes.
+// time; a CREATED pair's place in the list is the running count plus its rank among the CREATED pairs of its chunk (BlockAppend,
+// block_dev.hpp: integer only), so the list has the reference's creation order and the same input gives the same bytes.
 __global__ __launch_bounds__(1024) void tri_compact_kernel(const TriNeighbour* __restrict__ nbs, int T, const uint16_t* __restrict__ status,
                                                            const double* __restrict__ points, int cap, int* __restrict__ head,
                                                            int* __restrict__ out_nb, int* __restrict__ out_i1, int* __restrict__ out_i2,
                                                            double* __restrict__ out_pts) {
-  __shared__ int s_made[16], s_tri[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int total = 0;
+  __shared__ int wave_tot[16 * 2];
+  const int tid = threadIdx.x;
+  BlockAppend<1024, 2> app(wave_tot);                                        // [0] CREATED: the list goes on over the neighbours, [1] triangulated
   for (int t = 0; t < T; ++t) {
     const int np = nbs[t].n_pairs_dev ? *nbs[t].n_pairs_dev : nbs[t].n_pairs;
     const size_t base = (size_t)nbs[t].out_base;
     const int* pairs = nbs[t].pairs;
-    int n_tri = 0, n_made = 0;
+    const int start = app.total[0];
+    app.total[1] = 0;
     for (int c0 = 0; c0 < np; c0 += 1024) {
       const int i = c0 + tid;
       const unsigned st = i < np ? (status[base + i] & 0xffu) : (unsigned)ORBX_TRI_SKIPPED;
-      const bool made = st == ORBX_TRI_CREATED;
-      const bool tri = i < np && st != ORBX_TRI_SKIPPED && st != ORBX_TRI_DLT_DEGENERATE && st != ORBX_TRI_BAD_INDEX;   // :260
-      const unsigned long long mb = __ballot(made), tb = __ballot(tri);
-      if (lane == 0) { s_made[wave] = __popcll(mb); s_tri[wave] = __popcll(tb); }
-      __syncthreads();
-      int before = 0, cm = 0, ct = 0;
-      for (int w = 0; w < 16; ++w) { if (w < wave) before += s_made[w]; cm += s_made[w]; ct += s_tri[w]; }
-      if (made) {
-        const int o = total + n_made + before + __popcll(mb & ((1ull << lane) - 1ull));
+      const bool fl[2] = {st == ORBX_TRI_CREATED,
+                          i < np && st != ORBX_TRI_SKIPPED && st != ORBX_TRI_DLT_DEGENERATE && st != ORBX_TRI_BAD_INDEX};   // :260
+      int at[2];
+      app.round(fl, at);
+      if (fl[0]) {
+        const int o = at[0];
         if (o < cap) {
           out_nb[o] = t; out_i1[o] = pairs[2 * (size_t)i]; out_i2[o] = pairs[2 * (size_t)i + 1];
           out_pts[3 * (size_t)o] = points[3 * (base + i)]; out_pts[3 * (size_t)o + 1] = points[3 * (base + i) + 1];
           out_pts[3 * (size_t)o + 2] = points[3 * (base + i) + 2];
         }
       }
-      n_made += cm; n_tri += ct;
-      __syncthreads();
     }
-    if (tid == 0) { head[1 + 4 * t] = 0; head[2 + 4 * t] = np; head[3 + 4 * t] = n_tri; head[4 + 4 * t] = n_made; }
-    total += n_made;
+    if (tid == 0) { head[1 + 4 * t] = 0; head[2 + 4 * t] = np; head[3 + 4 * t] = app.total[1]; head[4 + 4 * t] = app.total[0] - start; }
   }
-  if (tid == 0) head[0] = total;
+  if (tid == 0) head[0] = app.total[0];
 }
 
 }  // namespace

@@ -12,8 +12,8 @@ if [ "$SRC" = "orb_kernels.hip" ]; then EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1";
     -Wno-unused-value -Wno-pass-failed $EXTRA "$@" -c "$SRC" -o "$OBJ"
 mkdir -p ../../build_ab
 OBJS=""
-for f in orbx_api match_kernels orb_kernels ba_kernels bow_kernels euroc_io keyframe pnp_kernels pose_inertial_kernels kfdb_kernels triangulate_kernels track_kernels track_ref_kernels loop_verify_kernels; do
-  if [ "$f.hip" = "$SRC" ]; then OBJS="$OBJS $OBJ"; else OBJS="$OBJS $f.o"; fi
+for f in $(sed -n 's/^SRCS := //p' Makefile); do   # the Makefile's list: every object of the regular build
+  if [ "$f" = "$SRC" ]; then OBJS="$OBJS $OBJ"; else OBJS="$OBJS ${f%.hip}.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build_ab/$NAME.so $OBJS -lz -lpthread -ldl
 rm -f "$OBJ"

@@ -1,4 +1,4 @@
-"""Compare two directories written by bench.py --dump-outputs file by file with np.array_equal.   usage: compare_dumps.py <dir A> <dir B>
+"""Compare two directories written by bench.py --dump-outputs or scripts/dump_call_outputs.py file by file with np.array_equal.   usage: compare_dumps.py <dir A> <dir B>
 Exit status 0 only if both hold the same .npy files and every one compares equal."""
 import os
 import sys
