@@ -1095,6 +1095,59 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
                                     int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
                                     orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results);
 
+/* ---- covisibility from the resident map: weights, best neighbours, local-map tracking (map.rs:339-386, :476-489; tracker.rs:826-843) ----
+ * The covisibility graph, computed where the slot tables lie instead of maintained on the host per association.  kfs [n_kfs] are
+ * the keyframes the caller considers (host array, copied before the call returns; is_bad filtering = leaving a keyframe out);
+ * every index below is a position in kfs[].  The reference's weight depends on the association history and its order on HashMap
+ * iteration, so the library fixes a derived, deterministic definition:
+ *   [spec] obs(k) = the DISTINCT slots s of kfs[k]'s slot table with 0 <= s < capacity and live[s] when the kernels run.  A
+ *     keyframe without a table observes nothing; a slot listed at two features of one keyframe counts once.
+ *   [spec] weight[q][k] = the number of slots in both obs(query[q]) and obs(k), for k != query[q], and weight[q][query[q]] = 0 (no self connection,
+ *     keyframe.rs:270-273).  Symmetric by construction; where every shared point is associated once per keyframe it equals
+ *     covisibility_weights() (map.rs:361-383).
+ *   [spec] best(q, n) = the keyframes with weight > 0 by weight descending, then by position in kfs[] ascending, at most n
+ *     (get_best_covisibles / get_local_keyframes_readonly, keyframe.rs:313-345, map.rs:476-489).  The tie order is fixed: a caller
+ *     that lists kfs[] by id ascending gets the order include/orbx_map.hpp recommends.
+ *   [spec] local keyframes of a frame with reference index r (tracker.rs:826-843): r >= 0: [r] ++ best(r, n_best) in that order
+ *     (the reference unions into a HashSet; the order is fixed because the first-seen order of the map-point list, and so PnP's
+ *     correspondence order, follows from it); r == -1 (no reference keyframe, :830-834): all of kfs[] in the order given.
+ *
+ * orbx_map_covisibility_device: query [n_queries] is a host array (copied before the call returns).  Outputs, device memory, each
+ * may be NULL: d_weights [n_queries][n_kfs] int32, d_best [n_queries][n_best] int32 (-1 padded), d_n_best [n_queries] int32 (the
+ * entries of the row that are not padding).  Asynchronous on the handle's stream, no host synchronisation inside; the store's mark
+ * tables are left as they were found, so a call costs what its keyframes cost, not what the map holds.  Every row is the same
+ * bytes in any batch composition.  orbx_map_covisibility: the same with host outputs, synchronous.
+ * ORBX_ERR_INVALID before anything is enqueued: an index outside [0, n_kfs), n_best < 0, n_queries > 65535, a keyframe of another
+ * handle or whose table is bound to another store.  n_kfs = 0 or n_queries = 0: nothing is done, ORBX_OK.
+ *
+ * orbx_map_track_local_device = orbx_map_track_frames_device (ORBX_MAP_SOURCE_KEYFRAMES) with frame b's keyframe list chosen on the
+ * device: the local keyframes of ref_kf[b] (host [n_frames], -1 = all of kfs[]) with n_best neighbours.  Added output d_local_kf
+ * [n_frames][1 + n_best] int32 (may be NULL): the list chosen, -1 padded; for ref_kf[b] = -1 the row is all -1 (the list is kfs[]
+ * itself).  Every other argument and output is orbx_map_track_frames_device's and equals, byte for byte, that call's on the
+ * keyframe lists the specification gives.  list_cap must reach the host-known bound: per frame the reference keyframe's feature
+ * count plus the n_best largest of the other keyframes', at most the capacity; for -1 the sum over all keyframes, at most the
+ * capacity.  ORBX_ERR_INVALID as above (ref_kf outside [-1, n_kfs)).  orbx_map_track_local: the host form, as orbx_map_track_frames
+ * is to its device form (local_kf [n_frames][1 + n_best], may be NULL).
+ * Still the caller's: ids, the id -> slot map, is_bad (by leaving keyframes out of kfs[]) and the spanning tree. */
+int orbx_map_covisibility_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries,
+                                 const int* query, int n_best, int* d_weights, int* d_best, int* d_n_best);
+int orbx_map_covisibility(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries,
+                          const int* query, int n_best, int* weights, int* best, int* n_best_out);
+int orbx_map_track_local_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                                orbx_map_points* mp, int n_frames, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf,
+                                int n_best, const orbx_keypoint* d_kp, const uint8_t* d_desc, const int* d_feat_start,
+                                const int* d_feat_count, int feat_count_stride, int max_feat, const double* d_search_poses_wc,
+                                const double* d_priors_wc, int list_cap, int* d_local_kf, int* d_list_offsets, int* d_list_slot,
+                                double* d_positions, uint8_t* d_mp_desc, int* d_offsets, double* d_pts3d, float* d_pts2d,
+                                int* d_mp_idx, int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out,
+                                orbx_pnp_result* d_pnp_results, int* d_matched, int* d_matched_slot, orbx_track_result* d_results);
+int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
+                         orbx_map_points* mp, int n_frames, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf, int n_best,
+                         const orbx_keypoint* kp, const uint8_t* desc, const int* feat_offsets, const double* search_poses_wc,
+                         const double* priors_wc, int list_cap, int* local_kf, int* list_offsets, int* list_slot, int* offsets,
+                         double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out, uint8_t* inlier_out,
+                         double* err_out, orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

@@ -798,10 +798,56 @@ struct MapTrackResult : TrackResult {
   std::vector<int> list_slot, matched_slot;
 };
 
+// Covisibility of the resident map (orbx_map_covisibility, orbx.h): row q belongs to keyframes[queries[q]]; every index is a
+// position in `keyframes`.  best rows are weight descending, then position ascending, -1 padded; n_best[q] entries are not padding.
+struct Covisibility {
+  int n_kfs = 0, n_best_max = 0;
+  std::vector<int> weights;      // [queries][n_kfs]
+  std::vector<int> best;         // [queries][n_best_max]
+  std::vector<int> n_best;       // [queries]
+  int weight(size_t q, size_t k) const { return weights[q * (size_t)n_kfs + k]; }
+  // get_best_covisibles (keyframe.rs:313-345) of query q
+  std::vector<int> best_of(size_t q) const {
+    const int* row = best.data() + q * (size_t)n_best_max;
+    return std::vector<int>(row, row + n_best[q]);
+  }
+};
+
+inline Covisibility map_covisibility(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& queries,
+                                     int n_best) {
+  Covisibility c;
+  c.n_kfs = (int)keyframes.size(); c.n_best_max = std::max(n_best, 0);
+  const size_t Q = queries.size();
+  c.weights.assign(Q * keyframes.size(), 0); c.best.assign(Q * (size_t)c.n_best_max, -1); c.n_best.assign(Q, 0);
+  h.check(orbx_map_covisibility(h.get(), store.get(), c.n_kfs, keyframes.data(), (int)Q, queries.data(), n_best, c.weights.empty() ? nullptr : c.weights.data(),
+                                c.best.empty() ? nullptr : c.best.data(), c.n_best.empty() ? nullptr : c.n_best.data()));
+  return c;
+}
+
+// The local-map form's source: the keyframes the caller considers, per frame the index of its reference keyframe (-1: all of
+// them) and the number of best covisibles taken beside it.  local_kf receives, per frame, what was chosen (-1 padded).
+struct MapLocalSource {
+  const std::vector<const orbx_keyframe*>* keyframes = nullptr;
+  const std::vector<int>* ref_kf = nullptr;
+  int n_best = 0;
+  std::vector<std::vector<int>>* local_kf = nullptr;
+};
+
 // The batch form: source = ORBX_MAP_SOURCE_KEYFRAMES or ORBX_MAP_SOURCE_SLOTS for every frame of the call; mode as track_frames.
+// With `local` the frames' own keyframes / slots are not read: the lists are chosen on the device (orbx_map_track_local).
 inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel& camera, MapPointStore& store, const std::vector<MapTrackFrame>& frames,
-                                                    int source, int mode, const orbx_track_config* cfg = nullptr) {
+                                                    int source, int mode, const orbx_track_config* cfg = nullptr, const MapLocalSource* local = nullptr) {
   const int B = (int)frames.size();
+  std::vector<int> kf_n;                                          // local: every keyframe's feature count
+  if (local) {
+    if (!local->keyframes || !local->ref_kf || (int)local->ref_kf->size() != B)
+      throw std::invalid_argument("map_track_frames: one reference keyframe index per frame");
+    for (const orbx_keyframe* k : *local->keyframes) {
+      int n = 0;
+      h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+      kf_n.push_back(n);
+    }
+  }
   orbx_track_config tc;
   orbx_default_track_config(mode, &tc);
   if (cfg) tc = *cfg;
@@ -826,7 +872,21 @@ inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel
     desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
     push7(sp, f.search_pose); push7(pr, f.prior);
     fo[b + 1] = (int)kp.size();
-    if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
+    if (local) {
+      // the host-known bound: the reference keyframe's features plus the n_best largest of the others' (all where it is -1)
+      const int r = (*local->ref_kf)[b];
+      size_t cand = 0;
+      if (r < 0 || r >= (int)kf_n.size()) {
+        for (int n : kf_n) cand += (size_t)n;
+      } else {
+        std::vector<int> others(kf_n);
+        others.erase(others.begin() + r);
+        std::sort(others.begin(), others.end(), std::greater<int>());
+        cand = (size_t)kf_n[(size_t)r];
+        for (size_t i = 0; i < others.size() && (int)i < local->n_best; ++i) cand += (size_t)others[i];
+      }
+      M += std::min(cand, (size_t)capacity);
+    } else if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
       size_t cand = 0;
       for (const orbx_keyframe* k : f.keyframes) {
         int n = 0;
@@ -849,9 +909,22 @@ inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel
   std::vector<orbx_pnp_result> pres(Bz);
   std::vector<orbx_track_result> res(Bz);
   const orbx_camera cam = camera.c();
-  h.check(orbx_map_track_frames(h.get(), &cam, &tc, &pc, store.get(), source, B, kfs.data(), ko.data(), src.data(), so.data(), kp.data(), desc.data(),
-                                fo.data(), sp.data(), pr.data(), (int)M, lo.data(), ls.data(), off.data(), p3.data(), p2.data(), mi.data(), fi.data(),
-                                poses.data(), inl.data(), err.data(), pres.data(), matched.data(), mslot.data(), res.data()));
+  if (local) {
+    const size_t stride = 1 + (size_t)std::max(local->n_best, 0);
+    std::vector<int> lk(Bz * stride, -1);
+    h.check(orbx_map_track_local(h.get(), &cam, &tc, &pc, store.get(), B, (int)local->keyframes->size(), local->keyframes->data(), local->ref_kf->data(),
+                                 local->n_best, kp.data(), desc.data(), fo.data(), sp.data(), pr.data(), (int)M, lk.data(), lo.data(), ls.data(), off.data(),
+                                 p3.data(), p2.data(), mi.data(), fi.data(), poses.data(), inl.data(), err.data(), pres.data(), matched.data(), mslot.data(),
+                                 res.data()));
+    if (local->local_kf) {
+      local->local_kf->clear();
+      for (int b = 0; b < B; ++b) local->local_kf->emplace_back(lk.begin() + (size_t)b * stride, lk.begin() + ((size_t)b + 1) * stride);
+    }
+  } else {
+    h.check(orbx_map_track_frames(h.get(), &cam, &tc, &pc, store.get(), source, B, kfs.data(), ko.data(), src.data(), so.data(), kp.data(), desc.data(),
+                                  fo.data(), sp.data(), pr.data(), (int)M, lo.data(), ls.data(), off.data(), p3.data(), p2.data(), mi.data(), fi.data(),
+                                  poses.data(), inl.data(), err.data(), pres.data(), matched.data(), mslot.data(), res.data()));
+  }
   std::vector<MapTrackResult> out(B);
   for (int b = 0; b < B; ++b) {
     MapTrackResult& r = out[b];
@@ -883,6 +956,20 @@ inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel
 inline MapTrackResult track_local_map(Handle& h, const CameraModel& camera, MapPointStore& store, const FeatureSet& features,
                                       const std::vector<const orbx_keyframe*>& keyframes, const SE3& pose, const SE3& imu_prior) {
   return map_track_frames(h, camera, store, {MapTrackFrame{&features, keyframes, {}, pose, imu_prior}}, ORBX_MAP_SOURCE_KEYFRAMES, 1)[0];
+}
+
+// tracker.rs:826-988 with K1 u K2 chosen on the device as well (tracker.rs:826-843; map.rs:476-489): `keyframes` are the keyframes the
+// caller considers (is_bad ones left out), ref_kf the index of the frame's reference keyframe among them (-1: none, all of them
+// are taken), n_best the covisibles taken beside it.  local_kf, when given, receives [ref_kf] ++ best, -1 padded (all -1 for -1).
+inline MapTrackResult track_local_map(Handle& h, const CameraModel& camera, MapPointStore& store, const FeatureSet& features,
+                                      const std::vector<const orbx_keyframe*>& keyframes, int ref_kf, int n_best, const SE3& pose, const SE3& imu_prior,
+                                      std::vector<int>* local_kf = nullptr) {
+  const std::vector<int> ref{ref_kf};
+  std::vector<std::vector<int>> chosen;
+  const MapLocalSource local{&keyframes, &ref, n_best, &chosen};
+  MapTrackResult r = map_track_frames(h, camera, store, {MapTrackFrame{&features, {}, {}, pose, imu_prior}}, ORBX_MAP_SOURCE_KEYFRAMES, 1, nullptr, &local)[0];
+  if (local_kf) *local_kf = chosen[0];
+  return r;
 }
 
 // tracker.rs:1086-1192 on one frame: `slots` = the previous frame's matched_slot (-1 entries and slots no longer live are skipped).

@@ -100,6 +100,7 @@ ABI_SYMBOLS = [
     "orbx_map_points_create", "orbx_map_points_destroy", "orbx_map_points_info", "orbx_map_points_set", "orbx_map_points_set_device",
     "orbx_map_points_erase", "orbx_map_points_download", "orbx_keyframe_set_map_point_slots", "orbx_map_select_points_device",
     "orbx_map_track_frames_device", "orbx_map_track_frames", "orbx_map_track_reference_device",
+    "orbx_map_covisibility_device", "orbx_map_covisibility", "orbx_map_track_local_device", "orbx_map_track_local",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 
@@ -1170,6 +1171,127 @@ class Handle:
         for k in ("matches", "points3d", "points2d", "kf_idx", "feat_idx", "inlier", "err", "kf_positions", "kf_valid"):
             o[k] = o[k][:K]
         return o
+
+    # ---- covisibility from the resident map (include/orbx.h, "covisibility from the resident map") ----
+    @staticmethod
+    def _kf_array(keyframes):
+        return (C.c_void_p * max(len(keyframes), 1))(*[k._p for k in keyframes])
+
+    @staticmethod
+    def _local_bounds(mp, keyframes, ref_kf, n_best):
+        """per frame the host-known bound of its list: the reference keyframe's feature count plus the n_best largest of the
+        others', every keyframe's where the reference is -1, at most the capacity"""
+        ns = np.array([k.n for k in keyframes], np.int64)
+        K = len(ns)
+        order = np.argsort(-ns, kind="stable")
+        place = np.empty(K, np.int64); place[order] = np.arange(K)
+        top = np.concatenate([[0], np.cumsum(ns[order])])                  # top[i]: the i largest feature counts summed
+        nb = min(max(n_best, 0), max(K - 1, 0))
+        out = []
+        for r in ref_kf:
+            c = top[K] if r < 0 or r >= K else (top[nb + 1] if place[r] < nb else top[nb] + ns[r])
+            out.append(int(min(c, mp.capacity)))
+        return out
+
+    def map_covisibility_device(self, mp: "MapPointStore", keyframes, queries, n_best=0, weights=True, device=None):
+        """Covisibility weights and best neighbours of keyframes[q] for q in queries (indices into `keyframes`, a list of KeyFrame),
+        counted on the device from the slot tables and the store's live bytes (orbx_map_covisibility_device).  Returns a dict of
+        CUDA tensors: weights [Q,n_kfs] int32 (absent with weights=False), and with n_best > 0 best [Q,n_best] int32 (indices into
+        `keyframes`, weight descending then index ascending, -1 padded) and n_best [Q] int32.  Asynchronous on the handle's stream."""
+        import torch
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1)
+        Q, K, nb = len(q), len(keyframes), int(n_best)
+        dev = device or torch.device("cuda", self.device)
+        o = {}
+        if weights:
+            o["weights"] = torch.zeros((Q, K), dtype=torch.int32, device=dev)
+        if nb > 0:
+            o["best"] = torch.full((Q, nb), -1, dtype=torch.int32, device=dev)
+            o["n_best"] = torch.zeros(Q, dtype=torch.int32, device=dev)
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_covisibility_device(self._h, mp._p, C.c_int(K), self._kf_array(keyframes), C.c_int(Q), _vp(q if Q else np.zeros(1, np.int32)),
+                                                         C.c_int(nb), _vp(o.get("weights")), _vp(o.get("best")), _vp(o.get("n_best"))))
+        return o
+
+    def map_covisibility(self, mp: "MapPointStore", keyframes, queries, n_best=0):
+        """The host form (orbx_map_covisibility), synchronous: (weights [Q,n_kfs] int32, best [Q,n_best] int32, n_best [Q] int32)
+        as numpy arrays."""
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1)
+        Q, K, nb = len(q), len(keyframes), int(n_best)
+        w = np.zeros((Q, K), np.int32); best = np.full((Q, max(nb, 0)), -1, np.int32); cnt = np.zeros(Q, np.int32)
+        self._check(self._L.orbx_map_covisibility(self._h, mp._p, C.c_int(K), self._kf_array(keyframes), C.c_int(Q), _vp(q if Q else np.zeros(1, np.int32)),
+                                                  C.c_int(nb), _vp(w) if w.size else None, _vp(best) if best.size else None, _vp(cnt) if Q else None))
+        return w, best, cnt
+
+    def map_track_local_device(self, camera, mp: "MapPointStore", keyframes, ref_kf, n_best, kp, desc, feat_start, feat_count, max_feat, search_poses_wc,
+                               priors_wc, cfg: "TrackConfig" = None, pnp_cfg: PnPConfig = None):
+        """map_track_frames_device with every frame's keyframe list chosen on the device (orbx_map_track_local_device): frame b's
+        list is [ref_kf[b]] + its n_best best covisibles among `keyframes` (a list of KeyFrame; ref_kf holds indices into it), or
+        all of `keyframes` where ref_kf[b] is -1.  Returns map_track_frames_device's dict plus local_kf [B,1+n_best] int32: the
+        keyframes chosen, -1 padded (all -1 for ref_kf[b] = -1)."""
+        import torch
+        ref = np.ascontiguousarray(ref_kf, np.int32).reshape(-1)
+        B, nb = len(ref), int(n_best)
+        bounds = self._local_bounds(mp, keyframes, ref.tolist(), nb)
+        M = int(sum(bounds))
+        dev = search_poses_wc.device
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(offsets=mk(max(B, 0) + 1, torch.int32), points3d=mk((max(M, 1), 3), torch.float64), points2d=mk((max(M, 1), 2), torch.float32),
+                 mp_idx=mk(max(M, 1), torch.int32), feat_idx=mk(max(M, 1), torch.int32), poses=mk((max(B, 1), 7), torch.float64),
+                 inlier=mk(max(M, 1), torch.uint8), err=mk(max(M, 1), torch.float64), pnp_results=mk((max(B, 1), PNP_RESULT.itemsize), torch.uint8),
+                 matched=mk((max(B, 1), max(int(max_feat), 1)), torch.int32), matched_slot=mk((max(B, 1), max(int(max_feat), 1)), torch.int32),
+                 results=mk((max(B, 1), TRACK_RESULT.itemsize), torch.uint8), local_kf=mk((max(B, 1), 1 + max(nb, 0)), torch.int32))
+        o.update(self._map_list_outputs(B, M, dev))
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        fc_stride = self._feat_count_stride(feat_count, B)
+        self._after_torch(kp, desc, feat_start, feat_count, search_poses_wc, priors_wc, *o.values())
+        self._check(self._L.orbx_map_track_local_device(
+            self._h, C.byref(cam), C.byref(c), C.byref(pc), mp._p, C.c_int(B), C.c_int(len(keyframes)), self._kf_array(keyframes),
+            _vp(ref if B else np.zeros(1, np.int32)), C.c_int(nb), _vp(kp), _vp(desc), _vp(feat_start), _vp(feat_count), C.c_int(fc_stride), C.c_int(int(max_feat)),
+            _vp(search_poses_wc), _vp(priors_wc), C.c_int(M), _vp(o["local_kf"]), _vp(o["list_offsets"]), _vp(o["list_slot"]), _vp(o["positions"]),
+            _vp(o["mp_desc"]), _vp(o["offsets"]), _vp(o["points3d"]), _vp(o["points2d"]), _vp(o["mp_idx"]), _vp(o["feat_idx"]), _vp(o["poses"]), _vp(o["inlier"]),
+            _vp(o["err"]), _vp(o["pnp_results"]), _vp(o["matched"]), _vp(o["matched_slot"]), _vp(o["results"])))
+        o["matched"] = o["matched"][:, :int(max_feat)]; o["matched_slot"] = o["matched_slot"][:, :int(max_feat)]
+        for k in ("points3d", "points2d", "mp_idx", "feat_idx", "inlier", "err", "list_slot", "positions", "mp_desc"):
+            o[k] = o[k][:M]
+        return o
+
+    def map_track_local(self, camera, mp: "MapPointStore", frames, keyframes, ref_kf, n_best, cfg: "TrackConfig" = None, pnp_cfg: PnPConfig = None):
+        """The host form (orbx_map_track_local): frames = [(kp, desc, search_pose_wc, prior_wc), ...] in host arrays, keyframes /
+        ref_kf / n_best as map_track_local_device.  One upload, one download.  Returns [(TrackFrameResult, list_slot, matched_slot,
+        local_kf [1+n_best]), ...]."""
+        B, nb = len(frames), int(n_best)
+        ref = np.ascontiguousarray(ref_kf, np.int32).reshape(-1)
+        if len(ref) != B:
+            raise ValueError("one reference keyframe index per frame")
+        bounds = self._local_bounds(mp, keyframes, ref.tolist(), nb)
+        kps = [np.ascontiguousarray(f[0], KEYPOINT).reshape(-1) for f in frames]
+        des = [np.ascontiguousarray(f[1], np.uint8).reshape(-1, 32) for f in frames]
+        if any(len(a) != len(b) for a, b in zip(kps, des)):
+            raise ValueError("keypoints / descriptors differ in length")
+        fo = np.zeros(B + 1, np.int32); fo[1:] = np.cumsum([len(a) for a in kps])
+        NF, M = int(fo[-1]), int(sum(bounds))
+        kp = np.concatenate(kps) if NF else np.zeros(1, KEYPOINT)
+        de = np.concatenate(des) if NF else np.zeros((1, 32), np.uint8)
+        sp = np.ascontiguousarray(np.stack([np.asarray(f[2], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        pr = np.ascontiguousarray(np.stack([np.asarray(f[3], np.float64).reshape(7) for f in frames]) if B else np.zeros((1, 7)), np.float64)
+        Mz, Bz = max(M, 1), max(B, 1)
+        lo = np.zeros(B + 1, np.int32); ls = np.zeros(Mz, np.int32); off = np.zeros(B + 1, np.int32); lk = np.full((Bz, 1 + max(nb, 0)), -1, np.int32)
+        p3 = np.zeros((Mz, 3)); p2 = np.zeros((Mz, 2), np.float32); mi = np.zeros(Mz, np.int32); fi = np.zeros(Mz, np.int32)
+        poses = np.zeros((Bz, 7)); inl = np.zeros(Mz, np.uint8); err = np.zeros(Mz)
+        pres = np.zeros(Bz, PNP_RESULT); matched = np.zeros(max(NF, 1), np.int32); mslot = np.zeros(max(NF, 1), np.int32); res = np.zeros(Bz, TRACK_RESULT)
+        c = (cfg or TrackConfig())._c(); pc = (pnp_cfg or PnPConfig())._c(); cam = camera._c()
+        self._check(self._L.orbx_map_track_local(
+            self._h, C.byref(cam), C.byref(c), C.byref(pc), mp._p, C.c_int(B), C.c_int(len(keyframes)), self._kf_array(keyframes),
+            _vp(ref if B else np.zeros(1, np.int32)), C.c_int(nb), _vp(kp), _vp(de), _vp(fo), _vp(sp), _vp(pr), C.c_int(M), _vp(lk), _vp(lo), _vp(ls), _vp(off),
+            _vp(p3), _vp(p2), _vp(mi), _vp(fi), _vp(poses), _vp(inl), _vp(err), _vp(pres), _vp(matched), _vp(mslot), _vp(res)))
+        out = []
+        for b in range(B):
+            s = slice(int(off[b]), int(off[b + 1]))
+            t = TrackFrameResult(poses[b].copy(), int(res[b]["n_inliers"]), matched[fo[b]:fo[b + 1]].copy(), err[s].copy(), inl[s].astype(bool), p3[s].copy(),
+                                 p2[s].copy(), mi[s].copy(), fi[s].copy(), int(res[b]["status"]), int(res[b]["n_in_front"]), _pnp_stats(pres[b]))
+            out.append((t, ls[lo[b]:lo[b + 1]].copy(), mslot[fo[b]:fo[b + 1]].copy(), lk[b].copy()))
+        return out
 
     def compute_sim3_ransac_batch(self, problems, cfg: "Sim3SolverConfig" = None):
         """compute_sim3_ransac (sim3_solver.rs:63-145) for many point sets [(points1 [n,3], points2 [n,3]), ...] in one call (one
@@ -2312,6 +2434,21 @@ class BaBatch:
                 res.append(dict(poses_wc=self._views[i][0], points=self._views[i][1], iterations=a.iterations, initial_error=a.initial_error,
                                 final_error=a.final_error))
         return res
+
+
+def covisibility_lists(kf_ids, best, n_best):
+    """The covisibility lists of MapSnapshot from the device result: kf_ids [nkf] (the ids of the keyframes handed to
+    map_covisibility, in that order, every one of them a query in the same order), best [nkf,n] / n_best [nkf] as returned.
+    -> (cov_start int32 [nkf+1], cov_kf_id uint64 [ncov]): per keyframe its neighbours' ids, weight descending then position
+    ascending."""
+    ids = np.asarray(kf_ids, np.uint64).reshape(-1)
+    best = np.asarray(best, np.int64).reshape(len(ids), -1)
+    cnt = np.asarray(n_best, np.int64).reshape(-1)
+    if len(cnt) != len(ids):
+        raise ValueError("one best row per keyframe")
+    start = np.zeros(len(ids) + 1, np.int32); start[1:] = np.cumsum(cnt)
+    rows = [ids[best[k, :cnt[k]]] for k in range(len(ids))]
+    return start, (np.concatenate(rows) if rows else np.zeros(0, np.uint64)).astype(np.uint64)
 
 
 class MapSnapshot:

@@ -26,10 +26,11 @@ int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_
   const size_t n1 = (size_t)(n > 0 ? n : 1);
   Carve blk;
   const size_t o_kp = blk.take(sizeof(orbx_keypoint) * n1), o_desc = blk.take(32 * n1), o_pts = blk.take(24 * n1), o_has = blk.take(n1), o_mp = blk.take(n1),
-               o_slot = blk.take(4 * n1), total = blk.off;
+               o_slot = blk.take(4 * n1), o_uniq = blk.take(4 * n1), total = blk.off;
   if (hipMalloc((void**)&kf->block, total) != hipSuccess) { delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: out of device memory"); }
   kf->d_kp = (orbx_keypoint*)(kf->block + o_kp); kf->d_desc = kf->block + o_desc; kf->d_points = (double*)(kf->block + o_pts);
   kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp; kf->d_mp_slot = (int*)(kf->block + o_slot);
+  kf->d_mp_uniq = (int*)(kf->block + o_uniq);
   hipStream_t st = h->stream;
   hipError_t e = hipMemsetAsync(kf->block + o_pts, 0, total - o_pts, st);       // points (0,0,0), no stereo point, no map point
   if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_kp, d_kp, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyDeviceToDevice, st);

@@ -17,7 +17,21 @@
 //                     compaction inside the chunk by ballot / prefix; list_slot, positions and descriptors gathered
 // Every frame has a table of its own ([frame][capacity]), so frames of one call that share keyframes do not meet.  The only atomics
 // are that integer min: every output is a deterministic function of the inputs.
+//
+// Covisibility (map.rs:339-386, :476-489; tracker.rs:826-843) counts, for a marked set of keyframes, how many of its live slots
+// every other keyframe observes, and ranks the result:
+//   cov_mark_kernel   (chunk of a member keyframe's features, member) mark[query][slot] = 1 for live slots; run again with 0 behind
+//                     the count, so that a call leaves the table as it found it (plain stores of one value: no atomics)
+//   cov_count_kernel  (keyframe k, group of COV_Q queries) walks k's de-duplicated slot table once, tests live and each query's
+//                     marks, block_sum -> weights[q][k]; 0 where k is the query itself
+//   cov_rank_kernel   one workgroup per query: rank(i) = #{j : w_j > w_i or (w_j == w_i and j < i)}; i goes to best[rank] when
+//                     w_i > 0 and rank < n_best
+//   cov_seg_kernel    one workgroup per frame: [reference] ++ best (or every keyframe) as the MapSeg / n_cand arrays that the three
+//                     selection launches read, which then run unchanged
+// A keyframe's observed set counts a slot once: orbx_keyframe_set_map_point_slots keeps, beside the table, a copy with every repeat
+// set to -1 (d_mp_uniq), so distinctness costs nothing per (query, keyframe).
 #include <algorithm>
+#include <numeric>
 #include <vector>
 
 #include "block_dev.hpp"
@@ -34,6 +48,7 @@ struct orbx_map_points {
   std::vector<unsigned> stamp;         // per slot the last call that named it (a slot listed twice in one call is refused)
   unsigned gen = 0;
   DevBuf first;                        // [frames][capacity] first-sighting tables, EMPTY between calls
+  DevBuf mark;                         // [queries][capacity] bytes: covisibility's marked sets, 0 between calls (never shared with `first`)
 };
 
 namespace {
@@ -200,6 +215,134 @@ __global__ __launch_bounds__(MS_THREADS) void map_ref_gather_kernel(const MapRef
   out_pos[3 * o] = ok ? pos[3 * (size_t)s] : 0.0; out_pos[3 * o + 1] = ok ? pos[3 * (size_t)s + 1] : 0.0; out_pos[3 * o + 2] = ok ? pos[3 * (size_t)s + 2] : 0.0;
 }
 
+// ---- covisibility ------------------------------------------------------------------------------------------------------
+
+constexpr int COV_Q = 4;                         // queries one count workgroup serves: a keyframe's table and live bytes are read once for all of them
+constexpr int COV_TILE = 1024;                   // weights of a row the ranking workgroup holds in LDS at a time
+
+// One keyframe of a call: its slot table, the same with repeats set to -1 (both NULL: no table), its features.
+struct CovKf {
+  const int* slots; const int* uniq;
+  int n, pad_;
+};
+// Keyframe `kf` belongs to query q's marked set.  (The public calls mark one keyframe per query; the kernels do not care.)
+struct CovMember {
+  int kf, q;
+};
+struct CovArgs {
+  int capacity, n_kfs, n_q, n_best;
+  const uint8_t* live; const CovKf* kfs; const CovMember* members;
+  const int* self;                               // [n_q] the keyframe whose weight is 0 in row q (the query itself), -1: none
+  uint8_t* mark; int* weights; int* best; int* n_best_out;
+};
+
+__global__ __launch_bounds__(MS_THREADS) void cov_mark_kernel(CovArgs A, int value) {
+  const CovMember m = A.members[blockIdx.y];
+  const CovKf kf = A.kfs[m.kf];
+  if (!kf.uniq) return;
+  uint8_t* mark = A.mark + (size_t)m.q * A.capacity;
+#pragma unroll
+  for (int k = 0; k < MS_PER; ++k) {
+    const int i = blockIdx.x * MS_CHUNK + k * MS_THREADS + threadIdx.x;
+    if (i >= kf.n) continue;
+    const int s = kf.uniq[i];
+    if (s >= 0 && s < A.capacity && (value == 0 || A.live[s])) mark[s] = (uint8_t)value;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void cov_count_kernel(CovArgs A) {
+  __shared__ int wave_tot[(MS_THREADS / 64) * COV_Q];
+  const int k = blockIdx.x, q0 = blockIdx.y * COV_Q, nq = min(COV_Q, A.n_q - q0);
+  const CovKf kf = A.kfs[k];
+  const uint8_t* mark = A.mark + (size_t)q0 * A.capacity;
+  int c[COV_Q];
+#pragma unroll
+  for (int j = 0; j < COV_Q; ++j) c[j] = 0;
+  if (kf.uniq) {
+    for (int i = threadIdx.x; i < kf.n; i += MS_THREADS) {
+      const int s = kf.uniq[i];
+      if (s < 0 || s >= A.capacity || !A.live[s]) continue;
+#pragma unroll
+      for (int j = 0; j < COV_Q; ++j)
+        if (j < nq) c[j] += mark[(size_t)j * A.capacity + s];
+    }
+  }
+  block_sum<MS_THREADS, COV_Q>(c, wave_tot);
+#pragma unroll
+  for (int j = 0; j < COV_Q; ++j)
+    if (j < nq && (int)threadIdx.x == j) A.weights[(size_t)(q0 + j) * A.n_kfs + k] = A.self[q0 + j] == k ? 0 : c[j];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void cov_rank_kernel(CovArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  __shared__ int tile[COV_TILE];
+  const int q = blockIdx.x, n = A.n_kfs, tid = threadIdx.x;
+  const int* w = A.weights + (size_t)q * n;
+  int* best = A.best ? A.best + (size_t)q * A.n_best : nullptr;
+  int positive = 0;
+  for (int i0 = 0; i0 < n; i0 += MS_THREADS) {
+    const int i = i0 + tid;
+    const int wi = i < n ? w[i] : 0;
+    positive += wi > 0;
+    if (!best) continue;                                                   // (the same in every thread)
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += COV_TILE) {                             // the row through LDS, COV_TILE weights at a time: every lane reads the same word
+      __syncthreads();
+      for (int t = tid; t < COV_TILE; t += MS_THREADS) tile[t] = j0 + t < n ? w[j0 + t] : 0;
+      __syncthreads();
+      if (wi > 0) {
+        const int m = min(COV_TILE, n - j0);
+        for (int t = 0; t < m; ++t) {
+          const int wj = tile[t];
+          rank += wj > wi || (wj == wi && j0 + t < i);
+        }
+      }
+    }
+    if (wi > 0 && rank < A.n_best) best[rank] = i;
+  }
+  positive = block_sum<MS_THREADS>(positive, wave_tot);
+  const int kept = min(positive, A.n_best);                                // ranks [0, kept) are taken, each by one keyframe: the positive weights outrank the zeros
+  if (A.n_best_out && threadIdx.x == 0) A.n_best_out[q] = kept;
+  if (best)
+    for (int j = kept + threadIdx.x; j < A.n_best; j += MS_THREADS) best[j] = -1;
+}
+
+// Frame b's keyframes as selection segments [seg_off[b], seg_off[b+1]): ref >= 0: the reference keyframe, then row b of best (-1:
+// a segment without candidates); ref == -1: every keyframe of the call in order.  The segments' bases by an ordered scan.
+__global__ __launch_bounds__(MS_THREADS) void cov_seg_kernel(CovArgs A, const int* ref, const int* seg_off, MapSeg* segs, int* n_cand, int* local_kf) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = ref[b], so = seg_off[b], S = seg_off[b + 1] - so;
+  int carry = 0;
+  for (int j0 = 0; j0 < S; j0 += MS_THREADS) {
+    const int j = j0 + tid;
+    int kfi = -1;
+    if (j < S) kfi = r < 0 ? j : j == 0 ? r : A.best[(size_t)b * A.n_best + (j - 1)];
+    CovKf kf{nullptr, nullptr, 0, 0};
+    if (kfi >= 0) kf = A.kfs[kfi];
+    int incl = kf.n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(incl, d);
+      if (lane >= d) incl += t;
+    }
+    __syncthreads();                                                       // (the previous round's totals are no longer read)
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int v = 0; v < MS_THREADS / 64; ++v) { const int t = wave_tot[v]; before += v < wave ? t : 0; all += t; }
+    if (j < S) {
+      segs[so + j] = MapSeg{kf.slots, carry + before + incl - kf.n, kf.n};
+      if (local_kf && r >= 0) local_kf[(size_t)b * (1 + A.n_best) + j] = kfi;
+    }
+    carry += all;
+  }
+  if (tid == 0) n_cand[b] = carry;
+  if (local_kf && r < 0)
+    for (int j = tid; j < 1 + A.n_best; j += MS_THREADS) local_kf[(size_t)b * (1 + A.n_best) + j] = -1;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // slots [n] of a set / erase call: in range, and (once) none twice
@@ -290,16 +433,10 @@ int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int sour
   return ORBX_OK;
 }
 
-// The three launches on the handle's stream.  d_src_slots and every output are device memory; list_cap: rows the outputs hold.
-int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int source, int B, const SelPlan& P, const int* d_src_slots, const int* src_offsets,
-                      int list_cap, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
-  const int total = P.bound_off[(size_t)B];
-  if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (the sum over the frames of their candidates, "
-                                         "per frame at most the capacity where keyframes are the source)", who, list_cap, total);
-  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15) ||
-      (source == ORBX_MAP_SOURCE_SLOTS && total > 0 && !d_src_slots))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
+// The three launches on the handle's stream, every table already in device memory (uploaded by ms_select_enqueue, or written by
+// cov_seg_kernel); max_cand bounds every frame's candidates on the host.
+int ms_select_launch(orbx_handle* h, orbx_map_points* mp, int source, int B, int max_cand, const MapSeg* d_segs, const int* d_seg_off, const int* d_n_cand,
+                     const int* d_src_slots, const int* d_src_off, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
   const size_t Bz = (size_t)B;
   if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
     const size_t need = 4 * Bz * (size_t)mp->capacity;
@@ -308,25 +445,16 @@ int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int 
       ORBX_HIP(h, hipMemsetAsync(mp->first.p, MS_EMPTY & 0xff, mp->first.bytes, h->stream));
     }
   }
-  const int n_chunk = std::max(1, (P.max_cand + MS_CHUNK - 1) / MS_CHUNK);
-  Carve up, ws;
-  const size_t o_sg = up.take(sizeof(MapSeg) * P.segs.size()), o_so = up.take(4 * (Bz + 1)), o_nc = up.take(4 * Bz), o_sr = up.take(4 * (Bz + 1));
+  const int n_chunk = std::max(1, (max_cand + MS_CHUNK - 1) / MS_CHUNK);
+  Carve ws;
   const size_t o_ca = ws.take(4 * Bz * (size_t)n_chunk * MS_CHUNK), o_cc = ws.take(4 * Bz * (size_t)n_chunk);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
-  if (!P.segs.empty()) std::memcpy(hs + o_sg, P.segs.data(), sizeof(MapSeg) * P.segs.size());
-  std::memcpy(hs + o_so, P.seg_off.data(), 4 * (Bz + 1));
-  std::memcpy(hs + o_nc, P.n_cand.data(), 4 * Bz);
-  if (source == ORBX_MAP_SOURCE_SLOTS) std::memcpy(hs + o_sr, src_offsets, 4 * (Bz + 1));
-  else std::memset(hs + o_sr, 0, 4 * (Bz + 1));
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
   if (int rc = orbx_reserve(h, h->ws_map[0], ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_map[0].p;
   SelArgs A{};
   A.source = source; A.capacity = mp->capacity; A.n_chunk = n_chunk;
   A.live = mp->d_live; A.pos = mp->d_pos; A.desc = mp->d_desc;
-  A.segs = (const MapSeg*)(ds + o_sg); A.seg_off = (const int*)(ds + o_so); A.n_cand = (const int*)(ds + o_nc);
-  A.src = d_src_slots; A.src_off = (const int*)(ds + o_sr);
+  A.segs = d_segs; A.seg_off = d_seg_off; A.n_cand = d_n_cand;
+  A.src = d_src_slots; A.src_off = d_src_off;
   A.first = (int*)mp->first.p; A.cand = (int*)(w + o_ca); A.chunk_count = (int*)(w + o_cc);
   A.list_off = d_list_off; A.list_slot = d_list_slot; A.out_pos = d_positions; A.out_desc = d_mp_desc;
   const dim3 grid(n_chunk, B), block(MS_THREADS);
@@ -346,12 +474,305 @@ int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int 
   return ORBX_OK;
 }
 
+// The selection from host tables: they go up through the ring, then the launches.  d_src_slots and every output are device memory;
+// list_cap: rows the outputs hold.
+int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int source, int B, const SelPlan& P, const int* d_src_slots, const int* src_offsets,
+                      int list_cap, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
+  const int total = P.bound_off[(size_t)B];
+  if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (the sum over the frames of their candidates, "
+                                         "per frame at most the capacity where keyframes are the source)", who, list_cap, total);
+  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15) ||
+      (source == ORBX_MAP_SOURCE_SLOTS && total > 0 && !d_src_slots))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)B;
+  Carve up;
+  const size_t o_sg = up.take(sizeof(MapSeg) * P.segs.size()), o_so = up.take(4 * (Bz + 1)), o_nc = up.take(4 * Bz), o_sr = up.take(4 * (Bz + 1));
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
+  if (!P.segs.empty()) std::memcpy(hs + o_sg, P.segs.data(), sizeof(MapSeg) * P.segs.size());
+  std::memcpy(hs + o_so, P.seg_off.data(), 4 * (Bz + 1));
+  std::memcpy(hs + o_nc, P.n_cand.data(), 4 * Bz);
+  if (source == ORBX_MAP_SOURCE_SLOTS) std::memcpy(hs + o_sr, src_offsets, 4 * (Bz + 1));
+  else std::memset(hs + o_sr, 0, 4 * (Bz + 1));
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
+  return ms_select_launch(h, mp, source, B, P.max_cand, (const MapSeg*)(ds + o_sg), (const int*)(ds + o_so), (const int*)(ds + o_nc), d_src_slots,
+                          (const int*)(ds + o_sr), d_list_off, d_list_slot, d_positions, d_mp_desc);
+}
+
 int ms_matched_slot_enqueue(orbx_handle* h, int B, int max_feat, const int* d_matched, const int* d_list_off, const int* d_list_slot, int* d_matched_slot) {
   if (max_feat <= 0) return ORBX_OK;
   ProfScope ps(h, "map_matched_slot_kernel", true);
   hipLaunchKernelGGL(map_matched_slot_kernel, dim3((max_feat + MS_THREADS - 1) / MS_THREADS, B), dim3(MS_THREADS), 0, h->stream, d_matched, d_list_off,
                      d_list_slot, max_feat, d_matched_slot);
   ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// ---- covisibility, host side ---------------------------------------------------------------------------------------------
+
+// The keyframes of a covisibility call, checked as ms_plan checks a selection's.
+struct CovPlan {
+  std::vector<CovKf> kfs;
+  int max_n = 0;
+};
+
+int cov_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_best, CovPlan& P) {
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (n_kfs < 0 || (n_kfs > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (n_kfs >= 0)", who);
+  if (n_best < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_best must not be negative", who);
+  P.kfs.resize((size_t)n_kfs);
+  for (int t = 0; t < n_kfs; ++t) {
+    const orbx_keyframe* kf = kfs[t];
+    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
+    if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+    P.kfs[(size_t)t] = CovKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, 0};
+    P.max_n = std::max(P.max_n, kf->n);
+  }
+  return ORBX_OK;
+}
+
+// What cov_enqueue adds for the tracking call: frame b's segments (seg_off: host [B+1]) and what was chosen.  The three arrays it
+// fills in the call's workspace are answered for ms_select_launch.
+struct CovSegs {
+  const int* seg_off; int* d_local_kf;
+  const MapSeg* d_segs; const int* d_seg_off; const int* d_n_cand;
+};
+
+// Mark, count, clear, rank (and the segments) on the handle's stream.  query [Q]: indices into the call's keyframes, -1 (only with
+// `segs`: a frame without a reference keyframe) marks nothing.  Outputs that are NULL and needed are kept in the call's workspace.
+int cov_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int Q, const int* query, int n_best, int* d_weights, int* d_best, int* d_n_best,
+                CovSegs* segs) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t Qz = (size_t)Q, K = P.kfs.size(), n_seg = segs ? (size_t)segs->seg_off[Q] : 0;
+  const bool rank = d_best || d_n_best || segs;
+  std::vector<CovMember> members;
+  int max_qn = 0;
+  for (int q = 0; q < Q; ++q)
+    if (query[q] >= 0) { members.push_back(CovMember{query[q], q}); max_qn = std::max(max_qn, P.kfs[(size_t)query[q]].n); }
+  const size_t need = Qz * (size_t)mp->capacity;
+  if (mp->mark.bytes < need) {                                              // the one fill of the tables: calls leave them 0
+    if (int rc = orbx_reserve(h, mp->mark, need)) return rc;
+    ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
+  }
+  Carve up, ws;
+  const size_t o_kf = up.take(sizeof(CovKf) * K), o_me = up.take(sizeof(CovMember) * members.size()), o_se = up.take(4 * Qz), o_so = up.take(segs ? 4 * (Qz + 1) : 0);
+  const size_t o_we = ws.take(d_weights ? 0 : 4 * Qz * K), o_be = ws.take(d_best || !segs ? 0 : 4 * Qz * (size_t)n_best), o_sg = ws.take(sizeof(MapSeg) * n_seg),
+               o_nc = ws.take(segs ? 4 * Qz : 0);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[5], up.off, &hs, &ds)) return rc;
+  if (K) std::memcpy(hs + o_kf, P.kfs.data(), sizeof(CovKf) * K);
+  if (!members.empty()) std::memcpy(hs + o_me, members.data(), sizeof(CovMember) * members.size());
+  std::memcpy(hs + o_se, query, 4 * Qz);
+  if (segs) std::memcpy(hs + o_so, segs->seg_off, 4 * (Qz + 1));
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[5], up.off)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_map[4], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[4].p;
+  CovArgs A{};
+  A.capacity = mp->capacity; A.n_kfs = (int)K; A.n_q = Q; A.n_best = n_best;
+  A.live = mp->d_live; A.kfs = (const CovKf*)(ds + o_kf); A.members = (const CovMember*)(ds + o_me); A.self = (const int*)(ds + o_se);
+  A.mark = (uint8_t*)mp->mark.p; A.weights = d_weights ? d_weights : (int*)(w + o_we);
+  A.best = d_best ? d_best : segs ? (int*)(w + o_be) : nullptr; A.n_best_out = d_n_best;
+  const dim3 block(MS_THREADS), mark_grid(std::max(1, (max_qn + MS_CHUNK - 1) / MS_CHUNK), (unsigned)members.size());
+  const bool marks = !members.empty() && max_qn > 0 && K > 0;
+  if (marks) {
+    ProfScope ps(h, "cov_mark_kernel");
+    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, A, 1);
+  }
+  if (K > 0) {
+    ProfScope ps(h, "cov_count_kernel", marks);
+    hipLaunchKernelGGL(cov_count_kernel, dim3((unsigned)K, (Q + COV_Q - 1) / COV_Q), block, 0, h->stream, A);
+  }
+  if (marks) {
+    ProfScope ps(h, "cov_mark_kernel", true);
+    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, A, 0);
+  }
+  if (rank) {
+    ProfScope ps(h, "cov_rank_kernel", K > 0);
+    hipLaunchKernelGGL(cov_rank_kernel, dim3(Q), block, 0, h->stream, A);
+  }
+  if (segs) {
+    ProfScope ps(h, "cov_seg_kernel", true);
+    hipLaunchKernelGGL(cov_seg_kernel, dim3(Q), block, 0, h->stream, A, A.self, (const int*)(ds + o_so), (MapSeg*)(w + o_sg), (int*)(w + o_nc), segs->d_local_kf);
+    segs->d_segs = (const MapSeg*)(w + o_sg); segs->d_seg_off = (const int*)(ds + o_so); segs->d_n_cand = (const int*)(w + o_nc);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+int cov_check_queries(orbx_handle* h, const char* who, const char* name, int n, const int* idx, int n_kfs, int lowest) {
+  if (n > 0 && !idx) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  for (int i = 0; i < n; ++i)
+    if (idx[i] < lowest || idx[i] >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: %s[%d] = %d is outside [0, %d)", who, name, i, idx[i], n_kfs);
+  return ORBX_OK;
+}
+
+// A local-map tracking call, checked and sized on the host: per frame its segments and the bound of its list — the reference
+// keyframe's features plus the n_best largest of the others' (every keyframe's where ref is -1), at most the capacity.
+struct LocalPlan {
+  CovPlan C;
+  std::vector<int> seg_off, bound_off;
+  int max_cand = 0;
+};
+
+int local_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int B, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf, int n_best,
+               LocalPlan& P) {
+  if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
+  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P.C)) return rc;
+  if (int rc = cov_check_queries(h, who, "ref_kf", B, ref_kf, n_kfs, -1)) return rc;
+  const size_t K = (size_t)n_kfs;
+  std::vector<int> order(K), place(K);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P.C.kfs[(size_t)a].n > P.C.kfs[(size_t)b].n; });
+  std::vector<long long> top(K + 1, 0);                                    // top[i]: the i largest feature counts summed
+  for (size_t i = 0; i < K; ++i) { place[(size_t)order[i]] = (int)i; top[i + 1] = top[i] + P.C.kfs[(size_t)order[i]].n; }
+  P.seg_off.assign((size_t)B + 1, 0); P.bound_off.assign((size_t)B + 1, 0);
+  long long total = 0, n_seg = 0;
+  for (int b = 0; b < B; ++b) {
+    const int r = ref_kf[b];
+    long long c = top[K];
+    if (r >= 0) {                                                           // the reference and the n_best largest of the others
+      const size_t nb = (size_t)std::min<long long>(n_best, (long long)K - 1);
+      c = (size_t)place[(size_t)r] < nb ? top[nb + 1] : top[nb] + P.C.kfs[(size_t)r].n;
+    }
+    if (c >= MS_EMPTY) return orbx_fail(h, ORBX_ERR_INVALID, "%s: frame %d has too many candidates", who, b);
+    n_seg += r >= 0 ? 1 + (long long)n_best : (long long)K;
+    total += std::min<long long>(c, mp->capacity);
+    if (n_seg > 0x7fffffff || total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the lists' bounds exceed 2^31 - 1 rows", who);
+    P.max_cand = std::max(P.max_cand, (int)c);
+    P.seg_off[(size_t)b + 1] = (int)n_seg; P.bound_off[(size_t)b + 1] = (int)total;
+  }
+  return ORBX_OK;
+}
+
+// covisibility, segments, then the three selection launches on them
+int local_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int B, const LocalPlan& P, const int* ref_kf, int n_best, int list_cap,
+                         int* d_local_kf, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
+  const int total = P.bound_off[(size_t)B];
+  if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (per frame the reference keyframe's features plus the "
+                                         "n_best largest of the others', at most the capacity)", who, list_cap, total);
+  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  CovSegs sg{P.seg_off.data(), d_local_kf, nullptr, nullptr, nullptr};
+  if (int rc = cov_enqueue(h, mp, P.C, B, ref_kf, n_best, nullptr, nullptr, nullptr, &sg)) return rc;
+  return ms_select_launch(h, mp, ORBX_MAP_SOURCE_KEYFRAMES, B, P.max_cand, sg.d_segs, sg.d_seg_off, sg.d_n_cand, nullptr, nullptr, d_list_off, d_list_slot,
+                          d_positions, d_mp_desc);
+}
+
+// ---- tracking from the store: what the keyframe / slot forms and the local-map forms share --------------------------------
+// bound_off [B+1]: the offsets of the lists' host-known bounds.  select(...) enqueues the call's selection into the list outputs.
+
+// The device form's features, poses and outputs (orbx_map_track_frames_device's, in its order).
+struct MapTrackDev {
+  const orbx_keypoint* d_kp; const uint8_t* d_desc; const int* d_feat_start; const int* d_feat_count; int feat_count_stride, max_feat;
+  const double* d_search_poses_wc; const double* d_priors_wc;
+  int* d_list_offsets; int* d_list_slot; double* d_positions; uint8_t* d_mp_desc; int* d_offsets; double* d_pts3d; float* d_pts2d; int* d_mp_idx; int* d_feat_idx;
+  double* d_poses_wc_out; uint8_t* d_inlier_out; double* d_err_out; orbx_pnp_result* d_pnp_results; int* d_matched; int* d_matched_slot; orbx_track_result* d_results;
+};
+
+template <class Select>
+int ms_track_device(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, int n_frames,
+                    const int* bound_off, const MapTrackDev& D, Select select) {
+  int max_mp = 0;
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, bound_off, &max_mp, who)) return rc;
+  const int B = n_frames, M = bound_off[B];
+  if (D.max_feat < 0 || D.feat_count_stride < 1 || !D.d_feat_start || !D.d_feat_count || !D.d_search_poses_wc || !D.d_priors_wc || !D.d_offsets ||
+      !D.d_poses_wc_out || !D.d_pnp_results || !D.d_results || (D.max_feat > 0 && (!D.d_kp || !D.d_desc || !D.d_matched || !D.d_matched_slot)) ||
+      (M > 0 && (!D.d_pts3d || !D.d_pts2d || !D.d_mp_idx || !D.d_feat_idx || !D.d_inlier_out || !D.d_err_out)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  orbx_prof_begin_call(h);
+  if (int rc = select()) return rc;
+  TrackArgs A{};
+  A.max_feat = D.max_feat; A.fc_stride = D.feat_count_stride;
+  A.kp = D.d_kp; A.desc = D.d_desc; A.feat_start = D.d_feat_start; A.feat_count = D.d_feat_count;
+  A.positions = D.d_positions; A.mp_desc = D.d_mp_desc; A.mp_off = D.d_list_offsets;
+  A.search_poses = D.d_search_poses_wc; A.priors = D.d_priors_wc;
+  A.offsets = D.d_offsets; A.pts3d = D.d_pts3d; A.pts2d = D.d_pts2d; A.mp_idx = D.d_mp_idx; A.feat_idx = D.d_feat_idx;
+  A.poses_out = D.d_poses_wc_out; A.matched = D.d_matched; A.results = D.d_results;
+  if (int rc = track_launch(h, cam, cfg, pnp_cfg, B, max_mp, (size_t)M, A, D.d_inlier_out, D.d_err_out, D.d_pnp_results)) return rc;
+  return ms_matched_slot_enqueue(h, B, D.max_feat, D.d_matched, D.d_list_offsets, D.d_list_slot, D.d_matched_slot);
+}
+
+// The host form's arrays (orbx_map_track_frames's, in its order); src_slots [S] and local_kf [n_local] are the two forms' extras.
+struct MapTrackHost {
+  const int* src_slots; size_t S;
+  const orbx_keypoint* kp; const uint8_t* desc; const int* feat_offsets; const double* search_poses_wc; const double* priors_wc;
+  int list_cap;
+  int* local_kf; size_t n_local;
+  int* list_offsets; int* list_slot; int* offsets; double* pts3d; float* pts2d; int* mp_idx; int* feat_idx; double* poses_wc_out; uint8_t* inlier_out;
+  double* err_out; orbx_pnp_result* pnp_results; int* matched; int* matched_slot; orbx_track_result* results;
+};
+
+// select(d_src_slots, d_local_kf, d_list_off, d_list_slot, d_positions, d_mp_desc)
+template <class Select>
+int ms_track_host(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, int n_frames,
+                  const int* bound_off, const MapTrackHost& H, Select select) {
+  int max_feat = 0, max_mp = 0;
+  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, bound_off, &max_mp, who)) return rc;
+  if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, H.feat_offsets, &max_feat)) return rc;
+  const int* feat_offsets = H.feat_offsets;
+  const size_t B = (size_t)n_frames, NF = (size_t)feat_offsets[B], M = (size_t)bound_off[B], mf = (size_t)max_feat, S = H.S, NL = H.n_local;
+  if (H.list_cap < 0 || (size_t)H.list_cap < M) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d", who, H.list_cap, (int)M);
+  if (!H.search_poses_wc || !H.priors_wc || !H.list_offsets || !H.offsets || !H.poses_wc_out || !H.pnp_results || !H.results || (S > 0 && !H.src_slots) ||
+      (NF > 0 && (!H.kp || !H.desc || !H.matched || !H.matched_slot)) ||
+      (M > 0 && (!H.list_slot || !H.pts3d || !H.pts2d || !H.mp_idx || !H.feat_idx || !H.inlier_out || !H.err_out)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // one blob each way: [kp | desc | search poses | priors | feat_start | feat_count | source slots] up,
+  // [list offsets | list slots | offsets | pts3d | pts2d | mp_idx | feat_idx | poses | err | pnp records | matched | matched slots |
+  //  records | inliers | local keyframes] down, and behind them the gathered positions and descriptors, which stay on the device
+  Carve in, out;
+  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_sp = in.take(56 * B), i_pr = in.take(56 * B), i_fs = in.take(4 * B),
+               i_fc = in.take(4 * B), i_ss = in.take(4 * S);
+  const size_t o_lo = out.take(4 * (B + 1)), o_ls = out.take(4 * M), o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * M), o_p2 = out.take(8 * M),
+               o_mi = out.take(4 * M), o_fi = out.take(4 * M), o_ps = out.take(56 * B), o_er = out.take(8 * M),
+               o_pn = out.take(sizeof(orbx_pnp_result) * B), o_ma = out.take(4 * B * mf), o_ms = out.take(4 * B * mf),
+               o_rs = out.take(sizeof(orbx_track_result) * B), o_in = out.take(M), o_lk = out.take(4 * NL);
+  const size_t down_bytes = out.off;
+  const size_t o_gp = out.take(24 * M), o_gd = out.take(32 * M);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
+  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+  if (NF) { std::memcpy(hi + i_kp, H.kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, H.desc, 32 * NF); }
+  std::memcpy(hi + i_sp, H.search_poses_wc, 56 * B);
+  std::memcpy(hi + i_pr, H.priors_wc, 56 * B);
+  for (size_t b = 0; b < B; ++b) {
+    ((int*)(hi + i_fs))[b] = feat_offsets[b];
+    ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
+  }
+  if (S) std::memcpy(hi + i_ss, H.src_slots, 4 * S);
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
+  orbx_prof_begin_call(h);
+  int* d_lo = (int*)(dout + o_lo); int* d_ls = (int*)(dout + o_ls);
+  if (int rc = select((const int*)(di + i_ss), H.local_kf ? (int*)(dout + o_lk) : nullptr, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd)) return rc;
+  TrackArgs A{};
+  A.max_feat = max_feat; A.fc_stride = 1;
+  A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
+  A.positions = (const double*)(dout + o_gp); A.mp_desc = dout + o_gd; A.mp_off = d_lo;
+  A.search_poses = (const double*)(di + i_sp); A.priors = (const double*)(di + i_pr);
+  A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2); A.mp_idx = (int*)(dout + o_mi);
+  A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps); A.matched = (int*)(dout + o_ma);
+  A.results = (orbx_track_result*)(dout + o_rs);
+  if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
+    return rc;
+  if (int rc = ms_matched_slot_enqueue(h, n_frames, max_feat, A.matched, d_lo, d_ls, (int*)(dout + o_ms))) return rc;
+  if (int rc = orbx_host_call_download(h, c, down_bytes)) return rc;
+  std::memcpy(H.list_offsets, ho + o_lo, 4 * (B + 1));
+  std::memcpy(H.offsets, ho + o_of, 4 * (B + 1));
+  std::memcpy(H.poses_wc_out, ho + o_ps, 56 * B);
+  std::memcpy(H.pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
+  std::memcpy(H.results, ho + o_rs, sizeof(orbx_track_result) * B);
+  if (H.local_kf && NL) std::memcpy(H.local_kf, ho + o_lk, 4 * NL);
+  const size_t L = (size_t)H.list_offsets[B], N = (size_t)H.offsets[B];
+  if (L) std::memcpy(H.list_slot, ho + o_ls, 4 * L);
+  if (N) {
+    std::memcpy(H.pts3d, ho + o_p3, 24 * N); std::memcpy(H.pts2d, ho + o_p2, 8 * N); std::memcpy(H.mp_idx, ho + o_mi, 4 * N);
+    std::memcpy(H.feat_idx, ho + o_fi, 4 * N); std::memcpy(H.err_out, ho + o_er, 8 * N); std::memcpy(H.inlier_out, ho + o_in, N);
+  }
+  for (size_t b = 0; b < B; ++b) {
+    const size_t n = (size_t)(feat_offsets[b + 1] - feat_offsets[b]);
+    if (n) { std::memcpy(H.matched + feat_offsets[b], ho + o_ma + 4 * b * mf, 4 * n); std::memcpy(H.matched_slot + feat_offsets[b], ho + o_ms + 4 * b * mf, 4 * n); }
+  }
   return ORBX_OK;
 }
 
@@ -382,6 +803,7 @@ void orbx_map_points_destroy(orbx_map_points* mp) {
   hipStreamSynchronize(mp->h->stream);
   if (mp->block) hipFree(mp->block);
   if (mp->first.p) hipFree(mp->first.p);
+  if (mp->mark.p) hipFree(mp->mark.p);
   delete mp;
 }
 
@@ -460,7 +882,16 @@ int orbx_keyframe_set_map_point_slots(orbx_keyframe* kf, const orbx_map_points* 
     if (slots[i] < -1 || slots[i] >= mp->capacity) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d (feature %d) is outside [-1, %d)", who, slots[i], i, mp->capacity);
   ORBX_HIP(h, hipSetDevice(h->device));
   if (kf->n > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_slot, slots, 4 * (size_t)kf->n, hipMemcpyHostToDevice, h->stream));
+    // beside the table, the same with every repeat of a slot set to -1 (the first feature that names it keeps it): what
+    // covisibility counts, each observed slot once
+    const size_t n = (size_t)kf->n;
+    std::vector<int> uniq(slots, slots + n), order(n);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slots[a] < slots[b]; });
+    for (size_t i = 1; i < n; ++i)
+      if (slots[order[i]] == slots[order[i - 1]]) uniq[(size_t)order[i]] = -1;
+    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_slot, slots, 4 * n, hipMemcpyHostToDevice, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_uniq, uniq.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
     ORBX_HIP(h, hipStreamSynchronize(h->stream));                       // the caller's array is free when the call returns
   }
   kf->slot_store = mp;
@@ -490,24 +921,12 @@ int orbx_map_track_frames_device(orbx_handle* h, const orbx_camera* cam, const o
   SelPlan P;
   if (n_frames > 0)
     if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
-  int max_mp = 0;
-  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, &max_mp, who)) return rc;
-  const int B = n_frames, M = P.bound_off[(size_t)B];
-  if (max_feat < 0 || feat_count_stride < 1 || !d_feat_start || !d_feat_count || !d_search_poses_wc || !d_priors_wc || !d_offsets || !d_poses_wc_out ||
-      !d_pnp_results || !d_results || (max_feat > 0 && (!d_kp || !d_desc || !d_matched || !d_matched_slot)) ||
-      (M > 0 && (!d_pts3d || !d_pts2d || !d_mp_idx || !d_feat_idx || !d_inlier_out || !d_err_out)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  orbx_prof_begin_call(h);
-  if (int rc = ms_select_enqueue(h, who, mp, source, B, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc)) return rc;
-  TrackArgs A{};
-  A.max_feat = max_feat; A.fc_stride = feat_count_stride;
-  A.kp = d_kp; A.desc = d_desc; A.feat_start = d_feat_start; A.feat_count = d_feat_count;
-  A.positions = d_positions; A.mp_desc = d_mp_desc; A.mp_off = d_list_offsets;
-  A.search_poses = d_search_poses_wc; A.priors = d_priors_wc;
-  A.offsets = d_offsets; A.pts3d = d_pts3d; A.pts2d = d_pts2d; A.mp_idx = d_mp_idx; A.feat_idx = d_feat_idx;
-  A.poses_out = d_poses_wc_out; A.matched = d_matched; A.results = d_results;
-  if (int rc = track_launch(h, cam, cfg, pnp_cfg, B, max_mp, (size_t)M, A, d_inlier_out, d_err_out, d_pnp_results)) return rc;
-  return ms_matched_slot_enqueue(h, B, max_feat, d_matched, d_list_offsets, d_list_slot, d_matched_slot);
+  const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
+                      d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
+                      d_matched, d_matched_slot, d_results};
+  return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, D, [&] {
+    return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  });
 }
 
 int orbx_map_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, orbx_map_points* mp,
@@ -521,73 +940,87 @@ int orbx_map_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_tra
   SelPlan P;
   if (n_frames > 0)
     if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
-  int max_feat = 0, max_mp = 0;
-  if (int rc = track_check(h, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, &max_mp, who)) return rc;
-  if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
-  const size_t B = (size_t)n_frames, NF = (size_t)feat_offsets[B], M = (size_t)P.bound_off[B], mf = (size_t)max_feat;
-  const size_t S = source == ORBX_MAP_SOURCE_SLOTS ? (size_t)src_offsets[B] : 0;
-  if (list_cap < 0 || (size_t)list_cap < M) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d", who, list_cap, (int)M);
-  if (!search_poses_wc || !priors_wc || !list_offsets || !offsets || !poses_wc_out || !pnp_results || !results || (S > 0 && !src_slots) ||
-      (NF > 0 && (!kp || !desc || !matched || !matched_slot)) ||
-      (M > 0 && (!list_slot || !pts3d || !pts2d || !mp_idx || !feat_idx || !inlier_out || !err_out)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  const size_t S = n_frames > 0 && source == ORBX_MAP_SOURCE_SLOTS ? (size_t)src_offsets[n_frames] : 0;
+  const MapTrackHost H{src_slots, S, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, nullptr, 0, list_offsets, list_slot, offsets, pts3d, pts2d,
+                       mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
+  return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, H,
+                       [&](const int* d_src, int*, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
+                         return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src, src_offsets, P.bound_off[(size_t)n_frames], d_lo, d_ls, d_gp, d_gd);
+                       });
+}
+
+int orbx_map_covisibility_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries, const int* query,
+                                 int n_best, int* d_weights, int* d_best, int* d_n_best) {
+  static const char* who = "orbx_map_covisibility_device";
+  if (!h) return ORBX_ERR_INVALID;
+  CovPlan P;
+  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
+  if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
+  if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
+  if (n_queries == 0 || n_kfs == 0 || (!d_weights && !d_n_best && (!d_best || n_best == 0))) return ORBX_OK;
+  return cov_enqueue(h, mp, P, n_queries, query, n_best, d_weights, n_best > 0 ? d_best : nullptr, d_n_best, nullptr);
+}
+
+int orbx_map_covisibility(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries, const int* query, int n_best,
+                          int* weights, int* best, int* n_best_out) {
+  static const char* who = "orbx_map_covisibility";
+  if (!h) return ORBX_ERR_INVALID;
+  CovPlan P;
+  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
+  if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
+  if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
+  if (n_queries == 0 || n_kfs == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  // one blob each way: [kp | desc | search poses | priors | feat_start | feat_count | source slots] up,
-  // [list offsets | list slots | offsets | pts3d | pts2d | mp_idx | feat_idx | poses | err | pnp records | matched | matched slots |
-  //  records | inliers] down, and behind them the gathered positions and descriptors, which stay on the device
-  Carve in, out;
-  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_sp = in.take(56 * B), i_pr = in.take(56 * B), i_fs = in.take(4 * B),
-               i_fc = in.take(4 * B), i_ss = in.take(4 * S);
-  const size_t o_lo = out.take(4 * (B + 1)), o_ls = out.take(4 * M), o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * M), o_p2 = out.take(8 * M),
-               o_mi = out.take(4 * M), o_fi = out.take(4 * M), o_ps = out.take(56 * B), o_er = out.take(8 * M),
-               o_pn = out.take(sizeof(orbx_pnp_result) * B), o_ma = out.take(4 * B * mf), o_ms = out.take(4 * B * mf),
-               o_rs = out.take(sizeof(orbx_track_result) * B), o_in = out.take(M);
-  const size_t down_bytes = out.off;
-  const size_t o_gp = out.take(24 * M), o_gd = out.take(32 * M);
+  const size_t Q = (size_t)n_queries, K = (size_t)n_kfs, nb = (size_t)n_best;
+  Carve out;
+  const size_t o_we = out.take(weights ? 4 * Q * K : 0), o_be = out.take(best ? 4 * Q * nb : 0), o_nb = out.take(n_best_out ? 4 * Q : 0);
+  if (out.off == 0) return ORBX_OK;
   HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
-  if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
-  std::memcpy(hi + i_sp, search_poses_wc, 56 * B);
-  std::memcpy(hi + i_pr, priors_wc, 56 * B);
-  for (size_t b = 0; b < B; ++b) {
-    ((int*)(hi + i_fs))[b] = feat_offsets[b];
-    ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
-  }
-  if (S) std::memcpy(hi + i_ss, src_slots, 4 * S);
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  orbx_prof_begin_call(h);
-  int* d_lo = (int*)(dout + o_lo); int* d_ls = (int*)(dout + o_ls);
-  if (int rc = ms_select_enqueue(h, who, mp, source, n_frames, P, (const int*)(di + i_ss), src_offsets, (int)M, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd))
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  if (int rc = cov_enqueue(h, mp, P, n_queries, query, n_best, weights ? (int*)(c.dout + o_we) : nullptr, best && nb ? (int*)(c.dout + o_be) : nullptr,
+                           n_best_out ? (int*)(c.dout + o_nb) : nullptr, nullptr))
     return rc;
-  TrackArgs A{};
-  A.max_feat = max_feat; A.fc_stride = 1;
-  A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
-  A.positions = (const double*)(dout + o_gp); A.mp_desc = dout + o_gd; A.mp_off = d_lo;
-  A.search_poses = (const double*)(di + i_sp); A.priors = (const double*)(di + i_pr);
-  A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2); A.mp_idx = (int*)(dout + o_mi);
-  A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps); A.matched = (int*)(dout + o_ma);
-  A.results = (orbx_track_result*)(dout + o_rs);
-  if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
-    return rc;
-  if (int rc = ms_matched_slot_enqueue(h, n_frames, max_feat, A.matched, d_lo, d_ls, (int*)(dout + o_ms))) return rc;
-  if (int rc = orbx_host_call_download(h, c, down_bytes)) return rc;
-  std::memcpy(list_offsets, ho + o_lo, 4 * (B + 1));
-  std::memcpy(offsets, ho + o_of, 4 * (B + 1));
-  std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
-  std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
-  std::memcpy(results, ho + o_rs, sizeof(orbx_track_result) * B);
-  const size_t L = (size_t)list_offsets[B], N = (size_t)offsets[B];
-  if (L) std::memcpy(list_slot, ho + o_ls, 4 * L);
-  if (N) {
-    std::memcpy(pts3d, ho + o_p3, 24 * N); std::memcpy(pts2d, ho + o_p2, 8 * N); std::memcpy(mp_idx, ho + o_mi, 4 * N);
-    std::memcpy(feat_idx, ho + o_fi, 4 * N); std::memcpy(err_out, ho + o_er, 8 * N); std::memcpy(inlier_out, ho + o_in, N);
-  }
-  for (size_t b = 0; b < B; ++b) {
-    const size_t n = (size_t)(feat_offsets[b + 1] - feat_offsets[b]);
-    if (n) { std::memcpy(matched + feat_offsets[b], ho + o_ma + 4 * b * mf, 4 * n); std::memcpy(matched_slot + feat_offsets[b], ho + o_ms + 4 * b * mf, 4 * n); }
-  }
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+  if (weights) std::memcpy(weights, c.ho + o_we, 4 * Q * K);
+  if (best && nb) std::memcpy(best, c.ho + o_be, 4 * Q * nb);
+  if (n_best_out) std::memcpy(n_best_out, c.ho + o_nb, 4 * Q);
   return ORBX_OK;
+}
+
+int orbx_map_track_local_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, orbx_map_points* mp,
+                                int n_frames, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf, int n_best, const orbx_keypoint* d_kp,
+                                const uint8_t* d_desc, const int* d_feat_start, const int* d_feat_count, int feat_count_stride, int max_feat,
+                                const double* d_search_poses_wc, const double* d_priors_wc, int list_cap, int* d_local_kf, int* d_list_offsets,
+                                int* d_list_slot, double* d_positions, uint8_t* d_mp_desc, int* d_offsets, double* d_pts3d, float* d_pts2d, int* d_mp_idx,
+                                int* d_feat_idx, double* d_poses_wc_out, uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_pnp_results,
+                                int* d_matched, int* d_matched_slot, orbx_track_result* d_results) {
+  static const char* who = "orbx_map_track_local_device";
+  if (!h) return ORBX_ERR_INVALID;
+  LocalPlan P;
+  if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
+  const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
+                      d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
+                      d_matched, d_matched_slot, d_results};
+  return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), D, [&] {
+    return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, list_cap, d_local_kf, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  });
+}
+
+int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, orbx_map_points* mp,
+                         int n_frames, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf, int n_best, const orbx_keypoint* kp,
+                         const uint8_t* desc, const int* feat_offsets, const double* search_poses_wc, const double* priors_wc, int list_cap, int* local_kf,
+                         int* list_offsets, int* list_slot, int* offsets, double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out,
+                         uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results) {
+  static const char* who = "orbx_map_track_local";
+  if (!h) return ORBX_ERR_INVALID;
+  LocalPlan P;
+  if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
+  const MapTrackHost H{nullptr, 0, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, local_kf, (size_t)n_frames * (1 + (size_t)n_best), list_offsets,
+                       list_slot, offsets, pts3d, pts2d, mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
+  return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), H,
+                       [&](const int*, int* d_lk, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
+                         return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, P.bound_off[(size_t)n_frames], d_lk, d_lo, d_ls, d_gp, d_gd);
+                       });
 }
 
 int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,

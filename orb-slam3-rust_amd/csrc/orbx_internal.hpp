@@ -242,7 +242,7 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
-  DevBuf ws_map[4];                      // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table
+  DevBuf ws_map[6];                      // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries
   PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
   UploadRing ring_map;                   // the tables on their way to ws_map[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
@@ -276,13 +276,14 @@ struct orbx_keyframe {
   uint64_t id = 0, timestamp_ns = 0;
   double pose_wc[7] = {1, 0, 0, 0, 0, 0, 0};
   int n = 0;
-  uint8_t* block = nullptr;          // one device allocation: kp | desc | points_cam | has_point | mp_flag | mp_slot
+  uint8_t* block = nullptr;          // one device allocation: kp | desc | points_cam | has_point | mp_flag | mp_slot | mp_uniq
   orbx_keypoint* d_kp = nullptr;
   uint8_t* d_desc = nullptr;
   double* d_points = nullptr;
   uint8_t* d_has_point = nullptr;
   uint8_t* d_mp_flag = nullptr;
   int* d_mp_slot = nullptr;          // per feature the slot of its map point in slot_store, -1 = None (orbx_keyframe_set_map_point_slots)
+  int* d_mp_uniq = nullptr;          // d_mp_slot with every repeat of a slot inside the keyframe set to -1: the keyframe's observed set, each slot once (covisibility)
   const orbx_map_points* slot_store = nullptr;   // the store the table was set against; NULL: no table (every feature -1)
   std::vector<int64_t> mp_ids;       // matched_map_points (host side: ids are map bookkeeping), -1 = None
   // FeatureVector as one node id per feature (orbx_keyframe_set_feature_nodes): host copy, and the feature indices sorted by
