@@ -503,6 +503,19 @@ int orbx_ba_solve_visual_obs32(orbx_handle* h, const orbx_camera* cam, const orb
                                orbx_should_stop_fn should_stop, void* user, double* poses_wc_out,
                                int* iterations, double* initial_error, double* final_error);
 
+/* orbx_ba_solve_visual_obs32 with the observations in DEVICE memory of the handle's device (16-byte aligned), written by work already
+ * ordered on the handle's stream — orbx_map_collect_ba_window_device's d_obs32, or the caller's own kernels after orbx_synchronize.
+ * They are copied device to device into the solver's blob, where the index checks, the grouping and the per-keyframe lists are made
+ * as for host observations: the same kernels see the same bytes, so every output equals orbx_ba_solve_visual_obs32's on a host copy
+ * bit for bit, and nothing crosses the host link but poses and points.  Poses, points and the scalars stay host arrays.  Not with an
+ * all-reduce hook / communicator installed (the partitioned solve's host passes read the observations): ORBX_ERR_INVALID.  An
+ * observation index out of range is ORBX_ERR_INVALID as ever; the message names the observation, not its contents. */
+int orbx_ba_solve_visual_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
+                                      const double* poses_cw, int F, const double* fixed_poses_cw, int M,
+                                      double* points, int N, const orbx_ba_obs32* d_obs32,
+                                      orbx_should_stop_fn should_stop, void* user, double* poses_wc_out,
+                                      int* iterations, double* initial_error, double* final_error);
+
 /* Many independent windows in ONE call ("many BA windows": one map per stream / per robot).  Each
  * window is exactly one orbx_ba_solve_visual problem (same arguments, same LM loop, local_ba_lm.rs:1012-1056) with its own
  * LM state on the device; all windows share every kernel launch — the window is the second grid dimension — so W reduced
@@ -1147,6 +1160,60 @@ int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_trac
                          const double* priors_wc, int list_cap, int* local_kf, int* list_offsets, int* list_slot, int* offsets,
                          double* pts3d, float* pts2d, int* mp_idx, int* feat_idx, double* poses_wc_out, uint8_t* inlier_out,
                          double* err_out, orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results);
+
+/* ---- local BA from the resident map: the window collected on the device (local_ba_lm.rs:665-726, :800-897; local_mapper.rs:377-410) ----
+ * collect_visual_ba_data walked a host map with hash sets and built one observation per feature for the solver to upload.  Here the
+ * window is made where the slot tables, the keypoints and the store lie.  kfs [n_kfs] are the keyframes the caller considers (host
+ * array, copied before the call returns; is_bad filtering = leaving a keyframe out); every index below is a position in kfs[].
+ *   [spec] local = [cur] ++ best(cur, max_covisible), best as orbx_map_covisibility defines it (collect_local_keyframes, :665-683,
+ *     with the covisibility list in the library's fixed order).  local[0] is the anchor and is fixed (:821); local[1..] are the K
+ *     optimised keyframes, in that order.
+ *   [spec] P = the distinct live slots of local's tables in first-seen order, keyframes in local order and features in index order:
+ *     what ORBX_MAP_SOURCE_KEYFRAMES gives for one frame (:686-704).  M = |P|; a point's mp_idx is its position in P.
+ *   [spec] c(k), for every keyframe of kfs[] = the number of features i whose table entry s satisfies 0 <= s < capacity, live[s] and
+ *     s in P.  Every feature counts, repeats of a slot inside one keyframe included (:863-882 pushes one observation per feature); a
+ *     keyframe without a table has c = 0.
+ *   [spec] fixed = the keyframes k not in local with c(k) > 0, by ascending position in kfs[].  (The reference finds them through
+ *     mp.observations in HashMap order, :707-726; here they are derived from the tables, in a fixed order.  Where every observation
+ *     is associated in both directions the set is the reference's.)  F = 1 + their number: fixed index 0 is the anchor, fixed index
+ *     1 + j is fixed[j].
+ *   [spec] observations: the observers in the order local[0], local[1..], fixed[0..] (:889-890), each observer's counted features in
+ *     index order, one orbx_ba_obs32 per counted feature: kf_idx = i - 1 for local[i], i >= 1; -1 for the anchor; -2 - j for fixed[j]
+ *     (orbx_ba_obs32's coding of fixed observers); mp_idx as above; u, v = the keypoint's x, y as the f32 they are.  N = their number.
+ *   [spec] M = 0 (equivalently N = 0) is ORBX_ERR_EMPTY: the reference's None (:813-815, :884-886).  K = 0 (no covisibles) is a valid
+ *     collection; what the solver answers for it is the solver's.
+ *
+ * orbx_map_collect_ba_window_device: outputs, device memory: d_counts [4] int32 = K, F, M, N; d_local_kf [1 + max_covisible] int32,
+ * -1 padded; d_fixed_kf [n_kfs] int32, entries [0, F - 1) then -1; d_list_slot [list_cap] and d_positions [list_cap][3]: P's slots and
+ * positions, rows [0, M); d_obs32 [obs_cap] (16-byte aligned), rows [0, N).  list_cap must reach the bound orbx_map_track_local_device
+ * states for one frame with reference cur and n_best = max_covisible; obs_cap the sum of the feature counts of kfs[].  Nothing is
+ * ever truncated.  Asynchronous on the handle's stream, no host synchronisation inside; the store's tables are left as they were
+ * found, and no launch is sized by the capacity: a call costs what its keyframes cost, not what the map holds.  Every output is the
+ * same bytes on every run.  ORBX_ERR_INVALID before anything is enqueued: cur outside [0, n_kfs) (so n_kfs = 0: there is no cur),
+ * max_covisible < 0, n_kfs > 65535, a cap below its bound, a keyframe of another handle or whose table is bound to another store.
+ * orbx_map_collect_ba_window: the same with host outputs, synchronous; ORBX_ERR_EMPTY where the specification says so (counts,
+ * local_kf and fixed_kf are then written, the rows are not).  With T_cw = the inverses of the keyframes' poses (optimised:
+ * local[1..]; fixed: local[0], then fixed[]) its outputs are orbx_ba_solve_visual_obs32's arguments.
+ *
+ * orbx_map_local_ba = phases 1-3 of local_bundle_adjustment's visual branch (local_mapper.rs:377-410) on the resident map: the
+ * collection with max_covisible = cfg->max_covisible_keyframes; ONE download of counts, local and fixed keyframes, P's slots and
+ * positions, the only synchronisation before the solve; T_cw from the keyframes' own pose_wc; orbx_ba_solve_visual_obs32_device on
+ * the observations where they lie; then, if the solve iterated (:396), the M optimised positions written to P's slots through
+ * orbx_map_points_set's scatter, positions only (the point half of apply_visual_ba_results, :1125-1135).  Outputs, host memory:
+ * local_kf_out [1 + max_covisible] (-1 padded), poses_wc_out [max_covisible][7]: the optimised T_wc of local[1..], rows [0, K)
+ * (the keyframes are const here: the caller applies them with orbx_keyframe_set_pose, as it applies ids), counts_out [4] = K, F, M,
+ * N, and the solver's scalars.  ORBX_ERR_EMPTY where the collection or the solver says so, the store untouched.  Not with an
+ * all-reduce hook / communicator installed.
+ * Still the caller's: ids, orbx_keyframe_set_pose, the spanning tree, and the inertial branch (temporal chain, preintegrations). */
+int orbx_map_collect_ba_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur,
+                                      int max_covisible, int list_cap, int obs_cap, int* d_counts, int* d_local_kf, int* d_fixed_kf,
+                                      int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32);
+int orbx_map_collect_ba_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur,
+                               int max_covisible, int list_cap, int obs_cap, int* counts, int* local_kf, int* fixed_kf, int* list_slot,
+                               double* positions, orbx_ba_obs32* obs32);
+int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs,
+                      const orbx_keyframe* const* kfs, int cur, orbx_should_stop_fn should_stop, void* user, int* local_kf_out,
+                      double* poses_wc_out, int* counts_out, int* iterations, double* initial_error, double* final_error);
 
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and

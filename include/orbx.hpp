@@ -978,6 +978,144 @@ inline MapTrackResult track_with_motion_model(Handle& h, const CameraModel& came
   return map_track_frames(h, camera, store, {MapTrackFrame{&features, {}, slots, predicted_pose, predicted_pose}}, ORBX_MAP_SOURCE_SLOTS, 0)[0];
 }
 
+// ---- local BA from the resident map (orbx.h, "local BA from the resident map"): the window collected on the device ----
+// Every keyframe index is a position in the `keyframes` the caller hands over (is_bad ones left out).
+struct BAWindow {
+  int K = 0, F = 0, M = 0, N = 0;
+  std::vector<int> local_kf;                           // [1 + max_covisible], -1 padded: the anchor, then the K optimised keyframes
+  std::vector<int> fixed_kf;                           // [F - 1]: the other observers, ascending
+  std::vector<int> list_slot;                          // [M]: the window's points as slots; mp_idx is a position here
+  std::vector<std::array<double, 3>> positions;        // [M]
+  std::vector<orbx_ba_obs32> obs32;                    // [N]
+};
+
+// The host-known bounds of a collection call: rows of the point list (the bound of track_local_map's list for the reference
+// `cur` with max_covisible neighbours) and of the observations (every feature of `keyframes`).
+inline void ba_window_bounds(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, int cur, int max_covisible, int* list_cap,
+                             int* obs_cap) {
+  std::vector<int> kf_n;
+  size_t all = 0;
+  for (const orbx_keyframe* k : keyframes) {
+    int n = 0;
+    h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+    kf_n.push_back(n); all += (size_t)n;
+  }
+  size_t cand = all;
+  if (cur >= 0 && cur < (int)kf_n.size()) {
+    std::vector<int> others(kf_n);
+    others.erase(others.begin() + cur);
+    std::sort(others.begin(), others.end(), std::greater<int>());
+    cand = (size_t)kf_n[(size_t)cur];
+    for (size_t i = 0; i < others.size() && (int)i < max_covisible; ++i) cand += (size_t)others[i];
+  }
+  *list_cap = (int)std::min(cand, (size_t)store.capacity());
+  *obs_cap = (int)all;
+}
+
+// orbx_map_collect_ba_window_device: every output is the caller's device memory (d_counts [4], d_local_kf [1 + max_covisible],
+// d_fixed_kf [keyframes.size()], d_list_slot / d_positions [list_cap], d_obs32 [obs_cap], 16-byte aligned); asynchronous.
+inline void map_collect_ba_window_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, int cur, int max_covisible,
+                                         int list_cap, int obs_cap, int* d_counts, int* d_local_kf, int* d_fixed_kf, int* d_list_slot, double* d_positions,
+                                         orbx_ba_obs32* d_obs32) {
+  h.check(orbx_map_collect_ba_window_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), cur, max_covisible, list_cap, obs_cap, d_counts,
+                                            d_local_kf, d_fixed_kf, d_list_slot, d_positions, d_obs32));
+}
+
+// orbx_map_collect_ba_window: the same into host vectors, synchronous; nullopt where the reference returns None (:813-815, :884-886).
+inline std::optional<BAWindow> map_collect_ba_window(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, int cur,
+                                                     int max_covisible) {
+  int list_cap = 0, obs_cap = 0;
+  ba_window_bounds(h, store, keyframes, cur, max_covisible, &list_cap, &obs_cap);
+  BAWindow w;
+  int counts[4] = {0, 0, 0, 0};
+  w.local_kf.assign(1 + (size_t)std::max(max_covisible, 0), -1); w.fixed_kf.assign(std::max<size_t>(keyframes.size(), 1), -1);
+  w.list_slot.resize(std::max(list_cap, 1)); w.positions.resize(std::max(list_cap, 1)); w.obs32.resize(std::max(obs_cap, 1));
+  const int rc = orbx_map_collect_ba_window(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), cur, max_covisible, list_cap, obs_cap, counts,
+                                            w.local_kf.data(), w.fixed_kf.data(), w.list_slot.data(), w.positions[0].data(), w.obs32.data());
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  w.K = counts[0]; w.F = counts[1]; w.M = counts[2]; w.N = counts[3];
+  w.fixed_kf.resize((size_t)w.F - 1); w.list_slot.resize((size_t)w.M); w.positions.resize((size_t)w.M); w.obs32.resize((size_t)w.N);
+  return w;
+}
+
+struct BAWindowSolve {
+  std::vector<SE3> poses_wc;                           // [K]: the optimised keyframes, T_wc
+  size_t iterations = 0;
+  double initial_error = 0, final_error = 0;
+};
+
+// orbx_ba_solve_visual_obs32_device: solve_visual_ba on flat arrays with the observations in device memory (d_obs32 [n_obs],
+// 16-byte aligned, ordered on the handle's stream).  poses_cw [K] / fixed_cw [F] are T_cw; points [M] in/out.
+inline std::optional<BAWindowSolve> solve_visual_ba_obs32_device(Handle& h, const CameraModel& camera, const LocalBAConfigLM& config, const std::vector<SE3>& poses_cw,
+                                                                 const std::vector<SE3>& fixed_cw, std::vector<std::array<double, 3>>& points,
+                                                                 const orbx_ba_obs32* d_obs32, int n_obs, const std::function<bool()>& should_stop) {
+  std::vector<double> poses, fixed;
+  auto push7 = [](std::vector<double>& v, const SE3& p) {
+    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
+    v.insert(v.end(), p.translation.begin(), p.translation.end());
+  };
+  for (const SE3& p : poses_cw) push7(poses, p);
+  for (const SE3& p : fixed_cw) push7(fixed, p);
+  const int K = (int)poses_cw.size();
+  std::vector<double> out((size_t)std::max(K, 1) * 7);
+  int it = 0;
+  double e0 = 0, e1 = 0;
+  const orbx_camera c = camera.c();
+  const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, config.max_covisible_keyframes};
+  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
+  void* user = const_cast<std::function<bool()>*>(&should_stop);
+  const int rc = orbx_ba_solve_visual_obs32_device(h.get(), &c, &cfg, K, poses.data(), (int)fixed_cw.size(), fixed.data(), (int)points.size(),
+                                                   points.empty() ? nullptr : points[0].data(), n_obs, d_obs32, should_stop ? +tramp : nullptr, user, out.data(), &it,
+                                                   &e0, &e1);
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  BAWindowSolve r;
+  for (int i = 0; i < K; ++i) {
+    SE3 p;
+    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
+    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    r.poses_wc.push_back(p);
+  }
+  r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
+  return r;
+}
+
+struct MapLocalBAResult : BAWindowSolve {              // poses_wc[i] belongs to keyframes[local_kf[1 + i]]
+  int K = 0, F = 0, M = 0, N = 0;
+  std::vector<int> local_kf;                           // [1 + max_covisible_keyframes], -1 padded
+};
+
+// orbx_map_local_ba: local_bundle_adjustment's visual branch (local_mapper.rs:377-410) on the resident map — collected on the
+// device, solved where the observations lie, the optimised positions written back into the store.  The caller applies the poses
+// (orbx_keyframe_set_pose), as it applies ids.  nullopt where the reference returns None.
+inline std::optional<MapLocalBAResult> map_local_ba(Handle& h, const CameraModel& camera, const LocalBAConfigLM& config, MapPointStore& store,
+                                                    const std::vector<const orbx_keyframe*>& keyframes, int cur, const std::function<bool()>& should_stop) {
+  const int mc = config.max_covisible_keyframes;
+  MapLocalBAResult r;
+  r.local_kf.assign(1 + (size_t)std::max(mc, 0), -1);
+  std::vector<double> out((size_t)std::max(mc, 1) * 7);
+  int counts[4] = {0, 0, 0, 0}, it = 0;
+  double e0 = 0, e1 = 0;
+  const orbx_camera c = camera.c();
+  const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, mc};
+  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
+  void* user = const_cast<std::function<bool()>*>(&should_stop);
+  const int rc = orbx_map_local_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), cur, should_stop ? +tramp : nullptr, user,
+                                   r.local_kf.data(), out.data(), counts, &it, &e0, &e1);
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  r.K = counts[0]; r.F = counts[1]; r.M = counts[2]; r.N = counts[3];
+  for (int i = 0; i < r.K; ++i) {
+    SE3 p;
+    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
+    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    r.poses_wc.push_back(p);
+  }
+  r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
+  return r;
+}
+
 // ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
 // One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
 // validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).

@@ -101,6 +101,7 @@ ABI_SYMBOLS = [
     "orbx_map_points_erase", "orbx_map_points_download", "orbx_keyframe_set_map_point_slots", "orbx_map_select_points_device",
     "orbx_map_track_frames_device", "orbx_map_track_frames", "orbx_map_track_reference_device",
     "orbx_map_covisibility_device", "orbx_map_covisibility", "orbx_map_track_local_device", "orbx_map_track_local",
+    "orbx_map_collect_ba_window_device", "orbx_map_collect_ba_window", "orbx_ba_solve_visual_obs32_device", "orbx_map_local_ba",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 
@@ -1293,6 +1294,99 @@ class Handle:
             out.append((t, ls[lo[b]:lo[b + 1]].copy(), mslot[fo[b]:fo[b + 1]].copy(), lk[b].copy()))
         return out
 
+    # ---- local BA from the resident map (include/orbx.h, "local BA from the resident map") ----
+    def _ba_window_bounds(self, mp, keyframes, cur, max_covisible):
+        """(list bound, observation bound) of a collection call: map_track_local_device's bound for one frame with reference
+        `cur`, and every feature of `keyframes`"""
+        return self._local_bounds(mp, keyframes, [int(cur)], int(max_covisible))[0], int(sum(k.n for k in keyframes))
+
+    def map_collect_ba_window_device(self, mp: "MapPointStore", keyframes, cur, max_covisible, device=None):
+        """The local-BA window of keyframes[cur], collected on the device from the slot tables, the keypoints and the store
+        (orbx_map_collect_ba_window_device).  Returns a dict of CUDA tensors: counts [4] int32 = (K, F, M, N), local_kf
+        [1+max_covisible] int32 (-1 padded; [0] is the anchor, [1:1+K] the optimised keyframes), fixed_kf [n_kfs] int32 (the F-1
+        other observers, ascending, then -1), list_slot [cap] int32 and positions [cap,3] f64 (the window's points, rows [0, M)),
+        obs32 [obs_cap,16] u8 (rows [0, N) are BA_OBS32 records).  Every index is a position in `keyframes`.  Asynchronous on the
+        handle's stream."""
+        import torch
+        cap, ocap = self._ba_window_bounds(mp, keyframes, cur, max_covisible)
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(counts=mk(4, torch.int32), local_kf=mk(1 + max(int(max_covisible), 0), torch.int32), fixed_kf=mk(max(len(keyframes), 1), torch.int32),
+                 list_slot=mk(max(cap, 1), torch.int32), positions=mk((max(cap, 1), 3), torch.float64), obs32=mk((max(ocap, 1), BA_OBS32.itemsize), torch.uint8))
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_collect_ba_window_device(
+            self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(int(cur)), C.c_int(int(max_covisible)), C.c_int(cap), C.c_int(ocap),
+            _vp(o["counts"]), _vp(o["local_kf"]), _vp(o["fixed_kf"]), _vp(o["list_slot"]), _vp(o["positions"]), _vp(o["obs32"])))
+        o["fixed_kf"] = o["fixed_kf"][:len(keyframes)]; o["list_slot"] = o["list_slot"][:cap]; o["positions"] = o["positions"][:cap]; o["obs32"] = o["obs32"][:ocap]
+        return o
+
+    def map_collect_ba_window(self, mp: "MapPointStore", keyframes, cur, max_covisible):
+        """The host form (orbx_map_collect_ba_window), synchronous: a dict of numpy arrays cut to their sizes — counts [4],
+        local_kf [1+max_covisible], fixed_kf [F-1], list_slot [M], positions [M,3], obs32 [N] BA_OBS32 — or None where the window
+        is empty (the reference's None, local_ba_lm.rs:813-815, :884-886)."""
+        cap, ocap = self._ba_window_bounds(mp, keyframes, cur, max_covisible)
+        counts = np.zeros(4, np.int32); lk = np.full(1 + max(int(max_covisible), 0), -1, np.int32); fx = np.full(max(len(keyframes), 1), -1, np.int32)
+        ls = np.zeros(max(cap, 1), np.int32); pos = np.zeros((max(cap, 1), 3)); obs = np.zeros(max(ocap, 1), BA_OBS32)
+        rc = self._L.orbx_map_collect_ba_window(
+            self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(int(cur)), C.c_int(int(max_covisible)), C.c_int(cap), C.c_int(ocap),
+            _vp(counts), _vp(lk), _vp(fx), _vp(ls), _vp(pos), _vp(obs))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        K, F, M, N = (int(x) for x in counts)
+        return dict(counts=counts, local_kf=lk, fixed_kf=fx[:F - 1].copy(), list_slot=ls[:M].copy(), positions=pos[:M].copy(), obs32=obs[:N].copy())
+
+    def ba_solve_visual_obs32_device(self, camera, cfg, poses_cw, fixed_cw, points, obs32, n_obs, should_stop=None):
+        """ba_solve_visual with the observations in device memory (orbx_ba_solve_visual_obs32_device): obs32 is a CUDA tensor whose
+        first 16 * n_obs bytes are BA_OBS32 records (map_collect_ba_window_device's), 16-byte aligned.  Poses and points are host
+        arrays; the result is ba_solve_visual's dict, bit for bit what it gives for a host copy of the observations."""
+        poses_cw = np.ascontiguousarray(poses_cw, np.float64).reshape(-1, 7)
+        fixed_cw = np.ascontiguousarray(fixed_cw, np.float64).reshape(-1, 7)
+        pts = np.array(points, np.float64, copy=True).reshape(-1, 3)
+        K, F, M, N = len(poses_cw), len(fixed_cw), len(pts), int(n_obs)
+        if N < 0 or N * BA_OBS32.itemsize > obs32.numel() * obs32.element_size():
+            raise ValueError("obs32 holds fewer than n_obs records")
+        out_wc = np.zeros((max(K, 1), 7))
+        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
+        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cam = camera._c(); c = cfg._c()
+        self._after_torch(obs32)
+        rc = self._L.orbx_ba_solve_visual_obs32_device(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_cw), C.c_int(F), _vp(fixed_cw), C.c_int(M), _vp(pts),
+                                                       C.c_int(N), _vp(obs32), cb, None, _vp(out_wc), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        return dict(poses_wc=out_wc[:K], points=pts, iterations=it.value, initial_error=e0.value, final_error=e1.value)
+
+    def map_local_ba(self, camera, mp: "MapPointStore", keyframes, cur, cfg: "LocalBAConfigLM" = None, should_stop=None,
+                     read_points=True) -> Optional["MapLocalBAResult"]:
+        """Local BA of keyframes[cur]'s window on the resident map (orbx_map_local_ba): the window is collected on the device, solved
+        with its observations where they lie, and the optimised positions are written back into the store.  Returns a
+        MapLocalBAResult — optimized_poses keyed by position in `keyframes` (apply them with KeyFrame.set_pose),
+        optimized_points keyed by slot, read back from the store (read_points=False leaves them out: a caller that keeps its map on
+        the device has no use for them) — or None where the reference returns None."""
+        import torch
+        cfg = cfg or LocalBAConfigLM()
+        mc = int(cfg.max_covisible_keyframes)
+        lk = np.full(1 + max(mc, 0), -1, np.int32); poses = np.zeros((max(mc, 1), 7)); counts = np.zeros(4, np.int32)
+        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
+        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cam = camera._c(); c = cfg._c()
+        rc = self._L.orbx_map_local_ba(self._h, C.byref(cam), C.byref(c), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(int(cur)), cb, None,
+                                       _vp(lk), _vp(poses), _vp(counts), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        K, F, M, N = (int(x) for x in counts)
+        opt_poses = {int(lk[1 + i]): poses[i].copy() for i in range(K)}
+        if not read_points:
+            return MapLocalBAResult(opt_poses, {}, it.value, e0.value, e1.value, lk, counts, None, None)
+        # the window's points: the selection over the local keyframes, whose gathered positions are now the optimised ones
+        sel = self.map_select_points_device(mp, keyframes=[[keyframes[i] for i in lk[:1 + K]]])
+        torch.cuda.synchronize()
+        slots = sel["list_slot"][:M].cpu().numpy(); pts = sel["positions"][:M].cpu().numpy()
+        return MapLocalBAResult(opt_poses, {int(s): pts[j] for j, s in enumerate(slots)}, it.value, e0.value, e1.value, lk, counts, slots, pts)
+
     def compute_sim3_ransac_batch(self, problems, cfg: "Sim3SolverConfig" = None):
         """compute_sim3_ransac (sim3_solver.rs:63-145) for many point sets [(points1 [n,3], points2 [n,3]), ...] in one call (one
         upload, one download).  Returns (sim3 [P,8], inlier masks (list of [n] u8), results [P] SIM3_RESULT); each problem's bytes
@@ -2078,6 +2172,17 @@ class VisualBAResultData:
     iterations: int = 0
     initial_error: float = 0.0
     final_error: float = 0.0
+
+
+@dataclass
+class MapLocalBAResult(VisualBAResultData):
+    """Handle.map_local_ba's result: VisualBAResultData with optimized_poses keyed by position in the call's keyframe list and
+    optimized_points keyed by slot, plus the window itself: local_kf [1+max_covisible] (-1 padded), counts (K, F, M, N), and the
+    points as arrays in the window's order (list_slot [M], points [M,3])."""
+    local_kf: np.ndarray = None
+    counts: np.ndarray = None
+    list_slot: np.ndarray = None
+    points: np.ndarray = None
 
 
 def flatten_ba_problem(problem: VisualBAProblemData):

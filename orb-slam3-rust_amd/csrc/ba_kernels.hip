@@ -3427,7 +3427,7 @@ static_assert(sizeof(orbx_ba_obs) == 32 && offsetof(orbx_ba_obs, mp_idx) == 8 &&
 static_assert(sizeof(orbx_ba_obs32) == 16 && offsetof(orbx_ba_obs32, mp_idx) == 4 && offsetof(orbx_ba_obs32, u) == 8, "... or one int2 and one float2");
 
 // windows whose observations follow each other in the caller's memory: one copy
-struct Run { int w0, w1; size_t off, bytes; const void* src; bool direct; };
+struct Run { int w0, w1; size_t off, bytes; const void* src; bool direct; bool on_device = false; };   // on_device: a direct run whose source is device memory
 
 // grids and kernel choices of the LM loop's launches: functions of the windows' sizes, the batch and the device (ba_launch_shape)
 struct BaShape {
@@ -3624,12 +3624,13 @@ void ba_plan_uploads(BaCtx& c) {
     if (c.plan[(size_t)w].skip || ww.N == 0) continue;
     const void* src = ww.obs32 ? (const void*)ww.obs32 : (const void*)ww.obs;
     const size_t bytes = (ww.obs32 ? sizeof(orbx_ba_obs32) : sizeof(orbx_ba_obs)) * (size_t)ww.N;
-    if (!runs.empty() && (const char*)runs.back().src + runs.back().bytes == (const char*)src && runs.back().off + runs.back().bytes == c.plan[(size_t)w].i_obs) {
+    if (!runs.empty() && runs.back().on_device == ww.obs_on_device && (const char*)runs.back().src + runs.back().bytes == (const char*)src &&
+        runs.back().off + runs.back().bytes == c.plan[(size_t)w].i_obs) {
       runs.back().bytes += bytes; runs.back().w1 = w + 1;
-    } else runs.push_back(Run{w, w + 1, c.plan[(size_t)w].i_obs, bytes, src, false});
+    } else runs.push_back(Run{w, w + 1, c.plan[(size_t)w].i_obs, bytes, src, false, ww.obs_on_device});
   }
   for (Run& r : runs) {
-    r.direct = host_is_pinned(r.src, r.bytes);
+    r.direct = r.on_device || host_is_pinned(r.src, r.bytes);            // device memory: the copy is device to device, ordered on the stream behind whatever wrote it
     if (!r.direct) c.any_stage = true;
   }
 }
@@ -3671,7 +3672,7 @@ int ba_send_direct(BaCtx& c) {
   }
   c.direct_sent = true;                                                  // (set first: a failure part-way has already enqueued the earlier runs)
   for (const Run& r : c.runs)
-    if (r.direct) ORBX_HIP(h, hipMemcpyAsync(c.dobs + r.off, r.src, r.bytes, hipMemcpyHostToDevice, c.st));
+    if (r.direct) ORBX_HIP(h, hipMemcpyAsync(c.dobs + r.off, r.src, r.bytes, r.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.st));
   return ORBX_OK;
 }
 // ---- upload, host part, one window per task: LM state, pose parameters, points, fixed poses — and the observations of a window whose
@@ -4089,6 +4090,8 @@ int ba_report_bad_index(BaCtx& c) {
     if (code == 0) continue;
     const BaWinHost& ww = c.win[w];
     const int i = 0x7fffffff - code;
+    if (ww.obs_on_device)                                                  // (the observation is not the host's to read)
+      return orbx_fail(c.h, ORBX_ERR_INVALID, "window %d observation %d (device memory): index out of range (K %d, F %d, M %d)", w, i, ww.K, ww.F, ww.M);
     int kf, fx, mp;
     if (ww.obs32) { const orbx_ba_obs32& o = ww.obs32[i]; kf = o.kf_idx >= 0 ? o.kf_idx : -1; fx = o.kf_idx >= 0 ? -1 : -1 - o.kf_idx; mp = o.mp_idx; }
     else { const orbx_ba_obs& o = ww.obs[i]; kf = o.kf_idx; fx = o.fixed_idx; mp = o.mp_idx; }
@@ -4174,6 +4177,11 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   if (W <= 0) return ORBX_OK;
   if ((inertial || have_coll) && W != 1)
     return orbx_fail(h, ORBX_ERR_INVALID, "the inertial mode and the all-reduce hook take one window per call");
+  // observations in device memory: the partitioned solve's hosts pass over their partition, and a batch's halves order their uploads on
+  // two streams — neither is for memory another stream may still be writing
+  for (int w = 0; w < W; ++w)
+    if (win[w].obs_on_device && (have_coll || W != 1 || inertial))
+      return orbx_fail(h, ORBX_ERR_INVALID, "observations in device memory: one visual window, without an all-reduce hook or communicator");
   for (int w = 0; w < W; ++w) { *win[w].iterations = 0; *win[w].initial_error = 0.0; *win[w].final_error = 0.0; win[w].status = ORBX_OK; }
   // ORBX_BA_TIMING=1: host-side phase times of this call on stderr (plan, preprocessing, descriptors + upload enqueue, launch
   // enqueue, drain, unpack)
@@ -4229,8 +4237,9 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
 int ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
                     const double* poses_cw, int F, const double* fixed_poses_cw, int M, double* points, int N,
                     const orbx_ba_obs* obs, orbx_should_stop_fn should_stop, void* user, double* poses_wc_out,
-                    int* iterations, double* initial_error, double* final_error, bool global_mode, const BaInertialHost* inr, const orbx_ba_obs32* obs32) {
-  BaWinHost w{K, F, M, N, poses_cw, fixed_poses_cw, points, obs, poses_wc_out, iterations, initial_error, final_error, ORBX_OK, obs32};
+                    int* iterations, double* initial_error, double* final_error, bool global_mode, const BaInertialHost* inr, const orbx_ba_obs32* obs32,
+                    bool obs_on_device) {
+  BaWinHost w{K, F, M, N, poses_cw, fixed_poses_cw, points, obs, poses_wc_out, iterations, initial_error, final_error, ORBX_OK, obs32, obs_on_device};
   return ba_solve_batch(h, cam, cfg, 1, &w, should_stop, user, global_mode, inr, true);
 }
 

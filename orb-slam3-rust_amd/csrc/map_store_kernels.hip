@@ -30,6 +30,18 @@
 //                     selection launches read, which then run unchanged
 // A keyframe's observed set counts a slot once: orbx_keyframe_set_map_point_slots keeps, beside the table, a copy with every repeat
 // set to -1 (d_mp_uniq), so distinctness costs nothing per (query, keyframe).
+//
+// The local-BA window (local_ba_lm.rs:665-726, :800-897; local_mapper.rs:377-410) is one query's covisibility and one frame's
+// selection, unchanged, and five launches behind them:
+//   bac_index_kernel    index[slot] = position in P for the list's entries (row 0 of `first`, EMPTY between calls)
+//   bac_count_kernel    (chunk of a keyframe's features, keyframe) over ALL keyframes of the call: the features whose slot — the
+//                       table WITH repeats: every feature is an observation — is in range, live and indexed; per chunk the count
+//   bac_order_kernel    one workgroup: every keyframe's role (anchor / optimised i / fixed j / none), the fixed keyframes by ascending
+//                       position (ordered append), where every observer's observations start (scan in observer order), K F M N
+//   bac_emit_kernel     (chunk, keyframe) ordered compaction behind the observer's earlier chunks; one 16-byte store per observation
+//   bac_restore_kernel  index[slot] = EMPTY again: the call leaves the table as it found it
+// orbx_map_local_ba hands the observations to the solver where they lie (ba_kernels.hip: BaWinHost::obs_on_device) and scatters the
+// optimised positions back through map_scatter_kernel.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -341,6 +353,143 @@ __global__ __launch_bounds__(MS_THREADS) void cov_seg_kernel(CovArgs A, const in
   if (tid == 0) n_cand[b] = carry;
   if (local_kf && r < 0)
     for (int j = tid; j < 1 + A.n_best; j += MS_THREADS) local_kf[(size_t)b * (1 + A.n_best) + j] = -1;
+}
+
+// ---- local BA window (include/orbx.h, "local BA from the resident map"; local_ba_lm.rs:665-726, :800-897) ----------------
+
+constexpr int BAC_NONE = 0x7fffffff;             // role of a keyframe that observes none of the window's points
+
+// One keyframe of a collection call: its slot table WITH repeats (NULL: no table) and its keypoints (28-byte rows).
+struct BacKf {
+  const int* slots; const orbx_keypoint* kp;
+  int n, pad_;
+};
+struct BacArgs {
+  int capacity, n_kfs, n_chunk, n_local;         // n_local = 1 + max_covisible: entries of local_kf
+  const uint8_t* live; const BacKf* kfs;
+  const int* list_off; const int* list_slot;     // the selection's outputs: M = list_off[1]
+  int* index;                                    // the store's first-sighting table, row 0: EMPTY outside the launches below
+  int* chunk_count;                              // [n_kfs][n_chunk]
+  int* kf_count; int* role; int* obs_base;       // [n_kfs]: c(k); the kf_idx its observations carry (BAC_NONE: none); where they start
+  const int* local_kf;                           // [n_local], -1 padded (cov_seg_kernel)
+  int* counts; int* fixed_kf; orbx_ba_obs32* obs;
+};
+
+// index[slot] = position in P ...
+__global__ __launch_bounds__(MS_THREADS) void bac_index_kernel(BacArgs A) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i < A.list_off[1]) A.index[A.list_slot[i]] = i;
+}
+// ... and back to EMPTY: the call leaves the table as it found it
+__global__ __launch_bounds__(MS_THREADS) void bac_restore_kernel(BacArgs A) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i < A.list_off[1]) A.index[A.list_slot[i]] = MS_EMPTY;
+}
+
+// does feature i of `kf` observe a point of the window?  -> its mp_idx, or -1
+__device__ __forceinline__ int bac_mp_idx(const BacArgs& A, const BacKf& kf, int i) {
+  if (i >= kf.n) return -1;
+  const int s = kf.slots[i];
+  if (s < 0 || s >= A.capacity || !A.live[s]) return -1;
+  const int m = A.index[s];
+  return m == MS_EMPTY ? -1 : m;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void bac_count_kernel(BacArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int k = blockIdx.y;
+  const BacKf kf = A.kfs[k];
+  const int p0 = blockIdx.x * MS_CHUNK + threadIdx.x * MS_PER;
+  int n = 0;
+  if (kf.slots) {
+#pragma unroll
+    for (int j = 0; j < MS_PER; ++j) n += bac_mp_idx(A, kf, p0 + j) >= 0;
+  }
+  n = block_sum<MS_THREADS>(n, wave_tot);
+  if (threadIdx.x == 0) A.chunk_count[k * A.n_chunk + blockIdx.x] = n;
+}
+
+// One workgroup: every keyframe's role, the fixed keyframes by position, where every observer's observations start, the counts.
+__global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
+  __shared__ int lds[MS_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n_kfs;
+  for (int k = tid; k < n; k += MS_THREADS) {
+    int c = 0;
+    for (int j = 0; j < A.n_chunk; ++j) c += A.chunk_count[k * A.n_chunk + j];
+    A.kf_count[k] = c; A.role[k] = BAC_NONE;
+  }
+  __syncthreads();
+  int n_loc = 0;                                                           // local_kf's entries before the padding: each names another keyframe
+  for (int j = tid; j < A.n_local; j += MS_THREADS) {
+    const int k = A.local_kf[j];
+    if (k >= 0) { A.role[k] = j - 1; ++n_loc; }                           // anchor -1, optimised keyframe i: i - 1
+  }
+  n_loc = block_sum<MS_THREADS>(n_loc, lds);                               // (its barriers order the roles before the reads below)
+  BlockAppend<MS_THREADS, 1> fixed(lds);
+  for (int k0 = 0; k0 < n; k0 += MS_THREADS) {                             // the other observers, ascending position
+    const int k = k0 + tid;
+    const bool f = k < n && A.role[k] == BAC_NONE && A.kf_count[k] > 0;
+    const int at = fixed.round(f);
+    if (f) { A.fixed_kf[at] = k; A.role[k] = -2 - at; }
+  }
+  const int n_fixed = fixed.total[0], n_obs = n_loc + n_fixed;
+  for (int k = n_fixed + tid; k < n; k += MS_THREADS) A.fixed_kf[k] = -1;
+  __syncthreads();                                                         // fixed_kf is read below by other threads than wrote it
+  int carry = 0;
+  for (int o0 = 0; o0 < n_obs; o0 += MS_THREADS) {                         // exclusive scan of the counts in observer order
+    const int o = o0 + tid;
+    const int k = o >= n_obs ? -1 : o < n_loc ? A.local_kf[o] : A.fixed_kf[o - n_loc];
+    const int c = k >= 0 ? A.kf_count[k] : 0;
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(incl, d);
+      if (lane >= d) incl += t;
+    }
+    __syncthreads();                                                       // (the previous round's totals are no longer read)
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int v = 0; v < MS_THREADS / 64; ++v) { const int t = lds[v]; before += v < wave ? t : 0; all += t; }
+    if (k >= 0) A.obs_base[k] = carry + before + incl - c;
+    carry += all;
+  }
+  if (tid == 0) { A.counts[0] = n_loc - 1; A.counts[1] = 1 + n_fixed; A.counts[2] = A.list_off[1]; A.counts[3] = carry; }
+}
+
+// (chunk, keyframe): ordered compaction of the chunk's counted features behind the observer's earlier chunks
+__global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int role = A.role[k];
+  if (role == BAC_NONE || A.kf_count[k] == 0) return;                      // (the same in every thread)
+  const BacKf kf = A.kfs[k];
+  int base = A.obs_base[k];
+  for (int j = 0; j < (int)blockIdx.x; ++j) base += A.chunk_count[k * A.n_chunk + j];
+  const int p0 = blockIdx.x * MS_CHUNK + tid * MS_PER;
+  int mp[MS_PER], n = 0;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) { mp[j] = bac_mp_idx(A, kf, p0 + j); n += mp[j] >= 0; }
+  int incl = n;                                                            // inclusive scan of the threads' counts over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  size_t o = (size_t)base + (incl - n);
+  for (int w = 0; w < wave; ++w) o += wave_tot[w];
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    if (mp[j] < 0) continue;
+    const float* xy = (const float*)(kf.kp + (p0 + j));                    // 28-byte rows: two dword loads
+    int4 v;
+    v.x = role; v.y = mp[j]; v.z = __float_as_int(xy[0]); v.w = __float_as_int(xy[1]);
+    *(int4*)(A.obs + o) = v;
+    ++o;
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -657,6 +806,97 @@ int local_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, i
   if (int rc = cov_enqueue(h, mp, P.C, B, ref_kf, n_best, nullptr, nullptr, nullptr, &sg)) return rc;
   return ms_select_launch(h, mp, ORBX_MAP_SOURCE_KEYFRAMES, B, P.max_cand, sg.d_segs, sg.d_seg_off, sg.d_n_cand, nullptr, nullptr, d_list_off, d_list_slot,
                           d_positions, d_mp_desc);
+}
+
+// ---- local BA window, host side --------------------------------------------------------------------------------------------
+
+// A collection call, checked and sized on the host: the local-map plan of one frame whose reference is `cur` (list bound,
+// segments), the keyframes' tables with their keypoints, and the bound of the observations: every feature of kfs[].
+struct BacPlan {
+  LocalPlan L;
+  std::vector<BacKf> kfs;
+  int n_feat = 0, max_n = 0;
+};
+
+int bac_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible, BacPlan& P) {
+  if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
+  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+  if (max_covisible < 0 || max_covisible >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "%s: max_covisible must not be negative", who);
+  if (int rc = local_plan(h, who, mp, 1, n_kfs, kfs, &cur, max_covisible, P.L)) return rc;
+  P.kfs.resize((size_t)n_kfs);
+  long long total = 0;
+  for (int t = 0; t < n_kfs; ++t) {
+    const orbx_keyframe* kf = kfs[t];
+    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0};
+    total += kf->n; P.max_n = std::max(P.max_n, kf->n);
+  }
+  if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+  P.n_feat = (int)total;
+  return ORBX_OK;
+}
+
+// Everything on the handle's stream: covisibility and selection as the tracking call runs them, then the five launches above.
+int bac_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BacPlan& P, int cur, int max_covisible, int list_cap, int obs_cap, int* d_counts,
+                int* d_local_kf, int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  const int bound = P.L.bound_off[1], n_kfs = (int)P.kfs.size();
+  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (cur's features plus the max_covisible largest of the "
+                                         "others', at most the capacity)", who, list_cap, bound);
+  if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
+  if (!d_counts || !d_local_kf || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_obs32 is 16-byte aligned)", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t K = (size_t)n_kfs;
+  const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK);
+  Carve ws;
+  const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
+               o_ob = ws.take(4 * K);
+  if (int rc = orbx_reserve(h, h->ws_map[6], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[6].p;
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[7], sizeof(BacKf) * K, &hs, &ds)) return rc;
+  std::memcpy(hs, P.kfs.data(), sizeof(BacKf) * K);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[7], sizeof(BacKf) * K)) return rc;
+  // local = [cur] ++ best and P: what one frame of orbx_map_track_local_device gets (the descriptors it gathers stay in the workspace)
+  if (int rc = local_select_enqueue(h, who, mp, 1, P.L, &cur, max_covisible, bound, d_local_kf, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)) return rc;
+  BacArgs A{};
+  A.capacity = mp->capacity; A.n_kfs = n_kfs; A.n_chunk = n_chunk; A.n_local = 1 + max_covisible;
+  A.live = mp->d_live; A.kfs = (const BacKf*)ds; A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot;
+  A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
+  A.chunk_count = (int*)(w + o_cc); A.kf_count = (int*)(w + o_kc); A.role = (int*)(w + o_ro); A.obs_base = (int*)(w + o_ob);
+  A.local_kf = d_local_kf; A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
+  const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
+  {
+    ProfScope ps(h, "bac_index_kernel", true);
+    hipLaunchKernelGGL(bac_index_kernel, list_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_count_kernel", true);
+    hipLaunchKernelGGL(bac_count_kernel, kf_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_order_kernel", true);
+    hipLaunchKernelGGL(bac_order_kernel, dim3(1), block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_emit_kernel", true);
+    hipLaunchKernelGGL(bac_emit_kernel, kf_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_restore_kernel", true);
+    hipLaunchKernelGGL(bac_restore_kernel, list_grid, block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// se3.rs:56-63 with nalgebra's quaternion-vector product, one IEEE operation at a time (include/orbx.hpp's se3_inverse)
+void bac_pose_inverse(const double* p, double* out) {
+  const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
+  const double* v = p + 4;
+  const double t[3] = {2.0 * (y * v[2] - z * v[1]), 2.0 * (z * v[0] - x * v[2]), 2.0 * (x * v[1] - y * v[0])};
+  const double c[3] = {y * t[2] - z * t[1], z * t[0] - x * t[2], x * t[1] - y * t[0]};
+  out[0] = w; out[1] = x; out[2] = y; out[3] = z;
+  for (int i = 0; i < 3; ++i) out[4 + i] = -(t[i] * w + c[i] + v[i]);
 }
 
 // ---- tracking from the store: what the keyframe / slot forms and the local-map forms share --------------------------------
@@ -1021,6 +1261,111 @@ int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_trac
                        [&](const int*, int* d_lk, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
                          return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, P.bound_off[(size_t)n_frames], d_lk, d_lo, d_ls, d_gp, d_gd);
                        });
+}
+
+int orbx_map_collect_ba_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible,
+                                      int list_cap, int obs_cap, int* d_counts, int* d_local_kf, int* d_fixed_kf, int* d_list_slot, double* d_positions,
+                                      orbx_ba_obs32* d_obs32) {
+  static const char* who = "orbx_map_collect_ba_window_device";
+  if (!h) return ORBX_ERR_INVALID;
+  BacPlan P;
+  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
+  return bac_enqueue(h, who, mp, P, cur, max_covisible, list_cap, obs_cap, d_counts, d_local_kf, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+}
+
+int orbx_map_collect_ba_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible, int list_cap,
+                               int obs_cap, int* counts, int* local_kf, int* fixed_kf, int* list_slot, double* positions, orbx_ba_obs32* obs32) {
+  static const char* who = "orbx_map_collect_ba_window";
+  if (!h) return ORBX_ERR_INVALID;
+  BacPlan P;
+  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
+  const size_t bound = (size_t)P.L.bound_off[1], nf = (size_t)P.n_feat, nl = 1 + (size_t)max_covisible, K = (size_t)n_kfs;
+  if (list_cap < (int)bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, (int)bound, P.n_feat);
+  if (!counts || !local_kf || !fixed_kf || (bound > 0 && (!list_slot || !positions)) || (nf > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // the sizes first (counts, local and fixed keyframes), then as many rows as they say: two downloads, nothing sized by a bound
+  Carve out;
+  const size_t o_cn = out.take(16), o_lk = out.take(4 * nl), o_fx = out.take(4 * K);
+  const size_t head = out.off;
+  const size_t o_ls = out.take(4 * bound), o_po = out.take(24 * bound), o_ob = out.take(16 * nf);
+  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, head)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_map[1].p;
+  if (int rc = bac_enqueue(h, who, mp, P, cur, max_covisible, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_lk), (int*)(d + o_fx), (int*)(d + o_ls),
+                           (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
+    return rc;
+  uint8_t* hp = (uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(hp, d, head, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  std::memcpy(counts, hp + o_cn, 16); std::memcpy(local_kf, hp + o_lk, 4 * nl); std::memcpy(fixed_kf, hp + o_fx, 4 * K);
+  const size_t M = (size_t)counts[2], N = (size_t)counts[3];
+  if (M == 0 || N == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
+  Carve rows;
+  const size_t r_ls = rows.take(4 * M), r_po = rows.take(24 * M), r_ob = rows.take(16 * N);
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, rows.off)) return rc;
+  hp = (uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_ls, d + o_ls, 4 * M, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_po, d + o_po, 24 * M, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_ob, d + o_ob, 16 * N, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  std::memcpy(list_slot, hp + r_ls, 4 * M); std::memcpy(positions, hp + r_po, 24 * M); std::memcpy(obs32, hp + r_ob, 16 * N);
+  return ORBX_OK;
+}
+
+int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs,
+                      int cur, orbx_should_stop_fn should_stop, void* user, int* local_kf_out, double* poses_wc_out, int* counts_out, int* iterations,
+                      double* initial_error, double* final_error) {
+  static const char* who = "orbx_map_local_ba";
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || !local_kf_out || !counts_out || !iterations || !initial_error || !final_error || (cfg->max_covisible_keyframes > 0 && !poses_wc_out))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)", who);
+  const int max_cov = cfg->max_covisible_keyframes;
+  BacPlan P;
+  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_cov, P)) return rc;
+  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+  const size_t bound = (size_t)P.L.bound_off[1], nf = (size_t)P.n_feat, nl = 1 + (size_t)max_cov, K = (size_t)n_kfs;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // phase 1 (collect_visual_ba_data, :800-897) on the device; ONE download: counts | local | fixed | P's slots | P's positions
+  Carve out;
+  const size_t o_cn = out.take(16), o_lk = out.take(4 * nl), o_fx = out.take(4 * K), o_ls = out.take(4 * bound), o_po = out.take(24 * bound);
+  const size_t down = out.off;
+  const size_t o_ob = out.take(16 * nf);
+  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
+  uint8_t* d = (uint8_t*)h->ws_map[1].p;
+  orbx_prof_begin_call(h);
+  if (int rc = bac_enqueue(h, who, mp, P, cur, max_cov, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_lk), (int*)(d + o_fx), (int*)(d + o_ls),
+                           (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
+    return rc;
+  uint8_t* hp = (uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(hp, d, down, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  const int* cn = (const int*)(hp + o_cn);
+  const int* lk = (const int*)(hp + o_lk);
+  const int* fx = (const int*)(hp + o_fx);
+  const int Ko = cn[0], F = cn[1], M = cn[2], N = cn[3];
+  std::memcpy(counts_out, cn, 16); std::memcpy(local_kf_out, lk, 4 * nl);
+  if (M == 0 || N == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
+  try {
+    // T_cw from the keyframes' own poses (:825-841): the optimised ones, then the anchor and the other fixed observers
+    std::vector<double> poses_cw(7 * (size_t)std::max(Ko, 1)), fixed_cw(7 * (size_t)F), points((const double*)(hp + o_po), (const double*)(hp + o_po) + 3 * (size_t)M);
+    std::vector<int> slots((const int*)(hp + o_ls), (const int*)(hp + o_ls) + M);
+    for (int i = 0; i < Ko; ++i) bac_pose_inverse(kfs[lk[1 + i]]->pose_wc, &poses_cw[7 * (size_t)i]);
+    bac_pose_inverse(kfs[lk[0]]->pose_wc, &fixed_cw[0]);
+    for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
+    // phase 2 (solve_visual_ba, :912-1098) on the observations where they lie
+    if (int rc = ba_solve_visual(h, cam, cfg, Ko, poses_cw.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
+                                 initial_error, final_error, false, nullptr, (const orbx_ba_obs32*)(d + o_ob), true))
+      return rc;
+    // phase 3, the point half of apply_visual_ba_results (:1125-1135; local_mapper.rs:396: only a solve that iterated is applied)
+    if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
+    return ORBX_OK;
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
+  } catch (...) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
+  }
 }
 
 int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,

@@ -1076,6 +1076,29 @@ int orbx_ba_solve_visual_obs32(orbx_handle* h, const orbx_camera* cam, const orb
   }
 }
 
+int orbx_ba_solve_visual_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
+                                      const double* poses_cw, int F, const double* fixed_poses_cw, int M,
+                                      double* points, int N, const orbx_ba_obs32* d_obs32, orbx_should_stop_fn should_stop,
+                                      void* user, double* poses_wc_out, int* iterations, double* initial_error,
+                                      double* final_error) {
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || K < 0 || F < 0 || M < 0 || N < 0 || !iterations || !initial_error || !final_error ||
+      (K > 0 && (!poses_cw || !poses_wc_out)) || (F > 0 && !fixed_poses_cw) || (M > 0 && !points) ||
+      (N > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
+    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32_device: bad argument (d_obs32 is 16-byte aligned)");
+  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32_device: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)");
+  ORBX_HIP(h, hipSetDevice(h->device));
+  orbx_prof_begin_call(h);
+  try {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user,
+                           poses_wc_out, iterations, initial_error, final_error, false, nullptr, d_obs32, true);
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32_device: out of host memory");
+  } catch (...) {
+    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32_device: unexpected C++ exception");
+  }
+}
+
 int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int n_windows,
                                orbx_ba_window* windows, orbx_should_stop_fn should_stop, void* user) {
   if (!h) return ORBX_ERR_INVALID;

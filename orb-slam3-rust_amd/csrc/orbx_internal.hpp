@@ -242,7 +242,7 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
-  DevBuf ws_map[6];                      // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries
+  DevBuf ws_map[8];                      // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs
   PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
   UploadRing ring_map;                   // the tables on their way to ws_map[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
@@ -492,7 +492,8 @@ int ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config
                     double* points, int N, const orbx_ba_obs* obs, orbx_should_stop_fn should_stop,
                     void* user, double* poses_wc_out, int* iterations, double* initial_error,
                     double* final_error, bool global_mode = false, const struct BaInertialHost* inr = nullptr,
-                    const orbx_ba_obs32* obs32 = nullptr);   // obs32: the 16-byte form of the observations, used instead of obs when given
+                    const orbx_ba_obs32* obs32 = nullptr,    // obs32: the 16-byte form of the observations, used instead of obs when given
+                    bool obs_on_device = false);             // ... and it lies in device memory of the handle's device, ordered on its stream
 // one window of a batch as the caller hands it over (orbx_ba_solve_visual_batch); status: ORBX_OK or ORBX_ERR_EMPTY
 struct BaWinHost {
   int K, F, M, N;
@@ -500,6 +501,8 @@ struct BaWinHost {
   double* poses_wc_out; int* iterations; double* initial_error; double* final_error;
   int status;
   const orbx_ba_obs32* obs32 = nullptr;       // the 16-byte form of the observations (orbx.h): used instead of obs when given
+  bool obs_on_device = false;                 // obs / obs32 is device memory, written by work already enqueued on the handle's stream: copied
+                                              // device to device into the blob; no host path may read it (one window, no collective)
 };
 // What one ba_solve_batch call is told about the batch it is a half of (orbx_ba_solve_visual_batch builds one per half; default: none).
 // The two halves of a batch share one PCIe link: the second half's uploads are ordered behind the first half's (its kernels then start
