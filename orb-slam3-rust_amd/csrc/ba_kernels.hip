@@ -49,6 +49,7 @@
 #include <chrono>
 #include <thread>
 
+#include "block_dev.hpp"
 #include "orbx_internal.hpp"
 #include "pose_dev.hpp"
 
@@ -275,10 +276,9 @@ __global__ __launch_bounds__(256) void ba_prep_count_kernel(const BaWin* __restr
 // one block per window: exclusive scans.  pt_fill is left zeroed for the place pass.
 __global__ __launch_bounds__(1024) void ba_prep_scan_kernel(const BaWin* __restrict__ wins) {
   __shared__ int s_wave[16];
-  __shared__ int s_carry;
   const BaWin win = ba_win_global(wins, blockIdx.y);
   BaState* S = win.S;
-  if (S->done) return;
+  if (S->done) return;                                                    // (uniform, as S->bad: the window is the block's, both written by earlier launches)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (S->bad != 0) {                                                      // (uniform: written by the previous launch)
     __syncthreads();
@@ -288,35 +288,22 @@ __global__ __launch_bounds__(1024) void ba_prep_scan_kernel(const BaWin* __restr
   const int K = win.d.K, M = win.d.M;
   int* __restrict__ pt_start = const_cast<int*>(win.pt_start);
   int* __restrict__ pt_fill = win.pt_fill;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int j0 = 0; j0 < M; j0 += 1024) {
+  BlockScan<1024> scan(s_wave);
+  for (int j0 = 0; j0 < M; j0 += 1024) {                                  // (M is the window's: every thread takes every round)
     const int j = j0 + tid;
     const int c = j < M ? pt_fill[j] : 0;
     if (j < M) pt_fill[j] = 0;
-    int inc = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int base = s_carry;
-    for (int w2 = 0; w2 < wave; ++w2) base += s_wave[w2];
-    if (j < M) pt_start[j] = base + inc - c;
-    __syncthreads();
-    if (tid == 1023) s_carry = base + inc;
-    __syncthreads();
+    const int at = scan.round(c);
+    if (j < M) pt_start[j] = at;
   }
-  if (tid == 0) pt_start[M] = s_carry;
+  if (tid == 0) pt_start[M] = scan.total;
   if (wave == 0) {
     // kf_start[k + 1] = observations of the keyframes 0 .. k: a wave scan, two keyframes per lane (K <= 128) — one thread's loop of K
     // dependent read-modify-writes was most of this launch at 49 keyframes (16 us)
     int* kf_start = const_cast<int*>(win.kf_start);                      // (kf_start[0] = 0: zeroed with the counters)
     static_assert(BA_MAX_K <= 128, "two keyframes per lane of one wave");
     const int k0 = 2 * lane, c0 = k0 < K ? kf_start[k0 + 1] : 0, c1 = k0 + 1 < K ? kf_start[k0 + 2] : 0;
-    int inc = c0 + c1;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-    const int before = inc - c0 - c1;
+    const int before = wave_inclusive_scan(c0 + c1) - c0 - c1;
     if (k0 < K) kf_start[k0 + 1] = before + c0;
     if (k0 + 1 < K) kf_start[k0 + 2] = before + c0 + c1;
   }
@@ -420,38 +407,27 @@ __global__ __launch_bounds__(256) void ba_slots_kernel(const BaWin* __restrict__
 
 // The keyframe lists (for each optimised keyframe the observations it makes, in point-major order, and their map points) from the slot
 // map: block k walks the points in chunks of 256, a thread counts its point's chain for keyframe k (0, 1, rarely more), a block-wide
-// exclusive scan places them behind the keyframe's host-computed start.  Until round 3's end the host built these 8 bytes per observation
+// exclusive scan (BlockScan) places them behind the keyframe's start.  Until round 3's end the host built these 8 bytes per observation
 // and uploaded them with every call.  Same order as the host's pass produced (ascending observation index within a keyframe).
-// (Round 5: 1024 threads — the block walks the points in chunks of its size with three barriers per chunk; with the sixteen-lane slot kernel
+// (Round 5: 1024 threads — the block walks the points in chunks of its size, then with three barriers per chunk, two since BlockScan; with the sixteen-lane slot kernel
 // the two launches together 27.5 -> 11.8 us per call at 20 keyframes / 2000 points, 82 -> 29.4 us at 50 / 8000: profiles/r05_ba_setup_kernels_ab.txt)
 constexpr int BA_KFL_THREADS = 1024;
 __global__ __launch_bounds__(BA_KFL_THREADS) void ba_kflist_kernel(const BaWin* __restrict__ wins) {
   __shared__ int s_wave[BA_KFL_THREADS / 64];
-  __shared__ int s_base;
   const BaWin win = ba_win_global(wins, blockIdx.y);
   const int K = win.d.K, M = win.d.M, k = blockIdx.x;
-  if (win.S->done || k >= K) return;
+  if (win.S->done || k >= K) return;                                        // (uniform: the window and k are the block's)
   const int* __restrict__ slot_first = win.slot_first; const int* __restrict__ nxt = win.obs_next;
   int* __restrict__ kf_obs = win.kf_obs; int* __restrict__ kf_pt = win.kf_pt;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_base = win.kf_start[k];
-  __syncthreads();
+  const int tid = threadIdx.x;
+  BlockScan<BA_KFL_THREADS> scan(s_wave, win.kf_start[k]);
   for (int j0 = 0; j0 < M; j0 += BA_KFL_THREADS) {
     const int j = j0 + tid;
     const int first = j < M ? slot_first[(size_t)j * K + k] : -1;
     int cnt = 0;
     for (int i = first; i >= 0; i = nxt[i]) ++cnt;
-    int inc = cnt;                                                          // inclusive scan over the wave, then over the four waves
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int pos = s_base + inc - cnt;
-    for (int w2 = 0; w2 < wave; ++w2) pos += s_wave[w2];
+    int pos = scan.round(cnt);
     for (int i = first; i >= 0; i = nxt[i]) { kf_obs[pos] = i; kf_pt[pos] = j; ++pos; }
-    __syncthreads();
-    if (tid == BA_KFL_THREADS - 1) s_base = pos;                            // (the last thread's end = the chunk's end)
-    __syncthreads();
   }
 }
 

@@ -1,6 +1,7 @@
-// block_dev.hpp — workgroup primitives shared by the kernels: the fixed-order block sum (int or f64) and the ordered append
-// ("Workgroup primitives").  Every thread of the workgroup must reach each call; THREADS is the workgroup's size, a
-// multiple of 64.
+// block_dev.hpp — workgroup primitives shared by the kernels: the fixed-order block sum (int or f64), the ordered append, the
+// ordered scan of counts and the counter scan of the counting sorts ("Workgroup primitives").  Every thread of the
+// workgroup must reach each call — a call under a condition that is not uniform over the block hangs it; THREADS is the
+// workgroup's size, a multiple of 64.
 // Device code only, inside an anonymous namespace: each translation unit that includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,5 +80,75 @@ struct BlockAppend {
     return at[0];
   }
 };
+
+// Inclusive scan of v over the 64 lanes of a wave: the one step the scans below share.  No LDS, no barrier.
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T t = __shfl_up(v, off);
+    if (lane >= off) v += t;
+  }
+  return v;
+}
+
+// Ordered exclusive scan of counts: BlockAppend from flags to counts.  Each round every thread passes its count and gets the number
+// of items of the threads before it, in thread order, over this and all earlier rounds, plus whatever `total` started from (a list
+// behind a base) — the place of the thread's first item.  total is the same in every thread: the count so far.  Two barriers per
+// round; the first also covers an earlier use of the same LDS.
+// round<false> is for a single round whose total only the last thread needs, or nobody (a counting sort's end sentinel): a thread
+// adds the waves before it and no more, and total is the block's in thread THREADS - 1 alone.  No round may follow it.  (Sixteen
+// wave totals summed in every thread cost a 1024-thread counting sort some 20 VGPRs and 35 instructions, and the one-launch stereo
+// matcher a wave of occupancy: profiles/block_scan_codegen.txt.)
+template <int THREADS, typename T = int>
+struct BlockScan {
+  T* wave_tot;        // LDS [THREADS / 64]
+  T total;
+  __device__ __forceinline__ explicit BlockScan(T* lds, T start = 0) : wave_tot(lds), total(start) {}
+  template <bool UNIFORM = true>
+  __device__ __forceinline__ T round(T count) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T incl = wave_inclusive_scan(count);
+    __syncthreads();                                                      // (the previous round's totals are no longer read)
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+    if (UNIFORM) {
+#pragma unroll
+      for (int w = 0; w < THREADS / 64; ++w) { const T t = wave_tot[w]; before += w < wave ? t : 0; all += t; }
+    } else {
+      for (int w = 0; w < wave; ++w) before += wave_tot[w];
+      all = before + incl;                                                // (the last thread's: the block's)
+    }
+    const T at = total + before + incl - count;
+    total += all;
+    return at;
+  }
+};
+
+struct NoEmit {
+  template <typename T>
+  __device__ __forceinline__ void operator()(int, T) const {}
+};
+
+// In-place exclusive prefix over THREADS x PER counters in LDS (int or unsigned), thread t scanning counters [PER t, PER t + PER):
+// the middle of a counting sort.  emit(i, start) is called by that thread with every counter's start as it is produced, from
+// registers (a sort writes its cell_start there).  Returns the total, as BlockScan<THREADS>::round<UNIFORM> leaves it: in every
+// thread, or with UNIFORM = false in the last thread only — the end sentinel, written by the caller in one place.
+// wave_tot: LDS [THREADS / 64].  The caller puts a barrier between the last update of the counters and this call, and one between
+// this call and the first read of a start from LDS; inside, BlockScan's two.
+template <int THREADS, int PER, bool UNIFORM = true, typename T, typename Emit = NoEmit>
+__device__ __forceinline__ T block_counter_scan(T* cnt, T* wave_tot, Emit emit = Emit()) {
+  const int i0 = PER * threadIdx.x;
+  T c[PER], tot = 0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) { c[k] = cnt[i0 + k]; tot += c[k]; }
+  BlockScan<THREADS, T> scan(wave_tot);
+  T run = scan.template round<UNIFORM>(tot);
+#pragma unroll
+  for (int k = 0; k < PER; ++k) { emit(i0 + k, run); cnt[i0 + k] = run; run += c[k]; }
+  return scan.total;
+}
 
 }  // namespace

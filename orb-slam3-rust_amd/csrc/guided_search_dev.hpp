@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "../../include/orbx.h"
+#include "block_dev.hpp"
 
 namespace {
 
@@ -54,7 +55,7 @@ __device__ __forceinline__ void grid_build_body(const orbx_keypoint* __restrict_
                                                 unsigned short* __restrict__ cell_of) {
   __shared__ int cnt[GG_CELLS];
   __shared__ int wsum[GG_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int i = tid; i < GG_CELLS; i += GG_THREADS) cnt[i] = 0;
   __syncthreads();
   for (int i = tid; i < n; i += GG_THREADS) {
@@ -65,20 +66,8 @@ __device__ __forceinline__ void grid_build_body(const orbx_keypoint* __restrict_
     atomicAdd(&cnt[c], 1);
   }
   __syncthreads();
-  int c3[3], tot = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { c3[k] = cnt[3 * tid + k]; tot += c3[k]; }
-  int inc = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = inc - tot;
-  for (int wv = 0; wv < wave; ++wv) base += wsum[wv];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { cell_start[3 * tid + k] = base; cnt[3 * tid + k] = base; base += c3[k]; }
-  if (tid == GG_THREADS - 1) cell_start[GG_CELLS] = base;
+  const int total = block_counter_scan<GG_THREADS, GG_CELLS / GG_THREADS, false>(cnt, wsum, [&](int i, int start) { cell_start[i] = start; });
+  if (tid == GG_THREADS - 1) cell_start[GG_CELLS] = total;                // (round<false>: the last thread holds the total)
   __syncthreads();
   for (int i = tid; i < n; i += GG_THREADS) sorted_idx[atomicAdd(&cnt[cell_of[i]], 1)] = i;
 }

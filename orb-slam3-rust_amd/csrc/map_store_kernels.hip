@@ -13,8 +13,8 @@
 //   map_flag_kernel   a candidate survives iff the table holds its own number; the survivor puts the table's entry back to EMPTY,
 //                     so that a call leaves the table as it found it and costs what its candidates cost, not what the map holds;
 //                     per chunk the number of survivors
-//   map_emit_kernel   a chunk's base = the survivors of all chunks before it (earlier frames, then earlier chunks); ordered
-//                     compaction inside the chunk by ballot / prefix; list_slot, positions and descriptors gathered
+//   map_emit_kernel   a chunk's base = the survivors of all chunks before it (earlier frames, then earlier chunks; block_sum);
+//                     ordered compaction inside the chunk behind it (BlockScan); list_slot, positions and descriptors gathered
 // Every frame has a table of its own ([frame][capacity]), so frames of one call that share keyframes do not meet.  The only atomics
 // are that integer min: every output is a deterministic function of the inputs.
 //
@@ -27,7 +27,7 @@
 //   cov_rank_kernel   one workgroup per query: rank(i) = #{j : w_j > w_i or (w_j == w_i and j < i)}; i goes to best[rank] when
 //                     w_i > 0 and rank < n_best
 //   cov_seg_kernel    one workgroup per frame: [reference] ++ best (or every keyframe) as the MapSeg / n_cand arrays that the three
-//                     selection launches read, which then run unchanged
+//                     selection launches read, which then run unchanged; the segments' bases by BlockScan, a round per 256
 // A keyframe's observed set counts a slot once: orbx_keyframe_set_map_point_slots keeps, beside the table, a copy with every repeat
 // set to -1 (d_mp_uniq), so distinctness costs nothing per (query, keyframe).
 //
@@ -37,11 +37,12 @@
 //   bac_count_kernel    (chunk of a keyframe's features, keyframe) over ALL keyframes of the call: the features whose slot — the
 //                       table WITH repeats: every feature is an observation — is in range, live and indexed; per chunk the count
 //   bac_order_kernel    one workgroup: every keyframe's role (anchor / optimised i / fixed j / none), the fixed keyframes by ascending
-//                       position (ordered append), where every observer's observations start (scan in observer order), K F M N
+//                       position (BlockAppend), where every observer's observations start (BlockScan in observer order), K F M N
 //   bac_emit_kernel     (chunk, keyframe) ordered compaction behind the observer's earlier chunks; one 16-byte store per observation
 //   bac_restore_kernel  index[slot] = EMPTY again: the call leaves the table as it found it
 // orbx_map_local_ba hands the observations to the solver where they lie (ba_kernels.hip: BaWinHost::obs_on_device) and scatters the
 // optimised positions back through map_scatter_kernel.
+// The sums, the ordered append and the scans of counts are block_dev.hpp's: every thread of a workgroup reaches each of them.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(MS_THREADS) void map_flag_kernel(SelArgs A) {
 
 __global__ __launch_bounds__(MS_THREADS) void map_emit_kernel(SelArgs A, int B) {
   __shared__ int wave_tot[MS_THREADS / 64];
-  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, tid = threadIdx.x;
   const int me = b * A.n_chunk + blockIdx.x;
   int part = 0;
   for (int j = tid; j < me; j += MS_THREADS) part += A.chunk_count[j];
@@ -164,17 +165,7 @@ __global__ __launch_bounds__(MS_THREADS) void map_emit_kernel(SelArgs A, int B) 
   int slot[MS_PER], n = 0;
 #pragma unroll
   for (int k = 0; k < MS_PER; ++k) { slot[k] = cand[k]; n += slot[k] >= 0; }
-  int incl = n;                                                            // inclusive scan of the threads' counts over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  size_t o = (size_t)base + (incl - n);
-  for (int w = 0; w < wave; ++w) o += wave_tot[w];
+  size_t o = (size_t)BlockScan<MS_THREADS>(wave_tot, base).round(n);
 #pragma unroll
   for (int k = 0; k < MS_PER; ++k) {
     const int s = slot[k];
@@ -323,34 +314,22 @@ __global__ __launch_bounds__(MS_THREADS) void cov_rank_kernel(CovArgs A) {
 // a segment without candidates); ref == -1: every keyframe of the call in order.  The segments' bases by an ordered scan.
 __global__ __launch_bounds__(MS_THREADS) void cov_seg_kernel(CovArgs A, const int* ref, const int* seg_off, MapSeg* segs, int* n_cand, int* local_kf) {
   __shared__ int wave_tot[MS_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int r = ref[b], so = seg_off[b], S = seg_off[b + 1] - so;
-  int carry = 0;
-  for (int j0 = 0; j0 < S; j0 += MS_THREADS) {
+  BlockScan<MS_THREADS> scan(wave_tot);
+  for (int j0 = 0; j0 < S; j0 += MS_THREADS) {                             // (S is the block's: every thread takes every round)
     const int j = j0 + tid;
     int kfi = -1;
     if (j < S) kfi = r < 0 ? j : j == 0 ? r : A.best[(size_t)b * A.n_best + (j - 1)];
     CovKf kf{nullptr, nullptr, 0, 0};
     if (kfi >= 0) kf = A.kfs[kfi];
-    int incl = kf.n;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    __syncthreads();                                                       // (the previous round's totals are no longer read)
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int v = 0; v < MS_THREADS / 64; ++v) { const int t = wave_tot[v]; before += v < wave ? t : 0; all += t; }
+    const int base = scan.round(kf.n);
     if (j < S) {
-      segs[so + j] = MapSeg{kf.slots, carry + before + incl - kf.n, kf.n};
+      segs[so + j] = MapSeg{kf.slots, base, kf.n};
       if (local_kf && r >= 0) local_kf[(size_t)b * (1 + A.n_best) + j] = kfi;
     }
-    carry += all;
   }
-  if (tid == 0) n_cand[b] = carry;
+  if (tid == 0) n_cand[b] = scan.total;
   if (local_kf && r < 0)
     for (int j = tid; j < 1 + A.n_best; j += MS_THREADS) local_kf[(size_t)b * (1 + A.n_best) + j] = -1;
 }
@@ -412,7 +391,7 @@ __global__ __launch_bounds__(MS_THREADS) void bac_count_kernel(BacArgs A) {
 // One workgroup: every keyframe's role, the fixed keyframes by position, where every observer's observations start, the counts.
 __global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
   __shared__ int lds[MS_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n_kfs;
+  const int tid = threadIdx.x, n = A.n_kfs;
   for (int k = tid; k < n; k += MS_THREADS) {
     int c = 0;
     for (int j = 0; j < A.n_chunk; ++j) c += A.chunk_count[k * A.n_chunk + j];
@@ -435,35 +414,22 @@ __global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
   const int n_fixed = fixed.total[0], n_obs = n_loc + n_fixed;
   for (int k = n_fixed + tid; k < n; k += MS_THREADS) A.fixed_kf[k] = -1;
   __syncthreads();                                                         // fixed_kf is read below by other threads than wrote it
-  int carry = 0;
-  for (int o0 = 0; o0 < n_obs; o0 += MS_THREADS) {                         // exclusive scan of the counts in observer order
+  BlockScan<MS_THREADS> start(lds);
+  for (int o0 = 0; o0 < n_obs; o0 += MS_THREADS) {                         // exclusive scan of the counts in observer order (n_obs is the block's)
     const int o = o0 + tid;
     const int k = o >= n_obs ? -1 : o < n_loc ? A.local_kf[o] : A.fixed_kf[o - n_loc];
-    const int c = k >= 0 ? A.kf_count[k] : 0;
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    __syncthreads();                                                       // (the previous round's totals are no longer read)
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int v = 0; v < MS_THREADS / 64; ++v) { const int t = lds[v]; before += v < wave ? t : 0; all += t; }
-    if (k >= 0) A.obs_base[k] = carry + before + incl - c;
-    carry += all;
+    const int at = start.round(k >= 0 ? A.kf_count[k] : 0);
+    if (k >= 0) A.obs_base[k] = at;
   }
-  if (tid == 0) { A.counts[0] = n_loc - 1; A.counts[1] = 1 + n_fixed; A.counts[2] = A.list_off[1]; A.counts[3] = carry; }
+  if (tid == 0) { A.counts[0] = n_loc - 1; A.counts[1] = 1 + n_fixed; A.counts[2] = A.list_off[1]; A.counts[3] = start.total; }
 }
 
 // (chunk, keyframe): ordered compaction of the chunk's counted features behind the observer's earlier chunks
 __global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
   __shared__ int wave_tot[MS_THREADS / 64];
-  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.y, tid = threadIdx.x;
   const int role = A.role[k];
-  if (role == BAC_NONE || A.kf_count[k] == 0) return;                      // (the same in every thread)
+  if (role == BAC_NONE || A.kf_count[k] == 0) return;                      // (the same in every thread: k is the block's, both written by an earlier launch)
   const BacKf kf = A.kfs[k];
   int base = A.obs_base[k];
   for (int j = 0; j < (int)blockIdx.x; ++j) base += A.chunk_count[k * A.n_chunk + j];
@@ -471,12 +437,10 @@ __global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
   int mp[MS_PER], n = 0;
 #pragma unroll
   for (int j = 0; j < MS_PER; ++j) { mp[j] = bac_mp_idx(A, kf, p0 + j); n += mp[j] >= 0; }
-  int incl = n;                                                            // inclusive scan of the threads' counts over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
+  // Not BlockScan: its barrier in front of the store, which this single use of wave_tot does not need, measured 0.02 to 0.17 us of
+  // 7 to 9 us in every row (profiles/block_scan_ab.txt).  The parent's text, with the shared wave step.
+  const int lane = tid & 63, wave = tid >> 6;
+  const int incl = wave_inclusive_scan(n);
   if (lane == 63) wave_tot[wave] = incl;
   __syncthreads();
   size_t o = (size_t)base + (incl - n);
@@ -537,6 +501,21 @@ int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const 
   return ORBX_OK;
 }
 
+// keyframe t of a selection or covisibility call: not null, of this handle, its slot table (if it has one) of this store
+int ms_check_keyframe(orbx_handle* h, const char* who, const orbx_map_points* mp, const orbx_keyframe* kf, int t) {
+  if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
+  if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+  return ORBX_OK;
+}
+
+// the list outputs of a selection whose lists hold at most `total` rows (src_missing: the slot form without its source array)
+int ms_check_list_outputs(orbx_handle* h, const char* who, int total, const int* d_list_off, const int* d_list_slot, const double* d_positions,
+                          const uint8_t* d_mp_desc, bool src_missing = false) {
+  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15) || (total > 0 && src_missing))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  return ORBX_OK;
+}
+
 // What a selection call is, checked and sized on the host: per frame the candidates and the bound of its list.
 struct SelPlan {
   std::vector<MapSeg> segs;
@@ -559,8 +538,7 @@ int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int sour
       long long c = 0;
       for (int t = kf_offsets[b]; t < kf_offsets[b + 1]; ++t) {
         const orbx_keyframe* kf = kfs[t];
-        if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
-        if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+        if (int rc = ms_check_keyframe(h, who, mp, kf, t)) return rc;
         P.segs.push_back(MapSeg{kf->slot_store ? kf->d_mp_slot : nullptr, (int)c, kf->n});
         c += kf->n;
         if (c >= MS_EMPTY) return orbx_fail(h, ORBX_ERR_INVALID, "%s: frame %d has too many candidates", who, b);
@@ -630,9 +608,7 @@ int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int 
   const int total = P.bound_off[(size_t)B];
   if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (the sum over the frames of their candidates, "
                                          "per frame at most the capacity where keyframes are the source)", who, list_cap, total);
-  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15) ||
-      (source == ORBX_MAP_SOURCE_SLOTS && total > 0 && !d_src_slots))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  if (int rc = ms_check_list_outputs(h, who, total, d_list_off, d_list_slot, d_positions, d_mp_desc, source == ORBX_MAP_SOURCE_SLOTS && !d_src_slots)) return rc;
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t Bz = (size_t)B;
   Carve up;
@@ -673,8 +649,7 @@ int cov_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_k
   P.kfs.resize((size_t)n_kfs);
   for (int t = 0; t < n_kfs; ++t) {
     const orbx_keyframe* kf = kfs[t];
-    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
-    if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+    if (int rc = ms_check_keyframe(h, who, mp, kf, t)) return rc;
     P.kfs[(size_t)t] = CovKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, 0};
     P.max_n = std::max(P.max_n, kf->n);
   }
@@ -800,8 +775,7 @@ int local_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, i
   const int total = P.bound_off[(size_t)B];
   if (list_cap < total) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the lists' bound %d (per frame the reference keyframe's features plus the "
                                          "n_best largest of the others', at most the capacity)", who, list_cap, total);
-  if (!d_list_off || (total > 0 && (!d_list_slot || !d_positions || !d_mp_desc)) || ((uintptr_t)d_mp_desc & 15))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc is 16-byte aligned)", who);
+  if (int rc = ms_check_list_outputs(h, who, total, d_list_off, d_list_slot, d_positions, d_mp_desc)) return rc;
   CovSegs sg{P.seg_off.data(), d_local_kf, nullptr, nullptr, nullptr};
   if (int rc = cov_enqueue(h, mp, P.C, B, ref_kf, n_best, nullptr, nullptr, nullptr, &sg)) return rc;
   return ms_select_launch(h, mp, ORBX_MAP_SOURCE_KEYFRAMES, B, P.max_cand, sg.d_segs, sg.d_seg_off, sg.d_n_cand, nullptr, nullptr, d_list_off, d_list_slot,

@@ -61,29 +61,16 @@ __global__ __launch_bounds__(SB_THREADS) void stereo_bucket_kernel(const orbx_ke
                                                                    float2* __restrict__ sxy /*[pair][cap]*/) {
   __shared__ int cnt[SB_ROWS];
   __shared__ int wsum[SB_THREADS / 64];
-  const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int pair = blockIdx.x, tid = threadIdx.x;
   const orbx_keypoint* kpR = kp + (size_t)(2 * pair + 1) * cap;
   const int nR = min(nkp[2 * pair + 1], cap);
   for (int i = tid; i < SB_ROWS; i += SB_THREADS) cnt[i] = 0;
   __syncthreads();
   for (int i = tid; i < nR; i += SB_THREADS) atomicAdd(&cnt[row_bucket(kpR[i].y)], 1);
   __syncthreads();
-  // exclusive scan of 4096 counters: 4 per thread, wave scan, cross-wave offsets
-  int c[4], tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { c[k] = cnt[4 * tid + k]; tot += c[k]; }
-  int inc = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = inc - tot;
-  for (int wv = 0; wv < wave; ++wv) base += wsum[wv];
-  __syncthreads();
   int* bs = bstart + (size_t)pair * (SB_ROWS + 1);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { bs[4 * tid + k] = base; cnt[4 * tid + k] = base; base += c[k]; }
-  if (tid == SB_THREADS - 1) bs[SB_ROWS] = base;
+  const int total = block_counter_scan<SB_THREADS, SB_ROWS / SB_THREADS, false>(cnt, wsum, [&](int i, int start) { bs[i] = start; });
+  if (tid == SB_THREADS - 1) bs[SB_ROWS] = total;          // (round<false>: the last thread holds the total)
   __syncthreads();
   for (int i = tid; i < nR; i += SB_THREADS) {
     const float x = kpR[i].x, y = kpR[i].y;
@@ -249,26 +236,15 @@ __global__ __launch_bounds__(SML_THREADS) void stereo_match_lds_kernel(
   if (FUSED) {
     // counting sort of the right keypoints by image row (stereo_bucket_kernel's steps; the order inside a bucket is what the atomics give)
     const orbx_keypoint* kpR = kpL + cap;
-    static_assert(SB_ROWS == 4 * SML_THREADS, "four counters per thread in the scan");
-    const int lane = tid & 63, wave = tid >> 6;
+    static_assert(SB_ROWS % SML_THREADS == 0, "whole counters per thread in the scan");
     for (int i = tid; i < SB_ROWS; i += SML_THREADS) s_cur[i] = 0;
     __syncthreads();
     for (int i = tid; i < nR; i += SML_THREADS) atomicAdd(&s_cur[row_bucket(kpR[i].y)], 1);
     __syncthreads();
-    int c[4], tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { c[k] = s_cur[4 * tid + k]; tot += c[k]; }
-    int inc = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-    int* wsum = reinterpret_cast<int*>(s_tmp);                                          // (free until the rounds write their results)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = inc - tot;
-    for (int wv = 0; wv < wave; ++wv) base += wsum[wv];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { s_bs[4 * tid + k] = base; s_cur[4 * tid + k] = base; base += c[k]; }
-    if (tid == SML_THREADS - 1) s_bs[SB_ROWS] = base;
+    // (FUSED is the kernel's and nL the pair's: every thread of the block is here.)  The wave totals lie in s_tmp, free until the rounds write
+    // their results.
+    const int total = block_counter_scan<SML_THREADS, SB_ROWS / SML_THREADS, false>(s_cur, reinterpret_cast<int*>(s_tmp), [&](int i, int start) { s_bs[i] = start; });
+    if (tid == SML_THREADS - 1) s_bs[SB_ROWS] = total;
     __syncthreads();
     for (int i = tid; i < nR; i += SML_THREADS) {
       const float x = kpR[i].x, y = kpR[i].y;
@@ -553,7 +529,7 @@ __device__ __forceinline__ void tri_grid_build_body(const orbx_keypoint* __restr
                                                     uint8_t* __restrict__ taken) {
   __shared__ int cnt[4096];
   __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int ncell = cols * rows;
   for (int i = tid; i < 4096; i += 1024) cnt[i] = 0;
   __syncthreads();
@@ -565,20 +541,9 @@ __device__ __forceinline__ void tri_grid_build_body(const orbx_keypoint* __restr
     atomicAdd(&cnt[cell], 1);
   }
   __syncthreads();
-  int c4[4], tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { c4[k] = cnt[4 * tid + k]; tot += c4[k]; }
-  int inc = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = inc - tot;
-  for (int wv = 0; wv < wave; ++wv) base += wsum[wv];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { if (4 * tid + k <= ncell) cell_start[4 * tid + k] = base; cnt[4 * tid + k] = base; base += c4[k]; }
-  if (tid == 1023 && ncell == 4096) cell_start[4096] = base;           // 64 x 64: the end sentinel lies past the last thread's four slots
+  // cell_start[0 .. ncell): the cells' starts; cell_start[ncell]: the total, whatever the grid's size (the counters from ncell on are zero)
+  const int total = block_counter_scan<1024, 4, false>(cnt, wsum, [&](int i, int start) { if (i < ncell) cell_start[i] = start; });
+  if (tid == 1023) cell_start[ncell] = total;                          // (round<false>: the last thread holds the total)
   __syncthreads();
   for (int i = tid; i < n; i += 1024) sorted_idx[atomicAdd(&cnt[cell_of[i]], 1)] = i;
 }
@@ -743,7 +708,7 @@ __global__ __launch_bounds__(256) void tri_resolve_kernel(TriArgs A, int* __rest
 __global__ __launch_bounds__(1024) void tri_grid_build_batch_kernel(const TriBatchItem* __restrict__ items) {
   const TriBatchItem& it = items[blockIdx.x];
   const int n2 = it.A.n2;
-  if (it.A.rng_lo) {                                                      // FeatureVector form: no grid, only the taken flags (:606-608)
+  if (it.A.rng_lo) {                                                      // FeatureVector form (the item's: the whole block): no grid, only the taken flags (:606-608)
     for (int i = threadIdx.x; i < n2; i += 1024) it.A.taken[i] = it.mp2[i];
     return;
   }

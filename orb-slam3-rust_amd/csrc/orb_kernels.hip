@@ -31,6 +31,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "block_dev.hpp"
 #include "orbx_internal.hpp"
 
 namespace {
@@ -1154,26 +1155,9 @@ __device__ __forceinline__ void rank_pass(const unsigned long long* __restrict__
 // entry x | y << 16 | slot-in-level << 32.  describe_fused_kernel walks that list, so the 16 keypoints of a block are
 // neighbours in one band and share the cache lines of their patch rows (results go to the keypoint's slot: the order
 // of processing is free).
-// exclusive prefix sum over skey[0..1024) in place (all RK_NT threads; skey[1024..1024+RK_NT/64) is scratch): 1024 / RK_NT counters per
-// thread, scan inside each wave, totals of the waves before
-__device__ __forceinline__ void rank_prefix_1024(unsigned* skey, int tid) {
-  constexpr int CE = 1024 / RK_NT;
-  unsigned cv[CE], tot = 0;
-#pragma unroll
-  for (int q = 0; q < CE; ++q) { cv[q] = skey[CE * tid + q]; tot += cv[q]; }
-  unsigned inc = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned t = __shfl_up(inc, off);
-    if ((tid & 63) >= off) inc += t;
-  }
-  if ((tid & 63) == 63) skey[1024 + (tid >> 6)] = inc;
-  __syncthreads();
-  unsigned run = inc - tot;
-  for (int w = 0; w < (tid >> 6); ++w) run += skey[1024 + w];
-#pragma unroll
-  for (int q = 0; q < CE; ++q) { skey[CE * tid + q] = run; run += cv[q]; }
-}
+// exclusive prefix sum over skey[0..1024) in place (all RK_NT threads; skey[1024..1024+RK_NT/64) is scratch): block_dev.hpp's counter scan,
+// 1024 / RK_NT counters per thread; nobody needs the total
+__device__ __forceinline__ void rank_prefix_1024(unsigned* skey) { block_counter_scan<RK_NT, 1024 / RK_NT, false>(skey, skey + 1024); }
 
 // With describe tiles (g.dt_total > 0) the spatial order is by describe tile — cell = tile index inside the level — and the kernel also
 // leaves each tile's (begin, end) range of that list in tile_rng: describe_tile_kernel's blocks own one tile each.
@@ -1327,7 +1311,7 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
       }
     }
     __syncthreads();
-    rank_prefix_1024(skey, tid);
+    rank_prefix_1024(skey);                                        // (M and Ksel are the block's — every wave reads them off the same histogram: all threads are here)
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < KE; ++e) {
@@ -1367,7 +1351,7 @@ __global__ __launch_bounds__(RK_NT) void rank_select_kernel(OrbGeom g, int n_img
   __syncthreads();
   for (unsigned i = tid; i < K; i += RK_NT) atomicAdd(&skey[tile_of((unsigned)out[i])], 1u);
   __syncthreads();
-  rank_prefix_1024(skey, tid);
+  rank_prefix_1024(skey);
   __syncthreads();
   for (unsigned i = tid; i < K; i += RK_NT) {
     const unsigned long long v = out[i];
