@@ -1215,6 +1215,70 @@ int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_conf
                       const orbx_keyframe* const* kfs, int cur, orbx_should_stop_fn should_stop, void* user, int* local_kf_out,
                       double* poses_wc_out, int* counts_out, int* iterations, double* initial_error, double* final_error);
 
+/* ---- observations from the resident map: lists, refresh, redundancy (map_point.rs:140-156; local_mapper.rs:421-469, :487-583) ----
+ * mp.observations — which keyframes see a point, and at which feature — is the inverse of the slot tables.  Like the covisibility
+ * graph it is derived from the tables where they lie instead of maintained per association.  kfs [n_kfs] are the keyframes the
+ * caller considers (host array, copied before the call returns; is_bad filtering = leaving a keyframe out); every keyframe index
+ * below is a position in kfs[].
+ *   [spec] obs(k) is covisibility's: the distinct slots s of kfs[k]'s table with 0 <= s < capacity and live[s] when the kernels run.
+ *     The feature that observes s in k is the FIRST feature that names it.  (The reference's HashMap<KeyFrameId, usize> holds one
+ *     feature per keyframe and the last add_observation wins; here the choice is fixed.  Where every point is associated once per
+ *     keyframe the two agree.)  A keyframe without a table observes nothing.
+ *   [spec] observations(s) = the pairs (k, feat) with s in obs(k), by ascending k.  (The reference iterates a HashMap;
+ *     orbx_refresh_map_points takes "the order as given", and this is the order given.)
+ *   [spec] n_observers(s) = |observations(s)|.
+ * Every call below has a _device form — asynchronous on the handle's stream, no host synchronisation inside, outputs in device
+ * memory — and a host form: synchronous, one download, outputs packed.  The store's tables are left as they were found and no
+ * launch is sized by the capacity: a call costs what its keyframes and points cost.  Every output is the same bytes on every run.
+ * ORBX_ERR_INVALID before anything is enqueued, the store and the outputs untouched: n_kfs > 65535, a keyframe of another handle or
+ * whose table is bound to another store, and what each call adds.
+ *
+ * orbx_map_observations[_device]: slots [M] are the points asked for, a HOST array in both forms, checked like orbx_map_points_set's:
+ * ORBX_ERR_INVALID for a slot outside [0, capacity), a slot listed twice, or a slot that is not live.  Point p owns rows
+ * [obs_start[p], obs_start[p+1]) of obs_kf / obs_feat; obs_start [M+1], obs_start[0] = 0.  obs_cap, the rows obs_kf and obs_feat
+ * hold, must reach the sum of the feature counts of kfs[] (else ORBX_ERR_INVALID); nothing is ever truncated.  The outputs are the
+ * arguments orbx_refresh_map_points_device takes, with T = n_kfs.  The observation test of map-point culling (map_point.rs:140-156,
+ * local_mapper.rs:421-469) is obs_start[p+1] - obs_start[p] < min_observations; found_ratio is 1.0 in the reference (nothing
+ * increments its counters); the grace period, ids and is_bad stay with the caller.
+ *
+ * orbx_map_refresh_points[_device] = phase 4 of search_in_neighbors on the resident map: the lists above for slots [M] (HOST array,
+ * checked as above); then orbx_refresh_map_points's launches, unchanged, on the resident keyframes' own descriptors, their camera
+ * centres (the translation of pose_wc, as orbx_keyframe_refresh_map_points takes them) and the points' positions and current
+ * descriptors read from the store; then the chosen descriptors written back into the store's slots through orbx_map_points_set's
+ * scatter, descriptors only.  mp_desc [M][32] out, normals [M][3] in/out (the store keeps none), min_distance / max_distance [M],
+ * records [M] (device form: mp_desc and normals 8-byte aligned).  Every output equals, byte for byte,
+ * orbx_keyframe_refresh_map_points called with the specification's lists and the store's rows; afterwards
+ * orbx_map_points_download of slots gives mp_desc.  Positions and live bytes are untouched.  M = 0: ORBX_OK.
+ *
+ * orbx_map_keyframe_redundancy[_device] = the decision of cull_keyframes (local_mapper.rs:487-583) for n_cand candidates at once; the
+ * reference collects to_cull before it removes anything, so every candidate's decision is independent.  cand [n_cand] is a HOST
+ * array of positions in kfs[] (an index may repeat); the caller leaves out the current keyframe, roots and bad keyframes (:516-533)
+ * and finds "covisible with current" by orbx_map_covisibility's weights > 0.
+ *   [spec] total(c) = the features of kfs[c] whose table entry s satisfies 0 <= s < capacity and live[s]; every feature counts,
+ *     repeats of a slot included (:539-547 walks map_point_ids).
+ *   [spec] redundant(c) = those of them with n_observers(s) - 1 >= min_observations (c itself is one of the observers, :549-555).
+ *   [spec] cull(c) = total > 0 && (double)redundant / (double)total > threshold: one IEEE f64 division (:561-565; 0.9, or 0.5).
+ *   A candidate without a table gives 0, 0, 0.
+ * Outputs total / redundant [n_cand] int32, cull [n_cand] u8.  ORBX_ERR_INVALID also for an index outside [0, n_kfs),
+ * min_observations < 0, n_cand > 65535.  n_cand = 0: nothing is done, ORBX_OK.
+ * Still the caller's: removal itself (IMU preintegration merging, the spanning tree, ids), the fuse and merge phases of
+ * search_in_neighbors, normals. */
+int orbx_map_observations_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
+                                 int obs_cap, int* d_obs_start, int* d_obs_kf, int* d_obs_feat);
+int orbx_map_observations(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
+                          int obs_cap, int* obs_start, int* obs_kf, int* obs_feat);
+int orbx_map_refresh_points_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
+                                   double scale_range, uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance,
+                                   orbx_mp_refresh_record* d_records);
+int orbx_map_refresh_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
+                            double scale_range, uint8_t* mp_desc, double* normals, double* min_distance, double* max_distance,
+                            orbx_mp_refresh_record* records);
+int orbx_map_keyframe_redundancy_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand,
+                                        const int* cand, int min_observations, double threshold, int* d_total, int* d_redundant,
+                                        uint8_t* d_cull);
+int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand,
+                                 const int* cand, int min_observations, double threshold, int* total, int* redundant, uint8_t* cull);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

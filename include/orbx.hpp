@@ -1116,6 +1116,89 @@ inline std::optional<MapLocalBAResult> map_local_ba(Handle& h, const CameraModel
   return r;
 }
 
+// ---- observations from the resident map (orbx.h, "observations from the resident map"): lists, refresh, redundancy ----
+// mp.observations derived from the slot tables.  Every keyframe index is a position in the `keyframes` the caller hands over
+// (is_bad ones left out); slots are live, none twice.
+struct MapObservations {
+  std::vector<int> obs_start;                          // [M + 1]: point p owns rows [obs_start[p], obs_start[p + 1])
+  std::vector<int> obs_kf, obs_feat;                   // the observing keyframes, ascending, and the first feature of each that names the point
+  int n_observers(size_t p) const { return obs_start[p + 1] - obs_start[p]; }
+  // MapPoint::should_cull's observation half (map_point.rs:140-156; found_ratio is 1.0: nothing increments its counters)
+  bool too_few_observers(size_t p, int min_observations) const { return n_observers(p) < min_observations; }
+};
+
+// rows obs_kf / obs_feat must hold: every feature of `keyframes`
+inline int map_observations_bound(Handle& h, const std::vector<const orbx_keyframe*>& keyframes) {
+  size_t all = 0;
+  for (const orbx_keyframe* k : keyframes) {
+    int n = 0;
+    h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+    all += (size_t)n;
+  }
+  return (int)all;
+}
+
+// orbx_map_observations_device: d_obs_start [slots.size() + 1], d_obs_kf / d_obs_feat [obs_cap] are the caller's device memory — the
+// arguments of orbx_refresh_map_points_device; asynchronous.
+inline void map_observations_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& slots, int obs_cap,
+                                    int* d_obs_start, int* d_obs_kf, int* d_obs_feat) {
+  h.check(orbx_map_observations_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)slots.size(), slots.data(), obs_cap, d_obs_start, d_obs_kf,
+                                       d_obs_feat));
+}
+
+// orbx_map_observations: the same into host vectors cut to their sizes, synchronous.
+inline MapObservations map_observations(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& slots) {
+  const int cap = map_observations_bound(h, keyframes);
+  MapObservations o;
+  o.obs_start.assign(slots.size() + 1, 0); o.obs_kf.resize((size_t)std::max(cap, 1)); o.obs_feat.resize((size_t)std::max(cap, 1));
+  h.check(orbx_map_observations(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)slots.size(), slots.data(), cap, o.obs_start.data(),
+                                o.obs_kf.data(), o.obs_feat.data()));
+  o.obs_kf.resize((size_t)o.obs_start.back()); o.obs_feat.resize((size_t)o.obs_start.back());
+  return o;
+}
+
+// orbx_map_refresh_points: phase 4 of search_in_neighbors (search_in_neighbors.rs:139-150) on the resident map.  normals [M] are
+// the points' current normals (the store keeps none); the chosen descriptors are in the result and in the store afterwards.
+inline MapPointRefresh map_refresh_points(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& slots,
+                                          double scale_range, const std::vector<std::array<double, 3>>& normals) {
+  const size_t M = slots.size();
+  if (normals.size() != M) throw Error(ORBX_ERR_INVALID, "map_refresh_points: one normal per slot");
+  MapPointRefresh r{std::vector<uint8_t>(32 * M), normals, std::vector<double>(M), std::vector<double>(M), std::vector<orbx_mp_refresh_record>(M)};
+  h.check(orbx_map_refresh_points(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)M, slots.data(), scale_range, r.mp_descriptors.data(),
+                                  M ? r.normals[0].data() : nullptr, r.min_distance.data(), r.max_distance.data(), r.records.data()));
+  return r;
+}
+// orbx_map_refresh_points_device: d_mp_desc [M][32] out, d_normals [M][3] in/out (both 8-byte aligned), d_min_distance /
+// d_max_distance [M], d_records [M] are the caller's device memory; asynchronous.
+inline void map_refresh_points_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& slots,
+                                      double scale_range, uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance,
+                                      orbx_mp_refresh_record* d_records) {
+  h.check(orbx_map_refresh_points_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)slots.size(), slots.data(), scale_range, d_mp_desc,
+                                         d_normals, d_min_distance, d_max_distance, d_records));
+}
+
+// cull_keyframes' decision (local_mapper.rs:487-583) for keyframes[candidates[i]]: the caller leaves out the current keyframe,
+// roots and bad keyframes, and removes what is culled (IMU preintegration merging, the spanning tree and ids are its own).
+struct KeyFrameRedundancy {
+  std::vector<int> total, redundant;                   // [candidates]: features with a live point; those whose point has min_observations other observers
+  std::vector<uint8_t> cull;                           // redundant / total > threshold
+};
+inline KeyFrameRedundancy map_keyframe_redundancy(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes,
+                                                  const std::vector<int>& candidates, int min_observations = 3, double threshold = 0.9) {
+  const size_t n = candidates.size();
+  KeyFrameRedundancy r{std::vector<int>(n), std::vector<int>(n), std::vector<uint8_t>(n)};
+  h.check(orbx_map_keyframe_redundancy(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)n, candidates.data(), min_observations, threshold,
+                                       r.total.data(), r.redundant.data(), r.cull.data()));
+  return r;
+}
+// orbx_map_keyframe_redundancy_device: d_total / d_redundant [candidates.size()] int32 and d_cull [candidates.size()] u8 are the
+// caller's device memory; asynchronous.
+inline void map_keyframe_redundancy_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& candidates,
+                                           int min_observations, double threshold, int* d_total, int* d_redundant, uint8_t* d_cull) {
+  h.check(orbx_map_keyframe_redundancy_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)candidates.size(), candidates.data(),
+                                              min_observations, threshold, d_total, d_redundant, d_cull));
+}
+
 // ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
 // One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
 // validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).

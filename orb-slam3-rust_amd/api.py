@@ -102,6 +102,8 @@ ABI_SYMBOLS = [
     "orbx_map_track_frames_device", "orbx_map_track_frames", "orbx_map_track_reference_device",
     "orbx_map_covisibility_device", "orbx_map_covisibility", "orbx_map_track_local_device", "orbx_map_track_local",
     "orbx_map_collect_ba_window_device", "orbx_map_collect_ba_window", "orbx_ba_solve_visual_obs32_device", "orbx_map_local_ba",
+    "orbx_map_observations_device", "orbx_map_observations", "orbx_map_refresh_points_device", "orbx_map_refresh_points",
+    "orbx_map_keyframe_redundancy_device", "orbx_map_keyframe_redundancy",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 
@@ -1335,6 +1337,104 @@ class Handle:
         self._check(rc)
         K, F, M, N = (int(x) for x in counts)
         return dict(counts=counts, local_kf=lk, fixed_kf=fx[:F - 1].copy(), list_slot=ls[:M].copy(), positions=pos[:M].copy(), obs32=obs[:N].copy())
+
+    # ---- observations from the resident map (include/orbx.h, "observations from the resident map") ----
+    @staticmethod
+    def _obs_slots(slots):
+        a = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        return a, (a if len(a) else np.zeros(1, np.int32))
+
+    def map_observations_device(self, mp: "MapPointStore", keyframes, slots, device=None):
+        """mp.observations of the points in `slots` (a host array of live slots, none twice), derived on the device from the slot
+        tables of `keyframes` (orbx_map_observations_device).  Returns a dict of CUDA tensors: obs_start [M+1] int32, obs_kf / obs_feat
+        [cap] int32 with cap = the keyframes' feature counts summed; point p owns rows obs_start[p]..obs_start[p+1]: the keyframes
+        (positions in `keyframes`, ascending) that observe it and the first feature of each that names it.  The arguments of
+        refresh_map_points_device.  Asynchronous on the handle's stream."""
+        import torch
+        a, ap = self._obs_slots(slots)
+        cap = int(sum(k.n for k in keyframes))
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        o = dict(obs_start=mk(len(a) + 1), obs_kf=mk(max(cap, 1)), obs_feat=mk(max(cap, 1)))
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_observations_device(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(a)), _vp(ap), C.c_int(cap),
+                                                         _vp(o["obs_start"]), _vp(o["obs_kf"]), _vp(o["obs_feat"])))
+        o["obs_kf"] = o["obs_kf"][:cap]; o["obs_feat"] = o["obs_feat"][:cap]
+        return o
+
+    def map_observations(self, mp: "MapPointStore", keyframes, slots):
+        """The host form (orbx_map_observations), synchronous: (obs_start [M+1], obs_kf [N], obs_feat [N]) as numpy int32 arrays cut
+        to N = obs_start[M].  A point's observer count, obs_start[p+1] - obs_start[p], is what map-point culling compares with
+        min_observations."""
+        a, ap = self._obs_slots(slots)
+        cap = int(sum(k.n for k in keyframes))
+        os_ = np.zeros(len(a) + 1, np.int32); ok = np.zeros(max(cap, 1), np.int32); of = np.zeros(max(cap, 1), np.int32)
+        self._check(self._L.orbx_map_observations(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(a)), _vp(ap), C.c_int(cap),
+                                                  _vp(os_), _vp(ok), _vp(of)))
+        N = int(os_[-1])
+        return os_, ok[:N].copy(), of[:N].copy()
+
+    def map_refresh_points_device(self, mp: "MapPointStore", keyframes, slots, scale_range, normals):
+        """Phase 4 of search_in_neighbors on the resident map (orbx_map_refresh_points_device): the observation lists of `slots` from
+        the tables, refresh_map_points' kernels on the keyframes' own descriptors and camera centres and the store's rows, and the
+        chosen descriptors written back into the store.  normals: CUDA tensor [M,3] f64, updated IN PLACE (the store keeps none).
+        Returns a dict of CUDA tensors: mp_desc [M,32] u8, min_distance / max_distance [M] f64, records [M,16] u8
+        (MP_REFRESH_RECORD).  Asynchronous on the handle's stream."""
+        import torch
+        a, ap = self._obs_slots(slots)
+        M = len(a)
+        if tuple(normals.shape) != (M, 3) or normals.dtype != torch.float64 or not normals.is_contiguous():
+            raise ValueError("map_refresh_points_device: normals is a contiguous [M,3] f64 tensor")
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=normals.device)
+        o = dict(mp_desc=mk((max(M, 1), 32), torch.uint8), min_distance=mk(max(M, 1), torch.float64), max_distance=mk(max(M, 1), torch.float64),
+                 records=mk((max(M, 1), MP_REFRESH_RECORD.itemsize), torch.uint8))
+        self._after_torch(normals, *o.values())
+        self._check(self._L.orbx_map_refresh_points_device(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(M), _vp(ap),
+                                                           C.c_double(scale_range), _vp(o["mp_desc"]), _vp(normals), _vp(o["min_distance"]),
+                                                           _vp(o["max_distance"]), _vp(o["records"])))
+        return {k: v[:M] for k, v in o.items()}
+
+    def map_refresh_points(self, mp: "MapPointStore", keyframes, slots, scale_range, normals) -> "MapPointRefresh":
+        """The host form (orbx_map_refresh_points), synchronous: normals [M,3] are the points' current normals (not modified); the
+        result is KeyFrame.refresh_map_points' on the derived lists and the store's rows, byte for byte, and the store holds its
+        mp_desc afterwards."""
+        a, ap = self._obs_slots(slots)
+        M = len(a)
+        nr = np.array(normals, np.float64).reshape(-1, 3)
+        if len(nr) != M:
+            raise ValueError("map_refresh_points: one normal per slot")
+        out = MapPointRefresh(np.zeros((M, 32), np.uint8), nr, np.zeros(M), np.zeros(M), np.zeros(M, MP_REFRESH_RECORD))
+        self._after_torch()
+        self._check(self._L.orbx_map_refresh_points(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(M), _vp(ap), C.c_double(scale_range),
+                                                    _vp(out.mp_desc) if M else None, _vp(out.normals) if M else None, _vp(out.min_distance) if M else None,
+                                                    _vp(out.max_distance) if M else None, _vp(out.records) if M else None))
+        return out
+
+    def map_keyframe_redundancy_device(self, mp: "MapPointStore", keyframes, candidates, min_observations=3, threshold=0.9, device=None):
+        """cull_keyframes' decision (local_mapper.rs:487-583) for keyframes[c], c in candidates (orbx_map_keyframe_redundancy_device).
+        Returns a dict of CUDA tensors: total [n_cand] int32 (features with a live point), redundant [n_cand] int32 (those whose point
+        has min_observations other observers among `keyframes`), cull [n_cand] u8 (redundant / total > threshold).  Asynchronous."""
+        import torch
+        c = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+        n = len(c)
+        dev = device or torch.device("cuda", self.device)
+        o = dict(total=torch.zeros(max(n, 1), dtype=torch.int32, device=dev), redundant=torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
+                 cull=torch.zeros(max(n, 1), dtype=torch.uint8, device=dev))
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_keyframe_redundancy_device(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(n),
+                                                                _vp(c if n else np.zeros(1, np.int32)), C.c_int(int(min_observations)), C.c_double(threshold),
+                                                                _vp(o["total"]), _vp(o["redundant"]), _vp(o["cull"])))
+        return {k: v[:n] for k, v in o.items()}
+
+    def map_keyframe_redundancy(self, mp: "MapPointStore", keyframes, candidates, min_observations=3, threshold=0.9):
+        """The host form (orbx_map_keyframe_redundancy), synchronous: (total int32 [n_cand], redundant int32 [n_cand], cull u8 [n_cand])."""
+        c = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+        n = len(c)
+        total = np.zeros(max(n, 1), np.int32); red = np.zeros(max(n, 1), np.int32); cull = np.zeros(max(n, 1), np.uint8)
+        self._check(self._L.orbx_map_keyframe_redundancy(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(n),
+                                                         _vp(c if n else np.zeros(1, np.int32)), C.c_int(int(min_observations)), C.c_double(threshold), _vp(total),
+                                                         _vp(red), _vp(cull)))
+        return total[:n], red[:n], cull[:n]
 
     def ba_solve_visual_obs32_device(self, camera, cfg, poses_cw, fixed_cw, points, obs32, n_obs, should_stop=None):
         """ba_solve_visual with the observations in device memory (orbx_ba_solve_visual_obs32_device): obs32 is a CUDA tensor whose

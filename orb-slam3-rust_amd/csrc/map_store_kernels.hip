@@ -42,6 +42,9 @@
 //   bac_restore_kernel  index[slot] = EMPTY again: the call leaves the table as it found it
 // orbx_map_local_ba hands the observations to the solver where they lie (ba_kernels.hip: BaWinHost::obs_on_device) and scatters the
 // optimised positions back through map_scatter_kernel.
+// mp.observations (map_point.rs:140-156), the inverse of the slot tables, is derived the same way for the points a call names:
+// the lists behind orbx_map_observations and orbx_map_refresh_points (search_in_neighbors.rs:139-150) and the counts behind
+// orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
 // The sums, the ordered append and the scans of counts are block_dev.hpp's: every thread of a workgroup reaches each of them.
 #include <algorithm>
 #include <numeric>
@@ -560,18 +563,23 @@ int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int sour
   return ORBX_OK;
 }
 
+// the one fill of the first-sighting tables: calls leave them EMPTY
+int ms_reserve_first(orbx_handle* h, orbx_map_points* mp, size_t rows) {
+  const size_t need = 4 * rows * (size_t)mp->capacity;
+  if (mp->first.bytes < need) {
+    if (int rc = orbx_reserve(h, mp->first, need)) return rc;
+    ORBX_HIP(h, hipMemsetAsync(mp->first.p, MS_EMPTY & 0xff, mp->first.bytes, h->stream));
+  }
+  return ORBX_OK;
+}
+
 // The three launches on the handle's stream, every table already in device memory (uploaded by ms_select_enqueue, or written by
 // cov_seg_kernel); max_cand bounds every frame's candidates on the host.
 int ms_select_launch(orbx_handle* h, orbx_map_points* mp, int source, int B, int max_cand, const MapSeg* d_segs, const int* d_seg_off, const int* d_n_cand,
                      const int* d_src_slots, const int* d_src_off, int* d_list_off, int* d_list_slot, double* d_positions, uint8_t* d_mp_desc) {
   const size_t Bz = (size_t)B;
-  if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
-    const size_t need = 4 * Bz * (size_t)mp->capacity;
-    if (mp->first.bytes < need) {                                           // the one fill of the tables: calls leave them EMPTY
-      if (int rc = orbx_reserve(h, mp->first, need)) return rc;
-      ORBX_HIP(h, hipMemsetAsync(mp->first.p, MS_EMPTY & 0xff, mp->first.bytes, h->stream));
-    }
-  }
+  if (source == ORBX_MAP_SOURCE_KEYFRAMES)
+    if (int rc = ms_reserve_first(h, mp, Bz)) return rc;
   const int n_chunk = std::max(1, (max_cand + MS_CHUNK - 1) / MS_CHUNK);
   Carve ws;
   const size_t o_ca = ws.take(4 * Bz * (size_t)n_chunk * MS_CHUNK), o_cc = ws.take(4 * Bz * (size_t)n_chunk);
@@ -990,6 +998,394 @@ int ms_track_host(orbx_handle* h, const char* who, const orbx_camera* cam, const
   return ORBX_OK;
 }
 
+// ---- observations (include/orbx.h, "observations from the resident map"; map_point.rs:140-156, local_mapper.rs:421-469, :487-583) ----
+// mp.observations, the inverse of the slot tables, for the points a call names:
+//   obs_index_kernel      index[slot] = position of the slot in the call's list (row 0 of `first`, EMPTY between calls); count = 0
+//   obs_count_kernel      (chunk of a keyframe's features, keyframe) over the de-duplicated tables: an integer atomicAdd on the count
+//                         of every indexed point a feature names — a sum, whatever the execution order
+//   obs_part_kernel       per MS_CHUNK counts their sum; obs_scan_kernel: a chunk's base = the sums before it (block_sum), the
+//                         exclusive scan inside it (BlockScan) -> obs_start, and a copy of it as every point's cursor
+//   obs_append_kernel     the count kernel's walk again: (keyframe, feature) goes to the point's segment at atomicAdd(cursor), in
+//                         whatever order the hardware takes the features
+//   obs_rank_kernel       one thread per entry of a segment of at most OBS_SHORT: the keyframes of a segment are distinct, so the
+//                         number of smaller ones is the entry's place by ascending keyframe — that fixes the bytes
+//   obs_rank_long_kernel  a workgroup per longer point at a time, the segment's keyframes through LDS in tiles of MS_THREADS
+//   obs_restore_kernel    index[slot] = EMPTY again
+// Keyframe redundancy (cull_keyframes) needs the counts only: index, count, then
+//   red_count_kernel      (chunk of a candidate's features, candidate) over the table WITH repeats: the features whose slot is live,
+//                         and those of them whose point has min_observations other observers; block_sum -> the chunk's two sums
+//   red_tail_kernel       one thread per candidate: the chunks summed in order, total, redundant, cull (one f64 division)
+// and restore.  The candidates' distinct live slots are one frame's ORBX_MAP_SOURCE_KEYFRAMES selection, unchanged.
+
+constexpr int OBS_SHORT = 64;                    // longest segment obs_rank_kernel orders
+
+struct ObsArgs {
+  int capacity, n_kfs, n_chunk, min_obs;
+  const uint8_t* live; const CovKf* kfs;
+  const int* n_list; const int* list_slot;       // the call's points: *n_list slots, none twice
+  int* index;                                    // the store's first-sighting table, row 0: EMPTY outside the launches below
+  int* count; int* part; int* cursor;            // [points]; [chunks of points]; [points]
+  int* tmp_kf; int* tmp_feat;                    // the segments before they are ordered
+  int* obs_start; int* obs_kf; int* obs_feat;
+  const int* cand; int n_cand; double threshold; // redundancy
+  int* chunk_tot; int* total; int* redundant; uint8_t* cull;
+};
+
+__global__ __launch_bounds__(MS_THREADS) void obs_index_kernel(ObsArgs A) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i < *A.n_list) { A.index[A.list_slot[i]] = i; A.count[i] = 0; }
+}
+__global__ __launch_bounds__(MS_THREADS) void obs_restore_kernel(ObsArgs A) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i < *A.n_list) A.index[A.list_slot[i]] = MS_EMPTY;
+}
+
+// does feature i of `kf` observe a point of the call (the first feature of the keyframe that names it)?  -> its position, or -1
+__device__ __forceinline__ int obs_point(const ObsArgs& A, const CovKf& kf, int i) {
+  if (i >= kf.n) return -1;
+  const int s = kf.uniq[i];
+  if (s < 0 || s >= A.capacity || !A.live[s]) return -1;
+  const int p = A.index[s];
+  return p == MS_EMPTY ? -1 : p;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_count_kernel(ObsArgs A) {
+  const CovKf kf = A.kfs[blockIdx.y];
+  if (!kf.uniq) return;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    const int p = obs_point(A, kf, blockIdx.x * MS_CHUNK + j * MS_THREADS + threadIdx.x);
+    if (p >= 0) atomicAdd(&A.count[p], 1);
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_part_kernel(ObsArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int n = *A.n_list, p0 = blockIdx.x * MS_CHUNK + threadIdx.x * MS_PER;
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) c += p0 + j < n ? A.count[p0 + j] : 0;
+  c = block_sum<MS_THREADS>(c, wave_tot);
+  if (threadIdx.x == 0) A.part[blockIdx.x] = c;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_scan_kernel(ObsArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int n = *A.n_list, tid = threadIdx.x, p0 = blockIdx.x * MS_CHUNK + tid * MS_PER;
+  int before = 0;
+  for (int j = tid; j < (int)blockIdx.x; j += MS_THREADS) before += A.part[j];
+  const int base = block_sum<MS_THREADS>(before, wave_tot);
+  int c[MS_PER], mine = 0;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) { c[j] = p0 + j < n ? A.count[p0 + j] : 0; mine += c[j]; }
+  int at = BlockScan<MS_THREADS>(wave_tot, base).round(mine);
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    if (p0 + j < n) { A.obs_start[p0 + j] = at; A.cursor[p0 + j] = at; }
+    at += c[j];
+    if (p0 + j + 1 == n) A.obs_start[n] = at;
+  }
+  if (n == 0 && blockIdx.x == 0 && tid == 0) A.obs_start[0] = 0;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_append_kernel(ObsArgs A) {
+  const int k = blockIdx.y;
+  const CovKf kf = A.kfs[k];
+  if (!kf.uniq) return;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    const int i = blockIdx.x * MS_CHUNK + j * MS_THREADS + threadIdx.x;
+    const int p = obs_point(A, kf, i);
+    if (p < 0) continue;
+    const int at = atomicAdd(&A.cursor[p], 1);
+    A.tmp_kf[at] = k; A.tmp_feat[at] = i;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_rank_kernel(ObsArgs A) {
+  const int n = *A.n_list, e = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (e >= A.obs_start[n]) return;
+  int lo = 0, hi = n;                                                      // the point that owns e: the last one that starts at or before it
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (A.obs_start[mid] <= e) lo = mid + 1; else hi = mid;
+  }
+  const int s = A.obs_start[lo - 1], len = A.obs_start[lo] - s;
+  if (len > OBS_SHORT) return;
+  const int k = A.tmp_kf[e];
+  int rank = 0;
+  for (int j = 0; j < len; ++j) rank += A.tmp_kf[s + j] < k;
+  A.obs_kf[s + rank] = k; A.obs_feat[s + rank] = A.tmp_feat[e];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void obs_rank_long_kernel(ObsArgs A) {
+  __shared__ int tile[MS_THREADS];
+  const int n = *A.n_list, tid = threadIdx.x;
+  for (int p = blockIdx.x; p < n; p += gridDim.x) {                        // (p, s and len are the block's: every thread takes every barrier)
+    const int s = A.obs_start[p], len = A.obs_start[p + 1] - s;
+    if (len <= OBS_SHORT) continue;
+    for (int i0 = 0; i0 < len; i0 += MS_THREADS) {
+      const int i = i0 + tid;
+      const int k = i < len ? A.tmp_kf[s + i] : 0;
+      int rank = 0;
+      for (int j0 = 0; j0 < len; j0 += MS_THREADS) {
+        __syncthreads();
+        tile[tid] = j0 + tid < len ? A.tmp_kf[s + j0 + tid] : 0x7fffffff;
+        __syncthreads();
+        const int m = min(MS_THREADS, len - j0);
+        for (int t = 0; t < m; ++t) rank += tile[t] < k;
+      }
+      if (i < len) { A.obs_kf[s + rank] = k; A.obs_feat[s + rank] = A.tmp_feat[s + i]; }
+    }
+  }
+}
+
+// rows of the listed slots as the refresh reads them: positions [M][3] and the current descriptors [M][32]
+__global__ __launch_bounds__(MS_THREADS) void obs_gather_kernel(const int* slots, int n, const double* pos, const uint8_t* desc, double* out_pos, uint8_t* out_desc) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const size_t s = (size_t)slots[i];
+  out_pos[3 * (size_t)i] = pos[3 * s]; out_pos[3 * (size_t)i + 1] = pos[3 * s + 1]; out_pos[3 * (size_t)i + 2] = pos[3 * s + 2];
+  const uint32_t* d = (const uint32_t*)(desc + 32 * s);
+  uint32_t* q = (uint32_t*)(out_desc + 32 * (size_t)i);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) q[k] = d[k];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void red_count_kernel(ObsArgs A) {
+  __shared__ int wave_tot[(MS_THREADS / 64) * 2];
+  const CovKf kf = A.kfs[A.cand[blockIdx.y]];
+  int v[2] = {0, 0};
+  if (kf.slots) {
+#pragma unroll
+    for (int j = 0; j < MS_PER; ++j) {
+      const int i = blockIdx.x * MS_CHUNK + j * MS_THREADS + threadIdx.x;
+      if (i >= kf.n) continue;
+      const int s = kf.slots[i];
+      if (s < 0 || s >= A.capacity || !A.live[s]) continue;
+      ++v[0];
+      const int p = A.index[s];                                            // (every live slot of a candidate is in the list)
+      if (p != MS_EMPTY && A.count[p] - 1 >= A.min_obs) ++v[1];
+    }
+  }
+  block_sum<MS_THREADS, 2>(v, wave_tot);
+  if (threadIdx.x < 2) A.chunk_tot[2 * ((size_t)blockIdx.y * A.n_chunk + blockIdx.x) + threadIdx.x] = v[threadIdx.x];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void red_tail_kernel(ObsArgs A) {
+  const int c = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (c >= A.n_cand) return;
+  int total = 0, red = 0;
+  for (int j = 0; j < A.n_chunk; ++j) { total += A.chunk_tot[2 * ((size_t)c * A.n_chunk + j)]; red += A.chunk_tot[2 * ((size_t)c * A.n_chunk + j) + 1]; }
+  A.total[c] = total; A.redundant[c] = red;
+  A.cull[c] = total > 0 && (double)red / (double)total > A.threshold ? 1 : 0;     // local_mapper.rs:561-565
+}
+
+// The keyframes of an observation call, checked as covisibility checks its own, and the host-known bound of the entries.
+struct ObsPlan {
+  CovPlan C;
+  int n_feat = 0;
+};
+
+int obs_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, ObsPlan& P) {
+  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, 0, P.C)) return rc;
+  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+  long long total = 0;
+  for (const CovKf& k : P.C.kfs) total += k.n;
+  if (total > 0x7fff0000) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 65536 features", who);
+  P.n_feat = (int)total;
+  return ORBX_OK;
+}
+
+// slots [M] of an observation call: what orbx_map_points_set asks of its own, and live in the store's host mirror
+int obs_check_slots(orbx_map_points* mp, const char* who, const int* slots, int M) {
+  if (int rc = ms_check_slots(mp, who, slots, M, true)) return rc;
+  for (int i = 0; i < M; ++i)
+    if (!mp->live[(size_t)slots[i]]) return orbx_fail(mp->h, ORBX_ERR_INVALID, "%s: slot %d (entry %d) is not live", who, slots[i], i);
+  return ORBX_OK;
+}
+
+// What obs_enqueue is asked for.  The points: `slots` (host [n_points], checked) or, where slots is NULL, a list a selection left
+// in device memory (d_slots, its length in *d_n, at most n_points).  Lists: the three outputs; redundancy: cand and its outputs.
+struct ObsCall {
+  int n_points = 0;
+  const int* slots = nullptr; const int* d_n = nullptr; const int* d_slots = nullptr;
+  int* d_obs_start = nullptr; int* d_obs_kf = nullptr; int* d_obs_feat = nullptr;
+  int n_cand = 0, min_obs = 0; const int* cand = nullptr; double threshold = 0.0;
+  int* d_total = nullptr; int* d_redundant = nullptr; uint8_t* d_cull = nullptr;
+};
+
+// entries the lists of n_points points can hold: every feature once, and no point more often than there are keyframes
+int obs_entry_bound(const ObsPlan& P, int n_points) { return (int)std::min<long long>(P.n_feat, (long long)n_points * (long long)P.C.kfs.size()); }
+
+// Everything on the handle's stream.  The tables (keyframes, slots, candidates) go up through the ring; d_slots_out: where the
+// points' slots lie in device memory afterwards.
+int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const ObsCall& c, const int** d_slots_out = nullptr) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  if (int rc = ms_reserve_first(h, mp, 1)) return rc;
+  const size_t K = P.C.kfs.size(), Mb = (size_t)c.n_points, Nb = c.d_obs_start ? (size_t)obs_entry_bound(P, c.n_points) : 0, NC = (size_t)c.n_cand;
+  const int n_chunk = std::max(1, (P.C.max_n + MS_CHUNK - 1) / MS_CHUNK), n_part = std::max(1, (int)((Mb + MS_CHUNK - 1) / MS_CHUNK));
+  Carve up, ws;
+  const size_t o_kf = up.take(sizeof(CovKf) * K), o_n = up.take(4), o_sl = up.take(c.slots ? 4 * Mb : 0), o_ca = up.take(4 * NC);
+  const size_t o_cn = ws.take(4 * Mb), o_cu = ws.take(4 * Mb), o_pa = ws.take(4 * (size_t)n_part), o_tk = ws.take(4 * Nb), o_tf = ws.take(4 * Nb),
+               o_ct = ws.take(8 * NC * (size_t)n_chunk);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[9], up.off, &hs, &ds)) return rc;
+  if (K) std::memcpy(hs + o_kf, P.C.kfs.data(), sizeof(CovKf) * K);
+  std::memcpy(hs + o_n, &c.n_points, 4);
+  if (c.slots && Mb) std::memcpy(hs + o_sl, c.slots, 4 * Mb);
+  if (NC) std::memcpy(hs + o_ca, c.cand, 4 * NC);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[9], up.off)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_map[8], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[8].p;
+  ObsArgs A{};
+  A.capacity = mp->capacity; A.n_kfs = (int)K; A.n_chunk = n_chunk; A.min_obs = c.min_obs;
+  A.live = mp->d_live; A.kfs = (const CovKf*)(ds + o_kf);
+  A.n_list = c.slots ? (const int*)(ds + o_n) : c.d_n; A.list_slot = c.slots ? (const int*)(ds + o_sl) : c.d_slots;
+  A.index = (int*)mp->first.p;
+  A.count = (int*)(w + o_cn); A.part = (int*)(w + o_pa); A.cursor = (int*)(w + o_cu); A.tmp_kf = (int*)(w + o_tk); A.tmp_feat = (int*)(w + o_tf);
+  A.obs_start = c.d_obs_start; A.obs_kf = c.d_obs_kf; A.obs_feat = c.d_obs_feat;
+  A.cand = (const int*)(ds + o_ca); A.n_cand = c.n_cand; A.threshold = c.threshold;
+  A.chunk_tot = (int*)(w + o_ct); A.total = c.d_total; A.redundant = c.d_redundant; A.cull = c.d_cull;
+  if (d_slots_out) *d_slots_out = A.list_slot;
+  const dim3 block(MS_THREADS), list_grid(std::max(1, (int)((Mb + MS_THREADS - 1) / MS_THREADS))), kf_grid(n_chunk, (unsigned)K);
+  const bool walk = K > 0 && P.C.max_n > 0 && Mb > 0;
+  {
+    ProfScope ps(h, "obs_index_kernel");
+    hipLaunchKernelGGL(obs_index_kernel, list_grid, block, 0, h->stream, A);
+  }
+  if (walk) {
+    ProfScope ps(h, "obs_count_kernel", true);
+    hipLaunchKernelGGL(obs_count_kernel, kf_grid, block, 0, h->stream, A);
+  }
+  if (c.d_obs_start) {
+    {
+      ProfScope ps(h, "obs_part_kernel", true);
+      hipLaunchKernelGGL(obs_part_kernel, dim3(n_part), block, 0, h->stream, A);
+    }
+    {
+      ProfScope ps(h, "obs_scan_kernel", true);
+      hipLaunchKernelGGL(obs_scan_kernel, dim3(n_part), block, 0, h->stream, A);
+    }
+    if (walk && Nb > 0) {
+      {
+        ProfScope ps(h, "obs_append_kernel", true);
+        hipLaunchKernelGGL(obs_append_kernel, kf_grid, block, 0, h->stream, A);
+      }
+      {
+        ProfScope ps(h, "obs_rank_kernel", true);
+        hipLaunchKernelGGL(obs_rank_kernel, dim3((unsigned)((Nb + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
+      }
+      if (K > (size_t)OBS_SHORT) {                                          // (a segment is never longer than the call has keyframes)
+        ProfScope ps(h, "obs_rank_long_kernel", true);
+        hipLaunchKernelGGL(obs_rank_long_kernel, dim3((unsigned)std::min<size_t>(Mb, 4 * (size_t)h->n_cu)), block, 0, h->stream, A);
+      }
+    }
+  }
+  if (NC) {
+    {
+      ProfScope ps(h, "red_count_kernel", true);
+      hipLaunchKernelGGL(red_count_kernel, dim3(n_chunk, (unsigned)NC), block, 0, h->stream, A);
+    }
+    {
+      ProfScope ps(h, "red_tail_kernel", true);
+      hipLaunchKernelGGL(red_tail_kernel, dim3((unsigned)((NC + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
+    }
+  }
+  {
+    ProfScope ps(h, "obs_restore_kernel", true);
+    hipLaunchKernelGGL(obs_restore_kernel, list_grid, block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// orbx_map_observations[_device]: the checks, then the lists into device memory
+int obs_lists_call(orbx_handle* h, const char* who, orbx_map_points* mp, const ObsPlan& P, int M, const int* slots, int obs_cap, int* d_obs_start, int* d_obs_kf,
+                   int* d_obs_feat) {
+  if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
+  if (!d_obs_start || (P.n_feat > 0 && M > 0 && (!d_obs_kf || !d_obs_feat))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ObsCall c;
+  c.n_points = M; c.slots = slots; c.d_obs_start = d_obs_start; c.d_obs_kf = d_obs_kf; c.d_obs_feat = d_obs_feat;
+  return obs_enqueue(h, mp, P, c);
+}
+
+// orbx_map_refresh_points[_device] behind their checks: the lists, the points' rows out of the store, mappoint_kernels.hip's
+// launches on them, the chosen descriptors back into the store.  Every pointer is device memory, slots a host array.
+int obs_refresh_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const ObsPlan& P, const orbx_keyframe* const* kfs, int M, const int* slots,
+                        double scale_range, const double* d_normals_in, uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance,
+                        orbx_mp_refresh_record* d_records) {
+  const size_t Mz = (size_t)M, Nb = (size_t)obs_entry_bound(P, M), T = P.C.kfs.size();
+  std::vector<MapPointKf> tab(T);
+  for (size_t t = 0; t < T; ++t) {
+    tab[t].desc = kfs[t]->d_desc; tab[t].n = kfs[t]->n; tab[t].pad_ = 0;
+    std::memcpy(tab[t].centre, kfs[t]->pose_wc + 4, sizeof(tab[t].centre));
+  }
+  Carve ws;
+  const size_t o_os = ws.take(4 * (Mz + 1)), o_ok = ws.take(4 * Nb), o_of = ws.take(4 * Nb), o_po = ws.take(24 * Mz);
+  if (int rc = orbx_reserve(h, h->ws_map[10], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[10].p;
+  ObsCall c;
+  c.n_points = M; c.slots = slots; c.d_obs_start = (int*)(w + o_os); c.d_obs_kf = (int*)(w + o_ok); c.d_obs_feat = (int*)(w + o_of);
+  const int* d_slots = nullptr;
+  if (int rc = obs_enqueue(h, mp, P, c, &d_slots)) return rc;
+  const dim3 grid((M + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
+  {
+    ProfScope ps(h, "obs_gather_kernel", true);
+    hipLaunchKernelGGL(obs_gather_kernel, grid, block, 0, h->stream, d_slots, M, (const double*)mp->d_pos, (const uint8_t*)mp->d_desc, (double*)(w + o_po), d_mp_desc);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  // the entries' host-known bound stands in for obs_start[M]: the kernels take every length from obs_start itself
+  if (int rc = mp_refresh_enqueue(h, who, M, (int)Nb, (const double*)(w + o_po), c.d_obs_start, c.d_obs_kf, c.d_obs_feat, (int)T, tab.data(), scale_range, d_mp_desc,
+                                  d_normals_in, d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records))
+    return rc;
+  {
+    ProfScope ps(h, "map_scatter_kernel");
+    hipLaunchKernelGGL(map_scatter_kernel, grid, block, 0, h->stream, d_slots, M, (const double*)nullptr, (const uint8_t*)d_mp_desc, 1, mp->d_pos, mp->d_desc,
+                       mp->d_live);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// A redundancy call, checked and sized on the host: the keyframes, and the candidates as one frame of a selection.
+struct RedPlan {
+  ObsPlan O;
+  SelPlan S;
+};
+
+int red_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand, const int* cand,
+             int min_observations, RedPlan& P) {
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P.O)) return rc;
+  if (n_cand < 0 || n_cand > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_cand <= 65535)", who);
+  if (min_observations < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: min_observations must not be negative", who);
+  if (int rc = cov_check_queries(h, who, "cand", n_cand, cand, n_kfs, 0)) return rc;
+  if (n_cand == 0) return ORBX_OK;
+  std::vector<const orbx_keyframe*> ck((size_t)n_cand);
+  for (int i = 0; i < n_cand; ++i) ck[(size_t)i] = kfs[cand[i]];
+  const int off[2] = {0, n_cand};
+  return ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ck.data(), off, nullptr, P.S);
+}
+
+// The candidates' distinct live slots by the selection (its gathered rows stay in the workspace), then counts and sums.
+int red_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const RedPlan& P, int n_cand, const int* cand, int min_observations, double threshold,
+                int* d_total, int* d_redundant, uint8_t* d_cull) {
+  if (!d_total || !d_redundant || !d_cull) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  const int bound = P.S.bound_off[1];
+  Carve ws;
+  const size_t o_lo = ws.take(8), o_ls = ws.take(4 * (size_t)bound), o_po = ws.take(24 * (size_t)bound), o_de = ws.take(32 * (size_t)bound);
+  if (int rc = orbx_reserve(h, h->ws_map[10], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[10].p;
+  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), (int*)(w + o_ls), (double*)(w + o_po),
+                                 w + o_de))
+    return rc;
+  ObsCall c;
+  c.n_points = bound; c.d_n = (const int*)(w + o_lo) + 1; c.d_slots = (const int*)(w + o_ls);
+  c.n_cand = n_cand; c.cand = cand; c.min_obs = min_observations; c.threshold = threshold;
+  c.d_total = d_total; c.d_redundant = d_redundant; c.d_cull = d_cull;
+  return obs_enqueue(h, mp, P.O, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1340,6 +1736,112 @@ int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_conf
   } catch (...) {
     return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
   }
+}
+
+int orbx_map_observations_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, int obs_cap,
+                                 int* d_obs_start, int* d_obs_kf, int* d_obs_feat) {
+  static const char* who = "orbx_map_observations_device";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+  return obs_lists_call(h, who, mp, P, M, slots, obs_cap, d_obs_start, d_obs_kf, d_obs_feat);
+}
+
+int orbx_map_observations(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, int obs_cap, int* obs_start,
+                          int* obs_kf, int* obs_feat) {
+  static const char* who = "orbx_map_observations";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+  if (obs_cap < P.n_feat || !obs_start || (P.n_feat > 0 && M > 0 && (!obs_kf || !obs_feat)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (obs_cap %d must reach the observations' bound %d: the features of kfs[] summed)", who, obs_cap, P.n_feat);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t Mz = (size_t)M, Nb = (size_t)obs_entry_bound(P, M);
+  Carve out;
+  const size_t o_os = out.take(4 * (Mz + 1)), o_ok = out.take(4 * Nb), o_of = out.take(4 * Nb);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  if (int rc = obs_lists_call(h, who, mp, P, M, slots, P.n_feat, (int*)(c.dout + o_os), (int*)(c.dout + o_ok), (int*)(c.dout + o_of))) return rc;
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+  std::memcpy(obs_start, c.ho + o_os, 4 * (Mz + 1));
+  const size_t N = (size_t)obs_start[M];
+  if (N) { std::memcpy(obs_kf, c.ho + o_ok, 4 * N); std::memcpy(obs_feat, c.ho + o_of, 4 * N); }
+  return ORBX_OK;
+}
+
+int orbx_map_refresh_points_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, double scale_range,
+                                   uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance, orbx_mp_refresh_record* d_records) {
+  static const char* who = "orbx_map_refresh_points_device";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+  if (M == 0) return ORBX_OK;
+  if (!d_mp_desc || !d_normals || !d_min_distance || !d_max_distance || !d_records || ((uintptr_t)d_mp_desc & 7) || ((uintptr_t)d_normals & 7))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc and d_normals are 8-byte aligned)", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  return obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, d_normals, d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records);
+}
+
+int orbx_map_refresh_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, double scale_range,
+                            uint8_t* mp_desc, double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
+  static const char* who = "orbx_map_refresh_points";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+  if (M == 0) return ORBX_OK;
+  if (!mp_desc || !normals || !min_distance || !max_distance || !records) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // the normals up (they are kept where no observer is far enough), one blob down: [mp_desc | normals | min | max | records]
+  const size_t Mz = (size_t)M;
+  Carve in, out;
+  const size_t i_nr = in.take(24 * Mz);
+  const size_t o_md = out.take(32 * Mz), o_nr = out.take(24 * Mz), o_mn = out.take(8 * Mz), o_mx = out.take(8 * Mz), o_rc = out.take(sizeof(orbx_mp_refresh_record) * Mz);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
+  std::memcpy(c.hi + i_nr, normals, 24 * Mz);
+  if (int rc = orbx_host_call_upload(h, c)) return rc;
+  if (int rc = obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, (const double*)(c.di + i_nr), c.dout + o_md, (double*)(c.dout + o_nr),
+                                   (double*)(c.dout + o_mn), (double*)(c.dout + o_mx), (orbx_mp_refresh_record*)(c.dout + o_rc)))
+    return rc;
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+  std::memcpy(mp_desc, c.ho + o_md, 32 * Mz); std::memcpy(normals, c.ho + o_nr, 24 * Mz);
+  std::memcpy(min_distance, c.ho + o_mn, 8 * Mz); std::memcpy(max_distance, c.ho + o_mx, 8 * Mz);
+  std::memcpy(records, c.ho + o_rc, sizeof(orbx_mp_refresh_record) * Mz);
+  return ORBX_OK;
+}
+
+int orbx_map_keyframe_redundancy_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand, const int* cand,
+                                        int min_observations, double threshold, int* d_total, int* d_redundant, uint8_t* d_cull) {
+  static const char* who = "orbx_map_keyframe_redundancy_device";
+  if (!h) return ORBX_ERR_INVALID;
+  RedPlan P;
+  if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
+  if (n_cand == 0) return ORBX_OK;
+  return red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, d_total, d_redundant, d_cull);
+}
+
+int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand, const int* cand,
+                                 int min_observations, double threshold, int* total, int* redundant, uint8_t* cull) {
+  static const char* who = "orbx_map_keyframe_redundancy";
+  if (!h) return ORBX_ERR_INVALID;
+  RedPlan P;
+  if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
+  if (n_cand == 0) return ORBX_OK;
+  if (!total || !redundant || !cull) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t NC = (size_t)n_cand;
+  Carve out;
+  const size_t o_to = out.take(4 * NC), o_re = out.take(4 * NC), o_cu = out.take(NC);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  if (int rc = red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, (int*)(c.dout + o_to), (int*)(c.dout + o_re), c.dout + o_cu)) return rc;
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+  std::memcpy(total, c.ho + o_to, 4 * NC); std::memcpy(redundant, c.ho + o_re, 4 * NC); std::memcpy(cull, c.ho + o_cu, NC);
+  return ORBX_OK;
 }
 
 int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
