@@ -1261,8 +1261,8 @@ int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_conf
  *   A candidate without a table gives 0, 0, 0.
  * Outputs total / redundant [n_cand] int32, cull [n_cand] u8.  ORBX_ERR_INVALID also for an index outside [0, n_kfs),
  * min_observations < 0, n_cand > 65535.  n_cand = 0: nothing is done, ORBX_OK.
- * Still the caller's: removal itself (IMU preintegration merging, the spanning tree, ids), the fuse and merge phases of
- * search_in_neighbors, normals. */
+ * Still the caller's: removal itself (IMU preintegration merging, the spanning tree, ids), normals; of search_in_neighbors the
+ * choice of the neighbours (the fuse and merge phases: the next block). */
 int orbx_map_observations_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
                                  int obs_cap, int* d_obs_start, int* d_obs_kf, int* d_obs_feat);
 int orbx_map_observations(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots,
@@ -1278,6 +1278,77 @@ int orbx_map_keyframe_redundancy_device(orbx_handle* h, orbx_map_points* mp, int
                                         uint8_t* d_cull);
 int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand,
                                  const int* cand, int min_observations, double threshold, int* total, int* redundant, uint8_t* cull);
+
+/* ---- fuse and merge on the resident map (search_in_neighbors.rs:240-390, map.rs:770-...: merge_map_points) ------------------------
+ * fuse_points_into_keyframes walks points x targets sequentially and mutates as it goes: a match on a feature without a point is
+ * associated, a match on a feature with another point merges the two, the point with more observations keeps (the projected one
+ * on ties), the goner's observers are re-pointed or erased.  Its outcome depends on orders the reference leaves to HashSet
+ * iteration (neighbor_ids, neighbor_only_mps, the goner's observations) and on counts that change during the walk; the library fixes
+ * a derived, deterministic definition of ONE PASS fuse(src, tgt).  kfs [n_kfs], src [n_src], tgt [n_tgt] are host arrays (copied
+ * before the call returns); src and tgt hold positions in kfs[].  All reads are of the state at entry to the pass; obs(k),
+ * n_observers(s) and "live" are those of the observations block, over kfs[].
+ *   [spec] L = the distinct live slots of the tables of kfs[src[0..n_src)] in first-seen order: what ORBX_MAP_SOURCE_KEYFRAMES gives
+ *     one frame.  P = |L|.
+ *   [spec] search: for point j (p = L[j]) and target t, match[j][t] = -1 if p is in obs(tgt[t]) (:272); otherwise the feature that
+ *     orbx_keyframe_fuse_search returns for the store's position and descriptor of p against kfs[tgt[t]], or -1 — bit for bit the
+ *     existing search, with the same inverse of pose_wc made on the host the same way.
+ *   [spec] classes: a match (j, t, f) with e = table(tgt[t])[f], the entry read WITH repeats: if 0 <= e < capacity and live[e], p and
+ *     e are the same point; otherwise p CLAIMS (t, f), and all points that claim one feature are the same point.  Classes are the
+ *     connected components over slots.
+ *   [spec] keeper of a class = the member with the largest n_observers; ties go to the member earliest in L, a tied member that is
+ *     not in L comes after all those in L, by ascending slot.  Every other member of a class of two or more is a GONER.
+ *   [spec] tables: for every keyframe k of kfs[] and every class C that has a claim or at least two members, G = the features of k
+ *     whose entry is a live member of C together with the features of k claimed by members of C.  If a feature of G already names
+ *     the keeper, the features naming the keeper stay and all others of G become -1; otherwise the lowest-indexed feature of G gets
+ *     the keeper and the others become -1.  Nothing else in any table changes; a keyframe that is not in kfs[] is not touched: the
+ *     caller passes every keyframe that may observe the points involved.
+ *   [spec] outputs: counts[4] = {P, matches, added, goners} (added: the features whose entry went from "no live point" to a slot),
+ *     list_slot [P], match [P][n_tgt], goner[] / keeper[] by ascending goner slot.
+ * Deviations from the sequential reference: counts are those at entry (the reference's grow as it associates); a projected point
+ * that loses a merge still contributes its later matches to its class (the reference drops them: the point no longer exists); the
+ * orders above are fixed.  Where every class has at most two members, no feature is matched twice, every merge keeps the projected
+ * point and the two counts of a merged pair differ by more than n_tgt, the pass equals the reference replayed in L order and target
+ * order.
+ * Liveness: the store keeps a host mirror of its live bytes, so the device form leaves them alone.  After the pass no table of
+ * kfs[] names a goner, and the goner list is an output (the caller needs it anyway to retire ids).  Positions, descriptors,
+ * d_mp_flag and mp_ids are untouched (merge_map_points changes none of them).  d_mp_uniq of every keyframe whose table changed is
+ * made again.  A target without a table is given one, every entry -1, when the call is accepted: to every reader the same thing.
+ *
+ * orbx_map_fuse_device: asynchronous on the handle's stream, no host synchronisation inside; the store's tables are left as found
+ * and no launch is sized by the capacity; the outputs are the same bytes on every run.  list_cap, the rows d_list_slot holds (and
+ * d_match rows of n_tgt), must reach L's bound: the features of kfs[src[..]] summed, at most the capacity.  d_goner / d_keeper hold
+ * that bound + the sum of the targets' feature counts.  d_counts [4].
+ * orbx_map_fuse: the same with host outputs, synchronous, one download; the goners are then erased as orbx_map_points_erase does.
+ * ORBX_ERR_INVALID before anything is enqueued, tables, store and outputs untouched: an index outside [0, n_kfs), a target listed
+ * twice, a keyframe listed twice in kfs[], n_kfs > 65535, desc_threshold > 256, list_cap below its bound, a keyframe of another
+ * handle or bound to another store.  n_src = 0, n_tgt = 0 or P = 0: ORBX_OK, counts written and nothing else.
+ *
+ * orbx_map_search_in_neighbors = phases 2 to 4 of search_in_neighbors for the current keyframe kfs[cur] and neighbours nb [n_nb]
+ * (positions in kfs[], none twice, none of them cur; choosing them — orbx_map_covisibility's best list, the secondaries, the temporal
+ * chain — stays with the caller): pass A = fuse([cur], nb); pass B = fuse(nb, [cur]) on the tables as A left them, enqueued behind A
+ * with no synchronisation between; ONE download of both passes' counts and goner lists and of the affected list; the erase;
+ * orbx_map_refresh_points on the affected list.  The affected list is the distinct live slots of [cur] ++ nb after both passes in
+ * first-seen order, made by the selection kernels.  counts [8]: pass A's four, then pass B's; goner_a / keeper_a / goner_b /
+ * keeper_b hold goner_cap rows each, at least the larger of the two passes' bounds above; affected_slot and the refresh outputs
+ * (mp_desc [..][32], normals [..][3], min_distance, max_distance, records: orbx_map_refresh_points's, in the affected list's order)
+ * hold affected_cap rows, at least the features of cur and nb[] summed, at most the capacity.  slot_normals [capacity][3] (NULL:
+ * zeros) gives every slot's normal before the call: the store keeps none.  The refusals are those above.
+ *
+ * orbx_keyframe_get_map_point_slots: the table as it lies in device memory (every entry -1 without one); synchronous.
+ * Still the caller's: the choice of the neighbours, ids and the id -> slot map (goner / keeper and the tables read back say what to
+ * apply), removal, normals. */
+int orbx_keyframe_get_map_point_slots(const orbx_keyframe* kf, int* slots);
+int orbx_map_fuse_device(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src,
+                         const int* src, int n_tgt, const int* tgt, double radius_scale, unsigned desc_threshold, int list_cap,
+                         int* d_counts, int* d_list_slot, int* d_match, int* d_goner, int* d_keeper);
+int orbx_map_fuse(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src,
+                  const int* src, int n_tgt, const int* tgt, double radius_scale, unsigned desc_threshold, int list_cap, int* counts,
+                  int* list_slot, int* match, int* goner, int* keeper);
+int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int cur,
+                                 int n_nb, const int* nb, double radius_scale, unsigned desc_threshold, double scale_range,
+                                 const double* slot_normals, int goner_cap, int affected_cap, int* counts, int* goner_a, int* keeper_a,
+                                 int* goner_b, int* keeper_b, int* n_affected, int* affected_slot, uint8_t* mp_desc, double* normals,
+                                 double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
 
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and

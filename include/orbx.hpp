@@ -1199,6 +1199,113 @@ inline void map_keyframe_redundancy_device(Handle& h, MapPointStore& store, cons
                                               min_observations, threshold, d_total, d_redundant, d_cull));
 }
 
+// ---- fuse and merge on the resident map (orbx.h, "fuse and merge on the resident map"; search_in_neighbors.rs:240-390) ----
+// One pass fuse(src, tgt): the distinct live points of keyframes[src[..]] searched in keyframes[tgt[..]]; a match associates or
+// merges; the tables of `keyframes` are rewritten where they lie.  The keyframes are not const here.
+struct MapFuse {
+  int P = 0, matches = 0, added = 0;                   // counts[0..2]; goner.size() is counts[3]
+  std::vector<int> list_slot;                          // [P]
+  std::vector<int> match;                              // [P][n_tgt]: the matched feature or -1
+  std::vector<int> goner, keeper;                      // by ascending goner slot: the caller retires the goners' ids
+};
+
+inline int keyframe_features(Handle& h, const orbx_keyframe* k) {
+  int n = 0;
+  h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+  return n;
+}
+// (rows of the list, rows of the goner lists) a pass needs: the features of keyframes[src[..]], at most the capacity; that plus the
+// targets' features.  Indices out of range count nothing: the library refuses them.
+inline std::pair<int, int> map_fuse_bounds(Handle& h, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, const std::vector<int>& src,
+                                           const std::vector<int>& tgt) {
+  auto sum = [&](const std::vector<int>& idx) {
+    long long n = 0;
+    for (int i : idx)
+      if (i >= 0 && (size_t)i < keyframes.size()) n += keyframe_features(h, keyframes[(size_t)i]);
+    return n;
+  };
+  int cap = 0;
+  h.check(orbx_map_points_info(store.get(), &cap, nullptr));
+  const long long bound = std::min<long long>(sum(src), cap);
+  return {(int)bound, (int)(bound + sum(tgt))};
+}
+
+// orbx_map_fuse_device: d_counts [4], d_list_slot [list_cap], d_match [list_cap][tgt.size()], d_goner / d_keeper [the second of
+// map_fuse_bounds] are the caller's device memory; asynchronous; the store's live bytes are untouched.
+inline void map_fuse_device(Handle& h, const CameraModel& camera, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, const std::vector<int>& src,
+                            const std::vector<int>& tgt, double radius_scale, unsigned desc_threshold, int list_cap, int* d_counts, int* d_list_slot, int* d_match,
+                            int* d_goner, int* d_keeper) {
+  const orbx_camera c = camera.c();
+  h.check(orbx_map_fuse_device(h.get(), &c, store.get(), (int)keyframes.size(), keyframes.data(), (int)src.size(), src.data(), (int)tgt.size(), tgt.data(), radius_scale,
+                               desc_threshold, list_cap, d_counts, d_list_slot, d_match, d_goner, d_keeper));
+}
+
+// orbx_map_fuse: the same into host vectors cut to their sizes, synchronous; the goners are erased from the store.
+inline MapFuse map_fuse(Handle& h, const CameraModel& camera, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, const std::vector<int>& src,
+                        const std::vector<int>& tgt, double radius_scale, unsigned desc_threshold = 50) {
+  const auto [cap, gcap] = map_fuse_bounds(h, store, keyframes, src, tgt);
+  const size_t T = tgt.size();
+  MapFuse r;
+  int counts[4] = {0, 0, 0, 0};
+  r.list_slot.resize((size_t)std::max(cap, 1)); r.match.resize((size_t)std::max(cap, 1) * std::max<size_t>(T, 1));
+  r.goner.resize((size_t)std::max(gcap, 1)); r.keeper.resize((size_t)std::max(gcap, 1));
+  const orbx_camera c = camera.c();
+  h.check(orbx_map_fuse(h.get(), &c, store.get(), (int)keyframes.size(), keyframes.data(), (int)src.size(), src.data(), (int)T, tgt.data(), radius_scale, desc_threshold,
+                        cap, counts, r.list_slot.data(), r.match.data(), r.goner.data(), r.keeper.data()));
+  r.P = counts[0]; r.matches = counts[1]; r.added = counts[2];
+  r.list_slot.resize((size_t)r.P); r.match.resize((size_t)r.P * T); r.goner.resize((size_t)counts[3]); r.keeper.resize((size_t)counts[3]);
+  return r;
+}
+
+// orbx_map_search_in_neighbors: phases 2 to 4 of search_in_neighbors for keyframes[cur] and keyframes[neighbours[..]] (choosing them
+// stays with the caller): fuse([cur], neighbours), fuse(neighbours, [cur]), one download, the goners erased, map_refresh_points on
+// the affected list.  slot_normals: every slot's normal before the call, [capacity], or empty for zeros (the store keeps none).
+struct MapSearchInNeighbors {
+  int counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};            // pass A's {P, matches, added, goners}, then pass B's
+  std::vector<int> goner_a, keeper_a, goner_b, keeper_b;
+  std::vector<int> affected;                           // the distinct live slots of [cur] ++ neighbours afterwards, first seen first
+  MapPointRefresh refresh;                             // in the affected list's order
+  size_t num_fused() const { return goner_a.size() + goner_b.size(); }                       // SearchInNeighborsResult (search_in_neighbors.rs:43-50)
+  size_t num_observations_added() const { return (size_t)counts[2] + (size_t)counts[6]; }
+};
+inline MapSearchInNeighbors map_search_in_neighbors(Handle& h, const CameraModel& camera, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, int cur,
+                                                    const std::vector<int>& neighbours, double radius_scale, double scale_range,
+                                                    const std::vector<std::array<double, 3>>& slot_normals = {}, unsigned desc_threshold = 50) {
+  int capacity = 0;
+  h.check(orbx_map_points_info(store.get(), &capacity, nullptr));
+  if (!slot_normals.empty() && slot_normals.size() != (size_t)capacity) throw Error(ORBX_ERR_INVALID, "map_search_in_neighbors: one normal per slot of the store");
+  long long f_cur = 0, f_nb = 0;
+  if (cur >= 0 && (size_t)cur < keyframes.size()) f_cur = keyframe_features(h, keyframes[(size_t)cur]);
+  for (int i : neighbours)
+    if (i >= 0 && (size_t)i < keyframes.size()) f_nb += keyframe_features(h, keyframes[(size_t)i]);
+  const long long cap = capacity;
+  const size_t gcap = (size_t)std::max<long long>(std::max(std::min(f_cur, cap) + f_nb, std::min(f_nb, cap) + f_cur), 1);
+  const size_t acap = (size_t)std::max<long long>(std::min(f_cur + f_nb, cap), 1);
+  MapSearchInNeighbors r;
+  r.goner_a.resize(gcap); r.keeper_a.resize(gcap); r.goner_b.resize(gcap); r.keeper_b.resize(gcap); r.affected.resize(acap);
+  r.refresh = MapPointRefresh{std::vector<uint8_t>(32 * acap), std::vector<std::array<double, 3>>(acap), std::vector<double>(acap), std::vector<double>(acap),
+                              std::vector<orbx_mp_refresh_record>(acap)};
+  int M = 0;
+  const orbx_camera c = camera.c();
+  h.check(orbx_map_search_in_neighbors(h.get(), &c, store.get(), (int)keyframes.size(), keyframes.data(), cur, (int)neighbours.size(), neighbours.data(), radius_scale,
+                                       desc_threshold, scale_range, slot_normals.empty() ? nullptr : slot_normals[0].data(), (int)gcap, (int)acap, r.counts,
+                                       r.goner_a.data(), r.keeper_a.data(), r.goner_b.data(), r.keeper_b.data(), &M, r.affected.data(), r.refresh.mp_descriptors.data(),
+                                       r.refresh.normals[0].data(), r.refresh.min_distance.data(), r.refresh.max_distance.data(), r.refresh.records.data()));
+  r.goner_a.resize((size_t)r.counts[3]); r.keeper_a.resize((size_t)r.counts[3]); r.goner_b.resize((size_t)r.counts[7]); r.keeper_b.resize((size_t)r.counts[7]);
+  r.affected.resize((size_t)M);
+  r.refresh.mp_descriptors.resize(32 * (size_t)M); r.refresh.normals.resize((size_t)M); r.refresh.min_distance.resize((size_t)M);
+  r.refresh.max_distance.resize((size_t)M); r.refresh.records.resize((size_t)M);
+  return r;
+}
+
+// orbx_keyframe_get_map_point_slots: the table as it lies in device memory (-1 everywhere without one): what the caller applies to its ids
+inline std::vector<int> keyframe_map_point_slots(Handle& h, const orbx_keyframe* kf) {
+  std::vector<int> slots((size_t)std::max(keyframe_features(h, kf), 1), -1);
+  h.check(orbx_keyframe_get_map_point_slots(kf, slots.data()));
+  slots.resize((size_t)keyframe_features(h, kf));
+  return slots;
+}
+
 // ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
 // One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
 // validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).

@@ -104,6 +104,7 @@ ABI_SYMBOLS = [
     "orbx_map_collect_ba_window_device", "orbx_map_collect_ba_window", "orbx_ba_solve_visual_obs32_device", "orbx_map_local_ba",
     "orbx_map_observations_device", "orbx_map_observations", "orbx_map_refresh_points_device", "orbx_map_refresh_points",
     "orbx_map_keyframe_redundancy_device", "orbx_map_keyframe_redundancy",
+    "orbx_keyframe_get_map_point_slots", "orbx_map_fuse_device", "orbx_map_fuse", "orbx_map_search_in_neighbors",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 
@@ -1436,6 +1437,87 @@ class Handle:
                                                          _vp(red), _vp(cull)))
         return total[:n], red[:n], cull[:n]
 
+    # ---- fuse and merge on the resident map (include/orbx.h, "fuse and merge on the resident map") ----
+    @staticmethod
+    def _fuse_bounds(mp, keyframes, src, tgt):
+        """(L's bound, the goner lists' bound) of one pass: the features of keyframes[src[..]], at most the capacity; that plus the
+        targets' features.  Indices out of range count nothing: the library refuses them."""
+        n = lambda idx: int(sum(keyframes[i].n for i in idx if 0 <= i < len(keyframes)))
+        bound = min(n(src), mp.capacity)
+        return bound, bound + n(tgt)
+
+    def map_fuse_device(self, camera, mp: "MapPointStore", keyframes, src, tgt, radius_scale, desc_threshold=TH_LOW, device=None):
+        """One pass fuse(src, tgt) of search_in_neighbors' fuse and merge on the resident map (orbx_map_fuse_device): the distinct
+        live points of keyframes[src[..]] are searched in keyframes[tgt[..]], matches associate or merge, and every table of
+        `keyframes` is rewritten where it lies.  Returns a dict of CUDA tensors: counts [4] int32 = (P, matches, added, goners),
+        list_slot [cap] int32 (rows [0, P)), match [cap, n_tgt] int32 (rows [0, P): the matched feature or -1), goner / keeper
+        [goner cap] int32 (rows [0, goners), by ascending goner slot).  The store's live bytes are untouched: erasing the goners is
+        the caller's (map_fuse does it).  Asynchronous on the handle's stream."""
+        import torch
+        src = np.ascontiguousarray(src, np.int32).reshape(-1); tgt = np.ascontiguousarray(tgt, np.int32).reshape(-1)
+        cap, gcap = self._fuse_bounds(mp, keyframes, src, tgt)
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        o = dict(counts=mk(4), list_slot=mk(max(cap, 1)), match=mk((max(cap, 1), max(len(tgt), 1))), goner=mk(max(gcap, 1)), keeper=mk(max(gcap, 1)))
+        cam = camera._c()
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_fuse_device(self._h, C.byref(cam), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(src)),
+                                                 _vp(src if len(src) else np.zeros(1, np.int32)), C.c_int(len(tgt)), _vp(tgt if len(tgt) else np.zeros(1, np.int32)),
+                                                 C.c_double(radius_scale), C.c_uint(int(desc_threshold)), C.c_int(cap), _vp(o["counts"]), _vp(o["list_slot"]),
+                                                 _vp(o["match"]), _vp(o["goner"]), _vp(o["keeper"])))
+        o["list_slot"] = o["list_slot"][:cap]; o["match"] = o["match"][:cap, :len(tgt)]; o["goner"] = o["goner"][:gcap]; o["keeper"] = o["keeper"][:gcap]
+        return o
+
+    def map_fuse(self, camera, mp: "MapPointStore", keyframes, src, tgt, radius_scale, desc_threshold=TH_LOW):
+        """The host form (orbx_map_fuse), synchronous: a dict of numpy int32 arrays cut to their sizes — counts [4], list_slot [P],
+        match [P, n_tgt], goner / keeper [goners] — and the goners erased from the store."""
+        src = np.ascontiguousarray(src, np.int32).reshape(-1); tgt = np.ascontiguousarray(tgt, np.int32).reshape(-1)
+        cap, gcap = self._fuse_bounds(mp, keyframes, src, tgt)
+        T = len(tgt)
+        counts = np.zeros(4, np.int32); ls = np.zeros(max(cap, 1), np.int32); ma = np.full(max(cap, 1) * max(T, 1), -1, np.int32)
+        go = np.zeros(max(gcap, 1), np.int32); ke = np.zeros(max(gcap, 1), np.int32)
+        cam = camera._c()
+        self._after_torch()
+        self._check(self._L.orbx_map_fuse(self._h, C.byref(cam), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(src)),
+                                          _vp(src if len(src) else np.zeros(1, np.int32)), C.c_int(T), _vp(tgt if T else np.zeros(1, np.int32)),
+                                          C.c_double(radius_scale), C.c_uint(int(desc_threshold)), C.c_int(cap), _vp(counts), _vp(ls), _vp(ma), _vp(go), _vp(ke)))
+        P, G = int(counts[0]), int(counts[3])
+        return dict(counts=counts, list_slot=ls[:P].copy(), match=ma[:P * T].reshape(P, T).copy(), goner=go[:G].copy(), keeper=ke[:G].copy())
+
+    def map_search_in_neighbors(self, camera, mp: "MapPointStore", keyframes, cur, neighbours, radius_scale, scale_range, desc_threshold=TH_LOW,
+                                slot_normals=None):
+        """Phases 2 to 4 of search_in_neighbors for keyframes[cur] and keyframes[neighbours[..]] on the resident map
+        (orbx_map_search_in_neighbors), synchronous: pass A fuse([cur], neighbours), pass B fuse(neighbours, [cur]), one download, the
+        goners erased, map_refresh_points on the affected list.  slot_normals [capacity,3]: every slot's normal before the call
+        (None: zeros).  Returns a dict: counts [2,4] int32, goner_a / keeper_a / goner_b / keeper_b, affected [M] int32 and
+        refresh (MapPointRefresh, in the affected list's order)."""
+        nb = np.ascontiguousarray(neighbours, np.int32).reshape(-1)
+        n = lambda idx: int(sum(keyframes[i].n for i in idx if 0 <= i < len(keyframes)))
+        f_cur, f_nb = n([int(cur)]), n(nb)
+        gcap = max(min(f_cur, mp.capacity) + f_nb, min(f_nb, mp.capacity) + f_cur, 1)
+        acap = max(min(f_cur + f_nb, mp.capacity), 1)
+        counts = np.zeros(8, np.int32)
+        g = [np.zeros(gcap, np.int32) for _ in range(4)]
+        n_aff = C.c_int(0)
+        aff = np.zeros(acap, np.int32)
+        out = MapPointRefresh(np.zeros((acap, 32), np.uint8), np.zeros((acap, 3)), np.zeros(acap), np.zeros(acap), np.zeros(acap, MP_REFRESH_RECORD))
+        sn = None
+        if slot_normals is not None:
+            sn = np.ascontiguousarray(slot_normals, np.float64).reshape(-1, 3)
+            if len(sn) != mp.capacity:
+                raise ValueError("map_search_in_neighbors: slot_normals is [capacity,3]")
+        cam = camera._c()
+        self._after_torch()
+        self._check(self._L.orbx_map_search_in_neighbors(
+            self._h, C.byref(cam), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(int(cur)), C.c_int(len(nb)),
+            _vp(nb if len(nb) else np.zeros(1, np.int32)), C.c_double(radius_scale), C.c_uint(int(desc_threshold)), C.c_double(scale_range),
+            _vp(sn) if sn is not None else None, C.c_int(gcap), C.c_int(acap), _vp(counts), _vp(g[0]), _vp(g[1]), _vp(g[2]), _vp(g[3]), C.byref(n_aff), _vp(aff),
+            _vp(out.mp_desc), _vp(out.normals), _vp(out.min_distance), _vp(out.max_distance), _vp(out.records)))
+        M, Ga, Gb = n_aff.value, int(counts[3]), int(counts[7])
+        refresh = MapPointRefresh(out.mp_desc[:M].copy(), out.normals[:M].copy(), out.min_distance[:M].copy(), out.max_distance[:M].copy(), out.records[:M].copy())
+        return dict(counts=counts.reshape(2, 4), goner_a=g[0][:Ga].copy(), keeper_a=g[1][:Ga].copy(), goner_b=g[2][:Gb].copy(), keeper_b=g[3][:Gb].copy(),
+                    affected=aff[:M].copy(), refresh=refresh)
+
     def ba_solve_visual_obs32_device(self, camera, cfg, poses_cw, fixed_cw, points, obs32, n_obs, should_stop=None):
         """ba_solve_visual with the observations in device memory (orbx_ba_solve_visual_obs32_device): obs32 is a CUDA tensor whose
         first 16 * n_obs bytes are BA_OBS32 records (map_collect_ba_window_device's), 16-byte aligned.  Poses and points are host
@@ -2351,6 +2433,7 @@ class KeyFrame:
             [C.c_void_p] * 6
         L.orbx_keyframe_fuse_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_uint,
                                                 C.c_void_p, C.c_void_p]
+        L.orbx_keyframe_get_map_point_slots.argtypes = [C.c_void_p, C.c_void_p]
         self._p = C.c_void_p()
         pose = np.ascontiguousarray(pose_wc, np.float64).reshape(7)
         handle._after_torch()
@@ -2383,6 +2466,13 @@ class KeyFrame:
         a = np.array([-1 if m is None else int(m) for m in slots], np.int32)
         assert len(a) == self.n
         self._handle._check(self._L.orbx_keyframe_set_map_point_slots(self._p, mp._p, _vp(a if self.n else np.zeros(1, np.int32))))
+
+    def get_map_point_slots(self):
+        """The slot table [n] int32 as it lies in device memory (orbx_keyframe_get_map_point_slots; every entry -1 without a table):
+        what map_fuse / map_search_in_neighbors left, for the caller to apply to its ids.  Synchronous."""
+        a = np.full(max(self.n, 1), -1, np.int32)
+        self._handle._check(self._L.orbx_keyframe_get_map_point_slots(self._p, _vp(a)))
+        return a[:self.n].copy()
 
     def map_points(self):
         a = np.zeros(max(self.n, 1), np.int64)

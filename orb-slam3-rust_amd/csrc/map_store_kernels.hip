@@ -45,12 +45,15 @@
 // mp.observations (map_point.rs:140-156), the inverse of the slot tables, is derived the same way for the points a call names:
 // the lists behind orbx_map_observations and orbx_map_refresh_points (search_in_neighbors.rs:139-150) and the counts behind
 // orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
+// The fuse and merge phases of search_in_neighbors (search_in_neighbors.rs:240-390, map.rs:770-868) act on the tables themselves:
+// orbx_map_fuse[_device] and orbx_map_search_in_neighbors; the kernels are described where they stand ("fuse and merge", below).
 // The sums, the ordered append and the scans of counts are block_dev.hpp's: every thread of a workgroup reaches each of them.
 #include <algorithm>
 #include <numeric>
 #include <vector>
 
 #include "block_dev.hpp"
+#include "fuse_search_dev.hpp"
 #include "orbx_internal.hpp"
 
 struct orbx_map_points {
@@ -1386,6 +1389,505 @@ int red_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const RedP
   return obs_enqueue(h, mp, P.O, c);
 }
 
+// ---- fuse and merge (include/orbx.h, "fuse and merge on the resident map"; search_in_neighbors.rs:240-390, map.rs:770-...) ----
+// One pass fuse(src, tgt) over the tables where they lie.  L is one frame's ORBX_MAP_SOURCE_KEYFRAMES selection, unchanged, with its
+// gathered positions and descriptors; the marks are cov_mark_kernel's, one row per target; the observer counts obs_count_kernel's.
+// A node is a slot the pass may merge: L's entry j is node j; a live slot a matched feature names that is not in L is node
+// P + (the lowest j * n_tgt + t of the matches that name it).  index[slot] (row 0 of `first`) holds the node.
+//   mf_begin_kernel    index[L[j]] = j; counts = {P, 0, 0, 0}
+//   mf_search_kernel   (128 points, target): the mark test, then fuse_search_dev.hpp's search on the target's own arrays -> match
+//   mf_name_kernel     per match the live slot its feature names (atomicMin of the node on index) or a claim (atomicMin of j on
+//                      the feature's cell: the claimants of a feature meet in the lowest of them); the matches counted
+//   mf_class_kernel    one workgroup: every match is an edge (j, named node) or (j, lowest claimant); minimum-label propagation with
+//                      integer atomicMin to the fixed point — every node ends with the lowest node of its component
+//   mf_key_kernel      per class: packed (observers, order) maximum -> the keeper; members; whether it has a claim
+//   mf_goner_kernel    the members of classes of two or more that are not the keeper, through an atomic cursor;
+//   mf_goner_rank_kernel  the slots are distinct, so the number of smaller ones is a goner's place: that fixes the bytes
+//   mf_feat_kernel     (chunk, keyframe) over ALL keyframes: the class a feature belongs to by its entry or by a claim, and whether it
+//                      names the keeper
+//   mf_rewrite_kernel  (chunk, keyframe) every feature of a class walks its keyframe's features through LDS: does one name the keeper,
+//                      which is the lowest of the class; the new entry; the keyframes that changed; the associations counted
+//   mf_uniq_kernel     (chunk, keyframe) of a changed keyframe: d_mp_uniq again — an entry stays where no earlier feature holds it
+//   mf_restore_kernel  index back to EMPTY for L and every named slot
+// Every atomic is an integer min, max or add: the outputs are the same bytes whatever the execution order.
+
+constexpr int MF_CLASS_THREADS = 1024;
+
+struct MfTgt {                                   // one target of a pass
+  const orbx_keypoint* kp; const uint8_t* desc;  // where the resident keyframe keeps them
+  const int* slots;                              // its table WITH repeats
+  int n, feat_off;                               // its features; where they start among the targets' features (the claim cells)
+  double pose_cw[7];                             // the inverse of pose_wc, made on the host as orbx_fuse_search_device makes it
+};
+struct MfKf {                                    // one keyframe of kfs[] as the rewrite sees it
+  int* slots; int* uniq;                         // NULL: no table
+  int n, feat_off;                               // its features; where they start among all features of kfs[]
+  int tgt, pad_;                                 // its place in tgt[], -1: not a target
+};
+struct MfArgs {
+  orbx_camera cam;
+  double radius_scale;
+  unsigned thr;
+  int capacity, n_kfs, n_tgt;
+  const uint8_t* live; const uint8_t* mark;
+  const MfTgt* tgts; const MfKf* kfs;
+  const int* list_off; const int* list_slot; const double* list_pos; const uint8_t* list_desc;      // the selection's outputs: P = list_off[1]
+  int* index;                                    // the store's first-sighting table, row 0: EMPTY outside the launches below
+  int* match; int* match_e; int* edge;           // [P][n_tgt]: the feature; the live slot it names (-1: a claim, or no match); the other end's node
+  int* claim;                                    // [targets' features] the lowest claimant, EMPTY: none
+  int* nobs; int* label;                         // [nodes]
+  unsigned long long* key; int* csize; int* cclaim;   // [nodes], read at a class's label
+  int* feat_cls;                                 // [features of kfs[]] class label * 2 + (names the keeper), -1: in no class that changes a table
+  int* changed;                                  // [n_kfs]
+  int* cursor; int* tmp_goner; int* tmp_keeper;
+  int* counts; int* goner; int* keeper;
+};
+
+__device__ __forceinline__ bool mf_live(const MfArgs& A, int s) { return s >= 0 && s < A.capacity && A.live[s]; }
+// the slot behind a class's key: an entry of L (high bit: 0x7fffffff - j below it) or a slot outside it (0x7fffffff - slot)
+__device__ __forceinline__ int mf_key_slot(const MfArgs& A, unsigned long long key) {
+  const unsigned low = (unsigned)key;
+  return (low & 0x80000000u) ? A.list_slot[0x7fffffff - (int)(low & 0x7fffffffu)] : 0x7fffffff - (int)low;
+}
+// node id -> (is it a node, its slot, the order half of its key)
+__device__ __forceinline__ bool mf_node(const MfArgs& A, int P, int id, int* slot, unsigned* low) {
+  if (id < P) { *slot = A.list_slot[id]; *low = 0x80000000u | (unsigned)(0x7fffffff - id); return true; }
+  const int m = id - P;
+  if (A.match[m] < 0) return false;
+  const int e = A.match_e[m];
+  if (e < 0 || A.index[e] != id) return false;
+  *slot = e; *low = (unsigned)(0x7fffffff - e);
+  return true;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_begin_kernel(MfArgs A, int with_index) {
+  const int P = A.list_off ? A.list_off[1] : 0, i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (with_index && i < P) A.index[A.list_slot[i]] = i;
+  if (i < 4) A.counts[i] = i == 0 ? P : 0;
+}
+
+__global__ __launch_bounds__(FUSE_THREADS) void mf_search_kernel(MfArgs A) {
+  __shared__ FuseLds lds;
+  const int P = A.list_off[1], t = blockIdx.y, j = blockIdx.x * FUSE_THREADS + threadIdx.x;
+  if ((int)(blockIdx.x * FUSE_THREADS) >= P) return;                       // (the block's: every thread of a block that stays reaches the barriers)
+  const MfTgt g = A.tgts[t];
+  const size_t jc = (size_t)(j < P ? j : 0);
+  const bool valid = j < P && !A.mark[(size_t)t * A.capacity + A.list_slot[jc]];      // :272, in front of the projection
+  const unsigned long long best = fuse_search_point(A.cam, valid, A.list_pos + 3 * jc, A.list_desc + 32 * jc, A.tgts[t].pose_cw, g.kp, g.desc, g.n,
+                                                    A.radius_scale, A.thr, lds);
+  if (j < P) A.match[(size_t)j * A.n_tgt + t] = best == ~0ull ? -1 : (int)(unsigned)(best & 0xffffffffull);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_name_kernel(MfArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const int P = A.list_off[1], T = A.n_tgt, m = blockIdx.x * MS_THREADS + threadIdx.x;
+  int hit = 0;
+  if (m < P * T) {
+    const int f = A.match[m];
+    int e = -1;
+    if (f >= 0) {
+      const int j = m / T;
+      const MfTgt& g = A.tgts[m - j * T];
+      hit = 1;
+      e = g.slots[f];
+      if (mf_live(A, e)) atomicMin(&A.index[e], P + m);
+      else { e = -1; atomicMin(&A.claim[g.feat_off + f], j); }
+    }
+    A.match_e[m] = e;
+  }
+  hit = block_sum<MS_THREADS>(hit, wave_tot);
+  if (threadIdx.x == 0 && hit) atomicAdd(&A.counts[1], hit);
+}
+
+__global__ __launch_bounds__(MF_CLASS_THREADS) void mf_class_kernel(MfArgs A) {
+  __shared__ int again;
+  const int P = A.list_off[1], T = A.n_tgt, M = P * T, N = P + M, tid = threadIdx.x;
+  for (int id = tid; id < N; id += MF_CLASS_THREADS) A.label[id] = id;
+  for (int m = tid; m < M; m += MF_CLASS_THREADS) {
+    const int f = A.match[m];
+    int o = -1;
+    if (f >= 0) {
+      const int e = A.match_e[m];
+      o = e >= 0 ? A.index[e] : A.claim[A.tgts[m % T].feat_off + f];
+    }
+    A.edge[m] = o;
+  }
+  __threadfence();
+  for (;;) {
+    __syncthreads();                                                       // (the labels and edges written above; the flag read below)
+    if (tid == 0) again = 0;
+    __syncthreads();
+    bool moved = false;
+    for (int m = tid; m < M; m += MF_CLASS_THREADS) {
+      const int o = A.edge[m];
+      if (o < 0) continue;
+      const int a = m / T;
+      const int la = __hip_atomic_load(&A.label[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int lb = __hip_atomic_load(&A.label[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (la == lb) continue;
+      const int lo = min(la, lb);
+      atomicMin(&A.label[a], lo); atomicMin(&A.label[o], lo);
+      atomicMin(&A.label[max(la, lb)], lo);                                // (the higher label's own node: its other members follow in the step below)
+      moved = true;
+    }
+    __syncthreads();
+    for (int id = tid; id < N; id += MF_CLASS_THREADS) {
+      const int l = __hip_atomic_load(&A.label[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int ll = __hip_atomic_load(&A.label[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (ll < l) { atomicMin(&A.label[id], ll); moved = true; }
+    }
+    if (moved) again = 1;
+    __syncthreads();
+    if (!again) break;                                                     // (the same in every thread: nothing writes it before the next barrier)
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_key_kernel(MfArgs A) {
+  const int P = A.list_off[1], id = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (id >= P + P * A.n_tgt) return;
+  int slot; unsigned low;
+  if (mf_node(A, P, id, &slot, &low)) {
+    const int c = A.label[id];
+    atomicMax(&A.key[c], ((unsigned long long)(unsigned)A.nobs[id] << 32) | low);
+    atomicAdd(&A.csize[c], 1);
+  }
+  if (id >= P && A.match[id - P] >= 0 && A.match_e[id - P] < 0) A.cclaim[A.label[(id - P) / A.n_tgt]] = 1;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_goner_kernel(MfArgs A) {
+  const int P = A.list_off[1], id = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (id >= P + P * A.n_tgt) return;
+  int slot; unsigned low;
+  if (!mf_node(A, P, id, &slot, &low)) return;
+  const int c = A.label[id];
+  const unsigned long long key = A.key[c];
+  if (A.csize[c] < 2 || (unsigned)key == low) return;
+  const int at = atomicAdd(A.cursor, 1);
+  A.tmp_goner[at] = slot; A.tmp_keeper[at] = mf_key_slot(A, key);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_goner_rank_kernel(MfArgs A) {
+  __shared__ int tile[MS_THREADS];
+  const int G = *A.cursor, tid = threadIdx.x, e = blockIdx.x * MS_THREADS + tid;
+  if (blockIdx.x == 0 && tid == 0) A.counts[3] = G;
+  if ((int)(blockIdx.x * MS_THREADS) >= G) return;                         // (the block's)
+  const int s = e < G ? A.tmp_goner[e] : 0x7fffffff;
+  int rank = 0;
+  for (int j0 = 0; j0 < G; j0 += MS_THREADS) {
+    __syncthreads();
+    tile[tid] = j0 + tid < G ? A.tmp_goner[j0 + tid] : 0x7fffffff;
+    __syncthreads();
+    const int n = min(MS_THREADS, G - j0);
+    for (int t = 0; t < n; ++t) rank += tile[t] < s;
+  }
+  if (e < G) { A.goner[rank] = s; A.keeper[rank] = A.tmp_keeper[e]; }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_feat_kernel(MfArgs A) {
+  const MfKf kf = A.kfs[blockIdx.y];
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i >= kf.n) return;
+  int cls = -1;
+  if (kf.slots) {
+    const int e = kf.slots[i];
+    if (mf_live(A, e)) {
+      const int id = A.index[e];
+      if (id != MS_EMPTY) {
+        const int c = A.label[id];
+        if (A.csize[c] >= 2 || A.cclaim[c]) cls = 2 * c + (mf_key_slot(A, A.key[c]) == e ? 1 : 0);
+      }
+    } else if (kf.tgt >= 0) {
+      const int j = A.claim[A.tgts[kf.tgt].feat_off + i];
+      if (j != MS_EMPTY) cls = 2 * A.label[j];
+    }
+  }
+  A.feat_cls[kf.feat_off + i] = cls;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_rewrite_kernel(MfArgs A) {
+  __shared__ int tile[MS_THREADS];
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const MfKf kf = A.kfs[blockIdx.y];
+  const int tid = threadIdx.x, i = blockIdx.x * MS_THREADS + tid;
+  if (!kf.slots || (int)(blockIdx.x * MS_THREADS) >= kf.n) return;         // (the block's)
+  const int* cls = A.feat_cls + kf.feat_off;
+  const int mine = i < kf.n ? cls[i] : -1;
+  if (!__syncthreads_or(mine >= 0)) return;
+  const int c = mine >> 1;
+  int lowest = -1;
+  bool names = false;
+  for (int j0 = 0; j0 < kf.n; j0 += MS_THREADS) {
+    __syncthreads();
+    tile[tid] = j0 + tid < kf.n ? cls[j0 + tid] : -1;
+    __syncthreads();
+    if (mine < 0) continue;
+    const int n = min(MS_THREADS, kf.n - j0);
+    for (int t = 0; t < n; ++t) {
+      const int v = tile[t];
+      if (v < 0 || (v >> 1) != c) continue;
+      names |= (v & 1) != 0;
+      if (lowest < 0) lowest = j0 + t;
+    }
+  }
+  int added = 0;
+  if (mine >= 0) {
+    const int old = kf.slots[i];
+    const int now = names ? ((mine & 1) ? old : -1) : i == lowest ? mf_key_slot(A, A.key[c]) : -1;
+    if (now != old) { kf.slots[i] = now; A.changed[blockIdx.y] = 1; }
+    added = now >= 0 && !mf_live(A, old);
+  }
+  added = block_sum<MS_THREADS>(added, wave_tot);
+  if (tid == 0 && added) atomicAdd(&A.counts[2], added);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_uniq_kernel(MfArgs A) {
+  __shared__ int tile[MS_THREADS];
+  const MfKf kf = A.kfs[blockIdx.y];
+  const int tid = threadIdx.x, i = blockIdx.x * MS_THREADS + tid;
+  if (!kf.slots || !A.changed[blockIdx.y] || (int)(blockIdx.x * MS_THREADS) >= kf.n) return;      // (the block's)
+  const int s = i < kf.n ? kf.slots[i] : -1;
+  bool earlier = false;
+  for (int j0 = 0; j0 <= (int)(blockIdx.x * MS_THREADS); j0 += MS_THREADS) {
+    __syncthreads();
+    tile[tid] = j0 + tid < kf.n ? kf.slots[j0 + tid] : -1;
+    __syncthreads();
+    const int n = min(MS_THREADS, i - j0);                                 // the features before i
+    for (int t = 0; t < n; ++t) earlier |= tile[t] == s;
+  }
+  if (i < kf.n) kf.uniq[i] = s >= 0 && !earlier ? s : -1;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_restore_kernel(MfArgs A) {
+  const int P = A.list_off[1], id = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (id >= P + P * A.n_tgt) return;
+  if (id < P) A.index[A.list_slot[id]] = MS_EMPTY;
+  else if (A.match[id - P] >= 0 && A.match_e[id - P] >= 0) A.index[A.match_e[id - P]] = MS_EMPTY;
+}
+
+// A pass, checked and sized on the host.
+struct MfPlan {
+  SelPlan S;                                     // L: one frame whose keyframes are kfs[src[..]]
+  std::vector<CovKf> ckfs;
+  std::vector<CovMember> members;
+  std::vector<MfTgt> tgts;
+  std::vector<MfKf> kfs;
+  int bound = 0, f_tgt = 0, n_feat = 0, max_n = 0, goner_bound = 0;
+};
+
+// se3.rs:56-63 as orbx_fuse_search_device makes it (orbx_api.hip: quat_rotate, one IEEE operation at a time)
+void mf_pose_inverse(const double* p, double* o) {
+  const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
+  const double* v = p + 4;
+  const double t0 = 2.0 * (y * v[2] - z * v[1]), t1 = 2.0 * (z * v[0] - x * v[2]), t2 = 2.0 * (x * v[1] - y * v[0]);
+  const double c0 = y * t2 - z * t1, c1 = z * t0 - x * t2, c2 = x * t1 - y * t0;
+  o[0] = w; o[1] = x; o[2] = y; o[3] = z;
+  o[4] = -(t0 * w + c0 + v[0]); o[5] = -(t1 * w + c1 + v[1]); o[6] = -(t2 * w + c2 + v[2]);
+}
+
+// what can be refused: nothing is enqueued and no keyframe touched
+int mf_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src,
+             int n_tgt, const int* tgt, unsigned desc_threshold) {
+  if (!cam) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (n_kfs < 0 || n_kfs > 0xffff || (n_kfs > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_kfs <= 65535: the keyframe is a grid dimension)", who);
+  if (n_src < 0 || n_tgt < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (n_src >= 0, n_tgt >= 0)", who);
+  if (desc_threshold > 256) return orbx_fail(h, ORBX_ERR_INVALID, "%s: desc_threshold %u is above 256", who, desc_threshold);
+  if (int rc = cov_check_queries(h, who, "src", n_src, src, n_kfs, 0)) return rc;
+  if (int rc = cov_check_queries(h, who, "tgt", n_tgt, tgt, n_kfs, 0)) return rc;
+  std::vector<const orbx_keyframe*> seen((size_t)n_kfs);
+  for (int t = 0; t < n_kfs; ++t) {
+    if (int rc = ms_check_keyframe(h, who, mp, kfs[t], t)) return rc;
+    seen[(size_t)t] = kfs[t];
+  }
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return orbx_fail(h, ORBX_ERR_INVALID, "%s: a keyframe is listed twice in kfs[] (their tables are rewritten)", who);
+  std::vector<uint8_t> is_tgt((size_t)n_kfs, 0);
+  for (int t = 0; t < n_tgt; ++t) {
+    if (is_tgt[(size_t)tgt[t]]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: tgt[%d] = %d is listed twice", who, t, tgt[t]);
+    is_tgt[(size_t)tgt[t]] = 1;
+  }
+  return ORBX_OK;
+}
+
+// A target without a table gets one, every entry -1: what the absence of a table means to every reader, and room for associations.
+int mf_give_tables(orbx_handle* h, const orbx_map_points* mp, orbx_keyframe* const* kfs, int n_tgt, const int* tgt) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  for (int t = 0; t < n_tgt; ++t) {
+    orbx_keyframe* kf = kfs[tgt[t]];
+    if (kf->slot_store) continue;
+    if (kf->n > 0) {
+      ORBX_HIP(h, hipMemsetAsync(kf->d_mp_slot, 0xff, 4 * (size_t)kf->n, h->stream));
+      ORBX_HIP(h, hipMemsetAsync(kf->d_mp_uniq, 0xff, 4 * (size_t)kf->n, h->stream));
+    }
+    kf->slot_store = mp;
+  }
+  return ORBX_OK;
+}
+
+// behind mf_check and mf_give_tables
+int mf_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src, int n_tgt, const int* tgt,
+            MfPlan& P) {
+  std::vector<const orbx_keyframe*> sk((size_t)n_src);
+  for (int i = 0; i < n_src; ++i) sk[(size_t)i] = kfs[src[i]];
+  const int off[2] = {0, n_src};
+  if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, sk.data(), off, nullptr, P.S)) return rc;
+  P.bound = P.S.bound_off[1];
+  P.ckfs.resize((size_t)n_kfs); P.kfs.resize((size_t)n_kfs); P.tgts.resize((size_t)n_tgt); P.members.resize((size_t)n_tgt);
+  long long total = 0;
+  for (int k = 0; k < n_kfs; ++k) {
+    orbx_keyframe* kf = kfs[k];
+    P.ckfs[(size_t)k] = CovKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, 0};
+    P.kfs[(size_t)k] = MfKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, (int)total, -1, 0};
+    total += kf->n; P.max_n = std::max(P.max_n, kf->n);
+    if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+  }
+  P.n_feat = (int)total;
+  long long ft = 0;
+  for (int t = 0; t < n_tgt; ++t) {
+    const orbx_keyframe* kf = kfs[tgt[t]];
+    MfTgt& g = P.tgts[(size_t)t];
+    g.kp = kf->d_kp; g.desc = kf->d_desc; g.slots = kf->d_mp_slot; g.n = kf->n; g.feat_off = (int)ft;
+    mf_pose_inverse(kf->pose_wc, g.pose_cw);
+    P.kfs[(size_t)tgt[t]].tgt = t;
+    P.members[(size_t)t] = CovMember{tgt[t], t};
+    ft += kf->n;
+  }
+  P.f_tgt = (int)ft;
+  if ((long long)P.bound * (1 + (long long)n_tgt) >= MS_EMPTY) return orbx_fail(h, ORBX_ERR_INVALID, "%s: too many (point, target) pairs", who);
+  P.goner_bound = (int)std::min<long long>((long long)P.bound + ft, 0x7fffffff);
+  return ORBX_OK;
+}
+
+// The pass on the handle's stream.  Every output is device memory; d_list_slot [bound], d_match [bound][n_tgt], d_goner / d_keeper
+// [goner_bound].
+int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map_points* mp, const MfPlan& P, double radius_scale, unsigned desc_threshold,
+               int* d_counts, int* d_list_slot, int* d_match, int* d_goner, int* d_keeper) {
+  const size_t K = P.kfs.size(), T = P.tgts.size(), B = (size_t)P.bound, Nb = B * (1 + T), Gb = (size_t)P.goner_bound;
+  const bool run = B > 0 && T > 0;
+  if (!d_counts || (B > 0 && !d_list_slot) || (run && (!d_match || !d_goner || !d_keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  Carve ws, up;
+  const size_t o_lo = ws.take(8), o_po = ws.take(24 * B), o_de = ws.take(32 * B);
+  const size_t o_me = ws.take(run ? 4 * B * T : 0), o_ed = ws.take(run ? 4 * B * T : 0), o_la = ws.take(run ? 4 * Nb : 0), o_fc = ws.take(run ? 4 * (size_t)P.n_feat : 0),
+               o_tg = ws.take(run ? 4 * Gb : 0), o_tk = ws.take(run ? 4 * Gb : 0), o_cl = ws.take(run ? 4 * (size_t)P.f_tgt : 0);
+  const size_t o_zero = ws.off;                                             // zeroed before every pass: observer counts, keys, sizes, claim flags, changed, cursor
+  const size_t o_no = ws.take(run ? 4 * Nb : 0), o_ke = ws.take(run ? 8 * Nb : 0), o_cs = ws.take(run ? 4 * Nb : 0), o_cc = ws.take(run ? 4 * Nb : 0),
+               o_ch = ws.take(run ? 4 * K : 0), o_cu = ws.take(run ? 4 : 0);
+  if (int rc = orbx_reserve(h, h->ws_map[11], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[11].p;
+  MfArgs A{};
+  A.counts = d_counts;
+  const dim3 block(MS_THREADS);
+  if (B == 0) {                                                             // no candidate: P = 0
+    ProfScope ps(h, "mf_begin_kernel");
+    hipLaunchKernelGGL(mf_begin_kernel, dim3(1), block, 0, h->stream, A, 0);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  }
+  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, P.bound, (int*)(w + o_lo), d_list_slot, (double*)(w + o_po), w + o_de))
+    return rc;
+  A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot; A.list_pos = (const double*)(w + o_po); A.list_desc = w + o_de;
+  A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
+  const dim3 list_grid((unsigned)((B + MS_THREADS - 1) / MS_THREADS));
+  if (!run) {
+    ProfScope ps(h, "mf_begin_kernel", true);
+    hipLaunchKernelGGL(mf_begin_kernel, dim3(1), block, 0, h->stream, A, 0);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  }
+  const size_t need = T * (size_t)mp->capacity;
+  if (mp->mark.bytes < need) {                                              // the one fill of the tables: calls leave them 0
+    if (int rc = orbx_reserve(h, mp->mark, need)) return rc;
+    ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
+  }
+  const size_t u_ck = up.take(sizeof(CovKf) * K), u_me = up.take(sizeof(CovMember) * T), u_tg = up.take(sizeof(MfTgt) * T), u_kf = up.take(sizeof(MfKf) * K);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[12], up.off, &hs, &ds)) return rc;
+  std::memcpy(hs + u_ck, P.ckfs.data(), sizeof(CovKf) * K); std::memcpy(hs + u_me, P.members.data(), sizeof(CovMember) * T);
+  std::memcpy(hs + u_tg, P.tgts.data(), sizeof(MfTgt) * T); std::memcpy(hs + u_kf, P.kfs.data(), sizeof(MfKf) * K);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[12], up.off)) return rc;
+  ORBX_HIP(h, hipMemsetAsync(w + o_zero, 0, ws.off - o_zero, h->stream));
+  if (P.f_tgt > 0) ORBX_HIP(h, hipMemsetAsync(w + o_cl, MS_EMPTY & 0xff, 4 * (size_t)P.f_tgt, h->stream));
+  A.cam = *cam; A.radius_scale = radius_scale; A.thr = desc_threshold;
+  A.capacity = mp->capacity; A.n_kfs = (int)K; A.n_tgt = (int)T;
+  A.live = mp->d_live; A.mark = (const uint8_t*)mp->mark.p;
+  A.tgts = (const MfTgt*)(ds + u_tg); A.kfs = (const MfKf*)(ds + u_kf);
+  A.match = d_match; A.match_e = (int*)(w + o_me); A.edge = (int*)(w + o_ed); A.claim = (int*)(w + o_cl);
+  A.nobs = (int*)(w + o_no); A.label = (int*)(w + o_la); A.key = (unsigned long long*)(w + o_ke); A.csize = (int*)(w + o_cs); A.cclaim = (int*)(w + o_cc);
+  A.feat_cls = (int*)(w + o_fc); A.changed = (int*)(w + o_ch); A.cursor = (int*)(w + o_cu); A.tmp_goner = (int*)(w + o_tg); A.tmp_keeper = (int*)(w + o_tk);
+  A.goner = d_goner; A.keeper = d_keeper;
+  CovArgs C{};
+  C.capacity = mp->capacity; C.n_kfs = (int)K; C.n_q = (int)T; C.live = mp->d_live; C.kfs = (const CovKf*)(ds + u_ck); C.members = (const CovMember*)(ds + u_me);
+  C.mark = (uint8_t*)mp->mark.p;
+  ObsArgs O{};
+  O.capacity = mp->capacity; O.n_kfs = (int)K; O.live = mp->d_live; O.kfs = C.kfs; O.index = A.index; O.count = A.nobs;
+  int max_tn = 0;
+  for (const MfTgt& g : P.tgts) max_tn = std::max(max_tn, g.n);
+  const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK), n_fine = std::max(1, (P.max_n + MS_THREADS - 1) / MS_THREADS);
+  const dim3 mark_grid(std::max(1, (max_tn + MS_CHUNK - 1) / MS_CHUNK), (unsigned)T), pair_grid((unsigned)((B * T + MS_THREADS - 1) / MS_THREADS)),
+      node_grid((unsigned)((Nb + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, (unsigned)K), feat_grid(n_fine, (unsigned)K);
+  {
+    ProfScope ps(h, "mf_begin_kernel", true);
+    hipLaunchKernelGGL(mf_begin_kernel, list_grid, block, 0, h->stream, A, 1);
+  }
+  {
+    ProfScope ps(h, "cov_mark_kernel", true);
+    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, C, 1);
+  }
+  {
+    ProfScope ps(h, "mf_search_kernel", true);
+    hipLaunchKernelGGL(mf_search_kernel, dim3((unsigned)((B + FUSE_THREADS - 1) / FUSE_THREADS), (unsigned)T), dim3(FUSE_THREADS), 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "cov_mark_kernel", true);
+    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, C, 0);
+  }
+  {
+    ProfScope ps(h, "mf_name_kernel", true);
+    hipLaunchKernelGGL(mf_name_kernel, pair_grid, block, 0, h->stream, A);
+  }
+  if (P.max_n > 0) {
+    ProfScope ps(h, "obs_count_kernel", true);
+    hipLaunchKernelGGL(obs_count_kernel, kf_grid, block, 0, h->stream, O);
+  }
+  {
+    ProfScope ps(h, "mf_class_kernel", true);
+    hipLaunchKernelGGL(mf_class_kernel, dim3(1), dim3(MF_CLASS_THREADS), 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "mf_key_kernel", true);
+    hipLaunchKernelGGL(mf_key_kernel, node_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "mf_goner_kernel", true);
+    hipLaunchKernelGGL(mf_goner_kernel, node_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "mf_goner_rank_kernel", true);
+    hipLaunchKernelGGL(mf_goner_rank_kernel, dim3((unsigned)std::max<size_t>(1, (Gb + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
+  }
+  if (P.max_n > 0) {
+    {
+      ProfScope ps(h, "mf_feat_kernel", true);
+      hipLaunchKernelGGL(mf_feat_kernel, feat_grid, block, 0, h->stream, A);
+    }
+    {
+      ProfScope ps(h, "mf_rewrite_kernel", true);
+      hipLaunchKernelGGL(mf_rewrite_kernel, feat_grid, block, 0, h->stream, A);
+    }
+    {
+      ProfScope ps(h, "mf_uniq_kernel", true);
+      hipLaunchKernelGGL(mf_uniq_kernel, feat_grid, block, 0, h->stream, A);
+    }
+  }
+  {
+    ProfScope ps(h, "mf_restore_kernel", true);
+    hipLaunchKernelGGL(mf_restore_kernel, node_grid, block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1886,6 +2388,132 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
   return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
                                  max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
                                  d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+}
+
+int orbx_keyframe_get_map_point_slots(const orbx_keyframe* kf, int* slots) {
+  if (!kf) return ORBX_ERR_INVALID;
+  orbx_handle* h = kf->h;
+  if (kf->n > 0 && !slots) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_get_map_point_slots: bad argument");
+  if (kf->n == 0) return ORBX_OK;
+  if (!kf->slot_store) { std::fill(slots, slots + kf->n, -1); return ORBX_OK; }       // no table: every feature -1
+  ORBX_HIP(h, hipSetDevice(h->device));
+  ORBX_HIP(h, hipMemcpyAsync(slots, kf->d_mp_slot, 4 * (size_t)kf->n, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  return ORBX_OK;
+}
+
+int orbx_map_fuse_device(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src, int n_tgt,
+                         const int* tgt, double radius_scale, unsigned desc_threshold, int list_cap, int* d_counts, int* d_list_slot, int* d_match, int* d_goner,
+                         int* d_keeper) {
+  static const char* who = "orbx_map_fuse_device";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
+  long long cand = 0;                                                       // L's bound, before anything is touched: the candidates, at most the capacity
+  for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
+  const long long bound = std::min<long long>(cand, mp->capacity);
+  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
+  if (!d_counts || (bound > 0 && !d_list_slot) || (bound > 0 && n_tgt > 0 && (!d_match || !d_goner || !d_keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
+  MfPlan P;
+  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
+  return mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, d_counts, d_list_slot, d_match, d_goner, d_keeper);
+}
+
+int orbx_map_fuse(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src, int n_tgt, const int* tgt,
+                  double radius_scale, unsigned desc_threshold, int list_cap, int* counts, int* list_slot, int* match, int* goner, int* keeper) {
+  static const char* who = "orbx_map_fuse";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
+  long long cand = 0;
+  for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
+  const long long bound = std::min<long long>(cand, mp->capacity);
+  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
+  if (!counts || (bound > 0 && !list_slot) || (bound > 0 && n_tgt > 0 && (!match || !goner || !keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
+  MfPlan P;
+  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
+  const size_t B = (size_t)P.bound, T = (size_t)n_tgt, Gb = (size_t)P.goner_bound;
+  Carve out;
+  const size_t o_cn = out.take(16), o_go = out.take(4 * Gb), o_ke = out.take(4 * Gb), o_ls = out.take(4 * B), o_ma = out.take(4 * B * T);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  orbx_prof_begin_call(h);
+  if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, (int*)(c.dout + o_cn), (int*)(c.dout + o_ls), (int*)(c.dout + o_ma), (int*)(c.dout + o_go),
+                          (int*)(c.dout + o_ke)))
+    return rc;
+  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+  std::memcpy(counts, c.ho + o_cn, 16);
+  const size_t Pn = (size_t)counts[0], G = (size_t)counts[3];
+  if (Pn) std::memcpy(list_slot, c.ho + o_ls, 4 * Pn);
+  if (Pn && T) std::memcpy(match, c.ho + o_ma, 4 * Pn * T);
+  if (G) { std::memcpy(goner, c.ho + o_go, 4 * G); std::memcpy(keeper, c.ho + o_ke, 4 * G); }
+  return G ? orbx_map_points_erase(mp, goner, (int)G) : ORBX_OK;
+}
+
+int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int cur, int n_nb, const int* nb,
+                                 double radius_scale, unsigned desc_threshold, double scale_range, const double* slot_normals, int goner_cap, int affected_cap,
+                                 int* counts, int* goner_a, int* keeper_a, int* goner_b, int* keeper_b, int* n_affected, int* affected_slot, uint8_t* mp_desc,
+                                 double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
+  static const char* who = "orbx_map_search_in_neighbors";
+  if (!h) return ORBX_ERR_INVALID;
+  if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
+  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, 1, &cur, n_nb, nb, desc_threshold)) return rc;
+  for (int i = 0; i < n_nb; ++i)
+    if (nb[i] == cur) return orbx_fail(h, ORBX_ERR_INVALID, "%s: nb[%d] is the current keyframe", who, i);
+  // the three lists' bounds, before anything is touched
+  long long f_nb = 0;
+  for (int i = 0; i < n_nb; ++i) f_nb += kfs[nb[i]]->n;
+  const long long cap = mp->capacity, f_cur = kfs[cur]->n;
+  const long long gb_a = std::min(f_cur, cap) + f_nb, gb_b = std::min(f_nb, cap) + f_cur, ab = std::min(f_cur + f_nb, cap);
+  if (f_cur + f_nb > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+  if (goner_cap < std::max(gb_a, gb_b)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: goner_cap %d is below the passes' bound %d", who, goner_cap, (int)std::max(gb_a, gb_b));
+  if (affected_cap < ab) return orbx_fail(h, ORBX_ERR_INVALID, "%s: affected_cap %d is below the list's bound %d (the features of cur and nb[], at most the capacity)", who, affected_cap, (int)ab);
+  if (!counts || !n_affected || (gb_a > 0 && (!goner_a || !keeper_a || !goner_b || !keeper_b)) ||
+      (ab > 0 && (!affected_slot || !mp_desc || !normals || !min_distance || !max_distance || !records)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  std::vector<int> both((size_t)n_nb + 1);
+  both[0] = cur;
+  for (int i = 0; i < n_nb; ++i) both[(size_t)i + 1] = nb[i];
+  if (int rc = mf_give_tables(h, mp, kfs, n_nb + 1, both.data())) return rc;
+  MfPlan A, B;
+  SelPlan S;
+  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, 1, &cur, n_nb, nb, A)) return rc;
+  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_nb, nb, 1, &cur, B)) return rc;
+  std::vector<const orbx_keyframe*> ak((size_t)n_nb + 1);
+  for (size_t i = 0; i < ak.size(); ++i) ak[i] = kfs[both[i]];
+  const int aoff[2] = {0, n_nb + 1};
+  if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ak.data(), aoff, nullptr, S)) return rc;
+  const size_t Ta = (size_t)n_nb, Ba = (size_t)A.bound, Bb = (size_t)B.bound, Ga = (size_t)A.goner_bound, Gb = (size_t)B.goner_bound, Ab = (size_t)S.bound_off[1];
+  // ONE download: counts A | counts B | goners and keepers of A, of B | the affected list; behind it what stays on the device
+  Carve out;
+  const size_t o_cn = out.take(32), o_ga = out.take(4 * Ga), o_ka = out.take(4 * Ga), o_gb = out.take(4 * Gb), o_kb = out.take(4 * Gb), o_ao = out.take(8),
+               o_as = out.take(4 * Ab);
+  const size_t down = out.off;
+  const size_t o_la = out.take(4 * Ba), o_ma = out.take(4 * Ba * Ta), o_lb = out.take(4 * Bb), o_mb = out.take(4 * Bb), o_ap = out.take(24 * Ab), o_ad = out.take(32 * Ab);
+  // (the refresh below is a host form of its own: it takes the pinned buffer and the blob workspace once everything is copied out of them)
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  uint8_t* d = c.dout;
+  orbx_prof_begin_call(h);
+  if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, (int*)(d + o_cn), (int*)(d + o_la), (int*)(d + o_ma), (int*)(d + o_ga), (int*)(d + o_ka))) return rc;
+  if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, (int*)(d + o_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), (int*)(d + o_gb), (int*)(d + o_kb))) return rc;
+  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, (int*)(d + o_ao), (int*)(d + o_as), (double*)(d + o_ap), d + o_ad))
+    return rc;
+  if (int rc = orbx_host_call_download(h, c, down)) return rc;
+  std::memcpy(counts, c.ho + o_cn, 32);
+  const size_t na = (size_t)counts[3], nbg = (size_t)counts[7], M = (size_t)((const int*)(c.ho + o_ao))[1];
+  if (na) { std::memcpy(goner_a, c.ho + o_ga, 4 * na); std::memcpy(keeper_a, c.ho + o_ka, 4 * na); }
+  if (nbg) { std::memcpy(goner_b, c.ho + o_gb, 4 * nbg); std::memcpy(keeper_b, c.ho + o_kb, 4 * nbg); }
+  *n_affected = (int)M;
+  if (M) std::memcpy(affected_slot, c.ho + o_as, 4 * M);
+  if (na) if (int rc = orbx_map_points_erase(mp, goner_a, (int)na)) return rc;
+  if (nbg) if (int rc = orbx_map_points_erase(mp, goner_b, (int)nbg)) return rc;
+  if (M == 0) return ORBX_OK;
+  for (size_t i = 0; i < M; ++i) {
+    const double* v = slot_normals ? slot_normals + 3 * (size_t)affected_slot[i] : nullptr;
+    normals[3 * i] = v ? v[0] : 0.0; normals[3 * i + 1] = v ? v[1] : 0.0; normals[3 * i + 2] = v ? v[2] : 0.0;
+  }
+  return orbx_map_refresh_points(h, mp, n_kfs, kfs, (int)M, affected_slot, scale_range, mp_desc, normals, min_distance, max_distance, records);
 }
 
 }  // extern "C"

@@ -242,7 +242,7 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
-  DevBuf ws_map[11];                     // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs, [8] observations: counts, cursors, block sums and the unordered entries; the redundancy call's list and chunk sums, [9] observations: the call's keyframe table, slots and candidates, [10] orbx_map_refresh_points: the lists and the gathered positions
+  DevBuf ws_map[13];                     // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs, [8] observations: counts, cursors, block sums and the unordered entries; the redundancy call's list and chunk sums, [9] observations: the call's keyframe table, slots and candidates, [10] orbx_map_refresh_points: the lists and the gathered positions, [11] fuse and merge: L's gathered rows, matches, edges, claims, per-node and per-feature scratch, [12] fuse and merge: the call's keyframe and target tables
   PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
   UploadRing ring_map;                   // the tables on their way to ws_map[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
