@@ -1336,7 +1336,7 @@ int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs,
  *
  * orbx_keyframe_get_map_point_slots: the table as it lies in device memory (every entry -1 without one); synchronous.
  * Still the caller's: the choice of the neighbours, ids and the id -> slot map (goner / keeper and the tables read back say what to
- * apply), removal, normals. */
+ * apply), normals; removal: orbx_map_remove_points, below. */
 int orbx_keyframe_get_map_point_slots(const orbx_keyframe* kf, int* slots);
 int orbx_map_fuse_device(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src,
                          const int* src, int n_tgt, const int* tgt, double radius_scale, unsigned desc_threshold, int list_cap,
@@ -1349,6 +1349,79 @@ int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_ma
                                  const double* slot_normals, int goner_cap, int affected_cap, int* counts, int* goner_a, int* keeper_a,
                                  int* goner_b, int* keeper_b, int* n_affected, int* affected_slot, uint8_t* mp_desc, double* normals,
                                  double* min_distance, double* max_distance, orbx_mp_refresh_record* records);
+
+/* ---- create and cull map points on the resident map (local_mapper.rs:105-142: steps 2, 3, 3b and 5 of process_keyframe) -------------
+ * The steps of process_keyframe that WRITE the tables and the store, so that a keyframe goes extractor -> tracking -> insertion ->
+ * new points -> fuse -> BA -> cull with its tables never leaving the device.  Conventions are those of the fuse block: kfs / nbs /
+ * free_slots / slots / cand are host arrays copied before the call returns, all work is ordered on the handle's stream, a refusal
+ * is ORBX_ERR_INVALID before anything is enqueued with tables, store and outputs untouched, the outputs are the same bytes on every
+ * run, no launch is sized by the capacity, and "names a live point" means an entry s with 0 <= s < capacity and live[s].
+ *
+ * orbx_keyframe_set_map_point_slots_device (step 2, associate_matched_points :208-223): orbx_keyframe_set_map_point_slots from a
+ * device array d_slots [n] (4-byte aligned), e.g. the tracker's d_matched_slot row; asynchronous, no synchronisation.
+ *   [spec] a value outside [-1, capacity) is stored as -1: the host cannot check it without a wait.
+ *   d_mp_uniq is made on the device (the first feature that names a slot keeps it); on in-range input the table and d_mp_uniq are
+ *   byte for byte the host form's.
+ *
+ * orbx_map_create_points[_device] (steps 3 and 3b: triangulate_new_points :232-268, triangulate_from_neighbors triangulation.rs:71-308
+ * with create_map_point and the associate calls).  phases: ORBX_MAP_CREATE_STEREO | ORBX_MAP_CREATE_NEIGHBOURS.  free_slots [n_free]:
+ * the slots the new points take, in creation order (the caller owns the id -> slot map); every list holds n_free rows and only
+ * created points are listed.  All reads are of the state at entry unless said.
+ *   [spec] flag(k, i) = the table of keyframe k names a live point at feature i.  A keyframe without a table has every flag 0 and is
+ *     given a table of -1 when the call is accepted.  d_mp_flag and mp_ids are neither read nor written.
+ *   [spec] stereo phase: the candidates are the features i of cur in ascending i with has_point[i] && !flag(cur, i); S is their number.
+ *     Candidate r takes free_slots[r] if r < n_free: position pose_wc(cur) * points_cam[i] (rotation matrix, then translation),
+ *     descriptor = cur's row i, table(cur)[i] = the slot, listed with new_neighbour = -1 and new_idx2 = -1.  A candidate with
+ *     r >= n_free is dropped: no slot, no table write, its flag stays 0.  S' = min(S, n_free).
+ *   [spec] neighbour phase: the searches, the pair loop, the ordered compaction and stats [T][4] of
+ *     orbx_keyframe_triangulate_from_neighbors(cur, nbs[0..T)), with flag(cur, .) | "given a slot by the stereo phase" and
+ *     flag(nbs[t], .) in place of the keyframes' d_mp_flag.  N = the validated pairs, in creation order (neighbour, then the search's
+ *     pair order).  Pair e takes free_slots[S' + e] if that exists: the triangulated position, descriptor = cur's row idx1
+ *     (triangulation.rs:280), table(nbs[t])[idx2] = the slot, and table(cur)[idx1] = the slot of the LAST created pair with that idx1:
+ *     the reference clones the current keyframe's flags before the loop (:94-107), so one feature is matched in several neighbours
+ *     and each associate overwrites the one before (:289).
+ *   [spec] counts [4] = {S, N, created, dropped}, created = min(S + N, n_free), dropped = S + N - created.
+ *   Deviation: the earlier points of a feature matched in several neighbours are created all the same and are observed by their
+ *   neighbour only (observations are derived from the tables); the reference's mp.observations still lists the current keyframe.
+ *   d_mp_uniq of every keyframe whose table changed is made again.
+ *   PRECONDITION (the caller's): no table names a slot handed over as free — orbx_map_remove_points guarantees it.
+ * orbx_map_create_points_device: asynchronous, no host synchronisation inside; the epipolar geometry and the node ranges are made on
+ *   the host and go up with the other tables.  It leaves the store untouched (positions, descriptors, live bytes, mirror): the
+ *   caller makes the points live with orbx_map_points_set_device(mp, free_slots, created, d_new_points, d_new_desc) once it has read
+ *   d_counts; until then every reader skips the new entries as not live.  d_new_desc [n_free][32] is 16-byte aligned.
+ * orbx_map_create_points: the device form into a workspace, ONE download (counts, lists, stats), then that set_device for the first
+ *   `created` slots: orbx_map_points_download of new_slot gives new_points and the descriptor rows byte for byte.
+ * Refused: T outside [0, 256], max_descriptor_dist > 256, cur among nbs or a neighbour twice, a keyframe of another handle or bound to
+ * another store, phases outside 1..3, n_free < 0, a free slot outside [0, capacity), listed twice or live.  n_free = 0 is accepted:
+ * counts and stats are written, nothing else.
+ *
+ * orbx_map_remove_points (remove_map_point_full, map.rs:609-631, for a list): every entry, repeats included, of d_mp_slot and
+ * d_mp_uniq of kfs[] that names a listed slot becomes -1, then the slots are erased as orbx_map_points_erase does.  slots [n] is
+ * checked like erase's (repeats allowed); a slot that is not live is accepted and its stale entries are purged too.  n_cleared: the
+ * table entries (of d_mp_slot) cleared — NULL: nothing is downloaded and the call does not wait; else one 4-byte download.  A keyframe
+ * outside kfs[] is not touched; a keyframe twice in kfs[] is refused.
+ *
+ * orbx_map_cull_points (cull_map_points :421-469): cand [M] is checked like orbx_map_observations' slots (in range, once, live).
+ *   [spec] culled = the candidates with n_observers(s) < min_observations (the observations block's count over kfs[]), in cand order;
+ *   then orbx_map_remove_points on them.  Synchronous, one download (the counts: the store's mirror needs the list).
+ * found_ratio is 1.0 in the reference and its in-grace rule (:443) can never fire, because nothing increments visible_count; the
+ * grace period and is_bad are the caller's, exercised through its choice of cand.
+ * Still the caller's: ids and the id -> slot map, the choice of the neighbours, growth of the store, normals, keyframe removal. */
+#define ORBX_MAP_CREATE_STEREO 1
+#define ORBX_MAP_CREATE_NEIGHBOURS 2
+int orbx_keyframe_set_map_point_slots_device(orbx_keyframe* kf, const orbx_map_points* mp, const int* d_slots);
+int orbx_map_create_points_device(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                                  orbx_map_points* mp, orbx_keyframe* cur, orbx_keyframe* const* nbs, int T, int phases,
+                                  const int* free_slots, int n_free, int* d_counts, int* d_new_slot, int* d_new_neighbour,
+                                  int* d_new_idx1, int* d_new_idx2, double* d_new_points, uint8_t* d_new_desc, int* d_stats);
+int orbx_map_create_points(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial,
+                           orbx_map_points* mp, orbx_keyframe* cur, orbx_keyframe* const* nbs, int T, int phases, const int* free_slots,
+                           int n_free, int* counts, int* new_slot, int* new_neighbour, int* new_idx1, int* new_idx2, double* new_points,
+                           int* stats);
+int orbx_map_remove_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n, const int* slots,
+                           int* n_cleared);
+int orbx_map_cull_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* cand,
+                         int min_observations, int* n_culled, int* culled);
 
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and

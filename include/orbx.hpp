@@ -1306,6 +1306,73 @@ inline std::vector<int> keyframe_map_point_slots(Handle& h, const orbx_keyframe*
   return slots;
 }
 
+// ---- create and cull map points on the resident map (orbx.h, "create and cull map points on the resident map") ----
+// orbx_keyframe_set_map_point_slots_device: the table from a device array [n] (the tracker's matched_slot row); asynchronous
+inline void keyframe_set_map_point_slots_device(Handle& h, orbx_keyframe* kf, MapPointStore& store, const int* d_slots) {
+  h.check(orbx_keyframe_set_map_point_slots_device(kf, store.get(), d_slots));
+}
+
+// Steps 3 and 3b of process_keyframe: the stereo points of `current` and the points triangulated with `neighbours` take free_slots
+// in creation order and are written into the keyframes' tables where they lie.
+struct MapCreatedPoints {
+  int n_stereo = 0, n_pairs = 0, dropped = 0;           // counts[0], counts[1], counts[3]; new_slot.size() is counts[2]
+  std::vector<int> new_slot, new_neighbour, new_idx1, new_idx2;        // in creation order; a stereo point has neighbour -1 and idx2 -1
+  std::vector<std::array<double, 3>> new_points;
+  std::vector<int> stats;                               // [T][4]: searched, matches_found, triangulated, validated
+};
+
+// orbx_map_create_points_device: every output is the caller's device memory (lists of free_slots.size() rows, d_new_desc 16-byte
+// aligned); asynchronous; the store is untouched until the caller's set_device for the first counts[2] slots.
+inline void map_create_points_device(Handle& h, const CameraModel& camera, const TriangulationConfig& config, bool is_inertial, MapPointStore& store,
+                                     orbx_keyframe* current, const std::vector<orbx_keyframe*>& neighbours, int phases, const std::vector<int>& free_slots,
+                                     int* d_counts, int* d_new_slot, int* d_new_neighbour, int* d_new_idx1, int* d_new_idx2, double* d_new_points,
+                                     uint8_t* d_new_desc, int* d_stats) {
+  const orbx_camera c = camera.c();
+  const orbx_triangulation_config cfg = config.c();
+  h.check(orbx_map_create_points_device(h.get(), &c, &cfg, is_inertial ? 1 : 0, store.get(), current, neighbours.data(), (int)neighbours.size(), phases,
+                                        free_slots.data(), (int)free_slots.size(), d_counts, d_new_slot, d_new_neighbour, d_new_idx1, d_new_idx2, d_new_points,
+                                        d_new_desc, d_stats));
+}
+
+// orbx_map_create_points: the same into host vectors cut to `created`, synchronous; the new points are live in the store afterwards.
+inline MapCreatedPoints map_create_points(Handle& h, const CameraModel& camera, const TriangulationConfig& config, bool is_inertial, MapPointStore& store,
+                                          orbx_keyframe* current, const std::vector<orbx_keyframe*>& neighbours, const std::vector<int>& free_slots,
+                                          int phases = ORBX_MAP_CREATE_STEREO | ORBX_MAP_CREATE_NEIGHBOURS) {
+  const size_t nf = std::max<size_t>(free_slots.size(), 1), T = neighbours.size();
+  MapCreatedPoints r;
+  int counts[4] = {0, 0, 0, 0};
+  r.new_slot.resize(nf); r.new_neighbour.resize(nf); r.new_idx1.resize(nf); r.new_idx2.resize(nf); r.new_points.resize(nf); r.stats.resize(4 * std::max<size_t>(T, 1));
+  const orbx_camera c = camera.c();
+  const orbx_triangulation_config cfg = config.c();
+  h.check(orbx_map_create_points(h.get(), &c, &cfg, is_inertial ? 1 : 0, store.get(), current, neighbours.data(), (int)T, phases, free_slots.data(),
+                                 (int)free_slots.size(), counts, r.new_slot.data(), r.new_neighbour.data(), r.new_idx1.data(), r.new_idx2.data(),
+                                 r.new_points[0].data(), r.stats.data()));
+  r.n_stereo = counts[0]; r.n_pairs = counts[1]; r.dropped = counts[3];
+  const size_t m = (size_t)counts[2];
+  r.new_slot.resize(m); r.new_neighbour.resize(m); r.new_idx1.resize(m); r.new_idx2.resize(m); r.new_points.resize(m); r.stats.resize(4 * T);
+  return r;
+}
+
+// orbx_map_remove_points (remove_map_point_full for a list): every entry of the tables of `keyframes` that names a listed slot
+// becomes -1, then the slots are erased.  Returns the table entries cleared; count = false: no download, no wait, -1.
+inline int map_remove_points(Handle& h, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, const std::vector<int>& slots, bool count = true) {
+  int n = -1;
+  h.check(orbx_map_remove_points(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)slots.size(), slots.data(), count ? &n : nullptr));
+  return n;
+}
+
+// orbx_map_cull_points (cull_map_points): the candidates observed by fewer than min_observations of `keyframes`, in their order,
+// removed as map_remove_points removes them.  The grace period and is_bad are the caller's, through its choice of candidates.
+inline std::vector<int> map_cull_points(Handle& h, MapPointStore& store, const std::vector<orbx_keyframe*>& keyframes, const std::vector<int>& candidates,
+                                        int min_observations) {
+  std::vector<int> culled(std::max<size_t>(candidates.size(), 1));
+  int n = 0;
+  h.check(orbx_map_cull_points(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)candidates.size(), candidates.data(), min_observations, &n,
+                               culled.data()));
+  culled.resize((size_t)n);
+  return culled;
+}
+
 // ---- track_with_reference_kf (orbx_track_reference, orbx.h): cross-checked matching against the reference keyframe, gather, PnP ----
 // One frame's input: its features, its reference keyframe's descriptors and, per keyframe feature, the map point's position and a
 // validity byte (1: kf.get_map_point(i) is Some and the map still holds that point, tracker.rs:1024-1036), and PnP's prior (T_wc).

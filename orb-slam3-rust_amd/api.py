@@ -105,8 +105,11 @@ ABI_SYMBOLS = [
     "orbx_map_observations_device", "orbx_map_observations", "orbx_map_refresh_points_device", "orbx_map_refresh_points",
     "orbx_map_keyframe_redundancy_device", "orbx_map_keyframe_redundancy",
     "orbx_keyframe_get_map_point_slots", "orbx_map_fuse_device", "orbx_map_fuse", "orbx_map_search_in_neighbors",
+    "orbx_keyframe_set_map_point_slots_device", "orbx_map_create_points_device", "orbx_map_create_points", "orbx_map_remove_points",
+    "orbx_map_cull_points",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
+MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS = 1, 2    # orbx_map_create_points' phases (a bit mask)
 
 
 BOW_VECTORS_MAX = 8192      # descriptors per orbx_bow_vectors call (bow_kernels.hip: BOWV_MAX)
@@ -320,6 +323,12 @@ def load_library():
         L.orbx_vocab_load_text.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
         L.orbx_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.orbx_destroy.restype = None
+        L.orbx_keyframe_set_map_point_slots_device.argtypes = [C.c_void_p] * 3
+        L.orbx_map_create_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                    C.c_int] + [C.c_void_p] * 8
+        L.orbx_map_create_points.argtypes = L.orbx_map_create_points_device.argtypes[:11] + [C.c_void_p] * 7
+        L.orbx_map_remove_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orbx_map_cull_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         for name in ABI_SYMBOLS:
             getattr(L, name)
         _lib = L
@@ -1518,6 +1527,74 @@ class Handle:
         return dict(counts=counts.reshape(2, 4), goner_a=g[0][:Ga].copy(), keeper_a=g[1][:Ga].copy(), goner_b=g[2][:Gb].copy(), keeper_b=g[3][:Gb].copy(),
                     affected=aff[:M].copy(), refresh=refresh)
 
+    # ---- create and cull map points on the resident map (include/orbx.h, "create and cull map points on the resident map") ----
+    def map_create_points_device(self, camera, mp: "MapPointStore", cur: "KeyFrame", neighbours, free_slots, phases=MAP_CREATE_STEREO | MAP_CREATE_NEIGHBOURS,
+                                 config: "TriangulationConfig" = None, is_inertial=False, device=None):
+        """Steps 3 and 3b of process_keyframe on the resident map (orbx_map_create_points_device): the stereo points of `cur` and the
+        points triangulated with `neighbours` take free_slots (a host array) in creation order and are written into the keyframes'
+        tables where they lie.  Returns a dict of CUDA tensors: counts [4] int32 = (S, N, created, dropped), new_slot / new_neighbour /
+        new_idx1 / new_idx2 [n_free] int32, new_points [n_free,3] f64, new_desc [n_free,32] u8 (rows [0, created)), stats [T,4] int32.
+        The store is untouched: mp.set_device(free_slots[:created], new_points[:created], new_desc[:created]) makes the points live.
+        Asynchronous on the handle's stream."""
+        import torch
+        fs = np.ascontiguousarray(free_slots, np.int32).reshape(-1)
+        nf, T = len(fs), len(neighbours)
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(counts=mk(4), new_slot=mk(max(nf, 1)), new_neighbour=mk(max(nf, 1)), new_idx1=mk(max(nf, 1)), new_idx2=mk(max(nf, 1)),
+                 new_points=mk((max(nf, 1), 3), torch.float64), new_desc=mk((max(nf, 1), 32), torch.uint8), stats=mk((max(T, 1), 4)))
+        cam = camera._c(); cfg = (config or TriangulationConfig())._c()
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_create_points_device(
+            self._h, C.byref(cam), C.byref(cfg), int(bool(is_inertial)), mp._p, cur._p, self._kf_array(neighbours), T, int(phases),
+            _vp(fs if nf else np.zeros(1, np.int32)), nf, _vp(o["counts"]), _vp(o["new_slot"]), _vp(o["new_neighbour"]), _vp(o["new_idx1"]), _vp(o["new_idx2"]),
+            _vp(o["new_points"]), _vp(o["new_desc"]), _vp(o["stats"])))
+        for k in ("new_slot", "new_neighbour", "new_idx1", "new_idx2", "new_points", "new_desc"):
+            o[k] = o[k][:nf]
+        o["stats"] = o["stats"][:T]
+        return o
+
+    def map_create_points(self, camera, mp: "MapPointStore", cur: "KeyFrame", neighbours, free_slots, phases=MAP_CREATE_STEREO | MAP_CREATE_NEIGHBOURS,
+                          config: "TriangulationConfig" = None, is_inertial=False):
+        """The host form (orbx_map_create_points), synchronous: one download, then the new points are made live in the store.
+        Returns a dict of numpy arrays cut to `created`: counts [4], new_slot / new_neighbour / new_idx1 / new_idx2 int32, new_points
+        [created,3] f64, stats [T,4] int32."""
+        fs = np.ascontiguousarray(free_slots, np.int32).reshape(-1)
+        nf, T = len(fs), len(neighbours)
+        counts = np.zeros(4, np.int32); stats = np.zeros((max(T, 1), 4), np.int32)
+        li = [np.zeros(max(nf, 1), np.int32) for _ in range(4)]
+        pts = np.zeros((max(nf, 1), 3))
+        cam = camera._c(); cfg = (config or TriangulationConfig())._c()
+        self._after_torch()
+        self._check(self._L.orbx_map_create_points(
+            self._h, C.byref(cam), C.byref(cfg), int(bool(is_inertial)), mp._p, cur._p, self._kf_array(neighbours), T, int(phases),
+            _vp(fs if nf else np.zeros(1, np.int32)), nf, _vp(counts), _vp(li[0]), _vp(li[1]), _vp(li[2]), _vp(li[3]), _vp(pts), _vp(stats)))
+        m = int(counts[2])
+        return dict(counts=counts, new_slot=li[0][:m].copy(), new_neighbour=li[1][:m].copy(), new_idx1=li[2][:m].copy(), new_idx2=li[3][:m].copy(),
+                    new_points=pts[:m].copy(), stats=stats[:T].copy())
+
+    def map_remove_points(self, mp: "MapPointStore", keyframes, slots, count=True):
+        """remove_map_point_full for a list (orbx_map_remove_points): every entry of the tables of `keyframes` that names a listed
+        slot becomes -1, then the slots are erased.  Returns the number of table entries cleared (one 4-byte download), or None with
+        count=False (nothing is downloaded, the call does not wait)."""
+        a = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = C.c_int(0)
+        self._after_torch()
+        self._check(self._L.orbx_map_remove_points(self._h, mp._p, len(keyframes), self._kf_array(keyframes), len(a), _vp(a if len(a) else np.zeros(1, np.int32)),
+                                                   C.byref(n) if count else None))
+        return n.value if count else None
+
+    def map_cull_points(self, mp: "MapPointStore", keyframes, candidates, min_observations):
+        """cull_map_points on the resident map (orbx_map_cull_points), synchronous: the candidates (live slots, none twice) observed
+        by fewer than min_observations of `keyframes` are removed as map_remove_points removes them.  Returns them, int32, in the
+        candidates' order."""
+        a = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+        n = C.c_int(0); out = np.zeros(max(len(a), 1), np.int32)
+        self._after_torch()
+        self._check(self._L.orbx_map_cull_points(self._h, mp._p, len(keyframes), self._kf_array(keyframes), len(a), _vp(a if len(a) else np.zeros(1, np.int32)),
+                                                 int(min_observations), C.byref(n), _vp(out)))
+        return out[:n.value].copy()
+
     def ba_solve_visual_obs32_device(self, camera, cfg, poses_cw, fixed_cw, points, obs32, n_obs, should_stop=None):
         """ba_solve_visual with the observations in device memory (orbx_ba_solve_visual_obs32_device): obs32 is a CUDA tensor whose
         first 16 * n_obs bytes are BA_OBS32 records (map_collect_ba_window_device's), 16-byte aligned.  Poses and points are host
@@ -2459,9 +2536,22 @@ class KeyFrame:
 
     def set_map_point_slots(self, mp: "MapPointStore", slots):
         """The per-feature slot table [n] (int, -1 or None = no map point) against the resident store `mp`, kept in the keyframe's
-        device block; slots=None clears it.  set_map_points and the ids are untouched."""
+        device block; slots=None clears it.  A CUDA tensor (int32 [n], e.g. a row of the tracker's matched_slot) goes through
+        orbx_keyframe_set_map_point_slots_device: asynchronous, a value outside [-1, capacity) is stored as -1.  set_map_points and
+        the ids are untouched."""
         if slots is None:
             self._handle._check(self._L.orbx_keyframe_set_map_point_slots(self._p, None, None))
+            return
+        if getattr(slots, "is_cuda", False):
+            import torch
+            if slots.dtype != torch.int32 or not slots.is_contiguous() or slots.numel() < self.n:
+                raise ValueError("set_map_point_slots: a CUDA table is a contiguous int32 tensor of at least n entries")
+            if slots.device.index != self._handle.device:
+                raise ValueError("set_map_point_slots: the table lies on cuda:%s, the handle on cuda:%d" % (slots.device.index, self._handle.device))
+            if self.n == 0:
+                slots = torch.zeros(1, dtype=torch.int32, device=slots.device)     # (an empty tensor has no address)
+            self._handle._after_torch(slots)
+            self._handle._check(self._L.orbx_keyframe_set_map_point_slots_device(self._p, mp._p, _vp(slots)))
             return
         a = np.array([-1 if m is None else int(m) for m in slots], np.int32)
         assert len(a) == self.n

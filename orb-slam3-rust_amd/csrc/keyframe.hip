@@ -9,6 +9,107 @@
 
 #include "orbx_internal.hpp"
 
+// ---- the neighbour loop of triangulate_from_neighbors (triangulation.rs:117-294), shared by orbx_keyframe_triangulate_from_neighbors
+// and orbx_map_create_points[_device] (map_store_kernels.hip): which neighbours are searched and where their tables and scratch
+// lie (plan), the tables themselves (fill), the launches (launch).  The callers differ in where the flags come from and in how the
+// tables travel.
+
+void tri_nb_plan(const orbx_camera* cam, const orbx_keyframe* cur, const orbx_keyframe* const* kfs, int T, TriNbPlan& P) {
+  P.n1 = cur->n;
+  const bool grid_ok = tri_grid_dims(cam, &P.cols, &P.rows);
+  for (int t = 0; t < T; ++t) {
+    const double dx = kfs[t]->pose_wc[4] - cur->pose_wc[4], dy = kfs[t]->pose_wc[5] - cur->pose_wc[5], dz = kfs[t]->pose_wc[6] - cur->pose_wc[6];
+    if (std::sqrt(dx * dx + dy * dy + dz * dz) < cam->baseline) continue;                  // :137-141
+    if (P.n1 == 0 || kfs[t]->n == 0) continue;
+    const bool bow = cur->has_nodes && kfs[t]->has_nodes;                                   // :145
+    if (!bow && !grid_ok) continue;
+    P.orig.push_back(t);
+    P.max_n2 = std::max(P.max_n2, kfs[t]->n);
+  }
+  const size_t Ts = P.orig.size(), n1 = (size_t)P.n1;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+  P.sl.resize(Ts);
+  P.o_items = take(sizeof(TriBatchItem) * Ts); P.o_nbs = take(sizeof(TriNeighbour) * Ts);
+  for (size_t k = 0; k < Ts; ++k) {
+    const orbx_keyframe* kf = kfs[P.orig[k]];
+    P.sl[k].bow = cur->has_nodes && kf->has_nodes;
+    if (P.sl[k].bow) { P.sl[k].sorted = take(4 * (size_t)kf->n); P.sl[k].lo = take(4 * n1); P.sl[k].hi = take(4 * n1); }
+  }
+  P.up_bytes = off;
+  off = 0;
+  for (size_t k = 0; k < Ts; ++k) {
+    const size_t n2 = (size_t)kfs[P.orig[k]]->n;
+    TriNbPlan::Slices& s = P.sl[k];
+    if (!s.bow) { s.cell_start = take(4 * 4100); s.sorted = take(4 * n2); s.cell_of = take(2 * n2); }
+    s.prop = take(4 * n1); s.owner = take(4 * n2); s.pairs = take(8 * n1); s.n_out = take(16); s.taken = take(n2);
+  }
+  P.o_status = take(2 * Ts * n1); P.o_points = take(24 * Ts * n1);
+  P.ws_bytes = off;
+}
+
+// host side of the step: epipolar geometry per neighbour, candidate ranges where both keyframes carry nodes
+void tri_nb_fill(const TriNbPlan& P, const orbx_camera* cam, const orbx_triangulation_config* cfg, const orbx_keyframe* cur, const orbx_keyframe* const* kfs,
+                 const uint8_t* d_mp1, const uint8_t* const* d_mp2, uint8_t* up, uint8_t* d_up, uint8_t* d_ws) {
+  const int n1 = P.n1;
+  TriBatchItem* items = (TriBatchItem*)(up + P.o_items);
+  TriNeighbour* nbs = (TriNeighbour*)(up + P.o_nbs);
+  for (size_t k = 0; k < P.orig.size(); ++k) {
+    const orbx_keyframe* kf = kfs[P.orig[k]];
+    const TriNbPlan::Slices& s = P.sl[k];
+    TriBatchItem it{};
+    double ep[2];
+    orbx_triangulation_geometry(cam, cur->pose_wc, kf->pose_wc, ep, it.A.F);
+    it.A.epx = ep[0]; it.A.epy = ep[1];
+    it.A.cols = s.bow ? 0 : P.cols; it.A.rows = s.bow ? 0 : P.rows; it.A.max_dist = cfg->max_descriptor_dist; it.A.n1 = n1; it.A.n2 = kf->n;
+    it.A.kp1 = cur->d_kp; it.A.desc1 = cur->d_desc; it.A.mp1 = d_mp1; it.A.stereo1 = cur->d_has_point;
+    it.A.kp2 = kf->d_kp; it.A.desc2 = kf->d_desc;
+    it.A.sorted_idx = (const int*)((s.bow ? d_up : d_ws) + s.sorted);
+    it.A.taken = d_ws + s.taken;
+    if (s.bow) {
+      it.A.rng_lo = (const int*)(d_up + s.lo); it.A.rng_hi = (const int*)(d_up + s.hi);
+      int* sorted = (int*)(up + s.sorted); int* lo = (int*)(up + s.lo); int* hi = (int*)(up + s.hi);
+      if (kf->n > 0) memcpy(sorted, kf->node_sorted.data(), 4 * (size_t)kf->n);
+      const uint32_t* node2 = kf->node.data();
+      const int* sb = kf->node_sorted.data(); const int* se = sb + kf->node_m;
+      for (int i = 0; i < n1; ++i) {                                                       // the features of keyframe 2 in feature i's node (:577-581)
+        lo[i] = hi[i] = 0;
+        const uint32_t key = cur->node[(size_t)i];
+        if (key == 0xffffffffu) continue;
+        const int* b = std::lower_bound(sb, se, key, [&](int a, uint32_t kk) { return node2[a] < kk; });
+        const int* e = std::upper_bound(b, se, key, [&](uint32_t kk, int a) { return kk < node2[a]; });
+        lo[i] = (int)(b - sb); hi[i] = (int)(e - sb);
+      }
+    } else {
+      it.A.cell_start = (const int*)(d_ws + s.cell_start); it.A.cell_of = (const unsigned short*)(d_ws + s.cell_of);
+    }
+    it.mp2 = d_mp2[P.orig[k]];
+    it.prop = (int*)(d_ws + s.prop); it.owner = (int*)(d_ws + s.owner); it.pairs = (int*)(d_ws + s.pairs); it.n_out = (int*)(d_ws + s.n_out);
+    items[k] = it;
+    TriNeighbour nb{};
+    nb.kp2 = kf->d_kp; nb.pts2 = kf->d_points; nb.has2 = kf->d_has_point; nb.n2 = kf->n;
+    memcpy(nb.pose2, kf->pose_wc, sizeof(nb.pose2));
+    nb.pairs = it.pairs; nb.n_pairs_dev = it.n_out; nb.n_pairs = 0; nb.out_base = (int)k * n1;
+    nbs[k] = nb;
+  }
+}
+
+// the searches, the pair loop and the ordered compaction on the handle's stream, behind the upload of the tables
+int tri_nb_launch(orbx_handle* h, const TriNbPlan& P, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, const orbx_keyframe* cur,
+                  const uint8_t* d_up, uint8_t* d_ws, int cap, int* d_head, int* d_out_nb, int* d_out_idx1, int* d_out_idx2, double* d_out_points) {
+  const int Ts = (int)P.orig.size();
+  TriCommon c{};
+  tri_common_fill(&c, cam, cfg, is_inertial);
+  c.kp1 = cur->d_kp; c.pts1 = cur->d_points; c.has1 = cur->d_has_point; c.n1 = P.n1;
+  memcpy(c.pose1, cur->pose_wc, sizeof(c.pose1));
+  const TriNeighbour* d_nbs = (const TriNeighbour*)(d_up + P.o_nbs);
+  uint16_t* d_status = (uint16_t*)(d_ws + P.o_status);
+  double* d_points = (double*)(d_ws + P.o_points);
+  if (int rc = launch_search_for_triangulation_batch(h, (const TriBatchItem*)(d_up + P.o_items), Ts, P.n1, P.max_n2)) return rc;
+  if (int rc = launch_triangulate_pairs(h, c, TriNeighbour{}, d_nbs, Ts, P.n1, d_status, d_points)) return rc;
+  return launch_triangulate_compact(h, d_nbs, Ts, d_status, d_points, cap, d_head, d_out_nb, d_out_idx1, d_out_idx2, d_out_points);
+}
+
 extern "C" {
 
 int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t* d_desc, int n, const double* d_points_cam,
@@ -176,106 +277,31 @@ int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* 
       return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: keyframe %d is null or of another handle", t);
   if (T == 0) return ORBX_OK;
   memset(stats, 0, sizeof(int) * 4 * (size_t)T);
-  const int n1 = cur->n;
-  int cols = 0, rows = 0;
-  const bool grid_ok = tri_grid_dims(cam, &cols, &rows);
-  std::vector<int> orig;                                                 // searched neighbour k -> index in kfs
-  int max_n2 = 0;
-  for (int t = 0; t < T; ++t) {
-    const double dx = kfs[t]->pose_wc[4] - cur->pose_wc[4], dy = kfs[t]->pose_wc[5] - cur->pose_wc[5], dz = kfs[t]->pose_wc[6] - cur->pose_wc[6];
-    if (std::sqrt(dx * dx + dy * dy + dz * dz) < cam->baseline) continue;                  // :137-141
-    if (n1 == 0 || kfs[t]->n == 0) continue;
-    const bool bow = cur->has_nodes && kfs[t]->has_nodes;                                   // :145
-    if (!bow && !grid_ok) continue;
-    orig.push_back(t);
-    max_n2 = std::max(max_n2, kfs[t]->n);
-  }
-  const int Ts = (int)orig.size();
+  TriNbPlan P;
+  tri_nb_plan(cam, cur, kfs, T, P);
+  const int Ts = (int)P.orig.size();
   if (Ts == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  // ---- layout of the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch] [status | points] [result blob]
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
-  struct Slices { size_t sorted, lo, hi, cell_start, prop, owner, pairs, n_out, cell_of, taken; bool bow; };
-  std::vector<Slices> sl((size_t)Ts);
-  const size_t o_items = take(sizeof(TriBatchItem) * (size_t)Ts), o_nbs = take(sizeof(TriNeighbour) * (size_t)Ts);
-  for (int k = 0; k < Ts; ++k) {
-    const orbx_keyframe* kf = kfs[orig[(size_t)k]];
-    sl[(size_t)k].bow = cur->has_nodes && kf->has_nodes;
-    if (sl[(size_t)k].bow) { sl[(size_t)k].sorted = take(4 * (size_t)kf->n); sl[(size_t)k].lo = take(4 * (size_t)n1); sl[(size_t)k].hi = take(4 * (size_t)n1); }
-  }
-  const size_t up_bytes = off;
-  for (int k = 0; k < Ts; ++k) {
-    const size_t n2 = (size_t)kfs[orig[(size_t)k]]->n;
-    Slices& s = sl[(size_t)k];
-    if (!s.bow) { s.cell_start = take(4 * 4100); s.sorted = take(4 * n2); s.cell_of = take(2 * n2); }
-    s.prop = take(4 * (size_t)n1); s.owner = take(4 * n2); s.pairs = take(8 * (size_t)n1); s.n_out = take(16); s.taken = take(n2);
-  }
-  const size_t slots = (size_t)Ts * (size_t)n1;
-  const size_t o_status = take(2 * slots), o_points = take(24 * slots);
+  // ---- the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch | status | points] [result blob]
+  const size_t slots = (size_t)Ts * (size_t)P.n1;
   const size_t capd = std::min((size_t)cap, slots);
-  const size_t o_res = off, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd, r_i1 = r_nb + 4 * capd,
-               r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
-  off += res_bytes;
-  if (int rc = orbx_reserve(h, h->ws_io[10], off)) return rc;
+  const size_t o_res = P.up_bytes + P.ws_bytes, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd,
+               r_i1 = r_nb + 4 * capd, r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
+  if (int rc = orbx_reserve(h, h->ws_io[10], o_res + res_bytes)) return rc;
   uint8_t* d = (uint8_t*)h->ws_io[10].p;
-  // ---- host side of the step: epipolar geometry per neighbour, candidate ranges where both keyframes carry nodes
-  std::vector<uint8_t> up(up_bytes), down(res_bytes);
-  TriBatchItem* items = (TriBatchItem*)(up.data() + o_items);
-  TriNeighbour* nbs = (TriNeighbour*)(up.data() + o_nbs);
-  for (int k = 0; k < Ts; ++k) {
-    const orbx_keyframe* kf = kfs[orig[(size_t)k]];
-    const Slices& s = sl[(size_t)k];
-    TriBatchItem it{};
-    double ep[2];
-    orbx_triangulation_geometry(cam, cur->pose_wc, kf->pose_wc, ep, it.A.F);
-    it.A.epx = ep[0]; it.A.epy = ep[1];
-    it.A.cols = s.bow ? 0 : cols; it.A.rows = s.bow ? 0 : rows; it.A.max_dist = cfg->max_descriptor_dist; it.A.n1 = n1; it.A.n2 = kf->n;
-    it.A.kp1 = cur->d_kp; it.A.desc1 = cur->d_desc; it.A.mp1 = cur->d_mp_flag; it.A.stereo1 = cur->d_has_point;
-    it.A.kp2 = kf->d_kp; it.A.desc2 = kf->d_desc;
-    it.A.sorted_idx = (const int*)(d + s.sorted);
-    it.A.taken = d + s.taken;
-    if (s.bow) {
-      it.A.rng_lo = (const int*)(d + s.lo); it.A.rng_hi = (const int*)(d + s.hi);
-      int* sorted = (int*)(up.data() + s.sorted); int* lo = (int*)(up.data() + s.lo); int* hi = (int*)(up.data() + s.hi);
-      if (kf->n > 0) memcpy(sorted, kf->node_sorted.data(), 4 * (size_t)kf->n);
-      const uint32_t* node2 = kf->node.data();
-      const int* sb = kf->node_sorted.data(); const int* se = sb + kf->node_m;
-      for (int i = 0; i < n1; ++i) {                                                       // the features of keyframe 2 in feature i's node (:577-581)
-        lo[i] = hi[i] = 0;
-        const uint32_t key = cur->node[(size_t)i];
-        if (key == 0xffffffffu) continue;
-        const int* b = std::lower_bound(sb, se, key, [&](int a, uint32_t kk) { return node2[a] < kk; });
-        const int* e = std::upper_bound(b, se, key, [&](uint32_t kk, int a) { return kk < node2[a]; });
-        lo[i] = (int)(b - sb); hi[i] = (int)(e - sb);
-      }
-    } else {
-      it.A.cell_start = (const int*)(d + s.cell_start); it.A.cell_of = (const unsigned short*)(d + s.cell_of);
-    }
-    it.mp2 = kf->d_mp_flag;
-    it.prop = (int*)(d + s.prop); it.owner = (int*)(d + s.owner); it.pairs = (int*)(d + s.pairs); it.n_out = (int*)(d + s.n_out);
-    items[k] = it;
-    TriNeighbour nb{};
-    nb.kp2 = kf->d_kp; nb.pts2 = kf->d_points; nb.has2 = kf->d_has_point; nb.n2 = kf->n;
-    memcpy(nb.pose2, kf->pose_wc, sizeof(nb.pose2));
-    nb.pairs = it.pairs; nb.n_pairs_dev = it.n_out; nb.n_pairs = 0; nb.out_base = k * n1;
-    nbs[k] = nb;
-  }
-  TriCommon c{};
-  tri_common_fill(&c, cam, cfg, is_inertial);
-  c.kp1 = cur->d_kp; c.pts1 = cur->d_points; c.has1 = cur->d_has_point; c.n1 = n1;
-  memcpy(c.pose1, cur->pose_wc, sizeof(c.pose1));
+  std::vector<uint8_t> up(P.up_bytes), down(res_bytes);
+  std::vector<const uint8_t*> mp2((size_t)T);
+  for (int t = 0; t < T; ++t) mp2[(size_t)t] = kfs[t]->d_mp_flag;
+  // map_point_ids[i].is_some() = the keyframes' map-point flags (triangulation.rs:94-107, :401-527)
+  tri_nb_fill(P, cam, cfg, cur, kfs, cur->d_mp_flag, mp2.data(), up.data(), d, d + P.up_bytes);
   // ---- one upload, the launches, one download, one synchronisation
   hipStream_t st = h->stream;
-  hipError_t e = hipMemcpyAsync(d, up.data(), up_bytes, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d, up.data(), P.up_bytes, hipMemcpyHostToDevice, st);
   int rc = ORBX_OK;
   if (e == hipSuccess) {
     orbx_prof_begin_call(h);
-    rc = launch_search_for_triangulation_batch(h, (const TriBatchItem*)(d + o_items), Ts, n1, max_n2);
-    if (!rc) rc = launch_triangulate_pairs(h, c, TriNeighbour{}, (const TriNeighbour*)(d + o_nbs), Ts, n1, (uint16_t*)(d + o_status), (double*)(d + o_points));
-    if (!rc) rc = launch_triangulate_compact(h, (const TriNeighbour*)(d + o_nbs), Ts, (const uint16_t*)(d + o_status), (const double*)(d + o_points), (int)capd,
-                                             (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1), (int*)(d + o_res + r_i2),
-                                             (double*)(d + o_res + r_pts));
+    rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, d, d + P.up_bytes, (int)capd, (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1),
+                       (int*)(d + o_res + r_i2), (double*)(d + o_res + r_pts));
     if (!rc) e = hipMemcpyAsync(down.data(), d + o_res, res_bytes, hipMemcpyDeviceToHost, st);
   }
   const hipError_t es = hipStreamSynchronize(st);                       // also on the error paths: `up` / `down` are locals
@@ -284,13 +310,13 @@ int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* 
     return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_triangulate_from_neighbors: %s", hipGetErrorString(e != hipSuccess ? e : es));
   const int* head = (const int*)(down.data() + r_head);
   for (int k = 0; k < Ts; ++k) {
-    int* s4 = stats + 4 * (size_t)orig[(size_t)k];
+    int* s4 = stats + 4 * (size_t)P.orig[(size_t)k];
     s4[0] = 1; s4[1] = head[2 + 4 * k]; s4[2] = head[3 + 4 * k]; s4[3] = head[4 + 4 * k];
   }
   *n_out = head[0];
   const size_t nw = std::min((size_t)head[0], capd);
   const int* nb_k = (const int*)(down.data() + r_nb);
-  for (size_t i = 0; i < nw; ++i) out_neighbour[i] = orig[(size_t)nb_k[i]];
+  for (size_t i = 0; i < nw; ++i) out_neighbour[i] = P.orig[(size_t)nb_k[i]];
   if (nw > 0) {
     memcpy(out_idx1, down.data() + r_i1, 4 * nw);
     memcpy(out_idx2, down.data() + r_i2, 4 * nw);

@@ -47,6 +47,9 @@
 // orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
 // The fuse and merge phases of search_in_neighbors (search_in_neighbors.rs:240-390, map.rs:770-868) act on the tables themselves:
 // orbx_map_fuse[_device] and orbx_map_search_in_neighbors; the kernels are described where they stand ("fuse and merge", below).
+// New points and removed ones are written into the tables the same way (local_mapper.rs:208-268, :421-469, map.rs:609-631):
+// orbx_keyframe_set_map_point_slots_device, orbx_map_create_points[_device], orbx_map_remove_points, orbx_map_cull_points; the
+// kernels are described where they stand ("creation and removal", below).
 // The sums, the ordered append and the scans of counts are block_dev.hpp's: every thread of a workgroup reaches each of them.
 #include <algorithm>
 #include <numeric>
@@ -55,6 +58,7 @@
 #include "block_dev.hpp"
 #include "fuse_search_dev.hpp"
 #include "orbx_internal.hpp"
+#include "pose_dev.hpp"
 
 struct orbx_map_points {
   orbx_handle* h = nullptr;
@@ -511,6 +515,34 @@ int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const 
 int ms_check_keyframe(orbx_handle* h, const char* who, const orbx_map_points* mp, const orbx_keyframe* kf, int t) {
   if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
   if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, t);
+  return ORBX_OK;
+}
+
+// kfs [n_kfs] of a call that rewrites tables: none twice
+int ms_check_no_repeat(orbx_handle* h, const char* who, int n_kfs, const orbx_keyframe* const* kfs) {
+  std::vector<const orbx_keyframe*> seen(kfs, kfs + n_kfs);
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return orbx_fail(h, ORBX_ERR_INVALID, "%s: a keyframe is listed twice in kfs[] (their tables are rewritten)", who);
+  return ORBX_OK;
+}
+
+// ... and each as ms_check_keyframe asks
+int ms_check_distinct(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs) {
+  for (int t = 0; t < n_kfs; ++t)
+    if (int rc = ms_check_keyframe(h, who, mp, kfs[t], t)) return rc;
+  return ms_check_no_repeat(h, who, n_kfs, kfs);
+}
+
+// erase behind its checks: d_slots [n] already lies in device memory; the live bytes and their host mirror
+int ms_erase_launch(orbx_handle* h, orbx_map_points* mp, const int* d_slots, const int* slots, int n) {
+  {
+    ProfScope ps(h, "map_scatter_kernel");
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, d_slots, n, (const double*)nullptr,
+                       (const uint8_t*)nullptr, 0, mp->d_pos, mp->d_desc, mp->d_live);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  for (int i = 0; i < n; ++i)
+    if (mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 0; --mp->n_live; }
   return ORBX_OK;
 }
 
@@ -1222,8 +1254,8 @@ struct ObsCall {
 int obs_entry_bound(const ObsPlan& P, int n_points) { return (int)std::min<long long>(P.n_feat, (long long)n_points * (long long)P.C.kfs.size()); }
 
 // Everything on the handle's stream.  The tables (keyframes, slots, candidates) go up through the ring; d_slots_out: where the
-// points' slots lie in device memory afterwards.
-int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const ObsCall& c, const int** d_slots_out = nullptr) {
+// points' slots lie in device memory afterwards; d_count_out: where their observer counts lie (until the next observation call).
+int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const ObsCall& c, const int** d_slots_out = nullptr, const int** d_count_out = nullptr) {
   ORBX_HIP(h, hipSetDevice(h->device));
   if (int rc = ms_reserve_first(h, mp, 1)) return rc;
   const size_t K = P.C.kfs.size(), Mb = (size_t)c.n_points, Nb = c.d_obs_start ? (size_t)obs_entry_bound(P, c.n_points) : 0, NC = (size_t)c.n_cand;
@@ -1251,6 +1283,7 @@ int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const Obs
   A.cand = (const int*)(ds + o_ca); A.n_cand = c.n_cand; A.threshold = c.threshold;
   A.chunk_tot = (int*)(w + o_ct); A.total = c.d_total; A.redundant = c.d_redundant; A.cull = c.d_cull;
   if (d_slots_out) *d_slots_out = A.list_slot;
+  if (d_count_out) *d_count_out = A.count;
   const dim3 block(MS_THREADS), list_grid(std::max(1, (int)((Mb + MS_THREADS - 1) / MS_THREADS))), kf_grid(n_chunk, (unsigned)K);
   const bool walk = K > 0 && P.C.max_n > 0 && Mb > 0;
   {
@@ -1640,21 +1673,27 @@ __global__ __launch_bounds__(MS_THREADS) void mf_rewrite_kernel(MfArgs A) {
   if (tid == 0 && added) atomicAdd(&A.counts[2], added);
 }
 
-__global__ __launch_bounds__(MS_THREADS) void mf_uniq_kernel(MfArgs A) {
-  __shared__ int tile[MS_THREADS];
-  const MfKf kf = A.kfs[blockIdx.y];
+// d_mp_uniq of the block's MS_THREADS features of one table: an entry stays where no earlier feature holds it.  Every thread of
+// the block reaches the barriers; tile: LDS [MS_THREADS].
+__device__ __forceinline__ void uniq_rows(const int* slots, int* uniq, int n_feat, int* tile) {
   const int tid = threadIdx.x, i = blockIdx.x * MS_THREADS + tid;
-  if (!kf.slots || !A.changed[blockIdx.y] || (int)(blockIdx.x * MS_THREADS) >= kf.n) return;      // (the block's)
-  const int s = i < kf.n ? kf.slots[i] : -1;
+  const int s = i < n_feat ? slots[i] : -1;
   bool earlier = false;
   for (int j0 = 0; j0 <= (int)(blockIdx.x * MS_THREADS); j0 += MS_THREADS) {
     __syncthreads();
-    tile[tid] = j0 + tid < kf.n ? kf.slots[j0 + tid] : -1;
+    tile[tid] = j0 + tid < n_feat ? slots[j0 + tid] : -1;
     __syncthreads();
     const int n = min(MS_THREADS, i - j0);                                 // the features before i
     for (int t = 0; t < n; ++t) earlier |= tile[t] == s;
   }
-  if (i < kf.n) kf.uniq[i] = s >= 0 && !earlier ? s : -1;
+  if (i < n_feat) uniq[i] = s >= 0 && !earlier ? s : -1;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mf_uniq_kernel(MfArgs A) {
+  __shared__ int tile[MS_THREADS];
+  const MfKf kf = A.kfs[blockIdx.y];
+  if (!kf.slots || !A.changed[blockIdx.y] || (int)(blockIdx.x * MS_THREADS) >= kf.n) return;      // (the block's)
+  uniq_rows(kf.slots, kf.uniq, kf.n, tile);
 }
 
 __global__ __launch_bounds__(MS_THREADS) void mf_restore_kernel(MfArgs A) {
@@ -1694,13 +1733,7 @@ int mf_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx
   if (desc_threshold > 256) return orbx_fail(h, ORBX_ERR_INVALID, "%s: desc_threshold %u is above 256", who, desc_threshold);
   if (int rc = cov_check_queries(h, who, "src", n_src, src, n_kfs, 0)) return rc;
   if (int rc = cov_check_queries(h, who, "tgt", n_tgt, tgt, n_kfs, 0)) return rc;
-  std::vector<const orbx_keyframe*> seen((size_t)n_kfs);
-  for (int t = 0; t < n_kfs; ++t) {
-    if (int rc = ms_check_keyframe(h, who, mp, kfs[t], t)) return rc;
-    seen[(size_t)t] = kfs[t];
-  }
-  std::sort(seen.begin(), seen.end());
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return orbx_fail(h, ORBX_ERR_INVALID, "%s: a keyframe is listed twice in kfs[] (their tables are rewritten)", who);
+  if (int rc = ms_check_distinct(h, who, mp, n_kfs, kfs)) return rc;
   std::vector<uint8_t> is_tgt((size_t)n_kfs, 0);
   for (int t = 0; t < n_tgt; ++t) {
     if (is_tgt[(size_t)tgt[t]]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: tgt[%d] = %d is listed twice", who, t, tgt[t]);
@@ -1888,6 +1921,317 @@ int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map
   return ORBX_OK;
 }
 
+// ---- creation and removal (include/orbx.h, "create and cull map points on the resident map"; local_mapper.rs:208-268, :421-469,
+// triangulation.rs:286-290, map.rs:609-631) ----
+// New points are written into the tables where they lie; a keyframe's flags are derived from its table and the live bytes.
+//   mc_table_kernel    a table from a device array: a value outside [-1, capacity) becomes -1; mc_uniq_one_kernel: its d_mp_uniq
+//   mc_flag_kernel     (chunk, keyframe) flag = the table names a live point — what d_mp_flag is to the host-id calls
+//   mc_stereo_kernel   one workgroup over the current keyframe in chunks of MS_CHUNK: the candidates (stereo point, no flag) ranked in
+//                      feature order (BlockScan); candidate r takes free_slots[r]: table, flag, list row, position, descriptor
+//   (the neighbour loop of keyframe.hip, reading these flags, leaves its ordered lists in the workspace)
+//   mc_pair_kernel     pair e takes free_slots[S' + e]: list row, the neighbour's table, atomicMax(last[idx1], e) — an integer maximum,
+//                      whatever the order; counts and stats
+//   mc_last_kernel     the pair that holds last[idx1] writes the current keyframe's entry: the reference's sequential overwriting
+//   mc_uniq_kernel     (block, keyframe) of a changed keyframe: d_mp_uniq again
+// Removal marks the listed slots in the store's mark bytes (row 0, 0 between calls), clears every entry of the call's tables that
+// names a marked slot (mr_clear_kernel: block_sum, one integer atomicAdd per block on the counter), and takes the marks back.
+
+struct McKf {                                    // one keyframe of a creation or removal call
+  int* slots; int* uniq;                         // NULL: no table (removal; creation gives every keyframe one)
+  uint8_t* flag;                                 // creation: [n] scratch
+  int n, pad_;
+};
+struct McArgs {
+  int capacity, n_free, n1, cap_pairs, T;
+  const uint8_t* live; const McKf* kfs;          // kfs [1 + T]: the current keyframe, then the neighbours
+  const int* free_slots;                         // [n_free]
+  const int* orig; const int* searched;          // searched neighbour -> its place in nbs[]; [T] the inverse, -1: not searched
+  const uint8_t* has1; const double* pts1; const uint8_t* desc1;
+  double pose1[7];
+  const int* head; const int* p_nb; const int* p_i1; const int* p_i2; const double* p_pts;      // the neighbour loop's lists (head NULL: it did not run)
+  int* last; int* changed; int* n_stereo;        // [n1], -1: none; [1 + T]; {S, S'}
+  int* counts; int* new_slot; int* new_nb; int* new_i1; int* new_i2; double* new_pts; uint8_t* new_desc; int* stats;
+};
+
+__device__ __forceinline__ void mc_copy_desc(uint8_t* out, const uint8_t* in) {        // (both 16-byte aligned)
+  const uint4* d = (const uint4*)in;
+  uint4* q = (uint4*)out;
+  q[0] = d[0]; q[1] = d[1];
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_table_kernel(const int* in, int n, int capacity, int* slots) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int s = in[i];
+  slots[i] = s >= 0 && s < capacity ? s : -1;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_uniq_one_kernel(const int* slots, int* uniq, int n) {
+  __shared__ int tile[MS_THREADS];
+  uniq_rows(slots, uniq, n, tile);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_flag_kernel(McArgs A) {
+  const McKf kf = A.kfs[blockIdx.y];
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    const int i = blockIdx.x * MS_CHUNK + j * MS_THREADS + threadIdx.x;
+    if (i >= kf.n) continue;
+    const int s = kf.slots[i];
+    kf.flag[i] = s >= 0 && s < A.capacity && A.live[s] ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_stereo_kernel(McArgs A) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  __shared__ double R[9];
+  const int tid = threadIdx.x;
+  const McKf kf = A.kfs[0];
+  if (tid == 0) quat_to_R(A.pose1, R);
+  BlockScan<MS_THREADS> scan(wave_tot);                                     // (its first barrier also covers R)
+  for (int c0 = 0; c0 < A.n1; c0 += MS_CHUNK) {                             // (the bounds are the block's: every thread reaches every round)
+    const int i0 = c0 + tid * MS_PER;
+    bool cand[MS_PER];
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < MS_PER; ++k) { cand[k] = i0 + k < A.n1 && A.has1[i0 + k] && !kf.flag[i0 + k]; n += cand[k]; }
+    int r = scan.round(n);
+#pragma unroll
+    for (int k = 0; k < MS_PER; ++k) {
+      if (!cand[k]) continue;
+      const int i = i0 + k, at = r++;
+      if (at >= A.n_free) continue;                                         // dropped: no slot, no table write, the flag stays 0
+      const int slot = A.free_slots[at];
+      kf.slots[i] = slot; kf.flag[i] = 1;
+      A.new_slot[at] = slot; A.new_nb[at] = -1; A.new_i1[at] = i; A.new_i2[at] = -1;
+      const double* p = A.pts1 + 3 * (size_t)i;                             // pose_wc * points_cam[i]: rotate, then translate
+      A.new_pts[3 * (size_t)at] = R[0] * p[0] + R[1] * p[1] + R[2] * p[2] + A.pose1[4];
+      A.new_pts[3 * (size_t)at + 1] = R[3] * p[0] + R[4] * p[1] + R[5] * p[2] + A.pose1[5];
+      A.new_pts[3 * (size_t)at + 2] = R[6] * p[0] + R[7] * p[1] + R[8] * p[2] + A.pose1[6];
+      mc_copy_desc(A.new_desc + 32 * (size_t)at, A.desc1 + 32 * (size_t)i);
+    }
+  }
+  if (tid == 0) {
+    A.n_stereo[0] = scan.total; A.n_stereo[1] = min(scan.total, A.n_free);
+    if (scan.total > 0 && A.n_free > 0) A.changed[0] = 1;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_pair_kernel(McArgs A) {
+  const int e = blockIdx.x * MS_THREADS + threadIdx.x;
+  const int S = A.n_stereo[0], Sp = A.n_stereo[1], N = A.head ? A.head[0] : 0;
+  if (e == 0) {
+    const int created = min(S + N, A.n_free);
+    A.counts[0] = S; A.counts[1] = N; A.counts[2] = created; A.counts[3] = S + N - created;
+  }
+  if (e < 4 * A.T) {                                                        // stats [T][4]: searched, matches_found, triangulated, validated
+    const int k = A.head ? A.searched[e >> 2] : -1, j = e & 3;
+    A.stats[e] = k < 0 ? 0 : j == 0 ? 1 : A.head[1 + 4 * k + j];
+  }
+  const int g = Sp + e;
+  if (e >= N || e >= A.cap_pairs || g >= A.n_free) return;
+  const int t = A.orig[A.p_nb[e]], i1 = A.p_i1[e], i2 = A.p_i2[e], slot = A.free_slots[g];
+  A.new_slot[g] = slot; A.new_nb[g] = t; A.new_i1[g] = i1; A.new_i2[g] = i2;
+  A.new_pts[3 * (size_t)g] = A.p_pts[3 * (size_t)e]; A.new_pts[3 * (size_t)g + 1] = A.p_pts[3 * (size_t)e + 1]; A.new_pts[3 * (size_t)g + 2] = A.p_pts[3 * (size_t)e + 2];
+  mc_copy_desc(A.new_desc + 32 * (size_t)g, A.desc1 + 32 * (size_t)i1);     // triangulation.rs:280
+  A.kfs[1 + t].slots[i2] = slot;                                            // (a search gives a feature of the neighbour to one pair)
+  A.changed[1 + t] = 1;
+  atomicMax(&A.last[i1], e);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_last_kernel(McArgs A) {
+  const int e = blockIdx.x * MS_THREADS + threadIdx.x;
+  const int g = A.n_stereo[1] + e;
+  if (e >= A.head[0] || e >= A.cap_pairs || g >= A.n_free) return;
+  const int i1 = A.p_i1[e];
+  if (A.last[i1] != e) return;                                              // triangulation.rs:289: each associate overwrites the one before
+  A.kfs[0].slots[i1] = A.free_slots[g];
+  A.changed[0] = 1;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mc_uniq_kernel(McArgs A) {
+  __shared__ int tile[MS_THREADS];
+  const McKf kf = A.kfs[blockIdx.y];
+  if (!A.changed[blockIdx.y] || (int)(blockIdx.x * MS_THREADS) >= kf.n) return;                  // (the block's)
+  uniq_rows(kf.slots, kf.uniq, kf.n, tile);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mr_mark_kernel(const int* slots, int n, uint8_t* mark, int value) {
+  const int i = blockIdx.x * MS_THREADS + threadIdx.x;
+  if (i < n) mark[slots[i]] = (uint8_t)value;                               // (repeats store the same byte)
+}
+
+__global__ __launch_bounds__(MS_THREADS) void mr_clear_kernel(const McKf* kfs, int capacity, const uint8_t* mark, int* n_cleared) {
+  __shared__ int wave_tot[MS_THREADS / 64];
+  const McKf kf = kfs[blockIdx.y];
+  if (!kf.slots || (int)(blockIdx.x * MS_CHUNK) >= kf.n) return;            // (the block's)
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < MS_PER; ++j) {
+    const int i = blockIdx.x * MS_CHUNK + j * MS_THREADS + threadIdx.x;
+    if (i >= kf.n) continue;
+    const int s = kf.slots[i];
+    if (s < 0 || s >= capacity || !mark[s]) continue;
+    kf.slots[i] = -1; kf.uniq[i] = -1;                                      // (uniq[i] is s or -1: every occurrence goes, so clearing in place is exact)
+    ++c;
+  }
+  c = block_sum<MS_THREADS>(c, wave_tot);
+  if (threadIdx.x == 0 && c) atomicAdd(n_cleared, c);
+}
+
+// What orbx_map_create_points[_device] refuses, before anything is enqueued or any keyframe touched.
+int mc_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_triangulation_config* cfg, orbx_map_points* mp, const orbx_keyframe* cur,
+             const orbx_keyframe* const* nbs, int T, int phases, const int* free_slots, int n_free) {
+  if (!cam || !cfg || T < 0 || T > 256 || cfg->max_descriptor_dist > 256 || (T > 0 && !nbs))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= T <= 256; max_descriptor_dist <= 256)", who);
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (phases < 1 || phases > (ORBX_MAP_CREATE_STEREO | ORBX_MAP_CREATE_NEIGHBOURS)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: phases = %d is outside 1..3", who, phases);
+  std::vector<const orbx_keyframe*> all((size_t)T + 1);
+  all[0] = cur;
+  for (int t = 0; t < T; ++t) all[(size_t)t + 1] = nbs[t];
+  if (int rc = ms_check_distinct(h, who, mp, T + 1, all.data())) return rc;  // (the current keyframe among its neighbours: listed twice)
+  if (int rc = ms_check_slots(mp, who, free_slots, n_free, true)) return rc;
+  for (int i = 0; i < n_free; ++i)
+    if (mp->live[(size_t)free_slots[i]]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: free_slots[%d] = %d is live", who, i, free_slots[i]);
+  return ORBX_OK;
+}
+
+// Both phases on the handle's stream, behind mc_check.  Every output is device memory; the list rows hold n_free entries.
+int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, orbx_map_points* mp, orbx_keyframe* cur,
+               orbx_keyframe* const* nbs, int T, int phases, const int* free_slots, int n_free, int* d_counts, int* d_new_slot, int* d_new_nb, int* d_new_i1,
+               int* d_new_i2, double* d_new_pts, uint8_t* d_new_desc, int* d_stats) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  std::vector<orbx_keyframe*> all((size_t)T + 1);
+  std::vector<int> idx((size_t)T + 1);
+  all[0] = cur;
+  for (int t = 0; t < T; ++t) all[(size_t)t + 1] = nbs[t];
+  std::iota(idx.begin(), idx.end(), 0);
+  if (int rc = mf_give_tables(h, mp, all.data(), T + 1, idx.data())) return rc;
+  TriNbPlan P;
+  if (phases & ORBX_MAP_CREATE_NEIGHBOURS) tri_nb_plan(cam, cur, nbs, T, P);
+  const size_t K = (size_t)T + 1, Ts = P.orig.size(), n1 = (size_t)cur->n, NF = (size_t)n_free;
+  const size_t capd = std::min(NF, Ts * n1);                                // pair e takes free_slots[S' + e]: no pair beyond n_free is listed
+  int max_n = 0;
+  size_t n_feat = 0;
+  for (const orbx_keyframe* kf : all) { max_n = std::max(max_n, kf->n); n_feat += (size_t)kf->n; }
+  Carve up, ws;
+  const size_t u_kf = up.take(sizeof(McKf) * K), u_fr = up.take(4 * NF), u_or = up.take(4 * Ts), u_se = up.take(4 * (size_t)T), u_tri = up.take(P.up_bytes);
+  const size_t o_fl = ws.take(n_feat), o_la = ws.take(4 * n1), o_zero = ws.off, o_ch = ws.take(4 * K), o_ns = ws.take(8), o_zend = ws.off, o_tri = ws.take(P.ws_bytes),
+               o_he = ws.take(4 * (1 + 4 * Ts)), o_nb = ws.take(4 * capd), o_i1 = ws.take(4 * capd), o_i2 = ws.take(4 * capd), o_pt = ws.take(24 * capd);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[13], up.off, &hs, &ds)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_map[14], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[14].p;
+  McKf* kt = (McKf*)(hs + u_kf);
+  std::vector<const uint8_t*> mp2((size_t)T);
+  size_t f = 0;
+  for (size_t k = 0; k < K; ++k) {
+    kt[k] = McKf{all[k]->d_mp_slot, all[k]->d_mp_uniq, w + o_fl + f, all[k]->n, 0};
+    if (k > 0) mp2[k - 1] = kt[k].flag;
+    f += (size_t)all[k]->n;
+  }
+  if (NF) std::memcpy(hs + u_fr, free_slots, 4 * NF);
+  int* searched = (int*)(hs + u_se);
+  for (int t = 0; t < T; ++t) searched[t] = -1;
+  for (size_t k = 0; k < Ts; ++k) searched[P.orig[k]] = (int)k;
+  if (Ts) {
+    std::memcpy(hs + u_or, P.orig.data(), 4 * Ts);
+    tri_nb_fill(P, cam, cfg, cur, nbs, kt[0].flag, mp2.data(), hs + u_tri, ds + u_tri, w + o_tri);
+  }
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[13], up.off)) return rc;
+  ORBX_HIP(h, hipMemsetAsync(w + o_zero, 0, o_zend - o_zero, h->stream));
+  if (n1) ORBX_HIP(h, hipMemsetAsync(w + o_la, 0xff, 4 * n1, h->stream));
+  McArgs A{};
+  A.capacity = mp->capacity; A.n_free = n_free; A.n1 = cur->n; A.cap_pairs = (int)capd; A.T = T;
+  A.live = mp->d_live; A.kfs = (const McKf*)(ds + u_kf); A.free_slots = (const int*)(ds + u_fr); A.orig = (const int*)(ds + u_or);
+  A.searched = (const int*)(ds + u_se);
+  A.has1 = cur->d_has_point; A.pts1 = cur->d_points; A.desc1 = cur->d_desc;
+  std::memcpy(A.pose1, cur->pose_wc, sizeof(A.pose1));
+  A.p_nb = (const int*)(w + o_nb); A.p_i1 = (const int*)(w + o_i1); A.p_i2 = (const int*)(w + o_i2); A.p_pts = (const double*)(w + o_pt);
+  A.last = (int*)(w + o_la); A.changed = (int*)(w + o_ch); A.n_stereo = (int*)(w + o_ns);
+  A.counts = d_counts; A.new_slot = d_new_slot; A.new_nb = d_new_nb; A.new_i1 = d_new_i1; A.new_i2 = d_new_i2; A.new_pts = d_new_pts; A.new_desc = d_new_desc;
+  A.stats = d_stats;
+  const dim3 block(MS_THREADS);
+  orbx_prof_begin_call(h);
+  if (max_n > 0) {
+    ProfScope ps(h, "mc_flag_kernel");
+    hipLaunchKernelGGL(mc_flag_kernel, dim3((max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, h->stream, A);
+  }
+  if ((phases & ORBX_MAP_CREATE_STEREO) && n1 > 0) {
+    ProfScope ps(h, "mc_stereo_kernel", true);
+    hipLaunchKernelGGL(mc_stereo_kernel, dim3(1), block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  if (Ts) {
+    if (int rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, ds + u_tri, w + o_tri, (int)capd, (int*)(w + o_he), (int*)(w + o_nb), (int*)(w + o_i1), (int*)(w + o_i2),
+                               (double*)(w + o_pt)))
+      return rc;
+    A.head = (const int*)(w + o_he);
+  }
+  const dim3 pair_grid((unsigned)((std::max<size_t>({capd, 4 * (size_t)T, (size_t)1}) + MS_THREADS - 1) / MS_THREADS));
+  {
+    ProfScope ps(h, "mc_pair_kernel", max_n > 0);
+    hipLaunchKernelGGL(mc_pair_kernel, pair_grid, block, 0, h->stream, A);
+  }
+  if (capd > 0) {
+    ProfScope ps(h, "mc_last_kernel", true);
+    hipLaunchKernelGGL(mc_last_kernel, pair_grid, block, 0, h->stream, A);
+  }
+  if (max_n > 0 && n_free > 0) {
+    ProfScope ps(h, "mc_uniq_kernel", true);
+    hipLaunchKernelGGL(mc_uniq_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, (unsigned)K), block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// orbx_map_remove_points behind its checks: marks, the tables of P's keyframes, marks back, the erase.  *d_cleared: where the
+// number of cleared entries lies.
+int mr_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int n, const int* slots, const int** d_cleared) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t K = P.kfs.size(), N = (size_t)n;
+  if (mp->mark.bytes < (size_t)mp->capacity) {                              // the one fill of the tables: calls leave them 0
+    if (int rc = orbx_reserve(h, mp->mark, (size_t)mp->capacity)) return rc;
+    ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
+  }
+  Carve up;
+  const size_t u_kf = up.take(sizeof(McKf) * K), u_sl = up.take(4 * N), u_cn = up.take(4);
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[15], up.off, &hs, &ds)) return rc;
+  McKf* kt = (McKf*)(hs + u_kf);
+  for (size_t k = 0; k < K; ++k) kt[k] = McKf{const_cast<int*>(P.kfs[k].slots), const_cast<int*>(P.kfs[k].uniq), nullptr, P.kfs[k].n, 0};
+  std::memcpy(hs + u_sl, slots, 4 * N);
+  std::memset(hs + u_cn, 0, 4);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[15], up.off)) return rc;
+  const int* d_slots = (const int*)(ds + u_sl);
+  uint8_t* mark = (uint8_t*)mp->mark.p;
+  const dim3 block(MS_THREADS), list_grid((unsigned)((N + MS_THREADS - 1) / MS_THREADS));
+  *d_cleared = (const int*)(ds + u_cn);
+  orbx_prof_begin_call(h);
+  if (K > 0 && P.max_n > 0) {
+    {
+      ProfScope ps(h, "mr_mark_kernel");
+      hipLaunchKernelGGL(mr_mark_kernel, list_grid, block, 0, h->stream, d_slots, n, mark, 1);
+    }
+    {
+      ProfScope ps(h, "mr_clear_kernel", true);
+      hipLaunchKernelGGL(mr_clear_kernel, dim3((P.max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, h->stream, (const McKf*)(ds + u_kf), mp->capacity,
+                         (const uint8_t*)mark, (int*)(ds + u_cn));
+    }
+    {
+      ProfScope ps(h, "mr_mark_kernel", true);
+      hipLaunchKernelGGL(mr_mark_kernel, list_grid, block, 0, h->stream, d_slots, n, mark, 0);
+    }
+  }
+  return ms_erase_launch(h, mp, d_slots, slots, n);
+}
+
+// the keyframes of a removal or culling call: as the observation calls check theirs, and none twice (their tables are rewritten)
+int mr_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, ObsPlan& P) {
+  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  return ms_check_no_repeat(h, who, n_kfs, kfs);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1948,15 +2292,7 @@ int orbx_map_points_erase(orbx_map_points* mp, const int* slots, int n) {
   if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], 4 * (size_t)n, &hs, &ds)) return rc;
   std::memcpy(hs, slots, 4 * (size_t)n);
   if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], 4 * (size_t)n)) return rc;
-  {
-    ProfScope ps(h, "map_scatter_kernel");
-    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, (const int*)ds, n, (const double*)nullptr,
-                       (const uint8_t*)nullptr, 0, mp->d_pos, mp->d_desc, mp->d_live);
-  }
-  ORBX_HIP(h, hipGetLastError());
-  for (int i = 0; i < n; ++i)
-    if (mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 0; --mp->n_live; }
-  return ORBX_OK;
+  return ms_erase_launch(h, mp, (const int*)ds, slots, n);
 }
 
 int orbx_map_points_download(orbx_map_points* mp, const int* slots, int n, double* positions, uint8_t* desc, uint8_t* live) {
@@ -2514,6 +2850,121 @@ int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_ma
     normals[3 * i] = v ? v[0] : 0.0; normals[3 * i + 1] = v ? v[1] : 0.0; normals[3 * i + 2] = v ? v[2] : 0.0;
   }
   return orbx_map_refresh_points(h, mp, n_kfs, kfs, (int)M, affected_slot, scale_range, mp_desc, normals, min_distance, max_distance, records);
+}
+
+int orbx_keyframe_set_map_point_slots_device(orbx_keyframe* kf, const orbx_map_points* mp, const int* d_slots) {
+  static const char* who = "orbx_keyframe_set_map_point_slots_device";
+  if (!kf) return ORBX_ERR_INVALID;
+  orbx_handle* h = kf->h;
+  if (!mp || mp->h != h || !d_slots || ((uintptr_t)d_slots & 3)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle, or d_slots is null or not 4-byte aligned", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  if (kf->n > 0) {
+    const dim3 grid((kf->n + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
+    {
+      ProfScope ps(h, "mc_table_kernel");
+      hipLaunchKernelGGL(mc_table_kernel, grid, block, 0, h->stream, d_slots, kf->n, mp->capacity, kf->d_mp_slot);
+    }
+    {
+      ProfScope ps(h, "mc_uniq_one_kernel", true);
+      hipLaunchKernelGGL(mc_uniq_one_kernel, grid, block, 0, h->stream, (const int*)kf->d_mp_slot, kf->d_mp_uniq, kf->n);
+    }
+    ORBX_HIP(h, hipGetLastError());
+  }
+  kf->slot_store = mp;
+  return ORBX_OK;
+}
+
+int orbx_map_create_points_device(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, orbx_map_points* mp,
+                                  orbx_keyframe* cur, orbx_keyframe* const* nbs, int T, int phases, const int* free_slots, int n_free, int* d_counts,
+                                  int* d_new_slot, int* d_new_neighbour, int* d_new_idx1, int* d_new_idx2, double* d_new_points, uint8_t* d_new_desc, int* d_stats) {
+  static const char* who = "orbx_map_create_points_device";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
+  if (!d_counts || (T > 0 && !d_stats) || (n_free > 0 && (!d_new_slot || !d_new_neighbour || !d_new_idx1 || !d_new_idx2 || !d_new_points || !d_new_desc)) ||
+      ((uintptr_t)d_new_desc & 15))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_new_desc is 16-byte aligned)", who);
+  return mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, d_counts, d_new_slot, d_new_neighbour, d_new_idx1, d_new_idx2, d_new_points,
+                    d_new_desc, d_stats);
+}
+
+int orbx_map_create_points(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, orbx_map_points* mp, orbx_keyframe* cur,
+                           orbx_keyframe* const* nbs, int T, int phases, const int* free_slots, int n_free, int* counts, int* new_slot, int* new_neighbour,
+                           int* new_idx1, int* new_idx2, double* new_points, int* stats) {
+  static const char* who = "orbx_map_create_points";
+  if (!h) return ORBX_ERR_INVALID;
+  if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
+  if (!counts || (T > 0 && !stats) || (n_free > 0 && (!new_slot || !new_neighbour || !new_idx1 || !new_idx2 || !new_points)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  // ONE download: counts | stats | the lists; the descriptors stay behind them for set_device
+  const size_t NF = (size_t)n_free, Tz = (size_t)T;
+  Carve out;
+  const size_t o_cn = out.take(16), o_st = out.take(16 * Tz), o_sl = out.take(4 * NF), o_nb = out.take(4 * NF), o_i1 = out.take(4 * NF), o_i2 = out.take(4 * NF),
+               o_pt = out.take(24 * NF);
+  const size_t down = out.off;
+  const size_t o_de = out.take(32 * NF);
+  HostCall c;
+  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+  uint8_t* d = c.dout;
+  if (int rc = mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, (int*)(d + o_cn), (int*)(d + o_sl), (int*)(d + o_nb), (int*)(d + o_i1),
+                          (int*)(d + o_i2), (double*)(d + o_pt), d + o_de, (int*)(d + o_st)))
+    return rc;
+  if (int rc = orbx_host_call_download(h, c, down)) return rc;
+  std::memcpy(counts, c.ho + o_cn, 16);
+  if (Tz) std::memcpy(stats, c.ho + o_st, 16 * Tz);
+  const size_t created = (size_t)counts[2];
+  if (created == 0) return ORBX_OK;
+  std::memcpy(new_slot, c.ho + o_sl, 4 * created); std::memcpy(new_neighbour, c.ho + o_nb, 4 * created);
+  std::memcpy(new_idx1, c.ho + o_i1, 4 * created); std::memcpy(new_idx2, c.ho + o_i2, 4 * created);
+  std::memcpy(new_points, c.ho + o_pt, 24 * created);
+  return ms_set(mp, who, free_slots, (int)created, (const double*)(d + o_pt), d + o_de, false);
+}
+
+int orbx_map_remove_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n, const int* slots, int* n_cleared) {
+  static const char* who = "orbx_map_remove_points";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+  if (n == 0) { if (n_cleared) *n_cleared = 0; return ORBX_OK; }
+  const int* d_cleared = nullptr;
+  if (int rc = mr_enqueue(h, mp, P.C, n, slots, &d_cleared)) return rc;
+  if (!n_cleared) return ORBX_OK;
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, 4)) return rc;
+  ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_cleared, 4, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  std::memcpy(n_cleared, h->pin_map.p, 4);
+  return ORBX_OK;
+}
+
+int orbx_map_cull_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* cand, int min_observations,
+                         int* n_culled, int* culled) {
+  static const char* who = "orbx_map_cull_points";
+  if (!h) return ORBX_ERR_INVALID;
+  ObsPlan P;
+  if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+  if (int rc = obs_check_slots(mp, who, cand, M)) return rc;
+  if (!n_culled || (M > 0 && !culled)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  *n_culled = 0;
+  if (M == 0) return ORBX_OK;
+  ORBX_HIP(h, hipSetDevice(h->device));
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, 4 * (size_t)M)) return rc;
+  ObsCall c;
+  c.n_points = M; c.slots = cand;
+  const int* d_count = nullptr;
+  orbx_prof_begin_call(h);
+  if (int rc = obs_enqueue(h, mp, P, c, nullptr, &d_count)) return rc;
+  // the one download: the candidates' observer counts.  The comparison is the host's: the mirror needs the list anyway.
+  ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_count, 4 * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  const int* count = (const int*)h->pin_map.p;
+  int n = 0;
+  for (int i = 0; i < M; ++i)
+    if (count[i] < min_observations) culled[n++] = cand[i];               // local_mapper.rs:452: strictly fewer
+  *n_culled = n;
+  if (n == 0) return ORBX_OK;
+  const int* d_cleared = nullptr;
+  return mr_enqueue(h, mp, P.C, n, culled, &d_cleared);
 }
 
 }  // extern "C"

@@ -242,7 +242,7 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
-  DevBuf ws_map[13];                     // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs, [8] observations: counts, cursors, block sums and the unordered entries; the redundancy call's list and chunk sums, [9] observations: the call's keyframe table, slots and candidates, [10] orbx_map_refresh_points: the lists and the gathered positions, [11] fuse and merge: L's gathered rows, matches, edges, claims, per-node and per-feature scratch, [12] fuse and merge: the call's keyframe and target tables
+  DevBuf ws_map[16];                     // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs, [8] observations: counts, cursors, block sums and the unordered entries; the redundancy call's list and chunk sums, [9] observations: the call's keyframe table, slots and candidates, [10] orbx_map_refresh_points: the lists and the gathered positions, [11] fuse and merge: L's gathered rows, matches, edges, claims, per-node and per-feature scratch, [12] fuse and merge: the call's keyframe and target tables, [13] point creation: the call's tables (keyframes, free slots, the neighbour loop's), [14] point creation: flags, last-writer cells and the neighbour loop's scratch and lists, [15] point removal: the call's keyframe table and slots, the counter
   PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
   UploadRing ring_map;                   // the tables on their way to ws_map[2]
   // pipelined host-batch path: copy streams, events, double-buffered staging
@@ -405,6 +405,23 @@ int launch_triangulate_pairs(orbx_handle* h, const TriCommon& c, const TriNeighb
 // d_head [1 + 4T] = n_created | per neighbour (unused, matches_found, triangulated, validated); lists of `cap` entries
 int launch_triangulate_compact(orbx_handle* h, const TriNeighbour* d_many, int T, const uint16_t* d_status, const double* d_points, int cap,
                                int* d_head, int* d_out_nb, int* d_out_idx1, int* d_out_idx2, double* d_out_points);
+// ---- the neighbour loop of triangulate_from_neighbors (keyframe.hip; triangulation.rs:117-294) ----
+// What the loop is for one current keyframe and its neighbours, made on the host: the neighbours that are searched, and byte offsets
+// into two device blocks — the uploaded tables (items | neighbours | FeatureVector tables: up_bytes) and the scratch (ws_bytes).
+struct TriNbPlan {
+  struct Slices { size_t sorted, lo, hi, cell_start, prop, owner, pairs, n_out, cell_of, taken; bool bow; };
+  std::vector<int> orig;       // searched neighbour k -> index in kfs[]
+  std::vector<Slices> sl;      // [searched]
+  int n1 = 0, max_n2 = 0, cols = 0, rows = 0;
+  size_t up_bytes = 0, ws_bytes = 0, o_items = 0, o_nbs = 0, o_status = 0, o_points = 0;
+};
+void tri_nb_plan(const orbx_camera* cam, const orbx_keyframe* cur, const orbx_keyframe* const* kfs, int T, TriNbPlan& P);
+// the tables into up [up_bytes] (host), as they will lie at d_up; d_mp1 / d_mp2 [T]: the map-point flags of cur / kfs[t] (device)
+void tri_nb_fill(const TriNbPlan& P, const orbx_camera* cam, const orbx_triangulation_config* cfg, const orbx_keyframe* cur, const orbx_keyframe* const* kfs,
+                 const uint8_t* d_mp1, const uint8_t* const* d_mp2, uint8_t* up, uint8_t* d_up, uint8_t* d_ws);
+// searches, pair loop, ordered compaction (the lists of `cap` rows; d_head [1 + 4 * searched], d_out_nb counts searched neighbours)
+int tri_nb_launch(orbx_handle* h, const TriNbPlan& P, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, const orbx_keyframe* cur,
+                  const uint8_t* d_up, uint8_t* d_ws, int cap, int* d_head, int* d_out_nb, int* d_out_idx1, int* d_out_idx2, double* d_out_points);
 int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_positions, const uint8_t* d_mp_desc, int P,
                        const double* d_kf_pose_cw, const int* d_kf_off, const orbx_keypoint* d_kps, const uint8_t* d_descs,
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist);
