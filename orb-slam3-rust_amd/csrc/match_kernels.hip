@@ -207,7 +207,7 @@ __global__ __launch_bounds__(SML_THREADS) void stereo_match_lds_kernel(
     const int* __restrict__ nkp, int cap, float max_disp, float min_disp,
     const int* __restrict__ bstart, const int* __restrict__ sidx, const float2* __restrict__ sxy,
     int2* __restrict__ tmp, orbx_camera cam, orbx_dmatch* __restrict__ matches,
-    int* __restrict__ nmatches, double* __restrict__ points, uint8_t* __restrict__ has_point) {
+    int* __restrict__ nmatches, double* __restrict__ points, uint8_t* __restrict__ has_point, int pairs_reversed) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sml_smem[];
   uint4* s_desc = reinterpret_cast<uint4*>(sml_smem);                                  // [cap][2]
   float2* s_xy = reinterpret_cast<float2*>(sml_smem + (size_t)cap * 32);               // [cap]
@@ -215,7 +215,8 @@ __global__ __launch_bounds__(SML_THREADS) void stereo_match_lds_kernel(
   int* s_bs = s_idx + cap;                                                             // [SB_ROWS + 1]
   int* s_cur = s_bs + (SB_ROWS + 1);                                                   // FUSED: [SB_ROWS] counters / cursors, then the wave totals of the compaction
   int2* s_tmp = reinterpret_cast<int2*>(sml_smem + (((size_t)cap * 44 + (size_t)(2 * SB_ROWS + 1) * 4 + 7) & ~(size_t)7));   // FUSED: [cap]
-  const int pair = blockIdx.x;
+  // (the pairs in the order opposite to the extractor's last launch: the keypoints and descriptors written last are read first)
+  const int pair = pairs_reversed ? (int)(gridDim.x - 1u - blockIdx.x) : (int)blockIdx.x;
   const orbx_keypoint* kpL = kp + (size_t)(2 * pair) * cap;
   const uint8_t* dL = desc + (size_t)(2 * pair) * cap * 32;
   const uint8_t* dR = dL + (size_t)cap * 32;
@@ -763,7 +764,7 @@ __global__ __launch_bounds__(256) void hamming_batch_kernel(const uint8_t* __res
 
 int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
                         const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
-                        double* d_points, uint8_t* d_has_point) {
+                        double* d_points, uint8_t* d_has_point, bool pairs_reversed) {
   if (batch <= 0) return ORBX_OK;
   const hipStream_t st = h->stream;
   // workspace: tmp int2[batch*cap] | sxy float2[batch*cap] | sidx int[batch*cap] | bstart int[batch*(SB_ROWS+1)]
@@ -789,7 +790,7 @@ int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, co
   if (use_lds && lds_fused <= 160 * 1024 && sm_env != 2) {
     ProfScope ps(h, "stereo_match_kernel", true);
     hipLaunchKernelGGL(stereo_match_lds_kernel<true>, dim3(batch), dim3(SML_THREADS), lds_fused, st, d_kp, d_desc, d_nkp,
-                       cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point);
+                       cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point, pairs_reversed ? 1 : 0);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   }
@@ -800,7 +801,7 @@ int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, co
   if (use_lds) {
     ProfScope ps(h, "stereo_match_kernel", true);
     hipLaunchKernelGGL(stereo_match_lds_kernel<false>, dim3(batch), dim3(SML_THREADS), lds_need, st, d_kp, d_desc, d_nkp,
-                       cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point);
+                       cap_kp, max_disp, min_disp, bstart, sidx, sxy, tmp, h->cam, d_matches, d_nmatches, d_points, d_has_point, pairs_reversed ? 1 : 0);
   } else {
     ProfScope ps(h, "stereo_match_kernel", true);
     dim3 grid((cap_kp + SM_LEFT_PER_BLOCK - 1) / SM_LEFT_PER_BLOCK, batch);

@@ -50,20 +50,31 @@ __constant__ __attribute__((aligned(16))) signed char c_pattern[256 * 4];
 // loses the locality.)  The division by per_img uses the host's floor(2^32/per_img) and one fix-up
 // step — these kernels launch 100k+ short blocks and a generic division is ~40 scalar instructions
 // of prologue.  Speed only; any placement gives the same results.
-struct XcdMap { unsigned per_img, magic; };
+// Direction: consecutive launches of a call walk the image groups in opposite directions (XcdOrder in launch_orb_extract), so that a
+// launch starts with the images its predecessor wrote or read last instead of those touched longest ago: resize 0.506 -> 0.490 ms, Harris
+// 0.250 -> 0.236 ms per 512 pairs (profiles/r08_pyramid_order_and_tail.txt).  Reversed, the group is n_groups-1-grp = (grp ^ ~0) + n_groups (rev_xor, rev_add; forward 0, 0);
+// x stays, so an image keeps its XCD, and the partial last group (n_img not a multiple of 8) is then dispatched first.
+struct XcdMap { unsigned per_img, magic, rev_xor, rev_add; };
 __device__ __forceinline__ bool xcd_decode_at(XcdMap m, int n_img, unsigned L, int& img, int& b) {
   const unsigned x = L & 7u, slot = L >> 3;
   unsigned grp = __umulhi(slot, m.magic);
   unsigned r = slot - grp * m.per_img;
   if (r >= m.per_img) { ++grp; r -= m.per_img; }
+  grp = (grp ^ m.rev_xor) + m.rev_add;
   b = (int)r;
   img = (int)(grp * 8u + x);
   return img < n_img;
 }
 __device__ __forceinline__ bool xcd_decode(XcdMap m, int n_img, int& img, int& b) { return xcd_decode_at(m, n_img, blockIdx.x, img, b); }
-static inline XcdMap xcd_map(int per_img) {
-  return XcdMap{(unsigned)per_img, per_img > 1 ? (unsigned)(0x100000000ull / (unsigned)per_img) : 0xffffffffu};
+static inline XcdMap xcd_map(int per_img, int n_img = 0, bool reversed = false) {
+  return XcdMap{(unsigned)per_img, per_img > 1 ? (unsigned)(0x100000000ull / (unsigned)per_img) : 0xffffffffu,
+                reversed ? 0xffffffffu : 0u, reversed ? (unsigned)((n_img + 7) / 8) : 0u};
 }
+// the direction of a call's k-th launch through the map: a function of the launch's position in the call, no state between calls
+struct XcdOrder {
+  int n_img, k = 0;
+  XcdMap next(int per_img) { return xcd_map(per_img, n_img, (k++ & 1) != 0); }
+};
 static inline dim3 xcd_grid(int per_img, int n_img) { return dim3(8u * (unsigned)((n_img + 7) / 8) * (unsigned)per_img); }
 
 __device__ __forceinline__ const uint8_t* level_ptr(const OrbSrc& s, const OrbGeom& g, int img, int l,
@@ -2281,6 +2292,7 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
     s.l0 = s.pyr; s.l0_img_stride = g.slot_bytes; s.l0_pitch = g.lv[0].pitch;
   }
   h->last_src = s; h->last_n_images = n;     // (orbx_debug_read_level addresses these images)
+  XcdOrder ord{n};
   {
     ProfScope ps(h, "resize_kernel");
     for (int l = 1; l < nl; ++l) {
@@ -2290,10 +2302,10 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
       const int tx = (g.lv[l].w + 63) / 64, ty = (g.lv[l].h + 16 * rows - 1) / (16 * rows);
       const int chains = (tx * ty + RESIZE_CHAIN - 1) / RESIZE_CHAIN;
       if (small)
-        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS_SMALL>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
+        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS_SMALL>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, ord.next(chains), tx, tx * ty,
                            tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
       else
-        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, xcd_map(chains), tx, tx * ty,
+        hipLaunchKernelGGL(resize_kernel<RESIZE_ROWS>, xcd_grid(chains, n), dim3(256), 0, st, s, g, l, n, ord.next(chains), tx, tx * ty,
                            tab + h->resize_tab_off[2 * l], tab + h->resize_tab_off[2 * l + 1]);
     }
   }
@@ -2304,10 +2316,11 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
     // chains of FAST_CHAIN tiles per block once there are blocks to spare (each CU holds 8): for a pair one tile per block
     const int chain_len = (size_t)g.ftiles_total * n >= (size_t)4 * 8 * h->n_cu ? FAST_CHAIN : 1;
     const int chains = (g.ftiles_total + chain_len - 1) / chain_len;
+    const XcdMap fxm = ord.next(chains);
     if (g.fast_threshold < 128)
-      hipLaunchKernelGGL(fast_kernel<true>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
+      hipLaunchKernelGGL(fast_kernel<true>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, fxm, tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
     else
-      hipLaunchKernelGGL(fast_kernel<false>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, xcd_map(chains), tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
+      hipLaunchKernelGGL(fast_kernel<false>, xcd_grid(chains, n), dim3(FT_THREADS), 0, st, s, g, n, fxm, tab + h->ftile_tab_off, cand, cc, hs, g.ftiles_total, chain_len, h->d_status);
   }
   {
     ProfScope ps(h, "harris_select_kernel", true);
@@ -2327,12 +2340,12 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
     for (int l = 0; l < nl; ++l) hp.start[l + 1] = hp.start[l] + std::max(1, (int)lrint(hb_total * ((double)g.lv[l].w * g.lv[l].h) / area));
     for (int l = nl; l < ORBX_MAX_LEVELS; ++l) hp.start[l + 1] = hp.start[nl];
     const int hblocks = hp.start[nl];
-    hipLaunchKernelGGL(harris_select_kernel, xcd_grid(hblocks, n), dim3(256), 0, st, s, g, n, xcd_map(hblocks),
+    hipLaunchKernelGGL(harris_select_kernel, xcd_grid(hblocks, n), dim3(256), 0, st, s, g, n, ord.next(hblocks),
                        (const unsigned*)cand, cc, hs, sel, sc, hp);
   }
   {
     ProfScope ps(h, "rank_select_kernel", true);
-    hipLaunchKernelGGL(rank_select_kernel, xcd_grid(nl, n), dim3(RK_NT), 0, st, g, n, xcd_map(nl), sel, sc,
+    hipLaunchKernelGGL(rank_select_kernel, xcd_grid(nl, n), dim3(RK_NT), 0, st, g, n, ord.next(nl), sel, sc,
                        sel2, kp, dtile);
   }
   // Round 5: one workgroup per describe tile, the patch blur shared by the tile's keypoints (describe_tile_kernel); ORBX_DESC_TILE=0 (read when
@@ -2344,14 +2357,14 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
   if (g.dt_total > 0 && (dt_force || (size_t)g.dt_total * (size_t)n >= (size_t)8 * (size_t)h->n_cu)) {
     ProfScope ps(h, "describe_tile_kernel", true);
     // the level's bytes of a window are read where the level lives: level 0 may be the caller's image (row pitch s.l0_pitch >= w >= 64)
-    hipLaunchKernelGGL(describe_tile_kernel, xcd_grid(g.dt_total, n), dim3(256), 0, st, s, g, n, xcd_map(g.dt_total), tab + h->dtile_tab_off,
+    hipLaunchKernelGGL(describe_tile_kernel, xcd_grid(g.dt_total, n), dim3(256), 0, st, s, g, n, ord.next(g.dt_total), tab + h->dtile_tab_off,
                        (const uint2*)dtile, (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp,
                        d_desc, d_nkp, cap_kp, (float)h->orb.patch_size, h->d_status);
   } else {
     ProfScope ps(h, "describe_fused_kernel", true);
     const int blocks_x16 = (h->orb.n_features + 64 + 15) / 16;   // 16 keypoints per block and round
     const int blocks_x = (blocks_x16 + ORBX_DF_ITERS - 1) / ORBX_DF_ITERS;
-    hipLaunchKernelGGL(describe_fused_kernel, xcd_grid(blocks_x, n), dim3(256), 0, st, s, g, n, xcd_map(blocks_x), blocks_x,
+    hipLaunchKernelGGL(describe_fused_kernel, xcd_grid(blocks_x, n), dim3(256), 0, st, s, g, n, ord.next(blocks_x), blocks_x,
                        (const unsigned long long*)sel2, (const unsigned long long*)sel, kp, d_kp, d_desc,
                        d_nkp, cap_kp, (float)h->orb.patch_size, h->d_status);
   }
@@ -2363,6 +2376,7 @@ int launch_orb_extract(orbx_handle* h, const uint8_t* d_images, int n_images, in
   // Round 5: the same with the second stream staggered by a phase, each range starting behind the previous one's pyramid: 145.2 k frames/s on
   // one stream, 144.6 k as 2 ranges, 139.5 k as 4 — every kernel stretches by what the other stream takes (profiles/r05_stagger_two_streams_negative.txt);
   // removed.  The whole-level blur on a second stream beside the FAST chain, while the descriptors still read a blurred pyramid: +2-3 %; moot since round 4.)
+  h->xcd_next_reversed = (ord.k & 1) != 0;
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

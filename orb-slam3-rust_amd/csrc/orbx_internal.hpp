@@ -219,6 +219,7 @@ struct orbx_handle {
   std::vector<unsigned> resize_tab_off;  // element offsets: [2*l] x table, [2*l+1] y table
   unsigned btile_tab_off = 0, ftile_tab_off = 0, dtile_tab_off = 0;   // tile -> (level, tx, ty) tables of the blur / FAST / describe launches, same buffer
   OrbSrc last_src{};                               // where the level images of the last extraction live, and how many images it held:
+  bool xcd_next_reversed = false;                  // set by launch_orb_extract: the image order of the launch after its last one (the matcher's, in orbx_process_stereo_batch_device)
   int last_n_images = 0;                           // orbx_debug_read_level(which = 1) blurs them on demand (the product path keeps no blurred pyramid)
   // grow-only workspaces
   DevBuf ws_pyr, ws_blur, ws_cand, ws_counters, ws_sel, ws_sel2, ws_match, ws_io[12];
@@ -334,9 +335,10 @@ void orbx_prof_end_call(orbx_handle* h);
 
 // ---- kernel launchers (defined in the .hip files) --------------------------------------------------
 // matcher (match_kernels.hip)
+// (pairs_reversed: the one-workgroup-per-pair matcher walks the pairs downwards — the launch after an extraction whose last launch walked upwards)
 int launch_stereo_match(orbx_handle* h, int batch, const orbx_keypoint* d_kp, const uint8_t* d_desc,
                         const int* d_nkp, int cap_kp, orbx_dmatch* d_matches, int* d_nmatches,
-                        double* d_points, uint8_t* d_has_point);
+                        double* d_points, uint8_t* d_has_point, bool pairs_reversed = false);
 int launch_crosscheck(orbx_handle* h, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                       orbx_dmatch* d_out, int* d_n_out);
 int launch_hamming_batch(orbx_handle* h, const uint8_t* d_a, const uint8_t* d_b, int n, uint32_t* d_out);
