@@ -616,6 +616,29 @@ int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_in
                            double* poses_wc_out, double* vel_out, double* bias_out, int* iterations,
                            double* initial_error, double* final_error);
 
+/* orbx_ba_solve_inertial with the observations in the 16-byte form.  kf_idx as in orbx_ba_obs32: >= 0 the window keyframe, < 0 the
+ * fixed observer -1 - kf_idx (F = the identity pose).  is_stereo, which orbx_ba_obs carries in bit 0 of _pad, rides in mp_idx:
+ * mp_idx & ORBX_BA_OBS32_STEREO is the flag and mp_idx & ~ORBX_BA_OBS32_STEREO the point index, so M >= 0x40000000 is refused
+ * (ORBX_ERR_INVALID).  ONLY the inertial entry points read the bit: the visual and global forms take mp_idx whole, where a set bit
+ * is an index out of range.  The decode is made on the device in the passes that group the observations; every kernel behind them
+ * sees the same values, so all outputs equal orbx_ba_solve_inertial's on the widened observations (flag in _pad) bit for bit.
+ * _device: d_obs32 is DEVICE memory of the handle's device (16-byte aligned), written by work already ordered on the handle's
+ * stream — orbx_map_collect_inertial_window_device's d_obs32; an index out of range names the observation, not its contents.
+ * Everything else — edges, refusals, ORBX_ERR_EMPTY, outputs for all K keyframes — is orbx_ba_solve_inertial's. */
+#define ORBX_BA_OBS32_STEREO 0x40000000
+int orbx_ba_solve_inertial_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K,
+                                 const double* poses_wc, const double* velocities, const double* biases, int F,
+                                 const double* fixed_poses_cw, int M, double* points, int N, const orbx_ba_obs32* obs32, int E,
+                                 const int* edge_kf, const double* preint, orbx_should_stop_fn should_stop, void* user,
+                                 double* poses_wc_out, double* vel_out, double* bias_out, int* iterations,
+                                 double* initial_error, double* final_error);
+int orbx_ba_solve_inertial_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K,
+                                        const double* poses_wc, const double* velocities, const double* biases, int F,
+                                        const double* fixed_poses_cw, int M, double* points, int N, const orbx_ba_obs32* d_obs32,
+                                        int E, const int* edge_kf, const double* preint, orbx_should_stop_fn should_stop,
+                                        void* user, double* poses_wc_out, double* vel_out, double* bias_out, int* iterations,
+                                        double* initial_error, double* final_error);
+
 /* ---- PnP-RANSAC pose estimation (src/geometry/pnp.rs) --------------------------------------------------------
  * Replaces solve_pnp_ransac / solve_pnp_ransac_detailed (pnp.rs:29-134): cv::solvePnPRansac(100 iterations, 8 px,
  * confidence 0.99, SOLVEPNP_ITERATIVE, useExtrinsicGuess = prior given) + Rodrigues, the result inverted back to T_wc, then the
@@ -1204,7 +1227,7 @@ int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_trac
  * (the keyframes are const here: the caller applies them with orbx_keyframe_set_pose, as it applies ids), counts_out [4] = K, F, M,
  * N, and the solver's scalars.  ORBX_ERR_EMPTY where the collection or the solver says so, the store untouched.  Not with an
  * all-reduce hook / communicator installed.
- * Still the caller's: ids, orbx_keyframe_set_pose, the spanning tree, and the inertial branch (temporal chain, preintegrations). */
+ * Still the caller's: ids, orbx_keyframe_set_pose, the spanning tree.  (The inertial branch: orbx_map_local_inertial_ba below.) */
 int orbx_map_collect_ba_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur,
                                       int max_covisible, int list_cap, int obs_cap, int* d_counts, int* d_local_kf, int* d_fixed_kf,
                                       int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32);
@@ -1214,6 +1237,54 @@ int orbx_map_collect_ba_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, c
 int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs,
                       const orbx_keyframe* const* kfs, int cur, orbx_should_stop_fn should_stop, void* user, int* local_kf_out,
                       double* poses_wc_out, int* counts_out, int* iterations, double* initial_error, double* final_error);
+
+/* ---- local INERTIAL BA from the resident map (local_inertial_ba.rs:366-421, :930-1030; local_mapper.rs:343-375) ----
+ * Once the IMU is initialised every keyframe's local BA takes the inertial branch: the window is a temporal chain, not a covisibility
+ * neighbourhood, and an observation says whether its feature has a stereo point.  kfs [n_kfs] as above (host array, copied before the
+ * call returns; is_bad filtering = leaving a keyframe out, which also stands for the existence test of collect_fixed_keyframes,
+ * :418-421).  chain [n_chain]: positions in kfs[], OLDEST FIRST — collect_temporal_keyframes' result (:366-384); the caller follows
+ * its own prev_kf links, ids and links being the caller's.
+ *   [spec] K = n_chain; chain[0] is the anchor: a window keyframe (index 0) whose observations are fixed (:1009-1013).
+ *   [spec] P = the distinct live slots of the chain's tables in first-seen order, keyframes in chain order and features in index
+ *     order (:387-403): what ORBX_MAP_SOURCE_KEYFRAMES gives for one frame that names the chain.  M = |P|.
+ *   [spec] c(k), for every keyframe of kfs[], exactly as for the visual window: every feature counts, repeats included; no table: 0.
+ *   [spec] fixed = the keyframes not in the chain with c(k) > 0, by ascending position in kfs[].  F = 1 + their number: fixed index 0
+ *     is the anchor (:973-978), fixed index 1 + j is fixed[j].
+ *   [spec] observations: the observers in the order chain[0], chain[1..], fixed[0..], each observer's counted features in index
+ *     order, one orbx_ba_obs32 each: kf_idx = i for chain[i], i >= 1 (window index 0 never occurs); -1 for chain[0]; -2 - j for
+ *     fixed[j].  mp_idx = the position in P, OR ORBX_BA_OBS32_STEREO where the observer's has_point[feature] != 0 (:1006-1007; a
+ *     keyframe created without d_has_point never sets it).  u, v = the keypoint's x, y as the f32 they are.  N = their number.
+ * orbx_map_collect_inertial_window_device: outputs, device memory: d_counts [4] int32 = K, F, M, N; d_fixed_kf [n_kfs] int32, entries
+ * [0, F - 1) then -1; d_list_slot [list_cap], d_positions [list_cap][3]: rows [0, M); d_obs32 [obs_cap] (16-byte aligned): rows
+ * [0, N).  list_cap must reach the chain's feature counts summed, at most the capacity; obs_cap the feature counts of kfs[] summed.
+ * Asynchronous on the handle's stream; the store's tables are left as found; no launch is sized by the capacity; every output is the
+ * same bytes on every run.  ORBX_ERR_EMPTY, before anything is enqueued: n_chain < 2 (:940-942).  ORBX_ERR_INVALID, before anything
+ * is enqueued: a chain entry outside [0, n_kfs) or listed twice, n_kfs > 65535, a cap below its bound, a keyframe of another handle
+ * or whose table is bound to another store.
+ * orbx_map_collect_inertial_window: the same with host outputs, synchronous; M = 0 (:946-948) is ORBX_ERR_EMPTY with counts and
+ * fixed_kf written and no rows.  With poses_wc = the chain's poses and fixed T_cw = the inverses of the anchor's and fixed[]'s poses
+ * its outputs are orbx_ba_solve_inertial_obs32's arguments.
+ *
+ * orbx_map_local_inertial_ba = phases 1-3 of the inertial branch (local_mapper.rs:343-375): the collection; ONE download of counts,
+ * fixed keyframes, P's slots and positions; poses_wc from kfs[chain[i]]'s pose_wc and the fixed T_cw from the anchor and fixed[];
+ * orbx_ba_solve_inertial_obs32_device on the observations where they lie; then, if the solve iterated (:363), the M positions written
+ * to P's slots, positions only.  velocities [K][3], biases [K][6], edge_kf [E][2] (window indices = positions in chain[]) and
+ * preint [E][11] are the caller's, as for orbx_ba_solve_inertial (build_imu_edges is a loop over preintegrations the host holds);
+ * every rule for them holds, and they are checked before anything is enqueued.  Outputs, host memory, for all K keyframes:
+ * poses_wc_out [K][7], vel_out [K][3], bias_out [K][6]; fixed_kf_out [n_kfs]; counts_out [4]; the solver's scalars.  The keyframes are
+ * const: the caller applies orbx_keyframe_set_pose and keeps velocities and biases.  ORBX_ERR_EMPTY / ORBX_ERR_INVALID as the parts
+ * define them (more than 51 keyframes: the solver's), the store untouched.  Not with an all-reduce hook / communicator installed. */
+int orbx_map_collect_inertial_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs,
+                                            int n_chain, const int* chain, int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf,
+                                            int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32);
+int orbx_map_collect_inertial_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain,
+                                     const int* chain, int list_cap, int obs_cap, int* counts, int* fixed_kf, int* list_slot,
+                                     double* positions, orbx_ba_obs32* obs32);
+int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, orbx_map_points* mp,
+                               int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain, const double* velocities,
+                               const double* biases, int E, const int* edge_kf, const double* preint,
+                               orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out, double* bias_out,
+                               int* fixed_kf_out, int* counts_out, int* iterations, double* initial_error, double* final_error);
 
 /* ---- observations from the resident map: lists, refresh, redundancy (map_point.rs:140-156; local_mapper.rs:421-469, :487-583) ----
  * mp.observations — which keyframes see a point, and at which feature — is the inverse of the slot tables.  Like the covisibility

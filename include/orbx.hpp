@@ -1780,6 +1780,126 @@ inline std::optional<InertialBAResultData> solve_inertial_ba(Handle& h, const In
   return r;
 }
 
+// ---- local inertial BA from the resident map (orbx.h, "local INERTIAL BA from the resident map") ----
+// The window of a temporal chain (positions in `keyframes`, oldest first: collect_temporal_keyframes' result), collected on the
+// device.  mp_idx of an observation carries is_stereo as ORBX_BA_OBS32_STEREO.
+struct InertialBAWindow {
+  int K = 0, F = 0, M = 0, N = 0;
+  std::vector<int> fixed_kf;                           // [F - 1]: the other observers, ascending (fixed index 0 is the anchor chain[0])
+  std::vector<int> list_slot;                          // [M]
+  std::vector<std::array<double, 3>> positions;        // [M]
+  std::vector<orbx_ba_obs32> obs32;                    // [N]
+};
+
+inline void inertial_window_bounds(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& chain,
+                                   int* list_cap, int* obs_cap) {
+  std::vector<int> kf_n;
+  size_t all = 0, cand = 0;
+  for (const orbx_keyframe* k : keyframes) {
+    int n = 0;
+    h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+    kf_n.push_back(n); all += (size_t)n;
+  }
+  for (int c : chain) if (c >= 0 && c < (int)kf_n.size()) cand += (size_t)kf_n[(size_t)c];
+  *list_cap = (int)std::min(cand, (size_t)store.capacity());
+  *obs_cap = (int)all;
+}
+
+// orbx_map_collect_inertial_window_device: every output is the caller's device memory (d_counts [4], d_fixed_kf [keyframes.size()],
+// d_list_slot / d_positions [list_cap], d_obs32 [obs_cap], 16-byte aligned); asynchronous.  false where the chain is shorter than two.
+inline bool map_collect_inertial_window_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& chain,
+                                               int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf, int* d_list_slot, double* d_positions,
+                                               orbx_ba_obs32* d_obs32) {
+  const int rc = orbx_map_collect_inertial_window_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)chain.size(), chain.data(), list_cap,
+                                                         obs_cap, d_counts, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+  if (rc == ORBX_ERR_EMPTY) return false;
+  h.check(rc);
+  return true;
+}
+
+// orbx_map_collect_inertial_window: the same into host vectors, synchronous; nullopt where the reference returns None (:940-942, :946-948).
+inline std::optional<InertialBAWindow> map_collect_inertial_window(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes,
+                                                                   const std::vector<int>& chain) {
+  int list_cap = 0, obs_cap = 0;
+  inertial_window_bounds(h, store, keyframes, chain, &list_cap, &obs_cap);
+  InertialBAWindow w;
+  int counts[4] = {0, 0, 0, 0};
+  w.fixed_kf.assign(std::max<size_t>(keyframes.size(), 1), -1);
+  w.list_slot.resize(std::max(list_cap, 1)); w.positions.resize(std::max(list_cap, 1)); w.obs32.resize(std::max(obs_cap, 1));
+  const int rc = orbx_map_collect_inertial_window(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), (int)chain.size(), chain.data(), list_cap, obs_cap,
+                                                  counts, w.fixed_kf.data(), w.list_slot.data(), w.positions[0].data(), w.obs32.data());
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  w.K = counts[0]; w.F = counts[1]; w.M = counts[2]; w.N = counts[3];
+  w.fixed_kf.resize((size_t)w.F - 1); w.list_slot.resize((size_t)w.M); w.positions.resize((size_t)w.M); w.obs32.resize((size_t)w.N);
+  return w;
+}
+
+struct MapLocalInertialBAResult {                      // row i of the three belongs to keyframes[chain[i]]; row 0 is the anchor's (the reference skips it, :1250)
+  int K = 0, F = 0, M = 0, N = 0;
+  std::vector<SE3> poses_wc;
+  std::vector<std::array<double, 3>> velocities;
+  std::vector<ImuBias> biases;
+  std::vector<int> fixed_kf;                           // [F - 1]
+  size_t iterations = 0;
+  double initial_error = 0, final_error = 0;
+};
+
+// orbx_map_local_inertial_ba: local_bundle_adjustment's inertial branch (local_mapper.rs:343-375) on the resident map — collected on the
+// device, solved where the observations lie, the optimised positions written back into the store.  velocities / biases: one per chain
+// entry; edges: (i, j) positions in `chain` with their preintegrations (build_imu_edges, the caller's).  The caller applies the poses
+// (orbx_keyframe_set_pose) and keeps velocities and biases.  nullopt where the reference returns None.
+inline std::optional<MapLocalInertialBAResult> map_local_inertial_ba(Handle& h, const CameraModel& camera, const LocalInertialBAConfig& config, MapPointStore& store,
+                                                                     const std::vector<const orbx_keyframe*>& keyframes, const std::vector<int>& chain,
+                                                                     const std::vector<std::array<double, 3>>& velocities, const std::vector<ImuBias>& biases,
+                                                                     const std::vector<std::array<int, 2>>& edges, const std::vector<PreintegratedState>& preints,
+                                                                     const std::function<bool()>& should_stop) {
+  const size_t K = chain.size();
+  if (velocities.size() != K || biases.size() != K || preints.size() != edges.size()) throw std::invalid_argument("map_local_inertial_ba: inconsistent array lengths");
+  std::vector<double> vel, bias, preint;
+  std::vector<int> ek;
+  for (size_t i = 0; i < K; ++i) {
+    vel.insert(vel.end(), velocities[i].begin(), velocities[i].end());
+    bias.insert(bias.end(), biases[i].gyro.begin(), biases[i].gyro.end());
+    bias.insert(bias.end(), biases[i].accel.begin(), biases[i].accel.end());
+  }
+  for (size_t e = 0; e < edges.size(); ++e) {
+    ek.push_back(edges[e][0]); ek.push_back(edges[e][1]);
+    preint.insert(preint.end(), preints[e].delta_rot.begin(), preints[e].delta_rot.end());
+    preint.insert(preint.end(), preints[e].delta_vel.begin(), preints[e].delta_vel.end());
+    preint.insert(preint.end(), preints[e].delta_pos.begin(), preints[e].delta_pos.end());
+    preint.push_back(preints[e].dt);
+  }
+  std::vector<double> po(std::max<size_t>(K, 1) * 7), vo(std::max<size_t>(K, 1) * 3), bo(std::max<size_t>(K, 1) * 6);
+  MapLocalInertialBAResult r;
+  r.fixed_kf.assign(std::max<size_t>(keyframes.size(), 1), -1);
+  int counts[4] = {0, 0, 0, 0}, it = 0;
+  double e0 = 0, e1 = 0;
+  const orbx_camera c = camera.c();
+  const orbx_inertial_ba_config cfg{config.max_iterations, config.window_size, config.huber_threshold_mono, config.huber_threshold_stereo,
+                                    config.initial_lambda, config.gyro_rw_info, config.accel_rw_info};
+  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
+  const int rc = orbx_map_local_inertial_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), (int)K, chain.data(), vel.data(), bias.data(),
+                                            (int)edges.size(), ek.data(), preint.data(), should_stop ? +tramp : nullptr,
+                                            const_cast<std::function<bool()>*>(&should_stop), po.data(), vo.data(), bo.data(), r.fixed_kf.data(), counts, &it, &e0, &e1);
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  r.K = counts[0]; r.F = counts[1]; r.M = counts[2]; r.N = counts[3];
+  r.fixed_kf.resize((size_t)r.F - 1);
+  for (size_t i = 0; i < K; ++i) {
+    SE3 p;
+    for (int q = 0; q < 4; ++q) p.rotation[q] = po[7 * i + q];
+    for (int q = 0; q < 3; ++q) p.translation[q] = po[7 * i + 4 + q];
+    r.poses_wc.push_back(p);
+    r.velocities.push_back({vo[3 * i], vo[3 * i + 1], vo[3 * i + 2]});
+    ImuBias b;
+    for (int q = 0; q < 3; ++q) { b.gyro[q] = bo[6 * i + q]; b.accel[q] = bo[6 * i + 3 + q]; }
+    r.biases.push_back(b);
+  }
+  r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
+  return r;
+}
+
 // ---- pose-inertial optimization for tracking (src/optimizer/pose_inertial_optim.rs) ----------------------------------
 struct PoseInertialConfig {   // pose_inertial_optim.rs:19-45
   size_t max_iterations = 4;

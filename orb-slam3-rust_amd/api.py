@@ -44,8 +44,12 @@ BA_OBS = np.dtype([("kf_idx", "<i4"), ("fixed_idx", "<i4"), ("mp_idx", "<i4"), (
 BA_OBS32 = np.dtype([("kf_idx", "<i4"), ("mp_idx", "<i4"), ("u", "<f4"), ("v", "<f4")])
 
 
-def ba_obs_to_obs32(obs, n_fixed):
-    """orbx_ba_obs -> orbx_ba_obs32, or None if a coordinate is not exactly an f32 (the reference's always are: kp.pt() widened, local_ba_lm.rs:870-872)."""
+BA_OBS32_STEREO = 0x40000000   # ORBX_BA_OBS32_STEREO: is_stereo in mp_idx, read by the inertial entry points only
+
+
+def ba_obs_to_obs32(obs, n_fixed, inertial=False):
+    """orbx_ba_obs -> orbx_ba_obs32, or None if a coordinate is not exactly an f32 (the reference's always are: kp.pt() widened, local_ba_lm.rs:870-872).
+    inertial=True: `_pad & 1` (is_stereo) is carried into mp_idx as BA_OBS32_STEREO — the form ba_solve_inertial_obs32 takes."""
     obs = np.ascontiguousarray(obs, BA_OBS)
     u32, v32 = obs["u"].astype(np.float32), obs["v"].astype(np.float32)
     if not (np.array_equal(u32.astype(np.float64), obs["u"]) and np.array_equal(v32.astype(np.float64), obs["v"])):
@@ -54,6 +58,10 @@ def ba_obs_to_obs32(obs, n_fixed):
     fixed = np.where(obs["fixed_idx"] >= 0, obs["fixed_idx"], n_fixed)
     out["kf_idx"] = np.where(obs["kf_idx"] >= 0, obs["kf_idx"], -1 - fixed)
     out["mp_idx"] = obs["mp_idx"]; out["u"] = u32; out["v"] = v32
+    if inertial:
+        if len(obs) and (int(obs["mp_idx"].max()) >= BA_OBS32_STEREO):
+            raise ValueError("a point index reaches the stereo flag's bit")
+        out["mp_idx"] = np.where((obs["_pad"] & 1) != 0, obs["mp_idx"] | BA_OBS32_STEREO, obs["mp_idx"])
     return out
 
 
@@ -107,6 +115,8 @@ ABI_SYMBOLS = [
     "orbx_keyframe_get_map_point_slots", "orbx_map_fuse_device", "orbx_map_fuse", "orbx_map_search_in_neighbors",
     "orbx_keyframe_set_map_point_slots_device", "orbx_map_create_points_device", "orbx_map_create_points", "orbx_map_remove_points",
     "orbx_map_cull_points",
+    "orbx_ba_solve_inertial_obs32", "orbx_ba_solve_inertial_obs32_device", "orbx_map_collect_inertial_window_device",
+    "orbx_map_collect_inertial_window", "orbx_map_local_inertial_ba",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS = 1, 2    # orbx_map_create_points' phases (a bit mask)
@@ -1348,6 +1358,88 @@ class Handle:
         K, F, M, N = (int(x) for x in counts)
         return dict(counts=counts, local_kf=lk, fixed_kf=fx[:F - 1].copy(), list_slot=ls[:M].copy(), positions=pos[:M].copy(), obs32=obs[:N].copy())
 
+    # ---- local inertial BA from the resident map (include/orbx.h, "local INERTIAL BA from the resident map") ----
+    @staticmethod
+    def _inertial_window_bounds(mp, keyframes, chain):
+        """(list bound, observation bound): the chain's feature counts summed, at most the capacity; every feature of `keyframes`"""
+        n = len(keyframes)
+        cap = sum(keyframes[i].n for i in chain if 0 <= i < n)
+        return int(min(cap, mp.capacity)), int(sum(k.n for k in keyframes))
+
+    def map_collect_inertial_window_device(self, mp: "MapPointStore", keyframes, chain, device=None):
+        """The inertial local-BA window of the temporal chain `chain` (positions in `keyframes`, oldest first), collected on the
+        device (orbx_map_collect_inertial_window_device).  Returns a dict of CUDA tensors: counts [4] int32 = (K, F, M, N), fixed_kf
+        [n_kfs] int32 (the F-1 other observers, ascending, then -1), list_slot [cap] int32 and positions [cap,3] f64 (rows [0, M)),
+        obs32 [obs_cap,16] u8 (rows [0, N) are BA_OBS32 records whose mp_idx carries BA_OBS32_STEREO).  Asynchronous on the
+        handle's stream.  None where the chain has fewer than two keyframes."""
+        import torch
+        ch = np.ascontiguousarray(chain, np.int32).reshape(-1)
+        cap, ocap = self._inertial_window_bounds(mp, keyframes, ch)
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(counts=mk(4, torch.int32), fixed_kf=mk(max(len(keyframes), 1), torch.int32), list_slot=mk(max(cap, 1), torch.int32),
+                 positions=mk((max(cap, 1), 3), torch.float64), obs32=mk((max(ocap, 1), BA_OBS32.itemsize), torch.uint8))
+        self._after_torch(*o.values())
+        rc = self._L.orbx_map_collect_inertial_window_device(
+            self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(ch)), _vp(ch if len(ch) else np.zeros(1, np.int32)), C.c_int(cap),
+            C.c_int(ocap), _vp(o["counts"]), _vp(o["fixed_kf"]), _vp(o["list_slot"]), _vp(o["positions"]), _vp(o["obs32"]))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        o["fixed_kf"] = o["fixed_kf"][:len(keyframes)]; o["list_slot"] = o["list_slot"][:cap]; o["positions"] = o["positions"][:cap]; o["obs32"] = o["obs32"][:ocap]
+        return o
+
+    def map_collect_inertial_window(self, mp: "MapPointStore", keyframes, chain, empty_info=None):
+        """The host form (orbx_map_collect_inertial_window), synchronous: a dict of numpy arrays cut to their sizes — counts [4],
+        fixed_kf [F-1], list_slot [M], positions [M,3], obs32 [N] BA_OBS32 — or None where the window is empty (the reference's
+        None, local_inertial_ba.rs:940-942, :946-948).  empty_info: a dict that then receives counts and fixed_kf as written."""
+        ch = np.ascontiguousarray(chain, np.int32).reshape(-1)
+        cap, ocap = self._inertial_window_bounds(mp, keyframes, ch)
+        counts = np.zeros(4, np.int32); fx = np.full(max(len(keyframes), 1), -1, np.int32)
+        ls = np.zeros(max(cap, 1), np.int32); pos = np.zeros((max(cap, 1), 3)); obs = np.zeros(max(ocap, 1), BA_OBS32)
+        rc = self._L.orbx_map_collect_inertial_window(
+            self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(len(ch)), _vp(ch if len(ch) else np.zeros(1, np.int32)), C.c_int(cap),
+            C.c_int(ocap), _vp(counts), _vp(fx), _vp(ls), _vp(pos), _vp(obs))
+        if rc == ORBX_ERR_EMPTY:
+            if empty_info is not None:
+                empty_info["counts"] = counts; empty_info["fixed_kf"] = fx[:len(keyframes)]
+            return None
+        self._check(rc)
+        K, F, M, N = (int(x) for x in counts)
+        return dict(counts=counts, fixed_kf=fx[:F - 1].copy(), list_slot=ls[:M].copy(), positions=pos[:M].copy(), obs32=obs[:N].copy())
+
+    def map_local_inertial_ba(self, camera, mp: "MapPointStore", keyframes, chain, velocities, biases, edge_kf, preint,
+                              cfg: "LocalInertialBAConfig" = None, should_stop=None):
+        """Inertial local BA of the temporal chain `chain` (positions in `keyframes`, oldest first) on the resident map
+        (orbx_map_local_inertial_ba): the window is collected on the device, solved with its observations where they lie, and the
+        optimised positions are written back into the store if the solve iterated.  velocities [K,3], biases [K,6], edge_kf [E,2]
+        (positions in `chain`) and preint [E,11] as for ba_solve_inertial.  Returns a dict — poses_wc [K,7], velocities [K,3],
+        biases [K,6] for every keyframe of the chain (apply the poses with KeyFrame.set_pose), fixed_kf [F-1], counts (K, F, M, N),
+        iterations, initial_error, final_error — or None where the reference returns None."""
+        cfg = cfg or LocalInertialBAConfig()
+        ch = np.ascontiguousarray(chain, np.int32).reshape(-1)
+        K = len(ch)
+        vel = np.ascontiguousarray(velocities, np.float64).reshape(-1, 3); bias = np.ascontiguousarray(biases, np.float64).reshape(-1, 6)
+        ek = np.ascontiguousarray(edge_kf, np.int32).reshape(-1, 2); pre = np.ascontiguousarray(preint, np.float64).reshape(-1, 11)
+        if len(vel) != K or len(bias) != K or len(pre) != len(ek):
+            raise ValueError("map_local_inertial_ba: inconsistent array lengths")
+        out_p = np.zeros((max(K, 1), 7)); out_v = np.zeros((max(K, 1), 3)); out_b = np.zeros((max(K, 1), 6))
+        fx = np.full(max(len(keyframes), 1), -1, np.int32); counts = np.zeros(4, np.int32)
+        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
+        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cam = camera._c(); c = cfg._c()
+        pad = lambda a, shape: a if len(a) else np.zeros(shape, a.dtype)
+        rc = self._L.orbx_map_local_inertial_ba(
+            self._h, C.byref(cam), C.byref(c), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(K), _vp(pad(ch, 1)), _vp(pad(vel, (1, 3))),
+            _vp(pad(bias, (1, 6))), C.c_int(len(ek)), _vp(pad(ek, (1, 2))), _vp(pad(pre, (1, 11))), cb, None, _vp(out_p), _vp(out_v), _vp(out_b), _vp(fx),
+            _vp(counts), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        F = int(counts[1])
+        return dict(poses_wc=out_p[:K], velocities=out_v[:K], biases=out_b[:K], fixed_kf=fx[:F - 1].copy(), counts=counts, iterations=it.value,
+                    initial_error=e0.value, final_error=e1.value)
+
     # ---- observations from the resident map (include/orbx.h, "observations from the resident map") ----
     @staticmethod
     def _obs_slots(slots):
@@ -2276,6 +2368,45 @@ class Handle:
         self._check(rc)
         return dict(poses_wc=out_p[:K], velocities=out_v[:K], biases=out_b[:K], points=pts, iterations=it.value,
                     initial_error=e0.value, final_error=e1.value)
+
+    def _ba_solve_inertial_obs32(self, fn, camera, cfg, poses_wc, velocities, biases, fixed_cw, points, obs32, N, edge_kf, preint, should_stop):
+        poses_wc = np.ascontiguousarray(poses_wc, np.float64).reshape(-1, 7)
+        vel = np.ascontiguousarray(velocities, np.float64).reshape(-1, 3); bias = np.ascontiguousarray(biases, np.float64).reshape(-1, 6)
+        fixed_cw = np.ascontiguousarray(fixed_cw, np.float64).reshape(-1, 7)
+        pts = np.array(points, np.float64, copy=True).reshape(-1, 3)
+        ek = np.ascontiguousarray(edge_kf, np.int32).reshape(-1, 2); pre = np.ascontiguousarray(preint, np.float64).reshape(-1, 11)
+        K, F, M, E = len(poses_wc), len(fixed_cw), len(pts), len(ek)
+        if len(vel) != K or len(bias) != K or len(pre) != E:
+            raise ValueError("ba_solve_inertial_obs32: inconsistent array lengths")
+        out_p = np.zeros((max(K, 1), 7)); out_v = np.zeros((max(K, 1), 3)); out_b = np.zeros((max(K, 1), 6))
+        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
+        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cam = camera._c(); c = cfg._c()
+        rc = fn(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_wc), _vp(vel), _vp(bias), C.c_int(F), _vp(fixed_cw), C.c_int(M), _vp(pts), C.c_int(N),
+                _vp(obs32), C.c_int(E), _vp(ek), _vp(pre), cb, None, _vp(out_p), _vp(out_v), _vp(out_b), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc in (ORBX_ERR_EMPTY,):
+            return None                      # reference returns None, local_inertial_ba.rs:1080-1082
+        self._check(rc)
+        return dict(poses_wc=out_p[:K], velocities=out_v[:K], biases=out_b[:K], points=pts, iterations=it.value,
+                    initial_error=e0.value, final_error=e1.value)
+
+    def ba_solve_inertial_obs32(self, camera, cfg, poses_wc, velocities, biases, fixed_cw, points, obs32, edge_kf, preint, should_stop=None):
+        """ba_solve_inertial on the 16-byte observations (orbx_ba_solve_inertial_obs32): obs32 is a BA_OBS32 array whose mp_idx
+        carries is_stereo as BA_OBS32_STEREO (ba_obs_to_obs32(..., inertial=True)).  Bit for bit ba_solve_inertial's result on
+        the widened observations."""
+        obs32 = np.ascontiguousarray(obs32, BA_OBS32)
+        return self._ba_solve_inertial_obs32(self._L.orbx_ba_solve_inertial_obs32, camera, cfg, poses_wc, velocities, biases, fixed_cw, points, obs32, len(obs32),
+                                             edge_kf, preint, should_stop)
+
+    def ba_solve_inertial_obs32_device(self, camera, cfg, poses_wc, velocities, biases, fixed_cw, points, obs32, n_obs, edge_kf, preint, should_stop=None):
+        """... with the observations in device memory (orbx_ba_solve_inertial_obs32_device): obs32 is a CUDA tensor whose first
+        16 * n_obs bytes are BA_OBS32 records (map_collect_inertial_window_device's), 16-byte aligned."""
+        N = int(n_obs)
+        if N < 0 or N * BA_OBS32.itemsize > obs32.numel() * obs32.element_size():
+            raise ValueError("obs32 holds fewer than n_obs records")
+        self._after_torch(obs32)
+        return self._ba_solve_inertial_obs32(self._L.orbx_ba_solve_inertial_obs32_device, camera, cfg, poses_wc, velocities, biases, fixed_cw, points, obs32, N,
+                                             edge_kf, preint, should_stop)
 
     def ba_solve_global(self, camera, cfg, poses_cw, fixed_pose_cw, points, obs, should_stop=None):
         """solve_global_ba (global_ba.rs:184-418): every keyframe but the first is optimised."""

@@ -112,7 +112,8 @@ struct BaWin {
   double *res;           // [16] result block, see ba_decide_kernel
   // the observation CSR is built on the device once per call (ba_prep_*_kernel) from the caller's observations as they were handed over
   const orbx_ba_obs* obs_raw;   // [N], input order (obs32 == 0), or
-  int obs32;             // ... the same array in the 16-byte form orbx_ba_obs32 (kf_idx < 0: fixed observer -1 - kf_idx; u, v as f32)
+  int obs32;             // ... the same array in the 16-byte form orbx_ba_obs32 (kf_idx < 0: fixed observer -1 - kf_idx; u, v as f32);
+                         // 2: an inertial window's, mp_idx carrying ORBX_BA_OBS32_STEREO — read by the <true> forms of the prep kernels only
   int pad_;
   int *pt_fill;          // [M] per-point counters: observations of the point (count pass), then its fill position (place pass)
   int *obs_tmp;          // [N] observation indices grouped by map point, in arrival order within a point (sorted by ba_prep_order_kernel)
@@ -240,15 +241,21 @@ __global__ void ba_iter_kernel(const BaWin* __restrict__ wins, int iter) {
 //   place: observation index -> its point's segment of obs_tmp
 //   order: per point, sort the segment; gather the observations into o_kf / o_uv / o_flag
 constexpr int BA_PREP_OPB = 1024;   // observations per block of the count / place passes (256 threads x 4)
-// (kf_idx, fixed_idx, mp_idx, _pad) of observation i in either wire format; the 16-byte form carries the fixed observer in kf_idx
+// (kf_idx, fixed_idx, mp_idx, _pad) of observation i in either wire format; the 16-byte form carries the fixed observer in kf_idx.
+// FLAG32: the launches of an inertial window in the 16-byte form (BaWin::obs32 == 2), whose mp_idx carries is_stereo in
+// ORBX_BA_OBS32_STEREO: _pad = that bit, mp_idx = the rest (a negative mp_idx stays negative).  The visual launches are the <false>
+// instantiation: their code does not know the bit, and an index that has it set is out of range there.
+template <bool FLAG32>
 __device__ __forceinline__ int4 ba_obs_ids(const BaWin& win, int i) {
   if (win.obs32) {
     const int2 q = *reinterpret_cast<const int2*>(reinterpret_cast<const orbx_ba_obs32*>(win.obs_raw) + i);
     const int f = -1 - q.x;                                                // fixed observer f; f == F: the identity pose (= fixed_idx -1 of orbx_ba_obs)
+    if (FLAG32) return make_int4(q.x >= 0 ? q.x : -1, (q.x >= 0 || f == win.d.F) ? -1 : f, q.y & ~ORBX_BA_OBS32_STEREO, (q.y & ORBX_BA_OBS32_STEREO) ? 1 : 0);
     return make_int4(q.x >= 0 ? q.x : -1, (q.x >= 0 || f == win.d.F) ? -1 : f, q.y, 0);
   }
   return *reinterpret_cast<const int4*>(&win.obs_raw[i]);
 }
+template <bool FLAG32>
 __global__ __launch_bounds__(256) void ba_prep_count_kernel(const BaWin* __restrict__ wins) {
   __shared__ int s_kf[BA_MAX_K];
   const BaWin win = ba_win_global(wins, blockIdx.y);
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(256) void ba_prep_count_kernel(const BaWin* __restr
   for (int r = 0; r < BA_PREP_OPB / 256; ++r) {
     const int i = i0 + r * 256 + tid;
     if (i >= N) break;
-    const int4 q = ba_obs_ids(win, i);                                    // kf_idx, fixed_idx, mp_idx, _pad
+    const int4 q = ba_obs_ids<FLAG32>(win, i);                            // kf_idx, fixed_idx, mp_idx, _pad
     if (q.z < 0 || q.z >= M || q.x >= K || (q.x < 0 && q.y >= F)) { atomicMax(&win.S->bad, 0x7fffffff - i); continue; }
     atomicAdd(&pt_fill[q.z], 1);
     if (q.x >= 0) atomicAdd(&s_kf[q.x], 1);
@@ -309,6 +316,7 @@ __global__ __launch_bounds__(1024) void ba_prep_scan_kernel(const BaWin* __restr
   }
 }
 
+template <bool FLAG32>
 __global__ __launch_bounds__(256) void ba_prep_place_kernel(const BaWin* __restrict__ wins) {
   const BaWin win = ba_win_global(wins, blockIdx.y);
   const int N = win.d.N;
@@ -319,13 +327,15 @@ __global__ __launch_bounds__(256) void ba_prep_place_kernel(const BaWin* __restr
   for (int r = 0; r < BA_PREP_OPB / 256; ++r) {
     const int i = i0 + r * 256 + threadIdx.x;
     if (i >= N) break;
-    const int mp = win.obs32 ? reinterpret_cast<const orbx_ba_obs32*>(win.obs_raw)[i].mp_idx : win.obs_raw[i].mp_idx;
+    int mp = win.obs32 ? reinterpret_cast<const orbx_ba_obs32*>(win.obs_raw)[i].mp_idx : win.obs_raw[i].mp_idx;
+    if (FLAG32 && win.obs32) mp &= ~ORBX_BA_OBS32_STEREO;
     win.obs_tmp[pt_start[mp] + atomicAdd(&win.pt_fill[mp], 1)] = i;
   }
 }
 
 // 16 lanes per map point: the point's observation indices into ascending (= input) order by counting, for each, the smaller ones
 // (a track is ~16 observations; a long one costs its square over 16 lanes), then the observations themselves into that order.
+template <bool FLAG32>
 __global__ __launch_bounds__(256) void ba_prep_order_kernel(const BaWin* __restrict__ wins) {
   const BaWin win = ba_win_global(wins, blockIdx.y);
   const int F = win.d.F, M = win.d.M;
@@ -341,7 +351,7 @@ __global__ __launch_bounds__(256) void ba_prep_order_kernel(const BaWin* __restr
     const int idx = tmp[e];
     int rank = 0;
     for (int k = 0; k < n; ++k) rank += tmp[k] < idx ? 1 : 0;
-    const int4 q = ba_obs_ids(win, idx);
+    const int4 q = ba_obs_ids<FLAG32>(win, idx);
     double2_t uv;
     if (win.obs32) {                                                       // f32 -> f64: exact, what the host's `as f64` (local_ba_lm.rs:870-872) does
       const float2 f = *reinterpret_cast<const float2*>(&reinterpret_cast<const orbx_ba_obs32*>(win.obs_raw)[idx].u);
@@ -1334,6 +1344,7 @@ __global__ __launch_bounds__(256) void ba_gather_kernel(const BaWin* __restrict_
 #endif
 constexpr int BA_SOLVE_THREADS = ORBX_BA_SOLVE_THREADS;   // 256 / 512 / 1024 threads: 43.9 / 36.7 / 35.2 us per solve at n = 114 (end of round 3)
 constexpr int BA_MAX_N = 768;
+static_assert(BA_MAX_N / 15 == BA_INERTIAL_MAX_K, "orbx_internal.hpp states the inertial window's limit");
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -3751,7 +3762,7 @@ void ba_bind_window(const BaCtx& c, int w, BaWin& b) {
   b.pt_start = (const int*)(dar + pl.a_ptstart); b.o_kf = (const int*)(dar + pl.a_okf);
   b.o_uv = (const double*)(dar + pl.a_ouv);
   b.kf_start = (const int*)(dcnt + pl.c_kfstart); b.kf_obs = (int*)(dar + pl.a_kfobs); b.kf_pt = (int*)(dar + pl.a_kfpt);
-  b.obs_raw = (const orbx_ba_obs*)(c.dobs + pl.i_obs); b.obs32 = c.win[w].obs32 ? 1 : 0; b.pt_fill = (int*)(dcnt + pl.c_fill); b.obs_tmp = (int*)(dar + pl.a_tmp);
+  b.obs_raw = (const orbx_ba_obs*)(c.dobs + pl.i_obs); b.obs32 = c.win[w].obs32 ? (c.inertial ? 2 : 1) : 0; b.pt_fill = (int*)(dcnt + pl.c_fill); b.obs_tmp = (int*)(dar + pl.a_tmp);
   b.o_flag = c.inertial ? (int*)(dar + pl.a_oflag) : nullptr;
   b.Mz = (double*)(dar + pl.a_mz);
   b.Vinv = (double*)(dar + pl.a_vinv); b.gl = (double*)(dar + pl.a_gl); b.vg = (double*)(dar + pl.a_vg);
@@ -3861,10 +3872,18 @@ int ba_enqueue_csr(BaCtx& c) {
   if (c.maxN > 0) {
     ProfScope ps(c.h, "ba_prep");
     const dim3 go((c.maxN + BA_PREP_OPB - 1) / BA_PREP_OPB, c.W);
-    hipLaunchKernelGGL(ba_prep_count_kernel, go, dim3(256), 0, c.st, c.d_wins);
-    hipLaunchKernelGGL(ba_prep_scan_kernel, dim3(1, c.W), dim3(1024), 0, c.st, c.d_wins);
-    hipLaunchKernelGGL(ba_prep_place_kernel, go, dim3(256), 0, c.st, c.d_wins);
-    if (c.s.maxM > 0) hipLaunchKernelGGL(ba_prep_order_kernel, dim3((c.s.maxM * 16 + 255) / 256, c.W), dim3(256), 0, c.st, c.d_wins);
+    const dim3 gm((c.s.maxM * 16 + 255) / 256, c.W);
+    if (c.inertial && c.win[0].obs32) {                                    // one inertial window in the 16-byte form: mp_idx carries the stereo flag
+      hipLaunchKernelGGL(ba_prep_count_kernel<true>, go, dim3(256), 0, c.st, c.d_wins);
+      hipLaunchKernelGGL(ba_prep_scan_kernel, dim3(1, c.W), dim3(1024), 0, c.st, c.d_wins);
+      hipLaunchKernelGGL(ba_prep_place_kernel<true>, go, dim3(256), 0, c.st, c.d_wins);
+      if (c.s.maxM > 0) hipLaunchKernelGGL(ba_prep_order_kernel<true>, gm, dim3(256), 0, c.st, c.d_wins);
+    } else {
+      hipLaunchKernelGGL(ba_prep_count_kernel<false>, go, dim3(256), 0, c.st, c.d_wins);
+      hipLaunchKernelGGL(ba_prep_scan_kernel, dim3(1, c.W), dim3(1024), 0, c.st, c.d_wins);
+      hipLaunchKernelGGL(ba_prep_place_kernel<false>, go, dim3(256), 0, c.st, c.d_wins);
+      if (c.s.maxM > 0) hipLaunchKernelGGL(ba_prep_order_kernel<false>, gm, dim3(256), 0, c.st, c.d_wins);
+    }
   }
   return ORBX_OK;
 }
@@ -4069,7 +4088,10 @@ int ba_report_bad_index(BaCtx& c) {
     if (ww.obs_on_device)                                                  // (the observation is not the host's to read)
       return orbx_fail(c.h, ORBX_ERR_INVALID, "window %d observation %d (device memory): index out of range (K %d, F %d, M %d)", w, i, ww.K, ww.F, ww.M);
     int kf, fx, mp;
-    if (ww.obs32) { const orbx_ba_obs32& o = ww.obs32[i]; kf = o.kf_idx >= 0 ? o.kf_idx : -1; fx = o.kf_idx >= 0 ? -1 : -1 - o.kf_idx; mp = o.mp_idx; }
+    if (ww.obs32) {
+      const orbx_ba_obs32& o = ww.obs32[i];
+      kf = o.kf_idx >= 0 ? o.kf_idx : -1; fx = o.kf_idx >= 0 ? -1 : -1 - o.kf_idx; mp = c.inertial ? o.mp_idx & ~ORBX_BA_OBS32_STEREO : o.mp_idx;
+    }
     else { const orbx_ba_obs& o = ww.obs[i]; kf = o.kf_idx; fx = o.fixed_idx; mp = o.mp_idx; }
     return orbx_fail(c.h, ORBX_ERR_INVALID, "window %d observation %d: index out of range (kf %d/%d, fixed %d/%d, mp %d/%d)", w, i, kf,
                      ww.K, fx, ww.F, mp, ww.M);
@@ -4156,8 +4178,10 @@ int ba_solve_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config*
   // observations in device memory: the partitioned solve's hosts pass over their partition, and a batch's halves order their uploads on
   // two streams — neither is for memory another stream may still be writing
   for (int w = 0; w < W; ++w)
-    if (win[w].obs_on_device && (have_coll || W != 1 || inertial))
-      return orbx_fail(h, ORBX_ERR_INVALID, "observations in device memory: one visual window, without an all-reduce hook or communicator");
+    if (win[w].obs_on_device && (have_coll || W != 1))
+      return orbx_fail(h, ORBX_ERR_INVALID, "observations in device memory: one window, without an all-reduce hook or communicator");
+  if (inertial && win[0].obs32 && win[0].M >= ORBX_BA_OBS32_STEREO)
+    return orbx_fail(h, ORBX_ERR_INVALID, "inertial observations in the 16-byte form: M = %d reaches the stereo flag's bit (0x40000000)", win[0].M);
   for (int w = 0; w < W; ++w) { *win[w].iterations = 0; *win[w].initial_error = 0.0; *win[w].final_error = 0.0; win[w].status = ORBX_OK; }
   // ORBX_BA_TIMING=1: host-side phase times of this call on stderr (plan, preprocessing, descriptors + upload enqueue, launch
   // enqueue, drain, unpack)

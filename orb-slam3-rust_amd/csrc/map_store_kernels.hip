@@ -42,6 +42,10 @@
 //   bac_restore_kernel  index[slot] = EMPTY again: the call leaves the table as it found it
 // orbx_map_local_ba hands the observations to the solver where they lie (ba_kernels.hip: BaWinHost::obs_on_device) and scatters the
 // optimised positions back through map_scatter_kernel.
+// The INERTIAL window (local_inertial_ba.rs:366-429, :933-1030; local_mapper.rs:343-375) is one frame's selection over the temporal
+// chain the caller names and the same five launches: bac_order_kernel<true> takes the roles from the chain (chain[0] the anchor,
+// chain[i] window keyframe i), bac_emit_kernel<true> ORs has_point[feature] != 0 into mp_idx (ORBX_BA_OBS32_STEREO).
+// orbx_map_local_inertial_ba hands them to the inertial solver where they lie and scatters the positions back the same way.
 // mp.observations (map_point.rs:140-156), the inverse of the slot tables, is derived the same way for the points a call names:
 // the lists behind orbx_map_observations and orbx_map_refresh_points (search_in_neighbors.rs:139-150) and the counts behind
 // orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
@@ -352,6 +356,7 @@ constexpr int BAC_NONE = 0x7fffffff;             // role of a keyframe that obse
 struct BacKf {
   const int* slots; const orbx_keypoint* kp;
   int n, pad_;
+  const uint8_t* has_point;                      // [n] the keyframe's stereo bytes (the inertial window's emit only)
 };
 struct BacArgs {
   int capacity, n_kfs, n_chunk, n_local;         // n_local = 1 + max_covisible: entries of local_kf
@@ -360,7 +365,7 @@ struct BacArgs {
   int* index;                                    // the store's first-sighting table, row 0: EMPTY outside the launches below
   int* chunk_count;                              // [n_kfs][n_chunk]
   int* kf_count; int* role; int* obs_base;       // [n_kfs]: c(k); the kf_idx its observations carry (BAC_NONE: none); where they start
-  const int* local_kf;                           // [n_local], -1 padded (cov_seg_kernel)
+  const int* local_kf;                           // [n_local], -1 padded (cov_seg_kernel); the inertial window: chain [n_local], oldest first
   int* counts; int* fixed_kf; orbx_ba_obs32* obs;
 };
 
@@ -399,6 +404,9 @@ __global__ __launch_bounds__(MS_THREADS) void bac_count_kernel(BacArgs A) {
 }
 
 // One workgroup: every keyframe's role, the fixed keyframes by position, where every observer's observations start, the counts.
+// CHAIN: the inertial window (local_inertial_ba.rs:930-1030).  local_kf is the temporal chain, every entry a keyframe: chain[0] the
+// anchor (-1), chain[i] window keyframe i — the anchor keeps window index 0, which no observation carries — and K counts all of them.
+template <bool CHAIN>
 __global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
   __shared__ int lds[MS_THREADS / 64];
   const int tid = threadIdx.x, n = A.n_kfs;
@@ -411,7 +419,7 @@ __global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
   int n_loc = 0;                                                           // local_kf's entries before the padding: each names another keyframe
   for (int j = tid; j < A.n_local; j += MS_THREADS) {
     const int k = A.local_kf[j];
-    if (k >= 0) { A.role[k] = j - 1; ++n_loc; }                           // anchor -1, optimised keyframe i: i - 1
+    if (k >= 0) { A.role[k] = CHAIN && j > 0 ? j : j - 1; ++n_loc; }      // anchor -1, optimised keyframe i: i - 1 (chain[i]: i)
   }
   n_loc = block_sum<MS_THREADS>(n_loc, lds);                               // (its barriers order the roles before the reads below)
   BlockAppend<MS_THREADS, 1> fixed(lds);
@@ -431,10 +439,14 @@ __global__ __launch_bounds__(MS_THREADS) void bac_order_kernel(BacArgs A) {
     const int at = start.round(k >= 0 ? A.kf_count[k] : 0);
     if (k >= 0) A.obs_base[k] = at;
   }
-  if (tid == 0) { A.counts[0] = n_loc - 1; A.counts[1] = 1 + n_fixed; A.counts[2] = A.list_off[1]; A.counts[3] = start.total; }
+  if (tid == 0) { A.counts[0] = CHAIN ? n_loc : n_loc - 1; A.counts[1] = 1 + n_fixed; A.counts[2] = A.list_off[1]; A.counts[3] = start.total; }
 }
 
 // (chunk, keyframe): ordered compaction of the chunk's counted features behind the observer's earlier chunks
+// STEREO: the inertial window: mp_idx carries has_point[feature] != 0 in ORBX_BA_OBS32_STEREO.  A thread's MS_PER features are four
+// consecutive bytes at a multiple of four: ONE dword load beside the 28-byte rows, not four byte gathers (the array is a 256-byte
+// aligned part of the keyframe's block, padded to a multiple of 256: the dword that holds feature n - 1 lies inside it).
+template <bool STEREO>
 __global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
   __shared__ int wave_tot[MS_THREADS / 64];
   const int k = blockIdx.y, tid = threadIdx.x;
@@ -447,6 +459,8 @@ __global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
   int mp[MS_PER], n = 0;
 #pragma unroll
   for (int j = 0; j < MS_PER; ++j) { mp[j] = bac_mp_idx(A, kf, p0 + j); n += mp[j] >= 0; }
+  static_assert(MS_PER == 4, "a thread's stereo bytes are one dword");
+  const unsigned has = STEREO && n > 0 ? *(const unsigned*)(kf.has_point + p0) : 0u;   // (n > 0: p0 < kf.n)
   // Not BlockScan: its barrier in front of the store, which this single use of wave_tot does not need, measured 0.02 to 0.17 us of
   // 7 to 9 us in every row (profiles/block_scan_ab.txt).  The parent's text, with the shared wave step.
   const int lane = tid & 63, wave = tid >> 6;
@@ -460,7 +474,7 @@ __global__ __launch_bounds__(MS_THREADS) void bac_emit_kernel(BacArgs A) {
     if (mp[j] < 0) continue;
     const float* xy = (const float*)(kf.kp + (p0 + j));                    // 28-byte rows: two dword loads
     int4 v;
-    v.x = role; v.y = mp[j]; v.z = __float_as_int(xy[0]); v.w = __float_as_int(xy[1]);
+    v.x = role; v.y = STEREO && ((has >> (8 * j)) & 0xffu) ? mp[j] | ORBX_BA_OBS32_STEREO : mp[j]; v.z = __float_as_int(xy[0]); v.w = __float_as_int(xy[1]);
     *(int4*)(A.obs + o) = v;
     ++o;
   }
@@ -844,7 +858,7 @@ int bac_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_k
   long long total = 0;
   for (int t = 0; t < n_kfs; ++t) {
     const orbx_keyframe* kf = kfs[t];
-    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0};
+    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0, nullptr};
     total += kf->n; P.max_n = std::max(P.max_n, kf->n);
   }
   if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
@@ -892,11 +906,106 @@ int bac_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BacP
   }
   {
     ProfScope ps(h, "bac_order_kernel", true);
-    hipLaunchKernelGGL(bac_order_kernel, dim3(1), block, 0, h->stream, A);
+    hipLaunchKernelGGL(bac_order_kernel<false>, dim3(1), block, 0, h->stream, A);
   }
   {
     ProfScope ps(h, "bac_emit_kernel", true);
-    hipLaunchKernelGGL(bac_emit_kernel, kf_grid, block, 0, h->stream, A);
+    hipLaunchKernelGGL(bac_emit_kernel<false>, kf_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_restore_kernel", true);
+    hipLaunchKernelGGL(bac_restore_kernel, list_grid, block, 0, h->stream, A);
+  }
+  ORBX_HIP(h, hipGetLastError());
+  return ORBX_OK;
+}
+
+// ---- local inertial BA window, host side (include/orbx.h; local_inertial_ba.rs:366-421, :930-1030) -------------------------------
+
+// An inertial collection call, checked and sized on the host: the chain's selection as one frame of ORBX_MAP_SOURCE_KEYFRAMES, the
+// keyframes' tables with keypoints and stereo bytes, the bound of the observations.
+struct BicPlan {
+  SelPlan S;
+  std::vector<BacKf> kfs;
+  std::vector<int> chain;
+  int n_feat = 0, max_n = 0;
+};
+
+int bic_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain, BicPlan& P) {
+  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (n_kfs < 0 || (n_kfs > 0 && !kfs) || n_chain < 0 || (n_chain > 0 && !chain)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+  std::vector<uint8_t> in_chain((size_t)n_kfs, 0);
+  for (int i = 0; i < n_chain; ++i) {
+    if (chain[i] < 0 || chain[i] >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: chain[%d] = %d is outside [0, n_kfs = %d)", who, i, chain[i], n_kfs);
+    if (in_chain[(size_t)chain[i]]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: chain[%d] = %d is listed twice", who, i, chain[i]);
+    in_chain[(size_t)chain[i]] = 1;
+  }
+  P.kfs.resize((size_t)n_kfs);
+  long long total = 0;
+  for (int t = 0; t < n_kfs; ++t) {
+    const orbx_keyframe* kf = kfs[t];
+    if (int rc = ms_check_keyframe(h, who, mp, kf, t)) return rc;
+    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0, kf->d_has_point};
+    total += kf->n; P.max_n = std::max(P.max_n, kf->n);
+  }
+  if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+  P.n_feat = (int)total;
+  if (n_chain < 2) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the temporal window needs two keyframes", who);   // local_inertial_ba.rs:940-942
+  P.chain.assign(chain, chain + n_chain);
+  std::vector<const orbx_keyframe*> ck((size_t)n_chain);
+  for (int i = 0; i < n_chain; ++i) ck[(size_t)i] = kfs[chain[i]];
+  const int off[2] = {0, n_chain};
+  return ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ck.data(), off, nullptr, P.S);
+}
+
+// Everything on the handle's stream: the chain's selection, then index, count, order (chain roles), emit (stereo bit), restore.
+int bic_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BicPlan& P, int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf,
+                int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  const int bound = P.S.bound_off[1], n_kfs = (int)P.kfs.size(), n_chain = (int)P.chain.size();
+  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the chain's features summed, at most the capacity)", who,
+                                         list_cap, bound);
+  if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
+  if (!d_counts || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_obs32 is 16-byte aligned)", who);
+  ORBX_HIP(h, hipSetDevice(h->device));
+  const size_t K = (size_t)n_kfs;
+  const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK);
+  Carve ws, up;
+  const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
+               o_ob = ws.take(4 * K);
+  const size_t u_kf = up.take(sizeof(BacKf) * K), u_ch = up.take(4 * (size_t)n_chain);
+  if (int rc = orbx_reserve(h, h->ws_map[6], ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map[6].p;
+  uint8_t *hs, *ds;
+  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[7], up.off, &hs, &ds)) return rc;
+  std::memcpy(hs + u_kf, P.kfs.data(), sizeof(BacKf) * K);
+  std::memcpy(hs + u_ch, P.chain.data(), 4 * (size_t)n_chain);
+  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[7], up.off)) return rc;
+  // P: one frame's selection from the chain's tables, in chain order (the descriptors it gathers stay in the workspace)
+  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)) return rc;
+  BacArgs A{};
+  A.capacity = mp->capacity; A.n_kfs = n_kfs; A.n_chunk = n_chunk; A.n_local = n_chain;
+  A.live = mp->d_live; A.kfs = (const BacKf*)(ds + u_kf); A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot;
+  A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
+  A.chunk_count = (int*)(w + o_cc); A.kf_count = (int*)(w + o_kc); A.role = (int*)(w + o_ro); A.obs_base = (int*)(w + o_ob);
+  A.local_kf = (const int*)(ds + u_ch); A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
+  const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
+  {
+    ProfScope ps(h, "bac_index_kernel", true);
+    hipLaunchKernelGGL(bac_index_kernel, list_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_count_kernel", true);
+    hipLaunchKernelGGL(bac_count_kernel, kf_grid, block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_order_kernel", true);
+    hipLaunchKernelGGL(bac_order_kernel<true>, dim3(1), block, 0, h->stream, A);
+  }
+  {
+    ProfScope ps(h, "bac_emit_kernel", true);
+    hipLaunchKernelGGL(bac_emit_kernel<true>, kf_grid, block, 0, h->stream, A);
   }
   {
     ProfScope ps(h, "bac_restore_kernel", true);
@@ -2567,6 +2676,125 @@ int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_conf
                                  initial_error, final_error, false, nullptr, (const orbx_ba_obs32*)(d + o_ob), true))
       return rc;
     // phase 3, the point half of apply_visual_ba_results (:1125-1135; local_mapper.rs:396: only a solve that iterated is applied)
+    if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
+    return ORBX_OK;
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
+  } catch (...) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
+  }
+}
+
+int orbx_map_collect_inertial_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain,
+                                            int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  static const char* who = "orbx_map_collect_inertial_window_device";
+  if (!h) return ORBX_ERR_INVALID;
+  try {
+    BicPlan P;
+    if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
+    return bic_enqueue(h, who, mp, P, list_cap, obs_cap, d_counts, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
+  }
+}
+
+int orbx_map_collect_inertial_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain,
+                                     int list_cap, int obs_cap, int* counts, int* fixed_kf, int* list_slot, double* positions, orbx_ba_obs32* obs32) {
+  static const char* who = "orbx_map_collect_inertial_window";
+  if (!h) return ORBX_ERR_INVALID;
+  try {
+    BicPlan P;
+    if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
+    const size_t bound = (size_t)P.S.bound_off[1], nf = (size_t)P.n_feat, K = (size_t)n_kfs;
+    if (list_cap < (int)bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, (int)bound, P.n_feat);
+    if (!counts || !fixed_kf || (bound > 0 && (!list_slot || !positions)) || (nf > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // the sizes first (counts, fixed keyframes), then as many rows as they say: two downloads, nothing sized by a bound
+    Carve out;
+    const size_t o_cn = out.take(16), o_fx = out.take(4 * K);
+    const size_t head = out.off;
+    const size_t o_ls = out.take(4 * bound), o_po = out.take(24 * bound), o_ob = out.take(16 * nf);
+    if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, head)) return rc;
+    uint8_t* d = (uint8_t*)h->ws_map[1].p;
+    if (int rc = bic_enqueue(h, who, mp, P, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_fx), (int*)(d + o_ls), (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
+      return rc;
+    uint8_t* hp = (uint8_t*)h->pin_map.p;
+    ORBX_HIP(h, hipMemcpyAsync(hp, d, head, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(counts, hp + o_cn, 16); std::memcpy(fixed_kf, hp + o_fx, 4 * K);
+    const size_t M = (size_t)counts[2], N = (size_t)counts[3];
+    if (M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);   // local_inertial_ba.rs:946-948
+    Carve rows;
+    const size_t r_ls = rows.take(4 * M), r_po = rows.take(24 * M), r_ob = rows.take(16 * N);
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, rows.off)) return rc;
+    hp = (uint8_t*)h->pin_map.p;
+    ORBX_HIP(h, hipMemcpyAsync(hp + r_ls, d + o_ls, 4 * M, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(hp + r_po, d + o_po, 24 * M, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(hp + r_ob, d + o_ob, 16 * N, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(list_slot, hp + r_ls, 4 * M); std::memcpy(positions, hp + r_po, 24 * M); std::memcpy(obs32, hp + r_ob, 16 * N);
+    return ORBX_OK;
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
+  }
+}
+
+int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, orbx_map_points* mp, int n_kfs,
+                               const orbx_keyframe* const* kfs, int n_chain, const int* chain, const double* velocities, const double* biases, int E,
+                               const int* edge_kf, const double* preint, orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out,
+                               double* bias_out, int* fixed_kf_out, int* counts_out, int* iterations, double* initial_error, double* final_error) {
+  static const char* who = "orbx_map_local_inertial_ba";
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || !fixed_kf_out || !counts_out || !iterations || !initial_error || !final_error || E < 0 || (E > 0 && (!edge_kf || !preint)) ||
+      (n_chain > 0 && (!velocities || !biases || !poses_wc_out || !vel_out || !bias_out)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the inertial solve is not partitioned: no all-reduce hook or communicator", who);
+  try {
+    BicPlan P;
+    if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
+    // the solver's own refusals, made before the collection is enqueued (ba_check_inertial repeats them)
+    if (n_chain > BA_INERTIAL_MAX_K) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most %d keyframes per inertial window", who, BA_INERTIAL_MAX_K);
+    for (int e = 0; e < E; ++e) {
+      const int i = edge_kf[2 * e], j = edge_kf[2 * e + 1];
+      if (i < 0 || i >= n_chain || j < 0 || j >= n_chain) return orbx_fail(h, ORBX_ERR_INVALID, "%s: IMU edge %d: keyframe index out of range", who, e);
+      if (i == j) return orbx_fail(h, ORBX_ERR_INVALID, "%s: IMU edge %d: both ends are keyframe %d", who, e, i);
+    }
+    *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+    const size_t bound = (size_t)P.S.bound_off[1], nf = (size_t)P.n_feat, K = (size_t)n_kfs;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // phase 1 (collect_inertial_ba_data, :930-1030) on the device; ONE download: counts | fixed | P's slots | P's positions
+    Carve out;
+    const size_t o_cn = out.take(16), o_fx = out.take(4 * K), o_ls = out.take(4 * bound), o_po = out.take(24 * bound);
+    const size_t down = out.off;
+    const size_t o_ob = out.take(16 * nf);
+    if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
+    uint8_t* d = (uint8_t*)h->ws_map[1].p;
+    orbx_prof_begin_call(h);
+    if (int rc = bic_enqueue(h, who, mp, P, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_fx), (int*)(d + o_ls), (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
+      return rc;
+    uint8_t* hp = (uint8_t*)h->pin_map.p;
+    ORBX_HIP(h, hipMemcpyAsync(hp, d, down, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    const int* cn = (const int*)(hp + o_cn);
+    const int* fx = (const int*)(hp + o_fx);
+    const int Kw = cn[0], F = cn[1], M = cn[2], N = cn[3];
+    std::memcpy(counts_out, cn, 16); std::memcpy(fixed_kf_out, fx, 4 * K);
+    if (M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);   // :946-948
+    // T_wc of the chain as it is; T_cw of the anchor and the other fixed observers (:973-978)
+    std::vector<double> poses_wc(7 * (size_t)Kw), fixed_cw(7 * (size_t)F), points((const double*)(hp + o_po), (const double*)(hp + o_po) + 3 * (size_t)M);
+    std::vector<int> slots((const int*)(hp + o_ls), (const int*)(hp + o_ls) + M);
+    for (int i = 0; i < Kw; ++i) std::memcpy(&poses_wc[7 * (size_t)i], kfs[chain[i]]->pose_wc, 56);
+    bac_pose_inverse(kfs[chain[0]]->pose_wc, &fixed_cw[0]);
+    for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
+    // phase 2 (solve_inertial_ba, :1074-1275) on the observations where they lie
+    orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
+    BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
+    if (int rc = ba_solve_visual(h, cam, &vc, Kw, poses_wc.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
+                                 initial_error, final_error, false, &in, (const orbx_ba_obs32*)(d + o_ob), true))
+      return rc;
+    // phase 3, the point half of apply_inertial_ba_results (local_mapper.rs:363: only a solve that iterated is applied)
     if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
     return ORBX_OK;
   } catch (const std::bad_alloc&) {

@@ -1236,6 +1236,53 @@ int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_in
   }
 }
 
+// the two 16-byte forms of orbx_ba_solve_inertial: mp_idx carries is_stereo (ORBX_BA_OBS32_STEREO), decoded by the prep launches
+static int ba_solve_inertial_obs32(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K, const double* poses_wc,
+                                   const double* velocities, const double* biases, int F, const double* fixed_poses_cw, int M, double* points, int N,
+                                   const orbx_ba_obs32* obs32, bool on_device, int E, const int* edge_kf, const double* preint,
+                                   orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out, double* bias_out, int* iterations,
+                                   double* initial_error, double* final_error) {
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || K < 0 || F < 0 || M < 0 || N < 0 || E < 0 || !iterations || !initial_error || !final_error ||
+      (K > 0 && (!poses_wc || !velocities || !biases || !poses_wc_out || !vel_out || !bias_out)) || (F > 0 && !fixed_poses_cw) ||
+      (M > 0 && !points) || (N > 0 && !obs32) || (E > 0 && (!edge_kf || !preint)) || (on_device && ((uintptr_t)obs32 & 15)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument%s", who, on_device ? " (d_obs32 is 16-byte aligned)" : "");
+  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the inertial solve is not partitioned: no all-reduce hook or communicator", who);
+  if (M >= ORBX_BA_OBS32_STEREO) return orbx_fail(h, ORBX_ERR_INVALID, "%s: M = %d reaches the stereo flag's bit (0x40000000)", who, M);
+  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+  if (K < 2) return orbx_fail(h, ORBX_ERR_EMPTY, "inertial BA needs two keyframes in the window");   // local_inertial_ba.rs:1080-1082
+  ORBX_HIP(h, hipSetDevice(h->device));
+  orbx_prof_begin_call(h);
+  orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
+  BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
+  try {
+    return ba_solve_visual(h, cam, &vc, K, poses_wc, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations,
+                           initial_error, final_error, false, &in, obs32, on_device);
+  } catch (const std::bad_alloc&) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
+  } catch (...) {
+    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
+  }
+}
+
+int orbx_ba_solve_inertial_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K, const double* poses_wc,
+                                 const double* velocities, const double* biases, int F, const double* fixed_poses_cw, int M, double* points,
+                                 int N, const orbx_ba_obs32* obs32, int E, const int* edge_kf, const double* preint,
+                                 orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out, double* bias_out,
+                                 int* iterations, double* initial_error, double* final_error) {
+  return ba_solve_inertial_obs32(h, "orbx_ba_solve_inertial_obs32", cam, cfg, K, poses_wc, velocities, biases, F, fixed_poses_cw, M, points, N, obs32, false, E,
+                                 edge_kf, preint, should_stop, user, poses_wc_out, vel_out, bias_out, iterations, initial_error, final_error);
+}
+
+int orbx_ba_solve_inertial_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K, const double* poses_wc,
+                                        const double* velocities, const double* biases, int F, const double* fixed_poses_cw, int M, double* points,
+                                        int N, const orbx_ba_obs32* d_obs32, int E, const int* edge_kf, const double* preint,
+                                        orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out, double* bias_out,
+                                        int* iterations, double* initial_error, double* final_error) {
+  return ba_solve_inertial_obs32(h, "orbx_ba_solve_inertial_obs32_device", cam, cfg, K, poses_wc, velocities, biases, F, fixed_poses_cw, M, points, N, d_obs32,
+                                 true, E, edge_kf, preint, should_stop, user, poses_wc_out, vel_out, bias_out, iterations, initial_error, final_error);
+}
+
 int orbx_ba_solve_global(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
                          const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs* obs,
                          orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations,

@@ -557,3 +557,4 @@ struct BaInertialHost {
   double* vel_out;            // [K][3]
   double* bias_out;           // [K][6]
 };
+constexpr int BA_INERTIAL_MAX_K = 51;   // keyframes of an inertial window: BA_MAX_N / 15 (ba_kernels.hip), for callers that refuse before they enqueue
