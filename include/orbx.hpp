@@ -81,6 +81,7 @@ class Handle {
     if (rc != ORBX_OK) throw Error(rc, orbx_last_error(nullptr));
     n_features_ = n_features;
   }
+  Handle(orbx_handle* adopted, int n_features) : h_(adopted), n_features_(n_features) {}   // takes over a handle made through the C ABI (or none)
   Handle(const Handle&) = delete;
   Handle& operator=(const Handle&) = delete;
   Handle(Handle&& o) noexcept : h_(o.h_), n_features_(o.n_features_) { o.h_ = nullptr; }
@@ -166,6 +167,16 @@ struct SE3 {   // se3.rs:5-8; rotation as unit quaternion (w, x, y, z)
   std::array<double, 4> rotation{1, 0, 0, 0};
   std::array<double, 3> translation{0, 0, 0};
 };
+
+namespace detail {
+// SE3 <-> the seven doubles of the C ABI (qw, qx, qy, qz, tx, ty, tz)
+inline void push7(std::vector<double>& v, const SE3& p) { v.insert(v.end(), p.rotation.begin(), p.rotation.end()); v.insert(v.end(), p.translation.begin(), p.translation.end()); }
+inline SE3 se3_from7(const double* p) { return SE3{{p[0], p[1], p[2], p[3]}, {p[4], p[5], p[6]}}; }
+// a std::function<bool()> as the (orbx_should_stop_fn, user) pair of a solve: an empty function is the null callback, `user` its address
+inline int stop_trampoline(void* user) { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; }
+inline orbx_should_stop_fn stop_fn(const std::function<bool()>& f) { return f ? &stop_trampoline : nullptr; }
+inline void* stop_user(const std::function<bool()>& f) { return const_cast<std::function<bool()>*>(&f); }
+}  // namespace detail
 
 // triangulation.rs:401-527.  has_map_point1/2: the `map_point_ids[i].is_some()` flags; has_point_cam1: the
 // `points_cam1[i].is_some()` flags.  Returns (idx1, idx2) pairs in ascending idx1.
@@ -307,15 +318,11 @@ inline std::optional<VisualBAResultData> solve_visual_ba(Handle& h, const Visual
   for (size_t i = 0; i < problem.optimized_kf_ids.size(); ++i) kf_idx[problem.optimized_kf_ids[i]] = (int)i;   // :928-933
   for (size_t i = 0; i < problem.mp_ids.size(); ++i) mp_idx[problem.mp_ids[i]] = (int)i;                       // :935-940
   std::vector<double> poses, fixed, points;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
   for (KeyFrameId id : problem.optimized_kf_ids) {                       // :966-977 (missing pose -> zero params = identity)
     auto it = problem.local_kf_poses.find(id);
-    push7(poses, it != problem.local_kf_poses.end() ? it->second : SE3{});
+    detail::push7(poses, it != problem.local_kf_poses.end() ? it->second : SE3{});
   }
-  for (const auto& kv : problem.fixed_kf_poses) { fixed_idx[kv.first] = (int)fixed_idx.size(); push7(fixed, kv.second); }
+  for (const auto& kv : problem.fixed_kf_poses) { fixed_idx[kv.first] = (int)fixed_idx.size(); detail::push7(fixed, kv.second); }
   for (MapPointId id : problem.mp_ids) {                                 // :980-987
     auto it = problem.local_mp_positions.find(id);
     const std::array<double, 3> p = it != problem.local_mp_positions.end() ? it->second : std::array<double, 3>{0, 0, 0};
@@ -348,18 +355,14 @@ inline std::optional<VisualBAResultData> solve_visual_ba(Handle& h, const Visual
   const orbx_camera c = camera.c();
   const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold,
                            config.max_covisible_keyframes};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
-  void* user = const_cast<std::function<bool()>*>(&should_stop);
   const int rc = all_f32 ? orbx_ba_solve_visual_obs32(h.get(), &c, &cfg, K, poses.data(), F, fixed.data(), M, points.data(), (int)obs32.size(),
-                                                      obs32.data(), should_stop ? +tramp : nullptr, user, out.data(), &it, &e0, &e1)
+                                                      obs32.data(), detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(), &it, &e0, &e1)
                          : orbx_ba_solve_visual(h.get(), &c, &cfg, K, poses.data(), F, fixed.data(), M, points.data(), (int)obs.size(),
-                                                obs.data(), should_stop ? +tramp : nullptr, user, out.data(), &it, &e0, &e1);
+                                                obs.data(), detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(), &it, &e0, &e1);
   if (rc != ORBX_OK) return std::nullopt;                                // :923-925 and every failure -> None
   VisualBAResultData r;
   for (int i = 0; i < K; ++i) {
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    const SE3 p = detail::se3_from7(&out[7 * (size_t)i]);
     r.optimized_poses[problem.optimized_kf_ids[i]] = p;                  // T_wc, :1076
   }
   for (int j = 0; j < M; ++j) r.optimized_points[problem.mp_ids[j]] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
@@ -685,10 +688,6 @@ inline std::vector<TrackResult> track_frames(Handle& h, const CameraModel& camer
   std::vector<KeyPoint> kp;
   std::vector<uint8_t> desc, md;
   std::vector<double> pos, sp, pr;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
   for (int b = 0; b < B; ++b) {
     const TrackFrame& f = frames[b];
     if (!f.features || f.features->descriptors.size() != 32 * f.features->keypoints.size() || f.mp_descriptors.size() != 32 * f.positions.size())
@@ -697,7 +696,7 @@ inline std::vector<TrackResult> track_frames(Handle& h, const CameraModel& camer
     desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
     for (const auto& p : f.positions) pos.insert(pos.end(), p.begin(), p.end());
     md.insert(md.end(), f.mp_descriptors.begin(), f.mp_descriptors.end());
-    push7(sp, f.search_pose); push7(pr, f.prior);
+    detail::push7(sp, f.search_pose); detail::push7(pr, f.prior);
     fo[b + 1] = (int)kp.size(); mo[b + 1] = (int)(pos.size() / 3);
   }
   const size_t NF = kp.size(), M = pos.size() / 3, Bz = (size_t)std::max(B, 1);
@@ -859,10 +858,6 @@ inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel
   std::vector<KeyPoint> kp;
   std::vector<uint8_t> desc;
   std::vector<double> sp, pr;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
   size_t M = 0;                                                   // the lists' host-known bound
   for (int b = 0; b < B; ++b) {
     const MapTrackFrame& f = frames[b];
@@ -870,7 +865,7 @@ inline std::vector<MapTrackResult> map_track_frames(Handle& h, const CameraModel
       throw std::invalid_argument("map_track_frames: a frame's descriptors do not match its keypoints");
     kp.insert(kp.end(), f.features->keypoints.begin(), f.features->keypoints.end());
     desc.insert(desc.end(), f.features->descriptors.begin(), f.features->descriptors.end());
-    push7(sp, f.search_pose); push7(pr, f.prior);
+    detail::push7(sp, f.search_pose); detail::push7(pr, f.prior);
     fo[b + 1] = (int)kp.size();
     if (local) {
       // the host-known bound: the reference keyframe's features plus the n_best largest of the others' (all where it is -1)
@@ -1051,30 +1046,22 @@ inline std::optional<BAWindowSolve> solve_visual_ba_obs32_device(Handle& h, cons
                                                                  const std::vector<SE3>& fixed_cw, std::vector<std::array<double, 3>>& points,
                                                                  const orbx_ba_obs32* d_obs32, int n_obs, const std::function<bool()>& should_stop) {
   std::vector<double> poses, fixed;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
-  for (const SE3& p : poses_cw) push7(poses, p);
-  for (const SE3& p : fixed_cw) push7(fixed, p);
+  for (const SE3& p : poses_cw) detail::push7(poses, p);
+  for (const SE3& p : fixed_cw) detail::push7(fixed, p);
   const int K = (int)poses_cw.size();
   std::vector<double> out((size_t)std::max(K, 1) * 7);
   int it = 0;
   double e0 = 0, e1 = 0;
   const orbx_camera c = camera.c();
   const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, config.max_covisible_keyframes};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
-  void* user = const_cast<std::function<bool()>*>(&should_stop);
   const int rc = orbx_ba_solve_visual_obs32_device(h.get(), &c, &cfg, K, poses.data(), (int)fixed_cw.size(), fixed.data(), (int)points.size(),
-                                                   points.empty() ? nullptr : points[0].data(), n_obs, d_obs32, should_stop ? +tramp : nullptr, user, out.data(), &it,
+                                                   points.empty() ? nullptr : points[0].data(), n_obs, d_obs32, detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(), &it,
                                                    &e0, &e1);
   if (rc == ORBX_ERR_EMPTY) return std::nullopt;
   h.check(rc);
   BAWindowSolve r;
   for (int i = 0; i < K; ++i) {
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    const SE3 p = detail::se3_from7(&out[7 * (size_t)i]);
     r.poses_wc.push_back(p);
   }
   r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
@@ -1099,17 +1086,13 @@ inline std::optional<MapLocalBAResult> map_local_ba(Handle& h, const CameraModel
   double e0 = 0, e1 = 0;
   const orbx_camera c = camera.c();
   const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, mc};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
-  void* user = const_cast<std::function<bool()>*>(&should_stop);
-  const int rc = orbx_map_local_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), cur, should_stop ? +tramp : nullptr, user,
+  const int rc = orbx_map_local_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), cur, detail::stop_fn(should_stop), detail::stop_user(should_stop),
                                    r.local_kf.data(), out.data(), counts, &it, &e0, &e1);
   if (rc == ORBX_ERR_EMPTY) return std::nullopt;
   h.check(rc);
   r.K = counts[0]; r.F = counts[1]; r.M = counts[2]; r.N = counts[3];
   for (int i = 0; i < r.K; ++i) {
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    const SE3 p = detail::se3_from7(&out[7 * (size_t)i]);
     r.poses_wc.push_back(p);
   }
   r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
@@ -1600,15 +1583,11 @@ inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAPr
   for (size_t i = 0; i < n_kfs; ++i) if (i != fixed_pos) { kf_to_param[problem.kf_ids[i]] = (int)opt_ids.size(); opt_ids.push_back(problem.kf_ids[i]); }
   std::unordered_map<MapPointId, int> mp_to_param;
   for (size_t i = 0; i < n_mps; ++i) mp_to_param[problem.mp_ids[i]] = (int)i;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
   std::vector<double> poses, fixed, points;
-  for (KeyFrameId id : opt_ids) { auto it = problem.kf_poses.find(id); push7(poses, it != problem.kf_poses.end() ? it->second : SE3{}); }   // :232-243
+  for (KeyFrameId id : opt_ids) { auto it = problem.kf_poses.find(id); detail::push7(poses, it != problem.kf_poses.end() ? it->second : SE3{}); }   // :232-243
   auto fit = problem.kf_poses.find(problem.fixed_kf_id);
   const SE3 fixed_pose = fit != problem.kf_poses.end() ? fit->second : SE3{};                                                             // :256-261
-  push7(fixed, fixed_pose);
+  detail::push7(fixed, fixed_pose);
   for (MapPointId id : problem.mp_ids) {
     auto it = problem.mp_positions.find(id);
     const std::array<double, 3> p = it != problem.mp_positions.end() ? it->second : std::array<double, 3>{0, 0, 0};
@@ -1632,17 +1611,14 @@ inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAPr
   double e0 = 0, e1 = 0;
   const orbx_camera c = camera.c();
   const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, 0};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
   const int rc = orbx_ba_solve_global(h.get(), &c, &cfg, K, poses.data(), fixed.data(), M, points.data(), (int)obs.size(), obs.data(),
-                                      should_stop ? +tramp : nullptr, const_cast<std::function<bool()>*>(&should_stop), out.data(), &it,
+                                      detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(), &it,
                                       &e0, &e1);
   if (rc != ORBX_OK) return std::nullopt;
   GlobalBAResult r;
   r.optimized_poses[problem.fixed_kf_id] = se3_inverse(fixed_pose);      // :386
   for (int i = 0; i < K; ++i) {
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = out[7 * (size_t)i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = out[7 * (size_t)i + 4 + q];
+    const SE3 p = detail::se3_from7(&out[7 * (size_t)i]);
     r.optimized_poses[opt_ids[(size_t)i]] = p;
   }
   for (int j = 0; j < M; ++j) r.optimized_points[problem.mp_ids[(size_t)j]] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
@@ -1709,13 +1685,9 @@ inline std::optional<InertialBAResultData> solve_inertial_ba(Handle& h, const In
   for (int i = 0; i < K; ++i) kf_idx[problem.opt_kf_ids[(size_t)i]] = i;
   for (int i = 0; i < M; ++i) mp_idx[problem.mp_ids[(size_t)i]] = i;
   std::vector<double> poses, vel, bias, fixed, points, preint;
-  auto push7 = [](std::vector<double>& v, const SE3& p) {
-    v.insert(v.end(), p.rotation.begin(), p.rotation.end());
-    v.insert(v.end(), p.translation.begin(), p.translation.end());
-  };
   for (KeyFrameId id : problem.opt_kf_ids) {                               // :1140-1174, missing entries stay zero
     auto p = problem.kf_poses.find(id);
-    push7(poses, p != problem.kf_poses.end() ? p->second : SE3{});
+    detail::push7(poses, p != problem.kf_poses.end() ? p->second : SE3{});
     auto v = problem.kf_velocities.find(id);
     const std::array<double, 3> vv = v != problem.kf_velocities.end() ? v->second : std::array<double, 3>{0, 0, 0};
     vel.insert(vel.end(), vv.begin(), vv.end());
@@ -1724,7 +1696,7 @@ inline std::optional<InertialBAResultData> solve_inertial_ba(Handle& h, const In
     bias.insert(bias.end(), bb.gyro.begin(), bb.gyro.end());
     bias.insert(bias.end(), bb.accel.begin(), bb.accel.end());
   }
-  for (const auto& kv : problem.fixed_kf_poses) { fixed_idx[kv.first] = (int)fixed_idx.size(); push7(fixed, kv.second); }
+  for (const auto& kv : problem.fixed_kf_poses) { fixed_idx[kv.first] = (int)fixed_idx.size(); detail::push7(fixed, kv.second); }
   for (MapPointId id : problem.mp_ids) {
     auto it = problem.mp_positions.find(id);
     const std::array<double, 3> p = it != problem.mp_positions.end() ? it->second : std::array<double, 3>{0, 0, 0};
@@ -1757,18 +1729,15 @@ inline std::optional<InertialBAResultData> solve_inertial_ba(Handle& h, const In
   const orbx_camera c = camera.c();
   const orbx_inertial_ba_config cfg{config.max_iterations, config.window_size, config.huber_threshold_mono, config.huber_threshold_stereo,
                                     config.initial_lambda, config.gyro_rw_info, config.accel_rw_info};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
   const int rc = orbx_ba_solve_inertial(h.get(), &c, &cfg, K, poses.data(), vel.data(), bias.data(), (int)fixed_idx.size(), fixed.data(), M,
                                         points.data(), (int)obs.size(), obs.data(), (int)(edges.size() / 2), edges.data(), preint.data(),
-                                        should_stop ? +tramp : nullptr, const_cast<std::function<bool()>*>(&should_stop), po.data(), vo.data(),
+                                        detail::stop_fn(should_stop), detail::stop_user(should_stop), po.data(), vo.data(),
                                         bo.data(), &it, &e0, &e1);
   if (rc != ORBX_OK) return std::nullopt;
   InertialBAResultData r;
   for (int i = 1; i < K; ++i) {                                            // skip(1), :1250
     const KeyFrameId id = problem.opt_kf_ids[(size_t)i];
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = po[7 * (size_t)i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = po[7 * (size_t)i + 4 + q];
+    const SE3 p = detail::se3_from7(&po[7 * (size_t)i]);
     r.optimized_poses[id] = p;
     r.optimized_velocities[id] = {vo[3 * (size_t)i], vo[3 * (size_t)i + 1], vo[3 * (size_t)i + 2]};
     ImuBias b;
@@ -1878,19 +1847,15 @@ inline std::optional<MapLocalInertialBAResult> map_local_inertial_ba(Handle& h, 
   const orbx_camera c = camera.c();
   const orbx_inertial_ba_config cfg{config.max_iterations, config.window_size, config.huber_threshold_mono, config.huber_threshold_stereo,
                                     config.initial_lambda, config.gyro_rw_info, config.accel_rw_info};
-  auto tramp = [](void* user) -> int { return (*static_cast<const std::function<bool()>*>(user))() ? 1 : 0; };
   const int rc = orbx_map_local_inertial_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), (int)K, chain.data(), vel.data(), bias.data(),
-                                            (int)edges.size(), ek.data(), preint.data(), should_stop ? +tramp : nullptr,
-                                            const_cast<std::function<bool()>*>(&should_stop), po.data(), vo.data(), bo.data(), r.fixed_kf.data(), counts, &it, &e0, &e1);
+                                            (int)edges.size(), ek.data(), preint.data(), detail::stop_fn(should_stop),
+                                            detail::stop_user(should_stop), po.data(), vo.data(), bo.data(), r.fixed_kf.data(), counts, &it, &e0, &e1);
   if (rc == ORBX_ERR_EMPTY) return std::nullopt;
   h.check(rc);
   r.K = counts[0]; r.F = counts[1]; r.M = counts[2]; r.N = counts[3];
   r.fixed_kf.resize((size_t)r.F - 1);
   for (size_t i = 0; i < K; ++i) {
-    SE3 p;
-    for (int q = 0; q < 4; ++q) p.rotation[q] = po[7 * i + q];
-    for (int q = 0; q < 3; ++q) p.translation[q] = po[7 * i + 4 + q];
-    r.poses_wc.push_back(p);
+    r.poses_wc.push_back(detail::se3_from7(&po[7 * i]));
     r.velocities.push_back({vo[3 * i], vo[3 * i + 1], vo[3 * i + 2]});
     ImuBias b;
     for (int q = 0; q < 3; ++q) { b.gyro[q] = bo[6 * i + q]; b.accel[q] = bo[6 * i + 3 + q]; }

@@ -515,15 +515,15 @@ inline std::optional<GlobalBAResult> run_global_ba(Handle& h, MapSnapshot& map, 
                                                    const std::function<void(const std::function<void()>&)>& lock_read = nullptr,
                                                    const std::function<void(const std::function<void()>&)>& lock_write = nullptr) {
   running.store(true);
+  struct Clear { std::atomic<bool>& flag; ~Clear() { flag.store(false); } } clear{running};   // ... a thrown orbx::Error or a throwing lock callback included
   std::optional<GlobalBAProblemData> problem;
   auto phase1 = [&] { problem = collect_global_ba_data(map); };
   if (lock_read) lock_read(phase1); else phase1();
-  if (!problem) { running.store(false); return std::nullopt; }
+  if (!problem) return std::nullopt;
   std::optional<GlobalBAResult> result = solve_global_ba(h, *problem, camera, config, [&] { return !running.load(); });
-  if (!result) { running.store(false); return std::nullopt; }
+  if (!result) return std::nullopt;
   auto phase3 = [&] { apply_global_ba_results(map, *result); };
   if (lock_write) lock_write(phase3); else phase3();
-  running.store(false);
   return result;
 }
 

@@ -275,6 +275,15 @@ KFDB_MAX_WORDS = 8192                     # words of one BowVector in the databa
 SHOULD_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
+
+def _stop_callback(should_stop):
+    """A solve's orbx_should_stop_fn argument; the caller keeps it in a local while the C call runs (ctypes frees an unreferenced callback)."""
+    return SHOULD_STOP_FN(lambda user: 1 if should_stop() else 0) if should_stop else C.cast(None, SHOULD_STOP_FN)
+
+
+def _solve_outs():
+    return C.c_int(), C.c_double(), C.c_double()          # a solve's iterations, initial_error, final_error: passed with C.byref
+
 _lib = None
 _live_handles = weakref.WeakSet()
 
@@ -308,9 +317,10 @@ def load_library():
                 pass
         L = C.CDLL(LIB_PATH)
         L.orbx_version.restype = C.c_char_p
-        if L.orbx_abi_version() != ABI_VERSION:
+        abi = getattr(L, "orbx_abi_version", None)                  # (a library from before the symbol existed counts as version 0)
+        if abi is None or abi() != ABI_VERSION:
             raise RuntimeError("liborbx_hip.so was built from an orbx.h of ABI version %d, this mirror restates version %d: rebuild with "
-                               "__graft_entry__.build()" % (L.orbx_abi_version(), ABI_VERSION))
+                               "__graft_entry__.build()" % (abi() if abi else 0, ABI_VERSION))
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_last_error.argtypes = [C.c_void_p]
         L.orbx_stream.restype = C.c_void_p
@@ -1425,8 +1435,8 @@ class Handle:
             raise ValueError("map_local_inertial_ba: inconsistent array lengths")
         out_p = np.zeros((max(K, 1), 7)); out_v = np.zeros((max(K, 1), 3)); out_b = np.zeros((max(K, 1), 6))
         fx = np.full(max(len(keyframes), 1), -1, np.int32); counts = np.zeros(4, np.int32)
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         pad = lambda a, shape: a if len(a) else np.zeros(shape, a.dtype)
         rc = self._L.orbx_map_local_inertial_ba(
@@ -1698,8 +1708,8 @@ class Handle:
         if N < 0 or N * BA_OBS32.itemsize > obs32.numel() * obs32.element_size():
             raise ValueError("obs32 holds fewer than n_obs records")
         out_wc = np.zeros((max(K, 1), 7))
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         self._after_torch(obs32)
         rc = self._L.orbx_ba_solve_visual_obs32_device(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_cw), C.c_int(F), _vp(fixed_cw), C.c_int(M), _vp(pts),
@@ -1720,8 +1730,8 @@ class Handle:
         cfg = cfg or LocalBAConfigLM()
         mc = int(cfg.max_covisible_keyframes)
         lk = np.full(1 + max(mc, 0), -1, np.int32); poses = np.zeros((max(mc, 1), 7)); counts = np.zeros(4, np.int32)
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         rc = self._L.orbx_map_local_ba(self._h, C.byref(cam), C.byref(c), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(int(cur)), cb, None,
                                        _vp(lk), _vp(poses), _vp(counts), C.byref(it), C.byref(e0), C.byref(e1))
@@ -2243,8 +2253,8 @@ class Handle:
         obs = np.ascontiguousarray(obs, BA_OBS32 if o32 else BA_OBS)
         K, F, M, N = len(poses_cw), len(fixed_cw), len(pts), len(obs)
         out_wc = np.zeros((max(K, 1), 7))
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         fn = self._L.orbx_ba_solve_visual_obs32 if o32 else self._L.orbx_ba_solve_visual
         rc = fn(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_cw),
@@ -2303,7 +2313,7 @@ class Handle:
             a.poses_cw = poses_cw.ctypes.data; a.fixed_poses_cw = fixed_cw.ctypes.data; a.points = p_pts + 24 * o_pts
             a.obs = obs.ctypes.data; a.poses_wc_out = p_out + 56 * o_out
             o_pts += M; o_out += Ko
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         self._check(self._L.orbx_ba_solve_visual_batch(self._h, C.byref(cam), C.byref(c), C.c_int(len(windows)), arr, cb, None))
         res = []
@@ -2357,8 +2367,8 @@ class Handle:
         if len(vel) != K or len(bias) != K or len(pre) != E:
             raise ValueError("ba_solve_inertial: inconsistent array lengths")
         out_p = np.zeros((max(K, 1), 7)); out_v = np.zeros((max(K, 1), 3)); out_b = np.zeros((max(K, 1), 6))
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         rc = self._L.orbx_ba_solve_inertial(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_wc), _vp(vel), _vp(bias), C.c_int(F),
                                             _vp(fixed_cw), C.c_int(M), _vp(pts), C.c_int(N), _vp(obs), C.c_int(E), _vp(ek), _vp(pre), cb,
@@ -2379,8 +2389,8 @@ class Handle:
         if len(vel) != K or len(bias) != K or len(pre) != E:
             raise ValueError("ba_solve_inertial_obs32: inconsistent array lengths")
         out_p = np.zeros((max(K, 1), 7)); out_v = np.zeros((max(K, 1), 3)); out_b = np.zeros((max(K, 1), 6))
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         rc = fn(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_wc), _vp(vel), _vp(bias), C.c_int(F), _vp(fixed_cw), C.c_int(M), _vp(pts), C.c_int(N),
                 _vp(obs32), C.c_int(E), _vp(ek), _vp(pre), cb, None, _vp(out_p), _vp(out_v), _vp(out_b), C.byref(it), C.byref(e0), C.byref(e1))
@@ -2417,8 +2427,8 @@ class Handle:
         obs = np.ascontiguousarray(obs, BA_OBS32 if o32 else BA_OBS)
         K, M, N = len(poses_cw), len(pts), len(obs)
         out_wc = np.zeros((max(K, 1), 7))
-        it = C.c_int(); e0 = C.c_double(); e1 = C.c_double()
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         fn = self._L.orbx_ba_solve_global_obs32 if o32 else self._L.orbx_ba_solve_global
         rc = fn(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_cw), _vp(fixed), C.c_int(M),
@@ -2938,7 +2948,7 @@ class BaBatch:
         are views of the batch's own arrays, valid until the next solve()."""
         h = self._handle
         np.copyto(self.points, self.points0)
-        cb = SHOULD_STOP_FN((lambda user: 1 if should_stop() else 0)) if should_stop else C.cast(None, SHOULD_STOP_FN)
+        cb = _stop_callback(should_stop)
         cam = camera._c(); c = cfg._c()
         h._check(h._L.orbx_ba_solve_visual_batch(h._h, C.byref(cam), C.byref(c), C.c_int(self.n), self.arr, cb, None))
         res = []

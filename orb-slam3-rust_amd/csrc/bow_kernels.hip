@@ -247,62 +247,66 @@ extern "C" {
 int orbx_vocab_create(orbx_handle* h, int n_nodes, const uint32_t* parent, const uint8_t* is_leaf, const uint8_t* desc,
                       const double* weight, int k, int l, orbx_vocabulary** out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!out || n_nodes < 1 || (n_nodes > 1 && (!parent || !is_leaf || !desc || !weight)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_vocab_create: bad argument");
-  orbx_vocabulary* v = new orbx_vocabulary();
-  v->k = k; v->l = l; v->n_nodes = n_nodes;
-  v->parent.assign(parent ? parent : nullptr, parent ? parent + n_nodes : nullptr);
-  if (v->parent.empty()) v->parent.assign(1, 0xffffffffu);
-  v->is_leaf.assign((size_t)n_nodes, 0); v->desc.assign(32 * (size_t)n_nodes, 0); v->weight.assign((size_t)n_nodes, 0.0);
-  for (int i = 1; i < n_nodes; ++i) { v->is_leaf[i] = is_leaf[i] != 0; v->weight[i] = weight[i]; }
-  if (n_nodes > 1) memcpy(v->desc.data() + 32, desc + 32, 32 * (size_t)(n_nodes - 1));
-  v->parent[0] = 0xffffffffu;
-  if (int rc = vocab_upload(h, v)) { vocab_free_device(v); delete v; return rc; }
-  *out = v;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_vocab_create", [&]() -> int {
+    if (!out || n_nodes < 1 || (n_nodes > 1 && (!parent || !is_leaf || !desc || !weight)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_vocab_create: bad argument");
+    orbx_vocabulary* v = new orbx_vocabulary();
+    v->k = k; v->l = l; v->n_nodes = n_nodes;
+    v->parent.assign(parent ? parent : nullptr, parent ? parent + n_nodes : nullptr);
+    if (v->parent.empty()) v->parent.assign(1, 0xffffffffu);
+    v->is_leaf.assign((size_t)n_nodes, 0); v->desc.assign(32 * (size_t)n_nodes, 0); v->weight.assign((size_t)n_nodes, 0.0);
+    for (int i = 1; i < n_nodes; ++i) { v->is_leaf[i] = is_leaf[i] != 0; v->weight[i] = weight[i]; }
+    if (n_nodes > 1) memcpy(v->desc.data() + 32, desc + 32, 32 * (size_t)(n_nodes - 1));
+    v->parent[0] = 0xffffffffu;
+    if (int rc = vocab_upload(h, v)) { vocab_free_device(v); delete v; return rc; }
+    *out = v;
+    return ORBX_OK;
+  });
 }
 
 int orbx_vocab_load_text(orbx_handle* h, const char* path, orbx_vocabulary** out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!path || !out) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_vocab_load_text: bad argument");
-  std::ifstream f(path);
-  if (!f) return orbx_fail(h, ORBX_ERR_INVALID, "Failed to open vocabulary file: %s", path);        // mod.rs:118-119
-  std::string line;
-  std::vector<std::string> parts;
-  auto split = [&](const std::string& s) { parts.clear(); std::istringstream is(s); std::string t; while (is >> t) parts.push_back(t); };
-  if (!std::getline(f, line)) return orbx_fail(h, ORBX_ERR_INVALID, "Empty vocabulary file");       // :124-127
-  split(line);
-  if (parts.size() < 2) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid header format, expected: k L [scoring weighting]");
-  unsigned long long k, l;
-  if (!parse_uint(parts[0], ~0ull, &k)) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid k value");
-  if (!parse_uint(parts[1], ~0ull, &l)) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid L value");
-  orbx_vocabulary* v = new orbx_vocabulary();
-  v->k = (int)k; v->l = (int)l;
-  v->parent.push_back(0xffffffffu); v->is_leaf.push_back(0); v->desc.assign(32, 0); v->weight.push_back(0.0);   // root (:150)
-  size_t line_no = 1;
-  while (std::getline(f, line)) {
-    ++line_no;
+  return orbx_guard(h, "orbx_vocab_load_text", [&]() -> int {
+    if (!path || !out) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_vocab_load_text: bad argument");
+    std::ifstream f(path);
+    if (!f) return orbx_fail(h, ORBX_ERR_INVALID, "Failed to open vocabulary file: %s", path);        // mod.rs:118-119
+    std::string line;
+    std::vector<std::string> parts;
+    auto split = [&](const std::string& s) { parts.clear(); std::istringstream is(s); std::string t; while (is >> t) parts.push_back(t); };
+    if (!std::getline(f, line)) return orbx_fail(h, ORBX_ERR_INVALID, "Empty vocabulary file");       // :124-127
     split(line);
-    if (parts.size() < 35) continue;                                                                  // :155-157
-    unsigned long long pid, b;
-    if (!parse_uint(parts[0], 0xffffffffull, &pid)) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid parent_id at line %zu", line_no); }
-    uint8_t d[32];
-    for (int i = 0; i < 32; ++i) {
-      if (!parse_uint(parts[2 + i], 255, &b)) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid descriptor byte at line %zu", line_no); }
-      d[i] = (uint8_t)b;
+    if (parts.size() < 2) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid header format, expected: k L [scoring weighting]");
+    unsigned long long k, l;
+    if (!parse_uint(parts[0], ~0ull, &k)) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid k value");
+    if (!parse_uint(parts[1], ~0ull, &l)) return orbx_fail(h, ORBX_ERR_INVALID, "Invalid L value");
+    orbx_vocabulary* v = new orbx_vocabulary();
+    v->k = (int)k; v->l = (int)l;
+    v->parent.push_back(0xffffffffu); v->is_leaf.push_back(0); v->desc.assign(32, 0); v->weight.push_back(0.0);   // root (:150)
+    size_t line_no = 1;
+    while (std::getline(f, line)) {
+      ++line_no;
+      split(line);
+      if (parts.size() < 35) continue;                                                                  // :155-157
+      unsigned long long pid, b;
+      if (!parse_uint(parts[0], 0xffffffffull, &pid)) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid parent_id at line %zu", line_no); }
+      uint8_t d[32];
+      for (int i = 0; i < 32; ++i) {
+        if (!parse_uint(parts[2 + i], 255, &b)) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid descriptor byte at line %zu", line_no); }
+        d[i] = (uint8_t)b;
+      }
+      char* end = nullptr;
+      const double w = strtod(parts[34].c_str(), &end);
+      if (end == parts[34].c_str() || *end != 0) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid weight at line %zu", line_no); }
+      v->parent.push_back((uint32_t)pid);
+      v->is_leaf.push_back(parts[1] == "1");
+      v->desc.insert(v->desc.end(), d, d + 32);
+      v->weight.push_back(w);
     }
-    char* end = nullptr;
-    const double w = strtod(parts[34].c_str(), &end);
-    if (end == parts[34].c_str() || *end != 0) { delete v; return orbx_fail(h, ORBX_ERR_INVALID, "Invalid weight at line %zu", line_no); }
-    v->parent.push_back((uint32_t)pid);
-    v->is_leaf.push_back(parts[1] == "1");
-    v->desc.insert(v->desc.end(), d, d + 32);
-    v->weight.push_back(w);
-  }
-  v->n_nodes = (int)v->parent.size();
-  if (int rc = vocab_upload(h, v)) { vocab_free_device(v); delete v; return rc; }
-  *out = v;
-  return ORBX_OK;
+    v->n_nodes = (int)v->parent.size();
+    if (int rc = vocab_upload(h, v)) { vocab_free_device(v); delete v; return rc; }
+    *out = v;
+    return ORBX_OK;
+  });
 }
 
 void orbx_vocab_destroy(orbx_vocabulary* v) {
@@ -333,86 +337,94 @@ int orbx_vocab_nodes(const orbx_vocabulary* v, uint32_t* parent, uint8_t* is_lea
 int orbx_bow_transform_device(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* d_desc, int n, int levels_up, uint32_t* d_word,
                               uint32_t* d_leaf, uint32_t* d_node, double* d_weight) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!v || n < 0 || levels_up < 0 || (n > 0 && (!d_desc || !d_word || !d_leaf || !d_node || !d_weight)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: bad argument");
-  if (v->device != h->device) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: vocabulary lives on another device");
-  if (n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  ProfScope ps(h, "bow_transform_kernel");
-  hipLaunchKernelGGL(bow_transform_kernel, dim3((n + 15) / 16), dim3(256), 0, h->stream, v->d_child_start, v->d_child, v->d_desc, v->d_parent,
-                     v->d_word, v->d_weight, d_desc, n, levels_up, d_word, d_leaf, d_node, d_weight);
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_bow_transform_device", [&]() -> int {
+    if (!v || n < 0 || levels_up < 0 || (n > 0 && (!d_desc || !d_word || !d_leaf || !d_node || !d_weight)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: bad argument");
+    if (v->device != h->device) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: vocabulary lives on another device");
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    ProfScope ps(h, "bow_transform_kernel");
+    hipLaunchKernelGGL(bow_transform_kernel, dim3((n + 15) / 16), dim3(256), 0, h->stream, v->d_child_start, v->d_child, v->d_desc, v->d_parent,
+                       v->d_word, v->d_weight, d_desc, n, levels_up, d_word, d_leaf, d_node, d_weight);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  });
 }
 
 int orbx_bow_transform(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* desc, int n, int levels_up, uint32_t* out_word,
                        uint32_t* out_leaf, uint32_t* out_node, double* out_weight) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!v || n < 0 || levels_up < 0 || (n > 0 && (!desc || !out_word || !out_leaf || !out_node || !out_weight)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: bad argument");
-  if (n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve(h, h->ws_io[0], 32 * (size_t)n)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], (12 + 8) * (size_t)n)) return rc;
-  uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
-  double* d_w = (double*)h->ws_io[1].p;
-  uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
-  ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out_word, d_word, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_leaf, d_leaf, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_node, d_node, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_weight, d_w, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_bow_transform", [&]() -> int {
+    if (!v || n < 0 || levels_up < 0 || (n > 0 && (!desc || !out_word || !out_leaf || !out_node || !out_weight)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: bad argument");
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = orbx_reserve(h, h->ws_io[0], 32 * (size_t)n)) return rc;
+    if (int rc = orbx_reserve(h, h->ws_io[1], (12 + 8) * (size_t)n)) return rc;
+    uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
+    double* d_w = (double*)h->ws_io[1].p;
+    uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
+    ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
+    ORBX_HIP(h, hipMemcpyAsync(out_word, d_word, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(out_leaf, d_leaf, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(out_node, d_node, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(out_weight, d_w, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    return ORBX_OK;
+  });
 }
 
 int orbx_bow_vectors_device(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* d_desc, int n, int levels_up, uint32_t* d_bow_word,
                             double* d_bow_weight, uint32_t* d_fv_node, int* d_fv_start, int* d_fv_index, int* d_counts) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!v || n < 0 || levels_up < 0 || !d_counts || (n > 0 && (!d_desc || !d_bow_word || !d_bow_weight || !d_fv_node || !d_fv_start || !d_fv_index)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: bad argument");
-  if (n > BOWV_MAX) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: at most %d descriptors per call", BOWV_MAX);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (n == 0) { ORBX_HIP(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), h->stream)); return ORBX_OK; }
-  if (int rc = orbx_reserve(h, h->ws_io[9], (12 + 8) * (size_t)n)) return rc;
-  double* d_w = (double*)h->ws_io[9].p;
-  uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
-  if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
-  ProfScope ps(h, "bow_vectors_kernel");
-  hipLaunchKernelGGL(bow_vectors_kernel, dim3(1), dim3(BOWV_THREADS), 0, h->stream, d_word, d_node, d_w, n, d_bow_word, d_bow_weight, d_fv_node,
-                     d_fv_start, d_fv_index, d_counts);
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_bow_vectors_device", [&]() -> int {
+    if (!v || n < 0 || levels_up < 0 || !d_counts || (n > 0 && (!d_desc || !d_bow_word || !d_bow_weight || !d_fv_node || !d_fv_start || !d_fv_index)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: bad argument");
+    if (n > BOWV_MAX) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: at most %d descriptors per call", BOWV_MAX);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (n == 0) { ORBX_HIP(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), h->stream)); return ORBX_OK; }
+    if (int rc = orbx_reserve(h, h->ws_io[9], (12 + 8) * (size_t)n)) return rc;
+    double* d_w = (double*)h->ws_io[9].p;
+    uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
+    if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
+    ProfScope ps(h, "bow_vectors_kernel");
+    hipLaunchKernelGGL(bow_vectors_kernel, dim3(1), dim3(BOWV_THREADS), 0, h->stream, d_word, d_node, d_w, n, d_bow_word, d_bow_weight, d_fv_node,
+                       d_fv_start, d_fv_index, d_counts);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  });
 }
 
 int orbx_bow_vectors(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* desc, int n, int levels_up, uint32_t* bow_word, double* bow_weight,
                      int* n_bow, uint32_t* fv_node, int* fv_start, int* fv_index, int* n_fv) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!v || n < 0 || !n_bow || !n_fv || (n > 0 && (!desc || !bow_word || !bow_weight || !fv_node || !fv_start || !fv_index)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: bad argument");
-  *n_bow = 0; *n_fv = 0;
-  if (n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t nn = (size_t)n;
-  if (int rc = orbx_reserve(h, h->ws_io[0], 32 * nn)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 8 * nn + 4 * nn + 4 * nn + 4 * (nn + 1) + 4 * nn + 64)) return rc;
-  uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
-  double* d_bw = (double*)h->ws_io[1].p;
-  uint32_t* d_bword = (uint32_t*)(d_bw + n); uint32_t* d_fnode = d_bword + n;
-  int* d_fstart = (int*)(d_fnode + n); int* d_findex = d_fstart + n + 1; int* d_counts = d_findex + n;
-  ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * nn, hipMemcpyHostToDevice, h->stream));
-  if (int rc = orbx_bow_vectors_device(h, v, d_desc, n, levels_up, d_bword, d_bw, d_fnode, d_fstart, d_findex, d_counts)) return rc;
-  int cnt[2];
-  ORBX_HIP(h, hipMemcpyAsync(cnt, d_counts, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  *n_bow = cnt[0]; *n_fv = cnt[1];
-  ORBX_HIP(h, hipMemcpy(bow_word, d_bword, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
-  ORBX_HIP(h, hipMemcpy(bow_weight, d_bw, 8 * (size_t)cnt[0], hipMemcpyDeviceToHost));
-  ORBX_HIP(h, hipMemcpy(fv_node, d_fnode, 4 * (size_t)cnt[1], hipMemcpyDeviceToHost));
-  ORBX_HIP(h, hipMemcpy(fv_start, d_fstart, 4 * ((size_t)cnt[1] + 1), hipMemcpyDeviceToHost));
-  ORBX_HIP(h, hipMemcpy(fv_index, d_findex, 4 * nn, hipMemcpyDeviceToHost));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_bow_vectors", [&]() -> int {
+    if (!v || n < 0 || !n_bow || !n_fv || (n > 0 && (!desc || !bow_word || !bow_weight || !fv_node || !fv_start || !fv_index)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: bad argument");
+    *n_bow = 0; *n_fv = 0;
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t nn = (size_t)n;
+    if (int rc = orbx_reserve(h, h->ws_io[0], 32 * nn)) return rc;
+    if (int rc = orbx_reserve(h, h->ws_io[1], 8 * nn + 4 * nn + 4 * nn + 4 * (nn + 1) + 4 * nn + 64)) return rc;
+    uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
+    double* d_bw = (double*)h->ws_io[1].p;
+    uint32_t* d_bword = (uint32_t*)(d_bw + n); uint32_t* d_fnode = d_bword + n;
+    int* d_fstart = (int*)(d_fnode + n); int* d_findex = d_fstart + n + 1; int* d_counts = d_findex + n;
+    ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * nn, hipMemcpyHostToDevice, h->stream));
+    if (int rc = orbx_bow_vectors_device(h, v, d_desc, n, levels_up, d_bword, d_bw, d_fnode, d_fstart, d_findex, d_counts)) return rc;
+    int cnt[2];
+    ORBX_HIP(h, hipMemcpyAsync(cnt, d_counts, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    *n_bow = cnt[0]; *n_fv = cnt[1];
+    ORBX_HIP(h, hipMemcpy(bow_word, d_bword, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
+    ORBX_HIP(h, hipMemcpy(bow_weight, d_bw, 8 * (size_t)cnt[0], hipMemcpyDeviceToHost));
+    ORBX_HIP(h, hipMemcpy(fv_node, d_fnode, 4 * (size_t)cnt[1], hipMemcpyDeviceToHost));
+    ORBX_HIP(h, hipMemcpy(fv_start, d_fstart, 4 * ((size_t)cnt[1] + 1), hipMemcpyDeviceToHost));
+    ORBX_HIP(h, hipMemcpy(fv_index, d_findex, 4 * nn, hipMemcpyDeviceToHost));
+    return ORBX_OK;
+  });
 }
 
 // OrbVocabulary::score (mod.rs:357-374): 1 - 0.5 * ||v1 - v2||_1 of two BowVectors given as (ascending word id, weight) arrays — the

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -160,125 +161,125 @@ extern "C" {
 // PNG -> 8-bit grey rows.  out == nullptr: only the size is returned.  Returns ORBX_ERR_INVALID for files that are not
 // a non-interlaced greyscale PNG (8/16 bit, optional alpha) or are damaged; ORBX_ERR_CAPACITY when w > stride.
 int orbx_png_decode_gray8(const uint8_t* file, size_t n, uint8_t* out, size_t stride, int* w_out, int* h_out) {
-  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-  if (!file || n < 8 + 25 || memcmp(file, sig, 8) != 0) return ORBX_ERR_INVALID;
-  size_t p = 8;
-  uint32_t w = 0, h = 0;
-  int depth = 0, ctype = -1;
-  std::vector<uint8_t> z;
-  bool have_hdr = false, end = false;
-  while (p + 12 <= n && !end) {
-    const uint32_t len = be32(file + p);
-    const uint8_t* type = file + p + 4;
-    if (p + 12 + (size_t)len > n) return ORBX_ERR_INVALID;
-    const uint8_t* data = file + p + 8;
-    if (!memcmp(type, "IHDR", 4)) {
-      if (len != 13) return ORBX_ERR_INVALID;
-      w = be32(data); h = be32(data + 4); depth = data[8]; ctype = data[9];
-      if (data[10] != 0 || data[11] != 0 || data[12] != 0) return ORBX_ERR_INVALID;   // compression, filter method, interlace
-      if (!(ctype == 0 || ctype == 4) || !(depth == 8 || depth == 16) || w == 0 || h == 0 || w > 65535 || h > 65535) return ORBX_ERR_INVALID;
-      have_hdr = true;
-    } else if (!memcmp(type, "IDAT", 4)) {
-      z.insert(z.end(), data, data + len);
-    } else if (!memcmp(type, "IEND", 4)) {
-      end = true;
-    }
-    p += 12 + (size_t)len;
-  }
-  if (!have_hdr) return ORBX_ERR_INVALID;
-  if (w_out) *w_out = (int)w;
-  if (h_out) *h_out = (int)h;
-  if (!out) return ORBX_OK;
-  if ((size_t)w > stride) return ORBX_ERR_CAPACITY;
-  const int bpp = (ctype == 4 ? 2 : 1) * (depth / 8);        // bytes per pixel in the filtered stream
-  const size_t row = (size_t)w * bpp;
-  std::vector<uint8_t> raw((row + 1) * (size_t)h);
-  uLongf got = (uLongf)raw.size();
-  if (uncompress(raw.data(), &got, z.data(), (uLong)z.size()) != Z_OK || got != raw.size()) return ORBX_ERR_INVALID;
-  // reconstruction (PNG spec 9.2).  8-bit grey without alpha is rebuilt straight in the caller's rows (the previous
-  // output row is the `prior` line); other layouts go through two scratch lines and keep the grey / high byte.
-  std::vector<uint8_t> zero(row, 0), line[2];
-  if (bpp != 1) { line[0].assign(row, 0); line[1].assign(row, 0); }
-  const uint8_t* prev = zero.data();
-  for (uint32_t y = 0; y < h; ++y) {
-    const uint8_t* src = raw.data() + (row + 1) * (size_t)y;
-    const int ft = *src++;
-    uint8_t* cur = bpp == 1 ? out + stride * (size_t)y : line[y & 1].data();
-    const size_t B = (size_t)bpp;
-    switch (ft) {
-      case 0: memcpy(cur, src, row); break;
-      case 1:
-        for (size_t i = 0; i < B; ++i) cur[i] = src[i];
-        for (size_t i = B; i < row; ++i) cur[i] = (uint8_t)(src[i] + cur[i - B]);
-        break;
-      case 2: for (size_t i = 0; i < row; ++i) cur[i] = (uint8_t)(src[i] + prev[i]); break;
-      case 3:
-        for (size_t i = 0; i < B; ++i) cur[i] = (uint8_t)(src[i] + (prev[i] >> 1));
-        for (size_t i = B; i < row; ++i) cur[i] = (uint8_t)(src[i] + ((cur[i - B] + prev[i]) >> 1));
-        break;
-      case 4: {
-        for (size_t i = 0; i < B; ++i) cur[i] = (uint8_t)(src[i] + prev[i]);      // a = c = 0 -> predictor b
-        for (size_t i = B; i < row; ++i) {
-          const int a = cur[i - B], b = prev[i], c = prev[i - B];
-          const int pb0 = a - c, pa0 = b - c;                                      // p - b, p - a
-          const int pa = pa0 < 0 ? -pa0 : pa0, pb = pb0 < 0 ? -pb0 : pb0, pc0 = pa0 + pb0, pc = pc0 < 0 ? -pc0 : pc0;
-          const int pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-          cur[i] = (uint8_t)(src[i] + pr);
-        }
-        break;
+  return orbx_guard(nullptr, "orbx_png_decode_gray8", [&]() -> int {
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (!file || n < 8 + 25 || memcmp(file, sig, 8) != 0) return ORBX_ERR_INVALID;
+    size_t p = 8;
+    uint32_t w = 0, h = 0;
+    int depth = 0, ctype = -1;
+    std::vector<uint8_t> z;
+    bool have_hdr = false, end = false;
+    while (p + 12 <= n && !end) {
+      const uint32_t len = be32(file + p);
+      const uint8_t* type = file + p + 4;
+      if (p + 12 + (size_t)len > n) return ORBX_ERR_INVALID;
+      const uint8_t* data = file + p + 8;
+      if (!memcmp(type, "IHDR", 4)) {
+        if (len != 13) return ORBX_ERR_INVALID;
+        w = be32(data); h = be32(data + 4); depth = data[8]; ctype = data[9];
+        if (data[10] != 0 || data[11] != 0 || data[12] != 0) return ORBX_ERR_INVALID;   // compression, filter method, interlace
+        if (!(ctype == 0 || ctype == 4) || !(depth == 8 || depth == 16) || w == 0 || h == 0 || w > 65535 || h > 65535) return ORBX_ERR_INVALID;
+        have_hdr = true;
+      } else if (!memcmp(type, "IDAT", 4)) {
+        z.insert(z.end(), data, data + len);
+      } else if (!memcmp(type, "IEND", 4)) {
+        end = true;
       }
-      default: return ORBX_ERR_INVALID;
+      p += 12 + (size_t)len;
     }
-    if (bpp != 1) {
-      uint8_t* o = out + stride * (size_t)y;
-      for (uint32_t x = 0; x < w; ++x) o[x] = cur[(size_t)x * bpp];   // grey (high byte of 16 bit), alpha dropped
+    if (!have_hdr) return ORBX_ERR_INVALID;
+    if (w_out) *w_out = (int)w;
+    if (h_out) *h_out = (int)h;
+    if (!out) return ORBX_OK;
+    if ((size_t)w > stride) return ORBX_ERR_CAPACITY;
+    const int bpp = (ctype == 4 ? 2 : 1) * (depth / 8);        // bytes per pixel in the filtered stream
+    const size_t row = (size_t)w * bpp;
+    std::vector<uint8_t> raw((row + 1) * (size_t)h);
+    uLongf got = (uLongf)raw.size();
+    if (uncompress(raw.data(), &got, z.data(), (uLong)z.size()) != Z_OK || got != raw.size()) return ORBX_ERR_INVALID;
+    // reconstruction (PNG spec 9.2).  8-bit grey without alpha is rebuilt straight in the caller's rows (the previous
+    // output row is the `prior` line); other layouts go through two scratch lines and keep the grey / high byte.
+    std::vector<uint8_t> zero(row, 0), line[2];
+    if (bpp != 1) { line[0].assign(row, 0); line[1].assign(row, 0); }
+    const uint8_t* prev = zero.data();
+    for (uint32_t y = 0; y < h; ++y) {
+      const uint8_t* src = raw.data() + (row + 1) * (size_t)y;
+      const int ft = *src++;
+      uint8_t* cur = bpp == 1 ? out + stride * (size_t)y : line[y & 1].data();
+      const size_t B = (size_t)bpp;
+      switch (ft) {
+        case 0: memcpy(cur, src, row); break;
+        case 1:
+          for (size_t i = 0; i < B; ++i) cur[i] = src[i];
+          for (size_t i = B; i < row; ++i) cur[i] = (uint8_t)(src[i] + cur[i - B]);
+          break;
+        case 2: for (size_t i = 0; i < row; ++i) cur[i] = (uint8_t)(src[i] + prev[i]); break;
+        case 3:
+          for (size_t i = 0; i < B; ++i) cur[i] = (uint8_t)(src[i] + (prev[i] >> 1));
+          for (size_t i = B; i < row; ++i) cur[i] = (uint8_t)(src[i] + ((cur[i - B] + prev[i]) >> 1));
+          break;
+        case 4: {
+          for (size_t i = 0; i < B; ++i) cur[i] = (uint8_t)(src[i] + prev[i]);      // a = c = 0 -> predictor b
+          for (size_t i = B; i < row; ++i) {
+            const int a = cur[i - B], b = prev[i], c = prev[i - B];
+            const int pb0 = a - c, pa0 = b - c;                                      // p - b, p - a
+            const int pa = pa0 < 0 ? -pa0 : pa0, pb = pb0 < 0 ? -pb0 : pb0, pc0 = pa0 + pb0, pc = pc0 < 0 ? -pc0 : pc0;
+            const int pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+            cur[i] = (uint8_t)(src[i] + pr);
+          }
+          break;
+        }
+        default: return ORBX_ERR_INVALID;
+      }
+      if (bpp != 1) {
+        uint8_t* o = out + stride * (size_t)y;
+        for (uint32_t x = 0; x < w; ++x) o[x] = cur[(size_t)x * bpp];   // grey (high byte of 16 bit), alpha dropped
+      }
+      prev = cur;
     }
-    prev = cur;
-  }
-  return ORBX_OK;
+    return ORBX_OK;
+  });
 }
 
 // EurocDataset::new (euroc.rs:64-90), the image side: cam0/cam1 data.csv, both sensor.yaml.  `root` is the mav0 directory.
 int orbx_euroc_open(const char* root, orbx_euroc** out, char* err, size_t err_cap) {
-  if (!root || !out) return ORBX_ERR_INVALID;
-  orbx_euroc* d = new orbx_euroc();
-  d->root = root;
-  std::string e;
-  if (load_image_list(d->root + "/cam0/data.csv", d->ts0, d->file0, e) || load_image_list(d->root + "/cam1/data.csv", d->ts1, d->file1, e)) {
-    const int rc = euroc_fail(nullptr, err, err_cap, e);
-    delete d;
-    return rc;
-  }
-  if (d->ts0.size() != d->ts1.size()) {                                    // :69-71
-    const int rc = euroc_fail(nullptr, err, err_cap, "cam0 and cam1 have different number of frames");
-    delete d;
-    return rc;
-  }
-  std::vector<double> k0, k1, T0, T1;
-  for (int c = 0; c < 2; ++c) {
-    const std::string yp = d->root + (c ? "/cam1/sensor.yaml" : "/cam0/sensor.yaml");
-    std::vector<uint8_t> bytes;
-    if (!read_file(yp, bytes)) { const int rc = euroc_fail(nullptr, err, err_cap, "Failed to open " + yp); delete d; return rc; }
-    const std::string text(bytes.begin(), bytes.end());
-    std::vector<double>& k = c ? k1 : k0;
-    std::vector<double>& T = c ? T1 : T0;
-    if (!yaml_numbers(text, "intrinsics", "", k) || !yaml_numbers(text, "T_BS", "data", T)) {
-      const int rc = euroc_fail(nullptr, err, err_cap, yp + ": missing intrinsics or T_BS.data"); delete d; return rc;
+  return orbx_guard(nullptr, "orbx_euroc_open", [&]() -> int {
+    if (!root || !out) return ORBX_ERR_INVALID;
+    std::unique_ptr<orbx_euroc> d(new orbx_euroc());                          // (freed on every way out that does not hand it over)
+    d->root = root;
+    std::string e;
+    if (load_image_list(d->root + "/cam0/data.csv", d->ts0, d->file0, e) || load_image_list(d->root + "/cam1/data.csv", d->ts1, d->file1, e)) {
+      return euroc_fail(nullptr, err, err_cap, e);
     }
-    if (k.size() != 4) { const int rc = euroc_fail(nullptr, err, err_cap, "Expected 4 intrinsics [fx, fy, cx, cy]"); delete d; return rc; }   // :364-369
-    if (T.size() != 16) { const int rc = euroc_fail(nullptr, err, err_cap, "Expected 16 elements for transform"); delete d; return rc; }       // :379-381
-  }
-  d->cam = orbx_camera{k0[0], k0[1], k0[2], k0[3], stereo_baseline(T0, T1)};
-  memcpy(d->k_right, k1.data(), sizeof(d->k_right));
-  if (!d->file0.empty()) {
-    std::vector<uint8_t> bytes;
-    const std::string ip = d->root + "/cam0/data/" + d->file0[0];
-    if (!read_file(ip, bytes) || orbx_png_decode_gray8(bytes.data(), bytes.size(), nullptr, 0, &d->w, &d->h) != ORBX_OK) {
-      const int rc = euroc_fail(nullptr, err, err_cap, "Failed to read left image " + ip); delete d; return rc;
+    if (d->ts0.size() != d->ts1.size()) {                                    // :69-71
+      return euroc_fail(nullptr, err, err_cap, "cam0 and cam1 have different number of frames");
     }
-  }
-  *out = d;
-  return ORBX_OK;
+    std::vector<double> k0, k1, T0, T1;
+    for (int c = 0; c < 2; ++c) {
+      const std::string yp = d->root + (c ? "/cam1/sensor.yaml" : "/cam0/sensor.yaml");
+      std::vector<uint8_t> bytes;
+      if (!read_file(yp, bytes)) return euroc_fail(nullptr, err, err_cap, "Failed to open " + yp);
+      const std::string text(bytes.begin(), bytes.end());
+      std::vector<double>& k = c ? k1 : k0;
+      std::vector<double>& T = c ? T1 : T0;
+      if (!yaml_numbers(text, "intrinsics", "", k) || !yaml_numbers(text, "T_BS", "data", T)) {
+        return euroc_fail(nullptr, err, err_cap, yp + ": missing intrinsics or T_BS.data");
+      }
+      if (k.size() != 4) return euroc_fail(nullptr, err, err_cap, "Expected 4 intrinsics [fx, fy, cx, cy]");   // :364-369
+      if (T.size() != 16) return euroc_fail(nullptr, err, err_cap, "Expected 16 elements for transform");       // :379-381
+    }
+    d->cam = orbx_camera{k0[0], k0[1], k0[2], k0[3], stereo_baseline(T0, T1)};
+    memcpy(d->k_right, k1.data(), sizeof(d->k_right));
+    if (!d->file0.empty()) {
+      std::vector<uint8_t> bytes;
+      const std::string ip = d->root + "/cam0/data/" + d->file0[0];
+      if (!read_file(ip, bytes) || orbx_png_decode_gray8(bytes.data(), bytes.size(), nullptr, 0, &d->w, &d->h) != ORBX_OK) {
+        return euroc_fail(nullptr, err, err_cap, "Failed to read left image " + ip);
+      }
+    }
+    *out = d.release();
+    return ORBX_OK;
+  });
 }
 
 void orbx_euroc_close(orbx_euroc* d) { delete d; }
@@ -304,38 +305,40 @@ int orbx_euroc_calibration(const orbx_euroc* d, orbx_camera* left, double* k_rig
 // out[pair][2][h][w] (left then right; pass a pinned buffer from orbx_host_alloc to overlap the copy to the device).
 // Every image must have the size of the first one.
 int orbx_euroc_read_pairs(orbx_euroc* d, int first, int count, uint8_t* out, int threads) {
-  if (!d || first < 0 || count < 0 || (size_t)first + (size_t)count > d->ts0.size() || (count > 0 && !out)) {
-    if (d) d->err = "orbx_euroc_read_pairs: bad range";
-    return ORBX_ERR_INVALID;
-  }
-  const size_t img = (size_t)d->w * d->h;
-  std::atomic<int> next{0}, bad{-1};
-  auto work = [&]() {
-    std::vector<uint8_t> bytes;
-    for (;;) {
-      const int j = next.fetch_add(1);
-      if (j >= 2 * count) return;
-      const int pr = j >> 1, side = j & 1;
-      const std::string path = d->root + (side ? "/cam1/data/" + d->file1[(size_t)(first + pr)] : "/cam0/data/" + d->file0[(size_t)(first + pr)]);
-      int w = 0, h = 0;
-      if (!read_file(path, bytes) || orbx_png_decode_gray8(bytes.data(), bytes.size(), nullptr, 0, &w, &h) != ORBX_OK || w != d->w || h != d->h ||
-          orbx_png_decode_gray8(bytes.data(), bytes.size(), out + ((size_t)pr * 2 + side) * img, (size_t)d->w, nullptr, nullptr) != ORBX_OK) {
-        int expect = -1;
-        bad.compare_exchange_strong(expect, j);
-      }
+  return orbx_guard(nullptr, "orbx_euroc_read_pairs", [&]() -> int {
+    if (!d || first < 0 || count < 0 || (size_t)first + (size_t)count > d->ts0.size() || (count > 0 && !out)) {
+      if (d) d->err = "orbx_euroc_read_pairs: bad range";
+      return ORBX_ERR_INVALID;
     }
-  };
-  const int nt = std::max(1, std::min(threads, 2 * count));
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; ++t) pool.emplace_back(work);
-  work();
-  for (auto& t : pool) t.join();
-  if (bad.load() >= 0) {
-    const int j = bad.load();
-    d->err = std::string("Failed to read ") + ((j & 1) ? "right" : "left") + " image of frame " + std::to_string(first + (j >> 1));   // :122-125
-    return ORBX_ERR_INVALID;
-  }
-  return ORBX_OK;
+    const size_t img = (size_t)d->w * d->h;
+    std::atomic<int> next{0}, bad{-1};
+    // image j of the range; false: it cannot be read (nothing may leave a thread: out of memory counts as unreadable)
+    auto read = [&](int j, std::vector<uint8_t>& bytes) {
+      try {
+        const int pr = j >> 1, side = j & 1;
+        const std::string path = d->root + (side ? "/cam1/data/" + d->file1[(size_t)(first + pr)] : "/cam0/data/" + d->file0[(size_t)(first + pr)]);
+        int w = 0, h = 0;
+        return read_file(path, bytes) && orbx_png_decode_gray8(bytes.data(), bytes.size(), nullptr, 0, &w, &h) == ORBX_OK && w == d->w && h == d->h &&
+               orbx_png_decode_gray8(bytes.data(), bytes.size(), out + ((size_t)pr * 2 + side) * img, (size_t)d->w, nullptr, nullptr) == ORBX_OK;
+      } catch (...) { return false; }
+    };
+    auto work = [&]() {
+      std::vector<uint8_t> bytes;
+      for (int j; (j = next.fetch_add(1)) < 2 * count;)
+        if (!read(j, bytes)) { int expect = -1; bad.compare_exchange_strong(expect, j); }
+    };
+    const int nt = std::max(1, std::min(threads, 2 * count));
+    std::vector<std::thread> pool;
+    try { for (int t = 1; t < nt; ++t) pool.emplace_back(work); } catch (...) {}      // fewer threads than asked for: the others take its share
+    work();
+    for (auto& t : pool) t.join();
+    if (bad.load() >= 0) {
+      const int j = bad.load();
+      d->err = std::string("Failed to read ") + ((j & 1) ? "right" : "left") + " image of frame " + std::to_string(first + (j >> 1));   // :122-125
+      return ORBX_ERR_INVALID;
+    }
+    return ORBX_OK;
+  });
 }
 
 }  // extern "C"

@@ -116,31 +116,33 @@ int orbx_keyframe_create(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_
                          const uint8_t* d_has_point, uint64_t keyframe_id, uint64_t timestamp_ns, const double* pose_wc,
                          orbx_keyframe** out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!out || n < 0 || (n > 0 && (!d_kp || !d_desc)) || ((d_points_cam == nullptr) != (d_has_point == nullptr)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_create: bad argument");
-  *out = nullptr;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_keyframe* kf = new orbx_keyframe();
-  kf->h = h; kf->id = keyframe_id; kf->timestamp_ns = timestamp_ns; kf->n = n;
-  if (pose_wc) memcpy(kf->pose_wc, pose_wc, sizeof(kf->pose_wc));
-  kf->mp_ids.assign((size_t)n, -1);
-  const size_t n1 = (size_t)(n > 0 ? n : 1);
-  Carve blk;
-  const size_t o_kp = blk.take(sizeof(orbx_keypoint) * n1), o_desc = blk.take(32 * n1), o_pts = blk.take(24 * n1), o_has = blk.take(n1), o_mp = blk.take(n1),
-               o_slot = blk.take(4 * n1), o_uniq = blk.take(4 * n1), total = blk.off;
-  if (hipMalloc((void**)&kf->block, total) != hipSuccess) { delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: out of device memory"); }
-  kf->d_kp = (orbx_keypoint*)(kf->block + o_kp); kf->d_desc = kf->block + o_desc; kf->d_points = (double*)(kf->block + o_pts);
-  kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp; kf->d_mp_slot = (int*)(kf->block + o_slot);
-  kf->d_mp_uniq = (int*)(kf->block + o_uniq);
-  hipStream_t st = h->stream;
-  hipError_t e = hipMemsetAsync(kf->block + o_pts, 0, total - o_pts, st);       // points (0,0,0), no stereo point, no map point
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_kp, d_kp, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_desc, d_desc, 32 * (size_t)n, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && n > 0 && d_points_cam) e = hipMemcpyAsync(kf->d_points, d_points_cam, 24 * (size_t)n, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && n > 0 && d_has_point) e = hipMemcpyAsync(kf->d_has_point, d_has_point, (size_t)n, hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) { hipFree(kf->block); delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: %s", hipGetErrorString(e)); }
-  *out = kf;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_create", [&]() -> int {
+    if (!out || n < 0 || (n > 0 && (!d_kp || !d_desc)) || ((d_points_cam == nullptr) != (d_has_point == nullptr)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_create: bad argument");
+    *out = nullptr;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    orbx_keyframe* kf = new orbx_keyframe();
+    kf->h = h; kf->id = keyframe_id; kf->timestamp_ns = timestamp_ns; kf->n = n;
+    if (pose_wc) memcpy(kf->pose_wc, pose_wc, sizeof(kf->pose_wc));
+    kf->mp_ids.assign((size_t)n, -1);
+    const size_t n1 = (size_t)(n > 0 ? n : 1);
+    Carve blk;
+    const size_t o_kp = blk.take(sizeof(orbx_keypoint) * n1), o_desc = blk.take(32 * n1), o_pts = blk.take(24 * n1), o_has = blk.take(n1), o_mp = blk.take(n1),
+                 o_slot = blk.take(4 * n1), o_uniq = blk.take(4 * n1), total = blk.off;
+    if (hipMalloc((void**)&kf->block, total) != hipSuccess) { delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: out of device memory"); }
+    kf->d_kp = (orbx_keypoint*)(kf->block + o_kp); kf->d_desc = kf->block + o_desc; kf->d_points = (double*)(kf->block + o_pts);
+    kf->d_has_point = kf->block + o_has; kf->d_mp_flag = kf->block + o_mp; kf->d_mp_slot = (int*)(kf->block + o_slot);
+    kf->d_mp_uniq = (int*)(kf->block + o_uniq);
+    hipStream_t st = h->stream;
+    hipError_t e = hipMemsetAsync(kf->block + o_pts, 0, total - o_pts, st);       // points (0,0,0), no stereo point, no map point
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_kp, d_kp, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(kf->d_desc, d_desc, 32 * (size_t)n, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && n > 0 && d_points_cam) e = hipMemcpyAsync(kf->d_points, d_points_cam, 24 * (size_t)n, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && n > 0 && d_has_point) e = hipMemcpyAsync(kf->d_has_point, d_has_point, (size_t)n, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) { hipFree(kf->block); delete kf; return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_create: %s", hipGetErrorString(e)); }
+    *out = kf;
+    return ORBX_OK;
+  });
 }
 
 void orbx_keyframe_destroy(orbx_keyframe* kf) {
@@ -169,14 +171,16 @@ int orbx_keyframe_set_pose(orbx_keyframe* kf, const double* pose_wc) {
 int orbx_keyframe_set_map_points(orbx_keyframe* kf, const int64_t* mp_ids) {
   if (!kf || (kf->n > 0 && !mp_ids)) return ORBX_ERR_INVALID;
   orbx_handle* h = kf->h;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  std::vector<uint8_t> flag((size_t)kf->n);
-  for (int i = 0; i < kf->n; ++i) { kf->mp_ids[(size_t)i] = mp_ids[i]; flag[(size_t)i] = mp_ids[i] >= 0 ? 1 : 0; }
-  if (kf->n > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_flag, flag.data(), (size_t)kf->n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));                     // flag is a local
-  }
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_set_map_points", [&]() -> int {
+    ORBX_HIP(h, hipSetDevice(h->device));
+    std::vector<uint8_t> flag((size_t)kf->n);
+    for (int i = 0; i < kf->n; ++i) { kf->mp_ids[(size_t)i] = mp_ids[i]; flag[(size_t)i] = mp_ids[i] >= 0 ? 1 : 0; }
+    if (kf->n > 0) {
+      ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_flag, flag.data(), (size_t)kf->n, hipMemcpyHostToDevice, h->stream));
+      ORBX_HIP(h, hipStreamSynchronize(h->stream));                     // flag is a local
+    }
+    return ORBX_OK;
+  });
 }
 
 int orbx_keyframe_get_map_points(const orbx_keyframe* kf, int64_t* mp_ids) {
@@ -207,60 +211,66 @@ const uint8_t* orbx_keyframe_device_descriptors(const orbx_keyframe* kf) { retur
 int orbx_keyframe_guided_match(orbx_handle* h, const orbx_keyframe* kf, double img_w, double img_h, const double* q_uv,
                                const uint8_t* q_desc, int nq, double radius, int mode, int* out_idx, uint32_t* out_dist) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!kf || kf->h != h || nq < 0 || (nq > 0 && (!q_uv || !q_desc || !out_idx || !out_dist)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_guided_match: bad argument (a keyframe belongs to the handle that made it)");
-  if (nq == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // only the queries travel (48 B each up, 8 B each down); the frame's n x 60 B of features stay where they are
-  if (int rc = orbx_reserve(h, h->ws_io[8], 16 * (size_t)nq + 32 * (size_t)nq + 8 * (size_t)nq)) return rc;
-  double* d_uv = (double*)h->ws_io[8].p;
-  uint8_t* d_qd = (uint8_t*)(d_uv + 2 * (size_t)nq);
-  int* d_idx = (int*)(d_qd + 32 * (size_t)nq);
-  uint32_t* d_dist = (uint32_t*)(d_idx + nq);
-  ORBX_HIP(h, hipMemcpyAsync(d_uv, q_uv, 16 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_qd, q_desc, 32 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-  if (int rc = orbx_guided_match_device(h, kf->d_kp, kf->d_desc, kf->n, img_w, img_h, d_uv, d_qd, nq, radius, mode, d_idx, d_dist)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_guided_match", [&]() -> int {
+    if (!kf || kf->h != h || nq < 0 || (nq > 0 && (!q_uv || !q_desc || !out_idx || !out_dist)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_guided_match: bad argument (a keyframe belongs to the handle that made it)");
+    if (nq == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // only the queries travel (48 B each up, 8 B each down); the frame's n x 60 B of features stay where they are
+    if (int rc = orbx_reserve(h, h->ws_io[8], 16 * (size_t)nq + 32 * (size_t)nq + 8 * (size_t)nq)) return rc;
+    double* d_uv = (double*)h->ws_io[8].p;
+    uint8_t* d_qd = (uint8_t*)(d_uv + 2 * (size_t)nq);
+    int* d_idx = (int*)(d_qd + 32 * (size_t)nq);
+    uint32_t* d_dist = (uint32_t*)(d_idx + nq);
+    ORBX_HIP(h, hipMemcpyAsync(d_uv, q_uv, 16 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(d_qd, q_desc, 32 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
+    if (int rc = orbx_guided_match_device(h, kf->d_kp, kf->d_desc, kf->n, img_w, img_h, d_uv, d_qd, nq, radius, mode, d_idx, d_dist)) return rc;
+    ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    return ORBX_OK;
+  });
 }
 
 int orbx_keyframe_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const orbx_keyframe* kf1, const orbx_keyframe* kf2,
                                            unsigned max_dist, int* out_pairs, int* n_out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || !kf1 || !kf2 || kf1->h != h || kf2->h != h || !n_out || (kf1->n > 0 && !out_pairs))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_search_for_triangulation: bad argument");
-  *n_out = 0;
-  if (kf1->n == 0 || kf2->n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(int) * (2 * (size_t)kf1->n + 4))) return rc;
-  int* d_pairs = (int*)h->ws_io[8].p;
-  int* d_n = d_pairs + 2 * (size_t)kf1->n;
-  // map_point_ids[i].is_some() = the keyframe's map-point flags, points_cam[i].is_some() = its stereo flags (triangulation.rs:401-527)
-  if (int rc = orbx_search_for_triangulation_device(h, cam, kf1->d_kp, kf1->d_desc, kf1->d_mp_flag, kf1->d_has_point, kf1->n, kf2->d_kp,
-                                                    kf2->d_desc, kf2->d_mp_flag, kf2->n, kf1->pose_wc, kf2->pose_wc, max_dist, d_pairs, d_n))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_search_for_triangulation", [&]() -> int {
+    if (!cam || !kf1 || !kf2 || kf1->h != h || kf2->h != h || !n_out || (kf1->n > 0 && !out_pairs))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_search_for_triangulation: bad argument");
+    *n_out = 0;
+    if (kf1->n == 0 || kf2->n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(int) * (2 * (size_t)kf1->n + 4))) return rc;
+    int* d_pairs = (int*)h->ws_io[8].p;
+    int* d_n = d_pairs + 2 * (size_t)kf1->n;
+    // map_point_ids[i].is_some() = the keyframe's map-point flags, points_cam[i].is_some() = its stereo flags (triangulation.rs:401-527)
+    if (int rc = orbx_search_for_triangulation_device(h, cam, kf1->d_kp, kf1->d_desc, kf1->d_mp_flag, kf1->d_has_point, kf1->n, kf2->d_kp,
+                                                      kf2->d_desc, kf2->d_mp_flag, kf2->n, kf1->pose_wc, kf2->pose_wc, max_dist, d_pairs, d_n))
+      return rc;
+    ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
+    return ORBX_OK;
+  });
 }
 
 int orbx_keyframe_set_feature_nodes(orbx_keyframe* kf, const uint32_t* node) {
   if (!kf) return ORBX_ERR_INVALID;
-  kf->has_nodes = false; kf->node.clear(); kf->node_sorted.clear(); kf->node_m = 0;
-  if (!node) return ORBX_OK;
-  const int n = kf->n;
-  kf->node.assign(node, node + n);
-  kf->node_sorted.resize((size_t)n);
-  for (int i = 0; i < n; ++i) kf->node_sorted[(size_t)i] = i;
-  std::stable_sort(kf->node_sorted.begin(), kf->node_sorted.end(), [&](int a, int b) { return node[a] < node[b]; });
-  int m = n;
-  while (m > 0 && node[kf->node_sorted[(size_t)m - 1]] == 0xffffffffu) --m;
-  kf->node_m = m;
-  kf->has_nodes = true;
-  return ORBX_OK;
+  return orbx_guard(kf->h, "orbx_keyframe_set_feature_nodes", [&]() -> int {
+    kf->has_nodes = false; kf->node.clear(); kf->node_sorted.clear(); kf->node_m = 0;
+    if (!node) return ORBX_OK;
+    const int n = kf->n;
+    kf->node.assign(node, node + n);
+    kf->node_sorted.resize((size_t)n);
+    for (int i = 0; i < n; ++i) kf->node_sorted[(size_t)i] = i;
+    std::stable_sort(kf->node_sorted.begin(), kf->node_sorted.end(), [&](int a, int b) { return node[a] < node[b]; });
+    int m = n;
+    while (m > 0 && node[kf->node_sorted[(size_t)m - 1]] == 0xffffffffu) --m;
+    kf->node_m = m;
+    kf->has_nodes = true;
+    return ORBX_OK;
+  });
 }
 
 // triangulate_from_neighbors (triangulation.rs:71-308) without get_neighbor_keyframes and the map mutation: see include/orbx.h.
@@ -268,61 +278,63 @@ int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* 
                                              const orbx_keyframe* cur, const orbx_keyframe* const* kfs, int T, int cap, int* out_neighbour,
                                              int* out_idx1, int* out_idx2, double* out_points, int* n_out, int* stats) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || !cfg || !cur || cur->h != h || !n_out || T < 0 || T > 256 || cap < 0 || cfg->max_descriptor_dist > 256 || (T > 0 && (!kfs || !stats)) ||
-      (cap > 0 && (!out_neighbour || !out_idx1 || !out_idx2 || !out_points)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: bad argument (T <= 256; max_descriptor_dist <= 256; a keyframe belongs to the handle that made it)");
-  *n_out = 0;
-  for (int t = 0; t < T; ++t)
-    if (!kfs[t] || kfs[t]->h != h)
-      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: keyframe %d is null or of another handle", t);
-  if (T == 0) return ORBX_OK;
-  memset(stats, 0, sizeof(int) * 4 * (size_t)T);
-  TriNbPlan P;
-  tri_nb_plan(cam, cur, kfs, T, P);
-  const int Ts = (int)P.orig.size();
-  if (Ts == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // ---- the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch | status | points] [result blob]
-  const size_t slots = (size_t)Ts * (size_t)P.n1;
-  const size_t capd = std::min((size_t)cap, slots);
-  const size_t o_res = P.up_bytes + P.ws_bytes, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd,
-               r_i1 = r_nb + 4 * capd, r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
-  if (int rc = orbx_reserve(h, h->ws_io[10], o_res + res_bytes)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_io[10].p;
-  std::vector<uint8_t> up(P.up_bytes), down(res_bytes);
-  std::vector<const uint8_t*> mp2((size_t)T);
-  for (int t = 0; t < T; ++t) mp2[(size_t)t] = kfs[t]->d_mp_flag;
-  // map_point_ids[i].is_some() = the keyframes' map-point flags (triangulation.rs:94-107, :401-527)
-  tri_nb_fill(P, cam, cfg, cur, kfs, cur->d_mp_flag, mp2.data(), up.data(), d, d + P.up_bytes);
-  // ---- one upload, the launches, one download, one synchronisation
-  hipStream_t st = h->stream;
-  hipError_t e = hipMemcpyAsync(d, up.data(), P.up_bytes, hipMemcpyHostToDevice, st);
-  int rc = ORBX_OK;
-  if (e == hipSuccess) {
-    orbx_prof_begin_call(h);
-    rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, d, d + P.up_bytes, (int)capd, (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1),
-                       (int*)(d + o_res + r_i2), (double*)(d + o_res + r_pts));
-    if (!rc) e = hipMemcpyAsync(down.data(), d + o_res, res_bytes, hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t es = hipStreamSynchronize(st);                       // also on the error paths: `up` / `down` are locals
-  if (rc) return rc;
-  if (e != hipSuccess || es != hipSuccess)
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_triangulate_from_neighbors: %s", hipGetErrorString(e != hipSuccess ? e : es));
-  const int* head = (const int*)(down.data() + r_head);
-  for (int k = 0; k < Ts; ++k) {
-    int* s4 = stats + 4 * (size_t)P.orig[(size_t)k];
-    s4[0] = 1; s4[1] = head[2 + 4 * k]; s4[2] = head[3 + 4 * k]; s4[3] = head[4 + 4 * k];
-  }
-  *n_out = head[0];
-  const size_t nw = std::min((size_t)head[0], capd);
-  const int* nb_k = (const int*)(down.data() + r_nb);
-  for (size_t i = 0; i < nw; ++i) out_neighbour[i] = P.orig[(size_t)nb_k[i]];
-  if (nw > 0) {
-    memcpy(out_idx1, down.data() + r_i1, 4 * nw);
-    memcpy(out_idx2, down.data() + r_i2, 4 * nw);
-    memcpy(out_points, down.data() + r_pts, 24 * nw);
-  }
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_triangulate_from_neighbors", [&]() -> int {
+    if (!cam || !cfg || !cur || cur->h != h || !n_out || T < 0 || T > 256 || cap < 0 || cfg->max_descriptor_dist > 256 || (T > 0 && (!kfs || !stats)) ||
+        (cap > 0 && (!out_neighbour || !out_idx1 || !out_idx2 || !out_points)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: bad argument (T <= 256; max_descriptor_dist <= 256; a keyframe belongs to the handle that made it)");
+    *n_out = 0;
+    for (int t = 0; t < T; ++t)
+      if (!kfs[t] || kfs[t]->h != h)
+        return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_triangulate_from_neighbors: keyframe %d is null or of another handle", t);
+    if (T == 0) return ORBX_OK;
+    memset(stats, 0, sizeof(int) * 4 * (size_t)T);
+    TriNbPlan P;
+    tri_nb_plan(cam, cur, kfs, T, P);
+    const int Ts = (int)P.orig.size();
+    if (Ts == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // ---- the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch | status | points] [result blob]
+    const size_t slots = (size_t)Ts * (size_t)P.n1;
+    const size_t capd = std::min((size_t)cap, slots);
+    const size_t o_res = P.up_bytes + P.ws_bytes, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd,
+                 r_i1 = r_nb + 4 * capd, r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
+    if (int rc = orbx_reserve(h, h->ws_io[10], o_res + res_bytes)) return rc;
+    uint8_t* d = (uint8_t*)h->ws_io[10].p;
+    std::vector<uint8_t> up(P.up_bytes), down(res_bytes);
+    std::vector<const uint8_t*> mp2((size_t)T);
+    for (int t = 0; t < T; ++t) mp2[(size_t)t] = kfs[t]->d_mp_flag;
+    // map_point_ids[i].is_some() = the keyframes' map-point flags (triangulation.rs:94-107, :401-527)
+    tri_nb_fill(P, cam, cfg, cur, kfs, cur->d_mp_flag, mp2.data(), up.data(), d, d + P.up_bytes);
+    // ---- one upload, the launches, one download, one synchronisation
+    hipStream_t st = h->stream;
+    hipError_t e = hipMemcpyAsync(d, up.data(), P.up_bytes, hipMemcpyHostToDevice, st);
+    int rc = ORBX_OK;
+    if (e == hipSuccess) {
+      orbx_prof_begin_call(h);
+      rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, d, d + P.up_bytes, (int)capd, (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1),
+                         (int*)(d + o_res + r_i2), (double*)(d + o_res + r_pts));
+      if (!rc) e = hipMemcpyAsync(down.data(), d + o_res, res_bytes, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);                       // also on the error paths: `up` / `down` are locals
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess)
+      return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_triangulate_from_neighbors: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    const int* head = (const int*)(down.data() + r_head);
+    for (int k = 0; k < Ts; ++k) {
+      int* s4 = stats + 4 * (size_t)P.orig[(size_t)k];
+      s4[0] = 1; s4[1] = head[2 + 4 * k]; s4[2] = head[3 + 4 * k]; s4[3] = head[4 + 4 * k];
+    }
+    *n_out = head[0];
+    const size_t nw = std::min((size_t)head[0], capd);
+    const int* nb_k = (const int*)(down.data() + r_nb);
+    for (size_t i = 0; i < nw; ++i) out_neighbour[i] = P.orig[(size_t)nb_k[i]];
+    if (nw > 0) {
+      memcpy(out_idx1, down.data() + r_i1, 4 * nw);
+      memcpy(out_idx2, down.data() + r_i2, 4 * nw);
+      memcpy(out_points, down.data() + r_pts, 24 * nw);
+    }
+    return ORBX_OK;
+  });
 }
 
 // track_with_reference_kf (tracker.rs:992-1064) against resident keyframes: see include/orbx.h.  The launches are
@@ -336,65 +348,69 @@ int orbx_keyframe_track_reference(orbx_handle* h, const orbx_camera* cam, const 
                                   orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results) {
   static const char* who = "orbx_keyframe_track_reference";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
-  if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && (!kfs || !kf_offsets)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
-  if (n_frames == 0) return ORBX_OK;
-  if (kf_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets[0] must be 0", who);
-  std::vector<TrackRefItem> items((size_t)n_frames);
-  for (int b = 0; b < n_frames; ++b) {
-    const orbx_keyframe* kf = kfs[b];
-    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, b);
-    if (kf_offsets[b + 1] - kf_offsets[b] != kf->n)
-      return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets gives keyframe %d %d rows, it has %d features", who, b, kf_offsets[b + 1] - kf_offsets[b], kf->n);
-    items[(size_t)b].kf_desc = kf->d_desc; items[(size_t)b].kf_off = kf_offsets[b]; items[(size_t)b].n = kf->n;
-  }
-  return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
-                                 max_feat, items.data(), kf_positions, kf_valid, true, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
-                                 d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
+    if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && (!kfs || !kf_offsets)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
+    if (n_frames == 0) return ORBX_OK;
+    if (kf_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets[0] must be 0", who);
+    std::vector<TrackRefItem> items((size_t)n_frames);
+    for (int b = 0; b < n_frames; ++b) {
+      const orbx_keyframe* kf = kfs[b];
+      if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, b);
+      if (kf_offsets[b + 1] - kf_offsets[b] != kf->n)
+        return orbx_fail(h, ORBX_ERR_INVALID, "%s: kf_offsets gives keyframe %d %d rows, it has %d features", who, b, kf_offsets[b + 1] - kf_offsets[b], kf->n);
+      items[(size_t)b].kf_desc = kf->d_desc; items[(size_t)b].kf_off = kf_offsets[b]; items[(size_t)b].n = kf->n;
+    }
+    return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
+                                   max_feat, items.data(), kf_positions, kf_valid, true, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
+                                   d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  });
 }
 
 int orbx_keyframe_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* positions, const uint8_t* mp_desc, int P,
                               const orbx_keyframe* const* kfs, int T, double radius_scale, unsigned desc_threshold, int* out_idx,
                               uint32_t* out_dist) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || P < 0 || T < 0 || (P > 0 && (!positions || !mp_desc)) || (T > 0 && !kfs) || (P > 0 && T > 0 && (!out_idx || !out_dist)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: bad argument");
-  if (P == 0 || T == 0) return ORBX_OK;
-  std::vector<int> off((size_t)T + 1, 0);
-  std::vector<double> poses(7 * (size_t)T);
-  for (int t = 0; t < T; ++t) {
-    if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: keyframe %d is null or of another handle", t);
-    off[(size_t)t + 1] = off[(size_t)t] + kfs[t]->n;
-    memcpy(&poses[7 * (size_t)t], kfs[t]->pose_wc, 56);
-  }
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t n = (size_t)std::max(off[(size_t)T], 1), pt = (size_t)P * T;
-  // the target keyframes' features side by side (device-to-device, no host hop), the map points and the result block
-  if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(orbx_keypoint) * n + 32 * n + 32 * (size_t)P + 24 * (size_t)P + 4 * ((size_t)T + 1) + 8 * pt + 64)) return rc;
-  uint8_t* b = (uint8_t*)h->ws_io[8].p;
-  double* d_pos = (double*)b; b += 24 * (size_t)P;
-  int* d_idx = (int*)b; b += 4 * pt; uint32_t* d_dist = (uint32_t*)b; b += 4 * pt;
-  orbx_keypoint* d_kps = (orbx_keypoint*)b; b += sizeof(orbx_keypoint) * n;
-  uint8_t* d_descs = b; b += 32 * n;
-  uint8_t* d_mpd = b; b += 32 * (size_t)P;
-  int* d_off = (int*)b;
-  hipStream_t st = h->stream;
-  for (int t = 0; t < T; ++t)
-    if (kfs[t]->n > 0) {
-      ORBX_HIP(h, hipMemcpyAsync(d_kps + off[(size_t)t], kfs[t]->d_kp, sizeof(orbx_keypoint) * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
-      ORBX_HIP(h, hipMemcpyAsync(d_descs + 32 * (size_t)off[(size_t)t], kfs[t]->d_desc, 32 * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
+  return orbx_guard(h, "orbx_keyframe_fuse_search", [&]() -> int {
+    if (!cam || P < 0 || T < 0 || (P > 0 && (!positions || !mp_desc)) || (T > 0 && !kfs) || (P > 0 && T > 0 && (!out_idx || !out_dist)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: bad argument");
+    if (P == 0 || T == 0) return ORBX_OK;
+    std::vector<int> off((size_t)T + 1, 0);
+    std::vector<double> poses(7 * (size_t)T);
+    for (int t = 0; t < T; ++t) {
+      if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: keyframe %d is null or of another handle", t);
+      off[(size_t)t + 1] = off[(size_t)t] + kfs[t]->n;
+      memcpy(&poses[7 * (size_t)t], kfs[t]->pose_wc, 56);
     }
-  ORBX_HIP(h, hipMemcpyAsync(d_pos, positions, 24 * (size_t)P, hipMemcpyHostToDevice, st));
-  ORBX_HIP(h, hipMemcpyAsync(d_mpd, mp_desc, 32 * (size_t)P, hipMemcpyHostToDevice, st));
-  ORBX_HIP(h, hipMemcpyAsync(d_off, off.data(), 4 * ((size_t)T + 1), hipMemcpyHostToDevice, st));
-  ORBX_HIP(h, hipStreamSynchronize(st));                               // `off` is a local
-  if (int rc = orbx_fuse_search_device(h, cam, d_pos, d_mpd, P, poses.data(), d_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_idx, d_dist))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * pt, hipMemcpyDeviceToHost, st));
-  ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * pt, hipMemcpyDeviceToHost, st));
-  ORBX_HIP(h, hipStreamSynchronize(st));
-  return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t n = (size_t)std::max(off[(size_t)T], 1), pt = (size_t)P * T;
+    // the target keyframes' features side by side (device-to-device, no host hop), the map points and the result block
+    if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(orbx_keypoint) * n + 32 * n + 32 * (size_t)P + 24 * (size_t)P + 4 * ((size_t)T + 1) + 8 * pt + 64)) return rc;
+    uint8_t* b = (uint8_t*)h->ws_io[8].p;
+    double* d_pos = (double*)b; b += 24 * (size_t)P;
+    int* d_idx = (int*)b; b += 4 * pt; uint32_t* d_dist = (uint32_t*)b; b += 4 * pt;
+    orbx_keypoint* d_kps = (orbx_keypoint*)b; b += sizeof(orbx_keypoint) * n;
+    uint8_t* d_descs = b; b += 32 * n;
+    uint8_t* d_mpd = b; b += 32 * (size_t)P;
+    int* d_off = (int*)b;
+    hipStream_t st = h->stream;
+    for (int t = 0; t < T; ++t)
+      if (kfs[t]->n > 0) {
+        ORBX_HIP(h, hipMemcpyAsync(d_kps + off[(size_t)t], kfs[t]->d_kp, sizeof(orbx_keypoint) * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
+        ORBX_HIP(h, hipMemcpyAsync(d_descs + 32 * (size_t)off[(size_t)t], kfs[t]->d_desc, 32 * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
+      }
+    ORBX_HIP(h, hipMemcpyAsync(d_pos, positions, 24 * (size_t)P, hipMemcpyHostToDevice, st));
+    ORBX_HIP(h, hipMemcpyAsync(d_mpd, mp_desc, 32 * (size_t)P, hipMemcpyHostToDevice, st));
+    ORBX_HIP(h, hipMemcpyAsync(d_off, off.data(), 4 * ((size_t)T + 1), hipMemcpyHostToDevice, st));
+    ORBX_HIP(h, hipStreamSynchronize(st));                               // `off` is a local
+    if (int rc = orbx_fuse_search_device(h, cam, d_pos, d_mpd, P, poses.data(), d_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_idx, d_dist))
+      return rc;
+    ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * pt, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * pt, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(h, hipStreamSynchronize(st));
+    return ORBX_OK;
+  });
 }
 
 int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
@@ -403,51 +419,53 @@ int orbx_keyframe_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam,
                                          orbx_loop_verify_result* results) {
   static const char* who = "orbx_keyframe_verify_loop_candidates";
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || !cfg || n_pairs < 0 || (n_pairs > 0 && (!cur_kfs || !loop_kfs || !sim3 || !results)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_pairs == 0) return ORBX_OK;
-  const size_t B = (size_t)n_pairs;
-  std::vector<LoopVerifyPair> pairs(B);
-  size_t N1 = 0;
-  for (size_t b = 0; b < B; ++b) {
-    const orbx_keyframe* c = cur_kfs[b];
-    const orbx_keyframe* l = loop_kfs[b];
-    if (!c || !l || c->h != h || l->h != h || N1 + (size_t)c->n > 0x7fffffffu)
-      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad keyframe at pair %d (a keyframe belongs to the handle that made it)", who, (int)b);
-    LoopVerifyPair& p = pairs[b];
-    p.c_desc = c->d_desc; p.c_pts = c->d_points; p.c_has = c->d_has_point; p.c_node = c->has_nodes ? c->node.data() : nullptr; p.n1 = c->n;
-    p.l_kp = l->d_kp; p.l_desc = l->d_desc; p.l_pts = l->d_points; p.l_has = l->d_has_point; p.l_node = l->has_nodes ? l->node.data() : nullptr;
-    p.n2 = l->n;
-    memcpy(p.pose_c, c->pose_wc, sizeof(p.pose_c)); memcpy(p.pose_l, l->pose_wc, sizeof(p.pose_l));
-    p.out_off = (int)N1;
-    N1 += (size_t)c->n;
-  }
-  if (N1 > 0 && (!matches || !feature_matches || !pts_current || !pts_loop || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // the outputs in one device block: [sim3 | records | matches | feature matches | pts current | pts loop | inliers]
-  Carve out;
-  const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
-               o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
-  if (int rc = orbx_reserve(h, h->ws_lv[1], out.off)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_lv[1].p;
-  if (int rc = loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), (orbx_dmatch*)(d + o_ma), (int*)(d + o_fm), (double*)(d + o_pc),
-                                   (double*)(d + o_pl), d + o_in, (double*)(d + o_s3), (orbx_loop_verify_result*)(d + o_rs)))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(sim3, d + o_s3, 64 * B, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(results, d + o_rs, sizeof(orbx_loop_verify_result) * B, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  for (size_t b = 0; b < B; ++b) {                                          // only what the records count travels
-    const size_t k0 = (size_t)pairs[b].out_off, nm = (size_t)results[b].n_matches, np = (size_t)results[b].n_pairs;
-    if (nm) ORBX_HIP(h, hipMemcpyAsync(matches + k0, d + o_ma + sizeof(orbx_dmatch) * k0, sizeof(orbx_dmatch) * nm, hipMemcpyDeviceToHost, h->stream));
-    if (np) {
-      ORBX_HIP(h, hipMemcpyAsync(feature_matches + 2 * k0, d + o_fm + 8 * k0, 8 * np, hipMemcpyDeviceToHost, h->stream));
-      ORBX_HIP(h, hipMemcpyAsync(pts_current + 3 * k0, d + o_pc + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
-      ORBX_HIP(h, hipMemcpyAsync(pts_loop + 3 * k0, d + o_pl + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
-      ORBX_HIP(h, hipMemcpyAsync(inlier + k0, d + o_in + k0, np, hipMemcpyDeviceToHost, h->stream));
+  return orbx_guard(h, who, [&]() -> int {
+    if (!cam || !cfg || n_pairs < 0 || (n_pairs > 0 && (!cur_kfs || !loop_kfs || !sim3 || !results)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (n_pairs == 0) return ORBX_OK;
+    const size_t B = (size_t)n_pairs;
+    std::vector<LoopVerifyPair> pairs(B);
+    size_t N1 = 0;
+    for (size_t b = 0; b < B; ++b) {
+      const orbx_keyframe* c = cur_kfs[b];
+      const orbx_keyframe* l = loop_kfs[b];
+      if (!c || !l || c->h != h || l->h != h || N1 + (size_t)c->n > 0x7fffffffu)
+        return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad keyframe at pair %d (a keyframe belongs to the handle that made it)", who, (int)b);
+      LoopVerifyPair& p = pairs[b];
+      p.c_desc = c->d_desc; p.c_pts = c->d_points; p.c_has = c->d_has_point; p.c_node = c->has_nodes ? c->node.data() : nullptr; p.n1 = c->n;
+      p.l_kp = l->d_kp; p.l_desc = l->d_desc; p.l_pts = l->d_points; p.l_has = l->d_has_point; p.l_node = l->has_nodes ? l->node.data() : nullptr;
+      p.n2 = l->n;
+      memcpy(p.pose_c, c->pose_wc, sizeof(p.pose_c)); memcpy(p.pose_l, l->pose_wc, sizeof(p.pose_l));
+      p.out_off = (int)N1;
+      N1 += (size_t)c->n;
     }
-  }
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+    if (N1 > 0 && (!matches || !feature_matches || !pts_current || !pts_loop || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // the outputs in one device block: [sim3 | records | matches | feature matches | pts current | pts loop | inliers]
+    Carve out;
+    const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
+                 o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
+    if (int rc = orbx_reserve(h, h->ws_lv[1], out.off)) return rc;
+    uint8_t* d = (uint8_t*)h->ws_lv[1].p;
+    if (int rc = loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), (orbx_dmatch*)(d + o_ma), (int*)(d + o_fm), (double*)(d + o_pc),
+                                     (double*)(d + o_pl), d + o_in, (double*)(d + o_s3), (orbx_loop_verify_result*)(d + o_rs)))
+      return rc;
+    ORBX_HIP(h, hipMemcpyAsync(sim3, d + o_s3, 64 * B, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipMemcpyAsync(results, d + o_rs, sizeof(orbx_loop_verify_result) * B, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b) {                                          // only what the records count travels
+      const size_t k0 = (size_t)pairs[b].out_off, nm = (size_t)results[b].n_matches, np = (size_t)results[b].n_pairs;
+      if (nm) ORBX_HIP(h, hipMemcpyAsync(matches + k0, d + o_ma + sizeof(orbx_dmatch) * k0, sizeof(orbx_dmatch) * nm, hipMemcpyDeviceToHost, h->stream));
+      if (np) {
+        ORBX_HIP(h, hipMemcpyAsync(feature_matches + 2 * k0, d + o_fm + 8 * k0, 8 * np, hipMemcpyDeviceToHost, h->stream));
+        ORBX_HIP(h, hipMemcpyAsync(pts_current + 3 * k0, d + o_pc + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
+        ORBX_HIP(h, hipMemcpyAsync(pts_loop + 3 * k0, d + o_pl + 24 * k0, 24 * np, hipMemcpyDeviceToHost, h->stream));
+        ORBX_HIP(h, hipMemcpyAsync(inlier + k0, d + o_in + k0, np, hipMemcpyDeviceToHost, h->stream));
+      }
+    }
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    return ORBX_OK;
+  });
 }
 
 // phase 4 of search_in_neighbors (search_in_neighbors.rs:139-150) on resident keyframes: see include/orbx.h.  The launches are
@@ -457,16 +475,18 @@ int orbx_keyframe_refresh_map_points(orbx_handle* h, int M, const double* positi
                                      double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
   static const char* who = "orbx_keyframe_refresh_map_points";
   if (!h) return ORBX_ERR_INVALID;
-  if (M < 0 || T < 0 || (T > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  std::vector<MapPointKf> tab((size_t)T);
-  for (int t = 0; t < T; ++t) {
-    if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
-    tab[(size_t)t].desc = kfs[t]->d_desc; tab[(size_t)t].n = kfs[t]->n; tab[(size_t)t].pad_ = 0;
-    memcpy(tab[(size_t)t].centre, kfs[t]->pose_wc + 4, sizeof(tab[(size_t)t].centre));
-  }
-  if (M == 0) return ORBX_OK;
-  return mp_refresh_host_call(h, who, M, positions, obs_start, obs_kf, obs_feat, T, tab.data(), nullptr, nullptr, scale_range, mp_desc, normals,
-                              min_distance, max_distance, records);
+  return orbx_guard(h, who, [&]() -> int {
+    if (M < 0 || T < 0 || (T > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    std::vector<MapPointKf> tab((size_t)T);
+    for (int t = 0; t < T; ++t) {
+      if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
+      tab[(size_t)t].desc = kfs[t]->d_desc; tab[(size_t)t].n = kfs[t]->n; tab[(size_t)t].pad_ = 0;
+      memcpy(tab[(size_t)t].centre, kfs[t]->pose_wc + 4, sizeof(tab[(size_t)t].centre));
+    }
+    if (M == 0) return ORBX_OK;
+    return mp_refresh_host_call(h, who, M, positions, obs_start, obs_kf, obs_feat, T, tab.data(), nullptr, nullptr, scale_range, mp_desc, normals,
+                                min_distance, max_distance, records);
+  });
 }
 
 }  // extern "C"

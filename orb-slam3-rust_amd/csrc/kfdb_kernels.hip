@@ -470,11 +470,13 @@ void orbx_default_loop_detector_config(orbx_loop_detector_config* cfg) {
 
 int orbx_kfdb_create(orbx_handle* h, orbx_kfdb** out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!out) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_create: bad argument");
-  orbx_kfdb* db = new orbx_kfdb();
-  db->h = h;
-  *out = db;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_create", [&]() -> int {
+    if (!out) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_create: bad argument");
+    orbx_kfdb* db = new orbx_kfdb();
+    db->h = h;
+    *out = db;
+    return ORBX_OK;
+  });
 }
 
 void orbx_kfdb_destroy(orbx_kfdb* db) {
@@ -489,73 +491,81 @@ void orbx_kfdb_destroy(orbx_kfdb* db) {
 int orbx_kfdb_add(orbx_kfdb* db, uint64_t keyframe_id, int map_index, int is_bad, const uint32_t* word, const double* weight, int n) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if (n < 0 || n > KFDB_MAX_WORDS || map_index < 0 || (n > 0 && (!word || !weight)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add: bad argument (at most %d words, map index >= 0)", KFDB_MAX_WORDS);
-  if (!ascending(word, n)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add: word ids must strictly ascend");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t bytes = pad32(4 * (size_t)n) + pad32(8 * (size_t)n);
-  if (int rc = kfdb_grow(db, bytes)) return rc;
-  auto it = db->slot_of.find(keyframe_id);
-  if (it != db->slot_of.end()) kfdb_tombstone(db, it->second);        // HashMap::insert replaces (keyframe_db.rs:45-47)
-  HostEntry e;
-  e.id = keyframe_id; e.off = db->arena_used; e.reserved = bytes; e.n = e.cap = n; e.map = map_index;
-  e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
-  const int slot = (int)db->slots.size();
-  if (n > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(db->d_arena + e.off, word, 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(db->d_arena + e.off + pad32(4 * (size_t)n), weight, 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  }
-  hipLaunchKernelGGL(kfdb_set_entry_kernel, dim3(1), dim3(1), 0, h->stream, db->d_table, slot, KfdbEntry{e.id, e.off, n, map_index, e.flags, 0});
-  ORBX_HIP(h, hipGetLastError());
-  db->slots.push_back(e); db->slot_of[keyframe_id] = slot; db->arena_used += bytes;
-  if (n > 0) ORBX_HIP(h, hipStreamSynchronize(h->stream));            // the caller's buffers are free on return
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_add", [&]() -> int {
+    if (n < 0 || n > KFDB_MAX_WORDS || map_index < 0 || (n > 0 && (!word || !weight)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add: bad argument (at most %d words, map index >= 0)", KFDB_MAX_WORDS);
+    if (!ascending(word, n)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add: word ids must strictly ascend");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t bytes = pad32(4 * (size_t)n) + pad32(8 * (size_t)n);
+    if (int rc = kfdb_grow(db, bytes)) return rc;
+    auto it = db->slot_of.find(keyframe_id);
+    if (it != db->slot_of.end()) kfdb_tombstone(db, it->second);        // HashMap::insert replaces (keyframe_db.rs:45-47)
+    HostEntry e;
+    e.id = keyframe_id; e.off = db->arena_used; e.reserved = bytes; e.n = e.cap = n; e.map = map_index;
+    e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
+    const int slot = (int)db->slots.size();
+    if (n > 0) {
+      ORBX_HIP(h, hipMemcpyAsync(db->d_arena + e.off, word, 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+      ORBX_HIP(h, hipMemcpyAsync(db->d_arena + e.off + pad32(4 * (size_t)n), weight, 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(kfdb_set_entry_kernel, dim3(1), dim3(1), 0, h->stream, db->d_table, slot, KfdbEntry{e.id, e.off, n, map_index, e.flags, 0});
+    ORBX_HIP(h, hipGetLastError());
+    db->slots.push_back(e); db->slot_of[keyframe_id] = slot; db->arena_used += bytes;
+    if (n > 0) ORBX_HIP(h, hipStreamSynchronize(h->stream));            // the caller's buffers are free on return
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_add_device(orbx_kfdb* db, uint64_t keyframe_id, int map_index, int is_bad, const uint32_t* d_word, const double* d_weight,
                          const int* d_count, int max_n) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if (max_n < 0 || max_n > KFDB_MAX_WORDS || map_index < 0 || !d_count || (max_n > 0 && (!d_word || !d_weight)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add_device: bad argument (at most %d words, map index >= 0)", KFDB_MAX_WORDS);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t bytes = pad32(4 * (size_t)max_n) + pad32(8 * (size_t)max_n);
-  if (int rc = kfdb_grow(db, bytes)) return rc;
-  auto it = db->slot_of.find(keyframe_id);
-  if (it != db->slot_of.end()) kfdb_tombstone(db, it->second);
-  HostEntry e;
-  e.id = keyframe_id; e.off = db->arena_used; e.reserved = bytes; e.n = -1; e.cap = max_n; e.map = map_index;
-  e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
-  const int slot = (int)db->slots.size();
-  hipLaunchKernelGGL(kfdb_add_device_kernel, dim3(1), dim3(KFDB_THREADS), 0, h->stream, db->d_table, slot, KfdbEntry{e.id, e.off, 0, map_index, e.flags, 0},
-                     db->d_arena, d_word, d_weight, d_count, max_n);
-  ORBX_HIP(h, hipGetLastError());
-  db->slots.push_back(e); db->slot_of[keyframe_id] = slot; db->arena_used += bytes;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_add_device", [&]() -> int {
+    if (max_n < 0 || max_n > KFDB_MAX_WORDS || map_index < 0 || !d_count || (max_n > 0 && (!d_word || !d_weight)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_add_device: bad argument (at most %d words, map index >= 0)", KFDB_MAX_WORDS);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t bytes = pad32(4 * (size_t)max_n) + pad32(8 * (size_t)max_n);
+    if (int rc = kfdb_grow(db, bytes)) return rc;
+    auto it = db->slot_of.find(keyframe_id);
+    if (it != db->slot_of.end()) kfdb_tombstone(db, it->second);
+    HostEntry e;
+    e.id = keyframe_id; e.off = db->arena_used; e.reserved = bytes; e.n = -1; e.cap = max_n; e.map = map_index;
+    e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
+    const int slot = (int)db->slots.size();
+    hipLaunchKernelGGL(kfdb_add_device_kernel, dim3(1), dim3(KFDB_THREADS), 0, h->stream, db->d_table, slot, KfdbEntry{e.id, e.off, 0, map_index, e.flags, 0},
+                       db->d_arena, d_word, d_weight, d_count, max_n);
+    ORBX_HIP(h, hipGetLastError());
+    db->slots.push_back(e); db->slot_of[keyframe_id] = slot; db->arena_used += bytes;
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_erase(orbx_kfdb* db, uint64_t keyframe_id) {
   if (!db) return ORBX_ERR_INVALID;
-  auto it = db->slot_of.find(keyframe_id);
-  if (it == db->slot_of.end()) return ORBX_OK;                        // HashMap::remove of an absent key (keyframe_db.rs:50-52)
-  orbx_handle* h = db->h;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  kfdb_tombstone(db, it->second);
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
+  return orbx_guard(db->h, "orbx_kfdb_erase", [&]() -> int {
+    auto it = db->slot_of.find(keyframe_id);
+    if (it == db->slot_of.end()) return ORBX_OK;                        // HashMap::remove of an absent key (keyframe_db.rs:50-52)
+    orbx_handle* h = db->h;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    kfdb_tombstone(db, it->second);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_set_bad(orbx_kfdb* db, uint64_t keyframe_id, int is_bad) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  auto it = db->slot_of.find(keyframe_id);
-  if (it == db->slot_of.end()) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_set_bad: no such keyframe");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  HostEntry& e = db->slots[(size_t)it->second];
-  e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
-  hipLaunchKernelGGL(kfdb_set_flags_kernel, dim3(1), dim3(1), 0, h->stream, db->d_table, it->second, e.flags);
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_set_bad", [&]() -> int {
+    auto it = db->slot_of.find(keyframe_id);
+    if (it == db->slot_of.end()) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_set_bad: no such keyframe");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    HostEntry& e = db->slots[(size_t)it->second];
+    e.flags = KFDB_LIVE | (is_bad ? KFDB_BAD : 0u);
+    hipLaunchKernelGGL(kfdb_set_flags_kernel, dim3(1), dim3(1), 0, h->stream, db->d_table, it->second, e.flags);
+    ORBX_HIP(h, hipGetLastError());
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_size(const orbx_kfdb* db, int* n_entries, int* n_slots) {
@@ -567,90 +577,96 @@ int orbx_kfdb_size(const orbx_kfdb* db, int* n_entries, int* n_slots) {
 
 int orbx_kfdb_compact(orbx_kfdb* db) {
   if (!db) return ORBX_ERR_INVALID;
-  return kfdb_compact(db);
+  return orbx_guard(db->h, "orbx_kfdb_compact", [&] { return kfdb_compact(db); });
 }
 
 int orbx_kfdb_download(orbx_kfdb* db, uint64_t keyframe_id, uint32_t* word, double* weight, int cap, int* n, int* map_index, int* is_bad) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if (!n || cap < 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: bad argument");
-  auto it = db->slot_of.find(keyframe_id);
-  if (it == db->slot_of.end()) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: no such keyframe");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  kfdb_free_retired(db);
-  HostEntry& e = db->slots[(size_t)it->second];
-  KfdbEntry t;
-  ORBX_HIP(h, hipMemcpy(&t, db->d_table + it->second, sizeof(t), hipMemcpyDeviceToHost));
-  e.n = t.n;
-  *n = t.n;
-  if (map_index) *map_index = e.map;
-  if (is_bad) *is_bad = (e.flags & KFDB_BAD) ? 1 : 0;
-  if (t.n > cap) return orbx_fail(h, ORBX_ERR_CAPACITY, "orbx_kfdb_download: %d words, capacity %d", t.n, cap);
-  if (t.n > 0 && (!word || !weight)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: bad argument");
-  if (t.n > 0) {
-    ORBX_HIP(h, hipMemcpy(word, db->d_arena + t.off, 4 * (size_t)t.n, hipMemcpyDeviceToHost));
-    ORBX_HIP(h, hipMemcpy(weight, db->d_arena + t.off + pad32(4 * (size_t)t.n), 8 * (size_t)t.n, hipMemcpyDeviceToHost));
-  }
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_download", [&]() -> int {
+    if (!n || cap < 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: bad argument");
+    auto it = db->slot_of.find(keyframe_id);
+    if (it == db->slot_of.end()) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: no such keyframe");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    kfdb_free_retired(db);
+    HostEntry& e = db->slots[(size_t)it->second];
+    KfdbEntry t;
+    ORBX_HIP(h, hipMemcpy(&t, db->d_table + it->second, sizeof(t), hipMemcpyDeviceToHost));
+    e.n = t.n;
+    *n = t.n;
+    if (map_index) *map_index = e.map;
+    if (is_bad) *is_bad = (e.flags & KFDB_BAD) ? 1 : 0;
+    if (t.n > cap) return orbx_fail(h, ORBX_ERR_CAPACITY, "orbx_kfdb_download: %d words, capacity %d", t.n, cap);
+    if (t.n > 0 && (!word || !weight)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_download: bad argument");
+    if (t.n > 0) {
+      ORBX_HIP(h, hipMemcpy(word, db->d_arena + t.off, 4 * (size_t)t.n, hipMemcpyDeviceToHost));
+      ORBX_HIP(h, hipMemcpy(weight, db->d_arena + t.off + pad32(4 * (size_t)t.n), 8 * (size_t)t.n, hipMemcpyDeviceToHost));
+    }
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_score(orbx_kfdb* db, int scoring, const uint32_t* q_word, const double* q_weight, int nq, uint64_t* ids, double* scores, int cap,
                     int* n_out) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if ((scoring != ORBX_KFDB_SCORE_L1 && scoring != ORBX_KFDB_SCORE_DOT) || nq < 0 || nq > KFDB_MAX_WORDS || (nq > 0 && (!q_word || !q_weight)) || !n_out ||
-      cap < 0 || (cap > 0 && (!ids || !scores)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_score: bad argument");
-  if (!ascending(q_word, nq)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_score: word ids must strictly ascend");
-  const int n = (int)db->slot_of.size();
-  *n_out = n;
-  if (n > cap) return orbx_fail(h, ORBX_ERR_CAPACITY, "orbx_kfdb_score: %d entries, capacity %d", n, cap);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = kfdb_before_query(db)) return rc;
-  std::vector<QueryHost> qs(1);
-  qs[0].w = q_word; qs[0].v = q_weight; qs[0].n = nq;
-  Launch L;
-  if (int rc = kfdb_launch(db, scoring, qs, -1, nullptr, -1, L)) return rc;
-  std::vector<double> all(db->slots.size());
-  if (!all.empty()) ORBX_HIP(h, hipMemcpyAsync(all.data(), L.d_scores, 8 * all.size(), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  kfdb_free_retired(db);
-  std::vector<std::pair<unsigned long long, int>> order;               // live entries in ascending keyframe id
-  order.reserve((size_t)n);
-  for (const auto& kv : db->slot_of) order.emplace_back(kv.first, kv.second);
-  std::sort(order.begin(), order.end());
-  for (int i = 0; i < n; ++i) { ids[i] = order[(size_t)i].first; scores[i] = all[(size_t)order[(size_t)i].second]; }
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_score", [&]() -> int {
+    if ((scoring != ORBX_KFDB_SCORE_L1 && scoring != ORBX_KFDB_SCORE_DOT) || nq < 0 || nq > KFDB_MAX_WORDS || (nq > 0 && (!q_word || !q_weight)) || !n_out ||
+        cap < 0 || (cap > 0 && (!ids || !scores)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_score: bad argument");
+    if (!ascending(q_word, nq)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_score: word ids must strictly ascend");
+    const int n = (int)db->slot_of.size();
+    *n_out = n;
+    if (n > cap) return orbx_fail(h, ORBX_ERR_CAPACITY, "orbx_kfdb_score: %d entries, capacity %d", n, cap);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = kfdb_before_query(db)) return rc;
+    std::vector<QueryHost> qs(1);
+    qs[0].w = q_word; qs[0].v = q_weight; qs[0].n = nq;
+    Launch L;
+    if (int rc = kfdb_launch(db, scoring, qs, -1, nullptr, -1, L)) return rc;
+    std::vector<double> all(db->slots.size());
+    if (!all.empty()) ORBX_HIP(h, hipMemcpyAsync(all.data(), L.d_scores, 8 * all.size(), hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    kfdb_free_retired(db);
+    std::vector<std::pair<unsigned long long, int>> order;               // live entries in ascending keyframe id
+    order.reserve((size_t)n);
+    for (const auto& kv : db->slot_of) order.emplace_back(kv.first, kv.second);
+    std::sort(order.begin(), order.end());
+    for (int i = 0; i < n; ++i) { ids[i] = order[(size_t)i].first; scores[i] = all[(size_t)order[(size_t)i].second]; }
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_detect_candidates(orbx_kfdb* db, const uint32_t* q_word, const double* q_weight, int nq, int exclude_map, int max_results,
                                 uint64_t* ids, int* map_indices, double* scores, int* n_out) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if (nq < 0 || nq > KFDB_MAX_WORDS || (nq > 0 && (!q_word || !q_weight)) || !n_out || max_results < 0 || (max_results > 0 && (!ids || !scores)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_candidates: bad argument");
-  if (!ascending(q_word, nq)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_candidates: word ids must strictly ascend");
-  *n_out = 0;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = kfdb_before_query(db)) return rc;
-  std::vector<QueryHost> qs(1);
-  qs[0].w = q_word; qs[0].v = q_weight; qs[0].n = nq;
-  Launch L;
-  if (int rc = kfdb_launch(db, ORBX_KFDB_SCORE_DOT, qs, 1, nullptr, exclude_map < 0 ? -1 : exclude_map, L)) return rc;
-  int count = 0;
-  ORBX_HIP(h, hipMemcpyAsync(&count, L.d_counts, 4, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  kfdb_free_retired(db);
-  std::vector<KfdbCand> c;
-  if (int rc = kfdb_fetch_sorted(db, L, 0, count, c)) return rc;
-  const int m = std::min(count, max_results);                          // cands.truncate(max_results), keyframe_db.rs:92
-  for (int i = 0; i < m; ++i) {
-    ids[i] = c[(size_t)i].id; scores[i] = c[(size_t)i].score;
-    if (map_indices) map_indices[i] = db->slots[(size_t)db->slot_of[c[(size_t)i].id]].map;
-  }
-  *n_out = m;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_kfdb_detect_candidates", [&]() -> int {
+    if (nq < 0 || nq > KFDB_MAX_WORDS || (nq > 0 && (!q_word || !q_weight)) || !n_out || max_results < 0 || (max_results > 0 && (!ids || !scores)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_candidates: bad argument");
+    if (!ascending(q_word, nq)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_candidates: word ids must strictly ascend");
+    *n_out = 0;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = kfdb_before_query(db)) return rc;
+    std::vector<QueryHost> qs(1);
+    qs[0].w = q_word; qs[0].v = q_weight; qs[0].n = nq;
+    Launch L;
+    if (int rc = kfdb_launch(db, ORBX_KFDB_SCORE_DOT, qs, 1, nullptr, exclude_map < 0 ? -1 : exclude_map, L)) return rc;
+    int count = 0;
+    ORBX_HIP(h, hipMemcpyAsync(&count, L.d_counts, 4, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    kfdb_free_retired(db);
+    std::vector<KfdbCand> c;
+    if (int rc = kfdb_fetch_sorted(db, L, 0, count, c)) return rc;
+    const int m = std::min(count, max_results);                          // cands.truncate(max_results), keyframe_db.rs:92
+    for (int i = 0; i < m; ++i) {
+      ids[i] = c[(size_t)i].id; scores[i] = c[(size_t)i].score;
+      if (map_indices) map_indices[i] = db->slots[(size_t)db->slot_of[c[(size_t)i].id]].map;
+    }
+    *n_out = m;
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_detect_loop_candidates_batch(orbx_kfdb* db, const orbx_loop_detector_config* cfg, int scoring, int n_queries, const uint64_t* current_ids,
@@ -658,55 +674,57 @@ int orbx_kfdb_detect_loop_candidates_batch(orbx_kfdb* db, const orbx_loop_detect
                                            int* counts) {
   if (!db) return ORBX_ERR_INVALID;
   orbx_handle* h = db->h;
-  if (!cfg_ok(cfg) || (scoring != ORBX_KFDB_SCORE_L1 && scoring != ORBX_KFDB_SCORE_DOT) || n_queries < 0 || cap < 0 ||
-      (n_queries > 0 && (!current_ids || !connected_offsets || !counts)) || (n_queries > 0 && cap > 0 && (!ids || !scores)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: bad argument");
-  if (n_queries == 0) return ORBX_OK;
-  if (connected_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: connected_offsets must ascend from 0");
-  for (int q = 0; q < n_queries; ++q)
-    if (connected_offsets[q + 1] < connected_offsets[q])
-      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: connected_offsets must ascend from 0");
-  if (connected_offsets[n_queries] > 0 && !connected) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: bad argument");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = kfdb_before_query(db)) return rc;
-  // the host's part: which queries exist, and which connected ids the threshold walk scores (detector.rs:276-290, in the given order)
-  std::vector<QueryHost> qs;
-  std::vector<int> launch_of((size_t)n_queries, -1);
-  for (int q = 0; q < n_queries; ++q) {
-    counts[q] = 0;
-    auto it = db->slot_of.find(current_ids[q]);
-    if (it == db->slot_of.end()) continue;                             // :195-198: unknown keyframe -> no candidates
-    QueryHost s;
-    s.slot = it->second; s.cur_id = current_ids[q]; s.map = db->slots[(size_t)s.slot].map;
-    const uint64_t* cn = connected + connected_offsets[q];
-    const int nc = connected_offsets[q + 1] - connected_offsets[q];
-    for (int i = 0; i < nc && (int)s.thr_slots.size() < cfg->max_covisibles_to_check; ++i) {                          // :277-279
-      auto ct = db->slot_of.find(cn[i]);
-      if (ct == db->slot_of.end() || db->slots[(size_t)ct->second].map != s.map) continue;                            // :281 map.get_keyframe
-      s.thr_slots.push_back(ct->second);
+  return orbx_guard(h, "orbx_kfdb_detect_loop_candidates_batch", [&]() -> int {
+    if (!cfg_ok(cfg) || (scoring != ORBX_KFDB_SCORE_L1 && scoring != ORBX_KFDB_SCORE_DOT) || n_queries < 0 || cap < 0 ||
+        (n_queries > 0 && (!current_ids || !connected_offsets || !counts)) || (n_queries > 0 && cap > 0 && (!ids || !scores)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: bad argument");
+    if (n_queries == 0) return ORBX_OK;
+    if (connected_offsets[0] != 0) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: connected_offsets must ascend from 0");
+    for (int q = 0; q < n_queries; ++q)
+      if (connected_offsets[q + 1] < connected_offsets[q])
+        return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: connected_offsets must ascend from 0");
+    if (connected_offsets[n_queries] > 0 && !connected) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_kfdb_detect_loop_candidates: bad argument");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = kfdb_before_query(db)) return rc;
+    // the host's part: which queries exist, and which connected ids the threshold walk scores (detector.rs:276-290, in the given order)
+    std::vector<QueryHost> qs;
+    std::vector<int> launch_of((size_t)n_queries, -1);
+    for (int q = 0; q < n_queries; ++q) {
+      counts[q] = 0;
+      auto it = db->slot_of.find(current_ids[q]);
+      if (it == db->slot_of.end()) continue;                             // :195-198: unknown keyframe -> no candidates
+      QueryHost s;
+      s.slot = it->second; s.cur_id = current_ids[q]; s.map = db->slots[(size_t)s.slot].map;
+      const uint64_t* cn = connected + connected_offsets[q];
+      const int nc = connected_offsets[q + 1] - connected_offsets[q];
+      for (int i = 0; i < nc && (int)s.thr_slots.size() < cfg->max_covisibles_to_check; ++i) {                          // :277-279
+        auto ct = db->slot_of.find(cn[i]);
+        if (ct == db->slot_of.end() || db->slots[(size_t)ct->second].map != s.map) continue;                            // :281 map.get_keyframe
+        s.thr_slots.push_back(ct->second);
+      }
+      s.conn.assign(cn, cn + nc);
+      std::sort(s.conn.begin(), s.conn.end());
+      launch_of[(size_t)q] = (int)qs.size();
+      qs.push_back(std::move(s));
     }
-    s.conn.assign(cn, cn + nc);
-    std::sort(s.conn.begin(), s.conn.end());
-    launch_of[(size_t)q] = (int)qs.size();
-    qs.push_back(std::move(s));
-  }
-  if (qs.empty()) return ORBX_OK;
-  Launch L;
-  if (int rc = kfdb_launch(db, scoring, qs, 0, cfg, -1, L)) return rc;
-  std::vector<int> cnt(qs.size());
-  ORBX_HIP(h, hipMemcpyAsync(cnt.data(), L.d_counts, 4 * cnt.size(), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  kfdb_free_retired(db);
-  std::vector<KfdbCand> c;
-  for (int q = 0; q < n_queries; ++q) {
-    const int li = launch_of[(size_t)q];
-    if (li < 0) continue;
-    if (int rc = kfdb_fetch_sorted(db, L, li, cnt[(size_t)li], c)) return rc;
-    counts[q] = cnt[(size_t)li];
-    const int m = std::min(cnt[(size_t)li], cap);
-    for (int i = 0; i < m; ++i) { ids[(size_t)q * cap + i] = c[(size_t)i].id; scores[(size_t)q * cap + i] = c[(size_t)i].score; }
-  }
-  return ORBX_OK;
+    if (qs.empty()) return ORBX_OK;
+    Launch L;
+    if (int rc = kfdb_launch(db, scoring, qs, 0, cfg, -1, L)) return rc;
+    std::vector<int> cnt(qs.size());
+    ORBX_HIP(h, hipMemcpyAsync(cnt.data(), L.d_counts, 4 * cnt.size(), hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    kfdb_free_retired(db);
+    std::vector<KfdbCand> c;
+    for (int q = 0; q < n_queries; ++q) {
+      const int li = launch_of[(size_t)q];
+      if (li < 0) continue;
+      if (int rc = kfdb_fetch_sorted(db, L, li, cnt[(size_t)li], c)) return rc;
+      counts[q] = cnt[(size_t)li];
+      const int m = std::min(cnt[(size_t)li], cap);
+      for (int i = 0; i < m; ++i) { ids[(size_t)q * cap + i] = c[(size_t)i].id; scores[(size_t)q * cap + i] = c[(size_t)i].score; }
+    }
+    return ORBX_OK;
+  });
 }
 
 int orbx_kfdb_detect_loop_candidates(orbx_kfdb* db, const orbx_loop_detector_config* cfg, int scoring, uint64_t current_id, const uint64_t* connected,

@@ -792,49 +792,53 @@ int orbx_sim3_ransac_batch_device(orbx_handle* h, const orbx_sim3_config* cfg, i
                                   orbx_sim3_result* d_results) {
   static const char* who = "orbx_sim3_ransac_batch_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = s3_check_config(h, cfg, who)) return rc;
-  if (n_problems < 0 || max_n < 0 || (n_problems > 0 && (!d_offsets || !d_sim3 || !d_results)) || (max_n > 0 && (!d_pts1 || !d_pts2 || !d_inlier)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_problems == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve(h, h->ws_lv[0], s3_ws(n_problems, cfg->max_iterations).bytes)) return rc;
-  S3Args S{};
-  S.cfg = *cfg; S.max_n = max_n; S.stride = 1; S.start = d_offsets; S.count = nullptr;
-  S.pts1 = d_pts1; S.pts2 = d_pts2; S.sim3 = d_sim3; S.inl = d_inlier; S.results = d_results;
-  orbx_prof_begin_call(h);
-  return s3_launch(h, S, n_problems, (uint8_t*)h->ws_lv[0].p);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = s3_check_config(h, cfg, who)) return rc;
+    if (n_problems < 0 || max_n < 0 || (n_problems > 0 && (!d_offsets || !d_sim3 || !d_results)) || (max_n > 0 && (!d_pts1 || !d_pts2 || !d_inlier)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (n_problems == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = orbx_reserve(h, h->ws_lv[0], s3_ws(n_problems, cfg->max_iterations).bytes)) return rc;
+    S3Args S{};
+    S.cfg = *cfg; S.max_n = max_n; S.stride = 1; S.start = d_offsets; S.count = nullptr;
+    S.pts1 = d_pts1; S.pts2 = d_pts2; S.sim3 = d_sim3; S.inl = d_inlier; S.results = d_results;
+    orbx_prof_begin_call(h);
+    return s3_launch(h, S, n_problems, (uint8_t*)h->ws_lv[0].p);
+  });
 }
 
 int orbx_sim3_ransac_batch(orbx_handle* h, const orbx_sim3_config* cfg, int n_problems, const int* offsets, const double* pts1,
                            const double* pts2, double* sim3, uint8_t* inlier, orbx_sim3_result* results) {
   static const char* who = "orbx_sim3_ransac_batch";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = s3_check_config(h, cfg, who)) return rc;
-  if (n_problems < 0 || (n_problems > 0 && (!offsets || !sim3 || !results))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_problems == 0) return ORBX_OK;
-  int max_n = 0;
-  if (int rc = orbx_check_offsets(h, who, "offsets", "problem", n_problems, offsets, &max_n)) return rc;
-  const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
-  if (N > 0 && (!pts1 || !pts2 || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // one blob each way: [offsets | pts1 | pts2] up, [sim3 | results | inliers] down
-  Carve in, out;
-  const size_t i_of = in.take(4 * (P + 1)), i_p1 = in.take(24 * N), i_p2 = in.take(24 * N);
-  const size_t o_s3 = out.take(64 * P), o_rs = out.take(sizeof(orbx_sim3_result) * P), o_in = out.take(N);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[3], in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
-  std::memcpy(hi + i_of, offsets, 4 * (P + 1));
-  if (N) { std::memcpy(hi + i_p1, pts1, 24 * N); std::memcpy(hi + i_p2, pts2, 24 * N); }
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  if (int rc = orbx_sim3_ransac_batch_device(h, cfg, n_problems, max_n, (const int*)(di + i_of), (const double*)(di + i_p1),
-                                             (const double*)(di + i_p2), (double*)(dout + o_s3), dout + o_in, (orbx_sim3_result*)(dout + o_rs)))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(sim3, ho + o_s3, 64 * P);
-  std::memcpy(results, ho + o_rs, sizeof(orbx_sim3_result) * P);
-  if (N) std::memcpy(inlier, ho + o_in, N);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = s3_check_config(h, cfg, who)) return rc;
+    if (n_problems < 0 || (n_problems > 0 && (!offsets || !sim3 || !results))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (n_problems == 0) return ORBX_OK;
+    int max_n = 0;
+    if (int rc = orbx_check_offsets(h, who, "offsets", "problem", n_problems, offsets, &max_n)) return rc;
+    const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
+    if (N > 0 && (!pts1 || !pts2 || !inlier)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // one blob each way: [offsets | pts1 | pts2] up, [sim3 | results | inliers] down
+    Carve in, out;
+    const size_t i_of = in.take(4 * (P + 1)), i_p1 = in.take(24 * N), i_p2 = in.take(24 * N);
+    const size_t o_s3 = out.take(64 * P), o_rs = out.take(sizeof(orbx_sim3_result) * P), o_in = out.take(N);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[3], in.off, out.off, c)) return rc;
+    uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+    std::memcpy(hi + i_of, offsets, 4 * (P + 1));
+    if (N) { std::memcpy(hi + i_p1, pts1, 24 * N); std::memcpy(hi + i_p2, pts2, 24 * N); }
+    if (int rc = orbx_host_call_upload(h, c)) return rc;
+    if (int rc = orbx_sim3_ransac_batch_device(h, cfg, n_problems, max_n, (const int*)(di + i_of), (const double*)(di + i_p1),
+                                               (const double*)(di + i_p2), (double*)(dout + o_s3), dout + o_in, (orbx_sim3_result*)(dout + o_rs)))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(sim3, ho + o_s3, 64 * P);
+    std::memcpy(results, ho + o_rs, sizeof(orbx_sim3_result) * P);
+    if (N) std::memcpy(inlier, ho + o_in, N);
+    return ORBX_OK;
+  });
 }
 
 int orbx_verify_loop_candidates_device(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
@@ -847,28 +851,30 @@ int orbx_verify_loop_candidates_device(orbx_handle* h, const orbx_camera* cam, c
                                        orbx_loop_verify_result* d_results) {
   static const char* who = "orbx_verify_loop_candidates_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = lv_check_config(h, cfg, who)) return rc;
-  if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_pairs == 0) return ORBX_OK;
-  if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
-  if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
-  if (!cur_poses_wc || !loop_poses_wc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  std::vector<LoopVerifyPair> pairs((size_t)n_pairs);
-  for (int b = 0; b < n_pairs; ++b) {
-    LoopVerifyPair& p = pairs[(size_t)b];
-    const size_t c0 = (size_t)cur_offsets[b], l0 = (size_t)loop_offsets[b];
-    p.c_desc = d_cur_desc ? d_cur_desc + 32 * c0 : nullptr; p.c_pts = d_cur_points_cam ? d_cur_points_cam + 3 * c0 : nullptr;
-    p.c_has = d_cur_has_point ? d_cur_has_point + c0 : nullptr; p.c_node = cur_node ? cur_node + c0 : nullptr;
-    p.n1 = cur_offsets[b + 1] - cur_offsets[b];
-    p.l_kp = d_loop_kp ? d_loop_kp + l0 : nullptr; p.l_desc = d_loop_desc ? d_loop_desc + 32 * l0 : nullptr;
-    p.l_pts = d_loop_points_cam ? d_loop_points_cam + 3 * l0 : nullptr; p.l_has = d_loop_has_point ? d_loop_has_point + l0 : nullptr;
-    p.l_node = loop_node ? loop_node + l0 : nullptr;
-    p.n2 = loop_offsets[b + 1] - loop_offsets[b];
-    std::memcpy(p.pose_c, cur_poses_wc + 7 * (size_t)b, 56); std::memcpy(p.pose_l, loop_poses_wc + 7 * (size_t)b, 56);
-    p.out_off = cur_offsets[b];
-  }
-  return loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), d_matches, d_feature_matches, d_pts_current, d_pts_loop, d_inlier,
-                             d_sim3, d_results);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = lv_check_config(h, cfg, who)) return rc;
+    if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (n_pairs == 0) return ORBX_OK;
+    if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
+    if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
+    if (!cur_poses_wc || !loop_poses_wc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    std::vector<LoopVerifyPair> pairs((size_t)n_pairs);
+    for (int b = 0; b < n_pairs; ++b) {
+      LoopVerifyPair& p = pairs[(size_t)b];
+      const size_t c0 = (size_t)cur_offsets[b], l0 = (size_t)loop_offsets[b];
+      p.c_desc = d_cur_desc ? d_cur_desc + 32 * c0 : nullptr; p.c_pts = d_cur_points_cam ? d_cur_points_cam + 3 * c0 : nullptr;
+      p.c_has = d_cur_has_point ? d_cur_has_point + c0 : nullptr; p.c_node = cur_node ? cur_node + c0 : nullptr;
+      p.n1 = cur_offsets[b + 1] - cur_offsets[b];
+      p.l_kp = d_loop_kp ? d_loop_kp + l0 : nullptr; p.l_desc = d_loop_desc ? d_loop_desc + 32 * l0 : nullptr;
+      p.l_pts = d_loop_points_cam ? d_loop_points_cam + 3 * l0 : nullptr; p.l_has = d_loop_has_point ? d_loop_has_point + l0 : nullptr;
+      p.l_node = loop_node ? loop_node + l0 : nullptr;
+      p.n2 = loop_offsets[b + 1] - loop_offsets[b];
+      std::memcpy(p.pose_c, cur_poses_wc + 7 * (size_t)b, 56); std::memcpy(p.pose_l, loop_poses_wc + 7 * (size_t)b, 56);
+      p.out_off = cur_offsets[b];
+    }
+    return loop_verify_enqueue(h, who, cam, cfg, n_pairs, pairs.data(), d_matches, d_feature_matches, d_pts_current, d_pts_loop, d_inlier,
+                               d_sim3, d_results);
+  });
 }
 
 int orbx_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const orbx_loop_verify_config* cfg, int n_pairs,
@@ -880,52 +886,54 @@ int orbx_verify_loop_candidates(orbx_handle* h, const orbx_camera* cam, const or
                                 orbx_loop_verify_result* results) {
   static const char* who = "orbx_verify_loop_candidates";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = lv_check_config(h, cfg, who)) return rc;
-  if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_pairs == 0) return ORBX_OK;
-  if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
-  if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
-  const size_t B = (size_t)n_pairs, N1 = (size_t)cur_offsets[B], N2 = (size_t)loop_offsets[B];
-  if (!cur_poses_wc || !loop_poses_wc || !sim3 || !results || (N1 > 0 && (!cur_desc || !cur_points_cam || !cur_has_point || !matches ||
-      !feature_matches || !pts_current || !pts_loop || !inlier)) || (N2 > 0 && (!loop_kp || !loop_desc || !loop_points_cam || !loop_has_point)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // one blob each way: [cur desc | cur points | cur has | loop kp | loop desc | loop points | loop has] up,
-  // [sim3 | records | matches | feature matches | pts current | pts loop | inliers] down
-  Carve in, out;
-  const size_t i_cd = in.take(32 * N1), i_cp = in.take(24 * N1), i_ch = in.take(N1), i_lk = in.take(sizeof(orbx_keypoint) * N2), i_ld = in.take(32 * N2),
-               i_lp = in.take(24 * N2), i_lh = in.take(N2);
-  const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
-               o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[1], in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
-  if (N1) { std::memcpy(hi + i_cd, cur_desc, 32 * N1); std::memcpy(hi + i_cp, cur_points_cam, 24 * N1); std::memcpy(hi + i_ch, cur_has_point, N1); }
-  if (N2) {
-    std::memcpy(hi + i_lk, loop_kp, sizeof(orbx_keypoint) * N2); std::memcpy(hi + i_ld, loop_desc, 32 * N2);
-    std::memcpy(hi + i_lp, loop_points_cam, 24 * N2); std::memcpy(hi + i_lh, loop_has_point, N2);
-  }
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  if (int rc = orbx_verify_loop_candidates_device(h, cam, cfg, n_pairs, di + i_cd, (const double*)(di + i_cp), di + i_ch, cur_node, cur_offsets,
-                                                  cur_poses_wc, (const orbx_keypoint*)(di + i_lk), di + i_ld, (const double*)(di + i_lp), di + i_lh,
-                                                  loop_node, loop_offsets, loop_poses_wc, (orbx_dmatch*)(dout + o_ma), (int*)(dout + o_fm),
-                                                  (double*)(dout + o_pc), (double*)(dout + o_pl), dout + o_in, (double*)(dout + o_s3),
-                                                  (orbx_loop_verify_result*)(dout + o_rs)))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(sim3, ho + o_s3, 64 * B);
-  std::memcpy(results, ho + o_rs, sizeof(orbx_loop_verify_result) * B);
-  for (size_t b = 0; b < B; ++b) {
-    const size_t k0 = (size_t)cur_offsets[b], nm = (size_t)results[b].n_matches, np = (size_t)results[b].n_pairs;
-    if (nm) std::memcpy(matches + k0, ho + o_ma + sizeof(orbx_dmatch) * k0, sizeof(orbx_dmatch) * nm);
-    if (np) {
-      std::memcpy(feature_matches + 2 * k0, ho + o_fm + 8 * k0, 8 * np);
-      std::memcpy(pts_current + 3 * k0, ho + o_pc + 24 * k0, 24 * np);
-      std::memcpy(pts_loop + 3 * k0, ho + o_pl + 24 * k0, 24 * np);
-      std::memcpy(inlier + k0, ho + o_in + k0, np);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = lv_check_config(h, cfg, who)) return rc;
+    if (!cam || n_pairs < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (n_pairs == 0) return ORBX_OK;
+    if (int rc = orbx_check_offsets(h, who, "cur_offsets", "pair", n_pairs, cur_offsets, nullptr, LV_MAX_FEAT)) return rc;
+    if (int rc = orbx_check_offsets(h, who, "loop_offsets", "pair", n_pairs, loop_offsets, nullptr, LV_MAX_FEAT)) return rc;
+    const size_t B = (size_t)n_pairs, N1 = (size_t)cur_offsets[B], N2 = (size_t)loop_offsets[B];
+    if (!cur_poses_wc || !loop_poses_wc || !sim3 || !results || (N1 > 0 && (!cur_desc || !cur_points_cam || !cur_has_point || !matches ||
+        !feature_matches || !pts_current || !pts_loop || !inlier)) || (N2 > 0 && (!loop_kp || !loop_desc || !loop_points_cam || !loop_has_point)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // one blob each way: [cur desc | cur points | cur has | loop kp | loop desc | loop points | loop has] up,
+    // [sim3 | records | matches | feature matches | pts current | pts loop | inliers] down
+    Carve in, out;
+    const size_t i_cd = in.take(32 * N1), i_cp = in.take(24 * N1), i_ch = in.take(N1), i_lk = in.take(sizeof(orbx_keypoint) * N2), i_ld = in.take(32 * N2),
+                 i_lp = in.take(24 * N2), i_lh = in.take(N2);
+    const size_t o_s3 = out.take(64 * B), o_rs = out.take(sizeof(orbx_loop_verify_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * N1),
+                 o_fm = out.take(8 * N1), o_pc = out.take(24 * N1), o_pl = out.take(24 * N1), o_in = out.take(N1);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_lv, h->ws_lv[1], in.off, out.off, c)) return rc;
+    uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+    if (N1) { std::memcpy(hi + i_cd, cur_desc, 32 * N1); std::memcpy(hi + i_cp, cur_points_cam, 24 * N1); std::memcpy(hi + i_ch, cur_has_point, N1); }
+    if (N2) {
+      std::memcpy(hi + i_lk, loop_kp, sizeof(orbx_keypoint) * N2); std::memcpy(hi + i_ld, loop_desc, 32 * N2);
+      std::memcpy(hi + i_lp, loop_points_cam, 24 * N2); std::memcpy(hi + i_lh, loop_has_point, N2);
     }
-  }
-  return ORBX_OK;
+    if (int rc = orbx_host_call_upload(h, c)) return rc;
+    if (int rc = orbx_verify_loop_candidates_device(h, cam, cfg, n_pairs, di + i_cd, (const double*)(di + i_cp), di + i_ch, cur_node, cur_offsets,
+                                                    cur_poses_wc, (const orbx_keypoint*)(di + i_lk), di + i_ld, (const double*)(di + i_lp), di + i_lh,
+                                                    loop_node, loop_offsets, loop_poses_wc, (orbx_dmatch*)(dout + o_ma), (int*)(dout + o_fm),
+                                                    (double*)(dout + o_pc), (double*)(dout + o_pl), dout + o_in, (double*)(dout + o_s3),
+                                                    (orbx_loop_verify_result*)(dout + o_rs)))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(sim3, ho + o_s3, 64 * B);
+    std::memcpy(results, ho + o_rs, sizeof(orbx_loop_verify_result) * B);
+    for (size_t b = 0; b < B; ++b) {
+      const size_t k0 = (size_t)cur_offsets[b], nm = (size_t)results[b].n_matches, np = (size_t)results[b].n_pairs;
+      if (nm) std::memcpy(matches + k0, ho + o_ma + sizeof(orbx_dmatch) * k0, sizeof(orbx_dmatch) * nm);
+      if (np) {
+        std::memcpy(feature_matches + 2 * k0, ho + o_fm + 8 * k0, 8 * np);
+        std::memcpy(pts_current + 3 * k0, ho + o_pc + 24 * k0, 24 * np);
+        std::memcpy(pts_loop + 3 * k0, ho + o_pl + 24 * k0, 24 * np);
+        std::memcpy(inlier + k0, ho + o_in + k0, np);
+      }
+    }
+    return ORBX_OK;
+  });
 }
 
 }  // extern "C"

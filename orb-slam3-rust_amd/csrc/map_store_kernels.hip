@@ -46,6 +46,9 @@
 // chain the caller names and the same five launches: bac_order_kernel<true> takes the roles from the chain (chain[0] the anchor,
 // chain[i] window keyframe i), bac_emit_kernel<true> ORs has_point[feature] != 0 into mp_idx (ORBX_BA_OBS32_STEREO).
 // orbx_map_local_inertial_ba hands them to the inertial solver where they lie and scatters the positions back the same way.
+// Both windows are one host path: WinPlan (bac_plan / bic_plan check and size a covisible window / a chain), win_enqueue (the kind's
+// selection, then the five launches), win_collect_host (the host forms) and win_local_ba (collect, download, poses, solve, write back).
+// Every extern "C" entry point runs its body inside orbx_guard (orbx_internal.hpp): no C++ exception crosses the C boundary.
 // mp.observations (map_point.rs:140-156), the inverse of the slot tables, is derived the same way for the points a call names:
 // the lists behind orbx_map_observations and orbx_map_refresh_points (search_in_neighbors.rs:139-150) and the counts behind
 // orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
@@ -56,6 +59,7 @@
 // kernels are described where they stand ("creation and removal", below).
 // The sums, the ordered append and the scans of counts are block_dev.hpp's: every thread of a workgroup reaches each of them.
 #include <algorithm>
+#include <memory>
 #include <numeric>
 #include <vector>
 
@@ -525,6 +529,18 @@ int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const 
   return ORBX_OK;
 }
 
+// Three refusals many calls share: the store (not null, of this handle), the keyframes of a call whose launches have one grid row
+// per keyframe, and the features of a call's keyframes summed (they are numbered in an int).
+int ms_check_store(orbx_handle* h, const char* who, const orbx_map_points* mp) {
+  return mp && mp->h == h ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+}
+int ms_check_grid_keyframes(orbx_handle* h, const char* who, int n_kfs) {
+  return n_kfs <= 0xffff ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+}
+int ms_check_feature_total(orbx_handle* h, const char* who, long long total) {
+  return total <= 0x7fffffff ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+}
+
 // keyframe t of a selection or covisibility call: not null, of this handle, its slot table (if it has one) of this store
 int ms_check_keyframe(orbx_handle* h, const char* who, const orbx_map_points* mp, const orbx_keyframe* kf, int t) {
   if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, t);
@@ -577,7 +593,7 @@ struct SelPlan {
 
 int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int source, int B, const orbx_keyframe* const* kfs, const int* kf_offsets,
             const int* src_offsets, SelPlan& P) {
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (int rc = ms_check_store(h, who, mp)) return rc;
   if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
   if (source != ORBX_MAP_SOURCE_KEYFRAMES && source != ORBX_MAP_SOURCE_SLOTS) return orbx_fail(h, ORBX_ERR_INVALID, "%s: unknown source kind %d", who, source);
   P.n_cand.assign((size_t)B, 0); P.bound_off.assign((size_t)B + 1, 0); P.seg_off.assign((size_t)B + 1, 0);
@@ -700,7 +716,7 @@ struct CovPlan {
 };
 
 int cov_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_best, CovPlan& P) {
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (int rc = ms_check_store(h, who, mp)) return rc;
   if (n_kfs < 0 || (n_kfs > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (n_kfs >= 0)", who);
   if (n_best < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_best must not be negative", who);
   P.kfs.resize((size_t)n_kfs);
@@ -841,132 +857,77 @@ int local_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, i
 
 // ---- local BA window, host side --------------------------------------------------------------------------------------------
 
-// A collection call, checked and sized on the host: the local-map plan of one frame whose reference is `cur` (list bound,
-// segments), the keyframes' tables with their keypoints, and the bound of the observations: every feature of kfs[].
-struct BacPlan {
-  LocalPlan L;
+// A collection call, checked and sized on the host.  Its kind: the covisible window of local BA (cur and its max_covisible best
+// neighbours, picked on the device) or the temporal chain of local inertial BA (named by the caller; chain[0] is the anchor).
+// The keyframes' tables with their keypoints (the chain's: and stereo bytes), the observations' bound (every feature of kfs[]), the
+// list's bound, and the kind's selection plan: one local-map frame whose reference is `cur`, or the chain as one frame of keyframes.
+enum WinKind { WIN_COVISIBLE, WIN_CHAIN };
+struct WinPlan {
+  WinKind kind = WIN_COVISIBLE;
   std::vector<BacKf> kfs;
-  int n_feat = 0, max_n = 0;
+  int n_feat = 0, max_n = 0, bound = 0;
+  LocalPlan L; int cur = 0, max_covisible = 0;       // WIN_COVISIBLE
+  SelPlan S; std::vector<int> chain;                 // WIN_CHAIN
+  int n_local() const { return kind == WIN_CHAIN ? (int)chain.size() : 1 + max_covisible; }   // rows of local_kf
 };
 
-int bac_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible, BacPlan& P) {
-  if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
-  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
-  if (max_covisible < 0 || max_covisible >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "%s: max_covisible must not be negative", who);
-  if (int rc = local_plan(h, who, mp, 1, n_kfs, kfs, &cur, max_covisible, P.L)) return rc;
+// the keyframe table and the observations' bound (each keyframe as ms_check_keyframe asks)
+int win_plan_kfs(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, WinPlan& P) {
   P.kfs.resize((size_t)n_kfs);
   long long total = 0;
   for (int t = 0; t < n_kfs; ++t) {
     const orbx_keyframe* kf = kfs[t];
-    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0, nullptr};
+    if (int rc = ms_check_keyframe(h, who, mp, kf, t)) return rc;
+    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0, P.kind == WIN_CHAIN ? kf->d_has_point : nullptr};
     total += kf->n; P.max_n = std::max(P.max_n, kf->n);
   }
-  if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+  if (int rc = ms_check_feature_total(h, who, total)) return rc;
   P.n_feat = (int)total;
   return ORBX_OK;
 }
 
-// Everything on the handle's stream: covisibility and selection as the tracking call runs them, then the five launches above.
-int bac_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BacPlan& P, int cur, int max_covisible, int list_cap, int obs_cap, int* d_counts,
-                int* d_local_kf, int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
-  const int bound = P.L.bound_off[1], n_kfs = (int)P.kfs.size();
-  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (cur's features plus the max_covisible largest of the "
-                                         "others', at most the capacity)", who, list_cap, bound);
-  if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
-  if (!d_counts || !d_local_kf || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_obs32 is 16-byte aligned)", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t K = (size_t)n_kfs;
-  const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK);
-  Carve ws;
-  const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
-               o_ob = ws.take(4 * K);
-  if (int rc = orbx_reserve(h, h->ws_map[6], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[6].p;
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[7], sizeof(BacKf) * K, &hs, &ds)) return rc;
-  std::memcpy(hs, P.kfs.data(), sizeof(BacKf) * K);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[7], sizeof(BacKf) * K)) return rc;
-  // local = [cur] ++ best and P: what one frame of orbx_map_track_local_device gets (the descriptors it gathers stay in the workspace)
-  if (int rc = local_select_enqueue(h, who, mp, 1, P.L, &cur, max_covisible, bound, d_local_kf, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)) return rc;
-  BacArgs A{};
-  A.capacity = mp->capacity; A.n_kfs = n_kfs; A.n_chunk = n_chunk; A.n_local = 1 + max_covisible;
-  A.live = mp->d_live; A.kfs = (const BacKf*)ds; A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot;
-  A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
-  A.chunk_count = (int*)(w + o_cc); A.kf_count = (int*)(w + o_kc); A.role = (int*)(w + o_ro); A.obs_base = (int*)(w + o_ob);
-  A.local_kf = d_local_kf; A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
-  const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
-  {
-    ProfScope ps(h, "bac_index_kernel", true);
-    hipLaunchKernelGGL(bac_index_kernel, list_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_count_kernel", true);
-    hipLaunchKernelGGL(bac_count_kernel, kf_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_order_kernel", true);
-    hipLaunchKernelGGL(bac_order_kernel<false>, dim3(1), block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_emit_kernel", true);
-    hipLaunchKernelGGL(bac_emit_kernel<false>, kf_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_restore_kernel", true);
-    hipLaunchKernelGGL(bac_restore_kernel, list_grid, block, 0, h->stream, A);
-  }
-  ORBX_HIP(h, hipGetLastError());
-  return ORBX_OK;
+int bac_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible, WinPlan& P) {
+  if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
+  if (int rc = ms_check_grid_keyframes(h, who, n_kfs)) return rc;
+  if (max_covisible < 0 || max_covisible >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "%s: max_covisible must not be negative", who);
+  P.kind = WIN_COVISIBLE; P.cur = cur; P.max_covisible = max_covisible;
+  if (int rc = local_plan(h, who, mp, 1, n_kfs, kfs, &cur, max_covisible, P.L)) return rc;
+  P.bound = P.L.bound_off[1];
+  return win_plan_kfs(h, who, mp, n_kfs, kfs, P);
 }
 
-// ---- local inertial BA window, host side (include/orbx.h; local_inertial_ba.rs:366-421, :930-1030) -------------------------------
-
-// An inertial collection call, checked and sized on the host: the chain's selection as one frame of ORBX_MAP_SOURCE_KEYFRAMES, the
-// keyframes' tables with keypoints and stereo bytes, the bound of the observations.
-struct BicPlan {
-  SelPlan S;
-  std::vector<BacKf> kfs;
-  std::vector<int> chain;
-  int n_feat = 0, max_n = 0;
-};
-
-int bic_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain, BicPlan& P) {
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+int bic_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain, WinPlan& P) {
+  if (int rc = ms_check_store(h, who, mp)) return rc;
   if (n_kfs < 0 || (n_kfs > 0 && !kfs) || n_chain < 0 || (n_chain > 0 && !chain)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+  if (int rc = ms_check_grid_keyframes(h, who, n_kfs)) return rc;
   std::vector<uint8_t> in_chain((size_t)n_kfs, 0);
   for (int i = 0; i < n_chain; ++i) {
     if (chain[i] < 0 || chain[i] >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: chain[%d] = %d is outside [0, n_kfs = %d)", who, i, chain[i], n_kfs);
     if (in_chain[(size_t)chain[i]]) return orbx_fail(h, ORBX_ERR_INVALID, "%s: chain[%d] = %d is listed twice", who, i, chain[i]);
     in_chain[(size_t)chain[i]] = 1;
   }
-  P.kfs.resize((size_t)n_kfs);
-  long long total = 0;
-  for (int t = 0; t < n_kfs; ++t) {
-    const orbx_keyframe* kf = kfs[t];
-    if (int rc = ms_check_keyframe(h, who, mp, kf, t)) return rc;
-    P.kfs[(size_t)t] = BacKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->d_kp, kf->n, 0, kf->d_has_point};
-    total += kf->n; P.max_n = std::max(P.max_n, kf->n);
-  }
-  if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
-  P.n_feat = (int)total;
+  P.kind = WIN_CHAIN;
+  if (int rc = win_plan_kfs(h, who, mp, n_kfs, kfs, P)) return rc;
   if (n_chain < 2) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the temporal window needs two keyframes", who);   // local_inertial_ba.rs:940-942
   P.chain.assign(chain, chain + n_chain);
   std::vector<const orbx_keyframe*> ck((size_t)n_chain);
   for (int i = 0; i < n_chain; ++i) ck[(size_t)i] = kfs[chain[i]];
   const int off[2] = {0, n_chain};
-  return ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ck.data(), off, nullptr, P.S);
+  if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ck.data(), off, nullptr, P.S)) return rc;
+  P.bound = P.S.bound_off[1];
+  return ORBX_OK;
 }
 
-// Everything on the handle's stream: the chain's selection, then index, count, order (chain roles), emit (stereo bit), restore.
-int bic_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BicPlan& P, int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf,
-                int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
-  const int bound = P.S.bound_off[1], n_kfs = (int)P.kfs.size(), n_chain = (int)P.chain.size();
-  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the chain's features summed, at most the capacity)", who,
-                                         list_cap, bound);
+// Everything on the handle's stream: the kind's selection (covisibility and selection as the tracking call runs them, or the chain's),
+// then the five launches above.  d_local_kf: the covisible window's output (the chain's local_kf is the uploaded chain).
+int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, int list_cap, int obs_cap, int* d_counts, int* d_local_kf,
+                int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  const bool chain = P.kind == WIN_CHAIN;
+  const int bound = P.bound, n_kfs = (int)P.kfs.size();
+  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (%s, at most the capacity)", who, list_cap, bound,
+                                         chain ? "the chain's features summed" : "cur's features plus the max_covisible largest of the others'");
   if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
-  if (!d_counts || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
+  if (!d_counts || (!chain && !d_local_kf) || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_obs32 is 16-byte aligned)", who);
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t K = (size_t)n_kfs;
@@ -974,22 +935,28 @@ int bic_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BicP
   Carve ws, up;
   const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
                o_ob = ws.take(4 * K);
-  const size_t u_kf = up.take(sizeof(BacKf) * K), u_ch = up.take(4 * (size_t)n_chain);
+  const size_t u_kf = up.take(sizeof(BacKf) * K), u_ch = up.take(4 * P.chain.size());
   if (int rc = orbx_reserve(h, h->ws_map[6], ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_map[6].p;
   uint8_t *hs, *ds;
   if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[7], up.off, &hs, &ds)) return rc;
   std::memcpy(hs + u_kf, P.kfs.data(), sizeof(BacKf) * K);
-  std::memcpy(hs + u_ch, P.chain.data(), 4 * (size_t)n_chain);
+  if (chain) std::memcpy(hs + u_ch, P.chain.data(), 4 * P.chain.size());
   if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[7], up.off)) return rc;
-  // P: one frame's selection from the chain's tables, in chain order (the descriptors it gathers stay in the workspace)
-  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)) return rc;
+  // P: local = [cur] ++ best as one frame of orbx_map_track_local_device gets it, or the chain's tables in chain order (descriptors stay in the workspace)
+  if (int rc = chain ? ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)
+                     : local_select_enqueue(h, who, mp, 1, P.L, &P.cur, P.max_covisible, bound, d_local_kf, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd))
+    return rc;
   BacArgs A{};
-  A.capacity = mp->capacity; A.n_kfs = n_kfs; A.n_chunk = n_chunk; A.n_local = n_chain;
+  A.capacity = mp->capacity; A.n_kfs = n_kfs; A.n_chunk = n_chunk; A.n_local = P.n_local();
   A.live = mp->d_live; A.kfs = (const BacKf*)(ds + u_kf); A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot;
   A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
   A.chunk_count = (int*)(w + o_cc); A.kf_count = (int*)(w + o_kc); A.role = (int*)(w + o_ro); A.obs_base = (int*)(w + o_ob);
-  A.local_kf = (const int*)(ds + u_ch); A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
+  A.local_kf = chain ? (const int*)(ds + u_ch) : d_local_kf; A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
+  // order and emit are the kind's: roles from local_kf and plain mp_idx, or roles from the chain and the stereo bit
+  using BacKernel = void (*)(BacArgs);
+  static const BacKernel covisible[2] = {bac_order_kernel<false>, bac_emit_kernel<false>}, temporal[2] = {bac_order_kernel<true>, bac_emit_kernel<true>};
+  const BacKernel* of_kind = chain ? temporal : covisible;
   const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
   {
     ProfScope ps(h, "bac_index_kernel", true);
@@ -1001,11 +968,11 @@ int bic_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const BicP
   }
   {
     ProfScope ps(h, "bac_order_kernel", true);
-    hipLaunchKernelGGL(bac_order_kernel<true>, dim3(1), block, 0, h->stream, A);
+    hipLaunchKernelGGL(of_kind[0], dim3(1), block, 0, h->stream, A);
   }
   {
     ProfScope ps(h, "bac_emit_kernel", true);
-    hipLaunchKernelGGL(bac_emit_kernel<true>, kf_grid, block, 0, h->stream, A);
+    hipLaunchKernelGGL(of_kind[1], kf_grid, block, 0, h->stream, A);
   }
   {
     ProfScope ps(h, "bac_restore_kernel", true);
@@ -1023,6 +990,96 @@ void bac_pose_inverse(const double* p, double* out) {
   const double c[3] = {y * t[2] - z * t[1], z * t[0] - x * t[2], x * t[1] - y * t[0]};
   out[0] = w; out[1] = x; out[2] = y; out[3] = z;
   for (int i = 0; i < 3; ++i) out[4 + i] = -(t[i] * w + c[i] + v[i]);
+}
+
+// a window without a point to optimise: M == 0, and for the covisible window N == 0 (local_inertial_ba.rs:946-948)
+int win_check_empty(orbx_handle* h, const char* who, const WinPlan& P, const int* counts) {
+  if (P.kind == WIN_CHAIN) return counts[2] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);
+  return counts[2] && counts[3] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
+}
+
+// The collection into ws_map[1] (d) and its first download (hp), which the call waits for: counts | local (covisible) | fixed, and
+// with `rows` | P's slots | P's positions at their bounds.  The observations stay at d + o_ob.
+struct WinDown { size_t o_cn, o_lk, o_fx, o_ls, o_po, o_ob; uint8_t* d; const uint8_t* hp; };
+int win_collect_down(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, bool rows, WinDown& o) {
+  const size_t bound = (size_t)P.bound, nl = P.kind == WIN_CHAIN ? 0 : (size_t)P.n_local(), K = P.kfs.size();
+  ORBX_HIP(h, hipSetDevice(h->device));
+  Carve out;
+  o.o_cn = out.take(16); o.o_lk = out.take(4 * nl); o.o_fx = out.take(4 * K);
+  const size_t head = out.off;
+  o.o_ls = out.take(4 * bound); o.o_po = out.take(24 * bound);
+  const size_t down = rows ? out.off : head;
+  o.o_ob = out.take(16 * (size_t)P.n_feat);
+  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
+  uint8_t* d = o.d = (uint8_t*)h->ws_map[1].p;
+  if (int rc = win_enqueue(h, who, mp, P, P.bound, P.n_feat, (int*)(d + o.o_cn), (int*)(d + o.o_lk), (int*)(d + o.o_fx), (int*)(d + o.o_ls), (double*)(d + o.o_po),
+                           (orbx_ba_obs32*)(d + o.o_ob)))
+    return rc;
+  o.hp = (const uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d, down, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  return ORBX_OK;
+}
+
+// The host forms of the collection: the sizes first, then as many rows as they say: two downloads, nothing sized by a bound.
+int win_collect_host(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, int list_cap, int obs_cap, int* counts, int* local_kf, int* fixed_kf,
+                     int* list_slot, double* positions, orbx_ba_obs32* obs32) {
+  const bool chain = P.kind == WIN_CHAIN;
+  if (list_cap < P.bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, P.bound, P.n_feat);
+  if (!counts || (!chain && !local_kf) || !fixed_kf || (P.bound > 0 && (!list_slot || !positions)) || (P.n_feat > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  WinDown w;
+  if (int rc = win_collect_down(h, who, mp, P, false, w)) return rc;
+  std::memcpy(counts, w.hp + w.o_cn, 16); std::memcpy(fixed_kf, w.hp + w.o_fx, 4 * P.kfs.size());
+  if (!chain) std::memcpy(local_kf, w.hp + w.o_lk, 4 * (size_t)P.n_local());
+  if (int rc = win_check_empty(h, who, P, counts)) return rc;
+  const size_t M = (size_t)counts[2], N = (size_t)counts[3];
+  Carve rows;
+  const size_t r_ls = rows.take(4 * M), r_po = rows.take(24 * M), r_ob = rows.take(16 * N);
+  if (int rc = orbx_reserve_pinned(h, h->pin_map, rows.off)) return rc;
+  uint8_t* hp = (uint8_t*)h->pin_map.p;
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_ls, w.d + w.o_ls, 4 * M, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_po, w.d + w.o_po, 24 * M, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipMemcpyAsync(hp + r_ob, w.d + w.o_ob, 16 * N, hipMemcpyDeviceToHost, h->stream));
+  ORBX_HIP(h, hipStreamSynchronize(h->stream));
+  std::memcpy(list_slot, hp + r_ls, 4 * M); std::memcpy(positions, hp + r_po, 24 * M); std::memcpy(obs32, hp + r_ob, 16 * N);
+  return ORBX_OK;
+}
+
+// Local BA on a planned window: collect_*_ba_data (local_ba_lm.rs:800-897, local_inertial_ba.rs:930-1030) on the device with ONE
+// download; solve_*_ba (:912-1098, :1074-1275) on the observations where they lie (`in`: the inertial solve's extras; its window
+// keyframes' T_wc go in as they are where the visual solve takes T_cw, :825-841, :973-978); the point half of apply_*_ba_results
+// (local_mapper.rs:363, :396: only a solve that iterated is applied).  The covisible window answers local_kf_out, the chain fixed_kf_out.
+int win_local_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_ba_config* cfg, const BaInertialHost* in, orbx_map_points* mp,
+                 const orbx_keyframe* const* kfs, const WinPlan& P, orbx_should_stop_fn should_stop, void* user, int* local_kf_out, int* fixed_kf_out,
+                 double* poses_wc_out, int* counts_out, int* iterations, double* initial_error, double* final_error) {
+  const bool chain = P.kind == WIN_CHAIN;
+  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+  orbx_prof_begin_call(h);
+  WinDown w;
+  if (int rc = win_collect_down(h, who, mp, P, true, w)) return rc;
+  const int* cn = (const int*)(w.hp + w.o_cn);
+  const int* fx = (const int*)(w.hp + w.o_fx);
+  const int* local = chain ? P.chain.data() : (const int*)(w.hp + w.o_lk);   // [0] the anchor; the window: the chain's from 0, the covisible from 1
+  const double* pos = (const double*)(w.hp + w.o_po);
+  const int Kw = cn[0], F = cn[1], M = cn[2], N = cn[3];
+  std::memcpy(counts_out, cn, 16);
+  if (chain) std::memcpy(fixed_kf_out, fx, 4 * P.kfs.size());
+  else std::memcpy(local_kf_out, local, 4 * (size_t)P.n_local());
+  if (int rc = win_check_empty(h, who, P, cn)) return rc;
+  std::vector<double> poses(7 * (size_t)std::max(Kw, 1)), fixed_cw(7 * (size_t)F), points(pos, pos + 3 * (size_t)M);
+  std::vector<int> slots((const int*)(w.hp + w.o_ls), (const int*)(w.hp + w.o_ls) + M);
+  for (int i = 0; i < Kw; ++i) {
+    if (chain) std::memcpy(&poses[7 * (size_t)i], kfs[local[i]]->pose_wc, 56);
+    else bac_pose_inverse(kfs[local[1 + i]]->pose_wc, &poses[7 * (size_t)i]);
+  }
+  bac_pose_inverse(kfs[local[0]]->pose_wc, &fixed_cw[0]);
+  for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
+  if (int rc = ba_solve_visual(h, cam, cfg, Kw, poses.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
+                               initial_error, final_error, false, in, (const orbx_ba_obs32*)(w.d + w.o_ob), true))
+    return rc;
+  if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
+  return ORBX_OK;
 }
 
 // ---- tracking from the store: what the keyframe / slot forms and the local-map forms share --------------------------------
@@ -1333,7 +1390,7 @@ struct ObsPlan {
 
 int obs_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, ObsPlan& P) {
   if (int rc = cov_plan(h, who, mp, n_kfs, kfs, 0, P.C)) return rc;
-  if (n_kfs > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+  if (int rc = ms_check_grid_keyframes(h, who, n_kfs)) return rc;
   long long total = 0;
   for (const CovKf& k : P.C.kfs) total += k.n;
   if (total > 0x7fff0000) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 65536 features", who);
@@ -1836,7 +1893,7 @@ void mf_pose_inverse(const double* p, double* o) {
 int mf_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src,
              int n_tgt, const int* tgt, unsigned desc_threshold) {
   if (!cam) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (int rc = ms_check_store(h, who, mp)) return rc;
   if (n_kfs < 0 || n_kfs > 0xffff || (n_kfs > 0 && !kfs)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_kfs <= 65535: the keyframe is a grid dimension)", who);
   if (n_src < 0 || n_tgt < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (n_src >= 0, n_tgt >= 0)", who);
   if (desc_threshold > 256) return orbx_fail(h, ORBX_ERR_INVALID, "%s: desc_threshold %u is above 256", who, desc_threshold);
@@ -1881,7 +1938,7 @@ int mf_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kf
     P.ckfs[(size_t)k] = CovKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, 0};
     P.kfs[(size_t)k] = MfKf{kf->slot_store ? kf->d_mp_slot : nullptr, kf->slot_store ? kf->d_mp_uniq : nullptr, kf->n, (int)total, -1, 0};
     total += kf->n; P.max_n = std::max(P.max_n, kf->n);
-    if (total > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
+    if (int rc = ms_check_feature_total(h, who, total)) return rc;
   }
   P.n_feat = (int)total;
   long long ft = 0;
@@ -2193,7 +2250,7 @@ int mc_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx
              const orbx_keyframe* const* nbs, int T, int phases, const int* free_slots, int n_free) {
   if (!cam || !cfg || T < 0 || T > 256 || cfg->max_descriptor_dist > 256 || (T > 0 && !nbs))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= T <= 256; max_descriptor_dist <= 256)", who);
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
+  if (int rc = ms_check_store(h, who, mp)) return rc;
   if (phases < 1 || phases > (ORBX_MAP_CREATE_STEREO | ORBX_MAP_CREATE_NEIGHBOURS)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: phases = %d is outside 1..3", who, phases);
   std::vector<const orbx_keyframe*> all((size_t)T + 1);
   all[0] = cur;
@@ -2347,19 +2404,21 @@ extern "C" {
 
 int orbx_map_points_create(orbx_handle* h, int capacity, orbx_map_points** out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!out || capacity < 1 || capacity >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_map_points_create: bad argument (1 <= capacity < %d)", MS_EMPTY / 64);
-  *out = nullptr;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_map_points* mp = new orbx_map_points();
-  mp->h = h; mp->capacity = capacity;
-  mp->live.assign((size_t)capacity, 0); mp->stamp.assign((size_t)capacity, 0u);
-  Carve blk;
-  const size_t o_po = blk.take(24 * (size_t)capacity), o_de = blk.take(32 * (size_t)capacity), o_li = blk.take((size_t)capacity);
-  if (hipMalloc((void**)&mp->block, blk.off) != hipSuccess) { delete mp; return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: out of device memory"); }
-  mp->d_pos = (double*)(mp->block + o_po); mp->d_desc = mp->block + o_de; mp->d_live = mp->block + o_li;
-  if (hipMemsetAsync(mp->block, 0, blk.off, h->stream) != hipSuccess) { hipFree(mp->block); delete mp; return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: memset failed"); }
-  *out = mp;
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_map_points_create", [&]() -> int {
+    if (!out || capacity < 1 || capacity >= MS_EMPTY / 64) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_map_points_create: bad argument (1 <= capacity < %d)", MS_EMPTY / 64);
+    *out = nullptr;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    std::unique_ptr<orbx_map_points> mp(new orbx_map_points());             // (freed on every way out that does not hand it over)
+    mp->h = h; mp->capacity = capacity;
+    mp->live.assign((size_t)capacity, 0); mp->stamp.assign((size_t)capacity, 0u);
+    Carve blk;
+    const size_t o_po = blk.take(24 * (size_t)capacity), o_de = blk.take(32 * (size_t)capacity), o_li = blk.take((size_t)capacity);
+    if (hipMalloc((void**)&mp->block, blk.off) != hipSuccess) return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: out of device memory");
+    mp->d_pos = (double*)(mp->block + o_po); mp->d_desc = mp->block + o_de; mp->d_live = mp->block + o_li;
+    if (hipMemsetAsync(mp->block, 0, blk.off, h->stream) != hipSuccess) { hipFree(mp->block); return orbx_fail(h, ORBX_ERR_HIP, "orbx_map_points_create: memset failed"); }
+    *out = mp.release();
+    return ORBX_OK;
+  });
 }
 
 void orbx_map_points_destroy(orbx_map_points* mp) {
@@ -2381,78 +2440,86 @@ int orbx_map_points_info(const orbx_map_points* mp, int* capacity, int* n_live) 
 
 int orbx_map_points_set(orbx_map_points* mp, const int* slots, int n, const double* positions, const uint8_t* desc) {
   if (!mp) return ORBX_ERR_INVALID;
-  return ms_set(mp, "orbx_map_points_set", slots, n, positions, desc, true);
+  return orbx_guard(mp->h, "orbx_map_points_set", [&] { return ms_set(mp, "orbx_map_points_set", slots, n, positions, desc, true); });
 }
 
 int orbx_map_points_set_device(orbx_map_points* mp, const int* slots, int n, const double* d_positions, const uint8_t* d_desc) {
   if (!mp) return ORBX_ERR_INVALID;
-  if (((uintptr_t)d_desc & 3) || ((uintptr_t)d_positions & 7)) return orbx_fail(mp->h, ORBX_ERR_INVALID, "orbx_map_points_set_device: d_desc is 4-byte, d_positions 8-byte aligned");
-  return ms_set(mp, "orbx_map_points_set_device", slots, n, d_positions, d_desc, false);
+  return orbx_guard(mp->h, "orbx_map_points_set_device", [&]() -> int {
+    if (((uintptr_t)d_desc & 3) || ((uintptr_t)d_positions & 7)) return orbx_fail(mp->h, ORBX_ERR_INVALID, "orbx_map_points_set_device: d_desc is 4-byte, d_positions 8-byte aligned");
+    return ms_set(mp, "orbx_map_points_set_device", slots, n, d_positions, d_desc, false);
+  });
 }
 
 int orbx_map_points_erase(orbx_map_points* mp, const int* slots, int n) {
   static const char* who = "orbx_map_points_erase";
   if (!mp) return ORBX_ERR_INVALID;
   orbx_handle* h = mp->h;
-  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
-  if (n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], 4 * (size_t)n, &hs, &ds)) return rc;
-  std::memcpy(hs, slots, 4 * (size_t)n);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], 4 * (size_t)n)) return rc;
-  return ms_erase_launch(h, mp, (const int*)ds, slots, n);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    uint8_t *hs, *ds;
+    if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], 4 * (size_t)n, &hs, &ds)) return rc;
+    std::memcpy(hs, slots, 4 * (size_t)n);
+    if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], 4 * (size_t)n)) return rc;
+    return ms_erase_launch(h, mp, (const int*)ds, slots, n);
+  });
 }
 
 int orbx_map_points_download(orbx_map_points* mp, const int* slots, int n, double* positions, uint8_t* desc, uint8_t* live) {
   static const char* who = "orbx_map_points_download";
   if (!mp) return ORBX_ERR_INVALID;
   orbx_handle* h = mp->h;
-  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
-  if (n == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // tests and debugging: the whole store comes down, the rows asked for are picked on the host
-  const size_t cap = (size_t)mp->capacity, bytes = (size_t)((mp->d_live + cap) - mp->block);
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, bytes)) return rc;
-  uint8_t* hp = (uint8_t*)h->pin_map.p;
-  ORBX_HIP(h, hipMemcpyAsync(hp, mp->block, bytes, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  const double* hpos = (const double*)(hp + ((uint8_t*)mp->d_pos - mp->block));
-  const uint8_t* hdesc = hp + (mp->d_desc - mp->block);
-  const uint8_t* hlive = hp + (mp->d_live - mp->block);
-  for (int i = 0; i < n; ++i) {
-    const size_t s = (size_t)slots[i];
-    if (positions) std::memcpy(positions + 3 * (size_t)i, hpos + 3 * s, 24);
-    if (desc) std::memcpy(desc + 32 * (size_t)i, hdesc + 32 * s, 32);
-    if (live) live[i] = hlive[s];
-  }
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // tests and debugging: the whole store comes down, the rows asked for are picked on the host
+    const size_t cap = (size_t)mp->capacity, bytes = (size_t)((mp->d_live + cap) - mp->block);
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, bytes)) return rc;
+    uint8_t* hp = (uint8_t*)h->pin_map.p;
+    ORBX_HIP(h, hipMemcpyAsync(hp, mp->block, bytes, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    const double* hpos = (const double*)(hp + ((uint8_t*)mp->d_pos - mp->block));
+    const uint8_t* hdesc = hp + (mp->d_desc - mp->block);
+    const uint8_t* hlive = hp + (mp->d_live - mp->block);
+    for (int i = 0; i < n; ++i) {
+      const size_t s = (size_t)slots[i];
+      if (positions) std::memcpy(positions + 3 * (size_t)i, hpos + 3 * s, 24);
+      if (desc) std::memcpy(desc + 32 * (size_t)i, hdesc + 32 * s, 32);
+      if (live) live[i] = hlive[s];
+    }
+    return ORBX_OK;
+  });
 }
 
 int orbx_keyframe_set_map_point_slots(orbx_keyframe* kf, const orbx_map_points* mp, const int* slots) {
   static const char* who = "orbx_keyframe_set_map_point_slots";
   if (!kf) return ORBX_ERR_INVALID;
   orbx_handle* h = kf->h;
-  if (!slots) { kf->slot_store = nullptr; return ORBX_OK; }
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
-  for (int i = 0; i < kf->n; ++i)
-    if (slots[i] < -1 || slots[i] >= mp->capacity) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d (feature %d) is outside [-1, %d)", who, slots[i], i, mp->capacity);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (kf->n > 0) {
-    // beside the table, the same with every repeat of a slot set to -1 (the first feature that names it keeps it): what
-    // covisibility counts, each observed slot once
-    const size_t n = (size_t)kf->n;
-    std::vector<int> uniq(slots, slots + n), order(n);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slots[a] < slots[b]; });
-    for (size_t i = 1; i < n; ++i)
-      if (slots[order[i]] == slots[order[i - 1]]) uniq[(size_t)order[i]] = -1;
-    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_slot, slots, 4 * n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_uniq, uniq.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));                       // the caller's array is free when the call returns
-  }
-  kf->slot_store = mp;
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    if (!slots) { kf->slot_store = nullptr; return ORBX_OK; }
+    if (int rc = ms_check_store(h, who, mp)) return rc;
+    for (int i = 0; i < kf->n; ++i)
+      if (slots[i] < -1 || slots[i] >= mp->capacity) return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d (feature %d) is outside [-1, %d)", who, slots[i], i, mp->capacity);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (kf->n > 0) {
+      // beside the table, the same with every repeat of a slot set to -1 (the first feature that names it keeps it): what
+      // covisibility counts, each observed slot once
+      const size_t n = (size_t)kf->n;
+      std::vector<int> uniq(slots, slots + n), order(n);
+      std::iota(order.begin(), order.end(), 0);
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slots[a] < slots[b]; });
+      for (size_t i = 1; i < n; ++i)
+        if (slots[order[i]] == slots[order[i - 1]]) uniq[(size_t)order[i]] = -1;
+      ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_slot, slots, 4 * n, hipMemcpyHostToDevice, h->stream));
+      ORBX_HIP(h, hipMemcpyAsync(kf->d_mp_uniq, uniq.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
+      ORBX_HIP(h, hipStreamSynchronize(h->stream));                       // the caller's array is free when the call returns
+    }
+    kf->slot_store = mp;
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_select_points_device(orbx_handle* h, orbx_map_points* mp, int source, int n_frames, const orbx_keyframe* const* kfs, const int* kf_offsets,
@@ -2460,9 +2527,11 @@ int orbx_map_select_points_device(orbx_handle* h, orbx_map_points* mp, int sourc
                                   double* d_positions, uint8_t* d_mp_desc) {
   static const char* who = "orbx_map_select_points_device";
   if (!h) return ORBX_ERR_INVALID;
-  SelPlan P;
-  if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
-  return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  return orbx_guard(h, who, [&]() -> int {
+    SelPlan P;
+    if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+    return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  });
 }
 
 int orbx_map_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg,
@@ -2475,14 +2544,16 @@ int orbx_map_track_frames_device(orbx_handle* h, const orbx_camera* cam, const o
                                  orbx_pnp_result* d_pnp_results, int* d_matched, int* d_matched_slot, orbx_track_result* d_results) {
   static const char* who = "orbx_map_track_frames_device";
   if (!h) return ORBX_ERR_INVALID;
-  SelPlan P;
-  if (n_frames > 0)
-    if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
-  const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
-                      d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
-                      d_matched, d_matched_slot, d_results};
-  return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, D, [&] {
-    return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  return orbx_guard(h, who, [&]() -> int {
+    SelPlan P;
+    if (n_frames > 0)
+      if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+    const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
+                        d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
+                        d_matched, d_matched_slot, d_results};
+    return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, D, [&] {
+      return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src_slots, src_offsets, list_cap, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+    });
   });
 }
 
@@ -2494,54 +2565,60 @@ int orbx_map_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_tra
                           orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results) {
   static const char* who = "orbx_map_track_frames";
   if (!h) return ORBX_ERR_INVALID;
-  SelPlan P;
-  if (n_frames > 0)
-    if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
-  const size_t S = n_frames > 0 && source == ORBX_MAP_SOURCE_SLOTS ? (size_t)src_offsets[n_frames] : 0;
-  const MapTrackHost H{src_slots, S, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, nullptr, 0, list_offsets, list_slot, offsets, pts3d, pts2d,
-                       mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
-  return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, H,
-                       [&](const int* d_src, int*, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
-                         return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src, src_offsets, P.bound_off[(size_t)n_frames], d_lo, d_ls, d_gp, d_gd);
-                       });
+  return orbx_guard(h, who, [&]() -> int {
+    SelPlan P;
+    if (n_frames > 0)
+      if (int rc = ms_plan(h, who, mp, source, n_frames, kfs, kf_offsets, src_offsets, P)) return rc;
+    const size_t S = n_frames > 0 && source == ORBX_MAP_SOURCE_SLOTS ? (size_t)src_offsets[n_frames] : 0;
+    const MapTrackHost H{src_slots, S, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, nullptr, 0, list_offsets, list_slot, offsets, pts3d, pts2d,
+                         mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
+    return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, n_frames > 0 ? P.bound_off.data() : nullptr, H,
+                         [&](const int* d_src, int*, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
+                           return ms_select_enqueue(h, who, mp, source, n_frames, P, d_src, src_offsets, P.bound_off[(size_t)n_frames], d_lo, d_ls, d_gp, d_gd);
+                         });
+  });
 }
 
 int orbx_map_covisibility_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries, const int* query,
                                  int n_best, int* d_weights, int* d_best, int* d_n_best) {
   static const char* who = "orbx_map_covisibility_device";
   if (!h) return ORBX_ERR_INVALID;
-  CovPlan P;
-  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
-  if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
-  if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
-  if (n_queries == 0 || n_kfs == 0 || (!d_weights && !d_n_best && (!d_best || n_best == 0))) return ORBX_OK;
-  return cov_enqueue(h, mp, P, n_queries, query, n_best, d_weights, n_best > 0 ? d_best : nullptr, d_n_best, nullptr);
+  return orbx_guard(h, who, [&]() -> int {
+    CovPlan P;
+    if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
+    if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
+    if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
+    if (n_queries == 0 || n_kfs == 0 || (!d_weights && !d_n_best && (!d_best || n_best == 0))) return ORBX_OK;
+    return cov_enqueue(h, mp, P, n_queries, query, n_best, d_weights, n_best > 0 ? d_best : nullptr, d_n_best, nullptr);
+  });
 }
 
 int orbx_map_covisibility(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries, const int* query, int n_best,
                           int* weights, int* best, int* n_best_out) {
   static const char* who = "orbx_map_covisibility";
   if (!h) return ORBX_ERR_INVALID;
-  CovPlan P;
-  if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
-  if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
-  if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
-  if (n_queries == 0 || n_kfs == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t Q = (size_t)n_queries, K = (size_t)n_kfs, nb = (size_t)n_best;
-  Carve out;
-  const size_t o_we = out.take(weights ? 4 * Q * K : 0), o_be = out.take(best ? 4 * Q * nb : 0), o_nb = out.take(n_best_out ? 4 * Q : 0);
-  if (out.off == 0) return ORBX_OK;
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  if (int rc = cov_enqueue(h, mp, P, n_queries, query, n_best, weights ? (int*)(c.dout + o_we) : nullptr, best && nb ? (int*)(c.dout + o_be) : nullptr,
-                           n_best_out ? (int*)(c.dout + o_nb) : nullptr, nullptr))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  if (weights) std::memcpy(weights, c.ho + o_we, 4 * Q * K);
-  if (best && nb) std::memcpy(best, c.ho + o_be, 4 * Q * nb);
-  if (n_best_out) std::memcpy(n_best_out, c.ho + o_nb, 4 * Q);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    CovPlan P;
+    if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P)) return rc;
+    if (n_queries < 0 || n_queries > 0xffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (0 <= n_queries <= 65535)", who);
+    if (int rc = cov_check_queries(h, who, "query", n_queries, query, n_kfs, 0)) return rc;
+    if (n_queries == 0 || n_kfs == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t Q = (size_t)n_queries, K = (size_t)n_kfs, nb = (size_t)n_best;
+    Carve out;
+    const size_t o_we = out.take(weights ? 4 * Q * K : 0), o_be = out.take(best ? 4 * Q * nb : 0), o_nb = out.take(n_best_out ? 4 * Q : 0);
+    if (out.off == 0) return ORBX_OK;
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    if (int rc = cov_enqueue(h, mp, P, n_queries, query, n_best, weights ? (int*)(c.dout + o_we) : nullptr, best && nb ? (int*)(c.dout + o_be) : nullptr,
+                             n_best_out ? (int*)(c.dout + o_nb) : nullptr, nullptr))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    if (weights) std::memcpy(weights, c.ho + o_we, 4 * Q * K);
+    if (best && nb) std::memcpy(best, c.ho + o_be, 4 * Q * nb);
+    if (n_best_out) std::memcpy(n_best_out, c.ho + o_nb, 4 * Q);
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_track_local_device(orbx_handle* h, const orbx_camera* cam, const orbx_track_config* cfg, const orbx_pnp_config* pnp_cfg, orbx_map_points* mp,
@@ -2553,13 +2630,15 @@ int orbx_map_track_local_device(orbx_handle* h, const orbx_camera* cam, const or
                                 int* d_matched, int* d_matched_slot, orbx_track_result* d_results) {
   static const char* who = "orbx_map_track_local_device";
   if (!h) return ORBX_ERR_INVALID;
-  LocalPlan P;
-  if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
-  const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
-                      d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
-                      d_matched, d_matched_slot, d_results};
-  return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), D, [&] {
-    return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, list_cap, d_local_kf, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+  return orbx_guard(h, who, [&]() -> int {
+    LocalPlan P;
+    if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
+    const MapTrackDev D{d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride, max_feat, d_search_poses_wc, d_priors_wc, d_list_offsets, d_list_slot,
+                        d_positions, d_mp_desc, d_offsets, d_pts3d, d_pts2d, d_mp_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results,
+                        d_matched, d_matched_slot, d_results};
+    return ms_track_device(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), D, [&] {
+      return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, list_cap, d_local_kf, d_list_offsets, d_list_slot, d_positions, d_mp_desc);
+    });
   });
 }
 
@@ -2570,14 +2649,16 @@ int orbx_map_track_local(orbx_handle* h, const orbx_camera* cam, const orbx_trac
                          uint8_t* inlier_out, double* err_out, orbx_pnp_result* pnp_results, int* matched, int* matched_slot, orbx_track_result* results) {
   static const char* who = "orbx_map_track_local";
   if (!h) return ORBX_ERR_INVALID;
-  LocalPlan P;
-  if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
-  const MapTrackHost H{nullptr, 0, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, local_kf, (size_t)n_frames * (1 + (size_t)n_best), list_offsets,
-                       list_slot, offsets, pts3d, pts2d, mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
-  return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), H,
-                       [&](const int*, int* d_lk, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
-                         return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, P.bound_off[(size_t)n_frames], d_lk, d_lo, d_ls, d_gp, d_gd);
-                       });
+  return orbx_guard(h, who, [&]() -> int {
+    LocalPlan P;
+    if (int rc = local_plan(h, who, mp, n_frames, n_kfs, kfs, ref_kf, n_best, P)) return rc;
+    const MapTrackHost H{nullptr, 0, kp, desc, feat_offsets, search_poses_wc, priors_wc, list_cap, local_kf, (size_t)n_frames * (1 + (size_t)n_best), list_offsets,
+                         list_slot, offsets, pts3d, pts2d, mp_idx, feat_idx, poses_wc_out, inlier_out, err_out, pnp_results, matched, matched_slot, results};
+    return ms_track_host(h, who, cam, cfg, pnp_cfg, n_frames, P.bound_off.data(), H,
+                         [&](const int*, int* d_lk, int* d_lo, int* d_ls, double* d_gp, uint8_t* d_gd) {
+                           return local_select_enqueue(h, who, mp, n_frames, P, ref_kf, n_best, P.bound_off[(size_t)n_frames], d_lk, d_lo, d_ls, d_gp, d_gd);
+                         });
+  });
 }
 
 int orbx_map_collect_ba_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible,
@@ -2585,48 +2666,22 @@ int orbx_map_collect_ba_window_device(orbx_handle* h, orbx_map_points* mp, int n
                                       orbx_ba_obs32* d_obs32) {
   static const char* who = "orbx_map_collect_ba_window_device";
   if (!h) return ORBX_ERR_INVALID;
-  BacPlan P;
-  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
-  return bac_enqueue(h, who, mp, P, cur, max_covisible, list_cap, obs_cap, d_counts, d_local_kf, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
+    if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
+    return win_enqueue(h, who, mp, P, list_cap, obs_cap, d_counts, d_local_kf, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+  });
 }
 
 int orbx_map_collect_ba_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int cur, int max_covisible, int list_cap,
                                int obs_cap, int* counts, int* local_kf, int* fixed_kf, int* list_slot, double* positions, orbx_ba_obs32* obs32) {
   static const char* who = "orbx_map_collect_ba_window";
   if (!h) return ORBX_ERR_INVALID;
-  BacPlan P;
-  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
-  const size_t bound = (size_t)P.L.bound_off[1], nf = (size_t)P.n_feat, nl = 1 + (size_t)max_covisible, K = (size_t)n_kfs;
-  if (list_cap < (int)bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, (int)bound, P.n_feat);
-  if (!counts || !local_kf || !fixed_kf || (bound > 0 && (!list_slot || !positions)) || (nf > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // the sizes first (counts, local and fixed keyframes), then as many rows as they say: two downloads, nothing sized by a bound
-  Carve out;
-  const size_t o_cn = out.take(16), o_lk = out.take(4 * nl), o_fx = out.take(4 * K);
-  const size_t head = out.off;
-  const size_t o_ls = out.take(4 * bound), o_po = out.take(24 * bound), o_ob = out.take(16 * nf);
-  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, head)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_map[1].p;
-  if (int rc = bac_enqueue(h, who, mp, P, cur, max_covisible, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_lk), (int*)(d + o_fx), (int*)(d + o_ls),
-                           (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
-    return rc;
-  uint8_t* hp = (uint8_t*)h->pin_map.p;
-  ORBX_HIP(h, hipMemcpyAsync(hp, d, head, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  std::memcpy(counts, hp + o_cn, 16); std::memcpy(local_kf, hp + o_lk, 4 * nl); std::memcpy(fixed_kf, hp + o_fx, 4 * K);
-  const size_t M = (size_t)counts[2], N = (size_t)counts[3];
-  if (M == 0 || N == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
-  Carve rows;
-  const size_t r_ls = rows.take(4 * M), r_po = rows.take(24 * M), r_ob = rows.take(16 * N);
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, rows.off)) return rc;
-  hp = (uint8_t*)h->pin_map.p;
-  ORBX_HIP(h, hipMemcpyAsync(hp + r_ls, d + o_ls, 4 * M, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(hp + r_po, d + o_po, 24 * M, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(hp + r_ob, d + o_ob, 16 * N, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  std::memcpy(list_slot, hp + r_ls, 4 * M); std::memcpy(positions, hp + r_po, 24 * M); std::memcpy(obs32, hp + r_ob, 16 * N);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
+    if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_covisible, P)) return rc;
+    return win_collect_host(h, who, mp, P, list_cap, obs_cap, counts, local_kf, fixed_kf, list_slot, positions, obs32);
+  });
 }
 
 int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs,
@@ -2634,110 +2689,37 @@ int orbx_map_local_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_conf
                       double* initial_error, double* final_error) {
   static const char* who = "orbx_map_local_ba";
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || !cfg || !local_kf_out || !counts_out || !iterations || !initial_error || !final_error || (cfg->max_covisible_keyframes > 0 && !poses_wc_out))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)", who);
-  const int max_cov = cfg->max_covisible_keyframes;
-  BacPlan P;
-  if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, max_cov, P)) return rc;
-  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
-  const size_t bound = (size_t)P.L.bound_off[1], nf = (size_t)P.n_feat, nl = 1 + (size_t)max_cov, K = (size_t)n_kfs;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // phase 1 (collect_visual_ba_data, :800-897) on the device; ONE download: counts | local | fixed | P's slots | P's positions
-  Carve out;
-  const size_t o_cn = out.take(16), o_lk = out.take(4 * nl), o_fx = out.take(4 * K), o_ls = out.take(4 * bound), o_po = out.take(24 * bound);
-  const size_t down = out.off;
-  const size_t o_ob = out.take(16 * nf);
-  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
-  uint8_t* d = (uint8_t*)h->ws_map[1].p;
-  orbx_prof_begin_call(h);
-  if (int rc = bac_enqueue(h, who, mp, P, cur, max_cov, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_lk), (int*)(d + o_fx), (int*)(d + o_ls),
-                           (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
-    return rc;
-  uint8_t* hp = (uint8_t*)h->pin_map.p;
-  ORBX_HIP(h, hipMemcpyAsync(hp, d, down, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  const int* cn = (const int*)(hp + o_cn);
-  const int* lk = (const int*)(hp + o_lk);
-  const int* fx = (const int*)(hp + o_fx);
-  const int Ko = cn[0], F = cn[1], M = cn[2], N = cn[3];
-  std::memcpy(counts_out, cn, 16); std::memcpy(local_kf_out, lk, 4 * nl);
-  if (M == 0 || N == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
-  try {
-    // T_cw from the keyframes' own poses (:825-841): the optimised ones, then the anchor and the other fixed observers
-    std::vector<double> poses_cw(7 * (size_t)std::max(Ko, 1)), fixed_cw(7 * (size_t)F), points((const double*)(hp + o_po), (const double*)(hp + o_po) + 3 * (size_t)M);
-    std::vector<int> slots((const int*)(hp + o_ls), (const int*)(hp + o_ls) + M);
-    for (int i = 0; i < Ko; ++i) bac_pose_inverse(kfs[lk[1 + i]]->pose_wc, &poses_cw[7 * (size_t)i]);
-    bac_pose_inverse(kfs[lk[0]]->pose_wc, &fixed_cw[0]);
-    for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
-    // phase 2 (solve_visual_ba, :912-1098) on the observations where they lie
-    if (int rc = ba_solve_visual(h, cam, cfg, Ko, poses_cw.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
-                                 initial_error, final_error, false, nullptr, (const orbx_ba_obs32*)(d + o_ob), true))
-      return rc;
-    // phase 3, the point half of apply_visual_ba_results (:1125-1135; local_mapper.rs:396: only a solve that iterated is applied)
-    if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
-    return ORBX_OK;
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
-  }
+  return orbx_guard(h, who, [&]() -> int {
+    if (!cam || !cfg || !local_kf_out || !counts_out || !iterations || !initial_error || !final_error || (cfg->max_covisible_keyframes > 0 && !poses_wc_out))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)", who);
+    WinPlan P;
+    if (int rc = bac_plan(h, who, mp, n_kfs, kfs, cur, cfg->max_covisible_keyframes, P)) return rc;
+    return win_local_ba(h, who, cam, cfg, nullptr, mp, kfs, P, should_stop, user, local_kf_out, nullptr, poses_wc_out, counts_out, iterations, initial_error,
+                        final_error);
+  });
 }
 
 int orbx_map_collect_inertial_window_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain,
                                             int list_cap, int obs_cap, int* d_counts, int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
   static const char* who = "orbx_map_collect_inertial_window_device";
   if (!h) return ORBX_ERR_INVALID;
-  try {
-    BicPlan P;
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
     if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
-    return bic_enqueue(h, who, mp, P, list_cap, obs_cap, d_counts, d_fixed_kf, d_list_slot, d_positions, d_obs32);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
-  }
+    return win_enqueue(h, who, mp, P, list_cap, obs_cap, d_counts, nullptr, d_fixed_kf, d_list_slot, d_positions, d_obs32);
+  });
 }
 
 int orbx_map_collect_inertial_window(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_chain, const int* chain,
                                      int list_cap, int obs_cap, int* counts, int* fixed_kf, int* list_slot, double* positions, orbx_ba_obs32* obs32) {
   static const char* who = "orbx_map_collect_inertial_window";
   if (!h) return ORBX_ERR_INVALID;
-  try {
-    BicPlan P;
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
     if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
-    const size_t bound = (size_t)P.S.bound_off[1], nf = (size_t)P.n_feat, K = (size_t)n_kfs;
-    if (list_cap < (int)bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, (int)bound, P.n_feat);
-    if (!counts || !fixed_kf || (bound > 0 && (!list_slot || !positions)) || (nf > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-    ORBX_HIP(h, hipSetDevice(h->device));
-    // the sizes first (counts, fixed keyframes), then as many rows as they say: two downloads, nothing sized by a bound
-    Carve out;
-    const size_t o_cn = out.take(16), o_fx = out.take(4 * K);
-    const size_t head = out.off;
-    const size_t o_ls = out.take(4 * bound), o_po = out.take(24 * bound), o_ob = out.take(16 * nf);
-    if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
-    if (int rc = orbx_reserve_pinned(h, h->pin_map, head)) return rc;
-    uint8_t* d = (uint8_t*)h->ws_map[1].p;
-    if (int rc = bic_enqueue(h, who, mp, P, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_fx), (int*)(d + o_ls), (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
-      return rc;
-    uint8_t* hp = (uint8_t*)h->pin_map.p;
-    ORBX_HIP(h, hipMemcpyAsync(hp, d, head, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    std::memcpy(counts, hp + o_cn, 16); std::memcpy(fixed_kf, hp + o_fx, 4 * K);
-    const size_t M = (size_t)counts[2], N = (size_t)counts[3];
-    if (M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);   // local_inertial_ba.rs:946-948
-    Carve rows;
-    const size_t r_ls = rows.take(4 * M), r_po = rows.take(24 * M), r_ob = rows.take(16 * N);
-    if (int rc = orbx_reserve_pinned(h, h->pin_map, rows.off)) return rc;
-    hp = (uint8_t*)h->pin_map.p;
-    ORBX_HIP(h, hipMemcpyAsync(hp + r_ls, d + o_ls, 4 * M, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(hp + r_po, d + o_po, 24 * M, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(hp + r_ob, d + o_ob, 16 * N, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    std::memcpy(list_slot, hp + r_ls, 4 * M); std::memcpy(positions, hp + r_po, 24 * M); std::memcpy(obs32, hp + r_ob, 16 * N);
-    return ORBX_OK;
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
-  }
+    return win_collect_host(h, who, mp, P, list_cap, obs_cap, counts, nullptr, fixed_kf, list_slot, positions, obs32);
+  });
 }
 
 int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, orbx_map_points* mp, int n_kfs,
@@ -2746,12 +2728,12 @@ int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orb
                                double* bias_out, int* fixed_kf_out, int* counts_out, int* iterations, double* initial_error, double* final_error) {
   static const char* who = "orbx_map_local_inertial_ba";
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || !cfg || !fixed_kf_out || !counts_out || !iterations || !initial_error || !final_error || E < 0 || (E > 0 && (!edge_kf || !preint)) ||
-      (n_chain > 0 && (!velocities || !biases || !poses_wc_out || !vel_out || !bias_out)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the inertial solve is not partitioned: no all-reduce hook or communicator", who);
-  try {
-    BicPlan P;
+  return orbx_guard(h, who, [&]() -> int {
+    if (!cam || !cfg || !fixed_kf_out || !counts_out || !iterations || !initial_error || !final_error || E < 0 || (E > 0 && (!edge_kf || !preint)) ||
+        (n_chain > 0 && (!velocities || !biases || !poses_wc_out || !vel_out || !bias_out)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the inertial solve is not partitioned: no all-reduce hook or communicator", who);
+    WinPlan P;
     if (int rc = bic_plan(h, who, mp, n_kfs, kfs, n_chain, chain, P)) return rc;
     // the solver's own refusals, made before the collection is enqueued (ba_check_inertial repeats them)
     if (n_chain > BA_INERTIAL_MAX_K) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most %d keyframes per inertial window", who, BA_INERTIAL_MAX_K);
@@ -2760,154 +2742,129 @@ int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orb
       if (i < 0 || i >= n_chain || j < 0 || j >= n_chain) return orbx_fail(h, ORBX_ERR_INVALID, "%s: IMU edge %d: keyframe index out of range", who, e);
       if (i == j) return orbx_fail(h, ORBX_ERR_INVALID, "%s: IMU edge %d: both ends are keyframe %d", who, e, i);
     }
-    *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
-    const size_t bound = (size_t)P.S.bound_off[1], nf = (size_t)P.n_feat, K = (size_t)n_kfs;
-    ORBX_HIP(h, hipSetDevice(h->device));
-    // phase 1 (collect_inertial_ba_data, :930-1030) on the device; ONE download: counts | fixed | P's slots | P's positions
-    Carve out;
-    const size_t o_cn = out.take(16), o_fx = out.take(4 * K), o_ls = out.take(4 * bound), o_po = out.take(24 * bound);
-    const size_t down = out.off;
-    const size_t o_ob = out.take(16 * nf);
-    if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
-    if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
-    uint8_t* d = (uint8_t*)h->ws_map[1].p;
-    orbx_prof_begin_call(h);
-    if (int rc = bic_enqueue(h, who, mp, P, (int)bound, P.n_feat, (int*)(d + o_cn), (int*)(d + o_fx), (int*)(d + o_ls), (double*)(d + o_po), (orbx_ba_obs32*)(d + o_ob)))
-      return rc;
-    uint8_t* hp = (uint8_t*)h->pin_map.p;
-    ORBX_HIP(h, hipMemcpyAsync(hp, d, down, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    const int* cn = (const int*)(hp + o_cn);
-    const int* fx = (const int*)(hp + o_fx);
-    const int Kw = cn[0], F = cn[1], M = cn[2], N = cn[3];
-    std::memcpy(counts_out, cn, 16); std::memcpy(fixed_kf_out, fx, 4 * K);
-    if (M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);   // :946-948
-    // T_wc of the chain as it is; T_cw of the anchor and the other fixed observers (:973-978)
-    std::vector<double> poses_wc(7 * (size_t)Kw), fixed_cw(7 * (size_t)F), points((const double*)(hp + o_po), (const double*)(hp + o_po) + 3 * (size_t)M);
-    std::vector<int> slots((const int*)(hp + o_ls), (const int*)(hp + o_ls) + M);
-    for (int i = 0; i < Kw; ++i) std::memcpy(&poses_wc[7 * (size_t)i], kfs[chain[i]]->pose_wc, 56);
-    bac_pose_inverse(kfs[chain[0]]->pose_wc, &fixed_cw[0]);
-    for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
-    // phase 2 (solve_inertial_ba, :1074-1275) on the observations where they lie
-    orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
-    BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
-    if (int rc = ba_solve_visual(h, cam, &vc, Kw, poses_wc.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
-                                 initial_error, final_error, false, &in, (const orbx_ba_obs32*)(d + o_ob), true))
-      return rc;
-    // phase 3, the point half of apply_inertial_ba_results (local_mapper.rs:363: only a solve that iterated is applied)
-    if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
-    return ORBX_OK;
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
-  }
+    const orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
+    const BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
+    return win_local_ba(h, who, cam, &vc, &in, mp, kfs, P, should_stop, user, nullptr, fixed_kf_out, poses_wc_out, counts_out, iterations, initial_error,
+                        final_error);
+  });
 }
 
 int orbx_map_observations_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, int obs_cap,
                                  int* d_obs_start, int* d_obs_kf, int* d_obs_feat) {
   static const char* who = "orbx_map_observations_device";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
-  return obs_lists_call(h, who, mp, P, M, slots, obs_cap, d_obs_start, d_obs_kf, d_obs_feat);
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+    return obs_lists_call(h, who, mp, P, M, slots, obs_cap, d_obs_start, d_obs_kf, d_obs_feat);
+  });
 }
 
 int orbx_map_observations(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, int obs_cap, int* obs_start,
                           int* obs_kf, int* obs_feat) {
   static const char* who = "orbx_map_observations";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
-  if (obs_cap < P.n_feat || !obs_start || (P.n_feat > 0 && M > 0 && (!obs_kf || !obs_feat)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (obs_cap %d must reach the observations' bound %d: the features of kfs[] summed)", who, obs_cap, P.n_feat);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t Mz = (size_t)M, Nb = (size_t)obs_entry_bound(P, M);
-  Carve out;
-  const size_t o_os = out.take(4 * (Mz + 1)), o_ok = out.take(4 * Nb), o_of = out.take(4 * Nb);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  if (int rc = obs_lists_call(h, who, mp, P, M, slots, P.n_feat, (int*)(c.dout + o_os), (int*)(c.dout + o_ok), (int*)(c.dout + o_of))) return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(obs_start, c.ho + o_os, 4 * (Mz + 1));
-  const size_t N = (size_t)obs_start[M];
-  if (N) { std::memcpy(obs_kf, c.ho + o_ok, 4 * N); std::memcpy(obs_feat, c.ho + o_of, 4 * N); }
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+    if (obs_cap < P.n_feat || !obs_start || (P.n_feat > 0 && M > 0 && (!obs_kf || !obs_feat)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (obs_cap %d must reach the observations' bound %d: the features of kfs[] summed)", who, obs_cap, P.n_feat);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t Mz = (size_t)M, Nb = (size_t)obs_entry_bound(P, M);
+    Carve out;
+    const size_t o_os = out.take(4 * (Mz + 1)), o_ok = out.take(4 * Nb), o_of = out.take(4 * Nb);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    if (int rc = obs_lists_call(h, who, mp, P, M, slots, P.n_feat, (int*)(c.dout + o_os), (int*)(c.dout + o_ok), (int*)(c.dout + o_of))) return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(obs_start, c.ho + o_os, 4 * (Mz + 1));
+    const size_t N = (size_t)obs_start[M];
+    if (N) { std::memcpy(obs_kf, c.ho + o_ok, 4 * N); std::memcpy(obs_feat, c.ho + o_of, 4 * N); }
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_refresh_points_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, double scale_range,
                                    uint8_t* d_mp_desc, double* d_normals, double* d_min_distance, double* d_max_distance, orbx_mp_refresh_record* d_records) {
   static const char* who = "orbx_map_refresh_points_device";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
-  if (M == 0) return ORBX_OK;
-  if (!d_mp_desc || !d_normals || !d_min_distance || !d_max_distance || !d_records || ((uintptr_t)d_mp_desc & 7) || ((uintptr_t)d_normals & 7))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc and d_normals are 8-byte aligned)", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  return obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, d_normals, d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records);
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+    if (M == 0) return ORBX_OK;
+    if (!d_mp_desc || !d_normals || !d_min_distance || !d_max_distance || !d_records || ((uintptr_t)d_mp_desc & 7) || ((uintptr_t)d_normals & 7))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_mp_desc and d_normals are 8-byte aligned)", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    return obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, d_normals, d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records);
+  });
 }
 
 int orbx_map_refresh_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* slots, double scale_range,
                             uint8_t* mp_desc, double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
   static const char* who = "orbx_map_refresh_points";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
-  if (M == 0) return ORBX_OK;
-  if (!mp_desc || !normals || !min_distance || !max_distance || !records) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // the normals up (they are kept where no observer is far enough), one blob down: [mp_desc | normals | min | max | records]
-  const size_t Mz = (size_t)M;
-  Carve in, out;
-  const size_t i_nr = in.take(24 * Mz);
-  const size_t o_md = out.take(32 * Mz), o_nr = out.take(24 * Mz), o_mn = out.take(8 * Mz), o_mx = out.take(8 * Mz), o_rc = out.take(sizeof(orbx_mp_refresh_record) * Mz);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
-  std::memcpy(c.hi + i_nr, normals, 24 * Mz);
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  if (int rc = obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, (const double*)(c.di + i_nr), c.dout + o_md, (double*)(c.dout + o_nr),
-                                   (double*)(c.dout + o_mn), (double*)(c.dout + o_mx), (orbx_mp_refresh_record*)(c.dout + o_rc)))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(mp_desc, c.ho + o_md, 32 * Mz); std::memcpy(normals, c.ho + o_nr, 24 * Mz);
-  std::memcpy(min_distance, c.ho + o_mn, 8 * Mz); std::memcpy(max_distance, c.ho + o_mx, 8 * Mz);
-  std::memcpy(records, c.ho + o_rc, sizeof(orbx_mp_refresh_record) * Mz);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = obs_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = obs_check_slots(mp, who, slots, M)) return rc;
+    if (M == 0) return ORBX_OK;
+    if (!mp_desc || !normals || !min_distance || !max_distance || !records) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // the normals up (they are kept where no observer is far enough), one blob down: [mp_desc | normals | min | max | records]
+    const size_t Mz = (size_t)M;
+    Carve in, out;
+    const size_t i_nr = in.take(24 * Mz);
+    const size_t o_md = out.take(32 * Mz), o_nr = out.take(24 * Mz), o_mn = out.take(8 * Mz), o_mx = out.take(8 * Mz), o_rc = out.take(sizeof(orbx_mp_refresh_record) * Mz);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
+    std::memcpy(c.hi + i_nr, normals, 24 * Mz);
+    if (int rc = orbx_host_call_upload(h, c)) return rc;
+    if (int rc = obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, (const double*)(c.di + i_nr), c.dout + o_md, (double*)(c.dout + o_nr),
+                                     (double*)(c.dout + o_mn), (double*)(c.dout + o_mx), (orbx_mp_refresh_record*)(c.dout + o_rc)))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(mp_desc, c.ho + o_md, 32 * Mz); std::memcpy(normals, c.ho + o_nr, 24 * Mz);
+    std::memcpy(min_distance, c.ho + o_mn, 8 * Mz); std::memcpy(max_distance, c.ho + o_mx, 8 * Mz);
+    std::memcpy(records, c.ho + o_rc, sizeof(orbx_mp_refresh_record) * Mz);
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_keyframe_redundancy_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand, const int* cand,
                                         int min_observations, double threshold, int* d_total, int* d_redundant, uint8_t* d_cull) {
   static const char* who = "orbx_map_keyframe_redundancy_device";
   if (!h) return ORBX_ERR_INVALID;
-  RedPlan P;
-  if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
-  if (n_cand == 0) return ORBX_OK;
-  return red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, d_total, d_redundant, d_cull);
+  return orbx_guard(h, who, [&]() -> int {
+    RedPlan P;
+    if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
+    if (n_cand == 0) return ORBX_OK;
+    return red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, d_total, d_redundant, d_cull);
+  });
 }
 
 int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_cand, const int* cand,
                                  int min_observations, double threshold, int* total, int* redundant, uint8_t* cull) {
   static const char* who = "orbx_map_keyframe_redundancy";
   if (!h) return ORBX_ERR_INVALID;
-  RedPlan P;
-  if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
-  if (n_cand == 0) return ORBX_OK;
-  if (!total || !redundant || !cull) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t NC = (size_t)n_cand;
-  Carve out;
-  const size_t o_to = out.take(4 * NC), o_re = out.take(4 * NC), o_cu = out.take(NC);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  if (int rc = red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, (int*)(c.dout + o_to), (int*)(c.dout + o_re), c.dout + o_cu)) return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(total, c.ho + o_to, 4 * NC); std::memcpy(redundant, c.ho + o_re, 4 * NC); std::memcpy(cull, c.ho + o_cu, NC);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    RedPlan P;
+    if (int rc = red_plan(h, who, mp, n_kfs, kfs, n_cand, cand, min_observations, P)) return rc;
+    if (n_cand == 0) return ORBX_OK;
+    if (!total || !redundant || !cull) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t NC = (size_t)n_cand;
+    Carve out;
+    const size_t o_to = out.take(4 * NC), o_re = out.take(4 * NC), o_cu = out.take(NC);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    if (int rc = red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, (int*)(c.dout + o_to), (int*)(c.dout + o_re), c.dout + o_cu)) return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(total, c.ho + o_to, 4 * NC); std::memcpy(redundant, c.ho + o_re, 4 * NC); std::memcpy(cull, c.ho + o_cu, NC);
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences,
@@ -2918,52 +2875,56 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
                                     uint8_t* d_inlier_out, double* d_err_out, orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results) {
   static const char* who = "orbx_map_track_reference_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
-  if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && !kfs))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
-  if (!mp || mp->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
-  if (n_frames == 0) return ORBX_OK;
-  const size_t B = (size_t)n_frames;
-  std::vector<TrackRefItem> items(B);
-  std::vector<MapRefItem> tab(B);
-  long long K = 0;
-  int max_n = 0;
-  for (size_t b = 0; b < B; ++b) {
-    const orbx_keyframe* kf = kfs[b];
-    if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, (int)b);
-    if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, (int)b);
-    if (K + kf->n > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: too many keyframe features", who);
-    items[b].kf_desc = kf->d_desc; items[b].kf_off = (int)K; items[b].n = kf->n;
-    tab[b] = MapRefItem{kf->slot_store ? kf->d_mp_slot : nullptr, (int)K, kf->n};
-    K += kf->n; max_n = std::max(max_n, kf->n);
-  }
-  if (K > 0 && (!d_kf_positions || !d_kf_valid)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (max_n > 0) {
-    uint8_t *hs, *ds;
-    if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B, &hs, &ds)) return rc;
-    std::memcpy(hs, tab.data(), sizeof(MapRefItem) * B);
-    if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B)) return rc;
-    ProfScope ps(h, "map_ref_gather_kernel");
-    hipLaunchKernelGGL(map_ref_gather_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, n_frames), dim3(MS_THREADS), 0, h->stream, (const MapRefItem*)ds,
-                       mp->d_live, mp->d_pos, mp->capacity, d_kf_positions, d_kf_valid);
-  }
-  ORBX_HIP(h, hipGetLastError());
-  return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
-                                 max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
-                                 d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = orbx_pnp_check_config(h, pnp_cfg, who)) return rc;
+    if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && !kfs))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
+    if (int rc = ms_check_store(h, who, mp)) return rc;
+    if (n_frames == 0) return ORBX_OK;
+    const size_t B = (size_t)n_frames;
+    std::vector<TrackRefItem> items(B);
+    std::vector<MapRefItem> tab(B);
+    long long K = 0;
+    int max_n = 0;
+    for (size_t b = 0; b < B; ++b) {
+      const orbx_keyframe* kf = kfs[b];
+      if (!kf || kf->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d is null or of another handle", who, (int)b);
+      if (kf->slot_store && kf->slot_store != mp) return orbx_fail(h, ORBX_ERR_INVALID, "%s: keyframe %d's slot table belongs to another store", who, (int)b);
+      if (K + kf->n > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: too many keyframe features", who);
+      items[b].kf_desc = kf->d_desc; items[b].kf_off = (int)K; items[b].n = kf->n;
+      tab[b] = MapRefItem{kf->slot_store ? kf->d_mp_slot : nullptr, (int)K, kf->n};
+      K += kf->n; max_n = std::max(max_n, kf->n);
+    }
+    if (K > 0 && (!d_kf_positions || !d_kf_valid)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (max_n > 0) {
+      uint8_t *hs, *ds;
+      if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B, &hs, &ds)) return rc;
+      std::memcpy(hs, tab.data(), sizeof(MapRefItem) * B);
+      if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B)) return rc;
+      ProfScope ps(h, "map_ref_gather_kernel");
+      hipLaunchKernelGGL(map_ref_gather_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, n_frames), dim3(MS_THREADS), 0, h->stream, (const MapRefItem*)ds,
+                         mp->d_live, mp->d_pos, mp->capacity, d_kf_positions, d_kf_valid);
+    }
+    ORBX_HIP(h, hipGetLastError());
+    return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
+                                   max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d, d_kf_idx,
+                                   d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  });
 }
 
 int orbx_keyframe_get_map_point_slots(const orbx_keyframe* kf, int* slots) {
   if (!kf) return ORBX_ERR_INVALID;
   orbx_handle* h = kf->h;
-  if (kf->n > 0 && !slots) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_get_map_point_slots: bad argument");
-  if (kf->n == 0) return ORBX_OK;
-  if (!kf->slot_store) { std::fill(slots, slots + kf->n, -1); return ORBX_OK; }       // no table: every feature -1
-  ORBX_HIP(h, hipSetDevice(h->device));
-  ORBX_HIP(h, hipMemcpyAsync(slots, kf->d_mp_slot, 4 * (size_t)kf->n, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_keyframe_get_map_point_slots", [&]() -> int {
+    if (kf->n > 0 && !slots) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_get_map_point_slots: bad argument");
+    if (kf->n == 0) return ORBX_OK;
+    if (!kf->slot_store) { std::fill(slots, slots + kf->n, -1); return ORBX_OK; }       // no table: every feature -1
+    ORBX_HIP(h, hipSetDevice(h->device));
+    ORBX_HIP(h, hipMemcpyAsync(slots, kf->d_mp_slot, 4 * (size_t)kf->n, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_fuse_device(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src, int n_tgt,
@@ -2971,47 +2932,51 @@ int orbx_map_fuse_device(orbx_handle* h, const orbx_camera* cam, orbx_map_points
                          int* d_keeper) {
   static const char* who = "orbx_map_fuse_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
-  long long cand = 0;                                                       // L's bound, before anything is touched: the candidates, at most the capacity
-  for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
-  const long long bound = std::min<long long>(cand, mp->capacity);
-  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
-  if (!d_counts || (bound > 0 && !d_list_slot) || (bound > 0 && n_tgt > 0 && (!d_match || !d_goner || !d_keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
-  MfPlan P;
-  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
-  return mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, d_counts, d_list_slot, d_match, d_goner, d_keeper);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
+    long long cand = 0;                                                       // L's bound, before anything is touched: the candidates, at most the capacity
+    for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
+    const long long bound = std::min<long long>(cand, mp->capacity);
+    if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
+    if (!d_counts || (bound > 0 && !d_list_slot) || (bound > 0 && n_tgt > 0 && (!d_match || !d_goner || !d_keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
+    MfPlan P;
+    if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
+    return mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, d_counts, d_list_slot, d_match, d_goner, d_keeper);
+  });
 }
 
 int orbx_map_fuse(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src, int n_tgt, const int* tgt,
                   double radius_scale, unsigned desc_threshold, int list_cap, int* counts, int* list_slot, int* match, int* goner, int* keeper) {
   static const char* who = "orbx_map_fuse";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
-  long long cand = 0;
-  for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
-  const long long bound = std::min<long long>(cand, mp->capacity);
-  if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
-  if (!counts || (bound > 0 && !list_slot) || (bound > 0 && n_tgt > 0 && (!match || !goner || !keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
-  MfPlan P;
-  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
-  const size_t B = (size_t)P.bound, T = (size_t)n_tgt, Gb = (size_t)P.goner_bound;
-  Carve out;
-  const size_t o_cn = out.take(16), o_go = out.take(4 * Gb), o_ke = out.take(4 * Gb), o_ls = out.take(4 * B), o_ma = out.take(4 * B * T);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  orbx_prof_begin_call(h);
-  if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, (int*)(c.dout + o_cn), (int*)(c.dout + o_ls), (int*)(c.dout + o_ma), (int*)(c.dout + o_go),
-                          (int*)(c.dout + o_ke)))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(counts, c.ho + o_cn, 16);
-  const size_t Pn = (size_t)counts[0], G = (size_t)counts[3];
-  if (Pn) std::memcpy(list_slot, c.ho + o_ls, 4 * Pn);
-  if (Pn && T) std::memcpy(match, c.ho + o_ma, 4 * Pn * T);
-  if (G) { std::memcpy(goner, c.ho + o_go, 4 * G); std::memcpy(keeper, c.ho + o_ke, 4 * G); }
-  return G ? orbx_map_points_erase(mp, goner, (int)G) : ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, desc_threshold)) return rc;
+    long long cand = 0;
+    for (int i = 0; i < n_src; ++i) cand += kfs[src[i]]->n;
+    const long long bound = std::min<long long>(cand, mp->capacity);
+    if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (the features of kfs[src[..]], at most the capacity)", who, list_cap, (int)bound);
+    if (!counts || (bound > 0 && !list_slot) || (bound > 0 && n_tgt > 0 && (!match || !goner || !keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (int rc = mf_give_tables(h, mp, kfs, n_tgt, tgt)) return rc;
+    MfPlan P;
+    if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
+    const size_t B = (size_t)P.bound, T = (size_t)n_tgt, Gb = (size_t)P.goner_bound;
+    Carve out;
+    const size_t o_cn = out.take(16), o_go = out.take(4 * Gb), o_ke = out.take(4 * Gb), o_ls = out.take(4 * B), o_ma = out.take(4 * B * T);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    orbx_prof_begin_call(h);
+    if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, (int*)(c.dout + o_cn), (int*)(c.dout + o_ls), (int*)(c.dout + o_ma), (int*)(c.dout + o_go),
+                            (int*)(c.dout + o_ke)))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(counts, c.ho + o_cn, 16);
+    const size_t Pn = (size_t)counts[0], G = (size_t)counts[3];
+    if (Pn) std::memcpy(list_slot, c.ho + o_ls, 4 * Pn);
+    if (Pn && T) std::memcpy(match, c.ho + o_ma, 4 * Pn * T);
+    if (G) { std::memcpy(goner, c.ho + o_go, 4 * G); std::memcpy(keeper, c.ho + o_ke, 4 * G); }
+    return G ? orbx_map_points_erase(mp, goner, (int)G) : ORBX_OK;
+  });
 }
 
 int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int cur, int n_nb, const int* nb,
@@ -3020,86 +2985,90 @@ int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_ma
                                  double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
   static const char* who = "orbx_map_search_in_neighbors";
   if (!h) return ORBX_ERR_INVALID;
-  if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
-  if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, 1, &cur, n_nb, nb, desc_threshold)) return rc;
-  for (int i = 0; i < n_nb; ++i)
-    if (nb[i] == cur) return orbx_fail(h, ORBX_ERR_INVALID, "%s: nb[%d] is the current keyframe", who, i);
-  // the three lists' bounds, before anything is touched
-  long long f_nb = 0;
-  for (int i = 0; i < n_nb; ++i) f_nb += kfs[nb[i]]->n;
-  const long long cap = mp->capacity, f_cur = kfs[cur]->n;
-  const long long gb_a = std::min(f_cur, cap) + f_nb, gb_b = std::min(f_nb, cap) + f_cur, ab = std::min(f_cur + f_nb, cap);
-  if (f_cur + f_nb > 0x7fffffff) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
-  if (goner_cap < std::max(gb_a, gb_b)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: goner_cap %d is below the passes' bound %d", who, goner_cap, (int)std::max(gb_a, gb_b));
-  if (affected_cap < ab) return orbx_fail(h, ORBX_ERR_INVALID, "%s: affected_cap %d is below the list's bound %d (the features of cur and nb[], at most the capacity)", who, affected_cap, (int)ab);
-  if (!counts || !n_affected || (gb_a > 0 && (!goner_a || !keeper_a || !goner_b || !keeper_b)) ||
-      (ab > 0 && (!affected_slot || !mp_desc || !normals || !min_distance || !max_distance || !records)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  std::vector<int> both((size_t)n_nb + 1);
-  both[0] = cur;
-  for (int i = 0; i < n_nb; ++i) both[(size_t)i + 1] = nb[i];
-  if (int rc = mf_give_tables(h, mp, kfs, n_nb + 1, both.data())) return rc;
-  MfPlan A, B;
-  SelPlan S;
-  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, 1, &cur, n_nb, nb, A)) return rc;
-  if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_nb, nb, 1, &cur, B)) return rc;
-  std::vector<const orbx_keyframe*> ak((size_t)n_nb + 1);
-  for (size_t i = 0; i < ak.size(); ++i) ak[i] = kfs[both[i]];
-  const int aoff[2] = {0, n_nb + 1};
-  if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ak.data(), aoff, nullptr, S)) return rc;
-  const size_t Ta = (size_t)n_nb, Ba = (size_t)A.bound, Bb = (size_t)B.bound, Ga = (size_t)A.goner_bound, Gb = (size_t)B.goner_bound, Ab = (size_t)S.bound_off[1];
-  // ONE download: counts A | counts B | goners and keepers of A, of B | the affected list; behind it what stays on the device
-  Carve out;
-  const size_t o_cn = out.take(32), o_ga = out.take(4 * Ga), o_ka = out.take(4 * Ga), o_gb = out.take(4 * Gb), o_kb = out.take(4 * Gb), o_ao = out.take(8),
-               o_as = out.take(4 * Ab);
-  const size_t down = out.off;
-  const size_t o_la = out.take(4 * Ba), o_ma = out.take(4 * Ba * Ta), o_lb = out.take(4 * Bb), o_mb = out.take(4 * Bb), o_ap = out.take(24 * Ab), o_ad = out.take(32 * Ab);
-  // (the refresh below is a host form of its own: it takes the pinned buffer and the blob workspace once everything is copied out of them)
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  uint8_t* d = c.dout;
-  orbx_prof_begin_call(h);
-  if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, (int*)(d + o_cn), (int*)(d + o_la), (int*)(d + o_ma), (int*)(d + o_ga), (int*)(d + o_ka))) return rc;
-  if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, (int*)(d + o_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), (int*)(d + o_gb), (int*)(d + o_kb))) return rc;
-  if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, (int*)(d + o_ao), (int*)(d + o_as), (double*)(d + o_ap), d + o_ad))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, down)) return rc;
-  std::memcpy(counts, c.ho + o_cn, 32);
-  const size_t na = (size_t)counts[3], nbg = (size_t)counts[7], M = (size_t)((const int*)(c.ho + o_ao))[1];
-  if (na) { std::memcpy(goner_a, c.ho + o_ga, 4 * na); std::memcpy(keeper_a, c.ho + o_ka, 4 * na); }
-  if (nbg) { std::memcpy(goner_b, c.ho + o_gb, 4 * nbg); std::memcpy(keeper_b, c.ho + o_kb, 4 * nbg); }
-  *n_affected = (int)M;
-  if (M) std::memcpy(affected_slot, c.ho + o_as, 4 * M);
-  if (na) if (int rc = orbx_map_points_erase(mp, goner_a, (int)na)) return rc;
-  if (nbg) if (int rc = orbx_map_points_erase(mp, goner_b, (int)nbg)) return rc;
-  if (M == 0) return ORBX_OK;
-  for (size_t i = 0; i < M; ++i) {
-    const double* v = slot_normals ? slot_normals + 3 * (size_t)affected_slot[i] : nullptr;
-    normals[3 * i] = v ? v[0] : 0.0; normals[3 * i + 1] = v ? v[1] : 0.0; normals[3 * i + 2] = v ? v[2] : 0.0;
-  }
-  return orbx_map_refresh_points(h, mp, n_kfs, kfs, (int)M, affected_slot, scale_range, mp_desc, normals, min_distance, max_distance, records);
+  return orbx_guard(h, who, [&]() -> int {
+    if (n_kfs <= 0 || cur < 0 || cur >= n_kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: cur = %d is outside [0, n_kfs = %d)", who, cur, n_kfs);
+    if (int rc = mf_check(h, who, cam, mp, n_kfs, kfs, 1, &cur, n_nb, nb, desc_threshold)) return rc;
+    for (int i = 0; i < n_nb; ++i)
+      if (nb[i] == cur) return orbx_fail(h, ORBX_ERR_INVALID, "%s: nb[%d] is the current keyframe", who, i);
+    // the three lists' bounds, before anything is touched
+    long long f_nb = 0;
+    for (int i = 0; i < n_nb; ++i) f_nb += kfs[nb[i]]->n;
+    const long long cap = mp->capacity, f_cur = kfs[cur]->n;
+    const long long gb_a = std::min(f_cur, cap) + f_nb, gb_b = std::min(f_nb, cap) + f_cur, ab = std::min(f_cur + f_nb, cap);
+    if (int rc = ms_check_feature_total(h, who, f_cur + f_nb)) return rc;
+    if (goner_cap < std::max(gb_a, gb_b)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: goner_cap %d is below the passes' bound %d", who, goner_cap, (int)std::max(gb_a, gb_b));
+    if (affected_cap < ab) return orbx_fail(h, ORBX_ERR_INVALID, "%s: affected_cap %d is below the list's bound %d (the features of cur and nb[], at most the capacity)", who, affected_cap, (int)ab);
+    if (!counts || !n_affected || (gb_a > 0 && (!goner_a || !keeper_a || !goner_b || !keeper_b)) ||
+        (ab > 0 && (!affected_slot || !mp_desc || !normals || !min_distance || !max_distance || !records)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    std::vector<int> both((size_t)n_nb + 1);
+    both[0] = cur;
+    for (int i = 0; i < n_nb; ++i) both[(size_t)i + 1] = nb[i];
+    if (int rc = mf_give_tables(h, mp, kfs, n_nb + 1, both.data())) return rc;
+    MfPlan A, B;
+    SelPlan S;
+    if (int rc = mf_plan(h, who, mp, n_kfs, kfs, 1, &cur, n_nb, nb, A)) return rc;
+    if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_nb, nb, 1, &cur, B)) return rc;
+    std::vector<const orbx_keyframe*> ak((size_t)n_nb + 1);
+    for (size_t i = 0; i < ak.size(); ++i) ak[i] = kfs[both[i]];
+    const int aoff[2] = {0, n_nb + 1};
+    if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ak.data(), aoff, nullptr, S)) return rc;
+    const size_t Ta = (size_t)n_nb, Ba = (size_t)A.bound, Bb = (size_t)B.bound, Ga = (size_t)A.goner_bound, Gb = (size_t)B.goner_bound, Ab = (size_t)S.bound_off[1];
+    // ONE download: counts A | counts B | goners and keepers of A, of B | the affected list; behind it what stays on the device
+    Carve out;
+    const size_t o_cn = out.take(32), o_ga = out.take(4 * Ga), o_ka = out.take(4 * Ga), o_gb = out.take(4 * Gb), o_kb = out.take(4 * Gb), o_ao = out.take(8),
+                 o_as = out.take(4 * Ab);
+    const size_t down = out.off;
+    const size_t o_la = out.take(4 * Ba), o_ma = out.take(4 * Ba * Ta), o_lb = out.take(4 * Bb), o_mb = out.take(4 * Bb), o_ap = out.take(24 * Ab), o_ad = out.take(32 * Ab);
+    // (the refresh below is a host form of its own: it takes the pinned buffer and the blob workspace once everything is copied out of them)
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    uint8_t* d = c.dout;
+    orbx_prof_begin_call(h);
+    if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, (int*)(d + o_cn), (int*)(d + o_la), (int*)(d + o_ma), (int*)(d + o_ga), (int*)(d + o_ka))) return rc;
+    if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, (int*)(d + o_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), (int*)(d + o_gb), (int*)(d + o_kb))) return rc;
+    if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, (int*)(d + o_ao), (int*)(d + o_as), (double*)(d + o_ap), d + o_ad))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, down)) return rc;
+    std::memcpy(counts, c.ho + o_cn, 32);
+    const size_t na = (size_t)counts[3], nbg = (size_t)counts[7], M = (size_t)((const int*)(c.ho + o_ao))[1];
+    if (na) { std::memcpy(goner_a, c.ho + o_ga, 4 * na); std::memcpy(keeper_a, c.ho + o_ka, 4 * na); }
+    if (nbg) { std::memcpy(goner_b, c.ho + o_gb, 4 * nbg); std::memcpy(keeper_b, c.ho + o_kb, 4 * nbg); }
+    *n_affected = (int)M;
+    if (M) std::memcpy(affected_slot, c.ho + o_as, 4 * M);
+    if (na) if (int rc = orbx_map_points_erase(mp, goner_a, (int)na)) return rc;
+    if (nbg) if (int rc = orbx_map_points_erase(mp, goner_b, (int)nbg)) return rc;
+    if (M == 0) return ORBX_OK;
+    for (size_t i = 0; i < M; ++i) {
+      const double* v = slot_normals ? slot_normals + 3 * (size_t)affected_slot[i] : nullptr;
+      normals[3 * i] = v ? v[0] : 0.0; normals[3 * i + 1] = v ? v[1] : 0.0; normals[3 * i + 2] = v ? v[2] : 0.0;
+    }
+    return orbx_map_refresh_points(h, mp, n_kfs, kfs, (int)M, affected_slot, scale_range, mp_desc, normals, min_distance, max_distance, records);
+  });
 }
 
 int orbx_keyframe_set_map_point_slots_device(orbx_keyframe* kf, const orbx_map_points* mp, const int* d_slots) {
   static const char* who = "orbx_keyframe_set_map_point_slots_device";
   if (!kf) return ORBX_ERR_INVALID;
   orbx_handle* h = kf->h;
-  if (!mp || mp->h != h || !d_slots || ((uintptr_t)d_slots & 3)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle, or d_slots is null or not 4-byte aligned", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (kf->n > 0) {
-    const dim3 grid((kf->n + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
-    {
-      ProfScope ps(h, "mc_table_kernel");
-      hipLaunchKernelGGL(mc_table_kernel, grid, block, 0, h->stream, d_slots, kf->n, mp->capacity, kf->d_mp_slot);
+  return orbx_guard(h, who, [&]() -> int {
+    if (!mp || mp->h != h || !d_slots || ((uintptr_t)d_slots & 3)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle, or d_slots is null or not 4-byte aligned", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (kf->n > 0) {
+      const dim3 grid((kf->n + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
+      {
+        ProfScope ps(h, "mc_table_kernel");
+        hipLaunchKernelGGL(mc_table_kernel, grid, block, 0, h->stream, d_slots, kf->n, mp->capacity, kf->d_mp_slot);
+      }
+      {
+        ProfScope ps(h, "mc_uniq_one_kernel", true);
+        hipLaunchKernelGGL(mc_uniq_one_kernel, grid, block, 0, h->stream, (const int*)kf->d_mp_slot, kf->d_mp_uniq, kf->n);
+      }
+      ORBX_HIP(h, hipGetLastError());
     }
-    {
-      ProfScope ps(h, "mc_uniq_one_kernel", true);
-      hipLaunchKernelGGL(mc_uniq_one_kernel, grid, block, 0, h->stream, (const int*)kf->d_mp_slot, kf->d_mp_uniq, kf->n);
-    }
-    ORBX_HIP(h, hipGetLastError());
-  }
-  kf->slot_store = mp;
-  return ORBX_OK;
+    kf->slot_store = mp;
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_create_points_device(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, orbx_map_points* mp,
@@ -3107,12 +3076,14 @@ int orbx_map_create_points_device(orbx_handle* h, const orbx_camera* cam, const 
                                   int* d_new_slot, int* d_new_neighbour, int* d_new_idx1, int* d_new_idx2, double* d_new_points, uint8_t* d_new_desc, int* d_stats) {
   static const char* who = "orbx_map_create_points_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
-  if (!d_counts || (T > 0 && !d_stats) || (n_free > 0 && (!d_new_slot || !d_new_neighbour || !d_new_idx1 || !d_new_idx2 || !d_new_points || !d_new_desc)) ||
-      ((uintptr_t)d_new_desc & 15))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_new_desc is 16-byte aligned)", who);
-  return mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, d_counts, d_new_slot, d_new_neighbour, d_new_idx1, d_new_idx2, d_new_points,
-                    d_new_desc, d_stats);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
+    if (!d_counts || (T > 0 && !d_stats) || (n_free > 0 && (!d_new_slot || !d_new_neighbour || !d_new_idx1 || !d_new_idx2 || !d_new_points || !d_new_desc)) ||
+        ((uintptr_t)d_new_desc & 15))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_new_desc is 16-byte aligned)", who);
+    return mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, d_counts, d_new_slot, d_new_neighbour, d_new_idx1, d_new_idx2, d_new_points,
+                      d_new_desc, d_stats);
+  });
 }
 
 int orbx_map_create_points(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_config* cfg, int is_inertial, orbx_map_points* mp, orbx_keyframe* cur,
@@ -3120,79 +3091,85 @@ int orbx_map_create_points(orbx_handle* h, const orbx_camera* cam, const orbx_tr
                            int* new_idx1, int* new_idx2, double* new_points, int* stats) {
   static const char* who = "orbx_map_create_points";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
-  if (!counts || (T > 0 && !stats) || (n_free > 0 && (!new_slot || !new_neighbour || !new_idx1 || !new_idx2 || !new_points)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // ONE download: counts | stats | the lists; the descriptors stay behind them for set_device
-  const size_t NF = (size_t)n_free, Tz = (size_t)T;
-  Carve out;
-  const size_t o_cn = out.take(16), o_st = out.take(16 * Tz), o_sl = out.take(4 * NF), o_nb = out.take(4 * NF), o_i1 = out.take(4 * NF), o_i2 = out.take(4 * NF),
-               o_pt = out.take(24 * NF);
-  const size_t down = out.off;
-  const size_t o_de = out.take(32 * NF);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-  uint8_t* d = c.dout;
-  if (int rc = mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, (int*)(d + o_cn), (int*)(d + o_sl), (int*)(d + o_nb), (int*)(d + o_i1),
-                          (int*)(d + o_i2), (double*)(d + o_pt), d + o_de, (int*)(d + o_st)))
-    return rc;
-  if (int rc = orbx_host_call_download(h, c, down)) return rc;
-  std::memcpy(counts, c.ho + o_cn, 16);
-  if (Tz) std::memcpy(stats, c.ho + o_st, 16 * Tz);
-  const size_t created = (size_t)counts[2];
-  if (created == 0) return ORBX_OK;
-  std::memcpy(new_slot, c.ho + o_sl, 4 * created); std::memcpy(new_neighbour, c.ho + o_nb, 4 * created);
-  std::memcpy(new_idx1, c.ho + o_i1, 4 * created); std::memcpy(new_idx2, c.ho + o_i2, 4 * created);
-  std::memcpy(new_points, c.ho + o_pt, 24 * created);
-  return ms_set(mp, who, free_slots, (int)created, (const double*)(d + o_pt), d + o_de, false);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = mc_check(h, who, cam, cfg, mp, cur, nbs, T, phases, free_slots, n_free)) return rc;
+    if (!counts || (T > 0 && !stats) || (n_free > 0 && (!new_slot || !new_neighbour || !new_idx1 || !new_idx2 || !new_points)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // ONE download: counts | stats | the lists; the descriptors stay behind them for set_device
+    const size_t NF = (size_t)n_free, Tz = (size_t)T;
+    Carve out;
+    const size_t o_cn = out.take(16), o_st = out.take(16 * Tz), o_sl = out.take(4 * NF), o_nb = out.take(4 * NF), o_i1 = out.take(4 * NF), o_i2 = out.take(4 * NF),
+                 o_pt = out.take(24 * NF);
+    const size_t down = out.off;
+    const size_t o_de = out.take(32 * NF);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    uint8_t* d = c.dout;
+    if (int rc = mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, (int*)(d + o_cn), (int*)(d + o_sl), (int*)(d + o_nb), (int*)(d + o_i1),
+                            (int*)(d + o_i2), (double*)(d + o_pt), d + o_de, (int*)(d + o_st)))
+      return rc;
+    if (int rc = orbx_host_call_download(h, c, down)) return rc;
+    std::memcpy(counts, c.ho + o_cn, 16);
+    if (Tz) std::memcpy(stats, c.ho + o_st, 16 * Tz);
+    const size_t created = (size_t)counts[2];
+    if (created == 0) return ORBX_OK;
+    std::memcpy(new_slot, c.ho + o_sl, 4 * created); std::memcpy(new_neighbour, c.ho + o_nb, 4 * created);
+    std::memcpy(new_idx1, c.ho + o_i1, 4 * created); std::memcpy(new_idx2, c.ho + o_i2, 4 * created);
+    std::memcpy(new_points, c.ho + o_pt, 24 * created);
+    return ms_set(mp, who, free_slots, (int)created, (const double*)(d + o_pt), d + o_de, false);
+  });
 }
 
 int orbx_map_remove_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n, const int* slots, int* n_cleared) {
   static const char* who = "orbx_map_remove_points";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
-  if (n == 0) { if (n_cleared) *n_cleared = 0; return ORBX_OK; }
-  const int* d_cleared = nullptr;
-  if (int rc = mr_enqueue(h, mp, P.C, n, slots, &d_cleared)) return rc;
-  if (!n_cleared) return ORBX_OK;
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, 4)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_cleared, 4, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  std::memcpy(n_cleared, h->pin_map.p, 4);
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
+    if (n == 0) { if (n_cleared) *n_cleared = 0; return ORBX_OK; }
+    const int* d_cleared = nullptr;
+    if (int rc = mr_enqueue(h, mp, P.C, n, slots, &d_cleared)) return rc;
+    if (!n_cleared) return ORBX_OK;
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, 4)) return rc;
+    ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_cleared, 4, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(n_cleared, h->pin_map.p, 4);
+    return ORBX_OK;
+  });
 }
 
 int orbx_map_cull_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* cand, int min_observations,
                          int* n_culled, int* culled) {
   static const char* who = "orbx_map_cull_points";
   if (!h) return ORBX_ERR_INVALID;
-  ObsPlan P;
-  if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
-  if (int rc = obs_check_slots(mp, who, cand, M)) return rc;
-  if (!n_culled || (M > 0 && !culled)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  *n_culled = 0;
-  if (M == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve_pinned(h, h->pin_map, 4 * (size_t)M)) return rc;
-  ObsCall c;
-  c.n_points = M; c.slots = cand;
-  const int* d_count = nullptr;
-  orbx_prof_begin_call(h);
-  if (int rc = obs_enqueue(h, mp, P, c, nullptr, &d_count)) return rc;
-  // the one download: the candidates' observer counts.  The comparison is the host's: the mirror needs the list anyway.
-  ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_count, 4 * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  const int* count = (const int*)h->pin_map.p;
-  int n = 0;
-  for (int i = 0; i < M; ++i)
-    if (count[i] < min_observations) culled[n++] = cand[i];               // local_mapper.rs:452: strictly fewer
-  *n_culled = n;
-  if (n == 0) return ORBX_OK;
-  const int* d_cleared = nullptr;
-  return mr_enqueue(h, mp, P.C, n, culled, &d_cleared);
+  return orbx_guard(h, who, [&]() -> int {
+    ObsPlan P;
+    if (int rc = mr_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    if (int rc = obs_check_slots(mp, who, cand, M)) return rc;
+    if (!n_culled || (M > 0 && !culled)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    *n_culled = 0;
+    if (M == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (int rc = orbx_reserve_pinned(h, h->pin_map, 4 * (size_t)M)) return rc;
+    ObsCall c;
+    c.n_points = M; c.slots = cand;
+    const int* d_count = nullptr;
+    orbx_prof_begin_call(h);
+    if (int rc = obs_enqueue(h, mp, P, c, nullptr, &d_count)) return rc;
+    // the one download: the candidates' observer counts.  The comparison is the host's: the mirror needs the list anyway.
+    ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_count, 4 * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    const int* count = (const int*)h->pin_map.p;
+    int n = 0;
+    for (int i = 0; i < M; ++i)
+      if (count[i] < min_observations) culled[n++] = cand[i];               // local_mapper.rs:452: strictly fewer
+    *n_culled = n;
+    if (n == 0) return ORBX_OK;
+    const int* d_cleared = nullptr;
+    return mr_enqueue(h, mp, P.C, n, culled, &d_cleared);
+  });
 }
 
 }  // extern "C"

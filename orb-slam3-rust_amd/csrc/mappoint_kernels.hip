@@ -349,13 +349,15 @@ int orbx_refresh_map_points_device(orbx_handle* h, int M, int n_obs, const doubl
                                    orbx_mp_refresh_record* d_records) {
   static const char* who = "orbx_refresh_map_points_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (M < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (M == 0) return ORBX_OK;
-  std::vector<MapPointKf> kfs;
-  if (int rc = mp_packed_table(h, who, T, kf_poses_wc, kf_feat_offset, d_descs, kfs)) return rc;
-  if (T > 0 && kf_feat_offset[T] > 0 && !d_descs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  return mp_refresh_enqueue(h, who, M, n_obs, d_positions, d_obs_start, d_obs_kf, d_obs_feat, T, kfs.data(), scale_range, d_mp_desc, d_normals,
-                            d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records);
+  return orbx_guard(h, who, [&]() -> int {
+    if (M < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (M == 0) return ORBX_OK;
+    std::vector<MapPointKf> kfs;
+    if (int rc = mp_packed_table(h, who, T, kf_poses_wc, kf_feat_offset, d_descs, kfs)) return rc;
+    if (T > 0 && kf_feat_offset[T] > 0 && !d_descs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    return mp_refresh_enqueue(h, who, M, n_obs, d_positions, d_obs_start, d_obs_kf, d_obs_feat, T, kfs.data(), scale_range, d_mp_desc, d_normals,
+                              d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records);
+  });
 }
 
 int orbx_refresh_map_points(orbx_handle* h, int M, const double* positions, const int* obs_start, const int* obs_kf, const int* obs_feat, int T,
@@ -363,12 +365,14 @@ int orbx_refresh_map_points(orbx_handle* h, int M, const double* positions, cons
                             double* normals, double* min_distance, double* max_distance, orbx_mp_refresh_record* records) {
   static const char* who = "orbx_refresh_map_points";
   if (!h) return ORBX_ERR_INVALID;
-  if (M < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  if (M == 0) return ORBX_OK;
-  std::vector<MapPointKf> kfs;
-  if (int rc = mp_packed_table(h, who, T, kf_poses_wc, kf_feat_offset, nullptr, kfs)) return rc;
-  return mp_refresh_host_call(h, who, M, positions, obs_start, obs_kf, obs_feat, T, kfs.data(), T > 0 ? kf_feat_offset : nullptr, descs,
-                              scale_range, mp_desc, normals, min_distance, max_distance, records);
+  return orbx_guard(h, who, [&]() -> int {
+    if (M < 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (M == 0) return ORBX_OK;
+    std::vector<MapPointKf> kfs;
+    if (int rc = mp_packed_table(h, who, T, kf_poses_wc, kf_feat_offset, nullptr, kfs)) return rc;
+    return mp_refresh_host_call(h, who, M, positions, obs_start, obs_kf, obs_feat, T, kfs.data(), T > 0 ? kf_feat_offset : nullptr, descs,
+                                scale_range, mp_desc, normals, min_distance, max_distance, records);
+  });
 }
 
 }  // extern "C"

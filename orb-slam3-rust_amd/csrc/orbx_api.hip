@@ -24,7 +24,8 @@ int orbx_fail(orbx_handle* h, int code, const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
-  if (h) h->err = buf; else g_create_error = buf;
+  std::string& err = h ? h->err : g_create_error;
+  try { err = buf; } catch (...) { err.clear(); }                         // (orbx_guard reports through here: nothing may be thrown)
   return code;
 }
 
@@ -1043,14 +1044,9 @@ int orbx_ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_c
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
   orbx_prof_begin_call(h);
-  try {
-    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, obs, should_stop, user,
-                           poses_wc_out, iterations, initial_error, final_error);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_visual", [&]() -> int {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations, initial_error, final_error);
+  });
 }
 
 int orbx_ba_solve_visual_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
@@ -1066,14 +1062,9 @@ int orbx_ba_solve_visual_obs32(orbx_handle* h, const orbx_camera* cam, const orb
   if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32: the partitioned solve takes orbx_ba_obs (orbx_ba_solve_visual)");
   ORBX_HIP(h, hipSetDevice(h->device));
   orbx_prof_begin_call(h);
-  try {
-    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user,
-                           poses_wc_out, iterations, initial_error, final_error, false, nullptr, obs32);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_visual_obs32", [&]() -> int {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, nullptr, obs32);
+  });
 }
 
 int orbx_ba_solve_visual_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
@@ -1089,14 +1080,9 @@ int orbx_ba_solve_visual_obs32_device(orbx_handle* h, const orbx_camera* cam, co
   if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32_device: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)");
   ORBX_HIP(h, hipSetDevice(h->device));
   orbx_prof_begin_call(h);
-  try {
-    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user,
-                           poses_wc_out, iterations, initial_error, final_error, false, nullptr, d_obs32, true);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32_device: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_obs32_device: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_visual_obs32_device", [&]() -> int {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, nullptr, d_obs32, true);
+  });
 }
 
 int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int n_windows,
@@ -1106,7 +1092,7 @@ int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orb
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_batch: bad argument");
   if (n_windows > 65535) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_batch: at most 65535 windows per call");
   // (no C++ exception may cross this C boundary: allocation or thread-creation failure is reported as an error code)
-  try {
+  return orbx_guard(h, "orbx_ba_solve_visual_batch", [&]() -> int {
     std::vector<BaWinHost> w((size_t)n_windows);
     for (int i = 0; i < n_windows; ++i) {
       orbx_ba_window& q = windows[i];
@@ -1175,11 +1161,7 @@ int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orb
     } else rc = ba_solve_batch(h, cam, cfg, n_windows, w.data(), should_stop, user);
     for (int i = 0; i < n_windows; ++i) windows[i].status = rc == ORBX_OK ? w[i].status : rc;
     return rc;
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_batch: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_visual_batch: unexpected C++ exception");
-  }
+  });
 }
 
 int orbx_debug_ba_blocks(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw, int F,
@@ -1226,14 +1208,9 @@ int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_in
   orbx_prof_begin_call(h);
   orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
   BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
-  try {
-    return ba_solve_visual(h, cam, &vc, K, poses_wc, F, fixed_poses_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations,
-                           initial_error, final_error, false, &in);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_inertial: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_inertial: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_inertial", [&]() -> int {
+    return ba_solve_visual(h, cam, &vc, K, poses_wc, F, fixed_poses_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, &in);
+  });
 }
 
 // the two 16-byte forms of orbx_ba_solve_inertial: mp_idx carries is_stereo (ORBX_BA_OBS32_STEREO), decoded by the prep launches
@@ -1255,14 +1232,9 @@ static int ba_solve_inertial_obs32(orbx_handle* h, const char* who, const orbx_c
   orbx_prof_begin_call(h);
   orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
   BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
-  try {
-    return ba_solve_visual(h, cam, &vc, K, poses_wc, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations,
-                           initial_error, final_error, false, &in, obs32, on_device);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who);
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who);
-  }
+  return orbx_guard(h, who, [&]() -> int {
+    return ba_solve_visual(h, cam, &vc, K, poses_wc, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, &in, obs32, on_device);
+  });
 }
 
 int orbx_ba_solve_inertial_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_inertial_ba_config* cfg, int K, const double* poses_wc,
@@ -1295,14 +1267,9 @@ int orbx_ba_solve_global(orbx_handle* h, const orbx_camera* cam, const orbx_ba_c
   if (K < 1 || M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "global BA needs two keyframes and a map point");   // global_ba.rs:194-196
   ORBX_HIP(h, hipSetDevice(h->device));
   orbx_prof_begin_call(h);
-  try {
-    return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, obs, should_stop, user, poses_wc_out,
-                           iterations, initial_error, final_error, true);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_global: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_global: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_global", [&]() -> int {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations, initial_error, final_error, true);
+  });
 }
 
 int orbx_ba_solve_global_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
@@ -1318,14 +1285,9 @@ int orbx_ba_solve_global_obs32(orbx_handle* h, const orbx_camera* cam, const orb
   if (K < 1 || M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "global BA needs two keyframes and a map point");   // global_ba.rs:194-196
   ORBX_HIP(h, hipSetDevice(h->device));
   orbx_prof_begin_call(h);
-  try {
-    return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, nullptr, should_stop, user, poses_wc_out,
-                           iterations, initial_error, final_error, true, nullptr, obs32);
-  } catch (const std::bad_alloc&) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_global_obs32: out of host memory");
-  } catch (...) {
-    return orbx_fail(h, ORBX_ERR_HIP, "orbx_ba_solve_global_obs32: unexpected C++ exception");
-  }
+  return orbx_guard(h, "orbx_ba_solve_global_obs32", [&]() -> int {
+    return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, true, nullptr, obs32);
+  });
 }
 
 }  // extern "C"

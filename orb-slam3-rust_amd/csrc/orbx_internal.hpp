@@ -9,6 +9,7 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -296,6 +297,17 @@ struct orbx_keyframe {
 };
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
+// The body of an extern "C" entry point: no C++ exception may cross the C boundary (ctypes, Rust); h == nullptr: the code alone.
+template <class F>
+int orbx_guard(orbx_handle* h, const char* who, F&& body) noexcept {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return h ? orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who) : (int)ORBX_ERR_HIP;
+  } catch (...) {
+    return h ? orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who) : (int)ORBX_ERR_HIP;
+  }
+}
 int orbx_reserve(orbx_handle* h, DevBuf& b, size_t bytes);
 // Grow-only, in steps of 1 MiB.  A buffer that is replaced may still be read or written by a copy on the handle's stream: the stream is
 // synchronised before it is freed (so a host form may call this, a device form may not).

@@ -332,18 +332,20 @@ int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, cons
                                     double* d_poses_out, double* d_velocities_out, double* d_biases_out, uint8_t* d_inlier_out,
                                     orbx_pose_inertial_result* d_results) {
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = pi_check_config(h, cfg, "orbx_pose_inertial_batch_device")) return rc;
-  if (!cam || n_problems < 0 ||
-      (n_problems > 0 && (!d_offsets || !d_pts3d || !d_pts2d || !d_is_stereo || !d_poses_wc || !d_velocities || !d_biases ||
-                          !d_prev_kf_poses_wc || !d_prev_kf_velocities || !d_preints || !d_poses_out || !d_velocities_out ||
-                          !d_biases_out || !d_inlier_out || !d_results)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch_device: bad argument");
-  if (n_problems == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
-  const PiArgs a{d_offsets, d_pts3d, d_pts2d, d_is_stereo, d_poses_wc, d_velocities, d_biases, d_prev_kf_poses_wc, d_prev_kf_velocities,
-                 d_preints, d_poses_out, d_velocities_out, d_biases_out, d_inlier_out, d_results};
-  return pi_launch(h, cam, cfg, n_problems, a);
+  return orbx_guard(h, "orbx_pose_inertial_batch_device", [&]() -> int {
+    if (int rc = pi_check_config(h, cfg, "orbx_pose_inertial_batch_device")) return rc;
+    if (!cam || n_problems < 0 ||
+        (n_problems > 0 && (!d_offsets || !d_pts3d || !d_pts2d || !d_is_stereo || !d_poses_wc || !d_velocities || !d_biases ||
+                            !d_prev_kf_poses_wc || !d_prev_kf_velocities || !d_preints || !d_poses_out || !d_velocities_out ||
+                            !d_biases_out || !d_inlier_out || !d_results)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch_device: bad argument");
+    if (n_problems == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    orbx_prof_begin_call(h);
+    const PiArgs a{d_offsets, d_pts3d, d_pts2d, d_is_stereo, d_poses_wc, d_velocities, d_biases, d_prev_kf_poses_wc, d_prev_kf_velocities,
+                   d_preints, d_poses_out, d_velocities_out, d_biases_out, d_inlier_out, d_results};
+    return pi_launch(h, cam, cfg, n_problems, a);
+  });
 }
 
 int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, int n_problems,
@@ -352,49 +354,51 @@ int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_
                              const double* prev_kf_velocities, const double* preints, double* poses_out, double* velocities_out,
                              double* biases_out, uint8_t* inlier_out, orbx_pose_inertial_result* results) {
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = pi_check_config(h, cfg, "orbx_pose_inertial_batch")) return rc;
-  if (!cam || n_problems < 0 ||
-      (n_problems > 0 && (!offsets || !poses_wc || !velocities || !biases || !prev_kf_poses_wc || !prev_kf_velocities || !preints ||
-                          !poses_out || !velocities_out || !biases_out || !results)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
-  if (n_problems == 0) return ORBX_OK;
-  if (int rc = orbx_check_offsets(h, "orbx_pose_inertial_batch", "offsets", "problem", n_problems, offsets)) return rc;
-  const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
-  if (N > 0 && (!pts3d || !pts2d || !is_stereo)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // one blob each way: [offsets | pts3d | poses | velocities | biases | prev poses | prev velocities | preints | pts2d | is_stereo] up,
-  // [poses | velocities | biases | results | inliers] down
-  Carve in, out;
-  const size_t o_off = in.take(4 * (P + 1)), o_p3 = in.take(24 * N), o_po = in.take(56 * P), o_ve = in.take(24 * P), o_bi = in.take(48 * P),
-               o_pp = in.take(56 * P), o_pv = in.take(24 * P), o_pr = in.take(88 * P), o_p2 = in.take(8 * N), o_st = in.take(N);
-  const size_t d_po = out.take(56 * P), d_ve = out.take(24 * P), d_bi = out.take(48 * P), d_rs = out.take(sizeof(orbx_pose_inertial_result) * P),
-               d_in = out.take(N);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_pi, h->ws_pi, in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
-  std::memcpy(hi + o_off, offsets, 4 * (P + 1));
-  if (N) std::memcpy(hi + o_p3, pts3d, 24 * N);
-  std::memcpy(hi + o_po, poses_wc, 56 * P);
-  std::memcpy(hi + o_ve, velocities, 24 * P);
-  std::memcpy(hi + o_bi, biases, 48 * P);
-  std::memcpy(hi + o_pp, prev_kf_poses_wc, 56 * P);
-  std::memcpy(hi + o_pv, prev_kf_velocities, 24 * P);
-  std::memcpy(hi + o_pr, preints, 88 * P);
-  if (N) { std::memcpy(hi + o_p2, pts2d, 8 * N); std::memcpy(hi + o_st, is_stereo, N); }
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  orbx_prof_begin_call(h);
-  const PiArgs a{(const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2), di + o_st, (const double*)(di + o_po),
-                 (const double*)(di + o_ve), (const double*)(di + o_bi), (const double*)(di + o_pp), (const double*)(di + o_pv),
-                 (const double*)(di + o_pr), (double*)(dout + d_po), (double*)(dout + d_ve), (double*)(dout + d_bi), dout + d_in,
-                 (orbx_pose_inertial_result*)(dout + d_rs)};
-  if (int rc = pi_launch(h, cam, cfg, n_problems, a)) return rc;
-  if (int rc = orbx_host_call_download(h, c, inlier_out ? out.off : d_in)) return rc;   // the inlier flags travel only when asked for
-  std::memcpy(poses_out, ho + d_po, 56 * P);
-  std::memcpy(velocities_out, ho + d_ve, 24 * P);
-  std::memcpy(biases_out, ho + d_bi, 48 * P);
-  std::memcpy(results, ho + d_rs, sizeof(orbx_pose_inertial_result) * P);
-  if (N && inlier_out) std::memcpy(inlier_out, ho + d_in, N);
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_pose_inertial_batch", [&]() -> int {
+    if (int rc = pi_check_config(h, cfg, "orbx_pose_inertial_batch")) return rc;
+    if (!cam || n_problems < 0 ||
+        (n_problems > 0 && (!offsets || !poses_wc || !velocities || !biases || !prev_kf_poses_wc || !prev_kf_velocities || !preints ||
+                            !poses_out || !velocities_out || !biases_out || !results)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
+    if (n_problems == 0) return ORBX_OK;
+    if (int rc = orbx_check_offsets(h, "orbx_pose_inertial_batch", "offsets", "problem", n_problems, offsets)) return rc;
+    const size_t N = (size_t)offsets[n_problems], P = (size_t)n_problems;
+    if (N > 0 && (!pts3d || !pts2d || !is_stereo)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch: bad argument");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // one blob each way: [offsets | pts3d | poses | velocities | biases | prev poses | prev velocities | preints | pts2d | is_stereo] up,
+    // [poses | velocities | biases | results | inliers] down
+    Carve in, out;
+    const size_t o_off = in.take(4 * (P + 1)), o_p3 = in.take(24 * N), o_po = in.take(56 * P), o_ve = in.take(24 * P), o_bi = in.take(48 * P),
+                 o_pp = in.take(56 * P), o_pv = in.take(24 * P), o_pr = in.take(88 * P), o_p2 = in.take(8 * N), o_st = in.take(N);
+    const size_t d_po = out.take(56 * P), d_ve = out.take(24 * P), d_bi = out.take(48 * P), d_rs = out.take(sizeof(orbx_pose_inertial_result) * P),
+                 d_in = out.take(N);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_pi, h->ws_pi, in.off, out.off, c)) return rc;
+    uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+    std::memcpy(hi + o_off, offsets, 4 * (P + 1));
+    if (N) std::memcpy(hi + o_p3, pts3d, 24 * N);
+    std::memcpy(hi + o_po, poses_wc, 56 * P);
+    std::memcpy(hi + o_ve, velocities, 24 * P);
+    std::memcpy(hi + o_bi, biases, 48 * P);
+    std::memcpy(hi + o_pp, prev_kf_poses_wc, 56 * P);
+    std::memcpy(hi + o_pv, prev_kf_velocities, 24 * P);
+    std::memcpy(hi + o_pr, preints, 88 * P);
+    if (N) { std::memcpy(hi + o_p2, pts2d, 8 * N); std::memcpy(hi + o_st, is_stereo, N); }
+    if (int rc = orbx_host_call_upload(h, c)) return rc;
+    orbx_prof_begin_call(h);
+    const PiArgs a{(const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2), di + o_st, (const double*)(di + o_po),
+                   (const double*)(di + o_ve), (const double*)(di + o_bi), (const double*)(di + o_pp), (const double*)(di + o_pv),
+                   (const double*)(di + o_pr), (double*)(dout + d_po), (double*)(dout + d_ve), (double*)(dout + d_bi), dout + d_in,
+                   (orbx_pose_inertial_result*)(dout + d_rs)};
+    if (int rc = pi_launch(h, cam, cfg, n_problems, a)) return rc;
+    if (int rc = orbx_host_call_download(h, c, inlier_out ? out.off : d_in)) return rc;   // the inlier flags travel only when asked for
+    std::memcpy(poses_out, ho + d_po, 56 * P);
+    std::memcpy(velocities_out, ho + d_ve, 24 * P);
+    std::memcpy(biases_out, ho + d_bi, 48 * P);
+    std::memcpy(results, ho + d_rs, sizeof(orbx_pose_inertial_result) * P);
+    if (N && inlier_out) std::memcpy(inlier_out, ho + d_in, N);
+    return ORBX_OK;
+  });
 }
 
 int orbx_pose_inertial_optimize(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, const double* pose_wc,

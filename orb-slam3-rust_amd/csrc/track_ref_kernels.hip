@@ -280,19 +280,21 @@ int orbx_track_reference_device(orbx_handle* h, const orbx_camera* cam, const or
                                 orbx_pnp_result* d_pnp_results, orbx_track_ref_result* d_results) {
   static const char* who = "orbx_track_reference_device";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
-  if (n_frames == 0) return ORBX_OK;
-  if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets)) return rc;
-  if (kf_offsets[n_frames] > 0 && !d_kf_desc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  std::vector<TrackRefItem> items((size_t)n_frames);
-  for (int b = 0; b < n_frames; ++b) {
-    items[(size_t)b].kf_desc = d_kf_desc + 32 * (size_t)kf_offsets[b];
-    items[(size_t)b].kf_off = kf_offsets[b];
-    items[(size_t)b].n = kf_offsets[b + 1] - kf_offsets[b];
-  }
-  return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
-                                 max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d,
-                                 d_kf_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
+    if (n_frames == 0) return ORBX_OK;
+    if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets)) return rc;
+    if (kf_offsets[n_frames] > 0 && !d_kf_desc) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    std::vector<TrackRefItem> items((size_t)n_frames);
+    for (int b = 0; b < n_frames; ++b) {
+      items[(size_t)b].kf_desc = d_kf_desc + 32 * (size_t)kf_offsets[b];
+      items[(size_t)b].kf_off = kf_offsets[b];
+      items[(size_t)b].n = kf_offsets[b + 1] - kf_offsets[b];
+    }
+    return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
+                                   max_feat, items.data(), d_kf_positions, d_kf_valid, false, d_priors_wc, d_matches, d_offsets, d_pts3d, d_pts2d,
+                                   d_kf_idx, d_feat_idx, d_poses_wc_out, d_inlier_out, d_err_out, d_pnp_results, d_results);
+  });
 }
 
 int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* pnp_cfg, int min_correspondences, int n_frames,
@@ -303,63 +305,65 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
                          orbx_track_ref_result* results) {
   static const char* who = "orbx_track_reference";
   if (!h) return ORBX_ERR_INVALID;
-  if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
-  if (n_frames == 0) return ORBX_OK;
-  int max_feat = 0, max_kf = 0;
-  if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets, &max_kf)) return rc;
-  if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
-  const size_t B = (size_t)n_frames;
-  const size_t NF = (size_t)feat_offsets[B], K = (size_t)kf_offsets[B];
-  if (max_feat > TREF_MAX_FEAT || !priors_wc || !offsets || !poses_wc_out || !pnp_results || !results || (NF > 0 && (!kp || !desc)) ||
-      (K > 0 && (!kf_desc || !kf_positions || !kf_valid || !matches || !pts3d || !pts2d || !kf_idx || !feat_idx || !inlier_out || !err_out)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (at most %d features per frame)", who, TREF_MAX_FEAT);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  // one blob each way: [kp | desc | keyframe desc | positions | valid | priors | feat_start | feat_count | items] up,
-  // [offsets | pts3d | pts2d | kf_idx | feat_idx | poses | err | pnp records | records | matches | inliers] down
-  Carve in, out;
-  const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_kd = in.take(32 * K), i_po = in.take(24 * K), i_va = in.take(K),
-               i_pr = in.take(56 * B), i_fs = in.take(4 * B), i_fc = in.take(4 * B), i_it = in.take(sizeof(TrackRefItem) * B);
-  const size_t o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * K), o_p2 = out.take(8 * K), o_ki = out.take(4 * K), o_fi = out.take(4 * K),
-               o_ps = out.take(56 * B), o_er = out.take(8 * K), o_pn = out.take(sizeof(orbx_pnp_result) * B),
-               o_rs = out.take(sizeof(orbx_track_ref_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * K), o_in = out.take(K);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_tref, h->ws_tref[1], in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
-  if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
-  if (K) { std::memcpy(hi + i_kd, kf_desc, 32 * K); std::memcpy(hi + i_po, kf_positions, 24 * K); std::memcpy(hi + i_va, kf_valid, K); }
-  std::memcpy(hi + i_pr, priors_wc, 56 * B);
-  for (size_t b = 0; b < B; ++b) {
-    ((int*)(hi + i_fs))[b] = feat_offsets[b];
-    ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
-    TrackRefItem it;
-    it.kf_desc = di + i_kd + 32 * (size_t)kf_offsets[b]; it.kf_off = kf_offsets[b]; it.n = kf_offsets[b + 1] - kf_offsets[b];
-    ((TrackRefItem*)(hi + i_it))[b] = it;
-  }
-  if (int rc = orbx_host_call_upload(h, c)) return rc;
-  TrefArgs A{};
-  A.min_corr = min_correspondences; A.max_feat = max_feat; A.fc_stride = 1;
-  A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
-  A.items = (const TrackRefItem*)(di + i_it); A.positions = (const double*)(di + i_po); A.valid = di + i_va; A.priors = (const double*)(di + i_pr);
-  A.matches = (orbx_dmatch*)(dout + o_ma); A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2);
-  A.kf_idx = (int*)(dout + o_ki); A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps);
-  A.results = (orbx_track_ref_result*)(dout + o_rs);
-  orbx_prof_begin_call(h);
-  if (int rc = tref_launch(h, cam, pnp_cfg, n_frames, max_kf, K, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn))) return rc;
-  if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-  std::memcpy(offsets, ho + o_of, 4 * (B + 1));
-  std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
-  std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
-  std::memcpy(results, ho + o_rs, sizeof(orbx_track_ref_result) * B);
-  const size_t N = (size_t)offsets[B];
-  if (N) {
-    std::memcpy(pts3d, ho + o_p3, 24 * N); std::memcpy(pts2d, ho + o_p2, 8 * N); std::memcpy(kf_idx, ho + o_ki, 4 * N);
-    std::memcpy(feat_idx, ho + o_fi, 4 * N); std::memcpy(err_out, ho + o_er, 8 * N); std::memcpy(inlier_out, ho + o_in, N);
-  }
-  for (size_t b = 0; b < B; ++b) {
-    const size_t n = (size_t)results[b].n_matches;
-    if (n) std::memcpy(matches + kf_offsets[b], ho + o_ma + sizeof(orbx_dmatch) * (size_t)kf_offsets[b], sizeof(orbx_dmatch) * n);
-  }
-  return ORBX_OK;
+  return orbx_guard(h, who, [&]() -> int {
+    if (int rc = tref_check(h, cam, pnp_cfg, min_correspondences, n_frames, who)) return rc;
+    if (n_frames == 0) return ORBX_OK;
+    int max_feat = 0, max_kf = 0;
+    if (int rc = orbx_check_offsets(h, who, "kf_offsets", "frame", n_frames, kf_offsets, &max_kf)) return rc;
+    if (int rc = orbx_check_offsets(h, who, "feat_offsets", "frame", n_frames, feat_offsets, &max_feat)) return rc;
+    const size_t B = (size_t)n_frames;
+    const size_t NF = (size_t)feat_offsets[B], K = (size_t)kf_offsets[B];
+    if (max_feat > TREF_MAX_FEAT || !priors_wc || !offsets || !poses_wc_out || !pnp_results || !results || (NF > 0 && (!kp || !desc)) ||
+        (K > 0 && (!kf_desc || !kf_positions || !kf_valid || !matches || !pts3d || !pts2d || !kf_idx || !feat_idx || !inlier_out || !err_out)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (at most %d features per frame)", who, TREF_MAX_FEAT);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // one blob each way: [kp | desc | keyframe desc | positions | valid | priors | feat_start | feat_count | items] up,
+    // [offsets | pts3d | pts2d | kf_idx | feat_idx | poses | err | pnp records | records | matches | inliers] down
+    Carve in, out;
+    const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_kd = in.take(32 * K), i_po = in.take(24 * K), i_va = in.take(K),
+                 i_pr = in.take(56 * B), i_fs = in.take(4 * B), i_fc = in.take(4 * B), i_it = in.take(sizeof(TrackRefItem) * B);
+    const size_t o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * K), o_p2 = out.take(8 * K), o_ki = out.take(4 * K), o_fi = out.take(4 * K),
+                 o_ps = out.take(56 * B), o_er = out.take(8 * K), o_pn = out.take(sizeof(orbx_pnp_result) * B),
+                 o_rs = out.take(sizeof(orbx_track_ref_result) * B), o_ma = out.take(sizeof(orbx_dmatch) * K), o_in = out.take(K);
+    HostCall c;
+    if (int rc = orbx_host_call_begin(h, h->pin_tref, h->ws_tref[1], in.off, out.off, c)) return rc;
+    uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+    if (NF) { std::memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, desc, 32 * NF); }
+    if (K) { std::memcpy(hi + i_kd, kf_desc, 32 * K); std::memcpy(hi + i_po, kf_positions, 24 * K); std::memcpy(hi + i_va, kf_valid, K); }
+    std::memcpy(hi + i_pr, priors_wc, 56 * B);
+    for (size_t b = 0; b < B; ++b) {
+      ((int*)(hi + i_fs))[b] = feat_offsets[b];
+      ((int*)(hi + i_fc))[b] = feat_offsets[b + 1] - feat_offsets[b];
+      TrackRefItem it;
+      it.kf_desc = di + i_kd + 32 * (size_t)kf_offsets[b]; it.kf_off = kf_offsets[b]; it.n = kf_offsets[b + 1] - kf_offsets[b];
+      ((TrackRefItem*)(hi + i_it))[b] = it;
+    }
+    if (int rc = orbx_host_call_upload(h, c)) return rc;
+    TrefArgs A{};
+    A.min_corr = min_correspondences; A.max_feat = max_feat; A.fc_stride = 1;
+    A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
+    A.items = (const TrackRefItem*)(di + i_it); A.positions = (const double*)(di + i_po); A.valid = di + i_va; A.priors = (const double*)(di + i_pr);
+    A.matches = (orbx_dmatch*)(dout + o_ma); A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2);
+    A.kf_idx = (int*)(dout + o_ki); A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps);
+    A.results = (orbx_track_ref_result*)(dout + o_rs);
+    orbx_prof_begin_call(h);
+    if (int rc = tref_launch(h, cam, pnp_cfg, n_frames, max_kf, K, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn))) return rc;
+    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
+    std::memcpy(offsets, ho + o_of, 4 * (B + 1));
+    std::memcpy(poses_wc_out, ho + o_ps, 56 * B);
+    std::memcpy(pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
+    std::memcpy(results, ho + o_rs, sizeof(orbx_track_ref_result) * B);
+    const size_t N = (size_t)offsets[B];
+    if (N) {
+      std::memcpy(pts3d, ho + o_p3, 24 * N); std::memcpy(pts2d, ho + o_p2, 8 * N); std::memcpy(kf_idx, ho + o_ki, 4 * N);
+      std::memcpy(feat_idx, ho + o_fi, 4 * N); std::memcpy(err_out, ho + o_er, 8 * N); std::memcpy(inlier_out, ho + o_in, N);
+    }
+    for (size_t b = 0; b < B; ++b) {
+      const size_t n = (size_t)results[b].n_matches;
+      if (n) std::memcpy(matches + kf_offsets[b], ho + o_ma + sizeof(orbx_dmatch) * (size_t)kf_offsets[b], sizeof(orbx_dmatch) * n);
+    }
+    return ORBX_OK;
+  });
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 //   driver gcollect <snapshot.bin> 0 0 <out.bin>                                   collect_global_ba_data
 //   driver gapply   <snapshot.bin> <result.bin> <out.bin>                          apply_global_ba_results (result file as for `apply`)
 //   driver gba      <snapshot.bin> <stop_after_polls> 0 <out.bin>                  run_global_ba on the GPU
+//   driver gthrow   <snapshot.bin> 0 0 <out.bin>                                   run_global_ba whose read-lock callback throws (no GPU)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -255,6 +256,18 @@ int main(int argc, char** argv) {
       const double err[2] = {res ? res->initial_error : 0.0, res ? res->final_error : 0.0};
       put(f, err, 2);
       write_map_state(f, m);
+      fclose(f);
+    } else if (mode == "gthrow") {                                         // a read-lock callback that throws: `running` is cleared on that way out too
+      const orbx::CameraModel cam{458.654, 457.296, 367.215, 248.375, 0.11007};
+      orbx::Handle h(nullptr, 0);                                           // (never reached: the callback throws first)
+      std::atomic<bool> running{false};
+      bool seen = false, thrown = false;
+      try {
+        orbx::run_global_ba(h, m, cam, orbx::GlobalBAConfig{}, running, [&](const std::function<void()>&) { seen = running.load(); throw std::runtime_error("lock"); });
+      } catch (const std::runtime_error&) { thrown = true; }
+      FILE* f = fopen(argv[5], "wb");
+      const int64_t hdr[3] = {seen ? 1 : 0, thrown ? 1 : 0, running.load() ? 1 : 0};
+      put(f, hdr, 3);
       fclose(f);
     } else if (mode == "lba") {
       const orbx::CameraModel cam{458.654, 457.296, 367.215, 248.375, 0.11007};   // EuRoC cam0

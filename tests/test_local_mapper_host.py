@@ -660,6 +660,18 @@ def test_cpp_global_collect_and_apply_match_restatement(pkg, tmp_path):
         assert all(np.array_equal(mp_pos[i], m.map_points[int(j)].position) for i, j in enumerate(snap.mp_ids))
 
 
+def test_cpp_run_global_ba_clears_running_when_a_lock_throws(pkg, tmp_path):
+    """run_global_ba sets `running` on entry and clears it on EVERY way out: a read-lock callback that throws sees the flag set, the
+    exception reaches the caller, and the flag is false afterwards (no GPU: the callback throws before the handle is used)."""
+    pkg.load_library()
+    tmp = str(tmp_path)
+    exe = _build(tmp)
+    open(os.path.join(tmp, "snap.bin"), "wb").write(snapshot_of(pkg, random_map(1)[0]).to_bytes())
+    subprocess.run([exe, "gthrow", os.path.join(tmp, "snap.bin"), "0", "0", os.path.join(tmp, "gthrow.bin")], check=True)
+    seen_running, thrown, running_after = struct.unpack("<3q", open(os.path.join(tmp, "gthrow.bin"), "rb").read())
+    assert (seen_running, thrown, running_after) == (1, 1, 0)
+
+
 @pytest.mark.gpu
 def test_run_global_ba_three_phases(pkg, gpu_handle, tmp_path):
     """run_global_ba (global_ba.rs:450-500) end to end: the product's driver over flat arrays (collect -> GPU solve -> apply, unconditionally)
