@@ -343,9 +343,8 @@ int orbx_bow_transform_device(orbx_handle* h, const orbx_vocabulary* v, const ui
     if (v->device != h->device) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: vocabulary lives on another device");
     if (n == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    ProfScope ps(h, "bow_transform_kernel");
-    hipLaunchKernelGGL(bow_transform_kernel, dim3((n + 15) / 16), dim3(256), 0, h->stream, v->d_child_start, v->d_child, v->d_desc, v->d_parent,
-                       v->d_word, v->d_weight, d_desc, n, levels_up, d_word, d_leaf, d_node, d_weight);
+    orbx_launch(h, "bow_transform_kernel", false, bow_transform_kernel, dim3((n + 15) / 16), dim3(256), 0, v->d_child_start, v->d_child, v->d_desc, v->d_parent, v->d_word,
+                v->d_weight, d_desc, n, levels_up, d_word, d_leaf, d_node, d_weight);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   });
@@ -388,9 +387,8 @@ int orbx_bow_vectors_device(orbx_handle* h, const orbx_vocabulary* v, const uint
     double* d_w = (double*)h->ws_io[9].p;
     uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
     if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
-    ProfScope ps(h, "bow_vectors_kernel");
-    hipLaunchKernelGGL(bow_vectors_kernel, dim3(1), dim3(BOWV_THREADS), 0, h->stream, d_word, d_node, d_w, n, d_bow_word, d_bow_weight, d_fv_node,
-                       d_fv_start, d_fv_index, d_counts);
+    orbx_launch(h, "bow_vectors_kernel", false, bow_vectors_kernel, dim3(1), dim3(BOWV_THREADS), 0, d_word, d_node, d_w, n, d_bow_word, d_bow_weight, d_fv_node, d_fv_start,
+                d_fv_index, d_counts);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   });

@@ -419,22 +419,13 @@ int kfdb_launch(orbx_kfdb* db, int scoring, const std::vector<QueryHost>& qs, in
     db->lds_attr[dot] = true;
   }
   const dim3 grid((unsigned)((n_slots + KFDB_THREADS - 1) / KFDB_THREADS), (unsigned)Q);
-  {
-    ProfScope ps(h, "kfdb_score_kernel");
-    if (dot)
-      hipLaunchKernelGGL(kfdb_score_kernel<true>, grid, dim3(KFDB_THREADS), lds, st, db->d_table, db->d_arena, n_slots, (const KfdbQuery*)(dq + o_q),
-                         dq + o_blob, lds_words, L.d_scores);
-    else
-      hipLaunchKernelGGL(kfdb_score_kernel<false>, grid, dim3(KFDB_THREADS), lds, st, db->d_table, db->d_arena, n_slots, (const KfdbQuery*)(dq + o_q),
-                         dq + o_blob, lds_words, L.d_scores);
-    ORBX_HIP(h, hipGetLastError());
-  }
+  orbx_launch(h, "kfdb_score_kernel", false, dot ? kfdb_score_kernel<true> : kfdb_score_kernel<false>, grid, dim3(KFDB_THREADS), lds, db->d_table, db->d_arena, n_slots,
+              (const KfdbQuery*)(dq + o_q), dq + o_blob, lds_words, L.d_scores);
+  ORBX_HIP(h, hipGetLastError());
   if (mode >= 0) {
-    ProfScope ps(h, "kfdb_filter_kernel");
-    hipLaunchKernelGGL(kfdb_filter_kernel, grid, dim3(KFDB_THREADS), 0, st, db->d_table, n_slots, (const KfdbQuery*)(dq + o_q), (const int*)(dq + o_thr),
-                       (const unsigned long long*)(dq + o_conn), L.d_scores, mode, cfg ? cfg->min_score_ratio : 0.0,
-                       cfg ? cfg->min_covisibles_for_threshold : 0, cfg ? (unsigned long long)cfg->min_temporal_gap : 0ull, exclude_map, L.d_cand,
-                       L.d_counts);
+    orbx_launch(h, "kfdb_filter_kernel", false, kfdb_filter_kernel, grid, dim3(KFDB_THREADS), 0, db->d_table, n_slots, (const KfdbQuery*)(dq + o_q), (const int*)(dq + o_thr),
+                (const unsigned long long*)(dq + o_conn), L.d_scores, mode, cfg ? cfg->min_score_ratio : 0.0, cfg ? cfg->min_covisibles_for_threshold : 0,
+                cfg ? (unsigned long long)cfg->min_temporal_gap : 0ull, exclude_map, L.d_cand, L.d_counts);
     ORBX_HIP(h, hipGetLastError());
   }
   return ORBX_OK;

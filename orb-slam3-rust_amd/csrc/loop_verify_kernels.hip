@@ -657,19 +657,10 @@ int s3_launch(orbx_handle* h, S3Args S, int P, uint8_t* ws) {
   S.hok = S.hcnt + (size_t)P * H;
   S.model = (double*)(ws + lay.model);
   const double thr2 = S.cfg.inlier_threshold * S.cfg.inlier_threshold;      // :245
-  {
-    ProfScope ps(h, "sim3_hypothesis_kernel");
-    hipLaunchKernelGGL(sim3_hypothesis_kernel, dim3(P, (H + 63) / 64), dim3(64), 0, h->stream, S);
-  }
-  if (S.max_n >= 3) {
-    ProfScope ps(h, "sim3_score_kernel", true);
-    hipLaunchKernelGGL(sim3_score_kernel, dim3(P, (S.max_n + S3_THREADS - 1) / S3_THREADS, (H + S3_CHUNK - 1) / S3_CHUNK), dim3(S3_THREADS), 0, h->stream,
-                       S, thr2);
-  }
-  {
-    ProfScope ps(h, "sim3_final_kernel", true);
-    hipLaunchKernelGGL(sim3_final_kernel, dim3(P), dim3(S3_THREADS), 0, h->stream, S, thr2);
-  }
+  orbx_launch(h, "sim3_hypothesis_kernel", false, sim3_hypothesis_kernel, dim3(P, (H + 63) / 64), dim3(64), 0, S);
+  if (S.max_n >= 3)
+    orbx_launch(h, "sim3_score_kernel", true, sim3_score_kernel, dim3(P, (S.max_n + S3_THREADS - 1) / S3_THREADS, (H + S3_CHUNK - 1) / S3_CHUNK), dim3(S3_THREADS), 0, S, thr2);
+  orbx_launch(h, "sim3_final_kernel", true, sim3_final_kernel, dim3(P), dim3(S3_THREADS), 0, S, thr2);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -739,24 +730,13 @@ int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam,
   S.pts1 = d_pts_current; S.pts2 = d_pts_loop; S.sim3 = d_sim3; S.inl = d_inlier; S.results = (orbx_sim3_result*)(w + o_sres);
   A.model = (const double*)(w + o_s3 + s3.model);
   orbx_prof_begin_call(h);
-  if (any_bf && max_n1 > 0) {
-    ProfScope ps(h, "lv_match_kernel");
-    hipLaunchKernelGGL(lv_match_kernel<false>, dim3((max_n1 + LV_TILE - 1) / LV_TILE, B), dim3(LV_THREADS), 0, h->stream, A);
-  }
-  if (any_fv && max_n1 > 0) {
-    ProfScope ps(h, "lv_match_kernel_fv", any_bf);
-    hipLaunchKernelGGL(lv_match_kernel<true>, dim3((max_n1 + LV_TILE - 1) / LV_TILE, B), dim3(LV_THREADS), 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "lv_resolve_kernel", max_n1 > 0);
-    hipLaunchKernelGGL(lv_resolve_kernel, dim3(B), dim3(LV_THREADS), 0, h->stream, A);
-  }
+  const dim3 match_grid((max_n1 + LV_TILE - 1) / LV_TILE, B);
+  if (any_bf && max_n1 > 0) orbx_launch(h, "lv_match_kernel", false, lv_match_kernel<false>, match_grid, dim3(LV_THREADS), 0, A);
+  if (any_fv && max_n1 > 0) orbx_launch(h, "lv_match_kernel_fv", any_bf, lv_match_kernel<true>, match_grid, dim3(LV_THREADS), 0, A);
+  orbx_launch(h, "lv_resolve_kernel", max_n1 > 0, lv_resolve_kernel, dim3(B), dim3(LV_THREADS), 0, A);
   ORBX_HIP(h, hipGetLastError());
   if (int rc = s3_launch(h, S, B, w + o_s3)) return rc;
-  {
-    ProfScope ps(h, "lv_finish_kernel", true);
-    hipLaunchKernelGGL(lv_finish_kernel, dim3(B), dim3(LV_THREADS), 0, h->stream, A);
-  }
+  orbx_launch(h, "lv_finish_kernel", true, lv_finish_kernel, dim3(B), dim3(LV_THREADS), 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

@@ -49,6 +49,10 @@
 // Both windows are one host path: WinPlan (bac_plan / bic_plan check and size a covisible window / a chain), win_enqueue (the kind's
 // selection, then the five launches), win_collect_host (the host forms) and win_local_ba (collect, download, poses, solve, write back).
 // Every extern "C" entry point runs its body inside orbx_guard (orbx_internal.hpp): no C++ exception crosses the C boundary.
+// The host code states three things once each (orbx_internal.hpp): a launch with its profiling scope is orbx_launch(h, label, chained,
+// kernel, grid, block, lds, args...); the host tables of a device form are the pieces of an UploadPlan (put, then send, or begin /
+// commit around what is made in place) on ring_map; the outputs of a host form are the pieces of an OutputPlan (add, begin, dev,
+// finish, copy for a length the download tells).  Every workspace is a named member of orbx_handle::ws_map (MapWorkspaces).
 // mp.observations (map_point.rs:140-156), the inverse of the slot tables, is derived the same way for the points a call names:
 // the lists behind orbx_map_observations and orbx_map_refresh_points (search_in_neighbors.rs:139-150) and the counts behind
 // orbx_map_keyframe_redundancy (local_mapper.rs:487-583); the kernels are described where they stand ("observations", below).
@@ -508,21 +512,14 @@ int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const 
       return orbx_fail(h, ORBX_ERR_INVALID, "%s: slot %d is not live yet: its first set needs positions and descriptors", who, slots[i]);
   if (n == 0 || (!positions && !desc)) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  Carve up;
-  const size_t N = (size_t)n, o_sl = up.take(4 * N), o_po = up.take(on_host && positions ? 24 * N : 0), o_de = up.take(on_host && desc ? 32 * N : 0);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
-  std::memcpy(hs + o_sl, slots, 4 * N);
-  if (on_host && positions) std::memcpy(hs + o_po, positions, 24 * N);
-  if (on_host && desc) std::memcpy(hs + o_de, desc, 32 * N);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
+  UploadPlan up;
+  const size_t N = (size_t)n, o_sl = up.put(slots, 4 * N), o_po = up.put(positions, on_host && positions ? 24 * N : 0), o_de = up.put(desc, on_host && desc ? 32 * N : 0);
+  if (int rc = up.send(h, h->ring_map, h->ws_map.call_tables)) return rc;
+  uint8_t* const ds = up.device;
   const double* d_pos = !positions ? nullptr : on_host ? (const double*)(ds + o_po) : positions;
   const uint8_t* d_desc = !desc ? nullptr : on_host ? ds + o_de : desc;
-  {
-    ProfScope ps(h, "map_scatter_kernel");
-    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, (const int*)(ds + o_sl), n, d_pos, d_desc, 1,
-                       mp->d_pos, mp->d_desc, mp->d_live);
-  }
+  orbx_launch(h, "map_scatter_kernel", false, map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, (const int*)(ds + o_sl), n, d_pos, d_desc, 1,
+              mp->d_pos, mp->d_desc, mp->d_live);
   ORBX_HIP(h, hipGetLastError());
   for (int i = 0; i < n; ++i)
     if (!mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 1; ++mp->n_live; }
@@ -565,11 +562,8 @@ int ms_check_distinct(orbx_handle* h, const char* who, const orbx_map_points* mp
 
 // erase behind its checks: d_slots [n] already lies in device memory; the live bytes and their host mirror
 int ms_erase_launch(orbx_handle* h, orbx_map_points* mp, const int* d_slots, const int* slots, int n) {
-  {
-    ProfScope ps(h, "map_scatter_kernel");
-    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, h->stream, d_slots, n, (const double*)nullptr,
-                       (const uint8_t*)nullptr, 0, mp->d_pos, mp->d_desc, mp->d_live);
-  }
+  orbx_launch(h, "map_scatter_kernel", false, map_scatter_kernel, dim3((n + MS_THREADS - 1) / MS_THREADS), dim3(MS_THREADS), 0, d_slots, n, (const double*)nullptr,
+              (const uint8_t*)nullptr, 0, mp->d_pos, mp->d_desc, mp->d_live);
   ORBX_HIP(h, hipGetLastError());
   for (int i = 0; i < n; ++i)
     if (mp->live[(size_t)slots[i]]) { mp->live[(size_t)slots[i]] = 0; --mp->n_live; }
@@ -648,8 +642,8 @@ int ms_select_launch(orbx_handle* h, orbx_map_points* mp, int source, int B, int
   const int n_chunk = std::max(1, (max_cand + MS_CHUNK - 1) / MS_CHUNK);
   Carve ws;
   const size_t o_ca = ws.take(4 * Bz * (size_t)n_chunk * MS_CHUNK), o_cc = ws.take(4 * Bz * (size_t)n_chunk);
-  if (int rc = orbx_reserve(h, h->ws_map[0], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[0].p;
+  if (int rc = orbx_reserve(h, h->ws_map.sel_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.sel_scratch.p;
   SelArgs A{};
   A.source = source; A.capacity = mp->capacity; A.n_chunk = n_chunk;
   A.live = mp->d_live; A.pos = mp->d_pos; A.desc = mp->d_desc;
@@ -658,18 +652,9 @@ int ms_select_launch(orbx_handle* h, orbx_map_points* mp, int source, int B, int
   A.first = (int*)mp->first.p; A.cand = (int*)(w + o_ca); A.chunk_count = (int*)(w + o_cc);
   A.list_off = d_list_off; A.list_slot = d_list_slot; A.out_pos = d_positions; A.out_desc = d_mp_desc;
   const dim3 grid(n_chunk, B), block(MS_THREADS);
-  if (source == ORBX_MAP_SOURCE_KEYFRAMES) {
-    ProfScope ps(h, "map_mark_kernel");
-    hipLaunchKernelGGL(map_mark_kernel, grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "map_flag_kernel", source == ORBX_MAP_SOURCE_KEYFRAMES);
-    hipLaunchKernelGGL(map_flag_kernel, grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "map_emit_kernel", true);
-    hipLaunchKernelGGL(map_emit_kernel, grid, block, 0, h->stream, A, B);
-  }
+  if (source == ORBX_MAP_SOURCE_KEYFRAMES) orbx_launch(h, "map_mark_kernel", false, map_mark_kernel, grid, block, 0, A);
+  orbx_launch(h, "map_flag_kernel", source == ORBX_MAP_SOURCE_KEYFRAMES, map_flag_kernel, grid, block, 0, A);
+  orbx_launch(h, "map_emit_kernel", true, map_emit_kernel, grid, block, 0, A, B);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -684,25 +669,22 @@ int ms_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, int 
   if (int rc = ms_check_list_outputs(h, who, total, d_list_off, d_list_slot, d_positions, d_mp_desc, source == ORBX_MAP_SOURCE_SLOTS && !d_src_slots)) return rc;
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t Bz = (size_t)B;
-  Carve up;
-  const size_t o_sg = up.take(sizeof(MapSeg) * P.segs.size()), o_so = up.take(4 * (Bz + 1)), o_nc = up.take(4 * Bz), o_sr = up.take(4 * (Bz + 1));
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], up.off, &hs, &ds)) return rc;
-  if (!P.segs.empty()) std::memcpy(hs + o_sg, P.segs.data(), sizeof(MapSeg) * P.segs.size());
-  std::memcpy(hs + o_so, P.seg_off.data(), 4 * (Bz + 1));
-  std::memcpy(hs + o_nc, P.n_cand.data(), 4 * Bz);
-  if (source == ORBX_MAP_SOURCE_SLOTS) std::memcpy(hs + o_sr, src_offsets, 4 * (Bz + 1));
-  else std::memset(hs + o_sr, 0, 4 * (Bz + 1));
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], up.off)) return rc;
+  const bool from_slots = source == ORBX_MAP_SOURCE_SLOTS;
+  UploadPlan up;
+  const size_t o_sg = up.put(P.segs.data(), sizeof(MapSeg) * P.segs.size()), o_so = up.put(P.seg_off.data(), 4 * (Bz + 1)), o_nc = up.put(P.n_cand.data(), 4 * Bz),
+               o_sr = up.put(from_slots ? src_offsets : nullptr, 4 * (Bz + 1));
+  if (int rc = up.begin(h, h->ring_map, h->ws_map.call_tables)) return rc;
+  if (!from_slots) std::memset(up.host + o_sr, 0, 4 * (Bz + 1));
+  if (int rc = up.commit(h, h->ring_map, h->ws_map.call_tables)) return rc;
+  uint8_t* const ds = up.device;
   return ms_select_launch(h, mp, source, B, P.max_cand, (const MapSeg*)(ds + o_sg), (const int*)(ds + o_so), (const int*)(ds + o_nc), d_src_slots,
                           (const int*)(ds + o_sr), d_list_off, d_list_slot, d_positions, d_mp_desc);
 }
 
 int ms_matched_slot_enqueue(orbx_handle* h, int B, int max_feat, const int* d_matched, const int* d_list_off, const int* d_list_slot, int* d_matched_slot) {
   if (max_feat <= 0) return ORBX_OK;
-  ProfScope ps(h, "map_matched_slot_kernel", true);
-  hipLaunchKernelGGL(map_matched_slot_kernel, dim3((max_feat + MS_THREADS - 1) / MS_THREADS, B), dim3(MS_THREADS), 0, h->stream, d_matched, d_list_off,
-                     d_list_slot, max_feat, d_matched_slot);
+  orbx_launch(h, "map_matched_slot_kernel", true, map_matched_slot_kernel, dim3((max_feat + MS_THREADS - 1) / MS_THREADS, B), dim3(MS_THREADS), 0, d_matched, d_list_off,
+              d_list_slot, max_feat, d_matched_slot);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -752,19 +734,16 @@ int cov_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int Q, co
     if (int rc = orbx_reserve(h, mp->mark, need)) return rc;
     ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
   }
-  Carve up, ws;
-  const size_t o_kf = up.take(sizeof(CovKf) * K), o_me = up.take(sizeof(CovMember) * members.size()), o_se = up.take(4 * Qz), o_so = up.take(segs ? 4 * (Qz + 1) : 0);
+  UploadPlan up;
+  Carve ws;
+  const size_t o_kf = up.put(P.kfs.data(), sizeof(CovKf) * K), o_me = up.put(members.data(), sizeof(CovMember) * members.size()), o_se = up.put(query, 4 * Qz),
+               o_so = up.put(segs ? segs->seg_off : nullptr, segs ? 4 * (Qz + 1) : 0);
   const size_t o_we = ws.take(d_weights ? 0 : 4 * Qz * K), o_be = ws.take(d_best || !segs ? 0 : 4 * Qz * (size_t)n_best), o_sg = ws.take(sizeof(MapSeg) * n_seg),
                o_nc = ws.take(segs ? 4 * Qz : 0);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[5], up.off, &hs, &ds)) return rc;
-  if (K) std::memcpy(hs + o_kf, P.kfs.data(), sizeof(CovKf) * K);
-  if (!members.empty()) std::memcpy(hs + o_me, members.data(), sizeof(CovMember) * members.size());
-  std::memcpy(hs + o_se, query, 4 * Qz);
-  if (segs) std::memcpy(hs + o_so, segs->seg_off, 4 * (Qz + 1));
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[5], up.off)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_map[4], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[4].p;
+  if (int rc = up.send(h, h->ring_map, h->ws_map.cov_tables)) return rc;
+  uint8_t* const ds = up.device;
+  if (int rc = orbx_reserve(h, h->ws_map.cov_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.cov_scratch.p;
   CovArgs A{};
   A.capacity = mp->capacity; A.n_kfs = (int)K; A.n_q = Q; A.n_best = n_best;
   A.live = mp->d_live; A.kfs = (const CovKf*)(ds + o_kf); A.members = (const CovMember*)(ds + o_me); A.self = (const int*)(ds + o_se);
@@ -772,25 +751,12 @@ int cov_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int Q, co
   A.best = d_best ? d_best : segs ? (int*)(w + o_be) : nullptr; A.n_best_out = d_n_best;
   const dim3 block(MS_THREADS), mark_grid(std::max(1, (max_qn + MS_CHUNK - 1) / MS_CHUNK), (unsigned)members.size());
   const bool marks = !members.empty() && max_qn > 0 && K > 0;
-  if (marks) {
-    ProfScope ps(h, "cov_mark_kernel");
-    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, A, 1);
-  }
-  if (K > 0) {
-    ProfScope ps(h, "cov_count_kernel", marks);
-    hipLaunchKernelGGL(cov_count_kernel, dim3((unsigned)K, (Q + COV_Q - 1) / COV_Q), block, 0, h->stream, A);
-  }
-  if (marks) {
-    ProfScope ps(h, "cov_mark_kernel", true);
-    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, A, 0);
-  }
-  if (rank) {
-    ProfScope ps(h, "cov_rank_kernel", K > 0);
-    hipLaunchKernelGGL(cov_rank_kernel, dim3(Q), block, 0, h->stream, A);
-  }
+  if (marks) orbx_launch(h, "cov_mark_kernel", false, cov_mark_kernel, mark_grid, block, 0, A, 1);
+  if (K > 0) orbx_launch(h, "cov_count_kernel", marks, cov_count_kernel, dim3((unsigned)K, (Q + COV_Q - 1) / COV_Q), block, 0, A);
+  if (marks) orbx_launch(h, "cov_mark_kernel", true, cov_mark_kernel, mark_grid, block, 0, A, 0);
+  if (rank) orbx_launch(h, "cov_rank_kernel", K > 0, cov_rank_kernel, dim3(Q), block, 0, A);
   if (segs) {
-    ProfScope ps(h, "cov_seg_kernel", true);
-    hipLaunchKernelGGL(cov_seg_kernel, dim3(Q), block, 0, h->stream, A, A.self, (const int*)(ds + o_so), (MapSeg*)(w + o_sg), (int*)(w + o_nc), segs->d_local_kf);
+    orbx_launch(h, "cov_seg_kernel", true, cov_seg_kernel, dim3(Q), block, 0, A, A.self, (const int*)(ds + o_so), (MapSeg*)(w + o_sg), (int*)(w + o_nc), segs->d_local_kf);
     segs->d_segs = (const MapSeg*)(w + o_sg); segs->d_seg_off = (const int*)(ds + o_so); segs->d_n_cand = (const int*)(w + o_nc);
   }
   ORBX_HIP(h, hipGetLastError());
@@ -932,17 +898,15 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t K = (size_t)n_kfs;
   const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK);
-  Carve ws, up;
+  Carve ws;
+  UploadPlan up;
   const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
                o_ob = ws.take(4 * K);
-  const size_t u_kf = up.take(sizeof(BacKf) * K), u_ch = up.take(4 * P.chain.size());
-  if (int rc = orbx_reserve(h, h->ws_map[6], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[6].p;
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[7], up.off, &hs, &ds)) return rc;
-  std::memcpy(hs + u_kf, P.kfs.data(), sizeof(BacKf) * K);
-  if (chain) std::memcpy(hs + u_ch, P.chain.data(), 4 * P.chain.size());
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[7], up.off)) return rc;
+  const size_t u_kf = up.put(P.kfs.data(), sizeof(BacKf) * K), u_ch = up.put(P.chain.data(), 4 * P.chain.size());
+  if (int rc = orbx_reserve(h, h->ws_map.win_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.win_scratch.p;
+  if (int rc = up.send(h, h->ring_map, h->ws_map.win_tables)) return rc;
+  uint8_t* const ds = up.device;
   // P: local = [cur] ++ best as one frame of orbx_map_track_local_device gets it, or the chain's tables in chain order (descriptors stay in the workspace)
   if (int rc = chain ? ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd)
                      : local_select_enqueue(h, who, mp, 1, P.L, &P.cur, P.max_covisible, bound, d_local_kf, (int*)(w + o_lo), d_list_slot, d_positions, w + o_gd))
@@ -958,32 +922,18 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
   static const BacKernel covisible[2] = {bac_order_kernel<false>, bac_emit_kernel<false>}, temporal[2] = {bac_order_kernel<true>, bac_emit_kernel<true>};
   const BacKernel* of_kind = chain ? temporal : covisible;
   const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
-  {
-    ProfScope ps(h, "bac_index_kernel", true);
-    hipLaunchKernelGGL(bac_index_kernel, list_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_count_kernel", true);
-    hipLaunchKernelGGL(bac_count_kernel, kf_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_order_kernel", true);
-    hipLaunchKernelGGL(of_kind[0], dim3(1), block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_emit_kernel", true);
-    hipLaunchKernelGGL(of_kind[1], kf_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "bac_restore_kernel", true);
-    hipLaunchKernelGGL(bac_restore_kernel, list_grid, block, 0, h->stream, A);
-  }
+  orbx_launch(h, "bac_index_kernel", true, bac_index_kernel, list_grid, block, 0, A);
+  orbx_launch(h, "bac_count_kernel", true, bac_count_kernel, kf_grid, block, 0, A);
+  orbx_launch(h, "bac_order_kernel", true, of_kind[0], dim3(1), block, 0, A);
+  orbx_launch(h, "bac_emit_kernel", true, of_kind[1], kf_grid, block, 0, A);
+  orbx_launch(h, "bac_restore_kernel", true, bac_restore_kernel, list_grid, block, 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
 
-// se3.rs:56-63 with nalgebra's quaternion-vector product, one IEEE operation at a time (include/orbx.hpp's se3_inverse)
-void bac_pose_inverse(const double* p, double* out) {
+// se3.rs:56-63 with nalgebra's quaternion-vector product, one IEEE operation at a time (include/orbx.hpp's se3_inverse; what
+// orbx_fuse_search_device's quat_rotate makes of it, orbx_api.hip)
+void ms_pose_inverse(const double* p, double* out) {
   const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
   const double* v = p + 4;
   const double t[3] = {2.0 * (y * v[2] - z * v[1]), 2.0 * (z * v[0] - x * v[2]), 2.0 * (x * v[1] - y * v[0])};
@@ -998,7 +948,7 @@ int win_check_empty(orbx_handle* h, const char* who, const WinPlan& P, const int
   return counts[2] && counts[3] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
 }
 
-// The collection into ws_map[1] (d) and its first download (hp), which the call waits for: counts | local (covisible) | fixed, and
+// The collection into ws_map.host_blobs (d) and its first download (hp), which the call waits for: counts | local (covisible) | fixed, and
 // with `rows` | P's slots | P's positions at their bounds.  The observations stay at d + o_ob.
 struct WinDown { size_t o_cn, o_lk, o_fx, o_ls, o_po, o_ob; uint8_t* d; const uint8_t* hp; };
 int win_collect_down(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, bool rows, WinDown& o) {
@@ -1010,9 +960,9 @@ int win_collect_down(orbx_handle* h, const char* who, orbx_map_points* mp, const
   o.o_ls = out.take(4 * bound); o.o_po = out.take(24 * bound);
   const size_t down = rows ? out.off : head;
   o.o_ob = out.take(16 * (size_t)P.n_feat);
-  if (int rc = orbx_reserve(h, h->ws_map[1], out.off)) return rc;
+  if (int rc = orbx_reserve(h, h->ws_map.host_blobs, out.off)) return rc;
   if (int rc = orbx_reserve_pinned(h, h->pin_map, down)) return rc;
-  uint8_t* d = o.d = (uint8_t*)h->ws_map[1].p;
+  uint8_t* d = o.d = (uint8_t*)h->ws_map.host_blobs.p;
   if (int rc = win_enqueue(h, who, mp, P, P.bound, P.n_feat, (int*)(d + o.o_cn), (int*)(d + o.o_lk), (int*)(d + o.o_fx), (int*)(d + o.o_ls), (double*)(d + o.o_po),
                            (orbx_ba_obs32*)(d + o.o_ob)))
     return rc;
@@ -1071,10 +1021,10 @@ int win_local_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const 
   std::vector<int> slots((const int*)(w.hp + w.o_ls), (const int*)(w.hp + w.o_ls) + M);
   for (int i = 0; i < Kw; ++i) {
     if (chain) std::memcpy(&poses[7 * (size_t)i], kfs[local[i]]->pose_wc, 56);
-    else bac_pose_inverse(kfs[local[1 + i]]->pose_wc, &poses[7 * (size_t)i]);
+    else ms_pose_inverse(kfs[local[1 + i]]->pose_wc, &poses[7 * (size_t)i]);
   }
-  bac_pose_inverse(kfs[local[0]]->pose_wc, &fixed_cw[0]);
-  for (int j = 0; j + 1 < F; ++j) bac_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
+  ms_pose_inverse(kfs[local[0]]->pose_wc, &fixed_cw[0]);
+  for (int j = 0; j + 1 < F; ++j) ms_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
   if (int rc = ba_solve_visual(h, cam, cfg, Kw, poses.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
                                initial_error, final_error, false, in, (const orbx_ba_obs32*)(w.d + w.o_ob), true))
     return rc;
@@ -1144,18 +1094,25 @@ int ms_track_host(orbx_handle* h, const char* who, const orbx_camera* cam, const
   // one blob each way: [kp | desc | search poses | priors | feat_start | feat_count | source slots] up,
   // [list offsets | list slots | offsets | pts3d | pts2d | mp_idx | feat_idx | poses | err | pnp records | matched | matched slots |
   //  records | inliers | local keyframes] down, and behind them the gathered positions and descriptors, which stay on the device
-  Carve in, out;
+  Carve in;
+  OutputPlan out;
   const size_t i_kp = in.take(sizeof(orbx_keypoint) * NF), i_de = in.take(32 * NF), i_sp = in.take(56 * B), i_pr = in.take(56 * B), i_fs = in.take(4 * B),
                i_fc = in.take(4 * B), i_ss = in.take(4 * S);
-  const size_t o_lo = out.take(4 * (B + 1)), o_ls = out.take(4 * M), o_of = out.take(4 * (B + 1)), o_p3 = out.take(24 * M), o_p2 = out.take(8 * M),
-               o_mi = out.take(4 * M), o_fi = out.take(4 * M), o_ps = out.take(56 * B), o_er = out.take(8 * M),
-               o_pn = out.take(sizeof(orbx_pnp_result) * B), o_ma = out.take(4 * B * mf), o_ms = out.take(4 * B * mf),
-               o_rs = out.take(sizeof(orbx_track_result) * B), o_in = out.take(M), o_lk = out.take(4 * NL);
-  const size_t down_bytes = out.off;
-  const size_t o_gp = out.take(24 * M), o_gd = out.take(32 * M);
-  HostCall c;
-  if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
-  uint8_t *hi = c.hi, *ho = c.ho, *di = c.di, *dout = c.dout;
+  // (the rows' lengths come down with the offsets: they are copied once those are known; matched / matched_slot are copied frame by frame)
+  const auto p_lo = out.add(H.list_offsets, B + 1), p_ls = out.add(H.list_slot, M, true), p_of = out.add(H.offsets, B + 1);
+  const auto p_p3 = out.add(H.pts3d, 3 * M, true);
+  const auto p_p2 = out.add(H.pts2d, 2 * M, true);
+  const auto p_mi = out.add(H.mp_idx, M, true), p_fi = out.add(H.feat_idx, M, true);
+  const auto p_ps = out.add(H.poses_wc_out, 7 * B), p_er = out.add(H.err_out, M, true);
+  const auto p_pn = out.add(H.pnp_results, B);
+  const auto p_ma = out.add((int*)nullptr, B * mf), p_ms = out.add((int*)nullptr, B * mf);
+  const auto p_rs = out.add(H.results, B);
+  const auto p_in = out.add(H.inlier_out, M, true);
+  const auto p_lk = out.add(H.local_kf, NL);
+  const size_t o_gp = out.keep(24 * M), o_gd = out.keep(32 * M);
+  if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs, in.off)) return rc;
+  const HostCall& c = out.call;
+  uint8_t *hi = c.hi, *di = c.di, *dout = c.dout;
   if (NF) { std::memcpy(hi + i_kp, H.kp, sizeof(orbx_keypoint) * NF); std::memcpy(hi + i_de, H.desc, 32 * NF); }
   std::memcpy(hi + i_sp, H.search_poses_wc, 56 * B);
   std::memcpy(hi + i_pr, H.priors_wc, 56 * B);
@@ -1166,35 +1123,26 @@ int ms_track_host(orbx_handle* h, const char* who, const orbx_camera* cam, const
   if (S) std::memcpy(hi + i_ss, H.src_slots, 4 * S);
   if (int rc = orbx_host_call_upload(h, c)) return rc;
   orbx_prof_begin_call(h);
-  int* d_lo = (int*)(dout + o_lo); int* d_ls = (int*)(dout + o_ls);
-  if (int rc = select((const int*)(di + i_ss), H.local_kf ? (int*)(dout + o_lk) : nullptr, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd)) return rc;
+  int* d_lo = out.dev(p_lo); int* d_ls = out.dev(p_ls);
+  if (int rc = select((const int*)(di + i_ss), H.local_kf ? out.dev(p_lk) : nullptr, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd)) return rc;
   TrackArgs A{};
   A.max_feat = max_feat; A.fc_stride = 1;
   A.kp = (const orbx_keypoint*)(di + i_kp); A.desc = di + i_de; A.feat_start = (const int*)(di + i_fs); A.feat_count = (const int*)(di + i_fc);
   A.positions = (const double*)(dout + o_gp); A.mp_desc = dout + o_gd; A.mp_off = d_lo;
   A.search_poses = (const double*)(di + i_sp); A.priors = (const double*)(di + i_pr);
-  A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2); A.mp_idx = (int*)(dout + o_mi);
-  A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps); A.matched = (int*)(dout + o_ma);
-  A.results = (orbx_track_result*)(dout + o_rs);
-  if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
-    return rc;
-  if (int rc = ms_matched_slot_enqueue(h, n_frames, max_feat, A.matched, d_lo, d_ls, (int*)(dout + o_ms))) return rc;
-  if (int rc = orbx_host_call_download(h, c, down_bytes)) return rc;
-  std::memcpy(H.list_offsets, ho + o_lo, 4 * (B + 1));
-  std::memcpy(H.offsets, ho + o_of, 4 * (B + 1));
-  std::memcpy(H.poses_wc_out, ho + o_ps, 56 * B);
-  std::memcpy(H.pnp_results, ho + o_pn, sizeof(orbx_pnp_result) * B);
-  std::memcpy(H.results, ho + o_rs, sizeof(orbx_track_result) * B);
-  if (H.local_kf && NL) std::memcpy(H.local_kf, ho + o_lk, 4 * NL);
+  A.offsets = out.dev(p_of); A.pts3d = out.dev(p_p3); A.pts2d = out.dev(p_p2); A.mp_idx = out.dev(p_mi);
+  A.feat_idx = out.dev(p_fi); A.poses_out = out.dev(p_ps); A.matched = out.dev(p_ma);
+  A.results = out.dev(p_rs);
+  if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, out.dev(p_in), out.dev(p_er), out.dev(p_pn))) return rc;
+  if (int rc = ms_matched_slot_enqueue(h, n_frames, max_feat, A.matched, d_lo, d_ls, out.dev(p_ms))) return rc;
+  if (int rc = out.finish(h)) return rc;
   const size_t L = (size_t)H.list_offsets[B], N = (size_t)H.offsets[B];
-  if (L) std::memcpy(H.list_slot, ho + o_ls, 4 * L);
-  if (N) {
-    std::memcpy(H.pts3d, ho + o_p3, 24 * N); std::memcpy(H.pts2d, ho + o_p2, 8 * N); std::memcpy(H.mp_idx, ho + o_mi, 4 * N);
-    std::memcpy(H.feat_idx, ho + o_fi, 4 * N); std::memcpy(H.err_out, ho + o_er, 8 * N); std::memcpy(H.inlier_out, ho + o_in, N);
-  }
+  if (int rc = out.copy(h, p_ls, L)) return rc;
+  for (int rc : {out.copy(h, p_p3, 3 * N), out.copy(h, p_p2, 2 * N), out.copy(h, p_mi, N), out.copy(h, p_fi, N), out.copy(h, p_er, N), out.copy(h, p_in, N)})
+    if (rc) return rc;
   for (size_t b = 0; b < B; ++b) {
     const size_t n = (size_t)(feat_offsets[b + 1] - feat_offsets[b]);
-    if (n) { std::memcpy(H.matched + feat_offsets[b], ho + o_ma + 4 * b * mf, 4 * n); std::memcpy(H.matched_slot + feat_offsets[b], ho + o_ms + 4 * b * mf, 4 * n); }
+    if (n) { std::memcpy(H.matched + feat_offsets[b], out.host(p_ma) + b * mf, 4 * n); std::memcpy(H.matched_slot + feat_offsets[b], out.host(p_ms) + b * mf, 4 * n); }
   }
   return ORBX_OK;
 }
@@ -1426,19 +1374,15 @@ int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const Obs
   if (int rc = ms_reserve_first(h, mp, 1)) return rc;
   const size_t K = P.C.kfs.size(), Mb = (size_t)c.n_points, Nb = c.d_obs_start ? (size_t)obs_entry_bound(P, c.n_points) : 0, NC = (size_t)c.n_cand;
   const int n_chunk = std::max(1, (P.C.max_n + MS_CHUNK - 1) / MS_CHUNK), n_part = std::max(1, (int)((Mb + MS_CHUNK - 1) / MS_CHUNK));
-  Carve up, ws;
-  const size_t o_kf = up.take(sizeof(CovKf) * K), o_n = up.take(4), o_sl = up.take(c.slots ? 4 * Mb : 0), o_ca = up.take(4 * NC);
+  UploadPlan up;
+  Carve ws;
+  const size_t o_kf = up.put(P.C.kfs.data(), sizeof(CovKf) * K), o_n = up.put(&c.n_points, 4), o_sl = up.put(c.slots, c.slots ? 4 * Mb : 0), o_ca = up.put(c.cand, 4 * NC);
   const size_t o_cn = ws.take(4 * Mb), o_cu = ws.take(4 * Mb), o_pa = ws.take(4 * (size_t)n_part), o_tk = ws.take(4 * Nb), o_tf = ws.take(4 * Nb),
                o_ct = ws.take(8 * NC * (size_t)n_chunk);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[9], up.off, &hs, &ds)) return rc;
-  if (K) std::memcpy(hs + o_kf, P.C.kfs.data(), sizeof(CovKf) * K);
-  std::memcpy(hs + o_n, &c.n_points, 4);
-  if (c.slots && Mb) std::memcpy(hs + o_sl, c.slots, 4 * Mb);
-  if (NC) std::memcpy(hs + o_ca, c.cand, 4 * NC);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[9], up.off)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_map[8], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[8].p;
+  if (int rc = up.send(h, h->ring_map, h->ws_map.obs_tables)) return rc;
+  uint8_t* const ds = up.device;
+  if (int rc = orbx_reserve(h, h->ws_map.obs_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.obs_scratch.p;
   ObsArgs A{};
   A.capacity = mp->capacity; A.n_kfs = (int)K; A.n_chunk = n_chunk; A.min_obs = c.min_obs;
   A.live = mp->d_live; A.kfs = (const CovKf*)(ds + o_kf);
@@ -1452,52 +1396,23 @@ int obs_enqueue(orbx_handle* h, orbx_map_points* mp, const ObsPlan& P, const Obs
   if (d_count_out) *d_count_out = A.count;
   const dim3 block(MS_THREADS), list_grid(std::max(1, (int)((Mb + MS_THREADS - 1) / MS_THREADS))), kf_grid(n_chunk, (unsigned)K);
   const bool walk = K > 0 && P.C.max_n > 0 && Mb > 0;
-  {
-    ProfScope ps(h, "obs_index_kernel");
-    hipLaunchKernelGGL(obs_index_kernel, list_grid, block, 0, h->stream, A);
-  }
-  if (walk) {
-    ProfScope ps(h, "obs_count_kernel", true);
-    hipLaunchKernelGGL(obs_count_kernel, kf_grid, block, 0, h->stream, A);
-  }
+  orbx_launch(h, "obs_index_kernel", false, obs_index_kernel, list_grid, block, 0, A);
+  if (walk) orbx_launch(h, "obs_count_kernel", true, obs_count_kernel, kf_grid, block, 0, A);
   if (c.d_obs_start) {
-    {
-      ProfScope ps(h, "obs_part_kernel", true);
-      hipLaunchKernelGGL(obs_part_kernel, dim3(n_part), block, 0, h->stream, A);
-    }
-    {
-      ProfScope ps(h, "obs_scan_kernel", true);
-      hipLaunchKernelGGL(obs_scan_kernel, dim3(n_part), block, 0, h->stream, A);
-    }
+    orbx_launch(h, "obs_part_kernel", true, obs_part_kernel, dim3(n_part), block, 0, A);
+    orbx_launch(h, "obs_scan_kernel", true, obs_scan_kernel, dim3(n_part), block, 0, A);
     if (walk && Nb > 0) {
-      {
-        ProfScope ps(h, "obs_append_kernel", true);
-        hipLaunchKernelGGL(obs_append_kernel, kf_grid, block, 0, h->stream, A);
-      }
-      {
-        ProfScope ps(h, "obs_rank_kernel", true);
-        hipLaunchKernelGGL(obs_rank_kernel, dim3((unsigned)((Nb + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
-      }
-      if (K > (size_t)OBS_SHORT) {                                          // (a segment is never longer than the call has keyframes)
-        ProfScope ps(h, "obs_rank_long_kernel", true);
-        hipLaunchKernelGGL(obs_rank_long_kernel, dim3((unsigned)std::min<size_t>(Mb, 4 * (size_t)h->n_cu)), block, 0, h->stream, A);
-      }
+      orbx_launch(h, "obs_append_kernel", true, obs_append_kernel, kf_grid, block, 0, A);
+      orbx_launch(h, "obs_rank_kernel", true, obs_rank_kernel, dim3((unsigned)((Nb + MS_THREADS - 1) / MS_THREADS)), block, 0, A);
+      if (K > (size_t)OBS_SHORT)                                            // (a segment is never longer than the call has keyframes)
+        orbx_launch(h, "obs_rank_long_kernel", true, obs_rank_long_kernel, dim3((unsigned)std::min<size_t>(Mb, 4 * (size_t)h->n_cu)), block, 0, A);
     }
   }
   if (NC) {
-    {
-      ProfScope ps(h, "red_count_kernel", true);
-      hipLaunchKernelGGL(red_count_kernel, dim3(n_chunk, (unsigned)NC), block, 0, h->stream, A);
-    }
-    {
-      ProfScope ps(h, "red_tail_kernel", true);
-      hipLaunchKernelGGL(red_tail_kernel, dim3((unsigned)((NC + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
-    }
+    orbx_launch(h, "red_count_kernel", true, red_count_kernel, dim3(n_chunk, (unsigned)NC), block, 0, A);
+    orbx_launch(h, "red_tail_kernel", true, red_tail_kernel, dim3((unsigned)((NC + MS_THREADS - 1) / MS_THREADS)), block, 0, A);
   }
-  {
-    ProfScope ps(h, "obs_restore_kernel", true);
-    hipLaunchKernelGGL(obs_restore_kernel, list_grid, block, 0, h->stream, A);
-  }
+  orbx_launch(h, "obs_restore_kernel", true, obs_restore_kernel, list_grid, block, 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -1525,27 +1440,21 @@ int obs_refresh_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, co
   }
   Carve ws;
   const size_t o_os = ws.take(4 * (Mz + 1)), o_ok = ws.take(4 * Nb), o_of = ws.take(4 * Nb), o_po = ws.take(24 * Mz);
-  if (int rc = orbx_reserve(h, h->ws_map[10], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[10].p;
+  if (int rc = orbx_reserve(h, h->ws_map.refresh_lists, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.refresh_lists.p;
   ObsCall c;
   c.n_points = M; c.slots = slots; c.d_obs_start = (int*)(w + o_os); c.d_obs_kf = (int*)(w + o_ok); c.d_obs_feat = (int*)(w + o_of);
   const int* d_slots = nullptr;
   if (int rc = obs_enqueue(h, mp, P, c, &d_slots)) return rc;
   const dim3 grid((M + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
-  {
-    ProfScope ps(h, "obs_gather_kernel", true);
-    hipLaunchKernelGGL(obs_gather_kernel, grid, block, 0, h->stream, d_slots, M, (const double*)mp->d_pos, (const uint8_t*)mp->d_desc, (double*)(w + o_po), d_mp_desc);
-  }
+  orbx_launch(h, "obs_gather_kernel", true, obs_gather_kernel, grid, block, 0, d_slots, M, (const double*)mp->d_pos, (const uint8_t*)mp->d_desc, (double*)(w + o_po), d_mp_desc);
   ORBX_HIP(h, hipGetLastError());
   // the entries' host-known bound stands in for obs_start[M]: the kernels take every length from obs_start itself
   if (int rc = mp_refresh_enqueue(h, who, M, (int)Nb, (const double*)(w + o_po), c.d_obs_start, c.d_obs_kf, c.d_obs_feat, (int)T, tab.data(), scale_range, d_mp_desc,
                                   d_normals_in, d_mp_desc, d_normals, d_min_distance, d_max_distance, d_records))
     return rc;
-  {
-    ProfScope ps(h, "map_scatter_kernel");
-    hipLaunchKernelGGL(map_scatter_kernel, grid, block, 0, h->stream, d_slots, M, (const double*)nullptr, (const uint8_t*)d_mp_desc, 1, mp->d_pos, mp->d_desc,
-                       mp->d_live);
-  }
+  orbx_launch(h, "map_scatter_kernel", false, map_scatter_kernel, grid, block, 0, d_slots, M, (const double*)nullptr, (const uint8_t*)d_mp_desc, 1, mp->d_pos, mp->d_desc,
+              mp->d_live);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -1576,8 +1485,8 @@ int red_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const RedP
   const int bound = P.S.bound_off[1];
   Carve ws;
   const size_t o_lo = ws.take(8), o_ls = ws.take(4 * (size_t)bound), o_po = ws.take(24 * (size_t)bound), o_de = ws.take(32 * (size_t)bound);
-  if (int rc = orbx_reserve(h, h->ws_map[10], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[10].p;
+  if (int rc = orbx_reserve(h, h->ws_map.refresh_lists, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.refresh_lists.p;
   if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, P.S, nullptr, nullptr, bound, (int*)(w + o_lo), (int*)(w + o_ls), (double*)(w + o_po),
                                  w + o_de))
     return rc;
@@ -1879,16 +1788,6 @@ struct MfPlan {
   int bound = 0, f_tgt = 0, n_feat = 0, max_n = 0, goner_bound = 0;
 };
 
-// se3.rs:56-63 as orbx_fuse_search_device makes it (orbx_api.hip: quat_rotate, one IEEE operation at a time)
-void mf_pose_inverse(const double* p, double* o) {
-  const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
-  const double* v = p + 4;
-  const double t0 = 2.0 * (y * v[2] - z * v[1]), t1 = 2.0 * (z * v[0] - x * v[2]), t2 = 2.0 * (x * v[1] - y * v[0]);
-  const double c0 = y * t2 - z * t1, c1 = z * t0 - x * t2, c2 = x * t1 - y * t0;
-  o[0] = w; o[1] = x; o[2] = y; o[3] = z;
-  o[4] = -(t0 * w + c0 + v[0]); o[5] = -(t1 * w + c1 + v[1]); o[6] = -(t2 * w + c2 + v[2]);
-}
-
 // what can be refused: nothing is enqueued and no keyframe touched
 int mf_check(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, int n_src, const int* src,
              int n_tgt, const int* tgt, unsigned desc_threshold) {
@@ -1946,7 +1845,7 @@ int mf_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kf
     const orbx_keyframe* kf = kfs[tgt[t]];
     MfTgt& g = P.tgts[(size_t)t];
     g.kp = kf->d_kp; g.desc = kf->d_desc; g.slots = kf->d_mp_slot; g.n = kf->n; g.feat_off = (int)ft;
-    mf_pose_inverse(kf->pose_wc, g.pose_cw);
+    ms_pose_inverse(kf->pose_wc, g.pose_cw);
     P.kfs[(size_t)tgt[t]].tgt = t;
     P.members[(size_t)t] = CovMember{tgt[t], t};
     ft += kf->n;
@@ -1965,21 +1864,21 @@ int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map
   const bool run = B > 0 && T > 0;
   if (!d_counts || (B > 0 && !d_list_slot) || (run && (!d_match || !d_goner || !d_keeper))) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   ORBX_HIP(h, hipSetDevice(h->device));
-  Carve ws, up;
+  Carve ws;
+  UploadPlan up;
   const size_t o_lo = ws.take(8), o_po = ws.take(24 * B), o_de = ws.take(32 * B);
   const size_t o_me = ws.take(run ? 4 * B * T : 0), o_ed = ws.take(run ? 4 * B * T : 0), o_la = ws.take(run ? 4 * Nb : 0), o_fc = ws.take(run ? 4 * (size_t)P.n_feat : 0),
                o_tg = ws.take(run ? 4 * Gb : 0), o_tk = ws.take(run ? 4 * Gb : 0), o_cl = ws.take(run ? 4 * (size_t)P.f_tgt : 0);
   const size_t o_zero = ws.off;                                             // zeroed before every pass: observer counts, keys, sizes, claim flags, changed, cursor
   const size_t o_no = ws.take(run ? 4 * Nb : 0), o_ke = ws.take(run ? 8 * Nb : 0), o_cs = ws.take(run ? 4 * Nb : 0), o_cc = ws.take(run ? 4 * Nb : 0),
                o_ch = ws.take(run ? 4 * K : 0), o_cu = ws.take(run ? 4 : 0);
-  if (int rc = orbx_reserve(h, h->ws_map[11], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[11].p;
+  if (int rc = orbx_reserve(h, h->ws_map.fuse_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.fuse_scratch.p;
   MfArgs A{};
   A.counts = d_counts;
   const dim3 block(MS_THREADS);
   if (B == 0) {                                                             // no candidate: P = 0
-    ProfScope ps(h, "mf_begin_kernel");
-    hipLaunchKernelGGL(mf_begin_kernel, dim3(1), block, 0, h->stream, A, 0);
+    orbx_launch(h, "mf_begin_kernel", false, mf_begin_kernel, dim3(1), block, 0, A, 0);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   }
@@ -1989,8 +1888,7 @@ int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map
   A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
   const dim3 list_grid((unsigned)((B + MS_THREADS - 1) / MS_THREADS));
   if (!run) {
-    ProfScope ps(h, "mf_begin_kernel", true);
-    hipLaunchKernelGGL(mf_begin_kernel, dim3(1), block, 0, h->stream, A, 0);
+    orbx_launch(h, "mf_begin_kernel", true, mf_begin_kernel, dim3(1), block, 0, A, 0);
     ORBX_HIP(h, hipGetLastError());
     return ORBX_OK;
   }
@@ -1999,12 +1897,10 @@ int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map
     if (int rc = orbx_reserve(h, mp->mark, need)) return rc;
     ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
   }
-  const size_t u_ck = up.take(sizeof(CovKf) * K), u_me = up.take(sizeof(CovMember) * T), u_tg = up.take(sizeof(MfTgt) * T), u_kf = up.take(sizeof(MfKf) * K);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[12], up.off, &hs, &ds)) return rc;
-  std::memcpy(hs + u_ck, P.ckfs.data(), sizeof(CovKf) * K); std::memcpy(hs + u_me, P.members.data(), sizeof(CovMember) * T);
-  std::memcpy(hs + u_tg, P.tgts.data(), sizeof(MfTgt) * T); std::memcpy(hs + u_kf, P.kfs.data(), sizeof(MfKf) * K);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[12], up.off)) return rc;
+  const size_t u_ck = up.put(P.ckfs.data(), sizeof(CovKf) * K), u_me = up.put(P.members.data(), sizeof(CovMember) * T), u_tg = up.put(P.tgts.data(), sizeof(MfTgt) * T),
+               u_kf = up.put(P.kfs.data(), sizeof(MfKf) * K);
+  if (int rc = up.send(h, h->ring_map, h->ws_map.fuse_tables)) return rc;
+  uint8_t* const ds = up.device;
   ORBX_HIP(h, hipMemsetAsync(w + o_zero, 0, ws.off - o_zero, h->stream));
   if (P.f_tgt > 0) ORBX_HIP(h, hipMemsetAsync(w + o_cl, MS_EMPTY & 0xff, 4 * (size_t)P.f_tgt, h->stream));
   A.cam = *cam; A.radius_scale = radius_scale; A.thr = desc_threshold;
@@ -2025,64 +1921,22 @@ int mf_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam, orbx_map
   const int n_chunk = std::max(1, (P.max_n + MS_CHUNK - 1) / MS_CHUNK), n_fine = std::max(1, (P.max_n + MS_THREADS - 1) / MS_THREADS);
   const dim3 mark_grid(std::max(1, (max_tn + MS_CHUNK - 1) / MS_CHUNK), (unsigned)T), pair_grid((unsigned)((B * T + MS_THREADS - 1) / MS_THREADS)),
       node_grid((unsigned)((Nb + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, (unsigned)K), feat_grid(n_fine, (unsigned)K);
-  {
-    ProfScope ps(h, "mf_begin_kernel", true);
-    hipLaunchKernelGGL(mf_begin_kernel, list_grid, block, 0, h->stream, A, 1);
-  }
-  {
-    ProfScope ps(h, "cov_mark_kernel", true);
-    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, C, 1);
-  }
-  {
-    ProfScope ps(h, "mf_search_kernel", true);
-    hipLaunchKernelGGL(mf_search_kernel, dim3((unsigned)((B + FUSE_THREADS - 1) / FUSE_THREADS), (unsigned)T), dim3(FUSE_THREADS), 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "cov_mark_kernel", true);
-    hipLaunchKernelGGL(cov_mark_kernel, mark_grid, block, 0, h->stream, C, 0);
-  }
-  {
-    ProfScope ps(h, "mf_name_kernel", true);
-    hipLaunchKernelGGL(mf_name_kernel, pair_grid, block, 0, h->stream, A);
-  }
+  orbx_launch(h, "mf_begin_kernel", true, mf_begin_kernel, list_grid, block, 0, A, 1);
+  orbx_launch(h, "cov_mark_kernel", true, cov_mark_kernel, mark_grid, block, 0, C, 1);
+  orbx_launch(h, "mf_search_kernel", true, mf_search_kernel, dim3((unsigned)((B + FUSE_THREADS - 1) / FUSE_THREADS), (unsigned)T), dim3(FUSE_THREADS), 0, A);
+  orbx_launch(h, "cov_mark_kernel", true, cov_mark_kernel, mark_grid, block, 0, C, 0);
+  orbx_launch(h, "mf_name_kernel", true, mf_name_kernel, pair_grid, block, 0, A);
+  if (P.max_n > 0) orbx_launch(h, "obs_count_kernel", true, obs_count_kernel, kf_grid, block, 0, O);
+  orbx_launch(h, "mf_class_kernel", true, mf_class_kernel, dim3(1), dim3(MF_CLASS_THREADS), 0, A);
+  orbx_launch(h, "mf_key_kernel", true, mf_key_kernel, node_grid, block, 0, A);
+  orbx_launch(h, "mf_goner_kernel", true, mf_goner_kernel, node_grid, block, 0, A);
+  orbx_launch(h, "mf_goner_rank_kernel", true, mf_goner_rank_kernel, dim3((unsigned)std::max<size_t>(1, (Gb + MS_THREADS - 1) / MS_THREADS)), block, 0, A);
   if (P.max_n > 0) {
-    ProfScope ps(h, "obs_count_kernel", true);
-    hipLaunchKernelGGL(obs_count_kernel, kf_grid, block, 0, h->stream, O);
+    orbx_launch(h, "mf_feat_kernel", true, mf_feat_kernel, feat_grid, block, 0, A);
+    orbx_launch(h, "mf_rewrite_kernel", true, mf_rewrite_kernel, feat_grid, block, 0, A);
+    orbx_launch(h, "mf_uniq_kernel", true, mf_uniq_kernel, feat_grid, block, 0, A);
   }
-  {
-    ProfScope ps(h, "mf_class_kernel", true);
-    hipLaunchKernelGGL(mf_class_kernel, dim3(1), dim3(MF_CLASS_THREADS), 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "mf_key_kernel", true);
-    hipLaunchKernelGGL(mf_key_kernel, node_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "mf_goner_kernel", true);
-    hipLaunchKernelGGL(mf_goner_kernel, node_grid, block, 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "mf_goner_rank_kernel", true);
-    hipLaunchKernelGGL(mf_goner_rank_kernel, dim3((unsigned)std::max<size_t>(1, (Gb + MS_THREADS - 1) / MS_THREADS)), block, 0, h->stream, A);
-  }
-  if (P.max_n > 0) {
-    {
-      ProfScope ps(h, "mf_feat_kernel", true);
-      hipLaunchKernelGGL(mf_feat_kernel, feat_grid, block, 0, h->stream, A);
-    }
-    {
-      ProfScope ps(h, "mf_rewrite_kernel", true);
-      hipLaunchKernelGGL(mf_rewrite_kernel, feat_grid, block, 0, h->stream, A);
-    }
-    {
-      ProfScope ps(h, "mf_uniq_kernel", true);
-      hipLaunchKernelGGL(mf_uniq_kernel, feat_grid, block, 0, h->stream, A);
-    }
-  }
-  {
-    ProfScope ps(h, "mf_restore_kernel", true);
-    hipLaunchKernelGGL(mf_restore_kernel, node_grid, block, 0, h->stream, A);
-  }
+  orbx_launch(h, "mf_restore_kernel", true, mf_restore_kernel, node_grid, block, 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -2280,14 +2134,17 @@ int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_
   int max_n = 0;
   size_t n_feat = 0;
   for (const orbx_keyframe* kf : all) { max_n = std::max(max_n, kf->n); n_feat += (size_t)kf->n; }
-  Carve up, ws;
-  const size_t u_kf = up.take(sizeof(McKf) * K), u_fr = up.take(4 * NF), u_or = up.take(4 * Ts), u_se = up.take(4 * (size_t)T), u_tri = up.take(P.up_bytes);
+  UploadPlan up;
+  Carve ws;
+  // (the keyframe table, `searched` and the neighbour loop's tables are made in place: they hold addresses inside the two workspaces)
+  const size_t u_kf = up.put(nullptr, sizeof(McKf) * K), u_fr = up.put(free_slots, 4 * NF), u_or = up.put(P.orig.data(), 4 * Ts), u_se = up.put(nullptr, 4 * (size_t)T),
+               u_tri = up.put(nullptr, P.up_bytes);
   const size_t o_fl = ws.take(n_feat), o_la = ws.take(4 * n1), o_zero = ws.off, o_ch = ws.take(4 * K), o_ns = ws.take(8), o_zend = ws.off, o_tri = ws.take(P.ws_bytes),
                o_he = ws.take(4 * (1 + 4 * Ts)), o_nb = ws.take(4 * capd), o_i1 = ws.take(4 * capd), o_i2 = ws.take(4 * capd), o_pt = ws.take(24 * capd);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[13], up.off, &hs, &ds)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_map[14], ws.off)) return rc;
-  uint8_t* w = (uint8_t*)h->ws_map[14].p;
+  if (int rc = up.begin(h, h->ring_map, h->ws_map.create_tables)) return rc;
+  uint8_t *const hs = up.host, *const ds = up.device;
+  if (int rc = orbx_reserve(h, h->ws_map.create_scratch, ws.off)) return rc;
+  uint8_t* w = (uint8_t*)h->ws_map.create_scratch.p;
   McKf* kt = (McKf*)(hs + u_kf);
   std::vector<const uint8_t*> mp2((size_t)T);
   size_t f = 0;
@@ -2296,15 +2153,11 @@ int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_
     if (k > 0) mp2[k - 1] = kt[k].flag;
     f += (size_t)all[k]->n;
   }
-  if (NF) std::memcpy(hs + u_fr, free_slots, 4 * NF);
   int* searched = (int*)(hs + u_se);
   for (int t = 0; t < T; ++t) searched[t] = -1;
   for (size_t k = 0; k < Ts; ++k) searched[P.orig[k]] = (int)k;
-  if (Ts) {
-    std::memcpy(hs + u_or, P.orig.data(), 4 * Ts);
-    tri_nb_fill(P, cam, cfg, cur, nbs, kt[0].flag, mp2.data(), hs + u_tri, ds + u_tri, w + o_tri);
-  }
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[13], up.off)) return rc;
+  if (Ts) tri_nb_fill(P, cam, cfg, cur, nbs, kt[0].flag, mp2.data(), hs + u_tri, ds + u_tri, w + o_tri);
+  if (int rc = up.commit(h, h->ring_map, h->ws_map.create_tables)) return rc;
   ORBX_HIP(h, hipMemsetAsync(w + o_zero, 0, o_zend - o_zero, h->stream));
   if (n1) ORBX_HIP(h, hipMemsetAsync(w + o_la, 0xff, 4 * n1, h->stream));
   McArgs A{};
@@ -2319,14 +2172,8 @@ int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_
   A.stats = d_stats;
   const dim3 block(MS_THREADS);
   orbx_prof_begin_call(h);
-  if (max_n > 0) {
-    ProfScope ps(h, "mc_flag_kernel");
-    hipLaunchKernelGGL(mc_flag_kernel, dim3((max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, h->stream, A);
-  }
-  if ((phases & ORBX_MAP_CREATE_STEREO) && n1 > 0) {
-    ProfScope ps(h, "mc_stereo_kernel", true);
-    hipLaunchKernelGGL(mc_stereo_kernel, dim3(1), block, 0, h->stream, A);
-  }
+  if (max_n > 0) orbx_launch(h, "mc_flag_kernel", false, mc_flag_kernel, dim3((max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, A);
+  if ((phases & ORBX_MAP_CREATE_STEREO) && n1 > 0) orbx_launch(h, "mc_stereo_kernel", true, mc_stereo_kernel, dim3(1), block, 0, A);
   ORBX_HIP(h, hipGetLastError());
   if (Ts) {
     if (int rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, ds + u_tri, w + o_tri, (int)capd, (int*)(w + o_he), (int*)(w + o_nb), (int*)(w + o_i1), (int*)(w + o_i2),
@@ -2335,18 +2182,9 @@ int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_
     A.head = (const int*)(w + o_he);
   }
   const dim3 pair_grid((unsigned)((std::max<size_t>({capd, 4 * (size_t)T, (size_t)1}) + MS_THREADS - 1) / MS_THREADS));
-  {
-    ProfScope ps(h, "mc_pair_kernel", max_n > 0);
-    hipLaunchKernelGGL(mc_pair_kernel, pair_grid, block, 0, h->stream, A);
-  }
-  if (capd > 0) {
-    ProfScope ps(h, "mc_last_kernel", true);
-    hipLaunchKernelGGL(mc_last_kernel, pair_grid, block, 0, h->stream, A);
-  }
-  if (max_n > 0 && n_free > 0) {
-    ProfScope ps(h, "mc_uniq_kernel", true);
-    hipLaunchKernelGGL(mc_uniq_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, (unsigned)K), block, 0, h->stream, A);
-  }
+  orbx_launch(h, "mc_pair_kernel", max_n > 0, mc_pair_kernel, pair_grid, block, 0, A);
+  if (capd > 0) orbx_launch(h, "mc_last_kernel", true, mc_last_kernel, pair_grid, block, 0, A);
+  if (max_n > 0 && n_free > 0) orbx_launch(h, "mc_uniq_kernel", true, mc_uniq_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, (unsigned)K), block, 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -2360,34 +2198,24 @@ int mr_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int n, con
     if (int rc = orbx_reserve(h, mp->mark, (size_t)mp->capacity)) return rc;
     ORBX_HIP(h, hipMemsetAsync(mp->mark.p, 0, mp->mark.bytes, h->stream));
   }
-  Carve up;
-  const size_t u_kf = up.take(sizeof(McKf) * K), u_sl = up.take(4 * N), u_cn = up.take(4);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[15], up.off, &hs, &ds)) return rc;
+  UploadPlan up;
+  const size_t u_kf = up.put(nullptr, sizeof(McKf) * K), u_sl = up.put(slots, 4 * N), u_cn = up.put(nullptr, 4);
+  if (int rc = up.begin(h, h->ring_map, h->ws_map.remove_tables)) return rc;
+  uint8_t *const hs = up.host, *const ds = up.device;
   McKf* kt = (McKf*)(hs + u_kf);
   for (size_t k = 0; k < K; ++k) kt[k] = McKf{const_cast<int*>(P.kfs[k].slots), const_cast<int*>(P.kfs[k].uniq), nullptr, P.kfs[k].n, 0};
-  std::memcpy(hs + u_sl, slots, 4 * N);
   std::memset(hs + u_cn, 0, 4);
-  if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[15], up.off)) return rc;
+  if (int rc = up.commit(h, h->ring_map, h->ws_map.remove_tables)) return rc;
   const int* d_slots = (const int*)(ds + u_sl);
   uint8_t* mark = (uint8_t*)mp->mark.p;
   const dim3 block(MS_THREADS), list_grid((unsigned)((N + MS_THREADS - 1) / MS_THREADS));
   *d_cleared = (const int*)(ds + u_cn);
   orbx_prof_begin_call(h);
   if (K > 0 && P.max_n > 0) {
-    {
-      ProfScope ps(h, "mr_mark_kernel");
-      hipLaunchKernelGGL(mr_mark_kernel, list_grid, block, 0, h->stream, d_slots, n, mark, 1);
-    }
-    {
-      ProfScope ps(h, "mr_clear_kernel", true);
-      hipLaunchKernelGGL(mr_clear_kernel, dim3((P.max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, h->stream, (const McKf*)(ds + u_kf), mp->capacity,
-                         (const uint8_t*)mark, (int*)(ds + u_cn));
-    }
-    {
-      ProfScope ps(h, "mr_mark_kernel", true);
-      hipLaunchKernelGGL(mr_mark_kernel, list_grid, block, 0, h->stream, d_slots, n, mark, 0);
-    }
+    orbx_launch(h, "mr_mark_kernel", false, mr_mark_kernel, list_grid, block, 0, d_slots, n, mark, 1);
+    orbx_launch(h, "mr_clear_kernel", true, mr_clear_kernel, dim3((P.max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, (const McKf*)(ds + u_kf), mp->capacity,
+                (const uint8_t*)mark, (int*)(ds + u_cn));
+    orbx_launch(h, "mr_mark_kernel", true, mr_mark_kernel, list_grid, block, 0, d_slots, n, mark, 0);
   }
   return ms_erase_launch(h, mp, d_slots, slots, n);
 }
@@ -2459,10 +2287,10 @@ int orbx_map_points_erase(orbx_map_points* mp, const int* slots, int n) {
     if (int rc = ms_check_slots(mp, who, slots, n, false)) return rc;
     if (n == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    uint8_t *hs, *ds;
-    if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[2], 4 * (size_t)n, &hs, &ds)) return rc;
+    uint8_t *hs, *ds;                                                     // (one piece, copied to its last byte and no further: no plan)
+    if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map.call_tables, 4 * (size_t)n, &hs, &ds)) return rc;
     std::memcpy(hs, slots, 4 * (size_t)n);
-    if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[2], 4 * (size_t)n)) return rc;
+    if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map.call_tables, 4 * (size_t)n)) return rc;
     return ms_erase_launch(h, mp, (const int*)ds, slots, n);
   });
 }
@@ -2605,19 +2433,14 @@ int orbx_map_covisibility(orbx_handle* h, orbx_map_points* mp, int n_kfs, const 
     if (n_queries == 0 || n_kfs == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
     const size_t Q = (size_t)n_queries, K = (size_t)n_kfs, nb = (size_t)n_best;
-    Carve out;
-    const size_t o_we = out.take(weights ? 4 * Q * K : 0), o_be = out.take(best ? 4 * Q * nb : 0), o_nb = out.take(n_best_out ? 4 * Q : 0);
-    if (out.off == 0) return ORBX_OK;
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-    if (int rc = cov_enqueue(h, mp, P, n_queries, query, n_best, weights ? (int*)(c.dout + o_we) : nullptr, best && nb ? (int*)(c.dout + o_be) : nullptr,
-                             n_best_out ? (int*)(c.dout + o_nb) : nullptr, nullptr))
+    OutputPlan out;
+    const auto p_we = out.add(weights, weights ? Q * K : 0), p_be = out.add(best, best ? Q * nb : 0), p_nb = out.add(n_best_out, n_best_out ? Q : 0);
+    if (out.down == 0) return ORBX_OK;
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
+    if (int rc = cov_enqueue(h, mp, P, n_queries, query, n_best, weights ? out.dev(p_we) : nullptr, best && nb ? out.dev(p_be) : nullptr,
+                             n_best_out ? out.dev(p_nb) : nullptr, nullptr))
       return rc;
-    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-    if (weights) std::memcpy(weights, c.ho + o_we, 4 * Q * K);
-    if (best && nb) std::memcpy(best, c.ho + o_be, 4 * Q * nb);
-    if (n_best_out) std::memcpy(n_best_out, c.ho + o_nb, 4 * Q);
-    return ORBX_OK;
+    return out.finish(h);
   });
 }
 
@@ -2773,16 +2596,14 @@ int orbx_map_observations(orbx_handle* h, orbx_map_points* mp, int n_kfs, const 
       return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (obs_cap %d must reach the observations' bound %d: the features of kfs[] summed)", who, obs_cap, P.n_feat);
     ORBX_HIP(h, hipSetDevice(h->device));
     const size_t Mz = (size_t)M, Nb = (size_t)obs_entry_bound(P, M);
-    Carve out;
-    const size_t o_os = out.take(4 * (Mz + 1)), o_ok = out.take(4 * Nb), o_of = out.take(4 * Nb);
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-    if (int rc = obs_lists_call(h, who, mp, P, M, slots, P.n_feat, (int*)(c.dout + o_os), (int*)(c.dout + o_ok), (int*)(c.dout + o_of))) return rc;
-    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-    std::memcpy(obs_start, c.ho + o_os, 4 * (Mz + 1));
-    const size_t N = (size_t)obs_start[M];
-    if (N) { std::memcpy(obs_kf, c.ho + o_ok, 4 * N); std::memcpy(obs_feat, c.ho + o_of, 4 * N); }
-    return ORBX_OK;
+    OutputPlan out;
+    const auto p_os = out.add(obs_start, Mz + 1), p_ok = out.add(obs_kf, Nb, true), p_of = out.add(obs_feat, Nb, true);
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
+    if (int rc = obs_lists_call(h, who, mp, P, M, slots, P.n_feat, out.dev(p_os), out.dev(p_ok), out.dev(p_of))) return rc;
+    if (int rc = out.finish(h)) return rc;
+    const size_t N = (size_t)obs_start[M];                                  // the entries there are, not their bound
+    if (int rc = out.copy(h, p_ok, N)) return rc;
+    return out.copy(h, p_of, N);
   });
 }
 
@@ -2815,21 +2636,20 @@ int orbx_map_refresh_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, cons
     ORBX_HIP(h, hipSetDevice(h->device));
     // the normals up (they are kept where no observer is far enough), one blob down: [mp_desc | normals | min | max | records]
     const size_t Mz = (size_t)M;
-    Carve in, out;
+    Carve in;
+    OutputPlan out;
     const size_t i_nr = in.take(24 * Mz);
-    const size_t o_md = out.take(32 * Mz), o_nr = out.take(24 * Mz), o_mn = out.take(8 * Mz), o_mx = out.take(8 * Mz), o_rc = out.take(sizeof(orbx_mp_refresh_record) * Mz);
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], in.off, out.off, c)) return rc;
+    const auto p_md = out.add(mp_desc, 32 * Mz);
+    const auto p_nr = out.add(normals, 3 * Mz), p_mn = out.add(min_distance, Mz), p_mx = out.add(max_distance, Mz);
+    const auto p_rc = out.add(records, Mz);
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs, in.off)) return rc;
+    const HostCall& c = out.call;
     std::memcpy(c.hi + i_nr, normals, 24 * Mz);
     if (int rc = orbx_host_call_upload(h, c)) return rc;
-    if (int rc = obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, (const double*)(c.di + i_nr), c.dout + o_md, (double*)(c.dout + o_nr),
-                                     (double*)(c.dout + o_mn), (double*)(c.dout + o_mx), (orbx_mp_refresh_record*)(c.dout + o_rc)))
+    if (int rc = obs_refresh_enqueue(h, who, mp, P, kfs, M, slots, scale_range, (const double*)(c.di + i_nr), out.dev(p_md), out.dev(p_nr), out.dev(p_mn), out.dev(p_mx),
+                                     out.dev(p_rc)))
       return rc;
-    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-    std::memcpy(mp_desc, c.ho + o_md, 32 * Mz); std::memcpy(normals, c.ho + o_nr, 24 * Mz);
-    std::memcpy(min_distance, c.ho + o_mn, 8 * Mz); std::memcpy(max_distance, c.ho + o_mx, 8 * Mz);
-    std::memcpy(records, c.ho + o_rc, sizeof(orbx_mp_refresh_record) * Mz);
-    return ORBX_OK;
+    return out.finish(h);
   });
 }
 
@@ -2856,14 +2676,12 @@ int orbx_map_keyframe_redundancy(orbx_handle* h, orbx_map_points* mp, int n_kfs,
     if (!total || !redundant || !cull) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
     ORBX_HIP(h, hipSetDevice(h->device));
     const size_t NC = (size_t)n_cand;
-    Carve out;
-    const size_t o_to = out.take(4 * NC), o_re = out.take(4 * NC), o_cu = out.take(NC);
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-    if (int rc = red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, (int*)(c.dout + o_to), (int*)(c.dout + o_re), c.dout + o_cu)) return rc;
-    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-    std::memcpy(total, c.ho + o_to, 4 * NC); std::memcpy(redundant, c.ho + o_re, 4 * NC); std::memcpy(cull, c.ho + o_cu, NC);
-    return ORBX_OK;
+    OutputPlan out;
+    const auto p_to = out.add(total, NC), p_re = out.add(redundant, NC);
+    const auto p_cu = out.add(cull, NC);
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
+    if (int rc = red_enqueue(h, who, mp, P, n_cand, cand, min_observations, threshold, out.dev(p_to), out.dev(p_re), out.dev(p_cu))) return rc;
+    return out.finish(h);
   });
 }
 
@@ -2898,13 +2716,12 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
     if (K > 0 && (!d_kf_positions || !d_kf_valid)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
     ORBX_HIP(h, hipSetDevice(h->device));
     if (max_n > 0) {
-      uint8_t *hs, *ds;
-      if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B, &hs, &ds)) return rc;
+      uint8_t *hs, *ds;                                                   // (one piece, copied to its last byte and no further: no plan)
+      if (int rc = orbx_ring_begin(h, h->ring_map, h->ws_map.ref_items, sizeof(MapRefItem) * B, &hs, &ds)) return rc;
       std::memcpy(hs, tab.data(), sizeof(MapRefItem) * B);
-      if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map[3], sizeof(MapRefItem) * B)) return rc;
-      ProfScope ps(h, "map_ref_gather_kernel");
-      hipLaunchKernelGGL(map_ref_gather_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, n_frames), dim3(MS_THREADS), 0, h->stream, (const MapRefItem*)ds,
-                         mp->d_live, mp->d_pos, mp->capacity, d_kf_positions, d_kf_valid);
+      if (int rc = orbx_ring_commit(h, h->ring_map, h->ws_map.ref_items, sizeof(MapRefItem) * B)) return rc;
+      orbx_launch(h, "map_ref_gather_kernel", false, map_ref_gather_kernel, dim3((max_n + MS_THREADS - 1) / MS_THREADS, n_frames), dim3(MS_THREADS), 0, (const MapRefItem*)ds,
+                  mp->d_live, mp->d_pos, mp->capacity, d_kf_positions, d_kf_valid);
     }
     ORBX_HIP(h, hipGetLastError());
     return track_reference_enqueue(h, who, cam, pnp_cfg, min_correspondences, n_frames, d_kp, d_desc, d_feat_start, d_feat_count, feat_count_stride,
@@ -2961,20 +2778,15 @@ int orbx_map_fuse(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, i
     MfPlan P;
     if (int rc = mf_plan(h, who, mp, n_kfs, kfs, n_src, src, n_tgt, tgt, P)) return rc;
     const size_t B = (size_t)P.bound, T = (size_t)n_tgt, Gb = (size_t)P.goner_bound;
-    Carve out;
-    const size_t o_cn = out.take(16), o_go = out.take(4 * Gb), o_ke = out.take(4 * Gb), o_ls = out.take(4 * B), o_ma = out.take(4 * B * T);
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
+    OutputPlan out;
+    const auto p_cn = out.add(counts, 4), p_go = out.add(goner, Gb, true), p_ke = out.add(keeper, Gb, true), p_ls = out.add(list_slot, B, true), p_ma = out.add(match, B * T, true);
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
     orbx_prof_begin_call(h);
-    if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, (int*)(c.dout + o_cn), (int*)(c.dout + o_ls), (int*)(c.dout + o_ma), (int*)(c.dout + o_go),
-                            (int*)(c.dout + o_ke)))
-      return rc;
-    if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
-    std::memcpy(counts, c.ho + o_cn, 16);
+    if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, out.dev(p_cn), out.dev(p_ls), out.dev(p_ma), out.dev(p_go), out.dev(p_ke))) return rc;
+    if (int rc = out.finish(h)) return rc;
     const size_t Pn = (size_t)counts[0], G = (size_t)counts[3];
-    if (Pn) std::memcpy(list_slot, c.ho + o_ls, 4 * Pn);
-    if (Pn && T) std::memcpy(match, c.ho + o_ma, 4 * Pn * T);
-    if (G) { std::memcpy(goner, c.ho + o_go, 4 * G); std::memcpy(keeper, c.ho + o_ke, 4 * G); }
+    for (int rc : {out.copy(h, p_ls, Pn), out.copy(h, p_ma, Pn * T), out.copy(h, p_go, G), out.copy(h, p_ke, G)})
+      if (rc) return rc;
     return G ? orbx_map_points_erase(mp, goner, (int)G) : ORBX_OK;
   });
 }
@@ -3015,27 +2827,23 @@ int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_ma
     if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, ak.data(), aoff, nullptr, S)) return rc;
     const size_t Ta = (size_t)n_nb, Ba = (size_t)A.bound, Bb = (size_t)B.bound, Ga = (size_t)A.goner_bound, Gb = (size_t)B.goner_bound, Ab = (size_t)S.bound_off[1];
     // ONE download: counts A | counts B | goners and keepers of A, of B | the affected list; behind it what stays on the device
-    Carve out;
-    const size_t o_cn = out.take(32), o_ga = out.take(4 * Ga), o_ka = out.take(4 * Ga), o_gb = out.take(4 * Gb), o_kb = out.take(4 * Gb), o_ao = out.take(8),
-                 o_as = out.take(4 * Ab);
-    const size_t down = out.off;
-    const size_t o_la = out.take(4 * Ba), o_ma = out.take(4 * Ba * Ta), o_lb = out.take(4 * Bb), o_mb = out.take(4 * Bb), o_ap = out.take(24 * Ab), o_ad = out.take(32 * Ab);
+    OutputPlan out;
+    const auto p_cn = out.add(counts, 8), p_ga = out.add(goner_a, Ga, true), p_ka = out.add(keeper_a, Ga, true), p_gb = out.add(goner_b, Gb, true),
+               p_kb = out.add(keeper_b, Gb, true), p_ao = out.add((int*)nullptr, 2), p_as = out.add(affected_slot, Ab, true);
+    const size_t o_la = out.keep(4 * Ba), o_ma = out.keep(4 * Ba * Ta), o_lb = out.keep(4 * Bb), o_mb = out.keep(4 * Bb), o_ap = out.keep(24 * Ab), o_ad = out.keep(32 * Ab);
     // (the refresh below is a host form of its own: it takes the pinned buffer and the blob workspace once everything is copied out of them)
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-    uint8_t* d = c.dout;
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
+    uint8_t* d = out.call.dout;
     orbx_prof_begin_call(h);
-    if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, (int*)(d + o_cn), (int*)(d + o_la), (int*)(d + o_ma), (int*)(d + o_ga), (int*)(d + o_ka))) return rc;
-    if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, (int*)(d + o_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), (int*)(d + o_gb), (int*)(d + o_kb))) return rc;
-    if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, (int*)(d + o_ao), (int*)(d + o_as), (double*)(d + o_ap), d + o_ad))
+    if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, out.dev(p_cn), (int*)(d + o_la), (int*)(d + o_ma), out.dev(p_ga), out.dev(p_ka))) return rc;
+    if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, out.dev(p_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), out.dev(p_gb), out.dev(p_kb))) return rc;
+    if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, out.dev(p_ao), out.dev(p_as), (double*)(d + o_ap), d + o_ad))
       return rc;
-    if (int rc = orbx_host_call_download(h, c, down)) return rc;
-    std::memcpy(counts, c.ho + o_cn, 32);
-    const size_t na = (size_t)counts[3], nbg = (size_t)counts[7], M = (size_t)((const int*)(c.ho + o_ao))[1];
-    if (na) { std::memcpy(goner_a, c.ho + o_ga, 4 * na); std::memcpy(keeper_a, c.ho + o_ka, 4 * na); }
-    if (nbg) { std::memcpy(goner_b, c.ho + o_gb, 4 * nbg); std::memcpy(keeper_b, c.ho + o_kb, 4 * nbg); }
+    if (int rc = out.finish(h)) return rc;
+    const size_t na = (size_t)counts[3], nbg = (size_t)counts[7], M = (size_t)out.host(p_ao)[1];
+    for (int rc : {out.copy(h, p_ga, na), out.copy(h, p_ka, na), out.copy(h, p_gb, nbg), out.copy(h, p_kb, nbg), out.copy(h, p_as, M)})
+      if (rc) return rc;
     *n_affected = (int)M;
-    if (M) std::memcpy(affected_slot, c.ho + o_as, 4 * M);
     if (na) if (int rc = orbx_map_points_erase(mp, goner_a, (int)na)) return rc;
     if (nbg) if (int rc = orbx_map_points_erase(mp, goner_b, (int)nbg)) return rc;
     if (M == 0) return ORBX_OK;
@@ -3056,14 +2864,8 @@ int orbx_keyframe_set_map_point_slots_device(orbx_keyframe* kf, const orbx_map_p
     ORBX_HIP(h, hipSetDevice(h->device));
     if (kf->n > 0) {
       const dim3 grid((kf->n + MS_THREADS - 1) / MS_THREADS), block(MS_THREADS);
-      {
-        ProfScope ps(h, "mc_table_kernel");
-        hipLaunchKernelGGL(mc_table_kernel, grid, block, 0, h->stream, d_slots, kf->n, mp->capacity, kf->d_mp_slot);
-      }
-      {
-        ProfScope ps(h, "mc_uniq_one_kernel", true);
-        hipLaunchKernelGGL(mc_uniq_one_kernel, grid, block, 0, h->stream, (const int*)kf->d_mp_slot, kf->d_mp_uniq, kf->n);
-      }
+      orbx_launch(h, "mc_table_kernel", false, mc_table_kernel, grid, block, 0, d_slots, kf->n, mp->capacity, kf->d_mp_slot);
+      orbx_launch(h, "mc_uniq_one_kernel", true, mc_uniq_one_kernel, grid, block, 0, (const int*)kf->d_mp_slot, kf->d_mp_uniq, kf->n);
       ORBX_HIP(h, hipGetLastError());
     }
     kf->slot_store = mp;
@@ -3098,26 +2900,22 @@ int orbx_map_create_points(orbx_handle* h, const orbx_camera* cam, const orbx_tr
     ORBX_HIP(h, hipSetDevice(h->device));
     // ONE download: counts | stats | the lists; the descriptors stay behind them for set_device
     const size_t NF = (size_t)n_free, Tz = (size_t)T;
-    Carve out;
-    const size_t o_cn = out.take(16), o_st = out.take(16 * Tz), o_sl = out.take(4 * NF), o_nb = out.take(4 * NF), o_i1 = out.take(4 * NF), o_i2 = out.take(4 * NF),
-                 o_pt = out.take(24 * NF);
-    const size_t down = out.off;
-    const size_t o_de = out.take(32 * NF);
-    HostCall c;
-    if (int rc = orbx_host_call_begin(h, h->pin_map, h->ws_map[1], 0, out.off, c)) return rc;
-    uint8_t* d = c.dout;
-    if (int rc = mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, (int*)(d + o_cn), (int*)(d + o_sl), (int*)(d + o_nb), (int*)(d + o_i1),
-                            (int*)(d + o_i2), (double*)(d + o_pt), d + o_de, (int*)(d + o_st)))
+    OutputPlan out;
+    const auto p_cn = out.add(counts, 4), p_st = out.add(stats, 4 * Tz), p_sl = out.add(new_slot, NF, true), p_nb = out.add(new_neighbour, NF, true),
+               p_i1 = out.add(new_idx1, NF, true), p_i2 = out.add(new_idx2, NF, true);
+    const auto p_pt = out.add(new_points, 3 * NF, true);
+    const size_t o_de = out.keep(32 * NF);
+    if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
+    uint8_t* d_de = out.call.dout + o_de;
+    if (int rc = mc_enqueue(h, cam, cfg, is_inertial, mp, cur, nbs, T, phases, free_slots, n_free, out.dev(p_cn), out.dev(p_sl), out.dev(p_nb), out.dev(p_i1), out.dev(p_i2),
+                            out.dev(p_pt), d_de, out.dev(p_st)))
       return rc;
-    if (int rc = orbx_host_call_download(h, c, down)) return rc;
-    std::memcpy(counts, c.ho + o_cn, 16);
-    if (Tz) std::memcpy(stats, c.ho + o_st, 16 * Tz);
+    if (int rc = out.finish(h)) return rc;
     const size_t created = (size_t)counts[2];
     if (created == 0) return ORBX_OK;
-    std::memcpy(new_slot, c.ho + o_sl, 4 * created); std::memcpy(new_neighbour, c.ho + o_nb, 4 * created);
-    std::memcpy(new_idx1, c.ho + o_i1, 4 * created); std::memcpy(new_idx2, c.ho + o_i2, 4 * created);
-    std::memcpy(new_points, c.ho + o_pt, 24 * created);
-    return ms_set(mp, who, free_slots, (int)created, (const double*)(d + o_pt), d + o_de, false);
+    for (int rc : {out.copy(h, p_sl, created), out.copy(h, p_nb, created), out.copy(h, p_i1, created), out.copy(h, p_i2, created), out.copy(h, p_pt, 3 * created)})
+      if (rc) return rc;
+    return ms_set(mp, who, free_slots, (int)created, out.dev(p_pt), d_de, false);
   });
 }
 

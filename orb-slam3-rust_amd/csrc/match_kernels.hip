@@ -834,10 +834,7 @@ int launch_crosscheck(orbx_handle* h, const uint8_t* d_q, int nq, const uint8_t*
     hipLaunchKernelGGL(nn_kernel, dim3((nq + NN_Q - 1) / NN_Q), dim3(256), 0, h->stream, d_q, nq, d_t, nt, fwd, fdist);
     hipLaunchKernelGGL(nn_kernel, dim3((nt + NN_Q - 1) / NN_Q), dim3(256), 0, h->stream, d_t, nt, d_q, nq, bwd, bdist);
   }
-  {
-    ProfScope ps(h, "crosscheck_compact_kernel");
-    hipLaunchKernelGGL(crosscheck_compact_kernel, dim3(1), dim3(256), 0, h->stream, fwd, fdist, bwd, nq, d_out, d_n_out);
-  }
+  orbx_launch(h, "crosscheck_compact_kernel", false, crosscheck_compact_kernel, dim3(1), dim3(256), 0, fwd, fdist, bwd, nq, d_out, d_n_out);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -862,15 +859,9 @@ int launch_guided_match(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t
   int* sorted_idx = cell_start + GG_CELLS + 1;
   unsigned short* cell_of = (unsigned short*)(sorted_idx + std::max(n, 1));
   const double winv = (double)GG_COLS / (img_w - 0.0), hinv = (double)GG_ROWS / (img_h - 0.0);   // tracking_frame.rs:58-59
-  {
-    ProfScope ps(h, "grid_build_kernel");
-    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(GG_THREADS), 0, h->stream, d_kp, n, winv, hinv, cell_start, sorted_idx, cell_of);
-  }
-  {
-    ProfScope ps(h, "guided_match_kernel");
-    hipLaunchKernelGGL(guided_match_kernel, dim3((nq + 3) / 4), dim3(256), 0, h->stream, d_desc, cell_start, sorted_idx, cell_of,
-                       d_q_uv, d_q_desc, nq, radius, winv, hinv, mode, d_out_idx, d_out_dist);
-  }
+  orbx_launch(h, "grid_build_kernel", false, grid_build_kernel, dim3(1), dim3(GG_THREADS), 0, d_kp, n, winv, hinv, cell_start, sorted_idx, cell_of);
+  orbx_launch(h, "guided_match_kernel", false, guided_match_kernel, dim3((nq + 3) / 4), dim3(256), 0, d_desc, cell_start, sorted_idx, cell_of, d_q_uv, d_q_desc, nq, radius, winv,
+              hinv, mode, d_out_idx, d_out_dist);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -885,14 +876,8 @@ bool tri_grid_dims(const orbx_camera* cam, int* cols, int* rows) {
 
 int launch_search_for_triangulation_batch(orbx_handle* h, const TriBatchItem* d_items, int T, int max_n1, int max_n2) {
   if (T <= 0) return ORBX_OK;
-  {
-    ProfScope ps(h, "tri_grid_build_batch_kernel");
-    hipLaunchKernelGGL(tri_grid_build_batch_kernel, dim3(T), dim3(1024), 0, h->stream, d_items);
-  }
-  if (max_n1 > 0) {
-    ProfScope ps(h, "tri_propose_batch_kernel");
-    hipLaunchKernelGGL(tri_propose_batch_kernel, dim3((max_n1 + 3) / 4, T), dim3(256), 0, h->stream, d_items);
-  }
+  orbx_launch(h, "tri_grid_build_batch_kernel", false, tri_grid_build_batch_kernel, dim3(T), dim3(1024), 0, d_items);
+  if (max_n1 > 0) orbx_launch(h, "tri_propose_batch_kernel", false, tri_propose_batch_kernel, dim3((max_n1 + 3) / 4, T), dim3(256), 0, d_items);
   {
     ProfScope ps(h, "tri_resolve_batch_kernel");
     const size_t lds = 5 * (size_t)std::max(max_n2, 0) + 16;                // sized by the largest neighbour of the call
@@ -934,14 +919,8 @@ int launch_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, cons
   A.cols = cols; A.rows = rows; A.max_dist = max_dist; A.n1 = n1; A.n2 = n2;
   A.kp1 = d_kp1; A.desc1 = d_desc1; A.mp1 = d_mp1; A.stereo1 = d_stereo1; A.kp2 = d_kp2; A.desc2 = d_desc2;
   A.cell_start = cell_start; A.sorted_idx = sorted_idx; A.cell_of = cell_of; A.taken = taken;
-  {
-    ProfScope ps(h, "tri_grid_build_kernel");
-    hipLaunchKernelGGL(tri_grid_build_kernel, dim3(1), dim3(1024), 0, h->stream, d_kp2, n2, cols, rows, d_mp2, cell_start, sorted_idx, cell_of, taken);
-  }
-  {
-    ProfScope ps(h, "tri_propose_kernel");
-    hipLaunchKernelGGL(tri_propose_kernel, dim3((n1 + 3) / 4), dim3(256), 0, h->stream, A, prop);
-  }
+  orbx_launch(h, "tri_grid_build_kernel", false, tri_grid_build_kernel, dim3(1), dim3(1024), 0, d_kp2, n2, cols, rows, d_mp2, cell_start, sorted_idx, cell_of, taken);
+  orbx_launch(h, "tri_propose_kernel", false, tri_propose_kernel, dim3((n1 + 3) / 4), dim3(256), 0, A, prop);
   {
     ProfScope ps(h, "tri_resolve_kernel");
     const size_t lds = 5 * (size_t)n2 + 16;
@@ -962,9 +941,8 @@ int launch_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* d_p
                        int T, double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist) {
   if (P <= 0 || T <= 0) return ORBX_OK;
   if (T > 65535) return orbx_fail(h, ORBX_ERR_INVALID, "fuse search: more than 65535 target keyframes");
-  ProfScope ps(h, "fuse_search_kernel");
-  hipLaunchKernelGGL(fuse_search_kernel, dim3((P + FUSE_THREADS - 1) / FUSE_THREADS, T), dim3(FUSE_THREADS), 0, h->stream, *cam, d_positions, d_mp_desc, P,
-                     d_kf_pose_cw, d_kf_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_out_idx, d_out_dist);
+  orbx_launch(h, "fuse_search_kernel", false, fuse_search_kernel, dim3((P + FUSE_THREADS - 1) / FUSE_THREADS, T), dim3(FUSE_THREADS), 0, *cam, d_positions, d_mp_desc, P,
+              d_kf_pose_cw, d_kf_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_out_idx, d_out_dist);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -992,10 +970,7 @@ int launch_search_for_triangulation_bow(orbx_handle* h, const double* F9, const 
   A.kp1 = d_kp1; A.desc1 = d_desc1; A.mp1 = d_mp1; A.stereo1 = d_stereo1; A.kp2 = d_kp2; A.desc2 = d_desc2;
   A.cell_start = nullptr; A.sorted_idx = d_sorted_idx; A.cell_of = nullptr; A.taken = taken;
   A.rng_lo = d_rng_lo; A.rng_hi = d_rng_hi;
-  {
-    ProfScope ps(h, "tri_propose_kernel");
-    hipLaunchKernelGGL(tri_propose_kernel, dim3((n1 + 3) / 4), dim3(256), 0, h->stream, A, prop);
-  }
+  orbx_launch(h, "tri_propose_kernel", false, tri_propose_kernel, dim3((n1 + 3) / 4), dim3(256), 0, A, prop);
   {
     ProfScope ps(h, "tri_resolve_kernel");
     const size_t lds = 5 * (size_t)n2 + 16;

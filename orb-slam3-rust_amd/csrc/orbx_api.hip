@@ -237,7 +237,7 @@ void orbx_destroy(orbx_handle* h) {
   for (DevBuf& b : h->ws_tref) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_lv) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_mp) if (b.p) hipFree(b.p);
-  for (DevBuf& b : h->ws_map) if (b.p) hipFree(b.p);
+  h->ws_map.for_each([](DevBuf& b) { if (b.p) hipFree(b.p); });
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
   for (int i = 0; i < 2; ++i) { if (h->ev_in[i]) hipEventDestroy(h->ev_in[i]); if (h->ev_comp[i]) hipEventDestroy(h->ev_comp[i]); if (h->ev_out[i]) hipEventDestroy(h->ev_out[i]); }
   if (h->ba_up_event) hipEventDestroy(h->ba_up_event);

@@ -189,6 +189,34 @@ struct HostCall {
   size_t in_bytes;
 };
 
+// The resident map's grow-only workspaces (map_store_kernels.hip), one per role.  A call family reserves its own members only, so two
+// live buffers of one stream never overlap; where families share a member, the member says so.
+struct MapWorkspaces {
+  DevBuf sel_scratch;     // selection: candidates and chunk counts
+  DevBuf host_blobs;      // every host form's input / output blobs, and the window collection of the BA drivers (shared by all of them: a host form waits for its download before it returns)
+  DevBuf call_tables;     // the selection's tables, orbx_map_points_set's slots and rows, orbx_map_points_erase's slots (shared: each goes up through ring_map and is read by the launches behind it)
+  DevBuf ref_items;       // the reference-keyframe form's item table
+  DevBuf cov_scratch;     // covisibility: weights, best lists and the segments made from them
+  DevBuf cov_tables;      // covisibility: the call's keyframe table and queries
+  DevBuf win_scratch;     // BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases
+  DevBuf win_tables;      // BA-window collection: the call's keyframe table and chain
+  DevBuf obs_scratch;     // observations: counts, cursors, block sums and the unordered entries; the redundancy call's chunk sums
+  DevBuf obs_tables;      // observations: the call's keyframe table, slots and candidates
+  DevBuf refresh_lists;   // orbx_map_refresh_points: the lists and the gathered positions; orbx_map_keyframe_redundancy: the candidates' list and gathered rows (shared: neither call runs inside the other)
+  DevBuf fuse_scratch;    // fuse and merge: L's gathered rows, matches, edges, claims, per-node and per-feature scratch
+  DevBuf fuse_tables;     // fuse and merge: the call's keyframe and target tables
+  DevBuf create_tables;   // point creation: the call's tables (keyframes, free slots, the neighbour loop's)
+  DevBuf create_scratch;  // point creation: flags, last-writer cells and the neighbour loop's scratch and lists
+  DevBuf remove_tables;   // point removal: the call's keyframe table and slots, the counter
+  template <class F>
+  void for_each(F&& f) {   // every member, so that orbx_destroy frees what is added here
+    for (DevBuf* b : {&sel_scratch, &host_blobs, &call_tables, &ref_items, &cov_scratch, &cov_tables, &win_scratch, &win_tables, &obs_scratch, &obs_tables,
+                      &refresh_lists, &fuse_scratch, &fuse_tables, &create_tables, &create_scratch, &remove_tables})
+      f(*b);
+  }
+};
+static_assert(sizeof(MapWorkspaces) == 16 * sizeof(DevBuf), "MapWorkspaces::for_each lists every member");
+
 struct KernelTimer {
   std::string name;
   std::vector<hipEvent_t> ev;  // start/stop pairs of the current call
@@ -244,9 +272,9 @@ struct orbx_handle {
   DevBuf ws_mp[3];                       // map-point refresh (mappoint_kernels.hip): [0] the long points' counter and list, [1] the host forms' input / output blobs, [2] the call's keyframe table
   PinnedBuf pin_mp;                      // pinned staging of the host forms
   UploadRing ring_mp;                    // the keyframe table on its way to ws_mp[2]
-  DevBuf ws_map[16];                     // resident map points (map_store_kernels.hip): [0] candidates and chunk counts of the selection, [1] the host form's input / output blobs, [2] the call's tables (and orbx_map_points_set's rows), [3] the reference-keyframe form's item table, [4] covisibility: weights, best lists and the segments made from them, [5] covisibility: the call's keyframe table and queries, [6] BA-window collection: list offsets, gathered descriptors, chunk counts, roles and bases, [7] BA-window collection: the call's keyframe table; the host form's and orbx_map_local_ba's outputs, [8] observations: counts, cursors, block sums and the unordered entries; the redundancy call's list and chunk sums, [9] observations: the call's keyframe table, slots and candidates, [10] orbx_map_refresh_points: the lists and the gathered positions, [11] fuse and merge: L's gathered rows, matches, edges, claims, per-node and per-feature scratch, [12] fuse and merge: the call's keyframe and target tables, [13] point creation: the call's tables (keyframes, free slots, the neighbour loop's), [14] point creation: flags, last-writer cells and the neighbour loop's scratch and lists, [15] point removal: the call's keyframe table and slots, the counter
-  PinnedBuf pin_map;                     // pinned staging of orbx_map_track_frames and orbx_map_points_download
-  UploadRing ring_map;                   // the tables on their way to ws_map[2]
+  MapWorkspaces ws_map;                  // resident map points (map_store_kernels.hip)
+  PinnedBuf pin_map;                     // pinned staging of the resident map's host forms and orbx_map_points_download
+  UploadRing ring_map;                   // every resident-map call's tables on their way to its *_tables workspace
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -322,6 +350,80 @@ int orbx_ring_commit(orbx_handle* h, UploadRing& r, const DevBuf& dev, size_t by
 int orbx_host_call_begin(orbx_handle* h, PinnedBuf& pin, DevBuf& dev, size_t in_bytes, size_t out_bytes, HostCall& c);
 int orbx_host_call_upload(orbx_handle* h, const HostCall& c);
 int orbx_host_call_download(orbx_handle* h, const HostCall& c, size_t bytes);
+
+// The host tables of a device form, every piece stated once.  put(src, bytes) reserves a 256-byte aligned piece as Carve does and
+// answers its offset; with a null source or no bytes it reserves and copies nothing (the caller fills the piece in place, through
+// `host`).  begin: orbx_ring_begin for the pieces' total, then the copies into the slot; `host` and `device` are the two bases.
+// commit: orbx_ring_commit of the same bytes.  send: both.  A plan holds CAP copied pieces: one more fails begin, none is dropped.
+struct UploadPlan {
+  static constexpr int CAP = 8;
+  struct Piece { size_t off; const void* src; size_t bytes; };
+  Carve c;
+  Piece piece[CAP];
+  int n = 0;
+  uint8_t* host = nullptr;
+  uint8_t* device = nullptr;
+  size_t put(const void* src, size_t bytes) {
+    const size_t o = c.take(bytes);
+    if (src && bytes) { if (n < CAP) piece[n] = Piece{o, src, bytes}; ++n; }
+    return o;
+  }
+  int begin(orbx_handle* h, UploadRing& r, DevBuf& dev) {
+    if (n > CAP) return orbx_fail(h, ORBX_ERR_HIP, "internal: an upload plan of %d pieces holds %d", n, CAP);
+    if (int rc = orbx_ring_begin(h, r, dev, c.off, &host, &device)) return rc;
+    for (int i = 0; i < n; ++i) std::memcpy(host + piece[i].off, piece[i].src, piece[i].bytes);
+    return ORBX_OK;
+  }
+  int commit(orbx_handle* h, UploadRing& r, const DevBuf& dev) { return orbx_ring_commit(h, r, dev, c.off); }
+  int send(orbx_handle* h, UploadRing& r, DevBuf& dev) {
+    if (int rc = begin(h, r, dev)) return rc;
+    return commit(h, r, dev);
+  }
+};
+
+// The outputs of a host form, every piece stated once.  add(dst, count) reserves count elements in the blob that comes down and
+// answers the piece; keep(bytes) reserves what stays on the device, behind everything that comes down.  begin: orbx_host_call_begin
+// for in_bytes and the pieces' total; from then on dev(p) is where the launches write piece p (an address inside HostCall::dout, which
+// does not exist before the total is known).  finish: orbx_host_call_download of the added pieces, then every piece with a
+// destination is copied to it whole.  A piece added with `later` is left to copy(p, n): n <= count elements, a number the download
+// itself tells (host(p) is the pinned copy).  A plan holds CAP pieces: one more fails begin, none is dropped.
+struct OutputPlan {
+  static constexpr int CAP = 16;
+  template <class T> struct Piece { int i; };
+  struct Rec { size_t off, bytes; void* dst; bool later; };
+  Carve c;
+  size_t down = 0;
+  Rec rec[CAP];
+  int n = 0;
+  HostCall call{};
+  template <class T>
+  Piece<T> add(T* dst, size_t count, bool later = false) {
+    const size_t bytes = sizeof(T) * count, o = c.take(bytes);
+    down = c.off;
+    if (n < CAP) rec[n] = Rec{o, bytes, dst, later};
+    return Piece<T>{n++};
+  }
+  size_t keep(size_t bytes) { return c.take(bytes); }
+  int begin(orbx_handle* h, PinnedBuf& pin, DevBuf& dev, size_t in_bytes = 0) {
+    if (n > CAP) return orbx_fail(h, ORBX_ERR_HIP, "internal: an output plan of %d pieces holds %d", n, CAP);
+    return orbx_host_call_begin(h, pin, dev, in_bytes, c.off, call);
+  }
+  template <class T> T* dev(Piece<T> p) const { return (T*)(call.dout + rec[p.i].off); }
+  template <class T> const T* host(Piece<T> p) const { return (const T*)(call.ho + rec[p.i].off); }
+  int finish(orbx_handle* h) {
+    if (int rc = orbx_host_call_download(h, call, down)) return rc;
+    for (int i = 0; i < n; ++i)
+      if (rec[i].dst && rec[i].bytes && !rec[i].later) std::memcpy(rec[i].dst, call.ho + rec[i].off, rec[i].bytes);
+    return ORBX_OK;
+  }
+  template <class T>
+  int copy(orbx_handle* h, Piece<T> p, size_t count) {
+    const Rec& r = rec[p.i];
+    if (sizeof(T) * count > r.bytes) return orbx_fail(h, ORBX_ERR_HIP, "internal: %zu elements copied out of an output piece of %zu bytes", count, r.bytes);
+    if (count) std::memcpy(r.dst, call.ho + r.off, sizeof(T) * count);
+    return ORBX_OK;
+  }
+};
 // CSR offsets off[0..n]: non-null, off[0] == 0, ascending, no span above `cap`; ORBX_OK or ORBX_ERR_INVALID (the message names who, the
 // array and the `unit` counted, such as "frame").  *max_span, when given, receives the largest off[i + 1] - off[i].
 int orbx_check_offsets(orbx_handle* h, const char* who, const char* name, const char* unit, int n, const int* off, int* max_span = nullptr,
@@ -342,6 +444,13 @@ struct ProfScope {
   ProfScope(orbx_handle* h, const char* name, bool chained = false);
   ~ProfScope();
 };
+// One launch on the handle's stream inside its profiling scope.  The label is the kernel's plain name, whichever instantiation or
+// kernel pointer is launched; hipGetLastError is the caller's, once per group of launches.
+template <class Kernel, class... Args>
+inline void orbx_launch(orbx_handle* h, const char* label, bool chained, Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, const Args&... args) {
+  ProfScope ps(h, label, chained);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, h->stream, args...);
+}
 void orbx_prof_begin_call(orbx_handle* h);
 void orbx_prof_end_call(orbx_handle* h);
 

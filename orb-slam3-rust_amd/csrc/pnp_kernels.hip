@@ -445,29 +445,17 @@ int pnp_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* cf
   const float thr2 = (float)(cfg->reproj_error * cfg->reproj_error);
   const orbx_camera c = *cam;
   const orbx_pnp_config g = *cfg;
-  {
-    ProfScope ps(h, "pnp_hypothesis_kernel");
-    hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(P, (H + 63) / 64), dim3(64), 0, h->stream, c, g, max_n, d_off, d_pts3d, d_pts2d,
-                       d_priors, d_hyp, d_cnt, d_ok);
-  }
+  orbx_launch(h, "pnp_hypothesis_kernel", false, pnp_hypothesis_kernel, dim3(P, (H + 63) / 64), dim3(64), 0, c, g, max_n, d_off, d_pts3d, d_pts2d, d_priors, d_hyp, d_cnt, d_ok);
   if (max_n >= 4) {
     // one correspondence per lane while that leaves the chip short of workgroups (a single problem spreads over many CUs), four
     // per lane for large batches (a quarter of the atomics and of the LDS staging)
     const int t1 = (max_n + PNP_SCORE_THREADS - 1) / PNP_SCORE_THREADS;
     const bool wide = (long long)P * t1 >= 4LL * h->n_cu;
-    ProfScope ps(h, "pnp_score_kernel");
-    if (wide)
-      hipLaunchKernelGGL(pnp_score_kernel<4>, dim3(P, (max_n + 4 * PNP_SCORE_THREADS - 1) / (4 * PNP_SCORE_THREADS)), dim3(PNP_SCORE_THREADS), 0,
-                         h->stream, c, H, thr2, max_n, d_off, d_pts3d, d_pts2d, d_hyp, d_ok, d_cnt);
-    else
-      hipLaunchKernelGGL(pnp_score_kernel<1>, dim3(P, t1), dim3(PNP_SCORE_THREADS), 0, h->stream, c, H, thr2, max_n, d_off, d_pts3d, d_pts2d,
-                         d_hyp, d_ok, d_cnt);
+    orbx_launch(h, "pnp_score_kernel", false, wide ? pnp_score_kernel<4> : pnp_score_kernel<1>, dim3(P, wide ? (max_n + 4 * PNP_SCORE_THREADS - 1) / (4 * PNP_SCORE_THREADS) : t1),
+                dim3(PNP_SCORE_THREADS), 0, c, H, thr2, max_n, d_off, d_pts3d, d_pts2d, d_hyp, d_ok, d_cnt);
   }
-  {
-    ProfScope ps(h, "pnp_refine_kernel");
-    hipLaunchKernelGGL(pnp_refine_kernel, dim3(P), dim3(PNP_REFINE_THREADS), 0, h->stream, c, g, max_n, thr2, d_off, d_pts3d, d_pts2d,
-                       d_priors, d_hyp, d_cnt, d_ok, d_poses, d_inl, d_err, d_res);
-  }
+  orbx_launch(h, "pnp_refine_kernel", false, pnp_refine_kernel, dim3(P), dim3(PNP_REFINE_THREADS), 0, c, g, max_n, thr2, d_off, d_pts3d, d_pts2d, d_priors, d_hyp, d_cnt, d_ok,
+              d_poses, d_inl, d_err, d_res);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

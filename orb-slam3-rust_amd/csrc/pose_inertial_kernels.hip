@@ -305,8 +305,7 @@ int pi_check_config(orbx_handle* h, const orbx_pose_inertial_config* c, const ch
 }
 
 int pi_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pose_inertial_config* cfg, int P, const PiArgs& a) {
-  ProfScope ps(h, "pose_inertial_kernel");
-  hipLaunchKernelGGL(pose_inertial_kernel, dim3(P), dim3(PI_THREADS), 0, h->stream, *cam, *cfg, a);
+  orbx_launch(h, "pose_inertial_kernel", false, pose_inertial_kernel, dim3(P), dim3(PI_THREADS), 0, *cam, *cfg, a);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

@@ -161,25 +161,13 @@ int track_launch(orbx_handle* h, const orbx_camera* cam, const orbx_track_config
   A.mode = cfg->mode; A.min_corr = cfg->min_correspondences; A.min_inl = cfg->min_inliers; A.radius = cfg->radius;
   A.winv = (double)GG_COLS / (cfg->img_w - 0.0); A.hinv = (double)GG_ROWS / (cfg->img_h - 0.0);   // tracking_frame.rs:58-59
   A.inl = d_inl; A.pnp_res = d_pnp;
-  {
-    ProfScope ps(h, "track_grid_build_kernel");
-    hipLaunchKernelGGL(track_grid_build_kernel, dim3(B), dim3(GG_THREADS), 0, h->stream, A);
-  }
-  if (max_mp > 0) {
-    ProfScope ps(h, "track_search_kernel", true);
-    hipLaunchKernelGGL(track_search_kernel, dim3((max_mp + 3) / 4, B), dim3(TRK_THREADS), 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "track_gather_kernel", true);
-    hipLaunchKernelGGL(track_gather_kernel, dim3(B), dim3(TRK_THREADS), 0, h->stream, A, B);
-  }
+  orbx_launch(h, "track_grid_build_kernel", false, track_grid_build_kernel, dim3(B), dim3(GG_THREADS), 0, A);
+  if (max_mp > 0) orbx_launch(h, "track_search_kernel", true, track_search_kernel, dim3((max_mp + 3) / 4, B), dim3(TRK_THREADS), 0, A);
+  orbx_launch(h, "track_gather_kernel", true, track_gather_kernel, dim3(B), dim3(TRK_THREADS), 0, A, B);
   ORBX_HIP(h, hipGetLastError());
   if (int rc = orbx_pnp_ransac_batch_device(h, cam, pnp_cfg, B, max_mp, A.offsets, A.pts3d, A.pts2d, A.priors, A.poses_out, d_inl, d_err, d_pnp))
     return rc;
-  {
-    ProfScope ps(h, "track_finish_kernel", true);
-    hipLaunchKernelGGL(track_finish_kernel, dim3(B), dim3(TRK_THREADS), 0, h->stream, A);
-  }
+  orbx_launch(h, "track_finish_kernel", true, track_finish_kernel, dim3(B), dim3(TRK_THREADS), 0, A);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

@@ -209,24 +209,14 @@ int tref_launch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_config* p
       ProfScope ps(h, "tref_col_init");
       ORBX_HIP(h, hipMemsetAsync(A.col_best, 0xff, 8 * (size_t)B * mf, h->stream));
     }
-    ProfScope ps(h, "tref_nn_kernel", true);
-    hipLaunchKernelGGL(tref_nn_kernel, dim3((max_kf + TREF_TILE - 1) / TREF_TILE, B), dim3(TREF_THREADS), 0, h->stream, A);
+    orbx_launch(h, "tref_nn_kernel", true, tref_nn_kernel, dim3((max_kf + TREF_TILE - 1) / TREF_TILE, B), dim3(TREF_THREADS), 0, A);
   }
-  {
-    ProfScope ps(h, "tref_resolve_kernel", max_kf > 0 && mf > 0);
-    hipLaunchKernelGGL(tref_resolve_kernel, dim3(B), dim3(TREF_THREADS), 0, h->stream, A);
-  }
-  {
-    ProfScope ps(h, "tref_gather_kernel", true);
-    hipLaunchKernelGGL(tref_gather_kernel, dim3(B), dim3(TREF_THREADS), 0, h->stream, A, B);
-  }
+  orbx_launch(h, "tref_resolve_kernel", max_kf > 0 && mf > 0, tref_resolve_kernel, dim3(B), dim3(TREF_THREADS), 0, A);
+  orbx_launch(h, "tref_gather_kernel", true, tref_gather_kernel, dim3(B), dim3(TREF_THREADS), 0, A, B);
   ORBX_HIP(h, hipGetLastError());
   if (int rc = orbx_pnp_ransac_batch_device(h, cam, pnp_cfg, B, max_kf, A.offsets, A.pts3d, A.pts2d, A.priors, A.poses_out, d_inl, d_err, d_pnp))
     return rc;
-  {
-    ProfScope ps(h, "tref_finish_kernel", true);
-    hipLaunchKernelGGL(tref_finish_kernel, dim3((B + 7) / 8), dim3(64), 0, h->stream, A, B);
-  }
+  orbx_launch(h, "tref_finish_kernel", true, tref_finish_kernel, dim3((B + 7) / 8), dim3(64), 0, A, B);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
@@ -249,13 +239,10 @@ int track_reference_enqueue(orbx_handle* h, const char* who, const orbx_camera* 
   ORBX_HIP(h, hipSetDevice(h->device));
   // the item table (and host-side positions / valid) go up through the upload ring, so that the caller's arrays are free when the
   // call returns
-  Carve up;
-  const size_t o_it = up.take(sizeof(TrackRefItem) * (size_t)B), o_pos = up.take(pos_on_host ? 24 * K : 0), o_val = up.take(pos_on_host ? K : 0);
-  uint8_t *hs, *ds;
-  if (int rc = orbx_ring_begin(h, h->ring_tref, h->ws_tref[2], up.off, &hs, &ds)) return rc;
-  std::memcpy(hs + o_it, items, sizeof(TrackRefItem) * (size_t)B);
-  if (pos_on_host && K) { std::memcpy(hs + o_pos, positions, 24 * K); std::memcpy(hs + o_val, valid, K); }
-  if (int rc = orbx_ring_commit(h, h->ring_tref, h->ws_tref[2], up.off)) return rc;
+  UploadPlan up;
+  const size_t o_it = up.put(items, sizeof(TrackRefItem) * (size_t)B), o_pos = up.put(positions, pos_on_host ? 24 * K : 0), o_val = up.put(valid, pos_on_host ? K : 0);
+  if (int rc = up.send(h, h->ring_tref, h->ws_tref[2])) return rc;
+  uint8_t* const ds = up.device;
   TrefArgs A{};
   A.min_corr = min_correspondences; A.max_feat = max_feat; A.fc_stride = feat_count_stride;
   A.kp = d_kp; A.desc = d_desc; A.feat_start = d_feat_start; A.feat_count = d_feat_count;

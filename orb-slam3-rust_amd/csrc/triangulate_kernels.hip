@@ -213,17 +213,14 @@ void tri_common_fill(TriCommon* c, const orbx_camera* cam, const orbx_triangulat
 int launch_triangulate_pairs(orbx_handle* h, const TriCommon& c, const TriNeighbour& one, const TriNeighbour* d_many, int T, int max_pairs,
                              uint16_t* d_status, double* d_points) {
   if (T <= 0 || max_pairs <= 0) return ORBX_OK;
-  ProfScope ps(h, "tri_triangulate_kernel");
-  hipLaunchKernelGGL(tri_triangulate_kernel, dim3((max_pairs + 255) / 256, T), dim3(256), 0, h->stream, c, one, d_many, d_status, d_points);
+  orbx_launch(h, "tri_triangulate_kernel", false, tri_triangulate_kernel, dim3((max_pairs + 255) / 256, T), dim3(256), 0, c, one, d_many, d_status, d_points);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }
 
 int launch_triangulate_compact(orbx_handle* h, const TriNeighbour* d_many, int T, const uint16_t* d_status, const double* d_points, int cap,
                                int* d_head, int* d_out_nb, int* d_out_idx1, int* d_out_idx2, double* d_out_points) {
-  ProfScope ps(h, "tri_compact_kernel");
-  hipLaunchKernelGGL(tri_compact_kernel, dim3(1), dim3(1024), 0, h->stream, d_many, T, d_status, d_points, cap, d_head, d_out_nb, d_out_idx1,
-                     d_out_idx2, d_out_points);
+  orbx_launch(h, "tri_compact_kernel", false, tri_compact_kernel, dim3(1), dim3(1024), 0, d_many, T, d_status, d_points, cap, d_head, d_out_nb, d_out_idx1, d_out_idx2, d_out_points);
   ORBX_HIP(h, hipGetLastError());
   return ORBX_OK;
 }

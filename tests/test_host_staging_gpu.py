@@ -6,7 +6,8 @@ positions / valid) into one of two pinned slots before it returns, so the caller
 enqueued back to back on a fresh handle with nothing synchronised in between, each table overwritten as soon as its call has returned
 (call 2's table is the largest, call 3 takes slot 0 again); every output must equal, byte for byte, the same call made alone on
 another fresh handle.  The overwriting values are wrong but in range (offsets of zero, no node, no valid row): a library that read a
-table late would give other bytes, not read out of bounds.
+table late would give other bytes, not read out of bounds.  The resident map's ring carries the tables of every orbx_map_* device
+form: three different forms share it in test_ring_map_device_forms.
 
 Staging growth: a host form's pinned buffer and workspace grow between a small, a large and a small call; each result equals the
 device form's on the same data.
@@ -213,6 +214,78 @@ def test_ring_verify_loop_candidates_device_feature_vector(pkg, cam):
     for k, ((got, _), (want, per_pair)) in enumerate(zip(together, alone)):
         assert all(len(p["matches"]) >= 15 and len(p["feature_matches"]) >= 15 for p in per_pair), k      # matched by node, and Sim3 ran
         assert got == want, k
+
+
+def _map_world(pkg, h):
+    """a store of capacity 64 with 48 live points and four keyframes of 8-16 features whose slot tables name live slots, dead slots,
+    -1 and repeats; made before the calls (set_map_point_slots waits for its copy)"""
+    import torch
+    rng = np.random.default_rng(231)
+    mp = pkg.MapPointStore(h, 64)
+    live = np.sort(rng.choice(64, 48, replace=False)).astype(np.int32)
+    mp.set(live, rng.normal(0.0, 2.0, (48, 3)), rng.integers(0, 256, (48, 32), dtype=np.uint8))
+    kfs = []
+    for n in (8, 11, 14, 16):
+        kfs.append(pkg.KeyFrame(h, torch.zeros((n, 7), dtype=torch.float32, device="cuda"), torch.zeros((n, 32), dtype=torch.uint8, device="cuda"), n))
+        kfs[-1].set_map_point_slots(mp, rng.integers(-1, 64, n).astype(np.int32))
+    return mp, kfs, live, _d(rng.integers(0, 64, 12).astype(np.int32))
+
+
+def test_ring_map_device_forms(pkg, cam):
+    """The resident map's ring (every orbx_map_* device form's tables go through it): covisibility (host table: queries), observations
+    (slots, the largest table) and the slot-source selection (src_offsets), back to back with nothing synchronised in between."""
+    def tables(live):
+        return [("cov", np.array([2, 0], np.int32)), ("obs", live[::-1][:40].copy()), ("sel", np.array([0, 5, 12], np.int32))]
+
+    def enqueue(h, world, kind, t):
+        mp, kfs, _, d_src = world
+        assert t.dtype == np.int32 and t.ndim == 1 and t.flags["C_CONTIGUOUS"]              # the wrapper hands the library this memory
+        if kind == "cov":
+            return h.map_covisibility_device(mp, kfs, t, n_best=2)
+        if kind == "obs":
+            return h.map_observations_device(mp, kfs, t)
+        return h.map_select_points_device(mp, src_slots=d_src, src_offsets=t)
+
+    def spoil(kind, t):                                                                      # wrong, and what the call accepts
+        assert t.flags["WRITEABLE"]
+        t[...] = {"cov": (t + 1) % 4, "obs": np.roll(t, 1), "sel": np.zeros_like(t)}[kind]
+
+    def finish(kind, o):
+        r = {k: v.cpu().numpy() for k, v in o.items()}
+        if kind == "cov":
+            assert int(r["weights"].sum()) > 0 and int(r["n_best"].min()) > 0
+            return [r[k].tobytes() for k in ("weights", "best", "n_best")]
+        if kind == "obs":
+            n = int(r["obs_start"][-1])
+            assert n > 20
+            return [r["obs_start"].tobytes(), r["obs_kf"][:n].tobytes(), r["obs_feat"][:n].tobytes()]
+        n = int(r["list_offsets"][-1])
+        assert 0 < n < 12 and int(r["list_offsets"][1]) > 0                                  # some entries are dead, both frames have a list
+        return [r["list_offsets"].tobytes()] + [r[k][:n].tobytes() for k in ("list_slot", "positions", "mp_desc")]
+
+    def run(which):
+        h = _fresh(pkg, cam)
+        try:
+            world = _map_world(pkg, h)
+            h.synchronize()
+            outs = []
+            for kind, t in tables(world[2]):
+                if which in (None, kind):
+                    outs.append((kind, enqueue(h, world, kind, t)))
+                    spoil(kind, t)
+            h.synchronize()
+            res = [finish(kind, o) for kind, o in outs]
+            for k in world[1]:
+                k.close()
+            world[0].close()
+            return res
+        finally:
+            h.close()
+
+    together = run(None)
+    assert len(together) == 3
+    for k, kind in enumerate(("cov", "obs", "sel")):
+        assert together[k] == run(kind)[0], kind
 
 
 # ---- staging growth -----------------------------------------------------------------------------------------------------
