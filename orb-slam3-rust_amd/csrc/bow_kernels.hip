@@ -358,19 +358,19 @@ int orbx_bow_transform(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* 
       return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_transform: bad argument");
     if (n == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    if (int rc = orbx_reserve(h, h->ws_io[0], 32 * (size_t)n)) return rc;
-    if (int rc = orbx_reserve(h, h->ws_io[1], (12 + 8) * (size_t)n)) return rc;
-    uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
-    double* d_w = (double*)h->ws_io[1].p;
-    uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
-    ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
-    ORBX_HIP(h, hipMemcpyAsync(out_word, d_word, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(out_leaf, d_leaf, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(out_node, d_node, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(out_weight, d_w, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    return ORBX_OK;
+    const size_t nn = (size_t)n;
+    Carve in;
+    const size_t i_de = in.take(32 * nn);
+    OutputPlan out;
+    const auto p_we = out.add(out_weight, nn);
+    const auto p_wo = out.add(out_word, nn);
+    const auto p_le = out.add(out_leaf, nn);
+    const auto p_no = out.add(out_node, nn);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    memcpy(out.call.hi + i_de, desc, 32 * nn);
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = orbx_bow_transform_device(h, v, out.call.di + i_de, n, levels_up, out.dev(p_wo), out.dev(p_le), out.dev(p_no), out.dev(p_we))) return rc;
+    return out.finish(h);
   });
 }
 
@@ -383,8 +383,8 @@ int orbx_bow_vectors_device(orbx_handle* h, const orbx_vocabulary* v, const uint
     if (n > BOWV_MAX) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_bow_vectors: at most %d descriptors per call", BOWV_MAX);
     ORBX_HIP(h, hipSetDevice(h->device));
     if (n == 0) { ORBX_HIP(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), h->stream)); return ORBX_OK; }
-    if (int rc = orbx_reserve(h, h->ws_io[9], (12 + 8) * (size_t)n)) return rc;
-    double* d_w = (double*)h->ws_io[9].p;
+    if (int rc = orbx_reserve(h, h->ws_io.bow_scratch, (12 + 8) * (size_t)n)) return rc;
+    double* d_w = (double*)h->ws_io.bow_scratch.p;
     uint32_t* d_word = (uint32_t*)(d_w + n); uint32_t* d_leaf = d_word + n; uint32_t* d_node = d_leaf + n;
     if (int rc = orbx_bow_transform_device(h, v, d_desc, n, levels_up, d_word, d_leaf, d_node, d_w)) return rc;
     orbx_launch(h, "bow_vectors_kernel", false, bow_vectors_kernel, dim3(1), dim3(BOWV_THREADS), 0, d_word, d_node, d_w, n, d_bow_word, d_bow_weight, d_fv_node, d_fv_start,
@@ -404,23 +404,26 @@ int orbx_bow_vectors(orbx_handle* h, const orbx_vocabulary* v, const uint8_t* de
     if (n == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
     const size_t nn = (size_t)n;
-    if (int rc = orbx_reserve(h, h->ws_io[0], 32 * nn)) return rc;
-    if (int rc = orbx_reserve(h, h->ws_io[1], 8 * nn + 4 * nn + 4 * nn + 4 * (nn + 1) + 4 * nn + 64)) return rc;
-    uint8_t* d_desc = (uint8_t*)h->ws_io[0].p;
-    double* d_bw = (double*)h->ws_io[1].p;
-    uint32_t* d_bword = (uint32_t*)(d_bw + n); uint32_t* d_fnode = d_bword + n;
-    int* d_fstart = (int*)(d_fnode + n); int* d_findex = d_fstart + n + 1; int* d_counts = d_findex + n;
-    ORBX_HIP(h, hipMemcpyAsync(d_desc, desc, 32 * nn, hipMemcpyHostToDevice, h->stream));
-    if (int rc = orbx_bow_vectors_device(h, v, d_desc, n, levels_up, d_bword, d_bw, d_fnode, d_fstart, d_findex, d_counts)) return rc;
-    int cnt[2];
-    ORBX_HIP(h, hipMemcpyAsync(cnt, d_counts, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    *n_bow = cnt[0]; *n_fv = cnt[1];
-    ORBX_HIP(h, hipMemcpy(bow_word, d_bword, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
-    ORBX_HIP(h, hipMemcpy(bow_weight, d_bw, 8 * (size_t)cnt[0], hipMemcpyDeviceToHost));
-    ORBX_HIP(h, hipMemcpy(fv_node, d_fnode, 4 * (size_t)cnt[1], hipMemcpyDeviceToHost));
-    ORBX_HIP(h, hipMemcpy(fv_start, d_fstart, 4 * ((size_t)cnt[1] + 1), hipMemcpyDeviceToHost));
-    ORBX_HIP(h, hipMemcpy(fv_index, d_findex, 4 * nn, hipMemcpyDeviceToHost));
+    Carve in;
+    const size_t i_de = in.take(32 * nn);
+    OutputPlan out;
+    const auto p_cn = out.add((int*)nullptr, 2);                          // n_bow, n_fv
+    const auto p_bw = out.add(bow_weight, nn, true);
+    const auto p_bo = out.add(bow_word, nn, true);
+    const auto p_fn = out.add(fv_node, nn, true);
+    const auto p_fs = out.add(fv_start, nn + 1, true);
+    const auto p_fi = out.add(fv_index, nn);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    memcpy(out.call.hi + i_de, desc, 32 * nn);
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = orbx_bow_vectors_device(h, v, out.call.di + i_de, n, levels_up, out.dev(p_bo), out.dev(p_bw), out.dev(p_fn), out.dev(p_fs), out.dev(p_fi),
+                                         out.dev(p_cn)))
+      return rc;
+    if (int rc = out.finish(h)) return rc;
+    const size_t nb = (size_t)out.host(p_cn)[0], nf = (size_t)out.host(p_cn)[1];
+    *n_bow = (int)nb; *n_fv = (int)nf;
+    for (int rc : {out.copy(h, p_bo, nb), out.copy(h, p_bw, nb), out.copy(h, p_fn, nf), out.copy(h, p_fs, nf + 1)})
+      if (rc) return rc;
     return ORBX_OK;
   });
 }

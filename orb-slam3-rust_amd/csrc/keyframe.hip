@@ -70,16 +70,7 @@ void tri_nb_fill(const TriNbPlan& P, const orbx_camera* cam, const orbx_triangul
       it.A.rng_lo = (const int*)(d_up + s.lo); it.A.rng_hi = (const int*)(d_up + s.hi);
       int* sorted = (int*)(up + s.sorted); int* lo = (int*)(up + s.lo); int* hi = (int*)(up + s.hi);
       if (kf->n > 0) memcpy(sorted, kf->node_sorted.data(), 4 * (size_t)kf->n);
-      const uint32_t* node2 = kf->node.data();
-      const int* sb = kf->node_sorted.data(); const int* se = sb + kf->node_m;
-      for (int i = 0; i < n1; ++i) {                                                       // the features of keyframe 2 in feature i's node (:577-581)
-        lo[i] = hi[i] = 0;
-        const uint32_t key = cur->node[(size_t)i];
-        if (key == 0xffffffffu) continue;
-        const int* b = std::lower_bound(sb, se, key, [&](int a, uint32_t kk) { return node2[a] < kk; });
-        const int* e = std::upper_bound(b, se, key, [&](uint32_t kk, int a) { return kk < node2[a]; });
-        lo[i] = (int)(b - sb); hi[i] = (int)(e - sb);
-      }
+      orbx_node_ranges(cur->node.data(), n1, kf->node.data(), kf->node_sorted.data(), kf->node_m, lo, hi);   // the features of keyframe 2 in feature i's node (:577-581)
     } else {
       it.A.cell_start = (const int*)(d_ws + s.cell_start); it.A.cell_of = (const unsigned short*)(d_ws + s.cell_of);
     }
@@ -217,18 +208,20 @@ int orbx_keyframe_guided_match(orbx_handle* h, const orbx_keyframe* kf, double i
     if (nq == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
     // only the queries travel (48 B each up, 8 B each down); the frame's n x 60 B of features stay where they are
-    if (int rc = orbx_reserve(h, h->ws_io[8], 16 * (size_t)nq + 32 * (size_t)nq + 8 * (size_t)nq)) return rc;
-    double* d_uv = (double*)h->ws_io[8].p;
-    uint8_t* d_qd = (uint8_t*)(d_uv + 2 * (size_t)nq);
-    int* d_idx = (int*)(d_qd + 32 * (size_t)nq);
-    uint32_t* d_dist = (uint32_t*)(d_idx + nq);
-    ORBX_HIP(h, hipMemcpyAsync(d_uv, q_uv, 16 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(d_qd, q_desc, 32 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-    if (int rc = orbx_guided_match_device(h, kf->d_kp, kf->d_desc, kf->n, img_w, img_h, d_uv, d_qd, nq, radius, mode, d_idx, d_dist)) return rc;
-    ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    return ORBX_OK;
+    const size_t NQ = (size_t)nq;
+    Carve in;
+    const size_t i_uv = in.take(16 * NQ), i_qd = in.take(32 * NQ);
+    OutputPlan out;
+    const auto p_idx = out.add(out_idx, NQ);
+    const auto p_dist = out.add(out_dist, NQ);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    memcpy(out.call.hi + i_uv, q_uv, 16 * NQ);
+    memcpy(out.call.hi + i_qd, q_desc, 32 * NQ);
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = orbx_guided_match_device(h, kf->d_kp, kf->d_desc, kf->n, img_w, img_h, (const double*)(out.call.di + i_uv), out.call.di + i_qd, nq, radius, mode,
+                                          out.dev(p_idx), out.dev(p_dist)))
+      return rc;
+    return out.finish(h);
   });
 }
 
@@ -241,17 +234,16 @@ int orbx_keyframe_search_for_triangulation(orbx_handle* h, const orbx_camera* ca
     *n_out = 0;
     if (kf1->n == 0 || kf2->n == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(int) * (2 * (size_t)kf1->n + 4))) return rc;
-    int* d_pairs = (int*)h->ws_io[8].p;
-    int* d_n = d_pairs + 2 * (size_t)kf1->n;
+    OutputPlan out;                                                       // nothing goes up: the count and the pairs come down
+    const auto p_n = out.add(n_out, 1);
+    const auto p_pr = out.add(out_pairs, 2 * (size_t)kf1->n, true);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob)) return rc;
     // map_point_ids[i].is_some() = the keyframe's map-point flags, points_cam[i].is_some() = its stereo flags (triangulation.rs:401-527)
     if (int rc = orbx_search_for_triangulation_device(h, cam, kf1->d_kp, kf1->d_desc, kf1->d_mp_flag, kf1->d_has_point, kf1->n, kf2->d_kp,
-                                                      kf2->d_desc, kf2->d_mp_flag, kf2->n, kf1->pose_wc, kf2->pose_wc, max_dist, d_pairs, d_n))
+                                                      kf2->d_desc, kf2->d_mp_flag, kf2->n, kf1->pose_wc, kf2->pose_wc, max_dist, out.dev(p_pr), out.dev(p_n)))
       return rc;
-    ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    ORBX_HIP(h, hipStreamSynchronize(h->stream));
-    if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
-    return ORBX_OK;
+    if (int rc = out.finish(h)) return rc;
+    return out.copy(h, p_pr, 2 * (size_t)*n_out);
   });
 }
 
@@ -263,11 +255,7 @@ int orbx_keyframe_set_feature_nodes(orbx_keyframe* kf, const uint32_t* node) {
     const int n = kf->n;
     kf->node.assign(node, node + n);
     kf->node_sorted.resize((size_t)n);
-    for (int i = 0; i < n; ++i) kf->node_sorted[(size_t)i] = i;
-    std::stable_sort(kf->node_sorted.begin(), kf->node_sorted.end(), [&](int a, int b) { return node[a] < node[b]; });
-    int m = n;
-    while (m > 0 && node[kf->node_sorted[(size_t)m - 1]] == 0xffffffffu) --m;
-    kf->node_m = m;
+    kf->node_m = orbx_sort_by_node(node, n, kf->node_sorted.data());
     kf->has_nodes = true;
     return ORBX_OK;
   });
@@ -293,46 +281,39 @@ int orbx_keyframe_triangulate_from_neighbors(orbx_handle* h, const orbx_camera* 
     const int Ts = (int)P.orig.size();
     if (Ts == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    // ---- the one workspace: [uploaded: items | neighbours | FeatureVector tables] [scratch | status | points] [result blob]
-    const size_t slots = (size_t)Ts * (size_t)P.n1;
-    const size_t capd = std::min((size_t)cap, slots);
-    const size_t o_res = P.up_bytes + P.ws_bytes, r_head = 0, r_pts = (4 * (1 + 4 * (size_t)Ts) + 15) & ~(size_t)15, r_nb = r_pts + 24 * capd,
-                 r_i1 = r_nb + 4 * capd, r_i2 = r_i1 + 4 * capd, res_bytes = r_i2 + 4 * capd;
-    if (int rc = orbx_reserve(h, h->ws_io[10], o_res + res_bytes)) return rc;
-    uint8_t* d = (uint8_t*)h->ws_io[10].p;
-    std::vector<uint8_t> up(P.up_bytes), down(res_bytes);
+    // ---- up: items | neighbours | FeatureVector tables; down: head | the lists; the scratch stays in its own workspace
+    const size_t Tz = (size_t)Ts, capd = std::min((size_t)cap, Tz * (size_t)P.n1);
+    Carve in;
+    in.take(P.up_bytes);
+    OutputPlan out;
+    const auto p_head = out.add((int*)nullptr, 1 + 4 * Tz);
+    const auto p_nb = out.add((int*)nullptr, capd);
+    const auto p_pts = out.add(out_points, 3 * capd, true);
+    const auto p_i1 = out.add(out_idx1, capd, true);
+    const auto p_i2 = out.add(out_idx2, capd, true);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    if (int rc = orbx_reserve(h, h->ws_io.nb_scratch, P.ws_bytes)) return rc;
+    uint8_t* d_ws = (uint8_t*)h->ws_io.nb_scratch.p;
     std::vector<const uint8_t*> mp2((size_t)T);
     for (int t = 0; t < T; ++t) mp2[(size_t)t] = kfs[t]->d_mp_flag;
     // map_point_ids[i].is_some() = the keyframes' map-point flags (triangulation.rs:94-107, :401-527)
-    tri_nb_fill(P, cam, cfg, cur, kfs, cur->d_mp_flag, mp2.data(), up.data(), d, d + P.up_bytes);
-    // ---- one upload, the launches, one download, one synchronisation
-    hipStream_t st = h->stream;
-    hipError_t e = hipMemcpyAsync(d, up.data(), P.up_bytes, hipMemcpyHostToDevice, st);
-    int rc = ORBX_OK;
-    if (e == hipSuccess) {
-      orbx_prof_begin_call(h);
-      rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, d, d + P.up_bytes, (int)capd, (int*)(d + o_res + r_head), (int*)(d + o_res + r_nb), (int*)(d + o_res + r_i1),
-                         (int*)(d + o_res + r_i2), (double*)(d + o_res + r_pts));
-      if (!rc) e = hipMemcpyAsync(down.data(), d + o_res, res_bytes, hipMemcpyDeviceToHost, st);
-    }
-    const hipError_t es = hipStreamSynchronize(st);                       // also on the error paths: `up` / `down` are locals
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess)
-      return orbx_fail(h, ORBX_ERR_HIP, "orbx_keyframe_triangulate_from_neighbors: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    const int* head = (const int*)(down.data() + r_head);
+    tri_nb_fill(P, cam, cfg, cur, kfs, cur->d_mp_flag, mp2.data(), out.call.hi, out.call.di, d_ws);
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = tri_nb_launch(h, P, cam, cfg, is_inertial, cur, out.call.di, d_ws, (int)capd, out.dev(p_head), out.dev(p_nb), out.dev(p_i1), out.dev(p_i2),
+                               out.dev(p_pts)))
+      return rc;
+    if (int rc = out.finish(h)) return rc;
+    const int* head = out.host(p_head);
     for (int k = 0; k < Ts; ++k) {
       int* s4 = stats + 4 * (size_t)P.orig[(size_t)k];
       s4[0] = 1; s4[1] = head[2 + 4 * k]; s4[2] = head[3 + 4 * k]; s4[3] = head[4 + 4 * k];
     }
     *n_out = head[0];
     const size_t nw = std::min((size_t)head[0], capd);
-    const int* nb_k = (const int*)(down.data() + r_nb);
+    const int* nb_k = out.host(p_nb);
     for (size_t i = 0; i < nw; ++i) out_neighbour[i] = P.orig[(size_t)nb_k[i]];
-    if (nw > 0) {
-      memcpy(out_idx1, down.data() + r_i1, 4 * nw);
-      memcpy(out_idx2, down.data() + r_i2, 4 * nw);
-      memcpy(out_points, down.data() + r_pts, 24 * nw);
-    }
+    for (int rc : {out.copy(h, p_i1, nw), out.copy(h, p_i2, nw), out.copy(h, p_pts, 3 * nw)})
+      if (rc) return rc;
     return ORBX_OK;
   });
 }
@@ -376,40 +357,44 @@ int orbx_keyframe_fuse_search(orbx_handle* h, const orbx_camera* cam, const doub
     if (!cam || P < 0 || T < 0 || (P > 0 && (!positions || !mp_desc)) || (T > 0 && !kfs) || (P > 0 && T > 0 && (!out_idx || !out_dist)))
       return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: bad argument");
     if (P == 0 || T == 0) return ORBX_OK;
-    std::vector<int> off((size_t)T + 1, 0);
     std::vector<double> poses(7 * (size_t)T);
+    size_t n = 0;
     for (int t = 0; t < T; ++t) {
       if (!kfs[t] || kfs[t]->h != h) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_keyframe_fuse_search: keyframe %d is null or of another handle", t);
-      off[(size_t)t + 1] = off[(size_t)t] + kfs[t]->n;
+      n += (size_t)kfs[t]->n;
       memcpy(&poses[7 * (size_t)t], kfs[t]->pose_wc, 56);
     }
     ORBX_HIP(h, hipSetDevice(h->device));
-    const size_t n = (size_t)std::max(off[(size_t)T], 1), pt = (size_t)P * T;
-    // the target keyframes' features side by side (device-to-device, no host hop), the map points and the result block
-    if (int rc = orbx_reserve(h, h->ws_io[8], sizeof(orbx_keypoint) * n + 32 * n + 32 * (size_t)P + 24 * (size_t)P + 4 * ((size_t)T + 1) + 8 * pt + 64)) return rc;
-    uint8_t* b = (uint8_t*)h->ws_io[8].p;
-    double* d_pos = (double*)b; b += 24 * (size_t)P;
-    int* d_idx = (int*)b; b += 4 * pt; uint32_t* d_dist = (uint32_t*)b; b += 4 * pt;
-    orbx_keypoint* d_kps = (orbx_keypoint*)b; b += sizeof(orbx_keypoint) * n;
-    uint8_t* d_descs = b; b += 32 * n;
-    uint8_t* d_mpd = b; b += 32 * (size_t)P;
-    int* d_off = (int*)b;
+    const size_t N = std::max(n, (size_t)1), Pz = (size_t)P, pt = Pz * (size_t)T;
+    // the map points and the offsets travel in the blob; the target keyframes' features go side by side, device to device
+    Carve in, side;
+    const size_t i_pos = in.take(24 * Pz), i_md = in.take(32 * Pz), i_off = in.take(4 * ((size_t)T + 1));
+    const size_t g_kps = side.take(sizeof(orbx_keypoint) * N), g_ds = side.take(32 * N);
+    OutputPlan out;
+    const auto p_idx = out.add(out_idx, pt);
+    const auto p_dist = out.add(out_dist, pt);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    if (int rc = orbx_reserve(h, h->ws_io.kf_gather, side.off)) return rc;
+    uint8_t *hi = out.call.hi, *di = out.call.di;
+    orbx_keypoint* d_kps = (orbx_keypoint*)((uint8_t*)h->ws_io.kf_gather.p + g_kps);
+    uint8_t* d_descs = (uint8_t*)h->ws_io.kf_gather.p + g_ds;
+    int* off = (int*)(hi + i_off);
+    off[0] = 0;
     hipStream_t st = h->stream;
-    for (int t = 0; t < T; ++t)
+    for (int t = 0; t < T; ++t) {
+      off[t + 1] = off[t] + kfs[t]->n;
       if (kfs[t]->n > 0) {
-        ORBX_HIP(h, hipMemcpyAsync(d_kps + off[(size_t)t], kfs[t]->d_kp, sizeof(orbx_keypoint) * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
-        ORBX_HIP(h, hipMemcpyAsync(d_descs + 32 * (size_t)off[(size_t)t], kfs[t]->d_desc, 32 * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
+        ORBX_HIP(h, hipMemcpyAsync(d_kps + off[t], kfs[t]->d_kp, sizeof(orbx_keypoint) * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
+        ORBX_HIP(h, hipMemcpyAsync(d_descs + 32 * (size_t)off[t], kfs[t]->d_desc, 32 * (size_t)kfs[t]->n, hipMemcpyDeviceToDevice, st));
       }
-    ORBX_HIP(h, hipMemcpyAsync(d_pos, positions, 24 * (size_t)P, hipMemcpyHostToDevice, st));
-    ORBX_HIP(h, hipMemcpyAsync(d_mpd, mp_desc, 32 * (size_t)P, hipMemcpyHostToDevice, st));
-    ORBX_HIP(h, hipMemcpyAsync(d_off, off.data(), 4 * ((size_t)T + 1), hipMemcpyHostToDevice, st));
-    ORBX_HIP(h, hipStreamSynchronize(st));                               // `off` is a local
-    if (int rc = orbx_fuse_search_device(h, cam, d_pos, d_mpd, P, poses.data(), d_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_idx, d_dist))
+    }
+    memcpy(hi + i_pos, positions, 24 * Pz);
+    memcpy(hi + i_md, mp_desc, 32 * Pz);
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = orbx_fuse_search_device(h, cam, (const double*)(di + i_pos), di + i_md, P, poses.data(), (const int*)(di + i_off), d_kps, d_descs, T, radius_scale,
+                                         desc_threshold, out.dev(p_idx), out.dev(p_dist)))
       return rc;
-    ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * pt, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * pt, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(h, hipStreamSynchronize(st));
-    return ORBX_OK;
+    return out.finish(h);
   });
 }
 

@@ -729,7 +729,6 @@ int loop_verify_enqueue(orbx_handle* h, const char* who, const orbx_camera* cam,
   S.cfg = cfg->sim3; S.max_n = max_n1; S.stride = LV_PRE; S.start = A.pre + 3; S.count = A.pre + 4;
   S.pts1 = d_pts_current; S.pts2 = d_pts_loop; S.sim3 = d_sim3; S.inl = d_inlier; S.results = (orbx_sim3_result*)(w + o_sres);
   A.model = (const double*)(w + o_s3 + s3.model);
-  orbx_prof_begin_call(h);
   const dim3 match_grid((max_n1 + LV_TILE - 1) / LV_TILE, B);
   if (any_bf && max_n1 > 0) orbx_launch(h, "lv_match_kernel", false, lv_match_kernel<false>, match_grid, dim3(LV_THREADS), 0, A);
   if (any_fv && max_n1 > 0) orbx_launch(h, "lv_match_kernel_fv", any_bf, lv_match_kernel<true>, match_grid, dim3(LV_THREADS), 0, A);
@@ -782,7 +781,6 @@ int orbx_sim3_ransac_batch_device(orbx_handle* h, const orbx_sim3_config* cfg, i
     S3Args S{};
     S.cfg = *cfg; S.max_n = max_n; S.stride = 1; S.start = d_offsets; S.count = nullptr;
     S.pts1 = d_pts1; S.pts2 = d_pts2; S.sim3 = d_sim3; S.inl = d_inlier; S.results = d_results;
-    orbx_prof_begin_call(h);
     return s3_launch(h, S, n_problems, (uint8_t*)h->ws_lv[0].p);
   });
 }

@@ -931,17 +931,6 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
   return ORBX_OK;
 }
 
-// se3.rs:56-63 with nalgebra's quaternion-vector product, one IEEE operation at a time (include/orbx.hpp's se3_inverse; what
-// orbx_fuse_search_device's quat_rotate makes of it, orbx_api.hip)
-void ms_pose_inverse(const double* p, double* out) {
-  const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
-  const double* v = p + 4;
-  const double t[3] = {2.0 * (y * v[2] - z * v[1]), 2.0 * (z * v[0] - x * v[2]), 2.0 * (x * v[1] - y * v[0])};
-  const double c[3] = {y * t[2] - z * t[1], z * t[0] - x * t[2], x * t[1] - y * t[0]};
-  out[0] = w; out[1] = x; out[2] = y; out[3] = z;
-  for (int i = 0; i < 3; ++i) out[4 + i] = -(t[i] * w + c[i] + v[i]);
-}
-
 // a window without a point to optimise: M == 0, and for the covisible window N == 0 (local_inertial_ba.rs:946-948)
 int win_check_empty(orbx_handle* h, const char* who, const WinPlan& P, const int* counts) {
   if (P.kind == WIN_CHAIN) return counts[2] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);
@@ -1005,7 +994,6 @@ int win_local_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const 
                  double* poses_wc_out, int* counts_out, int* iterations, double* initial_error, double* final_error) {
   const bool chain = P.kind == WIN_CHAIN;
   *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
-  orbx_prof_begin_call(h);
   WinDown w;
   if (int rc = win_collect_down(h, who, mp, P, true, w)) return rc;
   const int* cn = (const int*)(w.hp + w.o_cn);
@@ -1021,10 +1009,10 @@ int win_local_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const 
   std::vector<int> slots((const int*)(w.hp + w.o_ls), (const int*)(w.hp + w.o_ls) + M);
   for (int i = 0; i < Kw; ++i) {
     if (chain) std::memcpy(&poses[7 * (size_t)i], kfs[local[i]]->pose_wc, 56);
-    else ms_pose_inverse(kfs[local[1 + i]]->pose_wc, &poses[7 * (size_t)i]);
+    else orbx_pose_inverse(kfs[local[1 + i]]->pose_wc, &poses[7 * (size_t)i]);
   }
-  ms_pose_inverse(kfs[local[0]]->pose_wc, &fixed_cw[0]);
-  for (int j = 0; j + 1 < F; ++j) ms_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
+  orbx_pose_inverse(kfs[local[0]]->pose_wc, &fixed_cw[0]);
+  for (int j = 0; j + 1 < F; ++j) orbx_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
   if (int rc = ba_solve_visual(h, cam, cfg, Kw, poses.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
                                initial_error, final_error, false, in, (const orbx_ba_obs32*)(w.d + w.o_ob), true))
     return rc;
@@ -1053,7 +1041,6 @@ int ms_track_device(orbx_handle* h, const char* who, const orbx_camera* cam, con
       !D.d_poses_wc_out || !D.d_pnp_results || !D.d_results || (D.max_feat > 0 && (!D.d_kp || !D.d_desc || !D.d_matched || !D.d_matched_slot)) ||
       (M > 0 && (!D.d_pts3d || !D.d_pts2d || !D.d_mp_idx || !D.d_feat_idx || !D.d_inlier_out || !D.d_err_out)))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
-  orbx_prof_begin_call(h);
   if (int rc = select()) return rc;
   TrackArgs A{};
   A.max_feat = D.max_feat; A.fc_stride = D.feat_count_stride;
@@ -1122,7 +1109,6 @@ int ms_track_host(orbx_handle* h, const char* who, const orbx_camera* cam, const
   }
   if (S) std::memcpy(hi + i_ss, H.src_slots, 4 * S);
   if (int rc = orbx_host_call_upload(h, c)) return rc;
-  orbx_prof_begin_call(h);
   int* d_lo = out.dev(p_lo); int* d_ls = out.dev(p_ls);
   if (int rc = select((const int*)(di + i_ss), H.local_kf ? out.dev(p_lk) : nullptr, d_lo, d_ls, (double*)(dout + o_gp), dout + o_gd)) return rc;
   TrackArgs A{};
@@ -1845,7 +1831,7 @@ int mf_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kf
     const orbx_keyframe* kf = kfs[tgt[t]];
     MfTgt& g = P.tgts[(size_t)t];
     g.kp = kf->d_kp; g.desc = kf->d_desc; g.slots = kf->d_mp_slot; g.n = kf->n; g.feat_off = (int)ft;
-    ms_pose_inverse(kf->pose_wc, g.pose_cw);
+    orbx_pose_inverse(kf->pose_wc, g.pose_cw);
     P.kfs[(size_t)tgt[t]].tgt = t;
     P.members[(size_t)t] = CovMember{tgt[t], t};
     ft += kf->n;
@@ -2171,7 +2157,6 @@ int mc_enqueue(orbx_handle* h, const orbx_camera* cam, const orbx_triangulation_
   A.counts = d_counts; A.new_slot = d_new_slot; A.new_nb = d_new_nb; A.new_i1 = d_new_i1; A.new_i2 = d_new_i2; A.new_pts = d_new_pts; A.new_desc = d_new_desc;
   A.stats = d_stats;
   const dim3 block(MS_THREADS);
-  orbx_prof_begin_call(h);
   if (max_n > 0) orbx_launch(h, "mc_flag_kernel", false, mc_flag_kernel, dim3((max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, A);
   if ((phases & ORBX_MAP_CREATE_STEREO) && n1 > 0) orbx_launch(h, "mc_stereo_kernel", true, mc_stereo_kernel, dim3(1), block, 0, A);
   ORBX_HIP(h, hipGetLastError());
@@ -2210,7 +2195,6 @@ int mr_enqueue(orbx_handle* h, orbx_map_points* mp, const CovPlan& P, int n, con
   uint8_t* mark = (uint8_t*)mp->mark.p;
   const dim3 block(MS_THREADS), list_grid((unsigned)((N + MS_THREADS - 1) / MS_THREADS));
   *d_cleared = (const int*)(ds + u_cn);
-  orbx_prof_begin_call(h);
   if (K > 0 && P.max_n > 0) {
     orbx_launch(h, "mr_mark_kernel", false, mr_mark_kernel, list_grid, block, 0, d_slots, n, mark, 1);
     orbx_launch(h, "mr_clear_kernel", true, mr_clear_kernel, dim3((P.max_n + MS_CHUNK - 1) / MS_CHUNK, (unsigned)K), block, 0, (const McKf*)(ds + u_kf), mp->capacity,
@@ -2781,7 +2765,6 @@ int orbx_map_fuse(orbx_handle* h, const orbx_camera* cam, orbx_map_points* mp, i
     OutputPlan out;
     const auto p_cn = out.add(counts, 4), p_go = out.add(goner, Gb, true), p_ke = out.add(keeper, Gb, true), p_ls = out.add(list_slot, B, true), p_ma = out.add(match, B * T, true);
     if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
-    orbx_prof_begin_call(h);
     if (int rc = mf_enqueue(h, who, cam, mp, P, radius_scale, desc_threshold, out.dev(p_cn), out.dev(p_ls), out.dev(p_ma), out.dev(p_go), out.dev(p_ke))) return rc;
     if (int rc = out.finish(h)) return rc;
     const size_t Pn = (size_t)counts[0], G = (size_t)counts[3];
@@ -2834,7 +2817,6 @@ int orbx_map_search_in_neighbors(orbx_handle* h, const orbx_camera* cam, orbx_ma
     // (the refresh below is a host form of its own: it takes the pinned buffer and the blob workspace once everything is copied out of them)
     if (int rc = out.begin(h, h->pin_map, h->ws_map.host_blobs)) return rc;
     uint8_t* d = out.call.dout;
-    orbx_prof_begin_call(h);
     if (int rc = mf_enqueue(h, who, cam, mp, A, radius_scale, desc_threshold, out.dev(p_cn), (int*)(d + o_la), (int*)(d + o_ma), out.dev(p_ga), out.dev(p_ka))) return rc;
     if (int rc = mf_enqueue(h, who, cam, mp, B, radius_scale, desc_threshold, out.dev(p_cn) + 4, (int*)(d + o_lb), (int*)(d + o_mb), out.dev(p_gb), out.dev(p_kb))) return rc;
     if (int rc = ms_select_enqueue(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, S, nullptr, nullptr, (int)Ab, out.dev(p_ao), out.dev(p_as), (double*)(d + o_ap), d + o_ad))
@@ -2954,7 +2936,6 @@ int orbx_map_cull_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const o
     ObsCall c;
     c.n_points = M; c.slots = cand;
     const int* d_count = nullptr;
-    orbx_prof_begin_call(h);
     if (int rc = obs_enqueue(h, mp, P, c, nullptr, &d_count)) return rc;
     // the one download: the candidates' observer counts.  The comparison is the host's: the mirror needs the list anyway.
     ORBX_HIP(h, hipMemcpyAsync(h->pin_map.p, d_count, 4 * (size_t)M, hipMemcpyDeviceToHost, h->stream));

@@ -268,7 +268,6 @@ int mp_refresh_enqueue(orbx_handle* h, const char* who, int M, int n_obs, const 
   A.desc_out = d_mp_desc; A.normals_out = d_normals; A.min_distance = d_min_distance; A.max_distance = d_max_distance; A.records = d_records;
   A.n_long = (int*)(w + o_cnt); A.long_list = (int*)(w + o_list);
   ORBX_HIP(h, hipMemsetAsync(A.n_long, 0, sizeof(int), h->stream));
-  orbx_prof_begin_call(h);
   // the window that holds obs_start == n_obs (trailing points without observations) is launched too
   orbx_launch(h, "mp_refresh_kernel", false, mp_refresh_kernel, dim3(n_obs / MP_WIN + 1), dim3(MP_THREADS), 0, A);
   if (long_cap > 0) orbx_launch(h, "mp_refresh_long_kernel", true, mp_refresh_long_kernel, dim3(std::min(long_cap, 4 * h->n_cu)), dim3(MP_LONG_THREADS), 0, A);

@@ -153,8 +153,6 @@ ProfScope::~ProfScope() {
   h->timers[idx].ev.push_back(e);
   h->prof_tail = e;
 }
-void orbx_prof_begin_call(orbx_handle* h) { (void)h; }   // events accumulate until they are read
-void orbx_prof_end_call(orbx_handle* h) { (void)h; }
 
 extern "C" {
 
@@ -230,7 +228,7 @@ void orbx_destroy(orbx_handle* h) {
                     &h->ws_sel, &h->ws_sel2, &h->ws_match, &h->ws_dtile,
                     &h->ws_ba_in, &h->ws_ba_arena, &h->ws_ba_out, &h->ws_ba_imu, &h->ws_ba_s15, &h->ws_ba_debug};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
-  for (DevBuf& b : h->ws_io) if (b.p) hipFree(b.p);
+  h->ws_io.for_each([](DevBuf& b) { if (b.p) hipFree(b.p); });
   for (DevBuf& b : h->ws_pnp) if (b.p) hipFree(b.p);
   if (h->ws_pi.p) hipFree(h->ws_pi.p);
   for (DevBuf& b : h->ws_track) if (b.p) hipFree(b.p);
@@ -246,8 +244,8 @@ void orbx_destroy(orbx_handle* h) {
   for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
   if (h->pair_graph) hipGraphExecDestroy(h->pair_graph);
   orbx_rccl_drop(h);
-  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp, &h->pin_map};
-  UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv, &h->ring_mp, &h->ring_map};
+  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp, &h->pin_map, &h->pin_io};
+  UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv, &h->ring_mp, &h->ring_map, &h->ring_io};
   for (PinnedBuf* b : pins) if (b->p) hipHostFree(b->p);
   for (UploadRing* r : rings) {
     for (PinnedBuf& b : r->slot) if (b.p) hipHostFree(b.p);
@@ -339,7 +337,6 @@ int orbx_stereo_match_batch_device(orbx_handle* h, int batch, const orbx_keypoin
   if (batch < 0 || cap_kp < 1 || !d_kp || !d_desc || !d_nkp || !d_matches || !d_nmatches || !d_points || !d_has_point)
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_stereo_match_batch_device: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return launch_stereo_match(h, batch, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point);
 }
 
@@ -353,36 +350,32 @@ int orbx_stereo_match(orbx_handle* h, const orbx_keypoint* kpL, const uint8_t* d
   *n_matches = 0;
   if (nL == 0) return ORBX_OK;   // stereo.rs:95 loop body never runs
   ORBX_HIP(h, hipSetDevice(h->device));
-  const int cap = nL > nR ? nL : nR;
+  const int cap = nL > nR ? nL : nR;                                  // the pair as a batch of one: rows [0, cap) left, [cap, 2 cap) right
   const size_t kpb = sizeof(orbx_keypoint) * (size_t)cap, db = 32 * (size_t)cap;
-  if (int rc = orbx_reserve(h, h->ws_io[0], 2 * kpb)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 2 * db)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], 4 * sizeof(int))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], sizeof(orbx_dmatch) * (size_t)cap)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[4], sizeof(double) * 3 * (size_t)cap)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[5], (size_t)cap)) return rc;
-  orbx_keypoint* d_kp = (orbx_keypoint*)h->ws_io[0].p;
-  uint8_t* d_desc = (uint8_t*)h->ws_io[1].p;
-  int* d_n = (int*)h->ws_io[2].p;
-  const int counts[2] = {nL, nR};
-  ORBX_HIP(h, hipMemcpyAsync(d_kp, kpL, sizeof(orbx_keypoint) * (size_t)nL, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_desc, descL, 32 * (size_t)nL, hipMemcpyHostToDevice, h->stream));
+  Carve in;
+  const size_t i_kp = in.take(2 * kpb), i_de = in.take(2 * db), i_n = in.take(2 * sizeof(int));
+  OutputPlan out;
+  const auto p_n = out.add(n_matches, 1);
+  const auto p_pt = out.add(points_cam, 3 * (size_t)cap, true);
+  const auto p_hp = out.add(has_point, (size_t)cap, true);
+  const auto p_m = out.add(matches, (size_t)cap, true);
+  if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  uint8_t *hi = out.call.hi, *di = out.call.di;
+  memcpy(hi + i_kp, kpL, sizeof(orbx_keypoint) * (size_t)nL);
+  memcpy(hi + i_de, descL, 32 * (size_t)nL);
   if (nR > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(d_kp + cap, kpR, sizeof(orbx_keypoint) * (size_t)nR, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(d_desc + db, descR, 32 * (size_t)nR, hipMemcpyHostToDevice, h->stream));
+    memcpy(hi + i_kp + kpb, kpR, sizeof(orbx_keypoint) * (size_t)nR);
+    memcpy(hi + i_de + db, descR, 32 * (size_t)nR);
   }
-  ORBX_HIP(h, hipMemcpyAsync(d_n, counts, sizeof(counts), hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));  // `counts` is a stack buffer
-  orbx_prof_begin_call(h);
-  if (int rc = launch_stereo_match(h, 1, d_kp, d_desc, d_n, cap, (orbx_dmatch*)h->ws_io[3].p, d_n + 2,
-                                   (double*)h->ws_io[4].p, (uint8_t*)h->ws_io[5].p))
+  const int counts[2] = {nL, nR};
+  memcpy(hi + i_n, counts, sizeof(counts));
+  if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+  if (int rc = launch_stereo_match(h, 1, (const orbx_keypoint*)(di + i_kp), di + i_de, (const int*)(di + i_n), cap, out.dev(p_m), out.dev(p_n), out.dev(p_pt),
+                                   out.dev(p_hp)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(n_matches, d_n + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(points_cam, h->ws_io[4].p, sizeof(double) * 3 * (size_t)nL, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(has_point, h->ws_io[5].p, (size_t)nL, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (*n_matches > 0)
-    ORBX_HIP(h, hipMemcpy(matches, h->ws_io[3].p, sizeof(orbx_dmatch) * (size_t)*n_matches, hipMemcpyDeviceToHost));
+  if (int rc = out.finish(h)) return rc;
+  for (int rc : {out.copy(h, p_pt, 3 * (size_t)nL), out.copy(h, p_hp, (size_t)nL), out.copy(h, p_m, (size_t)*n_matches)})
+    if (rc) return rc;
   return ORBX_OK;
 }
 
@@ -392,7 +385,6 @@ int orbx_hamming_match_crosscheck_device(orbx_handle* h, const uint8_t* d_q, int
   if (nq < 0 || nt < 0 || !d_n_out || (nq > 0 && (!d_q || !d_out)) || (nt > 0 && !d_t))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_hamming_match_crosscheck_device: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return launch_crosscheck(h, d_q, nq, d_t, nt, d_out, d_n_out);
 }
 
@@ -404,21 +396,18 @@ int orbx_hamming_match_crosscheck(orbx_handle* h, const uint8_t* q, int nq, cons
   *n_out = 0;
   if (nq == 0 || nt == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  if (int rc = orbx_reserve(h, h->ws_io[0], 32 * (size_t)nq)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 32 * (size_t)nt)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], sizeof(int))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], sizeof(orbx_dmatch) * (size_t)nq)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[0].p, q, 32 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[1].p, t, 32 * (size_t)nt, hipMemcpyHostToDevice, h->stream));
-  orbx_prof_begin_call(h);
-  if (int rc = launch_crosscheck(h, (const uint8_t*)h->ws_io[0].p, nq, (const uint8_t*)h->ws_io[1].p, nt,
-                                 (orbx_dmatch*)h->ws_io[3].p, (int*)h->ws_io[2].p))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(n_out, h->ws_io[2].p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (*n_out > 0)
-    ORBX_HIP(h, hipMemcpy(out, h->ws_io[3].p, sizeof(orbx_dmatch) * (size_t)*n_out, hipMemcpyDeviceToHost));
-  return ORBX_OK;
+  Carve in;
+  const size_t i_q = in.take(32 * (size_t)nq), i_t = in.take(32 * (size_t)nt);
+  OutputPlan res;
+  const auto p_n = res.add(n_out, 1);
+  const auto p_m = res.add(out, (size_t)nq, true);
+  if (int rc = res.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  memcpy(res.call.hi + i_q, q, 32 * (size_t)nq);
+  memcpy(res.call.hi + i_t, t, 32 * (size_t)nt);
+  if (int rc = orbx_host_call_upload(h, res.call)) return rc;
+  if (int rc = launch_crosscheck(h, res.call.di + i_q, nq, res.call.di + i_t, nt, res.dev(p_m), res.dev(p_n))) return rc;
+  if (int rc = res.finish(h)) return rc;
+  return res.copy(h, p_m, (size_t)*n_out);
 }
 
 int orbx_hamming_batch_device(orbx_handle* h, const uint8_t* d_a, const uint8_t* d_b, int n_pairs,
@@ -427,7 +416,6 @@ int orbx_hamming_batch_device(orbx_handle* h, const uint8_t* d_a, const uint8_t*
   if (n_pairs < 0 || (n_pairs > 0 && (!d_a || !d_b || !d_out)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_hamming_batch_device: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return launch_hamming_batch(h, d_a, d_b, n_pairs, d_out);
 }
 
@@ -438,18 +426,16 @@ int orbx_hamming_batch(orbx_handle* h, const uint8_t* a, const uint8_t* b, int n
   if (n_pairs == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t bytes = 32 * (size_t)n_pairs;
-  if (int rc = orbx_reserve(h, h->ws_io[0], bytes)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], bytes)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], sizeof(uint32_t) * (size_t)n_pairs)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[0].p, a, bytes, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[1].p, b, bytes, hipMemcpyHostToDevice, h->stream));
-  orbx_prof_begin_call(h);
-  if (int rc = launch_hamming_batch(h, (const uint8_t*)h->ws_io[0].p, (const uint8_t*)h->ws_io[1].p, n_pairs,
-                                    (uint32_t*)h->ws_io[2].p))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out, h->ws_io[2].p, sizeof(uint32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  Carve in;
+  const size_t i_a = in.take(bytes), i_b = in.take(bytes);
+  OutputPlan res;
+  const auto p_d = res.add(out, (size_t)n_pairs);
+  if (int rc = res.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  memcpy(res.call.hi + i_a, a, bytes);
+  memcpy(res.call.hi + i_b, b, bytes);
+  if (int rc = orbx_host_call_upload(h, res.call)) return rc;
+  if (int rc = launch_hamming_batch(h, res.call.di + i_a, res.call.di + i_b, n_pairs, res.dev(p_d))) return rc;
+  return res.finish(h);
 }
 
 int orbx_guided_match_device(orbx_handle* h, const orbx_keypoint* d_kp, const uint8_t* d_desc, int n, double img_w,
@@ -460,7 +446,6 @@ int orbx_guided_match_device(orbx_handle* h, const orbx_keypoint* d_kp, const ui
       (n > 0 && (!d_kp || !d_desc)) || (nq > 0 && (!d_q_uv || !d_q_desc || !d_out_idx || !d_out_dist)))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_guided_match_device: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return launch_guided_match(h, d_kp, d_desc, n, img_w, img_h, d_q_uv, d_q_desc, nq, radius, mode, d_out_idx, d_out_dist);
 }
 
@@ -473,28 +458,25 @@ int orbx_guided_match(orbx_handle* h, const orbx_keypoint* kp, const uint8_t* de
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_guided_match: bad argument");
   if (nq == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t nn = (size_t)(n > 0 ? n : 1);
-  if (int rc = orbx_reserve(h, h->ws_io[0], sizeof(orbx_keypoint) * nn)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 32 * nn)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], 16 * (size_t)nq)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], 32 * (size_t)nq)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[4], 8 * (size_t)nq)) return rc;
+  const size_t nn = (size_t)(n > 0 ? n : 1), NQ = (size_t)nq;
+  Carve in;
+  const size_t i_kp = in.take(sizeof(orbx_keypoint) * nn), i_de = in.take(32 * nn), i_uv = in.take(16 * NQ), i_qd = in.take(32 * NQ);
+  OutputPlan out;
+  const auto p_idx = out.add(out_idx, NQ);
+  const auto p_dist = out.add(out_dist, NQ);
+  if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  uint8_t *hi = out.call.hi, *di = out.call.di;
   if (n > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(h->ws_io[0].p, kp, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(h->ws_io[1].p, desc, 32 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    memcpy(hi + i_kp, kp, sizeof(orbx_keypoint) * (size_t)n);
+    memcpy(hi + i_de, desc, 32 * (size_t)n);
   }
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[2].p, q_uv, 16 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[3].p, q_desc, 32 * (size_t)nq, hipMemcpyHostToDevice, h->stream));
-  int* d_idx = (int*)h->ws_io[4].p;
-  uint32_t* d_dist = (uint32_t*)(d_idx + nq);
-  orbx_prof_begin_call(h);
-  if (int rc = launch_guided_match(h, (const orbx_keypoint*)h->ws_io[0].p, (const uint8_t*)h->ws_io[1].p, n, img_w, img_h,
-                                   (const double*)h->ws_io[2].p, (const uint8_t*)h->ws_io[3].p, nq, radius, mode, d_idx, d_dist))
+  memcpy(hi + i_uv, q_uv, 16 * NQ);
+  memcpy(hi + i_qd, q_desc, 32 * NQ);
+  if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+  if (int rc = launch_guided_match(h, (const orbx_keypoint*)(di + i_kp), di + i_de, n, img_w, img_h, (const double*)(di + i_uv), di + i_qd, nq, radius, mode,
+                                   out.dev(p_idx), out.dev(p_dist)))
     return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, 4 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  return out.finish(h);
 }
 
 namespace {
@@ -541,6 +523,50 @@ extern "C++" void orbx_triangulation_geometry(const orbx_camera* cam, const doub
   triangulation_geometry(*cam, pose1_wc, pose2_wc, ep2, F9);
 }
 
+// The host form of the triangulation search behind orbx_search_for_triangulation and, with node1 / node2 given, its FeatureVector
+// form: that one adds keyframe 2's sorted list and keyframe 1's ranges to the upload and calls the other launcher.
+static int search_for_triangulation_host(orbx_handle* h, const orbx_camera* cam, const orbx_keypoint* kp1, const uint8_t* desc1, const uint8_t* mp1,
+                                         const uint8_t* stereo1, const uint32_t* node1, int n1, const orbx_keypoint* kp2, const uint8_t* desc2,
+                                         const uint8_t* mp2, const uint32_t* node2, int n2, const double* pose1_wc, const double* pose2_wc,
+                                         unsigned max_dist, int* out_pairs, int* n_out) {
+  ORBX_HIP(h, hipSetDevice(h->device));
+  double ep[2], F[9];
+  triangulation_geometry(*cam, pose1_wc, pose2_wc, ep, F);
+  const bool bow = node1 != nullptr;
+  const size_t N1 = (size_t)n1, N2 = (size_t)n2;
+  Carve in;
+  const size_t i_kp1 = in.take(sizeof(orbx_keypoint) * N1), i_kp2 = in.take(sizeof(orbx_keypoint) * N2), i_d1 = in.take(32 * N1), i_d2 = in.take(32 * N2),
+               i_mp1 = in.take(N1), i_st1 = in.take(N1), i_mp2 = in.take(N2);
+  const size_t i_so = in.take(bow ? 4 * N2 : 0), i_lo = in.take(bow ? 4 * N1 : 0), i_hi = in.take(bow ? 4 * N1 : 0);
+  OutputPlan out;
+  const auto p_n = out.add(n_out, 1);
+  const auto p_pr = out.add(out_pairs, 2 * N1, true);
+  if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  uint8_t *hi = out.call.hi, *di = out.call.di;
+  memcpy(hi + i_kp1, kp1, sizeof(orbx_keypoint) * N1);
+  memcpy(hi + i_kp2, kp2, sizeof(orbx_keypoint) * N2);
+  memcpy(hi + i_d1, desc1, 32 * N1);
+  memcpy(hi + i_d2, desc2, 32 * N2);
+  memcpy(hi + i_mp1, mp1, N1);
+  memcpy(hi + i_st1, stereo1, N1);
+  memcpy(hi + i_mp2, mp2, N2);
+  if (bow) {
+    int* sorted = (int*)(hi + i_so);
+    const int m2 = orbx_sort_by_node(node2, n2, sorted);
+    orbx_node_ranges(node1, n1, node2, sorted, m2, (int*)(hi + i_lo), (int*)(hi + i_hi));
+  }
+  if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+  const orbx_keypoint* d_kp1 = (const orbx_keypoint*)(di + i_kp1); const orbx_keypoint* d_kp2 = (const orbx_keypoint*)(di + i_kp2);
+  if (int rc = bow ? launch_search_for_triangulation_bow(h, F, ep, d_kp1, di + i_d1, di + i_mp1, di + i_st1, n1, d_kp2, di + i_d2, di + i_mp2, n2,
+                                                         (const int*)(di + i_so), (const int*)(di + i_lo), (const int*)(di + i_hi), max_dist, out.dev(p_pr),
+                                                         out.dev(p_n))
+                   : launch_search_for_triangulation(h, cam, F, ep, d_kp1, di + i_d1, di + i_mp1, di + i_st1, n1, d_kp2, di + i_d2, di + i_mp2, n2, max_dist,
+                                                     out.dev(p_pr), out.dev(p_n)))
+    return rc;
+  if (int rc = out.finish(h)) return rc;
+  return out.copy(h, p_pr, 2 * (size_t)*n_out);
+}
+
 int orbx_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const orbx_keypoint* kp1, const uint8_t* desc1,
                                   const uint8_t* mp1, const uint8_t* stereo1, int n1, const orbx_keypoint* kp2,
                                   const uint8_t* desc2, const uint8_t* mp2, int n2, const double* pose1_wc,
@@ -551,32 +577,8 @@ int orbx_search_for_triangulation(orbx_handle* h, const orbx_camera* cam, const 
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_search_for_triangulation: bad argument");
   *n_out = 0;
   if (n1 == 0 || n2 == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  double ep[2], F[9];
-  triangulation_geometry(*cam, pose1_wc, pose2_wc, ep, F);
-  const size_t s1 = sizeof(orbx_keypoint) * (size_t)n1, s2 = sizeof(orbx_keypoint) * (size_t)n2;
-  if (int rc = orbx_reserve(h, h->ws_io[0], s1 + s2)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 32 * ((size_t)n1 + n2))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], 2 * (size_t)n1 + n2)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], sizeof(int) * (2 * (size_t)n1 + 4))) return rc;
-  orbx_keypoint* d_kp1 = (orbx_keypoint*)h->ws_io[0].p; orbx_keypoint* d_kp2 = d_kp1 + n1;
-  uint8_t* d_d1 = (uint8_t*)h->ws_io[1].p; uint8_t* d_d2 = d_d1 + 32 * (size_t)n1;
-  uint8_t* d_mp1 = (uint8_t*)h->ws_io[2].p; uint8_t* d_st1 = d_mp1 + n1; uint8_t* d_mp2 = d_st1 + n1;
-  int* d_pairs = (int*)h->ws_io[3].p; int* d_n = d_pairs + 2 * (size_t)n1;
-  ORBX_HIP(h, hipMemcpyAsync(d_kp1, kp1, s1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_kp2, kp2, s2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_d1, desc1, 32 * (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_d2, desc2, 32 * (size_t)n2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_mp1, mp1, (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_st1, stereo1, (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_mp2, mp2, (size_t)n2, hipMemcpyHostToDevice, h->stream));
-  orbx_prof_begin_call(h);
-  if (int rc = launch_search_for_triangulation(h, cam, F, ep, d_kp1, d_d1, d_mp1, d_st1, n1, d_kp2, d_d2, d_mp2, n2, max_dist, d_pairs, d_n))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
-  return ORBX_OK;
+  return search_for_triangulation_host(h, cam, kp1, desc1, mp1, stereo1, nullptr, n1, kp2, desc2, mp2, nullptr, n2, pose1_wc, pose2_wc, max_dist, out_pairs,
+                                       n_out);
 }
 
 int orbx_search_for_triangulation_device(orbx_handle* h, const orbx_camera* cam, const orbx_keypoint* d_kp1, const uint8_t* d_desc1,
@@ -590,7 +592,6 @@ int orbx_search_for_triangulation_device(orbx_handle* h, const orbx_camera* cam,
   ORBX_HIP(h, hipSetDevice(h->device));
   double ep[2], F[9];
   triangulation_geometry(*cam, pose1_wc, pose2_wc, ep, F);
-  orbx_prof_begin_call(h);
   return launch_search_for_triangulation(h, cam, F, ep, d_kp1, d_desc1, d_mp1, d_stereo1, n1, d_kp2, d_desc2, d_mp2, n2, max_dist, d_pairs,
                                          d_n_out);
 }
@@ -600,131 +601,74 @@ int orbx_search_for_triangulation_bow(orbx_handle* h, const orbx_camera* cam, co
                                       const orbx_keypoint* kp2, const uint8_t* desc2, const uint8_t* mp2, const uint32_t* node2, int n2,
                                       const double* pose1_wc, const double* pose2_wc, unsigned max_dist, int* out_pairs, int* n_out) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || n1 < 0 || n2 < 0 || !pose1_wc || !pose2_wc || !n_out || max_dist > 256 ||
-      (n1 > 0 && (!kp1 || !desc1 || !mp1 || !stereo1 || !node1 || !out_pairs)) || (n2 > 0 && (!kp2 || !desc2 || !mp2 || !node2)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_search_for_triangulation_bow: bad argument");
-  *n_out = 0;
-  if (n1 == 0 || n2 == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  double ep[2], F[9];
-  triangulation_geometry(*cam, pose1_wc, pose2_wc, ep, F);
-  // FeatureVector of keyframe 2 as one sorted array: (node, index) ascending = every node's list in push order (:309)
-  std::vector<int> sorted((size_t)n2), lo((size_t)n1, 0), hi((size_t)n1, 0);
-  for (int i = 0; i < n2; ++i) sorted[(size_t)i] = i;
-  std::stable_sort(sorted.begin(), sorted.end(), [&](int a, int b) { return node2[a] < node2[b]; });
-  int m2 = n2;                                                           // features in no list sort last and are cut off
-  while (m2 > 0 && node2[sorted[(size_t)m2 - 1]] == 0xffffffffu) --m2;
-  for (int i = 0; i < n1; ++i) {
-    if (node1[i] == 0xffffffffu) continue;
-    const uint32_t key = node1[i];
-    const auto b = std::lower_bound(sorted.begin(), sorted.begin() + m2, key, [&](int a, uint32_t k) { return node2[a] < k; });
-    const auto e = std::upper_bound(b, sorted.begin() + m2, key, [&](uint32_t k, int a) { return k < node2[a]; });
-    lo[(size_t)i] = (int)(b - sorted.begin()); hi[(size_t)i] = (int)(e - sorted.begin());
-  }
-  const size_t s1 = sizeof(orbx_keypoint) * (size_t)n1, s2 = sizeof(orbx_keypoint) * (size_t)n2;
-  if (int rc = orbx_reserve(h, h->ws_io[0], s1 + s2)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 32 * ((size_t)n1 + n2))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], 2 * (size_t)n1 + n2)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], sizeof(int) * (2 * (size_t)n1 + 4))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[4], sizeof(int) * (2 * (size_t)n1 + (size_t)n2))) return rc;
-  orbx_keypoint* d_kp1 = (orbx_keypoint*)h->ws_io[0].p; orbx_keypoint* d_kp2 = d_kp1 + n1;
-  uint8_t* d_d1 = (uint8_t*)h->ws_io[1].p; uint8_t* d_d2 = d_d1 + 32 * (size_t)n1;
-  uint8_t* d_mp1 = (uint8_t*)h->ws_io[2].p; uint8_t* d_st1 = d_mp1 + n1; uint8_t* d_mp2 = d_st1 + n1;
-  int* d_pairs = (int*)h->ws_io[3].p; int* d_n = d_pairs + 2 * (size_t)n1;
-  int* d_lo = (int*)h->ws_io[4].p; int* d_hi = d_lo + n1; int* d_sorted = d_hi + n1;
-  ORBX_HIP(h, hipMemcpyAsync(d_kp1, kp1, s1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_kp2, kp2, s2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_d1, desc1, 32 * (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_d2, desc2, 32 * (size_t)n2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_mp1, mp1, (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_st1, stereo1, (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_mp2, mp2, (size_t)n2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_lo, lo.data(), sizeof(int) * (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_hi, hi.data(), sizeof(int) * (size_t)n1, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_sorted, sorted.data(), sizeof(int) * (size_t)n2, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));   // lo/hi/sorted are locals
-  orbx_prof_begin_call(h);
-  if (int rc = launch_search_for_triangulation_bow(h, F, ep, d_kp1, d_d1, d_mp1, d_st1, n1, d_kp2, d_d2, d_mp2, n2, d_sorted, d_lo, d_hi,
-                                                   max_dist, d_pairs, d_n))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(n_out, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  if (*n_out > 0) ORBX_HIP(h, hipMemcpy(out_pairs, d_pairs, sizeof(int) * 2 * (size_t)*n_out, hipMemcpyDeviceToHost));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_search_for_triangulation_bow", [&]() -> int {
+    if (!cam || n1 < 0 || n2 < 0 || !pose1_wc || !pose2_wc || !n_out || max_dist > 256 ||
+        (n1 > 0 && (!kp1 || !desc1 || !mp1 || !stereo1 || !node1 || !out_pairs)) || (n2 > 0 && (!kp2 || !desc2 || !mp2 || !node2)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_search_for_triangulation_bow: bad argument");
+    *n_out = 0;
+    if (n1 == 0 || n2 == 0) return ORBX_OK;
+    return search_for_triangulation_host(h, cam, kp1, desc1, mp1, stereo1, node1, n1, kp2, desc2, mp2, node2, n2, pose1_wc, pose2_wc, max_dist, out_pairs,
+                                         n_out);
+  });
 }
 
 int orbx_fuse_search_device(orbx_handle* h, const orbx_camera* cam, const double* d_positions, const uint8_t* d_mp_desc, int P,
                             const double* kf_poses_wc, const int* d_kf_feat_offset, const orbx_keypoint* d_kps, const uint8_t* d_descs, int T,
                             double radius_scale, unsigned desc_threshold, int* d_out_idx, uint32_t* d_out_dist) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || P < 0 || T < 0 || (P > 0 && (!d_positions || !d_mp_desc)) || (T > 0 && (!kf_poses_wc || !d_kf_feat_offset)) ||
-      (P > 0 && T > 0 && (!d_out_idx || !d_out_dist || !d_kps || !d_descs)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search_device: bad argument");
-  if (P == 0 || T == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  std::vector<double> cw(7 * (size_t)T);                                 // kf.pose.inverse() (se3.rs:56-63)
-  for (int t = 0; t < T; ++t) {
-    const double* p = kf_poses_wc + 7 * (size_t)t;
-    const Quat qi{p[0], -p[1], -p[2], -p[3]};
-    double r[3];
-    quat_rotate(qi, p + 4, r);
-    double* o = cw.data() + 7 * (size_t)t;
-    o[0] = qi.w; o[1] = qi.x; o[2] = qi.y; o[3] = qi.z; o[4] = -r[0]; o[5] = -r[1]; o[6] = -r[2];
-  }
-  if (int rc = orbx_reserve(h, h->ws_io[5], sizeof(double) * 7 * (size_t)T)) return rc;
-  ORBX_HIP(h, hipMemcpyAsync(h->ws_io[5].p, cw.data(), sizeof(double) * 7 * (size_t)T, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));   // cw is a local
-  orbx_prof_begin_call(h);
-  return launch_fuse_search(h, cam, d_positions, d_mp_desc, P, (const double*)h->ws_io[5].p, d_kf_feat_offset, d_kps, d_descs, T, radius_scale,
-                            desc_threshold, d_out_idx, d_out_dist);
+  return orbx_guard(h, "orbx_fuse_search_device", [&]() -> int {
+    if (!cam || P < 0 || T < 0 || (P > 0 && (!d_positions || !d_mp_desc)) || (T > 0 && (!kf_poses_wc || !d_kf_feat_offset)) ||
+        (P > 0 && T > 0 && (!d_out_idx || !d_out_dist || !d_kps || !d_descs)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search_device: bad argument");
+    if (P == 0 || T == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    // kf.pose.inverse() per keyframe, made in the ring slot: kf_poses_wc is free when the call returns and nothing waits for the stream
+    UploadPlan up;
+    const size_t o_cw = up.put(nullptr, sizeof(double) * 7 * (size_t)T);
+    if (int rc = up.begin(h, h->ring_io, h->ws_io.fuse_poses)) return rc;
+    for (int t = 0; t < T; ++t) orbx_pose_inverse(kf_poses_wc + 7 * (size_t)t, (double*)(up.host + o_cw) + 7 * (size_t)t);
+    if (int rc = up.commit(h, h->ring_io, h->ws_io.fuse_poses)) return rc;
+    return launch_fuse_search(h, cam, d_positions, d_mp_desc, P, (const double*)(up.device + o_cw), d_kf_feat_offset, d_kps, d_descs, T, radius_scale,
+                              desc_threshold, d_out_idx, d_out_dist);
+  });
 }
 
 int orbx_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* positions, const uint8_t* mp_desc, int P,
                      const double* kf_poses_wc, const int* kf_feat_offset, const orbx_keypoint* kps, const uint8_t* descs, int T,
                      double radius_scale, unsigned desc_threshold, int* out_idx, uint32_t* out_dist) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!cam || P < 0 || T < 0 || (P > 0 && (!positions || !mp_desc)) || (T > 0 && (!kf_poses_wc || !kf_feat_offset)) ||
-      (P > 0 && T > 0 && (!out_idx || !out_dist)))
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
-  if (P == 0 || T == 0) return ORBX_OK;
-  if (int rc = orbx_check_offsets(h, "orbx_fuse_search", "kf_feat_offset", "keyframe", T, kf_feat_offset)) return rc;
-  const int n = kf_feat_offset[T];
-  if (n > 0 && (!kps || !descs)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  std::vector<double> cw(7 * (size_t)T);                                 // kf.pose.inverse() (se3.rs:56-63)
-  for (int t = 0; t < T; ++t) {
-    const double* p = kf_poses_wc + 7 * (size_t)t;
-    const Quat qi{p[0], -p[1], -p[2], -p[3]};
-    double r[3];
-    quat_rotate(qi, p + 4, r);
-    double* o = cw.data() + 7 * (size_t)t;
-    o[0] = qi.w; o[1] = qi.x; o[2] = qi.y; o[3] = qi.z; o[4] = -r[0]; o[5] = -r[1]; o[6] = -r[2];
-  }
-  const size_t pt = (size_t)P * T;
-  if (int rc = orbx_reserve(h, h->ws_io[0], sizeof(orbx_keypoint) * (size_t)std::max(n, 1))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[1], 32 * ((size_t)std::max(n, 1) + P))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[2], sizeof(double) * (3 * (size_t)P + 7 * (size_t)T) + sizeof(int) * ((size_t)T + 1))) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[3], 8 * pt)) return rc;
-  orbx_keypoint* d_kps = (orbx_keypoint*)h->ws_io[0].p;
-  uint8_t* d_descs = (uint8_t*)h->ws_io[1].p; uint8_t* d_mpd = d_descs + 32 * (size_t)std::max(n, 1);
-  double* d_pos = (double*)h->ws_io[2].p; double* d_cw = d_pos + 3 * (size_t)P; int* d_off = (int*)(d_cw + 7 * (size_t)T);
-  int* d_idx = (int*)h->ws_io[3].p; uint32_t* d_dist = (uint32_t*)(d_idx + pt);
-  if (n > 0) {
-    ORBX_HIP(h, hipMemcpyAsync(d_kps, kps, sizeof(orbx_keypoint) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    ORBX_HIP(h, hipMemcpyAsync(d_descs, descs, 32 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  }
-  ORBX_HIP(h, hipMemcpyAsync(d_mpd, mp_desc, 32 * (size_t)P, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_pos, positions, sizeof(double) * 3 * (size_t)P, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_cw, cw.data(), sizeof(double) * 7 * (size_t)T, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(d_off, kf_feat_offset, sizeof(int) * ((size_t)T + 1), hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));   // cw is a local; pageable copies are staged but keep it simple
-  orbx_prof_begin_call(h);
-  if (int rc = launch_fuse_search(h, cam, d_pos, d_mpd, P, d_cw, d_off, d_kps, d_descs, T, radius_scale, desc_threshold, d_idx, d_dist))
-    return rc;
-  ORBX_HIP(h, hipMemcpyAsync(out_idx, d_idx, sizeof(int) * pt, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipMemcpyAsync(out_dist, d_dist, sizeof(uint32_t) * pt, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  return ORBX_OK;
+  return orbx_guard(h, "orbx_fuse_search", [&]() -> int {
+    if (!cam || P < 0 || T < 0 || (P > 0 && (!positions || !mp_desc)) || (T > 0 && (!kf_poses_wc || !kf_feat_offset)) ||
+        (P > 0 && T > 0 && (!out_idx || !out_dist)))
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
+    if (P == 0 || T == 0) return ORBX_OK;
+    if (int rc = orbx_check_offsets(h, "orbx_fuse_search", "kf_feat_offset", "keyframe", T, kf_feat_offset)) return rc;
+    const int n = kf_feat_offset[T];
+    if (n > 0 && (!kps || !descs)) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_fuse_search: bad argument");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t N = (size_t)std::max(n, 1), Pz = (size_t)P, Tz = (size_t)T, pt = Pz * Tz;
+    Carve in;
+    const size_t i_kps = in.take(sizeof(orbx_keypoint) * N), i_ds = in.take(32 * N), i_md = in.take(32 * Pz), i_pos = in.take(24 * Pz), i_cw = in.take(56 * Tz),
+                 i_off = in.take(4 * (Tz + 1));
+    OutputPlan out;
+    const auto p_idx = out.add(out_idx, pt);
+    const auto p_dist = out.add(out_dist, pt);
+    if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+    uint8_t *hi = out.call.hi, *di = out.call.di;
+    if (n > 0) {
+      memcpy(hi + i_kps, kps, sizeof(orbx_keypoint) * (size_t)n);
+      memcpy(hi + i_ds, descs, 32 * (size_t)n);
+    }
+    memcpy(hi + i_md, mp_desc, 32 * Pz);
+    memcpy(hi + i_pos, positions, 24 * Pz);
+    for (int t = 0; t < T; ++t) orbx_pose_inverse(kf_poses_wc + 7 * (size_t)t, (double*)(hi + i_cw) + 7 * (size_t)t);   // kf.pose.inverse()
+    memcpy(hi + i_off, kf_feat_offset, 4 * (Tz + 1));
+    if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+    if (int rc = launch_fuse_search(h, cam, (const double*)(di + i_pos), di + i_md, P, (const double*)(di + i_cw), (const int*)(di + i_off),
+                                    (const orbx_keypoint*)(di + i_kps), di + i_ds, T, radius_scale, desc_threshold, out.dev(p_idx), out.dev(p_dist)))
+      return rc;
+    return out.finish(h);
+  });
 }
 
 // ---- extraction + full per-frame path -------------------------------------------------------------------
@@ -732,16 +676,17 @@ int orbx_fuse_search(orbx_handle* h, const orbx_camera* cam, const double* posit
 int orbx_extract_batch_device(orbx_handle* h, const uint8_t* d_images, int n_images, int w, int h_px,
                               size_t stride, orbx_keypoint* d_kp, uint8_t* d_desc, int* d_nkp, int cap_kp) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!d_images || !d_kp || !d_desc || !d_nkp || n_images < 0 || cap_kp < 1)
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_extract_batch_device: bad argument");
-  if (w < 64 || h_px < 64 || w > h->max_w || h_px > h->max_h || stride < (size_t)w)
-    return orbx_fail(h, ORBX_ERR_INVALID, "image %dx%d (stride %zu) outside the handle's bounds %dx%d", w, h_px,
-                     stride, h->max_w, h->max_h);
-  if (n_images > 2 * h->max_batch)
-    return orbx_fail(h, ORBX_ERR_INVALID, "n_images %d exceeds 2*max_batch %d", n_images, 2 * h->max_batch);
-  ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
-  return launch_orb_extract(h, d_images, n_images, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp);
+  return orbx_guard(h, "orbx_extract_batch_device", [&]() -> int {
+    if (!d_images || !d_kp || !d_desc || !d_nkp || n_images < 0 || cap_kp < 1)
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_extract_batch_device: bad argument");
+    if (w < 64 || h_px < 64 || w > h->max_w || h_px > h->max_h || stride < (size_t)w)
+      return orbx_fail(h, ORBX_ERR_INVALID, "image %dx%d (stride %zu) outside the handle's bounds %dx%d", w, h_px,
+                       stride, h->max_w, h->max_h);
+    if (n_images > 2 * h->max_batch)
+      return orbx_fail(h, ORBX_ERR_INVALID, "n_images %d exceeds 2*max_batch %d", n_images, 2 * h->max_batch);
+    ORBX_HIP(h, hipSetDevice(h->device));
+    return launch_orb_extract(h, d_images, n_images, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp);
+  });
 }
 
 int orbx_process_stereo_batch_device(orbx_handle* h, const uint8_t* d_images, int batch, int w, int h_px,
@@ -749,13 +694,15 @@ int orbx_process_stereo_batch_device(orbx_handle* h, const uint8_t* d_images, in
                                      int cap_kp, orbx_dmatch* d_matches, int* d_nmatches, double* d_points,
                                      uint8_t* d_has_point) {
   if (!h) return ORBX_ERR_INVALID;
-  if (batch < 0 || batch > h->max_batch)
-    return orbx_fail(h, ORBX_ERR_INVALID, "batch %d outside 0..max_batch %d", batch, h->max_batch);
-  if (!d_matches || !d_nmatches || !d_points || !d_has_point)
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch_device: bad argument");
-  if (int rc = orbx_extract_batch_device(h, d_images, 2 * batch, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp))
-    return rc;
-  return launch_stereo_match(h, batch, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point, h->xcd_next_reversed);
+  return orbx_guard(h, "orbx_process_stereo_batch_device", [&]() -> int {
+    if (batch < 0 || batch > h->max_batch)
+      return orbx_fail(h, ORBX_ERR_INVALID, "batch %d outside 0..max_batch %d", batch, h->max_batch);
+    if (!d_matches || !d_nmatches || !d_points || !d_has_point)
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch_device: bad argument");
+    if (int rc = orbx_extract_batch_device(h, d_images, 2 * batch, w, h_px, stride, d_kp, d_desc, d_nkp, cap_kp))
+      return rc;
+    return launch_stereo_match(h, batch, d_kp, d_desc, d_nkp, cap_kp, d_matches, d_nmatches, d_points, d_has_point, h->xcd_next_reversed);
+  });
 }
 
 int orbx_process_stereo(orbx_handle* h, const uint8_t* left, size_t lstride, const uint8_t* right,
@@ -763,89 +710,91 @@ int orbx_process_stereo(orbx_handle* h, const uint8_t* left, size_t lstride, con
                         orbx_keypoint* kpR, uint8_t* descR, int* nR, int cap_kp, orbx_dmatch* matches,
                         int* n_matches, double* points_cam, uint8_t* has_point) {
   if (!h) return ORBX_ERR_INVALID;
-  if (!left || !right || !kpL || !descL || !nL || !kpR || !descR || !nR || !matches || !n_matches ||
-      !points_cam || !has_point || cap_kp < 1 || lstride < (size_t)w || rstride < (size_t)w)
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo: bad argument");
-  ORBX_HIP(h, hipSetDevice(h->device));
-  const size_t img = (size_t)w * h_px, cp = (size_t)cap_kp;
-  // every output of the pair in ONE device block (and one pinned host mirror): a single D2H copy and a single
-  // synchronisation per frame instead of one blocking copy per array
-  const size_t o_pts = 0;                                   // double[cp*3]
-  const size_t o_kp = o_pts + 24 * cp;                      // orbx_keypoint[2*cp]
-  const size_t o_m = o_kp + sizeof(orbx_keypoint) * 2 * cp; // orbx_dmatch[cp]
-  const size_t o_cnt = o_m + sizeof(orbx_dmatch) * cp;      // int nkp[2], nmatches, status
-  const size_t o_desc = o_cnt + 16;                         // u8[2*cp*32]
-  const size_t o_has = o_desc + 64 * cp;                    // u8[cp]
-  const size_t total = (o_has + cp + 63) & ~(size_t)63;
-  if (int rc = orbx_reserve(h, h->ws_io[6], 2 * img)) return rc;
-  if (int rc = orbx_reserve(h, h->ws_io[7], total)) return rc;
-  if (int rc = orbx_reserve_pinned(h, h->pin_stage, total)) return rc;
-  uint8_t* d_img = (uint8_t*)h->ws_io[6].p;
-  uint8_t* d_out = (uint8_t*)h->ws_io[7].p;
-  ORBX_HIP(h, hipMemcpy2DAsync(d_img, w, left, lstride, w, h_px, hipMemcpyHostToDevice, h->stream));
-  ORBX_HIP(h, hipMemcpy2DAsync(d_img + img, w, right, rstride, w, h_px, hipMemcpyHostToDevice, h->stream));
-  int* d_cnt = (int*)(d_out + o_cnt);
-  auto enqueue_device_part = [&]() -> int {
-    if (int rc = orbx_process_stereo_batch_device(h, d_img, 1, w, h_px, (size_t)w, (orbx_keypoint*)(d_out + o_kp), d_out + o_desc,
-                                                  d_cnt, cap_kp, (orbx_dmatch*)(d_out + o_m), d_cnt + 2, (double*)(d_out + o_pts),
-                                                  d_out + o_has))
-      return rc;
-    ORBX_HIP(h, hipMemcpyAsync(d_cnt + 3, h->d_status, sizeof(unsigned), hipMemcpyDeviceToDevice, h->stream));
-    ORBX_HIP(h, hipMemsetAsync(h->d_status, 0, sizeof(unsigned), h->stream));
-    return ORBX_OK;
-  };
-  // The device part (memset + ~20 short kernels) is launch-bound for one pair: after two eager calls with an
-  // unchanged configuration (all workspaces allocated, tables uploaded) it is captured into a hipGraph once and
-  // replayed with a single launch per frame.  ORBX_NO_GRAPH=1 or profiling keeps the eager path.
-  static const bool no_graph = getenv("ORBX_NO_GRAPH") != nullptr;
-  // (the geometry test covers an extract / batch call at another image size in between: it rewrites the tables the
-  // graph's kernels read — orb_prepare_geometry drops the graph itself, this keeps the eager-call count honest too)
-  const bool same = h->pg_w == w && h->pg_h == h_px && h->pg_cap == cap_kp && h->pg_img == (void*)d_img && h->pg_out == (void*)d_out &&
-                    h->geom_w == w && h->geom_h == h_px;
-  if (!same) {
-    if (h->pair_graph) { hipGraphExecDestroy(h->pair_graph); h->pair_graph = nullptr; }
-    h->pg_w = w; h->pg_h = h_px; h->pg_cap = cap_kp; h->pg_img = d_img; h->pg_out = d_out; h->pg_calls = 0;
-  }
-  if (no_graph || h->profiling) {
-    if (int rc = enqueue_device_part()) return rc;
-  } else if (h->pair_graph) {
-    ORBX_HIP(h, hipGraphLaunch(h->pair_graph, h->stream));
-  } else if (h->pg_calls < 2) {
-    ++h->pg_calls;
-    if (int rc = enqueue_device_part()) return rc;
-  } else {
-    hipGraph_t graph = nullptr;
-    ORBX_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_device_part();
-    const hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (rc != ORBX_OK || e != hipSuccess || !graph) {
-      if (graph) hipGraphDestroy(graph);
-      h->pg_calls = -1000000;      // capture is not possible here: stay eager
-      (void)hipGetLastError();
-      if (int rc2 = enqueue_device_part()) return rc2;
-    } else {
-      const hipError_t ei = hipGraphInstantiate(&h->pair_graph, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-      if (ei != hipSuccess) { h->pair_graph = nullptr; h->pg_calls = -1000000; (void)hipGetLastError(); if (int rc2 = enqueue_device_part()) return rc2; }
-      else ORBX_HIP(h, hipGraphLaunch(h->pair_graph, h->stream));
+  return orbx_guard(h, "orbx_process_stereo", [&]() -> int {
+    if (!left || !right || !kpL || !descL || !nL || !kpR || !descR || !nR || !matches || !n_matches ||
+        !points_cam || !has_point || cap_kp < 1 || lstride < (size_t)w || rstride < (size_t)w)
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo: bad argument");
+    ORBX_HIP(h, hipSetDevice(h->device));
+    const size_t img = (size_t)w * h_px, cp = (size_t)cap_kp;
+    // every output of the pair in ONE device block (and one pinned host mirror): a single D2H copy and a single
+    // synchronisation per frame instead of one blocking copy per array
+    const size_t o_pts = 0;                                   // double[cp*3]
+    const size_t o_kp = o_pts + 24 * cp;                      // orbx_keypoint[2*cp]
+    const size_t o_m = o_kp + sizeof(orbx_keypoint) * 2 * cp; // orbx_dmatch[cp]
+    const size_t o_cnt = o_m + sizeof(orbx_dmatch) * cp;      // int nkp[2], nmatches, status
+    const size_t o_desc = o_cnt + 16;                         // u8[2*cp*32]
+    const size_t o_has = o_desc + 64 * cp;                    // u8[cp]
+    const size_t total = (o_has + cp + 63) & ~(size_t)63;
+    if (int rc = orbx_reserve(h, h->ws_io.pair_images, 2 * img)) return rc;
+    if (int rc = orbx_reserve(h, h->ws_io.pair_out, total)) return rc;
+    if (int rc = orbx_reserve_pinned(h, h->pin_stage, total)) return rc;
+    uint8_t* d_img = (uint8_t*)h->ws_io.pair_images.p;
+    uint8_t* d_out = (uint8_t*)h->ws_io.pair_out.p;
+    ORBX_HIP(h, hipMemcpy2DAsync(d_img, w, left, lstride, w, h_px, hipMemcpyHostToDevice, h->stream));
+    ORBX_HIP(h, hipMemcpy2DAsync(d_img + img, w, right, rstride, w, h_px, hipMemcpyHostToDevice, h->stream));
+    int* d_cnt = (int*)(d_out + o_cnt);
+    auto enqueue_device_part = [&]() -> int {
+      if (int rc = orbx_process_stereo_batch_device(h, d_img, 1, w, h_px, (size_t)w, (orbx_keypoint*)(d_out + o_kp), d_out + o_desc,
+                                                    d_cnt, cap_kp, (orbx_dmatch*)(d_out + o_m), d_cnt + 2, (double*)(d_out + o_pts),
+                                                    d_out + o_has))
+        return rc;
+      ORBX_HIP(h, hipMemcpyAsync(d_cnt + 3, h->d_status, sizeof(unsigned), hipMemcpyDeviceToDevice, h->stream));
+      ORBX_HIP(h, hipMemsetAsync(h->d_status, 0, sizeof(unsigned), h->stream));
+      return ORBX_OK;
+    };
+    // The device part (memset + ~20 short kernels) is launch-bound for one pair: after two eager calls with an
+    // unchanged configuration (all workspaces allocated, tables uploaded) it is captured into a hipGraph once and
+    // replayed with a single launch per frame.  ORBX_NO_GRAPH=1 or profiling keeps the eager path.
+    static const bool no_graph = getenv("ORBX_NO_GRAPH") != nullptr;
+    // (the geometry test covers an extract / batch call at another image size in between: it rewrites the tables the
+    // graph's kernels read — orb_prepare_geometry drops the graph itself, this keeps the eager-call count honest too)
+    const bool same = h->pg_w == w && h->pg_h == h_px && h->pg_cap == cap_kp && h->pg_img == (void*)d_img && h->pg_out == (void*)d_out &&
+                      h->geom_w == w && h->geom_h == h_px;
+    if (!same) {
+      if (h->pair_graph) { hipGraphExecDestroy(h->pair_graph); h->pair_graph = nullptr; }
+      h->pg_w = w; h->pg_h = h_px; h->pg_cap = cap_kp; h->pg_img = d_img; h->pg_out = d_out; h->pg_calls = 0;
     }
-  }
-  ORBX_HIP(h, hipMemcpyAsync(h->pin_stage.p, d_out, total, hipMemcpyDeviceToHost, h->stream));
-  ORBX_HIP(h, hipStreamSynchronize(h->stream));
-  const uint8_t* S = (const uint8_t*)h->pin_stage.p;
-  const int* cnt = (const int*)(S + o_cnt);
-  const unsigned st = (unsigned)cnt[3];
-  if (st & ORBX_ST_KP_OVERFLOW) return orbx_fail(h, ORBX_ERR_CAPACITY, "an image produced more keypoints than cap_kp");
-  if (st) return orbx_fail(h, ORBX_ERR_HIP, "device status 0x%x", st);
-  *nL = cnt[0]; *nR = cnt[1]; *n_matches = cnt[2];
-  memcpy(kpL, S + o_kp, sizeof(orbx_keypoint) * (size_t)cnt[0]);
-  memcpy(kpR, S + o_kp + sizeof(orbx_keypoint) * cp, sizeof(orbx_keypoint) * (size_t)cnt[1]);
-  memcpy(descL, S + o_desc, 32 * (size_t)cnt[0]);
-  memcpy(descR, S + o_desc + 32 * cp, 32 * (size_t)cnt[1]);
-  memcpy(matches, S + o_m, sizeof(orbx_dmatch) * (size_t)cnt[2]);
-  memcpy(points_cam, S + o_pts, 24 * (size_t)cnt[0]);
-  memcpy(has_point, S + o_has, (size_t)cnt[0]);
-  return ORBX_OK;
+    if (no_graph || h->profiling) {
+      if (int rc = enqueue_device_part()) return rc;
+    } else if (h->pair_graph) {
+      ORBX_HIP(h, hipGraphLaunch(h->pair_graph, h->stream));
+    } else if (h->pg_calls < 2) {
+      ++h->pg_calls;
+      if (int rc = enqueue_device_part()) return rc;
+    } else {
+      hipGraph_t graph = nullptr;
+      ORBX_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+      const int rc = enqueue_device_part();
+      const hipError_t e = hipStreamEndCapture(h->stream, &graph);
+      if (rc != ORBX_OK || e != hipSuccess || !graph) {
+        if (graph) hipGraphDestroy(graph);
+        h->pg_calls = -1000000;      // capture is not possible here: stay eager
+        (void)hipGetLastError();
+        if (int rc2 = enqueue_device_part()) return rc2;
+      } else {
+        const hipError_t ei = hipGraphInstantiate(&h->pair_graph, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ei != hipSuccess) { h->pair_graph = nullptr; h->pg_calls = -1000000; (void)hipGetLastError(); if (int rc2 = enqueue_device_part()) return rc2; }
+        else ORBX_HIP(h, hipGraphLaunch(h->pair_graph, h->stream));
+      }
+    }
+    ORBX_HIP(h, hipMemcpyAsync(h->pin_stage.p, d_out, total, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP(h, hipStreamSynchronize(h->stream));
+    const uint8_t* S = (const uint8_t*)h->pin_stage.p;
+    const int* cnt = (const int*)(S + o_cnt);
+    const unsigned st = (unsigned)cnt[3];
+    if (st & ORBX_ST_KP_OVERFLOW) return orbx_fail(h, ORBX_ERR_CAPACITY, "an image produced more keypoints than cap_kp");
+    if (st) return orbx_fail(h, ORBX_ERR_HIP, "device status 0x%x", st);
+    *nL = cnt[0]; *nR = cnt[1]; *n_matches = cnt[2];
+    memcpy(kpL, S + o_kp, sizeof(orbx_keypoint) * (size_t)cnt[0]);
+    memcpy(kpR, S + o_kp + sizeof(orbx_keypoint) * cp, sizeof(orbx_keypoint) * (size_t)cnt[1]);
+    memcpy(descL, S + o_desc, 32 * (size_t)cnt[0]);
+    memcpy(descR, S + o_desc + 32 * cp, 32 * (size_t)cnt[1]);
+    memcpy(matches, S + o_m, sizeof(orbx_dmatch) * (size_t)cnt[2]);
+    memcpy(points_cam, S + o_pts, 24 * (size_t)cnt[0]);
+    memcpy(has_point, S + o_has, (size_t)cnt[0]);
+    return ORBX_OK;
+  });
 }
 
 void* orbx_host_alloc(size_t bytes) {
@@ -858,54 +807,56 @@ int orbx_process_stereo_batch(orbx_handle* h, const uint8_t* images, int batch, 
                               orbx_keypoint* kp, uint8_t* desc, int* nkp, int cap_kp, orbx_dmatch* matches, int* nmatches,
                               double* points, uint8_t* has_point) {
   if (!h) return ORBX_ERR_INVALID;
-  if (batch < 0 || cap_kp < 1 || !images || !kp || !desc || !nkp || !matches || !nmatches || !points || !has_point ||
-      stride < (size_t)w)
-    return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch: bad argument");
-  if (batch == 0) return ORBX_OK;
-  ORBX_HIP(h, hipSetDevice(h->device));
-  if (!h->s_in) {
-    ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-    ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_in[i], hipEventDisableTiming));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_comp[i], hipEventDisableTiming));
-      ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_out[i], hipEventDisableTiming));
+  return orbx_guard(h, "orbx_process_stereo_batch", [&]() -> int {
+    if (batch < 0 || cap_kp < 1 || !images || !kp || !desc || !nkp || !matches || !nmatches || !points || !has_point ||
+        stride < (size_t)w)
+      return orbx_fail(h, ORBX_ERR_INVALID, "orbx_process_stereo_batch: bad argument");
+    if (batch == 0) return ORBX_OK;
+    ORBX_HIP(h, hipSetDevice(h->device));
+    if (!h->s_in) {
+      ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
+      ORBX_HIP(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
+      for (int i = 0; i < 2; ++i) {
+        ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_in[i], hipEventDisableTiming));
+        ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_comp[i], hipEventDisableTiming));
+        ORBX_HIP(h, hipEventCreateWithFlags(&h->ev_out[i], hipEventDisableTiming));
+      }
     }
-  }
-  const int C = h->max_batch < 32 ? h->max_batch : 32;   // pairs per chunk
-  const size_t img_b = (size_t)h_px * stride * 2;          // one pair
-  const size_t sz[8] = {img_b * C, sizeof(orbx_keypoint) * 2 * (size_t)cap_kp * C, 64 * (size_t)cap_kp * C, sizeof(int) * 2 * (size_t)C,
-                        sizeof(orbx_dmatch) * (size_t)cap_kp * C, sizeof(int) * (size_t)C, 24 * (size_t)cap_kp * C, (size_t)cap_kp * C};
-  for (int b = 0; b < 2; ++b)
-    for (int i = 0; i < 8; ++i) if (int rc = orbx_reserve(h, h->ws_pipe[b][i], sz[i])) return rc;
-  // workspaces of the extractor are sized before the pipeline starts (orbx_reserve may synchronise)
-  const int n_chunks = (batch + C - 1) / C;
-  for (int c = 0; c < n_chunks; ++c) {
-    const int b = c & 1, p0 = c * C, np = (batch - p0 < C) ? batch - p0 : C;
-    DevBuf* d = h->ws_pipe[b];
-    if (c >= 2) ORBX_HIP(h, hipStreamWaitEvent(h->s_in, h->ev_comp[b], 0));    // image buffer b is free again
-    ORBX_HIP(h, hipMemcpyAsync(d[0].p, images + (size_t)p0 * img_b, img_b * np, hipMemcpyHostToDevice, h->s_in));
-    ORBX_HIP(h, hipEventRecord(h->ev_in[b], h->s_in));
-    ORBX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_in[b], 0));
-    if (c >= 2) ORBX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_out[b], 0));  // output buffers b have been downloaded
-    if (int rc = orbx_process_stereo_batch_device(h, (const uint8_t*)d[0].p, np, w, h_px, stride, (orbx_keypoint*)d[1].p,
-                                                  (uint8_t*)d[2].p, (int*)d[3].p, cap_kp, (orbx_dmatch*)d[4].p, (int*)d[5].p,
-                                                  (double*)d[6].p, (uint8_t*)d[7].p))
-      return rc;
-    ORBX_HIP(h, hipEventRecord(h->ev_comp[b], h->stream));
-    ORBX_HIP(h, hipStreamWaitEvent(h->s_out, h->ev_comp[b], 0));
-    const size_t cp = (size_t)cap_kp;
-    ORBX_HIP(h, hipMemcpyAsync(kp + 2 * cp * p0, d[1].p, sizeof(orbx_keypoint) * 2 * cp * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(desc + 64 * cp * p0, d[2].p, 64 * cp * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(nkp + 2 * (size_t)p0, d[3].p, sizeof(int) * 2 * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(matches + cp * p0, d[4].p, sizeof(orbx_dmatch) * cp * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(nmatches + p0, d[5].p, sizeof(int) * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(points + 3 * cp * p0, d[6].p, 24 * cp * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipMemcpyAsync(has_point + cp * p0, d[7].p, cp * np, hipMemcpyDeviceToHost, h->s_out));
-    ORBX_HIP(h, hipEventRecord(h->ev_out[b], h->s_out));
-  }
-  ORBX_HIP(h, hipStreamSynchronize(h->s_out));
-  return orbx_check_status(h);
+    const int C = h->max_batch < 32 ? h->max_batch : 32;   // pairs per chunk
+    const size_t img_b = (size_t)h_px * stride * 2;          // one pair
+    const size_t sz[8] = {img_b * C, sizeof(orbx_keypoint) * 2 * (size_t)cap_kp * C, 64 * (size_t)cap_kp * C, sizeof(int) * 2 * (size_t)C,
+                          sizeof(orbx_dmatch) * (size_t)cap_kp * C, sizeof(int) * (size_t)C, 24 * (size_t)cap_kp * C, (size_t)cap_kp * C};
+    for (int b = 0; b < 2; ++b)
+      for (int i = 0; i < 8; ++i) if (int rc = orbx_reserve(h, h->ws_pipe[b][i], sz[i])) return rc;
+    // workspaces of the extractor are sized before the pipeline starts (orbx_reserve may synchronise)
+    const int n_chunks = (batch + C - 1) / C;
+    for (int c = 0; c < n_chunks; ++c) {
+      const int b = c & 1, p0 = c * C, np = (batch - p0 < C) ? batch - p0 : C;
+      DevBuf* d = h->ws_pipe[b];
+      if (c >= 2) ORBX_HIP(h, hipStreamWaitEvent(h->s_in, h->ev_comp[b], 0));    // image buffer b is free again
+      ORBX_HIP(h, hipMemcpyAsync(d[0].p, images + (size_t)p0 * img_b, img_b * np, hipMemcpyHostToDevice, h->s_in));
+      ORBX_HIP(h, hipEventRecord(h->ev_in[b], h->s_in));
+      ORBX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_in[b], 0));
+      if (c >= 2) ORBX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_out[b], 0));  // output buffers b have been downloaded
+      if (int rc = orbx_process_stereo_batch_device(h, (const uint8_t*)d[0].p, np, w, h_px, stride, (orbx_keypoint*)d[1].p,
+                                                    (uint8_t*)d[2].p, (int*)d[3].p, cap_kp, (orbx_dmatch*)d[4].p, (int*)d[5].p,
+                                                    (double*)d[6].p, (uint8_t*)d[7].p))
+        return rc;
+      ORBX_HIP(h, hipEventRecord(h->ev_comp[b], h->stream));
+      ORBX_HIP(h, hipStreamWaitEvent(h->s_out, h->ev_comp[b], 0));
+      const size_t cp = (size_t)cap_kp;
+      ORBX_HIP(h, hipMemcpyAsync(kp + 2 * cp * p0, d[1].p, sizeof(orbx_keypoint) * 2 * cp * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(desc + 64 * cp * p0, d[2].p, 64 * cp * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(nkp + 2 * (size_t)p0, d[3].p, sizeof(int) * 2 * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(matches + cp * p0, d[4].p, sizeof(orbx_dmatch) * cp * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(nmatches + p0, d[5].p, sizeof(int) * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(points + 3 * cp * p0, d[6].p, 24 * cp * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipMemcpyAsync(has_point + cp * p0, d[7].p, cp * np, hipMemcpyDeviceToHost, h->s_out));
+      ORBX_HIP(h, hipEventRecord(h->ev_out[b], h->s_out));
+    }
+    ORBX_HIP(h, hipStreamSynchronize(h->s_out));
+    return orbx_check_status(h);
+  });
 }
 
 // ---- local BA ---------------------------------------------------------------------------------------------
@@ -1043,7 +994,6 @@ int orbx_ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_c
       (N > 0 && !obs))
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual: bad argument");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return orbx_guard(h, "orbx_ba_solve_visual", [&]() -> int {
     return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations, initial_error, final_error);
   });
@@ -1061,7 +1011,6 @@ int orbx_ba_solve_visual_obs32(orbx_handle* h, const orbx_camera* cam, const orb
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32: bad argument");
   if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32: the partitioned solve takes orbx_ba_obs (orbx_ba_solve_visual)");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return orbx_guard(h, "orbx_ba_solve_visual_obs32", [&]() -> int {
     return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, nullptr, obs32);
   });
@@ -1079,7 +1028,6 @@ int orbx_ba_solve_visual_obs32_device(orbx_handle* h, const orbx_camera* cam, co
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32_device: bad argument (d_obs32 is 16-byte aligned)");
   if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "orbx_ba_solve_visual_obs32_device: the partitioned solve reads its observations on the host (orbx_ba_solve_visual)");
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return orbx_guard(h, "orbx_ba_solve_visual_obs32_device", [&]() -> int {
     return ba_solve_visual(h, cam, cfg, K, poses_cw, F, fixed_poses_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, false, nullptr, d_obs32, true);
   });
@@ -1103,7 +1051,6 @@ int orbx_ba_solve_visual_batch(orbx_handle* h, const orbx_camera* cam, const orb
                        &q.initial_error, &q.final_error, ORBX_OK, q.obs32};
     }
     ORBX_HIP(h, hipSetDevice(h->device));
-    orbx_prof_begin_call(h);
     orbx_allreduce_fn saved = h->allreduce;          // independent windows: no collective
     void* saved_comm = h->rccl_comm;
     h->allreduce = nullptr; h->rccl_comm = nullptr;
@@ -1205,7 +1152,6 @@ int orbx_ba_solve_inertial(orbx_handle* h, const orbx_camera* cam, const orbx_in
   *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
   if (K < 2) return orbx_fail(h, ORBX_ERR_EMPTY, "inertial BA needs two keyframes in the window");   // local_inertial_ba.rs:1080-1082
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
   BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
   return orbx_guard(h, "orbx_ba_solve_inertial", [&]() -> int {
@@ -1229,7 +1175,6 @@ static int ba_solve_inertial_obs32(orbx_handle* h, const char* who, const orbx_c
   *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
   if (K < 2) return orbx_fail(h, ORBX_ERR_EMPTY, "inertial BA needs two keyframes in the window");   // local_inertial_ba.rs:1080-1082
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   orbx_ba_config vc{cfg->max_iterations, 0.0, 1e-8, cfg->huber_threshold_mono, 0};
   BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
   return orbx_guard(h, who, [&]() -> int {
@@ -1266,7 +1211,6 @@ int orbx_ba_solve_global(orbx_handle* h, const orbx_camera* cam, const orbx_ba_c
   *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
   if (K < 1 || M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "global BA needs two keyframes and a map point");   // global_ba.rs:194-196
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return orbx_guard(h, "orbx_ba_solve_global", [&]() -> int {
     return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, obs, should_stop, user, poses_wc_out, iterations, initial_error, final_error, true);
   });
@@ -1284,7 +1228,6 @@ int orbx_ba_solve_global_obs32(orbx_handle* h, const orbx_camera* cam, const orb
   *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
   if (K < 1 || M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "global BA needs two keyframes and a map point");   // global_ba.rs:194-196
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return orbx_guard(h, "orbx_ba_solve_global_obs32", [&]() -> int {
     return ba_solve_visual(h, cam, cfg, K, poses_cw, 1, fixed_pose_cw, M, points, N, nullptr, should_stop, user, poses_wc_out, iterations, initial_error, final_error, true, nullptr, obs32);
   });

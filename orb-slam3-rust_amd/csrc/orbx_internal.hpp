@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdarg>
@@ -217,6 +218,24 @@ struct MapWorkspaces {
 };
 static_assert(sizeof(MapWorkspaces) == 16 * sizeof(DevBuf), "MapWorkspaces::for_each lists every member");
 
+// The grow-only workspaces of the single-problem matchers and searches (orbx_api.hip, keyframe.hip, bow_kernels.hip,
+// triangulate_kernels.hip), one per role.  A host form holds host_blob from its upload to its download; whatever it calls in between
+// owns another member.
+struct IoWorkspaces {
+  DevBuf host_blob;       // every single-problem host form's input / output blob: orbx_stereo_match, orbx_hamming_match_crosscheck, orbx_hamming_batch, orbx_guided_match, orbx_search_for_triangulation[_bow], orbx_fuse_search, orbx_triangulate_pairs, orbx_bow_transform, orbx_bow_vectors and the orbx_keyframe_* searches (shared by all of them: a host form waits for its download before it returns, and none calls another host form)
+  DevBuf fuse_poses;      // orbx_fuse_search_device: the inverse keyframe poses, up through ring_io (its callers orbx_fuse_search and orbx_keyframe_fuse_search hold host_blob and kf_gather)
+  DevBuf bow_scratch;     // orbx_bow_vectors_device: word, leaf, node and weight per descriptor (its caller orbx_bow_vectors holds host_blob)
+  DevBuf nb_scratch;      // orbx_keyframe_triangulate_from_neighbors: the searches' scratch, pair status and points (tri_nb_plan's ws_bytes); its tables and lists are in host_blob
+  DevBuf kf_gather;       // orbx_keyframe_fuse_search: the target keyframes' features side by side (device-to-device; never leaves the device)
+  DevBuf pair_images;     // orbx_process_stereo: the image pair
+  DevBuf pair_out;        // orbx_process_stereo: the pair's output block (mirrored by pin_stage; both addresses are part of the captured graph)
+  template <class F>
+  void for_each(F&& f) {   // every member, so that orbx_destroy frees what is added here
+    for (DevBuf* b : {&host_blob, &fuse_poses, &bow_scratch, &nb_scratch, &kf_gather, &pair_images, &pair_out}) f(*b);
+  }
+};
+static_assert(sizeof(IoWorkspaces) == 7 * sizeof(DevBuf), "IoWorkspaces::for_each lists every member");
+
 struct KernelTimer {
   std::string name;
   std::vector<hipEvent_t> ev;  // start/stop pairs of the current call
@@ -251,7 +270,10 @@ struct orbx_handle {
   bool xcd_next_reversed = false;                  // set by launch_orb_extract: the image order of the launch after its last one (the matcher's, in orbx_process_stereo_batch_device)
   int last_n_images = 0;                           // orbx_debug_read_level(which = 1) blurs them on demand (the product path keeps no blurred pyramid)
   // grow-only workspaces
-  DevBuf ws_pyr, ws_blur, ws_cand, ws_counters, ws_sel, ws_sel2, ws_match, ws_io[12];
+  DevBuf ws_pyr, ws_blur, ws_cand, ws_counters, ws_sel, ws_sel2, ws_match;
+  IoWorkspaces ws_io;                    // the single-problem matchers and searches, and orbx_process_stereo's two blocks
+  PinnedBuf pin_io;                      // pinned staging of the single-problem host forms (one upload, one download)
+  UploadRing ring_io;                    // orbx_fuse_search_device's inverse poses on their way to ws_io.fuse_poses
   DevBuf ws_dtile;                       // [image][describe tile] (begin, end) inside the level's spatially ordered keypoint list (rank_select_kernel)
   DevBuf ws_ba_in, ws_ba_arena, ws_ba_out;   // ba_solve_batch: input blob (descriptors, states, parameters | observations), scratch arena, output blob
   DevBuf ws_ba_imu, ws_ba_s15;             // ... inertial: IMU edges, preintegrations and records; the 15-d reduced system
@@ -326,6 +348,13 @@ struct orbx_keyframe {
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
 // The body of an extern "C" entry point: no C++ exception may cross the C boundary (ctypes, Rust); h == nullptr: the code alone.
+// Every entry point that can allocate host memory runs inside it.  Left bare, because they allocate none: getters, destroy / close
+// and default-configuration calls, orbx_vocab_nodes, orbx_bow_score, orbx_keyframe_set_pose / get_map_points / download, the thin
+// wrappers of guarded calls (orbx_kfdb_detect_loop_candidates, orbx_pose_inertial_optimize, orbx_ba_solve_inertial_obs32[_device]),
+// and among the single-problem matchers and searches orbx_stereo_match[_batch_device], orbx_hamming_match_crosscheck[_device],
+// orbx_hamming_batch[_device], orbx_guided_match[_device], orbx_search_for_triangulation[_device] and orbx_triangulate_pairs[_device]:
+// their tables are made in pinned staging.  (orbx_search_for_triangulation_bow sorts, orbx_fuse_search[_device] and the extraction
+// calls may grow host tables: guarded.)
 template <class F>
 int orbx_guard(orbx_handle* h, const char* who, F&& body) noexcept {
   try {
@@ -334,6 +363,38 @@ int orbx_guard(orbx_handle* h, const char* who, F&& body) noexcept {
     return h ? orbx_fail(h, ORBX_ERR_HIP, "%s: out of host memory", who) : (int)ORBX_ERR_HIP;
   } catch (...) {
     return h ? orbx_fail(h, ORBX_ERR_HIP, "%s: unexpected C++ exception", who) : (int)ORBX_ERR_HIP;
+  }
+}
+// pose.inverse() of a T_wc given as (qw, qx, qy, qz, tx, ty, tz): se3.rs:56-63 with nalgebra's quaternion-vector product, one IEEE
+// operation at a time (include/orbx.hpp's se3_inverse)
+inline void orbx_pose_inverse(const double* p, double* out) {
+  const double w = p[0], x = -p[1], y = -p[2], z = -p[3];
+  const double* v = p + 4;
+  const double t[3] = {2.0 * (y * v[2] - z * v[1]), 2.0 * (z * v[0] - x * v[2]), 2.0 * (x * v[1] - y * v[0])};
+  const double c[3] = {y * t[2] - z * t[1], z * t[0] - x * t[2], x * t[1] - y * t[0]};
+  out[0] = w; out[1] = x; out[2] = y; out[3] = z;
+  for (int i = 0; i < 3; ++i) out[4 + i] = -(t[i] * w + c[i] + v[i]);
+}
+// A FeatureVector given as one node id per feature, as one sorted array: sorted [n] receives the feature indices by (node, index)
+// ascending, which is every node's list in push order (vocabulary/mod.rs:309); the features in no list (node 0xffffffff) sort last and
+// are cut off: the answer is how many remain.
+inline int orbx_sort_by_node(const uint32_t* node, int n, int* sorted) {
+  for (int i = 0; i < n; ++i) sorted[i] = i;
+  std::stable_sort(sorted, sorted + n, [&](int a, int b) { return node[a] < node[b]; });
+  int m = n;
+  while (m > 0 && node[sorted[m - 1]] == 0xffffffffu) --m;
+  return m;
+}
+// ... and for every feature i of keyframe 1 the range [lo[i], hi[i]) of sorted [m] that holds keyframe 2's features in feature i's
+// node (triangulation.rs:577-581); empty (0, 0) where feature i is in no list
+inline void orbx_node_ranges(const uint32_t* node1, int n1, const uint32_t* node2, const int* sorted, int m, int* lo, int* hi) {
+  for (int i = 0; i < n1; ++i) {
+    lo[i] = hi[i] = 0;
+    const uint32_t key = node1[i];
+    if (key == 0xffffffffu) continue;
+    const int* b = std::lower_bound(sorted, sorted + m, key, [&](int a, uint32_t k) { return node2[a] < k; });
+    const int* e = std::upper_bound(b, sorted + m, key, [&](uint32_t k, int a) { return k < node2[a]; });
+    lo[i] = (int)(b - sorted); hi[i] = (int)(e - sorted);
   }
 }
 int orbx_reserve(orbx_handle* h, DevBuf& b, size_t bytes);
@@ -451,8 +512,6 @@ inline void orbx_launch(orbx_handle* h, const char* label, bool chained, Kernel 
   ProfScope ps(h, label, chained);
   hipLaunchKernelGGL(kernel, grid, block, lds_bytes, h->stream, args...);
 }
-void orbx_prof_begin_call(orbx_handle* h);
-void orbx_prof_end_call(orbx_handle* h);
 
 // ---- kernel launchers (defined in the .hip files) --------------------------------------------------
 // matcher (match_kernels.hip)

@@ -487,7 +487,6 @@ int orbx_pnp_ransac_batch_device(orbx_handle* h, const orbx_camera* cam, const o
     return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pnp_ransac_batch_device: bad argument");
   if (n_problems == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  orbx_prof_begin_call(h);
   return pnp_launch(h, cam, cfg, n_problems, max_n, d_offsets, d_pts3d, d_pts2d, d_priors_wc, d_poses_wc_out, d_inlier_out, d_err_out, d_results);
 }
 
@@ -516,7 +515,6 @@ int orbx_pnp_ransac_batch(orbx_handle* h, const orbx_camera* cam, const orbx_pnp
   std::memcpy(hi + o_pr, priors_wc, 56 * P);
   if (N) std::memcpy(hi + o_p2, pts2d, 8 * N);
   if (int rc = orbx_host_call_upload(h, c)) return rc;
-  orbx_prof_begin_call(h);
   if (int rc = pnp_launch(h, cam, cfg, n_problems, max_n, (const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2),
                           (const double*)(di + o_pr), (double*)(dout + o_po), dout + o_in, (double*)(dout + o_er),
                           (orbx_pnp_result*)(dout + o_rs)))

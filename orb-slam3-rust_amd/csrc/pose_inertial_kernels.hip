@@ -340,7 +340,6 @@ int orbx_pose_inertial_batch_device(orbx_handle* h, const orbx_camera* cam, cons
       return orbx_fail(h, ORBX_ERR_INVALID, "orbx_pose_inertial_batch_device: bad argument");
     if (n_problems == 0) return ORBX_OK;
     ORBX_HIP(h, hipSetDevice(h->device));
-    orbx_prof_begin_call(h);
     const PiArgs a{d_offsets, d_pts3d, d_pts2d, d_is_stereo, d_poses_wc, d_velocities, d_biases, d_prev_kf_poses_wc, d_prev_kf_velocities,
                    d_preints, d_poses_out, d_velocities_out, d_biases_out, d_inlier_out, d_results};
     return pi_launch(h, cam, cfg, n_problems, a);
@@ -384,7 +383,6 @@ int orbx_pose_inertial_batch(orbx_handle* h, const orbx_camera* cam, const orbx_
     std::memcpy(hi + o_pr, preints, 88 * P);
     if (N) { std::memcpy(hi + o_p2, pts2d, 8 * N); std::memcpy(hi + o_st, is_stereo, N); }
     if (int rc = orbx_host_call_upload(h, c)) return rc;
-    orbx_prof_begin_call(h);
     const PiArgs a{(const int*)(di + o_off), (const double*)(di + o_p3), (const float*)(di + o_p2), di + o_st, (const double*)(di + o_po),
                    (const double*)(di + o_ve), (const double*)(di + o_bi), (const double*)(di + o_pp), (const double*)(di + o_pv),
                    (const double*)(di + o_pr), (double*)(dout + d_po), (double*)(dout + d_ve), (double*)(dout + d_bi), dout + d_in,

@@ -213,7 +213,6 @@ int orbx_track_frames_device(orbx_handle* h, const orbx_camera* cam, const orbx_
   A.search_poses = d_search_poses_wc; A.priors = d_priors_wc;
   A.offsets = d_offsets; A.pts3d = d_pts3d; A.pts2d = d_pts2d; A.mp_idx = d_mp_idx; A.feat_idx = d_feat_idx;
   A.poses_out = d_poses_wc_out; A.matched = d_matched; A.results = d_results;
-  orbx_prof_begin_call(h);
   return track_launch(h, cam, cfg, pnp_cfg, B, max_mp, (size_t)M, A, d_inlier_out, d_err_out, d_pnp_results);
 }
 
@@ -261,7 +260,6 @@ int orbx_track_frames(orbx_handle* h, const orbx_camera* cam, const orbx_track_c
   A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2); A.mp_idx = (int*)(dout + o_mi);
   A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps); A.matched = (int*)(dout + o_ma);
   A.results = (orbx_track_result*)(dout + o_rs);
-  orbx_prof_begin_call(h);
   if (int rc = track_launch(h, cam, cfg, pnp_cfg, n_frames, max_mp, M, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn)))
     return rc;
   if (int rc = orbx_host_call_download(h, c, out.off)) return rc;

@@ -252,7 +252,6 @@ int track_reference_enqueue(orbx_handle* h, const char* who, const orbx_camera* 
   A.priors = d_priors_wc;
   A.matches = d_matches; A.offsets = d_offsets; A.pts3d = d_pts3d; A.pts2d = d_pts2d; A.kf_idx = d_kf_idx; A.feat_idx = d_feat_idx;
   A.poses_out = d_poses_wc_out; A.results = d_results;
-  orbx_prof_begin_call(h);
   return tref_launch(h, cam, pnp_cfg, B, max_kf, K, A, d_inlier_out, d_err_out, d_pnp_results);
 }
 
@@ -333,7 +332,6 @@ int orbx_track_reference(orbx_handle* h, const orbx_camera* cam, const orbx_pnp_
     A.matches = (orbx_dmatch*)(dout + o_ma); A.offsets = (int*)(dout + o_of); A.pts3d = (double*)(dout + o_p3); A.pts2d = (float*)(dout + o_p2);
     A.kf_idx = (int*)(dout + o_ki); A.feat_idx = (int*)(dout + o_fi); A.poses_out = (double*)(dout + o_ps);
     A.results = (orbx_track_ref_result*)(dout + o_rs);
-    orbx_prof_begin_call(h);
     if (int rc = tref_launch(h, cam, pnp_cfg, n_frames, max_kf, K, A, dout + o_in, (double*)(dout + o_er), (orbx_pnp_result*)(dout + o_pn))) return rc;
     if (int rc = orbx_host_call_download(h, c, out.off)) return rc;
     std::memcpy(offsets, ho + o_of, 4 * (B + 1));

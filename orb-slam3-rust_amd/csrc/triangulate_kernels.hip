@@ -254,7 +254,6 @@ int orbx_triangulate_pairs_device(orbx_handle* h, const orbx_camera* cam, const 
   nb.kp2 = d_kp2; nb.pts2 = d_points_cam2; nb.has2 = d_has_point2; nb.n2 = n2;
   memcpy(nb.pose2, pose2_wc, sizeof(nb.pose2));
   nb.pairs = d_pairs; nb.n_pairs_dev = nullptr; nb.n_pairs = n_pairs; nb.out_base = 0;
-  orbx_prof_begin_call(h);
   return launch_triangulate_pairs(h, c, nb, nullptr, 1, n_pairs, d_out_status, d_out_points);
 }
 
@@ -273,42 +272,27 @@ int orbx_triangulate_pairs(orbx_handle* h, const orbx_camera* cam, const orbx_tr
                        pairs[2 * (size_t)i + 1], n1, n2);
   if (n_pairs == 0) return ORBX_OK;
   ORBX_HIP(h, hipSetDevice(h->device));
-  // one block: kp1 | kp2 | pts1 | pts2 | pairs | out_points | has1 | has2 | out_status, each part 16-byte aligned
-  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
   const size_t N1 = (size_t)std::max(n1, 1), N2 = (size_t)std::max(n2, 1), NP = (size_t)n_pairs;
-  const size_t o_kp1 = 0, o_kp2 = up(o_kp1 + sizeof(orbx_keypoint) * N1), o_p1 = up(o_kp2 + sizeof(orbx_keypoint) * N2), o_p2 = up(o_p1 + 24 * N1),
-               o_pr = up(o_p2 + 24 * N2), o_op = up(o_pr + 8 * NP), o_h1 = up(o_op + 24 * NP), o_h2 = up(o_h1 + N1), o_st = up(o_h2 + N2),
-               total = up(o_st + 2 * NP);
-  if (int rc = orbx_reserve(h, h->ws_io[11], total)) return rc;
-  uint8_t* b = (uint8_t*)h->ws_io[11].p;
-  hipStream_t st = h->stream;
-  // the copies read and write the caller's arrays: whatever fails, the stream is drained before the call returns
-  auto run = [&]() -> int {
-    if (n1 > 0) ORBX_HIP(h, hipMemcpyAsync(b + o_kp1, kp1, sizeof(orbx_keypoint) * (size_t)n1, hipMemcpyHostToDevice, st));
-    if (n2 > 0) ORBX_HIP(h, hipMemcpyAsync(b + o_kp2, kp2, sizeof(orbx_keypoint) * (size_t)n2, hipMemcpyHostToDevice, st));
-    if (n1 > 0 && points_cam1) {
-      ORBX_HIP(h, hipMemcpyAsync(b + o_p1, points_cam1, 24 * (size_t)n1, hipMemcpyHostToDevice, st));
-      ORBX_HIP(h, hipMemcpyAsync(b + o_h1, has_point1, (size_t)n1, hipMemcpyHostToDevice, st));
-    }
-    if (n2 > 0 && points_cam2) {
-      ORBX_HIP(h, hipMemcpyAsync(b + o_p2, points_cam2, 24 * (size_t)n2, hipMemcpyHostToDevice, st));
-      ORBX_HIP(h, hipMemcpyAsync(b + o_h2, has_point2, (size_t)n2, hipMemcpyHostToDevice, st));
-    }
-    ORBX_HIP(h, hipMemcpyAsync(b + o_pr, pairs, 8 * NP, hipMemcpyHostToDevice, st));
-    if (int rc = orbx_triangulate_pairs_device(h, cam, cfg, is_inertial, (const orbx_keypoint*)(b + o_kp1), points_cam1 ? (const double*)(b + o_p1) : nullptr,
-                                               points_cam1 ? b + o_h1 : nullptr, n1, pose1_wc, (const orbx_keypoint*)(b + o_kp2),
-                                               points_cam2 ? (const double*)(b + o_p2) : nullptr, points_cam2 ? b + o_h2 : nullptr, n2, pose2_wc,
-                                               (const int*)(b + o_pr), n_pairs, (double*)(b + o_op), (uint16_t*)(b + o_st)))
-      return rc;
-    ORBX_HIP(h, hipMemcpyAsync(out_points, b + o_op, 24 * NP, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(h, hipMemcpyAsync(out_status, b + o_st, 2 * NP, hipMemcpyDeviceToHost, st));
-    return ORBX_OK;
-  };
-  const int rc = run();
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (es != hipSuccess) return orbx_fail(h, ORBX_ERR_HIP, "orbx_triangulate_pairs: %s", hipGetErrorString(es));
-  return ORBX_OK;
+  Carve in;
+  const size_t i_kp1 = in.take(sizeof(orbx_keypoint) * N1), i_kp2 = in.take(sizeof(orbx_keypoint) * N2), i_p1 = in.take(24 * N1), i_p2 = in.take(24 * N2),
+               i_pr = in.take(8 * NP), i_h1 = in.take(N1), i_h2 = in.take(N2);
+  OutputPlan out;
+  const auto p_op = out.add(out_points, 3 * NP);
+  const auto p_st = out.add(out_status, NP);
+  if (int rc = out.begin(h, h->pin_io, h->ws_io.host_blob, in.off)) return rc;
+  uint8_t *hi = out.call.hi, *di = out.call.di;
+  if (n1 > 0) memcpy(hi + i_kp1, kp1, sizeof(orbx_keypoint) * (size_t)n1);
+  if (n2 > 0) memcpy(hi + i_kp2, kp2, sizeof(orbx_keypoint) * (size_t)n2);
+  if (n1 > 0 && points_cam1) { memcpy(hi + i_p1, points_cam1, 24 * (size_t)n1); memcpy(hi + i_h1, has_point1, (size_t)n1); }
+  if (n2 > 0 && points_cam2) { memcpy(hi + i_p2, points_cam2, 24 * (size_t)n2); memcpy(hi + i_h2, has_point2, (size_t)n2); }
+  memcpy(hi + i_pr, pairs, 8 * NP);
+  if (int rc = orbx_host_call_upload(h, out.call)) return rc;
+  if (int rc = orbx_triangulate_pairs_device(h, cam, cfg, is_inertial, (const orbx_keypoint*)(di + i_kp1), points_cam1 ? (const double*)(di + i_p1) : nullptr,
+                                             points_cam1 ? di + i_h1 : nullptr, n1, pose1_wc, (const orbx_keypoint*)(di + i_kp2),
+                                             points_cam2 ? (const double*)(di + i_p2) : nullptr, points_cam2 ? di + i_h2 : nullptr, n2, pose2_wc,
+                                             (const int*)(di + i_pr), n_pairs, out.dev(p_op), out.dev(p_st)))
+    return rc;
+  return out.finish(h);
 }
 
 }  // extern "C"

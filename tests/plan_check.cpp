@@ -1,4 +1,4 @@
-// Host-only check of UploadPlan and OutputPlan (orbx_internal.hpp): built and run by tests/test_plans.py, once more under
+// Host-only check of UploadPlan, OutputPlan and the host-only helpers (node sort, node ranges, pose inverse) of orbx_internal.hpp: built and run by tests/test_plans.py, once more under
 // -fsanitize=address,undefined.  The ring, the host-call skeleton and orbx_fail are this program's own: every buffer they hand out is a
 // heap block of exactly the bytes asked for, "device" memory included, so a piece that is placed or copied wrongly is an out-of-bounds
 // access the sanitizer sees, and what travels is compared byte by byte.
@@ -121,9 +121,42 @@ static void output() {
   CHECK(many.begin(nullptr, pin, dev) == ORBX_ERR_HIP && g_call_begins == begins && g_fails == fails + 2);
 }
 
+// orbx_sort_by_node / orbx_node_ranges / orbx_pose_inverse: every array is a heap block of exactly its size
+static void helpers() {
+  const uint32_t none = 0xffffffffu;
+  const uint32_t n2v[7] = {5, none, 2, 5, 2, none, 9};
+  uint32_t* node2 = (uint32_t*)block(sizeof n2v, 0); std::memcpy(node2, n2v, sizeof n2v);
+  int* sorted = (int*)block(7 * sizeof(int), 0x5A);
+  const int m = orbx_sort_by_node(node2, 7, sorted);
+  const int want[7] = {2, 4, 0, 3, 6, 1, 5};                               // by node, then by index; the features in no list last
+  CHECK(m == 5 && std::memcmp(sorted, want, sizeof want) == 0);
+  const uint32_t n1v[5] = {2, none, 7, 9, 5};
+  uint32_t* node1 = (uint32_t*)block(sizeof n1v, 0); std::memcpy(node1, n1v, sizeof n1v);
+  int* lo = (int*)block(5 * sizeof(int), 0x5A); int* hi = (int*)block(5 * sizeof(int), 0x5A);
+  orbx_node_ranges(node1, 5, node2, sorted, m, lo, hi);
+  const int want_lo[5] = {0, 0, 4, 4, 2}, want_hi[5] = {2, 0, 4, 5, 4};   // in no list: (0, 0); node 7 is not in keyframe 2: empty where it would be
+  CHECK(std::memcmp(lo, want_lo, sizeof want_lo) == 0 && std::memcmp(hi, want_hi, sizeof want_hi) == 0);
+  // all in no list, and none at all
+  uint32_t* all_none = (uint32_t*)block(3 * sizeof(uint32_t), 0xFF);
+  CHECK(orbx_sort_by_node(all_none, 3, sorted) == 0 && sorted[0] == 0 && sorted[2] == 2);
+  CHECK(orbx_sort_by_node(all_none, 0, (int*)block(0, 0)) == 0);
+  orbx_node_ranges(node1, 5, all_none, sorted, 0, lo, hi);
+  for (int i = 0; i < 5; ++i) CHECK(lo[i] == 0 && hi[i] == 0);
+  // the inverse of a pose, applied to the pose's translation, is the origin; a quarter turn about z
+  const double r = 0.70710678118654757;
+  const double pv[7] = {r, 0.0, 0.0, r, 1.0, 2.0, 3.0};
+  double* pose = (double*)block(sizeof pv, 0); std::memcpy(pose, pv, sizeof pv);
+  double* inv = (double*)block(7 * sizeof(double), 0);
+  orbx_pose_inverse(pose, inv);
+  CHECK(inv[0] == r && inv[1] == 0.0 && inv[2] == 0.0 && inv[3] == -r);
+  const double want_t[3] = {-2.0, 1.0, -3.0};                              // -(R^T t)
+  for (int i = 0; i < 3; ++i) CHECK(inv[4 + i] > want_t[i] - 1e-15 && inv[4 + i] < want_t[i] + 1e-15);
+}
+
 int main() {
   upload();
   output();
+  helpers();
   for (uint8_t* p : g_blocks) std::free(p);
   std::printf("plans %s\n", bad ? "FAILED" : "ok");
   return bad ? 1 : 0;
