@@ -1093,7 +1093,10 @@ int orbx_keyframe_refresh_map_points(orbx_handle* h, int M, const double* positi
  * orbx_map_track_reference_device = orbx_keyframe_track_reference with kf_positions / kf_valid made on the device from kfs[b]'s slot
  * table and the store: valid[i] = slot[i] >= 0 && live[slot[i]], positions[i] = that slot's position, else zeros.  They are
  * written to d_kf_positions [K][3] / d_kf_valid [K], K = the keyframes' feature counts summed in kfs order (frame b's rows start
- * where the earlier keyframes' end); the other outputs are sized by K as in orbx_track_reference_device. */
+ * where the earlier keyframes' end); the other outputs are sized by K as in orbx_track_reference_device.
+ *
+ * In the four calls above the frame is a grid dimension of the launches: n_frames > 65535 is ORBX_ERR_INVALID before anything is
+ * enqueued, with the store, the tables and the outputs untouched. */
 typedef struct orbx_map_points orbx_map_points;
 enum { ORBX_MAP_SOURCE_KEYFRAMES = 0, ORBX_MAP_SOURCE_SLOTS = 1 };
 int orbx_map_points_create(orbx_handle* h, int capacity, orbx_map_points** out);
@@ -1162,8 +1165,8 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
  * itself).  Every other argument and output is orbx_map_track_frames_device's and equals, byte for byte, that call's on the
  * keyframe lists the specification gives.  list_cap must reach the host-known bound: per frame the reference keyframe's feature
  * count plus the n_best largest of the other keyframes', at most the capacity; for -1 the sum over all keyframes, at most the
- * capacity.  ORBX_ERR_INVALID as above (ref_kf outside [-1, n_kfs)).  orbx_map_track_local: the host form, as orbx_map_track_frames
- * is to its device form (local_kf [n_frames][1 + n_best], may be NULL).
+ * capacity.  ORBX_ERR_INVALID as above (ref_kf outside [-1, n_kfs); n_frames > 65535: the frame is a grid dimension).
+ * orbx_map_track_local: the host form, as orbx_map_track_frames is to its device form (local_kf [n_frames][1 + n_best], may be NULL).
  * Still the caller's: ids, the id -> slot map, is_bad (by leaving keyframes out of kfs[]) and the spanning tree. */
 int orbx_map_covisibility_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int n_queries,
                                  const int* query, int n_best, int* d_weights, int* d_best, int* d_n_best);

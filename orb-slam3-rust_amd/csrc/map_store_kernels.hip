@@ -526,13 +526,16 @@ int ms_set(orbx_map_points* mp, const char* who, const int* slots, int n, const 
   return ORBX_OK;
 }
 
-// Three refusals many calls share: the store (not null, of this handle), the keyframes of a call whose launches have one grid row
-// per keyframe, and the features of a call's keyframes summed (they are numbered in an int).
+// Four refusals many calls share: the store (not null, of this handle), the keyframes and the frames of a call whose launches have one grid row
+// per keyframe or per frame, and the features of a call's keyframes summed (they are numbered in an int).
 int ms_check_store(orbx_handle* h, const char* who, const orbx_map_points* mp) {
   return mp && mp->h == h ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: the store is null or of another handle", who);
 }
 int ms_check_grid_keyframes(orbx_handle* h, const char* who, int n_kfs) {
   return n_kfs <= 0xffff ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 keyframes per call (the keyframe is a grid dimension)", who);
+}
+int ms_check_grid_frames(orbx_handle* h, const char* who, int n_frames) {
+  return n_frames <= 0xffff ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: at most 65535 frames per call (the frame is a grid dimension)", who);
 }
 int ms_check_feature_total(orbx_handle* h, const char* who, long long total) {
   return total <= 0x7fffffff ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_INVALID, "%s: the keyframes hold more than 2^31 - 1 features", who);
@@ -589,6 +592,7 @@ int ms_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int sour
             const int* src_offsets, SelPlan& P) {
   if (int rc = ms_check_store(h, who, mp)) return rc;
   if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
+  if (int rc = ms_check_grid_frames(h, who, B)) return rc;
   if (source != ORBX_MAP_SOURCE_KEYFRAMES && source != ORBX_MAP_SOURCE_SLOTS) return orbx_fail(h, ORBX_ERR_INVALID, "%s: unknown source kind %d", who, source);
   P.n_cand.assign((size_t)B, 0); P.bound_off.assign((size_t)B + 1, 0); P.seg_off.assign((size_t)B + 1, 0);
   long long total = 0;
@@ -781,6 +785,7 @@ struct LocalPlan {
 int local_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int B, int n_kfs, const orbx_keyframe* const* kfs, const int* ref_kf, int n_best,
                LocalPlan& P) {
   if (B <= 0) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_frames must be positive", who);
+  if (int rc = ms_check_grid_frames(h, who, B)) return rc;
   if (int rc = cov_plan(h, who, mp, n_kfs, kfs, n_best, P.C)) return rc;
   if (int rc = cov_check_queries(h, who, "ref_kf", B, ref_kf, n_kfs, -1)) return rc;
   const size_t K = (size_t)n_kfs;
@@ -2682,6 +2687,7 @@ int orbx_map_track_reference_device(orbx_handle* h, const orbx_camera* cam, cons
     if (!cam || min_correspondences < 4 || n_frames < 0 || (n_frames > 0 && !kfs))
       return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (min_correspondences >= 4, n_frames >= 0)", who);
     if (int rc = ms_check_store(h, who, mp)) return rc;
+    if (int rc = ms_check_grid_frames(h, who, n_frames)) return rc;
     if (n_frames == 0) return ORBX_OK;
     const size_t B = (size_t)n_frames;
     std::vector<TrackRefItem> items(B);
