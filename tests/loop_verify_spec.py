@@ -224,7 +224,7 @@ def verify_pair(cam, cur, loop, cfg=None, sim3_cfg=None):
             continue
         u = cam["fx"] * p[0] / p[2] + cam["cx"]; v = cam["fy"] * p[1] / p[2] + cam["cy"]
         du = u - float(loop["kp"]["x"][j]); dv = v - float(loop["kp"]["y"][j])
-        sc = c["scale_factor"] ** int(loop["kp"]["octave"][j])
+        sc = c["scale_factor"] ** min(max(int(loop["kp"]["octave"][j]), 0), 31)           # include/orbx.h: octave clamped to 0..31
         thr = c["chi2"] * sc * sc
         e = du * du + dv * dv
         out["margin"] = min(out["margin"], abs(e - thr) / thr, abs(p[2]) / max(np.linalg.norm(p), 1e-300))

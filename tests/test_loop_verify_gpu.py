@@ -32,8 +32,10 @@ def _cfg(pkg, verify=None, sim3=None):
     return pkg.LoopVerifyConfig(**dict(verify or {}, sim3=pkg.Sim3SolverConfig(**(sim3 or {}))))
 
 
-def _sim3_close(g, s, n_inliers, where):
-    tol = 1e-9 if n_inliers >= 50 else 1e-8
+def _sim3_close(g, s, n_inliers, where, tol=None, worst=worst):
+    """tol, worst: for tests/test_loop_verify_world_gpu.py, which states its own bound where a scene lies far from the origin or from
+    unit scale and keeps its own record"""
+    tol = tol or (1e-9 if n_inliers >= 50 else 1e-8)
     ang = pnp_spec.rotation_angle(g[:7], s[:7])
     dt = np.linalg.norm(g[4:7] - s[4:7]) / max(np.linalg.norm(s[4:7]), 1e-12)
     ds = abs(g[7] - s[7]) / s[7]
@@ -41,15 +43,15 @@ def _sim3_close(g, s, n_inliers, where):
     assert g[0] >= 0.0 and ang < tol and dt < tol and ds < tol, (where, ang, dt, ds)
 
 
-def _mse_close(g, s, where):
+def _mse_close(g, s, where, tol=1e-9, worst=worst):
     if s == 0.0:
         assert g == 0.0, where
         return
     worst["mse"] = max(worst["mse"], abs(g - s) / s)
-    assert abs(g - s) <= 1e-9 * s, (where, g, s)
+    assert abs(g - s) <= tol * s, (where, g, s)
 
 
-def assert_pair_matches_spec(g, s, where=""):
+def assert_pair_matches_spec(g, s, where="", tol=None, mse_tol=1e-9, worst=worst):
     assert g["status"] == s["status"], (where, g["status"], s["status"])
     for k in ("n_matches", "n_pairs", "best_hypothesis", "ransac_inliers", "n_inliers", "refined", "n_verified"):
         assert g["stats"][k] == s[k], (where, k, g["stats"][k], s[k])
@@ -60,10 +62,10 @@ def assert_pair_matches_spec(g, s, where=""):
     assert g["pts_current"].tobytes() == s["pts_current"].tobytes() and g["pts_loop"].tobytes() == s["pts_loop"].tobytes(), where
     assert np.array_equal(g["inlier"], s["inlier"]), where
     if s["status"] in (S.OK, S.TOO_FEW_INLIERS, S.TOO_FEW_VERIFIED):
-        _sim3_close(g["sim3"], s["sim3"], s["n_inliers"], where)
+        _sim3_close(g["sim3"], s["sim3"], s["n_inliers"], where, tol, worst)
     else:
         assert g["sim3"].tobytes() == S.IDENTITY.tobytes(), where
-    _mse_close(g["stats"]["mse"], s["mse"], where)
+    _mse_close(g["stats"]["mse"], s["mse"], where, mse_tol, worst)
 
 
 def _bytes(r):
