@@ -580,6 +580,31 @@ int orbx_ba_solve_global_obs32(orbx_handle* h, const orbx_camera* cam, const orb
                                const orbx_ba_obs32* obs32, orbx_should_stop_fn should_stop, void* user,
                                double* poses_wc_out, int* iterations, double* initial_error, double* final_error);
 
+/* Global BA over a whole map: orbx_ba_solve_global's arguments and semantics, word for word, on a path of its own that holds more
+ * optimised keyframes than the local-window solver's 128 — any 1 <= K <= orbx_ba_global_map_max_keyframes() (2048: the reduced system
+ * [6K + 1][6K] f64 in device memory is 1.2 GB there; the workspaces belong to the handle, grow on demand and are sized by the call's K,
+ * M and N, never by the cap).  A larger K is ORBX_ERR_INVALID before anything is enqueued; a failed allocation is ORBX_ERR_HIP.
+ * The calls always take this path, also for small K.  ORBX_ERR_EMPTY for K < 1, M == 0 or N == 0; ORBX_ERR_INVALID for an observation
+ * index out of range (the message names the observation, poses_wc_out and points are left untouched); should_stop is polled once per
+ * iteration; an iteration whose reduced system has a pivot that is not positive ends the solve with the parameters it started from.
+ * Every sum has a fixed order: two runs give the same bits.  Not partitioned: with an all-reduce hook or communicator installed the
+ * calls answer ORBX_ERR_INVALID.
+ *   _obs32: 16-byte observations, kf_idx -1 marks the fixed keyframe; _obs32_device: the same array in device memory of the handle's
+ *   device (16-byte aligned), written by work already enqueued on the handle's stream. */
+int orbx_ba_solve_global_map(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
+                             const double* poses_cw, const double* fixed_pose_cw, int M, double* points, int N,
+                             const orbx_ba_obs* obs, orbx_should_stop_fn should_stop, void* user,
+                             double* poses_wc_out, int* iterations, double* initial_error, double* final_error);
+int orbx_ba_solve_global_map_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
+                                   const double* poses_cw, const double* fixed_pose_cw, int M, double* points, int N,
+                                   const orbx_ba_obs32* obs32, orbx_should_stop_fn should_stop, void* user,
+                                   double* poses_wc_out, int* iterations, double* initial_error, double* final_error);
+int orbx_ba_solve_global_map_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K,
+                                          const double* poses_cw, const double* fixed_pose_cw, int M, double* points, int N,
+                                          const orbx_ba_obs32* d_obs32, orbx_should_stop_fn should_stop, void* user,
+                                          double* poses_wc_out, int* iterations, double* initial_error, double* final_error);
+int orbx_ba_global_map_max_keyframes(void);
+
 /* LocalInertialBAConfig (src/optimizer/local_inertial_ba.rs:109-141); orbx_default_inertial_ba_config = its Default:
  * 10 iterations, window 10, sqrt(5.991), sqrt(7.815), lambda 1e-2, gyro random-walk information 1e6, accel 1e4. */
 typedef struct {
@@ -1288,6 +1313,36 @@ int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orb
                                const double* biases, int E, const int* edge_kf, const double* preint,
                                orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, double* vel_out, double* bias_out,
                                int* fixed_kf_out, int* counts_out, int* iterations, double* initial_error, double* final_error);
+
+/* ---- global BA from the resident map (src/optimizer/global_ba.rs:100-181, :184-418; loop_closer.rs:237-240) ----
+ * collect_global_ba_data where the slot tables lie.  kfs [n_kfs] is the caller's list of the map's keyframes in ascending id (host
+ * array, copied before the call returns; is_bad filtering = leaving a keyframe out).
+ *   [spec] kfs[0] is the anchor (:124); kfs[1..] are the K = n_kfs - 1 optimised keyframes in that order.
+ *   [spec] P = the distinct slots s with 0 <= s < capacity and live[s] of all tables in first-seen order, keyframes in list order,
+ *     features in index order; M = |P|.  A keyframe without a table observes nothing.
+ *   [spec] one orbx_ba_obs32 per feature whose table entry is in P (a slot repeated inside a keyframe: one per feature), keyframes in
+ *     list order, features in index order: kf_idx = i - 1 (-1: the anchor), mp_idx = the position in P, u, v = the keypoint's f32.
+ *     N is their number.
+ * orbx_map_collect_global_device: asynchronous on the handle's stream; outputs in device memory: d_counts [4] = (K, 1, M, N),
+ * d_list_slot [list_cap], d_positions [list_cap][3] (rows [0, M)), d_obs32 [obs_cap] (rows [0, N), 16-byte aligned).  Nothing is
+ * truncated: list_cap >= min(the keyframes' features summed, capacity) and obs_cap >= the features summed, else ORBX_ERR_INVALID before
+ * anything is enqueued, as for n_kfs <= 0, n_kfs > 65535, a keyframe of another handle or whose table is bound to another store.  The
+ * same bytes come out on every run; the store and the tables are left as found.
+ * orbx_map_collect_global: the same with host outputs, synchronous; M == 0 (:176-178) is ORBX_ERR_EMPTY with counts written and no
+ * rows.  With T_cw = the inverses of the keyframes' poses its outputs are orbx_ba_solve_global_map_obs32's arguments.
+ * orbx_map_global_ba = run_global_ba's device half: the collection; ONE download of counts, P's slots and positions; T_cw from the
+ * keyframes' own pose_wc; orbx_ba_solve_global_map_obs32_device on the observations where they lie; then, if the solve iterated, the M
+ * positions written to P's slots, positions only.  poses_wc_out [n_kfs - 1][7] (host), counts_out [4] and the solver's scalars go to
+ * the caller, who applies the poses with orbx_keyframe_set_pose: the keyframes are const.  ORBX_ERR_EMPTY for n_kfs < 2 or M == 0,
+ * ORBX_ERR_INVALID for more optimised keyframes than orbx_ba_global_map_max_keyframes() (before anything is enqueued) and with an
+ * all-reduce hook / communicator installed; the store is then untouched. */
+int orbx_map_collect_global_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int list_cap,
+                                   int obs_cap, int* d_counts, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32);
+int orbx_map_collect_global(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int list_cap, int obs_cap,
+                            int* counts, int* list_slot, double* positions, orbx_ba_obs32* obs32);
+int orbx_map_global_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs,
+                       const orbx_keyframe* const* kfs, orbx_should_stop_fn should_stop, void* user, double* poses_wc_out,
+                       int* counts_out, int* iterations, double* initial_error, double* final_error);
 
 /* ---- observations from the resident map: lists, refresh, redundancy (map_point.rs:140-156; local_mapper.rs:421-469, :487-583) ----
  * mp.observations — which keyframes see a point, and at which feature — is the inverse of the slot tables.  Like the covisibility

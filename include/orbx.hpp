@@ -1571,8 +1571,9 @@ inline std::optional<VerifiedLoop> verify_loop_candidate(Handle& h, const Camera
 
 // global_ba.rs:184-418.  The id -> index re-keying is the reference's own (:198-229).  Observations of a map point
 // that is not in mp_ids are rejected (collect_global_ba_data never emits one, :160).
+// whole_map: through orbx_ba_solve_global_map, the path that takes more than 128 optimised keyframes (solve_global_ba_map below).
 inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAProblemData& problem, const CameraModel& camera,
-                                                     const GlobalBAConfig& config, const std::function<bool()>& should_stop) {
+                                                     const GlobalBAConfig& config, const std::function<bool()>& should_stop, bool whole_map = false) {
   const size_t n_kfs = problem.kf_ids.size(), n_mps = problem.mp_ids.size();
   if (n_kfs < 2 || n_mps == 0) return std::nullopt;                      // :194-196
   size_t fixed_pos = n_kfs;
@@ -1611,9 +1612,9 @@ inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAPr
   double e0 = 0, e1 = 0;
   const orbx_camera c = camera.c();
   const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, 0};
-  const int rc = orbx_ba_solve_global(h.get(), &c, &cfg, K, poses.data(), fixed.data(), M, points.data(), (int)obs.size(), obs.data(),
-                                      detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(), &it,
-                                      &e0, &e1);
+  const int rc = (whole_map ? orbx_ba_solve_global_map : orbx_ba_solve_global)(h.get(), &c, &cfg, K, poses.data(), fixed.data(), M, points.data(), (int)obs.size(),
+                                                                              obs.data(), detail::stop_fn(should_stop), detail::stop_user(should_stop), out.data(),
+                                                                              &it, &e0, &e1);
   if (rc != ORBX_OK) return std::nullopt;
   GlobalBAResult r;
   r.optimized_poses[problem.fixed_kf_id] = se3_inverse(fixed_pose);      // :386
@@ -1624,6 +1625,13 @@ inline std::optional<GlobalBAResult> solve_global_ba(Handle& h, const GlobalBAPr
   for (int j = 0; j < M; ++j) r.optimized_points[problem.mp_ids[(size_t)j]] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
   r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
   return r;
+}
+
+// solve_global_ba for a whole map (orbx_ba_solve_global_map): the same problem, result and semantics for up to
+// orbx_ba_global_map_max_keyframes() optimised keyframes; a larger map answers nullopt as any refused solve does.
+inline std::optional<GlobalBAResult> solve_global_ba_map(Handle& h, const GlobalBAProblemData& problem, const CameraModel& camera,
+                                                         const GlobalBAConfig& config, const std::function<bool()>& should_stop) {
+  return solve_global_ba(h, problem, camera, config, should_stop, true);
 }
 
 
@@ -1861,6 +1869,77 @@ inline std::optional<MapLocalInertialBAResult> map_local_inertial_ba(Handle& h, 
     for (int q = 0; q < 3; ++q) { b.gyro[q] = bo[6 * i + q]; b.accel[q] = bo[6 * i + 3 + q]; }
     r.biases.push_back(b);
   }
+  r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
+  return r;
+}
+
+// ---- global BA from the resident map (include/orbx.h, "global BA from the resident map"; global_ba.rs:100-181, :184-418) ----
+struct GlobalBAMapProblem {                            // orbx_map_collect_global's outputs cut to their sizes
+  int K = 0, M = 0, N = 0;                             // optimised keyframes (keyframes[1..]), points, observations
+  std::vector<int> list_slot;                          // [M] P: the distinct live slots in first-seen order
+  std::vector<std::array<double, 3>> positions;        // [M]
+  std::vector<orbx_ba_obs32> obs32;                    // [N] kf_idx -1: the anchor keyframes[0]
+};
+
+inline void global_map_bounds(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, int* list_cap, int* obs_cap) {
+  size_t all = 0;
+  for (const orbx_keyframe* k : keyframes) {
+    int n = 0;
+    h.check(orbx_keyframe_info(k, &n, nullptr, nullptr, nullptr));
+    all += (size_t)n;
+  }
+  *list_cap = (int)std::min(all, (size_t)store.capacity());
+  *obs_cap = (int)all;
+}
+
+// orbx_map_collect_global_device: every output is the caller's device memory (d_counts [4], d_list_slot / d_positions [list_cap],
+// d_obs32 [obs_cap], 16-byte aligned); asynchronous on the handle's stream.
+inline void map_collect_global_device(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes, int list_cap, int obs_cap,
+                                      int* d_counts, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  h.check(orbx_map_collect_global_device(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), list_cap, obs_cap, d_counts, d_list_slot, d_positions, d_obs32));
+}
+
+// orbx_map_collect_global: the same into host vectors, synchronous; nullopt where the keyframes observe no live map point (:176-178).
+inline std::optional<GlobalBAMapProblem> map_collect_global(Handle& h, MapPointStore& store, const std::vector<const orbx_keyframe*>& keyframes) {
+  int list_cap = 0, obs_cap = 0;
+  global_map_bounds(h, store, keyframes, &list_cap, &obs_cap);
+  GlobalBAMapProblem w;
+  int counts[4] = {0, 0, 0, 0};
+  w.list_slot.resize(std::max(list_cap, 1)); w.positions.resize(std::max(list_cap, 1)); w.obs32.resize(std::max(obs_cap, 1));
+  const int rc = orbx_map_collect_global(h.get(), store.get(), (int)keyframes.size(), keyframes.data(), list_cap, obs_cap, counts, w.list_slot.data(),
+                                         w.positions[0].data(), w.obs32.data());
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  w.K = counts[0]; w.M = counts[2]; w.N = counts[3];
+  w.list_slot.resize((size_t)w.M); w.positions.resize((size_t)w.M); w.obs32.resize((size_t)w.N);
+  return w;
+}
+
+struct MapGlobalBAResult {                             // poses_wc[i] belongs to keyframes[1 + i]; the anchor keyframes[0] keeps its pose (:386)
+  int K = 0, M = 0, N = 0;
+  std::vector<SE3> poses_wc;
+  size_t iterations = 0;
+  double initial_error = 0, final_error = 0;
+};
+
+// orbx_map_global_ba: run_global_ba's device half on the resident map (loop_closer.rs:237-240) — the whole map collected on the device,
+// solved where the observations lie, the optimised positions written back into the store.  The caller applies the poses
+// (orbx_keyframe_set_pose).  nullopt where the reference returns None.
+inline std::optional<MapGlobalBAResult> map_global_ba(Handle& h, const CameraModel& camera, const GlobalBAConfig& config, MapPointStore& store,
+                                                      const std::vector<const orbx_keyframe*>& keyframes, const std::function<bool()>& should_stop) {
+  const size_t K = keyframes.empty() ? 0 : keyframes.size() - 1;
+  std::vector<double> po(std::max<size_t>(K, 1) * 7);
+  int counts[4] = {0, 0, 0, 0}, it = 0;
+  double e0 = 0, e1 = 0;
+  const orbx_camera c = camera.c();
+  const orbx_ba_config cfg{config.max_iterations, config.param_tolerance, config.gradient_tolerance, config.huber_threshold, 0};
+  const int rc = orbx_map_global_ba(h.get(), &c, &cfg, store.get(), (int)keyframes.size(), keyframes.data(), detail::stop_fn(should_stop),
+                                    detail::stop_user(should_stop), po.data(), counts, &it, &e0, &e1);
+  if (rc == ORBX_ERR_EMPTY) return std::nullopt;
+  h.check(rc);
+  MapGlobalBAResult r;
+  r.K = counts[0]; r.M = counts[2]; r.N = counts[3];
+  for (size_t i = 0; i < K; ++i) r.poses_wc.push_back(detail::se3_from7(&po[7 * i]));
   r.iterations = (size_t)it; r.initial_error = e0; r.final_error = e1;
   return r;
 }

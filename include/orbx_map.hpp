@@ -510,17 +510,18 @@ inline size_t apply_global_ba_results(MapSnapshot& m, const GlobalBAResult& r) {
 
 // run_global_ba (global_ba.rs:450-500): collect under the read lock, solve with no lock (should_stop = the running flag cleared), apply under the
 // write lock — unconditionally, unlike local BA (:486-489); `running` is set on entry and cleared on every way out (:456, :468, :479, :498).
+// whole_map: the solve goes through solve_global_ba_map (orbx_ba_solve_global_map), which takes more than 128 optimised keyframes.
 inline std::optional<GlobalBAResult> run_global_ba(Handle& h, MapSnapshot& map, const CameraModel& camera, const GlobalBAConfig& config,
                                                    std::atomic<bool>& running,
                                                    const std::function<void(const std::function<void()>&)>& lock_read = nullptr,
-                                                   const std::function<void(const std::function<void()>&)>& lock_write = nullptr) {
+                                                   const std::function<void(const std::function<void()>&)>& lock_write = nullptr, bool whole_map = false) {
   running.store(true);
   struct Clear { std::atomic<bool>& flag; ~Clear() { flag.store(false); } } clear{running};   // ... a thrown orbx::Error or a throwing lock callback included
   std::optional<GlobalBAProblemData> problem;
   auto phase1 = [&] { problem = collect_global_ba_data(map); };
   if (lock_read) lock_read(phase1); else phase1();
   if (!problem) return std::nullopt;
-  std::optional<GlobalBAResult> result = solve_global_ba(h, *problem, camera, config, [&] { return !running.load(); });
+  std::optional<GlobalBAResult> result = solve_global_ba(h, *problem, camera, config, [&] { return !running.load(); }, whole_map);
   if (!result) return std::nullopt;
   auto phase3 = [&] { apply_global_ba_results(map, *result); };
   if (lock_write) lock_write(phase3); else phase3();

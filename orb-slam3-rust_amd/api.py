@@ -117,6 +117,8 @@ ABI_SYMBOLS = [
     "orbx_map_cull_points",
     "orbx_ba_solve_inertial_obs32", "orbx_ba_solve_inertial_obs32_device", "orbx_map_collect_inertial_window_device",
     "orbx_map_collect_inertial_window", "orbx_map_local_inertial_ba",
+    "orbx_ba_solve_global_map", "orbx_ba_solve_global_map_obs32", "orbx_ba_solve_global_map_obs32_device", "orbx_ba_global_map_max_keyframes",
+    "orbx_map_collect_global_device", "orbx_map_collect_global", "orbx_map_global_ba",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS = 1, 2    # orbx_map_create_points' phases (a bit mask)
@@ -1450,6 +1452,64 @@ class Handle:
         return dict(poses_wc=out_p[:K], velocities=out_v[:K], biases=out_b[:K], fixed_kf=fx[:F - 1].copy(), counts=counts, iterations=it.value,
                     initial_error=e0.value, final_error=e1.value)
 
+    # ---- global BA from the resident map (include/orbx.h, "global BA from the resident map") ----
+    @staticmethod
+    def _global_bounds(mp, keyframes):
+        """(list bound, observation bound): every feature of `keyframes`, the list's at most the capacity"""
+        n = int(sum(k.n for k in keyframes))
+        return int(min(n, mp.capacity)), n
+
+    def map_collect_global_device(self, mp: "MapPointStore", keyframes, device=None, list_cap=None, obs_cap=None):
+        """The whole map's global-BA problem (global_ba.rs:100-181), collected on the device from the slot tables, the keypoints and the
+        store (orbx_map_collect_global_device): keyframes[0] is the anchor, keyframes[1:] the K optimised keyframes.  Returns a dict of
+        CUDA tensors: counts [4] int32 = (K, 1, M, N), list_slot [cap] int32 and positions [cap,3] f64 (the distinct live slots in
+        first-seen order, rows [0, M)), obs32 [obs_cap,16] u8 (rows [0, N) are BA_OBS32 records, kf_idx -1 the anchor's).
+        Asynchronous on the handle's stream.  list_cap / obs_cap: other capacities than the bounds (one below its bound is refused)."""
+        import torch
+        cap, ocap = self._global_bounds(mp, keyframes)
+        cap = cap if list_cap is None else int(list_cap); ocap = ocap if obs_cap is None else int(obs_cap)
+        dev = device or torch.device("cuda", self.device)
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(counts=mk(4, torch.int32), list_slot=mk(max(cap, 1), torch.int32), positions=mk((max(cap, 1), 3), torch.float64),
+                 obs32=mk((max(ocap, 1), BA_OBS32.itemsize), torch.uint8))
+        self._after_torch(*o.values())
+        self._check(self._L.orbx_map_collect_global_device(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(cap), C.c_int(ocap),
+                                                           _vp(o["counts"]), _vp(o["list_slot"]), _vp(o["positions"]), _vp(o["obs32"])))
+        o["list_slot"] = o["list_slot"][:cap]; o["positions"] = o["positions"][:cap]; o["obs32"] = o["obs32"][:ocap]
+        return o
+
+    def map_collect_global(self, mp: "MapPointStore", keyframes, list_cap=None, obs_cap=None):
+        """The host form (orbx_map_collect_global), synchronous: a dict of numpy arrays cut to their sizes — counts [4], list_slot [M],
+        positions [M,3], obs32 [N] BA_OBS32 — or None where the keyframes observe no live map point (global_ba.rs:176-178)."""
+        cap, ocap = self._global_bounds(mp, keyframes)
+        cap = cap if list_cap is None else int(list_cap); ocap = ocap if obs_cap is None else int(obs_cap)
+        counts = np.zeros(4, np.int32); ls = np.zeros(max(cap, 1), np.int32); pos = np.zeros((max(cap, 1), 3)); obs = np.zeros(max(ocap, 1), BA_OBS32)
+        rc = self._L.orbx_map_collect_global(self._h, mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), C.c_int(cap), C.c_int(ocap), _vp(counts), _vp(ls),
+                                             _vp(pos), _vp(obs))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        K, F, M, N = (int(x) for x in counts)
+        return dict(counts=counts, list_slot=ls[:M].copy(), positions=pos[:M].copy(), obs32=obs[:N].copy())
+
+    def map_global_ba(self, camera, mp: "MapPointStore", keyframes, cfg: "GlobalBAConfig" = None, should_stop=None):
+        """Global BA of the whole resident map (orbx_map_global_ba): keyframes[0] stays fixed, the problem is collected on the device,
+        solved by the whole-map solver with its observations where they lie, and the optimised positions are written back into the
+        store if the solve iterated.  Returns a dict — poses_wc [K,7] of keyframes[1:] (apply them with KeyFrame.set_pose), counts
+        (K, 1, M, N), iterations, initial_error, final_error — or None where the reference returns None."""
+        cfg = cfg or GlobalBAConfig()
+        K = max(len(keyframes) - 1, 0)
+        out_p = np.zeros((max(K, 1), 7)); counts = np.zeros(4, np.int32)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
+        cam = camera._c(); c = cfg._c()
+        rc = self._L.orbx_map_global_ba(self._h, C.byref(cam), C.byref(c), mp._p, C.c_int(len(keyframes)), self._kf_array(keyframes), cb, None, _vp(out_p),
+                                        _vp(counts), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc == ORBX_ERR_EMPTY:
+            return None
+        self._check(rc)
+        return dict(poses_wc=out_p[:K], counts=counts, iterations=it.value, initial_error=e0.value, final_error=e1.value)
+
     # ---- observations from the resident map (include/orbx.h, "observations from the resident map") ----
     @staticmethod
     def _obs_slots(slots):
@@ -2438,6 +2498,48 @@ class Handle:
             return None                      # reference returns None, global_ba.rs:194-196
         self._check(rc)
         return dict(poses_wc=out_wc[:K], points=pts, iterations=it.value, initial_error=e0.value, final_error=e1.value)
+
+    def ba_global_map_max_keyframes(self) -> int:
+        """The most optimised keyframes ba_solve_global_map takes (orbx_ba_global_map_max_keyframes)."""
+        return int(self._L.orbx_ba_global_map_max_keyframes())
+
+    def _ba_solve_global_map(self, fn, camera, cfg, poses_cw, fixed_pose_cw, points, obs, N, should_stop):
+        poses_cw = np.ascontiguousarray(poses_cw, np.float64).reshape(-1, 7)
+        fixed = np.ascontiguousarray(fixed_pose_cw, np.float64).reshape(7)
+        pts = np.array(points, np.float64, copy=True).reshape(-1, 3)
+        K, M = len(poses_cw), len(pts)
+        out_wc = np.zeros((max(K, 1), 7))
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
+        cam = camera._c(); c = cfg._c()
+        rc = fn(self._h, C.byref(cam), C.byref(c), C.c_int(K), _vp(poses_cw), _vp(fixed), C.c_int(M), _vp(pts), C.c_int(N), _vp(obs), cb, None, _vp(out_wc),
+                C.byref(it), C.byref(e0), C.byref(e1))
+        if rc in (ORBX_ERR_EMPTY,):
+            return None                      # reference returns None, global_ba.rs:194-196
+        self._check(rc)
+        return dict(poses_wc=out_wc[:K], points=pts, iterations=it.value, initial_error=e0.value, final_error=e1.value)
+
+    def ba_solve_global_map(self, camera, cfg, poses_cw, fixed_pose_cw, points, obs, should_stop=None):
+        """ba_solve_global for a whole map (orbx_ba_solve_global_map[_obs32]): the same arguments, semantics and result dict, on the
+        path that takes up to ba_global_map_max_keyframes() optimised keyframes.  obs is a BA_OBS or a BA_OBS32 array."""
+        o32 = getattr(obs, "dtype", None) == BA_OBS32
+        obs = np.ascontiguousarray(obs, BA_OBS32 if o32 else BA_OBS)
+        fn = self._L.orbx_ba_solve_global_map_obs32 if o32 else self._L.orbx_ba_solve_global_map
+        return self._ba_solve_global_map(fn, camera, cfg, poses_cw, fixed_pose_cw, points, obs, len(obs), should_stop)
+
+    def ba_solve_global_map_obs32(self, camera, cfg, poses_cw, fixed_pose_cw, points, obs32, should_stop=None):
+        """ba_solve_global_map on the 16-byte observations (orbx_ba_solve_global_map_obs32); kf_idx -1 marks the fixed keyframe."""
+        obs32 = np.ascontiguousarray(obs32, BA_OBS32)
+        return self._ba_solve_global_map(self._L.orbx_ba_solve_global_map_obs32, camera, cfg, poses_cw, fixed_pose_cw, points, obs32, len(obs32), should_stop)
+
+    def ba_solve_global_map_obs32_device(self, camera, cfg, poses_cw, fixed_pose_cw, points, obs32, n_obs, should_stop=None):
+        """... with the observations in device memory (orbx_ba_solve_global_map_obs32_device): obs32 is a CUDA tensor whose first
+        16 * n_obs bytes are BA_OBS32 records, 16-byte aligned.  Bit for bit the result for a host copy of the observations."""
+        N = int(n_obs)
+        if N < 0 or N * BA_OBS32.itemsize > obs32.numel() * obs32.element_size():
+            raise ValueError("obs32 holds fewer than n_obs records")
+        self._after_torch(obs32)
+        return self._ba_solve_global_map(self._L.orbx_ba_solve_global_map_obs32_device, camera, cfg, poses_cw, fixed_pose_cw, points, obs32, N, should_stop)
 
 
 class StereoProcessor:

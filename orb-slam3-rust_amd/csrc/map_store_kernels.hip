@@ -832,14 +832,16 @@ int local_select_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, i
 // neighbours, picked on the device) or the temporal chain of local inertial BA (named by the caller; chain[0] is the anchor).
 // The keyframes' tables with their keypoints (the chain's: and stereo bytes), the observations' bound (every feature of kfs[]), the
 // list's bound, and the kind's selection plan: one local-map frame whose reference is `cur`, or the chain as one frame of keyframes.
-enum WinKind { WIN_COVISIBLE, WIN_CHAIN };
+// ... or the whole map of global BA (global_ba.rs:100-181): every keyframe of the call is in the list, kfs[0] the anchor, kfs[i] optimised
+// keyframe i - 1, no stereo bit: the chain's selection and uploaded list with the covisible window's order and emit kernels.
+enum WinKind { WIN_COVISIBLE, WIN_CHAIN, WIN_GLOBAL };
 struct WinPlan {
   WinKind kind = WIN_COVISIBLE;
   std::vector<BacKf> kfs;
   int n_feat = 0, max_n = 0, bound = 0;
   LocalPlan L; int cur = 0, max_covisible = 0;       // WIN_COVISIBLE
   SelPlan S; std::vector<int> chain;                 // WIN_CHAIN
-  int n_local() const { return kind == WIN_CHAIN ? (int)chain.size() : 1 + max_covisible; }   // rows of local_kf
+  int n_local() const { return kind != WIN_COVISIBLE ? (int)chain.size() : 1 + max_covisible; }   // rows of local_kf
 };
 
 // the keyframe table and the observations' bound (each keyframe as ms_check_keyframe asks)
@@ -889,16 +891,31 @@ int bic_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_k
   return ORBX_OK;
 }
 
+// The whole map: kfs[] is the caller's list in ascending id with the bad keyframes left out (global_ba.rs:100-124)
+int glb_plan(orbx_handle* h, const char* who, const orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, WinPlan& P) {
+  if (int rc = ms_check_store(h, who, mp)) return rc;
+  if (n_kfs <= 0 || !kfs) return orbx_fail(h, ORBX_ERR_INVALID, "%s: n_kfs must be positive", who);
+  if (int rc = ms_check_grid_keyframes(h, who, n_kfs)) return rc;
+  P.kind = WIN_GLOBAL;
+  if (int rc = win_plan_kfs(h, who, mp, n_kfs, kfs, P)) return rc;
+  P.chain.resize((size_t)n_kfs);
+  std::iota(P.chain.begin(), P.chain.end(), 0);
+  const int off[2] = {0, n_kfs};
+  if (int rc = ms_plan(h, who, mp, ORBX_MAP_SOURCE_KEYFRAMES, 1, kfs, off, nullptr, P.S)) return rc;
+  P.bound = P.S.bound_off[1];
+  return ORBX_OK;
+}
+
 // Everything on the handle's stream: the kind's selection (covisibility and selection as the tracking call runs them, or the chain's),
 // then the five launches above.  d_local_kf: the covisible window's output (the chain's local_kf is the uploaded chain).
 int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, int list_cap, int obs_cap, int* d_counts, int* d_local_kf,
                 int* d_fixed_kf, int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
-  const bool chain = P.kind == WIN_CHAIN;
+  const bool chain = P.kind != WIN_COVISIBLE, whole = P.kind == WIN_GLOBAL;   // chain: the list of local keyframes is the caller's, uploaded
   const int bound = P.bound, n_kfs = (int)P.kfs.size();
   if (list_cap < bound) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d is below the list's bound %d (%s, at most the capacity)", who, list_cap, bound,
-                                         chain ? "the chain's features summed" : "cur's features plus the max_covisible largest of the others'");
+                                         whole ? "the keyframes' features summed" : chain ? "the chain's features summed" : "cur's features plus the max_covisible largest of the others'");
   if (obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: obs_cap %d is below the observations' bound %d (the features of kfs[] summed)", who, obs_cap, P.n_feat);
-  if (!d_counts || (!chain && !d_local_kf) || !d_fixed_kf || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
+  if (!d_counts || (!chain && !d_local_kf) || (!whole && !d_fixed_kf) || (bound > 0 && (!d_list_slot || !d_positions)) || (P.n_feat > 0 && !d_obs32) || ((uintptr_t)d_obs32 & 15))
     return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument (d_obs32 is 16-byte aligned)", who);
   ORBX_HIP(h, hipSetDevice(h->device));
   const size_t K = (size_t)n_kfs;
@@ -906,7 +923,7 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
   Carve ws;
   UploadPlan up;
   const size_t o_lo = ws.take(8), o_gd = ws.take(32 * (size_t)bound), o_cc = ws.take(4 * K * (size_t)n_chunk), o_kc = ws.take(4 * K), o_ro = ws.take(4 * K),
-               o_ob = ws.take(4 * K);
+               o_ob = ws.take(4 * K), o_fx = ws.take(whole ? 4 * K : 0);   // (the whole map has no fixed observers to report: the order kernel's list stays here)
   const size_t u_kf = up.put(P.kfs.data(), sizeof(BacKf) * K), u_ch = up.put(P.chain.data(), 4 * P.chain.size());
   if (int rc = orbx_reserve(h, h->ws_map.win_scratch, ws.off)) return rc;
   uint8_t* w = (uint8_t*)h->ws_map.win_scratch.p;
@@ -921,11 +938,11 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
   A.live = mp->d_live; A.kfs = (const BacKf*)(ds + u_kf); A.list_off = (const int*)(w + o_lo); A.list_slot = d_list_slot;
   A.index = (int*)mp->first.p;                                              // (row 0; the selection has allocated it and left it EMPTY)
   A.chunk_count = (int*)(w + o_cc); A.kf_count = (int*)(w + o_kc); A.role = (int*)(w + o_ro); A.obs_base = (int*)(w + o_ob);
-  A.local_kf = chain ? (const int*)(ds + u_ch) : d_local_kf; A.counts = d_counts; A.fixed_kf = d_fixed_kf; A.obs = d_obs32;
+  A.local_kf = chain ? (const int*)(ds + u_ch) : d_local_kf; A.counts = d_counts; A.fixed_kf = whole ? (int*)(w + o_fx) : d_fixed_kf; A.obs = d_obs32;
   // order and emit are the kind's: roles from local_kf and plain mp_idx, or roles from the chain and the stereo bit
   using BacKernel = void (*)(BacArgs);
   static const BacKernel covisible[2] = {bac_order_kernel<false>, bac_emit_kernel<false>}, temporal[2] = {bac_order_kernel<true>, bac_emit_kernel<true>};
-  const BacKernel* of_kind = chain ? temporal : covisible;
+  const BacKernel* of_kind = P.kind == WIN_CHAIN ? temporal : covisible;
   const dim3 block(MS_THREADS), list_grid(std::max(1, (bound + MS_THREADS - 1) / MS_THREADS)), kf_grid(n_chunk, n_kfs);
   orbx_launch(h, "bac_index_kernel", true, bac_index_kernel, list_grid, block, 0, A);
   orbx_launch(h, "bac_count_kernel", true, bac_count_kernel, kf_grid, block, 0, A);
@@ -938,6 +955,7 @@ int win_enqueue(orbx_handle* h, const char* who, orbx_map_points* mp, const WinP
 
 // a window without a point to optimise: M == 0, and for the covisible window N == 0 (local_inertial_ba.rs:946-948)
 int win_check_empty(orbx_handle* h, const char* who, const WinPlan& P, const int* counts) {
+  if (P.kind == WIN_GLOBAL) return counts[2] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the keyframes observe no live map point", who);
   if (P.kind == WIN_CHAIN) return counts[2] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the chain observes no live map point", who);
   return counts[2] && counts[3] ? (int)ORBX_OK : orbx_fail(h, ORBX_ERR_EMPTY, "%s: the local keyframes observe no live map point", who);
 }
@@ -946,7 +964,7 @@ int win_check_empty(orbx_handle* h, const char* who, const WinPlan& P, const int
 // with `rows` | P's slots | P's positions at their bounds.  The observations stay at d + o_ob.
 struct WinDown { size_t o_cn, o_lk, o_fx, o_ls, o_po, o_ob; uint8_t* d; const uint8_t* hp; };
 int win_collect_down(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, bool rows, WinDown& o) {
-  const size_t bound = (size_t)P.bound, nl = P.kind == WIN_CHAIN ? 0 : (size_t)P.n_local(), K = P.kfs.size();
+  const size_t bound = (size_t)P.bound, nl = P.kind != WIN_COVISIBLE ? 0 : (size_t)P.n_local(), K = P.kfs.size();
   ORBX_HIP(h, hipSetDevice(h->device));
   Carve out;
   o.o_cn = out.take(16); o.o_lk = out.take(4 * nl); o.o_fx = out.take(4 * K);
@@ -969,12 +987,13 @@ int win_collect_down(orbx_handle* h, const char* who, orbx_map_points* mp, const
 // The host forms of the collection: the sizes first, then as many rows as they say: two downloads, nothing sized by a bound.
 int win_collect_host(orbx_handle* h, const char* who, orbx_map_points* mp, const WinPlan& P, int list_cap, int obs_cap, int* counts, int* local_kf, int* fixed_kf,
                      int* list_slot, double* positions, orbx_ba_obs32* obs32) {
-  const bool chain = P.kind == WIN_CHAIN;
+  const bool chain = P.kind != WIN_COVISIBLE, whole = P.kind == WIN_GLOBAL;
   if (list_cap < P.bound || obs_cap < P.n_feat) return orbx_fail(h, ORBX_ERR_INVALID, "%s: list_cap %d / obs_cap %d are below their bounds %d / %d", who, list_cap, obs_cap, P.bound, P.n_feat);
-  if (!counts || (!chain && !local_kf) || !fixed_kf || (P.bound > 0 && (!list_slot || !positions)) || (P.n_feat > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+  if (!counts || (!chain && !local_kf) || (!whole && !fixed_kf) || (P.bound > 0 && (!list_slot || !positions)) || (P.n_feat > 0 && !obs32)) return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
   WinDown w;
   if (int rc = win_collect_down(h, who, mp, P, false, w)) return rc;
-  std::memcpy(counts, w.hp + w.o_cn, 16); std::memcpy(fixed_kf, w.hp + w.o_fx, 4 * P.kfs.size());
+  std::memcpy(counts, w.hp + w.o_cn, 16);
+  if (!whole) std::memcpy(fixed_kf, w.hp + w.o_fx, 4 * P.kfs.size());
   if (!chain) std::memcpy(local_kf, w.hp + w.o_lk, 4 * (size_t)P.n_local());
   if (int rc = win_check_empty(h, who, P, counts)) return rc;
   const size_t M = (size_t)counts[2], N = (size_t)counts[3];
@@ -1020,6 +1039,33 @@ int win_local_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const 
   for (int j = 0; j + 1 < F; ++j) orbx_pose_inverse(kfs[fx[j]]->pose_wc, &fixed_cw[7 * (size_t)(j + 1)]);
   if (int rc = ba_solve_visual(h, cam, cfg, Kw, poses.data(), F, fixed_cw.data(), M, points.data(), N, nullptr, should_stop, user, poses_wc_out, iterations,
                                initial_error, final_error, false, in, (const orbx_ba_obs32*)(w.d + w.o_ob), true))
+    return rc;
+  if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
+  return ORBX_OK;
+}
+
+// Global BA on a planned whole map: collect_global_ba_data (global_ba.rs:100-181) on the device with ONE download; T_cw from the keyframes'
+// own poses; the whole-map solve (global_ba_kernels.hip) on the observations where they lie; the optimised positions back into the store
+// when the solve iterated.  poses_wc_out [n_kfs - 1][7]: the caller applies them (orbx_keyframe_set_pose).
+int win_global_ba(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, const orbx_keyframe* const* kfs,
+                  const WinPlan& P, orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* counts_out, int* iterations, double* initial_error,
+                  double* final_error) {
+  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+  WinDown w;
+  if (int rc = win_collect_down(h, who, mp, P, true, w)) return rc;
+  const int* cn = (const int*)(w.hp + w.o_cn);
+  const double* pos = (const double*)(w.hp + w.o_po);
+  const int K = cn[0], M = cn[2], N = cn[3];
+  std::memcpy(counts_out, cn, 16);
+  if (int rc = win_check_empty(h, who, P, cn)) return rc;
+  if (K < 1) return orbx_fail(h, ORBX_ERR_EMPTY, "%s: global BA needs two keyframes and a map point", who);   // global_ba.rs:194-196
+  std::vector<double> poses(7 * (size_t)K), points(pos, pos + 3 * (size_t)M);
+  std::vector<int> slots((const int*)(w.hp + w.o_ls), (const int*)(w.hp + w.o_ls) + M);
+  double fixed_cw[7];
+  orbx_pose_inverse(kfs[0]->pose_wc, fixed_cw);
+  for (int i = 0; i < K; ++i) orbx_pose_inverse(kfs[1 + i]->pose_wc, &poses[7 * (size_t)i]);
+  if (int rc = gba_solve(h, who, cam, cfg, K, poses.data(), fixed_cw, M, points.data(), N, nullptr, (const orbx_ba_obs32*)(w.d + w.o_ob), true, should_stop, user,
+                         poses_wc_out, iterations, initial_error, final_error))
     return rc;
   if (*iterations > 0) return ms_set(mp, who, slots.data(), M, points.data(), nullptr, true);
   return ORBX_OK;
@@ -2558,6 +2604,45 @@ int orbx_map_local_inertial_ba(orbx_handle* h, const orbx_camera* cam, const orb
     const BaInertialHost in{cfg, velocities, biases, E, edge_kf, preint, vel_out, bias_out};
     return win_local_ba(h, who, cam, &vc, &in, mp, kfs, P, should_stop, user, nullptr, fixed_kf_out, poses_wc_out, counts_out, iterations, initial_error,
                         final_error);
+  });
+}
+
+int orbx_map_collect_global_device(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int list_cap, int obs_cap, int* d_counts,
+                                   int* d_list_slot, double* d_positions, orbx_ba_obs32* d_obs32) {
+  static const char* who = "orbx_map_collect_global_device";
+  if (!h) return ORBX_ERR_INVALID;
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
+    if (int rc = glb_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    return win_enqueue(h, who, mp, P, list_cap, obs_cap, d_counts, nullptr, nullptr, d_list_slot, d_positions, d_obs32);
+  });
+}
+
+int orbx_map_collect_global(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int list_cap, int obs_cap, int* counts,
+                            int* list_slot, double* positions, orbx_ba_obs32* obs32) {
+  static const char* who = "orbx_map_collect_global";
+  if (!h) return ORBX_ERR_INVALID;
+  return orbx_guard(h, who, [&]() -> int {
+    WinPlan P;
+    if (int rc = glb_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    return win_collect_host(h, who, mp, P, list_cap, obs_cap, counts, nullptr, nullptr, list_slot, positions, obs32);
+  });
+}
+
+int orbx_map_global_ba(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs,
+                       orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* counts_out, int* iterations, double* initial_error,
+                       double* final_error) {
+  static const char* who = "orbx_map_global_ba";
+  if (!h) return ORBX_ERR_INVALID;
+  return orbx_guard(h, who, [&]() -> int {
+    if (!cam || !cfg || !counts_out || !iterations || !initial_error || !final_error || (n_kfs > 1 && !poses_wc_out))
+      return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument", who);
+    if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the whole-map solve is not partitioned: no all-reduce hook or communicator", who);
+    WinPlan P;
+    if (int rc = glb_plan(h, who, mp, n_kfs, kfs, P)) return rc;
+    // the solver's own refusal, made before the collection is enqueued
+    if (n_kfs - 1 > gba_max_keyframes()) return orbx_fail(h, ORBX_ERR_INVALID, "%s: at most %d optimised keyframes per call (n_kfs - 1 = %d)", who, gba_max_keyframes(), n_kfs - 1);
+    return win_global_ba(h, who, cam, cfg, mp, kfs, P, should_stop, user, poses_wc_out, counts_out, iterations, initial_error, final_error);
   });
 }
 

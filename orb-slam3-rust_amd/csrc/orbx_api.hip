@@ -236,6 +236,7 @@ void orbx_destroy(orbx_handle* h) {
   for (DevBuf& b : h->ws_lv) if (b.p) hipFree(b.p);
   for (DevBuf& b : h->ws_mp) if (b.p) hipFree(b.p);
   h->ws_map.for_each([](DevBuf& b) { if (b.p) hipFree(b.p); });
+  h->ws_gba.for_each([](DevBuf& b) { if (b.p) hipFree(b.p); });
   for (auto& set : h->ws_pipe) for (DevBuf& b : set) if (b.p) hipFree(b.p);
   for (int i = 0; i < 2; ++i) { if (h->ev_in[i]) hipEventDestroy(h->ev_in[i]); if (h->ev_comp[i]) hipEventDestroy(h->ev_comp[i]); if (h->ev_out[i]) hipEventDestroy(h->ev_out[i]); }
   if (h->ba_up_event) hipEventDestroy(h->ba_up_event);
@@ -244,7 +245,7 @@ void orbx_destroy(orbx_handle* h) {
   for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
   if (h->pair_graph) hipGraphExecDestroy(h->pair_graph);
   orbx_rccl_drop(h);
-  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp, &h->pin_map, &h->pin_io};
+  PinnedBuf* pins[] = {&h->pin_stage, &h->pin_ba_in, &h->pin_ba_out, &h->pin_pnp, &h->pin_pi, &h->pin_track, &h->pin_tref, &h->pin_lv, &h->pin_mp, &h->pin_map, &h->pin_io, &h->pin_gba};
   UploadRing* rings[] = {&h->ring_track, &h->ring_tref, &h->ring_lv, &h->ring_mp, &h->ring_map, &h->ring_io};
   for (PinnedBuf* b : pins) if (b->p) hipHostFree(b->p);
   for (UploadRing* r : rings) {
@@ -1234,3 +1235,49 @@ int orbx_ba_solve_global_obs32(orbx_handle* h, const orbx_camera* cam, const orb
 }
 
 }  // extern "C"
+
+// The whole-map forms of orbx_ba_solve_global (global_ba_kernels.hip): the same semantics, always on the path that holds more than 128
+// optimised keyframes.
+static int ba_solve_global_map(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
+                               const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs* obs, const orbx_ba_obs32* obs32,
+                               bool on_device, orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations,
+                               double* initial_error, double* final_error) {
+  if (!h) return ORBX_ERR_INVALID;
+  if (!cam || !cfg || K < 0 || M < 0 || N < 0 || !iterations || !initial_error || !final_error || !fixed_pose_cw ||
+      (K > 0 && (!poses_cw || !poses_wc_out)) || (M > 0 && !points) || (N > 0 && !obs && !obs32) || (on_device && ((uintptr_t)obs32 & 15)))
+    return orbx_fail(h, ORBX_ERR_INVALID, "%s: bad argument%s", who, on_device ? " (d_obs32 is 16-byte aligned)" : "");
+  if (h->allreduce || h->rccl_comm) return orbx_fail(h, ORBX_ERR_INVALID, "%s: the whole-map solve is not partitioned: no all-reduce hook or communicator", who);
+  *iterations = 0; *initial_error = 0.0; *final_error = 0.0;
+  if (K < 1 || M == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "global BA needs two keyframes and a map point");   // global_ba.rs:194-196
+  if (N == 0) return orbx_fail(h, ORBX_ERR_EMPTY, "no parameters or no residuals");
+  ORBX_HIP(h, hipSetDevice(h->device));
+  return orbx_guard(h, who, [&]() -> int {
+    return gba_solve(h, who, cam, cfg, K, poses_cw, fixed_pose_cw, M, points, N, obs, obs32, on_device, should_stop, user, poses_wc_out, iterations, initial_error, final_error);
+  });
+}
+
+int orbx_ba_solve_global_map(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
+                             const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs* obs,
+                             orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations,
+                             double* initial_error, double* final_error) {
+  return ba_solve_global_map(h, "orbx_ba_solve_global_map", cam, cfg, K, poses_cw, fixed_pose_cw, M, points, N, obs, nullptr, false, should_stop, user,
+                             poses_wc_out, iterations, initial_error, final_error);
+}
+
+int orbx_ba_solve_global_map_obs32(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
+                                   const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs32* obs32,
+                                   orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations,
+                                   double* initial_error, double* final_error) {
+  return ba_solve_global_map(h, "orbx_ba_solve_global_map_obs32", cam, cfg, K, poses_cw, fixed_pose_cw, M, points, N, nullptr, obs32, false, should_stop, user,
+                             poses_wc_out, iterations, initial_error, final_error);
+}
+
+int orbx_ba_solve_global_map_obs32_device(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
+                                          const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs32* d_obs32,
+                                          orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations,
+                                          double* initial_error, double* final_error) {
+  return ba_solve_global_map(h, "orbx_ba_solve_global_map_obs32_device", cam, cfg, K, poses_cw, fixed_pose_cw, M, points, N, nullptr, d_obs32, true, should_stop, user,
+                             poses_wc_out, iterations, initial_error, final_error);
+}
+
+int orbx_ba_global_map_max_keyframes(void) { return gba_max_keyframes(); }

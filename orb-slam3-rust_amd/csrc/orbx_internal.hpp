@@ -236,6 +236,18 @@ struct IoWorkspaces {
 };
 static_assert(sizeof(IoWorkspaces) == 7 * sizeof(DevBuf), "IoWorkspaces::for_each lists every member");
 
+// The grow-only workspaces of the whole-map global BA (global_ba_kernels.hip), one per role; nothing is sized by the keyframe cap.
+struct GlobalBaWorkspaces {
+  DevBuf blobs;           // the call's input blob (state, fixed poses, parameters, host observations) and output blob (result record, parameters)
+  DevBuf arena;           // lists, per-observation and per-point build results, trial parameters, the factored diagonal blocks
+  DevBuf system;          // the reduced system S [6K + 1][6K rounded up to 64]: lower triangle, the right-hand side as the last row
+  template <class F>
+  void for_each(F&& f) {   // every member, so that orbx_destroy frees what is added here
+    for (DevBuf* b : {&blobs, &arena, &system}) f(*b);
+  }
+};
+static_assert(sizeof(GlobalBaWorkspaces) == 3 * sizeof(DevBuf), "GlobalBaWorkspaces::for_each lists every member");
+
 struct KernelTimer {
   std::string name;
   std::vector<hipEvent_t> ev;  // start/stop pairs of the current call
@@ -297,6 +309,8 @@ struct orbx_handle {
   MapWorkspaces ws_map;                  // resident map points (map_store_kernels.hip)
   PinnedBuf pin_map;                     // pinned staging of the resident map's host forms and orbx_map_points_download
   UploadRing ring_map;                   // every resident-map call's tables on their way to its *_tables workspace
+  GlobalBaWorkspaces ws_gba;             // whole-map global BA (global_ba_kernels.hip)
+  PinnedBuf pin_gba;                     // pinned staging of its one upload and one download
   // pipelined host-batch path: copy streams, events, double-buffered staging
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -693,6 +707,13 @@ int ba_solve_visual(orbx_handle* h, const orbx_camera* cam, const orbx_ba_config
                     double* final_error, bool global_mode = false, const struct BaInertialHost* inr = nullptr,
                     const orbx_ba_obs32* obs32 = nullptr,    // obs32: the 16-byte form of the observations, used instead of obs when given
                     bool obs_on_device = false);             // ... and it lies in device memory of the handle's device, ordered on its stream
+// whole-map global BA (global_ba_kernels.hip): orbx_ba_solve_global's semantics for up to gba_max_keyframes() optimised keyframes.  obs or
+// obs32 is given; on_device: obs32 is device memory ordered on the handle's stream.  The caller has checked the pointers, K, M, N >= 1
+// and that no collective is installed.
+int gba_max_keyframes();
+int gba_solve(orbx_handle* h, const char* who, const orbx_camera* cam, const orbx_ba_config* cfg, int K, const double* poses_cw,
+              const double* fixed_pose_cw, int M, double* points, int N, const orbx_ba_obs* obs, const orbx_ba_obs32* obs32, bool on_device,
+              orbx_should_stop_fn should_stop, void* user, double* poses_wc_out, int* iterations, double* initial_error, double* final_error);
 // one window of a batch as the caller hands it over (orbx_ba_solve_visual_batch); status: ORBX_OK or ORBX_ERR_EMPTY
 struct BaWinHost {
   int K, F, M, N;
