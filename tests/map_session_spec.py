@@ -118,14 +118,14 @@ class Model:
                 nb.append(k)
         return dict(weights=w, best=b, n_best=n, neighbours=nb)
 
-    def create(self, cur, nb):
+    def create(self, cur, nb, is_inertial=0):
         n_free = min(len(self.free), W.MAX_FREE)
         free_slots = np.array([self.free.pop() for _ in range(n_free)], np.int32)
         T = self.T()
         order = [cur] + list(nb)
-        spec = MC.create_points(self.oracle, W.CAMERA, XS.default_config(), 0, self._keyframe(self.listed[cur]), [self._keyframe(self.listed[i]) for i in nb],
+        spec = MC.create_points(self.oracle, W.CAMERA, XS.default_config(), is_inertial, self._keyframe(self.listed[cur]), [self._keyframe(self.listed[i]) for i in nb],
                                 [T[i] for i in order], self.live, free_slots)
-        spec.update(free_slots=free_slots, order=order, tables_before=[T[i] for i in order], near=sum(1 for e in spec["evaluated"] if e[6] <= NEAR))
+        spec.update(free_slots=free_slots, order=order, is_inertial=is_inertial, tables_before=[T[i] for i in order], near=sum(1 for e in spec["evaluated"] if e[6] <= NEAR))
         return spec
 
     def take_created(self, spec, got):

@@ -140,7 +140,7 @@ class _HostForms:
     def create(self, m, want):
         d, order = self.d, want["order"]
         kfs = self._kfs(m)
-        r = d.h.map_create_points(d.cam, d.mp, kfs[order[0]], [kfs[i] for i in order[1:]], want["free_slots"])
+        r = d.h.map_create_points(d.cam, d.mp, kfs[order[0]], [kfs[i] for i in order[1:]], want["free_slots"], is_inertial=want["is_inertial"])
         near = {(e[0], e[1], e[2]) for e in want["evaluated"] if e[6] <= MARGIN}
         key = lambda x: [(int(t), int(a), int(b)) for t, a, b in zip(x["new_neighbour"], x["new_idx1"], x["new_idx2"])]
         got, exp = key(r), key(want)
