@@ -1552,6 +1552,74 @@ int orbx_map_remove_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const
 int orbx_map_cull_points(orbx_handle* h, orbx_map_points* mp, int n_kfs, const orbx_keyframe* const* kfs, int M, const int* cand,
                          int min_observations, int* n_culled, int* culled);
 
+/* ---- loop correction on the resident map: rigid correction and fuse (corrector.rs:383-619; loop_closer.rs:155-241, step 5) ------
+ * correct_loop — collect_correction_data, compute_correction, apply_correction, fuse_map_points — where the slot tables, the store
+ * and the poses lie.  The reference walks host hash maps in their iteration order and merges with counts that change as it goes; the
+ * library fixes a derived, deterministic definition.  kfs [n_kfs], parent [n_kfs] and sim3 [8] are host arrays (copied before the
+ * call returns); every keyframe index is a position in kfs[].  parent[k] is keyframe k's spanning-tree parent or -1; sim3 is
+ * sim3_current_to_loop as orbx_keyframe_verify_loop_candidates writes it (qw, qx, qy, qz, tx, ty, tz, scale), feature_matches that
+ * call's [n_matches][2] (current feature, loop feature).  All reads are of the state at entry; obs(k), n_observers(s), "live" and
+ * weight are those of the covisibility and observations blocks, over kfs[].
+ *   [spec] affected keyframes A (:433-465): arcs k -> c for parent[c] == k (a parent is not reached from its child) and k <-> j for
+ *     weight(k, j) >= min_covisibility_weight; A = the keyframes at most max_propagation_depth arcs from cur.  The reference's FIFO
+ *     walk gives this set whatever order it visits neighbours in.  (With min_covisibility_weight = 0 every pair is an arc; the
+ *     reference walks the keyframes it has weights for.)  affected[k] = 1 for k in A, else 0.
+ *   [spec] affected points (:467-480): the distinct live slots of the tables of A's keyframes, keyframes by ascending position and
+ *     features in index order — what ORBX_MAP_SOURCE_KEYFRAMES gives one frame — in list_slot; counts[1] of them.
+ *   [spec] correction (:493-515, sim3.rs:144-170): C = sim3^-1: q_c = the conjugate of sim3's quaternion, s_c = 1 / scale,
+ *     t_c = -(R_c t) * s_c.  Every affected point's position in the store becomes s_c * (R_c p) + t_c, once, however many keyframes
+ *     and features name it.  Every affected keyframe's pose becomes rotation q_c * q, translation s_c * (R_c t_wc) + t_c, the scale
+ *     dropped (to_se3); the quaternion product is not renormalised and its sign is left as it falls.  poses_wc[k] is that pose for
+ *     k in A and the pose as found otherwise.  Bytes of unaffected slots do not change.
+ *   [spec] pairs (:168-173): match (fc, fl) gives (a, b) = (table(cur)[fc], table(loop)[fl]); it counts iff both are in range and live
+ *     and a != b.  counts[2] = their number.
+ *   [spec] fuse (:572-619), order-free like the fuse block: classes are the connected components over the pairs; the keeper of a
+ *     class is the member with the largest n_observers at entry, ties to the member that occurs first in the flattened pair list
+ *     a0, b0, a1, b1, ... (a two-member tie keeps the current keyframe's point, as :589 does); every other member is a GONER.  In
+ *     every table of kfs[] an entry that names a goner becomes its keeper; nothing else changes; d_mp_uniq of the changed keyframes
+ *     is made again.  goner[] / keeper[] by ascending goner slot; counts[4] = {|A|, affected points, pairs, goners}.
+ * Deviations from the sequential reference: counts are those at entry (the reference's grow as it merges); a goner named at two
+ * features of one keyframe is replaced at both (the reference's observations map holds one feature per keyframe); a keyframe that
+ * already names the keeper may afterwards name it at two features, as in the reference — every reader of the tables counts such a
+ * slot once.  Where no slot occurs in two distinct pairs the result equals the reference replayed in list order.  Keepers' positions
+ * are the corrected ones; descriptors, d_mp_flag and mp_ids are untouched.  The pose graph stays out: the reference never solves it.
+ *
+ * orbx_map_correct_loop_device: asynchronous on the handle's stream, no host synchronisation inside; the N x N weights are counted
+ * by the covisibility kernels with every keyframe as a query and never leave the device (int32, at most 64 MB at
+ * orbx_map_loop_max_keyframes() = 4096 keyframes); the store's mark / index tables are left as found, no launch is sized by the
+ * capacity and the outputs are the same bytes on every run.  d_feature_matches [n_matches][2] is device memory; a match outside its
+ * keyframe's features is no pair.  Outputs, device memory: d_counts [4], d_affected [n_kfs] bytes, d_poses_wc [n_kfs][7],
+ * d_list_slot [list_cap], list_cap >= min(the features of kfs[] summed, capacity); d_goner / d_keeper [n_matches] (goners <= pairs).
+ * The keyframes' own pose_wc and the store's live bytes are left alone: the caller applies poses_wc and erases the goners.
+ * orbx_map_correct_loop: the same with host arrays, synchronous: ONE download of the counts, affected bytes, poses, list and goner
+ * lists; the poses of A applied as orbx_keyframe_set_pose does; the goners erased as orbx_map_points_erase does.
+ * orbx_map_close_loop = orbx_map_correct_loop, then, if ba_cfg is given, orbx_map_global_ba on the same kfs[] by its own rules
+ * (kfs[0] the anchor, the list in ascending id; its return value is the call's); poses_wc_out goes to the caller unapplied, as that
+ * call leaves it.
+ * ORBX_ERR_INVALID before anything is enqueued, store, tables and poses untouched: cur or a parent entry outside its range,
+ * parent[k] == k, loop outside [0, n_kfs) ([spec] -1 is accepted where n_matches == 0: no loop keyframe is read), cur == loop,
+ * n_kfs > orbx_map_loop_max_keyframes(), a keyframe listed twice, a keyframe of another handle or store, cur or loop without a table
+ * while n_matches > 0, a match index outside its keyframe (host form), a sim3 entry that is not finite or a scale <= 0, a negative
+ * configuration value, list_cap below its bound, n_matches < 0.  n_kfs = 0: ORBX_OK and nothing is done.
+ * Still the caller's: ids and the id -> slot map (goner / keeper say what to retire), the spanning tree, the loop edge. */
+typedef struct {
+  int min_covisibility_weight, max_propagation_depth;   /* 15, 100: corrector.rs:97-104 */
+} orbx_loop_correct_config;
+void orbx_default_loop_correct_config(orbx_loop_correct_config* cfg);
+int orbx_map_loop_max_keyframes(void);                  /* 4096 */
+int orbx_map_correct_loop_device(orbx_handle* h, const orbx_loop_correct_config* cfg, orbx_map_points* mp, int n_kfs,
+                                 orbx_keyframe* const* kfs, const int* parent, int cur, int loop, const double* sim3, int n_matches,
+                                 const int* d_feature_matches, int list_cap, int* d_counts, uint8_t* d_affected, double* d_poses_wc,
+                                 int* d_list_slot, int* d_goner, int* d_keeper);
+int orbx_map_correct_loop(orbx_handle* h, const orbx_loop_correct_config* cfg, orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs,
+                          const int* parent, int cur, int loop, const double* sim3, int n_matches, const int* feature_matches,
+                          int list_cap, int* counts, uint8_t* affected, double* poses_wc, int* list_slot, int* goner, int* keeper);
+int orbx_map_close_loop(orbx_handle* h, const orbx_camera* cam, const orbx_loop_correct_config* correct_cfg, const orbx_ba_config* ba_cfg,
+                        orbx_map_points* mp, int n_kfs, orbx_keyframe* const* kfs, const int* parent, int cur, int loop,
+                        const double* sim3, int n_matches, const int* feature_matches, int list_cap, int* counts, uint8_t* affected,
+                        double* poses_wc, int* list_slot, int* goner, int* keeper, orbx_should_stop_fn should_stop, void* user,
+                        double* poses_wc_out, int* ba_counts, int* iterations, double* initial_error, double* final_error);
+
 /* ---- keyframe BoW database and loop-candidate search (src/atlas/keyframe_db.rs, src/loop_closing/detector.rs) ------
  * Replaces KeyFrameDatabase (keyframe_db.rs:36-95: add / erase / detect_candidates, the relocalisation query over all maps) and
  * detect_loop_candidates (detector.rs:185-368, called for every keyframe by LoopCloser::process_keyframe, loop_closer.rs:155-170).

@@ -22,5 +22,5 @@ from .api import (  # noqa: F401
     track_with_reference_kf, Sim3SolverConfig, Sim3Result, LoopVerifyConfig, VerifiedLoop, SIM3_RESULT, LOOP_VERIFY_RESULT, SIM3_OK, SIM3_NO_MODEL,
     LOOP_OK, LOOP_TOO_FEW_POINTS, LOOP_TOO_FEW_MATCHES, LOOP_TOO_FEW_PAIRS, LOOP_NO_MODEL, LOOP_TOO_FEW_INLIERS, LOOP_TOO_FEW_VERIFIED,
     LOOP_VERIFY_MAX_FEAT, MP_REFRESH_RECORD, MapPointRefresh, MapPointRefreshData, compute_sim3_ransac, compute_sim3_from_matches, verify_loop_candidate,
-    MapPointStore, MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS, MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS, covisibility_lists, MapLocalBAResult)
+    MapPointStore, MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS, MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS, covisibility_lists, MapLocalBAResult, LoopCorrectConfig)
 from .build import LIB_PATH, build  # noqa: F401

@@ -119,6 +119,7 @@ ABI_SYMBOLS = [
     "orbx_map_collect_inertial_window", "orbx_map_local_inertial_ba",
     "orbx_ba_solve_global_map", "orbx_ba_solve_global_map_obs32", "orbx_ba_solve_global_map_obs32_device", "orbx_ba_global_map_max_keyframes",
     "orbx_map_collect_global_device", "orbx_map_collect_global", "orbx_map_global_ba",
+    "orbx_default_loop_correct_config", "orbx_map_loop_max_keyframes", "orbx_map_correct_loop_device", "orbx_map_correct_loop", "orbx_map_close_loop",
 ]
 MAP_SOURCE_KEYFRAMES, MAP_SOURCE_SLOTS = 0, 1      # orbx_map_select_points_device's source kinds
 MAP_CREATE_STEREO, MAP_CREATE_NEIGHBOURS = 1, 2    # orbx_map_create_points' phases (a bit mask)
@@ -155,6 +156,10 @@ class _BaConfig(C.Structure):
     _fields_ = [("max_iterations", C.c_int), ("param_tolerance", C.c_double),
                 ("gradient_tolerance", C.c_double), ("huber_threshold", C.c_double),
                 ("max_covisible_keyframes", C.c_int)]
+
+
+class _LoopCorrectConfig(C.Structure):
+    _fields_ = [("min_covisibility_weight", C.c_int), ("max_propagation_depth", C.c_int)]
 
 
 class _InertialBaConfig(C.Structure):
@@ -405,6 +410,16 @@ class GlobalBAConfig:
 
     def _c(self):
         return _BaConfig(self.max_iterations, self.param_tolerance, self.gradient_tolerance, self.huber_threshold, 0)
+
+
+@dataclass
+class LoopCorrectConfig:
+    """corrector.rs:97-104 (CorrectorConfig::default)"""
+    min_covisibility_weight: int = 15
+    max_propagation_depth: int = 100
+
+    def _c(self):
+        return _LoopCorrectConfig(self.min_covisibility_weight, self.max_propagation_depth)
 
 
 @dataclass
@@ -1688,6 +1703,99 @@ class Handle:
         refresh = MapPointRefresh(out.mp_desc[:M].copy(), out.normals[:M].copy(), out.min_distance[:M].copy(), out.max_distance[:M].copy(), out.records[:M].copy())
         return dict(counts=counts.reshape(2, 4), goner_a=g[0][:Ga].copy(), keeper_a=g[1][:Ga].copy(), goner_b=g[2][:Gb].copy(), keeper_b=g[3][:Gb].copy(),
                     affected=aff[:M].copy(), refresh=refresh)
+
+    # ---- loop correction on the resident map (include/orbx.h, "loop correction on the resident map") ----
+    @staticmethod
+    def _loop_args(mp, keyframes, parent, sim3, feature_matches):
+        """(parent, sim3, matches, n_matches, list_cap) of a loop-correction call as contiguous host arrays; list_cap is the list's
+        bound: the keyframes' features summed, at most the capacity"""
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        if len(par) != len(keyframes):
+            raise ValueError("loop correction: parent holds one entry per keyframe")
+        s3 = np.ascontiguousarray(sim3, np.float64).reshape(8)
+        fm = np.ascontiguousarray(feature_matches if feature_matches is not None else np.zeros((0, 2)), np.int32).reshape(-1, 2)
+        return par, s3, fm, len(fm), min(int(sum(k.n for k in keyframes)), mp.capacity)
+
+    def map_correct_loop_device(self, mp: "MapPointStore", keyframes, parent, cur, loop, sim3, feature_matches=None, cfg: "LoopCorrectConfig" = None,
+                                device=None):
+        """correct_loop on the resident map (orbx_map_correct_loop_device): the keyframes within reach of keyframes[cur] (spanning-tree
+        children through `parent`, covisibility arcs), their points and poses corrected by the inverse of sim3 (qw,qx,qy,qz,tx,ty,tz,
+        scale: verify_loop_candidates' sim3), and the matched points of cur and loop fused in every table.  feature_matches [n,2]
+        (current feature, loop feature): a CUDA int32 tensor or a host array.  Returns a dict of CUDA tensors: counts [4] int32 =
+        (affected keyframes, affected points, pairs, goners), affected [n_kfs] u8, poses_wc [n_kfs,7] f64, list_slot [cap] int32, goner /
+        keeper [n_matches] int32.  The keyframes' own poses and the store's live bytes are untouched: applying the poses and erasing
+        the goners is the caller's (map_correct_loop does both).  Asynchronous on the handle's stream."""
+        import torch
+        dev = device or torch.device("cuda", self.device)
+        if getattr(feature_matches, "is_cuda", False):
+            d_fm = feature_matches.to(torch.int32).contiguous().reshape(-1, 2)
+            par, s3, _, M, cap = self._loop_args(mp, keyframes, parent, sim3, None)
+            M = int(d_fm.shape[0])
+        else:
+            par, s3, fm, M, cap = self._loop_args(mp, keyframes, parent, sim3, feature_matches)
+            d_fm = torch.from_numpy(fm if M else np.zeros((1, 2), np.int32)).to(dev)
+        K = len(keyframes)
+        mk = lambda shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
+        o = dict(counts=mk(4), affected=mk(max(K, 1), torch.uint8), poses_wc=mk((max(K, 1), 7), torch.float64), list_slot=mk(max(cap, 1)),
+                 goner=mk(max(M, 1)), keeper=mk(max(M, 1)))
+        c = (cfg or LoopCorrectConfig())._c()
+        self._after_torch(d_fm, *o.values())
+        self._check(self._L.orbx_map_correct_loop_device(self._h, C.byref(c), mp._p, C.c_int(K), self._kf_array(keyframes), _vp(par if K else np.zeros(1, np.int32)),
+                                                         C.c_int(int(cur)), C.c_int(int(loop)), _vp(s3), C.c_int(M), _vp(d_fm), C.c_int(cap), _vp(o["counts"]),
+                                                         _vp(o["affected"]), _vp(o["poses_wc"]), _vp(o["list_slot"]), _vp(o["goner"]), _vp(o["keeper"])))
+        o["affected"] = o["affected"][:K]; o["poses_wc"] = o["poses_wc"][:K]; o["list_slot"] = o["list_slot"][:cap]; o["goner"] = o["goner"][:M]; o["keeper"] = o["keeper"][:M]
+        return o
+
+    def _loop_host_outputs(self, K, M, cap):
+        return dict(counts=np.zeros(4, np.int32), affected=np.zeros(max(K, 1), np.uint8), poses_wc=np.zeros((max(K, 1), 7)), list_slot=np.zeros(max(cap, 1), np.int32),
+                    goner=np.zeros(max(M, 1), np.int32), keeper=np.zeros(max(M, 1), np.int32))
+
+    @staticmethod
+    def _loop_cut(o, K):
+        P, G = int(o["counts"][1]), int(o["counts"][3])
+        return dict(counts=o["counts"], affected=o["affected"][:K].copy(), poses_wc=o["poses_wc"][:K].copy(), list_slot=o["list_slot"][:P].copy(),
+                    goner=o["goner"][:G].copy(), keeper=o["keeper"][:G].copy())
+
+    def map_correct_loop(self, mp: "MapPointStore", keyframes, parent, cur, loop, sim3, feature_matches=None, cfg: "LoopCorrectConfig" = None):
+        """The host form (orbx_map_correct_loop), synchronous: a dict of numpy arrays cut to their sizes — counts [4], affected [n_kfs],
+        poses_wc [n_kfs,7], list_slot [affected points], goner / keeper [goners] — with the corrected poses applied to the affected
+        keyframes and the goners erased from the store."""
+        par, s3, fm, M, cap = self._loop_args(mp, keyframes, parent, sim3, feature_matches)
+        K = len(keyframes)
+        o = self._loop_host_outputs(K, M, cap)
+        c = (cfg or LoopCorrectConfig())._c()
+        self._after_torch()
+        self._check(self._L.orbx_map_correct_loop(self._h, C.byref(c), mp._p, C.c_int(K), self._kf_array(keyframes), _vp(par if K else np.zeros(1, np.int32)),
+                                                  C.c_int(int(cur)), C.c_int(int(loop)), _vp(s3), C.c_int(M), _vp(fm if M else np.zeros((1, 2), np.int32)), C.c_int(cap),
+                                                  _vp(o["counts"]), _vp(o["affected"]), _vp(o["poses_wc"]), _vp(o["list_slot"]), _vp(o["goner"]), _vp(o["keeper"])))
+        return self._loop_cut(o, K)
+
+    def map_close_loop(self, camera, mp: "MapPointStore", keyframes, parent, cur, loop, sim3, feature_matches=None, cfg: "LoopCorrectConfig" = None,
+                       ba_cfg: "GlobalBAConfig" = None, global_ba=True, should_stop=None):
+        """Step 5 of LoopCloser::process_keyframe and the global BA behind it (orbx_map_close_loop): map_correct_loop, then, unless
+        global_ba is False, map_global_ba on the same keyframes (keyframes[0] the anchor).  Returns map_correct_loop's dict with
+        global_ba = map_global_ba's dict (None where that call returns None or was not asked for): its poses are not applied."""
+        par, s3, fm, M, cap = self._loop_args(mp, keyframes, parent, sim3, feature_matches)
+        K = len(keyframes)
+        o = self._loop_host_outputs(K, M, cap)
+        c = (cfg or LoopCorrectConfig())._c()
+        bc = (ba_cfg or GlobalBAConfig())._c()
+        out_p = np.zeros((max(K - 1, 1), 7)); ba_counts = np.zeros(4, np.int32)
+        it, e0, e1 = _solve_outs()
+        cb = _stop_callback(should_stop)
+        cam = camera._c()
+        self._after_torch()
+        rc = self._L.orbx_map_close_loop(self._h, C.byref(cam), C.byref(c), C.byref(bc) if global_ba else None, mp._p, C.c_int(K), self._kf_array(keyframes),
+                                         _vp(par if K else np.zeros(1, np.int32)), C.c_int(int(cur)), C.c_int(int(loop)), _vp(s3), C.c_int(M),
+                                         _vp(fm if M else np.zeros((1, 2), np.int32)), C.c_int(cap), _vp(o["counts"]), _vp(o["affected"]), _vp(o["poses_wc"]),
+                                         _vp(o["list_slot"]), _vp(o["goner"]), _vp(o["keeper"]), cb, None, _vp(out_p), _vp(ba_counts), C.byref(it), C.byref(e0), C.byref(e1))
+        if rc != ORBX_ERR_EMPTY:
+            self._check(rc)
+        res = self._loop_cut(o, K)
+        res["global_ba"] = None
+        if global_ba and rc == 0:
+            res["global_ba"] = dict(poses_wc=out_p[:max(K - 1, 0)], counts=ba_counts, iterations=it.value, initial_error=e0.value, final_error=e1.value)
+        return res
 
     # ---- create and cull map points on the resident map (include/orbx.h, "create and cull map points on the resident map") ----
     def map_create_points_device(self, camera, mp: "MapPointStore", cur: "KeyFrame", neighbours, free_slots, phases=MAP_CREATE_STEREO | MAP_CREATE_NEIGHBOURS,

@@ -72,20 +72,6 @@
 #include "orbx_internal.hpp"
 #include "pose_dev.hpp"
 
-struct orbx_map_points {
-  orbx_handle* h = nullptr;
-  int capacity = 0, n_live = 0;
-  uint8_t* block = nullptr;            // one device allocation: positions | descriptors | live
-  double* d_pos = nullptr;
-  uint8_t* d_desc = nullptr;
-  uint8_t* d_live = nullptr;
-  std::vector<uint8_t> live;           // host mirror of d_live: every change goes through set / set_device / erase, whose slots are host arrays
-  std::vector<unsigned> stamp;         // per slot the last call that named it (a slot listed twice in one call is refused)
-  unsigned gen = 0;
-  DevBuf first;                        // [frames][capacity] first-sighting tables, EMPTY between calls
-  DevBuf mark;                         // [queries][capacity] bytes: covisibility's marked sets, 0 between calls (never shared with `first`)
-};
-
 namespace {
 
 constexpr int MS_THREADS = 256;

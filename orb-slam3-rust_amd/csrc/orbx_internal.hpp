@@ -209,14 +209,16 @@ struct MapWorkspaces {
   DevBuf create_tables;   // point creation: the call's tables (keyframes, free slots, the neighbour loop's)
   DevBuf create_scratch;  // point creation: flags, last-writer cells and the neighbour loop's scratch and lists
   DevBuf remove_tables;   // point removal: the call's keyframe table and slots, the counter
+  DevBuf loop_scratch;    // loop correction (loop_close_kernels.hip): the N x N weights, candidates and chunk counts, pairs, per-node scratch
+  DevBuf loop_tables;     // loop correction: the call's keyframe table, parents and poses
   template <class F>
   void for_each(F&& f) {   // every member, so that orbx_destroy frees what is added here
     for (DevBuf* b : {&sel_scratch, &host_blobs, &call_tables, &ref_items, &cov_scratch, &cov_tables, &win_scratch, &win_tables, &obs_scratch, &obs_tables,
-                      &refresh_lists, &fuse_scratch, &fuse_tables, &create_tables, &create_scratch, &remove_tables})
+                      &refresh_lists, &fuse_scratch, &fuse_tables, &create_tables, &create_scratch, &remove_tables, &loop_scratch, &loop_tables})
       f(*b);
   }
 };
-static_assert(sizeof(MapWorkspaces) == 16 * sizeof(DevBuf), "MapWorkspaces::for_each lists every member");
+static_assert(sizeof(MapWorkspaces) == 18 * sizeof(DevBuf), "MapWorkspaces::for_each lists every member");
 
 // The grow-only workspaces of the single-problem matchers and searches (orbx_api.hip, keyframe.hip, bow_kernels.hip,
 // triangulate_kernels.hip), one per role.  A host form holds host_blob from its upload to its download; whatever it calls in between
@@ -358,6 +360,21 @@ struct orbx_keyframe {
   std::vector<uint32_t> node;
   std::vector<int> node_sorted;
   int node_m = 0;
+};
+
+// Map points resident on the device (map_store_kernels.hip; the loop closer acts on the same store: loop_close_kernels.hip).
+struct orbx_map_points {
+  orbx_handle* h = nullptr;
+  int capacity = 0, n_live = 0;
+  uint8_t* block = nullptr;            // one device allocation: positions | descriptors | live
+  double* d_pos = nullptr;
+  uint8_t* d_desc = nullptr;
+  uint8_t* d_live = nullptr;
+  std::vector<uint8_t> live;           // host mirror of d_live: every change goes through set / set_device / erase, whose slots are host arrays
+  std::vector<unsigned> stamp;         // per slot the last call that named it (a slot listed twice in one call is refused)
+  unsigned gen = 0;
+  DevBuf first;                        // [frames][capacity] first-sighting tables, EMPTY between calls
+  DevBuf mark;                         // [queries][capacity] bytes: covisibility's marked sets, 0 between calls (never shared with `first`)
 };
 
 int orbx_fail(orbx_handle* h, int code, const char* fmt, ...);
